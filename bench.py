@@ -16,17 +16,19 @@ reference's own N=1 answers); after the timed region the LAST replayed Result of
 rows 0-7 against the fixture (1e-4 in both norms), every request bit for bit against one eager synchronous infer() of the
 same tensor -- and the line says so (`parity_of_timed_path`).  A mismatch fails the run.
 
-The timed region is a block of exactly K steps between barrier + device synchronisation on both sides (max over
-ranks); the block is repeated until at least --min-seconds (1 s) have been timed and the MEDIAN block is reported
-(`steps` = K, `ms_per_step` = median block / K, `timed_blocks`, `timed_region_s`).  Every third block is instrumented (one of its
-steps runs alone with hipEvent brackets: the roofline measurement, inside the timed region); `ms_per_step_instrumented_blocks`
-reports those blocks' own median.
+The timed region is exactly K steps between barrier + device synchronisation on both sides (max over ranks): `steps` = K,
+`ms_per_step` = timed region / K.  In front of it, untimed, one instrumented block of K steps (one step in SAMPLE_EVERY runs alone
+with hipEvent brackets: the roofline measurement; --no-node-timing skips it); `ms_per_step_instrumented_blocks` reports that block.
+
+--dump-outputs DIR writes what the last timed step returned -- every Result array of the gathered batch, as a caller of infer()
+receives it -- to DIR/<Result name>.npy (float32 / float64; above 64 MB in all, a fixed seeded sample of rows).  Inputs and weights
+are seeded, so two builds run with the same arguments can be compared output for output.
 
 Rank 0 prints ONE JSON line (contract in the task statement) carrying
   roofline      for the dominant kernels, the fp32-MFMA Convolution launches (Winograd forms, pointwise, implicit GEMM):
                 `achieved` / `frac` = the flops the matrix cores EXECUTE per launch (Winograd families: 16/36, 36/144, 36/100 of the
                 algorithmic count, padded patches included) / the launches' device time, measured with hipEvents on the compute
-                stream inside the timed blocks, against the 157.3 TFLOP/s fp32 MFMA peak; `achieved_algorithmic` /
+                stream in the instrumented block, against the 157.3 TFLOP/s fp32 MFMA peak; `achieved_algorithmic` /
                 `frac_algorithmic` = SURVEY 8(d)'s algorithmic flops (2*N*K*C*kh*kw*oh*ow) over the same time (how fast the layers
                 get done; may exceed 1); `per_kernel` = per kernel family with its own bound min(MFMA peak, arithmetic intensity x
                 HBM peak); `traffic` / `traffic_by_kernel` = HBM bytes per launch from the committed PMC passes;
@@ -59,7 +61,7 @@ BATCH_PER_GPU = 256
 WEIGHT_SEED = 1234
 PEAK_MFMA_F32_TFLOPS = 157.3   # MI355X_MICROARCH.md: fp32 MFMA dense peak (2.4 GHz)
 PEAK_HBM_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E spec peak
-SAMPLE_EVERY = 20              # every 20th step of a timed block (the first included) runs alone, with event brackets
+SAMPLE_EVERY = 20              # every 20th step of the instrumented block (the first included) runs alone, with event brackets
 KERNEL_NODES = {'Convolution', 'MatMul', 'MaxPool', 'AvgPool', 'Add', 'Multiply', 'ReLU', 'SoftMax', 'LRN',
                 'Concat', 'Transpose', 'GroupConvolution', 'Clamp', 'Sigmoid', 'DetectionOutput'}
 
@@ -111,6 +113,25 @@ def rows_vs_reference(gathered, golden_out, batch, world, n_gold, parity):
         parity['max_norm_error_vs_reference'] = max(parity['max_norm_error_vs_reference'] or 0.0, err)
         parity['worst_element_of_1e-4_allowance'] = max(parity['worst_element_of_1e-4_allowance'] or 0.0, excess)
     return parity
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(outputs, out_dir):
+    """{Result name: ndarray} -> out_dir/<name>.npy, float32 (float64 for what float32 would not hold exactly).  Above DUMP_BYTES in
+    all, every array keeps the same fixed, seeded sample of its rows."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {}
+    for name, value in outputs.items():
+        a = np.asarray(value)
+        arrays[name] = a.astype(np.float32 if a.dtype in (np.float16, np.float32) else np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in sorted(arrays.items()):
+        if total > DUMP_BYTES and a.ndim and len(a) > 1:
+            keep = max(1, int(len(a) * DUMP_BYTES // total))
+            a = a[np.sort(np.random.default_rng(0).choice(len(a), keep, replace=False))]
+        np.save(os.path.join(out_dir, ''.join(c if c.isalnum() or c in '-_.' else '_' for c in name) + '.npy'), a)
 
 
 def cpu_baseline(blob, n_images):
@@ -427,7 +448,7 @@ def main():
     ap.add_argument('--no-node-timing', action='store_true')
     ap.add_argument('--no-extra', action='store_true', help='skip extra_configs (mnist batch 64, SSD batch 128)')
     ap.add_argument('--fp16-passes', type=int, default=0, help='profiling hook: run ONLY this many eager passes of the FP16 entry (GoogLeNet as an FP16 IR, batch 256, one stream) and exit')
-    ap.add_argument('--min-seconds', type=float, default=1.0, help='repeat the block of --steps steps until this much has been timed')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write the Result arrays of the last timed step to DIR/<name>.npy')
     ap.add_argument('--streams', type=int, default=0, help='compute streams the scheduler forks branches onto (0 = engine default)')
     ap.add_argument('--requests', type=int, default=int(os.environ.get('PVHIP_BENCH_REQUESTS', '6')), help='(default also from PVHIP_BENCH_REQUESTS: a sweep hook for a driver that cannot pass flags) ''infer requests in flight per GPU (each a whole batch; 1 = synchronous infer(); at most 8).  Six: same box, alternating, '
                     '3 / 4 / 5 / 6 / 7 / 8 requests: 53.3 / 52.3 / 53.4 / 53.8 / 53.5 / 52.8 k images/s -- the persistent kernels of more requests take CUs from each other')
@@ -484,7 +505,7 @@ def main():
     # synthetic input of this rank's shard, resident in HBM before the timed region
     x_host = synth.uniform_pixels(1000 + rank, (args.batch, 3, 224, 224))
     # rows 0-7 of request 0: the eight images the REFERENCE answered at N=1 on these weights (tests/golden/googlenet_rows8.npz,
-    # recorded by tests/golden/make_golden.py from /root/reference): the timed path is checked against them below
+    # recorded by tests/golden/make_golden.py from the reference): the timed path is checked against them below
     golden = np.load(os.path.join(REPO, 'tests', 'golden', 'googlenet_rows8.npz'))
     assert int(golden['weight_seed']) == WEIGHT_SEED
     n_gold = min(len(golden['image_seeds']), args.batch)
@@ -496,6 +517,7 @@ def main():
     in_name, out_name = net.inputs[0]['name'], net.outputs[0]['name']
     dispatch_s = [0.0]       # host seconds spent dispatching asynchronous passes
     last_result = {}         # request index -> the Result its LAST pass of the timed region returned (gathered over the ranks)
+    last_step = {}           # every Result of the latest step that finished: {Result name: ndarray}, what infer() returns
 
     def pipelined(steps, first=0, on_sample=None):
         """`steps` forward passes with up to n_req whole-batch requests in flight (request i on its own streams and
@@ -503,7 +525,9 @@ def main():
         in_flight, out = [], None
 
         def finish(r):
-            last_result[r] = ex.wait(r)[out_name]
+            last_step.clear()
+            last_step.update(ex.wait(r))
+            last_result[r] = last_step[out_name]
             return last_result[r]
 
         for step in range(first, first + steps):
@@ -591,7 +615,7 @@ def main():
         out = ex.infer({in_name: x_dev})[out_name]
     assert out.shape == (args.batch * world, 1000) and np.isfinite(out).all()
 
-    # A hipEvent bracket costs ~10-15 us of stream time, so inside the timed region only the dominant kernels
+    # A hipEvent bracket costs ~10-15 us of stream time, so in the instrumented block only the dominant kernels
     # (the Convolution launches) are bracketed, one bracket per RUN of consecutive Convolution launches and only on every
     # 20th step, which runs alone and on one stream.
     conv_ms, conv_launches, conv_brackets, sampled_steps = 0.0, 0, 0, 0
@@ -614,7 +638,7 @@ def main():
     def timed_block(instrumented):
         """EXACTLY args.steps steps between barrier + device synchronisation on both sides; max over ranks.  In an instrumented
         block every SAMPLE_EVERY-th step (the first included) is taken out of the request pipeline and runs alone with hipEvent
-        brackets around its Convolution launches: that is where roofline.achieved is measured, inside the timed region."""
+        brackets around its Convolution launches: that is where roofline.achieved is measured."""
         nonlocal host_dispatch
         group.barrier()
         device.synchronize()
@@ -629,28 +653,24 @@ def main():
                 if instrumented and step % SAMPLE_EVERY == 0:
                     sampled_step()
                 else:
-                    ex.infer({in_name: x_dev})
+                    res = ex.infer({in_name: x_dev})
                     host_dispatch += sum(t[3] for t in ex.last_node_times if t[1] != 'Result')
+                    last_step.clear()
+                    last_step.update(res)
+                    last_result[0] = res[out_name]
         ev1 = device.Event().record()
         device.synchronize()
         group.barrier()
         elapsed = group.allreduce_max(time.perf_counter() - t0)
         return elapsed, ev0.elapsed_ms(ev1)
 
-    # Block 0, 3, 6, ... are instrumented (one step per 20 runs alone, draining the request pipeline: ~2 % of such a block is
-    # the measurement itself); the median over all blocks is what is reported, and the instrumented blocks' own median beside it.
-    blocks, instrumented_blocks = [], []
-    while True:
-        inst = (not args.no_node_timing) and len(blocks) % 3 == 0
-        blocks.append(timed_block(inst))
-        if inst:
-            instrumented_blocks.append(blocks[-1][0])
-        # every rank takes the same decision: the block times are already the max over ranks
-        if sum(b[0] for b in blocks) >= args.min_seconds or len(blocks) >= 200:
-            break
-    elapsed = statistics.median(b[0] for b in blocks)
-    dev_ms = statistics.median(b[1] for b in blocks)
-    n_blocks = len(blocks)
+    # The instrumented block first, untimed (one step per 20 runs alone, draining the request pipeline: ~2 % of such a block is the
+    # measurement itself); then the timed region, exactly args.steps steps with nothing bracketed.
+    instrumented_s = timed_block(True)[0] if not args.no_node_timing else None
+    host_dispatch = 0.0
+    last_result.clear()
+    elapsed, dev_ms = timed_block(False)
+    timed_step = dict(last_step)        # what the last timed step returned, before the parity passes below run
 
     # ---- parity of the path that was just timed (every rank takes part: a gathered Result is a collective) ----
     # The last Result every request returned inside the timed region -- replayed from its own hipGraph with the other requests in
@@ -658,8 +678,6 @@ def main():
     # tensor carries them at rank * batch), 1e-4 in both norms; (b) one eager, synchronous infer() of the same tensor, bit for bit.
     parity = {'checked_requests': 0, 'rows_vs_reference': 0, 'max_norm_error_vs_reference': None, 'worst_element_of_1e-4_allowance': None,
               'replayed_equals_eager_bits': None}
-    if n_req == 1:
-        last_result[0] = ex.infer({in_name: x_dev})[out_name]
     saved_env = os.environ.get('PVHIP_AUTO_GRAPH')
     os.environ['PVHIP_AUTO_GRAPH'] = '0'
     try:
@@ -684,6 +702,8 @@ def main():
     parity_ok = bool(parity['replayed_equals_eager_bits']) and (not parity['rows_vs_reference'] or (
         parity['max_norm_error_vs_reference'] <= 1e-4 and parity['worst_element_of_1e-4_allowance'] <= 1.0))
     parity['ok'] = parity_ok
+    if args.dump_outputs and rank == 0:
+        dump_outputs(timed_step, args.dump_outputs)
     if informational:
         sustained = mfma_ceiling(device)       # (diagnostic library: mapped only now, after the timed region)
 
@@ -706,12 +726,10 @@ def main():
                                                   'the host -- sweep with --requests N or PVHIP_BENCH_REQUESTS=N (1 .. 8)',
                        'request_dispatch': ('hipGraph replay: each request records its pass once, on its own stream and tensors, and replays it'
                                             if replayed_requests == n_req and n_req > 1 else 'eager (~100 plugin calls per pass)')},
-            'timed_blocks': n_blocks, 'timed_region_s': round(sum(b[0] for b in blocks), 3),
-            'block_ms_min_median_max': [round(1e3 * min(b[0] for b in blocks), 3), round(1e3 * elapsed, 3), round(1e3 * max(b[0] for b in blocks), 3)],
-            'instrumented_blocks': len(instrumented_blocks),
-            'ms_per_step_instrumented_blocks': (1e3 * statistics.median(instrumented_blocks) / args.steps) if instrumented_blocks else None,
+            'timed_region_s': round(elapsed, 3),
+            'ms_per_step_instrumented_blocks': (1e3 * instrumented_s / args.steps) if instrumented_s is not None else None,
             'device_ms_per_step': dev_ms / args.steps,
-            'host_dispatch_ms_per_step': 1000.0 * host_dispatch / (args.steps * n_blocks),
+            'host_dispatch_ms_per_step': 1000.0 * host_dispatch / args.steps,
             'parity_of_timed_path': parity,
         }
         if single_rate is not None:
@@ -796,10 +814,10 @@ def main():
             if conv:
                 assert conv_launches == conv['launches'] * sampled_steps, (conv_launches, conv['launches'], sampled_steps)
                 layer_pass_ms = conv['ms']
-                conv['ms'] = conv_ms / sampled_steps             # run brackets inside the timed blocks
+                conv['ms'] = conv_ms / sampled_steps             # run brackets inside the instrumented block
                 n_launch = conv['launches']
                 flops_per_launch = conv['flops'] / n_launch          # algorithmic: 2*N*K*C*kh*kw*oh*ow, averaged
-                avg_launch_ms = conv['ms'] / n_launch                # hipEvents on the compute stream, timed steps
+                avg_launch_ms = conv['ms'] / n_launch                # hipEvents on the compute stream, sampled steps
                 tf = flops_per_launch / (avg_launch_ms * 1e-3) / 1e12
                 tf_exec = conv['exec'] / (conv['ms'] * 1e-3) / 1e12
                 traffic, traffic_src, traffic_by_kernel = None, None, None
@@ -879,12 +897,12 @@ def main():
                         'avg_launch_us': avg_launch_ms * 1e3,
                         'algorithmic_bytes_per_launch': conv['bytes'] / n_launch,
                         'event_sampled_steps': sampled_steps,
-                        'measured_on': 'every {}th step of every third timed block (blocks 0, 3, 6, ...; the first step included), run alone on one stream (the other steps keep {} requests in flight: '
+                        'measured_on': 'every {}th step of the untimed instrumented block in front of the timed region (the first step included), run alone on one stream (the other steps keep {} requests in flight: '
                                        'kernels overlap and a launch has no duration of its own)'.format(SAMPLE_EVERY, n_req),
                         'event_brackets_per_step': conv_brackets // sampled_steps,
                         'per_kernel': per_kernel,
                         'per_kernel_measured_on': 'the untimed per-layer pass (one hipEvent bracket per launch, one stream; Convolution total there {:.3f} ms '
-                                                  'against {:.3f} ms with run brackets in the timed blocks)'.format(layer_pass_ms, conv['ms'])}
+                                                  'against {:.3f} ms with run brackets in the instrumented block)'.format(layer_pass_ms, conv['ms'])}
             breakdown = {}
             rocprof_ms = rocprof_per_op() if args.batch == BATCH_PER_GPU else {}          # (the committed trace is the batch-256 workload)
             for typ, agg in sorted(by_type.items(), key=lambda kv: -kv[1]['ms']):

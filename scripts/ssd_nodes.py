@@ -1,8 +1,9 @@
 import os, sys
-sys.path.insert(0, '/root/repo')
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
 from pyopenvino_amd import IECore, device, synth
 device.init(0)
-xml = '/root/repo/models/ssd_mobilenet_v1_coco.xml'
+xml = os.path.join(REPO, 'models', 'ssd_mobilenet_v1_coco.xml')
 ie = IECore()
 net = ie.read_network(xml, weights=synth.synth_weights(xml, 1234))
 net.set_batch(128)

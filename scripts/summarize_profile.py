@@ -38,7 +38,7 @@ def main():
     prof = os.path.join(repo, 'profiles')
     os.makedirs(prof, exist_ok=True)
     md = ['# rocprofv3 summary `{}`'.format(tag), '',
-          'Command: `rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 5 --warmup 2 --cpu-images 0 --no-extra --min-seconds 0 --requests 1 --streams 1` '
+          'Command: `rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 5 --warmup 2 --cpu-images 0 --no-extra --requests 1 --streams 1` '
           '(googlenet-v1, batch 256, 1 GPU; one request at a time on ONE compute stream, so that a launch\'s start-to-end time is its own: '
           'this is what bench.py\'s roofline measures on its sampled steps).  The default command (several whole-batch requests in flight, '
           'kernels of different passes overlapping) is summarised at the end.', '']
@@ -91,7 +91,7 @@ def main():
         with open(os.path.join(prof, tag + '_kernel_stats_forked.csv'), 'w') as f:
             f.write(open(forked).read())
         forked_md = ['', '## Default command (requests in flight)', '',
-                     '`rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 5 --warmup 2 --cpu-images 0 --no-extra --min-seconds 0`: per-kernel table in `{}_kernel_stats_forked.csv`.  '
+                     '`rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 5 --warmup 2 --cpu-images 0 --no-extra`: per-kernel table in `{}_kernel_stats_forked.csv`.  '
                      'Convolution launches: {:.0f}, average start-to-end {:.2f} us -- longer than alone on one stream because launches of different '
                      'passes share the chip; the step is shorter.'.format(tag, calls, tot / max(1.0, calls) / 1e3)]
         fl = os.path.join(raw, 'bench_line_forked.json')

@@ -186,6 +186,22 @@ def test_bench_work_model_matches_survey_totals():
     assert abs(relu_bytes / 1e6 - 2 * 12.905) < 0.01
 
 
+def test_bench_dump_outputs_writes_float_arrays_within_the_cap(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: one DIR/<Result name>.npy per Result in float32 / float64; above the cap, the same seeded rows every time."""
+    import bench
+    prob = np.arange(12000, dtype=np.float32).reshape(12, 1000)
+    bench.dump_outputs({'prob/sink_port_0': prob, 'count': np.arange(3, dtype=np.int64)}, str(tmp_path / 'full'))
+    got = np.load(str(tmp_path / 'full' / 'prob_sink_port_0.npy'))
+    assert got.dtype == np.float32 and np.array_equal(got, prob)
+    assert np.load(str(tmp_path / 'full' / 'count.npy')).dtype == np.float64
+    monkeypatch.setattr(bench, 'DUMP_BYTES', 4 * 4000)
+    for run in ('a', 'b'):
+        bench.dump_outputs({'prob': prob}, str(tmp_path / run))
+    a, b = np.load(str(tmp_path / 'a' / 'prob.npy')), np.load(str(tmp_path / 'b' / 'prob.npy'))
+    assert a.shape == (4, 1000) and a.nbytes <= bench.DUMP_BYTES and np.array_equal(a, b)
+    assert all(any(np.array_equal(row, p) for p in prob) for row in a)
+
+
 def test_plan_folds_the_mean_add_into_conv1s_padding_pass():
     """GoogLeNet: data/mean (Add of one constant per input channel) feeds only conv1, a padded layer with C = 3: the Add is not
     dispatched, conv1 reads the Parameter and its padding pass adds the constant (the FP16 form too: test_plan_of_an_fp16_ir_...).  Unfused
