@@ -175,6 +175,14 @@ def test_conv_winograd_stress_elementwise(hip, monkeypatch, form):
         assert excess <= 0.5, '{} {}: only {:.2f} x inside the element-wise bound'.format(form, xs, 1.0 / max(excess, 1e-9))
 
 
+def check_alone_vs_float64(alone, x, wt, b, pd, what):
+    """A batch-256 layer's output (bias + ReLU fused) against the float64 reference on the 32 sampled images (tests/ref64.py)."""
+    import ref64
+    idx = ref64.SAMPLE_256
+    want = ref64.relu(ref64.convolution(np.asarray(x)[idx], np.asarray(wt), (1, 1), pd, pd) + np.asarray(b).astype(np.float64))
+    assert_close(alone[idx], want, helpers.REL_TOL, what + ' vs float64')
+
+
 def test_convolution_kernels_side_by_side_on_several_streams_at_batch_256(hip):
     """Batch 256 makes a persistent workgroup of the six-point Winograd kernel walk several tiles (the small cases above stop at
     one), and four streams make the loads slow: a register copied while a load was still on its way into it gave wrong results
@@ -191,7 +199,9 @@ def test_convolution_kernels_side_by_side_on_several_streams_at_batch_256(hip):
         pd = (ks // 2, ks // 2)
         run = (lambda node={}, x=x, wt=wt, b=b, pd=pd: conv.launch(node, x, wt, (1, 1), pd, pd, 'explicit', bias=b, act=('relu',)))
         dev.select_stream(0)
-        jobs.append((xs, ks, run, np.asarray(run())))
+        alone = np.asarray(run())
+        check_alone_vs_float64(alone, x, wt, b, pd, 'conv {}x{} {} alone'.format(ks, ks, xs))
+        jobs.append((xs, ks, run, alone))
     try:
         for rnd_ in range(2):
             outs = []
@@ -233,6 +243,7 @@ def test_pointwise_kernel_forms_side_by_side_on_several_streams_at_batch_256(hip
             want = np.maximum(np.einsum('kc,nchw->nkhw', np.asarray(wt)[:, :, 0, 0].astype(np.float64), np.asarray(x)[:2].astype(np.float64))
                               + np.asarray(b).astype(np.float64), 0)
             assert_close(alone[:2], want.astype(np.float32), helpers.REL_TOL, 'pointwise TN={}'.format(tn))
+        check_alone_vs_float64(alone, x, wt, b, pd, 'conv {}x{} {} alone (PVHIP_PW_TN={})'.format(ks, ks, xs, tn))
         jobs.append((xs, ks, run, alone))
     try:
         for rnd_ in range(2):
