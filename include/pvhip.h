@@ -34,7 +34,7 @@ extern "C" {
 #define PVHIP_ECOMM        -4   /* RCCL failure / library not loadable                        */
 #define PVHIP_EUNSUPPORTED -5   /* configuration outside what the kernels implement           */
 
-#define PVHIP_ABI_VERSION   16
+#define PVHIP_ABI_VERSION   17
 
 /* ---------------------------------------------------------------- runtime plumbing ---------- */
 /* No reference counterpart: the reference computes in host numpy arrays (inference_engine.py:245-256
@@ -61,7 +61,12 @@ int         pvhip_pool_epoch_end(int epoch);
 int         pvhip_memcpy_h2d(void* dst, const void* src, size_t bytes);  /* Parameter.py:11-13, Const.py:11-13 upload; async w.r.t. device, host buffer reusable on return */
 int         pvhip_memcpy_d2h(void* dst, const void* src, size_t bytes);  /* Result.py:17 read-back; SYNCHRONISES the stream */
 void*       pvhip_host_alloc(size_t bytes);   /* ABI v16: page-locked host memory for read-backs (NULL when it cannot be had: use pageable memory) */
-int         pvhip_host_free(void* p);
+int         pvhip_host_free(void* p);               /* ABI v17: PVHIP_EINVAL for an address pvhip_host_alloc did not return; pvhip_shutdown frees every block */
+int         pvhip_host_stats(size_t* blocks, size_t* bytes);   /* ABI v17: live pvhip_host_alloc blocks and their bytes (no device needed) */
+/* ABI v17: the upload of a request's staged input (inference_engine.py InferRequest.input_buffer): on the CURRENT stream, never
+ * synchronising.  `src` must lie wholly inside one live pvhip_host_alloc block -- PVHIP_EINVAL for pageable memory, before anything reaches the
+ * device -- and stays untouched until the copy has finished (record an event behind it).  Refused while a capture is open. */
+int         pvhip_memcpy_h2d_async(void* dst, const void* src, size_t bytes);
 int         pvhip_memcpy_d2d(void* dst, const void* src, size_t bytes);
 int         pvhip_memset(void* dst, int byte, size_t bytes);
 int         pvhip_sync(void);                           /* host-side wait for every compute stream   */
@@ -432,6 +437,14 @@ int pvhip_comm_init(const void* unique_id, int rank, int world);
 int pvhip_comm_allgather_f32(const float* send, float* recv, size_t count_per_rank);   /* every rank the SAME count (ncclAllGather) */
 int pvhip_comm_ranks(int* count);                 /* ncclCommCount of the communicator: how many ranks RCCL itself sees */
 int pvhip_comm_destroy(void);
+
+/* ---------------------------------------------------------------- input formats (ABI v17) --- */
+/* Parameter.py:11-13 casts the caller's array to the IR type; the reference's callers hand it `cv2_image.transpose((2,0,1)).astype(float32)`.
+ * A network input declared U8 and / or NHWC (IENetwork.input_info) is uploaded as it is and converted here, in one launch, into the fp32
+ * NCHW tensor `dst` of shape (n, c, h, w): src_u8 = 1: `src` holds uint8 values (else fp32); src_nhwc = 1: `src` is (n, h, w, c) (else
+ * (n, c, h, w)).  Exact: dst == src.transpose(0, 3, 1, 2).astype(float32) bit for bit.  fp32 NCHW is a device copy.  n <= 65535,
+ * c * h * w < 2^31, c <= 4096 for NHWC (pvhip_layout.hip). */
+int         pvhip_input_to_nchw_f32(const void* src, float* dst, int n, int c, int h, int w, int src_u8, int src_nhwc);
 
 #ifdef __cplusplus
 }

@@ -154,6 +154,17 @@ int sync_all_streams() {
     s.forked = s.current != 0;
     return PVHIP_OK;
 }
+
+// Every live block of page-locked host memory pvhip_host_alloc handed out (address -> bytes): pvhip_memcpy_h2d_async accepts a source
+// only inside one of them, and pvhip_shutdown returns them all.
+struct HostBlocks {
+    std::mutex               mu;
+    std::map<uintptr_t, size_t> live;
+};
+HostBlocks& host_blocks() {
+    static HostBlocks h;
+    return h;
+}
 }  // namespace
 }  // namespace pvhip
 
@@ -220,6 +231,12 @@ int pvhip_shutdown(void) {
     if (!s.ready) return PVHIP_OK;
     (void)pvhip_comm_destroy();
     (void)pvhip_pool_release();
+    {
+        HostBlocks& h = host_blocks();
+        std::lock_guard<std::mutex> g(h.mu);
+        for (auto& kv : h.live) (void)hipHostFree((void*)kv.first);
+        h.live.clear();
+    }
     {
         Pool& p = pool();
         std::lock_guard<std::mutex> g(p.mu);
@@ -404,13 +421,52 @@ void* pvhip_host_alloc(size_t bytes) {
     if (!state().ready || bytes == 0) return nullptr;
     void* p = nullptr;
     if (hipHostMalloc(&p, bytes, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+    HostBlocks& h = host_blocks();
+    std::lock_guard<std::mutex> g(h.mu);
+    h.live[(uintptr_t)p] = bytes;
     return p;
 }
 
 int pvhip_host_free(void* p) {
     PVHIP_REQUIRE_INIT();
     if (p == nullptr) return PVHIP_OK;
+    {
+        HostBlocks& h = host_blocks();
+        std::lock_guard<std::mutex> g(h.mu);
+        if (h.live.erase((uintptr_t)p) == 0) return fail(PVHIP_EINVAL, "pvhip_host_free: %p is not a live pvhip_host_alloc block", p);
+    }
     PVHIP_HIP(hipHostFree(p));
+    return PVHIP_OK;
+}
+
+int pvhip_host_stats(size_t* blocks, size_t* bytes) {
+    HostBlocks& h = host_blocks();
+    std::lock_guard<std::mutex> g(h.mu);
+    size_t total = 0;
+    for (auto& kv : h.live) total += kv.second;
+    if (blocks) *blocks = h.live.size();
+    if (bytes) *bytes = total;
+    return PVHIP_OK;
+}
+
+/* The upload of a request's staged input: on the current stream, never synchronising.  The host side must stay untouched until the copy
+ * has finished, so only page-locked memory of this library qualifies (a pageable source would make hipMemcpyAsync copy through a staging
+ * buffer the caller can race with, or wait): the whole range [src, src + bytes) must lie inside one live pvhip_host_alloc block. */
+int pvhip_memcpy_h2d_async(void* dst, const void* src, size_t bytes) {
+    PVHIP_REQUIRE_INIT();
+    if (bytes == 0) return PVHIP_OK;
+    PVHIP_CHECK_ARG(dst != nullptr && src != nullptr);
+    if (state().capturing) return fail(PVHIP_EINVAL, "pvhip_memcpy_h2d_async: a pass is being captured into a graph (uploads stay outside it)");
+    {
+        HostBlocks& h = host_blocks();
+        std::lock_guard<std::mutex> g(h.mu);
+        const uintptr_t a = (uintptr_t)src;
+        auto it = h.live.upper_bound(a);
+        const bool inside = it != h.live.begin() && (--it, a + bytes <= it->first + it->second);
+        if (!inside)
+            return fail(PVHIP_EINVAL, "pvhip_memcpy_h2d_async: source %p (+%zu bytes) is not page-locked memory from pvhip_host_alloc", src, bytes);
+    }
+    PVHIP_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, state().stream));
     return PVHIP_OK;
 }
 

@@ -6,6 +6,7 @@ library is missing or no GPU is visible, every entry point raises -- there is no
 """
 import ctypes
 import os
+import threading
 import weakref
 
 import numpy as np
@@ -43,6 +44,8 @@ SIGNATURES = {
     'pvhip_memcpy_d2h': (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_size_t]),
     'pvhip_host_alloc': (_c.c_void_p, [_c.c_size_t]),
     'pvhip_host_free': (_c.c_int, [_c.c_void_p]),
+    'pvhip_host_stats': (_c.c_int, [_c.POINTER(_c.c_size_t), _c.POINTER(_c.c_size_t)]),
+    'pvhip_memcpy_h2d_async': (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_size_t]),
     'pvhip_memcpy_d2d': (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_size_t]),
     'pvhip_memset': (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_size_t]),
     'pvhip_sync': (_c.c_int, []),
@@ -143,6 +146,7 @@ SIGNATURES = {
     'pvhip_comm_allgather_f32': (_c.c_int, [_fp, _fp, _c.c_size_t]),
     'pvhip_comm_ranks': (_c.c_int, [_c.POINTER(_c.c_int)]),
     'pvhip_comm_destroy': (_c.c_int, []),
+    'pvhip_input_to_nchw_f32': (_c.c_int, [_c.c_void_p, _fp] + [_c.c_int] * 6),
 }
 
 # entry points whose return value is not a status code
@@ -274,6 +278,27 @@ def synchronize():
     call('pvhip_sync')
 
 
+def shutdown():
+    """Release the device (pvhip_shutdown: the device pool, the streams and every page-locked host block) and forget the page-locked
+    read-back pool, whose addresses are gone with it.  Arrays still viewing page-locked memory must not be read afterwards.  init()
+    binds again."""
+    global _initialised_device, _pinned_total, _pinned_generation
+    with _pinned_lock:
+        _pinned_free.clear()
+        _pinned_total = 0
+        _pinned_generation += 1          # blocks handed out before: their finalizers neither return nor free them
+    if _lib is not None and _initialised_device is not None:
+        call('pvhip_shutdown')
+    _initialised_device = None
+
+
+def host_stats():
+    """(blocks, bytes) of page-locked host memory the library holds."""
+    a, b = _c.c_size_t(0), _c.c_size_t(0)
+    call('pvhip_host_stats', _c.byref(a), _c.byref(b))
+    return a.value, b.value
+
+
 def current_device():
     """Index of the GPU this process is bound to (None before init)."""
     return _initialised_device
@@ -324,13 +349,17 @@ def _contig_strides(shape):
 
 
 _PINNED_MAX_BYTES = 8 << 20          # per array; larger read-backs (activations in tests) stay pageable
-_PINNED_POOL_BYTES = 64 << 20        # page-locked memory this process keeps at most
+_PINNED_POOL_BYTES = 64 << 20        # page-locked memory this process keeps at most for read-backs
 _pinned_free = {}                    # rounded size -> [address, ...]
 _pinned_total = 0
+_pinned_generation = 0               # bumped by shutdown(): addresses of an earlier generation no longer exist
+_pinned_lock = threading.Lock()      # read-backs may be collected (finalizers) on any thread
 
 
-def _pinned_release(size, addr):
-    _pinned_free.setdefault(size, []).append(addr)
+def _pinned_release(size, addr, generation):
+    with _pinned_lock:
+        if generation == _pinned_generation:
+            _pinned_free.setdefault(size, []).append(addr)
 
 
 def _pinned_empty(shape, dtype):
@@ -341,19 +370,39 @@ def _pinned_empty(shape, dtype):
     if nbytes == 0 or nbytes > _PINNED_MAX_BYTES or os.environ.get('PVHIP_PINNED_RESULTS', '1') == '0':
         return np.empty(shape, dtype=dtype)
     size = 1 << max(12, (nbytes - 1).bit_length())
-    free = _pinned_free.get(size)
-    if free:
-        addr = free.pop()
-    else:
-        if _pinned_total + size > _PINNED_POOL_BYTES:
-            return np.empty(shape, dtype=dtype)
-        addr = call('pvhip_host_alloc', size)
-        if not addr:
-            return np.empty(shape, dtype=dtype)
-        _pinned_total += size
+    with _pinned_lock:
+        free = _pinned_free.get(size)
+        addr = free.pop() if free else None
+        if addr is None:
+            if _pinned_total + size > _PINNED_POOL_BYTES:
+                return np.empty(shape, dtype=dtype)
+            addr = call('pvhip_host_alloc', size)
+            if not addr:
+                return np.empty(shape, dtype=dtype)
+            _pinned_total += size
+        generation = _pinned_generation
     buf = (_c.c_char * size).from_address(addr)
-    weakref.finalize(buf, _pinned_release, size, addr)          # the array (and every view of it) keeps `buf` alive
+    weakref.finalize(buf, _pinned_release, size, addr, generation)   # the array (and every view of it) keeps `buf` alive
     return np.frombuffer(buf, dtype=dtype, count=nbytes // dtype.itemsize).reshape(shape)
+
+
+def _host_block_free(addr, generation):
+    if generation == _pinned_generation and _lib is not None:
+        _lib.pvhip_host_free(_c.c_void_p(addr))
+
+
+def host_empty(shape, dtype):
+    """A new array in page-locked memory of its own (pvhip_host_alloc; not from the read-back pool, not counted against its cap),
+    returned to the system when the last view of it is collected -- or by shutdown().  Raises if the memory cannot be had."""
+    ensure_init()
+    dtype = np.dtype(dtype)
+    nbytes = max(1, int(np.prod(shape, dtype=np.int64)) * dtype.itemsize)
+    addr = call('pvhip_host_alloc', nbytes)
+    if not addr:
+        raise PvhipError('pvhip_host_alloc({} bytes): no page-locked memory'.format(nbytes))
+    buf = (_c.c_char * nbytes).from_address(addr)
+    weakref.finalize(buf, _host_block_free, addr, _pinned_generation)
+    return np.frombuffer(buf, dtype=dtype, count=int(np.prod(shape, dtype=np.int64))).reshape(shape)
 
 
 class DeviceTensor:

@@ -102,11 +102,75 @@ class IECore:
         """`num_requests` (accepted and ignored by the reference, inference_engine.py:86) is the number of infer
         requests that may be in flight at once: `exenet.requests[i].start_async(inputs)` / `.wait()`, each request
         with its own graph state and its own compute streams.  `exenet.infer()` stays the synchronous call."""
+        network.input_info                   # (the declared input formats are shared with every request's copy of the network)
         exenet = Executable_Network(network)
         self.check_nodes(exenet.ienet.G)
         exenet.schedule_tasks()
         exenet.create_requests(max(1, int(num_requests)))
+        network._loaded = True               # input_info is fixed from here on
         return exenet
+
+
+class InputInfo:
+    """The format a caller hands one network input in (OpenVINO 2021's ``IENetwork.input_info[name]``): ``precision`` 'FP32' (default)
+    or 'U8', ``layout`` 'NCHW' (default) or 'NHWC'.  A U8 value v means float(v); an NHWC array is ``x.transpose(0, 3, 1, 2)`` of the NCHW
+    tensor the IR expects -- a cv2 image as it is, where the reference's callers hand ``img.transpose((2, 0, 1)).astype(np.float32)``.
+    Set between ``read_network`` and ``load_network``.  A declared input is uploaded as it is and converted on the device
+    (``pvhip_input_to_nchw_f32``); an input whose format is never set goes the default way."""
+    PRECISIONS = ('FP32', 'U8')
+    LAYOUTS = ('NCHW', 'NHWC')
+
+    def __init__(self, net, nid):
+        self._net, self._nid = net, nid
+        self._precision, self._layout = 'FP32', 'NCHW'
+        self.declared = False           # precision or layout set explicitly (to any value)
+
+    @property
+    def name(self):
+        return self._net.G.nodes[self._nid]['name']
+
+    @property
+    def dims(self):
+        """The NCHW shape of the tensor the IR expects."""
+        return tuple(int(d) for d in self._net.G.nodes[self._nid]['data']['shape'])
+
+    def supported(self):
+        """Declared formats exist for 4-D Parameters whose element type is f32 (FP16 IRs read with fp16_as_fp32 are, once promoted)."""
+        data = self._net.G.nodes[self._nid]['data']
+        return len(tuple(data['shape'])) == 4 and str(data.get('element_type', '')).lower() == 'f32'
+
+    @property
+    def precision(self):
+        return self._precision
+
+    @precision.setter
+    def precision(self, value):
+        self._precision = self._checked('precision', value, self.PRECISIONS)
+
+    @property
+    def layout(self):
+        return self._layout
+
+    @layout.setter
+    def layout(self, value):
+        self._layout = self._checked('layout', value, self.LAYOUTS)
+
+    def _checked(self, what, value, allowed):
+        if getattr(self._net, '_loaded', False):
+            raise ValueError('input {}: set input_info[...].{} between read_network and load_network, not after'.format(self.name, what))
+        if not isinstance(value, str) or value.upper() not in allowed:
+            raise ValueError('input {}: {} {!r} is not one of {}'.format(self.name, what, value, allowed))
+        if not self.supported():
+            data = self._net.G.nodes[self._nid]['data']
+            raise NotImplementedError('input {}: a declared {} needs a 4-D f32 Parameter; this one is {} {}'.format(
+                self.name, what, data.get('element_type'), tuple(data['shape'])))
+        self.declared = True
+        return value.upper()
+
+    def host_format(self):
+        """(shape, dtype) of the array a caller hands in this format."""
+        n, c, h, w = self.dims
+        return ((n, h, w, c) if self._layout == 'NHWC' else (n, c, h, w)), np.dtype(np.uint8 if self._precision == 'U8' else np.float32)
 
 
 class IENetwork:
@@ -121,6 +185,14 @@ class IENetwork:
         self.outputs = None
         self.batch_size = 1
         self.f16_mfma = False      # FP16 IR read with fp16_as_fp32=False: Convolution / MatMul on the f16 matrix cores
+
+    @property
+    def input_info(self) -> dict:
+        """{Parameter name: InputInfo}: the format each input is handed in (set before load_network)."""
+        info = self.__dict__.get('_input_info')
+        if info is None:
+            info = self._input_info = {self.G.nodes[n]['name']: InputInfo(self, n) for n in self.G.nodes if self.G.nodes[n]['type'] == 'Parameter'}
+        return info
 
     # ------------------------------------------------------------------ IR reading
     def read_IR_Model(self, model, weights=None):
@@ -287,6 +359,7 @@ class InferRequest:
             raise RuntimeError('request {} is still in flight: wait() first'.format(self.index))
         ex = self.runner
         G = ex.ienet.G
+        inputs = ex._stage_host_inputs(inputs)
         # The same device-resident tensors as the last calls: the pass is replayed from this request's own recording (one call
         # instead of ~100 dispatches; every request records its own pass on its own stream and keeps its own tensors, so the
         # replays of several requests run side by side like their eager passes do).
@@ -343,6 +416,18 @@ class InferRequest:
     def infer(self, inputs: dict) -> dict:
         self.start_async(inputs)
         return self.wait()
+
+    def input_buffer(self, name: str) -> np.ndarray:
+        """The host array this request uploads input `name` from: page-locked memory the request owns, allocated on the first call, in
+        the declared format (``IENetwork.input_info``; e.g. (256, 224, 224, 3) uint8 for U8 / NHWC).  Handing it to ``start_async({name:
+        buf})`` costs no host copy: it is uploaded asynchronously on the copy stream while other requests compute.
+
+        Ownership: the request reads this memory until its pass is done.  Fill it only between ``wait()`` (or before the first
+        ``start_async``) and the next ``start_async()``; writing it while the request is in flight changes what the pass may see.  The
+        memory is returned when the request's device state is released and the array is no longer referenced."""
+        if name not in self.runner.ienet.input_info:
+            raise KeyError('no network input named {!r}'.format(name))
+        return self.runner._host_input(name)['host']
 
 
 class CaptureStreamModel:
@@ -461,6 +546,7 @@ class Executable_Network:
         infer uploads and packs again.  A captured hipGraph holds raw addresses of exactly these tensors (packed weights, cached
         constants, Concat buffers): it goes first, or a later infer_graph() would replay kernels over freed or reused pool blocks."""
         self.release_graph()
+        self.__dict__.pop('_host_inputs', None)     # page-locked buffers go back once the caller holds no view of them
         G = self.ienet.G
         for nid in G.nodes:
             node = G.nodes[nid]
@@ -1557,6 +1643,7 @@ class Executable_Network:
         return self._graph
 
     def infer(self, inputs: dict, verbose: bool = False) -> dict:
+        inputs = self._stage_host_inputs(inputs)
         if self._graph_for(inputs, verbose) is None:
             return self._infer_eager(inputs, verbose)
         self.last_node_times = []
@@ -1588,3 +1675,60 @@ class Executable_Network:
         if verbose:
             print('@TOTAL_TIME,', time.time() - t0)
         return {name: G.nodes[nid]['result'] for nid, name in self.ienet.find_node_by_type('Result')}
+
+    # ---- host inputs in a declared format (IENetwork.input_info) or from a request's own page-locked buffer (InferRequest.input_buffer)
+    def _host_input(self, name):
+        """This request's staging of input `name`: the page-locked host array, the device tensor it is uploaded into, and the fp32 NCHW
+        tensor the pass reads -- the same address on every call, so the pass is recorded and replayed like a device-resident one."""
+        from . import device
+        slots = self.__dict__.setdefault('_host_inputs', {})
+        slot = slots.get(name)
+        if slot is None:
+            info = self.ienet.input_info[name]
+            if not info.supported():
+                raise NotImplementedError('input {}: page-locked input buffers exist for 4-D f32 Parameters only'.format(name))
+            shape, dtype = info.host_format()
+            fixed = device.DeviceTensor.empty(info.dims)
+            convert = info.precision != 'FP32' or info.layout != 'NCHW'
+            slot = {'host': device.host_empty(shape, dtype), 'fixed': fixed, 'event': device.Event(timed=False),
+                    'staging': device.DeviceTensor.empty(shape, dtype) if convert else fixed,
+                    'u8': info.precision == 'U8', 'nhwc': info.layout == 'NHWC'}
+            slots[name] = slot
+        return slot
+
+    def _stage_host_inputs(self, inputs: dict) -> dict:
+        """Inputs handed in a declared format, or in this request's own buffer, become the request's fixed fp32 NCHW device tensor: the
+        caller's array is copied into the page-locked buffer unless it IS that buffer, the buffer is uploaded on the copy stream, this
+        request's first stream waits for the copy's event and converts (one launch; none for FP32 NCHW).  No host synchronisation.
+        Every other input is returned unchanged (and goes the default way)."""
+        from . import device
+        out = None
+        for name, arr in inputs.items():
+            info = self.ienet.input_info.get(name)
+            if info is None or isinstance(arr, (device.DeviceTensor, device.ChannelSlice, device.BlockedHalf)):
+                continue
+            slot = self.__dict__.get('_host_inputs', {}).get(name)
+            own = (slot is not None and isinstance(arr, np.ndarray) and arr.shape == slot['host'].shape and arr.dtype == slot['host'].dtype
+                   and arr.ctypes.data == slot['host'].ctypes.data)
+            if not (own or info.declared):
+                continue
+            slot = self._host_input(name)
+            host = slot['host']
+            if not own:
+                a = np.asarray(arr)
+                if a.shape != host.shape:
+                    raise ValueError('input {}: declared {} / {} means shape {}, got {}'.format(name, info.precision, info.layout, host.shape, a.shape))
+                np.copyto(host, a, casting='same_kind' if host.dtype == np.float32 else 'safe')
+            device.select_stream(device.COPY_STREAM)
+            device.call('pvhip_memcpy_h2d_async', ctypes_void_p(slot['staging'].ptr), ctypes_void_p(host.ctypes.data), host.nbytes)
+            slot['event'].record()
+            device.select_stream(self.stream_base)
+            slot['event'].wait()
+            if slot['staging'] is not slot['fixed']:
+                device.call('pvhip_input_to_nchw_f32', ctypes_void_p(slot['staging'].ptr), ctypes_void_p(slot['fixed'].ptr),
+                            *slot['fixed'].shape, int(slot['u8']), int(slot['nhwc']))
+            device.select_stream(0)
+            if out is None:
+                out = dict(inputs)
+            out[name] = slot['fixed']
+        return inputs if out is None else out
