@@ -235,7 +235,7 @@ def _env_level(name, default):
 
 
 # ... and fp16 tensors blocked by eight channels: 0 = never, 1 = between a 1x1 convolution and the 3x3 / 5x5 behind it, 2 = whole modules and
-# the stem (Executable_Network.plan_fusion / plan_c8_modules read THIS value, the plugins too: one source for both sides)
+# the stem (fusion_plan.build reads THIS value, the plugins too: one source for both sides)
 conv_f16_c8 = _env_level('PVHIP_CONV_F16_C8', '2')
 fuse_poolconv = _env_level('PVHIP_FUSE_POOLCONV', '2')
 fuse_stem_conv = _env_level('PVHIP_FUSE_STEM_CONV', '1')          # the 1x1 convolution behind MaxPool + LRN in the same launch (0 = two launches)             # MaxPool + pool_proj as one launch: 0 = never (what the plan reads; the library parses its own copy)

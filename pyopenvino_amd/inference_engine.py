@@ -27,7 +27,7 @@ import xml.etree.ElementTree as et
 import networkx as nx
 import numpy as np
 
-from . import common_def
+from . import common_def, fusion_plan
 
 DEFAULT_PLUGIN_PACKAGE = 'pyopenvino_amd.op_plugins'
 
@@ -78,7 +78,7 @@ class IECore:
         at load, every FP16 port declared FP32); default: what the plugin package asks for (``COMPUTE_FP32``).  False with a
         package that declares ``F16_MFMA`` (this one): Convolution and MatMul round their operands to fp16 and run on the f16
         matrix cores with fp32 accumulation (``net.f16_mfma``), and the tensors between them are fp16 in HBM wherever the plan
-        can keep them so (``plan_fusion`` / ``plan_c8_modules``: channels blocked by eight, ``device.BlockedHalf`` -- GoogLeNet
+        can keep them so (``fusion_plan``: channels blocked by eight, ``device.BlockedHalf`` -- GoogLeNet
         from conv1's output to pool5; ``PVHIP_CONV_F16_C8=0``: fp32 NCHW tensors holding fp16 values); the ports stay declared
         FP32, which is what a reader outside those kernels gets.  With any other package the IR is left as it is (FP16 ports,
         float16 constants: the reference's own mode)."""
@@ -485,20 +485,14 @@ class Executable_Network:
         self.expected_rtol = 1.0        # the reference compares with np.allclose(rtol=1) (common_def.py:72)
         self.pickle_node_args = []      # node ids whose (node, inputs) run_tasks dumps to node_args_<id>.pickle (cf. :216, :275-278)
         self.pickle_dir = '.'           # where (the reference writes into the working directory)
-        self.task_list = []
+        self.list_schedule = []         # the static list schedule (schedule_tasks); the plan's task order is this or another legal order of it
+        self.plan = fusion_plan.FusionPlan(ienetwork.G, [])     # which nodes fold into which launch (plan_fusion); task_list is its order
         self.last_node_times = []       # [(node id, type, name, host seconds)] of the last run_tasks
         self.comm = None                # shard.BatchShardComm when the batch is sharded over ranks
         self.device_timing = None       # None, 'all', or a set of layer types: bracket those nodes with hipEvents
         self.device_timing_runs = False # True: consecutive bracketed nodes share ONE bracket (a bracket costs ~10-15 us
                                         # of stream time, which a per-node bracket would add to every launch)
         self.fuse_epilogues = True      # run Convolution -> Add(per-channel const) -> ReLU chains as one launch
-        self._fusion = {}               # conv node id -> {'bias': const id, 'add': id, 'relu': id or None}
-        self._fused_away = set()        # node ids whose compute() is folded into their producer
-        self._concat_direct = {}        # Concat node id -> total channels, when every input is written in place
-        self._lrn_pool = {}             # LRN node id -> id of the MaxPool folded into it, or MaxPool id -> id of the LRN folded into it
-        self._siblings = {}             # Convolution node id -> ids of the convolutions of the same input launched with it
-        self._pool_conv = {}            # Convolution node id -> (MaxPool node folded into its input tile, id of the MaxPool's data input)
-        self._pre_add = {}              # Convolution node id -> (Add node folded into its padding pass, Const id, id of the Add's data input)
         self.fuse_siblings = os.environ.get('PVHIP_FUSE_SIBLINGS', '1') != '0'
         self._infer_serial = 0
         self._timed = []                # [(node id, type, name, start Event, stop Event)] of the last run_tasks
@@ -554,7 +548,7 @@ class Executable_Network:
                 del node[key]
             for port in node.get('output', {}).values():
                 port.pop('data', None)
-            for key in ('result', 'param', '_sibling_out', '_fuse_bias', '_out_into', '_out_c8', '_siblings', '_fuse_pool', '_fuse_pool_in', '_fuse_lrn'):
+            for key in ('result', 'param', '_sibling_out') + fusion_plan.HINT_KEYS:
                 node.pop(key, None)
 
     def start_async(self, request_id: int, inputs: dict):
@@ -586,386 +580,28 @@ class Executable_Network:
             if len(still) == len(pending):
                 raise RuntimeError('graph has nodes that can never become ready')
             pending = still
-        self.list_schedule = list(order)         # the reference's order; plan_fusion may move mutually independent arms (order_for_locality)
-        self.task_list = order
+        self.list_schedule = order               # the reference's order; the plan may move mutually independent arms (locality order)
         self.plan_fusion()
 
     def plan_fusion(self):
+        """(Re)build the fusion plan of the list schedule for the current flags (fusion_plan.build)."""
         self._plan_serial = self.__dict__.get('_plan_serial', 0) + 1      # a captured pass is a pass of ONE plan
-        """Peephole over the scheduled graph (SURVEY 8(f)-1): a Convolution whose only consumer is an Add of a
-        per-output-channel Const (1,K,1,1), optionally followed by a ReLU as the Add's only consumer, is run
-        as ONE launch: the Convolution plugin receives the bias tensor / relu flag on its node dict and
-        applies them in the kernel epilogue (the same fp32 add and the same select, so the fused result is
-        bit-identical to the three launches); the Add and ReLU nodes are not dispatched and their output
-        ports alias the fused tensor.  Plugins that do not understand the hints (any foreign Convolution
-        plugin) never see them because fusion is only planned for this package's plugin."""
-        self._fusion, self._fused_away, self._lrn_pool, self._siblings, self._pool_conv = {}, set(), {}, {}, {}
-        self._pre_add, self._c8_out, self._c8_concat, self._c8_entry = {}, set(), set(), set()
-        self._stem_conv = {}                 # MaxPool (leading MaxPool + LRN) -> the 1x1 convolution behind the LRN that rides in the same launch
-        if 'list_schedule' in self.__dict__:
-            self.task_list = list(self.list_schedule)
-        if not self.fuse_epilogues:
-            return
-        from . import device           # settings only (parsed from the environment at import / reload_settings(): the SAME values the plugins read)
-        G = self.ienet.G
-        # LRN whose only consumer is a MaxPool the fused kernel covers: one launch, the LRN tensor is never written
-        lrn_plugin = self.ienet.ie.plugins.plugins.get('LRN')
-        if lrn_plugin is not None and getattr(lrn_plugin, 'SUPPORTS_FUSED_POOL', False):
-            for lid in G.nodes:
-                if G.nodes[lid]['type'] != 'LRN':
-                    continue
-                succ = list(G.successors(lid))
-                if len(succ) != 1 or G.nodes[succ[0]]['type'] != 'MaxPool' or G.edges[(lid, succ[0])]['connection'][3] != 0:
-                    continue
-                if lrn_plugin.pool_fusable(G.nodes[lid], G.nodes[succ[0]]):
-                    self._lrn_pool[lid] = succ[0]
-                    self._fused_away.add(succ[0])
-        # the other order: a MaxPool whose only consumer is an LRN (GoogLeNet: pool1/3x3_s2 -> pool1/norm1)
-        pool_plugin = self.ienet.ie.plugins.plugins.get('MaxPool')
-        if pool_plugin is not None and getattr(pool_plugin, 'SUPPORTS_FUSED_LRN', False):
-            for pid in G.nodes:
-                if G.nodes[pid]['type'] != 'MaxPool' or pid in self._fused_away:
-                    continue
-                succ = list(G.successors(pid))
-                if len(succ) != 1 or G.nodes[succ[0]]['type'] != 'LRN' or G.edges[(pid, succ[0])]['connection'][3] != 0:
-                    continue
-                if succ[0] in self._lrn_pool or succ[0] in self._fused_away:
-                    continue                 # that LRN already leads an LRN -> MaxPool launch
-                if pool_plugin.lrn_fusable(G.nodes[pid], G.nodes[succ[0]]):
-                    self._lrn_pool[pid] = succ[0]
-                    self._fused_away.add(succ[0])
-        conv_plugin = self.ienet.ie.plugins.plugins.get('Convolution')
-        if conv_plugin is None or not getattr(conv_plugin, 'SUPPORTS_FUSED_EPILOGUE', False):
-            return
-        fusable = {t for t in ('Convolution', 'GroupConvolution')
-                   if getattr(self.ienet.ie.plugins.plugins.get(t), 'SUPPORTS_FUSED_EPILOGUE', False)}
-        for cid in G.nodes:
-            if G.nodes[cid]['type'] not in fusable:
-                continue
-            succ = list(G.successors(cid))
-            if len(succ) != 1 or G.nodes[succ[0]]['type'] != 'Add':
-                continue
-            aid = succ[0]
-            if G.edges[(cid, aid)]['connection'][3] != 0:
-                continue
-            others = [p for p in G.pred[aid] if p != cid]
-            if len(others) != 1 or G.nodes[others[0]]['type'] != 'Const':
-                continue
-            bid = others[0]
-            k_out = next(iter(G.nodes[cid]['output'].values()))['dims'][1]
-            if tuple(G.nodes[bid]['data']['shape']) != (1, k_out, 1, 1) or G.nodes[bid]['data']['element_type'] != 'f32':
-                continue
-            rid, act = None, None
-            asucc = list(G.successors(aid))
-            if len(asucc) == 1 and G.nodes[asucc[0]]['type'] == 'ReLU':
-                rid, act = asucc[0], ('relu',)
-            elif len(asucc) == 1 and G.nodes[asucc[0]]['type'] == 'Clamp':
-                rid = asucc[0]
-                act = ('clamp', float(G.nodes[rid]['data']['min']), float(G.nodes[rid]['data']['max']))
-            self._fusion[cid] = {'bias': bid, 'add': aid, 'relu': rid, 'act': act, 'into': None}
-            self._fused_away.add(aid)
-            if rid is not None:
-                self._fused_away.add(rid)
-        # Second peephole: a channel Concat (axis 1, NCHW) all of whose inputs are ends of fused convolution
-        # chains with no other consumer is not dispatched either: each producing convolution writes its
-        # channels straight into the Concat's output tensor (Concat.py:9-13 becomes a store pattern).
-        self._concat_direct = {}
-        tail_of = {}
-        for cid, f in self._fusion.items():
-            tail_of[f['relu'] if f['relu'] is not None else f['add']] = cid
-        for nid in G.nodes:
-            node = G.nodes[nid]
-            if node['type'] != 'Concat' or int(node['data']['axis']) != 1:
-                continue
-            out_dims = next(iter(node['output'].values()))['dims']
-            preds = list(G.pred[nid])
-            if len(out_dims) != 4 or len(preds) < 2 or len(preds) != len(node['input']):
-                continue
-            plan, coff, ok = [], 0, True
-            for pred in preds:                       # edge order == np.concatenate order (Concat.py:11-12)
-                cid = tail_of.get(pred)
-                if cid is None or len(list(G.successors(pred))) != 1:
-                    ok = False
-                    break
-                k = next(iter(G.nodes[cid]['output'].values()))['dims'][1]
-                plan.append((cid, coff))
-                coff += k
-            if not ok or coff != out_dims[1]:
-                continue
-            for cid, off in plan:
-                self._fusion[cid]['into'] = (nid, off)
-            self._concat_direct[nid] = coff
-            self._fused_away.add(nid)
+        self.plan = fusion_plan.build(self.ienet.G, self.list_schedule, self.ienet.ie.plugins.plugins, self.fuse_epilogues,
+                                      self.fuse_siblings, bool(getattr(self.ienet, 'f16_mfma', False)))
 
-        f16 = bool(getattr(self.ienet, 'f16_mfma', False))     # the f16-MFMA kernel fuses the epilogue and the Concat store only
-        # A 3x3 / stride 1 / pad 1 MaxPool whose only consumer is a fused 1x1 convolution (pool -> pool_proj): the MaxPool is not
-        # dispatched, the convolution reads the MaxPool's input and pools while it builds its input tile.
-        if (not f16 or device.conv_f16_dma) and getattr(conv_plugin, 'SUPPORTS_POOLED_INPUT', False) and device.fuse_poolconv != 0:
-            for cid in list(self._fusion):
-                if G.nodes[cid]['type'] != 'Convolution':
-                    continue
-                src = next((p_ for p_ in G.pred[cid] if G.edges[(p_, cid)]['connection'][3] == 0), None)
-                if src is None or G.nodes[src]['type'] != 'MaxPool' or src in self._fused_away or len(list(G.successors(src))) != 1:
-                    continue
-                psrc = next((p_ for p_ in G.pred[src] if G.edges[(p_, src)]['connection'][3] == 0), None)
-                if psrc is not None and conv_plugin.pooled_fusable(G.nodes[cid], G.nodes[src]):
-                    self._pool_conv[cid] = (src, psrc)
-                    self._fused_away.add(src)
-        # An Add of a per-INPUT-channel Const whose only consumer is a convolution that pads its input in a pass of its own (GoogLeNet:
-        # data/mean -> conv1): the padding pass adds the constant on the way and the Add is not dispatched (same fp32 add: same bits).
-        if getattr(conv_plugin, 'SUPPORTS_PRE_ADD', False):
-            for cid in G.nodes:
-                if G.nodes[cid]['type'] != 'Convolution' or cid in self._pool_conv:
-                    continue
-                src = next((p_ for p_ in G.pred[cid] if G.edges[(p_, cid)]['connection'][3] == 0), None)
-                if src is None or G.nodes[src]['type'] != 'Add' or src in self._fused_away or len(list(G.successors(src))) != 1:
-                    continue
-                preds = list(G.pred[src])
-                consts = [p_ for p_ in preds if G.nodes[p_]['type'] == 'Const']
-                others = [p_ for p_ in preds if G.nodes[p_]['type'] != 'Const']
-                if len(preds) != 2 or len(consts) != 1 or len(others) != 1:
-                    continue
-                if (conv_plugin.pre_add_fusable(G.nodes[cid], G.nodes[src], G.nodes[consts[0]], True) if f16
-                        else conv_plugin.pre_add_fusable(G.nodes[cid], G.nodes[src], G.nodes[consts[0]])):
-                    self._pre_add[cid] = (src, consts[0], others[0])
-                    self._fused_away.add(src)
-        # Third peephole: fused convolution chains that read the SAME tensor with the same geometry and activation (the
-        # 1x1, 3x3_reduce and 5x5_reduce arms of an inception module) are one launch of the first of them in schedule
-        # order: the input is read once and every output-channel tile stores into the tensor of its own convolution
-        # (Convolution.launch_siblings; each output has the bits of its own launch).
-        if (not f16 or device.conv_f16_dma) and self.fuse_siblings and getattr(conv_plugin, 'SUPPORTS_SIBLINGS', False):
-            position = {t: i for i, t in enumerate(self.task_list)}
-            groups = {}
-            for cid, f in self._fusion.items():
-                if G.nodes[cid]['type'] != 'Convolution':
-                    continue
-                src = next((G.edges[(p_, cid)]['connection'][:2] for p_ in G.pred[cid] if G.edges[(p_, cid)]['connection'][3] == 0), None)
-                if src is None or G.nodes[src[0]]['type'] == 'Const':
-                    continue
-                geometry = tuple(G.nodes[cid]['input'][1]['dims'][2:]) + tuple(G.nodes[cid]['data'].get(k_) for k_ in ('strides', 'pads_begin', 'pads_end', 'auto_pad'))
-                groups.setdefault((tuple(src), f['act'], geometry), []).append(cid)
-            for members in groups.values():
-                members.sort(key=position.get)
-                members = members[:6]
-                if len(members) >= 2 and conv_plugin.siblings_fusable([G.nodes[m] for m in members]):
-                    self._siblings[members[0]] = members[1:]
-                    self._fused_away.update(members[1:])
-        # MaxPool -> LRN (one launch already) whose only reader is a fused 1x1 convolution chain that stands alone (no siblings, no Concat slot):
-        # the convolution rides in that launch too (GoogLeNet: pool1/3x3_s2 -> pool1/norm1 -> conv2/3x3_reduce) -- the normalised tensor never
-        # exists; the MaxPool task returns the convolution's output and the chain's ports alias it.  fp32 IRs only.
-        if not f16 and device.fuse_stem_conv != 0 and pool_plugin is not None and getattr(pool_plugin, 'SUPPORTS_FUSED_LRN_CONV', False):
-            for pid, lid in self._lrn_pool.items():
-                if G.nodes[pid]['type'] != 'MaxPool':
-                    continue
-                readers = list(G.successors(lid))
-                if len(readers) != 1 or G.edges[(lid, readers[0])]['connection'][3] != 0:
-                    continue
-                cid = readers[0]
-                f = self._fusion.get(cid)
-                if f is None or G.nodes[cid]['type'] != 'Convolution' or f['into'] is not None or cid in self._siblings or cid in self._fused_away \
-                        or cid in self._pool_conv or cid in self._pre_add:
-                    continue
-                if pool_plugin.lrn_conv_fusable(G.nodes[pid], G.nodes[lid], G.nodes[cid]):
-                    self._stem_conv[pid] = cid
-                    self._fused_away.update(n_ for n_ in (cid, f['add'], f['relu']) if n_ is not None)
-        # FP16 IRs on the f16 matrix cores: a fused 1x1 convolution chain whose ONLY reader is a 3x3 / 5x5 convolution that
-        # pvhip_conv2d_f16_c8 covers (3x3_reduce -> 3x3, 5x5_reduce -> 5x5) hands its output over as fp16 with the channels blocked by
-        # eight (device.BlockedHalf): what the reference holds there is a float16 tensor too (common_def.py:13-17), and the blocked
-        # form is the reader's MFMA operand as it stands.  PVHIP_CONV_F16_C8=0: fp32 NCHW everywhere, as before.
-        self._c8_out = set()
-        if f16 and device.conv_f16_c8 != 0 and device.conv_f16_dma and getattr(conv_plugin, 'SUPPORTS_C8', False):
-            for cid, f in self._fusion.items():
-                if G.nodes[cid]['type'] != 'Convolution' or f['into'] is not None or cid in self._pool_conv or cid in self._pre_add:
-                    continue
-                if f['act'] is not None and f['act'][0] != 'relu':
-                    continue
-                tail = f['relu'] if f['relu'] is not None else f['add']
-                readers = list(G.successors(tail))
-                if len(readers) != 1 or G.nodes[readers[0]]['type'] != 'Convolution' or G.edges[(tail, readers[0])]['connection'][3] != 0:
-                    continue
-                rid = readers[0]
-                if rid in self._pool_conv or rid in self._pre_add or rid in self._siblings or rid in self._fused_away:
-                    continue
-                if conv_plugin.c8_writer_ok(G.nodes[cid]) and conv_plugin.c8_reader_ok(G.nodes[rid]):
-                    self._c8_out.add(cid)
-            # ... and the stem: a convolution whose only reader is a 3x3 MaxPool (with its LRN folded in: GoogLeNet's conv1 -> pool1 -> norm1)
-            # whose readers are convolutions that take a blocked input: the MaxPool plugin pools a blocked tensor as it is
-            if device.conv_f16_c8 == 2 and getattr(conv_plugin, 'SUPPORTS_C8_MODULES', False):
-                for cid, f in self._fusion.items():
-                    if G.nodes[cid]['type'] != 'Convolution' or f['into'] is not None or cid in self._pool_conv or cid in self._siblings or cid in self._fused_away:
-                        continue
-                    if f['act'] is not None and f['act'][0] != 'relu':
-                        continue
-                    tail = f['relu'] if f['relu'] is not None else f['add']
-                    readers = list(G.successors(tail))
-                    if len(readers) != 1 or G.nodes[readers[0]]['type'] not in ('MaxPool', 'LRN') or readers[0] in self._fused_away:
-                        continue
-                    pid = readers[0]                                 # a 3x3 MaxPool (alone, or leading MaxPool + LRN), or an LRN leading LRN + MaxPool
-                    folded = self._lrn_pool.get(pid)
-                    if G.nodes[pid]['type'] == 'LRN' and folded is None:
-                        continue
-                    # the SAME predicates the MaxPool / LRN plugins decide with at run time (blocked_ok): what is planned blocked is blocked
-                    if G.nodes[pid]['type'] == 'MaxPool':
-                        if not pool_plugin.blocked_ok(G.nodes[pid], G.nodes[folded] if folded is not None else None):
-                            continue
-                    elif not lrn_plugin.blocked_ok(G.nodes[pid], G.nodes[folded]):
-                        continue
-                    out_node = folded if folded is not None else pid   # the node folded into the leading one carries the tensor
-                    after = list(G.successors(out_node))
-                    folded_pools = {p[0] for p in self._pool_conv.values()}
-
-                    def takes_blocked(r):
-                        if r in folded_pools:                        # a MaxPool folded into its pool_proj convolution
-                            pc = next(c_ for c_, p_ in self._pool_conv.items() if p_[0] == r)
-                            return conv_plugin.c8_module_member_ok(G.nodes[pc], G.nodes[r])
-                        return r in self._fusion and G.nodes[r]['type'] == 'Convolution' and conv_plugin.c8_module_member_ok(G.nodes[r]) and \
-                            (r in self._c8_out or r in self._siblings)
-                    if not after or not all(takes_blocked(r) for r in after):
-                        continue
-                        # the writer: the f16 1x1 launch, the f16 form of the LDS-DMA kernel (conv1), or -- its own input being blocked -- the module form
-                    own_src = next((p_ for p_ in G.pred[cid] if G.edges[(p_, cid)]['connection'][3] == 0), None)
-                    own_blocked = any(own_src == (self._fusion[c_]['relu'] if self._fusion[c_]['relu'] is not None else self._fusion[c_]['add'])
-                                      for c_ in self._c8_out)
-                    if conv_plugin.c8_writer_ok(G.nodes[cid]) or conv_plugin.c8_dma_writer_ok(G.nodes[cid]) or \
-                            (own_blocked and conv_plugin.c8_module_member_ok(G.nodes[cid])):
-                        self._c8_out.add(cid)
-            if device.conv_f16_c8 == 2 and device.fuse_stem_conv != 0 and pool_plugin is not None and getattr(pool_plugin, 'SUPPORTS_FUSED_LRN_CONV', False):
-                # ... and the 1x1 convolution behind a blocked MaxPool + LRN rides in that launch, as in an fp32 IR (GoogLeNet: conv1 [blocked] ->
-                # pool1 + norm1 -> conv2/3x3_reduce [blocked for conv2/3x3]): pvhip_maxpool3x3_lrn_conv1x1_c8
-                tails = {(self._fusion[c_]['relu'] if self._fusion[c_]['relu'] is not None else self._fusion[c_]['add']) for c_ in self._c8_out}
-                for pid, lid in self._lrn_pool.items():
-                    if G.nodes[pid]['type'] != 'MaxPool' or pid in self._stem_conv:
-                        continue
-                    src = next((p_ for p_ in G.pred[pid] if G.edges[(p_, pid)]['connection'][3] == 0), None)
-                    readers = list(G.successors(lid))
-                    if src not in tails or len(readers) != 1 or G.edges[(lid, readers[0])]['connection'][3] != 0:
-                        continue
-                    cid = readers[0]
-                    f = self._fusion.get(cid)
-                    if f is None or cid not in self._c8_out or cid in self._siblings or cid in self._fused_away or cid in self._pool_conv \
-                            or (f['act'] is not None and f['act'][0] != 'relu'):
-                        continue
-                    if pool_plugin.lrn_conv_fusable(G.nodes[pid], G.nodes[lid], G.nodes[cid], True):
-                        self._stem_conv[pid] = cid
-                        self._fused_away.update(n_ for n_ in (cid, f['add'], f['relu']) if n_ is not None)
-            if device.conv_f16_c8 == 2 and getattr(conv_plugin, 'SUPPORTS_C8_MODULES', False):
-                self.plan_c8_modules(conv_plugin)
-        self.order_for_locality()
-
-    def plan_c8_modules(self, conv_plugin):
-        """FP16 IRs, second step (default; PVHIP_CONV_F16_C8=1: only the tensors between a 1x1 convolution and the 3x3 / 5x5 behind it): whole inception modules on blocked fp16 tensors.  A channel Concat whose members are
-        fused convolution chains that all (a) read a tensor that WILL be blocked -- the previous module's blocked Concat, a 3x3 MaxPool of
-        one, a 3x3_reduce / 5x5_reduce tensor (`_c8_out`), or the converted entry tensor -- and (b) run on pvhip_conv2d_f16_c8_multi, gets a
-        blocked buffer (`_c8_concat`).  The tensor the first module reads is converted once (`_c8_entry`).  A reader that does not take
-        the blocked layout densifies by itself (device.as_device): only writers need this plan."""
-        G = self.ienet.G
-        pool_plugin, lrn_plugin = (self.ienet.ie.plugins.plugins.get(t) for t in ('MaxPool', 'LRN'))
-        pool_plugin = pool_plugin if hasattr(pool_plugin, 'blocked_ok') else None
-        lrn_plugin = lrn_plugin if hasattr(lrn_plugin, 'blocked_ok') else None
-        src_of = lambda nid: next((p_ for p_ in G.pred[nid] if G.edges[(p_, nid)]['connection'][3] == 0), None)   # noqa: E731
-        blocked = set()
-        for cid in self._c8_out:
-            f = self._fusion[cid]
-            blocked.add(f['relu'] if f['relu'] is not None else f['add'])
-
-        def data_src(cid):
-            pooled = self._pool_conv.get(cid)
-            return src_of(pooled[0]) if pooled is not None else src_of(cid)
-
-        def member_ok(cid, assume=None):
-            f = self._fusion.get(cid)
-            if f is None or cid in self._pre_add or (f['act'] is not None and f['act'][0] != 'relu'):
-                return False
-            pooled = self._pool_conv.get(cid)
-            src = data_src(cid)
-            if src is None or not (src in blocked or src == assume):
-                return False
-            return conv_plugin.c8_module_member_ok(G.nodes[cid], G.nodes[pooled[0]] if pooled is not None else None)
-
-        members_of = {}
-        for cid, f in self._fusion.items():
-            if f['into'] is not None:
-                members_of.setdefault(f['into'][0], []).append(cid)
-        for nid in self.list_schedule:
-            node = G.nodes[nid]
-            if node['type'] == 'MaxPool':
-                src = src_of(nid)
-                folded = G.nodes[self._lrn_pool[nid]] if nid in self._lrn_pool else None
-                # MaxPool.blocked_ok / LRN.blocked_ok: the predicates the plugins themselves decide with at run time
-                if src in blocked and nid not in self._lrn_pool.values() and pool_plugin is not None and pool_plugin.blocked_ok(node, folded):
-                    blocked.add(nid)          # the plugin pools a blocked tensor as it is (a folded pool hands its input on)
-                    if nid in self._lrn_pool:
-                        blocked.add(self._lrn_pool[nid])      # MaxPool + LRN on the blocked tensor: the folded LRN carries it
-            elif node['type'] == 'LRN' and nid in self._lrn_pool and src_of(nid) in blocked and lrn_plugin is not None \
-                    and lrn_plugin.blocked_ok(node, G.nodes[self._lrn_pool[nid]]):
-                blocked.add(self._lrn_pool[nid])              # LRN + MaxPool on a blocked tensor: the folded MaxPool carries it
-            elif node['type'] == 'Concat' and nid in self._concat_direct:
-                members = members_of.get(nid, [])
-                if not members or int(next(iter(node['output'].values()))['dims'][1]) % 16 != 0:
-                    continue          # (a blocked tensor holds whole 16-channel stages; its members write whole 8-channel blocks: c8_module_member_ok)
-                # the first module: the tensor its 1x1 arms read is not blocked yet -- it is converted if that makes the module blocked
-                entry = None
-                srcs = {data_src(m) for m in members}
-                outside = [s_ for s_ in srcs if s_ not in blocked]
-                if len(outside) == 1 and G.nodes[outside[0]]['type'] not in ('Convolution', 'Concat', 'Const', 'Parameter'):
-                    entry = outside[0]
-                    readers = list(G.successors(entry))
-                    folded_pools = {p[0] for p in self._pool_conv.values()}
-                    if not all(r in self._fusion or r in folded_pools for r in readers):
-                        entry = None
-                if all(member_ok(m, assume=entry) for m in members):
-                    self._c8_concat.add(nid)
-                    blocked.add(nid)
-                    if entry is not None:
-                        self._c8_entry.add(entry)
-                        blocked.add(entry)
-
-    def order_for_locality(self):
-        """Another legal order of the same list schedule (round 4; scripts/exp_hoist.py).  The reference's sweep (:218-242) runs the
-        arms of an inception module as 1x1 / 3x3_reduce / 5x5_reduce (here: ONE sibling launch), 3x3, 5x5, pool -> pool_proj.  The
-        arms behind a sibling launch are mutually independent, so:
-          * MaxPool + pool_proj, which reads the SAME module input as the sibling launch (38-205 MB), goes right behind it -- the
-            tensor is then still in L2 / the 256 MB Infinity Cache instead of behind the traffic of the 3x3 and 5x5 arms
-            (its seven launches 0.492 -> 0.444 ms);
-          * the remaining arms run in ascending order of their output (5x5 before 3x3): the largest part of the module's output is
-            written last, closest to the next module's reads (all convolutions 4.98 -> 4.88-4.91 ms, one infer() -2 %).
-        Same launches, same tensors, same bits; PVHIP_SCHEDULE_LOCALITY=0 keeps the reference's order."""
-        if os.environ.get('PVHIP_SCHEDULE_LOCALITY', '1') == '0' or not self._siblings:
-            return
-        G = self.ienet.G
-        order = list(self.task_list)
-        position = {t: i for i, t in enumerate(order)}
-        src_of = lambda cid: next((p_ for p_ in G.pred[cid] if G.edges[(p_, cid)]['connection'][3] == 0), None)   # noqa: E731
-        for lead in sorted(self._siblings, key=position.get):
-            members = [lead] + list(self._siblings[lead])
-            tails = set()
-            for m in members:
-                f = self._fusion[m]
-                tails.add(f['relu'] if f['relu'] is not None else f['add'])
-            arms = [t for t in order if t not in self._fused_away and G.nodes[t]['type'] == 'Convolution' and src_of(t) in tails
-                    and t in self._fusion and t not in self._siblings]
-            pooled = [c for c, (_, psrc) in self._pool_conv.items() if psrc == src_of(lead)]
-            out_elems = lambda t: int(np.prod(next(iter(G.nodes[t]['output'].values()))['dims']))                # noqa: E731
-            arms.sort(key=lambda t: (out_elems(t), position[t]))
-            moved = pooled + arms
-            if not moved:
-                continue
-            # every moved task depends on the lead's launch (or on the lead's own input) and on constants only: any order behind the lead is legal
-            legal = all(all(G.nodes[p_]['type'] == 'Const' or p_ in tails or (t in pooled and p_ == self._pool_conv[t][0]) for p_ in G.pred[t]) for t in moved)
-            if not legal:
-                continue
-            # a moved unit = the convolution with the nodes folded into it (its MaxPool in front, its Add / ReLU behind), so that the
-            # list stays a topological order of the WHOLE graph
-            units = []
-            for t in moved:
-                f = self._fusion[t]
-                units += ([self._pool_conv[t][0]] if t in pooled else []) + [t] + [n_ for n_ in (f['add'], f['relu']) if n_ is not None]
-            gone = set(units)
-            rest = [t for t in order if t not in gone]
-            lead_chain = [lead] + [n_ for m in members for n_ in ((m,) if m != lead else ()) + (self._fusion[m]['add'], self._fusion[m]['relu']) if n_ is not None]
-            at = max(rest.index(n_) for n_ in lead_chain) + 1
-            order = rest[:at] + units + rest[at:]
-        self.task_list = order
+    task_list = property(lambda self: self.plan.order, lambda self, order: setattr(self.plan, 'order', order))
+    # the plan's fields under their old names, read-only (the live objects: callers look into them, tests edit _c8_entry in place)
+    _fusion = property(lambda self: self.plan.fusion)
+    _fused_away = property(lambda self: self.plan.fused_away)
+    _concat_direct = property(lambda self: self.plan.concat_direct)
+    _lrn_pool = property(lambda self: self.plan.lrn_pool)
+    _siblings = property(lambda self: self.plan.siblings)
+    _pool_conv = property(lambda self: self.plan.pool_conv)
+    _pre_add = property(lambda self: self.plan.pre_add)
+    _stem_conv = property(lambda self: self.plan.stem_conv)
+    _c8_out = property(lambda self: self.plan.c8_out)
+    _c8_concat = property(lambda self: self.plan.c8_concat)
+    _c8_entry = property(lambda self: self.plan.c8_entry)
 
     def prepare_inputs_for_task(self, task) -> dict:
         """{sink port: tensor} gathered from the predecessors' output ports, in edge order."""
@@ -990,41 +626,12 @@ class Executable_Network:
         n = max(1, min(int(self.compute_streams), 8 - self.stream_base))
         if (n <= 1 and self.stream_base == 0 and not self.defer_sync) or not all(getattr(sys.modules.get(m.__package__), 'DEVICE_STREAMS', False) for m in registry.values()):
             return None                  # some plugin of the set computes on the host
-        key = (tuple(self.task_list), frozenset(self._fused_away), n)
+        key = (tuple(self.task_list), frozenset(self.plan.fused_away), n)
         plan = self._stream_plans.get(key)
         if plan is not None:
             return plan
-        G = self.ienet.G
-        owner = {}                       # folded-away node -> the dispatched node that writes its tensor
-        for cid, f in self._fusion.items():
-            for nid in (f['add'], f['relu']):
-                if nid is not None:
-                    owner[nid] = cid
-        for lid, pid in self._lrn_pool.items():
-            owner[pid] = lid
-        for lead, sibs in self._siblings.items():
-            for sid in sibs:
-                for nid in (sid, self._fusion[sid]['add'], self._fusion[sid]['relu']):
-                    if nid is not None:
-                        owner[nid] = lead
-        for pid, cid in self._stem_conv.items():       # the 1x1 convolution chain behind MaxPool + LRN: written by the MaxPool's launch
-            for nid in (cid, self._fusion[cid]['add'], self._fusion[cid]['relu']):
-                if nid is not None:
-                    owner[nid] = pid
-
-        folded_adds = {pool_id: src_id for pool_id, src_id in self._pool_conv.values()}      # MaxPools folded into their consumer's fetch
-        folded_adds.update({add_id: src_id for add_id, _, src_id in self._pre_add.values()})  # Adds folded into a padding pass
-
-        def producers(nid):
-            if nid in folded_adds:           # an Add folded into its consumer's fetch: whoever wrote the Add's input
-                return producers(folded_adds[nid])
-            if nid in self._concat_direct and nid in self._fused_away:
-                return [p for pred in G.pred[nid] for p in producers(pred)]
-            if nid in owner:
-                return [owner[nid]]
-            if G.nodes[nid]['type'] in ('Const', 'Parameter'):
-                return []                # uploads are synchronous (or the tensor is already resident)
-            return [nid]
+        G, fp = self.ienet.G, self.plan
+        producers, handed_on = fp.writers, fp.handed_on     # (a MaxPool / Add folded into its consumer's fetch hands its input on)
 
         def prod(dims):
             out = 1
@@ -1033,8 +640,8 @@ class Executable_Network:
             return out
 
         def cost(task, alone=False):     # rough device time of a task in microseconds (ranking only)
-            if not alone and task in self._siblings:
-                return cost(task, True) + sum(cost(s_, True) for s_ in self._siblings[task])
+            if not alone and task in fp.siblings:
+                return cost(task, True) + sum(cost(s_, True) for s_ in fp.siblings[task])
             node = G.nodes[task]
             out = prod(next(iter(node['output'].values()))['dims']) if node.get('output') else 0
             if node['type'] == 'Convolution':
@@ -1045,32 +652,20 @@ class Executable_Network:
             inp = prod(node['input'][0]['dims']) if node.get('input') else 0
             return 4.0 * (inp + out) / 4.5e6
 
-        dispatched = [t for t in self.task_list
-                      if t not in self._fused_away and G.nodes[t]['type'] not in ('Const', 'Parameter')]
+        dispatched = [t for t in fp.order if t not in fp.fused_away and G.nodes[t]['type'] not in ('Const', 'Parameter')]
         position = {t: i for i, t in enumerate(dispatched)}
-
-        def tail(task):                  # graph node whose output port carries the tensor the task writes
-            if task in self._stem_conv:
-                f = self._fusion[self._stem_conv[task]]
-                return f['relu'] if f['relu'] is not None else (f['add'] if f['add'] is not None else self._stem_conv[task])
-            if task in self._lrn_pool:
-                return self._lrn_pool[task]
-            f = self._fusion.get(task)
-            if f is None:
-                return task
-            return f['relu'] if f['relu'] is not None else f['add']
 
         def consumers(nid):              # dispatched tasks that read the tensor of graph node nid
             out = []
             for succ in G.successors(nid):
-                if (succ in self._concat_direct and succ in self._fused_away) or succ in folded_adds:
+                if succ in fp.concat_direct or succ in handed_on:
                     out += [c_ for c_ in consumers(succ) if c_ not in out]     # (a folded Add / MaxPool hands the tensor on)
                 elif succ in position and succ not in out:
                     out.append(succ)
             return sorted(out, key=position.get)
 
         def joins(task):                 # the task writes into a tensor that other tasks write too
-            f = self._fusion.get(task)
+            f = fp.fusion.get(task)
             return f is not None and f['into'] is not None
 
         arm_memo = {}
@@ -1080,7 +675,7 @@ class Executable_Network:
                 total, cur = 0.0, task
                 while True:
                     total += cost(cur)
-                    nxt = consumers(tail(cur))
+                    nxt = consumers(fp.output_of(cur))
                     if joins(cur) or len(nxt) != 1:
                         break
                     srcs = {p for pred in G.pred[nxt[0]] for p in producers(pred)}
@@ -1094,23 +689,23 @@ class Executable_Network:
         for task in dispatched:
             preds = sorted(G.pred[task], key=lambda p: G.edges[(p, task)]['connection'][3])
             primary = next((p for p in preds if producers(p)), None)
-            while primary in folded_adds:        # read through a folded Add / MaxPool: the arms fork at ITS input
-                primary = folded_adds[primary]
+            while primary in handed_on:          # read through a folded Add / MaxPool: the arms fork at ITS input
+                primary = handed_on[primary]
             if primary is None:
                 stream_of[task] = 0
                 finish[task] = cost(task)
             else:
                 if primary not in rank_of:           # heaviest arm first; schedule order breaks ties
                     cons, writers_ = consumers(primary), producers(primary)
-                    if len(writers_) == 1 and writers_[0] in self._siblings:
+                    if len(writers_) == 1 and writers_[0] in fp.siblings:
                         # one launch wrote several tensors: the arms behind ALL of them fan out from its stream
                         cons = []
-                        for t in [writers_[0]] + list(self._siblings[writers_[0]]):
+                        for t in [writers_[0]] + list(fp.siblings[writers_[0]]):
                             if not joins(t):         # (a tensor assembled with others is ranked when its last writer is known)
-                                cons += [c for c in consumers(tail(t)) if c not in cons]
+                                cons += [c for c in consumers(fp.output_of(t)) if c not in cons]
                     arms = sorted(cons, key=lambda t: (-arm_cost(t), position[t]))
                     # the lighter arms behind a sibling launch skip the streams taken by the arms the launch itself forked with
-                    skip = width_of.get(writers_[0], 1) - 1 if (len(writers_) == 1 and writers_[0] in self._siblings) else 0
+                    skip = width_of.get(writers_[0], 1) - 1 if (len(writers_) == 1 and writers_[0] in fp.siblings) else 0
                     rank_of[primary] = {t: (j + skip if j else 0) for j, t in enumerate(arms)}
                 srcs = producers(primary)
                 base = max(srcs, key=lambda p: (finish[p], -position[p]))     # the producer expected to finish last
@@ -1138,7 +733,7 @@ class Executable_Network:
         stream_of, waits, _ = plan
         model, out = CaptureStreamModel(), []
         for task in self.task_list:
-            if task in self._fused_away or task not in stream_of:
+            if task in self.plan.fused_away or task not in stream_of:
                 continue
             for dep in waits[task]:
                 out.append((model.wait(stream_of[task], stream_of[dep]), stream_of[task], stream_of[dep], dep))
@@ -1196,8 +791,9 @@ class Executable_Network:
             epoch = self._open_epoch
             cap_model = CaptureStreamModel() if self.__dict__.get('_recording') else None
             ops = self.__dict__.get('_stream_ops')      # tests: the cross-stream waits of the pass as they are issued
-        for task in self.task_list:
-            if task in self._fused_away:
+        fp = self.plan
+        for task in fp.order:
+            if task in fp.fused_away:
                 continue
             node = G.nodes[task]
             node_type = node['type']
@@ -1218,67 +814,8 @@ class Executable_Network:
                         held.append(relay)
                     else:
                         done_events[dep].wait()
-            pooled_in = self._pool_conv.get(task)
-            if pooled_in is not None:        # the folded MaxPool hands its own input on: the kernel pools while it builds its tile
-                pool_id, _ = pooled_in
-                edge = next(G.edges[(p_, pool_id)]['connection'] for p_ in G.pred[pool_id] if G.edges[(p_, pool_id)]['connection'][3] == 0)
-                out = G.nodes[pool_id]['output']
-                out[next(iter(out))]['data'] = G.nodes[edge[0]]['output'][edge[1]]['data']
-                node['_fuse_pool_in'] = G.nodes[pool_id]
-            else:
-                node.pop('_fuse_pool_in', None)
-            pre_add = self._pre_add.get(task)
-            if pre_add is not None:          # the folded Add hands its data input on; its constant rides in the padding pass
-                add_id, const_id, src_id = pre_add
-                edge = G.edges[(src_id, add_id)]['connection']
-                out = G.nodes[add_id]['output']
-                out[next(iter(out))]['data'] = G.nodes[edge[0]]['output'][edge[1]]['data']
-                node['_pre_add'] = G.nodes[const_id]['output'][0]['data']
-            else:
-                node.pop('_pre_add', None)
+            self._set_hints(task, node)
             inputs = self.prepare_inputs_for_task(task) if 'input' in node else {}
-            if node_type in ('Convolution', 'MatMul'):
-                node['_f16_mfma'] = bool(getattr(self.ienet, 'f16_mfma', False))
-            fusion = self._fusion.get(task)
-            node.pop('_out_into', None)
-            if fusion is not None:
-                node['_fuse_bias'] = G.nodes[fusion['bias']]['output'][0]['data']
-                node['_fuse_act'] = fusion['act']
-                if fusion['into'] is not None:
-                    node['_out_into'] = (self._concat_buffer(fusion['into'][0]), fusion['into'][1])
-            else:
-                node.pop('_fuse_bias', None)
-                node.pop('_fuse_act', None)
-            sibs = self._siblings.get(task)
-            if task in self._c8_out:
-                node['_out_c8'] = True
-            else:
-                node.pop('_out_c8', None)
-            if sibs:
-                node['_siblings'] = []
-                for sid in sibs:
-                    sf = self._fusion[sid]
-                    node['_siblings'].append({'node': G.nodes[sid], 'inputs': self.prepare_inputs_for_task(sid),
-                                              'bias': G.nodes[sf['bias']]['output'][0]['data'],
-                                              'into': (self._concat_buffer(sf['into'][0]), sf['into'][1]) if sf['into'] is not None else None,
-                                              'c8': sid in self._c8_out})
-            else:
-                node.pop('_siblings', None)
-            pooled = self._lrn_pool.get(task)        # the node folded into this one: a MaxPool behind an LRN, or an LRN behind a MaxPool
-            fuse_key = '_fuse_pool' if node_type == 'LRN' else '_fuse_lrn'
-            if pooled is not None:
-                node[fuse_key] = G.nodes[pooled]
-            else:
-                node.pop(fuse_key, None)
-            stem_conv = self._stem_conv.get(task)        # the 1x1 convolution behind MaxPool + LRN, in the same launch
-            if stem_conv is not None:
-                sf = self._fusion[stem_conv]
-                wsrc = next(G.edges[(p_, stem_conv)]['connection'] for p_ in G.pred[stem_conv] if G.edges[(p_, stem_conv)]['connection'][3] == 1)
-                node['_fuse_conv'] = {'node': G.nodes[stem_conv], 'w': G.nodes[wsrc[0]]['output'][wsrc[1]]['data'],
-                                      'bias': G.nodes[sf['bias']]['output'][0]['data'], 'act': sf['act'],
-                                      'c8': bool(getattr(self.ienet, 'f16_mfma', False))}       # FP16 IRs: on blocked fp16 tensors
-            else:
-                node.pop('_fuse_conv', None)
             plugin = registry.get(node_type)
             if plugin is None:
                 print("ERROR: Operation '{}' (node={}) is not supported.".format(node_type, node['name']))
@@ -1308,35 +845,18 @@ class Executable_Network:
                 common_def.compare_results(node['name'], next(iter(res.values())), self.expected_result, disp_results=False,
                                            rtol=self.expected_rtol)
             if len(res) > 0:
-                if self._c8_entry and (task in self._c8_entry or (pooled is not None and pooled in self._c8_entry)):
+                if fp.c8_entry and (task in fp.c8_entry or fp.lrn_pool.get(task) in fp.c8_entry):
                     # the tensor the first blocked module reads: converted once, every reader gets the blocked form
                     from . import device as dev_
                     res = {port_id: (dev_.BlockedHalf.from_dense(data) if isinstance(data, dev_.DeviceTensor) and data.ndim == 4 else data)
                            for port_id, data in res.items()}
                 for port_id, data in res.items():
                     node['output'][port_id]['data'] = data
-                if fusion is not None:
-                    fused = next(iter(res.values()))
-                    for nid in (fusion['add'], fusion['relu']):
-                        if nid is not None:
-                            out = G.nodes[nid]['output']
-                            out[next(iter(out))]['data'] = fused
-                if sibs:                         # the launch wrote the siblings' tensors too
-                    for sid, tensor in zip(sibs, node.pop('_sibling_out')):
-                        chain = [sid, self._fusion[sid]['add'], self._fusion[sid]['relu']]
-                        for nid in chain:
-                            if nid is not None:
-                                out = G.nodes[nid]['output']
-                                out[next(iter(out))]['data'] = tensor
-                if pooled is not None:           # the folded node's port carries the tensor
-                    out = G.nodes[pooled]['output']
-                    out[next(iter(out))]['data'] = next(iter(res.values()))
-                if stem_conv is not None:        # ... and so do the ports of the folded convolution chain (what the launch returned IS its output;
-                    sf = self._fusion[stem_conv]  # the pooled and the normalised tensor do not exist: their ports hold it only as a placeholder)
-                    for nid in (stem_conv, sf['add'], sf['relu']):
-                        if nid is not None:
-                            out = G.nodes[nid]['output']
-                            out[next(iter(out))]['data'] = next(iter(res.values()))
+                receivers = fp.receivers.get(task)
+                if receivers:                    # the ports of the nodes folded into the launch (a sibling launch: of its members too)
+                    outs = [next(iter(res.values()))] + (list(node.pop('_sibling_out')) if task in fp.siblings else [])
+                    for k, nid in receivers:
+                        self._set_port(nid, outs[k])
         if open_run is not None:
             self._close_run(open_run)
         if plan is not None:
@@ -1358,6 +878,50 @@ class Executable_Network:
                 device.select_stream(0)
                 device.synchronize()
                 device.pool_epoch_end(epoch)
+
+    def _set_port(self, nid, tensor):
+        out = self.ienet.G.nodes[nid]['output']
+        out[next(iter(out))]['data'] = tensor
+
+    def _set_hints(self, task, node):
+        """Clear every hint (HINT_KEYS) on the task's node dict and set the task's own, on every pass (Concat buffers and port tensors change
+        from pass to pass).  A MaxPool / Add folded into the task's fetch hands its input on: its port takes that tensor first."""
+        G, fp = self.ienet.G, self.plan
+        for key in fusion_plan.HINT_KEYS:
+            node.pop(key, None)
+        pooled_in, pre_add = fp.pool_conv.get(task), fp.pre_add.get(task)
+        for folded in (pooled_in, pre_add):
+            if folded is not None:
+                edge = G.edges[(fp.handed_on[folded[0]], folded[0])]['connection']
+                self._set_port(folded[0], G.nodes[edge[0]]['output'][edge[1]]['data'])
+        if pooled_in is not None:        # the kernel pools while it builds its tile
+            node['_fuse_pool_in'] = G.nodes[pooled_in[0]]
+        if pre_add is not None:          # the Add's constant rides in the padding pass
+            node['_pre_add'] = G.nodes[pre_add[1]]['output'][0]['data']
+        if node['type'] in ('Convolution', 'MatMul'):
+            node['_f16_mfma'] = fp.f16
+        fusion = fp.fusion.get(task)
+        if fusion is not None:
+            node['_fuse_bias'] = G.nodes[fusion['bias']]['output'][0]['data']
+            node['_fuse_act'] = fusion['act']
+            if fusion['into'] is not None:
+                node['_out_into'] = (self._concat_buffer(fusion['into'][0]), fusion['into'][1])
+        if task in fp.c8_out:
+            node['_out_c8'] = True
+        for sid in fp.siblings.get(task, ()):
+            sf = fp.fusion[sid]
+            node.setdefault('_siblings', []).append({'node': G.nodes[sid], 'inputs': self.prepare_inputs_for_task(sid),
+                                                     'bias': G.nodes[sf['bias']]['output'][0]['data'], 'c8': sid in fp.c8_out,
+                                                     'into': (self._concat_buffer(sf['into'][0]), sf['into'][1]) if sf['into'] is not None else None})
+        folded = fp.lrn_pool.get(task)   # the node folded into this one: a MaxPool behind an LRN, or an LRN behind a MaxPool
+        if folded is not None:
+            node['_fuse_pool' if node['type'] == 'LRN' else '_fuse_lrn'] = G.nodes[folded]
+        stem_conv = fp.stem_conv.get(task)   # the 1x1 convolution behind MaxPool + LRN, in the same launch
+        if stem_conv is not None:
+            sf = fp.fusion[stem_conv]
+            wsrc = next(G.edges[(p_, stem_conv)]['connection'] for p_ in G.pred[stem_conv] if G.edges[(p_, stem_conv)]['connection'][3] == 1)
+            node['_fuse_conv'] = {'node': G.nodes[stem_conv], 'w': G.nodes[wsrc[0]]['output'][wsrc[1]]['data'],     # c8: FP16 IRs, blocked
+                                  'bias': G.nodes[sf['bias']]['output'][0]['data'], 'act': sf['act'], 'c8': fp.f16}
 
     # ---- hipGraph replay of a whole pass (what the reference's run_tasks loop, :259-292, becomes: one launch call)
     def capture_graph(self, inputs: dict, warm: int = 2, streams=1):
@@ -1504,7 +1068,7 @@ class Executable_Network:
         if node.get('_buf_serial') != self._infer_serial:
             dims = node['output'][port]['dims']
             # FP16 IRs, module form: the Concat's buffer is fp16 blocked by eight channels and every member writes its range of it
-            node['output'][port]['data'] = device.BlockedHalf(dims) if cat_id in self._c8_concat else device.DeviceTensor.empty(dims)
+            node['output'][port]['data'] = device.BlockedHalf(dims) if cat_id in self.plan.c8_concat else device.DeviceTensor.empty(dims)
             node['_buf_serial'] = self._infer_serial
         return node['output'][port]['data']
 
@@ -1551,28 +1115,12 @@ class Executable_Network:
         for node_name, val in inputs.items():
             if node_name in by_name:
                 G.nodes[by_name[node_name]]['param'] = val
-        full, fa = self.task_list, self._fused_away
+        full = self.plan
+        self.plan = full.restricted(needed, set(targets))
         try:
-            self.task_list = [t for t in full if t in needed]
-            # a fused chain must be wholly inside the sub-graph, or be run unfused
-            keep = {}
-            for cid, f in self._fusion.items():
-                chain = [cid, f['add']] + ([f['relu']] if f['relu'] is not None else [])
-                if all(c in needed for c in chain):
-                    keep[cid] = dict(f, into=None)      # Concat elimination is not applied to sub-graphs
-            saved = (self._fusion, self._fused_away, self._concat_direct, self._lrn_pool, self._siblings, self._pool_conv, self._pre_add)
-            self._siblings, self._pool_conv, self._pre_add = {}, {}, {}      # sub-graph runs launch every convolution (MaxPool, Add) on its own
-            self._fusion = {c: f for c, f in keep.items()}
-            self._fused_away = {n for f in self._fusion.values() for n in (f['add'], f['relu']) if n is not None}
-            self._concat_direct = {}
-            self._lrn_pool = {l: p_ for l, p_ in self._lrn_pool.items() if l in needed and p_ in needed and l not in targets}
-            self._fused_away |= set(self._lrn_pool.values())
-            try:
-                self.run_tasks(False)
-            finally:
-                self._fusion, self._fused_away, self._concat_direct, self._lrn_pool, self._siblings, self._pool_conv, self._pre_add = saved
+            self.run_tasks(False)
         finally:
-            self.task_list = full
+            self.plan = full
         out = {}
         for name, t in zip(node_names, targets):
             ports = G.nodes[t]['output']

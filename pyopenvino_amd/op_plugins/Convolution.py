@@ -657,7 +657,7 @@ def compute(node: dict, inputs: dict = None, kernel_type: str = 'hip', debug: bo
         blocked_into = (into_ is not None and isinstance(into_[0], dev.BlockedHalf)) or \
             any(sib.get('into') is not None and isinstance(sib['into'][0], dev.BlockedHalf) for sib in sibs_)
         if blocked_into and not isinstance(inputs[0], dev.BlockedHalf):
-            # plan_c8_modules gave this launch the module's blocked Concat buffer, but a producer in front of it handed over a dense tensor
+            # the fusion plan (_c8_modules) gave this launch the module's blocked Concat buffer, but a producer in front of it handed over a dense tensor
             # after all (a kernel refused its size at launch): convert it here -- the values the reference holds (float16) -- and go on
             inputs = dict(inputs)
             inputs[0] = dev.BlockedHalf.from_dense(dev.as_device(inputs[0]))
@@ -687,7 +687,7 @@ def compute(node: dict, inputs: dict = None, kernel_type: str = 'hip', debug: bo
         y, node['_sibling_out'] = outs[0], outs[1:]
     elif (into is not None and isinstance(into[0], dev.BlockedHalf)) or any(sib.get('into') is not None and isinstance(sib['into'][0], dev.BlockedHalf)
                                                                             for sib in siblings or ()):
-        raise RuntimeError('{}: a blocked fp16 Concat buffer, but this launch cannot write it (plan_c8_modules promised a blocked input and '
+        raise RuntimeError('{}: a blocked fp16 Concat buffer, but this launch cannot write it (the fusion plan promised a blocked input and '
                            'pvhip_conv2d_f16_c8_multi)'.format(node.get('name')))
     elif reader_path:
         y = launch_c8(node, inputs[0], w, bias=bias, act=node.get('_fuse_act'), into=into)

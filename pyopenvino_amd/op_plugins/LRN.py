@@ -47,7 +47,7 @@ def pool_fusable(node: dict, pool_node: dict) -> bool:
 def blocked_ok(node: dict, pool_node: dict) -> bool:
     """True when compute() runs LRN + MaxPool (node['_fuse_pool'] = pool_node) on a dev.BlockedHalf input as it is and returns a
     dev.BlockedHalf (FP16 IRs; IR attributes and port dims, no device needed).  The ONE predicate of the plan
-    (Executable_Network.plan_c8_modules) and of compute()."""
+    (fusion_plan._c8_modules) and of compute()."""
     try:
         if pool_node is None or int(node['data']['size']) != 5:
             return False

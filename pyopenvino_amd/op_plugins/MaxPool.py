@@ -86,7 +86,7 @@ def lrn_conv_fusable(node: dict, lrn_node: dict, conv_node: dict, f16: bool = Fa
 def blocked_ok(node: dict, lrn_node: dict = None) -> bool:
     """True when compute() pools a dev.BlockedHalf input of this node as it is and returns a dev.BlockedHalf (FP16 IRs; IR attributes
     and port dims, no device needed): a 3x3 window with a non-empty output, and an LRN folded behind it only over five channels.
-    The ONE predicate of the plan (Executable_Network.plan_c8_modules) and of compute(): what the plan calls blocked IS blocked."""
+    The ONE predicate of the plan (fusion_plan._c8_modules) and of compute(): what the plan calls blocked IS blocked."""
     try:
         attrs = node['data']
         if tuple(common_def.string_to_tuple(attrs['kernel'])) != (3, 3):
