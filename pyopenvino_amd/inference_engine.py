@@ -16,9 +16,12 @@ Differences from the reference, all outside the numeric path:
   * ``infer`` can shard the batch across ranks (one process per GPU): every rank runs the unchanged
     scheduler on its slice and the Result plugin all-gathers the Result tensors.
 """
+import contextlib
+import copy
+import ctypes
 import importlib
 import os
-from ctypes import byref, c_void_p as ctypes_void_p
+import pickle
 import pkgutil
 import sys
 import time
@@ -27,7 +30,8 @@ import xml.etree.ElementTree as et
 import networkx as nx
 import numpy as np
 
-from . import common_def, fusion_plan
+from . import common_def, device, fusion_plan, stream_plan
+from .stream_plan import CaptureStreamModel
 
 DEFAULT_PLUGIN_PACKAGE = 'pyopenvino_amd.op_plugins'
 
@@ -358,7 +362,6 @@ class InferRequest:
         if self._in_flight:
             raise RuntimeError('request {} is still in flight: wait() first'.format(self.index))
         ex = self.runner
-        G = ex.ienet.G
         inputs = ex._stage_host_inputs(inputs)
         # The same device-resident tensors as the last calls: the pass is replayed from this request's own recording (one call
         # instead of ~100 dispatches; every request records its own pass on its own stream and keeps its own tensors, so the
@@ -366,22 +369,10 @@ class InferRequest:
         self._replayed = ex._graph_for(inputs, gathers_later=True)
         if self._replayed is not None:
             ex.launch_graph(self._replayed)
-            self._in_flight = True
-            return
-        by_name = {G.nodes[n]['name']: n for n in G.nodes}
-        for node_name, val in inputs.items():
-            if node_name in by_name:
-                G.nodes[by_name[node_name]]['param'] = val
-        for nid, _ in ex.ienet.find_node_by_type('Result'):
-            G.nodes[nid]['comm'] = None          # the shards are gathered in wait(): one collective at a time, on stream 0
-            G.nodes[nid]['_async'] = True        # keep the result on the device: wait() reads it back
-        ex.defer_sync = True
-        try:
-            ex.run_tasks(False)
-        finally:
-            ex.defer_sync = False
-            for nid, _ in ex.ienet.find_node_by_type('Result'):
-                G.nodes[nid].pop('_async', None)
+        else:
+            ex._bind_inputs(inputs)
+            with ex._results_on_device():        # the shards are gathered in wait(): one collective at a time, on stream 0
+                ex.run_tasks(False)
         self._in_flight = True
 
     def wait(self) -> dict:
@@ -390,27 +381,10 @@ class InferRequest:
         ex.wait_done()
         self._in_flight = False
         out = {}
-        comm = self.owner.comm
-        replayed, self._replayed = self.__dict__.get('_replayed'), None
+        replayed, self._replayed = self._replayed, None
         for nid, name in ex.ienet.find_node_by_type('Result'):
             value = replayed['results'][name] if replayed is not None else G.nodes[nid]['result']
-            if hasattr(value, 'numpy') and not isinstance(value, np.ndarray):
-                from . import device
-                # The copy to the host synchronises the stream it is issued on: use one that has nothing else queued
-                # (this request's own have drained; another request's have not).
-                # With sharded batches the gather and the copy go to the copy stream (index 8), which no request computes on:
-                # every rank waits for its requests in the same order, so the collectives of the one communicator
-                # are issued in the same order everywhere and never overlap each other.
-                gathers = comm is not None and comm.world > 1
-                device.select_stream(device.COPY_STREAM if gathers else ex.stream_base)
-                if gathers:
-                    value = comm.allgather_rows(value)
-                value = value.numpy() if hasattr(value, 'numpy') and not isinstance(value, np.ndarray) else np.asarray(value)
-                device.select_stream(0)
-            elif comm is not None and comm.world > 1:
-                value = comm.allgather_rows(value)
-            G.nodes[nid]['result'] = value
-            out[name] = value
+            G.nodes[nid]['result'] = out[name] = ex._read_back(value, self.owner.comm)
         return out
 
     def infer(self, inputs: dict) -> dict:
@@ -430,51 +404,17 @@ class InferRequest:
         return self.runner._host_input(name)['host']
 
 
-class CaptureStreamModel:
-    """What ROCm 7.2's runtime keeps per stream while a multi-stream hipGraph recording is open, restated from the disassembly of
-    its hipStreamWaitEvent / Stream::EndCapture (libamdhip64.so.7.2.70200 +0x2f63b9 / +0x2df7f0; profiles/r04_capture.md).
-
-    When a stream W that is not the origin of the capture waits for an event recorded on stream E, and E's current parent is not
-    W, the runtime sets parent(W) = E and appends W to E's list of parallel streams (once) -- on EVERY such wait, not only on the
-    one that makes W join.  hipStreamEndCapture then walks those lists recursively from the origin and clears them on the way
-    back.  The parent test stops a 2-cycle only while E's parent still IS W; after E has waited for a third stream in between,
-    W <-> E (or a longer ring) closes, the walk never returns and the process dies of stack overflow inside hipStreamEndCapture
-    (what LESSONS.md lesson 30 filed as "crashes inside the runtime").  The origin never registers anywhere, so a dependency that
-    would close a ring is RELAYED through it: the origin waits for E's event, records a fresh one, W waits for that."""
-
-    def __init__(self):
-        self.parent = {}        # non-origin stream -> stream of the event it last registered under
-        self.lists = {}         # stream -> streams in its parallel-capture list
-
-    def _reaches(self, src, dst):
-        todo, seen = [src], set()
-        while todo:
-            cur = todo.pop()
-            if cur == dst:
-                return True
-            if cur not in seen:
-                seen.add(cur)
-                todo.extend(self.lists.get(cur, ()))
-        return False
-
-    def wait(self, waiter: int, event_stream: int) -> str:
-        """Stream `waiter` is about to wait for an event recorded on `event_stream` (0 = the origin).  'plain': issue the wait;
-        'relay': it would close a ring in the runtime's lists -- go through the origin (the bookkeeping of the relay's own two
-        waits is applied here)."""
-        if waiter == 0 or waiter == event_stream:
-            return 'plain'                              # the origin registers nowhere
-        if self.parent.get(event_stream) == waiter:
-            return 'plain'                              # the runtime's own test: nothing is registered
-        if event_stream != 0 and self._reaches(waiter, event_stream):
-            self.parent[waiter] = 0                     # relayed: origin waits (registers nothing), waiter waits for the origin's event
-            self.lists.setdefault(0, set()).add(waiter)
-            return 'relay'
-        self.parent[waiter] = event_stream
-        self.lists.setdefault(event_stream, set()).add(waiter)
-        return 'plain'
-
-    def has_ring(self) -> bool:
-        return any(self._reaches(w, s) for s, ws in self.lists.items() for w in ws)
+@contextlib.contextmanager
+def _overridden(obj, **values):
+    """Set these attributes of `obj` for the block and restore their old values after it."""
+    saved = {name: getattr(obj, name) for name in values}
+    for name, value in values.items():
+        setattr(obj, name, value)
+    try:
+        yield
+    finally:
+        for name, value in saved.items():
+            setattr(obj, name, value)
 
 
 class Executable_Network:
@@ -501,14 +441,32 @@ class Executable_Network:
         self.compute_streams = int(os.environ.get('PVHIP_STREAMS', '4'))
         self.stream_base = 0            # first compute stream of this network (several requests in flight use disjoint sets)
         self.defer_sync = False         # True: run_tasks returns after the device-side join; the caller waits
-        self._stream_plans = {}
+        self.requests = []              # InferRequest per request in flight (create_requests); a request's own runner has none
+        self._plan_serial = 0           # counts plan_fusion() calls: a captured pass is a pass of ONE plan
+        self._stream_plans = {}         # {(task order, fused-away set, streams): StreamPlan}
+        self._recording = False         # a hipGraph capture is open (capture_graph): cross-stream waits go through CaptureStreamModel
+        # untimed events that order the streams: spare ones, and those of the pass in flight -- reused only after that pass has been
+        # waited for (wait_done, or the start of the next pass, which follows a synchronous one)
+        self._order_events, self._events_in_flight = [], []
+        self._event_pool = []           # timed events for the device_timing brackets
+        self._pending = None            # (allocation epoch or None, event) of a pass issued without a host wait: wait_done() ends it
+        self._host_inputs = {}          # {input name: page-locked staging of it} (_host_input)
+        self._graph = None              # the recorded pass (capture_graph): {'handle', 'inputs', 'keep', 'results', 'by_hand'}
+        self._auto_graph = {'key': None, 'seen': 0, 'failed': False, 'captured': False}     # infer()'s own recording (_graph_for)
+        self._auto_graph_busy = False   # _graph_for is recording
+        registry, G = ienetwork.ie.plugins.plugins, ienetwork.G
+        # every plugin package of the set keeps its tensors on the device and computes on the current stream: passes fork over streams
+        self._device_streams = all(getattr(sys.modules.get(m.__package__), 'DEVICE_STREAMS', False) for m in registry.values())
+        # every layer type of the network says its compute() can be recorded (a foreign plugin set does not: its pass stays eager)
+        self._graph_safe = all(getattr(registry.get(G.nodes[n]['type']), 'GRAPH_CAPTURE_SAFE', False) for n in G.nodes)
+
+    _stream_ops = None                  # tests: a list that collects the cross-stream waits of a pass as they are issued
 
     def create_requests(self, count: int):
         """Request 0 runs on this network's own graph; the others on copies of it made now, before anything has been
         uploaded (constants are uploaded and weights packed per request: the IRs' weights are tens of MB).  The
         compute streams (`compute_streams`, 4: what the device's hardware queues take without multiplexing -- more
         streams than that serialise behind each other's event waits) are split evenly between the requests."""
-        import copy
         if count > 8:
             raise ValueError('at most 8 requests (one compute stream each)')
         # A graph that has already been loaded or inferred holds device tensors (cached constants, packed weights, node
@@ -528,7 +486,6 @@ class Executable_Network:
             runner = Executable_Network(twin)
             runner.fuse_epilogues = self.fuse_epilogues
             runner.schedule_tasks()
-            runner.requests = []
             self.requests.append(InferRequest(self, runner, i))
         if count > 1:
             for i, req in enumerate(self.requests):
@@ -540,7 +497,7 @@ class Executable_Network:
         infer uploads and packs again.  A captured hipGraph holds raw addresses of exactly these tensors (packed weights, cached
         constants, Concat buffers): it goes first, or a later infer_graph() would replay kernels over freed or reused pool blocks."""
         self.release_graph()
-        self.__dict__.pop('_host_inputs', None)     # page-locked buffers go back once the caller holds no view of them
+        self._host_inputs = {}                      # page-locked buffers go back once the caller holds no view of them
         G = self.ienet.G
         for nid in G.nodes:
             node = G.nodes[nid]
@@ -585,7 +542,7 @@ class Executable_Network:
 
     def plan_fusion(self):
         """(Re)build the fusion plan of the list schedule for the current flags (fusion_plan.build)."""
-        self._plan_serial = self.__dict__.get('_plan_serial', 0) + 1      # a captured pass is a pass of ONE plan
+        self._plan_serial += 1
         self.plan = fusion_plan.build(self.ienet.G, self.list_schedule, self.ienet.ie.plugins.plugins, self.fuse_epilogues,
                                       self.fuse_siblings, bool(getattr(self.ienet, 'f16_mfma', False)))
 
@@ -613,185 +570,106 @@ class Executable_Network:
         return inputs
 
     def plan_streams(self):
-        """Static stream assignment for the current task list (the reference's list scheduler
-        runs the branches of a module one after the other, :259-292).  The consumers of a tensor are ranked by
-        the estimated time of the arm each one starts (the chain of single-consumer nodes behind it); the
-        heaviest stays on the stream the tensor was produced on, the others go to the next streams, so the arms
-        of a fan-out run side by side.  A tensor assembled by several producers (an eliminated Concat) counts as
-        produced on the stream of the producer expected to finish last.  Both rules keep the critical path of
-        consecutive modules on ONE stream: its kernels follow each other without waiting for a cross-stream event
-        (measured 25-40 us per join), which only the lighter arms pay.  Returns (stream of task, tasks to wait
-        for, tasks that must record an event) or None when not applicable."""
-        registry = self.ienet.ie.plugins.plugins
+        """The stream plan of the current task list over this network's streams (stream_plan.build): a StreamPlan (stream of task,
+        tasks to wait for, tasks that must record an event), or None when not applicable."""
         n = max(1, min(int(self.compute_streams), 8 - self.stream_base))
-        if (n <= 1 and self.stream_base == 0 and not self.defer_sync) or not all(getattr(sys.modules.get(m.__package__), 'DEVICE_STREAMS', False) for m in registry.values()):
-            return None                  # some plugin of the set computes on the host
+        if (n <= 1 and self.stream_base == 0 and not self.defer_sync) or not self._device_streams:
+            return None                  # one stream and a synchronous pass, or some plugin of the set computes on the host
         key = (tuple(self.task_list), frozenset(self.plan.fused_away), n)
-        plan = self._stream_plans.get(key)
-        if plan is not None:
-            return plan
-        G, fp = self.ienet.G, self.plan
-        producers, handed_on = fp.writers, fp.handed_on     # (a MaxPool / Add folded into its consumer's fetch hands its input on)
-
-        def prod(dims):
-            out = 1
-            for d in dims:
-                out *= int(d)
-            return out
-
-        def cost(task, alone=False):     # rough device time of a task in microseconds (ranking only)
-            if not alone and task in fp.siblings:
-                return cost(task, True) + sum(cost(s_, True) for s_ in fp.siblings[task])
-            node = G.nodes[task]
-            out = prod(next(iter(node['output'].values()))['dims']) if node.get('output') else 0
-            if node['type'] == 'Convolution':
-                k = node['input'][1]['dims']
-                return 2.0 * out * k[1] * k[2] * k[3] / 100e6 + 4.0 * out / 4.5e6
-            if node['type'] == 'MatMul':
-                return 2.0 * out * node['input'][0]['dims'][-1] / 20e6
-            inp = prod(node['input'][0]['dims']) if node.get('input') else 0
-            return 4.0 * (inp + out) / 4.5e6
-
-        dispatched = [t for t in fp.order if t not in fp.fused_away and G.nodes[t]['type'] not in ('Const', 'Parameter')]
-        position = {t: i for i, t in enumerate(dispatched)}
-
-        def consumers(nid):              # dispatched tasks that read the tensor of graph node nid
-            out = []
-            for succ in G.successors(nid):
-                if succ in fp.concat_direct or succ in handed_on:
-                    out += [c_ for c_ in consumers(succ) if c_ not in out]     # (a folded Add / MaxPool hands the tensor on)
-                elif succ in position and succ not in out:
-                    out.append(succ)
-            return sorted(out, key=position.get)
-
-        def joins(task):                 # the task writes into a tensor that other tasks write too
-            f = fp.fusion.get(task)
-            return f is not None and f['into'] is not None
-
-        arm_memo = {}
-
-        def arm_cost(task):              # the task plus the chain of sole consumers behind it, up to the next fork / join
-            if task not in arm_memo:
-                total, cur = 0.0, task
-                while True:
-                    total += cost(cur)
-                    nxt = consumers(fp.output_of(cur))
-                    if joins(cur) or len(nxt) != 1:
-                        break
-                    srcs = {p for pred in G.pred[nxt[0]] for p in producers(pred)}
-                    if srcs != {cur}:
-                        break
-                    cur = nxt[0]
-                arm_memo[task] = total
-            return arm_memo[task]
-
-        stream_of, waits, records, rank_of, finish, width_of = {}, {}, set(), {}, {}, {}
-        for task in dispatched:
-            preds = sorted(G.pred[task], key=lambda p: G.edges[(p, task)]['connection'][3])
-            primary = next((p for p in preds if producers(p)), None)
-            while primary in handed_on:          # read through a folded Add / MaxPool: the arms fork at ITS input
-                primary = handed_on[primary]
-            if primary is None:
-                stream_of[task] = 0
-                finish[task] = cost(task)
-            else:
-                if primary not in rank_of:           # heaviest arm first; schedule order breaks ties
-                    cons, writers_ = consumers(primary), producers(primary)
-                    if len(writers_) == 1 and writers_[0] in fp.siblings:
-                        # one launch wrote several tensors: the arms behind ALL of them fan out from its stream
-                        cons = []
-                        for t in [writers_[0]] + list(fp.siblings[writers_[0]]):
-                            if not joins(t):         # (a tensor assembled with others is ranked when its last writer is known)
-                                cons += [c for c in consumers(fp.output_of(t)) if c not in cons]
-                    arms = sorted(cons, key=lambda t: (-arm_cost(t), position[t]))
-                    # the lighter arms behind a sibling launch skip the streams taken by the arms the launch itself forked with
-                    skip = width_of.get(writers_[0], 1) - 1 if (len(writers_) == 1 and writers_[0] in fp.siblings) else 0
-                    rank_of[primary] = {t: (j + skip if j else 0) for j, t in enumerate(arms)}
-                srcs = producers(primary)
-                base = max(srcs, key=lambda p: (finish[p], -position[p]))     # the producer expected to finish last
-                stream_of[task] = (stream_of[base] + rank_of[primary].get(task, 0)) % n
-                width_of[task] = len(rank_of[primary])
-                finish[task] = finish[base] + cost(task)
-            deps = []
-            for pred in preds:
-                for p in producers(pred):
-                    if stream_of[p] != stream_of[task] and p not in deps:
-                        deps.append(p)
-            waits[task] = deps
-            records.update(deps)
-        plan = (stream_of, waits, records)
-        self._stream_plans[key] = plan
-        return plan
+        if key not in self._stream_plans:
+            self._stream_plans[key] = stream_plan.build(self.ienet.G, self.plan, n)
+        return self._stream_plans[key]
 
     def recorded_waits(self):
-        """The cross-stream waits a RECORDING of the current plan makes, in dispatch order, as (how, waiting stream, event's stream,
-        producer task) with how = 'plain' | 'relay' (CaptureStreamModel) -- what _dispatch_tasks issues while a capture is open,
-        computed from the plan alone (no device)."""
-        plan = self.plan_streams()
-        if plan is None:
-            return [], CaptureStreamModel()
-        stream_of, waits, _ = plan
-        model, out = CaptureStreamModel(), []
-        for task in self.task_list:
-            if task in self.plan.fused_away or task not in stream_of:
-                continue
-            for dep in waits[task]:
-                out.append((model.wait(stream_of[task], stream_of[dep]), stream_of[task], stream_of[dep], dep))
-        return out, model
+        """stream_plan.recorded_waits of the current plans: what _dispatch_tasks issues while a capture is open."""
+        return stream_plan.recorded_waits(self.plan_streams(), self.plan)
 
     def recording_rings(self) -> bool:
         """True when a recording of the current plan would leave a ring in the runtime's parallel-stream lists."""
         return self.recorded_waits()[1].has_ring()
 
-    def run_tasks(self, verbose: bool = False):
+    def _bind_inputs(self, inputs: dict) -> dict:
+        """Hand each input to the Parameter of that name (other names are ignored).  Returns {node name: node id}."""
         G = self.ienet.G
-        registry = self.ienet.ie.plugins.plugins
-        times = []
-        open_run = None
+        by_name = {G.nodes[n]['name']: n for n in G.nodes}
+        for node_name, val in inputs.items():
+            if node_name in by_name:
+                G.nodes[by_name[node_name]]['param'] = val
+        return by_name
+
+    @contextlib.contextmanager
+    def _results_on_device(self):
+        """The passes run inside keep their Results on the device, ungathered (the caller reads them back: _read_back), and
+        run_tasks returns after the device-side join, without a host wait (wait_done)."""
+        G, results = self.ienet.G, self.ienet.find_node_by_type('Result')
+        for nid, _ in results:
+            G.nodes[nid]['comm'] = None
+            G.nodes[nid]['_async'] = True
+        self.defer_sync = True
+        try:
+            yield
+        finally:
+            self.defer_sync = False
+            for nid, _ in results:
+                G.nodes[nid].pop('_async', None)
+
+    def _read_back(self, value, comm=None):
+        """A Result as infer() returns it: a device tensor is copied to the host, gathered over the ranks first when the batch is sharded.
+        The copy synchronises the stream it is issued on: use one that has nothing else queued (this network's own have drained;
+        another request's have not).  With sharded batches the gather and the copy go to the copy stream, which no request computes
+        on: every rank waits for its requests in the same order, so the collectives of the one communicator are issued in the same
+        order everywhere and never overlap each other."""
+        gathers = comm is not None and comm.world > 1
+        if not (hasattr(value, 'numpy') and not isinstance(value, np.ndarray)):
+            return comm.allgather_rows(value) if gathers else value
+        device.select_stream(device.COPY_STREAM if gathers else self.stream_base)
+        value = np.asarray(comm.allgather_rows(value) if gathers else value)
+        device.select_stream(0)
+        return value
+
+    def _order_event(self):
+        """An untimed event for the pass being issued (it orders the streams); it is recorded again once that pass has been waited for."""
+        event = self._order_events.pop() if self._order_events else device.Event(timed=False)
+        self._events_in_flight.append(event)
+        return event
+
+    def run_tasks(self, verbose: bool = False):
         self._infer_serial += 1
         self._recycle_events()
         plan = self.plan_streams()
+        epoch = None
         if plan is not None:
-            from . import device
-            stream_of, waits, records = plan
-            done_events, spare, current = {}, self.__dict__.setdefault('_order_events', []), 0
-            held = self.__dict__.setdefault('_events_in_flight', [])
-            spare.extend(held)           # the pass that recorded them has been waited for by now
-            del held[:]
-            base = self.stream_base
+            self._order_events += self._events_in_flight     # the pass that recorded them has been waited for by now
+            self._events_in_flight = []
             # blocks allocated during this pass and freed before it has finished on the device (workspaces) are
             # parked until it has; the previous pass's outputs, replaced as we go, are reusable at once
-            epoch = self._open_epoch = device.pool_epoch_begin()
-            device.select_stream(base)
+            epoch = device.pool_epoch_begin()
+            device.select_stream(self.stream_base)
         try:
-            self._dispatch_tasks(G, registry, plan, times, verbose)
+            self.last_node_times = self._dispatch_tasks(plan, epoch, verbose)
         except BaseException:
             # a plugin raised in the middle of a pass: leave the device in a defined state -- every stream drained, stream 0
             # current, the allocation epoch closed (its parked blocks back in the pool) -- and let the error travel on
             if plan is not None:
-                from . import device
                 try:
                     device.select_stream(0)
                     device.synchronize()
                     device.pool_epoch_dispatched()
-                    device.pool_epoch_end(self._open_epoch)
+                    device.pool_epoch_end(epoch)
                 except Exception:
                     pass
             raise
-        self.last_node_times = times
 
-    def _dispatch_tasks(self, G, registry, plan, times, verbose):
-        open_run = None
+    def _dispatch_tasks(self, plan, epoch, verbose):
+        """One pass over the task list: `plan` the stream plan (or None), `epoch` the allocation epoch run_tasks opened, the base stream
+        current.  Returns [(node id, type, name, host seconds)]."""
+        G, registry, fp = self.ienet.G, self.ienet.ie.plugins.plugins, self.plan
+        open_run, times = None, []
         if plan is not None:
-            from . import device
             stream_of, waits, records = plan
-            done_events, spare, current = {}, self.__dict__.setdefault('_order_events', []), 0
-            held = self.__dict__.setdefault('_events_in_flight', [])
-            base = self.stream_base
-            epoch = self._open_epoch
-            cap_model = CaptureStreamModel() if self.__dict__.get('_recording') else None
-            ops = self.__dict__.get('_stream_ops')      # tests: the cross-stream waits of the pass as they are issued
-        fp = self.plan
+            done_events, current, base = {}, 0, self.stream_base
+            cap_model = CaptureStreamModel() if self._recording else None
+            ops = self._stream_ops
         for task in fp.order:
             if task in fp.fused_away:
                 continue
@@ -808,10 +686,9 @@ class Executable_Network:
                     if how == 'relay':                   # (a recording only: see CaptureStreamModel)
                         device.select_stream(base)
                         done_events[dep].wait()
-                        relay = (spare.pop() if spare else device.Event(timed=False)).record()
+                        relay = self._order_event().record()
                         device.select_stream(base + current)
                         relay.wait()
-                        held.append(relay)
                     else:
                         done_events[dep].wait()
             self._set_hints(task, node)
@@ -835,7 +712,7 @@ class Executable_Network:
             if timed and not self.device_timing_runs:
                 open_run = self._close_run(open_run)
             if plan is not None and task in records:
-                done_events[task] = (spare.pop() if spare else device.Event(timed=False)).record()
+                done_events[task] = self._order_event().record()
             times.append((task, node_type, node['name'], dt))
             if verbose:
                 print('{}, {}, {}, {}'.format(task, node_type, node['name'], dt))
@@ -847,8 +724,7 @@ class Executable_Network:
             if len(res) > 0:
                 if fp.c8_entry and (task in fp.c8_entry or fp.lrn_pool.get(task) in fp.c8_entry):
                     # the tensor the first blocked module reads: converted once, every reader gets the blocked form
-                    from . import device as dev_
-                    res = {port_id: (dev_.BlockedHalf.from_dense(data) if isinstance(data, dev_.DeviceTensor) and data.ndim == 4 else data)
+                    res = {port_id: (device.BlockedHalf.from_dense(data) if isinstance(data, device.DeviceTensor) and data.ndim == 4 else data)
                            for port_id, data in res.items()}
                 for port_id, data in res.items():
                     node['output'][port_id]['data'] = data
@@ -865,19 +741,18 @@ class Executable_Network:
             joins = []
             for st in sorted(set(stream_of.values()) - {0}):
                 device.select_stream(base + st)
-                joins.append((spare.pop() if spare else device.Event(timed=False)).record())
+                joins.append(self._order_event().record())
             device.select_stream(base)
             for ev in joins:
                 ev.wait()
-            held.extend(joins)
-            held.extend(done_events.values())
             device.pool_epoch_dispatched()
             if self.defer_sync:          # asynchronous request: wait_done() ends the pass
-                self._pending = (epoch, (spare.pop() if spare else device.Event(timed=False)).record())
+                self._pending = (epoch, self._order_event().record())
             else:
                 device.select_stream(0)
                 device.synchronize()
                 device.pool_epoch_end(epoch)
+        return times
 
     def _set_port(self, nid, tensor):
         out = self.ienet.G.nodes[nid]['output']
@@ -934,63 +809,43 @@ class Executable_Network:
         parallel capture streams meets a ring when non-origin streams wait for each other in both directions over time,
         profiles/r04_capture.md); the dispatcher now relays the ring-closing waits through the origin stream (CaptureStreamModel)."""
         if streams != 'plan':
-            saved_streams = self.compute_streams
-            self.compute_streams = max(1, int(streams))
-            try:
+            with _overridden(self, compute_streams=max(1, int(streams))):
                 return self.capture_graph(inputs, warm=warm, streams='plan')
-            finally:
-                self.compute_streams = saved_streams
-        from . import device
         G = self.ienet.G
         if not all(isinstance(v, device.DeviceTensor) for v in inputs.values()):
             raise ValueError('capture_graph needs device-resident inputs (DeviceTensor): their addresses go into the graph')
         self.release_graph()
         for _ in range(max(1, warm)):           # the pool learns every block size of the pass: a capture must not hipMalloc
-            self._infer_eager(inputs)
-        by_name = {G.nodes[n]['name']: n for n in G.nodes}
-        for node_name, val in inputs.items():
-            G.nodes[by_name[node_name]]['param'] = val
-        results = self.ienet.find_node_by_type('Result')
-        for nid, _ in results:
-            G.nodes[nid]['comm'] = None
-            G.nodes[nid]['_async'] = True       # the Result stays on the device: infer_graph() reads it back
-        saved_timing, self.device_timing = self.device_timing, None
+            self._infer_eager(inputs)         # (which binds the inputs)
         if self.recording_rings():              # (cannot happen with the relays in place: refuse before any HIP call, never crash)
             raise device.PvhipError('capture_graph: this stream plan would close a ring in the runtime\'s parallel-stream lists '
                                     '(hipStreamEndCapture of ROCm 7.2 never returns from it); record on one stream')
         device.select_stream(self.stream_base)
         device.call('pvhip_graph_begin_capture')
-        handle = ctypes_void_p()
+        handle = ctypes.c_void_p()
         first_error = None
         try:
-            self.defer_sync = self._recording = True
-            try:
+            with _overridden(self, device_timing=None, _recording=True), self._results_on_device():    # infer_graph() reads the Results back
                 self.run_tasks(False)
-            finally:
-                self.defer_sync = self._recording = False
-                self.device_timing = saved_timing
-                for nid, _ in results:
-                    G.nodes[nid].pop('_async', None)
         except BaseException as exc:            # noqa: BLE001 -- kept: end_capture below may fail too and must not mask it
             first_error = exc
         try:
             device.select_stream(self.stream_base)
-            device.call('pvhip_graph_end_capture', byref(handle))       # (also after an error: the capture must be closed)
+            device.call('pvhip_graph_end_capture', ctypes.byref(handle))       # (also after an error: the capture must be closed)
         except Exception:                       # noqa: BLE001
             if first_error is None:
                 raise
         if first_error is not None:
             if handle.value:
-                device.call('pvhip_graph_destroy', ctypes_void_p(handle.value))
+                device.call('pvhip_graph_destroy', ctypes.c_void_p(handle.value))
             raise first_error
-        pending = self.__dict__.pop('_pending', None)   # its event belongs to the graph: nothing to wait for, just close the epoch
-        if pending is not None:
-            device.pool_epoch_end(pending[0])
-        keep = [p['data'] for n in G.nodes for p in G.nodes[n].get('output', {}).values() if 'data' in p]
-        keep += [G.nodes[nid]['result'] for nid, _ in results]
-        self._graph = {'handle': handle.value, 'inputs': dict(inputs), 'keep': keep,
-                       'results': {name: G.nodes[nid]['result'] for nid, name in results}}
-        self._graph['by_hand'] = not self.__dict__.get('_auto_graph_busy')     # a recording made by hand is never replaced by infer()
+        if self._pending is not None:           # its event belongs to the graph: nothing to wait for, just close the epoch
+            device.pool_epoch_end(self._pending[0])
+            self._pending = None
+        results = {name: G.nodes[nid]['result'] for nid, name in self.ienet.find_node_by_type('Result')}
+        keep = [p['data'] for n in G.nodes for p in G.nodes[n].get('output', {}).values() if 'data' in p] + list(results.values())
+        self._graph = {'handle': handle.value, 'inputs': dict(inputs), 'keep': keep, 'results': results,
+                       'by_hand': not self._auto_graph_busy}       # a recording made by hand is never replaced by infer()
         device.select_stream(0)
 
     def dump_node_args(self, task, node, inputs):
@@ -999,8 +854,6 @@ class Executable_Network:
         `resources/node_args_6.pickle` was made this way).  What the file holds is what the REFERENCE's plugins can load: device
         tensors are copied to host ndarrays, and the scheduler's private hints (`_fuse_bias`, `_out_into`, device caches: every key
         that starts with an underscore) stay out, so a fused Convolution replays as the plain Convolution it is in the IR."""
-        import pickle
-        from . import device
 
         def plain(obj):
             if isinstance(obj, (device.DeviceTensor, device.ChannelSlice)):
@@ -1017,9 +870,7 @@ class Executable_Network:
     def infer_graph(self, inputs: dict = None) -> dict:
         """Replay the captured pass (for new inputs: copied device-to-device into the captured input tensors first) and return
         {Result name: ndarray} like infer()."""
-        from . import device
-        import ctypes
-        g = self.__dict__.get('_graph')
+        g = self._graph
         if g is None:
             raise RuntimeError('no captured graph: call capture_graph(inputs) first')
         device.select_stream(self.stream_base)
@@ -1031,38 +882,31 @@ class Executable_Network:
             if src.shape != dst.shape:
                 raise ValueError('input {} has shape {}, the graph was captured for {}'.format(name, src.shape, dst.shape))
             device.call('pvhip_memcpy_d2d', ctypes.c_void_p(dst.ptr), ctypes.c_void_p(src.ptr), dst.nbytes)
-        device.call('pvhip_graph_launch', ctypes.c_void_p(g['handle']))
-        out = {name: (t.numpy() if hasattr(t, 'numpy') and not isinstance(t, np.ndarray) else np.asarray(t)) for name, t in g['results'].items()}
-        device.select_stream(0)
+        self.launch_graph(g)
+        out = {name: self._read_back(t) for name, t in g['results'].items()}
+        self.wait_done()
         device.synchronize()
         return out
 
     def release_graph(self):
-        g = self.__dict__.pop('_graph', None)
-        if '_auto_graph' in self.__dict__:
-            self._auto_graph.update(captured=False, seen=0)
+        g, self._graph = self._graph, None
+        self._auto_graph.update(captured=False, seen=0)
         if g is not None:
-            from . import device
-            import ctypes
             device.call('pvhip_graph_destroy', ctypes.c_void_p(g['handle']))
 
     def wait_done(self):
-        """Host-side wait for a pass dispatched with defer_sync (its streams have been joined on the base stream)."""
-        replayed = self.__dict__.pop('_replay_done', None)
-        if replayed is not None:
-            replayed.synchronize()
-            self.__dict__.setdefault('_event_pool', []).append(replayed)
-        pending = self.__dict__.pop('_pending', None)
-        if pending is not None:
-            from . import device
-            epoch, done = pending
+        """Host-side wait for a pass dispatched with defer_sync (its streams have been joined on the base stream) or replayed by
+        launch_graph."""
+        if self._pending is not None:
+            (epoch, done), self._pending = self._pending, None
             done.synchronize()
-            device.pool_epoch_end(epoch)
-            self.__dict__.setdefault('_order_events', []).append(done)
+            if epoch is not None:
+                device.pool_epoch_end(epoch)
+            self._order_events += self._events_in_flight
+            self._events_in_flight = []
 
     def _concat_buffer(self, cat_id):
         """Output tensor of a Concat whose producers write in place; one fresh tensor per infer."""
-        from . import device
         node = self.ienet.G.nodes[cat_id]
         port = next(iter(node['output']))
         if node.get('_buf_serial') != self._infer_serial:
@@ -1074,9 +918,7 @@ class Executable_Network:
 
     # ---- device-side per-node timing (hipEvents on the compute stream; cf. the time.time() bracket :279-283)
     def _event(self):
-        from . import device
-        pool = self.__dict__.setdefault('_event_pool', [])
-        return pool.pop() if pool else device.Event()
+        return self._event_pool.pop() if self._event_pool else device.Event()
 
     NO_LAUNCH_TYPES = ('Const', 'Parameter', 'Reshape')   # their compute() puts nothing on the stream
 
@@ -1086,9 +928,8 @@ class Executable_Network:
         return None
 
     def _recycle_events(self):
-        pool = self.__dict__.setdefault('_event_pool', [])
         for _, _, _, e0, e1, _ in self._timed:
-            pool.extend((e0, e1))
+            self._event_pool.extend((e0, e1))
         self._timed = []
 
     def device_times_ms(self, with_counts: bool = False):
@@ -1107,20 +948,13 @@ class Executable_Network:
         box / class heads, whose host-side PriorBox / DetectionOutput consumers are out of scope) and return
         {node name: tensor of its first output port} -- device tensors are returned as they are."""
         G = self.ienet.G
-        by_name = {G.nodes[n]['name']: n for n in G.nodes}
+        by_name = self._bind_inputs(inputs)
         targets = [by_name[name] for name in node_names]
         needed = set(targets)
         for t in targets:
             needed.update(nx.ancestors(G, t))
-        for node_name, val in inputs.items():
-            if node_name in by_name:
-                G.nodes[by_name[node_name]]['param'] = val
-        full = self.plan
-        self.plan = full.restricted(needed, set(targets))
-        try:
+        with _overridden(self, plan=self.plan.restricted(needed, set(targets))):
             self.run_tasks(False)
-        finally:
-            self.plan = full
         out = {}
         for name, t in zip(node_names, targets):
             ports = G.nodes[t]['output']
@@ -1136,8 +970,7 @@ class Executable_Network:
     AUTO_GRAPH_AFTER = 2
 
     def _auto_graph_key(self, inputs, verbose, gathers_later=False):
-        from . import device
-        if verbose or os.environ.get('PVHIP_AUTO_GRAPH', '1') == '0' or self.__dict__.get('_auto_graph_busy'):
+        if verbose or os.environ.get('PVHIP_AUTO_GRAPH', '1') == '0' or self._auto_graph_busy:
             return None
         if self.expected_result is not None or self.pickle_node_args or self.device_timing is not None or self.defer_sync:
             return None
@@ -1145,75 +978,57 @@ class Executable_Network:
             return None                             # (a request gathers its shards in wait(), after the recorded pass)
         if not inputs or not all(isinstance(v, device.DeviceTensor) for v in inputs.values()):
             return None
-        registry = self.ienet.ie.plugins.plugins
-        if not all(getattr(sys.modules.get(m.__package__), 'DEVICE_STREAMS', False) for m in registry.values()):
-            return None
-        if '_graph_safe' not in self.__dict__:      # every layer type of this network says its compute() can be recorded
-            G = self.ienet.G                        # (a foreign plugin set does not: its pass stays eager)
-            self._graph_safe = all(getattr(registry.get(G.nodes[n]['type']), 'GRAPH_CAPTURE_SAFE', False) for n in G.nodes)
-        if not self._graph_safe:
+        if not (self._device_streams and self._graph_safe):
             return None
         # (the recording reads the inputs where they lie: another tensor is another recording, never a copy into the caller's tensor)
         return (tuple(sorted((k, tuple(v.shape), v.ptr) for k, v in inputs.items())), self.compute_streams, self.stream_base,
-                self.__dict__.get('_plan_serial', 0), self.fuse_epilogues, device.settings_serial, self.kernel_type)
+                self._plan_serial, self.fuse_epilogues, device.settings_serial, self.kernel_type)
 
     def _graph_for(self, inputs, verbose=False, gathers_later=False):
         """The recording that replays this pass, or None: the pass is dispatched eagerly (and counted; the recording is made on the
         call after AUTO_GRAPH_AFTER identical eager ones)."""
         key = self._auto_graph_key(inputs, verbose, gathers_later)
-        state = self.__dict__.setdefault('_auto_graph', {'key': None, 'seen': 0, 'failed': False})
-        g = self.__dict__.get('_graph')
-        if key is None or state['failed'] or (g is not None and g.get('by_hand')):
+        state, g = self._auto_graph, self._graph
+        if key is None or state['failed'] or (g is not None and g['by_hand']):
             return None
         if state['key'] != key:
-            if state['key'] is not None and self.__dict__.get('_graph') is not None and state.get('captured'):
+            if state['captured']:           # (release_graph clears 'captured': it is set exactly while infer()'s own recording exists)
                 self.release_graph()
             state.update(key=key, seen=0, captured=False)
-        if state.get('captured') and self.__dict__.get('_graph') is not None:
-            return self._graph
+        if state['captured']:
+            return g
         state['seen'] += 1
         if state['seen'] <= self.AUTO_GRAPH_AFTER:
             return None
-        self._auto_graph_busy = True
-        saved_comm = self.comm
-        if gathers_later:
-            self.comm = None                # (the warm pass in front of the recording must not gather either: wait() does)
         try:
-            self.capture_graph(inputs, warm=1)
+            # (with gathers_later, the warm pass in front of the recording must not gather either: wait() does)
+            with _overridden(self, _auto_graph_busy=True, comm=None if gathers_later else self.comm):
+                self.capture_graph(inputs, warm=1)
             state['captured'] = True
         except Exception as exc:           # noqa: BLE001 -- replay is an optimisation: say why it is off, keep computing
             state['failed'] = True
             print('pyopenvino_amd: hipGraph replay of infer() disabled for this network ({}: {})'.format(type(exc).__name__, exc), file=sys.stderr)
             return None
-        finally:
-            self._auto_graph_busy = False
-            self.comm = saved_comm
         return self._graph
 
     def infer(self, inputs: dict, verbose: bool = False) -> dict:
         inputs = self._stage_host_inputs(inputs)
         if self._graph_for(inputs, verbose) is None:
             return self._infer_eager(inputs, verbose)
-        self.last_node_times = []
         return self.infer_graph(inputs)
 
     def launch_graph(self, g):
         """Asynchronous replay for an infer request: the recorded pass goes to this network's stream with one call; `wait_done()`
         waits for the event behind it."""
-        from . import device
-        import ctypes
         device.select_stream(self.stream_base)
         device.call('pvhip_graph_launch', ctypes.c_void_p(g['handle']))
-        self._replay_done = self._event().record()
+        self._pending = (None, self._order_event().record())
         device.select_stream(0)
         self.last_node_times = []
 
     def _infer_eager(self, inputs: dict, verbose: bool = False) -> dict:
         G = self.ienet.G
-        by_name = {G.nodes[n]['name']: n for n in G.nodes}
-        for node_name, val in inputs.items():
-            if node_name in by_name:
-                G.nodes[by_name[node_name]]['param'] = val
+        self._bind_inputs(inputs)
         for nid, _ in self.ienet.find_node_by_type('Result'):
             G.nodes[nid]['comm'] = self.comm
         if verbose:
@@ -1228,9 +1043,7 @@ class Executable_Network:
     def _host_input(self, name):
         """This request's staging of input `name`: the page-locked host array, the device tensor it is uploaded into, and the fp32 NCHW
         tensor the pass reads -- the same address on every call, so the pass is recorded and replayed like a device-resident one."""
-        from . import device
-        slots = self.__dict__.setdefault('_host_inputs', {})
-        slot = slots.get(name)
+        slot = self._host_inputs.get(name)
         if slot is None:
             info = self.ienet.input_info[name]
             if not info.supported():
@@ -1241,7 +1054,7 @@ class Executable_Network:
             slot = {'host': device.host_empty(shape, dtype), 'fixed': fixed, 'event': device.Event(timed=False),
                     'staging': device.DeviceTensor.empty(shape, dtype) if convert else fixed,
                     'u8': info.precision == 'U8', 'nhwc': info.layout == 'NHWC'}
-            slots[name] = slot
+            self._host_inputs[name] = slot
         return slot
 
     def _stage_host_inputs(self, inputs: dict) -> dict:
@@ -1249,13 +1062,12 @@ class Executable_Network:
         caller's array is copied into the page-locked buffer unless it IS that buffer, the buffer is uploaded on the copy stream, this
         request's first stream waits for the copy's event and converts (one launch; none for FP32 NCHW).  No host synchronisation.
         Every other input is returned unchanged (and goes the default way)."""
-        from . import device
-        out = None
+        out = dict(inputs)
         for name, arr in inputs.items():
             info = self.ienet.input_info.get(name)
             if info is None or isinstance(arr, (device.DeviceTensor, device.ChannelSlice, device.BlockedHalf)):
                 continue
-            slot = self.__dict__.get('_host_inputs', {}).get(name)
+            slot = self._host_inputs.get(name)
             own = (slot is not None and isinstance(arr, np.ndarray) and arr.shape == slot['host'].shape and arr.dtype == slot['host'].dtype
                    and arr.ctypes.data == slot['host'].ctypes.data)
             if not (own or info.declared):
@@ -1268,15 +1080,13 @@ class Executable_Network:
                     raise ValueError('input {}: declared {} / {} means shape {}, got {}'.format(name, info.precision, info.layout, host.shape, a.shape))
                 np.copyto(host, a, casting='same_kind' if host.dtype == np.float32 else 'safe')
             device.select_stream(device.COPY_STREAM)
-            device.call('pvhip_memcpy_h2d_async', ctypes_void_p(slot['staging'].ptr), ctypes_void_p(host.ctypes.data), host.nbytes)
+            device.call('pvhip_memcpy_h2d_async', ctypes.c_void_p(slot['staging'].ptr), ctypes.c_void_p(host.ctypes.data), host.nbytes)
             slot['event'].record()
             device.select_stream(self.stream_base)
             slot['event'].wait()
             if slot['staging'] is not slot['fixed']:
-                device.call('pvhip_input_to_nchw_f32', ctypes_void_p(slot['staging'].ptr), ctypes_void_p(slot['fixed'].ptr),
+                device.call('pvhip_input_to_nchw_f32', ctypes.c_void_p(slot['staging'].ptr), ctypes.c_void_p(slot['fixed'].ptr),
                             *slot['fixed'].shape, int(slot['u8']), int(slot['nhwc']))
             device.select_stream(0)
-            if out is None:
-                out = dict(inputs)
             out[name] = slot['fixed']
-        return inputs if out is None else out
+        return out
