@@ -162,6 +162,20 @@ class ConvDest(_c.Structure):
     _fields_ = [('y', _c.c_void_p), ('k', _c.c_int), ('channel_offset', _c.c_int), ('channels_total', _c.c_int), ('layout', _c.c_int)]
 
 
+def ptr(t):
+    """The device address of a tensor as a kernel argument, NULL for None (an optional operand: bias, per-channel Add)."""
+    return _c.c_void_p(t.ptr if t is not None else 0)
+
+
+def act_args(act):
+    """A fused activation (None, ('relu',) or ('clamp', lo, hi)) as the (code, lo, hi) the kernel epilogues take."""
+    if act is None:
+        return 0, 0.0, 0.0
+    if act[0] == 'relu':
+        return 1, 0.0, 0.0
+    return 2, float(act[1]), float(act[2])
+
+
 class PvhipError(RuntimeError):
     """A libpvhip call returned a negative status."""
 
@@ -222,11 +236,6 @@ def init(device: int = None) -> int:
 settings_serial = 0      # bumped by every reload: host-side plans that bake kernel choices in (a captured hipGraph) key on it
 
 
-conv_prepad = os.environ.get('PVHIP_CONV_PREPAD', '1') != '0'      # Convolution plugin: pad the input of a c-major layer in a pass of its own
-conv_f16_dma = os.environ.get('PVHIP_CONV_F16_DMA', '1') != '0'    # Convolution plugin, FP16 IRs: the f16 form of the LDS-DMA kernel where it applies
-conv_f16_span = int(os.environ.get('PVHIP_CONV_F16_SPAN', '1') or 0)  # ... and the span kernel before it: 1 = 3x3 / 5x5 layers, 2 = 1x1 too (slower there), 0 = never
-conv_stem_direct = os.environ.get('PVHIP_CONV_STEM_DIRECT', '1') != '0'   # Convolution plugin: the row-span kernel of a 7x7 / 2 first convolution reads the image itself (no padding pass)
-conv_f16_stem = os.environ.get('PVHIP_CONV_F16_STEM', '1') != '0'  # ... and the row-span kernel for a 7x7 / 2 first convolution over three channels with a blocked output
 def _env_level(name, default):
     try:
         return int(os.environ.get(name, default) or 0)
@@ -234,26 +243,31 @@ def _env_level(name, default):
         return int(default)
 
 
-# ... and fp16 tensors blocked by eight channels: 0 = never, 1 = between a 1x1 convolution and the 3x3 / 5x5 behind it, 2 = whole modules and
-# the stem (fusion_plan.build reads THIS value, the plugins too: one source for both sides)
-conv_f16_c8 = _env_level('PVHIP_CONV_F16_C8', '2')
-fuse_poolconv = _env_level('PVHIP_FUSE_POOLCONV', '2')
-fuse_stem_conv = _env_level('PVHIP_FUSE_STEM_CONV', '1')          # the 1x1 convolution behind MaxPool + LRN in the same launch (0 = two launches)             # MaxPool + pool_proj as one launch: 0 = never (what the plan reads; the library parses its own copy)
+def _plugin_settings():
+    """The PVHIP_* settings the plugins and fusion_plan.build read (libpvhip parses its own copy): one source for both sides."""
+    env = os.environ.get
+    return {
+        'conv_prepad': env('PVHIP_CONV_PREPAD', '1') != '0',        # Convolution plugin: pad the input of a c-major layer in a pass of its own
+        'conv_f16_dma': env('PVHIP_CONV_F16_DMA', '1') != '0',      # Convolution plugin, FP16 IRs: the f16 form of the LDS-DMA kernel where it applies
+        'conv_f16_span': int(env('PVHIP_CONV_F16_SPAN', '1') or 0),  # ... and the span kernel before it: 1 = 3x3 / 5x5 layers, 2 = 1x1 too (slower there), 0 = never
+        'conv_stem_direct': env('PVHIP_CONV_STEM_DIRECT', '1') != '0',  # the row-span kernel of a 7x7 / 2 first convolution reads the image itself (no padding pass)
+        'conv_f16_stem': env('PVHIP_CONV_F16_STEM', '1') != '0',    # ... and the row-span kernel for a 7x7 / 2 first convolution over three channels with a blocked output
+        # ... and fp16 tensors blocked by eight channels: 0 = never, 1 = between a 1x1 convolution and the 3x3 / 5x5 behind it, 2 = whole modules and the stem
+        'conv_f16_c8': _env_level('PVHIP_CONV_F16_C8', '2'),
+        'fuse_poolconv': _env_level('PVHIP_FUSE_POOLCONV', '2'),    # MaxPool + pool_proj as one launch: 0 = never
+        'fuse_stem_conv': _env_level('PVHIP_FUSE_STEM_CONV', '1'),  # the 1x1 convolution behind MaxPool + LRN in the same launch (0 = two launches)
+    }
+
+
+globals().update(_plugin_settings())
 
 
 def reload_settings():
     """Make libpvhip read the PVHIP_* environment variables again (it parses them once, at pvhip_init or at the first
-    query that needs them; no device needed)."""
-    global settings_serial, conv_prepad, conv_f16_dma, conv_f16_span, conv_f16_c8, conv_f16_stem, fuse_poolconv, conv_stem_direct, fuse_stem_conv
+    query that needs them; no device needed), and this module's copy with it."""
+    global settings_serial
     call('pvhip_settings_reload')
-    conv_prepad = os.environ.get('PVHIP_CONV_PREPAD', '1') != '0'
-    conv_f16_dma = os.environ.get('PVHIP_CONV_F16_DMA', '1') != '0'
-    conv_f16_span = int(os.environ.get('PVHIP_CONV_F16_SPAN', '1') or 0)
-    conv_f16_c8 = _env_level('PVHIP_CONV_F16_C8', '2')
-    fuse_poolconv = _env_level('PVHIP_FUSE_POOLCONV', '2')
-    fuse_stem_conv = _env_level('PVHIP_FUSE_STEM_CONV', '1')
-    conv_f16_stem = os.environ.get('PVHIP_CONV_F16_STEM', '1') != '0'
-    conv_stem_direct = os.environ.get('PVHIP_CONV_STEM_DIRECT', '1') != '0'
+    globals().update(_plugin_settings())
     settings_serial += 1
 
 

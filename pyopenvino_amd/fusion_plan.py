@@ -226,8 +226,7 @@ def _pre_add(p, conv):
         others = [p_ for p_ in preds if G.nodes[p_]['type'] != 'Const']
         if len(preds) != 2 or len(consts) != 1 or len(others) != 1:
             continue
-        if (conv.pre_add_fusable(G.nodes[cid], G.nodes[src], G.nodes[consts[0]], True) if p.f16
-                else conv.pre_add_fusable(G.nodes[cid], G.nodes[src], G.nodes[consts[0]])):
+        if conv.pre_add_fusable(G.nodes[cid], G.nodes[src], G.nodes[consts[0]], f16=p.f16):
             p.pre_add[cid] = (src, consts[0], others[0])
             p.fused_away.add(src)
 

@@ -48,14 +48,9 @@ def compute(node: dict, inputs: dict = None, kernel_type: str = 'hip', debug: bo
     if bias is not None:
         bias = dev.as_device(bias)
         assert bias.size == grp
-    act = node.get('_fuse_act')
-    act_code, act_lo, act_hi = 0, 0.0, 0.0
-    if act is not None:
-        act_code = 1 if act[0] == 'relu' else 2
-        if act_code == 2:
-            act_lo, act_hi = float(act[1]), float(act[2])
+    act_code, act_lo, act_hi = dev.act_args(node.get('_fuse_act'))
     y = dev.DeviceTensor.empty((n, grp, oh, ow))
     dev.call('pvhip_dwconv2d_f32', ctypes.c_void_p(x.ptr), ctypes.c_void_p(w.ptr), ctypes.c_void_p(y.ptr),
              n, grp, h, wd, kh, kw, oh, ow, strides[0], strides[1], pads_begin[0], pads_begin[1],
-             ctypes.c_void_p(bias.ptr if bias is not None else 0), act_code, act_lo, act_hi)
+             dev.ptr(bias), act_code, act_lo, act_hi)
     return {common_def.first_output_port(node): y}

@@ -146,7 +146,7 @@ def compute(node: dict, inputs: dict = None, kernel_type: str = 'hip', debug: bo
             yc = dev.BlockedHalf((n, k_out, oh, ow))
             dev.call('pvhip_maxpool3x3_lrn_conv1x1_c8', ctypes.c_void_p(blocked.ptr), ctypes.c_void_p(cw.ptr), ctypes.c_void_p(yc.ptr), n, c, h, w, oh, ow,
                      strides[0], strides[1], pads_begin[0], pads_begin[1], pads_end[0], pads_end[1], int(la['size']), float(la['alpha']), float(la['beta']),
-                     float(la['bias']), k_out, ctypes.c_void_p(cb_.ptr if cb_ is not None else 0), 1 if conv.get('act') is not None else 0)
+                     float(la['bias']), k_out, dev.ptr(cb_), 1 if conv.get('act') is not None else 0)
             conv['node']['_hip_f16'] = 'inside MaxPool + LRN (blocked tensors)'
             return {common_def.first_output_port(node): yc}
         yb = dev.BlockedHalf((n, c, oh, ow))
@@ -169,15 +169,11 @@ def compute(node: dict, inputs: dict = None, kernel_type: str = 'hip', debug: bo
         cb = dev.as_device(conv['bias']) if conv.get('bias') is not None else None
         k_out = cw.shape[0]
         assert tuple(cw.shape[1:]) == (c, 1, 1) and (cb is None or cb.size == k_out)
-        act, act_code, act_lo, act_hi = conv.get('act'), 0, 0.0, 0.0
-        if act is not None:
-            act_code = 1 if act[0] == 'relu' else 2
-            if act_code == 2:
-                act_lo, act_hi = float(act[1]), float(act[2])
+        act_code, act_lo, act_hi = dev.act_args(conv.get('act'))
         yc = dev.DeviceTensor.empty((n, k_out, oh, ow))
         dev.call('pvhip_maxpool_lrn_conv1x1_f32', ctypes.c_void_p(x.ptr), ctypes.c_void_p(cw.ptr), ctypes.c_void_p(yc.ptr), n, c, h, w, oh, ow,
                  kernel[0], kernel[1], strides[0], strides[1], pads_begin[0], pads_begin[1], pads_end[0], pads_end[1],
-                 int(la['size']), float(la['alpha']), float(la['beta']), float(la['bias']), k_out, ctypes.c_void_p(cb.ptr if cb is not None else 0),
+                 int(la['size']), float(la['alpha']), float(la['beta']), float(la['bias']), k_out, dev.ptr(cb),
                  act_code, act_lo, act_hi)
         return {common_def.first_output_port(node): yc}
     y = dev.DeviceTensor.empty((n, c, oh, ow))
