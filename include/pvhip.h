@@ -445,6 +445,16 @@ int pvhip_comm_destroy(void);
  * (n, c, h, w)).  Exact: dst == src.transpose(0, 3, 1, 2).astype(float32) bit for bit.  fp32 NCHW is a device copy.  n <= 65535,
  * c * h * w < 2^31, c <= 4096 for NHWC (pvhip_layout.hip). */
 int         pvhip_input_to_nchw_f32(const void* src, float* dst, int n, int c, int h, int w, int src_u8, int src_nhwc);
+/* Addition to ABI v17 (the version number is unchanged: nothing existing changed): an input with declared preprocessing
+ * (IENetwork.input_info[name].preprocess_info) -- bilinear resize of a (src_h, src_w) source to the Parameter's (dst_h, dst_w), channel
+ * reversal, per-channel mean / scale -- and the format change above, in ONE launch into the fp32 NCHW tensor `dst` (n, c, dst_h, dst_w).
+ * `src`: uint8 (src_u8 = 1) or fp32 values, (n, src_h, src_w, c) for src_nhwc = 1, else (n, c, src_h, src_w).  Resize iff the extents
+ * differ: half-pixel centres clamped at the border, no antialiasing, coordinates exact in integers (pvhip_preprocess.hip; the same rule
+ * in numpy: tests/preprocess_ref.py, matched bit for bit).  reverse_channels = 1: output channel k reads source channel c-1-k.  `mean` /
+ * `std_scale`: NULL or c device floats, y = (v - mean[k]) / std_scale[k].  Equal extents, no reversal, both NULL: exactly the conversion
+ * above.  n <= 65535, c <= 1024, c * h * w < 2^31 for source and destination, fp32 sources 4-byte aligned; else PVHIP_EINVAL. */
+int         pvhip_input_preprocess_f32(const void* src, float* dst, int n, int c, int src_h, int src_w, int dst_h, int dst_w,
+                                       int src_u8, int src_nhwc, int reverse_channels, const float* mean, const float* std_scale);
 
 #ifdef __cplusplus
 }
