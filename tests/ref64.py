@@ -1,8 +1,11 @@
-"""Float64 reference of the ops GoogLeNet uses, and the fused groups of an execution plan.  A helper module the tests import.
+"""Float64 reference of the ops GoogLeNet and SSD-MobileNet use, the fused groups of an execution plan, and the layer-by-layer check
+of a whole pass.  A helper module the tests import.
 
 The semantics are those of the reference's 'special' path as oracle/ops.py restates them: im2col convolution,
-MaxPool over the zero-padded input with ceil / floor rounding, AvgPool over the window clipped at h-1 / w-1, LRN with alpha NOT
-divided by size, SoftMax without a max shift.  Unlike the oracle, which rounds to float32 on purpose, every intermediate here is
+depthwise GroupConvolution with the same padding rules, MaxPool over the zero-padded input with ceil / floor rounding, AvgPool over
+the window clipped at h-1 / w-1, LRN with alpha NOT divided by size, SoftMax without a max shift, Multiply with the smaller operand
+broadcast, Sigmoid as 1 / (1 + exp(-x)).  DetectionOutput has no float64 definition here: its kernels follow the reference's float32
+rules, so the layer check holds it against the oracle fed the pass's own inputs (`check_detections`).  Unlike the oracle, which rounds to float32 on purpose, every intermediate here is
 float64: it is the yardstick the fp32 / fp16 kernels are held against, not a restatement of the reference's rounding.
 
 `groups(ex)` reads an Executable_Network's fusion plan and returns, for every launch, the node ids it computes, the ports that
@@ -19,6 +22,16 @@ from oracle.ops import out_extent
 # persistent walk) and 16 seeded positions in between
 SAMPLE_256 = sorted(set(range(8)) | set(range(248, 256)) |
                     set(int(i) for i in np.random.default_rng(256).choice(np.arange(8, 248), 16, replace=False)))
+# the same for a batch of 128 (SSD-MobileNet): 0-7, 120-127 (the last tiles of every persistent walk; 127 is the image the SSD fixture
+# pins) and 16 seeded positions in between
+SAMPLE_128 = sorted(set(range(8)) | set(range(120, 128)) |
+                    set(int(i) for i in np.random.default_rng(128).choice(np.arange(8, 120), 16, replace=False)))
+
+# SSD-MobileNet's prior-box subgraph: per feature map the two ShapeOf -> StridedSlice shape vectors, PriorBoxClustered (its boxes computed
+# once on the host and cached on the device) and the Unsqueeze; then the Concat of the six.  Its values depend on shapes only.
+SSD_PRIOR_BOX_SUBGRAPH = sorted(['PriorBoxClustered_{}{}'.format(k, s_) for k in range(6)
+                                 for s_ in ('/0_port', '/ss_0_port', '/1_port', '/ss_1_port', '/naked_not_unsqueezed', '')] +
+                                ['ConcatPriorBoxesClustered'])
 
 
 def _ints(s):
@@ -49,6 +62,26 @@ def convolution(x, w, strides, pads_begin, pads_end, auto_pad='explicit', chunk_
         win = sliding_window_view(xs, (kh, kw), axis=(2, 3))[:, :, ::sh, ::sw][:, :, :oh, :ow]       # m,c,oh,ow,kh,kw
         col = np.ascontiguousarray(win.transpose(0, 2, 3, 1, 4, 5)).reshape(m * oh * ow, c * kh * kw)
         out[i0:i0 + m] = (col @ wm).reshape(m, oh, ow, kn).transpose(0, 3, 1, 2)
+    return out
+
+
+def group_convolution_depthwise(x, w, strides, pads_begin, pads_end, auto_pad='explicit'):
+    """Weights [G,1,1,kh,kw], G == C: one kh x kw filter per channel over the zero-padded input, with the output extent and padding
+    rules of `convolution` (same_upper / same_lower keep the IR's pads; SSD's stride-2 layers pad 0 at the beginning, 1 at the end).
+    Summed tap by tap, so no (n, c, oh, ow, kh, kw) window array is ever built."""
+    x, w = _f64(x), _f64(w)
+    n, c, h, wd = x.shape
+    g, co, ci, kh, kw = w.shape
+    assert co == 1 and ci == 1 and g == c, 'depthwise weights {} for {} channels'.format(w.shape, c)
+    sh, sw = strides
+    oh = out_extent(h, kh, sh, pads_begin[0], pads_end[0], 'floor', auto_pad, False)
+    ow = out_extent(wd, kw, sw, pads_begin[1], pads_end[1], 'floor', auto_pad, False)
+    xp = np.pad(x, [(0, 0), (0, 0), (pads_begin[0], pads_end[0]), (pads_begin[1], pads_end[1])])
+    assert (oh - 1) * sh + kh <= xp.shape[2] and (ow - 1) * sw + kw <= xp.shape[3], 'window exceeds the padded input'
+    out = np.zeros((n, c, oh, ow))
+    for ky in range(kh):
+        for kx in range(kw):
+            out += xp[:, :, ky:ky + (oh - 1) * sh + 1:sh, kx:kx + (ow - 1) * sw + 1:sw] * w[:, 0, 0, ky, kx].reshape(1, c, 1, 1)
     return out
 
 
@@ -104,6 +137,22 @@ def add(a, b):
     return a + np.broadcast_to(b, a.shape)
 
 
+def multiply(a, b):
+    """The smaller operand broadcasts to the larger (the reference's rule)."""
+    a, b = _f64(a), _f64(b)
+    if a.size > b.size:
+        return a * np.broadcast_to(b, a.shape)
+    return np.broadcast_to(a, b.shape) * b
+
+
+def sigmoid(x):
+    return 1.0 / (1.0 + np.exp(-_f64(x)))
+
+
+def transpose(x, order):
+    return np.ascontiguousarray(_f64(x).transpose(tuple(int(v) for v in np.asarray(order).ravel())))
+
+
 def relu(x):
     x = _f64(x)
     return np.where(x < 0, 0.0, x)
@@ -131,7 +180,8 @@ def softmax_rows(x):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# one IR node, from its inputs in sink-port order (float64; f16: Convolution / MatMul operands rounded to fp16 first)
+# one IR node, from its inputs in sink-port order (float64; f16: Convolution / MatMul operands rounded to fp16 first -- not those of a
+# GroupConvolution: an FP16 IR runs depthwise on the fp32 kernel, on weights that already hold fp16 values)
 def f16r(a):
     return np.asarray(a, dtype=np.float32).astype(np.float16).astype(np.float64)
 
@@ -141,6 +191,8 @@ def eval_node(node, ins, f16=False):
     if t == 'Convolution':
         x, w = (f16r(ins[0]), f16r(ins[1])) if f16 else (ins[0], ins[1])
         return convolution(x, w, _ints(a['strides']), _ints(a['pads_begin']), _ints(a['pads_end']), a['auto_pad'])
+    if t == 'GroupConvolution':
+        return group_convolution_depthwise(ins[0], ins[1], _ints(a['strides']), _ints(a['pads_begin']), _ints(a['pads_end']), a['auto_pad'])
     if t == 'MaxPool':
         return maxpool(ins[0], _ints(a['strides']), _ints(a['pads_begin']), _ints(a['pads_end']), _ints(a['kernel']), a['rounding_type'],
                        a['auto_pad'])
@@ -151,6 +203,12 @@ def eval_node(node, ins, f16=False):
         return lrn(ins[0], float(a['alpha']), float(a['beta']), float(a['bias']), int(a['size']))
     if t == 'Add':
         return add(ins[0], ins[1])
+    if t == 'Multiply':
+        return multiply(ins[0], ins[1])
+    if t == 'Sigmoid':
+        return sigmoid(ins[0])
+    if t == 'Transpose':
+        return transpose(ins[0], ins[1])
     if t == 'ReLU':
         return relu(ins[0])
     if t == 'Clamp':
@@ -162,7 +220,7 @@ def eval_node(node, ins, f16=False):
         return matmul(x, w, a.get('transpose_a') == 'true', a.get('transpose_b') == 'true')
     if t == 'SoftMax':
         return softmax_rows(ins[0])
-    if t == 'Reshape':                 # the batch stays the leading axis (the sampled images are a subset of it)
+    if t == 'Reshape':                 # the batch stays the leading axis (the sampled images are a subset of it; set_batch scales it)
         dims = tuple(next(iter(node['output'].values()))['dims'])
         return _f64(ins[0]).reshape((ins[0].shape[0],) + dims[1:])
     raise NotImplementedError(t)
@@ -289,3 +347,192 @@ def f16_excess(got, ref, slack=None):
     if slack is not None:
         bound = bound + slack
     return float((np.abs(got - ref) / bound).max())
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the layer-by-layer check of a whole pass (tests/test_batch256_layers.py, tests/test_ssd_layers.py)
+WINO4S, WINO4S_RAGGED, WINO4, WINO4_RAGGED = 'conv_wino4s_kernel', 'conv_wino4s_kernel, ragged', 'conv_wino4_kernel', 'conv_wino4_kernel, ragged'
+
+
+def wino4_form(node):
+    """wino4_conv's choice for a six-point Winograd layer (pvhip_wino.hip, default settings), from the port dims."""
+    n, c, h, w = node['input'][0]['dims']
+    k, _, kh, _ = node['input'][1]['dims']
+    m = 4 if kh == 3 else 2
+    ragged = h % m != 0 or w % m != 0
+    n_tb, n_kb, stages = -(-(n * -(-h // m) * -(-w // m)) // 32), -(-k // 32), c // 4
+    tiles_s = n_tb * ((n_kb + 1) // 2)
+    shape_ok = n_kb >= 2 and stages % 4 == 0 and stages >= 4
+    pays = stages >= 28 or (stages >= 24 and ragged) or (12 <= stages <= 16 and tiles_s >= 2048)
+    return (WINO4S if shape_ok and pays else WINO4) + (', ragged' if ragged else '')
+
+
+def read_rows(t, idx):
+    """The sampled images of a tensor, as fp32 (BlockedHalf: the fp32 values of its fp16 contents).  Dense device tensors are read image
+    by image: only what is compared crosses to the host."""
+    from pyopenvino_amd import device as dev
+    import ctypes
+    if isinstance(t, np.ndarray):
+        return np.ascontiguousarray(t[idx], dtype=np.float32)
+    if isinstance(t, (dev.ChannelSlice, dev.BlockedChannelSlice)):
+        base = read_rows(t.base, idx)
+        return np.ascontiguousarray(base[:, t.coff:t.coff + t.shape[1]])
+    if isinstance(t, dev.BlockedHalf):
+        return read_rows(t.dense(), idx)
+    assert isinstance(t, dev.DeviceTensor) and t.dtype == np.float32, type(t)
+    per = int(np.prod(t.shape[1:], dtype=np.int64))
+    out = np.empty((len(idx),) + tuple(t.shape[1:]), dtype=np.float32)
+    for j, i in enumerate(idx):
+        assert 0 <= i < t.shape[0]
+        dev.call('pvhip_memcpy_d2h', ctypes.c_void_p(out[j].ctypes.data), ctypes.c_void_p(t.ptr + int(i) * per * 4), per * 4)
+    return out
+
+
+def conv_family(node):
+    from pyopenvino_amd.op_plugins import Convolution
+    return Convolution.kernel_kind(node)[0]
+
+
+def family(G, ex, g):
+    convs = g['convs']
+    if not convs:
+        return ' + '.join(G.nodes[n]['type'] for n in g['nodes'])
+    node = G.nodes[convs[-1]]
+    f16_kind = node.get('_hip_f16') or G.nodes[g['launch']].get('_hip_f16')        # FP16 IRs: what the launch's kernel recorded
+    fam = 'f16 ' + f16_kind if f16_kind else conv_family(node)
+    if 'Winograd' in fam and 'stem' not in fam:
+        fam += ' / ' + wino4_form(node)
+    lead = [G.nodes[n]['type'] for n in g['nodes'] if n not in convs and G.nodes[n]['type'] in ('MaxPool', 'LRN')]
+    return ' + '.join(lead + [fam])
+
+
+def is_blocked(t):
+    from pyopenvino_amd import device as dev
+    return isinstance(t, (dev.BlockedHalf, dev.BlockedChannelSlice))
+
+
+def port_data(G, src):
+    return G.nodes[src[0]]['output'][src[1]]['data']
+
+
+def check_pass(net, ex, sample, f16=False, only=None, skip=()):
+    """Every group of the plan (`only`: the first groups of the schedule, by count; `skip`: launch ids the caller checks itself) against
+    the float64 reference on the images `sample`.  -> {family: (worst excess, layer name)}."""
+    import helpers
+    G = net.G
+    gs = groups(ex)
+    if only is not None:
+        gs = gs[:only]
+    consts, worst, held = {}, {}, {}
+    for g in gs:
+        if g['launch'] in skip:
+            continue
+        ins = {src: held[src] if src in held else read_rows(port_data(G, src), sample) for src in g['inputs']}
+        held = ins                                       # the members of a sibling launch share it; the previous launch's inputs go
+        out_t = port_data(G, g['output'])
+        got = read_rows(out_t, sample)
+        name = G.nodes[g['nodes'][-1]]['name']
+        fam = family(G, ex, g)
+        ref = eval_group(G, g, ins, f16=f16, consts=consts)
+        assert got.shape == ref.shape, '{}: {} != {}'.format(name, got.shape, ref.shape)
+        assert np.isfinite(got).all(), '{}: non-finite values'.format(name)
+        # fp16 outputs: blocked tensors, and the AvgPool of a blocked tensor (fp32 storage holding the fp16 values the reference's float16
+        # AvgPool returns; tests/test_hip_ops.py::test_avgpool_on_a_blocked_tensor)
+        fp16_out = is_blocked(out_t) or (G.nodes[g['nodes'][-1]]['type'] == 'AvgPool' and
+                                         any(is_blocked(port_data(G, s_)) for s_ in g['inputs']))
+        if f16 and fp16_out:
+            slack = None
+            if g['launch'] in ex._stem_conv:
+                # pool1 -> norm1 -> conv2/3x3_reduce in one launch: the normalised tensor becomes an fp16 operand inside the launch, rounded
+                # from the kernel's fp32 LRN, so each operand may sit one fp16 rounding away from f16r(float64 LRN)
+                slack = _operand_slack(G, g, ins)
+            ex_ = f16_excess(got, ref, slack)
+            assert ex_ <= 1.0, '{} ({}): an element is {:.2f} x outside one fp16 rounding'.format(name, fam, ex_)
+        elif f16:
+            helpers.assert_close(got, ref, 1e-5, '{} ({})'.format(name, fam))
+            ex_ = helpers.elementwise_excess(got, ref)
+        else:
+            wino = any('Winograd' in conv_family(G.nodes[c]) for c in g['convs'])
+            ex_ = check_group(got, ref, winograd=wino, what='{} ({})'.format(name, fam))
+        if ex_ >= worst.get(fam, (-1.0, ''))[0]:
+            worst[fam] = (ex_, name)
+        del got, ref
+    return worst
+
+
+def _operand_slack(G, g, ins):
+    """2**-11 x (|W| * |x|), x the float64 input of the group's convolution: how far one fp16 rounding of each of its operands can move
+    its output."""
+    cid = g['convs'][0]
+    k = g['nodes'].index(cid)
+    feeder = g['nodes'][k - 1]
+    x = eval_group(G, dict(g, nodes=g['nodes'][:k], output=(feeder, next(iter(G.nodes[feeder]['output'])))), ins)
+    wsrc = next(tuple(G.edges[(p, cid)]['connection'][:2]) for p in G.pred[cid] if G.edges[(p, cid)]['connection'][3] == 1)
+    a = G.nodes[cid]['data']
+    return 2.0 ** -11 * convolution(np.abs(x), np.abs(const_value(G, *wsrc)), _ints(a['strides']), _ints(a['pads_begin']), _ints(a['pads_end']))
+
+
+def report(worst, what):
+    print('\n{}: worst element-wise excess per kernel family (<= 1 passes)'.format(what))
+    for fam, (ex_, name) in sorted(worst.items(), key=lambda kv: -kv[1][0]):
+        print('  {:8.4f}  {:60s} {}'.format(ex_, fam, name))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# DetectionOutput: the oracle's float32 rules, fed the pass's own loc / conf rows and priors
+NEAR_TIE = 1e-6          # two oracle scores this close (relative) may swap ranks between fp32 implementations
+
+
+def _tie_runs(scores):
+    """[(start, stop)] of the runs of adjacent records (descending score order) whose neighbours' scores lie within NEAR_TIE."""
+    runs, i0 = [], 0
+    for i in range(1, len(scores) + 1):
+        if i == len(scores) or abs(scores[i] - scores[i - 1]) > NEAR_TIE * max(abs(scores[i]), abs(scores[i - 1]), 1e-30):
+            if i - i0 > 1:
+                runs.append((i0, i))
+            i0 = i
+    return runs
+
+
+def compare_detections(got, want, what):
+    """One image's records [n, class, score, xmin, ymin, xmax, ymax] (records x 7) against the oracle's: the record index and class
+    columns bit for bit, score and boxes within REL_TOL; the records of a near-tie of the oracle's scores as a set.  -> the number of
+    real detections."""
+    import helpers
+    got, want = np.array(got, dtype=np.float32), np.asarray(want, dtype=np.float32)
+    assert got.shape == want.shape, '{}: {} != {}'.format(what, got.shape, want.shape)
+    assert np.array_equal(got[:, 0], want[:, 0]), '{}: record index column differs (a different number of detections)'.format(what)
+    real = int(np.argmax(want[:, 0] < 0)) if (want[:, 0] < 0).any() else len(want)
+    for i0, i1 in _tie_runs(want[:real, 2]):
+        for rows in (got[i0:i1], want[i0:i1]):
+            rows[:] = rows[np.lexsort((rows[:, 4], rows[:, 3], rows[:, 1]))]
+    assert np.array_equal(got[:, 1], want[:, 1]), '{}: classes differ'.format(what)
+    helpers.assert_close(got[:, 2:], want[:, 2:], helpers.REL_TOL, what + ': scores / boxes')
+    return real
+
+
+def check_detections(net, sample):
+    """The DetectionOutput node of `net` after a pass: each sampled image's records against the oracle's DetectionOutput fed the HIP
+    pass's own loc / conf rows of that image and its priors (read whole: they are not per image).  Asserts every sampled image has
+    real detections.  -> {image: number of detections}."""
+    from oracle.op_plugins import DetectionOutput as oracle_do
+    G = net.G
+    did = next(n for n in G.nodes if G.nodes[n]['type'] == 'DetectionOutput')
+    node = G.nodes[did]
+    srcs = [tuple(G.edges[(p, did)]['connection'][:2]) for p in sorted(G.pred[did], key=lambda p: G.edges[(p, did)]['connection'][3])]
+    loc, conf = (read_rows(port_data(G, s_), sample) for s_ in srcs[:2])
+    priors = np.asarray(port_data(G, srcs[2]), dtype=np.float32)
+    assert priors.shape[0] == 1, priors.shape
+    out = np.asarray(next(iter(node['output'].values()))['data'])
+    b = len(loc)
+    ins = {0: loc, 1: conf, 2: priors}
+    # the oracle validates its inputs against the node's ports: declare the sampled rows (fp32, whatever precision an FP16 IR declared)
+    onode = dict(node, input={p: dict(node['input'][p], precision='FP32', dims=tuple(ins[p].shape)) for p in ins})
+    want = next(iter(oracle_do.compute(onode, ins).values()))
+    per = want.shape[2] // b
+    assert out.shape[2] % per == 0
+    counts = {}
+    for j, i in enumerate(sample):
+        counts[i] = compare_detections(out[0, 0, i * per:(i + 1) * per], want[0, 0, j * per:(j + 1) * per], 'DetectionOutput image {}'.format(i))
+        assert counts[i] > 0 and out[0, 0, i * per, 1] > 0, 'image {}: no detections, the check would be vacuous'.format(i)
+    return counts

@@ -26,7 +26,7 @@ HIP = 'pyopenvino_amd.op_plugins'
 B = 256
 SAMPLE = ref64.SAMPLE_256
 
-WINO4S, WINO4S_RAGGED, WINO4, WINO4_RAGGED = 'conv_wino4s_kernel', 'conv_wino4s_kernel, ragged', 'conv_wino4_kernel', 'conv_wino4_kernel, ragged'
+WINO4S, WINO4S_RAGGED, WINO4, WINO4_RAGGED = ref64.WINO4S, ref64.WINO4S_RAGGED, ref64.WINO4, ref64.WINO4_RAGGED
 F43, F25, PW = 'Winograd F(4x4,3x3)', 'Winograd F(2x2,5x5)', 'pointwise'
 
 # Convolution.kernel_kind of every convolution of the fp32 pass, and the wino4_conv form of the six-point ones (module docstring)
@@ -40,123 +40,11 @@ for _m, _f3, _f5 in (('3a', WINO4, WINO4), ('3b', WINO4S, WINO4), ('4a', WINO4S_
     KINDS['inception_{}/5x5'.format(_m)] = (F25, _f5)
 
 
-def wino4_form(node):
-    """wino4_conv's choice for a six-point Winograd layer (pvhip_wino.hip, default settings), from the port dims."""
-    n, c, h, w = node['input'][0]['dims']
-    k, _, kh, _ = node['input'][1]['dims']
-    m = 4 if kh == 3 else 2
-    ragged = h % m != 0 or w % m != 0
-    n_tb, n_kb, stages = -(-(n * -(-h // m) * -(-w // m)) // 32), -(-k // 32), c // 4
-    tiles_s = n_tb * ((n_kb + 1) // 2)
-    shape_ok = n_kb >= 2 and stages % 4 == 0 and stages >= 4
-    pays = stages >= 28 or (stages >= 24 and ragged) or (12 <= stages <= 16 and tiles_s >= 2048)
-    return (WINO4S if shape_ok and pays else WINO4) + (', ragged' if ragged else '')
-
-
-def read_rows(t, idx):
-    """The sampled images of a tensor, as fp32 (BlockedHalf: the fp32 values of its fp16 contents).  Dense device tensors are read image
-    by image: only what is compared crosses to the host."""
-    from pyopenvino_amd import device as dev
-    import ctypes
-    if isinstance(t, np.ndarray):
-        return np.ascontiguousarray(t[idx], dtype=np.float32)
-    if isinstance(t, (dev.ChannelSlice, dev.BlockedChannelSlice)):
-        base = read_rows(t.base, idx)
-        return np.ascontiguousarray(base[:, t.coff:t.coff + t.shape[1]])
-    if isinstance(t, dev.BlockedHalf):
-        return read_rows(t.dense(), idx)
-    assert isinstance(t, dev.DeviceTensor) and t.dtype == np.float32, type(t)
-    per = int(np.prod(t.shape[1:], dtype=np.int64))
-    out = np.empty((len(idx),) + tuple(t.shape[1:]), dtype=np.float32)
-    for j, i in enumerate(idx):
-        assert 0 <= i < t.shape[0]
-        dev.call('pvhip_memcpy_d2h', ctypes.c_void_p(out[j].ctypes.data), ctypes.c_void_p(t.ptr + int(i) * per * 4), per * 4)
-    return out
-
-
-def family(G, ex, g):
-    convs = g['convs']
-    if not convs:
-        return ' + '.join(G.nodes[n]['type'] for n in g['nodes'])
-    from pyopenvino_amd.op_plugins import Convolution
-    node = G.nodes[convs[-1]]
-    f16_kind = node.get('_hip_f16') or G.nodes[g['launch']].get('_hip_f16')        # FP16 IRs: what the launch's kernel recorded
-    fam = 'f16 ' + f16_kind if f16_kind else Convolution.kernel_kind(node)[0]
-    if 'Winograd' in fam and 'stem' not in fam:
-        fam += ' / ' + wino4_form(node)
-    lead = [G.nodes[n]['type'] for n in g['nodes'] if n not in convs and G.nodes[n]['type'] in ('MaxPool', 'LRN')]
-    return ' + '.join(lead + [fam])
-
-
-def is_blocked(t):
-    from pyopenvino_amd import device as dev
-    return isinstance(t, (dev.BlockedHalf, dev.BlockedChannelSlice))
+wino4_form, conv_family, is_blocked, report = ref64.wino4_form, ref64.conv_family, ref64.is_blocked, ref64.report
 
 
 def check_pass(net, ex, f16=False, only=None):
-    """Every group of the plan (`only`: the first groups of the schedule, by count) against ref64 on SAMPLE.  -> {family: (worst excess,
-    layer name)}."""
-    G = net.G
-    gs = ref64.groups(ex)
-    if only is not None:
-        gs = gs[:only]
-    consts, worst, held = {}, {}, {}
-    for g in gs:
-        ins = {src: held[src] if src in held else read_rows(G.nodes[src[0]]['output'][src[1]]['data'], SAMPLE) for src in g['inputs']}
-        held = ins                                       # the members of a sibling launch share it; the previous launch's inputs go
-        out_t = G.nodes[g['output'][0]]['output'][g['output'][1]]['data']
-        got = read_rows(out_t, SAMPLE)
-        name = G.nodes[g['nodes'][-1]]['name']
-        fam = family(G, ex, g)
-        ref = ref64.eval_group(G, g, ins, f16=f16, consts=consts)
-        assert got.shape == ref.shape, '{}: {} != {}'.format(name, got.shape, ref.shape)
-        assert np.isfinite(got).all(), '{}: non-finite values'.format(name)
-        # fp16 outputs: blocked tensors, and the AvgPool of a blocked tensor (fp32 storage holding the fp16 values the reference's float16
-        # AvgPool returns; tests/test_hip_ops.py::test_avgpool_on_a_blocked_tensor)
-        fp16_out = is_blocked(out_t) or (G.nodes[g['nodes'][-1]]['type'] == 'AvgPool' and
-                                         any(is_blocked(G.nodes[s_[0]]['output'][s_[1]]['data']) for s_ in g['inputs']))
-        if f16 and fp16_out:
-            slack = None
-            if g['launch'] in ex._stem_conv:
-                # pool1 -> norm1 -> conv2/3x3_reduce in one launch: the normalised tensor becomes an fp16 operand inside the launch, rounded
-                # from the kernel's fp32 LRN, so each operand may sit one fp16 rounding away from f16r(float64 LRN)
-                slack = _operand_slack(G, g, ins)
-            ex_ = ref64.f16_excess(got, ref, slack)
-            assert ex_ <= 1.0, '{} ({}): an element is {:.2f} x outside one fp16 rounding'.format(name, fam, ex_)
-        elif f16:
-            helpers.assert_close(got, ref, 1e-5, '{} ({})'.format(name, fam))
-            ex_ = helpers.elementwise_excess(got, ref)
-        else:
-            wino = any('Winograd' in conv_family(G.nodes[c]) for c in g['convs'])
-            ex_ = ref64.check_group(got, ref, winograd=wino, what='{} ({})'.format(name, fam))
-        if ex_ >= worst.get(fam, (-1.0, ''))[0]:
-            worst[fam] = (ex_, name)
-        del got, ref
-    return worst
-
-
-def conv_family(node):
-    from pyopenvino_amd.op_plugins import Convolution
-    return Convolution.kernel_kind(node)[0]
-
-
-def _operand_slack(G, g, ins):
-    """2**-11 x (|W| * |x|), x the float64 input of the group's convolution: how far one fp16 rounding of each of its operands can move
-    its output."""
-    cid = g['convs'][0]
-    k = g['nodes'].index(cid)
-    feeder = g['nodes'][k - 1]
-    x = ref64.eval_group(G, dict(g, nodes=g['nodes'][:k], output=(feeder, next(iter(G.nodes[feeder]['output'])))), ins)
-    wsrc = next(tuple(G.edges[(p, cid)]['connection'][:2]) for p in G.pred[cid] if G.edges[(p, cid)]['connection'][3] == 1)
-    a = G.nodes[cid]['data']
-    return 2.0 ** -11 * ref64.convolution(np.abs(x), np.abs(ref64.const_value(G, *wsrc)), ref64._ints(a['strides']),
-                                          ref64._ints(a['pads_begin']), ref64._ints(a['pads_end']))
-
-
-def report(worst, what):
-    print('\n{}: worst element-wise excess per kernel family (<= 1 passes)'.format(what))
-    for fam, (ex_, name) in sorted(worst.items(), key=lambda kv: -kv[1][0]):
-        print('  {:8.4f}  {:60s} {}'.format(ex_, fam, name))
+    return ref64.check_pass(net, ex, SAMPLE, f16=f16, only=only)
 
 
 def _googlenet_input():

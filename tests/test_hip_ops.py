@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import helpers
+import ref64
 from helpers import assert_bit_exact, assert_close, first_out, load_case
 
 pytestmark = pytest.mark.gpu
@@ -1776,3 +1777,92 @@ def test_convolution_input_beyond_32bit_offsets_is_refused_loudly(hip):
     n = ctypes.create_string_buffer(256)
     hip.call('pvhip_device_name', n, 256)
     assert n.value.decode().strip()[0] not in '(', n.value      # a marketing name, or the architecture's, in front of the parenthesis
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The nontemporal forms of the streaming kernels at test sizes.  PVHIP_STREAM_NT=2 takes them at any size (by default they start at
+# 64 MiB moved, i.e. only on the batch-128 SSD pass); PVHIP_STREAM_WG=1 caps the grid of the runs-of-four kernels (unary_f4_kernel<Op,
+# true, 4>, binary_channel4_kernel<..., true, 4>) at kNumCU x 2 = 512 workgroups, so one sweep covers 512 x 4 x 256 float4 (8 MiB) and
+# the tensors below make the run loop wrap five to six times, end part-way through a sweep, and leave a float4 tail past the last whole
+# run (n4 % 1024 != 0) and, for the unary kernel, a scalar tail (n % 4 != 0).
+NT_UNARY = (7, 1519807)                 # n = 10638649: n % 4 = 1, n4 = 2659662 = 2597 runs of 1024 (5 sweeps + 37) + 334
+NT_CH4 = (5, 37, 236, 236)              # inner % 4 == 0: binary_channel4_kernel; n4 = 2575940 = 2515 runs (4 sweeps + 467) + 580
+NT_FAMILIES = ['unary', 'binary', 'maxpool', 'depthwise']
+
+
+def _nt_outputs(monkeypatch, capfd, family, mode):
+    """({case: (type, inputs, attributes, fused bias, output)}, the pool3 plan lines libpvhip printed) of the family's launches under
+    PVHIP_STREAM_NT=mode, PVHIP_STREAM_WG=1."""
+    from pyopenvino_amd import device as dev
+    helpers.setenv(monkeypatch, 'PVHIP_STREAM_WG', '1')
+    helpers.setenv(monkeypatch, 'PVHIP_POOL3_VERBOSE', '1')
+    helpers.setenv(monkeypatch, 'PVHIP_STREAM_NT', mode)
+    capfd.readouterr()
+    out = {}
+
+    def run(case, type_, ins, data=None, bias=None):
+        node = make_node(type_, ins, data)
+        if bias is not None:                                # depthwise with bias + Clamp 0..6 fused, as every SSD depthwise layer
+            node['_fuse_bias'], node['_fuse_act'] = dev.DeviceTensor.from_numpy(bias), ('clamp', 0.0, 6.0)
+        out[case] = (type_, ins, data, bias, np.asarray(first_out(hip_plugin(type_).compute(node, dict(enumerate(ins))))))
+
+    if family == 'unary':
+        x = rnd(71, NT_UNARY, 3.0)
+        run('ReLU', 'ReLU', [x])
+        run('Clamp', 'Clamp', [x], {'min': '0', 'max': '6'})
+        run('Sigmoid', 'Sigmoid', [x])
+    elif family == 'binary':
+        a, a2, c = rnd(72, NT_UNARY), rnd(73, NT_UNARY), rnd(74, (1, NT_CH4[1], 1, 1))
+        big = rnd(75, NT_CH4)
+        bc = {'auto_broadcast': 'numpy'}
+        odd, s1 = np.ascontiguousarray(big[:, :, :235, :235]), rnd(76, (1, 1, 1, 1))
+        for op in ('Add', 'Multiply'):
+            run(op + ' same shape', op, [a, a2], bc)                                    # binary_same_kernel<Op, true>
+            run(op + ' per channel', op, [big, c], bc)                                  # binary_channel4_kernel<Op, false, true, 4>
+            run(op + ' per channel, odd plane', op, [odd, c], bc)                       # inner % 4 != 0: binary_channel_kernel
+            run(op + ' strided', op, [big, rnd(77, (1, NT_CH4[1], 1, NT_CH4[3]))], bc)  # binary_strided_kernel
+        # Add broadcasts its second operand only (the reference's rule); Multiply the smaller one, either way round
+        run('Multiply per channel, swapped', 'Multiply', [c, big], bc)                  # the broadcast operand first
+        run('Add scalar', 'Add', [odd, s1], bc)                                         # SSD's preprocessing: binary_channel_kernel, C = 1
+        run('Multiply scalar', 'Multiply', [s1, odd], bc)
+    elif family == 'maxpool':
+        for xs, st, pb, pe, rounding in (((7, 192, 56, 56), (2, 2), (0, 0), (0, 0), 'ceil'), ((9, 256, 28, 28), (1, 1), (1, 1), (1, 1), 'ceil'),
+                                         ((9, 480, 28, 28), (2, 2), (0, 0), (0, 0), 'ceil'), ((5, 832, 14, 14), (1, 1), (1, 1), (1, 1), 'ceil')):
+            run('MaxPool {} s{}'.format(xs, st[0]), 'MaxPool', [rnd(sum(xs), xs, 1.0, -0.3)], pool_data((3, 3), st, pb, pe, rounding))
+    else:
+        for xs, st, pb, pe in (((5, 32, 150, 150), (1, 1), (1, 1), (1, 1)), ((5, 64, 150, 150), (2, 2), (0, 0), (1, 1)),
+                               ((7, 128, 75, 75), (2, 2), (1, 1), (1, 1)), ((9, 256, 38, 38), (2, 2), (0, 0), (1, 1)),
+                               ((9, 512, 19, 19), (1, 1), (1, 1), (1, 1)), ((7, 1024, 10, 10), (1, 1), (1, 1), (1, 1))):
+            x = np.clip(rnd(sum(xs), xs, 3.0, 2.0), 0, 6)
+            w, b = rnd(78, (xs[1], 1, 1, 3, 3), 0.4), rnd(79, (1, xs[1], 1, 1))
+            run('depthwise {} s{}'.format(xs, st[0]), 'GroupConvolution', [x, w], conv_data(st, pb, pe, 'same_upper'), bias=b)
+    plans = [l_ for l_ in capfd.readouterr().err.splitlines() if l_.startswith('pool3 ')]
+    return out, plans
+
+
+@pytest.mark.parametrize('family', NT_FAMILIES)
+def test_nontemporal_streaming_forms_at_small_sizes(hip, monkeypatch, capfd, family):
+    """Every kernel that reads PVHIP_STREAM_NT, in its nontemporal form (=2) on a grid capped by PVHIP_STREAM_WG=1: the same bits as the
+    plain form (=0) -- a nontemporal access must not change a value -- and the reference's values: bit for bit against the oracle for
+    the ops of helpers.BIT_EXACT, ref64.check_group against float64 for Sigmoid and depthwise + bias + Clamp 0..6."""
+    nt, nt_plans = _nt_outputs(monkeypatch, capfd, family, '2')
+    plain, plain_plans = _nt_outputs(monkeypatch, capfd, family, '0')
+    if family in ('maxpool', 'depthwise'):               # every launch on the cols kernel (its pool3 plan found), in both modes
+        for case, (_, ins, _, _, _) in nt.items():
+            n, c, h, w = ins[0].shape
+            tag = 'pool3 planes={} {}x{}->'.format(n * c, h, w)
+            for plans in (nt_plans, plain_plans):
+                assert any(l_.startswith(tag) and ': ok ' in l_ for l_ in plans), (case, plans)
+    assert nt.keys() == plain.keys()
+    for case, (type_, ins, data, bias, got) in nt.items():
+        assert_bit_exact(got, plain[case][4], case + ': nontemporal vs plain')
+        if type_ == 'Sigmoid':
+            ref64.check_group(got, ref64.sigmoid(ins[0]), what=case)
+        elif type_ == 'GroupConvolution':
+            st, pb, pe = (ref64._ints(data[k]) for k in ('strides', 'pads_begin', 'pads_end'))
+            conv = ref64.group_convolution_depthwise(ins[0], ins[1], st, pb, pe, data['auto_pad'])
+            ref64.check_group(got, np.clip(conv + bias, 0.0, 6.0), what=case)
+        else:
+            assert type_ in helpers.BIT_EXACT
+            want = first_out(oracle_plugin(type_).compute(make_node(type_, ins, data), dict(enumerate(ins)), kernel_type='special'))
+            assert_bit_exact(got, np.asarray(want, dtype=np.float32), case + ' vs oracle')

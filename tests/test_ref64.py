@@ -1,6 +1,7 @@
-"""tests/ref64.py -- the float64 reference the batch-256 layer checks hold the kernels against -- pinned on the CPU: against the oracle on
-seeded small shapes, against the reference's recorded per-op outputs, and a self-test showing that the comparison those checks use
-rejects subtle corruptions of a convolution's output.  CPU only."""
+"""tests/ref64.py -- the float64 reference the layer checks (GoogLeNet at batch 256, SSD-MobileNet at batch 128) hold the kernels
+against -- pinned on the CPU: against the oracle on seeded small shapes and SSD's depthwise geometries, against the reference's recorded
+per-op outputs, self-tests showing that the comparison those checks use rejects subtle corruptions of a convolution's and of a depthwise
+layer's output, and the groups of both plans.  CPU only."""
 import os
 
 import numpy as np
@@ -110,7 +111,69 @@ def test_eltwise_concat_matmul_softmax_vs_oracle():
         assert np.isnan(ref64.softmax_rows(np.array([[800.0, 1.0]]))).any()
 
 
-REF64_TYPES = ('Convolution', 'MaxPool', 'AvgPool', 'LRN', 'Add', 'ReLU', 'Clamp', 'Concat', 'MatMul', 'SoftMax')
+# SSD-MobileNet's depthwise layers: (x shape, strides, pads_begin, pads_end) -- stride 1 with (1,1)/(1,1), stride 2 with the (0,0)/(1,1)
+# pads of same_upper on even extents and (1,1)/(1,1) on 75x75, on 150^2, 75^2, 38^2, 19^2, 10^2, 5^2 and a 1x1 plane
+DW_CASES = [
+    ((2, 6, 150, 150), (1, 1), (1, 1), (1, 1)),          # Conv2d_1_depthwise
+    ((2, 5, 150, 150), (2, 2), (0, 0), (1, 1)),          # Conv2d_2_depthwise
+    ((2, 7, 75, 75), (1, 1), (1, 1), (1, 1)),            # Conv2d_3_depthwise
+    ((2, 7, 75, 75), (2, 2), (1, 1), (1, 1)),            # Conv2d_4_depthwise (odd extent: 38 = ceil(75 / 2))
+    ((2, 9, 38, 38), (2, 2), (0, 0), (1, 1)),            # Conv2d_6_depthwise
+    ((3, 8, 19, 19), (1, 1), (1, 1), (1, 1)),            # Conv2d_7..11_depthwise
+    ((3, 8, 19, 19), (2, 2), (1, 1), (1, 1)),            # Conv2d_12_depthwise
+    ((2, 16, 10, 10), (1, 1), (1, 1), (1, 1)),           # Conv2d_13_depthwise
+    ((2, 16, 10, 10), (2, 2), (0, 0), (1, 1)),           # 10 -> 5 with the extra layers' pads
+    ((3, 4, 5, 5), (2, 2), (1, 1), (1, 1)),              # 5 -> 3
+    ((3, 4, 5, 5), (1, 1), (1, 1), (1, 1)),
+    ((3, 6, 1, 1), (1, 1), (1, 1), (1, 1)),              # a 1x1 plane: only the centre tap reads the image
+    ((2, 6, 2, 2), (2, 2), (0, 0), (1, 1)),              # 2 -> 1
+]
+
+
+def dw_data(st, pb, pe, auto_pad='same_upper'):
+    return {'strides': '{},{}'.format(*st), 'pads_begin': '{},{}'.format(*pb), 'pads_end': '{},{}'.format(*pe), 'auto_pad': auto_pad,
+            'dilations': '1,1'}
+
+
+@pytest.mark.parametrize('xs,st,pb,pe', DW_CASES, ids=lambda v: 'x'.join(map(str, v)) if isinstance(v, tuple) else str(v))
+def test_group_convolution_depthwise_vs_oracle(xs, st, pb, pe):
+    x, w = rnd(30, xs), rnd(31, (xs[1], 1, 1, 3, 3), 0.4)
+    for auto_pad in ('same_upper', 'explicit'):
+        ref = ref64.eval_node(node('GroupConvolution', dw_data(st, pb, pe, auto_pad)), [x, w])
+        want = ops.group_convolution_depthwise(x, w, st, pb, pe, auto_pad)
+        pinned(ref, want, 'depthwise {} stride {} pads {} {} {}'.format(xs, st, pb, pe, auto_pad))
+    # the padding is where the IR says: at the end for (0,0)/(1,1) -- the first output reads no zero row or column
+    if pb == (0, 0) and xs[2] >= 3:
+        assert np.allclose(ref[:, :, 0, 0], (x[:, :, :3, :3].astype(np.float64) * w[None, :, 0, 0].astype(np.float64)).sum(axis=(2, 3)),
+                           rtol=1e-12, atol=1e-12)
+
+
+def test_group_convolution_is_not_rounded_to_fp16():
+    """f16=True rounds Convolution / MatMul operands only: an FP16 IR runs depthwise on the fp32 kernel."""
+    x, w = rnd(32, (2, 4, 7, 7)), rnd(33, (4, 1, 1, 3, 3), 0.4)
+    n_ = node('GroupConvolution', dw_data((1, 1), (1, 1), (1, 1)))
+    assert np.array_equal(ref64.eval_node(n_, [x, w], f16=True), ref64.eval_node(n_, [x, w]))
+    c = node('Convolution', dw_data((1, 1), (1, 1), (1, 1)))
+    wc = rnd(34, (3, 4, 3, 3), 0.4)
+    assert not np.array_equal(ref64.eval_node(c, [x, wc], f16=True), ref64.eval_node(c, [x, wc]))
+
+
+def test_multiply_sigmoid_transpose_vs_oracle():
+    a, s_, ch = rnd(40, (3, 5, 4, 3)), rnd(41, (1, 1, 1, 1)), rnd(42, (1, 5, 1, 1))
+    for x, y in ((a, s_), (s_, a), (a, ch), (ch, a), (a, rnd(43, (3, 5, 4, 3)))):
+        pinned(ref64.eval_node(node('Multiply', {}), [x, y]), ops.multiply(x, y), 'Multiply {} {}'.format(x.shape, y.shape))
+    x = rnd(44, (2, 1, 191, 91), 6.0)                       # SSD's conf logits: both tails of the curve
+    pinned(ref64.eval_node(node('Sigmoid', {}), [x]), ops.sigmoid(x), 'Sigmoid')
+    for shape, order in (((2, 12, 19, 19), (0, 2, 3, 1)), ((3, 546, 1, 1), (0, 2, 3, 1)), ((2, 5, 3, 4), (3, 1, 0, 2))):
+        x = rnd(45, shape)
+        got = ref64.eval_node(node('Transpose', {}), [x, np.array(order, dtype=np.int64)])
+        assert np.array_equal(got, np.ascontiguousarray(x.transpose(order)).astype(np.float64)), 'Transpose {} {}'.format(shape, order)
+        # the order arrives as a float64 Const when eval_group reads it from the IR
+        assert np.array_equal(got, ref64.transpose(x, np.array(order, dtype=np.float64)))
+
+
+REF64_TYPES = ('Convolution', 'GroupConvolution', 'MaxPool', 'AvgPool', 'LRN', 'Add', 'Multiply', 'ReLU', 'Clamp', 'Sigmoid', 'Concat',
+               'Transpose', 'Reshape', 'MatMul', 'SoftMax')
 
 
 def _fixtures():
@@ -128,7 +191,7 @@ def test_ref64_vs_reference_fixture(path):
     ins = [inputs[p] for p in sorted(inputs)]
     with np.errstate(over='ignore', invalid='ignore'):
         got = ref64.eval_node(node_, ins)
-    if node_['type'] in ('MaxPool', 'ReLU', 'Clamp', 'Concat'):
+    if node_['type'] in ('MaxPool', 'ReLU', 'Clamp', 'Concat', 'Transpose', 'Reshape'):
         assert np.array_equal(got.astype(np.float32), want, equal_nan=True), node_['name']
     else:
         pinned(got, want, node_['name'])
@@ -219,3 +282,144 @@ def test_groups_of_the_batch256_plan_cover_every_node_once():
     names = [G.nodes[g['nodes'][0]]['name'] for g in gs]
     assert names[:4] == ['data/mean', 'pool1/3x3_s2', 'conv2/3x3/WithoutBiases', 'conv2/norm26321'], names[:4]
     assert sum(len(g['convs']) for g in gs) == sum(G.nodes[n]['type'] == 'Convolution' for n in G.nodes) == 57
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the comparison rejects subtly wrong depthwise layers (SSD's stride-2 form: pads (0,0)/(1,1), bias + Clamp 0..6 fused)
+def _dw_layer():
+    x = np.clip(rnd(50, (3, 16, 10, 10), 3.0, 2.0), 0, 6)          # a Clamp 0..6 output, as the pointwise layer before hands it over
+    w = rnd(51, (16, 1, 1, 3, 3), 0.5)
+    b = rnd(52, (1, 16, 1, 1), 1.0)
+    return x, w, b
+
+
+def _dw_out(x, w, b, pb=(0, 0), pe=(1, 1), clamp_first=False):
+    conv = ref64.group_convolution_depthwise(x, w, (2, 2), pb, pe)
+    return np.clip(conv, 0, 6) + b if clamp_first else np.clip(conv + b, 0, 6)
+
+
+def _dw_corruptions():
+    x, w, b = _dw_layer()
+    ref = _dw_out(x, w, b)
+    bad = {'pads at the beginning': _dw_out(x, w, b, pb=(1, 1), pe=(0, 0))}
+    w2 = w.copy()
+    w2[9] = w[8]
+    bad['weights of the neighbouring channel'] = _dw_out(x, w2, b)
+    c = ref.copy()
+    c[1, :, -1, :] = 0
+    bad['last output row zeroed'] = c
+    bad['Clamp at 6 before the bias'] = _dw_out(x, w, b, clamp_first=True)
+    # the last output column's right-hand padding tap reads the next image's first column (a tile that runs past its plane)
+    conv = ref64.group_convolution_depthwise(x, w, (2, 2), (0, 0), (1, 1))
+    for ky in range(3):
+        oy = np.arange(5)[np.arange(5) * 2 + ky < 10]                # output rows whose tap row ky is inside the image
+        conv[0, :, oy, -1] += x[1, :, oy * 2 + ky, 0] * w[:, 0, 0, ky, 2]             # (rows, channels): advanced indices first
+    bad['padding tap read from the next image'] = np.clip(conv + b, 0, 6)
+    return ref, bad
+
+
+def test_clean_depthwise_passes_the_check():
+    ref, _ = _dw_corruptions()
+    assert ref64.check_group(ref.astype(np.float32), ref) <= 0.1
+
+
+@pytest.mark.parametrize('kind', ['pads at the beginning', 'weights of the neighbouring channel', 'last output row zeroed',
+                                  'Clamp at 6 before the bias', 'padding tap read from the next image'])
+def test_check_rejects_a_subtly_wrong_depthwise_layer(kind):
+    ref, bad = _dw_corruptions()
+    got = bad[kind].astype(np.float32)
+    assert not np.array_equal(got, ref.astype(np.float32)), kind
+    with pytest.raises(AssertionError):
+        ref64.check_group(got, ref, what=kind)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# DetectionOutput records: a near-tie of the oracle's scores may swap ranks, anything else may not
+def _records():
+    rng = np.random.default_rng(60)
+    want = np.zeros((100, 7), dtype=np.float32)
+    want[:40, 0] = np.arange(40)
+    want[:40, 1] = rng.integers(1, 91, 40)
+    want[:40, 2] = np.sort(rng.uniform(0.3, 0.9, 40))[::-1]
+    want[4, 2] = want[3, 2] * np.float32(1 - 3e-7)                  # a near-tie: records 3 and 4
+    want[3, 1], want[4, 1] = 17, 52
+    want[:40, 3:5] = rng.uniform(0, 0.5, (40, 2))
+    want[:40, 5:7] = want[:40, 3:5] + rng.uniform(0.05, 0.5, (40, 2))
+    want[40] = (-1, 0, 0, 0, 0, 0, 0)                                 # the terminator
+    return want
+
+
+def test_detection_records_compare_near_ties_as_a_set_and_reject_the_rest():
+    want = _records()
+    assert ref64.compare_detections(want.copy(), want, 'same') == 40
+    got = want.copy()
+    got[[3, 4], 1:] = got[[4, 3], 1:]                               # the tied pair in the other order: the same records
+    assert ref64.compare_detections(got, want, 'tie swapped') == 40
+    bad = {kind: want.copy() for kind in ('two records out of order', 'a wrong class', 'a score off by 1e-3', 'a box corner off',
+                                           'a detection lost')}
+    bad['two records out of order'][[9, 10], 1:] = want[[10, 9], 1:]
+    bad['a wrong class'][20, 1] += 1
+    bad['a score off by 1e-3'][7, 2] *= np.float32(1 + 1e-3)
+    bad['a box corner off'][30, 5] += np.float32(2e-3)
+    bad['a detection lost'][39:41] = want[40:42]
+    for kind, c in bad.items():
+        with pytest.raises(AssertionError):
+            ref64.compare_detections(c, want, kind)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# groups() on the SSD plan bench.py times (ssd_mobilenet_v1_coco fp32, batch 128, whole IR): no device needed to plan
+def test_groups_of_the_ssd_batch128_plan_cover_every_node_once():
+    """Every node belongs to exactly one group, the prior-box subgraph included: the loader folds its VALUES (PriorBoxClustered
+    computes its boxes once and hands the same device tensor out on every pass) but keeps its nodes as tasks, so no node is outside a
+    group.  The prior-box subgraph is exactly the part of the graph that does not depend on the image (the layer check reads it whole,
+    not by image).  The 47 fused chains are groups that end at the chain's last port; no placeholder port is an output."""
+    import networkx as nx
+    from pyopenvino_amd import device, synth
+    device.load_library()
+    z = np.load(os.path.join(helpers.GOLDEN, 'ssd_full_e2e.npz'))
+    blob = synth.synth_weights(os.path.join(helpers.MODELS, 'ssd_mobilenet_v1_coco.xml'), int(z['weight_seed']))
+    _, net, ex = helpers.build_network('pyopenvino_amd.op_plugins', 'ssd_mobilenet_v1_coco', weights=blob, batch=128)
+    G = net.G
+    gs = ref64.groups(ex)
+    seen = [n for g in gs for n in g['nodes']]
+    assert len(seen) == len(set(seen))
+    rest = {n for n in G.nodes if G.nodes[n]['type'] not in ('Const', 'Parameter', 'Result')} - set(seen)
+    assert rest == set(), sorted(G.nodes[n]['name'] for n in rest)
+    # the image-independent nodes: not reachable from the input once the ShapeOf edges (shape, not data) are cut
+    param = next(n for n in G.nodes if G.nodes[n]['type'] == 'Parameter')
+    data = nx.DiGraph([(u, v) for u, v in G.edges if G.nodes[v]['type'] != 'ShapeOf'])
+    per_image = nx.descendants(data, param)
+    static = sorted(G.nodes[n]['name'] for n in seen if n not in per_image)
+    assert static == ref64.SSD_PRIOR_BOX_SUBGRAPH, static
+    by_name = {G.nodes[n]['name']: n for n in G.nodes}
+    for name in ref64.SSD_PRIOR_BOX_SUBGRAPH:                         # each a group of its own
+        assert next(g for g in gs if by_name[name] in g['nodes'])['nodes'] == [by_name[name]], name
+    outs = {g['output'] for g in gs}
+    for g in gs:
+        assert g['output'][0] == g['nodes'][-1]
+        for src in g['inputs']:
+            assert src in outs or src[0] == param, (g, src)
+    # the fused chains: 34 Convolution + 13 GroupConvolution; Clamp 0..6 last, or the bias Add for the 12 box / class predictors
+    chains = {cid: ref64._chain(ex, cid) for cid in ex._fusion}
+    assert sorted(G.nodes[c]['type'] for c in chains).count('Convolution') == 34
+    assert sorted(G.nodes[c]['type'] for c in chains).count('GroupConvolution') == 13 and len(chains) == 47
+    by_out = {g['output']: g for g in gs}
+    clamped, predictors = 0, 0
+    for cid, chain in chains.items():
+        last = chain[-1]
+        g = by_out.get(ref64._port(G, last))
+        assert g is not None and g['nodes'] == chain, G.nodes[cid]['name']
+        f = ex._fusion[cid]
+        if f['relu'] is not None:
+            a = G.nodes[last]['data']
+            assert G.nodes[last]['type'] == 'Clamp' and float(a['min']) == 0.0 and float(a['max']) == 6.0 and f['act'] == ('clamp', 0.0, 6.0)
+            clamped += 1
+        else:
+            assert G.nodes[last]['type'] == 'Add' and last == f['add'] and 'Predictor' in G.nodes[cid]['name'], G.nodes[cid]['name']
+            predictors += 1
+    assert (clamped, predictors) == (35, 12)
+    assert sum(len(g['convs']) for g in gs) == sum(G.nodes[n]['type'] == 'Convolution' for n in G.nodes) == 34
+    # placeholder ports -- the convolution of every chain, the bias Add of a chain that goes on to a Clamp -- are never an output
+    placeholders = set(chains) | {f['add'] for f in ex._fusion.values() if f['relu'] is not None}
+    assert not placeholders & {o[0] for o in outs}
