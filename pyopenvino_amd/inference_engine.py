@@ -14,9 +14,11 @@ Differences from the reference, all outside the numeric path:
   * plugins are discovered as modules of a package (default ``pyopenvino_amd.op_plugins``) instead of a
     CWD-relative glob;
   * ``infer`` can shard the batch across ranks (one process per GPU): every rank runs the unchanged
-    scheduler on its slice and the Result plugin all-gathers the Result tensors.
+    scheduler on its slice and the Result plugin all-gathers the Result tensors;
+  * the format a caller hands an input in can be declared (``IENetwork.input_info``: input_format.py) and is fixed at ``load_network``;
+    host arrays of a declared format, or in a request's own page-locked buffers, are staged by the request's ``HostInputs``
+    (host_input.py).
 """
-import collections
 import contextlib
 import copy
 import ctypes
@@ -32,6 +34,8 @@ import networkx as nx
 import numpy as np
 
 from . import common_def, device, fusion_plan, stream_plan
+from .host_input import HostInputs
+from .input_format import InputInfo, PreProcessChannel, PreProcessInfo  # noqa: F401 -- the classes of IENetwork.input_info
 from .stream_plan import CaptureStreamModel
 
 DEFAULT_PLUGIN_PACKAGE = 'pyopenvino_amd.op_plugins'
@@ -107,227 +111,15 @@ class IECore:
         """`num_requests` (accepted and ignored by the reference, inference_engine.py:86) is the number of infer
         requests that may be in flight at once: `exenet.requests[i].start_async(inputs)` / `.wait()`, each request
         with its own graph state and its own compute streams.  `exenet.infer()` stays the synchronous call."""
-        for info in network.input_info.values():     # (the declared input formats are shared with every request's copy of the network)
+        for info in network.input_info.values():
             info._check_at_load()
-        exenet = Executable_Network(network)
+        # the declared input formats as fixed values: one mapping, shared by every request
+        exenet = Executable_Network(network, {name: info.frozen() for name, info in network.input_info.items()})
         self.check_nodes(exenet.ienet.G)
         exenet.schedule_tasks()
         exenet.create_requests(max(1, int(num_requests)))
         network._loaded = True               # input_info is fixed from here on
         return exenet
-
-
-class InputInfo:
-    """The format a caller hands one network input in (OpenVINO 2021's ``IENetwork.input_info[name]``): ``precision`` 'FP32' (default)
-    or 'U8', ``layout`` 'NCHW' (default) or 'NHWC'.  A U8 value v means float(v); an NHWC array is ``x.transpose(0, 3, 1, 2)`` of the NCHW
-    tensor the IR expects -- a cv2 image as it is, where the reference's callers hand ``img.transpose((2, 0, 1)).astype(np.float32)``.
-    Set between ``read_network`` and ``load_network``.  A declared input is uploaded as it is and converted on the device
-    (``pvhip_input_to_nchw_f32``); an input whose format is never set goes the default way.  ``preprocess_info`` adds a resize of a source
-    of any extent, channel reversal and mean / scale to that launch (``pvhip_input_preprocess_f32``)."""
-    PRECISIONS = ('FP32', 'U8')
-    LAYOUTS = ('NCHW', 'NHWC')
-
-    def __init__(self, net, nid):
-        self._net, self._nid = net, nid
-        self._precision, self._layout = 'FP32', 'NCHW'
-        self.declared = False           # precision or layout set explicitly (to any value)
-
-    @property
-    def name(self):
-        return self._net.G.nodes[self._nid]['name']
-
-    @property
-    def dims(self):
-        """The NCHW shape of the tensor the IR expects."""
-        return tuple(int(d) for d in self._net.G.nodes[self._nid]['data']['shape'])
-
-    def supported(self):
-        """Declared formats exist for 4-D Parameters whose element type is f32 (FP16 IRs read with fp16_as_fp32 are, once promoted)."""
-        data = self._net.G.nodes[self._nid]['data']
-        return len(tuple(data['shape'])) == 4 and str(data.get('element_type', '')).lower() == 'f32'
-
-    @property
-    def precision(self):
-        return self._precision
-
-    @precision.setter
-    def precision(self, value):
-        self._precision = self._checked('precision', value, self.PRECISIONS)
-
-    @property
-    def layout(self):
-        return self._layout
-
-    @layout.setter
-    def layout(self, value):
-        self._layout = self._checked('layout', value, self.LAYOUTS)
-
-    def _checked(self, what, value, allowed):
-        self._check_not_loaded(what)
-        if not isinstance(value, str) or value.upper() not in allowed:
-            raise ValueError('input {}: {} {!r} is not one of {}'.format(self.name, what, value, allowed))
-        self._declare(what)
-        return value.upper()
-
-    def _check_not_loaded(self, what):
-        if getattr(self._net, '_loaded', False):
-            raise ValueError('input {}: set input_info[...].{} between read_network and load_network, not after'.format(self.name, what))
-
-    def _declare(self, what):
-        """A valid value of `what` is being set: refused after load_network and for inputs without declared formats; else the input is
-        declared from now on."""
-        self._check_not_loaded(what)
-        if not self.supported():
-            self._unsupported(what)
-        self.declared = True
-
-    def _unsupported(self, what):
-        data = self._net.G.nodes[self._nid]['data']
-        raise NotImplementedError('input {}: a declared {} needs a 4-D f32 Parameter; this one is {} {}'.format(
-            self.name, what, data.get('element_type'), tuple(data['shape'])))
-
-    @property
-    def preprocess_info(self):
-        """The preprocessing the device applies to this input (OpenVINO 2021's ``input_info[name].preprocess_info``): PreProcessInfo."""
-        if not self.supported():
-            self._unsupported('preprocess_info')
-        pre = self.__dict__.get('_pre')
-        if pre is None:
-            pre = self._pre = PreProcessInfo(self)
-        return pre
-
-    def preprocessing(self):
-        """(resize, reverse_channels, (mean, std_scale) or None) as declared; (False, False, None) when nothing is."""
-        pre = self.__dict__.get('_pre')
-        if pre is None:
-            return False, False, None
-        means = (np.array([ch.mean_value for ch in pre._channels], np.float32), np.array([ch.std_scale for ch in pre._channels], np.float32))
-        return pre.resize_algorithm == 'RESIZE_BILINEAR', bool(pre.reverse_channels), means if pre.mean_variant == 'MEAN_VALUE' else None
-
-    def _check_at_load(self):
-        pre = self.__dict__.get('_pre')
-        if pre is not None and pre.mean_variant == 'MEAN_VALUE' and len(pre._channels) != self.dims[1]:
-            raise ValueError('input {}: mean_variant MEAN_VALUE with {} channels (preprocess_info.init), the input has {}'.format(
-                self.name, len(pre._channels), self.dims[1]))
-
-    def source_extent(self, source_size=None):
-        """The (h, w) a caller's array has: `source_size` with RESIZE_BILINEAR declared, else the network's own."""
-        n, c, h, w = self.dims
-        if source_size is None:
-            return h, w
-        sh, sw = (int(v) for v in source_size)
-        if (sh, sw) != (h, w) and not self.preprocessing()[0]:
-            raise ValueError('input {}: source size {} differs from the network\'s {} and no resize is declared '
-                             '(preprocess_info.resize_algorithm = \'RESIZE_BILINEAR\')'.format(self.name, (sh, sw), (h, w)))
-        if sh < 1 or sw < 1:
-            raise ValueError('input {}: source size {} is empty'.format(self.name, (sh, sw)))
-        return sh, sw
-
-    def host_format(self, source_size=None):
-        """(shape, dtype) of the array a caller hands in this format; with RESIZE_BILINEAR declared, `source_size` = (h, w) of the source
-        (default: the network's extent)."""
-        n, c, _, _ = self.dims
-        h, w = self.source_extent(source_size)
-        return ((n, h, w, c) if self._layout == 'NHWC' else (n, c, h, w)), np.dtype(np.uint8 if self._precision == 'U8' else np.float32)
-
-
-class PreProcessChannel:
-    """One channel of PreProcessInfo: ``mean_value`` (default 0) and ``std_scale`` (default 1, never 0)."""
-
-    def __init__(self, owner, index):
-        self._owner, self._index = owner, index
-        self._mean, self._std = 0.0, 1.0
-
-    @property
-    def mean_value(self):
-        return self._mean
-
-    @mean_value.setter
-    def mean_value(self, value):
-        value = self._owner._number('mean_value', value)
-        self._owner._info._declare('preprocess_info[c].mean_value')
-        self._mean = value
-
-    @property
-    def std_scale(self):
-        return self._std
-
-    @std_scale.setter
-    def std_scale(self, value):
-        value = self._owner._number('std_scale', value)
-        if value == 0:
-            raise ValueError('input {}: std_scale of channel {} is 0 in fp32'.format(self._owner._info.name, self._index))
-        self._owner._info._declare('preprocess_info[c].std_scale')
-        self._std = value
-
-
-class PreProcessInfo:
-    """What the device does to an input before the network reads it (OpenVINO 2021's PreProcessInfo; pvhip_input_preprocess_f32, in one
-    launch with the format change of ``precision`` / ``layout``):
-      * ``resize_algorithm``: 'NO_RESIZE' (default) or 'RESIZE_BILINEAR' -- a source of any (h, w) is resized to the Parameter's extent
-        (half-pixel centres, clamped at the border, as cv2 INTER_LINEAR; no antialiasing, so large downscales alias); a source at the
-        network's own extent is not resized at all;
-      * ``reverse_channels``: output channel c takes source channel C-1-c (a BGR frame into an RGB-trained IR);
-      * ``mean_variant``: 'NONE' (default) or 'MEAN_VALUE': y = (v - self[c].mean_value) / self[c].std_scale, after ``init(C)``.
-    Set between ``read_network`` and ``load_network``, like ``precision``; setting anything makes the input declared."""
-    RESIZE_ALGORITHMS = ('NO_RESIZE', 'RESIZE_BILINEAR')
-    MEAN_VARIANTS = ('NONE', 'MEAN_VALUE')
-
-    def __init__(self, info):
-        self._info = info
-        self._resize, self._mean_variant, self._reverse = 'NO_RESIZE', 'NONE', False
-        self._channels = []
-
-    @property
-    def resize_algorithm(self):
-        return self._resize
-
-    @resize_algorithm.setter
-    def resize_algorithm(self, value):
-        self._resize = self._info._checked('preprocess_info.resize_algorithm', value, self.RESIZE_ALGORITHMS)
-
-    @property
-    def mean_variant(self):
-        return self._mean_variant
-
-    @mean_variant.setter
-    def mean_variant(self, value):
-        self._mean_variant = self._info._checked('preprocess_info.mean_variant', value, self.MEAN_VARIANTS)
-
-    @property
-    def reverse_channels(self):
-        return self._reverse
-
-    @reverse_channels.setter
-    def reverse_channels(self, value):
-        if not isinstance(value, (bool, np.bool_)):
-            raise ValueError('input {}: preprocess_info.reverse_channels {!r} is not a bool'.format(self._info.name, value))
-        self._info._declare('preprocess_info.reverse_channels')
-        self._reverse = bool(value)
-
-    def init(self, num_channels: int):
-        """num_channels channels of mean 0 and scale 1 (MEAN_VALUE needs as many as the input has)."""
-        if isinstance(num_channels, bool) or not isinstance(num_channels, (int, np.integer)) or num_channels < 1:
-            raise ValueError('input {}: preprocess_info.init({!r}) needs a channel count >= 1'.format(self._info.name, num_channels))
-        self._info._declare('preprocess_info.init')
-        self._channels = [PreProcessChannel(self, k) for k in range(int(num_channels))]
-
-    def __len__(self):
-        return len(self._channels)
-
-    def __getitem__(self, index):
-        if not isinstance(index, (int, np.integer)) or not 0 <= index < len(self._channels):
-            raise IndexError('input {}: preprocess_info[{!r}]: {} channels (preprocess_info.init)'.format(self._info.name, index, len(self._channels)))
-        return self._channels[index]
-
-    def _number(self, what, value):
-        """`value` as the fp32 number the device uses; finite in fp32, or ValueError (nothing is declared here: the setter does that once
-        every check has passed)."""
-        ok = not isinstance(value, bool) and isinstance(value, (int, float, np.integer, np.floating))
-        with np.errstate(over='ignore'):
-            if not (ok and np.isfinite(np.float32(value))):
-                raise ValueError('input {}: {} {!r} is not a finite fp32 number'.format(self._info.name, what, value))
-        return float(np.float32(value))
 
 
 class IENetwork:
@@ -342,14 +134,15 @@ class IENetwork:
         self.outputs = None
         self.batch_size = 1
         self.f16_mfma = False      # FP16 IR read with fp16_as_fp32=False: Convolution / MatMul on the f16 matrix cores
+        self._input_info = None    # {Parameter name: InputInfo}, made when first asked for (the graph is built by then)
+        self._loaded = False       # load_network has taken the input formats: their setters refuse from then on
 
     @property
     def input_info(self) -> dict:
         """{Parameter name: InputInfo}: the format each input is handed in (set before load_network)."""
-        info = self.__dict__.get('_input_info')
-        if info is None:
-            info = self._input_info = {self.G.nodes[n]['name']: InputInfo(self, n) for n in self.G.nodes if self.G.nodes[n]['type'] == 'Parameter'}
-        return info
+        if self._input_info is None:
+            self._input_info = {self.G.nodes[n]['name']: InputInfo(self, n) for n in self.G.nodes if self.G.nodes[n]['type'] == 'Parameter'}
+        return self._input_info
 
     # ------------------------------------------------------------------ IR reading
     def read_IR_Model(self, model, weights=None):
@@ -515,7 +308,7 @@ class InferRequest:
         if self._in_flight:
             raise RuntimeError('request {} is still in flight: wait() first'.format(self.index))
         ex = self.runner
-        inputs = ex._stage_host_inputs(inputs)
+        inputs = ex.host_inputs.stage(inputs, ex.stream_base)
         # The same device-resident tensors as the last calls: the pass is replayed from this request's own recording (one call
         # instead of ~100 dispatches; every request records its own pass on its own stream and keeps its own tensors, so the
         # replays of several requests run side by side like their eager passes do).
@@ -554,10 +347,7 @@ class InferRequest:
         Ownership: the request reads this memory until its pass is done.  Fill it only between ``wait()`` (or before the first
         ``start_async``) and the next ``start_async()``; writing it while the request is in flight changes what the pass may see.  The
         memory is returned when the request's device state is released and the array is no longer referenced."""
-        info = self.runner.ienet.input_info.get(name)
-        if info is None:
-            raise KeyError('no network input named {!r}'.format(name))
-        return self.runner._host_input(name, info.source_extent(source_size))['host']
+        return self.runner.host_inputs.buffer(name, source_size)
 
 
 @contextlib.contextmanager
@@ -574,7 +364,8 @@ def _overridden(obj, **values):
 
 
 class Executable_Network:
-    def __init__(self, ienetwork: IENetwork):
+    def __init__(self, ienetwork: IENetwork, input_formats: dict = None):
+        """`input_formats`: {input name: InputFormat} as load_network froze them (default: as `ienetwork` declares them now)."""
         self.ienet = ienetwork
         self.kernel_type = 'hip'        # the reference's 'naive' / 'numpy' / 'special' are accepted too
         self.expected_result = None     # {node name: [precision, dims, ndarray]} (the reference's format) or {node name: ndarray}: per-layer compare hook (cf. :284-287)
@@ -606,7 +397,9 @@ class Executable_Network:
         self._order_events, self._events_in_flight = [], []
         self._event_pool = []           # timed events for the device_timing brackets
         self._pending = None            # (allocation epoch or None, event) of a pass issued without a host wait: wait_done() ends it
-        self._host_inputs = {}          # {input name: page-locked staging of it} (_host_input)
+        if input_formats is None:
+            input_formats = {name: info.frozen() for name, info in ienetwork.input_info.items()}
+        self.host_inputs = HostInputs(input_formats)    # host arrays in a declared format or the request's own buffers -> device tensors
         self._graph = None              # the recorded pass (capture_graph): {'handle', 'inputs', 'keep', 'results', 'by_hand'}
         self._auto_graph = {'key': None, 'seen': 0, 'failed': False, 'captured': False}     # infer()'s own recording (_graph_for)
         self._auto_graph_busy = False   # _graph_for is recording
@@ -617,6 +410,7 @@ class Executable_Network:
         self._graph_safe = all(getattr(registry.get(G.nodes[n]['type']), 'GRAPH_CAPTURE_SAFE', False) for n in G.nodes)
 
     _stream_ops = None                  # tests: a list that collects the cross-stream waits of a pass as they are issued
+    MAX_SOURCE_EXTENTS = HostInputs.MAX_SOURCE_EXTENTS
 
     def create_requests(self, count: int):
         """Request 0 runs on this network's own graph; the others on copies of it made now, before anything has been
@@ -639,7 +433,7 @@ class Executable_Network:
             twin.G = copy.deepcopy(self.ienet.G)
             twin.inputs = self.ienet.ie.construct_node_info(twin, 'Parameter')
             twin.outputs = self.ienet.ie.construct_node_info(twin, 'Result')
-            runner = Executable_Network(twin)
+            runner = Executable_Network(twin, self.host_inputs.formats)
             runner.fuse_epilogues = self.fuse_epilogues
             runner.schedule_tasks()
             self.requests.append(InferRequest(self, runner, i))
@@ -653,7 +447,7 @@ class Executable_Network:
         infer uploads and packs again.  A captured hipGraph holds raw addresses of exactly these tensors (packed weights, cached
         constants, Concat buffers): it goes first, or a later infer_graph() would replay kernels over freed or reused pool blocks."""
         self.release_graph()
-        self._host_inputs = {}                      # page-locked buffers go back once the caller holds no view of them
+        self.host_inputs.release()                  # page-locked buffers go back once the caller holds no view of them
         G = self.ienet.G
         for nid in G.nodes:
             node = G.nodes[nid]
@@ -1168,7 +962,7 @@ class Executable_Network:
         return self._graph
 
     def infer(self, inputs: dict, verbose: bool = False) -> dict:
-        inputs = self._stage_host_inputs(inputs)
+        inputs = self.host_inputs.stage(inputs, self.stream_base)
         if self._graph_for(inputs, verbose) is None:
             return self._infer_eager(inputs, verbose)
         return self.infer_graph(inputs)
@@ -1194,105 +988,3 @@ class Executable_Network:
         if verbose:
             print('@TOTAL_TIME,', time.time() - t0)
         return {name: G.nodes[nid]['result'] for nid, name in self.ienet.find_node_by_type('Result')}
-
-    # ---- host inputs in a declared format (IENetwork.input_info) or from a request's own page-locked buffer (InferRequest.input_buffer)
-    MAX_SOURCE_EXTENTS = 4              # source extents (h, w) of a resized input whose buffers a request keeps at once
-
-    def _input_slot(self, name):
-        """What this request keeps for input `name` whatever the source extent: the fp32 NCHW tensor the pass reads -- the same address on
-        every call, so the pass is recorded and replayed like a device-resident one whatever the source size --, the copy's event, the
-        declared format and preprocessing, and {extent: staging of that extent} (_host_input)."""
-        slot = self._host_inputs.get(name)
-        if slot is None:
-            info = self.ienet.input_info[name]
-            if not info.supported():
-                raise NotImplementedError('input {}: page-locked input buffers exist for 4-D f32 Parameters only'.format(name))
-            resize, reverse, means = info.preprocessing()
-            # mean / scale: c floats each, uploaded once per request with the rest of its input state (load_network needs no device)
-            mean, std = (None, None) if means is None else (device.DeviceTensor.from_numpy(means[0]), device.DeviceTensor.from_numpy(means[1]))
-            slot = {'fixed': device.DeviceTensor.empty(info.dims), 'event': device.Event(timed=False), 'extents': collections.OrderedDict(),
-                    'u8': info.precision == 'U8', 'nhwc': info.layout == 'NHWC', 'reverse': reverse, 'mean': mean, 'std': std}
-            self._host_inputs[name] = slot
-        return slot
-
-    def _host_input(self, name, extent=None):
-        """This request's staging of input `name` for sources of `extent` (h, w) (default: the network's): the page-locked host array and
-        the device tensor it is uploaded into (the fixed tensor itself for FP32 NCHW at the network's extent).  It holds no reference back
-        to the slot, so dropping the slot or the extent frees its memory at once."""
-        info = self.ienet.input_info[name]
-        slot = self._input_slot(name)
-        extent = tuple(extent) if extent is not None else tuple(info.dims[2:])
-        staged = slot['extents'].get(extent)
-        if staged is None:
-            shape, dtype = info.host_format(extent)
-            preprocess = extent != tuple(info.dims[2:]) or slot['reverse'] or slot['mean'] is not None
-            convert = preprocess or info.precision != 'FP32' or info.layout != 'NCHW'
-            staged = {'host': device.host_empty(shape, dtype), 'extent': extent, 'preprocess': preprocess,
-                      'staging': device.DeviceTensor.empty(shape, dtype) if convert else slot['fixed']}
-            slot['extents'][extent] = staged
-        return staged
-
-    def _drop_old_extents(self, name, keep):
-        """Release the staging of all but the MAX_SOURCE_EXTENTS most recently fed extents of input `name` (called while this request has
-        no pass in flight: nothing reads those buffers any more)."""
-        extents = self._host_inputs[name]['extents']
-        extents.move_to_end(keep)
-        while len(extents) > self.MAX_SOURCE_EXTENTS:
-            extents.popitem(last=False)
-
-    def _source_extent_of(self, info, a):
-        """(h, w) of the caller's array `a` for input `info`, checked against the declared format."""
-        shape, dtype = info.host_format()
-        resize = info.preprocessing()[0]
-        if not resize:
-            if a.shape != shape:
-                raise ValueError('input {}: declared {} / {} means shape {}, got {}'.format(info.name, info.precision, info.layout, shape, a.shape))
-            return tuple(info.dims[2:])
-        n, c = info.dims[:2]
-        if a.ndim != 4 or (a.shape[0], a.shape[3] if info.layout == 'NHWC' else a.shape[1]) != (n, c):
-            raise ValueError('input {}: declared {} / {} with RESIZE_BILINEAR means shape {} for any h, w; got {}'.format(
-                info.name, info.precision, info.layout, (n, 'h', 'w', c) if info.layout == 'NHWC' else (n, c, 'h', 'w'), a.shape))
-        return info.source_extent(a.shape[1:3] if info.layout == 'NHWC' else a.shape[2:4])
-
-    def _stage_host_inputs(self, inputs: dict) -> dict:
-        """Inputs handed in a declared format, or in this request's own buffer, become the request's fixed fp32 NCHW device tensor: the
-        caller's array is copied into the page-locked buffer of its extent unless it IS that buffer, the buffer is uploaded on the copy
-        stream, this request's first stream waits for the copy's event and converts (one launch; none for FP32 NCHW at the network's
-        extent): pvhip_input_preprocess_f32 when a resize, channel reversal or mean / scale is in effect, else pvhip_input_to_nchw_f32.
-        No host synchronisation.  Every other input is returned unchanged (and goes the default way)."""
-        out = dict(inputs)
-        for name, arr in inputs.items():
-            info = self.ienet.input_info.get(name)
-            if info is None or isinstance(arr, (device.DeviceTensor, device.ChannelSlice, device.BlockedHalf)):
-                continue
-            slot = self._host_inputs.get(name)
-            own = None
-            if slot is not None and isinstance(arr, np.ndarray):
-                own = next((s for s in slot['extents'].values() if arr.shape == s['host'].shape and arr.dtype == s['host'].dtype
-                            and arr.ctypes.data == s['host'].ctypes.data), None)
-            if own is None and not info.declared:
-                continue
-            staged = own
-            if staged is None:
-                a = np.asarray(arr)
-                staged = self._host_input(name, self._source_extent_of(info, a))
-                np.copyto(staged['host'], a, casting='same_kind' if staged['host'].dtype == np.float32 else 'safe')
-            self._drop_old_extents(name, staged['extent'])
-            slot = self._host_inputs[name]
-            host, fixed = staged['host'], slot['fixed']
-            device.select_stream(device.COPY_STREAM)
-            device.call('pvhip_memcpy_h2d_async', ctypes.c_void_p(staged['staging'].ptr), ctypes.c_void_p(host.ctypes.data), host.nbytes)
-            slot['event'].record()
-            device.select_stream(self.stream_base)
-            slot['event'].wait()
-            if staged['preprocess']:
-                ptr = lambda t: ctypes.c_void_p(t.ptr) if t is not None else None       # noqa: E731
-                device.call('pvhip_input_preprocess_f32', ctypes.c_void_p(staged['staging'].ptr), ctypes.c_void_p(fixed.ptr), *fixed.shape[:2],
-                            *staged['extent'], *fixed.shape[2:], int(slot['u8']), int(slot['nhwc']), int(slot['reverse']),
-                            ptr(slot['mean']), ptr(slot['std']))
-            elif staged['staging'] is not fixed:
-                device.call('pvhip_input_to_nchw_f32', ctypes.c_void_p(staged['staging'].ptr), ctypes.c_void_p(fixed.ptr),
-                            *fixed.shape, int(slot['u8']), int(slot['nhwc']))
-            device.select_stream(0)
-            out[name] = fixed
-        return out

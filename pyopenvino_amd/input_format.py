@@ -1,0 +1,276 @@
+"""The format a caller hands a network input in: what is declared between ``read_network`` and ``load_network`` (InputInfo, PreProcessInfo,
+PreProcessChannel: OpenVINO 2021's ``IENetwork.input_info``) and the fixed value it becomes at load (InputFormat), which owns the shape
+arithmetic of that format.  Host only: nothing here touches the device (host_input.py stages arrays of these formats)."""
+import dataclasses
+
+import numpy as np
+
+
+@dataclasses.dataclass(frozen=True, eq=False)
+class InputFormat:
+    """One input's format as a fixed value (``InputInfo.frozen()``; load_network makes one per input and every request reads that one):
+    ``dims`` the (n, c, h, w) of the fp32 tensor the IR expects, ``supported`` / ``declared`` as InputInfo has them, ``u8`` / ``nhwc`` the
+    declared precision and layout, ``resize`` / ``reverse`` / ``mean`` / ``std`` the declared preprocessing (fp32 arrays of c values, or
+    None without MEAN_VALUE).  An extent is the (h, w) of a caller's array."""
+    name: str
+    dims: tuple
+    supported: bool
+    declared: bool
+    u8: bool
+    nhwc: bool
+    resize: bool
+    reverse: bool
+    mean: np.ndarray
+    std: np.ndarray
+
+    @property
+    def host_dtype(self):
+        return np.dtype(np.uint8 if self.u8 else np.float32)
+
+    def host_shape(self, extent=None):
+        """The shape of a caller's array of `extent` (default: the network's own) in this layout."""
+        n, c = self.dims[:2]
+        h, w = extent if extent is not None else self.dims[2:]
+        return (n, h, w, c) if self.nhwc else (n, c, h, w)
+
+    def checked_extent(self, source_size=None):
+        """The (h, w) a caller's array has: `source_size` with RESIZE_BILINEAR declared, else the network's own."""
+        n, c, h, w = self.dims
+        if source_size is None:
+            return h, w
+        sh, sw = (int(v) for v in source_size)
+        if (sh, sw) != (h, w) and not self.resize:
+            raise ValueError('input {}: source size {} differs from the network\'s {} and no resize is declared '
+                             '(preprocess_info.resize_algorithm = \'RESIZE_BILINEAR\')'.format(self.name, (sh, sw), (h, w)))
+        if sh < 1 or sw < 1:
+            raise ValueError('input {}: source size {} is empty'.format(self.name, (sh, sw)))
+        return sh, sw
+
+    def extent_of(self, a):
+        """(h, w) of the caller's array `a`, checked against this format."""
+        declared = 'declared {} / {}'.format('U8' if self.u8 else 'FP32', 'NHWC' if self.nhwc else 'NCHW')
+        if not self.resize:
+            if a.shape != self.host_shape():
+                raise ValueError('input {}: {} means shape {}, got {}'.format(self.name, declared, self.host_shape(), a.shape))
+            return tuple(self.dims[2:])
+        if a.ndim != 4 or (a.shape[0], a.shape[3 if self.nhwc else 1]) != self.dims[:2]:
+            raise ValueError('input {}: {} with RESIZE_BILINEAR means shape {} for any h, w; got {}'.format(
+                self.name, declared, self.host_shape(('h', 'w')), a.shape))
+        return self.checked_extent(a.shape[1:3] if self.nhwc else a.shape[2:4])
+
+    def needs_preprocess(self, extent) -> bool:
+        """Arrays of `extent` go through pvhip_input_preprocess_f32: something besides the format change is in effect."""
+        return tuple(extent) != tuple(self.dims[2:]) or self.reverse or self.mean is not None
+
+    def needs_convert(self, extent) -> bool:
+        """Arrays of `extent` are not the fp32 NCHW tensor itself: they are uploaded into a staging tensor and converted by one launch."""
+        return self.needs_preprocess(extent) or self.u8 or self.nhwc
+
+
+class InputInfo:
+    """The format a caller hands one network input in (OpenVINO 2021's ``IENetwork.input_info[name]``): ``precision`` 'FP32' (default)
+    or 'U8', ``layout`` 'NCHW' (default) or 'NHWC'.  A U8 value v means float(v); an NHWC array is ``x.transpose(0, 3, 1, 2)`` of the NCHW
+    tensor the IR expects -- a cv2 image as it is, where the reference's callers hand ``img.transpose((2, 0, 1)).astype(np.float32)``.
+    Set between ``read_network`` and ``load_network``.  A declared input is uploaded as it is and converted on the device
+    (``pvhip_input_to_nchw_f32``); an input whose format is never set goes the default way.  ``preprocess_info`` adds a resize of a source
+    of any extent, channel reversal and mean / scale to that launch (``pvhip_input_preprocess_f32``)."""
+    PRECISIONS = ('FP32', 'U8')
+    LAYOUTS = ('NCHW', 'NHWC')
+
+    def __init__(self, net, nid):
+        self._net, self._nid = net, nid
+        self._precision, self._layout = 'FP32', 'NCHW'
+        self.declared = False           # precision or layout set explicitly (to any value)
+        self._pre = None                # PreProcessInfo, once preprocess_info has been asked for
+
+    @property
+    def name(self):
+        return self._net.G.nodes[self._nid]['name']
+
+    @property
+    def dims(self):
+        """The NCHW shape of the tensor the IR expects."""
+        return tuple(int(d) for d in self._net.G.nodes[self._nid]['data']['shape'])
+
+    def supported(self):
+        """Declared formats exist for 4-D Parameters whose element type is f32 (FP16 IRs read with fp16_as_fp32 are, once promoted)."""
+        data = self._net.G.nodes[self._nid]['data']
+        return len(tuple(data['shape'])) == 4 and str(data.get('element_type', '')).lower() == 'f32'
+
+    @property
+    def precision(self):
+        return self._precision
+
+    @precision.setter
+    def precision(self, value):
+        self._precision = self._checked('precision', value, self.PRECISIONS)
+
+    @property
+    def layout(self):
+        return self._layout
+
+    @layout.setter
+    def layout(self, value):
+        self._layout = self._checked('layout', value, self.LAYOUTS)
+
+    def _checked(self, what, value, allowed):
+        self._check_not_loaded(what)
+        if not isinstance(value, str) or value.upper() not in allowed:
+            raise ValueError('input {}: {} {!r} is not one of {}'.format(self.name, what, value, allowed))
+        self._declare(what)
+        return value.upper()
+
+    def _check_not_loaded(self, what):
+        if self._net._loaded:
+            raise ValueError('input {}: set input_info[...].{} between read_network and load_network, not after'.format(self.name, what))
+
+    def _declare(self, what):
+        """A valid value of `what` is being set: refused after load_network and for inputs without declared formats; else the input is
+        declared from now on."""
+        self._check_not_loaded(what)
+        if not self.supported():
+            self._unsupported(what)
+        self.declared = True
+
+    def _unsupported(self, what):
+        data = self._net.G.nodes[self._nid]['data']
+        raise NotImplementedError('input {}: a declared {} needs a 4-D f32 Parameter; this one is {} {}'.format(
+            self.name, what, data.get('element_type'), tuple(data['shape'])))
+
+    @property
+    def preprocess_info(self):
+        """The preprocessing the device applies to this input (OpenVINO 2021's ``input_info[name].preprocess_info``): PreProcessInfo."""
+        if not self.supported():
+            self._unsupported('preprocess_info')
+        if self._pre is None:
+            self._pre = PreProcessInfo(self)
+        return self._pre
+
+    def frozen(self) -> InputFormat:
+        """The format as declared now, as a fixed value (load_network takes it once the setters refuse)."""
+        pre, mean, std = self._pre, None, None
+        if pre is not None and pre.mean_variant == 'MEAN_VALUE':
+            mean = np.array([ch.mean_value for ch in pre._channels], np.float32)
+            std = np.array([ch.std_scale for ch in pre._channels], np.float32)
+        return InputFormat(self.name, self.dims, self.supported(), self.declared, self._precision == 'U8', self._layout == 'NHWC',
+                           pre is not None and pre.resize_algorithm == 'RESIZE_BILINEAR', pre is not None and pre.reverse_channels, mean, std)
+
+    def preprocessing(self):
+        """(resize, reverse_channels, (mean, std_scale) or None) as declared; (False, False, None) when nothing is."""
+        f = self.frozen()
+        return f.resize, f.reverse, (f.mean, f.std) if f.mean is not None else None
+
+    def _check_at_load(self):
+        pre = self._pre
+        if pre is not None and pre.mean_variant == 'MEAN_VALUE' and len(pre._channels) != self.dims[1]:
+            raise ValueError('input {}: mean_variant MEAN_VALUE with {} channels (preprocess_info.init), the input has {}'.format(
+                self.name, len(pre._channels), self.dims[1]))
+
+    def source_extent(self, source_size=None):
+        """The (h, w) a caller's array has: `source_size` with RESIZE_BILINEAR declared, else the network's own."""
+        return self.frozen().checked_extent(source_size)
+
+    def host_format(self, source_size=None):
+        """(shape, dtype) of the array a caller hands in this format; with RESIZE_BILINEAR declared, `source_size` = (h, w) of the source
+        (default: the network's extent)."""
+        f = self.frozen()
+        return f.host_shape(f.checked_extent(source_size)), f.host_dtype
+
+
+class PreProcessChannel:
+    """One channel of PreProcessInfo: ``mean_value`` (default 0) and ``std_scale`` (default 1, never 0)."""
+
+    def __init__(self, owner, index):
+        self._owner, self._index = owner, index
+        self._mean, self._std = 0.0, 1.0
+
+    @property
+    def mean_value(self):
+        return self._mean
+
+    @mean_value.setter
+    def mean_value(self, value):
+        value = self._owner._number('mean_value', value)
+        self._owner._info._declare('preprocess_info[c].mean_value')
+        self._mean = value
+
+    @property
+    def std_scale(self):
+        return self._std
+
+    @std_scale.setter
+    def std_scale(self, value):
+        value = self._owner._number('std_scale', value)
+        if value == 0:
+            raise ValueError('input {}: std_scale of channel {} is 0 in fp32'.format(self._owner._info.name, self._index))
+        self._owner._info._declare('preprocess_info[c].std_scale')
+        self._std = value
+
+
+class PreProcessInfo:
+    """What the device does to an input before the network reads it (OpenVINO 2021's PreProcessInfo; pvhip_input_preprocess_f32, in one
+    launch with the format change of ``precision`` / ``layout``):
+      * ``resize_algorithm``: 'NO_RESIZE' (default) or 'RESIZE_BILINEAR' -- a source of any (h, w) is resized to the Parameter's extent
+        (half-pixel centres, clamped at the border, as cv2 INTER_LINEAR; no antialiasing, so large downscales alias); a source at the
+        network's own extent is not resized at all;
+      * ``reverse_channels``: output channel c takes source channel C-1-c (a BGR frame into an RGB-trained IR);
+      * ``mean_variant``: 'NONE' (default) or 'MEAN_VALUE': y = (v - self[c].mean_value) / self[c].std_scale, after ``init(C)``.
+    Set between ``read_network`` and ``load_network``, like ``precision``; setting anything makes the input declared."""
+    RESIZE_ALGORITHMS = ('NO_RESIZE', 'RESIZE_BILINEAR')
+    MEAN_VARIANTS = ('NONE', 'MEAN_VALUE')
+
+    def __init__(self, info):
+        self._info = info
+        self._resize, self._mean_variant, self._reverse = 'NO_RESIZE', 'NONE', False
+        self._channels = []
+
+    @property
+    def resize_algorithm(self):
+        return self._resize
+
+    @resize_algorithm.setter
+    def resize_algorithm(self, value):
+        self._resize = self._info._checked('preprocess_info.resize_algorithm', value, self.RESIZE_ALGORITHMS)
+
+    @property
+    def mean_variant(self):
+        return self._mean_variant
+
+    @mean_variant.setter
+    def mean_variant(self, value):
+        self._mean_variant = self._info._checked('preprocess_info.mean_variant', value, self.MEAN_VARIANTS)
+
+    @property
+    def reverse_channels(self):
+        return self._reverse
+
+    @reverse_channels.setter
+    def reverse_channels(self, value):
+        if not isinstance(value, (bool, np.bool_)):
+            raise ValueError('input {}: preprocess_info.reverse_channels {!r} is not a bool'.format(self._info.name, value))
+        self._info._declare('preprocess_info.reverse_channels')
+        self._reverse = bool(value)
+
+    def init(self, num_channels: int):
+        """num_channels channels of mean 0 and scale 1 (MEAN_VALUE needs as many as the input has)."""
+        if isinstance(num_channels, bool) or not isinstance(num_channels, (int, np.integer)) or num_channels < 1:
+            raise ValueError('input {}: preprocess_info.init({!r}) needs a channel count >= 1'.format(self._info.name, num_channels))
+        self._info._declare('preprocess_info.init')
+        self._channels = [PreProcessChannel(self, k) for k in range(int(num_channels))]
+
+    def __len__(self):
+        return len(self._channels)
+
+    def __getitem__(self, index):
+        if not isinstance(index, (int, np.integer)) or not 0 <= index < len(self._channels):
+            raise IndexError('input {}: preprocess_info[{!r}]: {} channels (preprocess_info.init)'.format(self._info.name, index, len(self._channels)))
+        return self._channels[index]
+
+    def _number(self, what, value):
+        """`value` as the fp32 number the device uses; finite in fp32, or ValueError (nothing is declared here: the setter does that once
+        every check has passed)."""
+        ok = not isinstance(value, bool) and isinstance(value, (int, float, np.integer, np.floating))
+        with np.errstate(over='ignore'):
+            if not (ok and np.isfinite(np.float32(value))):
+                raise ValueError('input {}: {} {!r} is not a finite fp32 number'.format(self._info.name, what, value))
+        return float(np.float32(value))

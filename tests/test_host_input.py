@@ -1,6 +1,7 @@
 """Host inputs in a declared format (IENetwork.input_info: U8 / NHWC), uploaded asynchronously from page-locked per-request buffers
 (InferRequest.input_buffer) and converted on the device (pvhip_input_to_nchw_f32).  The first tests need no GPU."""
 import ctypes
+import functools
 import os
 import subprocess
 import sys
@@ -61,6 +62,77 @@ def test_input_info_outside_4d_f32_parameters_is_not_implemented():
     net.G.nodes[nid]['data']['shape'] = (1, 784)
     with pytest.raises(NotImplementedError):
         net.input_info[name].layout = 'NHWC'
+
+
+def _shape(layout, n, c, h, w):
+    return (n, h, w, c) if layout == 'NHWC' else (n, c, h, w)
+
+
+@functools.lru_cache(maxsize=None)
+def _weights(model):
+    """mnist ships its weights; the other IRs get seeded synthetic ones."""
+    from pyopenvino_amd import synth
+    return None if model == 'mnist' else synth.synth_weights(os.path.join(MODELS, model + '.xml'), 7)
+
+
+def _declared_net(model, precision, layout, resize):
+    from pyopenvino_amd import IECore
+    ie = IECore(plugin_package=HIP)
+    net = ie.read_network(os.path.join(MODELS, model + '.xml'), weights=_weights(model))
+    info = net.input_info[net.inputs[0]['name']]
+    info.precision, info.layout = precision, layout
+    if resize:
+        info.preprocess_info.resize_algorithm = 'RESIZE_BILINEAR'
+    return ie, net, info
+
+
+def _bad_arrays(info, precision, layout, resize, other):
+    """[(array of a shape the format refuses, the ValueError text infer() gives for it)]: a wrong batch, a wrong channel count and, with
+    no resize declared, a wrong extent.  The texts are written out here (and were compared with what the engine raised through infer()
+    before the shape checks moved into InputFormat), not taken from the code under test."""
+    n, c, h, w = info.dims
+    dtype = np.uint8 if precision == 'U8' else np.float32
+    if resize:
+        means = 'declared {} / {} with RESIZE_BILINEAR means shape {} for any h, w'.format(precision, layout, _shape(layout, n, c, 'h', 'w'))
+        shapes = [_shape(layout, n + 1, c, *other), _shape(layout, n, c + 1, *other), _shape(layout, n, c, *other)[1:]]
+        return [(np.empty(s, dtype), 'input {}: {}; got {}'.format(info.name, means, s)) for s in shapes]
+    means = 'declared {} / {} means shape {}'.format(precision, layout, _shape(layout, n, c, h, w))
+    shapes = [_shape(layout, n + 1, c, h, w), _shape(layout, n, c + 1, h, w), _shape(layout, n, c, *other)]
+    return [(np.empty(s, dtype), 'input {}: {}, got {}'.format(info.name, means, s)) for s in shapes]
+
+
+@pytest.mark.parametrize('resize', [False, True])
+@pytest.mark.parametrize('layout', ['NCHW', 'NHWC'])
+@pytest.mark.parametrize('precision', ['FP32', 'U8'])
+@pytest.mark.parametrize('model,other', [('mnist', (40, 50)), ('googlenet-v1', (256, 320))])
+def test_frozen_format_owns_the_shape_rules(model, other, precision, layout, resize):
+    """InputFormat (InputInfo.frozen()) against InputInfo.host_format at the network's extent and at one other, and the refusals of
+    arrays with a wrong batch, channel count or (no resize declared) extent, by extent_of and by infer() alike."""
+    ie, net, info = _declared_net(model, precision, layout, resize)
+    fmt = info.frozen()
+    n, c, h, w = info.dims
+    assert (fmt.name, fmt.dims, fmt.supported, fmt.declared) == (info.name, info.dims, True, True)
+    assert (fmt.u8, fmt.nhwc, fmt.resize, fmt.reverse, fmt.mean, fmt.std) == (precision == 'U8', layout == 'NHWC', resize, False, None, None)
+    for extent in [(h, w), other] if resize else [(h, w)]:
+        shape, dtype = info.host_format(extent)
+        assert shape == _shape(layout, n, c, *extent) and dtype == np.dtype(np.uint8 if precision == 'U8' else np.float32)
+        assert (fmt.host_shape(extent), fmt.host_dtype) == (shape, dtype)
+        assert fmt.checked_extent(extent) == extent
+        assert fmt.extent_of(np.empty(shape, dtype)) == extent
+        assert fmt.needs_preprocess(extent) == (extent != (h, w))
+        assert fmt.needs_convert(extent) == (extent != (h, w) or precision == 'U8' or layout == 'NHWC')
+    assert fmt.host_shape() == info.host_format()[0] and fmt.checked_extent() == (h, w)
+    if not resize:
+        for refused in (info.host_format, fmt.checked_extent):
+            with pytest.raises(ValueError, match='no resize is declared'):
+                refused(other)
+    ex = ie.load_network(net)
+    for bad, text in _bad_arrays(info, precision, layout, resize, other):
+        with pytest.raises(ValueError) as by_format:
+            fmt.extent_of(bad)
+        with pytest.raises(ValueError) as by_infer:               # refused before anything reaches the device
+            ex.infer({info.name: bad})
+        assert str(by_format.value) == str(by_infer.value) == text
 
 
 def test_abi_declares_the_async_upload_and_the_conversion():

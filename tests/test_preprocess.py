@@ -317,10 +317,10 @@ def test_release_device_state_frees_the_input_staging_at_once(hip):
     try:
         for h, w in extents:
             ex.infer({name: rng.integers(0, 256, (4, h, w, 1), dtype=np.uint8)})
-        staged = ex._host_inputs[name]['extents']
+        staged = ex.host_inputs.slots[name].extents
         assert sorted(staged) == sorted(extents)
-        host_bytes = sum(s['host'].nbytes for s in staged.values())
-        device_bytes = sum(s['staging'].nbytes for s in staged.values())
+        host_bytes = sum(s.host.nbytes for s in staged.values())
+        device_bytes = sum(s.staging.nbytes for s in staged.values())
         del staged
         blocks0, bytes0 = device.host_stats()
         in_use0 = device.pool_stats()[0]
@@ -369,7 +369,7 @@ def test_identity_extents_with_resize_declared_give_the_format_path_bits(hip):
                 info.preprocess_info.resize_algorithm = 'RESIZE_BILINEAR'
             ex = ie.load_network(net)
             outs.append(np.array(ex.infer({name: x})[net.outputs[0]['name']], copy=True))
-            fixed.append(np.asarray(ex._host_inputs[name]['fixed']))
+            fixed.append(np.asarray(ex.host_inputs.slots[name].fixed))
         assert_bit_exact(fixed[1], fixed[0], precision + ' input tensor')
         assert_bit_exact(fixed[1], np.ascontiguousarray(x.transpose(0, 3, 1, 2)).astype(np.float32), precision + ' input tensor vs the source')
         assert_bit_exact(outs[1], outs[0], precision + ' Result')
@@ -495,4 +495,4 @@ def test_six_requests_in_flight_two_source_extents(hip):
             got = ex.wait(r)[out_name]
             assert np.array_equal(got, want[fed[r]]), 'step {} request {} (source {})'.format(step, r, extents[fed[r] % 2])
     for req in ex.requests:
-        assert len(req.runner._host_inputs[name]['extents']) <= ex.MAX_SOURCE_EXTENTS
+        assert len(req.runner.host_inputs.slots[name].extents) <= ex.MAX_SOURCE_EXTENTS
