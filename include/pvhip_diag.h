@@ -1,7 +1,7 @@
 /* Entry points of the DIAGNOSTIC build only (make -C pyopenvino_amd/csrc diag -> libpvhip_diag.so, compiled with -DPVHIP_DIAG).
  *
  * libpvhip_diag.so exports everything include/pvhip.h declares plus what is declared here: measurement probes, the predecessor
- * convolution kernels kept for A/B runs (PVHIP_CONV_KERNEL=lds|wave, PVHIP_CONV_TILE, PVHIP_CONV_PW), the wrong-on-purpose
+ * convolution kernels kept for A/B runs (csrc/pvhip_diag_conv.hip: PVHIP_CONV_KERNEL=lds|wave, PVHIP_CONV_TILE, PVHIP_CONV_PW), the wrong-on-purpose
  * ablation paths (PVHIP_*_ABLATE) and in-kernel cycle stamps.  None of it is in the product library; nothing in pyopenvino_amd/
  * needs it.  Users: bench.py (roofline.sustained), scripts/, tests/diag_variants.py.                                          */
 #ifndef PVHIP_DIAG_H

@@ -9,7 +9,6 @@ PVHIP_LIBRARY=pyopenvino_amd/libpvhip_diag.so, so that the main test process onl
 import os
 
 import numpy as np
-import pytest
 
 import helpers
 from helpers import assert_bit_exact, assert_close, first_out
@@ -112,15 +111,13 @@ def test_mfma_ceiling_probe_reports_a_plausible_rate(hip):
 
 
 
-@pytest.mark.parametrize('kernel', ['lds'])
-def test_conv_fused_bias_and_activation_bit_exact(hip, monkeypatch, kernel):
-    """Fused epilogues (bias, then ReLU or Clamp) of both convolution kernels and of the depthwise kernel equal
-    the separate Add / ReLU / Clamp launches bit for bit."""
-    if kernel != 'default':
-        helpers.setenv(monkeypatch, 'PVHIP_CONV_KERNEL', kernel)
-        helpers.setenv(monkeypatch, 'PVHIP_CONV_WINOGRAD', '0')
-    cases = [('Convolution', (2, 32, 9, 9), (40, 32, 3, 3)),     # (r,s)-major kernel (LDS-DMA by default)
-             ('Convolution', (2, 5, 9, 9), (70, 5, 3, 3)),       # c-major kernel
+def test_conv_fused_bias_and_activation_bit_exact(hip, monkeypatch):
+    """Fused epilogues (bias, then ReLU or Clamp) of both register-staged convolution kernels (PVHIP_CONV_KERNEL=lds) and of the
+    depthwise kernel equal the separate Add / ReLU / Clamp launches bit for bit."""
+    helpers.setenv(monkeypatch, 'PVHIP_CONV_KERNEL', 'lds')
+    helpers.setenv(monkeypatch, 'PVHIP_CONV_WINOGRAD', '0')
+    cases = [('Convolution', (2, 32, 9, 9), (40, 32, 3, 3)),     # conv_igemm_rs_kernel
+             ('Convolution', (2, 5, 9, 9), (70, 5, 3, 3)),       # conv_igemm_kernel<.., true>
              ('GroupConvolution', (2, 24, 11, 11), (24, 1, 1, 3, 3))]
     for type_, xs, ws in cases:
         x, w = rnd(1, xs), rnd(2, ws, 0.2)
