@@ -455,6 +455,16 @@ int         pvhip_input_to_nchw_f32(const void* src, float* dst, int n, int c, i
  * above.  n <= 65535, c <= 1024, c * h * w < 2^31 for source and destination, fp32 sources 4-byte aligned; else PVHIP_EINVAL. */
 int         pvhip_input_preprocess_f32(const void* src, float* dst, int n, int c, int src_h, int src_w, int dst_h, int dst_w,
                                        int src_u8, int src_nhwc, int reverse_channels, const float* mean, const float* std_scale);
+/* Addition to ABI v17 (the version number is unchanged: nothing existing changed): the same launch for a YUV 4:2:0 source
+ * (preprocess_info.color_format 'NV12' / 'I420'), a video decoder's frame as it is.  `src`: uint8, n frames of 3 src_h / 2 rows of src_w
+ * bytes each: the Y plane, then src_h / 2 rows of src_w / 2 interleaved (U, V) pairs (planar = 0, NV12) or the U plane and the V plane of
+ * src_h / 2 x src_w / 2 bytes each (planar = 1, I420); any alignment.  Every pixel is converted with the (U, V) of its 2 x 2 block (no
+ * chroma interpolation) by the BT.601 limited-range rule in 20-bit integers (pvhip_preprocess.hip; in numpy: tests/yuv_ref.py) to uint8
+ * B, G, R -- channel 0 is B --, and that image goes through the resize, reversal (reverse_channels = 1: R, G, B) and mean / scale of
+ * pvhip_input_preprocess_f32 with c = 3 into `dst` (n, 3, dst_h, dst_w), bit for bit what that entry gives for the converted U8 NHWC
+ * image.  n <= 65535, src_h and src_w even, 3 * h * w < 2^31 for source and destination; else PVHIP_EINVAL. */
+int         pvhip_input_preprocess_yuv_f32(const void* src, float* dst, int n, int src_h, int src_w, int dst_h, int dst_w, int planar,
+                                           int reverse_channels, const float* mean, const float* std_scale);
 
 #ifdef __cplusplus
 }

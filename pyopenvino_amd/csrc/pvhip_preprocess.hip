@@ -16,6 +16,8 @@
 //      any source alignment takes the wide loads, with byte-wise head and tail;
 //   3. has every lane produce 4 consecutive output pixels of one row, for every channel, stored as float4 nontemporal stores into each
 //      channel plane (scalar stores when the destination rows are not 16-byte aligned).
+//
+// YUV 4:2:0 frames (NV12, I420) take the same launch with a colour conversion in front of the taps: preprocess_yuv_kernel, further down.
 #include "pvhip_common.h"
 
 #pragma clang fp contract(off)
@@ -192,6 +194,177 @@ void launch(const PrepArgs& a, dim3 grid, size_t lds, bool vs, hipStream_t st) {
     else    hipLaunchKernelGGL((preprocess_kernel<U8, RESIZE, false>), grid, dim3(kBlock), lds, st, a);
 }
 
+// ---------------------------------------------------------------------------------------------------------------- YUV 4:2:0 sources
+// A decoder's frame -- uint8, 3 h / 2 rows of w bytes per image: the Y plane, then NV12's h/2 rows of w/2 (U, V) pairs or I420's U plane
+// and V plane of h/2 x w/2 bytes each -- converted to B, G, R by the BT.601 limited-range rule in 20-bit fixed point
+//   t = max(Y - 16, 0) * 1220542 + 2^19,  R = (t + 1673527 (V - 128)) >> 20,  G = (t - 852492 (V - 128) - 409993 (U - 128)) >> 20,
+//   B = (t + 2116026 (U - 128)) >> 20  (arithmetic shifts), each clamped to [0, 255],
+// with the (U, V) of the pixel's 2 x 2 block (no chroma interpolation); the uint8 image that gives is then resized, reversed and scaled
+// exactly as a U8 NHWC source is above.  tests/yuv_ref.py is the conversion in numpy; every intermediate stays within +-5.7e8.
+//
+// The kernel has preprocess_kernel's shape.  A tile stages the Y spans it reads and, behind them, the chroma spans under them: rows
+// ys0/2..ys1/2, of each the pairs xs0/2..xs1/2 of the ABSOLUTE columns (a tile may start on an odd column) -- one span per row for NV12,
+// one in each plane for I420.  A pixel is converted where it is tapped, so a downscale converts four pixels per output pixel however
+// many it staged, and the three channels of a quad come from one pass over its taps.
+struct YuvArgs {
+    const unsigned char* src;
+    float* dst;
+    const float* mean;        // NULL: no mean
+    const float* std_scale;   // NULL: no scale
+    int hs, ws, hd, wd, tw, th;
+    int planar, reverse;
+    unsigned yslot, cslot;    // LDS bytes per staged Y span and per staged chroma span (multiples of 16)
+    unsigned stage_bytes;     // LDS bytes of the staging area (the coordinate tables follow it)
+};
+
+// B, G, R (in that order) of one pixel, as the floats of the converted bytes.
+__device__ __forceinline__ void yuv_to_bgr(int y, int u, int v, float (&o)[3]) {
+    y = y - 16 < 0 ? 0 : y - 16;
+    u -= 128; v -= 128;
+    const int t = y * 1220542 + (1 << 19);
+    const int b = (t + 2116026 * u) >> 20;
+    const int g = (t - 852492 * v - 409993 * u) >> 20;
+    const int r = (t + 1673527 * v) >> 20;
+    o[0] = (float)min(max(b, 0), 255);
+    o[1] = (float)min(max(g, 0), 255);
+    o[2] = (float)min(max(r, 0), 255);
+}
+
+// grid (ceil(wd / tw), ceil(hd / th), n); dynamic LDS stage_bytes + 12 (tw + th) bytes.  VS as in preprocess_kernel.
+template <bool RESIZE, bool VS>
+__global__ __launch_bounds__(kBlock) void preprocess_yuv_kernel(YuvArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    const int n = blockIdx.z, tx0 = blockIdx.x * a.tw, ty0 = blockIdx.y * a.th;
+    const int twv = min(a.tw, a.wd - tx0), thv = min(a.th, a.hd - ty0);
+    int* cx0 = reinterpret_cast<int*>(lds + a.stage_bytes);
+    int* cx1 = cx0 + a.tw;
+    float* cfx = reinterpret_cast<float*>(cx1 + a.tw);
+    int* ry0 = reinterpret_cast<int*>(cfx + a.tw);
+    int* ry1 = ry0 + a.th;
+    float* rfy = reinterpret_cast<float*>(ry1 + a.th);
+    for (int j = threadIdx.x; j < twv; j += kBlock) {
+        const Tap t = tap<RESIZE>(tx0 + j, a.ws, a.wd);
+        cx0[j] = t.i0; cx1[j] = t.i1; cfx[j] = t.f;
+    }
+    for (int j = threadIdx.x; j < thv; j += kBlock) {
+        const Tap t = tap<RESIZE>(ty0 + j, a.hs, a.hd);
+        ry0[j] = t.i0; ry1[j] = t.i1; rfy[j] = t.f;
+    }
+    const int xs0 = tap<RESIZE>(tx0, a.ws, a.wd).i0, xs1 = tap<RESIZE>(tx0 + twv - 1, a.ws, a.wd).i1;
+    const int ys0 = tap<RESIZE>(ty0, a.hs, a.hd).i0, ys1 = tap<RESIZE>(ty0 + thv - 1, a.hs, a.hd).i1;
+    const int rows = ys1 - ys0 + 1, yspan = xs1 - xs0 + 1;
+    const int ps0 = xs0 >> 1, cr0 = ys0 >> 1, crows = (ys1 >> 1) - cr0 + 1;       // first chroma pair and row, chroma rows
+    const int cstep = a.planar ? 1 : 2;                                            // bytes from one U (V) to the next
+    const int cspan = ((xs1 >> 1) - ps0 + 1) * cstep;
+    const int hw = a.ws >> 1;
+    const unsigned char* frame = a.src + (size_t)n * ((size_t)a.hs * a.ws / 2 * 3);
+    const unsigned char* chroma = frame + (size_t)a.hs * a.ws;
+    auto y_src = [&](int r) -> const unsigned char* { return frame + (size_t)(ys0 + r) * a.ws + xs0; };
+    // chroma span s: NV12 row s of the pairs; I420 row s of U for s < crows, row s - crows of V after them
+    auto c_src = [&](int s) -> const unsigned char* {
+        if (!a.planar) return chroma + (size_t)(cr0 + s) * a.ws + 2 * ps0;
+        const int p = s >= crows ? 1 : 0;
+        return chroma + ((size_t)p * (a.hs >> 1) + cr0 + s - p * crows) * hw + ps0;
+    };
+    unsigned char* lds_c = lds + (unsigned)rows * a.yslot;
+    // one 16-byte block k of a span of `span` bytes at g, into its slot at l (byte j of the span lies at l + (g & 15) + j)
+    auto stage = [&](const unsigned char* g, int span, unsigned char* l, unsigned k) {
+        const int lo = 16 * (int)k - (int)((uintptr_t)g & 15);
+        const unsigned char* b = g + lo;
+        l += 16 * k;
+        if (lo >= 0 && lo + 16 <= span) {
+            *reinterpret_cast<u4v*>(l) = *reinterpret_cast<const u4v*>(b);
+        } else {
+            for (int t = lo < 0 ? -lo : 0; t < 16 && lo + t < span; ++t) l[t] = b[t];
+        }
+    };
+    const unsigned ybps = (unsigned)yspan / 16 + 2, cbps = (unsigned)cspan / 16 + 2;
+    const unsigned yblk = (unsigned)rows * ybps, cblk = (unsigned)(crows * (a.planar ? 2 : 1)) * cbps;
+    for (unsigned i = threadIdx.x; i < yblk + cblk; i += kBlock) {
+        if (i < yblk) {
+            const unsigned s = i / ybps;
+            stage(y_src((int)s), yspan, lds + s * a.yslot, i - s * ybps);
+        } else {
+            const unsigned s = (i - yblk) / cbps;
+            stage(c_src((int)s), cspan, lds_c + s * a.cslot, i - yblk - s * cbps);
+        }
+    }
+    __syncthreads();
+
+    const int nq = (twv + 3) >> 2;
+    const size_t plane_out = (size_t)a.hd * a.wd;
+    float* out_n = a.dst + (size_t)n * 3 * plane_out;
+    for (int i = threadIdx.x; i < thv * nq; i += kBlock) {
+        const int r = i / nq, j0 = 4 * (i - r * nq);
+        const float fy = rfy[r], gy = 1.0f - fy;
+        // the two tapped rows: their Y spans, and the U and V of the chroma rows under them
+        const unsigned char *ly[2], *lu[2], *lv[2];
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const int ya = k ? ry1[r] : ry0[r];
+            const int yr = ya - ys0, cr = (ya >> 1) - cr0;
+            ly[k] = lds + (unsigned)yr * a.yslot + ((uintptr_t)y_src(yr) & 15);
+            lu[k] = lds_c + (unsigned)cr * a.cslot + ((uintptr_t)c_src(cr) & 15);
+            lv[k] = a.planar ? lds_c + (unsigned)(crows + cr) * a.cslot + ((uintptr_t)c_src(crows + cr) & 15) : lu[k] + 1;
+        }
+        float v[3][4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int j = j0 + u < twv ? j0 + u : j0;         // (a pixel past the tile computes column j0 again and is not stored)
+            const int xa = cx0[j], xb = cx1[j];
+            const int pa = ((xa >> 1) - ps0) * cstep, pb = ((xb >> 1) - ps0) * cstep;
+            float p00[3];
+            yuv_to_bgr(ly[0][xa - xs0], lu[0][pa], lv[0][pa], p00);
+            if (RESIZE) {
+                const float fx = cfx[j], gx = 1.0f - fx;
+                float p01[3], p10[3], p11[3];
+                yuv_to_bgr(ly[0][xb - xs0], lu[0][pb], lv[0][pb], p01);
+                yuv_to_bgr(ly[1][xa - xs0], lu[1][pa], lv[1][pa], p10);
+                yuv_to_bgr(ly[1][xb - xs0], lu[1][pb], lv[1][pb], p11);
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    const float top = gx * p00[c] + fx * p01[c];
+                    const float bot = gx * p10[c] + fx * p11[c];
+                    v[c][u] = gy * top + fy * bot;
+                }
+            } else {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) v[c][u] = p00[c];
+            }
+        }
+        float* o = out_n + (size_t)(ty0 + r) * a.wd + tx0 + j0;
+#pragma unroll
+        for (int oc = 0; oc < 3; ++oc, o += plane_out) {
+            float w[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) w[u] = a.reverse ? v[2 - oc][u] : v[oc][u];
+            if (a.mean != nullptr) {
+                const float m = a.mean[oc];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) w[u] = w[u] - m;
+            }
+            if (a.std_scale != nullptr) {
+                const float d = a.std_scale[oc];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) w[u] = w[u] / d;
+            }
+            if (VS && j0 + 3 < twv) {
+                stg4_nt(o, w);
+            } else {
+#pragma unroll
+                for (int u = 0; u < 4; ++u)
+                    if (j0 + u < twv) o[u] = w[u];
+            }
+        }
+    }
+}
+
+template <bool RESIZE>
+void launch_yuv(const YuvArgs& a, dim3 grid, size_t lds, bool vs, hipStream_t st) {
+    if (vs) hipLaunchKernelGGL((preprocess_yuv_kernel<RESIZE, true>), grid, dim3(kBlock), lds, st, a);
+    else    hipLaunchKernelGGL((preprocess_yuv_kernel<RESIZE, false>), grid, dim3(kBlock), lds, st, a);
+}
+
 }  // namespace
 
 extern "C" {
@@ -236,6 +409,51 @@ int pvhip_input_preprocess_f32(const void* src, float* dst, int n, int c, int sr
     hipStream_t st = state().stream;
     if (src_u8) resize ? launch<true, true>(a, grid, lds, vs, st) : launch<true, false>(a, grid, lds, vs, st);
     else        resize ? launch<false, true>(a, grid, lds, vs, st) : launch<false, false>(a, grid, lds, vs, st);
+    PVHIP_LAUNCH_CHECK();
+    return PVHIP_OK;
+}
+
+int pvhip_input_preprocess_yuv_f32(const void* src, float* dst, int n, int src_h, int src_w, int dst_h, int dst_w, int planar,
+                                   int reverse_channels, const float* mean, const float* std_scale) {
+    PVHIP_REQUIRE_INIT();
+    PVHIP_CHECK_ARG(src != nullptr && dst != nullptr);
+    PVHIP_CHECK_ARG(n > 0 && n <= 65535 && src_h > 0 && src_w > 0 && dst_h > 0 && dst_w > 0);
+    PVHIP_CHECK_ARG(src_h % 2 == 0 && src_w % 2 == 0);                               // 4:2:0: one (U, V) per 2 x 2 block
+    PVHIP_CHECK_ARG(planar == 0 || planar == 1);
+    PVHIP_CHECK_ARG((size_t)src_h * (size_t)src_w * 3 < ((size_t)1 << 31));           // one image's elements index in 32 bits
+    PVHIP_CHECK_ARG((size_t)dst_h * (size_t)dst_w * 3 < ((size_t)1 << 31));
+    const bool resize = src_h != dst_h || src_w != dst_w;
+    auto extent = [&](int t, int S, int D) -> size_t {                                // as above
+        if (!resize) return (size_t)t;
+        const size_t e = ((size_t)(t - 1) * (size_t)S + (size_t)D - 1) / (size_t)D + 2;
+        return e < (size_t)S ? e : (size_t)S;
+    };
+    // e consecutive rows (columns) lie over at most e / 2 + 1 chroma rows (pairs): the first may be an odd one
+    auto halves = [](size_t e, int S) { return e / 2 + 1 < (size_t)S / 2 ? e / 2 + 1 : (size_t)S / 2; };
+    auto yslot_of = [&](int tw) { return (extent(tw, src_w, dst_w) + 30) / 16 * 16; };
+    auto cslot_of = [&](int tw) { return (halves(extent(tw, src_w, dst_w), src_w) * (planar ? 1 : 2) + 30) / 16 * 16; };
+    auto stage_of = [&](int tw, int th) {
+        const size_t e = extent(th, src_h, dst_h);
+        return e * yslot_of(tw) + halves(e, src_h) * (planar ? 2 : 1) * cslot_of(tw);
+    };
+    auto lds_of = [&](int tw, int th) { return stage_of(tw, th) + 12 * ((size_t)tw + (size_t)th); };
+    int tw = dst_w;                        // whole rows, unless one row's sources do not fit
+    while (tw > 1 && lds_of(tw, 1) > kStageBudget) tw = tw > 4 ? (((tw + 1) / 2 + 3) & ~3) : tw - 1;
+    int th = 2 * kBlock / ((tw + 3) / 4);  // about two quads per lane
+    th = th < 1 ? 1 : (th > dst_h ? dst_h : th);
+    while (th > 1 && lds_of(tw, th) > kStageBudget) th = (th + 1) / 2;
+    PVHIP_CHECK_ARG(lds_of(tw, th) <= kStageBudget);
+    const dim3 grid((unsigned)((dst_w + tw - 1) / tw), (unsigned)((dst_h + th - 1) / th), (unsigned)n);
+    PVHIP_CHECK_ARG(grid.y <= 65535);
+    YuvArgs a;
+    a.src = (const unsigned char*)src; a.dst = dst; a.mean = mean; a.std_scale = std_scale;
+    a.hs = src_h; a.ws = src_w; a.hd = dst_h; a.wd = dst_w; a.tw = tw; a.th = th;
+    a.planar = planar; a.reverse = reverse_channels ? 1 : 0;
+    a.yslot = (unsigned)yslot_of(tw); a.cslot = (unsigned)cslot_of(tw); a.stage_bytes = (unsigned)stage_of(tw, th);
+    const bool vs = (uintptr_t)dst % 16 == 0 && dst_w % 4 == 0 && tw % 4 == 0;
+    const size_t lds = lds_of(tw, th);
+    hipStream_t st = state().stream;
+    resize ? launch_yuv<true>(a, grid, lds, vs, st) : launch_yuv<false>(a, grid, lds, vs, st);
     PVHIP_LAUNCH_CHECK();
     return PVHIP_OK;
 }

@@ -148,6 +148,7 @@ SIGNATURES = {
     'pvhip_comm_destroy': (_c.c_int, []),
     'pvhip_input_to_nchw_f32': (_c.c_int, [_c.c_void_p, _fp] + [_c.c_int] * 6),
     'pvhip_input_preprocess_f32': (_c.c_int, [_c.c_void_p, _fp] + [_c.c_int] * 9 + [_fp, _fp]),
+    'pvhip_input_preprocess_yuv_f32': (_c.c_int, [_c.c_void_p, _fp] + [_c.c_int] * 7 + [_fp, _fp]),
 }
 
 # entry points whose return value is not a status code

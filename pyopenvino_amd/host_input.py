@@ -68,7 +68,8 @@ class HostInputs:
         """`inputs` with every host input of a declared format, or in one of this request's own buffers, replaced by the request's fixed
         tensor: the caller's array is copied into the page-locked buffer of its extent unless it IS that buffer, the buffer is uploaded on
         the copy stream, stream `stream_base` waits for the copy's event and converts (one launch; none for FP32 NCHW at the network's
-        extent): pvhip_input_preprocess_f32 when a resize, channel reversal or mean / scale is in effect, else pvhip_input_to_nchw_f32.
+        extent): pvhip_input_preprocess_yuv_f32 for NV12 / I420 frames, pvhip_input_preprocess_f32 when a resize, channel reversal or
+        mean / scale is in effect, else pvhip_input_to_nchw_f32.
         Every other input is returned unchanged (and goes the default way).  All but the MAX_SOURCE_EXTENTS most recently fed extents
         of an input are released here: the request has no pass in flight, so nothing reads those buffers any more."""
         out = dict(inputs)
@@ -96,7 +97,10 @@ class HostInputs:
             slot.event.record()
             device.select_stream(stream_base)
             slot.event.wait()
-            if staged.preprocess:
+            if fmt.yuv:
+                device.call('pvhip_input_preprocess_yuv_f32', device.ptr(staged.staging), device.ptr(fixed), fixed.shape[0], *staged.extent,
+                            *fixed.shape[2:], int(fmt.color == 'I420'), int(fmt.reverse), device.ptr(slot.mean), device.ptr(slot.std))
+            elif staged.preprocess:
                 device.call('pvhip_input_preprocess_f32', device.ptr(staged.staging), device.ptr(fixed), *fixed.shape[:2], *staged.extent,
                             *fixed.shape[2:], int(fmt.u8), int(fmt.nhwc), int(fmt.reverse), device.ptr(slot.mean), device.ptr(slot.std))
             elif staged.staging is not fixed:

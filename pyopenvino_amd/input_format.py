@@ -11,7 +11,8 @@ class InputFormat:
     """One input's format as a fixed value (``InputInfo.frozen()``; load_network makes one per input and every request reads that one):
     ``dims`` the (n, c, h, w) of the fp32 tensor the IR expects, ``supported`` / ``declared`` as InputInfo has them, ``u8`` / ``nhwc`` the
     declared precision and layout, ``resize`` / ``reverse`` / ``mean`` / ``std`` the declared preprocessing (fp32 arrays of c values, or
-    None without MEAN_VALUE).  An extent is the (h, w) of a caller's array."""
+    None without MEAN_VALUE), ``color`` the declared colour format: 'RAW', or 'NV12' / 'I420' for YUV 4:2:0 frames, uint8 of shape
+    (n, 3 h / 2, w) whatever ``u8`` / ``nhwc`` say.  An extent is the (h, w) of a caller's image."""
     name: str
     dims: tuple
     supported: bool
@@ -22,23 +23,32 @@ class InputFormat:
     reverse: bool
     mean: np.ndarray
     std: np.ndarray
+    color: str = 'RAW'
+
+    @property
+    def yuv(self) -> bool:
+        return self.color != 'RAW'
 
     @property
     def host_dtype(self):
-        return np.dtype(np.uint8 if self.u8 else np.float32)
+        return np.dtype(np.uint8 if self.u8 or self.yuv else np.float32)
 
     def host_shape(self, extent=None):
         """The shape of a caller's array of `extent` (default: the network's own) in this layout."""
         n, c = self.dims[:2]
         h, w = extent if extent is not None else self.dims[2:]
+        if self.yuv:
+            return n, (h // 2 * 3 if isinstance(h, int) else '3h/2'), w
         return (n, h, w, c) if self.nhwc else (n, c, h, w)
 
     def checked_extent(self, source_size=None):
-        """The (h, w) a caller's array has: `source_size` with RESIZE_BILINEAR declared, else the network's own."""
+        """The (h, w) a caller's image has: `source_size` with RESIZE_BILINEAR declared, else the network's own (even, for YUV 4:2:0)."""
         n, c, h, w = self.dims
+        sh, sw = (int(v) for v in source_size) if source_size is not None else (h, w)
+        if self.yuv and (sh % 2 or sw % 2):
+            raise ValueError('input {}: {} frames have an even height and width, not {}'.format(self.name, self.color, (sh, sw)))
         if source_size is None:
             return h, w
-        sh, sw = (int(v) for v in source_size)
         if (sh, sw) != (h, w) and not self.resize:
             raise ValueError('input {}: source size {} differs from the network\'s {} and no resize is declared '
                              '(preprocess_info.resize_algorithm = \'RESIZE_BILINEAR\')'.format(self.name, (sh, sw), (h, w)))
@@ -48,6 +58,8 @@ class InputFormat:
 
     def extent_of(self, a):
         """(h, w) of the caller's array `a`, checked against this format."""
+        if self.yuv:
+            return self._yuv_extent_of(a)
         declared = 'declared {} / {}'.format('U8' if self.u8 else 'FP32', 'NHWC' if self.nhwc else 'NCHW')
         if not self.resize:
             if a.shape != self.host_shape():
@@ -58,9 +70,21 @@ class InputFormat:
                 self.name, declared, self.host_shape(('h', 'w')), a.shape))
         return self.checked_extent(a.shape[1:3] if self.nhwc else a.shape[2:4])
 
+    def _yuv_extent_of(self, a):
+        declared = 'declared {}'.format(self.color)
+        if not self.resize:
+            if a.shape != self.host_shape():
+                raise ValueError('input {}: {} means shape {}, got {}'.format(self.name, declared, self.host_shape(), a.shape))
+            return tuple(self.dims[2:])
+        if a.ndim != 3 or a.shape[0] != self.dims[0] or a.shape[1] % 3:
+            raise ValueError('input {}: {} with RESIZE_BILINEAR means shape {} for any even h, w; got {}'.format(
+                self.name, declared, self.host_shape(('h', 'w')), a.shape))
+        return self.checked_extent((a.shape[1] // 3 * 2, a.shape[2]))
+
     def needs_preprocess(self, extent) -> bool:
-        """Arrays of `extent` go through pvhip_input_preprocess_f32: something besides the format change is in effect."""
-        return tuple(extent) != tuple(self.dims[2:]) or self.reverse or self.mean is not None
+        """Arrays of `extent` go through pvhip_input_preprocess_f32 (YUV frames: pvhip_input_preprocess_yuv_f32, always): something
+        besides the format change is in effect."""
+        return tuple(extent) != tuple(self.dims[2:]) or self.reverse or self.mean is not None or self.yuv
 
     def needs_convert(self, extent) -> bool:
         """Arrays of `extent` are not the fp32 NCHW tensor itself: they are uploaded into a staging tensor and converted by one launch."""
@@ -73,7 +97,9 @@ class InputInfo:
     tensor the IR expects -- a cv2 image as it is, where the reference's callers hand ``img.transpose((2, 0, 1)).astype(np.float32)``.
     Set between ``read_network`` and ``load_network``.  A declared input is uploaded as it is and converted on the device
     (``pvhip_input_to_nchw_f32``); an input whose format is never set goes the default way.  ``preprocess_info`` adds a resize of a source
-    of any extent, channel reversal and mean / scale to that launch (``pvhip_input_preprocess_f32``)."""
+    of any extent, channel reversal and mean / scale to that launch (``pvhip_input_preprocess_f32``); its ``color_format`` 'NV12' /
+    'I420' makes the array a decoder's YUV 4:2:0 frames, uint8 of shape (n, 3 h / 2, w), converted to B, G, R in that launch
+    (``pvhip_input_preprocess_yuv_f32``)."""
     PRECISIONS = ('FP32', 'U8')
     LAYOUTS = ('NCHW', 'NHWC')
 
@@ -81,6 +107,7 @@ class InputInfo:
         self._net, self._nid = net, nid
         self._precision, self._layout = 'FP32', 'NCHW'
         self.declared = False           # precision or layout set explicitly (to any value)
+        self._precision_set = False     # precision set explicitly: 'FP32' then contradicts a YUV color_format
         self._pre = None                # PreProcessInfo, once preprocess_info has been asked for
 
     @property
@@ -104,6 +131,7 @@ class InputInfo:
     @precision.setter
     def precision(self, value):
         self._precision = self._checked('precision', value, self.PRECISIONS)
+        self._precision_set = True
 
     @property
     def layout(self):
@@ -152,8 +180,10 @@ class InputInfo:
         if pre is not None and pre.mean_variant == 'MEAN_VALUE':
             mean = np.array([ch.mean_value for ch in pre._channels], np.float32)
             std = np.array([ch.std_scale for ch in pre._channels], np.float32)
-        return InputFormat(self.name, self.dims, self.supported(), self.declared, self._precision == 'U8', self._layout == 'NHWC',
-                           pre is not None and pre.resize_algorithm == 'RESIZE_BILINEAR', pre is not None and pre.reverse_channels, mean, std)
+        color = pre.color_format if pre is not None else 'RAW'
+        return InputFormat(self.name, self.dims, self.supported(), self.declared, self._precision == 'U8' or color != 'RAW', self._layout == 'NHWC',
+                           pre is not None and pre.resize_algorithm == 'RESIZE_BILINEAR', pre is not None and pre.reverse_channels, mean, std,
+                           color)
 
     def preprocessing(self):
         """(resize, reverse_channels, (mean, std_scale) or None) as declared; (False, False, None) when nothing is."""
@@ -165,6 +195,15 @@ class InputInfo:
         if pre is not None and pre.mean_variant == 'MEAN_VALUE' and len(pre._channels) != self.dims[1]:
             raise ValueError('input {}: mean_variant MEAN_VALUE with {} channels (preprocess_info.init), the input has {}'.format(
                 self.name, len(pre._channels), self.dims[1]))
+        if pre is not None and pre.color_format != 'RAW':
+            if self.dims[1] != 3:
+                raise ValueError('input {}: color_format {} converts to 3 channels (B, G, R), the input has {}'.format(
+                    self.name, pre.color_format, self.dims[1]))
+            if self._precision_set and self._precision != 'U8':
+                raise ValueError('input {}: color_format {} frames are U8, precision {} is declared'.format(
+                    self.name, pre.color_format, self._precision))
+            if pre.resize_algorithm == 'NO_RESIZE':
+                self.frozen().checked_extent()     # the frames have the network's extent: an even one
 
     def source_extent(self, source_size=None):
         """The (h, w) a caller's array has: `source_size` with RESIZE_BILINEAR declared, else the network's own."""
@@ -214,14 +253,22 @@ class PreProcessInfo:
         (half-pixel centres, clamped at the border, as cv2 INTER_LINEAR; no antialiasing, so large downscales alias); a source at the
         network's own extent is not resized at all;
       * ``reverse_channels``: output channel c takes source channel C-1-c (a BGR frame into an RGB-trained IR);
-      * ``mean_variant``: 'NONE' (default) or 'MEAN_VALUE': y = (v - self[c].mean_value) / self[c].std_scale, after ``init(C)``.
+      * ``mean_variant``: 'NONE' (default) or 'MEAN_VALUE': y = (v - self[c].mean_value) / self[c].std_scale, after ``init(C)``;
+      * ``color_format``: 'RAW' (default: the array holds the channels themselves) or 'NV12' / 'I420': the array holds YUV 4:2:0 frames as a
+        video decoder writes them and ``cv2.cvtColor(..., COLOR_YUV2BGR_NV12 / _I420)`` takes them -- uint8 of shape (n, 3 h / 2, w), h and
+        w even: h rows of Y, then for NV12 h / 2 rows of w / 2 interleaved (U, V) pairs, for I420 the U plane and the V plane of
+        h / 2 x w / 2 bytes each.  The device converts them to B, G, R (BT.601 limited range in 20-bit integers, the chroma of a pixel's
+        2 x 2 block; pvhip_input_preprocess_yuv_f32) and resizes, reverses (R, G, B) and scales that image as it does a U8 B, G, R one.
+        The Parameter has 3 channels; ``precision`` is U8 by implication ('FP32' declared beside it is refused at load), ``layout`` is
+        not consulted.
     Set between ``read_network`` and ``load_network``, like ``precision``; setting anything makes the input declared."""
     RESIZE_ALGORITHMS = ('NO_RESIZE', 'RESIZE_BILINEAR')
     MEAN_VARIANTS = ('NONE', 'MEAN_VALUE')
+    COLOR_FORMATS = ('RAW', 'NV12', 'I420')
 
     def __init__(self, info):
         self._info = info
-        self._resize, self._mean_variant, self._reverse = 'NO_RESIZE', 'NONE', False
+        self._resize, self._mean_variant, self._reverse, self._color = 'NO_RESIZE', 'NONE', False, 'RAW'
         self._channels = []
 
     @property
@@ -239,6 +286,14 @@ class PreProcessInfo:
     @mean_variant.setter
     def mean_variant(self, value):
         self._mean_variant = self._info._checked('preprocess_info.mean_variant', value, self.MEAN_VARIANTS)
+
+    @property
+    def color_format(self):
+        return self._color
+
+    @color_format.setter
+    def color_format(self, value):
+        self._color = self._info._checked('preprocess_info.color_format', value, self.COLOR_FORMATS)
 
     @property
     def reverse_channels(self):
