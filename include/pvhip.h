@@ -465,6 +465,22 @@ int         pvhip_input_preprocess_f32(const void* src, float* dst, int n, int c
  * image.  n <= 65535, src_h and src_w even, 3 * h * w < 2^31 for source and destination; else PVHIP_EINVAL. */
 int         pvhip_input_preprocess_yuv_f32(const void* src, float* dst, int n, int src_h, int src_w, int dst_h, int dst_w, int planar,
                                            int reverse_channels, const float* mean, const float* std_scale);
+/* Addition to ABI v17 (the version number is unchanged: nothing existing changed): regions of interest.  The two launches above with a
+ * source rectangle per output image: `src` holds m frames of extent (src_h, src_w) in the format of the entry above it (m is independent
+ * of n), `rois` is a device pointer to n x 5 int32 (id, x, y, w, h) -- the order of OpenVINO's ROI struct --, and image b of `dst` is the
+ * rectangle [y, y + h) x [x, x + w) of frame id, cropped and THEN resized to (dst_h, dst_w): the taps clamp at the rectangle's edge, not
+ * the frame's; a rectangle of exactly (dst_h, dst_w) is copied, not interpolated; a YUV rectangle may have an odd origin and odd sizes (a
+ * pixel takes the chroma of its 2 x 2 block of the frame).  Reversal and mean / scale as above.  In numpy: tests/roi_ref.py, matched bit
+ * for bit.  max_roi_h / max_roi_w: the largest h and w in the table, which the caller knows (the tiles are sized for them on the host).
+ * The table is read on the device only: an image whose rectangle is not inside a frame (id outside [0, m), x or y < 0, w or h < 1,
+ * x + w > src_w, y + h > src_h) or exceeds max_roi_h / max_roi_w is written as quiet NaN, and nothing of `src` is read for it.
+ * The limits of the entries above, and rois != NULL, m >= 1, 1 <= max_roi_h <= src_h, 1 <= max_roi_w <= src_w; else PVHIP_EINVAL. */
+int         pvhip_input_preprocess_roi_f32(const void* src, float* dst, const int* rois, int n, int m, int c, int src_h, int src_w,
+                                           int dst_h, int dst_w, int max_roi_h, int max_roi_w, int src_u8, int src_nhwc,
+                                           int reverse_channels, const float* mean, const float* std_scale);
+int         pvhip_input_preprocess_yuv_roi_f32(const void* src, float* dst, const int* rois, int n, int m, int src_h, int src_w,
+                                               int dst_h, int dst_w, int max_roi_h, int max_roi_w, int planar, int reverse_channels,
+                                               const float* mean, const float* std_scale);
 
 #ifdef __cplusplus
 }

@@ -18,6 +18,12 @@
 //      channel plane (scalar stores when the destination rows are not 16-byte aligned).
 //
 // YUV 4:2:0 frames (NV12, I420) take the same launch with a colour conversion in front of the taps: preprocess_yuv_kernel, further down.
+//
+// Regions of interest (the ROI entries): image b of the output is the rectangle rois[b] = (id, x, y, w, h) of frame id of m frames, cropped
+// and then resized -- the taps clamp at the rectangle's edge, not the frame's.  Both kernels take it as a template parameter: a workgroup
+// reads its image's five ints, takes S = (h, w) for its taps and adds (id, y, x) to the addresses it stages from; a rectangle of exactly
+// the destination's extent is copied (fp32 sources: no 0 * inf; bytes give the same bits either way).  The table is device data, so an image whose rectangle does not lie inside a frame, or
+// exceeds the maxima the launch was sized for, is written as quiet NaN and nothing is read for it.  tests/roi_ref.py is the rule in numpy.
 #include "pvhip_common.h"
 
 #pragma clang fp contract(off)
@@ -66,7 +72,34 @@ struct PrepArgs {
     int nhwc, reverse;
     unsigned slot;            // LDS bytes per staged span (a multiple of 16)
     unsigned stage_bytes;     // LDS bytes of the staging area (the coordinate tables follow it)
+    const int* rois;          // ROI kernels: n x (id, x, y, w, h); hs, ws are then the extent of each of the m frames
+    int m, mh, mw;            // ... the frame count and the largest h and w the launch was sized for
 };
+
+// One image's rectangle (ROI kernels), read once per workgroup; ok: it lies inside frame id and within the launch's maxima.
+struct Roi {
+    int id, x, y, w, h;
+    bool ok;
+};
+
+__device__ __forceinline__ Roi roi_of(const int* rois, int b, int m, int hs, int ws, int mh, int mw) {
+    const int* q = rois + 5 * (size_t)b;
+    Roi r;
+    r.id = q[0]; r.x = q[1]; r.y = q[2]; r.w = q[3]; r.h = q[4];
+    r.ok = r.id >= 0 && r.id < m && r.x >= 0 && r.y >= 0 && r.w >= 1 && r.h >= 1 && r.w <= mw && r.h <= mh
+        && (long long)r.x + r.w <= ws && (long long)r.y + r.h <= hs;
+    return r;
+}
+
+// The tile (tx0.., ty0..) of twv x thv pixels in every one of c planes of one image: quiet NaN (an invalid rectangle).
+__device__ __forceinline__ void fill_nan(float* out_n, int c, size_t plane_out, int wd, int tx0, int ty0, int twv, int thv) {
+    const float q = __builtin_nanf("");
+    for (int oc = 0; oc < c; ++oc)
+        for (int i = threadIdx.x; i < thv * twv; i += kBlock) {
+            const int r = i / twv;
+            out_n[oc * plane_out + (size_t)(ty0 + r) * wd + tx0 + (i - r * twv)] = q;
+        }
+}
 
 template <bool U8>
 __device__ __forceinline__ float pixel(const unsigned char* span, int e) {
@@ -82,12 +115,25 @@ __device__ __forceinline__ void stg4_nt(float* p, const float (&v)[4]) {
 
 // grid (ceil(wd / tw), ceil(hd / th), n); dynamic LDS stage_bytes + 12 (tw + th) bytes.
 // VS: every tile's quads start 16-byte aligned in every output plane (dst aligned, wd and tw multiples of 4).
-template <bool U8, bool RESIZE, bool VS>
+// ROI (with RESIZE): image n is a rectangle of a frame (see the file comment); hs, ws below are the extent the taps see.
+template <bool U8, bool RESIZE, bool VS, bool ROI>
 __global__ __launch_bounds__(kBlock) void preprocess_kernel(PrepArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     constexpr int ES = U8 ? 1 : 4;
     const int n = blockIdx.z, tx0 = blockIdx.x * a.tw, ty0 = blockIdx.y * a.th;
     const int twv = min(a.tw, a.wd - tx0), thv = min(a.th, a.hd - ty0);
+    int hs = a.hs, ws = a.ws, img = n, ox = 0, oy = 0;
+    bool copy = false;                                        // (workgroup-uniform) the rectangle has the destination's extent
+    if (ROI) {
+        const Roi q = roi_of(a.rois, n, a.m, a.hs, a.ws, a.mh, a.mw);
+        if (!q.ok) {
+            fill_nan(a.dst + (size_t)n * a.c * ((size_t)a.hd * a.wd), a.c, (size_t)a.hd * a.wd, a.wd, tx0, ty0, twv, thv);
+            return;
+        }
+        hs = q.h; ws = q.w; img = q.id; ox = q.x; oy = q.y;
+        copy = !U8 && q.h == a.hd && q.w == a.wd;             // (bytes interpolate to the same bits: weight 0 on a finite value)
+    }
+    auto taps = [&](int d, int S, int D) { return ROI && copy ? tap<false>(d, S, D) : tap<RESIZE>(d, S, D); };
     int* cx0 = reinterpret_cast<int*>(lds + a.stage_bytes);
     int* cx1 = cx0 + a.tw;
     float* cfx = reinterpret_cast<float*>(cx1 + a.tw);
@@ -95,24 +141,24 @@ __global__ __launch_bounds__(kBlock) void preprocess_kernel(PrepArgs a) {
     int* ry1 = ry0 + a.th;
     float* rfy = reinterpret_cast<float*>(ry1 + a.th);
     for (int j = threadIdx.x; j < twv; j += kBlock) {
-        const Tap t = tap<RESIZE>(tx0 + j, a.ws, a.wd);
+        const Tap t = taps(tx0 + j, ws, a.wd);
         cx0[j] = t.i0; cx1[j] = t.i1; cfx[j] = t.f;
     }
     for (int j = threadIdx.x; j < thv; j += kBlock) {
-        const Tap t = tap<RESIZE>(ty0 + j, a.hs, a.hd);
+        const Tap t = taps(ty0 + j, hs, a.hd);
         ry0[j] = t.i0; ry1[j] = t.i1; rfy[j] = t.f;
     }
     // the source the tile reads (the taps are monotone in d): columns xs0..xs1 of rows ys0..ys1
-    const int xs0 = tap<RESIZE>(tx0, a.ws, a.wd).i0, xs1 = tap<RESIZE>(tx0 + twv - 1, a.ws, a.wd).i1;
-    const int ys0 = tap<RESIZE>(ty0, a.hs, a.hd).i0, ys1 = tap<RESIZE>(ty0 + thv - 1, a.hs, a.hd).i1;
+    const int xs0 = taps(tx0, ws, a.wd).i0, xs1 = taps(tx0 + twv - 1, ws, a.wd).i1;
+    const int ys0 = taps(ty0, hs, a.hd).i0, ys1 = taps(ty0 + thv - 1, hs, a.hd).i1;
     const int rows = ys1 - ys0 + 1;
     const int cs = a.nhwc ? a.c : 1, planes = a.nhwc ? 1 : a.c;
     const int span = (xs1 - xs0 + 1) * cs * ES;              // bytes of one staged span
     // span s = plane * rows + row: its first byte in the source
     auto span_src = [&](int s) -> const unsigned char* {
         const int p = s / rows, r = s - p * rows;
-        const size_t e = a.nhwc ? ((size_t)n * a.hs + ys0 + r) * a.ws * (size_t)a.c + (size_t)xs0 * a.c
-                                : (((size_t)n * a.c + p) * a.hs + ys0 + r) * a.ws + xs0;
+        const size_t e = a.nhwc ? ((size_t)img * a.hs + oy + ys0 + r) * a.ws * (size_t)a.c + (size_t)(ox + xs0) * a.c
+                                : (((size_t)img * a.c + p) * a.hs + oy + ys0 + r) * a.ws + ox + xs0;
         return a.src + e * ES;
     };
     const unsigned bps = (unsigned)span / 16 + 2;             // 16-byte blocks a span touches at most
@@ -159,7 +205,7 @@ __global__ __launch_bounds__(kBlock) void preprocess_kernel(PrepArgs a) {
             float v[4];
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
-                if (RESIZE) {
+                if (RESIZE && !(ROI && copy)) {
                     const float top = gx[u] * pixel<U8>(l0, xa[u] + ch) + fx[u] * pixel<U8>(l0, xb[u] + ch);
                     const float bot = gx[u] * pixel<U8>(l1, xa[u] + ch) + fx[u] * pixel<U8>(l1, xb[u] + ch);
                     v[u] = gy * top + fy * bot;
@@ -188,10 +234,10 @@ __global__ __launch_bounds__(kBlock) void preprocess_kernel(PrepArgs a) {
     }
 }
 
-template <bool U8, bool RESIZE>
+template <bool U8, bool RESIZE, bool ROI>
 void launch(const PrepArgs& a, dim3 grid, size_t lds, bool vs, hipStream_t st) {
-    if (vs) hipLaunchKernelGGL((preprocess_kernel<U8, RESIZE, true>), grid, dim3(kBlock), lds, st, a);
-    else    hipLaunchKernelGGL((preprocess_kernel<U8, RESIZE, false>), grid, dim3(kBlock), lds, st, a);
+    if (vs) hipLaunchKernelGGL((preprocess_kernel<U8, RESIZE, true, ROI>), grid, dim3(kBlock), lds, st, a);
+    else    hipLaunchKernelGGL((preprocess_kernel<U8, RESIZE, false, ROI>), grid, dim3(kBlock), lds, st, a);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- YUV 4:2:0 sources
@@ -215,6 +261,8 @@ struct YuvArgs {
     int planar, reverse;
     unsigned yslot, cslot;    // LDS bytes per staged Y span and per staged chroma span (multiples of 16)
     unsigned stage_bytes;     // LDS bytes of the staging area (the coordinate tables follow it)
+    const int* rois;          // ROI kernels: as in PrepArgs
+    int m, mh, mw;
 };
 
 // B, G, R (in that order) of one pixel, as the floats of the converted bytes.
@@ -231,11 +279,25 @@ __device__ __forceinline__ void yuv_to_bgr(int y, int u, int v, float (&o)[3]) {
 }
 
 // grid (ceil(wd / tw), ceil(hd / th), n); dynamic LDS stage_bytes + 12 (tw + th) bytes.  VS as in preprocess_kernel.
-template <bool RESIZE, bool VS>
+// ROI as in preprocess_kernel; the chroma of a pixel is that of its ABSOLUTE 2 x 2 block of the frame, so a rectangle may start on odd
+// coordinates and have odd sizes.
+template <bool RESIZE, bool VS, bool ROI>
 __global__ __launch_bounds__(kBlock) void preprocess_yuv_kernel(YuvArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     const int n = blockIdx.z, tx0 = blockIdx.x * a.tw, ty0 = blockIdx.y * a.th;
     const int twv = min(a.tw, a.wd - tx0), thv = min(a.th, a.hd - ty0);
+    int hs = a.hs, ws = a.ws, img = n, ox = 0, oy = 0;
+    if (ROI) {
+        const Roi q = roi_of(a.rois, n, a.m, a.hs, a.ws, a.mh, a.mw);
+        if (!q.ok) {
+            fill_nan(a.dst + (size_t)n * 3 * ((size_t)a.hd * a.wd), 3, (size_t)a.hd * a.wd, a.wd, tx0, ty0, twv, thv);
+            return;
+        }
+        hs = q.h; ws = q.w; img = q.id; ox = q.x; oy = q.y;
+    }
+    // (a rectangle of the destination's extent needs no copy path here: the converted pixels are bytes, and weight 0 on a finite value
+    // interpolates to the same bits)
+    auto taps = [&](int d, int S, int D) { return tap<RESIZE>(d, S, D); };
     int* cx0 = reinterpret_cast<int*>(lds + a.stage_bytes);
     int* cx1 = cx0 + a.tw;
     float* cfx = reinterpret_cast<float*>(cx1 + a.tw);
@@ -243,23 +305,23 @@ __global__ __launch_bounds__(kBlock) void preprocess_yuv_kernel(YuvArgs a) {
     int* ry1 = ry0 + a.th;
     float* rfy = reinterpret_cast<float*>(ry1 + a.th);
     for (int j = threadIdx.x; j < twv; j += kBlock) {
-        const Tap t = tap<RESIZE>(tx0 + j, a.ws, a.wd);
+        const Tap t = taps(tx0 + j, ws, a.wd);
         cx0[j] = t.i0; cx1[j] = t.i1; cfx[j] = t.f;
     }
     for (int j = threadIdx.x; j < thv; j += kBlock) {
-        const Tap t = tap<RESIZE>(ty0 + j, a.hs, a.hd);
+        const Tap t = taps(ty0 + j, hs, a.hd);
         ry0[j] = t.i0; ry1[j] = t.i1; rfy[j] = t.f;
     }
-    const int xs0 = tap<RESIZE>(tx0, a.ws, a.wd).i0, xs1 = tap<RESIZE>(tx0 + twv - 1, a.ws, a.wd).i1;
-    const int ys0 = tap<RESIZE>(ty0, a.hs, a.hd).i0, ys1 = tap<RESIZE>(ty0 + thv - 1, a.hs, a.hd).i1;
+    const int xs0 = taps(tx0, ws, a.wd).i0, xs1 = taps(tx0 + twv - 1, ws, a.wd).i1;
+    const int ys0 = taps(ty0, hs, a.hd).i0, ys1 = taps(ty0 + thv - 1, hs, a.hd).i1;
     const int rows = ys1 - ys0 + 1, yspan = xs1 - xs0 + 1;
-    const int ps0 = xs0 >> 1, cr0 = ys0 >> 1, crows = (ys1 >> 1) - cr0 + 1;       // first chroma pair and row, chroma rows
+    const int ps0 = (ox + xs0) >> 1, cr0 = (oy + ys0) >> 1, crows = ((oy + ys1) >> 1) - cr0 + 1;   // first chroma pair and row, chroma rows
     const int cstep = a.planar ? 1 : 2;                                            // bytes from one U (V) to the next
-    const int cspan = ((xs1 >> 1) - ps0 + 1) * cstep;
+    const int cspan = (((ox + xs1) >> 1) - ps0 + 1) * cstep;
     const int hw = a.ws >> 1;
-    const unsigned char* frame = a.src + (size_t)n * ((size_t)a.hs * a.ws / 2 * 3);
+    const unsigned char* frame = a.src + (size_t)img * ((size_t)a.hs * a.ws / 2 * 3);
     const unsigned char* chroma = frame + (size_t)a.hs * a.ws;
-    auto y_src = [&](int r) -> const unsigned char* { return frame + (size_t)(ys0 + r) * a.ws + xs0; };
+    auto y_src = [&](int r) -> const unsigned char* { return frame + (size_t)(oy + ys0 + r) * a.ws + ox + xs0; };
     // chroma span s: NV12 row s of the pairs; I420 row s of U for s < crows, row s - crows of V after them
     auto c_src = [&](int s) -> const unsigned char* {
         if (!a.planar) return chroma + (size_t)(cr0 + s) * a.ws + 2 * ps0;
@@ -302,7 +364,7 @@ __global__ __launch_bounds__(kBlock) void preprocess_yuv_kernel(YuvArgs a) {
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
             const int ya = k ? ry1[r] : ry0[r];
-            const int yr = ya - ys0, cr = (ya >> 1) - cr0;
+            const int yr = ya - ys0, cr = ((oy + ya) >> 1) - cr0;
             ly[k] = lds + (unsigned)yr * a.yslot + ((uintptr_t)y_src(yr) & 15);
             lu[k] = lds_c + (unsigned)cr * a.cslot + ((uintptr_t)c_src(cr) & 15);
             lv[k] = a.planar ? lds_c + (unsigned)(crows + cr) * a.cslot + ((uintptr_t)c_src(crows + cr) & 15) : lu[k] + 1;
@@ -312,7 +374,7 @@ __global__ __launch_bounds__(kBlock) void preprocess_yuv_kernel(YuvArgs a) {
         for (int u = 0; u < 4; ++u) {
             const int j = j0 + u < twv ? j0 + u : j0;         // (a pixel past the tile computes column j0 again and is not stored)
             const int xa = cx0[j], xb = cx1[j];
-            const int pa = ((xa >> 1) - ps0) * cstep, pb = ((xb >> 1) - ps0) * cstep;
+            const int pa = (((ox + xa) >> 1) - ps0) * cstep, pb = (((ox + xb) >> 1) - ps0) * cstep;
             float p00[3];
             yuv_to_bgr(ly[0][xa - xs0], lu[0][pa], lv[0][pa], p00);
             if (RESIZE) {
@@ -359,27 +421,29 @@ __global__ __launch_bounds__(kBlock) void preprocess_yuv_kernel(YuvArgs a) {
     }
 }
 
-template <bool RESIZE>
+template <bool RESIZE, bool ROI>
 void launch_yuv(const YuvArgs& a, dim3 grid, size_t lds, bool vs, hipStream_t st) {
-    if (vs) hipLaunchKernelGGL((preprocess_yuv_kernel<RESIZE, true>), grid, dim3(kBlock), lds, st, a);
-    else    hipLaunchKernelGGL((preprocess_yuv_kernel<RESIZE, false>), grid, dim3(kBlock), lds, st, a);
+    if (vs) hipLaunchKernelGGL((preprocess_yuv_kernel<RESIZE, true, ROI>), grid, dim3(kBlock), lds, st, a);
+    else    hipLaunchKernelGGL((preprocess_yuv_kernel<RESIZE, false, ROI>), grid, dim3(kBlock), lds, st, a);
 }
 
-}  // namespace
-
-extern "C" {
-
-int pvhip_input_preprocess_f32(const void* src, float* dst, int n, int c, int src_h, int src_w, int dst_h, int dst_w,
-                               int src_u8, int src_nhwc, int reverse_channels, const float* mean, const float* std_scale) {
+// The one launcher of preprocess_kernel.  rois == NULL: image b is the whole of source image b (m, roi_h, roi_w are not read).  Else image
+// b is a rectangle of one of m frames; the tiles and LDS slots are sized for the largest rectangle (roi_h, roi_w): extent() is monotone
+// in S, so the budget holds for every image.
+int preprocess_launch(const void* src, float* dst, const int* rois, int n, int m, int c, int src_h, int src_w, int dst_h, int dst_w,
+                      int roi_h, int roi_w, int src_u8, int src_nhwc, int reverse_channels, const float* mean, const float* std_scale) {
     PVHIP_REQUIRE_INIT();
     PVHIP_CHECK_ARG(src != nullptr && dst != nullptr);
     PVHIP_CHECK_ARG(n > 0 && n <= 65535 && c > 0 && c <= kMaxChannels && src_h > 0 && src_w > 0 && dst_h > 0 && dst_w > 0);
     PVHIP_CHECK_ARG((size_t)src_h * (size_t)src_w * (size_t)c < ((size_t)1 << 31));   // one image's elements index in 32 bits
     PVHIP_CHECK_ARG((size_t)dst_h * (size_t)dst_w * (size_t)c < ((size_t)1 << 31));
     PVHIP_CHECK_ARG(src_u8 || (uintptr_t)src % 4 == 0);                              // fp32 sources are element-aligned
-    const bool resize = src_h != dst_h || src_w != dst_w;
+    const bool roi = rois != nullptr;
+    if (roi) PVHIP_CHECK_ARG(m >= 1 && roi_h >= 1 && roi_h <= src_h && roi_w >= 1 && roi_w <= src_w);
+    const bool resize = roi || src_h != dst_h || src_w != dst_w;
     if (!resize && !reverse_channels && mean == nullptr && std_scale == nullptr)      // the format alone: the same bits as the
         return pvhip_input_to_nchw_f32(src, dst, n, c, dst_h, dst_w, src_u8, src_nhwc);   // path without preprocessing
+    const int tap_h = roi ? roi_h : src_h, tap_w = roi ? roi_w : src_w;               // the largest extent the taps of an image see
     const size_t es = src_u8 ? 1 : 4;
     const size_t cs = src_nhwc ? (size_t)c : 1, planes = src_nhwc ? 1 : (size_t)c;
     // source rows (columns) a tile of t destination rows (columns) reads at most: the taps advance by S/D per step
@@ -388,8 +452,8 @@ int pvhip_input_preprocess_f32(const void* src, float* dst, int n, int c, int sr
         const size_t e = ((size_t)(t - 1) * (size_t)S + (size_t)D - 1) / (size_t)D + 2;
         return e < (size_t)S ? e : (size_t)S;
     };
-    auto slot_of = [&](int tw) { return (extent(tw, src_w, dst_w) * cs * es + 30) / 16 * 16; };
-    auto stage_of = [&](int tw, int th) { return planes * extent(th, src_h, dst_h) * slot_of(tw); };
+    auto slot_of = [&](int tw) { return (extent(tw, tap_w, dst_w) * cs * es + 30) / 16 * 16; };
+    auto stage_of = [&](int tw, int th) { return planes * extent(th, tap_h, dst_h) * slot_of(tw); };
     auto lds_of = [&](int tw, int th) { return stage_of(tw, th) + 12 * ((size_t)tw + (size_t)th); };
     int tw = dst_w;                        // whole rows, unless one row's sources do not fit
     while (tw > 1 && lds_of(tw, 1) > kStageBudget) tw = tw > 4 ? (((tw + 1) / 2 + 3) & ~3) : tw - 1;
@@ -404,17 +468,20 @@ int pvhip_input_preprocess_f32(const void* src, float* dst, int n, int c, int sr
     a.c = c; a.hs = src_h; a.ws = src_w; a.hd = dst_h; a.wd = dst_w; a.tw = tw; a.th = th;
     a.nhwc = src_nhwc ? 1 : 0; a.reverse = reverse_channels ? 1 : 0;
     a.slot = (unsigned)slot_of(tw); a.stage_bytes = (unsigned)stage_of(tw, th);
+    a.rois = rois; a.m = m; a.mh = roi_h; a.mw = roi_w;
     const bool vs = (uintptr_t)dst % 16 == 0 && dst_w % 4 == 0 && tw % 4 == 0;
     const size_t lds = lds_of(tw, th);
     hipStream_t st = state().stream;
-    if (src_u8) resize ? launch<true, true>(a, grid, lds, vs, st) : launch<true, false>(a, grid, lds, vs, st);
-    else        resize ? launch<false, true>(a, grid, lds, vs, st) : launch<false, false>(a, grid, lds, vs, st);
+    if (roi)         src_u8 ? launch<true, true, true>(a, grid, lds, vs, st) : launch<false, true, true>(a, grid, lds, vs, st);
+    else if (src_u8) resize ? launch<true, true, false>(a, grid, lds, vs, st) : launch<true, false, false>(a, grid, lds, vs, st);
+    else             resize ? launch<false, true, false>(a, grid, lds, vs, st) : launch<false, false, false>(a, grid, lds, vs, st);
     PVHIP_LAUNCH_CHECK();
     return PVHIP_OK;
 }
 
-int pvhip_input_preprocess_yuv_f32(const void* src, float* dst, int n, int src_h, int src_w, int dst_h, int dst_w, int planar,
-                                   int reverse_channels, const float* mean, const float* std_scale) {
+// The one launcher of preprocess_yuv_kernel; rois, m, roi_h, roi_w as above.
+int preprocess_yuv_launch(const void* src, float* dst, const int* rois, int n, int m, int src_h, int src_w, int dst_h, int dst_w,
+                          int roi_h, int roi_w, int planar, int reverse_channels, const float* mean, const float* std_scale) {
     PVHIP_REQUIRE_INIT();
     PVHIP_CHECK_ARG(src != nullptr && dst != nullptr);
     PVHIP_CHECK_ARG(n > 0 && n <= 65535 && src_h > 0 && src_w > 0 && dst_h > 0 && dst_w > 0);
@@ -422,7 +489,10 @@ int pvhip_input_preprocess_yuv_f32(const void* src, float* dst, int n, int src_h
     PVHIP_CHECK_ARG(planar == 0 || planar == 1);
     PVHIP_CHECK_ARG((size_t)src_h * (size_t)src_w * 3 < ((size_t)1 << 31));           // one image's elements index in 32 bits
     PVHIP_CHECK_ARG((size_t)dst_h * (size_t)dst_w * 3 < ((size_t)1 << 31));
-    const bool resize = src_h != dst_h || src_w != dst_w;
+    const bool roi = rois != nullptr;
+    if (roi) PVHIP_CHECK_ARG(m >= 1 && roi_h >= 1 && roi_h <= src_h && roi_w >= 1 && roi_w <= src_w);
+    const bool resize = roi || src_h != dst_h || src_w != dst_w;
+    const int tap_h = roi ? roi_h : src_h, tap_w = roi ? roi_w : src_w;
     auto extent = [&](int t, int S, int D) -> size_t {                                // as above
         if (!resize) return (size_t)t;
         const size_t e = ((size_t)(t - 1) * (size_t)S + (size_t)D - 1) / (size_t)D + 2;
@@ -430,10 +500,10 @@ int pvhip_input_preprocess_yuv_f32(const void* src, float* dst, int n, int src_h
     };
     // e consecutive rows (columns) lie over at most e / 2 + 1 chroma rows (pairs): the first may be an odd one
     auto halves = [](size_t e, int S) { return e / 2 + 1 < (size_t)S / 2 ? e / 2 + 1 : (size_t)S / 2; };
-    auto yslot_of = [&](int tw) { return (extent(tw, src_w, dst_w) + 30) / 16 * 16; };
-    auto cslot_of = [&](int tw) { return (halves(extent(tw, src_w, dst_w), src_w) * (planar ? 1 : 2) + 30) / 16 * 16; };
+    auto yslot_of = [&](int tw) { return (extent(tw, tap_w, dst_w) + 30) / 16 * 16; };
+    auto cslot_of = [&](int tw) { return (halves(extent(tw, tap_w, dst_w), src_w) * (planar ? 1 : 2) + 30) / 16 * 16; };
     auto stage_of = [&](int tw, int th) {
-        const size_t e = extent(th, src_h, dst_h);
+        const size_t e = extent(th, tap_h, dst_h);
         return e * yslot_of(tw) + halves(e, src_h) * (planar ? 2 : 1) * cslot_of(tw);
     };
     auto lds_of = [&](int tw, int th) { return stage_of(tw, th) + 12 * ((size_t)tw + (size_t)th); };
@@ -450,12 +520,47 @@ int pvhip_input_preprocess_yuv_f32(const void* src, float* dst, int n, int src_h
     a.hs = src_h; a.ws = src_w; a.hd = dst_h; a.wd = dst_w; a.tw = tw; a.th = th;
     a.planar = planar; a.reverse = reverse_channels ? 1 : 0;
     a.yslot = (unsigned)yslot_of(tw); a.cslot = (unsigned)cslot_of(tw); a.stage_bytes = (unsigned)stage_of(tw, th);
+    a.rois = rois; a.m = m; a.mh = roi_h; a.mw = roi_w;
     const bool vs = (uintptr_t)dst % 16 == 0 && dst_w % 4 == 0 && tw % 4 == 0;
     const size_t lds = lds_of(tw, th);
     hipStream_t st = state().stream;
-    resize ? launch_yuv<true>(a, grid, lds, vs, st) : launch_yuv<false>(a, grid, lds, vs, st);
+    if (roi) launch_yuv<true, true>(a, grid, lds, vs, st);
+    else     resize ? launch_yuv<true, false>(a, grid, lds, vs, st) : launch_yuv<false, false>(a, grid, lds, vs, st);
     PVHIP_LAUNCH_CHECK();
     return PVHIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pvhip_input_preprocess_f32(const void* src, float* dst, int n, int c, int src_h, int src_w, int dst_h, int dst_w,
+                               int src_u8, int src_nhwc, int reverse_channels, const float* mean, const float* std_scale) {
+    return preprocess_launch(src, dst, nullptr, n, n, c, src_h, src_w, dst_h, dst_w, src_h, src_w, src_u8, src_nhwc, reverse_channels,
+                             mean, std_scale);
+}
+
+int pvhip_input_preprocess_yuv_f32(const void* src, float* dst, int n, int src_h, int src_w, int dst_h, int dst_w, int planar,
+                                   int reverse_channels, const float* mean, const float* std_scale) {
+    return preprocess_yuv_launch(src, dst, nullptr, n, n, src_h, src_w, dst_h, dst_w, src_h, src_w, planar, reverse_channels, mean, std_scale);
+}
+
+int pvhip_input_preprocess_roi_f32(const void* src, float* dst, const int* rois, int n, int m, int c, int src_h, int src_w, int dst_h,
+                                   int dst_w, int max_roi_h, int max_roi_w, int src_u8, int src_nhwc, int reverse_channels,
+                                   const float* mean, const float* std_scale) {
+    PVHIP_REQUIRE_INIT();
+    PVHIP_CHECK_ARG(rois != nullptr);
+    return preprocess_launch(src, dst, rois, n, m, c, src_h, src_w, dst_h, dst_w, max_roi_h, max_roi_w, src_u8, src_nhwc, reverse_channels,
+                             mean, std_scale);
+}
+
+int pvhip_input_preprocess_yuv_roi_f32(const void* src, float* dst, const int* rois, int n, int m, int src_h, int src_w, int dst_h,
+                                       int dst_w, int max_roi_h, int max_roi_w, int planar, int reverse_channels, const float* mean,
+                                       const float* std_scale) {
+    PVHIP_REQUIRE_INIT();
+    PVHIP_CHECK_ARG(rois != nullptr);
+    return preprocess_yuv_launch(src, dst, rois, n, m, src_h, src_w, dst_h, dst_w, max_roi_h, max_roi_w, planar, reverse_channels, mean,
+                                 std_scale);
 }
 
 }  // extern "C"

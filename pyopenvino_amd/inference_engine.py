@@ -337,17 +337,25 @@ class InferRequest:
         self.start_async(inputs)
         return self.wait()
 
-    def input_buffer(self, name: str, source_size=None) -> np.ndarray:
+    def input_buffer(self, name: str, source_size=None, frames=None) -> np.ndarray:
         """The host array this request uploads input `name` from: page-locked memory the request owns, allocated on the first call, in
         the declared format (``IENetwork.input_info``; e.g. (256, 224, 224, 3) uint8 for U8 / NHWC).  Handing it to ``start_async({name:
         buf})`` costs no host copy: it is uploaded asynchronously on the copy stream while other requests compute.  With RESIZE_BILINEAR
         declared, `source_size` = (h, w) of the source images (default: the network's extent); the request keeps buffers for its
-        Executable_Network.MAX_SOURCE_EXTENTS most recently fed extents and drops older ones when it next starts a pass.
+        Executable_Network.MAX_SOURCE_EXTENTS most recently fed extents and drops older ones when it next starts a pass.  `frames` = m:
+        the buffer of the m frames of a ``RoiInput`` instead -- the same shape with m in place of the batch; each (extent, m) counts as
+        one of those extents.
 
         Ownership: the request reads this memory until its pass is done.  Fill it only between ``wait()`` (or before the first
         ``start_async``) and the next ``start_async()``; writing it while the request is in flight changes what the pass may see.  The
         memory is returned when the request's device state is released and the array is no longer referenced."""
-        return self.runner.host_inputs.buffer(name, source_size)
+        return self.runner.host_inputs.buffer(name, source_size, frames)
+
+    def roi_buffer(self, name: str) -> np.ndarray:
+        """The page-locked (n, 5) int32 table this request uploads the rectangles of a ``RoiInput`` of input `name` from, row b =
+        (id, x, y, w, h).  ``RoiInput(input_buffer(name, (h, w), frames=m), roi_buffer(name))`` costs no host copy; ownership as for
+        ``input_buffer``."""
+        return self.runner.host_inputs.roi_buffer(name)
 
 
 @contextlib.contextmanager

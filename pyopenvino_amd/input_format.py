@@ -12,7 +12,9 @@ class InputFormat:
     ``dims`` the (n, c, h, w) of the fp32 tensor the IR expects, ``supported`` / ``declared`` as InputInfo has them, ``u8`` / ``nhwc`` the
     declared precision and layout, ``resize`` / ``reverse`` / ``mean`` / ``std`` the declared preprocessing (fp32 arrays of c values, or
     None without MEAN_VALUE), ``color`` the declared colour format: 'RAW', or 'NV12' / 'I420' for YUV 4:2:0 frames, uint8 of shape
-    (n, 3 h / 2, w) whatever ``u8`` / ``nhwc`` say.  An extent is the (h, w) of a caller's image."""
+    (n, 3 h / 2, w) whatever ``u8`` / ``nhwc`` say.  An extent is the (h, w) of a caller's image.  A RoiInput's frames have the same
+    shapes with their own count m in place of n (``host_shape(extent, frames=m)``, ``frames_extent_of``) and a table ``checked_rois``
+    accepts."""
     name: str
     dims: tuple
     supported: bool
@@ -33,9 +35,11 @@ class InputFormat:
     def host_dtype(self):
         return np.dtype(np.uint8 if self.u8 or self.yuv else np.float32)
 
-    def host_shape(self, extent=None):
-        """The shape of a caller's array of `extent` (default: the network's own) in this layout."""
+    def host_shape(self, extent=None, frames=None):
+        """The shape of a caller's array of `extent` (default: the network's own) in this layout; `frames` = m: of the m frames of a
+        RoiInput (default: one image per batch row)."""
         n, c = self.dims[:2]
+        n = n if frames is None else frames
         h, w = extent if extent is not None else self.dims[2:]
         if self.yuv:
             return n, (h // 2 * 3 if isinstance(h, int) else '3h/2'), w
@@ -81,6 +85,57 @@ class InputFormat:
                 self.name, declared, self.host_shape(('h', 'w')), a.shape))
         return self.checked_extent((a.shape[1] // 3 * 2, a.shape[2]))
 
+    def _roi_declared(self):
+        if not self.resize:
+            raise ValueError('input {}: a RoiInput is cropped and resized on the device: it needs a declared resize '
+                             '(preprocess_info.resize_algorithm = \'RESIZE_BILINEAR\')'.format(self.name))
+
+    def checked_frames(self, frames) -> int:
+        """The frame count m of a RoiInput as an int >= 1 (any count: it is independent of the batch)."""
+        self._roi_declared()
+        if isinstance(frames, bool) or not isinstance(frames, (int, np.integer)) or frames < 1:
+            raise ValueError('input {}: a RoiInput has m >= 1 frames, not {!r}'.format(self.name, frames))
+        return int(frames)
+
+    def frames_extent_of(self, a):
+        """((h, w), m) of the frames array `a` of a RoiInput, checked against this format."""
+        self._roi_declared()
+        if self.yuv:
+            ok = a.ndim == 3 and a.shape[0] >= 1 and a.shape[1] % 3 == 0
+            declared, any_hw = 'declared {}'.format(self.color), 'any even h, w'
+        else:
+            ok = a.ndim == 4 and a.shape[0] >= 1 and a.shape[3 if self.nhwc else 1] == self.dims[1]
+            declared, any_hw = 'declared {} / {}'.format('U8' if self.u8 else 'FP32', 'NHWC' if self.nhwc else 'NCHW'), 'any h, w'
+        if not ok:
+            raise ValueError('input {}: {} frames of a RoiInput have shape {} for any m >= 1 and {}; got {}'.format(
+                self.name, declared, self.host_shape(('h', 'w'), frames='m'), any_hw, a.shape))
+        if self.yuv:
+            return self.checked_extent((a.shape[1] // 3 * 2, a.shape[2])), a.shape[0]
+        return self.checked_extent(a.shape[1:3] if self.nhwc else a.shape[2:4]), a.shape[0]
+
+    def checked_rois(self, rois, extent, frames):
+        """The table of a RoiInput over `frames` frames of `extent` as a C-contiguous int32 (n, 5) array, and the (max h, max w) of its
+        rectangles: row b = (id, x, y, w, h), the order of OpenVINO's ROI struct, is the rectangle [y, y + h) x [x, x + w) of frame id
+        that becomes batch row b.  Integers only, 0 <= id < frames, w, h >= 1 and the rectangle inside the frame."""
+        self._roi_declared()
+        t = np.asarray(rois)
+        n, (H, W) = self.dims[0], extent
+        if t.shape != (n, 5):
+            raise ValueError('input {}: rois is a table of shape {} -- one (id, x, y, w, h) per batch row --, got {}'.format(
+                self.name, (n, 5), t.shape))
+        if t.dtype.kind not in 'iu':
+            raise ValueError('input {}: rois holds integers (id, x, y, w, h), got dtype {}'.format(self.name, t.dtype))
+        if t.dtype == np.uint64 and (t > np.iinfo(np.int64).max).any():
+            t = np.minimum(t, np.uint64(np.iinfo(np.int64).max))          # (refused below, whichever column)
+        t = t.astype(np.int64)
+        i, x, y, w, h = t.T
+        bad = (i < 0) | (i >= frames) | (x < 0) | (y < 0) | (w < 1) | (h < 1) | (x > W - w) | (y > H - h)
+        if bad.any():
+            b = int(np.argmax(bad))
+            raise ValueError('input {}: rois[{}] = {} is no rectangle (id, x, y, w, h) with w, h >= 1 inside one of {} frames of {}'.format(
+                self.name, b, tuple(int(v) for v in t[b]), frames, (H, W)))
+        return np.ascontiguousarray(t, np.int32), (int(h.max()), int(w.max()))
+
     def needs_preprocess(self, extent) -> bool:
         """Arrays of `extent` go through pvhip_input_preprocess_f32 (YUV frames: pvhip_input_preprocess_yuv_f32, always): something
         besides the format change is in effect."""
@@ -89,6 +144,25 @@ class InputFormat:
     def needs_convert(self, extent) -> bool:
         """Arrays of `extent` are not the fp32 NCHW tensor itself: they are uploaded into a staging tensor and converted by one launch."""
         return self.needs_preprocess(extent) or self.u8 or self.nhwc
+
+
+class RoiInput:
+    """A network input given as regions of interest (OpenVINO 2021's ROI blobs, ``make_shared_blob(frame, ROI{id, posX, posY, sizeX,
+    sizeY})``): ``infer({name: RoiInput(frames, rois)})``.  `frames`: m >= 1 source frames in the input's declared host format -- the
+    leading count is m, whatever the batch n --; `rois`: an integer (n, 5) table, row b = (id, x, y, w, h): batch row b is the rectangle
+    [y, y + h) x [x, x + w) of frame id, cropped and then resized to the network's extent, reversed and scaled as declared, on the
+    device in one launch (pvhip_input_preprocess_roi_f32 / _yuv_roi_f32).  The frames are uploaded once, however many rows read them, and
+    are not modified.  The input needs ``preprocess_info.resize_algorithm = 'RESIZE_BILINEAR'``.  The bilinear taps clamp at the edge
+    of the rectangle, not of the frame; a rectangle of exactly the network's extent is copied; an NV12 / I420 rectangle may have an odd
+    origin and odd sizes (only the frame's extent is even).  With `frames` = ``InferRequest.input_buffer(name, (h, w), frames=m)`` and
+    `rois` = ``InferRequest.roi_buffer(name)`` nothing is copied on the host."""
+    __slots__ = ('frames', 'rois')
+
+    def __init__(self, frames, rois):
+        self.frames, self.rois = frames, rois
+
+    def __repr__(self):
+        return 'RoiInput(frames={}, rois={})'.format(getattr(self.frames, 'shape', None), getattr(self.rois, 'shape', None))
 
 
 class InputInfo:
@@ -209,11 +283,13 @@ class InputInfo:
         """The (h, w) a caller's array has: `source_size` with RESIZE_BILINEAR declared, else the network's own."""
         return self.frozen().checked_extent(source_size)
 
-    def host_format(self, source_size=None):
+    def host_format(self, source_size=None, frames=None):
         """(shape, dtype) of the array a caller hands in this format; with RESIZE_BILINEAR declared, `source_size` = (h, w) of the source
-        (default: the network's extent)."""
+        (default: the network's extent) and `frames` = m: of the m frames of a RoiInput."""
         f = self.frozen()
-        return f.host_shape(f.checked_extent(source_size)), f.host_dtype
+        if frames is not None:
+            frames = f.checked_frames(frames)
+        return f.host_shape(f.checked_extent(source_size), frames), f.host_dtype
 
 
 class PreProcessChannel:
