@@ -27,6 +27,28 @@ SAMPLE_256 = sorted(set(range(8)) | set(range(248, 256)) |
 SAMPLE_128 = sorted(set(range(8)) | set(range(120, 128)) |
                     set(int(i) for i in np.random.default_rng(128).choice(np.arange(8, 120), 16, replace=False)))
 
+MIN_SAMPLE = 12         # sample() never returns fewer images than this (or the whole batch)
+
+
+def sample(n, first=8, last=8, between=16):
+    """The images of a batch of n a layer check compares: the first `first` (image 0 always), the last `last` (the last tiles of every
+    walk) and `between` positions in between, drawn by default_rng(n); the whole batch when n <= 16.  The defaults are the counts of
+    SAMPLE_256 / SAMPLE_128, which sample(256) / sample(128) reproduce.  Whatever the counts: both ends, and at least MIN_SAMPLE images."""
+    n = int(n)
+    if n <= 16:
+        return list(range(n))
+    if first < 1 or last < 1 or between < 0:
+        raise ValueError('a sample holds both ends of the batch')
+    lo, hi = min(first, n), max(n - last, 0)
+    gap = np.arange(lo, hi)
+    mid = np.random.default_rng(n).choice(gap, min(between, len(gap)), replace=False) if len(gap) else ()
+    out = sorted(set(range(lo)) | set(range(hi, n)) | set(int(i) for i in mid))
+    if len(out) < MIN_SAMPLE:
+        raise ValueError('{} images of a batch of {}: a sample holds at least {}'.format(len(out), n, MIN_SAMPLE))
+    assert out[0] == 0 and out[-1] == n - 1
+    return out
+
+
 # SSD-MobileNet's prior-box subgraph: per feature map the two ShapeOf -> StridedSlice shape vectors, PriorBoxClustered (its boxes computed
 # once on the host and cached on the device) and the Unsqueeze; then the Concat of the six.  Its values depend on shapes only.
 SSD_PRIOR_BOX_SUBGRAPH = sorted(['PriorBoxClustered_{}{}'.format(k, s_) for k in range(6)
@@ -400,7 +422,7 @@ def family(G, ex, g):
     node = G.nodes[convs[-1]]
     f16_kind = node.get('_hip_f16') or G.nodes[g['launch']].get('_hip_f16')        # FP16 IRs: what the launch's kernel recorded
     fam = 'f16 ' + f16_kind if f16_kind else conv_family(node)
-    if 'Winograd' in fam and 'stem' not in fam:
+    if fam in ('Winograd F(4x4,3x3)', 'Winograd F(2x2,5x5)'):         # the six-point layers (wino4_conv); F(2x2,3x3) has one form
         fam += ' / ' + wino4_form(node)
     lead = [G.nodes[n]['type'] for n in g['nodes'] if n not in convs and G.nodes[n]['type'] in ('MaxPool', 'LRN')]
     return ' + '.join(lead + [fam])
@@ -536,3 +558,70 @@ def check_detections(net, sample):
         counts[i] = compare_detections(out[0, 0, i * per:(i + 1) * per], want[0, 0, j * per:(j + 1) * per], 'DetectionOutput image {}'.format(i))
         assert counts[i] > 0 and out[0, 0, i * per, 1] > 0, 'image {}: no detections, the check would be vacuous'.format(i)
     return counts
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the census of kernel forms per batch (tests/test_batch_forms.py; no device needed)
+def launch_forms(net, ex, n):
+    """{conv name: (family, wino4 form or None, Route)} of every Convolution launch of the plan `ex` holds, at batch n.  family:
+    Convolution.kernel_kind's for an fp32 IR; 'f16 ' + the Route's label for an FP16 IR (what the launch leaves in node['_hip_f16'])."""
+    import test_conv_routes
+    from pyopenvino_amd.op_plugins import Convolution
+    G, out = net.G, {}
+    for cid, facts in test_conv_routes.launch_facts(ex).items():
+        node = G.nodes[cid]
+        assert node['input'][0]['dims'][0] == n, node['name']
+        r = Convolution.route(*facts)
+        fam, form = ('f16 ' + str(r.label), None) if ex.plan.f16 else (conv_family(node), None)
+        if fam in ('Winograd F(4x4,3x3)', 'Winograd F(2x2,5x5)') and r.entry == 'pvhip_conv2d_f32':
+            form = wino4_form(node)
+        out[node['name']] = (fam, form, r)
+    return out
+
+
+class Census:
+    """One loaded network whose batch is rewritten in place: at(n) sets the port dims to batch n with the network's own set_batch (from a
+    snapshot of the batch-1 dims), rebuilds the fusion plan and asks the library what every Convolution launch of that plan takes."""
+
+    def __init__(self, model, fp16, tmp_dir):
+        from pyopenvino_amd import IECore, synth
+        ie = IECore(plugin_package='pyopenvino_amd.op_plugins')
+        blob = synth.synth_weights(model, 1234)
+        if fp16:
+            xml16, blob16 = synth.fp16_ir(model, blob, tmp_dir)
+            self.net = ie.read_network(xml16, weights=blob16, fp16_as_fp32=False)
+        else:
+            self.net = ie.read_network(model, weights=blob)
+        assert self.net.batch_size == 1
+        self.fp16 = fp16
+        self.ex = ie.load_network(self.net)
+        G = self.net.G
+        self._dims = {(nid, side, p): tuple(d['dims']) for nid in G.nodes for side in ('input', 'output')
+                      for p, d in G.nodes[nid].get(side, {}).items()}
+        self._shapes = {nid: tuple(G.nodes[nid]['data']['shape']) for nid in G.nodes if G.nodes[nid]['type'] == 'Parameter'}
+
+    def at(self, n):
+        """launch_forms of the plan at batch n."""
+        G = self.net.G
+        for (nid, side, p), dims in self._dims.items():
+            G.nodes[nid][side][p]['dims'] = dims
+        for nid, shape in self._shapes.items():
+            G.nodes[nid]['data']['shape'] = shape
+        self.net.batch_size = 1
+        self.net.set_batch(n)
+        self.ex.plan_fusion()
+        return launch_forms(self.net, self.ex, n)
+
+
+def census_classes(census, batches):
+    """The sweep reduced to its breakpoints: ([(first batch of a class, {conv name: [family, wino4 form]})], whether any Route differs
+    anywhere in the sweep).  A new class starts wherever any launch's entry (family, form or Route) differs from the batch before."""
+    classes, first, last, routes_vary = [], None, None, False
+    for n in batches:
+        now = census.at(n)
+        first = now if first is None else first
+        routes_vary = routes_vary or {k: e[2] for k, e in now.items()} != {k: e[2] for k, e in first.items()}
+        if now != last:
+            classes.append((n, {name: [e[0], e[1]] for name, e in now.items()}))
+            last = now
+    return classes, routes_vary

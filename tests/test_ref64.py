@@ -258,6 +258,32 @@ def test_f16_bound_is_one_fp16_rounding():
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# sample(): the images a layer check compares
+def test_sample_reproduces_the_constants():
+    assert ref64.sample(256) == ref64.SAMPLE_256 and len(ref64.SAMPLE_256) == 32
+    assert ref64.sample(128) == ref64.SAMPLE_128 and len(ref64.SAMPLE_128) == 32
+
+
+def test_sample_holds_both_ends_and_never_fewer_than_twelve_images():
+    for n in range(1, 300):
+        for counts in ({}, {'first': 4, 'last': 8, 'between': 4}, {'first': 4, 'last': 8, 'between': 0}):
+            s = ref64.sample(n, **counts)
+            assert s == sorted(set(s)) and s[0] == 0 and s[-1] == n - 1, (n, counts)
+            if n <= 16:
+                assert s == list(range(n))
+                continue
+            first, last = counts.get('first', 8), counts.get('last', 8)
+            assert set(range(min(first, n))) <= set(s) and set(range(n - last, n)) <= set(s)
+            assert len(s) >= ref64.MIN_SAMPLE
+            assert len(s) == min(n, first + last + counts.get('between', 16)), (n, counts)
+        assert ref64.sample(n, first=4, last=8, between=4) == ref64.sample(n, first=4, last=8, between=4)         # seeded by n alone
+    assert len(ref64.sample(255, first=4, last=8, between=4)) == 16
+    for counts in ({'first': 1, 'last': 8, 'between': 2}, {'first': 4, 'last': 4, 'between': 0}, {'first': 0}, {'last': 0}):
+        with pytest.raises(ValueError):
+            ref64.sample(100, **counts)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # groups() on the plan bench.py times (GoogLeNet fp32, batch 256, default knobs): no device needed to plan
 def test_groups_of_the_batch256_plan_cover_every_node_once():
     from pyopenvino_amd import device, synth
