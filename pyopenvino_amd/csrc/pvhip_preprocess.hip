@@ -7,17 +7,19 @@
 // 64-bit integers; i0 = min(num / 2D, S-1), i1 = min(i0+1, S-1), f = (num - 2D i0) / 2D as ONE correctly rounded fp32 division (0 at
 // the last source index).  v = (1-fy)((1-fx)p00 + fx p01) + fy((1-fx)p10 + fx p11) in fp32, in that order, never contracted to fma.
 // Then y = (v - mean[c]) / std_scale[c], output channel c reading source channel C-1-c under reversal.  tests/preprocess_ref.py is the
-// same rule in numpy; the kernel matches it bit for bit.
+// same rule in numpy; the kernels match it bit for bit.
 //
-// A workgroup owns a tile of `th` output rows x `tw` output columns of one image (normally whole rows).  It
-//   1. tabulates the tile's column and row coordinates (x0, x1, fx), (y0, y1, fy) in LDS;
-//   2. stages the source it reads -- per channel plane (NCHW) or for all channels at once (NHWC), the rows y0(first)..y1(last), each the
-//      contiguous span of columns x0(first)..x1(last) -- into LDS with 16-byte loads; every span keeps its address modulo 16 in LDS, so
-//      any source alignment takes the wide loads, with byte-wise head and tail;
-//   3. has every lane produce 4 consecutive output pixels of one row, for every channel, stored as float4 nontemporal stores into each
-//      channel plane (scalar stores when the destination rows are not 16-byte aligned).
-//
-// YUV 4:2:0 frames (NV12, I420) take the same launch with a colour conversion in front of the taps: preprocess_yuv_kernel, further down.
+// Two kernels -- preprocess_kernel for U8 / FP32 images, preprocess_yuv_kernel for YUV 4:2:0 frames (NV12, I420), which converts every
+// tapped pixel to B, G, R in front of the interpolation -- differ in what they stage and in their inner loops, and share the rest (TileArgs):
+// a workgroup owns a tile of `th` output rows x `tw` output columns of one image (normally whole rows; plan_tiles).  It
+//   1. finds its tile and the source extent its taps see (tile_of);
+//   2. tabulates the tile's column and row coordinates (x0, x1, fx), (y0, y1, fy) in LDS (fill_tables);
+//   3. stages the source it reads -- for every row y0(first)..y1(last) the contiguous span of columns x0(first)..x1(last): per channel
+//      plane (NCHW), for all channels at once (NHWC), or of the Y plane and of the chroma under it (YUV) -- into LDS with 16-byte loads
+//      (stage_block); every span keeps its address modulo 16 in LDS (span_base), so any source alignment takes the wide loads, with
+//      byte-wise head and tail;
+//   4. has every lane produce 4 consecutive output pixels of one row, for every channel, stored as float4 nontemporal stores into each
+//      channel plane, scalar stores when the destination rows are not 16-byte aligned (finish_quad).
 //
 // Regions of interest (the ROI entries): image b of the output is the rectangle rois[b] = (id, x, y, w, h) of frame id of m frames, cropped
 // and then resized -- the taps clamp at the rectangle's edge, not the frame's.  Both kernels take it as a template parameter: a workgroup
@@ -63,42 +65,102 @@ __device__ __forceinline__ Tap tap(int d, int S, int D) {
     return t;
 }
 
-struct PrepArgs {
+// What a launch of either kernel is given; each kernel's own members follow it (PrepArgs, YuvArgs).
+struct TileArgs {
     const unsigned char* src;
     float* dst;
     const float* mean;        // NULL: no mean
     const float* std_scale;   // NULL: no scale
-    int c, hs, ws, hd, wd, tw, th;
-    int nhwc, reverse;
-    unsigned slot;            // LDS bytes per staged span (a multiple of 16)
+    int hs, ws, hd, wd, tw, th;
+    int reverse;
     unsigned stage_bytes;     // LDS bytes of the staging area (the coordinate tables follow it)
     const int* rois;          // ROI kernels: n x (id, x, y, w, h); hs, ws are then the extent of each of the m frames
     int m, mh, mw;            // ... the frame count and the largest h and w the launch was sized for
 };
 
-// One image's rectangle (ROI kernels), read once per workgroup; ok: it lies inside frame id and within the launch's maxima.
-struct Roi {
-    int id, x, y, w, h;
-    bool ok;
+// The tile of one workgroup: columns tx0.. (twv of them) of rows ty0.. (thv of them) of image n, whose taps see a source of hs x ws
+// pixels: the whole of source image img = n, or (ROI kernels) the rectangle at column ox, row oy of frame img.
+struct Tile {
+    int n, tx0, ty0, twv, thv;
+    int hs, ws, img, ox, oy;
 };
 
-__device__ __forceinline__ Roi roi_of(const int* rois, int b, int m, int hs, int ws, int mh, int mw) {
-    const int* q = rois + 5 * (size_t)b;
-    Roi r;
-    r.id = q[0]; r.x = q[1]; r.y = q[2]; r.w = q[3]; r.h = q[4];
-    r.ok = r.id >= 0 && r.id < m && r.x >= 0 && r.y >= 0 && r.w >= 1 && r.h >= 1 && r.w <= mw && r.h <= mh
-        && (long long)r.x + r.w <= ws && (long long)r.y + r.h <= hs;
-    return r;
+// grid (ceil(wd / tw), ceil(hd / th), n).  ROI: the image's rectangle (id, x, y, w, h) is read once per workgroup; false: it does not lie
+// inside frame id or exceeds the launch's maxima, the tile is filled with quiet NaN in all c planes and the workgroup is done.
+template <bool ROI>
+__device__ __forceinline__ bool tile_of(const TileArgs& a, int c, Tile& t) {
+    t.n = blockIdx.z; t.tx0 = blockIdx.x * a.tw; t.ty0 = blockIdx.y * a.th;
+    t.twv = min(a.tw, a.wd - t.tx0); t.thv = min(a.th, a.hd - t.ty0);
+    t.hs = a.hs; t.ws = a.ws; t.img = t.n; t.ox = 0; t.oy = 0;
+    if (ROI) {
+        const int* q = a.rois + 5 * (size_t)t.n;
+        t.img = q[0]; t.ox = q[1]; t.oy = q[2]; t.ws = q[3]; t.hs = q[4];
+        if (t.img >= 0 && t.img < a.m && t.ox >= 0 && t.oy >= 0 && t.ws >= 1 && t.hs >= 1 && t.ws <= a.mw && t.hs <= a.mh
+            && (long long)t.ox + t.ws <= a.ws && (long long)t.oy + t.hs <= a.hs)
+            return true;
+        const size_t plane_out = (size_t)a.hd * a.wd;
+        float* out_n = a.dst + (size_t)t.n * c * plane_out;
+        for (int oc = 0; oc < c; ++oc)
+            for (int i = threadIdx.x; i < t.thv * t.twv; i += kBlock) {
+                const int r = i / t.twv;
+                out_n[oc * plane_out + (size_t)(t.ty0 + r) * a.wd + t.tx0 + (i - r * t.twv)] = __builtin_nanf("");
+            }
+        return false;
+    }
+    return true;
 }
 
-// The tile (tx0.., ty0..) of twv x thv pixels in every one of c planes of one image: quiet NaN (an invalid rectangle).
-__device__ __forceinline__ void fill_nan(float* out_n, int c, size_t plane_out, int wd, int tx0, int ty0, int twv, int thv) {
-    const float q = __builtin_nanf("");
-    for (int oc = 0; oc < c; ++oc)
-        for (int i = threadIdx.x; i < thv * twv; i += kBlock) {
-            const int r = i / twv;
-            out_n[oc * plane_out + (size_t)(ty0 + r) * wd + tx0 + (i - r * twv)] = q;
-        }
+// The coordinate tables of a tile, in dynamic LDS behind the staging area: (x0, x1, fx) of each of its tw columns, then (y0, y1, fy) of
+// each of its th rows -- bytes(tw, th) in all --, and the source the tile reads (the taps are monotone in d): columns xs0..xs1 of rows
+// ys0..ys1.
+struct Tables {
+    int *cx0, *cx1;
+    float* cfx;
+    int *ry0, *ry1;
+    float* rfy;
+    int xs0, xs1, ys0, ys1;
+    static constexpr size_t bytes(int tw, int th) { return 3 * sizeof(int) * ((size_t)tw + (size_t)th); }
+};
+
+// taps(d, S, D): the Tap of destination index d.  Read the tables after a __syncthreads().
+template <class Taps>
+__device__ __forceinline__ Tables fill_tables(unsigned char* lds, const TileArgs& a, const Tile& t, Taps taps) {
+    Tables b;
+    b.cx0 = reinterpret_cast<int*>(lds + a.stage_bytes);
+    b.cx1 = b.cx0 + a.tw;
+    b.cfx = reinterpret_cast<float*>(b.cx1 + a.tw);
+    b.ry0 = reinterpret_cast<int*>(b.cfx + a.tw);
+    b.ry1 = b.ry0 + a.th;
+    b.rfy = reinterpret_cast<float*>(b.ry1 + a.th);
+    for (int j = threadIdx.x; j < t.twv; j += kBlock) {
+        const Tap p = taps(t.tx0 + j, t.ws, a.wd);
+        b.cx0[j] = p.i0; b.cx1[j] = p.i1; b.cfx[j] = p.f;
+    }
+    for (int j = threadIdx.x; j < t.thv; j += kBlock) {
+        const Tap p = taps(t.ty0 + j, t.hs, a.hd);
+        b.ry0[j] = p.i0; b.ry1[j] = p.i1; b.rfy[j] = p.f;
+    }
+    b.xs0 = taps(t.tx0, t.ws, a.wd).i0; b.xs1 = taps(t.tx0 + t.twv - 1, t.ws, a.wd).i1;
+    b.ys0 = taps(t.ty0, t.hs, a.hd).i0; b.ys1 = taps(t.ty0 + t.thv - 1, t.hs, a.hd).i1;
+    return b;
+}
+
+// A span -- contiguous source bytes starting at g -- is staged into an LDS slot (16-byte aligned, at least span + 30 bytes rounded down
+// to 16) at the source's address modulo 16: its byte j lies at span_base(slot, g) + j.
+__device__ __forceinline__ int misalign(const unsigned char* g) { return (int)((uintptr_t)g & 15); }
+
+__device__ __forceinline__ const unsigned char* span_base(const unsigned char* slot, const unsigned char* g) { return slot + misalign(g); }
+
+// Block k of the slot: 16 aligned source bytes in one load, or those of them that belong to the span (its head and tail) byte by byte.
+__device__ __forceinline__ void stage_block(const unsigned char* g, int span, unsigned char* slot, unsigned k) {
+    const int lo = 16 * (int)k - misalign(g);                 // the block's first byte, relative to the span's
+    const unsigned char* b = g + lo;
+    unsigned char* l = slot + 16 * k;
+    if (lo >= 0 && lo + 16 <= span) {
+        *reinterpret_cast<u4v*>(l) = *reinterpret_cast<const u4v*>(b);
+    } else {
+        for (int t = lo < 0 ? -lo : 0; t < 16 && lo + t < span; ++t) l[t] = b[t];
+    }
 }
 
 template <bool U8>
@@ -113,99 +175,92 @@ __device__ __forceinline__ void stg4_nt(float* p, const float (&v)[4]) {
     __builtin_nontemporal_store(w, reinterpret_cast<f4v*>(p));
 }
 
-// grid (ceil(wd / tw), ceil(hd / th), n); dynamic LDS stage_bytes + 12 (tw + th) bytes.
+// The quad v of output channel oc, destined for o[0..3] (columns j0.. of a tile of twv): mean, scale, store.
 // VS: every tile's quads start 16-byte aligned in every output plane (dst aligned, wd and tw multiples of 4).
-// ROI (with RESIZE): image n is a rectangle of a frame (see the file comment); hs, ws below are the extent the taps see.
+template <bool VS>
+__device__ __forceinline__ void finish_quad(const TileArgs& a, int oc, float (&v)[4], float* o, int j0, int twv) {
+    if (a.mean != nullptr) {
+        const float m = a.mean[oc];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) v[u] = v[u] - m;
+    }
+    if (a.std_scale != nullptr) {
+        const float d = a.std_scale[oc];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) v[u] = v[u] / d;
+    }
+    if (VS && j0 + 3 < twv) {
+        stg4_nt(o, v);
+    } else {
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+            if (j0 + u < twv) o[u] = v[u];
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------ U8 / FP32 images
+struct PrepArgs : TileArgs {
+    int c, nhwc;
+    unsigned slot;            // LDS bytes per staged span (a multiple of 16)
+};
+
+// dynamic LDS stage_bytes + Tables::bytes(tw, th).  ROI (with RESIZE): image n is a rectangle of a frame (see the file comment).
 template <bool U8, bool RESIZE, bool VS, bool ROI>
 __global__ __launch_bounds__(kBlock) void preprocess_kernel(PrepArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     constexpr int ES = U8 ? 1 : 4;
-    const int n = blockIdx.z, tx0 = blockIdx.x * a.tw, ty0 = blockIdx.y * a.th;
-    const int twv = min(a.tw, a.wd - tx0), thv = min(a.th, a.hd - ty0);
-    int hs = a.hs, ws = a.ws, img = n, ox = 0, oy = 0;
-    bool copy = false;                                        // (workgroup-uniform) the rectangle has the destination's extent
-    if (ROI) {
-        const Roi q = roi_of(a.rois, n, a.m, a.hs, a.ws, a.mh, a.mw);
-        if (!q.ok) {
-            fill_nan(a.dst + (size_t)n * a.c * ((size_t)a.hd * a.wd), a.c, (size_t)a.hd * a.wd, a.wd, tx0, ty0, twv, thv);
-            return;
-        }
-        hs = q.h; ws = q.w; img = q.id; ox = q.x; oy = q.y;
-        copy = !U8 && q.h == a.hd && q.w == a.wd;             // (bytes interpolate to the same bits: weight 0 on a finite value)
-    }
-    auto taps = [&](int d, int S, int D) { return ROI && copy ? tap<false>(d, S, D) : tap<RESIZE>(d, S, D); };
-    int* cx0 = reinterpret_cast<int*>(lds + a.stage_bytes);
-    int* cx1 = cx0 + a.tw;
-    float* cfx = reinterpret_cast<float*>(cx1 + a.tw);
-    int* ry0 = reinterpret_cast<int*>(cfx + a.tw);
-    int* ry1 = ry0 + a.th;
-    float* rfy = reinterpret_cast<float*>(ry1 + a.th);
-    for (int j = threadIdx.x; j < twv; j += kBlock) {
-        const Tap t = taps(tx0 + j, ws, a.wd);
-        cx0[j] = t.i0; cx1[j] = t.i1; cfx[j] = t.f;
-    }
-    for (int j = threadIdx.x; j < thv; j += kBlock) {
-        const Tap t = taps(ty0 + j, hs, a.hd);
-        ry0[j] = t.i0; ry1[j] = t.i1; rfy[j] = t.f;
-    }
-    // the source the tile reads (the taps are monotone in d): columns xs0..xs1 of rows ys0..ys1
-    const int xs0 = taps(tx0, ws, a.wd).i0, xs1 = taps(tx0 + twv - 1, ws, a.wd).i1;
-    const int ys0 = taps(ty0, hs, a.hd).i0, ys1 = taps(ty0 + thv - 1, hs, a.hd).i1;
-    const int rows = ys1 - ys0 + 1;
+    Tile t;
+    if (!tile_of<ROI>(a, a.c, t)) return;
+    // (workgroup-uniform) the rectangle has the destination's extent: fp32 sources are copied, identity weights would turn an inf
+    // neighbour into NaN (bytes interpolate to the same bits: weight 0 on a finite value)
+    const bool copy = ROI && !U8 && t.hs == a.hd && t.ws == a.wd;
+    const Tables tb = fill_tables(lds, a, t, [&](int d, int S, int D) { return copy ? tap<false>(d, S, D) : tap<RESIZE>(d, S, D); });
+    const int rows = tb.ys1 - tb.ys0 + 1;
     const int cs = a.nhwc ? a.c : 1, planes = a.nhwc ? 1 : a.c;
-    const int span = (xs1 - xs0 + 1) * cs * ES;              // bytes of one staged span
+    const int span = (tb.xs1 - tb.xs0 + 1) * cs * ES;        // bytes of one staged span
     // span s = plane * rows + row: its first byte in the source
     auto span_src = [&](int s) -> const unsigned char* {
         const int p = s / rows, r = s - p * rows;
-        const size_t e = a.nhwc ? ((size_t)img * a.hs + oy + ys0 + r) * a.ws * (size_t)a.c + (size_t)(ox + xs0) * a.c
-                                : (((size_t)img * a.c + p) * a.hs + oy + ys0 + r) * a.ws + ox + xs0;
+        const size_t e = a.nhwc ? ((size_t)t.img * a.hs + t.oy + tb.ys0 + r) * a.ws * (size_t)a.c + (size_t)(t.ox + tb.xs0) * a.c
+                                : (((size_t)t.img * a.c + p) * a.hs + t.oy + tb.ys0 + r) * a.ws + t.ox + tb.xs0;
         return a.src + e * ES;
     };
     const unsigned bps = (unsigned)span / 16 + 2;             // 16-byte blocks a span touches at most
     const unsigned nblk = (unsigned)(planes * rows) * bps;
     for (unsigned i = threadIdx.x; i < nblk; i += kBlock) {
-        const unsigned s = i / bps, k = i - s * bps;
-        const unsigned char* g = span_src((int)s);
-        const int sh = (int)((uintptr_t)g & 15);
-        const int lo = 16 * (int)k - sh;                      // the block's first byte, relative to the span's
-        const unsigned char* b = g + lo;
-        unsigned char* l = lds + s * a.slot + 16 * k;         // the span's byte j lies at s * slot + sh + j
-        if (lo >= 0 && lo + 16 <= span) {
-            *reinterpret_cast<u4v*>(l) = *reinterpret_cast<const u4v*>(b);
-        } else {
-            for (int t = lo < 0 ? -lo : 0; t < 16 && lo + t < span; ++t) l[t] = b[t];
-        }
+        const unsigned s = i / bps;
+        stage_block(span_src((int)s), span, lds + s * a.slot, i - s * bps);
     }
     __syncthreads();
 
-    const int nq = (twv + 3) >> 2;
+    const int nq = (t.twv + 3) >> 2;
     const size_t plane_out = (size_t)a.hd * a.wd;
-    float* out_n = a.dst + (size_t)n * a.c * plane_out;
-    for (int i = threadIdx.x; i < thv * nq; i += kBlock) {
+    float* out_n = a.dst + (size_t)t.n * a.c * plane_out;
+    for (int i = threadIdx.x; i < t.thv * nq; i += kBlock) {
         const int r = i / nq, j0 = 4 * (i - r * nq);
-        const int y0 = ry0[r] - ys0, y1 = ry1[r] - ys0;
-        const float fy = rfy[r], gy = 1.0f - fy;
+        const int y0 = tb.ry0[r] - tb.ys0, y1 = tb.ry1[r] - tb.ys0;
+        const float fy = tb.rfy[r], gy = 1.0f - fy;
         int xa[4], xb[4];
         float fx[4], gx[4];
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-            const int j = j0 + u < twv ? j0 + u : j0;         // (a pixel past the tile computes column j0 again and is not stored)
-            xa[u] = (cx0[j] - xs0) * cs;
-            xb[u] = (cx1[j] - xs0) * cs;
-            fx[u] = cfx[j];
+            const int j = j0 + u < t.twv ? j0 + u : j0;       // (a pixel past the tile computes column j0 again and is not stored)
+            xa[u] = (tb.cx0[j] - tb.xs0) * cs;
+            xb[u] = (tb.cx1[j] - tb.xs0) * cs;
+            fx[u] = tb.cfx[j];
             gx[u] = 1.0f - fx[u];
         }
-        float* o = out_n + (size_t)(ty0 + r) * a.wd + tx0 + j0;
+        float* o = out_n + (size_t)(t.ty0 + r) * a.wd + t.tx0 + j0;
         for (int oc = 0; oc < a.c; ++oc, o += plane_out) {
             const int sc = a.reverse ? a.c - 1 - oc : oc;
             const int s0 = (a.nhwc ? 0 : sc) * rows + y0, s1 = (a.nhwc ? 0 : sc) * rows + y1;
-            const unsigned char* l0 = lds + (unsigned)s0 * a.slot + ((uintptr_t)span_src(s0) & 15);
-            const unsigned char* l1 = lds + (unsigned)s1 * a.slot + ((uintptr_t)span_src(s1) & 15);
+            const unsigned char* l0 = span_base(lds + (unsigned)s0 * a.slot, span_src(s0));
+            const unsigned char* l1 = span_base(lds + (unsigned)s1 * a.slot, span_src(s1));
             const int ch = a.nhwc ? sc : 0;
             float v[4];
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
-                if (RESIZE && !(ROI && copy)) {
+                if (RESIZE && !copy) {
                     const float top = gx[u] * pixel<U8>(l0, xa[u] + ch) + fx[u] * pixel<U8>(l0, xb[u] + ch);
                     const float bot = gx[u] * pixel<U8>(l1, xa[u] + ch) + fx[u] * pixel<U8>(l1, xb[u] + ch);
                     v[u] = gy * top + fy * bot;
@@ -213,23 +268,7 @@ __global__ __launch_bounds__(kBlock) void preprocess_kernel(PrepArgs a) {
                     v[u] = pixel<U8>(l0, xa[u] + ch);
                 }
             }
-            if (a.mean != nullptr) {
-                const float m = a.mean[oc];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) v[u] = v[u] - m;
-            }
-            if (a.std_scale != nullptr) {
-                const float d = a.std_scale[oc];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) v[u] = v[u] / d;
-            }
-            if (VS && j0 + 3 < twv) {
-                stg4_nt(o, v);
-            } else {
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-                    if (j0 + u < twv) o[u] = v[u];
-            }
+            finish_quad<VS>(a, oc, v, o, j0, t.twv);
         }
     }
 }
@@ -248,21 +287,13 @@ void launch(const PrepArgs& a, dim3 grid, size_t lds, bool vs, hipStream_t st) {
 // with the (U, V) of the pixel's 2 x 2 block (no chroma interpolation); the uint8 image that gives is then resized, reversed and scaled
 // exactly as a U8 NHWC source is above.  tests/yuv_ref.py is the conversion in numpy; every intermediate stays within +-5.7e8.
 //
-// The kernel has preprocess_kernel's shape.  A tile stages the Y spans it reads and, behind them, the chroma spans under them: rows
-// ys0/2..ys1/2, of each the pairs xs0/2..xs1/2 of the ABSOLUTE columns (a tile may start on an odd column) -- one span per row for NV12,
-// one in each plane for I420.  A pixel is converted where it is tapped, so a downscale converts four pixels per output pixel however
-// many it staged, and the three channels of a quad come from one pass over its taps.
-struct YuvArgs {
-    const unsigned char* src;
-    float* dst;
-    const float* mean;        // NULL: no mean
-    const float* std_scale;   // NULL: no scale
-    int hs, ws, hd, wd, tw, th;
-    int planar, reverse;
+// A tile stages the Y spans it reads and, behind them, the chroma spans under them: rows ys0/2..ys1/2, of each the pairs xs0/2..xs1/2 of
+// the ABSOLUTE columns (a tile may start on an odd column) -- one span per row for NV12, one in each plane for I420.  A pixel is converted
+// where it is tapped, so a downscale converts four pixels per output pixel however many it staged, and the three channels of a quad come
+// from one pass over its taps.
+struct YuvArgs : TileArgs {
+    int planar;
     unsigned yslot, cslot;    // LDS bytes per staged Y span and per staged chroma span (multiples of 16)
-    unsigned stage_bytes;     // LDS bytes of the staging area (the coordinate tables follow it)
-    const int* rois;          // ROI kernels: as in PrepArgs
-    int m, mh, mw;
 };
 
 // B, G, R (in that order) of one pixel, as the floats of the converted bytes.
@@ -278,48 +309,22 @@ __device__ __forceinline__ void yuv_to_bgr(int y, int u, int v, float (&o)[3]) {
     o[2] = (float)min(max(r, 0), 255);
 }
 
-// grid (ceil(wd / tw), ceil(hd / th), n); dynamic LDS stage_bytes + 12 (tw + th) bytes.  VS as in preprocess_kernel.
-// ROI as in preprocess_kernel; the chroma of a pixel is that of its ABSOLUTE 2 x 2 block of the frame, so a rectangle may start on odd
-// coordinates and have odd sizes.
+// dynamic LDS stage_bytes + Tables::bytes(tw, th).  ROI (with RESIZE): the chroma of a pixel is that of its ABSOLUTE 2 x 2 block of the
+// frame, so a rectangle may start on odd coordinates and have odd sizes.  (A rectangle of the destination's extent needs no copy path
+// here: the converted pixels are bytes, and weight 0 on a finite value interpolates to the same bits.)
 template <bool RESIZE, bool VS, bool ROI>
 __global__ __launch_bounds__(kBlock) void preprocess_yuv_kernel(YuvArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-    const int n = blockIdx.z, tx0 = blockIdx.x * a.tw, ty0 = blockIdx.y * a.th;
-    const int twv = min(a.tw, a.wd - tx0), thv = min(a.th, a.hd - ty0);
-    int hs = a.hs, ws = a.ws, img = n, ox = 0, oy = 0;
-    if (ROI) {
-        const Roi q = roi_of(a.rois, n, a.m, a.hs, a.ws, a.mh, a.mw);
-        if (!q.ok) {
-            fill_nan(a.dst + (size_t)n * 3 * ((size_t)a.hd * a.wd), 3, (size_t)a.hd * a.wd, a.wd, tx0, ty0, twv, thv);
-            return;
-        }
-        hs = q.h; ws = q.w; img = q.id; ox = q.x; oy = q.y;
-    }
-    // (a rectangle of the destination's extent needs no copy path here: the converted pixels are bytes, and weight 0 on a finite value
-    // interpolates to the same bits)
-    auto taps = [&](int d, int S, int D) { return tap<RESIZE>(d, S, D); };
-    int* cx0 = reinterpret_cast<int*>(lds + a.stage_bytes);
-    int* cx1 = cx0 + a.tw;
-    float* cfx = reinterpret_cast<float*>(cx1 + a.tw);
-    int* ry0 = reinterpret_cast<int*>(cfx + a.tw);
-    int* ry1 = ry0 + a.th;
-    float* rfy = reinterpret_cast<float*>(ry1 + a.th);
-    for (int j = threadIdx.x; j < twv; j += kBlock) {
-        const Tap t = taps(tx0 + j, ws, a.wd);
-        cx0[j] = t.i0; cx1[j] = t.i1; cfx[j] = t.f;
-    }
-    for (int j = threadIdx.x; j < thv; j += kBlock) {
-        const Tap t = taps(ty0 + j, hs, a.hd);
-        ry0[j] = t.i0; ry1[j] = t.i1; rfy[j] = t.f;
-    }
-    const int xs0 = taps(tx0, ws, a.wd).i0, xs1 = taps(tx0 + twv - 1, ws, a.wd).i1;
-    const int ys0 = taps(ty0, hs, a.hd).i0, ys1 = taps(ty0 + thv - 1, hs, a.hd).i1;
-    const int rows = ys1 - ys0 + 1, yspan = xs1 - xs0 + 1;
-    const int ps0 = (ox + xs0) >> 1, cr0 = (oy + ys0) >> 1, crows = ((oy + ys1) >> 1) - cr0 + 1;   // first chroma pair and row, chroma rows
+    Tile t;
+    if (!tile_of<ROI>(a, 3, t)) return;
+    const Tables tb = fill_tables(lds, a, t, [](int d, int S, int D) { return tap<RESIZE>(d, S, D); });
+    const int ox = t.ox, oy = t.oy, xs0 = tb.xs0, ys0 = tb.ys0;
+    const int rows = tb.ys1 - ys0 + 1, yspan = tb.xs1 - xs0 + 1;
+    const int ps0 = (ox + xs0) >> 1, cr0 = (oy + ys0) >> 1, crows = ((oy + tb.ys1) >> 1) - cr0 + 1;   // first chroma pair and row, chroma rows
     const int cstep = a.planar ? 1 : 2;                                            // bytes from one U (V) to the next
-    const int cspan = (((ox + xs1) >> 1) - ps0 + 1) * cstep;
+    const int cspan = (((ox + tb.xs1) >> 1) - ps0 + 1) * cstep;
     const int hw = a.ws >> 1;
-    const unsigned char* frame = a.src + (size_t)img * ((size_t)a.hs * a.ws / 2 * 3);
+    const unsigned char* frame = a.src + (size_t)t.img * ((size_t)a.hs * a.ws / 2 * 3);
     const unsigned char* chroma = frame + (size_t)a.hs * a.ws;
     auto y_src = [&](int r) -> const unsigned char* { return frame + (size_t)(oy + ys0 + r) * a.ws + ox + xs0; };
     // chroma span s: NV12 row s of the pairs; I420 row s of U for s < crows, row s - crows of V after them
@@ -329,56 +334,45 @@ __global__ __launch_bounds__(kBlock) void preprocess_yuv_kernel(YuvArgs a) {
         return chroma + ((size_t)p * (a.hs >> 1) + cr0 + s - p * crows) * hw + ps0;
     };
     unsigned char* lds_c = lds + (unsigned)rows * a.yslot;
-    // one 16-byte block k of a span of `span` bytes at g, into its slot at l (byte j of the span lies at l + (g & 15) + j)
-    auto stage = [&](const unsigned char* g, int span, unsigned char* l, unsigned k) {
-        const int lo = 16 * (int)k - (int)((uintptr_t)g & 15);
-        const unsigned char* b = g + lo;
-        l += 16 * k;
-        if (lo >= 0 && lo + 16 <= span) {
-            *reinterpret_cast<u4v*>(l) = *reinterpret_cast<const u4v*>(b);
-        } else {
-            for (int t = lo < 0 ? -lo : 0; t < 16 && lo + t < span; ++t) l[t] = b[t];
-        }
-    };
     const unsigned ybps = (unsigned)yspan / 16 + 2, cbps = (unsigned)cspan / 16 + 2;
     const unsigned yblk = (unsigned)rows * ybps, cblk = (unsigned)(crows * (a.planar ? 2 : 1)) * cbps;
     for (unsigned i = threadIdx.x; i < yblk + cblk; i += kBlock) {
         if (i < yblk) {
             const unsigned s = i / ybps;
-            stage(y_src((int)s), yspan, lds + s * a.yslot, i - s * ybps);
+            stage_block(y_src((int)s), yspan, lds + s * a.yslot, i - s * ybps);
         } else {
             const unsigned s = (i - yblk) / cbps;
-            stage(c_src((int)s), cspan, lds_c + s * a.cslot, i - yblk - s * cbps);
+            stage_block(c_src((int)s), cspan, lds_c + s * a.cslot, i - yblk - s * cbps);
         }
     }
     __syncthreads();
 
-    const int nq = (twv + 3) >> 2;
+    const int nq = (t.twv + 3) >> 2;
     const size_t plane_out = (size_t)a.hd * a.wd;
-    float* out_n = a.dst + (size_t)n * 3 * plane_out;
-    for (int i = threadIdx.x; i < thv * nq; i += kBlock) {
+    float* out_n = a.dst + (size_t)t.n * 3 * plane_out;
+    for (int i = threadIdx.x; i < t.thv * nq; i += kBlock) {
         const int r = i / nq, j0 = 4 * (i - r * nq);
-        const float fy = rfy[r], gy = 1.0f - fy;
+        const float fy = tb.rfy[r], gy = 1.0f - fy;
         // the two tapped rows: their Y spans, and the U and V of the chroma rows under them
         const unsigned char *ly[2], *lu[2], *lv[2];
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
-            const int ya = k ? ry1[r] : ry0[r];
+            const int ya = k ? tb.ry1[r] : tb.ry0[r];
             const int yr = ya - ys0, cr = ((oy + ya) >> 1) - cr0;
-            ly[k] = lds + (unsigned)yr * a.yslot + ((uintptr_t)y_src(yr) & 15);
-            lu[k] = lds_c + (unsigned)cr * a.cslot + ((uintptr_t)c_src(cr) & 15);
-            lv[k] = a.planar ? lds_c + (unsigned)(crows + cr) * a.cslot + ((uintptr_t)c_src(crows + cr) & 15) : lu[k] + 1;
+            ly[k] = span_base(lds + (unsigned)yr * a.yslot, y_src(yr));
+            lu[k] = span_base(lds_c + (unsigned)cr * a.cslot, c_src(cr));
+            lv[k] = a.planar ? span_base(lds_c + (unsigned)(crows + cr) * a.cslot, c_src(crows + cr)) : lu[k] + 1;
         }
         float v[3][4];
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-            const int j = j0 + u < twv ? j0 + u : j0;         // (a pixel past the tile computes column j0 again and is not stored)
-            const int xa = cx0[j], xb = cx1[j];
+            const int j = j0 + u < t.twv ? j0 + u : j0;       // (a pixel past the tile computes column j0 again and is not stored)
+            const int xa = tb.cx0[j], xb = tb.cx1[j];
             const int pa = (((ox + xa) >> 1) - ps0) * cstep, pb = (((ox + xb) >> 1) - ps0) * cstep;
             float p00[3];
             yuv_to_bgr(ly[0][xa - xs0], lu[0][pa], lv[0][pa], p00);
             if (RESIZE) {
-                const float fx = cfx[j], gx = 1.0f - fx;
+                const float fx = tb.cfx[j], gx = 1.0f - fx;
                 float p01[3], p10[3], p11[3];
                 yuv_to_bgr(ly[0][xb - xs0], lu[0][pb], lv[0][pb], p01);
                 yuv_to_bgr(ly[1][xa - xs0], lu[1][pa], lv[1][pa], p10);
@@ -394,29 +388,13 @@ __global__ __launch_bounds__(kBlock) void preprocess_yuv_kernel(YuvArgs a) {
                 for (int c = 0; c < 3; ++c) v[c][u] = p00[c];
             }
         }
-        float* o = out_n + (size_t)(ty0 + r) * a.wd + tx0 + j0;
+        float* o = out_n + (size_t)(t.ty0 + r) * a.wd + t.tx0 + j0;
 #pragma unroll
         for (int oc = 0; oc < 3; ++oc, o += plane_out) {
             float w[4];
 #pragma unroll
             for (int u = 0; u < 4; ++u) w[u] = a.reverse ? v[2 - oc][u] : v[oc][u];
-            if (a.mean != nullptr) {
-                const float m = a.mean[oc];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) w[u] = w[u] - m;
-            }
-            if (a.std_scale != nullptr) {
-                const float d = a.std_scale[oc];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) w[u] = w[u] / d;
-            }
-            if (VS && j0 + 3 < twv) {
-                stg4_nt(o, w);
-            } else {
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-                    if (j0 + u < twv) o[u] = w[u];
-            }
+            finish_quad<VS>(a, oc, w, o, j0, t.twv);
         }
     }
 }
@@ -427,105 +405,108 @@ void launch_yuv(const YuvArgs& a, dim3 grid, size_t lds, bool vs, hipStream_t st
     else    hipLaunchKernelGGL((preprocess_yuv_kernel<RESIZE, false, ROI>), grid, dim3(kBlock), lds, st, a);
 }
 
-// The one launcher of preprocess_kernel.  rois == NULL: image b is the whole of source image b (m, roi_h, roi_w are not read).  Else image
-// b is a rectangle of one of m frames; the tiles and LDS slots are sized for the largest rectangle (roi_h, roi_w): extent() is monotone
-// in S, so the budget holds for every image.
-int preprocess_launch(const void* src, float* dst, const int* rois, int n, int m, int c, int src_h, int src_w, int dst_h, int dst_w,
-                      int roi_h, int roi_w, int src_u8, int src_nhwc, int reverse_channels, const float* mean, const float* std_scale) {
+// ---------------------------------------------------------------------------------------------------------------------- launchers
+// Both launchers take rois == NULL: image b is the whole of source image b, with m = n and (roi_h, roi_w) = (src_h, src_w); else image b
+// is a rectangle of one of m frames, and the tiles and LDS slots are sized for the largest rectangle (roi_h, roi_w): extent() is
+// monotone in S, so the budget holds for every image.
+
+// What both launchers check, and the members of `a` that follow from the arguments alone; c: the destination's channels.
+int common_args(TileArgs& a, const void* src, float* dst, const int* rois, int n, int m, int c, int src_h, int src_w, int dst_h, int dst_w,
+                int roi_h, int roi_w, int reverse_channels, const float* mean, const float* std_scale) {
     PVHIP_REQUIRE_INIT();
     PVHIP_CHECK_ARG(src != nullptr && dst != nullptr);
-    PVHIP_CHECK_ARG(n > 0 && n <= 65535 && c > 0 && c <= kMaxChannels && src_h > 0 && src_w > 0 && dst_h > 0 && dst_w > 0);
+    PVHIP_CHECK_ARG(n > 0 && n <= 65535 && c > 0 && src_h > 0 && src_w > 0 && dst_h > 0 && dst_w > 0);
     PVHIP_CHECK_ARG((size_t)src_h * (size_t)src_w * (size_t)c < ((size_t)1 << 31));   // one image's elements index in 32 bits
     PVHIP_CHECK_ARG((size_t)dst_h * (size_t)dst_w * (size_t)c < ((size_t)1 << 31));
-    PVHIP_CHECK_ARG(src_u8 || (uintptr_t)src % 4 == 0);                              // fp32 sources are element-aligned
-    const bool roi = rois != nullptr;
-    if (roi) PVHIP_CHECK_ARG(m >= 1 && roi_h >= 1 && roi_h <= src_h && roi_w >= 1 && roi_w <= src_w);
-    const bool resize = roi || src_h != dst_h || src_w != dst_w;
-    if (!resize && !reverse_channels && mean == nullptr && std_scale == nullptr)      // the format alone: the same bits as the
-        return pvhip_input_to_nchw_f32(src, dst, n, c, dst_h, dst_w, src_u8, src_nhwc);   // path without preprocessing
-    const int tap_h = roi ? roi_h : src_h, tap_w = roi ? roi_w : src_w;               // the largest extent the taps of an image see
-    const size_t es = src_u8 ? 1 : 4;
-    const size_t cs = src_nhwc ? (size_t)c : 1, planes = src_nhwc ? 1 : (size_t)c;
-    // source rows (columns) a tile of t destination rows (columns) reads at most: the taps advance by S/D per step
-    auto extent = [&](int t, int S, int D) -> size_t {
-        if (!resize) return (size_t)t;
-        const size_t e = ((size_t)(t - 1) * (size_t)S + (size_t)D - 1) / (size_t)D + 2;
-        return e < (size_t)S ? e : (size_t)S;
-    };
-    auto slot_of = [&](int tw) { return (extent(tw, tap_w, dst_w) * cs * es + 30) / 16 * 16; };
-    auto stage_of = [&](int tw, int th) { return planes * extent(th, tap_h, dst_h) * slot_of(tw); };
-    auto lds_of = [&](int tw, int th) { return stage_of(tw, th) + 12 * ((size_t)tw + (size_t)th); };
-    int tw = dst_w;                        // whole rows, unless one row's sources do not fit
+    PVHIP_CHECK_ARG(m >= 1 && roi_h >= 1 && roi_h <= src_h && roi_w >= 1 && roi_w <= src_w);
+    a.src = (const unsigned char*)src; a.dst = dst; a.mean = mean; a.std_scale = std_scale;
+    a.hs = src_h; a.ws = src_w; a.hd = dst_h; a.wd = dst_w; a.reverse = reverse_channels ? 1 : 0;
+    a.rois = rois; a.m = m; a.mh = roi_h; a.mw = roi_w;
+    return PVHIP_OK;
+}
+
+// Source rows (columns) a tile of t destination rows (columns) reads at most, of S onto D: the taps advance by S/D per step.
+size_t extent(bool resize, int t, int S, int D) {
+    if (!resize) return (size_t)t;
+    const size_t e = ((size_t)(t - 1) * (size_t)S + (size_t)D - 1) / (size_t)D + 2;
+    return e < (size_t)S ? e : (size_t)S;
+}
+
+struct TilePlan {
+    dim3 grid;
+    size_t lds;
+    bool vs;
+};
+
+// The tiles of a launch of n images: a.tw, a.th, a.stage_bytes and the launch's grid, LDS bytes and store form.  stage_of(tw, th): the
+// bytes a tile of that size stages; with its coordinate tables it has to fit the budget.
+template <class StageOf>
+int plan_tiles(TileArgs& a, int n, StageOf stage_of, TilePlan& p) {
+    auto lds_of = [&](int tw, int th) { return stage_of(tw, th) + Tables::bytes(tw, th); };
+    int tw = a.wd;                         // whole rows, unless one row's sources do not fit
     while (tw > 1 && lds_of(tw, 1) > kStageBudget) tw = tw > 4 ? (((tw + 1) / 2 + 3) & ~3) : tw - 1;
     int th = 2 * kBlock / ((tw + 3) / 4);  // about two quads per lane
-    th = th < 1 ? 1 : (th > dst_h ? dst_h : th);
+    th = th < 1 ? 1 : (th > a.hd ? a.hd : th);
     while (th > 1 && lds_of(tw, th) > kStageBudget) th = (th + 1) / 2;
     PVHIP_CHECK_ARG(lds_of(tw, th) <= kStageBudget);
-    const dim3 grid((unsigned)((dst_w + tw - 1) / tw), (unsigned)((dst_h + th - 1) / th), (unsigned)n);
-    PVHIP_CHECK_ARG(grid.y <= 65535);
+    p.grid = dim3((unsigned)((a.wd + tw - 1) / tw), (unsigned)((a.hd + th - 1) / th), (unsigned)n);
+    PVHIP_CHECK_ARG(p.grid.y <= 65535);
+    p.lds = lds_of(tw, th);
+    p.vs = (uintptr_t)a.dst % 16 == 0 && a.wd % 4 == 0 && tw % 4 == 0;
+    a.tw = tw; a.th = th; a.stage_bytes = (unsigned)stage_of(tw, th);
+    return PVHIP_OK;
+}
+
+// The one launcher of preprocess_kernel.
+int preprocess_launch(const void* src, float* dst, const int* rois, int n, int m, int c, int src_h, int src_w, int dst_h, int dst_w,
+                      int roi_h, int roi_w, int src_u8, int src_nhwc, int reverse_channels, const float* mean, const float* std_scale) {
     PrepArgs a;
-    a.src = (const unsigned char*)src; a.dst = dst; a.mean = mean; a.std_scale = std_scale;
-    a.c = c; a.hs = src_h; a.ws = src_w; a.hd = dst_h; a.wd = dst_w; a.tw = tw; a.th = th;
-    a.nhwc = src_nhwc ? 1 : 0; a.reverse = reverse_channels ? 1 : 0;
-    a.slot = (unsigned)slot_of(tw); a.stage_bytes = (unsigned)stage_of(tw, th);
-    a.rois = rois; a.m = m; a.mh = roi_h; a.mw = roi_w;
-    const bool vs = (uintptr_t)dst % 16 == 0 && dst_w % 4 == 0 && tw % 4 == 0;
-    const size_t lds = lds_of(tw, th);
+    int rc = common_args(a, src, dst, rois, n, m, c, src_h, src_w, dst_h, dst_w, roi_h, roi_w, reverse_channels, mean, std_scale);
+    if (rc != PVHIP_OK) return rc;
+    PVHIP_CHECK_ARG(c <= kMaxChannels);
+    PVHIP_CHECK_ARG(src_u8 || (uintptr_t)src % 4 == 0);                              // fp32 sources are element-aligned
+    const bool roi = rois != nullptr, resize = roi || src_h != dst_h || src_w != dst_w;
+    if (!resize && !reverse_channels && mean == nullptr && std_scale == nullptr)      // the format alone: the same bits as the
+        return pvhip_input_to_nchw_f32(src, dst, n, c, dst_h, dst_w, src_u8, src_nhwc);   // path without preprocessing
+    const size_t es = src_u8 ? 1 : 4;
+    const size_t cs = src_nhwc ? (size_t)c : 1, planes = src_nhwc ? 1 : (size_t)c;
+    auto slot_of = [&](int tw) { return (extent(resize, tw, roi_w, dst_w) * cs * es + 30) / 16 * 16; };
+    TilePlan p;
+    rc = plan_tiles(a, n, [&](int tw, int th) { return planes * extent(resize, th, roi_h, dst_h) * slot_of(tw); }, p);
+    if (rc != PVHIP_OK) return rc;
+    a.c = c; a.nhwc = src_nhwc ? 1 : 0; a.slot = (unsigned)slot_of(a.tw);
     hipStream_t st = state().stream;
-    if (roi)         src_u8 ? launch<true, true, true>(a, grid, lds, vs, st) : launch<false, true, true>(a, grid, lds, vs, st);
-    else if (src_u8) resize ? launch<true, true, false>(a, grid, lds, vs, st) : launch<true, false, false>(a, grid, lds, vs, st);
-    else             resize ? launch<false, true, false>(a, grid, lds, vs, st) : launch<false, false, false>(a, grid, lds, vs, st);
+    if (roi)         src_u8 ? launch<true, true, true>(a, p.grid, p.lds, p.vs, st) : launch<false, true, true>(a, p.grid, p.lds, p.vs, st);
+    else if (src_u8) resize ? launch<true, true, false>(a, p.grid, p.lds, p.vs, st) : launch<true, false, false>(a, p.grid, p.lds, p.vs, st);
+    else             resize ? launch<false, true, false>(a, p.grid, p.lds, p.vs, st) : launch<false, false, false>(a, p.grid, p.lds, p.vs, st);
     PVHIP_LAUNCH_CHECK();
     return PVHIP_OK;
 }
 
-// The one launcher of preprocess_yuv_kernel; rois, m, roi_h, roi_w as above.
+// The one launcher of preprocess_yuv_kernel.
 int preprocess_yuv_launch(const void* src, float* dst, const int* rois, int n, int m, int src_h, int src_w, int dst_h, int dst_w,
                           int roi_h, int roi_w, int planar, int reverse_channels, const float* mean, const float* std_scale) {
-    PVHIP_REQUIRE_INIT();
-    PVHIP_CHECK_ARG(src != nullptr && dst != nullptr);
-    PVHIP_CHECK_ARG(n > 0 && n <= 65535 && src_h > 0 && src_w > 0 && dst_h > 0 && dst_w > 0);
+    YuvArgs a;
+    int rc = common_args(a, src, dst, rois, n, m, 3, src_h, src_w, dst_h, dst_w, roi_h, roi_w, reverse_channels, mean, std_scale);
+    if (rc != PVHIP_OK) return rc;
     PVHIP_CHECK_ARG(src_h % 2 == 0 && src_w % 2 == 0);                               // 4:2:0: one (U, V) per 2 x 2 block
     PVHIP_CHECK_ARG(planar == 0 || planar == 1);
-    PVHIP_CHECK_ARG((size_t)src_h * (size_t)src_w * 3 < ((size_t)1 << 31));           // one image's elements index in 32 bits
-    PVHIP_CHECK_ARG((size_t)dst_h * (size_t)dst_w * 3 < ((size_t)1 << 31));
-    const bool roi = rois != nullptr;
-    if (roi) PVHIP_CHECK_ARG(m >= 1 && roi_h >= 1 && roi_h <= src_h && roi_w >= 1 && roi_w <= src_w);
-    const bool resize = roi || src_h != dst_h || src_w != dst_w;
-    const int tap_h = roi ? roi_h : src_h, tap_w = roi ? roi_w : src_w;
-    auto extent = [&](int t, int S, int D) -> size_t {                                // as above
-        if (!resize) return (size_t)t;
-        const size_t e = ((size_t)(t - 1) * (size_t)S + (size_t)D - 1) / (size_t)D + 2;
-        return e < (size_t)S ? e : (size_t)S;
-    };
+    const bool roi = rois != nullptr, resize = roi || src_h != dst_h || src_w != dst_w;
     // e consecutive rows (columns) lie over at most e / 2 + 1 chroma rows (pairs): the first may be an odd one
     auto halves = [](size_t e, int S) { return e / 2 + 1 < (size_t)S / 2 ? e / 2 + 1 : (size_t)S / 2; };
-    auto yslot_of = [&](int tw) { return (extent(tw, tap_w, dst_w) + 30) / 16 * 16; };
-    auto cslot_of = [&](int tw) { return (halves(extent(tw, tap_w, dst_w), src_w) * (planar ? 1 : 2) + 30) / 16 * 16; };
+    auto yslot_of = [&](int tw) { return (extent(resize, tw, roi_w, dst_w) + 30) / 16 * 16; };
+    auto cslot_of = [&](int tw) { return (halves(extent(resize, tw, roi_w, dst_w), src_w) * (planar ? 1 : 2) + 30) / 16 * 16; };
     auto stage_of = [&](int tw, int th) {
-        const size_t e = extent(th, tap_h, dst_h);
+        const size_t e = extent(resize, th, roi_h, dst_h);
         return e * yslot_of(tw) + halves(e, src_h) * (planar ? 2 : 1) * cslot_of(tw);
     };
-    auto lds_of = [&](int tw, int th) { return stage_of(tw, th) + 12 * ((size_t)tw + (size_t)th); };
-    int tw = dst_w;                        // whole rows, unless one row's sources do not fit
-    while (tw > 1 && lds_of(tw, 1) > kStageBudget) tw = tw > 4 ? (((tw + 1) / 2 + 3) & ~3) : tw - 1;
-    int th = 2 * kBlock / ((tw + 3) / 4);  // about two quads per lane
-    th = th < 1 ? 1 : (th > dst_h ? dst_h : th);
-    while (th > 1 && lds_of(tw, th) > kStageBudget) th = (th + 1) / 2;
-    PVHIP_CHECK_ARG(lds_of(tw, th) <= kStageBudget);
-    const dim3 grid((unsigned)((dst_w + tw - 1) / tw), (unsigned)((dst_h + th - 1) / th), (unsigned)n);
-    PVHIP_CHECK_ARG(grid.y <= 65535);
-    YuvArgs a;
-    a.src = (const unsigned char*)src; a.dst = dst; a.mean = mean; a.std_scale = std_scale;
-    a.hs = src_h; a.ws = src_w; a.hd = dst_h; a.wd = dst_w; a.tw = tw; a.th = th;
-    a.planar = planar; a.reverse = reverse_channels ? 1 : 0;
-    a.yslot = (unsigned)yslot_of(tw); a.cslot = (unsigned)cslot_of(tw); a.stage_bytes = (unsigned)stage_of(tw, th);
-    a.rois = rois; a.m = m; a.mh = roi_h; a.mw = roi_w;
-    const bool vs = (uintptr_t)dst % 16 == 0 && dst_w % 4 == 0 && tw % 4 == 0;
-    const size_t lds = lds_of(tw, th);
+    TilePlan p;
+    rc = plan_tiles(a, n, stage_of, p);
+    if (rc != PVHIP_OK) return rc;
+    a.planar = planar; a.yslot = (unsigned)yslot_of(a.tw); a.cslot = (unsigned)cslot_of(a.tw);
     hipStream_t st = state().stream;
-    if (roi) launch_yuv<true, true>(a, grid, lds, vs, st);
-    else     resize ? launch_yuv<true, false>(a, grid, lds, vs, st) : launch_yuv<false, false>(a, grid, lds, vs, st);
+    if (roi) launch_yuv<true, true>(a, p.grid, p.lds, p.vs, st);
+    else     resize ? launch_yuv<true, false>(a, p.grid, p.lds, p.vs, st) : launch_yuv<false, false>(a, p.grid, p.lds, p.vs, st);
     PVHIP_LAUNCH_CHECK();
     return PVHIP_OK;
 }

@@ -114,63 +114,75 @@ class HostInputs:
             np.copyto(rois_host, table)
         return staged, largest
 
+    def _find_or_copy(self, name, fmt, arr):
+        """The staging host array `arr` is fed through: the one whose page-locked buffer `arr` is, else -- for a declared format -- the
+        one of its extent with `arr` copied into it; None: the input goes the default way."""
+        slot = self.slots.get(name)
+        if slot is not None and isinstance(arr, np.ndarray):
+            # (the frames buffer of a RoiInput is none of them: handed in without its table it is an array like any other)
+            for s in slot.extents.values():
+                if s.frames is None and arr.shape == s.host.shape and arr.dtype == s.host.dtype and arr.ctypes.data == s.host.ctypes.data:
+                    return s
+        if not fmt.declared:
+            return None
+        a = np.asarray(arr)
+        staged = self._staging(name, fmt.extent_of(a))
+        np.copyto(staged.host, a, casting='same_kind' if staged.host.dtype == np.float32 else 'safe')
+        return staged
+
+    @staticmethod
+    def _convert(fmt, slot, staged, largest):
+        """The one launch that makes `slot.fixed` of what `staged` uploaded (none for FP32 NCHW at the network's extent):
+        pvhip_input_preprocess_yuv_f32 for NV12 / I420 frames, pvhip_input_preprocess_f32 when a resize, channel reversal or mean /
+        scale is in effect, else pvhip_input_to_nchw_f32; `largest` = (max_h, max_w) of a RoiInput's table: the _roi_f32 forms."""
+        fixed = slot.fixed
+        src, dst = device.ptr(staged.staging), device.ptr(fixed)
+        n, c, dst_hw = fixed.shape[0], fixed.shape[1], fixed.shape[2:]
+        how = (int(fmt.color == 'I420'),) if fmt.yuv else (int(fmt.u8), int(fmt.nhwc))
+        pre = (int(fmt.reverse), device.ptr(slot.mean), device.ptr(slot.std))
+        if largest is not None:
+            where = (src, dst, device.ptr(slot.rois), n, staged.frames)
+            if fmt.yuv:
+                device.call('pvhip_input_preprocess_yuv_roi_f32', *where, *staged.extent, *dst_hw, *largest, *how, *pre)
+            else:
+                device.call('pvhip_input_preprocess_roi_f32', *where, c, *staged.extent, *dst_hw, *largest, *how, *pre)
+        elif fmt.yuv:
+            device.call('pvhip_input_preprocess_yuv_f32', src, dst, n, *staged.extent, *dst_hw, *how, *pre)
+        elif staged.preprocess:
+            device.call('pvhip_input_preprocess_f32', src, dst, n, c, *staged.extent, *dst_hw, *how, *pre)
+        elif staged.staging is not fixed:
+            device.call('pvhip_input_to_nchw_f32', src, dst, *fixed.shape, *how)
+
     def stage(self, inputs: dict, stream_base: int) -> dict:
         """`inputs` with every host input of a declared format, or in one of this request's own buffers, replaced by the request's fixed
         tensor: the caller's array is copied into the page-locked buffer of its extent unless it IS that buffer, the buffer is uploaded on
-        the copy stream, stream `stream_base` waits for the copy's event and converts (one launch; none for FP32 NCHW at the network's
-        extent): pvhip_input_preprocess_yuv_f32 for NV12 / I420 frames, pvhip_input_preprocess_f32 when a resize, channel reversal or
-        mean / scale is in effect, else pvhip_input_to_nchw_f32.  A RoiInput's frames and table go the same way -- both uploaded on the
-        copy stream behind the one event -- and pvhip_input_preprocess_roi_f32 / _yuv_roi_f32 writes the fixed tensor.
+        the copy stream, stream `stream_base` waits for the copy's event and converts (_convert: one launch at the most).  A RoiInput's
+        frames and table go the same way, both uploaded on the copy stream behind the one event.
         Every other input is returned unchanged (and goes the default way).  All but the MAX_SOURCE_EXTENTS most recently fed extents
         of an input are released here: the request has no pass in flight, so nothing reads those buffers any more."""
         out = dict(inputs)
         for name, arr in inputs.items():
-            fmt = self.formats.get(name)
-            roi = isinstance(arr, RoiInput)
-            if roi:
+            fmt, largest = self.formats.get(name), None
+            if isinstance(arr, RoiInput):
                 staged, largest = self._stage_rois(name, self._format(name), arr)
-            if fmt is None or isinstance(arr, (device.DeviceTensor, device.ChannelSlice, device.BlockedHalf)):
+            elif fmt is None or isinstance(arr, (device.DeviceTensor, device.ChannelSlice, device.BlockedHalf)):
                 continue
-            slot = self.slots.get(name)
-            staged = staged if roi else None
-            if slot is not None and isinstance(arr, np.ndarray):
-                # (the frames buffer of a RoiInput is none of them: handed in without its table it is an array like any other)
-                staged = next((s for s in slot.extents.values() if s.frames is None and arr.shape == s.host.shape
-                               and arr.dtype == s.host.dtype and arr.ctypes.data == s.host.ctypes.data), None)
-            if staged is None:
-                if not fmt.declared:
+            else:
+                staged = self._find_or_copy(name, fmt, arr)
+                if staged is None:
                     continue
-                a = np.asarray(arr)
-                staged = self._staging(name, fmt.extent_of(a))
-                np.copyto(staged.host, a, casting='same_kind' if staged.host.dtype == np.float32 else 'safe')
             slot = self.slots[name]
             slot.extents.move_to_end(staged.key)
             while len(slot.extents) > self.MAX_SOURCE_EXTENTS:
                 slot.extents.popitem(last=False)
-            host, fixed = staged.host, slot.fixed
             device.select_stream(device.COPY_STREAM)
-            device.call('pvhip_memcpy_h2d_async', device.ptr(staged.staging), ctypes.c_void_p(host.ctypes.data), host.nbytes)
-            if roi:
+            device.call('pvhip_memcpy_h2d_async', device.ptr(staged.staging), ctypes.c_void_p(staged.host.ctypes.data), staged.host.nbytes)
+            if largest is not None:
                 device.call('pvhip_memcpy_h2d_async', device.ptr(slot.rois), ctypes.c_void_p(slot.rois_host.ctypes.data), slot.rois_host.nbytes)
             slot.event.record()
             device.select_stream(stream_base)
             slot.event.wait()
-            if roi:
-                where = (device.ptr(staged.staging), device.ptr(fixed), device.ptr(slot.rois), fixed.shape[0], staged.frames)
-                if fmt.yuv:
-                    device.call('pvhip_input_preprocess_yuv_roi_f32', *where, *staged.extent, *fixed.shape[2:], *largest,
-                                int(fmt.color == 'I420'), int(fmt.reverse), device.ptr(slot.mean), device.ptr(slot.std))
-                else:
-                    device.call('pvhip_input_preprocess_roi_f32', *where, fixed.shape[1], *staged.extent, *fixed.shape[2:], *largest,
-                                int(fmt.u8), int(fmt.nhwc), int(fmt.reverse), device.ptr(slot.mean), device.ptr(slot.std))
-            elif fmt.yuv:
-                device.call('pvhip_input_preprocess_yuv_f32', device.ptr(staged.staging), device.ptr(fixed), fixed.shape[0], *staged.extent,
-                            *fixed.shape[2:], int(fmt.color == 'I420'), int(fmt.reverse), device.ptr(slot.mean), device.ptr(slot.std))
-            elif staged.preprocess:
-                device.call('pvhip_input_preprocess_f32', device.ptr(staged.staging), device.ptr(fixed), *fixed.shape[:2], *staged.extent,
-                            *fixed.shape[2:], int(fmt.u8), int(fmt.nhwc), int(fmt.reverse), device.ptr(slot.mean), device.ptr(slot.std))
-            elif staged.staging is not fixed:
-                device.call('pvhip_input_to_nchw_f32', device.ptr(staged.staging), device.ptr(fixed), *fixed.shape, int(fmt.u8), int(fmt.nhwc))
+            self._convert(fmt, slot, staged, largest)
             device.select_stream(0)
-            out[name] = fixed
+            out[name] = slot.fixed
         return out

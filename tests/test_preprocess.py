@@ -299,6 +299,31 @@ def test_preprocess_kernel_bit_exact_in_column_tiles(hip, src_hw, dst_hw, dtype)
             assert_bit_exact(_device_preprocess(hip, src, dst_hw, nhwc, shift=shift, **opt), want, what + ', unaligned source')
 
 
+# Shapes whose tiles are narrower than a quad: fp32, C = 1024, one output row of 8 columns.  The planner halves the tile width to a
+# multiple of 4 while it exceeds 4 and then narrows it by one column at a time, until the sources of one output row of the tile fit
+# 48 KiB less the 12 (tw + 1) table bytes; a tile of tw columns reads e(tw) = min((tw - 1) S / 8 (rounded up) + 2, S) source columns.
+#   NHWC, S = 32: one span of e x 4096 bytes (+ 30, rounded down to 16): e(8) = 30, e(4) = 14 (57 KB), e(3) = 10 (40 KB): tw = 3
+#   NHWC, S = 64: e(3) = 18 (74 KB), e(2) = 10 (40 KB): tw = 2
+#   NCHW, S = 64: 1024 spans of (4 e + 30) / 16 * 16 bytes: e(4) = 26 (128 KB), e(3) = 18 (96 KB), e(2) = 10 (64 KB), e(1) = 2 (32 KB): tw = 1
+# With tw < 4 the stores are scalar, and every tile but the first starts at tx0 > 0.
+NARROW_SHAPES = [(True, (1, 32), (1, 8)), (True, (1, 64), (1, 8)), (False, (1, 64), (1, 8))]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('nhwc,src_hw,dst_hw', NARROW_SHAPES)
+def test_preprocess_kernel_bit_exact_in_tiles_narrower_than_a_quad(hip, nhwc, src_hw, dst_hw):
+    rng = np.random.default_rng(src_hw[1] + nhwc)
+    c = 1024
+    mean = rng.uniform(0, 255, c).astype(np.float32)
+    std = rng.uniform(0.5, 80, c).astype(np.float32)
+    x = _f32_values(rng, (1,) + src_hw + (c,))
+    src = x if nhwc else np.ascontiguousarray(x.transpose(0, 3, 1, 2))
+    want = preprocess(src, dst_hw, nhwc=nhwc, reverse_channels=True, mean=mean, std_scale=std)
+    what = 'fp32 {} {} -> {} c={}'.format('nhwc' if nhwc else 'nchw', src_hw, dst_hw, c)
+    assert_bit_exact(_device_preprocess(hip, src, dst_hw, nhwc, reverse=True, mean=mean, std=std), want, what)
+    assert_bit_exact(_device_preprocess(hip, src, dst_hw, nhwc, reverse=True, mean=mean, std=std, shift=4), want, what + ', unaligned source')
+
+
 @pytest.mark.gpu
 def test_release_device_state_frees_the_input_staging_at_once(hip):
     """The staging of every source extent (page-locked buffer, device tensor) goes back when the request's device state is released, by
