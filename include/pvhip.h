@@ -427,6 +427,20 @@ int pvhip_detection_output_f32(const float* loc, const float* conf, const float*
                                int num_priors, int num_classes, int records_per_image, float confidence_threshold,
                                float nms_threshold, int code_type_center_size, int variance_encoded_in_target,
                                int clip_before_nms, int clip_after_nms);
+/* Addition to ABI v17 (the version number is unchanged: nothing existing changed): the records above become the (id, x, y, w, h) table
+ * of the ROI preprocessing entries below, on the device, so that a cascade never reads them on the host.  `records`: images *
+ * records_per_image rows of 7 floats, image b being rows [b P, (b + 1) P).  An image's list ends at its first row whose column 0 is not
+ * >= 0 (the terminator above; NaN too).  A live row is selected when score >= min_confidence, its four corners are finite and
+ * (labels == NULL or) its label equals (float)labels[j] for some j < num_labels <= 64.  Its rectangle over a frame of (frame_h, frame_w):
+ * x0 = floor(min(max(xmin * frame_w, 0), frame_w)), x1 = ceil(min(max(xmax * frame_w, 0), frame_w)) in fp32, never contracted, y0 / y1
+ * alike with frame_h; it is dropped when x1 - x0 < min_w or y1 - y0 < min_h.  Survivors keep the order (image, position): survivor
+ * k < n becomes rois[k] = (b, x0, y0, w, h) with record_of[k] = b P + p; rows k >= count = min(selected, n) are (-1, 0, 0, 0, 0) -- which
+ * the ROI entries write as quiet NaN -- with record_of[k] = -1; counts[0] = count, counts[1] = selected (every survivor, which may
+ * exceed n).  The same rule in numpy: tests/detected_rois_ref.py, matched integer for integer.  One workgroup on the current stream,
+ * no allocation.  n, images, records_per_image, min_h, min_w >= 1, images * records_per_image < 2^31 / 7, frame_h, frame_w in [1, 2^24],
+ * `labels` NULL (any label; num_labels == 0) or a device pointer; else PVHIP_EINVAL. */
+int pvhip_detections_to_rois(const float* records, int* rois, int* record_of, int* counts, int n, int images, int records_per_image,
+                             int frame_h, int frame_w, float min_confidence, const int* labels, int num_labels, int min_h, int min_w);
 
 /* ---------------------------------------------------------------- multi-GPU gather ---------- */
 /* No reference counterpart (the reference is single-process).  Batch shards are independent; the only

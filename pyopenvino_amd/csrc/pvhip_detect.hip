@@ -230,9 +230,120 @@ __global__ __launch_bounds__(kDetBlock) void detect_records_kernel(DetArgs a) {
     if (tid == 0 && K < a.records) out[(size_t)K * 7] = -1.0f;
 }
 
+// ---- records -> the (id, x, y, w, h) table of the ROI preprocessing kernels (pvhip_preprocess.hip), for a cascade that never reads the
+// records on the host.  One workgroup (a latency kernel: 10^4 records); include/pvhip.h states the rule, tests/detected_rois_ref.py is
+// the same in numpy.  Images are taken in blocks of kRoiImages:
+//   1. ends[i] = position of the image's first record whose column 0 is not >= 0 (LDS atomicMin over its positions), else P;
+//   2. the block's records in chunks of kDetBlock, one per lane: the lane evaluates its record, the wave's ballot ranks it among its
+//      wave's survivors, the per-wave totals in LDS rank the wave within the chunk, and a running base ranks the chunk: a stable
+//      compaction whose result does not depend on timing.
+// Then rows count.. of the table are filled and the counts written.
+struct RoiArgs {
+    const float* rec;      // [N * P][7]
+    int*         rois;     // [n][5]
+    int*         rec_of;   // [n]
+    int*         counts;   // [2]: min(selected, n), selected
+    const int*   labels;   // [num_labels], or NULL: any label
+    int   n, N, P, H, W, num_labels, min_h, min_w;
+    float conf;
+};
+
+constexpr int kRoiImages = 4096;  // list ends held in LDS at once
+constexpr int kRoiLabels = 64;
+
+__global__ __launch_bounds__(kDetBlock) void detections_to_rois_kernel(RoiArgs a) {
+    __shared__ int   ends[kRoiImages];
+    __shared__ int   wave_total[2][kDetBlock / 64];
+    __shared__ float labels[kRoiLabels];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int P = a.P;
+    if (a.labels != nullptr && tid < a.num_labels) labels[tid] = (float)a.labels[tid];
+    const float fw = (float)a.W, fh = (float)a.H;
+    int base = 0, flip = 0;                                   // survivors so far (the same value in every lane)
+    for (int b0 = 0; b0 < a.N; b0 += kRoiImages) {
+        const int nb = min(kRoiImages, a.N - b0);
+        const int r0 = b0 * P, r1 = r0 + nb * P;              // (N * P < 2^31 / 7: the launcher checks)
+        for (int i = tid; i < nb; i += kDetBlock) ends[i] = P;
+        __syncthreads();
+        for (int r = r0 + tid; r < r1; r += kDetBlock) {
+            if (!(a.rec[(size_t)r * 7] >= 0.0f)) {
+                const int b = r / P;
+                atomicMin(&ends[b - b0], r - b * P);
+            }
+        }
+        __syncthreads();
+        for (int c0 = r0; c0 < r1; c0 += kDetBlock, flip ^= 1) {
+            const int r = c0 + tid;
+            bool keep = false;
+            int b = 0, x0 = 0, y0 = 0, w = 0, h = 0;
+            if (r < r1) {
+                b = r / P;
+                const float* q = a.rec + (size_t)r * 7;
+                const float label = q[1], score = q[2], xa = q[3], ya = q[4], xb = q[5], yb = q[6];
+                keep = r - b * P < ends[b - b0] && score >= a.conf && isfinite(xa) && isfinite(ya) && isfinite(xb) && isfinite(yb);
+                if (keep && a.labels != nullptr) {
+                    bool listed = false;
+                    for (int j = 0; j < a.num_labels; ++j) listed = listed || label == labels[j];
+                    keep = listed;
+                }
+                if (keep) {
+                    x0 = (int)floorf(fminf(fmaxf(xa * fw, 0.0f), fw));
+                    y0 = (int)floorf(fminf(fmaxf(ya * fh, 0.0f), fh));
+                    w  = (int)ceilf(fminf(fmaxf(xb * fw, 0.0f), fw)) - x0;
+                    h  = (int)ceilf(fminf(fmaxf(yb * fh, 0.0f), fh)) - y0;
+                    keep = w >= a.min_w && h >= a.min_h;
+                }
+            }
+            const unsigned long long votes = __ballot(keep);
+            const int rank = __builtin_amdgcn_mbcnt_hi((unsigned)(votes >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)votes, 0u));
+            if (lane == 0) wave_total[flip][wave] = __popcll(votes);
+            __syncthreads();                                  // (the other half of wave_total is the previous chunk's: one barrier per chunk)
+            int before = 0, total = 0;
+#pragma unroll
+            for (int v = 0; v < kDetBlock / 64; ++v) {
+                const int t = wave_total[flip][v];
+                before += v < wave ? t : 0;
+                total += t;
+            }
+            const long long k = (long long)base + before + rank;
+            if (keep && k < a.n) {
+                int* o = a.rois + 5 * (size_t)k;
+                o[0] = b; o[1] = x0; o[2] = y0; o[3] = w; o[4] = h;
+                a.rec_of[k] = r;
+            }
+            base += total;
+        }
+        __syncthreads();                                      // ends[] is rewritten for the next block of images
+    }
+    const int count = min(base, a.n);
+    for (int k = count + tid; k < a.n; k += kDetBlock) {
+        int* o = a.rois + 5 * (size_t)k;
+        o[0] = -1; o[1] = 0; o[2] = 0; o[3] = 0; o[4] = 0;
+        a.rec_of[k] = -1;
+    }
+    if (tid == 0) { a.counts[0] = count; a.counts[1] = base; }
+}
+
 }  // namespace
 
 extern "C" {
+
+int pvhip_detections_to_rois(const float* records, int* rois, int* record_of, int* counts, int n, int images, int records_per_image,
+                             int frame_h, int frame_w, float min_confidence, const int* labels, int num_labels, int min_h, int min_w) {
+    PVHIP_REQUIRE_INIT();
+    PVHIP_CHECK_ARG(records != nullptr && rois != nullptr && record_of != nullptr && counts != nullptr);
+    PVHIP_CHECK_ARG(n >= 1 && images >= 1 && records_per_image >= 1 && min_h >= 1 && min_w >= 1);
+    PVHIP_CHECK_ARG((long long)images * records_per_image < ((1LL << 31) / 7));
+    PVHIP_CHECK_ARG(frame_h >= 1 && frame_h <= (1 << 24) && frame_w >= 1 && frame_w <= (1 << 24));   // exact as fp32
+    PVHIP_CHECK_ARG(num_labels >= 0 && num_labels <= kRoiLabels && (num_labels == 0 || labels != nullptr));   // (NULL: any label)
+    RoiArgs a;
+    a.rec = records; a.rois = rois; a.rec_of = record_of; a.counts = counts; a.labels = labels;
+    a.n = n; a.N = images; a.P = records_per_image; a.H = frame_h; a.W = frame_w;
+    a.num_labels = num_labels; a.min_h = min_h; a.min_w = min_w; a.conf = min_confidence;
+    hipLaunchKernelGGL(detections_to_rois_kernel, dim3(1), dim3(kDetBlock), 0, state().stream, a);
+    PVHIP_LAUNCH_CHECK();
+    return PVHIP_OK;
+}
 
 int pvhip_detection_output_f32(const float* loc, const float* conf, const float* priors, float* out, int n,
                                int num_priors, int num_classes, int records_per_image, float confidence_threshold,

@@ -7,7 +7,7 @@ import ctypes
 import numpy as np
 
 from . import device
-from .input_format import RoiInput
+from .input_format import DetectedRois, DetectedTable, RoiInput
 
 
 class _Staging:
@@ -32,20 +32,45 @@ class _Slot:
     """What a request keeps for one input whatever the source extent: the fp32 NCHW tensor the pass reads -- the same address on every
     call, so the pass is recorded and replayed like a device-resident one whatever the source size --, the copy's event, mean / scale on
     the device (c floats each, uploaded once per request: load_network needs no device) and {extent: _Staging}, least recently fed first
-    -- a RoiInput's frames under (extent, m) --, and the (n, 5) int32 table of a RoiInput, page-locked and on the device, once one is fed."""
-    __slots__ = ('fixed', 'event', 'mean', 'std', 'extents', 'rois_host', 'rois')
+    -- a RoiInput's frames under (extent, m) --, and the (n, 5) int32 table of a RoiInput, page-locked and on the device, once one is fed.
+    The device table is the head of one block `table` of 6 n + 2 ints, (n, 5) rois | (n,) record_of | (count, selected): what
+    pvhip_detections_to_rois writes for a DetectedRois (`detected`: what that needs besides, once one is fed) and detected_rois() reads
+    back in one copy."""
+    __slots__ = ('fixed', 'event', 'mean', 'std', 'extents', 'rois_host', 'rois', 'table', 'detected')
 
     def __init__(self, fmt):
         self.fixed, self.event = device.DeviceTensor.empty(fmt.dims), device.Event(timed=False)
         self.mean, self.std = (None, None) if fmt.mean is None else (device.DeviceTensor.from_numpy(fmt.mean), device.DeviceTensor.from_numpy(fmt.std))
         self.extents = collections.OrderedDict()
-        self.rois_host = self.rois = None
+        self.rois_host = self.rois = self.table = self.detected = None
 
     def roi_table(self):
         if self.rois_host is None:
-            self.rois_host = device.host_empty((self.fixed.shape[0], 5), np.int32)
-            self.rois = device.DeviceTensor.empty(self.rois_host.shape, np.int32)
+            n = self.fixed.shape[0]
+            self.rois_host = device.host_empty((n, 5), np.int32)
+            self.table = device.DeviceTensor.empty((6 * n + 2,), np.int32)
+            self.rois = device.DeviceTensor(self.table._block, (n, 5), np.int32)
         return self.rois_host
+
+
+class _Detected:
+    """What a slot keeps for DetectedRois inputs: the labels, page-locked and on the device; the records of a host array, page-locked and
+    on the device, for the record count last fed; the event recorded behind the launch that reads a detector's Result (the detector's
+    next pass waits for it); `source`: the device tensor the last launch read, kept alive until the next pass of this input; `live`: the
+    last pass of the input was a DetectedRois."""
+    __slots__ = ('labels_host', 'labels', 'records_host', 'records', 'read', 'source', 'live')
+
+    def __init__(self):
+        self.labels_host = device.host_empty((DetectedRois.MAX_LABELS,), np.int32)
+        self.labels = device.DeviceTensor.empty(self.labels_host.shape, np.int32)
+        self.records_host = self.records = self.source = None
+        self.read, self.live = device.Event(timed=False), False
+
+    def records_for(self, rows):
+        if self.records_host is None or self.records_host.shape[0] != rows:
+            self.records_host = device.host_empty((rows, 7), np.float32)
+            self.records = device.DeviceTensor.empty((rows, 7), np.float32)
+        return self.records_host
 
 
 class HostInputs:
@@ -114,6 +139,89 @@ class HostInputs:
             np.copyto(rois_host, table)
         return staged, largest
 
+    @staticmethod
+    def _detections_of(name, det):
+        """What DetectedRois `det` reads, nothing waited for and nothing copied: (records -- a DeviceTensor or a host array --, the images
+        they belong to by default or None, the runner whose pass produces them and the event behind that pass, or (None, None))."""
+        src = det.detections
+        if not (hasattr(src, 'runner') and hasattr(src, 'start_async')):         # (an InferRequest: inference_engine imports this module)
+            return (src if isinstance(src, device.DeviceTensor) else np.asarray(src)), None, None, None
+        runner = src.runner
+        net = runner.ienet
+        results = net.find_node_by_type('Result')
+        if det.output is not None:
+            results = [r for r in results if r[1] == det.output]
+            if not results:
+                raise ValueError('input {}: the detector has no Result named {!r}'.format(name, det.output))
+        elif len(results) != 1:
+            raise ValueError('input {}: the detector has {} Results: output= names the DetectionOutput one'.format(name, len(results)))
+        nid = results[0][0]
+        if [net.G.nodes[p]['type'] for p in net.G.pred[nid]] != ['DetectionOutput']:
+            raise ValueError('input {}: Result {!r} of the detector is no DetectionOutput'.format(name, results[0][1]))
+        replayed, pending = (src._replayed, runner._pending) if src._in_flight else (None, None)
+        value = replayed['results'][results[0][1]] if replayed is not None else net.G.nodes[nid].get('result')
+        if value is None:
+            raise RuntimeError('input {}: the detector request never ran: start_async() or infer() it first'.format(name))
+        if not isinstance(value, device.DeviceTensor):        # waited for: its host Results, like an array
+            return np.asarray(value), net.batch_size, None, None
+        return value, net.batch_size, runner, (pending[1] if pending is not None else None)
+
+    def _stage_detected(self, name, fmt, det, sharded):
+        """The frames of DetectedRois `det` in this request's page-locked buffers, its records (a host array: in the slot's page-locked
+        buffer) and its options, everything checked before anything is allocated: (staging, [(device tensor, page-locked array)] to
+        upload beside the frames, launch), launch() being what `stage` issues on the base stream in front of the ROI launch."""
+        if sharded:
+            raise NotImplementedError('input {}: DetectedRois with a batch sharded over ranks'.format(name))
+        frames = det.frames if isinstance(det.frames, np.ndarray) else np.asarray(det.frames)
+        extent, m = fmt.frames_extent_of(frames)
+        conf, labels, (min_h, min_w) = det.checked_options(name)
+        records, images, runner, done = self._detections_of(name, det)
+        images = det.images if det.images is not None else (images if images is not None else m)
+        per_image = det.checked_records(name, records.shape, records.dtype, images, m)
+        staged = self._staging(name, extent, m)
+        if not (frames.dtype == staged.host.dtype and frames.flags.c_contiguous and frames.ctypes.data == staged.host.ctypes.data):
+            np.copyto(staged.host, frames, casting='same_kind' if staged.host.dtype == np.float32 else 'safe')
+        slot = self.slots[name]
+        slot.roi_table()
+        if slot.detected is None:
+            slot.detected = _Detected()
+        d = slot.detected
+        uploads = []
+        if labels is not None and len(labels):
+            d.labels_host[:len(labels)] = labels
+            uploads.append((d.labels, d.labels_host))
+        listed = device.ptr(d.labels if labels is not None else None)       # NULL: any label
+        if isinstance(records, device.DeviceTensor):
+            d.source = records
+        else:
+            np.copyto(d.records_for(images * per_image), records.reshape(-1, 7))
+            d.source = d.records
+            uploads.append((d.records, d.records_host))
+        n = slot.fixed.shape[0]
+
+        def launch():
+            if done is not None:
+                done.wait()                                   # the detector's pass, on the device
+            device.call('pvhip_detections_to_rois', device.ptr(d.source), ctypes.c_void_p(slot.table.ptr),
+                        ctypes.c_void_p(slot.table.ptr + 20 * n), ctypes.c_void_p(slot.table.ptr + 24 * n), n, images, per_image, *extent,
+                        conf, listed, 0 if labels is None else len(labels), min_h, min_w)
+            if runner is not None:                            # its next pass may overwrite that Result: not before this launch has read it
+                runner._result_readers.append(d.read.record())
+
+        return staged, uploads, launch
+
+    def detected_rois(self, name, stream_base) -> DetectedTable:
+        """The table the last pass of input `name` used, read back in one copy on stream `stream_base`, which has drained."""
+        self._format(name)
+        slot = self.slots.get(name)
+        if slot is None or slot.detected is None or not slot.detected.live:
+            raise RuntimeError('input {}: its last pass was not fed a DetectedRois'.format(name))
+        n = slot.fixed.shape[0]
+        device.select_stream(stream_base)
+        t = np.asarray(slot.table)
+        device.select_stream(0)
+        return DetectedTable(int(t[6 * n]), int(t[6 * n + 1]), t[:5 * n].reshape(n, 5).copy(), t[5 * n:6 * n].copy())
+
     def _find_or_copy(self, name, fmt, arr):
         """The staging host array `arr` is fed through: the one whose page-locked buffer `arr` is, else -- for a declared format -- the
         one of its extent with `arr` copied into it; None: the input goes the default way."""
@@ -153,18 +261,25 @@ class HostInputs:
         elif staged.staging is not fixed:
             device.call('pvhip_input_to_nchw_f32', src, dst, *fixed.shape, *how)
 
-    def stage(self, inputs: dict, stream_base: int) -> dict:
+    def stage(self, inputs: dict, stream_base: int, sharded: bool = False) -> dict:
         """`inputs` with every host input of a declared format, or in one of this request's own buffers, replaced by the request's fixed
         tensor: the caller's array is copied into the page-locked buffer of its extent unless it IS that buffer, the buffer is uploaded on
         the copy stream, stream `stream_base` waits for the copy's event and converts (_convert: one launch at the most).  A RoiInput's
-        frames and table go the same way, both uploaded on the copy stream behind the one event.
+        frames and table go the same way, both uploaded on the copy stream behind the one event.  A DetectedRois' frames too -- with its
+        labels, and its records when they are a host array --; its table is made by pvhip_detections_to_rois on `stream_base`, behind the
+        detector's pass when the records are the Result of a request in flight, and the ROI launch is sized for whole frames: the host
+        never sees the table (`sharded`: the batch is sharded over ranks, which a DetectedRois refuses).
         Every other input is returned unchanged (and goes the default way).  All but the MAX_SOURCE_EXTENTS most recently fed extents
         of an input are released here: the request has no pass in flight, so nothing reads those buffers any more."""
         out = dict(inputs)
         for name, arr in inputs.items():
-            fmt, largest = self.formats.get(name), None
+            fmt, largest, uploads, make_table = self.formats.get(name), None, (), None
             if isinstance(arr, RoiInput):
                 staged, largest = self._stage_rois(name, self._format(name), arr)
+                uploads = ((self.slots[name].rois, self.slots[name].rois_host),)
+            elif isinstance(arr, DetectedRois):
+                staged, uploads, make_table = self._stage_detected(name, self._format(name), arr, sharded)
+                largest = staged.extent                       # the host does not know the largest rectangle: the frame bounds it
             elif fmt is None or isinstance(arr, (device.DeviceTensor, device.ChannelSlice, device.BlockedHalf)):
                 continue
             else:
@@ -177,11 +292,17 @@ class HostInputs:
                 slot.extents.popitem(last=False)
             device.select_stream(device.COPY_STREAM)
             device.call('pvhip_memcpy_h2d_async', device.ptr(staged.staging), ctypes.c_void_p(staged.host.ctypes.data), staged.host.nbytes)
-            if largest is not None:
-                device.call('pvhip_memcpy_h2d_async', device.ptr(slot.rois), ctypes.c_void_p(slot.rois_host.ctypes.data), slot.rois_host.nbytes)
+            for dst, host in uploads:
+                device.call('pvhip_memcpy_h2d_async', device.ptr(dst), ctypes.c_void_p(host.ctypes.data), host.nbytes)
             slot.event.record()
             device.select_stream(stream_base)
             slot.event.wait()
+            if slot.detected is not None:
+                slot.detected.live = make_table is not None
+                if make_table is None:
+                    slot.detected.source = None
+            if make_table is not None:
+                make_table()
             self._convert(fmt, slot, staged, largest)
             device.select_stream(0)
             out[name] = slot.fixed

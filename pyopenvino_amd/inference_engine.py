@@ -35,7 +35,7 @@ import numpy as np
 
 from . import common_def, device, fusion_plan, stream_plan
 from .host_input import HostInputs
-from .input_format import InputInfo, PreProcessChannel, PreProcessInfo  # noqa: F401 -- the classes of IENetwork.input_info
+from .input_format import DetectedRois, InputInfo, PreProcessChannel, PreProcessInfo  # noqa: F401 -- the classes of IENetwork.input_info
 from .stream_plan import CaptureStreamModel
 
 DEFAULT_PLUGIN_PACKAGE = 'pyopenvino_amd.op_plugins'
@@ -308,7 +308,8 @@ class InferRequest:
         if self._in_flight:
             raise RuntimeError('request {} is still in flight: wait() first'.format(self.index))
         ex = self.runner
-        inputs = ex.host_inputs.stage(inputs, ex.stream_base)
+        inputs = ex.host_inputs.stage(inputs, ex.stream_base, ex.sharded or self.owner.sharded)
+        ex.wait_result_readers()
         # The same device-resident tensors as the last calls: the pass is replayed from this request's own recording (one call
         # instead of ~100 dispatches; every request records its own pass on its own stream and keeps its own tensors, so the
         # replays of several requests run side by side like their eager passes do).
@@ -356,6 +357,16 @@ class InferRequest:
         (id, x, y, w, h).  ``RoiInput(input_buffer(name, (h, w), frames=m), roi_buffer(name))`` costs no host copy; ownership as for
         ``input_buffer``."""
         return self.runner.host_inputs.roi_buffer(name)
+
+    def detected_rois(self, name: str):
+        """After ``wait()`` of a pass whose input `name` was a ``DetectedRois``: the record (count, selected, rois, records) -- `rois` the
+        (n, 5) int32 table that pass used, rows >= count being (-1, 0, 0, 0, 0); `records[k]` the flat row of the detections batch row
+        k came from (its label and score stand there), -1 from row count on; `selected` the records that passed the screen, which may
+        exceed n; count = min(selected, n).  One small page-locked read-back on this request's drained stream.  RuntimeError when the
+        last pass of that input was fed anything else."""
+        if self._in_flight:
+            raise RuntimeError('request {} is still in flight: wait() first'.format(self.index))
+        return self.runner.host_inputs.detected_rois(name, self.runner.stream_base)
 
 
 @contextlib.contextmanager
@@ -405,6 +416,9 @@ class Executable_Network:
         self._order_events, self._events_in_flight = [], []
         self._event_pool = []           # timed events for the device_timing brackets
         self._pending = None            # (allocation epoch or None, event) of a pass issued without a host wait: wait_done() ends it
+        # events behind the launches of OTHER requests that read this network's device-resident Result (a DetectedRois fed from this
+        # request while in flight): the next pass, eager or replayed, waits for them on the device before it can overwrite that tensor
+        self._result_readers = []
         if input_formats is None:
             input_formats = {name: info.frozen() for name, info in ienetwork.input_info.items()}
         self.host_inputs = HostInputs(input_formats)    # host arrays in a declared format or the request's own buffers -> device tensors
@@ -456,6 +470,7 @@ class Executable_Network:
         constants, Concat buffers): it goes first, or a later infer_graph() would replay kernels over freed or reused pool blocks."""
         self.release_graph()
         self.host_inputs.release()                  # page-locked buffers go back once the caller holds no view of them
+        self._result_readers = []
         G = self.ienet.G
         for nid in G.nodes:
             node = G.nodes[nid]
@@ -465,6 +480,17 @@ class Executable_Network:
                 port.pop('data', None)
             for key in ('result', 'param', '_sibling_out') + fusion_plan.HINT_KEYS:
                 node.pop(key, None)
+
+    sharded = property(lambda self: self.comm is not None and getattr(self.comm, 'world', 1) > 1)
+
+    def wait_result_readers(self):
+        """The base stream waits for every launch of another request that still reads the last pass's Result on the device."""
+        if self._result_readers:
+            readers, self._result_readers = self._result_readers, []
+            device.select_stream(self.stream_base)
+            for event in readers:
+                event.wait()
+            device.select_stream(0)
 
     def start_async(self, request_id: int, inputs: dict):
         self.requests[request_id].start_async(inputs)
@@ -970,7 +996,8 @@ class Executable_Network:
         return self._graph
 
     def infer(self, inputs: dict, verbose: bool = False) -> dict:
-        inputs = self.host_inputs.stage(inputs, self.stream_base)
+        inputs = self.host_inputs.stage(inputs, self.stream_base, self.sharded)
+        self.wait_result_readers()
         if self._graph_for(inputs, verbose) is None:
             return self._infer_eager(inputs, verbose)
         return self.infer_graph(inputs)

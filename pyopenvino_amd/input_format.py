@@ -1,6 +1,7 @@
 """The format a caller hands a network input in: what is declared between ``read_network`` and ``load_network`` (InputInfo, PreProcessInfo,
 PreProcessChannel: OpenVINO 2021's ``IENetwork.input_info``) and the fixed value it becomes at load (InputFormat), which owns the shape
 arithmetic of that format.  Host only: nothing here touches the device (host_input.py stages arrays of these formats)."""
+import collections
 import dataclasses
 
 import numpy as np
@@ -163,6 +164,74 @@ class RoiInput:
 
     def __repr__(self):
         return 'RoiInput(frames={}, rois={})'.format(getattr(self.frames, 'shape', None), getattr(self.rois, 'shape', None))
+
+
+class DetectedRois:
+    """A network input given as the regions another network detected (a cascade: detector, then classifier, both on this GPU):
+    ``start_async({name: DetectedRois(frames, detections)})``, wherever a RoiInput is accepted.  `frames`: as for RoiInput.  `detections`:
+    DetectionOutput records [rank, label, score, xmin, ymin, xmax, ymax] with normalised corners, as
+      * the ``InferRequest`` of another loaded network whose Result (`output` names it when there are several) is a DetectionOutput: in
+        flight, its device-resident Result is read with no host wait -- this request's stream waits for the detector's pass on the device
+        --; waited for, its last host Results are taken like an array;
+      * a ``device.DeviceTensor``, or a host array (uploaded behind the same event as the frames), float32 of shape (1, 1, R, 7) or (R, 7).
+    `images` = N: the images the R records belong to (default: the detector's batch; for an array, the frame count m), R // N records
+    each; image b's rectangles are cut from frame b, so N == m.  A record is used when it lies in front of its image's terminator, its
+    score is >= `min_confidence`, its corners are finite, its label is one of `labels` (None: any; at most MAX_LABELS ints >= 0) and
+    its rectangle -- floor / ceil of the corners scaled to the frame and clamped to it -- is at least `min_size` = (h, w).  The first n
+    of them, in the order (image, position), become batch rows 0..count-1; the other rows are quiet NaN.  The table is made on the device
+    (pvhip_detections_to_rois; the rule in numpy: tests/detected_rois_ref.py); ``InferRequest.detected_rois(name)`` reads it back.
+
+    The detector may be started again as soon as ``start_async`` of this input has returned: its next pass waits, on the device, until
+    the table has been made.  ``detector.wait()`` may come before or after that ``start_async``."""
+    __slots__ = ('frames', 'detections', 'output', 'images', 'min_confidence', 'labels', 'min_size')
+    MAX_LABELS = 64
+
+    def __init__(self, frames, detections, output=None, images=None, min_confidence=0.5, labels=None, min_size=(1, 1)):
+        self.frames, self.detections, self.output, self.images = frames, detections, output, images
+        self.min_confidence, self.labels, self.min_size = min_confidence, labels, min_size
+
+    def __repr__(self):
+        return 'DetectedRois(frames={}, detections={})'.format(getattr(self.frames, 'shape', None), type(self.detections).__name__)
+
+    def checked_options(self, name):
+        """(min_confidence as a float, labels as an int32 array or None, (min_h, min_w)) for input `name`, or ValueError."""
+        conf, labels, size = self.min_confidence, self.labels, self.min_size
+        if isinstance(conf, bool) or not isinstance(conf, (int, float, np.integer, np.floating)) or conf != conf:
+            raise ValueError('input {}: min_confidence {!r} is not a real number'.format(name, conf))
+        if labels is not None:
+            labels = np.asarray(labels)
+            if labels.ndim != 1 or labels.dtype.kind not in 'iu' or len(labels) > self.MAX_LABELS or (labels.astype(np.int64) < 0).any() \
+                    or (labels > np.iinfo(np.int32).max).any():
+                raise ValueError('input {}: labels is None or at most {} ints >= 0, got {!r}'.format(name, self.MAX_LABELS, self.labels))
+            labels = labels.astype(np.int32)
+        try:
+            ok = len(size) == 2 and all(not isinstance(v, bool) and isinstance(v, (int, np.integer)) and 1 <= v <= np.iinfo(np.int32).max for v in size)
+        except TypeError:
+            ok = False
+        if not ok:
+            raise ValueError('input {}: min_size is (h, w) with both >= 1, got {!r}'.format(name, size))
+        return float(conf), labels, (int(size[0]), int(size[1]))
+
+    def checked_records(self, name, shape, dtype, images, frames):
+        """The records per image P of detections of `shape` and `dtype` over `images` images, cut from `frames` frames; or ValueError."""
+        if np.dtype(dtype) != np.float32 or len(shape) not in (2, 4) or shape[-1] != 7 or tuple(shape[:-2]) not in ((), (1, 1)) or shape[-2] < 1:
+            raise ValueError('input {}: detections are float32 records of shape (1, 1, R, 7) or (R, 7), got {} {}'.format(
+                name, np.dtype(dtype).name, tuple(shape)))
+        if isinstance(images, bool) or not isinstance(images, (int, np.integer)) or images < 1:
+            raise ValueError('input {}: images is a count >= 1, not {!r}'.format(name, images))
+        if images != frames:
+            raise ValueError('input {}: image b\'s rectangles are cut from frame b: {} images need {} frames, got {}'.format(
+                name, images, images, frames))
+        if shape[-2] % images:
+            raise ValueError('input {}: {} records do not divide over {} images'.format(name, shape[-2], images))
+        if shape[-2] * 7 >= 2 ** 31:
+            raise ValueError('input {}: {} records are more than one launch indexes'.format(name, shape[-2]))
+        return int(shape[-2]) // int(images)
+
+
+# what InferRequest.detected_rois returns: the (n, 5) int32 table the pass used, the flat row of the detections each batch row came from
+# (-1 from row `count` on), how many records passed the screen (`selected`, which may exceed n) and count = min(selected, n)
+DetectedTable = collections.namedtuple('DetectedTable', 'count selected rois records')
 
 
 class InputInfo:
