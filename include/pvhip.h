@@ -137,6 +137,52 @@ int pvhip_softmax_rows_f32(const float* x, float* y, int rows, int cols);
  * window clipped to [0, C); alpha is NOT divided by size.  hw = H*W.                             */
 int pvhip_lrn_f32(const float* x, float* y, int n, int c, int hw, int size,
                   float alpha, float beta, float bias);
+/* Which kernel form a launch of the four entries above and of pvhip_dwconv2d_f32 takes (an addition to ABI v17).  Host-only like
+ * pvhip_conv2d_kernel_kind: no device needed, the PVHIP_* switches are honoured, and the answer comes from the SAME plan function
+ * the compute entry switches on.  Each query takes its entry's geometry arguments and fills form[PVHIP_FORM_INTS]; slots a form
+ * does not use are 0, and PVHIP_FORM_KIND is PVHIP_FORM_NONE for an empty tensor (nothing is launched).  Returns PVHIP_OK, or
+ * what the entry itself would return for these arguments (PVHIP_EINVAL, PVHIP_EUNSUPPORTED).  NOT thread-safe against launches of
+ * the same entries from another thread: the 3x3 column planner keeps an unsynchronised cache of plans that both sides use.    */
+#define PVHIP_FORM_INTS           16
+#define PVHIP_FORM_KIND           0   /* the kernel, ids below                                                              */
+#define PVHIP_FORM_G              1   /* (n, c) planes per workgroup / tile                                                 */
+#define PVHIP_FORM_BANDS          2   /* bands of output rows per plane (1: whole planes)                                   */
+#define PVHIP_FORM_BAND_ROWS      3   /* output rows per band                                                               */
+#define PVHIP_FORM_CLIP           4   /* MaxPool, LDS kernels: windows overhang the padded extent (the CLIP instantiation)  */
+#define PVHIP_FORM_VEC            5   /* AvgPool / depthwise LDS kernels: 1 when EVERY workgroup starts on a 16-byte boundary
+                                         (16-byte staging loads), 0 when some take the scalar loop; LRN: pixels per lane    */
+#define PVHIP_FORM_STAGE          6   /* column kernels: outputs leave through the output stage in LDS                      */
+#define PVHIP_FORM_NT             7   /* column kernels: nontemporal accesses (PVHIP_STREAM_NT)                             */
+#define PVHIP_FORM_S              8   /* column kernels: row segments per output column                                     */
+#define PVHIP_FORM_LRN_SIZE       9   /* LRN: the window                                                                    */
+#define PVHIP_FORM_LRN_BETA_MODE  10  /* LRN: 0 powf, 1 two square roots (beta 0.75, bias < 1e-20), 2 sqrt (0.5), 3 the
+                                         divisor itself (1.0), 4 exp2(-0.75 log2 d) (beta 0.75, bias >= 1e-20)              */
+#define PVHIP_FORM_GRID           11  /* LRN, SoftMax: workgroups launched                                                  */
+#define PVHIP_FORM_LOOPS          12  /* LRN, SoftMax: 1 when a workgroup's grid-stride loop runs more than once            */
+#define PVHIP_FORM_NONE          (-1)
+#define PVHIP_MAXPOOL_GLOBAL      0   /* maxpool2d_kernel: one lane per output, windows read from HBM                       */
+#define PVHIP_MAXPOOL_LDS         1   /* maxpool2d_lds_kernel<0,0>: run-time window                                         */
+#define PVHIP_MAXPOOL_LDS_2X2     2
+#define PVHIP_MAXPOOL_LDS_3X3     3
+#define PVHIP_MAXPOOL_COLS_S1     4   /* maxpool3x3_cols_kernel, stride 1                                                   */
+#define PVHIP_MAXPOOL_COLS_S2     5
+#define PVHIP_AVGPOOL_GLOBAL      0   /* avgpool2d_kernel                                                                   */
+#define PVHIP_AVGPOOL_LDS         1   /* avgpool2d_lds_kernel: whole planes of at most 16 KB                                */
+#define PVHIP_DWCONV_GLOBAL       0   /* dwconv_kernel                                                                      */
+#define PVHIP_DWCONV_LDS          1   /* dwconv2d_lds_kernel<0,0>                                                           */
+#define PVHIP_DWCONV_LDS_3X3      2
+#define PVHIP_DWCONV_COLS_S1      3   /* dwconv3x3_cols_kernel, stride 1                                                    */
+#define PVHIP_DWCONV_COLS_S2      4
+#define PVHIP_LRN_GENERIC         0   /* lrn_generic_kernel                                                                 */
+#define PVHIP_LRN_WINDOW          1   /* lrn_window_kernel<size, vec, beta mode>                                            */
+int pvhip_maxpool2d_form(int n, int c, int h, int w, int oh, int ow, int kh, int kw, int sh, int sw,
+                         int pad_top, int pad_left, int pad_bottom, int pad_right, int* form);
+int pvhip_avgpool2d_form(int n, int c, int h, int w, int oh, int ow, int kh, int kw, int sh, int sw, int* form);
+int pvhip_dwconv2d_form(int n, int g, int h, int wdt, int kh, int kw, int oh, int ow, int sh, int sw,
+                        int pad_top, int pad_left, int* form);
+int pvhip_lrn_form(int n, int c, int hw, int size, float beta, float bias, int* form);
+#define PVHIP_SOFTMAX_ROWS        0   /* softmax_rows_kernel: a workgroup per row, rows beyond the grid in a loop           */
+int pvhip_softmax_rows_form(int rows, int cols, int* form);
 /* LRN.py:10-22 followed by MaxPool.py:41-72 (3x3 window, stride 1 or 2) as ONE launch: y = maxpool(lrn(x)) with the
  * arithmetic and the pooling rules of the two entries above (bit-identical to calling them in turn); the LRN tensor is
  * never written.  x is (n, c, h, w), y is (n, c, oh, ow).  Covers size == 5, beta == 0.75, c % 8 == 0 and bands of

@@ -889,27 +889,53 @@ __global__ __launch_bounds__(kBlock) void lrn_generic_kernel(const float* __rest
     }
 }
 
-template <int SIZE, int BETA_MODE>
-void launch_lrn_window_b(const float* x, float* y, int n, int c, int hw, float alpha, float beta, float bias) {
-    if (hw % 4 == 0) {
-        const size_t cols = (size_t)n * (hw / 4);
-        hipLaunchKernelGGL((lrn_window_kernel<SIZE, 4, BETA_MODE>), dim3(grid_for(cols)), dim3(kBlock), 0, state().stream, x, y,
-                           n, c, hw, alpha, beta, bias);
+// Which kernel an LRN launch takes, decided HERE and nowhere else: pvhip_lrn_f32 switches on the plan, pvhip_lrn_form (no device
+// needed) reports it.  The register-window kernel is instantiated for windows of 3, 5 and 7 channels and wants whole chunks of
+// eight channels; VEC = 4 pixels per lane where a plane is a whole number of 16-byte pieces.
+struct LrnPlan {
+    int kind, size, vec, bm, grid, loops;
+};
+
+LrnPlan plan_lrn(int n, int c, int hw, int size, float beta, float bias) {
+    LrnPlan p;
+    p.bm = lrn_beta_mode(beta, bias);
+    if (c % 8 == 0 && c >= 8 && (size == 3 || size == 5 || size == 7)) {
+        p.kind = PVHIP_LRN_WINDOW;
+        p.size = size;
+        p.vec  = (hw % 4 == 0) ? 4 : 1;
+        p.grid = grid_for((size_t)n * (hw / p.vec));
+        p.loops = (size_t)n * (hw / p.vec) > (size_t)p.grid * kBlock;
     } else {
-        const size_t cols = (size_t)n * hw;
-        hipLaunchKernelGGL((lrn_window_kernel<SIZE, 1, BETA_MODE>), dim3(grid_for(cols)), dim3(kBlock), 0, state().stream, x, y,
-                           n, c, hw, alpha, beta, bias);
+        p.kind = PVHIP_LRN_GENERIC;
+        p.size = size;
+        p.vec  = 1;
+        p.grid = grid_for((size_t)n * c * hw);
+        p.loops = (size_t)n * c * hw > (size_t)p.grid * kBlock;
     }
+    return p;
+}
+
+// SoftMax: a workgroup per row, at most kMaxBlocks of them (rows beyond that in the kernel's loop).
+int plan_softmax_grid(int rows) { return rows < kMaxBlocks ? rows : kMaxBlocks; }
+
+template <int SIZE, int BETA_MODE>
+void launch_lrn_window_b(const LrnPlan& p, const float* x, float* y, int n, int c, int hw, float alpha, float beta, float bias) {
+    if (p.vec == 4)
+        hipLaunchKernelGGL((lrn_window_kernel<SIZE, 4, BETA_MODE>), dim3(p.grid), dim3(kBlock), 0, state().stream, x, y,
+                           n, c, hw, alpha, beta, bias);
+    else
+        hipLaunchKernelGGL((lrn_window_kernel<SIZE, 1, BETA_MODE>), dim3(p.grid), dim3(kBlock), 0, state().stream, x, y,
+                           n, c, hw, alpha, beta, bias);
 }
 
 template <int SIZE>
-void launch_lrn_window(const float* x, float* y, int n, int c, int hw, float alpha, float beta, float bias, int bm) {
-    switch (bm) {
-        case 1: launch_lrn_window_b<SIZE, 1>(x, y, n, c, hw, alpha, beta, bias); break;
-        case 2: launch_lrn_window_b<SIZE, 2>(x, y, n, c, hw, alpha, beta, bias); break;
-        case 3: launch_lrn_window_b<SIZE, 3>(x, y, n, c, hw, alpha, beta, bias); break;
-        case 4: launch_lrn_window_b<SIZE, 4>(x, y, n, c, hw, alpha, beta, bias); break;
-        default: launch_lrn_window_b<SIZE, 0>(x, y, n, c, hw, alpha, beta, bias); break;
+void launch_lrn_window(const LrnPlan& p, const float* x, float* y, int n, int c, int hw, float alpha, float beta, float bias) {
+    switch (p.bm) {
+        case 1: launch_lrn_window_b<SIZE, 1>(p, x, y, n, c, hw, alpha, beta, bias); break;
+        case 2: launch_lrn_window_b<SIZE, 2>(p, x, y, n, c, hw, alpha, beta, bias); break;
+        case 3: launch_lrn_window_b<SIZE, 3>(p, x, y, n, c, hw, alpha, beta, bias); break;
+        case 4: launch_lrn_window_b<SIZE, 4>(p, x, y, n, c, hw, alpha, beta, bias); break;
+        default: launch_lrn_window_b<SIZE, 0>(p, x, y, n, c, hw, alpha, beta, bias); break;
     }
 }
 
@@ -922,9 +948,21 @@ int pvhip_softmax_rows_f32(const float* x, float* y, int rows, int cols) {
     PVHIP_CHECK_ARG(rows >= 0 && cols >= 0);
     if (rows == 0 || cols == 0) return PVHIP_OK;
     PVHIP_CHECK_ARG(x != nullptr && y != nullptr);
-    const int g = rows < kMaxBlocks ? rows : kMaxBlocks;
+    const int g = plan_softmax_grid(rows);
     hipLaunchKernelGGL(softmax_rows_kernel, dim3(g), dim3(kBlock), 0, state().stream, x, y, rows, cols);
     PVHIP_LAUNCH_CHECK();
+    return PVHIP_OK;
+}
+
+int pvhip_softmax_rows_form(int rows, int cols, int* form) {
+    PVHIP_CHECK_ARG(form != nullptr);
+    for (int i = 0; i < PVHIP_FORM_INTS; ++i) form[i] = 0;
+    form[PVHIP_FORM_KIND] = PVHIP_FORM_NONE;
+    PVHIP_CHECK_ARG(rows >= 0 && cols >= 0);
+    if (rows == 0 || cols == 0) return PVHIP_OK;                     // nothing is launched
+    form[PVHIP_FORM_KIND]  = PVHIP_SOFTMAX_ROWS;
+    form[PVHIP_FORM_GRID]  = plan_softmax_grid(rows);
+    form[PVHIP_FORM_LOOPS] = rows > form[PVHIP_FORM_GRID] ? 1 : 0;
     return PVHIP_OK;
 }
 
@@ -935,16 +973,34 @@ int pvhip_lrn_f32(const float* x, float* y, int n, int c, int hw, int size, floa
     PVHIP_CHECK_ARG(x != nullptr && y != nullptr);
     if ((unsigned long long)n * c * hw >= (1ull << 31))
         return fail(PVHIP_EUNSUPPORTED, "pvhip_lrn_f32: tensor exceeds 2^31 elements");
-    const int bm = lrn_beta_mode(beta, bias);
-    switch ((c % 8 == 0 && c >= 8) ? size : 0) {
-        case 3: launch_lrn_window<3>(x, y, n, c, hw, alpha, beta, bias, bm); break;
-        case 5: launch_lrn_window<5>(x, y, n, c, hw, alpha, beta, bias, bm); break;
-        case 7: launch_lrn_window<7>(x, y, n, c, hw, alpha, beta, bias, bm); break;
+    const LrnPlan p = plan_lrn(n, c, hw, size, beta, bias);
+    switch (p.kind == PVHIP_LRN_WINDOW ? p.size : 0) {
+        case 3: launch_lrn_window<3>(p, x, y, n, c, hw, alpha, beta, bias); break;
+        case 5: launch_lrn_window<5>(p, x, y, n, c, hw, alpha, beta, bias); break;
+        case 7: launch_lrn_window<7>(p, x, y, n, c, hw, alpha, beta, bias); break;
         default:
-            hipLaunchKernelGGL(lrn_generic_kernel, dim3(grid_for((size_t)n * c * hw)), dim3(kBlock), 0, state().stream, x, y,
-                               n, c, hw, size, alpha, beta, bias, bm);
+            hipLaunchKernelGGL(lrn_generic_kernel, dim3(p.grid), dim3(kBlock), 0, state().stream, x, y,
+                               n, c, hw, size, alpha, beta, bias, p.bm);
     }
     PVHIP_LAUNCH_CHECK();
+    return PVHIP_OK;
+}
+
+int pvhip_lrn_form(int n, int c, int hw, int size, float beta, float bias, int* form) {
+    PVHIP_CHECK_ARG(form != nullptr);
+    for (int i = 0; i < PVHIP_FORM_INTS; ++i) form[i] = 0;
+    form[PVHIP_FORM_KIND] = PVHIP_FORM_NONE;
+    PVHIP_CHECK_ARG(n >= 0 && c >= 0 && hw >= 0 && size >= 1);
+    if ((size_t)n * c * hw == 0) return PVHIP_OK;                    // nothing is launched
+    if ((unsigned long long)n * c * hw >= (1ull << 31))
+        return fail(PVHIP_EUNSUPPORTED, "pvhip_lrn_form: tensor exceeds 2^31 elements");
+    const LrnPlan p = plan_lrn(n, c, hw, size, beta, bias);
+    form[PVHIP_FORM_KIND] = p.kind;
+    form[PVHIP_FORM_LRN_SIZE] = p.size;
+    form[PVHIP_FORM_GRID] = p.grid;
+    form[PVHIP_FORM_LOOPS] = p.loops;
+    form[PVHIP_FORM_VEC] = p.vec;
+    form[PVHIP_FORM_LRN_BETA_MODE] = p.bm;
     return PVHIP_OK;
 }
 

@@ -809,6 +809,177 @@ int check_pool_dims(const char* who, int n, int c, int h, int w, int oh, int ow,
     return PVHIP_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Launch plans.  Which kernel form a pooling / depthwise launch takes is decided HERE and nowhere else: the compute entries
+// switch on the plan, the pvhip_*_form queries (no device needed) report it.  No pointer is read; x / y only travel into the
+// argument block of the column kernels.
+
+// nontemporal accesses from the size on where the tensors cannot stay in L2 for the consumer anyway (PVHIP_STREAM_NT)
+bool stream_nt(int planes, int h, int w, int oh, int ow) {
+    const int ntm = settings().stream_nt;
+    return ntm == 2 || (ntm == 1 && (size_t)planes * ((size_t)h * w + (size_t)oh * ow) * 4 >= ((size_t)64 << 20));
+}
+
+struct MaxPoolPlan {
+    int       kind = PVHIP_MAXPOOL_GLOBAL;
+    int       G = 1, band_rows = 0, n_bands = 1;
+    bool      clip = false, nt = false;
+    size_t    lds = 0;
+    Pool3Plan p3{};            // PVHIP_MAXPOOL_COLS_*
+};
+
+MaxPoolPlan plan_maxpool(const float* x, float* y, const PoolArgs& a) {
+    MaxPoolPlan p;
+    const int planes = a.n_planes, h = a.h, w = a.w, oh = a.oh, ow = a.ow, kh = a.kh, kw = a.kw, sh = a.sh, sw = a.sw;
+    p.band_rows = oh;
+    if (kh == 3 && kw == 3 && sh == sw && (sh == 1 || sh == 2) &&
+        plan_pool3(x, y, planes, h, w, oh, ow, sh, a.pt, a.pl, a.hp, a.wp, p.p3)) {
+        p.kind = sh == 1 ? PVHIP_MAXPOOL_COLS_S1 : PVHIP_MAXPOOL_COLS_S2;
+        p.G = p.p3.a.G; p.band_rows = p.p3.a.band_rows; p.n_bands = p.p3.a.n_bands;
+        p.lds = p.p3.lds;
+        p.nt  = stream_nt(planes, h, w, oh, ow);
+        return p;
+    }
+    // LDS-staged path.  ~16 KB of LDS per workgroup (8-10 workgroups per CU overlap each other's load and
+    // compute phases; measured best on the GoogLeNet shapes): several whole planes per workgroup when planes
+    // are small, bands of output rows of one plane when a plane is larger than the budget.
+    const size_t group_bytes = (size_t)settings().pool_lds_kb * 1024;       // PVHIP_POOL_LDS_KB: tuning runs only
+    const size_t row_bytes   = (size_t)a.wp * sizeof(float);
+    const size_t plane_bytes = (size_t)a.hp * row_bytes;
+    const size_t min_band    = (size_t)(kh + sh) * row_bytes;       // at least two output rows per band
+    if (min_band > 60 * 1024) return p;                             // not even two output rows fit: one lane per output
+    int G = 1, band_rows = oh, n_bands = 1;
+    if (plane_bytes <= group_bytes) {
+        G = (int)(group_bytes / plane_bytes);
+        while (G > 4 && (planes + G - 1) / G < 8 * kNumCU) G >>= 1;
+        if ((h * w) % 4 != 0 && G >= 4) G &= ~3;     // every group starts 16-byte aligned in HBM
+        if (G > planes) G = planes;
+    } else {
+        const size_t budget  = group_bytes > min_band ? group_bytes : min_band;
+        const int    rows_in = (int)(budget / row_bytes);            // padded input rows per band: >= kh + sh, so band_rows >= 2
+        band_rows = (rows_in - kh) / sh + 1;
+        if (band_rows > oh) band_rows = oh;
+        n_bands = (oh + band_rows - 1) / band_rows;
+        band_rows = (oh + n_bands - 1) / n_bands;                // even out the bands
+        n_bands = (oh + band_rows - 1) / band_rows;
+    }
+    const int rows_l = (n_bands == 1) ? a.hp : ((band_rows - 1) * sh + kh < a.hp ? (band_rows - 1) * sh + kh : a.hp);
+    p.lds = (((size_t)G * rows_l * row_bytes) + 15) & ~(size_t)15;
+    // lds > 64 KB needs PVHIP_POOL_LDS_KB above 64: whole planes take G * plane_bytes <= group_bytes, and a band holds
+    // rows_l <= (band_rows - 1) * sh + kh <= rows_in rows (evening the bands out only shrinks band_rows), i.e. at most
+    // budget = max(group_bytes, min_band) <= 60 KB at the default of 16.  More than 65535 bands: a plane of 131070 rows
+    // and more whose rows are wider than 16 KB / (kh + sh).
+    if (p.lds > 64 * 1024 || n_bands > 65535) return p;
+    p.kind = (kh == 3 && kw == 3) ? PVHIP_MAXPOOL_LDS_3X3 : (kh == 2 && kw == 2) ? PVHIP_MAXPOOL_LDS_2X2 : PVHIP_MAXPOOL_LDS;
+    p.G = G; p.band_rows = band_rows; p.n_bands = n_bands;
+    p.clip = ((oh - 1) * sh + kh > a.hp) || ((ow - 1) * sw + kw > a.wp);
+    return p;
+}
+
+struct AvgPoolPlan {
+    int    kind = PVHIP_AVGPOOL_GLOBAL;
+    int    G = 1;
+    size_t lds = 0;
+};
+
+AvgPoolPlan plan_avgpool(const PoolArgs& a) {
+    AvgPoolPlan p;
+    const size_t plane_bytes = (size_t)a.h * a.w * sizeof(float);
+    if (plane_bytes > 16 * 1024) return p;
+    const int planes = a.n_planes;
+    int       G      = (int)(16 * 1024 / plane_bytes);
+    while (G > 4 && (planes + G - 1) / G < 8 * kNumCU) G >>= 1;
+    if ((a.h * a.w) % 4 != 0 && G >= 4) G &= ~3;
+    if (G > planes) G = planes;
+    p.kind = PVHIP_AVGPOOL_LDS;
+    p.G    = G;
+    p.lds  = (((size_t)G * plane_bytes) + 15) & ~(size_t)15;
+    return p;
+}
+
+struct DwPlan {
+    int       kind = PVHIP_DWCONV_GLOBAL;
+    int       G = 1, band_rows = 0, n_bands = 1;
+    int       hp = 0, wp = 0;  // padded extents: everything the windows touch (cells past the tensor are zeros by definition)
+    bool      nt = false;
+    size_t    lds = 0;
+    Pool3Plan p3{};            // PVHIP_DWCONV_COLS_*
+};
+
+DwPlan plan_dwconv(const float* x, float* y, int planes, int h, int wdt, int kh, int kw, int oh, int ow, int sh, int sw, int pad_top,
+                   int pad_left) {
+    DwPlan p;
+    int hp = (oh - 1) * sh + kh, wp = (ow - 1) * sw + kw;
+    if (hp < h + pad_top) hp = h + pad_top;
+    if (wp < wdt + pad_left) wp = wdt + pad_left;
+    p.hp = hp; p.wp = wp; p.band_rows = oh;
+    // 3x3, stride 1 or 2: the pipelined kernel on the MaxPool kernel's tiles (PVHIP_DWCONV_COLS=0: the one-shot LDS kernel)
+    if (kh == 3 && kw == 3 && sh == sw && (sh == 1 || sh == 2) && settings().dwconv_cols) {
+        // The lanes store their outputs themselves (PVHIP_DWCONV_COLS=2: through the MaxPool kernel's output stage in LDS, measured
+        // slower on every MobileNet layer: 1.32 against 1.16 ms over the 13 -- the stage costs LDS, i.e. halo rows and resident tiles).
+        // (bands of odd-width planes start on no boundary at all and ran 20 % slower than the one-shot kernel; MobileNet's 75x75
+        // planes fit whole)
+        const bool ok = plan_pool3(x, y, planes, h, wdt, oh, ow, sh, pad_top, pad_left, hp, wp, p.p3, true, settings().dwconv_cols == 2 ? 1 : 0) &&
+                        !(p.p3.a.n_bands > 1 && (wdt & 1));
+        if (ok) {
+            p.kind = sh == 1 ? PVHIP_DWCONV_COLS_S1 : PVHIP_DWCONV_COLS_S2;
+            p.G = p.p3.a.G; p.band_rows = p.p3.a.band_rows; p.n_bands = p.p3.a.n_bands;
+            p.lds = p.p3.lds;
+            p.nt  = stream_nt(planes, h, wdt, oh, ow);
+            return p;
+        }
+    }
+    const size_t group_bytes = 16 * 1024;
+    const size_t row_bytes   = (size_t)wp * sizeof(float);
+    const size_t plane_bytes = (size_t)hp * row_bytes;
+    const size_t min_band    = (size_t)(kh + sh) * row_bytes;
+    if (min_band > 48 * 1024) return p;                              // not even two output rows fit: one lane per output
+    int G = 1, band_rows = oh, n_bands = 1;
+    if (plane_bytes <= group_bytes) {
+        G = (int)(group_bytes / plane_bytes);
+        while (G > 4 && (planes + G - 1) / G < 8 * kNumCU) G >>= 1;
+        if ((h * wdt) % 4 != 0 && G >= 4) G &= ~3;
+        if (G > planes) G = planes;
+    } else {
+        const size_t budget  = group_bytes > min_band ? group_bytes : min_band;
+        const int    rows_in = (int)(budget / row_bytes);            // >= kh + sh, so band_rows >= 2
+        band_rows = (rows_in - kh) / sh + 1;
+        if (band_rows > oh) band_rows = oh;
+        n_bands   = (oh + band_rows - 1) / band_rows;
+        band_rows = (oh + n_bands - 1) / n_bands;
+        n_bands   = (oh + band_rows - 1) / band_rows;
+    }
+    const int rows_l = (n_bands == 1) ? hp : ((band_rows - 1) * sh + kh < hp ? (band_rows - 1) * sh + kh : hp);
+    p.lds = ((((size_t)G * rows_l * wp + 3) & ~(size_t)3) + (size_t)G * kh * kw) * sizeof(float);
+    // lds > 64 KB is REACHABLE here, unlike in plan_maxpool: the image of a band is at most max(16 KB, min_band) <= 48 KB, but the
+    // kh * kw weights sit behind it, and a window of 100 x 100 taps on rows of 100 floats is 40 KB of band plus 40 KB of weights.
+    // More than 65535 bands: as in plan_maxpool.
+    if (p.lds > 64 * 1024 || n_bands > 65535) return p;
+    p.kind = (kh == 3 && kw == 3) ? PVHIP_DWCONV_LDS_3X3 : PVHIP_DWCONV_LDS;
+    p.G = G; p.band_rows = band_rows; p.n_bands = n_bands;
+    return p;
+}
+
+// Whether EVERY workgroup of an LDS-staged launch starts on a 16-byte boundary of the input (the kernels test their own start: 16-byte
+// loads where it is aligned, the scalar loop where it is not).  For the form queries only: a host copy of the kernels' own tests, which
+// it must follow -- avgpool2d_lds_kernel's `((size_t)g0 * hw) & 3` with g0 = blockIdx.x * G, and dwconv2d_lds_kernel's `aligned =
+// (in_off & 3) == 0` with in_off = g0 * h * w + iy_lo * w, iy_lo = max(0, blockIdx.y * band_rows * sh - pt) (bands only with G == 1).
+int all_starts_aligned(int h, int w, int G, int planes, int n_bands, int band_rows, int sh, int pt) {
+    const bool planes_ok = ((size_t)h * w) % 4 == 0 || G % 4 == 0 || G >= planes;
+    if (n_bands == 1) return planes_ok ? 1 : 0;
+    if (!planes_ok) return 0;
+    for (int b = 0; b < n_bands; ++b) {
+        const int iy_lo = b * band_rows * sh - pt > 0 ? b * band_rows * sh - pt : 0;
+        if (((size_t)iy_lo * w) % 4 != 0) return 0;
+    }
+    return 1;
+}
+
+void clear_form(int* form) {
+    for (int i = 0; i < PVHIP_FORM_INTS; ++i) form[i] = 0;
+    form[PVHIP_FORM_KIND] = PVHIP_FORM_NONE;
+}
+
 }  // namespace
 
 extern "C" {
@@ -826,77 +997,70 @@ int pvhip_maxpool2d_f32(const float* x, float* y, int n, int c, int h, int w, in
     // every window must start inside the padded extent (numpy would raise on an empty np.max)
     if ((oh - 1) * sh >= a.hp || (ow - 1) * sw >= a.wp)
         return fail(PVHIP_EINVAL, "pvhip_maxpool2d_f32: window starts outside the padded input");
-    if (kh == 3 && kw == 3 && sh == sw && (sh == 1 || sh == 2)) {
-        Pool3Plan pl3;
-        if (plan_pool3(x, y, n * c, h, w, oh, ow, sh, pad_top, pad_left, a.hp, a.wp, pl3)) {
+    const MaxPoolPlan p = plan_maxpool(x, y, a);
+    switch (p.kind) {
+        case PVHIP_MAXPOOL_COLS_S1:
+        case PVHIP_MAXPOOL_COLS_S2: {
+            const Pool3Plan& pl3 = p.p3;
             Pool3Divs dv3{make_fastdiv((unsigned)pl3.a.n_bands), make_fastdiv((unsigned)(pl3.a.S * ow)), make_fastdiv((unsigned)ow)};
             const dim3 g3(pl3.grid), b3(kBlock);
-            // nontemporal accesses from the size on where the tensors cannot stay in L2 for the consumer anyway (PVHIP_STREAM_NT)
-            const int  ntm = settings().stream_nt;
-            const bool nt  = ntm == 2 || (ntm == 1 && (size_t)n * c * ((size_t)h * w + (size_t)oh * ow) * 4 >= ((size_t)64 << 20));
+            const bool nt = p.nt;
 #define PV_P3(ST_, STAGE_)                                                                                            \
     {                                                                                                                 \
         if (nt) hipLaunchKernelGGL((maxpool3x3_cols_kernel<ST_, STAGE_, true>), g3, b3, pl3.lds, state().stream, pl3.a, dv3);  \
         else    hipLaunchKernelGGL((maxpool3x3_cols_kernel<ST_, STAGE_, false>), g3, b3, pl3.lds, state().stream, pl3.a, dv3); \
     }
-            if (sh == 1) { if (pl3.stage) PV_P3(1, true) else PV_P3(1, false) }
-            else         { if (pl3.stage) PV_P3(2, true) else PV_P3(2, false) }
+            if (p.kind == PVHIP_MAXPOOL_COLS_S1) { if (pl3.stage) PV_P3(1, true) else PV_P3(1, false) }
+            else                                 { if (pl3.stage) PV_P3(2, true) else PV_P3(2, false) }
 #undef PV_P3
-            PVHIP_LAUNCH_CHECK();
-            return PVHIP_OK;
+            break;
         }
-    }
-    // LDS-staged path.  ~16 KB of LDS per workgroup (8-10 workgroups per CU overlap each other's load and
-    // compute phases; measured best on the GoogLeNet shapes): several whole planes per workgroup when planes
-    // are small, bands of output rows of one plane when a plane is larger than the budget.
-    const size_t group_bytes = (size_t)settings().pool_lds_kb * 1024;       // PVHIP_POOL_LDS_KB: tuning runs only
-    const size_t row_bytes   = (size_t)a.wp * sizeof(float);
-    const size_t plane_bytes = (size_t)a.hp * row_bytes;
-    const size_t min_band    = (size_t)(kh + sh) * row_bytes;       // at least two output rows per band
-    if (min_band <= 60 * 1024) {
-        const int planes = n * c;
-        int G = 1, band_rows = oh, n_bands = 1;
-        if (plane_bytes <= group_bytes) {
-            G = (int)(group_bytes / plane_bytes);
-            while (G > 4 && (planes + G - 1) / G < 8 * kNumCU) G >>= 1;
-            if ((h * w) % 4 != 0 && G >= 4) G &= ~3;     // every group starts 16-byte aligned in HBM
-            if (G > planes) G = planes;
-        } else if (plane_bytes > 60 * 1024 || plane_bytes > group_bytes) {
-            const size_t budget = plane_bytes <= group_bytes ? plane_bytes : (group_bytes > min_band ? group_bytes : min_band);
-            int rows_in = (int)(budget / row_bytes);                 // padded input rows per band
-            band_rows   = (rows_in - kh) / sh + 1;
-            if (band_rows < 1) band_rows = 1;
-            if (band_rows > oh) band_rows = oh;
-            n_bands = (oh + band_rows - 1) / band_rows;
-            band_rows = (oh + n_bands - 1) / n_bands;                // even out the bands
-            n_bands = (oh + band_rows - 1) / band_rows;
-        }
-        const int    rows_l = (n_bands == 1) ? a.hp : ((band_rows - 1) * sh + kh < a.hp ? (band_rows - 1) * sh + kh : a.hp);
-        const size_t lds    = (((size_t)G * rows_l * row_bytes) + 15) & ~(size_t)15;
-        if (lds > 64 * 1024 || n_bands > 65535) {
-            hipLaunchKernelGGL(maxpool2d_kernel, dim3(grid_for(total)), dim3(kBlock), 0, state().stream, x, y, a, total);
-            PVHIP_LAUNCH_CHECK();
-            return PVHIP_OK;
-        }
-        const dim3 grid((planes + G - 1) / G, n_bands);
-        const bool clip = ((oh - 1) * sh + kh > a.hp) || ((ow - 1) * sw + kw > a.wp);
-        PoolDivs dv{make_fastdiv((unsigned)(h * w)), make_fastdiv((unsigned)w), make_fastdiv((unsigned)(oh * ow)),
-                    make_fastdiv((unsigned)ow)};
+        case PVHIP_MAXPOOL_LDS:
+        case PVHIP_MAXPOOL_LDS_2X2:
+        case PVHIP_MAXPOOL_LDS_3X3: {
+            const dim3 grid((a.n_planes + p.G - 1) / p.G, p.n_bands);
+            PoolDivs dv{make_fastdiv((unsigned)(h * w)), make_fastdiv((unsigned)w), make_fastdiv((unsigned)(oh * ow)),
+                        make_fastdiv((unsigned)ow)};
 #define PV_POOL_LAUNCH(KH_, KW_)                                                                              \
     do {                                                                                                      \
-        if (clip)                                                                                             \
-            hipLaunchKernelGGL((maxpool2d_lds_kernel<KH_, KW_, true>), grid, dim3(kBlock), lds, state().stream, x, y, a, G, band_rows, dv);  \
+        if (p.clip)                                                                                           \
+            hipLaunchKernelGGL((maxpool2d_lds_kernel<KH_, KW_, true>), grid, dim3(kBlock), p.lds, state().stream, x, y, a, p.G, p.band_rows, dv);  \
         else                                                                                                  \
-            hipLaunchKernelGGL((maxpool2d_lds_kernel<KH_, KW_, false>), grid, dim3(kBlock), lds, state().stream, x, y, a, G, band_rows, dv); \
+            hipLaunchKernelGGL((maxpool2d_lds_kernel<KH_, KW_, false>), grid, dim3(kBlock), p.lds, state().stream, x, y, a, p.G, p.band_rows, dv); \
     } while (0)
-        if (kh == 3 && kw == 3) PV_POOL_LAUNCH(3, 3);
-        else if (kh == 2 && kw == 2) PV_POOL_LAUNCH(2, 2);
-        else PV_POOL_LAUNCH(0, 0);
+            if (p.kind == PVHIP_MAXPOOL_LDS_3X3) PV_POOL_LAUNCH(3, 3);
+            else if (p.kind == PVHIP_MAXPOOL_LDS_2X2) PV_POOL_LAUNCH(2, 2);
+            else PV_POOL_LAUNCH(0, 0);
 #undef PV_POOL_LAUNCH
-    } else {
-        hipLaunchKernelGGL(maxpool2d_kernel, dim3(grid_for(total)), dim3(kBlock), 0, state().stream, x, y, a, total);
+            break;
+        }
+        default:
+            hipLaunchKernelGGL(maxpool2d_kernel, dim3(grid_for(total)), dim3(kBlock), 0, state().stream, x, y, a, total);
     }
     PVHIP_LAUNCH_CHECK();
+    return PVHIP_OK;
+}
+
+int pvhip_maxpool2d_form(int n, int c, int h, int w, int oh, int ow, int kh, int kw, int sh, int sw, int pad_top, int pad_left,
+                         int pad_bottom, int pad_right, int* form) {
+    PVHIP_CHECK_ARG(form != nullptr);
+    clear_form(form);
+    int rc = check_pool_dims("pvhip_maxpool2d_form", n, c, h, w, oh, ow, kh, kw, sh, sw);
+    if (rc) return rc;
+    PVHIP_CHECK_ARG(pad_top >= 0 && pad_left >= 0 && pad_bottom >= 0 && pad_right >= 0);
+    if ((unsigned)n * c * oh * ow == 0) return PVHIP_OK;             // nothing is launched
+    PoolArgs a{n * c, h, w, oh, ow, kh, kw, sh, sw, pad_top, pad_left, h + pad_top + pad_bottom, w + pad_left + pad_right};
+    if ((oh - 1) * sh >= a.hp || (ow - 1) * sw >= a.wp)
+        return fail(PVHIP_EINVAL, "pvhip_maxpool2d_form: window starts outside the padded input");
+    const MaxPoolPlan p = plan_maxpool(nullptr, nullptr, a);
+    const bool cols = p.kind == PVHIP_MAXPOOL_COLS_S1 || p.kind == PVHIP_MAXPOOL_COLS_S2;
+    form[PVHIP_FORM_KIND] = p.kind;
+    if (p.kind == PVHIP_MAXPOOL_GLOBAL) return PVHIP_OK;
+    form[PVHIP_FORM_G] = p.G; form[PVHIP_FORM_BANDS] = p.n_bands; form[PVHIP_FORM_BAND_ROWS] = p.band_rows;
+    form[PVHIP_FORM_CLIP] = p.clip ? 1 : 0;
+    form[PVHIP_FORM_STAGE] = (cols && p.p3.stage) ? 1 : 0;
+    form[PVHIP_FORM_NT] = p.nt ? 1 : 0;
+    form[PVHIP_FORM_S] = cols ? p.p3.a.S : 0;
     return PVHIP_OK;
 }
 
@@ -909,21 +1073,30 @@ int pvhip_avgpool2d_f32(const float* x, float* y, int n, int c, int h, int w, in
     if (total == 0) return PVHIP_OK;
     PVHIP_CHECK_ARG(x != nullptr && y != nullptr);
     PoolArgs a{n * c, h, w, oh, ow, kh, kw, sh, sw, 0, 0, h, w};
-    const size_t plane_bytes = (size_t)h * w * sizeof(float);
-    if (plane_bytes <= 16 * 1024) {
-        const int planes = n * c;
-        int       G      = (int)(16 * 1024 / plane_bytes);
-        while (G > 4 && (planes + G - 1) / G < 8 * kNumCU) G >>= 1;
-        if ((h * w) % 4 != 0 && G >= 4) G &= ~3;
-        if (G > planes) G = planes;
-        const size_t lds = (((size_t)G * plane_bytes) + 15) & ~(size_t)15;
+    const AvgPoolPlan p = plan_avgpool(a);
+    if (p.kind == PVHIP_AVGPOOL_LDS) {
         PoolDivs dv{make_fastdiv((unsigned)(h * w)), make_fastdiv((unsigned)w), make_fastdiv((unsigned)(oh * ow)),
                     make_fastdiv((unsigned)ow)};
-        hipLaunchKernelGGL(avgpool2d_lds_kernel, dim3((planes + G - 1) / G), dim3(kBlock), lds, state().stream, x, y, a, G, dv);
+        hipLaunchKernelGGL(avgpool2d_lds_kernel, dim3((a.n_planes + p.G - 1) / p.G), dim3(kBlock), p.lds, state().stream, x, y, a, p.G, dv);
     } else {
         hipLaunchKernelGGL(avgpool2d_kernel, dim3(grid_for(total)), dim3(kBlock), 0, state().stream, x, y, a, total);
     }
     PVHIP_LAUNCH_CHECK();
+    return PVHIP_OK;
+}
+
+int pvhip_avgpool2d_form(int n, int c, int h, int w, int oh, int ow, int kh, int kw, int sh, int sw, int* form) {
+    PVHIP_CHECK_ARG(form != nullptr);
+    clear_form(form);
+    int rc = check_pool_dims("pvhip_avgpool2d_form", n, c, h, w, oh, ow, kh, kw, sh, sw);
+    if (rc) return rc;
+    if ((unsigned)n * c * oh * ow == 0) return PVHIP_OK;
+    PoolArgs a{n * c, h, w, oh, ow, kh, kw, sh, sw, 0, 0, h, w};
+    const AvgPoolPlan p = plan_avgpool(a);
+    form[PVHIP_FORM_KIND] = p.kind;
+    if (p.kind == PVHIP_AVGPOOL_GLOBAL) return PVHIP_OK;
+    form[PVHIP_FORM_G] = p.G; form[PVHIP_FORM_BANDS] = 1; form[PVHIP_FORM_BAND_ROWS] = oh;
+    form[PVHIP_FORM_VEC] = all_starts_aligned(h, w, p.G, a.n_planes, 1, oh, sh, 0);
     return PVHIP_OK;
 }
 
@@ -938,80 +1111,65 @@ int pvhip_dwconv2d_f32(const float* x, const float* w, float* y, int n, int g, i
     if (total == 0) return PVHIP_OK;
     PVHIP_CHECK_ARG(x != nullptr && w != nullptr && y != nullptr);
     DwEpilogue ep{bias, act, act_lo, act_hi};
-    // padded extents: everything the windows touch (cells past the tensor are zeros by definition)
-    int hp = (oh - 1) * sh + kh, wp = (ow - 1) * sw + kw;
-    if (hp < h + pad_top) hp = h + pad_top;
-    if (wp < wdt + pad_left) wp = wdt + pad_left;
-    // 3x3, stride 1 or 2: the pipelined kernel on the MaxPool kernel's tiles (PVHIP_DWCONV_COLS=0: the one-shot LDS kernel)
-    if (kh == 3 && kw == 3 && sh == sw && (sh == 1 || sh == 2) && settings().dwconv_cols) {
-        Pool3Plan plan;
-        // The lanes store their outputs themselves (PVHIP_DWCONV_COLS=2: through the MaxPool kernel's output stage in LDS, measured
-        // slower on every MobileNet layer: 1.32 against 1.16 ms over the 13 -- the stage costs LDS, i.e. halo rows and resident tiles).
-        // (bands of odd-width planes start on no boundary at all and ran 20 % slower than the one-shot kernel; MobileNet's 75x75
-        // planes fit whole)
-        const bool ok = plan_pool3(x, y, n * g, h, wdt, oh, ow, sh, pad_top, pad_left, hp, wp, plan, true, settings().dwconv_cols == 2 ? 1 : 0) &&
-                        !(plan.a.n_bands > 1 && (wdt & 1));
-        if (ok) {
+    const DwPlan p = plan_dwconv(x, y, n * g, h, wdt, kh, kw, oh, ow, sh, sw, pad_top, pad_left);
+    switch (p.kind) {
+        case PVHIP_DWCONV_COLS_S1:
+        case PVHIP_DWCONV_COLS_S2: {
+            const Pool3Plan& plan = p.p3;
             const Pool3Divs dv3{make_fastdiv((unsigned)plan.a.n_bands), make_fastdiv((unsigned)(plan.a.S * ow)), make_fastdiv((unsigned)ow)};
-            const int  ntm = settings().stream_nt;
-            const bool nt  = ntm == 2 || (ntm == 1 && (size_t)n * g * ((size_t)h * wdt + (size_t)oh * ow) * 4 >= ((size_t)64 << 20));
+            const bool nt = p.nt;
             const dim3 g3(plan.grid), b3(kBlock);
 #define PV_DW(ST_, NT_)                                                                                                       \
     {                                                                                                                         \
         if (plan.stage) hipLaunchKernelGGL((dwconv3x3_cols_kernel<ST_, NT_, true>), g3, b3, plan.lds, state().stream, plan.a, dv3, w, g, ep);  \
         else            hipLaunchKernelGGL((dwconv3x3_cols_kernel<ST_, NT_, false>), g3, b3, plan.lds, state().stream, plan.a, dv3, w, g, ep); \
     }
-            if (sh == 1) { if (nt) PV_DW(1, true) else PV_DW(1, false) }
-            else         { if (nt) PV_DW(2, true) else PV_DW(2, false) }
+            if (p.kind == PVHIP_DWCONV_COLS_S1) { if (nt) PV_DW(1, true) else PV_DW(1, false) }
+            else                                { if (nt) PV_DW(2, true) else PV_DW(2, false) }
 #undef PV_DW
-            PVHIP_LAUNCH_CHECK();
-            return PVHIP_OK;
+            break;
         }
-    }
-    PoolArgs a{n * g, h, wdt, oh, ow, kh, kw, sh, sw, pad_top, pad_left, hp, wp};
-    const size_t group_bytes = 16 * 1024;
-    const size_t row_bytes   = (size_t)wp * sizeof(float);
-    const size_t plane_bytes = (size_t)hp * row_bytes;
-    const size_t min_band    = (size_t)(kh + sh) * row_bytes;
-    bool         lds_ok      = min_band <= 48 * 1024;
-    int          G = 1, band_rows = oh, n_bands = 1;
-    if (lds_ok) {
-        const int planes = n * g;
-        if (plane_bytes <= group_bytes) {
-            G = (int)(group_bytes / plane_bytes);
-            while (G > 4 && (planes + G - 1) / G < 8 * kNumCU) G >>= 1;
-            if ((h * wdt) % 4 != 0 && G >= 4) G &= ~3;
-            if (G > planes) G = planes;
-        } else {
-            const size_t budget = group_bytes > min_band ? group_bytes : min_band;
-            const int    rows_in = (int)(budget / row_bytes);
-            band_rows = (rows_in - kh) / sh + 1;
-            if (band_rows < 1) band_rows = 1;
-            if (band_rows > oh) band_rows = oh;
-            n_bands   = (oh + band_rows - 1) / band_rows;
-            band_rows = (oh + n_bands - 1) / n_bands;
-            n_bands   = (oh + band_rows - 1) / band_rows;
-        }
-        const int    rows_l = (n_bands == 1) ? hp : ((band_rows - 1) * sh + kh < hp ? (band_rows - 1) * sh + kh : hp);
-        const size_t lds    = ((((size_t)G * rows_l * wp + 3) & ~(size_t)3) + (size_t)G * kh * kw) * sizeof(float);
-        if (lds > 64 * 1024 || n_bands > 65535) lds_ok = false;
-        if (lds_ok) {
-            const dim3 grid((planes + G - 1) / G, n_bands);
+        case PVHIP_DWCONV_LDS:
+        case PVHIP_DWCONV_LDS_3X3: {
+            PoolArgs a{n * g, h, wdt, oh, ow, kh, kw, sh, sw, pad_top, pad_left, p.hp, p.wp};
+            const dim3 grid((a.n_planes + p.G - 1) / p.G, p.n_bands);
             PoolDivs dv{make_fastdiv((unsigned)(h * wdt)), make_fastdiv((unsigned)wdt), make_fastdiv((unsigned)(oh * ow)),
                         make_fastdiv((unsigned)ow)};
-            if (kh == 3 && kw == 3)
-                hipLaunchKernelGGL((dwconv2d_lds_kernel<3, 3>), grid, dim3(kBlock), lds, state().stream, x, w, y, a, g, G,
-                                   band_rows, dv, ep);
+            if (p.kind == PVHIP_DWCONV_LDS_3X3)
+                hipLaunchKernelGGL((dwconv2d_lds_kernel<3, 3>), grid, dim3(kBlock), p.lds, state().stream, x, w, y, a, g, p.G,
+                                   p.band_rows, dv, ep);
             else
-                hipLaunchKernelGGL((dwconv2d_lds_kernel<0, 0>), grid, dim3(kBlock), lds, state().stream, x, w, y, a, g, G,
-                                   band_rows, dv, ep);
+                hipLaunchKernelGGL((dwconv2d_lds_kernel<0, 0>), grid, dim3(kBlock), p.lds, state().stream, x, w, y, a, g, p.G,
+                                   p.band_rows, dv, ep);
+            break;
+        }
+        default: {
+            DwArgs d{g, h, wdt, oh, ow, kh, kw, sh, sw, pad_top, pad_left};
+            hipLaunchKernelGGL(dwconv_kernel, dim3(grid_for((size_t)total)), dim3(kBlock), 0, state().stream, x, w, y, d, total, ep);
         }
     }
-    if (!lds_ok) {
-        DwArgs d{g, h, wdt, oh, ow, kh, kw, sh, sw, pad_top, pad_left};
-        hipLaunchKernelGGL(dwconv_kernel, dim3(grid_for((size_t)total)), dim3(kBlock), 0, state().stream, x, w, y, d, total, ep);
-    }
     PVHIP_LAUNCH_CHECK();
+    return PVHIP_OK;
+}
+
+int pvhip_dwconv2d_form(int n, int g, int h, int wdt, int kh, int kw, int oh, int ow, int sh, int sw, int pad_top, int pad_left,
+                        int* form) {
+    PVHIP_CHECK_ARG(form != nullptr);
+    clear_form(form);
+    int rc = check_pool_dims("pvhip_dwconv2d_form", n, g, h, wdt, oh, ow, kh, kw, sh, sw);
+    if (rc) return rc;
+    PVHIP_CHECK_ARG(pad_top >= 0 && pad_left >= 0);
+    if ((unsigned)n * g * oh * ow == 0) return PVHIP_OK;
+    const DwPlan p = plan_dwconv(nullptr, nullptr, n * g, h, wdt, kh, kw, oh, ow, sh, sw, pad_top, pad_left);
+    const bool cols = p.kind == PVHIP_DWCONV_COLS_S1 || p.kind == PVHIP_DWCONV_COLS_S2;
+    form[PVHIP_FORM_KIND] = p.kind;
+    if (p.kind == PVHIP_DWCONV_GLOBAL) return PVHIP_OK;
+    form[PVHIP_FORM_G] = p.G; form[PVHIP_FORM_BANDS] = p.n_bands; form[PVHIP_FORM_BAND_ROWS] = p.band_rows;
+    // (the column kernel copies from the 16-byte boundary below any start: it has one staging form)
+    form[PVHIP_FORM_VEC] = cols ? 1 : all_starts_aligned(h, wdt, p.G, n * g, p.n_bands, p.band_rows, sh, pad_top);
+    form[PVHIP_FORM_STAGE] = (cols && p.p3.stage) ? 1 : 0;
+    form[PVHIP_FORM_NT] = p.nt ? 1 : 0;
+    form[PVHIP_FORM_S] = cols ? p.p3.a.S : 0;
     return PVHIP_OK;
 }
 

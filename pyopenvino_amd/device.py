@@ -74,6 +74,11 @@ SIGNATURES = {
     'pvhip_avgpool2d_f32': (_c.c_int, [_fp, _fp] + [_c.c_int] * 10),
     'pvhip_softmax_rows_f32': (_c.c_int, [_fp, _fp, _c.c_int, _c.c_int]),
     'pvhip_lrn_f32': (_c.c_int, [_fp, _fp, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_float, _c.c_float, _c.c_float]),
+    'pvhip_maxpool2d_form': (_c.c_int, [_c.c_int] * 14 + [_c.POINTER(_c.c_int)]),
+    'pvhip_avgpool2d_form': (_c.c_int, [_c.c_int] * 10 + [_c.POINTER(_c.c_int)]),
+    'pvhip_dwconv2d_form': (_c.c_int, [_c.c_int] * 12 + [_c.POINTER(_c.c_int)]),
+    'pvhip_softmax_rows_form': (_c.c_int, [_c.c_int, _c.c_int, _c.POINTER(_c.c_int)]),
+    'pvhip_lrn_form': (_c.c_int, [_c.c_int] * 4 + [_c.c_float, _c.c_float, _c.POINTER(_c.c_int)]),
     'pvhip_lrn_maxpool_supported': (_c.c_int, [_c.c_int] * 5 + [_c.c_float, _c.c_float] + [_c.c_int] * 10),
     'pvhip_lrn_maxpool_f32': (_c.c_int, [_fp, _fp] + [_c.c_int] * 5 + [_c.c_float] * 3 + [_c.c_int] * 10),
     'pvhip_maxpool_lrn_supported': (_c.c_int, [_c.c_int] * 15 + [_c.c_float, _c.c_float]),
