@@ -34,7 +34,7 @@ extern "C" {
 #define PVHIP_ECOMM        -4   /* RCCL failure / library not loadable                        */
 #define PVHIP_EUNSUPPORTED -5   /* configuration outside what the kernels implement           */
 
-#define PVHIP_ABI_VERSION   17
+#define PVHIP_ABI_VERSION   18
 
 /* ---------------------------------------------------------------- runtime plumbing ---------- */
 /* No reference counterpart: the reference computes in host numpy arrays (inference_engine.py:245-256
@@ -264,6 +264,43 @@ int    pvhip_conv2d_f32(const float* x, const float* wpack, float* y,
 #define PVHIP_CONV_KIND_STEM_WINO    6   /* ABI v16: the same layer as Winograd F(3x3,4x4) on the space-to-depth image  */
 int    pvhip_conv2d_kernel_kind(int n, int c, int h, int w, int k_out, int kh, int kw, int oh, int ow,
                                 int sh, int sw, int pad_top, int pad_left);
+/* ABI v18.  Which kernel FORM inside its family a convolution launch takes: host-only like pvhip_conv2d_kernel_kind (no device needed, the
+ * PVHIP_* switches are honoured), answered by the SAME plan functions the launchers switch on (plan_pw, plan_tiles, plan_wino, plan_wino4).
+ * entry PVHIP_CONV_ENTRY_F32: what pvhip_conv2d_f32 launches for this geometry, and what pvhip_conv2d_multi_f32 launches on its pointwise
+ * route; PVHIP_CONV_ENTRY_F16_DMA: what pvhip_conv2d_f16_dma / pvhip_conv2d_multi_f16_dma launch.  For a multi-destination launch k_out is
+ * the panel width: the sum of the members' channel counts, each rounded up to 32.  Fills form[PVHIP_FORM_INTS] with the slots below (a set
+ * of its own: slots 2.. are read by family; unused slots are 0); PVHIP_CONV_FORM_KIND is PVHIP_FORM_NONE for an empty output (nothing is
+ * launched).  Returns PVHIP_OK, or what the entry would return for these arguments: PVHIP_EINVAL, PVHIP_EUNSUPPORTED (kh / kw >= 256, an
+ * input of 2^29 or an output of 2^31 elements and more, a window of 64 taps and more on the f16 entry).
+ * Not reported: the stem entries (pvhip_conv2d_stem_*, pvhip_conv2d_f16_stem*), the span / c8 / c8-multi readers, the MaxPool + 1x1
+ * launches, the fp32 multi launch with PVHIP_CONV_POINTWISE=0 (PVHIP_CONV_MULTI_BM), and the diagnostic build's overrides and ablations. */
+#define PVHIP_CONV_ENTRY_F32             0
+#define PVHIP_CONV_ENTRY_F16_DMA         1
+#define PVHIP_CONV_FORM_KIND             0   /* every family: PVHIP_CONV_KIND_* (the f16 entry: PVHIP_CONV_KIND_IGEMM)                   */
+#define PVHIP_CONV_FORM_GRID             1   /* every family: workgroups launched                                                        */
+#define PVHIP_CONV_FORM_PW_TN            2   /* pointwise: 32-channel tiles per workgroup (1, 2; 4 under PVHIP_PW_TN)                     */
+#define PVHIP_CONV_FORM_PW_VEC           3   /* pointwise: 1 = 16-byte copies (h * w a multiple of 4), 0 = dword copies                  */
+#define PVHIP_CONV_FORM_PW_NCHUNK        4   /* pointwise: groups of tn channel tiles                                                    */
+#define PVHIP_CONV_FORM_PW_STAGGER       5   /* pointwise: 1 when the workgroups start staggered (PVHIP_PW_STAGGER, large grids only)    */
+#define PVHIP_CONV_FORM_IGEMM_BM         2   /* implicit GEMM: output channels per tile (fp32: 32 / 64; f16: 32 / 64 / 128)              */
+#define PVHIP_CONV_FORM_IGEMM_KERNEL     3   /* implicit GEMM: PVHIP_IGEMM_* below                                                       */
+#define PVHIP_CONV_FORM_IGEMM_N_MTILES   4   /* implicit GEMM: channel tiles (GRID = N_MTILES x ceil(pixels / 128))                      */
+#define PVHIP_CONV_FORM_WINO_KB          2   /* F(2x2,3x3): output channels per workgroup (64 / 32)                                      */
+#define PVHIP_CONV_FORM_WINO_PATCHES     3   /* F(2x2,3x3): patches per workgroup (32 / 64)                                              */
+#define PVHIP_CONV_FORM_WINO_WAVES       4   /* F(2x2,3x3): waves per workgroup (4 / 8)                                                  */
+#define PVHIP_CONV_FORM_WINO4_M          2   /* six-point: 4 = F(4x4,3x3), 2 = F(2x2,5x5)                                                */
+#define PVHIP_CONV_FORM_WINO4_RAGGED     3   /* six-point: an extent is no multiple of m (the RAGGED instantiation)                      */
+#define PVHIP_CONV_FORM_WINO4_SHARED     4   /* six-point: 1 = conv_wino4s_kernel (shared V), 0 = conv_wino4_kernel (persistent)         */
+#define PVHIP_CONV_FORM_WINO4_ORDER      5   /* six-point: s_order (1: channel-pair-major tile order of the shared-V form)                */
+#define PVHIP_CONV_FORM_WINO4_TILES      6   /* six-point: n_tiles (persistent: patch blocks x channel blocks; shared V: x block pairs)   */
+#define PVHIP_CONV_FORM_WINO4_WALK       7   /* six-point: 1 when n_tiles exceeds the grid: a workgroup takes more than one tile         */
+#define PVHIP_IGEMM_REGISTER             0   /* conv_igemm_kernel: register-staged, windows of 64 taps and more (fp32 only)              */
+#define PVHIP_IGEMM_POINTWISE_COPY       1   /* conv_igemm_dma_kernel<.., kPW>: 1x1 / stride 1 / unpadded, whole pixel quads             */
+#define PVHIP_IGEMM_RS_MAJOR             2   /* ... (r,s)-major reduction (C a multiple of 16)                                           */
+#define PVHIP_IGEMM_C_MAJOR_VALID        3   /* ... c-major, no window leaves the tensor: no window test                                 */
+#define PVHIP_IGEMM_C_MAJOR_WINDOW       4   /* ... c-major with the window test                                                         */
+int    pvhip_conv2d_form(int entry, int n, int c, int h, int w, int k_out, int kh, int kw, int oh, int ow,
+                         int sh, int sw, int pad_top, int pad_left, int* form);
 /* MaxPool.py:41-72 (3x3 window, stride 1, pad 1 all round: output extent = input extent) followed by a 1x1 / stride 1 / unpadded
  * Convolution.py:57-87, as one launch: y = conv1x1(maxpool(x)); the pooled tensor is never written.  Bit-identical to
  * pvhip_maxpool2d_f32 followed by pvhip_conv2d_f32.  x is (n, c, h, w); wpack the pvhip_conv2d_pack_f32 panel of the (k_out, c, 1, 1)

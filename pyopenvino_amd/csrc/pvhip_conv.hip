@@ -403,58 +403,96 @@ void conv_args(ConvArgs& a, const ConvPanel& p, const float* x, const float* wpa
     a.y_ctotal = y_ctotal; a.y_coff = y_coff;
 }
 
+// What a launch of the implicit-GEMM kernels takes, decided HERE and nowhere else: the launchers below switch on the plan,
+// pvhip_conv2d_form reports it.  kernel: PVHIP_IGEMM_* (include/pvhip.h).
+struct IgemmPlan {
+    int bm, kernel, n_mtiles, n_ptiles;
+};
+
 // The forms of conv_igemm_dma_kernel.  Pointwise (1x1, stride 1, unpadded, whole pixel quads; PVHIP_CONV_NOPW: tuning): the tile is a plain copy
-inline bool dma_pointwise(const ConvArgs& a) {
-    return rs_major(a.C, a.kh, a.kw) && a.kh == 1 && a.kw == 1 && a.sh == 1 && a.sw == 1 && a.pt == 0 && a.pl == 0 && a.OH == a.H &&
-           a.OW == a.W && (a.H * a.W) % 4 == 0 && !settings().conv_nopw;
+inline bool dma_pointwise(int c, int h, int w, int kh, int kw, int oh, int ow, int sh, int sw, int pt, int pl) {
+    return rs_major(c, kh, kw) && kh == 1 && kw == 1 && sh == 1 && sw == 1 && pt == 0 && pl == 0 && oh == h &&
+           ow == w && (h * w) % 4 == 0 && !settings().conv_nopw;
 }
 // c-major without a window test: no padding and no window leaves the tensor (PVHIP_CONV_NOVALID: A/B)
-inline bool dma_valid(const ConvArgs& a) {
-    return a.pt == 0 && a.pl == 0 && (a.OH - 1) * a.sh + a.kh <= a.H && (a.OW - 1) * a.sw + a.kw <= a.W && !settings().conv_novalid;
+inline bool dma_valid(int h, int w, int kh, int kw, int oh, int ow, int sh, int sw, int pt, int pl) {
+    return pt == 0 && pl == 0 && (oh - 1) * sh + kh <= h && (ow - 1) * sw + kw <= w && !settings().conv_novalid;
 }
 
-// Every launch of conv_igemm_dma_kernel: the form follows from the arguments, BM x 128 tiles, a.n_mtiles x n_ptiles workgroups.
+// A launch on bm x 128 tiles: conv_igemm_dma_kernel in the form that follows from the geometry (every window of fewer than 64 taps), else
+// the register-staged conv_igemm_kernel with a compare per gathered element instead of the window-bit mask.
+IgemmPlan plan_tiles(int bm, int p_pixels, int c, int h, int w, int k, int kh, int kw, int oh, int ow, int sh, int sw, int pt, int pl) {
+    IgemmPlan p;
+    p.bm       = bm;
+    p.n_mtiles = (k + bm - 1) / bm;
+    p.n_ptiles = (p_pixels + 127) / 128;
+    if (!(dma_enabled() && dma_takes(kh, kw))) p.kernel = PVHIP_IGEMM_REGISTER;
+    else if (dma_pointwise(c, h, w, kh, kw, oh, ow, sh, sw, pt, pl)) p.kernel = PVHIP_IGEMM_POINTWISE_COPY;
+    else if (rs_major(c, kh, kw)) p.kernel = PVHIP_IGEMM_RS_MAJOR;
+    else if (dma_valid(h, w, kh, kw, oh, ow, sh, sw, pt, pl)) p.kernel = PVHIP_IGEMM_C_MAJOR_VALID;
+    else p.kernel = PVHIP_IGEMM_C_MAJOR_WINDOW;
+    return p;
+}
+inline IgemmPlan plan_tiles(int bm, const ConvArgs& a) {
+    return plan_tiles(bm, a.P, a.C, a.H, a.W, a.K, a.kh, a.kw, a.OH, a.OW, a.sh, a.sw, a.pt, a.pl);
+}
+
+// PVHIP_CONV_KIND_IGEMM, fp32.  Tiles (calibrated with scripts/tune_conv.py on the GoogLeNet shapes at batch 256): 128 pixels; 64 output
+// channels when that wastes less than half a tile and still leaves >= 4 workgroups per CU, else 32.
+int igemm_bm(int p_pixels, int k, int kh, int kw) {
+    int bm = (k % 64 == 0 || k % 64 > 32) ? 64 : 32;
+    if (bm == 64 && (long)((p_pixels + 127) / 128) * ((k + 63) / 64) < 4 * kNumCU) bm = 32;
+    if (kh == 1 && kw == 1) bm = 32;      // 1x1 layers: the smaller tile wins on every GoogLeNet shape (more workgroups per CU)
+    return bm;
+}
+
+// The f16 form (pvhip_conv2d_f16_dma, pvhip_conv2d_multi_f16_dma): the activation tile of a stage is re-read once per channel tile (through
+// L2, which is what this form is bound by): wide tiles.  PVHIP_CONV_F16_BM: tuning runs
+int f16_bm(int k) { return settings().f16_bm ? settings().f16_bm : (k > 64 ? 128 : (k > 32 ? 64 : 32)); }
+
+// Every launch of conv_igemm_dma_kernel: BM x 128 tiles, p.n_mtiles x p.n_ptiles workgroups, the form the plan names.
 // (PVHIP_CONV_LDS_PAD_KB: tuning, extra dynamic LDS caps the workgroups per CU.)
 template <int BM, bool kF16>
-int launch_dma(const ConvArgs& a, int n_ptiles) {
-    const dim3   grid(a.n_mtiles * n_ptiles), block(kBlock);
+int launch_dma(const IgemmPlan& p, const ConvArgs& a) {
+    const dim3   grid(p.n_mtiles * p.n_ptiles), block(kBlock);
     const size_t dyn = (size_t)settings().conv_lds_pad_kb * 1024;
-    if (dma_pointwise(a))
+    switch (p.kernel) {
+    case PVHIP_IGEMM_POINTWISE_COPY:
         hipLaunchKernelGGL((conv_igemm_dma_kernel<BM, true, true, false, kF16>), grid, block, dyn, state().stream, a);
-    else if (rs_major(a.C, a.kh, a.kw))
+        return PVHIP_OK;
+    case PVHIP_IGEMM_RS_MAJOR:
         hipLaunchKernelGGL((conv_igemm_dma_kernel<BM, true, false, false, kF16>), grid, block, dyn, state().stream, a);
-    else if constexpr (BM == 128 && !kF16 && !kDiagBuild)      // no fp32 route picks the widest tile for a c-major layer (PVHIP_CONV_TILE does)
+        return PVHIP_OK;
+    default: break;
+    }
+    if constexpr (BM == 128 && !kF16 && !kDiagBuild)      // no fp32 route picks the widest tile for a c-major layer (PVHIP_CONV_TILE does)
         return fail(PVHIP_EUNSUPPORTED, "conv_igemm_dma_kernel: no 128-channel tile for C=%d (not a multiple of %d)", a.C, kBK);
-    else if (dma_valid(a))
+    else if (p.kernel == PVHIP_IGEMM_C_MAJOR_VALID)
         hipLaunchKernelGGL((conv_igemm_dma_kernel<BM, false, false, true, kF16>), grid, block, dyn, state().stream, a);
     else
         hipLaunchKernelGGL((conv_igemm_dma_kernel<BM, false, false, false, kF16>), grid, block, dyn, state().stream, a);
     return PVHIP_OK;
 }
 
+// A launch by its plan: the LDS-DMA kernel, or (fp32, windows of 64 taps and more) the register-staged one.
 template <bool kF16>
-int launch_dma_bm(int bm, ConvArgs& a) {
-    a.n_mtiles = (a.K + bm - 1) / bm;
-    const int n_ptiles = (a.P + 127) / 128;
-    return bm == 128 ? launch_dma<128, kF16>(a, n_ptiles) : bm == 64 ? launch_dma<64, kF16>(a, n_ptiles) : launch_dma<32, kF16>(a, n_ptiles);
-}
-
-// PVHIP_CONV_KIND_IGEMM.  Tiles (calibrated with scripts/tune_conv.py on the GoogLeNet shapes at batch 256): 128 pixels; 64 output
-// channels when that wastes less than half a tile and still leaves >= 4 workgroups per CU, else 32.
-int launch_igemm(ConvArgs& a) {
-    int bm = (a.K % 64 == 0 || a.K % 64 > 32) ? 64 : 32, bn = 128;
-    if (bm == 64 && (long)((a.P + 127) / 128) * ((a.K + 63) / 64) < 4 * kNumCU) bm = 32;
-    if (a.kh == 1 && a.kw == 1) bm = 32;      // 1x1 layers: the smaller tile wins on every GoogLeNet shape (more workgroups per CU)
-#ifdef PVHIP_DIAG
-    if (int rc; diag_conv_override(a, &bm, &bn, &rc)) return rc;      // pvhip_diag_conv.hip
-#endif
-    if (dma_enabled() && dma_takes(a.kh, a.kw)) return launch_dma_bm<false>(bm, a);
-    // windows of 64 taps and more: the register-staged kernel with a compare per gathered element instead of the window-bit mask
-    a.n_mtiles = (a.K + bm - 1) / bm;
-    const dim3 grid(a.n_mtiles * ((a.P + bn - 1) / bn)), block(kBlock);
-    if (bm == 64) hipLaunchKernelGGL((conv_igemm_kernel<64, 128, 1, 4, false>), grid, block, 0, state().stream, a);
+int launch_plan(const IgemmPlan& p, ConvArgs& a) {
+    a.n_mtiles = p.n_mtiles;
+    if (p.kernel != PVHIP_IGEMM_REGISTER)
+        return p.bm == 128 ? launch_dma<128, kF16>(p, a) : p.bm == 64 ? launch_dma<64, kF16>(p, a) : launch_dma<32, kF16>(p, a);
+    const dim3 grid(p.n_mtiles * p.n_ptiles), block(kBlock);
+    if (p.bm == 64) hipLaunchKernelGGL((conv_igemm_kernel<64, 128, 1, 4, false>), grid, block, 0, state().stream, a);
     else hipLaunchKernelGGL((conv_igemm_kernel<32, 128, 1, 4, false>), grid, block, 0, state().stream, a);
     return PVHIP_OK;
+}
+
+int launch_igemm(ConvArgs& a) {
+    int bm = igemm_bm(a.P, a.K, a.kh, a.kw);
+#ifdef PVHIP_DIAG
+    int bn = 128;
+    if (int rc; diag_conv_override(a, &bm, &bn, &rc)) return rc;      // pvhip_diag_conv.hip
+#endif
+    return launch_plan<false>(plan_tiles(bm, a), a);
 }
 
 }  // namespace
@@ -518,8 +556,7 @@ static int conv2d_impl(const float* x, const float* wpack, float* y, int n, int 
     if (f16) {      // pvhip_conv2d_f16_dma: every layer on the LDS-DMA kernel's f16 form (the matrix work is 16x cheaper: no Winograd, wide tiles)
         if (!dma_takes(kh, kw) || !dma_enabled())
             return fail(PVHIP_EUNSUPPORTED, "pvhip_conv2d_f16_dma: C %% 16 == 0 or a window of fewer than 64 taps required (C=%d, %dx%d)", c, kh, kw);
-        // the activation tile of a stage is re-read once per channel tile (through L2, which is what this form is bound by): wide tiles
-        rc = launch_dma_bm<true>(settings().f16_bm ? settings().f16_bm : (k_out > 64 ? 128 : (k_out > 32 ? 64 : 32)), a);      // PVHIP_CONV_F16_BM: tuning runs
+        rc = launch_plan<true>(plan_tiles(f16_bm(k_out), a), a);
     } else {
         switch (conv_route(n, c, h, w, kh, kw, oh, ow, sh, sw, pad_top, pad_left)) {
         case PVHIP_CONV_KIND_POINTWISE: {      // pvhip_pw.hip
@@ -568,6 +605,73 @@ int pvhip_conv2d_kernel_kind(int n, int c, int h, int w, int k_out, int kh, int 
         return (settings().conv_stem_wino && pvhip_conv2d_stem_wino_supported(c, h, w, k_out, kh, kw, sh, sw, pad_top, pad_left, oh, ow) > 0)
                    ? PVHIP_CONV_KIND_STEM_WINO : PVHIP_CONV_KIND_STEM;
     return conv_route(n, c, h, w, kh, kw, oh, ow, sh, sw, pad_top, pad_left);
+}
+
+int pvhip_conv2d_form(int entry, int n, int c, int h, int w, int k_out, int kh, int kw, int oh, int ow, int sh, int sw, int pad_top,
+                      int pad_left, int* form) {
+    PVHIP_CHECK_ARG(form != nullptr);
+    for (int i = 0; i < PVHIP_FORM_INTS; ++i) form[i] = 0;
+    form[PVHIP_CONV_FORM_KIND] = PVHIP_FORM_NONE;
+    PVHIP_CHECK_ARG(entry == PVHIP_CONV_ENTRY_F32 || entry == PVHIP_CONV_ENTRY_F16_DMA);
+    PVHIP_CHECK_ARG(n >= 0 && c > 0 && h > 0 && w > 0 && k_out > 0 && kh > 0 && kw > 0 && oh >= 0 && ow >= 0);
+    PVHIP_CHECK_ARG(sh > 0 && sw > 0 && pad_top >= 0 && pad_left >= 0);
+    if (kh >= 256 || kw >= 256)
+        return fail(PVHIP_EUNSUPPORTED, "pvhip_conv2d_form: kh=%d kw=%d outside table encoding", kh, kw);
+    const unsigned long long in_e = (unsigned long long)n * c * h * w, out_e = (unsigned long long)n * k_out * oh * ow;
+    if (in_e >= (1ull << 29) || out_e >= (1ull << 31))
+        return fail(PVHIP_EUNSUPPORTED, "pvhip_conv2d_form: input exceeds 2^29 elements (buffer offsets below 2^31) or output 2^31");
+    if (out_e == 0) return PVHIP_OK;                                 // nothing is launched
+    const int pixels = n * oh * ow;
+    int kind = PVHIP_CONV_KIND_IGEMM;
+    if (entry == PVHIP_CONV_ENTRY_F16_DMA) {
+        if (!dma_takes(kh, kw) || !dma_enabled())
+            return fail(PVHIP_EUNSUPPORTED, "pvhip_conv2d_form: the f16 LDS-DMA entry takes windows of fewer than 64 taps (%dx%d)", kh, kw);
+    } else {
+        kind = conv_route(n, c, h, w, kh, kw, oh, ow, sh, sw, pad_top, pad_left);
+    }
+    switch (kind) {
+    case PVHIP_CONV_KIND_POINTWISE: {
+        const PwPlan p = plan_pw(n, c, h * w, k_out);
+        form[PVHIP_CONV_FORM_GRID]       = p.grid;
+        form[PVHIP_CONV_FORM_PW_TN]      = p.tn;
+        form[PVHIP_CONV_FORM_PW_VEC]     = p.vec ? 1 : 0;
+        form[PVHIP_CONV_FORM_PW_NCHUNK]  = p.nchunk;
+        form[PVHIP_CONV_FORM_PW_STAGGER] = p.stagger != 0 ? 1 : 0;
+        break;
+    }
+    case PVHIP_CONV_KIND_WINO_F2_3X3: {
+        const WinoPlan p = plan_wino(n, h, w, k_out);
+        if (p.grid > 0x7fffffffL) return fail(PVHIP_EUNSUPPORTED, "pvhip_conv2d_form: grid too large");
+        form[PVHIP_CONV_FORM_GRID]         = (int)p.grid;
+        form[PVHIP_CONV_FORM_WINO_KB]      = p.kb;
+        form[PVHIP_CONV_FORM_WINO_PATCHES] = p.nt;
+        form[PVHIP_CONV_FORM_WINO_WAVES]   = p.waves;
+        break;
+    }
+    case PVHIP_CONV_KIND_WINO_F4_3X3:
+    case PVHIP_CONV_KIND_WINO_F2_5X5: {
+        const Wino4Plan p = plan_wino4(kind == PVHIP_CONV_KIND_WINO_F4_3X3 ? 4 : 2, n, c, h, w, k_out);
+        if (p.tiles_max > 0x3fffffffL) return fail(PVHIP_EUNSUPPORTED, "pvhip_conv2d_form: too many tiles");
+        form[PVHIP_CONV_FORM_GRID]         = p.grid;
+        form[PVHIP_CONV_FORM_WINO4_M]      = p.m;
+        form[PVHIP_CONV_FORM_WINO4_RAGGED] = p.ragged ? 1 : 0;
+        form[PVHIP_CONV_FORM_WINO4_SHARED] = p.shared ? 1 : 0;
+        form[PVHIP_CONV_FORM_WINO4_ORDER]  = p.s_order;
+        form[PVHIP_CONV_FORM_WINO4_TILES]  = p.n_tiles;
+        form[PVHIP_CONV_FORM_WINO4_WALK]   = p.walk ? 1 : 0;
+        break;
+    }
+    default: {
+        const int bm = entry == PVHIP_CONV_ENTRY_F16_DMA ? f16_bm(k_out) : igemm_bm(pixels, k_out, kh, kw);
+        const IgemmPlan p = plan_tiles(bm, pixels, c, h, w, k_out, kh, kw, oh, ow, sh, sw, pad_top, pad_left);
+        form[PVHIP_CONV_FORM_GRID]           = p.n_mtiles * p.n_ptiles;
+        form[PVHIP_CONV_FORM_IGEMM_BM]       = p.bm;
+        form[PVHIP_CONV_FORM_IGEMM_KERNEL]   = p.kernel;
+        form[PVHIP_CONV_FORM_IGEMM_N_MTILES] = p.n_mtiles;
+    }
+    }
+    form[PVHIP_CONV_FORM_KIND] = kind;
+    return PVHIP_OK;
 }
 
 int pvhip_conv2d_multi_supported(int c, int kh, int kw, int sh, int sw, int pad_top, int pad_left, int n_dest) {
@@ -619,8 +723,8 @@ static int conv2d_multi_impl(const float* x, const float* wpack, int n, int c, i
                   act, act_lo, act_hi);
         a.nseg = n_dest;
         // a 64-channel tile may straddle two ranges: the epilogue looks the range up per 32 channels.  f16: wide tiles, the input tile is re-read per channel tile
-        if (f16) rc = launch_dma_bm<true>(settings().f16_bm ? settings().f16_bm : (k_panel > 64 ? 128 : (k_panel > 32 ? 64 : 32)), a);
-        else     rc = launch_dma_bm<false>(settings().multi_bm, a);          // PVHIP_CONV_MULTI_BM: tuning runs only
+        if (f16) rc = launch_plan<true>(plan_tiles(f16_bm(k_panel), a), a);
+        else     rc = launch_plan<false>(plan_tiles(settings().multi_bm, a), a);          // PVHIP_CONV_MULTI_BM: tuning runs only
     }
     if (rc) return rc;
     PVHIP_LAUNCH_CHECK();

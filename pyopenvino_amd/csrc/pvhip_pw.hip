@@ -407,36 +407,48 @@ int pw_pack(const float* w_oihw, float* ap, int k, int c) {
     return PVHIP_OK;
 }
 
+// Channel tiles per workgroup.  Measured on the GoogLeNet shapes at batch 256 (scripts/time_pw.py): two (64 pixels per wave,
+// 6 waves per SIMD by registers) beats four (128 pixels per wave, 4 waves per SIMD) on every panel -- more, smaller
+// workgroups interleave their first loads and their stores with each other's MFMAs -- and one (32 pixels per wave) wins
+// where two would leave the chip short of workgroups, or leave half a workgroup idle (odd T) on a small layer.
+PwPlan plan_pw(int n, int c, int hw, int k_panel) {
+    PwPlan p;
+    const int P = n * hw;
+    p.S = c / kBK; p.T = (k_panel + 31) / 32;
+    const long ptiles = (P + 127) / 128;
+    const long grid2  = ptiles * ((p.T + 1) / 2);
+    int tn = 2;
+    if (p.T == 1 || grid2 < 4L * kNumCU || ((p.T & 1) && grid2 < 16L * kNumCU)) tn = 1;
+    if (settings().pw_tn == 4 && p.T >= 3) tn = 4;      // PVHIP_PW_TN: tuning runs only
+    if (settings().pw_tn == 2 && p.T >= 2) tn = 2;
+    if (settings().pw_tn == 1) tn = 1;
+    p.tn = tn;
+    p.nchunk = (p.T + tn - 1) / tn;
+    // tile time of a four-tile workgroup sharing its SIMDs with three others: S stages x 32 MFMAs x 64 cycles x 4 at ~2.1 GHz;
+    // the four workgroups of a CU start a quarter of that apart (PVHIP_PW_STAGGER: percent of that quarter, tuning runs)
+    p.stagger = 0;
+    if (ptiles * p.nchunk > 8L * kNumCU)
+        p.stagger = (int)((double)p.S * 32.0 * 64.0 * 4.0 / 2100.0 * 100.0 / 4.0 * settings().pw_stagger_pct / 100.0);
+    p.grid = (int)ptiles * p.nchunk;
+    p.vec  = hw % 4 == 0;
+    return p;
+}
+
 int pw_conv(const float* x, const float* ap, int n, int c, int hw, int k_panel, const float* bias, int act, float act_lo, float act_hi,
             int ndest, const PwDest* dests) {
+    const PwPlan p = plan_pw(n, c, hw, k_panel);
     PwArgs a;
     a.x = x; a.ap = ap; a.bias = bias;
-    a.C = c; a.HW = hw; a.P = n * hw; a.S = c / kBK; a.T = (k_panel + 31) / 32;
+    a.C = c; a.HW = hw; a.P = n * hw; a.S = p.S; a.T = p.T;
     a.x_bytes = (unsigned)((unsigned long long)n * c * hw * 4ull);
     a.act = act; a.lo = act_lo; a.hi = act_hi;
     a.nseg = ndest;
     for (int i = 0; i < ndest; ++i) a.seg[i] = dests[i];
-    // Channel tiles per workgroup.  Measured on the GoogLeNet shapes at batch 256 (scripts/time_pw.py): two (64 pixels per wave,
-    // 6 waves per SIMD by registers) beats four (128 pixels per wave, 4 waves per SIMD) on every panel -- more, smaller
-    // workgroups interleave their first loads and their stores with each other's MFMAs -- and one (32 pixels per wave) wins
-    // where two would leave the chip short of workgroups, or leave half a workgroup idle (odd T) on a small layer.
-    const long ptiles = (a.P + 127) / 128;
-    const long grid2  = ptiles * ((a.T + 1) / 2);
-    int tn = 2;
-    if (a.T == 1 || grid2 < 4L * kNumCU || ((a.T & 1) && grid2 < 16L * kNumCU)) tn = 1;
-    if (settings().pw_tn == 4 && a.T >= 3) tn = 4;      // PVHIP_PW_TN: tuning runs only
-    if (settings().pw_tn == 2 && a.T >= 2) tn = 2;
-    if (settings().pw_tn == 1) tn = 1;
-    a.nchunk = (a.T + tn - 1) / tn;
-    // tile time of a four-tile workgroup sharing its SIMDs with three others: S stages x 32 MFMAs x 64 cycles x 4 at ~2.1 GHz;
-    // the four workgroups of a CU start a quarter of that apart (PVHIP_PW_STAGGER: percent of that quarter, tuning runs)
-    a.stagger = 0;
-    if ((long)((a.P + 127) / 128) * a.nchunk > 8L * kNumCU)
-        a.stagger = (int)((double)a.S * 32.0 * 64.0 * 4.0 / 2100.0 * 100.0 / 4.0 * settings().pw_stagger_pct / 100.0);
-    const int grid = ((a.P + 127) / 128) * a.nchunk;
-    if (tn == 4) launch_pw<4>(a, hw % 4 == 0, grid);
-    else if (tn == 2) launch_pw<2>(a, hw % 4 == 0, grid);
-    else launch_pw<1>(a, hw % 4 == 0, grid);
+    a.nchunk  = p.nchunk;
+    a.stagger = p.stagger;
+    if (p.tn == 4) launch_pw<4>(a, p.vec, p.grid);
+    else if (p.tn == 2) launch_pw<2>(a, p.vec, p.grid);
+    else launch_pw<1>(a, p.vec, p.grid);
     return PVHIP_OK;
 }
 

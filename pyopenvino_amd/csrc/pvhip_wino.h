@@ -36,4 +36,26 @@ int    pw_pack(const float* w_oihw, float* ap, int k, int c);
 int    pw_conv(const float* x, const float* ap, int n, int c, int hw, int k_panel, const float* bias, int act, float act_lo, float act_hi,
                int ndest, const PwDest* dests);
 
+// What each launcher above launches, decided in ONE plan function per launcher that reads no pointer: the launcher switches on the plan
+// and on nothing else, pvhip_conv2d_form (no device needed) reports it.
+struct PwPlan {
+    int  T, S, tn, nchunk, stagger, grid;     // 32-channel tiles, 16-channel stages, channel tiles per workgroup, chunks of them, start lag, workgroups
+    bool vec;                                 // 16-byte copies (hw % 4 == 0), else dword copies
+};
+PwPlan plan_pw(int n, int c, int hw, int k_panel);
+
+struct WinoPlan {           // F(2x2, 3x3)
+    int  kb, nt, waves, n_kb;                 // output channels / patches per workgroup, waves (4 / 8), channel blocks
+    bool small;                               // the 32 x 32 four-wave form
+    long grid;                                // workgroups (the launcher refuses more than 2^31 - 1)
+};
+WinoPlan plan_wino(int n, int h, int w, int k_out);
+
+struct Wino4Plan {          // the six-point kernels: F(4x4, 3x3) (m = 4) and F(2x2, 5x5) (m = 2)
+    int  m, n_kb, n_stages, s_order, n_tiles, grid;
+    long tiles_max;                           // patch blocks x channel blocks (the launcher refuses more than 2^30 - 1)
+    bool ragged, shared, walk;                // extents no multiple of m; conv_wino4s_kernel (shared V), else conv_wino4_kernel; n_tiles > grid
+};
+Wino4Plan plan_wino4(int m, int n, int c, int h, int w, int k_out);
+
 }  // namespace pvhip

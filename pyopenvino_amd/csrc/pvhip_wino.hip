@@ -1715,15 +1715,29 @@ int wino_pack(const float* w_oihw, float* u, int k, int c) {
     return PVHIP_OK;
 }
 
+// 32-channel blocks run as 32 channels x 32 patches on four waves (more, smaller workgroups: the layers whose K is not
+// made of 64-channel blocks are the small 14x14 ones); PVHIP_WINO_SMALL=0 selects 32 x 64 on eight waves (tuning runs)
+WinoPlan plan_wino(int n, int h, int w, int k_out) {
+    WinoPlan p;
+    p.kb    = wino_kb(k_out);
+    p.n_kb  = (k_out + p.kb - 1) / p.kb;
+    p.small = p.kb == 32 && settings().wino_small;
+    p.nt    = (p.kb == 64 || p.small) ? 32 : 64;
+    const long T = (long)n * ((h + 1) / 2) * ((w + 1) / 2);
+    p.grid  = (T + p.nt - 1) / p.nt * p.n_kb;
+    p.waves = p.small ? 4 : (settings().wino_waves == 8 ? 8 : 4);         // PVHIP_WINO_WAVES: tuning runs only
+    return p;
+}
+
 int wino_conv(const float* x, const float* u, float* y, int n, int c, int h, int w, int k_out, const float* bias, int act,
               float act_lo, float act_hi, int out_channel_offset, int out_channels_total) {
-    const int kb = wino_kb(k_out);
+    const WinoPlan p = plan_wino(n, h, w, k_out);
     WinoArgs a;
     a.x = x; a.u = u; a.y = y; a.bias = bias;
     a.N = n; a.C = c; a.H = h; a.W = w; a.K = k_out;
     a.TY = (h + 1) / 2; a.TX = (w + 1) / 2;
     a.T  = n * a.TY * a.TX;
-    a.n_kb = (k_out + kb - 1) / kb;
+    a.n_kb = p.n_kb;
     a.n_stages = c / kCB;
     a.x_bytes = (unsigned)((size_t)n * c * h * w * 4);
     a.u_bytes = (unsigned)(wino_pack_elems(k_out, c) * 4);
@@ -1734,18 +1748,12 @@ int wino_conv(const float* x, const float* u, float* y, int n, int c, int h, int
 #ifdef PVHIP_DIAG
     if (settings().wino4_ablate == 5) a.balance = 5;          // diagnostic build: s_memtime stamps (scripts/stamps_wino.py)
 #endif
-    // 32-channel blocks run as 32 channels x 32 patches on four waves (more, smaller workgroups: the layers whose K is not
-    // made of 64-channel blocks are the small 14x14 ones); PVHIP_WINO_SMALL=0 selects 32 x 64 on eight waves (tuning runs)
-    const bool  small = kb == 32 && settings().wino_small;
-    const int  nt   = (kb == 64 || small) ? 32 : 64;
-    const long n_tb = ((long)a.T + nt - 1) / nt;
-    if (n_tb * a.n_kb > 0x7fffffffL) return fail(PVHIP_EUNSUPPORTED, "wino_conv: grid too large");
-    const int   waves = settings().wino_waves;         // PVHIP_WINO_WAVES: tuning runs only
-    const dim3  grid((unsigned)(n_tb * a.n_kb));
-    if (small) hipLaunchKernelGGL((conv_wino_kernel<1, 1, 4>), grid, dim3(256), 0, state().stream, a);
-    else if (kb == 64 && waves == 8) hipLaunchKernelGGL((conv_wino_kernel<2, 1, 8>), grid, dim3(512), 0, state().stream, a);
-    else if (kb == 64) hipLaunchKernelGGL((conv_wino_kernel<2, 1, 4>), grid, dim3(256), 0, state().stream, a);
-    else if (waves == 8) hipLaunchKernelGGL((conv_wino_kernel<1, 2, 8>), grid, dim3(512), 0, state().stream, a);
+    if (p.grid > 0x7fffffffL) return fail(PVHIP_EUNSUPPORTED, "wino_conv: grid too large");
+    const dim3  grid((unsigned)p.grid);
+    if (p.small) hipLaunchKernelGGL((conv_wino_kernel<1, 1, 4>), grid, dim3(256), 0, state().stream, a);
+    else if (p.kb == 64 && p.waves == 8) hipLaunchKernelGGL((conv_wino_kernel<2, 1, 8>), grid, dim3(512), 0, state().stream, a);
+    else if (p.kb == 64) hipLaunchKernelGGL((conv_wino_kernel<2, 1, 4>), grid, dim3(256), 0, state().stream, a);
+    else if (p.waves == 8) hipLaunchKernelGGL((conv_wino_kernel<1, 2, 8>), grid, dim3(512), 0, state().stream, a);
     else hipLaunchKernelGGL((conv_wino_kernel<1, 2, 4>), grid, dim3(256), 0, state().stream, a);
     return PVHIP_OK;
 }
@@ -1799,65 +1807,82 @@ int wino4_pack(const float* w_oihw, float* u, int k, int c) {
     return PVHIP_OK;
 }
 
+// The form of a six-point launch.  Tile order of the shared-V form: MEASURED (scripts/traffic_wino_order.sh, FETCH_SIZE per launch;
+// scripts/time_wino_order.py): channel-pair-major reads
+// 58.5 / 79.8 MB instead of 68.9 / 96.8 on the 7x7 layers 5a / 5b (their transformed weights, 7.4 / 10.6 MB, are the LARGER operand and do not fit an
+// XCD's 4 MB L2; -1.2 % time) and 90-191 MB instead of 70-186 on the 14x14 layers (there the input is the larger one and is then re-read per pair; time
+// within +-1 %).  So: pair-major where twice the weights outweigh the input (5a, 5b).  PVHIP_TUNE3=1: always, =2: never (A/B runs).
+Wino4Plan plan_wino4(int m, int n, int c, int h, int w, int k_out) {
+    Wino4Plan p;
+    p.m = m;
+    p.ragged = h % m != 0 || w % m != 0;
+    const long T = (long)n * ((h + m - 1) / m) * ((w + m - 1) / m);
+    p.n_kb = (k_out + 31) / 32;
+    p.n_stages = c / kCB;
+    p.s_order = settings().tune[3] == 1 ? 1 : (settings().tune[3] == 2 ? 0 : (2 * wino4_pack_elems(k_out, c) > (size_t)n * c * h * w ? 1 : 0));
+    const long n_tb = (T + 31) / 32;
+    p.tiles_max = n_tb * p.n_kb;
+    // The shared-V form (conv_wino4s_kernel: one 16-wave workgroup per CU, two channel blocks on one transformed image per stage,
+    // counters instead of barriers): an even number of channel blocks, whole groups of four stages, and tiles for every CU.
+    // PVHIP_WINO_SHARED=0 never, =2 wherever it applies.
+    const int  mode = settings().wino_shared;
+    const long tiles_s = n_tb * ((p.n_kb + 1) / 2);
+    const bool shape_ok = p.n_kb >= 2 && p.n_stages % 4 == 0 && p.n_stages >= 4 && (p.n_kb % 2 == 0 || mode == 2 || settings().wino_shared_odd);
+    // Measured on GoogLeNet's layers at batch 256 (scripts/time_wino_shared.py, same box, alternating): it wins where the main loop is
+    // long against the epilogue passes of a tile -- C >= 112: 3b -9..-11 %, 4b -9 %, 4c -7 %, 4d -9 %, 4e -9 %, 5a -9 %, 5b -11..-13 %; the
+    // 14x14 layer with C = 96 (4a: -8 %) -- and on conv2/3x3 (C = 64, 4704 tiles: -4..-12 %); it loses on the 28x28 layer with C = 96
+    // (3a: +2 %) and is a wash on the 5x5 layers (4 .. 12 stages per tile).
+    const bool pays = p.n_stages >= 28 || (p.n_stages >= 24 && p.ragged) ||
+                      (p.n_stages <= 16 && p.n_stages >= 12 && tiles_s >= (long)settings().wino_shared_min_tiles);
+    p.shared = mode != 0 && shape_ok && (mode == 2 || pays);
+    // shared V: one workgroup per CU; persistent: two workgroups per CU (72 KB of LDS each), each walking tiles L, L + G, ...
+    const long tiles = p.shared ? tiles_s : p.tiles_max;
+    const long cap   = p.shared ? kNumCU : 2 * kNumCU;
+    p.n_tiles = (int)(tiles > 0x3fffffffL ? 0x3fffffffL : tiles);
+    p.grid    = (int)(tiles < cap ? tiles : cap);
+    p.walk    = tiles > cap;
+    return p;
+}
+
 int wino4_conv(int m, const float* x, const float* u, float* y, int n, int c, int h, int w, int k_out, const float* bias, int act,
                float act_lo, float act_hi, int out_channel_offset, int out_channels_total) {
+    const Wino4Plan p = plan_wino4(m, n, c, h, w, k_out);
     WinoArgs a;
     a.x = x; a.u = u; a.y = y; a.bias = bias;
     a.N = n; a.C = c; a.H = h; a.W = w; a.K = k_out;
     a.TY = (h + m - 1) / m; a.TX = (w + m - 1) / m;
-    const bool ragged = h % m != 0 || w % m != 0;
+    const bool ragged = p.ragged;
     a.T  = n * a.TY * a.TX;
-    a.n_kb = (k_out + 31) / 32;
+    a.n_kb = p.n_kb;
     a.balance = settings().wino_balance ? 1 : 0;
     a.s_lag = settings().wino_shared_lag;
     a.s_prio = settings().wino_shared_prio;
     a.s_old = settings().wino_shared_old;
     a.p_prio = settings().tune[7] == 1 ? 0 : 1;        // PVHIP_TUNE7=1: no priority for conv_wino4_kernel's producers (A/B runs)
     a.s_wide = settings().tune[5] == 1 ? 0 : 1;       // (PVHIP_TUNE5=1: the old pieces.  Same box, alternating: the 7x7 layers -3 % -- their odd rows stored single floats --, the 14x14 layers +-0.5 %)
-    // Tile order of the shared-V form.  MEASURED (scripts/traffic_wino_order.sh, FETCH_SIZE per launch; scripts/time_wino_order.py): channel-pair-major reads
-    // 58.5 / 79.8 MB instead of 68.9 / 96.8 on the 7x7 layers 5a / 5b (their transformed weights, 7.4 / 10.6 MB, are the LARGER operand and do not fit an
-    // XCD's 4 MB L2; -1.2 % time) and 90-191 MB instead of 70-186 on the 14x14 layers (there the input is the larger one and is then re-read per pair; time
-    // within +-1 %).  So: pair-major where twice the weights outweigh the input (5a, 5b).  PVHIP_TUNE3=1: always, =2: never (A/B runs).
-    a.s_order = settings().tune[3] == 1 ? 1 : (settings().tune[3] == 2 ? 0 : (2 * wino4_pack_elems(k_out, c) > (size_t)n * c * h * w ? 1 : 0));
-    a.n_stages = c / kCB;
+    a.s_order = p.s_order;
+    a.n_stages = p.n_stages;
     a.x_bytes = (unsigned)((size_t)n * c * h * w * 4);
     a.u_bytes = (unsigned)(wino4_pack_elems(k_out, c) * 4);
     a.act = act; a.act_lo = act_lo; a.act_hi = act_hi;
     a.y_ctotal = out_channels_total; a.y_coff = out_channel_offset;
-    const long n_tb = ((long)a.T + 31) / 32;
-    if (n_tb * a.n_kb > 0x3fffffffL) return fail(PVHIP_EUNSUPPORTED, "wino4_conv: too many tiles");
-    a.n_tiles = (int)(n_tb * a.n_kb);
+    if (p.tiles_max > 0x3fffffffL) return fail(PVHIP_EUNSUPPORTED, "wino4_conv: too many tiles");
+    a.n_tiles = p.n_tiles;
     w4_magic((unsigned)(a.TY * a.TX), a.tpi_mul, a.tpi_sh);
     w4_magic((unsigned)a.TX, a.tx_mul, a.tx_sh);
-    // The shared-V form (conv_wino4s_kernel: one 16-wave workgroup per CU, two channel blocks on one transformed image per stage,
-    // counters instead of barriers): an even number of channel blocks, whole groups of four stages, and tiles for every CU.
-    // PVHIP_WINO_SHARED=0 never, =2 wherever it applies.
-    {
-        const int  mode = settings().wino_shared;
-        const long tiles_s = n_tb * ((a.n_kb + 1) / 2);
-        const bool shape_ok = a.n_kb >= 2 && a.n_stages % 4 == 0 && a.n_stages >= 4 && (a.n_kb % 2 == 0 || mode == 2 || settings().wino_shared_odd);
-        // Measured on GoogLeNet's layers at batch 256 (scripts/time_wino_shared.py, same box, alternating): it wins where the main loop is
-        // long against the epilogue passes of a tile -- C >= 112: 3b -9..-11 %, 4b -9 %, 4c -7 %, 4d -9 %, 4e -9 %, 5a -9 %, 5b -11..-13 %; the
-        // 14x14 layer with C = 96 (4a: -8 %) -- and on conv2/3x3 (C = 64, 4704 tiles: -4..-12 %); it loses on the 28x28 layer with C = 96
-        // (3a: +2 %) and is a wash on the 5x5 layers (4 .. 12 stages per tile).
-        const bool pays = a.n_stages >= 28 || (a.n_stages >= 24 && ragged) ||
-                          (a.n_stages <= 16 && a.n_stages >= 12 && tiles_s >= (long)settings().wino_shared_min_tiles);
-        if (mode != 0 && shape_ok && (mode == 2 || pays)) {
-            a.n_tiles = (int)tiles_s;
-            const dim3 grid_s((unsigned)(tiles_s < kNumCU ? tiles_s : kNumCU));
-            if (m == 2) {
-                if (ragged) hipLaunchKernelGGL((conv_wino4s_kernel<2, true>), grid_s, dim3(1024), 0, state().stream, a);
-                else        hipLaunchKernelGGL((conv_wino4s_kernel<2, false>), grid_s, dim3(1024), 0, state().stream, a);
-            } else {
-                if (ragged) hipLaunchKernelGGL((conv_wino4s_kernel<4, true>), grid_s, dim3(1024), 0, state().stream, a);
-                else        hipLaunchKernelGGL((conv_wino4s_kernel<4, false>), grid_s, dim3(1024), 0, state().stream, a);
-            }
-            PVHIP_LAUNCH_CHECK();
-            return PVHIP_OK;
+    if (p.shared) {
+        const dim3 grid_s((unsigned)p.grid);
+        if (m == 2) {
+            if (ragged) hipLaunchKernelGGL((conv_wino4s_kernel<2, true>), grid_s, dim3(1024), 0, state().stream, a);
+            else        hipLaunchKernelGGL((conv_wino4s_kernel<2, false>), grid_s, dim3(1024), 0, state().stream, a);
+        } else {
+            if (ragged) hipLaunchKernelGGL((conv_wino4s_kernel<4, true>), grid_s, dim3(1024), 0, state().stream, a);
+            else        hipLaunchKernelGGL((conv_wino4s_kernel<4, false>), grid_s, dim3(1024), 0, state().stream, a);
         }
+        PVHIP_LAUNCH_CHECK();
+        return PVHIP_OK;
     }
-    // persistent: two workgroups per CU (72 KB of LDS each), each walking tiles L, L + G, ...
-    const dim3 grid((unsigned)(a.n_tiles < 2 * kNumCU ? a.n_tiles : 2 * kNumCU));
+    const dim3 grid((unsigned)p.grid);
     if (m == 2) {
         if (ragged) hipLaunchKernelGGL((conv_wino4_kernel<2, 0, true>), grid, dim3(512), 0, state().stream, a);
         else        hipLaunchKernelGGL((conv_wino4_kernel<2, 0>), grid, dim3(512), 0, state().stream, a);

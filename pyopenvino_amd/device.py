@@ -127,6 +127,7 @@ SIGNATURES = {
     'pvhip_conv2d_f16_dma_c8': (_c.c_int, [_fp, _fp, _c.c_void_p] + [_c.c_int] * 13 + [_fp, _c.c_int]),
     'pvhip_conv2d_f16_c8': (_c.c_int, [_c.c_void_p, _fp, _fp] + [_c.c_int] * 7 + [_fp, _c.c_int, _c.c_int, _c.c_int, _c.c_float, _c.c_float]),
     'pvhip_conv2d_kernel_kind': (_c.c_int, [_c.c_int] * 13),
+    'pvhip_conv2d_form': (_c.c_int, [_c.c_int] * 14 + [_c.POINTER(_c.c_int)]),
     'pvhip_conv2d_stem_f32_supported': (_c.c_int, [_c.c_int] * 12),
     'pvhip_conv2d_stem_f32_pack_elems': (_c.c_size_t, [_c.c_int]),
     'pvhip_conv2d_stem_f32_pack': (_c.c_int, [_fp, _fp, _c.c_int]),

@@ -389,6 +389,55 @@ def wino4_form(node):
     return (WINO4S if shape_ok and pays else WINO4) + (', ragged' if ragged else '')
 
 
+# pvhip_conv2d_form (include/pvhip.h: PVHIP_CONV_FORM_*, PVHIP_IGEMM_*): the form inside the family, as the library reports it
+CONV_ENTRIES = {'pvhip_conv2d_f32': 0, 'pvhip_conv2d_multi_f32': 0, 'pvhip_conv2d_f16_dma': 1, 'pvhip_conv2d_multi_f16_dma': 1}
+IGEMM_KERNELS = {0: 'reg', 1: 'pw', 2: 'rs', 3: 'cvalid', 4: 'cwindow'}
+
+
+def conv_form(entry, n, c, h, w, k, kh, kw, oh, ow, sh, sw, pt, pl):
+    """The form string of one launch (entry 0: pvhip_conv2d_f32 / the pointwise route of pvhip_conv2d_multi_f32, 1: the f16 LDS-DMA
+    entries; k: the panel width of a multi-destination launch), 'none' for an empty output.  Host-only: no device needed."""
+    import ctypes
+    from pyopenvino_amd import device
+    f = (ctypes.c_int * 16)()
+    device.call('pvhip_conv2d_form', entry, n, c, h, w, k, kh, kw, oh, ow, sh, sw, pt, pl, f)
+    kind, grid = f[0], f[1]
+    if kind == -1:
+        return 'none'
+    if kind == 1:
+        return 'pw tn={} vec={} nchunk={} stagger={} grid={}'.format(f[2], f[3], f[4], f[5], grid)
+    if kind == 2:
+        return 'wino2 kb={} patches={} waves={} grid={}'.format(f[2], f[3], f[4], grid)
+    if kind in (3, 4):
+        assert f[2] == (4 if kind == 3 else 2)
+        return 'wino4 m={} ragged={} shared={} order={} tiles={} grid={} walk={}'.format(f[2], f[3], f[4], f[5], f[6], grid, f[7])
+    assert kind == 0, kind
+    return '{} bm={} kernel={} mtiles={} grid={}'.format('f16' if entry else 'igemm', f[2], IGEMM_KERNELS[f[3]], f[4], grid)
+
+
+def launch_args(G, plan, cid, r):
+    """The arguments of conv_form for the launch the Route `r` gives Convolution node `cid`: the geometry the library is handed (behind
+    the padding pass, if the route has one) and, for a sibling launch, the panel width.  None: an entry the query does not cover."""
+    from pyopenvino_amd.op_plugins import Convolution
+    if r.entry not in CONV_ENTRIES:
+        return None
+    g = Convolution.geometry(G.nodes[cid])
+    h, w, pads, k = g.h, g.w, g.pads_begin, g.kn
+    if r.pad_row:
+        h, w, pads = g.h + g.pads_begin[0] + g.pads_end[0], r.pad_row, (0, 0)
+    if 'multi' in r.entry:
+        k = sum(-(-int(G.nodes[m]['input'][1]['dims'][0]) // 32) * 32 for m in [cid] + list(plan.siblings.get(cid, ())))
+        if not CONV_ENTRIES[r.entry] and Convolution.kernel_kind(G.nodes[cid])[0] != 'pointwise':
+            return None                 # the fp32 multi launch with PVHIP_CONV_POINTWISE=0
+    return (CONV_ENTRIES[r.entry], g.n, g.c, h, w, k, g.kh, g.kw, g.oh, g.ow, *g.strides, *pads)
+
+
+def wino4_form_of(form):
+    """The restatement's name (WINO4S ...) of a queried six-point form string."""
+    f = dict(v.split('=') for v in form.split()[1:])
+    return (WINO4S if f['shared'] == '1' else WINO4) + (', ragged' if f['ragged'] == '1' else '')
+
+
 def read_rows(t, idx):
     """The sampled images of a tensor, as fp32 (BlockedHalf: the fp32 values of its fp16 contents).  Dense device tensors are read image
     by image: only what is compared crosses to the host."""
@@ -424,6 +473,10 @@ def family(G, ex, g):
     fam = 'f16 ' + f16_kind if f16_kind else conv_family(node)
     if fam in ('Winograd F(4x4,3x3)', 'Winograd F(2x2,5x5)'):         # the six-point layers (wino4_conv); F(2x2,3x3) has one form
         fam += ' / ' + wino4_form(node)
+        route = node.get('_hip_route')
+        if route is not None and route[1].entry == 'pvhip_conv2d_f32':      # what the launch took, by the library's own plan
+            queried = conv_form(*launch_args(G, ex.plan, convs[-1], route[1]))
+            assert fam.endswith(wino4_form_of(queried)), (node['name'], queried, fam)
     lead = [G.nodes[n]['type'] for n in g['nodes'] if n not in convs and G.nodes[n]['type'] in ('MaxPool', 'LRN')]
     return ' + '.join(lead + [fam])
 
@@ -575,7 +628,20 @@ def launch_forms(net, ex, n):
         fam, form = ('f16 ' + str(r.label), None) if ex.plan.f16 else (conv_family(node), None)
         if fam in ('Winograd F(4x4,3x3)', 'Winograd F(2x2,5x5)') and r.entry == 'pvhip_conv2d_f32':
             form = wino4_form(node)
+            queried = conv_form(*launch_args(G, ex.plan, cid, r))          # the restatement and the library agree
+            assert wino4_form_of(queried) == form, (node['name'], queried, form)
         out[node['name']] = (fam, form, r)
+    return out
+
+
+def queried_forms(net, ex):
+    """{conv name: pvhip_conv2d_form's answer as a string, or None for an entry it does not cover} of the plan `ex` holds."""
+    import test_conv_routes
+    from pyopenvino_amd.op_plugins import Convolution
+    G, out = net.G, {}
+    for cid, facts in test_conv_routes.launch_facts(ex).items():
+        args = launch_args(G, ex.plan, cid, Convolution.route(*facts))
+        out[G.nodes[cid]['name']] = None if args is None else conv_form(*args)
     return out
 
 

@@ -24,9 +24,15 @@ tests (helpers.REL_TOL and ref64.DRIFT for fp32; 1e-5 and f16_excess <= 1 for th
 the last eight, four seeded positions in between; the whole batch up to 16), and the families the launches took are held against the
 golden table of the batch's class.
 
-Not verified by any query: which of pw_conv's tn forms, launch_igemm's tile heights and the one-tile-per-workgroup / walking forms of the
-persistent Winograd grid ran.  The chosen batches cross those switches by the formulas in pvhip_pw.hip, pvhip_conv.hip and pvhip_wino.hip
-(`pw_tn` and `dw_bytes_moved` below restate two of them); the census pins only what the library can be asked."""
+Which form inside its family a launch takes -- pw_conv's tn and copy, launch_igemm's and the f16 entry's tile height and kernel form,
+wino_conv's workgroup shape, the shared-V / persistent kernel of the six-point layers and whether its workgroups walk -- is pinned by
+pvhip_conv2d_form: tests/test_conv_forms.py asks it for every launch of these four sweeps that enters pvhip_conv2d_f32, the pointwise route
+of pvhip_conv2d_multi_f32, pvhip_conv2d_f16_dma or pvhip_conv2d_multi_f16_dma, holds the answer against the launchers' frozen inequalities,
+and runs a row of every class they fall in against float64; ref64.launch_forms and ref64.family hold ref64.wino4_form against the query.
+Still reported by no query: the forms inside the stem entries, the span / c8 / c8-multi readers (every launch of the GoogLeNet FP16 IR
+behind its stem), the MaxPool + 1x1 launches, the fp32 multi launch with PVHIP_CONV_POINTWISE=0, the diagnostic build's overrides and
+ablations, and the depthwise kernels' nontemporal switch (`dw_bytes_moved` below restates it; `pw_tn` restates plan_pw's tn, and
+test_conv_forms.py compares it with the query)."""
 import functools
 import json
 import os
