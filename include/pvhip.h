@@ -525,6 +525,20 @@ int pvhip_detection_output_f32(const float* loc, const float* conf, const float*
 int pvhip_detections_to_rois(const float* records, int* rois, int* record_of, int* counts, int n, int images, int records_per_image,
                              int frame_h, int frame_w, float min_confidence, const int* labels, int num_labels, int min_h, int min_w);
 
+/* ---------------------------------------------------------------- a classifier's answer ---- */
+/* Addition to ABI v18 (the version number is unchanged: nothing existing changed): the k best entries of every row of a contiguous
+ * (rows, cols) fp32 tensor -- what the reference's sample makes on the host with np.argsort(res[output_node_name][0])[::-1] -- so that
+ * only (rows, k) pairs are read back.  For a row x[0..cols) the answer is the first k positions of the row sorted by this total order:
+ *   1. NaN (any sign, any payload) ranks before every number: a poisoned row shows NaN as its first score;
+ *   2. then by value, descending; +0.0 and -0.0 are equal;
+ *   3. equal rank (ties, zeros of either sign, several NaNs): the lower index first.
+ * In numpy: np.lexsort((np.arange(cols), -np.where(isnan, 0, x), ~isnan))[:k] (tests/topk_ref.py; matched index for index).  On a row
+ * without ties or NaN this is np.argsort(x)[::-1][:k].  indices[r][j] is that position as an int32; values[r][j] holds the bits of
+ * x[r][indices[r][j]] unchanged (-0.0 stays -0.0, a NaN keeps its payload).  `indices` and `values` are (rows, k).  One launch on the
+ * current stream, no allocation, no workspace.  rows, cols >= 1, 1 <= k <= min(cols, 64), rows * cols < 2^31, no NULL pointer; else
+ * PVHIP_EINVAL and nothing is launched. */
+int pvhip_topk_rows_f32(const float* x, int rows, int cols, int k, int* indices, float* values);
+
 /* ---------------------------------------------------------------- multi-GPU gather ---------- */
 /* No reference counterpart (the reference is single-process).  Batch shards are independent; the only
  * exchange is an all-gather of the Result tensor over RCCL/xGMI.  unique_id is a 128-byte buffer. */

@@ -6,5 +6,6 @@ body is a hand-written HIP kernel reached through the C ABI of ``libpvhip.so`` (
 """
 from .inference_engine import IECore, IENetwork, Executable_Network  # noqa: F401
 from .input_format import DetectedRois, RoiInput  # noqa: F401
+from .top_k import TopK  # noqa: F401
 
-__all__ = ['IECore', 'IENetwork', 'Executable_Network', 'RoiInput', 'DetectedRois']
+__all__ = ['IECore', 'IENetwork', 'Executable_Network', 'RoiInput', 'DetectedRois', 'TopK']

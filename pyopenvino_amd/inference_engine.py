@@ -33,7 +33,7 @@ import xml.etree.ElementTree as et
 import networkx as nx
 import numpy as np
 
-from . import common_def, device, fusion_plan, stream_plan
+from . import common_def, device, fusion_plan, stream_plan, top_k as top_k_rule
 from .host_input import HostInputs
 from .input_format import DetectedRois, InputInfo, PreProcessChannel, PreProcessInfo  # noqa: F401 -- the classes of IENetwork.input_info
 from .stream_plan import CaptureStreamModel
@@ -298,28 +298,40 @@ class InferRequest:
     """One inference that can be in flight next to others (the OpenVINO infer-request idea behind the reference's
     unused `num_requests`): it owns a copy of the graph state (node outputs, cached device constants) and a set of
     compute streams, so that the kernels of several requests interleave on the device -- the HBM-bound layers of one
-    run beside the matrix-core-bound layers of another, and each fills the other's tails."""
+    run beside the matrix-core-bound layers of another, and each fills the other's tails.
+
+    `top_k` = k (every Result) or {Result name: k}: those Results come back from wait() as a ``TopK`` (indices, values) of shape (n, k)
+    -- the k best classes of every batch row by the rule of top_k.py -- made by one launch behind the pass and read back in one copy of
+    8 n k bytes; the full Result stays on the device.  Results not named come back whole.  ValueError, before anything is staged or
+    launched: a Result whose declared shape is not (n, C) or (n, C, 1, ...), k outside 1 .. min(C, 64), an unknown name, a sharded batch."""
 
     def __init__(self, owner, runner, index: int):
         self.owner, self.runner, self.index = owner, runner, index      # owner: the network load_network returned
         self._in_flight, self._replayed = False, None
+        self._top_k = {}                # {Result name: k} of the pass in flight
 
-    def start_async(self, inputs: dict):
+    def start_async(self, inputs: dict, top_k=None):
+        self._start(inputs, top_k, False)
+
+    def _start(self, inputs, top_k, verbose):
         if self._in_flight:
             raise RuntimeError('request {} is still in flight: wait() first'.format(self.index))
         ex = self.runner
+        self._top_k = top_k_rule.checked(ex.ienet, top_k, ex.sharded or self.owner.sharded)
         inputs = ex.host_inputs.stage(inputs, ex.stream_base, ex.sharded or self.owner.sharded)
         ex.wait_result_readers()
         # The same device-resident tensors as the last calls: the pass is replayed from this request's own recording (one call
         # instead of ~100 dispatches; every request records its own pass on its own stream and keeps its own tensors, so the
         # replays of several requests run side by side like their eager passes do).
-        self._replayed = ex._graph_for(inputs, gathers_later=True)
+        self._replayed = ex._graph_for(inputs, verbose, gathers_later=True)
         if self._replayed is not None:
             ex.launch_graph(self._replayed)
         else:
             ex._bind_inputs(inputs)
             with ex._results_on_device():        # the shards are gathered in wait(): one collective at a time, on stream 0
-                ex.run_tasks(False)
+                ex.run_tasks(verbose)
+        if self._top_k:                          # behind the pass, replayed or eager, and outside the recording: one recording serves both
+            ex.launch_top_k(self._top_k, self._replayed)
         self._in_flight = True
 
     def wait(self) -> dict:
@@ -329,13 +341,17 @@ class InferRequest:
         self._in_flight = False
         out = {}
         replayed, self._replayed = self._replayed, None
+        top_k, self._top_k = self._top_k, {}
         for nid, name in ex.ienet.find_node_by_type('Result'):
             value = replayed['results'][name] if replayed is not None else G.nodes[nid]['result']
-            G.nodes[nid]['result'] = out[name] = ex._read_back(value, self.owner.comm)
+            if name in top_k:                    # (n, k) pairs come back; the Result itself stays where it is
+                G.nodes[nid]['result'], out[name] = value, ex.read_top_k(name, top_k[name], value)
+            else:
+                G.nodes[nid]['result'] = out[name] = ex._read_back(value, self.owner.comm)
         return out
 
-    def infer(self, inputs: dict) -> dict:
-        self.start_async(inputs)
+    def infer(self, inputs: dict, top_k=None) -> dict:
+        self.start_async(inputs, top_k)
         return self.wait()
 
     def input_buffer(self, name: str, source_size=None, frames=None) -> np.ndarray:
@@ -419,6 +435,7 @@ class Executable_Network:
         # events behind the launches of OTHER requests that read this network's device-resident Result (a DetectedRois fed from this
         # request while in flight): the next pass, eager or replayed, waits for them on the device before it can overwrite that tensor
         self._result_readers = []
+        self._top_k_blocks = {}         # {(Result name, k): top_k.Blocks}: the device block and the page-locked block of a top_k pass
         if input_formats is None:
             input_formats = {name: info.frozen() for name, info in ienetwork.input_info.items()}
         self.host_inputs = HostInputs(input_formats)    # host arrays in a declared format or the request's own buffers -> device tensors
@@ -471,6 +488,7 @@ class Executable_Network:
         self.release_graph()
         self.host_inputs.release()                  # page-locked buffers go back once the caller holds no view of them
         self._result_readers = []
+        self._top_k_blocks = {}
         G = self.ienet.G
         for nid in G.nodes:
             node = G.nodes[nid]
@@ -492,8 +510,38 @@ class Executable_Network:
                 event.wait()
             device.select_stream(0)
 
-    def start_async(self, request_id: int, inputs: dict):
-        self.requests[request_id].start_async(inputs)
+    def start_async(self, request_id: int, inputs: dict, top_k=None):
+        self.requests[request_id].start_async(inputs, top_k)
+
+    def launch_top_k(self, top_k: dict, replayed):
+        """pvhip_topk_rows_f32 for every Result named in `top_k` = {name: k} that the pass just issued (`replayed`: its recording, or None
+        for an eager pass) leaves on the device, on the base stream behind that pass; wait_done() then waits for an event behind the
+        launches.  The blocks are this request's own, made on first use per (name, k).  A Result that is a host array gets the rule in
+        numpy when it is read (read_top_k)."""
+        G = self.ienet.G
+        values = {name: (replayed['results'][name] if replayed is not None else G.nodes[nid]['result'])
+                  for nid, name in self.ienet.find_node_by_type('Result') if name in top_k}
+        values = {name: value for name, value in values.items() if isinstance(value, device.DeviceTensor)}
+        if not values:
+            return
+        device.select_stream(self.stream_base)
+        for name, value in values.items():
+            key = (name, top_k[name])
+            if key not in self._top_k_blocks:
+                self._top_k_blocks[key] = top_k_rule.Blocks(top_k_rule.rows_of(value.shape)[0], top_k[name])
+            self._top_k_blocks[key].launch(value)
+        self._pending = (self._pending[0] if self._pending is not None else None, self._order_event().record())
+        device.select_stream(0)
+
+    def read_top_k(self, name: str, k: int, value):
+        """The TopK of Result `name` after wait_done(): one copy from the block launch_top_k filled, on this network's drained base
+        stream; the rule in numpy for a Result that is a host array."""
+        if not isinstance(value, device.DeviceTensor):
+            return top_k_rule.top_k_rows(np.asarray(value), k)
+        device.select_stream(self.stream_base)
+        out = self._top_k_blocks[(name, k)].read_back()
+        device.select_stream(0)
+        return out
 
     def wait(self, request_id: int) -> dict:
         return self.requests[request_id].wait()
@@ -995,7 +1043,12 @@ class Executable_Network:
             return None
         return self._graph
 
-    def infer(self, inputs: dict, verbose: bool = False) -> dict:
+    def infer(self, inputs: dict, verbose: bool = False, top_k=None) -> dict:
+        """`top_k` = k or {Result name: k}: those Results come back as a ``TopK`` of the k best classes per batch row (InferRequest)."""
+        if top_k is not None:                    # the pass of request 0 (this network's own graph and streams), waited for at once
+            request = self.requests[0] if self.requests else InferRequest(self, self, 0)
+            request._start(inputs, top_k, verbose)
+            return request.wait()
         inputs = self.host_inputs.stage(inputs, self.stream_base, self.sharded)
         self.wait_result_readers()
         if self._graph_for(inputs, verbose) is None:
