@@ -592,6 +592,29 @@ int         pvhip_input_preprocess_roi_f32(const void* src, float* dst, const in
 int         pvhip_input_preprocess_yuv_roi_f32(const void* src, float* dst, const int* rois, int n, int m, int src_h, int src_w,
                                                int dst_h, int dst_w, int max_roi_h, int max_roi_w, int planar, int reverse_channels,
                                                const float* mean, const float* std_scale);
+/* Addition to ABI v18 (the version number is unchanged: nothing existing changed): the same launch for frames of 4-byte units
+ * (preprocess_info.color_format 'YUY2' / 'UYVY' / 'BGRX' / 'RGBX'), a camera's, a capture card's or a screen capture's frame as it is.
+ * `src`: uint8, any alignment; kind 0 YUY2, 1 UYVY, 2 BGRX, 3 RGBX.
+ *   YUY2 / UYVY (packed YUV 4:2:2): n frames of shape (src_h, src_w, 2), src_w even, src_h any value >= 1.  Each row is src_w / 2 groups
+ *     of 4 bytes: Y0 U Y1 V for YUY2, U Y0 V Y1 for UYVY.  Pixel (y, x) has luma Y[x & 1] of group x / 2 of row y, and that group's
+ *     (U, V): chroma is not interpolated.  Each pixel goes to B, G, R by exactly the integer rule of pvhip_input_preprocess_yuv_f32
+ *     (BT.601 limited range over 2^20, arithmetic shifts, clamp to [0, 255]; tests/yuv_ref.py): the same function, not a second set of
+ *     constants.
+ *   BGRX / RGBX (four-byte pixels): n frames of shape (src_h, src_w, 4), any src_h, src_w >= 1.  The B, G, R image is bytes 0, 1, 2 of
+ *     every pixel for BGRX and bytes 2, 1, 0 for RGBX; byte 3 is never read into the result, whatever it holds.
+ * The resulting uint8 B, G, R image -- channel 0 is B -- goes through the resize, reversal (reverse_channels = 1: R, G, B) and mean /
+ * scale of pvhip_input_preprocess_f32 with c = 3 into `dst` (n, 3, dst_h, dst_w), bit for bit what that entry gives for the converted
+ * U8 NHWC image.  In numpy: tests/packed_ref.py.  The _roi form is pvhip_input_preprocess_roi_f32's for these frames: image b is the
+ * rectangle rois[b] = (id, x, y, w, h) of the CONVERTED frame id of m, the taps clamp at the rectangle's edge, a 4:2:2 pixel keeps the
+ * chroma of its absolute column pair (so a rectangle may start on an odd x and have an odd w), and an invalid or oversized rectangle is
+ * written as quiet NaN with nothing read for it.  One launch on the current stream, no allocation.  kind in 0..3, src_w even for kinds
+ * 0 and 1, no NULL src / dst (/ rois), every size >= 1, n <= 65535, 3 * h * w < 2^31 for source and destination, m >= 1,
+ * 1 <= max_roi_h <= src_h, 1 <= max_roi_w <= src_w; else PVHIP_EINVAL and nothing is launched. */
+int         pvhip_input_preprocess_packed_f32(const void* src, float* dst, int n, int src_h, int src_w, int dst_h, int dst_w,
+                                              int kind, int reverse_channels, const float* mean, const float* std_scale);
+int         pvhip_input_preprocess_packed_roi_f32(const void* src, float* dst, const int* rois, int n, int m, int src_h, int src_w,
+                                                  int dst_h, int dst_w, int max_roi_h, int max_roi_w, int kind, int reverse_channels,
+                                                  const float* mean, const float* std_scale);
 
 #ifdef __cplusplus
 }

@@ -9,8 +9,10 @@
 // Then y = (v - mean[c]) / std_scale[c], output channel c reading source channel C-1-c under reversal.  tests/preprocess_ref.py is the
 // same rule in numpy; the kernels match it bit for bit.
 //
-// Two kernels -- preprocess_kernel for U8 / FP32 images, preprocess_yuv_kernel for YUV 4:2:0 frames (NV12, I420), which converts every
-// tapped pixel to B, G, R in front of the interpolation -- differ in what they stage and in their inner loops, and share the rest (TileArgs):
+// Three kernels -- preprocess_kernel for U8 / FP32 images, preprocess_yuv_kernel for YUV 4:2:0 frames (NV12, I420), which converts every
+// tapped pixel to B, G, R in front of the interpolation, and preprocess_packed_kernel for frames of 4-byte units (packed YUV 4:2:2: YUY2,
+// UYVY; four-byte pixels: BGRX, RGBX), which decodes every tapped pixel -- differ in what they stage and in their inner loops, and share
+// the rest (TileArgs):
 // a workgroup owns a tile of `th` output rows x `tw` output columns of one image (normally whole rows; plan_tiles).  It
 //   1. finds its tile and the source extent its taps see (tile_of);
 //   2. tabulates the tile's column and row coordinates (x0, x1, fx), (y0, y1, fy) in LDS (fill_tables);
@@ -22,7 +24,7 @@
 //      channel plane, scalar stores when the destination rows are not 16-byte aligned (finish_quad).
 //
 // Regions of interest (the ROI entries): image b of the output is the rectangle rois[b] = (id, x, y, w, h) of frame id of m frames, cropped
-// and then resized -- the taps clamp at the rectangle's edge, not the frame's.  Both kernels take it as a template parameter: a workgroup
+// and then resized -- the taps clamp at the rectangle's edge, not the frame's.  Every kernel takes it as a template parameter: a workgroup
 // reads its image's five ints, takes S = (h, w) for its taps and adds (id, y, x) to the addresses it stages from; a rectangle of exactly
 // the destination's extent is copied (fp32 sources: no 0 * inf; bytes give the same bits either way).  The table is device data, so an image whose rectangle does not lie inside a frame, or
 // exceeds the maxima the launch was sized for, is written as quiet NaN and nothing is read for it.  tests/roi_ref.py is the rule in numpy.
@@ -405,8 +407,124 @@ void launch_yuv(const YuvArgs& a, dim3 grid, size_t lds, bool vs, hipStream_t st
     else    hipLaunchKernelGGL((preprocess_yuv_kernel<RESIZE, false, ROI>), grid, dim3(kBlock), lds, st, a);
 }
 
+// ------------------------------------------------------------------------------------------------------ packed 4-byte-unit sources
+// Frames whose rows are 4-byte units, uint8, any alignment:
+//   KIND 0 YUY2 (n, h, w, 2), w even: a row is w / 2 groups Y0 U Y1 V;   KIND 1 UYVY: groups U Y0 V Y1 -- a camera's or a capture card's
+//          packed YUV 4:2:2: pixel (y, x) has luma Y[x & 1] of group x / 2 of row y and that group's (U, V) (no chroma interpolation) and
+//          goes to B, G, R by yuv_to_bgr, the one integer rule of the 4:2:0 sources above; h may be odd;
+//   KIND 2 BGRX (n, h, w, 4): B, G, R are bytes 0, 1, 2 of a pixel;      KIND 3 RGBX: bytes 2, 1, 0 -- a screen capture's or a read-back's
+//          four-byte pixels; byte 3 is never read into the result; any h, w.
+// The uint8 B, G, R image that gives is then resized, reversed and scaled exactly as a U8 NHWC source is above.  tests/packed_ref.py is
+// the rule in numpy.
+//
+// A tile stages, for every source row ys0..ys1, ONE span of whole units: units (ox + xs0) >> 1 .. (ox + xs1) >> 1 of the ABSOLUTE columns
+// for 4:2:2 (a tile or a rectangle may start on an odd column), units ox + xs0 .. ox + xs1 for the X kinds.  A pixel is decoded where it
+// is tapped -- four decodes per output pixel under resize, one without --, the three channels of a quad come from one pass over its taps,
+// and the byte positions inside a unit are compile-time constants of KIND.
+struct PackedArgs : TileArgs {
+    unsigned slot;            // LDS bytes per staged row span (a multiple of 16)
+};
+
+// B, G, R of the pixel at column x of its rectangle (absolute column ox + x), from the row span `l` whose first unit is unit u0.
+template <int KIND>
+__device__ __forceinline__ void packed_to_bgr(const unsigned char* l, int ox, int x, int u0, float (&o)[3]) {
+    if (KIND < 2) {
+        const int ax = ox + x;
+        const unsigned char* g = l + 4 * ((ax >> 1) - u0);
+        constexpr int Y = KIND == 0 ? 0 : 1, U = KIND == 0 ? 1 : 0, V = KIND == 0 ? 3 : 2;
+        yuv_to_bgr(g[Y + 2 * (ax & 1)], g[U], g[V], o);
+    } else {
+        const unsigned char* g = l + 4 * (ox + x - u0);
+        o[0] = (float)g[KIND == 2 ? 0 : 2];
+        o[1] = (float)g[1];
+        o[2] = (float)g[KIND == 2 ? 2 : 0];
+    }
+}
+
+// dynamic LDS stage_bytes + Tables::bytes(tw, th).  ROI (with RESIZE): a 4:2:2 pixel keeps the chroma of its ABSOLUTE column pair, so a
+// rectangle may start on an odd x and have an odd w.  (No copy path for a rectangle of the destination's extent: the pixels are bytes.)
+template <int KIND, bool RESIZE, bool VS, bool ROI>
+__global__ __launch_bounds__(kBlock) void preprocess_packed_kernel(PackedArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    constexpr bool YUV = KIND < 2;
+    Tile t;
+    if (!tile_of<ROI>(a, 3, t)) return;
+    const Tables tb = fill_tables(lds, a, t, [](int d, int S, int D) { return tap<RESIZE>(d, S, D); });
+    const int ox = t.ox, oy = t.oy, ys0 = tb.ys0;
+    const int rows = tb.ys1 - ys0 + 1;
+    const int u0 = YUV ? (ox + tb.xs0) >> 1 : ox + tb.xs0;                         // the first and the last unit of every staged row
+    const int u1 = YUV ? (ox + tb.xs1) >> 1 : ox + tb.xs1;
+    const int span = (u1 - u0 + 1) * 4;
+    const size_t row_bytes = (size_t)a.ws * (YUV ? 2 : 4);
+    const unsigned char* frame = a.src + (size_t)t.img * ((size_t)a.hs * row_bytes);
+    auto row_src = [&](int r) -> const unsigned char* { return frame + (size_t)(oy + ys0 + r) * row_bytes + (size_t)u0 * 4; };
+    const unsigned bps = (unsigned)span / 16 + 2;             // 16-byte blocks a span touches at most
+    const unsigned nblk = (unsigned)rows * bps;
+    for (unsigned i = threadIdx.x; i < nblk; i += kBlock) {
+        const unsigned s = i / bps;
+        stage_block(row_src((int)s), span, lds + s * a.slot, i - s * bps);
+    }
+    __syncthreads();
+
+    const int nq = (t.twv + 3) >> 2;
+    const size_t plane_out = (size_t)a.hd * a.wd;
+    float* out_n = a.dst + (size_t)t.n * 3 * plane_out;
+    for (int i = threadIdx.x; i < t.thv * nq; i += kBlock) {
+        const int r = i / nq, j0 = 4 * (i - r * nq);
+        const float fy = tb.rfy[r], gy = 1.0f - fy;
+        const int r0 = tb.ry0[r] - ys0, r1 = tb.ry1[r] - ys0;                      // the two tapped rows
+        const unsigned char* l0 = span_base(lds + (unsigned)r0 * a.slot, row_src(r0));
+        const unsigned char* l1 = span_base(lds + (unsigned)r1 * a.slot, row_src(r1));
+        float v[3][4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int j = j0 + u < t.twv ? j0 + u : j0;       // (a pixel past the tile computes column j0 again and is not stored)
+            const int xa = tb.cx0[j], xb = tb.cx1[j];
+            float p00[3];
+            packed_to_bgr<KIND>(l0, ox, xa, u0, p00);
+            if (RESIZE) {
+                const float fx = tb.cfx[j], gx = 1.0f - fx;
+                float p01[3], p10[3], p11[3];
+                packed_to_bgr<KIND>(l0, ox, xb, u0, p01);
+                packed_to_bgr<KIND>(l1, ox, xa, u0, p10);
+                packed_to_bgr<KIND>(l1, ox, xb, u0, p11);
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    const float top = gx * p00[c] + fx * p01[c];
+                    const float bot = gx * p10[c] + fx * p11[c];
+                    v[c][u] = gy * top + fy * bot;
+                }
+            } else {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) v[c][u] = p00[c];
+            }
+        }
+        float* o = out_n + (size_t)(t.ty0 + r) * a.wd + t.tx0 + j0;
+#pragma unroll
+        for (int oc = 0; oc < 3; ++oc, o += plane_out) {
+            float w[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) w[u] = a.reverse ? v[2 - oc][u] : v[oc][u];
+            finish_quad<VS>(a, oc, w, o, j0, t.twv);
+        }
+    }
+}
+
+template <int KIND>
+void launch_packed(const PackedArgs& a, dim3 grid, size_t lds, bool vs, bool roi, bool resize, hipStream_t st) {
+#define PVHIP_PACKED(RESIZE, ROI)                                                                                              \
+    do {                                                                                                                           \
+        if (vs) hipLaunchKernelGGL((preprocess_packed_kernel<KIND, RESIZE, true, ROI>), grid, dim3(kBlock), lds, st, a);           \
+        else    hipLaunchKernelGGL((preprocess_packed_kernel<KIND, RESIZE, false, ROI>), grid, dim3(kBlock), lds, st, a);          \
+    } while (0)
+    if (roi)         PVHIP_PACKED(true, true);
+    else if (resize) PVHIP_PACKED(true, false);
+    else             PVHIP_PACKED(false, false);
+#undef PVHIP_PACKED
+}
+
 // ---------------------------------------------------------------------------------------------------------------------- launchers
-// Both launchers take rois == NULL: image b is the whole of source image b, with m = n and (roi_h, roi_w) = (src_h, src_w); else image b
+// The launchers take rois == NULL: image b is the whole of source image b, with m = n and (roi_h, roi_w) = (src_h, src_w); else image b
 // is a rectangle of one of m frames, and the tiles and LDS slots are sized for the largest rectangle (roi_h, roi_w): extent() is
 // monotone in S, so the budget holds for every image.
 
@@ -511,6 +629,34 @@ int preprocess_yuv_launch(const void* src, float* dst, const int* rois, int n, i
     return PVHIP_OK;
 }
 
+// The one launcher of preprocess_packed_kernel.  kind: 0 YUY2, 1 UYVY, 2 BGRX, 3 RGBX.
+int preprocess_packed_launch(const void* src, float* dst, const int* rois, int n, int m, int src_h, int src_w, int dst_h, int dst_w,
+                             int roi_h, int roi_w, int kind, int reverse_channels, const float* mean, const float* std_scale) {
+    PackedArgs a;
+    int rc = common_args(a, src, dst, rois, n, m, 3, src_h, src_w, dst_h, dst_w, roi_h, roi_w, reverse_channels, mean, std_scale);
+    if (rc != PVHIP_OK) return rc;
+    PVHIP_CHECK_ARG(kind >= 0 && kind <= 3);
+    const bool yuv = kind < 2;
+    PVHIP_CHECK_ARG(!yuv || src_w % 2 == 0);                                         // 4:2:2: one (U, V) per column pair
+    const bool roi = rois != nullptr, resize = roi || src_h != dst_h || src_w != dst_w;
+    // e consecutive columns lie in at most e / 2 + 1 groups of 4:2:2 (the first may be an odd one), and in e units of an X kind
+    auto units = [&](size_t e) { return !yuv ? e : (e / 2 + 1 < (size_t)src_w / 2 ? e / 2 + 1 : (size_t)src_w / 2); };
+    auto slot_of = [&](int tw) { return (units(extent(resize, tw, roi_w, dst_w)) * 4 + 30) / 16 * 16; };
+    TilePlan p;
+    rc = plan_tiles(a, n, [&](int tw, int th) { return extent(resize, th, roi_h, dst_h) * slot_of(tw); }, p);
+    if (rc != PVHIP_OK) return rc;
+    a.slot = (unsigned)slot_of(a.tw);
+    hipStream_t st = state().stream;
+    switch (kind) {
+        case 0:  launch_packed<0>(a, p.grid, p.lds, p.vs, roi, resize, st); break;
+        case 1:  launch_packed<1>(a, p.grid, p.lds, p.vs, roi, resize, st); break;
+        case 2:  launch_packed<2>(a, p.grid, p.lds, p.vs, roi, resize, st); break;
+        default: launch_packed<3>(a, p.grid, p.lds, p.vs, roi, resize, st); break;
+    }
+    PVHIP_LAUNCH_CHECK();
+    return PVHIP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -542,6 +688,21 @@ int pvhip_input_preprocess_yuv_roi_f32(const void* src, float* dst, const int* r
     PVHIP_CHECK_ARG(rois != nullptr);
     return preprocess_yuv_launch(src, dst, rois, n, m, src_h, src_w, dst_h, dst_w, max_roi_h, max_roi_w, planar, reverse_channels, mean,
                                  std_scale);
+}
+
+int pvhip_input_preprocess_packed_f32(const void* src, float* dst, int n, int src_h, int src_w, int dst_h, int dst_w, int kind,
+                                      int reverse_channels, const float* mean, const float* std_scale) {
+    return preprocess_packed_launch(src, dst, nullptr, n, n, src_h, src_w, dst_h, dst_w, src_h, src_w, kind, reverse_channels, mean,
+                                    std_scale);
+}
+
+int pvhip_input_preprocess_packed_roi_f32(const void* src, float* dst, const int* rois, int n, int m, int src_h, int src_w, int dst_h,
+                                          int dst_w, int max_roi_h, int max_roi_w, int kind, int reverse_channels, const float* mean,
+                                          const float* std_scale) {
+    PVHIP_REQUIRE_INIT();
+    PVHIP_CHECK_ARG(rois != nullptr);
+    return preprocess_packed_launch(src, dst, rois, n, m, src_h, src_w, dst_h, dst_w, max_roi_h, max_roi_w, kind, reverse_channels, mean,
+                                    std_scale);
 }
 
 }  // extern "C"

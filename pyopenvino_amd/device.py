@@ -159,6 +159,8 @@ SIGNATURES = {
     'pvhip_input_preprocess_yuv_f32': (_c.c_int, [_c.c_void_p, _fp] + [_c.c_int] * 7 + [_fp, _fp]),
     'pvhip_input_preprocess_roi_f32': (_c.c_int, [_c.c_void_p, _fp, _c.c_void_p] + [_c.c_int] * 12 + [_fp, _fp]),
     'pvhip_input_preprocess_yuv_roi_f32': (_c.c_int, [_c.c_void_p, _fp, _c.c_void_p] + [_c.c_int] * 10 + [_fp, _fp]),
+    'pvhip_input_preprocess_packed_f32': (_c.c_int, [_c.c_void_p, _fp] + [_c.c_int] * 7 + [_fp, _fp]),
+    'pvhip_input_preprocess_packed_roi_f32': (_c.c_int, [_c.c_void_p, _fp, _c.c_void_p] + [_c.c_int] * 10 + [_fp, _fp]),
 }
 
 # entry points whose return value is not a status code

@@ -241,21 +241,26 @@ class HostInputs:
     @staticmethod
     def _convert(fmt, slot, staged, largest):
         """The one launch that makes `slot.fixed` of what `staged` uploaded (none for FP32 NCHW at the network's extent):
-        pvhip_input_preprocess_yuv_f32 for NV12 / I420 frames, pvhip_input_preprocess_f32 when a resize, channel reversal or mean /
-        scale is in effect, else pvhip_input_to_nchw_f32; `largest` = (max_h, max_w) of a RoiInput's table: the _roi_f32 forms."""
+        pvhip_input_preprocess_yuv_f32 for NV12 / I420 frames, pvhip_input_preprocess_packed_f32 for YUY2 / UYVY / BGRX / RGBX frames,
+        pvhip_input_preprocess_f32 when a resize, channel reversal or mean / scale is in effect, else pvhip_input_to_nchw_f32;
+        `largest` = (max_h, max_w) of a RoiInput's table: the _roi_f32 forms."""
         fixed = slot.fixed
         src, dst = device.ptr(staged.staging), device.ptr(fixed)
         n, c, dst_hw = fixed.shape[0], fixed.shape[1], fixed.shape[2:]
-        how = (int(fmt.color == 'I420'),) if fmt.yuv else (int(fmt.u8), int(fmt.nhwc))
+        how = (int(fmt.color == 'I420'),) if fmt.yuv else (fmt.packed_kind,) if fmt.packed else (int(fmt.u8), int(fmt.nhwc))
         pre = (int(fmt.reverse), device.ptr(slot.mean), device.ptr(slot.std))
         if largest is not None:
             where = (src, dst, device.ptr(slot.rois), n, staged.frames)
             if fmt.yuv:
                 device.call('pvhip_input_preprocess_yuv_roi_f32', *where, *staged.extent, *dst_hw, *largest, *how, *pre)
+            elif fmt.packed:
+                device.call('pvhip_input_preprocess_packed_roi_f32', *where, *staged.extent, *dst_hw, *largest, *how, *pre)
             else:
                 device.call('pvhip_input_preprocess_roi_f32', *where, c, *staged.extent, *dst_hw, *largest, *how, *pre)
         elif fmt.yuv:
             device.call('pvhip_input_preprocess_yuv_f32', src, dst, n, *staged.extent, *dst_hw, *how, *pre)
+        elif fmt.packed:
+            device.call('pvhip_input_preprocess_packed_f32', src, dst, n, *staged.extent, *dst_hw, *how, *pre)
         elif staged.preprocess:
             device.call('pvhip_input_preprocess_f32', src, dst, n, c, *staged.extent, *dst_hw, *how, *pre)
         elif staged.staging is not fixed:

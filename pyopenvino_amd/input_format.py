@@ -6,6 +6,11 @@ import dataclasses
 
 import numpy as np
 
+# color formats whose frames are YUV 4:2:0 planes, (n, 3 h / 2, w), and those whose frames are rows of 4-byte units with the `kind` of
+# pvhip_input_preprocess_packed_f32: packed YUV 4:2:2 (n, h, w, 2) and four-byte pixels (n, h, w, 4)
+YUV420_FORMATS = ('NV12', 'I420')
+PACKED_KINDS = {'YUY2': 0, 'UYVY': 1, 'BGRX': 2, 'RGBX': 3}
+
 
 @dataclasses.dataclass(frozen=True, eq=False)
 class InputFormat:
@@ -13,7 +18,8 @@ class InputFormat:
     ``dims`` the (n, c, h, w) of the fp32 tensor the IR expects, ``supported`` / ``declared`` as InputInfo has them, ``u8`` / ``nhwc`` the
     declared precision and layout, ``resize`` / ``reverse`` / ``mean`` / ``std`` the declared preprocessing (fp32 arrays of c values, or
     None without MEAN_VALUE), ``color`` the declared colour format: 'RAW', or 'NV12' / 'I420' for YUV 4:2:0 frames, uint8 of shape
-    (n, 3 h / 2, w) whatever ``u8`` / ``nhwc`` say.  An extent is the (h, w) of a caller's image.  A RoiInput's frames have the same
+    (n, 3 h / 2, w), or 'YUY2' / 'UYVY' for packed YUV 4:2:2 frames, uint8 of shape (n, h, w, 2), or 'BGRX' / 'RGBX' for four-byte
+    pixels, uint8 of shape (n, h, w, 4), whatever ``u8`` / ``nhwc`` say.  An extent is the (h, w) of a caller's image.  A RoiInput's frames have the same
     shapes with their own count m in place of n (``host_shape(extent, frames=m)``, ``frames_extent_of``) and a table ``checked_rois``
     accepts."""
     name: str
@@ -30,11 +36,26 @@ class InputFormat:
 
     @property
     def yuv(self) -> bool:
-        return self.color != 'RAW'
+        """YUV 4:2:0 frames (NV12, I420)."""
+        return self.color in YUV420_FORMATS
+
+    @property
+    def packed(self) -> bool:
+        """Frames of 4-byte units (YUY2, UYVY, BGRX, RGBX): ``packed_kind`` is their `kind` for pvhip_input_preprocess_packed_f32 and
+        ``packed_bytes`` the trailing axis of their arrays: 2 bytes per pixel of 4:2:2, 4 of an X format."""
+        return self.color in PACKED_KINDS
+
+    @property
+    def packed_kind(self) -> int:
+        return PACKED_KINDS[self.color]
+
+    @property
+    def packed_bytes(self) -> int:
+        return 2 if self.packed_kind < 2 else 4
 
     @property
     def host_dtype(self):
-        return np.dtype(np.uint8 if self.u8 or self.yuv else np.float32)
+        return np.dtype(np.uint8 if self.u8 or self.yuv or self.packed else np.float32)
 
     def host_shape(self, extent=None, frames=None):
         """The shape of a caller's array of `extent` (default: the network's own) in this layout; `frames` = m: of the m frames of a
@@ -44,14 +65,19 @@ class InputFormat:
         h, w = extent if extent is not None else self.dims[2:]
         if self.yuv:
             return n, (h // 2 * 3 if isinstance(h, int) else '3h/2'), w
+        if self.packed:
+            return n, h, w, self.packed_bytes
         return (n, h, w, c) if self.nhwc else (n, c, h, w)
 
     def checked_extent(self, source_size=None):
-        """The (h, w) a caller's image has: `source_size` with RESIZE_BILINEAR declared, else the network's own (even, for YUV 4:2:0)."""
+        """The (h, w) a caller's image has: `source_size` with RESIZE_BILINEAR declared, else the network's own (even, for YUV 4:2:0; of even width, for
+        packed YUV 4:2:2)."""
         n, c, h, w = self.dims
         sh, sw = (int(v) for v in source_size) if source_size is not None else (h, w)
         if self.yuv and (sh % 2 or sw % 2):
             raise ValueError('input {}: {} frames have an even height and width, not {}'.format(self.name, self.color, (sh, sw)))
+        if self.packed and self.packed_bytes == 2 and sw % 2:
+            raise ValueError('input {}: {} frames have an even width, not {}'.format(self.name, self.color, (sh, sw)))
         if source_size is None:
             return h, w
         if (sh, sw) != (h, w) and not self.resize:
@@ -65,6 +91,8 @@ class InputFormat:
         """(h, w) of the caller's array `a`, checked against this format."""
         if self.yuv:
             return self._yuv_extent_of(a)
+        if self.packed:
+            return self._packed_extent_of(a)
         declared = 'declared {} / {}'.format('U8' if self.u8 else 'FP32', 'NHWC' if self.nhwc else 'NCHW')
         if not self.resize:
             if a.shape != self.host_shape():
@@ -86,6 +114,20 @@ class InputFormat:
                 self.name, declared, self.host_shape(('h', 'w')), a.shape))
         return self.checked_extent((a.shape[1] // 3 * 2, a.shape[2]))
 
+    def _packed_any_hw(self):
+        return 'any h and even w' if self.packed_bytes == 2 else 'any h, w'
+
+    def _packed_extent_of(self, a):
+        declared = 'declared {}'.format(self.color)
+        if not self.resize:
+            if a.shape != self.host_shape():
+                raise ValueError('input {}: {} means shape {}, got {}'.format(self.name, declared, self.host_shape(), a.shape))
+            return tuple(self.dims[2:])
+        if a.ndim != 4 or a.shape[0] != self.dims[0] or a.shape[3] != self.packed_bytes:
+            raise ValueError('input {}: {} with RESIZE_BILINEAR means shape {} for {}; got {}'.format(
+                self.name, declared, self.host_shape(('h', 'w')), self._packed_any_hw(), a.shape))
+        return self.checked_extent(a.shape[1:3])
+
     def _roi_declared(self):
         if not self.resize:
             raise ValueError('input {}: a RoiInput is cropped and resized on the device: it needs a declared resize '
@@ -104,6 +146,9 @@ class InputFormat:
         if self.yuv:
             ok = a.ndim == 3 and a.shape[0] >= 1 and a.shape[1] % 3 == 0
             declared, any_hw = 'declared {}'.format(self.color), 'any even h, w'
+        elif self.packed:
+            ok = a.ndim == 4 and a.shape[0] >= 1 and a.shape[3] == self.packed_bytes
+            declared, any_hw = 'declared {}'.format(self.color), self._packed_any_hw()
         else:
             ok = a.ndim == 4 and a.shape[0] >= 1 and a.shape[3 if self.nhwc else 1] == self.dims[1]
             declared, any_hw = 'declared {} / {}'.format('U8' if self.u8 else 'FP32', 'NHWC' if self.nhwc else 'NCHW'), 'any h, w'
@@ -112,7 +157,7 @@ class InputFormat:
                 self.name, declared, self.host_shape(('h', 'w'), frames='m'), any_hw, a.shape))
         if self.yuv:
             return self.checked_extent((a.shape[1] // 3 * 2, a.shape[2])), a.shape[0]
-        return self.checked_extent(a.shape[1:3] if self.nhwc else a.shape[2:4]), a.shape[0]
+        return self.checked_extent(a.shape[1:3] if self.nhwc or self.packed else a.shape[2:4]), a.shape[0]
 
     def checked_rois(self, rois, extent, frames):
         """The table of a RoiInput over `frames` frames of `extent` as a C-contiguous int32 (n, 5) array, and the (max h, max w) of its
@@ -138,9 +183,9 @@ class InputFormat:
         return np.ascontiguousarray(t, np.int32), (int(h.max()), int(w.max()))
 
     def needs_preprocess(self, extent) -> bool:
-        """Arrays of `extent` go through pvhip_input_preprocess_f32 (YUV frames: pvhip_input_preprocess_yuv_f32, always): something
-        besides the format change is in effect."""
-        return tuple(extent) != tuple(self.dims[2:]) or self.reverse or self.mean is not None or self.yuv
+        """Arrays of `extent` go through pvhip_input_preprocess_f32 (YUV 4:2:0 frames: pvhip_input_preprocess_yuv_f32, frames of 4-byte
+        units: pvhip_input_preprocess_packed_f32, always): something besides the format change is in effect."""
+        return tuple(extent) != tuple(self.dims[2:]) or self.reverse or self.mean is not None or self.yuv or self.packed
 
     def needs_convert(self, extent) -> bool:
         """Arrays of `extent` are not the fp32 NCHW tensor itself: they are uploaded into a staging tensor and converted by one launch."""
@@ -152,10 +197,10 @@ class RoiInput:
     sizeY})``): ``infer({name: RoiInput(frames, rois)})``.  `frames`: m >= 1 source frames in the input's declared host format -- the
     leading count is m, whatever the batch n --; `rois`: an integer (n, 5) table, row b = (id, x, y, w, h): batch row b is the rectangle
     [y, y + h) x [x, x + w) of frame id, cropped and then resized to the network's extent, reversed and scaled as declared, on the
-    device in one launch (pvhip_input_preprocess_roi_f32 / _yuv_roi_f32).  The frames are uploaded once, however many rows read them, and
+    device in one launch (pvhip_input_preprocess_roi_f32 / _yuv_roi_f32 / _packed_roi_f32).  The frames are uploaded once, however many rows read them, and
     are not modified.  The input needs ``preprocess_info.resize_algorithm = 'RESIZE_BILINEAR'``.  The bilinear taps clamp at the edge
     of the rectangle, not of the frame; a rectangle of exactly the network's extent is copied; an NV12 / I420 rectangle may have an odd
-    origin and odd sizes (only the frame's extent is even).  With `frames` = ``InferRequest.input_buffer(name, (h, w), frames=m)`` and
+    origin and odd sizes (only the frame's extent is even), and so may a YUY2 / UYVY one (only the frame's width is even).  With `frames` = ``InferRequest.input_buffer(name, (h, w), frames=m)`` and
     `rois` = ``InferRequest.roi_buffer(name)`` nothing is copied on the host."""
     __slots__ = ('frames', 'rois')
 
@@ -242,7 +287,8 @@ class InputInfo:
     (``pvhip_input_to_nchw_f32``); an input whose format is never set goes the default way.  ``preprocess_info`` adds a resize of a source
     of any extent, channel reversal and mean / scale to that launch (``pvhip_input_preprocess_f32``); its ``color_format`` 'NV12' /
     'I420' makes the array a decoder's YUV 4:2:0 frames, uint8 of shape (n, 3 h / 2, w), converted to B, G, R in that launch
-    (``pvhip_input_preprocess_yuv_f32``)."""
+    (``pvhip_input_preprocess_yuv_f32``), 'YUY2' / 'UYVY' a camera's packed YUV 4:2:2 frames, uint8 of shape (n, h, w, 2), and 'BGRX' /
+    'RGBX' a screen capture's four-byte pixels, uint8 of shape (n, h, w, 4) (``pvhip_input_preprocess_packed_f32``)."""
     PRECISIONS = ('FP32', 'U8')
     LAYOUTS = ('NCHW', 'NHWC')
 
@@ -250,7 +296,7 @@ class InputInfo:
         self._net, self._nid = net, nid
         self._precision, self._layout = 'FP32', 'NCHW'
         self.declared = False           # precision or layout set explicitly (to any value)
-        self._precision_set = False     # precision set explicitly: 'FP32' then contradicts a YUV color_format
+        self._precision_set = False     # precision set explicitly: 'FP32' then contradicts a color_format other than 'RAW'
         self._pre = None                # PreProcessInfo, once preprocess_info has been asked for
 
     @property
@@ -346,7 +392,7 @@ class InputInfo:
                 raise ValueError('input {}: color_format {} frames are U8, precision {} is declared'.format(
                     self.name, pre.color_format, self._precision))
             if pre.resize_algorithm == 'NO_RESIZE':
-                self.frozen().checked_extent()     # the frames have the network's extent: an even one
+                self.frozen().checked_extent()     # the frames have the network's extent: a legal one for the format (even; 4:2:2: even w)
 
     def source_extent(self, source_size=None):
         """The (h, w) a caller's array has: `source_size` with RESIZE_BILINEAR declared, else the network's own."""
@@ -404,12 +450,25 @@ class PreProcessInfo:
         w even: h rows of Y, then for NV12 h / 2 rows of w / 2 interleaved (U, V) pairs, for I420 the U plane and the V plane of
         h / 2 x w / 2 bytes each.  The device converts them to B, G, R (BT.601 limited range in 20-bit integers, the chroma of a pixel's
         2 x 2 block; pvhip_input_preprocess_yuv_f32) and resizes, reverses (R, G, B) and scales that image as it does a U8 B, G, R one.
-        The Parameter has 3 channels; ``precision`` is U8 by implication ('FP32' declared beside it is refused at load), ``layout`` is
-        not consulted.
+        Or 'YUY2' / 'UYVY' / 'BGRX' / 'RGBX': the array holds frames of 4-byte units, converted by pvhip_input_preprocess_packed_f32
+        (the same rule in numpy: tests/packed_ref.py):
+          - YUY2 / UYVY (packed YUV 4:2:2, a camera's or a capture card's frames): uint8 of shape (n, h, w, 2), the (h, w, 2) array
+            ``cv2.cvtColor(..., COLOR_YUV2BGR_YUY2 / _UYVY)`` takes; w even, h any value >= 1.  Each row is w / 2 groups of 4 bytes:
+            Y0 U Y1 V for YUY2, U Y0 V Y1 for UYVY.  Pixel (y, x) has luma Y[x & 1] of group x // 2 of row y, and that group's (U, V):
+            chroma is not interpolated.  Each pixel goes to B, G, R by exactly the integer rule of NV12 / I420 (BT.601 limited range
+            over 2^20, arithmetic shifts, clamp to [0, 255]): the same function, not a second set of constants.
+          - BGRX / RGBX (four-byte pixels, a screen capture's or a read-back's frames): uint8 of shape (n, h, w, 4), any h, w >= 1.
+            The B, G, R image is ``frames[..., 0:3]`` for BGRX and ``frames[..., 2::-1]`` for RGBX; byte 3 is never read into the
+            result, whatever it holds.
+        The resulting uint8 B, G, R image is resized, reversed (R, G, B) and scaled bit for bit as a U8 NHWC source is.  The rectangle
+        of a RoiInput is the crop of the converted frame: a 4:2:2 pixel keeps the chroma of its absolute column pair, so rectangles
+        may start on odd x and have odd w.
+        For every format but 'RAW' the Parameter has 3 channels; ``precision`` is U8 by implication ('FP32' declared beside it is
+        refused at load), ``layout`` is not consulted; without a declared resize the network's own extent must be legal for the format.
     Set between ``read_network`` and ``load_network``, like ``precision``; setting anything makes the input declared."""
     RESIZE_ALGORITHMS = ('NO_RESIZE', 'RESIZE_BILINEAR')
     MEAN_VARIANTS = ('NONE', 'MEAN_VALUE')
-    COLOR_FORMATS = ('RAW', 'NV12', 'I420')
+    COLOR_FORMATS = ('RAW', 'NV12', 'I420', 'YUY2', 'UYVY', 'BGRX', 'RGBX')
 
     def __init__(self, info):
         self._info = info
