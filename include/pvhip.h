@@ -539,6 +539,30 @@ int pvhip_detections_to_rois(const float* records, int* rois, int* record_of, in
  * PVHIP_EINVAL and nothing is launched. */
 int pvhip_topk_rows_f32(const float* x, int rows, int cols, int k, int* indices, float* values);
 
+/* ---------------------------------------------------------------- a detector's answer ------ */
+/* Addition to ABI v18 (the version number is unchanged: nothing existing changed): the records of pvhip_detection_output_f32 become one
+ * flat table of the detections a caller wants -- what the reference's sample makes on the host with `for record in res.reshape(100, 7):
+ * if conf > 0.5: x0 = int(xmin * img_w) ...` -- so that only the survivors are read back.  `records`: images * records_per_image rows of
+ * [rank, label, score, xmin, ymin, xmax, ymax], image b being rows [b P, (b + 1) P).  `live`, `selected` and the rectangle (x0, y0, w, h)
+ * over (frame_h, frame_w) are exactly those of pvhip_detections_to_rois above (one device function serves both): an image's list ends at
+ * its first row whose column 0 is not >= 0; a live row is selected when score >= min_confidence, its four corners are finite and (labels
+ * == NULL or) its label equals (float)labels[j] for some j < num_labels <= 64; x0 = floor(min(max(xmin * frame_w, 0), frame_w)), x1 =
+ * ceil(min(max(xmax * frame_w, 0), frame_w)) in fp32, never contracted, y0 / y1 alike with frame_h; dropped when x1 - x0 < min_w or
+ * y1 - y0 < min_h.  selected[b] counts the survivors of image b.  New here:
+ *   cap     image b keeps its first counts[b] = min(selected[b], max_per_image) survivors in position order (its best scores: an image's
+ *           records stand in descending score order);
+ *   table   the kept survivors of all images stand in (image, position) order without a gap between images; total = sum(counts);
+ *   row     one survivor is eight 32-bit words (b, x0, y0, w, h, label, score bits, record): label = (int32) of column 1 when that is
+ *           finite and in [-2^31, 2^31), else -1; score bits are the record's own; record = b P + p.  Rows >= total are not written.
+ * header = counts[images], then selected[images], then total: 2 * images + 1 ints.  `rows` holds images * min(P, max_per_image) rows of
+ * 32 bytes and is 16-byte aligned.  The same rule in numpy: tests/detections_ref.py, matched word for word.  Two launches on the current
+ * stream (count, then write: one wave per image; no atomics, no wait of one workgroup on another, so the result does not depend on
+ * timing), no allocation, no workspace.  images, records_per_image, min_h, min_w, max_per_image >= 1, images * records_per_image <
+ * 2^31 / 7, frame_h, frame_w in [1, 2^24], `labels` NULL (any label; num_labels == 0) or a device pointer with num_labels <= 64 (a
+ * non-NULL `labels` with num_labels == 0 selects nothing), no NULL records / header / rows; else PVHIP_EINVAL and nothing is launched. */
+int pvhip_detections_compact(const float* records, int images, int records_per_image, int frame_h, int frame_w, float min_confidence,
+                             const int* labels, int num_labels, int min_h, int min_w, int max_per_image, int* header, int* rows);
+
 /* ---------------------------------------------------------------- multi-GPU gather ---------- */
 /* No reference counterpart (the reference is single-process).  Batch shards are independent; the only
  * exchange is an all-gather of the Result tensor over RCCL/xGMI.  unique_id is a 128-byte buffer. */

@@ -5,7 +5,8 @@ holds one module per IR layer type exposing ``compute(node, inputs, kernel_type,
 body is a hand-written HIP kernel reached through the C ABI of ``libpvhip.so`` (``include/pvhip.h``).
 """
 from .inference_engine import IECore, IENetwork, Executable_Network  # noqa: F401
+from .detections import Detections, DetectionScreen  # noqa: F401
 from .input_format import DetectedRois, RoiInput  # noqa: F401
 from .top_k import TopK  # noqa: F401
 
-__all__ = ['IECore', 'IENetwork', 'Executable_Network', 'RoiInput', 'DetectedRois', 'TopK']
+__all__ = ['IECore', 'IENetwork', 'Executable_Network', 'RoiInput', 'DetectedRois', 'TopK', 'Detections', 'DetectionScreen']

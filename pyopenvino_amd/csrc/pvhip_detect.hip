@@ -20,6 +20,7 @@
 #include <cmath>
 
 #include "pvhip_common.h"
+#include "pvhip_detect_rule.h"
 
 using namespace pvhip;
 
@@ -249,7 +250,7 @@ struct RoiArgs {
 };
 
 constexpr int kRoiImages = 4096;  // list ends held in LDS at once
-constexpr int kRoiLabels = 64;
+constexpr int kRoiLabels = kScreenLabels;
 
 __global__ __launch_bounds__(kDetBlock) void detections_to_rois_kernel(RoiArgs a) {
     __shared__ int   ends[kRoiImages];
@@ -275,24 +276,12 @@ __global__ __launch_bounds__(kDetBlock) void detections_to_rois_kernel(RoiArgs a
         for (int c0 = r0; c0 < r1; c0 += kDetBlock, flip ^= 1) {
             const int r = c0 + tid;
             bool keep = false;
-            int b = 0, x0 = 0, y0 = 0, w = 0, h = 0;
+            int b = 0;
+            DetectionRect q{0, 0, 0, 0};
             if (r < r1) {
                 b = r / P;
-                const float* q = a.rec + (size_t)r * 7;
-                const float label = q[1], score = q[2], xa = q[3], ya = q[4], xb = q[5], yb = q[6];
-                keep = r - b * P < ends[b - b0] && score >= a.conf && isfinite(xa) && isfinite(ya) && isfinite(xb) && isfinite(yb);
-                if (keep && a.labels != nullptr) {
-                    bool listed = false;
-                    for (int j = 0; j < a.num_labels; ++j) listed = listed || label == labels[j];
-                    keep = listed;
-                }
-                if (keep) {
-                    x0 = (int)floorf(fminf(fmaxf(xa * fw, 0.0f), fw));
-                    y0 = (int)floorf(fminf(fmaxf(ya * fh, 0.0f), fh));
-                    w  = (int)ceilf(fminf(fmaxf(xb * fw, 0.0f), fw)) - x0;
-                    h  = (int)ceilf(fminf(fmaxf(yb * fh, 0.0f), fh)) - y0;
-                    keep = w >= a.min_w && h >= a.min_h;
-                }
+                keep = r - b * P < ends[b - b0] &&
+                       detection_screen(a.rec + (size_t)r * 7, a.conf, labels, a.labels != nullptr, a.num_labels, fh, fw, a.min_h, a.min_w, q);
             }
             const unsigned long long votes = __ballot(keep);
             const int rank = __builtin_amdgcn_mbcnt_hi((unsigned)(votes >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)votes, 0u));
@@ -308,7 +297,7 @@ __global__ __launch_bounds__(kDetBlock) void detections_to_rois_kernel(RoiArgs a
             const long long k = (long long)base + before + rank;
             if (keep && k < a.n) {
                 int* o = a.rois + 5 * (size_t)k;
-                o[0] = b; o[1] = x0; o[2] = y0; o[3] = w; o[4] = h;
+                o[0] = b; o[1] = q.x0; o[2] = q.y0; o[3] = q.w; o[4] = q.h;
                 a.rec_of[k] = r;
             }
             base += total;

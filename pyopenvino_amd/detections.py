@@ -1,0 +1,235 @@
+"""A detector's answer (``infer(..., detections=screen)``): the rule, the argument checks and the device launch.
+
+The rule (include/pvhip.h, pvhip_detections_compact; tests/detections_ref.py is the same again).  Records are [rank, label, score, xmin,
+ymin, xmax, ymax] with normalised corners; image b is rows [b P, (b + 1) P) of the R = images P rows.
+  live      an image's list ends at its first row whose column 0 is not >= 0 (DetectionOutput's -1 terminator; NaN too): that row and
+            everything behind it is ignored;
+  selected  live, score >= float32(min_confidence) (false for NaN), four finite corners, and `labels` is None or label == float32(l) for
+            a listed l (at most 64; [] selects nothing);
+  rectangle over frames of (H, W), in float32, never contracted: x0 = floor(min(max(xmin W, 0), W)), x1 = ceil(min(max(xmax W, 0), W)),
+            y0 / y1 alike with H; dropped when x1 - x0 < min_size[1] or y1 - y0 < min_size[0]
+-- so far exactly DetectedRois' rule (pvhip_detections_to_rois, tests/detected_rois_ref.py) --;
+  cap       image b keeps its first counts[b] = min(selected[b], max_per_image) survivors in position order: its best scores, because
+            an image's records stand in descending score order;
+  table     the kept survivors of all images in (image, position) order, no gap between images; total = sum(counts);
+  row       (b, x0, y0, w, h, label, score bits, record): label = int32 of column 1 (truncated) when that is finite and in
+            [-2^31, 2^31), else -1; the score's bits are the record's own; record = b P + p."""
+import collections
+import ctypes
+
+import numpy as np
+
+from . import device
+
+MAX_LABELS = 64
+MAX_EXTENT = 1 << 24                 # a frame extent is exact as float32
+_INT32_MAX = int(np.iinfo(np.int32).max)
+
+_Detections = collections.namedtuple('Detections', 'counts selected rois labels scores records')
+_Screen = collections.namedtuple('DetectionScreen', 'min_confidence frame_size labels min_size max_per_image')
+
+
+class Detections(_Detections):
+    """What a detector's Result started with detections=... comes back as: `counts` and `selected` (images,) int32 -- the rows image b
+    has in the table, and the records of it that passed the screen (more when the cap cut them) --; `rois` (total, 5) int32 in RoiInput's
+    (id, x, y, w, h) order, id = the image; `labels` (total,) int32; `scores` (total,) float32; `records` (total,) int32, the flat row of
+    the Result each came from.  total = counts.sum(); image b is rows [counts[:b].sum(), counts[:b + 1].sum())."""
+    __slots__ = ()
+
+    def of(self, b: int) -> tuple:
+        """(rois, labels, scores, records) of image b: slices of the table."""
+        images = len(self.counts)
+        if not -images <= b < images:
+            raise IndexError('image {} of {}'.format(b, images))
+        b = b % images
+        lo = int(self.counts[:b].sum())
+        rows = slice(lo, lo + int(self.counts[b]))
+        return self.rois[rows], self.labels[rows], self.scores[rows], self.records[rows]
+
+
+class DetectionScreen(_Screen):
+    """Which of a detector's records come back, and over which frames: score >= `min_confidence`; rectangles over frames of `frame_size`
+    = (H, W) (None: the extent of the network's single 4-D Parameter as declared); `labels`: None (any) or at most 64 ints; rectangles
+    of at least `min_size` = (h, w); at most `max_per_image` per image (None: all).  Immutable; the values are checked when a pass is
+    started with it (ValueError)."""
+    __slots__ = ()
+
+    def __new__(cls, min_confidence=0.5, frame_size=None, labels=None, min_size=(1, 1), max_per_image=None):
+        frozen = [_frozen(v) for v in (frame_size, labels, min_size)]
+        return super().__new__(cls, min_confidence, frozen[0], frozen[1], frozen[2], max_per_image)
+
+
+def _frozen(v):
+    """A list, range or 1-D array as a tuple, so that a screen is a key; anything else as it is, for resolved() to judge."""
+    if isinstance(v, np.ndarray):
+        return tuple(v.tolist()) if v.ndim == 1 else v
+    return tuple(v) if isinstance(v, (list, range)) else v
+
+
+def _count(v, hi=_INT32_MAX):
+    return not isinstance(v, bool) and isinstance(v, (int, np.integer)) and 1 <= v <= hi
+
+
+def _pair(v, hi):
+    return isinstance(v, tuple) and len(v) == 2 and all(_count(e, hi) for e in v)
+
+
+def resolved(screen, per_image: int, extent=None, what='') -> DetectionScreen:
+    """`screen` (a DetectionScreen, or a number: its min_confidence) with every value checked and in its one form -- a float, tuples of
+    ints, frame_size filled in from `extent`, max_per_image from `per_image` = P --, so that equal screens are equal keys; ValueError."""
+    if not isinstance(screen, DetectionScreen):
+        screen = DetectionScreen(min_confidence=screen)
+    conf, frame, labels, size, cap = screen
+    if isinstance(conf, bool) or not isinstance(conf, (int, float, np.integer, np.floating)) or not np.isfinite(conf):
+        raise ValueError('detections: {}min_confidence {!r} is not a finite number'.format(what, conf))
+    if labels is not None:
+        if not isinstance(labels, tuple) or len(labels) > MAX_LABELS or not all(
+                not isinstance(l, bool) and isinstance(l, (int, np.integer)) and -_INT32_MAX - 1 <= l <= _INT32_MAX for l in labels):
+            raise ValueError('detections: {}labels is None or at most {} ints, got {!r}'.format(what, MAX_LABELS, labels))
+        labels = tuple(int(l) for l in labels)
+    if not _pair(size, _INT32_MAX):
+        raise ValueError('detections: {}min_size is (h, w) with both >= 1, got {!r}'.format(what, size))
+    if frame is None:
+        frame = extent
+        if frame is None:
+            raise ValueError('detections: {}frame_size is needed: the network has no single 4-D Parameter to take it from'.format(what))
+    if not _pair(frame, MAX_EXTENT):
+        raise ValueError('detections: {}frame_size is (H, W) with both in 1 .. 2^24, got {!r}'.format(what, frame))
+    if cap is None:
+        cap = per_image
+    if not _count(cap):
+        raise ValueError('detections: {}max_per_image is None or a count >= 1, got {!r}'.format(what, cap))
+    return DetectionScreen(float(conf), (int(frame[0]), int(frame[1])), labels, (int(size[0]), int(size[1])), min(int(cap), int(per_image)))
+
+
+def compact_records(records, images: int, screen) -> Detections:
+    """The rule in numpy on a host array of float32 records, (1, 1, R, 7) or (R, 7), of `images` images: what a Result computed on the
+    host (a foreign plugin set) gets.  `screen`: a DetectionScreen with a frame_size (there is no network here to take it from)."""
+    rec = np.asarray(records)
+    if rec.dtype != np.float32 or rec.ndim not in (2, 4) or rec.shape[-1] != 7 or tuple(rec.shape[:-2]) not in ((), (1, 1)) or rec.shape[-2] < 1:
+        raise ValueError('detections: float32 records of shape (1, 1, R, 7) or (R, 7), got {} {}'.format(rec.dtype, rec.shape))
+    if not _count(images) or rec.shape[-2] % images:
+        raise ValueError('detections: {} records do not divide into {!r} images'.format(rec.shape[-2], images))
+    rec = rec.reshape(-1, 7)
+    N, P = int(images), rec.shape[0] // int(images)
+    conf, (H, W), labels, (min_h, min_w), cap = resolved(screen, P)
+    dead = ~(rec[:, 0] >= 0).reshape(N, P)
+    end = np.where(dead.any(axis=1), dead.argmax(axis=1), P)
+    keep = (np.arange(P)[None, :] < end[:, None]).ravel()
+    keep &= (rec[:, 2] >= np.float32(conf)) & np.isfinite(rec[:, 3:7]).all(axis=1)
+    if labels is not None:
+        keep &= np.isin(rec[:, 1], np.asarray(labels, np.int64).astype(np.float32))
+    corners = np.where(keep[:, None], rec[:, 3:7], np.float32(0))
+
+    def edge(v, extent, rounded):
+        e = np.float32(extent)
+        with np.errstate(over='ignore'):
+            return rounded(np.minimum(np.maximum(v * e, np.float32(0)), e)).astype(np.int32)
+
+    x0, y0 = edge(corners[:, 0], W, np.floor), edge(corners[:, 1], H, np.floor)
+    w, h = edge(corners[:, 2], W, np.ceil) - x0, edge(corners[:, 3], H, np.ceil) - y0
+    keep &= (w >= min_w) & (h >= min_h)
+    keep = keep.reshape(N, P)
+    selected = keep.sum(axis=1).astype(np.int32)
+    kept = np.flatnonzero((keep & (np.cumsum(keep, axis=1) <= cap)).ravel())
+    label = rec[kept, 1]
+    whole = np.isfinite(label) & (label >= np.float32(-2.0 ** 31)) & (label < np.float32(2.0 ** 31))
+    with np.errstate(invalid='ignore'):
+        label = np.where(whole, np.where(whole, label, np.float32(0)).astype(np.int32), np.int32(-1)).astype(np.int32)
+    rois = np.stack([(kept // P).astype(np.int32), x0[kept], y0[kept], w[kept], h[kept]], axis=1).astype(np.int32).reshape(-1, 5)
+    return Detections(np.minimum(selected, cap).astype(np.int32), selected, rois, label, rec[kept, 2].copy(), kept.astype(np.int32))
+
+
+def records_of(port, batch: int):
+    """P, the records per image, of a Result whose input port is declared (1, 1, R, 7) with R a multiple of `batch`; None for any other
+    shape."""
+    dims = tuple(int(d) for d in port['dims'])
+    if len(dims) != 4 or dims[:2] != (1, 1) or dims[3] != 7 or dims[2] < 1 or dims[2] % batch:
+        return None
+    return dims[2] // batch
+
+
+def _declared_extent(ienet):
+    """(H, W) of the network's single 4-D Parameter as declared, or None."""
+    shapes = [tuple(int(d) for d in ienet.G.nodes[nid]['data']['shape']) for nid, _ in ienet.find_node_by_type('Parameter')]
+    shapes = [s for s in shapes if len(s) == 4]
+    return (shapes[0][2], shapes[0][3]) if len(shapes) == 1 else None
+
+
+def checked(ienet, detections, sharded: bool) -> dict:
+    """{Result name: resolved DetectionScreen} of the `detections` argument of infer() / start_async() -- a DetectionScreen or a
+    min_confidence for every detector Result, or {Result name: either} --, {} for None.  Everything is looked up in the network as it
+    was read: no device is needed, nothing is allocated."""
+    if detections is None:
+        return {}
+    results = {name: next(iter(ienet.G.nodes[nid]['input'].values())) for nid, name in ienet.find_node_by_type('Result')}
+    batch = int(ienet.batch_size)
+    if isinstance(detections, dict):
+        unknown = [name for name in detections if name not in results]
+        if unknown:
+            raise ValueError('detections: the network has no Result named {!r} (it has {})'.format(unknown[0], sorted(results)))
+        wanted = dict(detections)
+    else:
+        wanted = {name: detections for name, port in results.items() if records_of(port, batch) is not None and port['precision'] == 'FP32'}
+        if not wanted:
+            described = ', '.join('{!r} {} {}'.format(name, port['precision'], tuple(port['dims'])) for name, port in sorted(results.items()))
+            raise ValueError('detections: the network has no FP32 Result of shape (1, 1, R, 7) with R a multiple of the batch {} (it has {})'.format(
+                batch, described))
+    if wanted and sharded:
+        raise ValueError('detections: not with a batch sharded over ranks')
+    out = {}
+    for name, screen in wanted.items():
+        port = results[name]
+        per_image = records_of(port, batch)
+        if per_image is None:
+            raise ValueError('detections: Result {!r} has shape {}: not (1, 1, R, 7) with R a multiple of the batch {}'.format(
+                name, tuple(port['dims']), batch))
+        if port['precision'] != 'FP32':
+            raise ValueError('detections: Result {!r} is {}: FP32 Results only'.format(name, port['precision']))
+        if batch * per_image >= (1 << 31) // 7:
+            raise ValueError('detections: Result {!r} has too many records ({} x {})'.format(name, batch, per_image))
+        out[name] = resolved(screen, per_image, _declared_extent(ienet), 'Result {!r}: '.format(name))
+    return out
+
+
+def _split(table, total: int) -> tuple:
+    """(rois, labels, scores, records) of the first `total` rows of an (n, 8) int32 table of the kernel's rows; the caller's own arrays."""
+    t = table[:total]
+    return t[:, :5].copy(), t[:, 5].copy(), t[:, 6].copy().view(np.float32), t[:, 7].copy()
+
+
+class Blocks:
+    """What a request keeps for one (Result name, resolved screen): the device header (counts, selected, total) and rows that
+    pvhip_detections_compact writes, the labels on the device (uploaded once, here), and the page-locked host twins of header and rows
+    that wait() reads back into: the header, then exactly 32 total bytes."""
+    __slots__ = ('images', 'per_image', 'screen', 'header', 'rows', 'labels', 'header_host', 'rows_host')
+
+    def __init__(self, images: int, per_image: int, screen: DetectionScreen):
+        self.images, self.per_image, self.screen = images, per_image, screen
+        capacity = images * min(per_image, screen.max_per_image)
+        self.header = device.DeviceTensor.empty((2 * images + 1,), np.int32)
+        self.rows = device.DeviceTensor.empty((capacity, 8), np.int32)
+        self.header_host = device.host_empty((2 * images + 1,), np.int32)
+        self.rows_host = device.host_empty((capacity, 8), np.int32)
+        # ([]: a device pointer with no label behind it, which selects nothing; None: NULL, any label)
+        self.labels = None if screen.labels is None else device.DeviceTensor.from_numpy(np.asarray(screen.labels + (0,), np.int32))
+
+    def launch(self, result):
+        """The entry's two launches on the current stream, behind whatever wrote `result` there."""
+        s = self.screen
+        assert result.dtype == np.float32 and int(np.prod(result.shape)) == 7 * self.images * self.per_image
+        device.call('pvhip_detections_compact', device.ptr(result), self.images, self.per_image, s.frame_size[0], s.frame_size[1],
+                    s.min_confidence, device.ptr(self.labels), 0 if s.labels is None else len(s.labels), s.min_size[0], s.min_size[1],
+                    s.max_per_image, ctypes.c_void_p(self.header.ptr), ctypes.c_void_p(self.rows.ptr))
+
+    def read_back(self) -> Detections:
+        """The answer, copied on the current stream, which has drained: the header, then the rows it counts; the arrays are the
+        caller's own."""
+        n = self.images
+        device.call('pvhip_memcpy_d2h', ctypes.c_void_p(self.header_host.ctypes.data), ctypes.c_void_p(self.header.ptr), self.header_host.nbytes)
+        total = int(self.header_host[2 * n])
+        if not 0 <= total <= self.rows_host.shape[0]:
+            raise device.PvhipError('pvhip_detections_compact left total = {} of at most {} rows'.format(total, self.rows_host.shape[0]))
+        if total:
+            device.call('pvhip_memcpy_d2h', ctypes.c_void_p(self.rows_host.ctypes.data), ctypes.c_void_p(self.rows.ptr), 32 * total)
+        return Detections(self.header_host[:n].copy(), self.header_host[n:2 * n].copy(), *_split(self.rows_host, total))

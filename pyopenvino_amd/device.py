@@ -149,6 +149,7 @@ SIGNATURES = {
                                               _c.c_float, _c.c_float, _c.c_int, _c.c_int, _c.c_int, _c.c_int]),
     'pvhip_detections_to_rois': (_c.c_int, [_c.c_void_p] * 4 + [_c.c_int] * 5 + [_c.c_float, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int]),
     'pvhip_topk_rows_f32': (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p]),
+    'pvhip_detections_compact': (_c.c_int, [_c.c_void_p] + [_c.c_int] * 4 + [_c.c_float, _c.c_void_p] + [_c.c_int] * 4 + [_c.c_void_p] * 2),
     'pvhip_comm_unique_id': (_c.c_int, [_c.c_void_p]),
     'pvhip_comm_init': (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int]),
     'pvhip_comm_allgather_f32': (_c.c_int, [_fp, _fp, _c.c_size_t]),

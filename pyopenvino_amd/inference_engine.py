@@ -33,7 +33,7 @@ import xml.etree.ElementTree as et
 import networkx as nx
 import numpy as np
 
-from . import common_def, device, fusion_plan, stream_plan, top_k as top_k_rule
+from . import common_def, detections as detections_rule, device, fusion_plan, stream_plan, top_k as top_k_rule
 from .host_input import HostInputs
 from .input_format import DetectedRois, InputInfo, PreProcessChannel, PreProcessInfo  # noqa: F401 -- the classes of IENetwork.input_info
 from .stream_plan import CaptureStreamModel
@@ -303,21 +303,35 @@ class InferRequest:
     `top_k` = k (every Result) or {Result name: k}: those Results come back from wait() as a ``TopK`` (indices, values) of shape (n, k)
     -- the k best classes of every batch row by the rule of top_k.py -- made by one launch behind the pass and read back in one copy of
     8 n k bytes; the full Result stays on the device.  Results not named come back whole.  ValueError, before anything is staged or
-    launched: a Result whose declared shape is not (n, C) or (n, C, 1, ...), k outside 1 .. min(C, 64), an unknown name, a sharded batch."""
+    launched: a Result whose declared shape is not (n, C) or (n, C, 1, ...), k outside 1 .. min(C, 64), an unknown name, a sharded batch.
+
+    `detections` = a ``DetectionScreen``, a min_confidence, or {Result name: either}: those detector Results -- every FP32 Result declared
+    (1, 1, R, 7) for the unnamed forms -- come back from wait() as a ``Detections`` (counts, selected, rois, labels, scores, records):
+    the records that pass the screen as one flat table by the rule of detections.py, made by pvhip_detections_compact behind the pass
+    and read back in two copies, 4 (2 n + 1) bytes and 32 bytes per row; the full Result stays on the device, where a ``DetectedRois``
+    of another request reads it as before.  ValueError ('detections: ...'), before anything is staged or launched: an unknown name, a
+    Result of another shape or precision, a value of the screen out of range, a sharded batch, no such Result for an unnamed form.
+    `top_k` and `detections` may be given together, for different Results."""
 
     def __init__(self, owner, runner, index: int):
         self.owner, self.runner, self.index = owner, runner, index      # owner: the network load_network returned
         self._in_flight, self._replayed = False, None
         self._top_k = {}                # {Result name: k} of the pass in flight
+        self._detections = {}           # {Result name: resolved DetectionScreen} of the pass in flight
 
-    def start_async(self, inputs: dict, top_k=None):
-        self._start(inputs, top_k, False)
+    def start_async(self, inputs: dict, top_k=None, detections=None):
+        self._start(inputs, top_k, False, detections)
 
-    def _start(self, inputs, top_k, verbose):
+    def _start(self, inputs, top_k, verbose, detections=None):
         if self._in_flight:
             raise RuntimeError('request {} is still in flight: wait() first'.format(self.index))
         ex = self.runner
-        self._top_k = top_k_rule.checked(ex.ienet, top_k, ex.sharded or self.owner.sharded)
+        wanted = top_k_rule.checked(ex.ienet, top_k, ex.sharded or self.owner.sharded)
+        screens = detections_rule.checked(ex.ienet, detections, ex.sharded or self.owner.sharded)
+        both = sorted(set(wanted) & set(screens))
+        if both:
+            raise ValueError('detections: Result {!r} is asked for with top_k as well'.format(both[0]))
+        self._top_k, self._detections = wanted, screens
         inputs = ex.host_inputs.stage(inputs, ex.stream_base, ex.sharded or self.owner.sharded)
         ex.wait_result_readers()
         # The same device-resident tensors as the last calls: the pass is replayed from this request's own recording (one call
@@ -332,6 +346,8 @@ class InferRequest:
                 ex.run_tasks(verbose)
         if self._top_k:                          # behind the pass, replayed or eager, and outside the recording: one recording serves both
             ex.launch_top_k(self._top_k, self._replayed)
+        if self._detections:                     # likewise
+            ex.launch_detections(self._detections, self._replayed)
         self._in_flight = True
 
     def wait(self) -> dict:
@@ -342,16 +358,19 @@ class InferRequest:
         out = {}
         replayed, self._replayed = self._replayed, None
         top_k, self._top_k = self._top_k, {}
+        screens, self._detections = self._detections, {}
         for nid, name in ex.ienet.find_node_by_type('Result'):
             value = replayed['results'][name] if replayed is not None else G.nodes[nid]['result']
             if name in top_k:                    # (n, k) pairs come back; the Result itself stays where it is
                 G.nodes[nid]['result'], out[name] = value, ex.read_top_k(name, top_k[name], value)
+            elif name in screens:                # the survivors come back; the records stay where they are
+                G.nodes[nid]['result'], out[name] = value, ex.read_detections(name, screens[name], value)
             else:
                 G.nodes[nid]['result'] = out[name] = ex._read_back(value, self.owner.comm)
         return out
 
-    def infer(self, inputs: dict, top_k=None) -> dict:
-        self.start_async(inputs, top_k)
+    def infer(self, inputs: dict, top_k=None, detections=None) -> dict:
+        self.start_async(inputs, top_k, detections)
         return self.wait()
 
     def input_buffer(self, name: str, source_size=None, frames=None) -> np.ndarray:
@@ -436,6 +455,7 @@ class Executable_Network:
         # request while in flight): the next pass, eager or replayed, waits for them on the device before it can overwrite that tensor
         self._result_readers = []
         self._top_k_blocks = {}         # {(Result name, k): top_k.Blocks}: the device block and the page-locked block of a top_k pass
+        self._detection_blocks = {}     # {(Result name, resolved DetectionScreen): detections.Blocks}, likewise for a detections pass
         if input_formats is None:
             input_formats = {name: info.frozen() for name, info in ienetwork.input_info.items()}
         self.host_inputs = HostInputs(input_formats)    # host arrays in a declared format or the request's own buffers -> device tensors
@@ -489,6 +509,7 @@ class Executable_Network:
         self.host_inputs.release()                  # page-locked buffers go back once the caller holds no view of them
         self._result_readers = []
         self._top_k_blocks = {}
+        self._detection_blocks = {}
         G = self.ienet.G
         for nid in G.nodes:
             node = G.nodes[nid]
@@ -510,8 +531,8 @@ class Executable_Network:
                 event.wait()
             device.select_stream(0)
 
-    def start_async(self, request_id: int, inputs: dict, top_k=None):
-        self.requests[request_id].start_async(inputs, top_k)
+    def start_async(self, request_id: int, inputs: dict, top_k=None, detections=None):
+        self.requests[request_id].start_async(inputs, top_k, detections)
 
     def launch_top_k(self, top_k: dict, replayed):
         """pvhip_topk_rows_f32 for every Result named in `top_k` = {name: k} that the pass just issued (`replayed`: its recording, or None
@@ -540,6 +561,37 @@ class Executable_Network:
             return top_k_rule.top_k_rows(np.asarray(value), k)
         device.select_stream(self.stream_base)
         out = self._top_k_blocks[(name, k)].read_back()
+        device.select_stream(0)
+        return out
+
+    def launch_detections(self, screens: dict, replayed):
+        """pvhip_detections_compact for every Result named in `screens` = {name: resolved DetectionScreen}, exactly as launch_top_k does
+        its launch: on the base stream behind the pass that `replayed` (or the eager pass) just issued, outside the recording, with the
+        event wait_done() waits for behind it.  The blocks are this request's own, made on first use per (name, screen).  A Result that
+        is a host array gets the rule in numpy when it is read (read_detections)."""
+        G = self.ienet.G
+        values = {name: (replayed['results'][name] if replayed is not None else G.nodes[nid]['result'])
+                  for nid, name in self.ienet.find_node_by_type('Result') if name in screens}
+        values = {name: value for name, value in values.items() if isinstance(value, device.DeviceTensor)}
+        if not values:
+            return
+        images = int(self.ienet.batch_size)
+        device.select_stream(self.stream_base)
+        for name, value in values.items():
+            key = (name, screens[name])
+            if key not in self._detection_blocks:
+                self._detection_blocks[key] = detections_rule.Blocks(images, value.shape[-2] // images, screens[name])
+            self._detection_blocks[key].launch(value)
+        self._pending = (self._pending[0] if self._pending is not None else None, self._order_event().record())
+        device.select_stream(0)
+
+    def read_detections(self, name: str, screen, value):
+        """The Detections of Result `name` after wait_done(): the header and then the rows it counts, from the blocks launch_detections
+        filled, on this network's drained base stream; the rule in numpy for a Result that is a host array."""
+        if not isinstance(value, device.DeviceTensor):
+            return detections_rule.compact_records(np.asarray(value), int(self.ienet.batch_size), screen)
+        device.select_stream(self.stream_base)
+        out = self._detection_blocks[(name, screen)].read_back()
         device.select_stream(0)
         return out
 
@@ -1043,11 +1095,12 @@ class Executable_Network:
             return None
         return self._graph
 
-    def infer(self, inputs: dict, verbose: bool = False, top_k=None) -> dict:
-        """`top_k` = k or {Result name: k}: those Results come back as a ``TopK`` of the k best classes per batch row (InferRequest)."""
-        if top_k is not None:                    # the pass of request 0 (this network's own graph and streams), waited for at once
+    def infer(self, inputs: dict, verbose: bool = False, top_k=None, detections=None) -> dict:
+        """`top_k` = k or {Result name: k}: those Results come back as a ``TopK`` of the k best classes per batch row; `detections` = a
+        ``DetectionScreen``, a min_confidence or {Result name: either}: those come back as a ``Detections`` (InferRequest)."""
+        if top_k is not None or detections is not None:   # the pass of request 0 (this network's own graph and streams), waited for at once
             request = self.requests[0] if self.requests else InferRequest(self, self, 0)
-            request._start(inputs, top_k, verbose)
+            request._start(inputs, top_k, verbose, detections)
             return request.wait()
         inputs = self.host_inputs.stage(inputs, self.stream_base, self.sharded)
         self.wait_result_readers()
