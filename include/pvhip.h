@@ -505,7 +505,11 @@ int pvhip_dwconv2d_f32(const float* x, const float* w, float* y, int n, int g, i
  * normalized boxes, as the reference asserts.  loc [n][P*4], conf [n][P*C], priors [1][2][P*4] (boxes, variances),
  * out [n*records][7] = [rank, class, score, xmin, ymin, xmax, ymax] in descending score order per image, a
  * [-1,0,..] terminator after the last record, zeros after it.  The reference handles n == 1 only; images are
- * independent here.  code_type_center_size: 1 = caffe.PriorBoxParameter.CENTER_SIZE, 0 = CORNER. */
+ * independent here.  code_type_center_size: 1 = caffe.PriorBoxParameter.CENTER_SIZE, 0 = CORNER.
+ * NaN: a prior with a NaN among its num_classes scores is never a candidate, whatever its other scores (the reference's argsort
+ * picks the NaN as the best score and NaN > threshold is false); a +inf best score is kept and ranks first.  A NaN in loc or in a prior
+ * box gives a box whose IoU with any other is NaN or 0, never above the threshold: it suppresses nothing, is not suppressed and is stored
+ * as it is.  num_priors: at most 11498 (13 bytes of LDS per prior + 4116 within 150 KB), else PVHIP_EUNSUPPORTED. */
 int pvhip_detection_output_f32(const float* loc, const float* conf, const float* priors, float* out, int n,
                                int num_priors, int num_classes, int records_per_image, float confidence_threshold,
                                float nms_threshold, int code_type_center_size, int variance_encoded_in_target,

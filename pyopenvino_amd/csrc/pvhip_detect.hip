@@ -5,7 +5,9 @@
 // Three launches (a global workspace holds the candidates of every image between them):
 //   candidates (one workgroup per image)
 //   1. per prior: best class and its score (ties -> the later class, what a stable ascending sort reversed gives;
-//      the reference's np.argsort is unstable, so equal scores have no defined order there)
+//      the reference's np.argsort is unstable, so equal scores have no defined order there).  A prior with a NaN among its
+//      class scores is never a candidate: np.argsort puts a NaN last, so the reference's reversed order picks it as the best
+//      score, and NaN > threshold is false
 //   2. priors with score > threshold and class != 0 are kept IN PRIOR ORDER (block scan)
 //   3. their boxes are decoded from the prior boxes / variances: float32 arithmetic in the reference's operation
 //      order (-ffp-contract=off), exp evaluated in double and rounded once, as math.exp on a numpy float32 does
@@ -104,13 +106,15 @@ __global__ __launch_bounds__(kDetBlock) void detect_candidates_kernel(DetArgs a)
         const float* row = conf + (size_t)p * a.C;
         float best = row[0];
         int   bc   = 0;
+        bool  nan  = best != best;
         for (int c = 1; c < a.C; ++c) {
             const float v = row[c];
+            nan |= v != v;
             if (v >= best) { best = v; bc = c; }
         }
         p_score[p] = best;
         p_cls[p]   = bc;
-        flag[p]    = (best > a.conf_thr && bc != 0) ? 1 : 0;
+        flag[p]    = (!nan && best > a.conf_thr && bc != 0) ? 1 : 0;
     }
     __syncthreads();
     // 2. candidates in prior order
