@@ -566,6 +566,41 @@ int pvhip_topk_rows_f32(const float* x, int rows, int cols, int k, int* indices,
  * non-NULL `labels` with num_labels == 0 selects nothing), no NULL records / header / rows; else PVHIP_EINVAL and nothing is launched. */
 int pvhip_detections_compact(const float* records, int images, int records_per_image, int frame_h, int frame_w, float min_confidence,
                              const int* labels, int num_labels, int min_h, int min_w, int max_per_image, int* header, int* rows);
+/* Addition to ABI v18 (the version number is unchanged: nothing existing changed): a TILED detector's answer.  The n batch rows of the
+ * pass are tiles of m frames -- `tiles` is the (n, 5) int32 device table of a RoiInput, row b = (f, x, y, w, h): batch row b saw the
+ * rectangle [y, y + h) x [x, x + w) of frame f --, and the records of all tiles become one table of FRAME detections: shifted into frame
+ * pixels, ordered by score, and suppressed greedily across the tiles of a frame, so that an object in the overlap of two tiles comes back
+ * once.  `records`: n * records_per_tile rows of [rank, label, score, xmin, ymin, xmax, ymax], tile b being rows [b P, (b + 1) P).
+ *   1. candidates  tile b contributes nothing if f is outside [0, m), w < 1 or h < 1 (or w or h above 2^24, which fp32 does not hold
+ *      exactly).  Otherwise its candidates are exactly the records pvhip_detections_compact selects over (frame_h, frame_w) = (h, w) of
+ *      the tile -- live, score >= min_confidence, four finite corners, the label filter, floor / ceil of the clamped fp32 products,
+ *      (min_h, min_w); one device function serves both entries -- so a rectangle clamps to its tile: the detector saw nothing else.  The
+ *      frame rectangle is (x + x0, y + y0, w, h) (the sums wrap as int32 do; a RoiInput's table never gets there).  A tile keeps its first
+ *      max_per_tile candidates in position order.  selected[f] = the kept candidates of all tiles of frame f.
+ *   2. order  the candidates of a frame are ordered by descending score as a float, +0.0 = -0.0 (no NaN passes the screen); ties go to the
+ *      lower flat record b P + p: the order of pvhip_topk_rows_f32.
+ *   3. suppression  greedy in that order: candidate i is dropped iff an earlier candidate j that was kept overlaps it -- and, with
+ *      per_label = 1, has the same label word (the row's int32 label below).  With int64 inter = the area of the intersection of the two
+ *      frame rectangles (0 when they do not meet), a_i, a_j = their areas, den = a_i + a_j - inter for PVHIP_OVERLAP_IOU and den =
+ *      min(a_i, a_j) for PVHIP_OVERLAP_IOS: i overlaps j iff (double)inter > (double)threshold * (double)den -- one IEEE float64 product
+ *      and one comparison; extents are at most 2^24, so every area is exact in float64.  Equality does not suppress.
+ *   4. cap and table  a frame keeps its first max_per_frame kept candidates: counts[f].  The table holds them in (frame, order of step 2)
+ *      order without gaps; a row is (f, x0, y0, w, h, label, score bits, record) as pvhip_detections_compact writes it, record = b P + p:
+ *      the tile of a row is record / P.  total = sum(counts).  Rows >= total are not written.
+ * header = counts[m], then selected[m], then total: 2 m + 1 ints.  `rows` holds min(n * max_per_tile, m * max_per_frame) rows of 32 bytes
+ * and is 16-byte aligned.  `scratch`: 9 * n * max_per_tile + n ints, 16-byte aligned, the caller's, overwritten: the candidate rows, the
+ * place of each in its frame's answer, the candidates of each tile.  The same rule in numpy: tests/tiles_ref.py, matched word for word.
+ * Three launches on the current stream (one wave per tile; one workgroup per frame: a sort of 64-bit keys in LDS, then the suppression;
+ * one wave per tile again), no allocation: no atomics and no wait of one workgroup on another, so nothing depends on timing.  n,
+ * records_per_tile, min_h, min_w, max_per_tile, max_per_frame >= 1, 1 <= frames < 2^30, n * records_per_tile < 2^31 / 7, n * max_per_tile
+ * <= 4096 (the candidate capacity), threshold in [0, 1] (not NaN), overlap one of the two kinds, per_label 0 or 1, `labels` NULL (any
+ * label; num_labels == 0) or a device pointer with num_labels <= 64 (non-NULL with num_labels == 0 selects nothing), no other NULL or
+ * misaligned pointer; else PVHIP_EINVAL and nothing is launched. */
+#define PVHIP_OVERLAP_IOU 0
+#define PVHIP_OVERLAP_IOS 1
+int pvhip_detections_merge_tiles(const float* records, const int* tiles, int n, int records_per_tile, int frames, float min_confidence,
+                                 const int* labels, int num_labels, int min_h, int min_w, int max_per_tile, int overlap, float threshold,
+                                 int per_label, int max_per_frame, int* scratch, int* header, int* rows);
 
 /* ---------------------------------------------------------------- multi-GPU gather ---------- */
 /* No reference counterpart (the reference is single-process).  Batch shards are independent; the only

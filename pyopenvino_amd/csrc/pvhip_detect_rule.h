@@ -1,7 +1,8 @@
 // The screen and the rectangle of one live DetectionOutput record: the one place where pvhip_detections_to_rois and
 // pvhip_detections_compact (include/pvhip.h states the rule of both) decide whether a record survives and what its rectangle is.
-// Whether a record is live -- in front of its image's first row whose column 0 is not >= 0 -- is the caller's business: the two
-// kernels find the list end in different ways.
+// Whether a record is live -- in front of its image's first row whose column 0 is not >= 0 -- is the caller's business: the
+// kernels find the list end in different ways.  walk_image below is the wave-per-image way of pvhip_detections_compact and
+// pvhip_detections_merge_tiles.
 #pragma once
 
 #include "pvhip_common.h"
@@ -35,6 +36,50 @@ __device__ __forceinline__ bool detection_screen(const float* __restrict__ q, fl
         keep = r.w >= min_w && r.h >= min_h;
     }
     return keep;
+}
+
+// What walk_image screens with: the records, P of them per image, and the screen's values.
+struct ScreenWalk {
+    const float* rec;      // [images * P][7]
+    const int*   labels;   // [num_labels], or NULL: any label
+    int   P, num_labels, min_h, min_w;
+    float conf;
+};
+
+__device__ __forceinline__ int lanes_below(unsigned long long votes) {
+    return __builtin_amdgcn_mbcnt_hi((unsigned)(votes >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)votes, 0u));
+}
+
+// Walks image b over a frame of (H, W), 64 records at a time, and hands every survivor with rank < limit to `emit(rank, record, rectangle,
+// q)`.  Returns the number of survivors seen (all of them when limit >= P).  The whole wave calls it; everything that steers the loop is
+// wave-uniform.
+template <typename Emit>
+__device__ __forceinline__ int walk_image(const ScreenWalk& a, int b, int H, int W, int limit, Emit emit) {
+    const int   lane = threadIdx.x & (kWave - 1);
+    const float fh = (float)H, fw = (float)W;
+    int seen = 0;
+    for (int p0 = 0; p0 < a.P && seen < limit; p0 += kWave) {
+        const int    p     = p0 + lane;
+        const bool   valid = p < a.P;
+        const int    r     = b * a.P + p;                                       // (images * P < 2^31 / 7: the launchers check)
+        const float* q     = a.rec + (size_t)r * 7;
+        const unsigned long long ends = __ballot(valid && !(q[0] >= 0.0f));
+        const int  first = ends ? __builtin_ctzll(ends) : kWave;               // the list ends at this lane's record
+        DetectionRect rect{0, 0, 0, 0};
+        const bool keep = valid && lane < first &&
+                          detection_screen(q, a.conf, a.labels, a.labels != nullptr, a.num_labels, fh, fw, a.min_h, a.min_w, rect);
+        const unsigned long long votes = __ballot(keep);
+        const int rank = seen + lanes_below(votes);
+        if (keep && rank < limit) emit(rank, r, rect, q);
+        seen += __popcll(votes);
+        if (ends) break;
+    }
+    return seen;
+}
+
+// The label word of a table row: (int32) of column 1 when that is finite and in [-2^31, 2^31), else -1.
+__device__ __forceinline__ int detection_label(float l) {
+    return (l >= -2147483648.0f && l < 2147483648.0f) ? (int)l : -1;           // (NaN and +-inf fail the comparisons)
 }
 
 }  // namespace pvhip

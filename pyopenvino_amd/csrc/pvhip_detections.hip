@@ -20,50 +20,18 @@ using namespace pvhip;
 namespace {
 
 struct CompactArgs {
-    const float* rec;      // [N * P][7]
-    const int*   labels;   // [num_labels], or NULL: any label
-    int*         header;   // counts[N], selected[N], total
-    int4*        rows;     // [N * min(P, cap)][2]
-    int   N, P, H, W, num_labels, min_h, min_w, cap;
-    float conf;
+    ScreenWalk walk;       // the records [N * P][7] and the screen
+    int*       header;     // counts[N], selected[N], total
+    int4*      rows;       // [N * min(P, cap)][2]
+    int N, H, W, cap;
 };
 
 constexpr int kImagesPerBlock = kBlock / kWave;
 
-__device__ __forceinline__ int lanes_below(unsigned long long votes) {
-    return __builtin_amdgcn_mbcnt_hi((unsigned)(votes >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)votes, 0u));
-}
-
-// Walks image b, 64 records at a time, and hands every kept survivor with rank < limit to `emit(rank, record, rectangle, q)`.  Returns the
-// number of survivors seen (all of them when limit >= P).  The whole wave calls it; everything that steers the loop is wave-uniform.
-template <typename Emit>
-__device__ __forceinline__ int walk_image(const CompactArgs& a, int b, int limit, Emit emit) {
-    const int   lane = threadIdx.x & (kWave - 1);
-    const float fh = (float)a.H, fw = (float)a.W;
-    int seen = 0;
-    for (int p0 = 0; p0 < a.P && seen < limit; p0 += kWave) {
-        const int    p     = p0 + lane;
-        const bool   valid = p < a.P;
-        const int    r     = b * a.P + p;                                       // (N * P < 2^31 / 7: the launcher checks)
-        const float* q     = a.rec + (size_t)r * 7;
-        const unsigned long long ends = __ballot(valid && !(q[0] >= 0.0f));
-        const int  first = ends ? __builtin_ctzll(ends) : kWave;               // the list ends at this lane's record
-        DetectionRect rect{0, 0, 0, 0};
-        const bool keep = valid && lane < first &&
-                          detection_screen(q, a.conf, a.labels, a.labels != nullptr, a.num_labels, fh, fw, a.min_h, a.min_w, rect);
-        const unsigned long long votes = __ballot(keep);
-        const int rank = seen + lanes_below(votes);
-        if (keep && rank < limit) emit(rank, r, rect, q);
-        seen += __popcll(votes);
-        if (ends) break;
-    }
-    return seen;
-}
-
 __global__ __launch_bounds__(kBlock) void detections_count_kernel(CompactArgs a) {
     const int b = blockIdx.x * kImagesPerBlock + (threadIdx.x >> 6);
     if (b >= a.N) return;                                                       // (the whole wave: nothing below meets a barrier)
-    const int selected = walk_image(a, b, a.P, [](int, int, const DetectionRect&, const float*) {});
+    const int selected = walk_image(a.walk, b, a.H, a.W, a.walk.P, [](int, int, const DetectionRect&, const float*) {});
     if ((threadIdx.x & (kWave - 1)) == 0) {
         a.header[b]       = min(selected, a.cap);
         a.header[a.N + b] = selected;
@@ -81,11 +49,9 @@ __global__ __launch_bounds__(kBlock) void detections_write_kernel(CompactArgs a)
     const int count = a.header[b];
     if (count > 0) {
         int4* out = a.rows + 2 * (size_t)base;
-        walk_image(a, b, count, [&](int rank, int r, const DetectionRect& rect, const float* q) {
-            const float l     = q[1];
-            const int   label = (l >= -2147483648.0f && l < 2147483648.0f) ? (int)l : -1;   // (NaN and +-inf fail the comparisons)
+        walk_image(a.walk, b, a.H, a.W, count, [&](int rank, int r, const DetectionRect& rect, const float* q) {
             out[2 * rank + 0] = make_int4(b, rect.x0, rect.y0, rect.w);
-            out[2 * rank + 1] = make_int4(rect.h, label, (int)__float_as_uint(q[2]), r);
+            out[2 * rank + 1] = make_int4(rect.h, detection_label(q[1]), (int)__float_as_uint(q[2]), r);
         });
     }
     if (b == a.N - 1 && lane == 0) a.header[2 * a.N] = base + count;
@@ -105,9 +71,9 @@ int pvhip_detections_compact(const float* records, int images, int records_per_i
     PVHIP_CHECK_ARG(frame_h >= 1 && frame_h <= (1 << 24) && frame_w >= 1 && frame_w <= (1 << 24));   // exact as fp32
     PVHIP_CHECK_ARG(num_labels >= 0 && num_labels <= kScreenLabels && (num_labels == 0 || labels != nullptr));   // (NULL: any label)
     CompactArgs a;
-    a.rec = records; a.labels = labels; a.header = header; a.rows = reinterpret_cast<int4*>(rows);
-    a.N = images; a.P = records_per_image; a.H = frame_h; a.W = frame_w;
-    a.num_labels = num_labels; a.min_h = min_h; a.min_w = min_w; a.cap = max_per_image; a.conf = min_confidence;
+    a.walk = ScreenWalk{records, labels, records_per_image, num_labels, min_h, min_w, min_confidence};
+    a.header = header; a.rows = reinterpret_cast<int4*>(rows);
+    a.N = images; a.H = frame_h; a.W = frame_w; a.cap = max_per_image;
     const dim3 grid((images + kImagesPerBlock - 1) / kImagesPerBlock);
     hipLaunchKernelGGL(detections_count_kernel, grid, dim3(kBlock), 0, state().stream, a);
     hipLaunchKernelGGL(detections_write_kernel, grid, dim3(kBlock), 0, state().stream, a);

@@ -158,10 +158,12 @@ def _declared_extent(ienet):
 
 def checked(ienet, detections, sharded: bool) -> dict:
     """{Result name: resolved DetectionScreen} of the `detections` argument of infer() / start_async() -- a DetectionScreen or a
-    min_confidence for every detector Result, or {Result name: either} --, {} for None.  Everything is looked up in the network as it
-    was read: no device is needed, nothing is allocated."""
+    min_confidence for every detector Result, or {Result name: either} --, {} for None; a ``TiledScreen`` in the place of a
+    DetectionScreen resolves to a TiledScreen with its `input` named.  Everything is looked up in the network as it was read: no device
+    is needed, nothing is allocated."""
     if detections is None:
         return {}
+    from . import tiled_detections                            # (it imports this module)
     results = {name: next(iter(ienet.G.nodes[nid]['input'].values())) for nid, name in ienet.find_node_by_type('Result')}
     batch = int(ienet.batch_size)
     if isinstance(detections, dict):
@@ -188,7 +190,11 @@ def checked(ienet, detections, sharded: bool) -> dict:
             raise ValueError('detections: Result {!r} is {}: FP32 Results only'.format(name, port['precision']))
         if batch * per_image >= (1 << 31) // 7:
             raise ValueError('detections: Result {!r} has too many records ({} x {})'.format(name, batch, per_image))
-        out[name] = resolved(screen, per_image, _declared_extent(ienet), 'Result {!r}: '.format(name))
+        what = 'Result {!r}: '.format(name)
+        if isinstance(screen, tiled_detections.TiledScreen):  # the batch rows are tiles of frames: tiled_detections.py's rule
+            out[name] = tiled_detections.resolved(screen, batch, per_image, what)._replace(input=tiled_detections.checked_input(ienet, screen, what))
+        else:
+            out[name] = resolved(screen, per_image, _declared_extent(ienet), what)
     return out
 
 

@@ -33,7 +33,7 @@ import xml.etree.ElementTree as et
 import networkx as nx
 import numpy as np
 
-from . import common_def, detections as detections_rule, device, fusion_plan, stream_plan, top_k as top_k_rule
+from . import common_def, detections as detections_rule, device, fusion_plan, stream_plan, tiled_detections as tiled_rule, top_k as top_k_rule
 from .host_input import HostInputs
 from .input_format import DetectedRois, InputInfo, PreProcessChannel, PreProcessInfo  # noqa: F401 -- the classes of IENetwork.input_info
 from .stream_plan import CaptureStreamModel
@@ -311,13 +311,19 @@ class InferRequest:
     and read back in two copies, 4 (2 n + 1) bytes and 32 bytes per row; the full Result stays on the device, where a ``DetectedRois``
     of another request reads it as before.  ValueError ('detections: ...'), before anything is staged or launched: an unknown name, a
     Result of another shape or precision, a value of the screen out of range, a sharded batch, no such Result for an unnamed form.
+    A ``TiledScreen`` in the place of a DetectionScreen, for a pass whose 4-D input is fed a ``RoiInput(frames, tiles)``: the batch rows
+    are tiles of the m frames and the Result comes back as a Detections over FRAMES -- shifted into frame pixels, ordered by score and
+    suppressed across the tiles of a frame by the rule of tiled_detections.py --, made by pvhip_detections_merge_tiles behind the pass with
+    the tile table stage() uploaded, and read back in the same two copies, 4 (2 m + 1) bytes and 32 bytes per row.  ValueError before
+    anything is staged or launched, besides the above: that input fed anything but a RoiInput, more than 4096 candidates.
     `top_k` and `detections` may be given together, for different Results."""
 
     def __init__(self, owner, runner, index: int):
         self.owner, self.runner, self.index = owner, runner, index      # owner: the network load_network returned
         self._in_flight, self._replayed = False, None
         self._top_k = {}                # {Result name: k} of the pass in flight
-        self._detections = {}           # {Result name: resolved DetectionScreen} of the pass in flight
+        self._detections = {}           # {Result name: resolved DetectionScreen or TiledScreen} of the pass in flight
+        self._tiles = {}                # {Result name: (input name, frame count m)} of its TiledScreens
 
     def start_async(self, inputs: dict, top_k=None, detections=None):
         self._start(inputs, top_k, False, detections)
@@ -326,13 +332,18 @@ class InferRequest:
         if self._in_flight:
             raise RuntimeError('request {} is still in flight: wait() first'.format(self.index))
         ex = self.runner
+        tiled_rule.checked_top_k(top_k, detections)
         wanted = top_k_rule.checked(ex.ienet, top_k, ex.sharded or self.owner.sharded)
         screens = detections_rule.checked(ex.ienet, detections, ex.sharded or self.owner.sharded)
         both = sorted(set(wanted) & set(screens))
         if both:
             raise ValueError('detections: Result {!r} is asked for with top_k as well'.format(both[0]))
+        tiled = {name: s for name, s in screens.items() if isinstance(s, tiled_rule.TiledScreen)}
+        tiled_rule.checked_feed(inputs, tiled)
         self._top_k, self._detections = wanted, screens
+        fed = {name: inputs[s.input] for name, s in tiled.items()}
         inputs = ex.host_inputs.stage(inputs, ex.stream_base, ex.sharded or self.owner.sharded)
+        self._tiles = {name: (tiled[name].input, int(np.shape(roi.frames)[0])) for name, roi in fed.items()}    # (staged: the frames are m frames)
         ex.wait_result_readers()
         # The same device-resident tensors as the last calls: the pass is replayed from this request's own recording (one call
         # instead of ~100 dispatches; every request records its own pass on its own stream and keeps its own tensors, so the
@@ -346,8 +357,11 @@ class InferRequest:
                 ex.run_tasks(verbose)
         if self._top_k:                          # behind the pass, replayed or eager, and outside the recording: one recording serves both
             ex.launch_top_k(self._top_k, self._replayed)
-        if self._detections:                     # likewise
-            ex.launch_detections(self._detections, self._replayed)
+        plain = {name: s for name, s in screens.items() if name not in tiled}
+        if plain:                                # likewise
+            ex.launch_detections(plain, self._replayed)
+        if tiled:                                # likewise, with the tile table stage() uploaded
+            ex.launch_tiled_detections(tiled, self._tiles, self._replayed)
         self._in_flight = True
 
     def wait(self) -> dict:
@@ -359,10 +373,13 @@ class InferRequest:
         replayed, self._replayed = self._replayed, None
         top_k, self._top_k = self._top_k, {}
         screens, self._detections = self._detections, {}
+        tiles, self._tiles = self._tiles, {}
         for nid, name in ex.ienet.find_node_by_type('Result'):
             value = replayed['results'][name] if replayed is not None else G.nodes[nid]['result']
             if name in top_k:                    # (n, k) pairs come back; the Result itself stays where it is
                 G.nodes[nid]['result'], out[name] = value, ex.read_top_k(name, top_k[name], value)
+            elif name in tiles:                  # the frames' detections come back; the records stay where they are
+                G.nodes[nid]['result'], out[name] = value, ex.read_tiled_detections(name, screens[name], tiles[name], value)
             elif name in screens:                # the survivors come back; the records stay where they are
                 G.nodes[nid]['result'], out[name] = value, ex.read_detections(name, screens[name], value)
             else:
@@ -456,6 +473,7 @@ class Executable_Network:
         self._result_readers = []
         self._top_k_blocks = {}         # {(Result name, k): top_k.Blocks}: the device block and the page-locked block of a top_k pass
         self._detection_blocks = {}     # {(Result name, resolved DetectionScreen): detections.Blocks}, likewise for a detections pass
+        self._tile_blocks = {}          # {(Result name, resolved TiledScreen, m): tiled_detections.Blocks}, likewise for a tiled one
         if input_formats is None:
             input_formats = {name: info.frozen() for name, info in ienetwork.input_info.items()}
         self.host_inputs = HostInputs(input_formats)    # host arrays in a declared format or the request's own buffers -> device tensors
@@ -510,6 +528,7 @@ class Executable_Network:
         self._result_readers = []
         self._top_k_blocks = {}
         self._detection_blocks = {}
+        self._tile_blocks = {}
         G = self.ienet.G
         for nid in G.nodes:
             node = G.nodes[nid]
@@ -592,6 +611,39 @@ class Executable_Network:
             return detections_rule.compact_records(np.asarray(value), int(self.ienet.batch_size), screen)
         device.select_stream(self.stream_base)
         out = self._detection_blocks[(name, screen)].read_back()
+        device.select_stream(0)
+        return out
+
+    def launch_tiled_detections(self, screens: dict, tiles: dict, replayed):
+        """pvhip_detections_merge_tiles for every Result named in `screens` = {name: resolved TiledScreen}, as launch_detections does its
+        launch: on the base stream behind the pass -- and behind the upload of the tile table, which that stream waited for in stage() --,
+        outside the recording.  `tiles` = {name: (input name, m)}: the table is that input's slot's, on the device.  The blocks are this
+        request's own, made on first use per (name, screen, m)."""
+        G = self.ienet.G
+        values = {name: (replayed['results'][name] if replayed is not None else G.nodes[nid]['result'])
+                  for nid, name in self.ienet.find_node_by_type('Result') if name in screens}
+        values = {name: value for name, value in values.items() if isinstance(value, device.DeviceTensor)}
+        if not values:
+            return
+        n = int(self.ienet.batch_size)
+        device.select_stream(self.stream_base)
+        for name, value in values.items():
+            source, m = tiles[name]
+            key = (name, screens[name], m)
+            if key not in self._tile_blocks:
+                self._tile_blocks[key] = tiled_rule.Blocks(n, value.shape[-2] // n, m, screens[name])
+            self._tile_blocks[key].launch(value, self.host_inputs.slots[source].rois)
+        self._pending = (self._pending[0] if self._pending is not None else None, self._order_event().record())
+        device.select_stream(0)
+
+    def read_tiled_detections(self, name: str, screen, tiles, value):
+        """The Detections over frames of Result `name` after wait_done(): the header and then the rows it counts, from the blocks
+        launch_tiled_detections filled; the rule in numpy, on the page-locked table, for a Result that is a host array."""
+        source, m = tiles
+        if not isinstance(value, device.DeviceTensor):
+            return tiled_rule.merge_tiles(np.asarray(value), self.host_inputs.slots[source].rois_host, m, screen)
+        device.select_stream(self.stream_base)
+        out = self._tile_blocks[(name, screen, m)].read_back()
         device.select_stream(0)
         return out
 

@@ -1,0 +1,230 @@
+"""A tiled detector's answer (``infer({input: RoiInput(frames, tiles)}, detections=TiledScreen(...))``): the rule, the argument checks and
+the device launch.  The batch rows of the pass are tiles of m frames; what comes back is one ``Detections`` over FRAMES.
+
+The rule (include/pvhip.h, pvhip_detections_merge_tiles; tests/tiles_ref.py is the same again).  Records are [rank, label, score, xmin,
+ymin, xmax, ymax]; batch row b is rows [b P, (b + 1) P); tile b = (f, x, y, w, h) is row b of the RoiInput's (n, 5) table.
+  1. candidates   tile b contributes nothing if f is outside [0, m), w < 1 or h < 1 (or w or h above 2^24).  Otherwise its candidates are
+                  exactly what detections.py's rule selects over frames of (h, w), the tile's extent: live, score >= float32(
+                  min_confidence), four finite corners, the label filter, floor / ceil of the clamped float32 products, min_size.  The
+                  frame rectangle is (x + x0, y + y0, w, h) (int32 sums): boxes clamp to the tile, because the detector saw nothing
+                  else.  A tile keeps its first max_per_tile candidates in position order; selected[f] is the number of kept candidates
+                  of all tiles of frame f.
+  2. order        within a frame by descending score as a float, +0.0 = -0.0 (no NaN passes the screen); ties go to the lower flat
+                  record: top_k.py's order.
+  3. suppression  greedy in that order: candidate i is dropped iff an earlier candidate j that was kept overlaps it, with equal int
+                  labels (the row's label word) when per_label is set.  int64 inter, a_i, a_j; den = a_i + a_j - inter for 'IOU', den =
+                  min(a_i, a_j) for 'IOS'; i overlaps j iff float64(inter) > float64(float32(threshold)) * float64(den): one IEEE float64
+                  product and one comparison, every area exact.  Equality does not suppress.
+  4. cap, table   a frame keeps its first max_per_frame kept candidates: counts[f].  The table is in (frame, order of step 2) order
+                  without gaps; rows (f, x0, y0, w, h, label, score bits, record) as detections.py's; record = b P + p, so the tile of a
+                  detection is record // P."""
+import collections
+import ctypes
+
+import numpy as np
+
+from . import detections, device
+from .detections import Detections
+
+MAX_CANDIDATES = 4096                # n * max_per_tile: what one workgroup sorts in LDS
+OVERLAPS = {'IOU': 0, 'IOS': 1}      # PVHIP_OVERLAP_IOU / _IOS
+
+_Tiled = collections.namedtuple('TiledScreen', 'min_confidence labels min_size max_per_tile overlap threshold per_label max_per_frame input')
+
+
+class TiledScreen(_Tiled):
+    """Wherever a ``DetectionScreen`` is accepted, for a pass whose 4-D input (`input` names it when the network has several) is fed a
+    ``RoiInput(frames, tiles)``: the batch rows are tiles of the m frames, and the Result comes back as a ``Detections`` over frames --
+    `counts` and `selected` of shape (m,), `rois[:, 0]` the frame and the rectangle in frame pixels, `records` the flat row of the Result
+    (its tile is records // P).  Candidates: score >= `min_confidence`, `labels` (None: any, or at most 64 ints), rectangles of at least
+    `min_size` = (h, w) clamped to their tile, the first `max_per_tile` of a tile (None: min(P, 4096 // n); n * max_per_tile <= 4096).
+    Within a frame they are taken by descending score and dropped when an earlier kept one -- of the same label when `per_label` --
+    overlaps them by more than `threshold`: `overlap` = 'IOU' (intersection over union) or 'IOS' (over the smaller area).  At most
+    `max_per_frame` per frame (None: all).  Immutable; the values are checked when a pass is started with it (ValueError)."""
+    __slots__ = ()
+
+    def __new__(cls, min_confidence=0.5, labels=None, min_size=(1, 1), max_per_tile=None, overlap='IOU', threshold=0.45, per_label=True,
+                max_per_frame=None, input=None):
+        frozen = [detections._frozen(v) for v in (labels, min_size)]
+        return super().__new__(cls, min_confidence, frozen[0], frozen[1], max_per_tile, overlap, threshold, per_label, max_per_frame, input)
+
+
+def resolved(screen: TiledScreen, tiles: int, per_tile: int, what='') -> TiledScreen:
+    """`screen` with every value checked and in its one form for n = `tiles` batch rows of P = `per_tile` records -- max_per_tile and
+    max_per_frame filled in --, so that equal screens are equal keys; `input` stays as it is (checked() knows the network).  ValueError."""
+    conf, labels, size, cap, overlap, threshold, per_label, frame_cap, name = screen
+    n, P = int(tiles), int(per_tile)
+    # (the plain screen's checks and forms of what the two share, over a placeholder frame)
+    conf, _, labels, size, _ = detections.resolved(detections.DetectionScreen(conf, (1, 1), labels, size, None), P, None, what)
+    if not isinstance(overlap, str) or overlap not in OVERLAPS:
+        raise ValueError('detections: {}overlap is \'IOU\' or \'IOS\', got {!r}'.format(what, overlap))
+    if isinstance(threshold, bool) or not isinstance(threshold, (int, float, np.integer, np.floating)) or not 0 <= threshold <= 1:
+        raise ValueError('detections: {}threshold {!r} is not a finite number in [0, 1]'.format(what, threshold))
+    if not isinstance(per_label, (bool, np.bool_)):
+        raise ValueError('detections: {}per_label is a bool, got {!r}'.format(what, per_label))
+    for key, v in (('max_per_tile', cap), ('max_per_frame', frame_cap)):
+        if v is not None and not detections._count(v):
+            raise ValueError('detections: {}{} is None or a count >= 1, got {!r}'.format(what, key, v))
+    if n > MAX_CANDIDATES:
+        raise ValueError('detections: {}{} tiles are more than the {} candidates one pass merges'.format(what, n, MAX_CANDIDATES))
+    cap = min(P, MAX_CANDIDATES // n) if cap is None else min(int(cap), P)
+    if n * cap > MAX_CANDIDATES:
+        raise ValueError('detections: {}{} tiles x max_per_tile {} is more than {} candidates: lower max_per_tile to {} or less'.format(
+            what, n, cap, MAX_CANDIDATES, MAX_CANDIDATES // n))
+    frame_cap = n * cap if frame_cap is None else min(int(frame_cap), n * cap)
+    return TiledScreen(conf, labels, size, cap, overlap, float(threshold), bool(per_label), frame_cap, name)
+
+
+def checked_input(ienet, screen: TiledScreen, what='') -> str:
+    """The name of the 4-D Parameter whose RoiInput carries the tile table: `screen.input`, or the network's only one; ValueError."""
+    names = [name for nid, name in ienet.find_node_by_type('Parameter') if len(ienet.G.nodes[nid]['data']['shape']) == 4]
+    if screen.input is None:
+        if len(names) != 1:
+            raise ValueError('detections: {}the network has {} 4-D Parameters ({}): input= names the one fed the tiles'.format(
+                what, len(names), sorted(names)))
+        return names[0]
+    if not isinstance(screen.input, str) or screen.input not in names:
+        raise ValueError('detections: {}input {!r} is no 4-D Parameter of the network (it has {})'.format(what, screen.input, sorted(names)))
+    return screen.input
+
+
+def checked_top_k(top_k, detections):
+    """No Result is named with a TiledScreen and in `top_k` as well (said here, in front of top_k's own checks, which refuse a
+    detector's Result for its shape); ValueError."""
+    if isinstance(top_k, dict) and isinstance(detections, dict):
+        both = sorted(name for name, screen in detections.items() if isinstance(screen, TiledScreen) and name in top_k)
+        if both:
+            raise ValueError('detections: Result {!r} is asked for with top_k as well'.format(both[0]))
+
+
+def checked_feed(inputs: dict, screens: dict):
+    """Every tiled screen's input is fed a RoiInput -- nothing else carries a tile table --; ValueError before anything is staged."""
+    from .input_format import RoiInput
+    for name, screen in screens.items():
+        fed = inputs.get(screen.input) if isinstance(inputs, dict) else None
+        if not isinstance(fed, RoiInput):
+            raise ValueError('detections: Result {!r}: a TiledScreen needs input {!r} fed a RoiInput (frames, tiles), got {}'.format(
+                name, screen.input, type(fed).__name__))
+
+
+def _edge(v, extent, rounded):
+    with np.errstate(over='ignore', invalid='ignore'):
+        return rounded(np.minimum(np.maximum(v * extent, np.float32(0)), extent)).astype(np.int64)
+
+
+def _overlap(box, others, kind: str, threshold: float):
+    """Step 3's comparison of one int64 (x0, y0, w, h) with the rows of `others`."""
+    iw = np.minimum(box[0] + box[2], others[:, 0] + others[:, 2]) - np.maximum(box[0], others[:, 0])
+    ih = np.minimum(box[1] + box[3], others[:, 1] + others[:, 3]) - np.maximum(box[1], others[:, 1])
+    inter = np.where((iw > 0) & (ih > 0), iw * ih, 0)
+    area, areas = box[2] * box[3], others[:, 2] * others[:, 3]
+    den = np.minimum(area, areas) if kind == 'IOS' else area + areas - inter
+    return inter.astype(np.float64) > np.float64(np.float32(threshold)) * den.astype(np.float64)
+
+
+def merge_tiles(records, rois, frames: int, screen) -> Detections:
+    """The rule in numpy on a host array of float32 records, (1, 1, R, 7) or (R, 7), of the n tiles `rois` (an integer (n, 5) table, row
+    b = (f, x, y, w, h)) of `frames` = m frames: what a Result computed on the host gets.  `screen`: a TiledScreen, or a min_confidence."""
+    rec, t = np.asarray(records), np.asarray(rois)
+    if rec.dtype != np.float32 or rec.ndim not in (2, 4) or rec.shape[-1] != 7 or tuple(rec.shape[:-2]) not in ((), (1, 1)) or rec.shape[-2] < 1:
+        raise ValueError('detections: float32 records of shape (1, 1, R, 7) or (R, 7), got {} {}'.format(rec.dtype, rec.shape))
+    if t.ndim != 2 or t.shape[1] != 5 or t.shape[0] < 1 or t.dtype.kind not in 'iu' or rec.shape[-2] % t.shape[0]:
+        raise ValueError('detections: an integer (n, 5) table of tiles with n dividing the {} records, got {} {}'.format(
+            rec.shape[-2], t.dtype, t.shape))
+    if not detections._count(frames):
+        raise ValueError('detections: {!r} frames'.format(frames))
+    rec, t = rec.reshape(-1, 7), t.astype(np.int64)
+    n, m = t.shape[0], int(frames)
+    P = rec.shape[0] // n
+    if not isinstance(screen, TiledScreen):
+        screen = TiledScreen(min_confidence=screen)
+    conf, labels, (min_h, min_w), cap, kind, threshold, per_label, frame_cap, _ = resolved(screen, n, P)
+    # 1. candidates
+    f, x, y, w, h = t.T
+    tile_ok = (f >= 0) & (f < m) & (w >= 1) & (w <= detections.MAX_EXTENT) & (h >= 1) & (h <= detections.MAX_EXTENT)
+    dead = ~(rec[:, 0] >= 0).reshape(n, P)
+    end = np.where(dead.any(axis=1), dead.argmax(axis=1), P)
+    keep = ((np.arange(P)[None, :] < end[:, None]) & tile_ok[:, None]).ravel()
+    keep &= (rec[:, 2] >= np.float32(conf)) & np.isfinite(rec[:, 3:7]).all(axis=1)
+    if labels is not None:
+        keep &= np.isin(rec[:, 1], np.asarray(labels, np.int64).astype(np.float32))
+    corners = np.where(keep[:, None], rec[:, 3:7], np.float32(0))
+    fw, fh = np.repeat(np.where(tile_ok, w, 1), P).astype(np.float32), np.repeat(np.where(tile_ok, h, 1), P).astype(np.float32)
+    x0, y0 = _edge(corners[:, 0], fw, np.floor), _edge(corners[:, 1], fh, np.floor)
+    bw, bh = _edge(corners[:, 2], fw, np.ceil) - x0, _edge(corners[:, 3], fh, np.ceil) - y0
+    keep &= (bw >= min_w) & (bh >= min_h)
+    keep = keep.reshape(n, P)
+    cand = np.flatnonzero((keep & (np.cumsum(keep, axis=1) <= cap)).ravel())
+    tile = cand // P
+    boxes = np.stack([(x[tile] + x0[cand]).astype(np.int32), (y[tile] + y0[cand]).astype(np.int32), bw[cand], bh[cand]], axis=1).astype(np.int64)
+    label = rec[cand, 1]
+    whole = np.isfinite(label) & (label >= np.float32(-2.0 ** 31)) & (label < np.float32(2.0 ** 31))
+    with np.errstate(invalid='ignore'):
+        label = np.where(whole, np.where(whole, label, np.float32(0)).astype(np.int32), np.int32(-1)).astype(np.int32)
+    score = rec[cand, 2]
+    counts, selected, rows = np.zeros(m, np.int32), np.zeros(m, np.int32), []
+    for frame in range(m):
+        mine = np.flatnonzero(f[tile] == frame)
+        selected[frame] = len(mine)
+        # 2. order (`mine` is in record order and the sort is stable; -0.0 and 0.0 compare equal)
+        mine = mine[np.argsort(-score[mine].astype(np.float64), kind='stable')]
+        # 3. suppression
+        gone = np.zeros(len(mine), bool)
+        for i in range(len(mine)):
+            if gone[i]:
+                continue
+            rows.append(mine[i])
+            counts[frame] += 1
+            if counts[frame] == frame_cap:                     # 4. cap
+                break
+            later = mine[i + 1:]
+            hit = _overlap(boxes[mine[i]], boxes[later], kind, threshold)
+            if per_label:
+                hit &= label[later] == label[mine[i]]
+            gone[i + 1:] |= hit
+    rows = np.asarray(rows, np.int64)
+    kept = cand[rows]
+    table = np.concatenate([f[tile[rows]][:, None], boxes[rows]], axis=1).astype(np.int32).reshape(-1, 5)
+    return Detections(counts, selected, table, label[rows].astype(np.int32), score[rows].copy(), kept.astype(np.int32))
+
+
+class Blocks:
+    """What a request keeps for one (Result name, resolved screen, m): the device header (counts, selected, total), rows and candidate
+    scratch that pvhip_detections_merge_tiles writes, the labels on the device (uploaded once, here), and the page-locked host twins of
+    header and rows that wait() reads back into: 4 (2 m + 1) bytes, then exactly 32 total bytes."""
+    __slots__ = ('tiles', 'per_tile', 'frames', 'screen', 'header', 'rows', 'scratch', 'labels', 'header_host', 'rows_host')
+
+    def __init__(self, tiles: int, per_tile: int, frames: int, screen: TiledScreen):
+        self.tiles, self.per_tile, self.frames, self.screen = tiles, per_tile, frames, screen
+        slots = tiles * screen.max_per_tile
+        capacity = min(slots, frames * screen.max_per_frame)
+        self.header = device.DeviceTensor.empty((2 * frames + 1,), np.int32)
+        self.rows = device.DeviceTensor.empty((capacity, 8), np.int32)
+        self.scratch = device.DeviceTensor.empty((9 * slots + tiles,), np.int32)
+        self.header_host = device.host_empty((2 * frames + 1,), np.int32)
+        self.rows_host = device.host_empty((capacity, 8), np.int32)
+        # ([]: a device pointer with no label behind it, which selects nothing; None: NULL, any label)
+        self.labels = None if screen.labels is None else device.DeviceTensor.from_numpy(np.asarray(screen.labels + (0,), np.int32))
+
+    def launch(self, result, table):
+        """The entry's three launches on the current stream, behind whatever wrote `result` and uploaded `table` (the slot's (n, 5)
+        device table) there."""
+        s = self.screen
+        assert result.dtype == np.float32 and int(np.prod(result.shape)) == 7 * self.tiles * self.per_tile
+        assert table.dtype == np.int32 and tuple(table.shape) == (self.tiles, 5)
+        device.call('pvhip_detections_merge_tiles', device.ptr(result), device.ptr(table), self.tiles, self.per_tile, self.frames,
+                    s.min_confidence, device.ptr(self.labels), 0 if s.labels is None else len(s.labels), s.min_size[0], s.min_size[1],
+                    s.max_per_tile, OVERLAPS[s.overlap], s.threshold, int(s.per_label), s.max_per_frame, ctypes.c_void_p(self.scratch.ptr),
+                    ctypes.c_void_p(self.header.ptr), ctypes.c_void_p(self.rows.ptr))
+
+    def read_back(self) -> Detections:
+        """The answer, copied on the current stream, which has drained: the header, then the rows it counts; the arrays are the
+        caller's own."""
+        m = self.frames
+        device.call('pvhip_memcpy_d2h', ctypes.c_void_p(self.header_host.ctypes.data), ctypes.c_void_p(self.header.ptr), self.header_host.nbytes)
+        total = int(self.header_host[2 * m])
+        if not 0 <= total <= self.rows_host.shape[0]:
+            raise device.PvhipError('pvhip_detections_merge_tiles left total = {} of at most {} rows'.format(total, self.rows_host.shape[0]))
+        if total:
+            device.call('pvhip_memcpy_d2h', ctypes.c_void_p(self.rows_host.ctypes.data), ctypes.c_void_p(self.rows.ptr), 32 * total)
+        return Detections(self.header_host[:m].copy(), self.header_host[m:2 * m].copy(), *detections._split(self.rows_host, total))
