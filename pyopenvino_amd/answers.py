@@ -1,0 +1,69 @@
+"""Answers behind the pass: the Results a start named with ``top_k=`` or ``detections=`` come back from wait() as a ``TopK`` or a
+``Detections`` made on the device instead of as the tensor.  One ``Answers`` per Executable_Network (one per request), as ``HostInputs``
+is on the way in: the request checks the arguments, binds the asks to the staged inputs, launches behind the pass and reads after it.
+
+An ask is one Result's question in its resolved form -- top_k.Ask, detections.Ask or tiled_detections.Ask, each with `bound`, `key`,
+`launch` and `on_host` --; which kind it is matters only where checked() makes it."""
+import numpy as np
+
+from . import detections as detections_rule, device, tiled_detections as tiled_rule, top_k as top_k_rule
+
+
+class Answers:
+    """`blocks` = {ask.key(Result name): its Blocks}, this request's own device and page-locked blocks, made on first use: (name, k),
+    (name, resolved DetectionScreen) or (name, resolved TiledScreen, m)."""
+
+    def __init__(self, runner):
+        self.runner, self.blocks = runner, {}       # runner: the Executable_Network whose base stream and Results these are
+
+    def release(self):
+        self.blocks = {}
+
+    def checked(self, inputs, top_k, detections, sharded: bool) -> dict:
+        """{Result name: ask} of the `top_k` and `detections` arguments of a start with `inputs`, {} when nothing is asked; ValueError.
+        Everything is looked up in the network as it was read: no device is needed, nothing is staged, allocated or launched."""
+        if top_k is None and detections is None:
+            return {}
+        ienet = self.runner.ienet
+        tiled_rule.checked_top_k(top_k, detections)
+        wanted = top_k_rule.checked(ienet, top_k, sharded)
+        screens = detections_rule.checked(ienet, detections, sharded)
+        both = sorted(set(wanted) & set(screens))
+        if both:
+            raise ValueError('detections: Result {!r} is asked for with top_k as well'.format(both[0]))
+        tiled = {name: s for name, s in screens.items() if isinstance(s, tiled_rule.TiledScreen)}
+        tiled_rule.checked_feed(inputs, tiled)
+        n = int(ienet.batch_size)
+        asks = {name: top_k_rule.Ask(k) for name, k in wanted.items()}
+        asks.update((name, tiled_rule.Ask(s, n, None, None) if name in tiled else detections_rule.Ask(s, n)) for name, s in screens.items())
+        return asks
+
+    def bound(self, asks: dict, inputs: dict) -> dict:
+        """`asks` for the pass whose `inputs`, as they were fed, host_inputs.stage() has just staged: a tiled ask learns its frame count
+        and its tile table here, where the frames are known to be m frames."""
+        slots = self.runner.host_inputs.slots
+        return {name: ask.bound(inputs, slots) for name, ask in asks.items()}
+
+    def launch(self, asks: dict, values: dict):
+        """Every ask's launches on the base stream, behind the pass -- replayed or eager, and outside the recording: one recording serves
+        every kind -- that left `values` = {Result name: tensor}, and behind the tile table stage() uploaded on that stream; wait_done()
+        then waits for one event behind them all.  A Result that is a host array gets the rule in numpy when it is read."""
+        ex = self.runner
+        on_device = [(name, ask) for name, ask in asks.items() if isinstance(values[name], device.DeviceTensor)]
+        if not on_device:
+            return
+        device.select_stream(ex.stream_base)
+        for name, ask in on_device:
+            self.blocks[ask.key(name)] = ask.launch(self.blocks.get(ask.key(name)), values[name])      # (made on first use)
+        ex._pending = (ex._pending[0] if ex._pending is not None else None, ex._order_event().record())
+        device.select_stream(0)
+
+    def read(self, name: str, ask, value):
+        """The answer of Result `name` after wait_done(): read back from the blocks launch() filled, on the drained base stream; the rule
+        in numpy -- a tiled one on the slot's page-locked table -- for a Result that is a host array."""
+        if not isinstance(value, device.DeviceTensor):
+            return ask.on_host(np.asarray(value))
+        device.select_stream(self.runner.stream_base)
+        out = self.blocks[ask.key(name)].read_back()
+        device.select_stream(0)
+        return out

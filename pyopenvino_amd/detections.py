@@ -102,42 +102,57 @@ def resolved(screen, per_image: int, extent=None, what='') -> DetectionScreen:
     return DetectionScreen(float(conf), (int(frame[0]), int(frame[1])), labels, (int(size[0]), int(size[1])), min(int(cap), int(per_image)))
 
 
-def compact_records(records, images: int, screen) -> Detections:
-    """The rule in numpy on a host array of float32 records, (1, 1, R, 7) or (R, 7), of `images` images: what a Result computed on the
-    host (a foreign plugin set) gets.  `screen`: a DetectionScreen with a frame_size (there is no network here to take it from)."""
+def records_checked(records) -> np.ndarray:
+    """`records` as an (R, 7) array, if they are float32 records of shape (1, 1, R, 7) or (R, 7) with R >= 1; ValueError."""
     rec = np.asarray(records)
     if rec.dtype != np.float32 or rec.ndim not in (2, 4) or rec.shape[-1] != 7 or tuple(rec.shape[:-2]) not in ((), (1, 1)) or rec.shape[-2] < 1:
         raise ValueError('detections: float32 records of shape (1, 1, R, 7) or (R, 7), got {} {}'.format(rec.dtype, rec.shape))
-    if not _count(images) or rec.shape[-2] % images:
-        raise ValueError('detections: {} records do not divide into {!r} images'.format(rec.shape[-2], images))
-    rec = rec.reshape(-1, 7)
-    N, P = int(images), rec.shape[0] // int(images)
-    conf, (H, W), labels, (min_h, min_w), cap = resolved(screen, P)
+    return rec.reshape(-1, 7)
+
+
+def screened(rec, groups: int, conf, labels, min_size, height, width, empty=None) -> tuple:
+    """The rule's `live`, `selected` and `rectangle` on (N P, 7) records of N = `groups` lists, over frames of (`height`, `width`) -- two
+    numbers, or float32 arrays with one extent per record --; `empty`: (N,) bool, the lists that take nothing.  (keep, x0, y0, w, h, label):
+    the (N, P) mask of the survivors before any cap, their rectangles as int64 and the rows' label words, one entry per record."""
+    N, P = groups, rec.shape[0] // groups
     dead = ~(rec[:, 0] >= 0).reshape(N, P)
     end = np.where(dead.any(axis=1), dead.argmax(axis=1), P)
-    keep = (np.arange(P)[None, :] < end[:, None]).ravel()
-    keep &= (rec[:, 2] >= np.float32(conf)) & np.isfinite(rec[:, 3:7]).all(axis=1)
+    live = np.arange(P)[None, :] < end[:, None]
+    if empty is not None:
+        live &= ~empty[:, None]
+    keep = live.ravel() & (rec[:, 2] >= np.float32(conf)) & np.isfinite(rec[:, 3:7]).all(axis=1)
     if labels is not None:
         keep &= np.isin(rec[:, 1], np.asarray(labels, np.int64).astype(np.float32))
     corners = np.where(keep[:, None], rec[:, 3:7], np.float32(0))
 
     def edge(v, extent, rounded):
         e = np.float32(extent)
-        with np.errstate(over='ignore'):
-            return rounded(np.minimum(np.maximum(v * e, np.float32(0)), e)).astype(np.int32)
+        with np.errstate(over='ignore', invalid='ignore'):
+            return rounded(np.minimum(np.maximum(v * e, np.float32(0)), e)).astype(np.int64)
 
-    x0, y0 = edge(corners[:, 0], W, np.floor), edge(corners[:, 1], H, np.floor)
-    w, h = edge(corners[:, 2], W, np.ceil) - x0, edge(corners[:, 3], H, np.ceil) - y0
-    keep &= (w >= min_w) & (h >= min_h)
-    keep = keep.reshape(N, P)
-    selected = keep.sum(axis=1).astype(np.int32)
-    kept = np.flatnonzero((keep & (np.cumsum(keep, axis=1) <= cap)).ravel())
-    label = rec[kept, 1]
+    x0, y0 = edge(corners[:, 0], width, np.floor), edge(corners[:, 1], height, np.floor)
+    w, h = edge(corners[:, 2], width, np.ceil) - x0, edge(corners[:, 3], height, np.ceil) - y0
+    keep &= (w >= min_size[1]) & (h >= min_size[0])
+    label = rec[:, 1]
     whole = np.isfinite(label) & (label >= np.float32(-2.0 ** 31)) & (label < np.float32(2.0 ** 31))
     with np.errstate(invalid='ignore'):
         label = np.where(whole, np.where(whole, label, np.float32(0)).astype(np.int32), np.int32(-1)).astype(np.int32)
-    rois = np.stack([(kept // P).astype(np.int32), x0[kept], y0[kept], w[kept], h[kept]], axis=1).astype(np.int32).reshape(-1, 5)
-    return Detections(np.minimum(selected, cap).astype(np.int32), selected, rois, label, rec[kept, 2].copy(), kept.astype(np.int32))
+    return keep.reshape(N, P), x0, y0, w, h, label
+
+
+def compact_records(records, images: int, screen) -> Detections:
+    """The rule in numpy on a host array of float32 records, (1, 1, R, 7) or (R, 7), of `images` images: what a Result computed on the
+    host (a foreign plugin set) gets.  `screen`: a DetectionScreen with a frame_size (there is no network here to take it from)."""
+    rec = records_checked(records)
+    if not _count(images) or rec.shape[0] % images:
+        raise ValueError('detections: {} records do not divide into {!r} images'.format(rec.shape[0], images))
+    N, P = int(images), rec.shape[0] // int(images)
+    conf, (H, W), labels, min_size, cap = resolved(screen, P)
+    keep, x0, y0, w, h, label = screened(rec, N, conf, labels, min_size, H, W)
+    selected = keep.sum(axis=1).astype(np.int32)
+    kept = np.flatnonzero((keep & (np.cumsum(keep, axis=1) <= cap)).ravel())
+    rois = np.stack([kept // P, x0[kept], y0[kept], w[kept], h[kept]], axis=1).astype(np.int32).reshape(-1, 5)
+    return Detections(np.minimum(selected, cap).astype(np.int32), selected, rois, label[kept], rec[kept, 2].copy(), kept.astype(np.int32))
 
 
 def records_of(port, batch: int):
@@ -163,7 +178,6 @@ def checked(ienet, detections, sharded: bool) -> dict:
     is needed, nothing is allocated."""
     if detections is None:
         return {}
-    from . import tiled_detections                            # (it imports this module)
     results = {name: next(iter(ienet.G.nodes[nid]['input'].values())) for nid, name in ienet.find_node_by_type('Result')}
     batch = int(ienet.batch_size)
     if isinstance(detections, dict):
@@ -191,51 +205,76 @@ def checked(ienet, detections, sharded: bool) -> dict:
         if batch * per_image >= (1 << 31) // 7:
             raise ValueError('detections: Result {!r} has too many records ({} x {})'.format(name, batch, per_image))
         what = 'Result {!r}: '.format(name)
-        if isinstance(screen, tiled_detections.TiledScreen):  # the batch rows are tiles of frames: tiled_detections.py's rule
-            out[name] = tiled_detections.resolved(screen, batch, per_image, what)._replace(input=tiled_detections.checked_input(ienet, screen, what))
+        if hasattr(screen, 'resolved_in'):                    # a TiledScreen: the batch rows are tiles of frames, tiled_detections.py's rule
+            out[name] = screen.resolved_in(ienet, per_image, what)
         else:
             out[name] = resolved(screen, per_image, _declared_extent(ienet), what)
     return out
 
 
-def _split(table, total: int) -> tuple:
-    """(rois, labels, scores, records) of the first `total` rows of an (n, 8) int32 table of the kernel's rows; the caller's own arrays."""
-    t = table[:total]
-    return t[:, :5].copy(), t[:, 5].copy(), t[:, 6].copy().view(np.float32), t[:, 7].copy()
+class TableBlocks:
+    """What a request keeps for one table-shaped answer over `groups` images or frames: the device header (counts, selected, total) and
+    rows that `ENTRY` writes, the labels on the device (uploaded once, here), and the page-locked host twins of header and rows that
+    wait() reads back into: the header, 4 (2 groups + 1) bytes, then exactly 32 total bytes."""
+    __slots__ = ('groups', 'screen', 'header', 'rows', 'labels', 'header_host', 'rows_host')
+    ENTRY = None
 
-
-class Blocks:
-    """What a request keeps for one (Result name, resolved screen): the device header (counts, selected, total) and rows that
-    pvhip_detections_compact writes, the labels on the device (uploaded once, here), and the page-locked host twins of header and rows
-    that wait() reads back into: the header, then exactly 32 total bytes."""
-    __slots__ = ('images', 'per_image', 'screen', 'header', 'rows', 'labels', 'header_host', 'rows_host')
-
-    def __init__(self, images: int, per_image: int, screen: DetectionScreen):
-        self.images, self.per_image, self.screen = images, per_image, screen
-        capacity = images * min(per_image, screen.max_per_image)
-        self.header = device.DeviceTensor.empty((2 * images + 1,), np.int32)
+    def __init__(self, groups: int, capacity: int, screen):
+        self.groups, self.screen = groups, screen
+        self.header = device.DeviceTensor.empty((2 * groups + 1,), np.int32)
         self.rows = device.DeviceTensor.empty((capacity, 8), np.int32)
-        self.header_host = device.host_empty((2 * images + 1,), np.int32)
+        self.header_host = device.host_empty((2 * groups + 1,), np.int32)
         self.rows_host = device.host_empty((capacity, 8), np.int32)
         # ([]: a device pointer with no label behind it, which selects nothing; None: NULL, any label)
         self.labels = None if screen.labels is None else device.DeviceTensor.from_numpy(np.asarray(screen.labels + (0,), np.int32))
+
+    def read_back(self) -> Detections:
+        """The answer, copied on the current stream, which has drained: the header, then the rows it counts; the arrays are the
+        caller's own."""
+        n = self.groups
+        device.call('pvhip_memcpy_d2h', ctypes.c_void_p(self.header_host.ctypes.data), ctypes.c_void_p(self.header.ptr), self.header_host.nbytes)
+        total = int(self.header_host[2 * n])
+        if not 0 <= total <= self.rows_host.shape[0]:
+            raise device.PvhipError('{} left total = {} of at most {} rows'.format(self.ENTRY, total, self.rows_host.shape[0]))
+        if total:
+            device.call('pvhip_memcpy_d2h', ctypes.c_void_p(self.rows_host.ctypes.data), ctypes.c_void_p(self.rows.ptr), 32 * total)
+        t = self.rows_host[:total]                             # the kernel's rows (id, x, y, w, h, label, score bits, record)
+        return Detections(self.header_host[:n].copy(), self.header_host[n:2 * n].copy(), t[:, :5].copy(), t[:, 5].copy(),
+                          t[:, 6].copy().view(np.float32), t[:, 7].copy())
+
+
+class Blocks(TableBlocks):
+    """The blocks of one (Result name, resolved screen): what pvhip_detections_compact writes."""
+    __slots__ = ('images', 'per_image')
+    ENTRY = 'pvhip_detections_compact'
+
+    def __init__(self, images: int, per_image: int, screen: DetectionScreen):
+        super().__init__(images, images * min(per_image, screen.max_per_image), screen)
+        self.images, self.per_image = images, per_image
 
     def launch(self, result):
         """The entry's two launches on the current stream, behind whatever wrote `result` there."""
         s = self.screen
         assert result.dtype == np.float32 and int(np.prod(result.shape)) == 7 * self.images * self.per_image
-        device.call('pvhip_detections_compact', device.ptr(result), self.images, self.per_image, s.frame_size[0], s.frame_size[1],
+        device.call(self.ENTRY, device.ptr(result), self.images, self.per_image, s.frame_size[0], s.frame_size[1],
                     s.min_confidence, device.ptr(self.labels), 0 if s.labels is None else len(s.labels), s.min_size[0], s.min_size[1],
                     s.max_per_image, ctypes.c_void_p(self.header.ptr), ctypes.c_void_p(self.rows.ptr))
 
-    def read_back(self) -> Detections:
-        """The answer, copied on the current stream, which has drained: the header, then the rows it counts; the arrays are the
-        caller's own."""
-        n = self.images
-        device.call('pvhip_memcpy_d2h', ctypes.c_void_p(self.header_host.ctypes.data), ctypes.c_void_p(self.header.ptr), self.header_host.nbytes)
-        total = int(self.header_host[2 * n])
-        if not 0 <= total <= self.rows_host.shape[0]:
-            raise device.PvhipError('pvhip_detections_compact left total = {} of at most {} rows'.format(total, self.rows_host.shape[0]))
-        if total:
-            device.call('pvhip_memcpy_d2h', ctypes.c_void_p(self.rows_host.ctypes.data), ctypes.c_void_p(self.rows.ptr), 32 * total)
-        return Detections(self.header_host[:n].copy(), self.header_host[n:2 * n].copy(), *_split(self.rows_host, total))
+
+class Ask(collections.namedtuple('Ask', 'screen images')):
+    """A Result of `images` images asked for with a resolved DetectionScreen, as answers.py drives it (top_k.Ask)."""
+    __slots__ = ()
+
+    def bound(self, inputs, slots):
+        return self
+
+    def key(self, name):
+        return (name, self.screen)
+
+    def launch(self, blocks, value):
+        blocks = blocks or Blocks(self.images, value.shape[-2] // self.images, self.screen)
+        blocks.launch(value)
+        return blocks
+
+    def on_host(self, value):
+        return compact_records(value, self.images, self.screen)

@@ -33,7 +33,8 @@ import xml.etree.ElementTree as et
 import networkx as nx
 import numpy as np
 
-from . import common_def, detections as detections_rule, device, fusion_plan, stream_plan, tiled_detections as tiled_rule, top_k as top_k_rule
+from . import common_def, device, fusion_plan, stream_plan
+from .answers import Answers
 from .host_input import HostInputs
 from .input_format import DetectedRois, InputInfo, PreProcessChannel, PreProcessInfo  # noqa: F401 -- the classes of IENetwork.input_info
 from .stream_plan import CaptureStreamModel
@@ -321,9 +322,7 @@ class InferRequest:
     def __init__(self, owner, runner, index: int):
         self.owner, self.runner, self.index = owner, runner, index      # owner: the network load_network returned
         self._in_flight, self._replayed = False, None
-        self._top_k = {}                # {Result name: k} of the pass in flight
-        self._detections = {}           # {Result name: resolved DetectionScreen or TiledScreen} of the pass in flight
-        self._tiles = {}                # {Result name: (input name, frame count m)} of its TiledScreens
+        self._asks = {}                 # {Result name: ask} of the pass in flight (answers.py): what top_k= and detections= named
 
     def start_async(self, inputs: dict, top_k=None, detections=None):
         self._start(inputs, top_k, False, detections)
@@ -332,18 +331,10 @@ class InferRequest:
         if self._in_flight:
             raise RuntimeError('request {} is still in flight: wait() first'.format(self.index))
         ex = self.runner
-        tiled_rule.checked_top_k(top_k, detections)
-        wanted = top_k_rule.checked(ex.ienet, top_k, ex.sharded or self.owner.sharded)
-        screens = detections_rule.checked(ex.ienet, detections, ex.sharded or self.owner.sharded)
-        both = sorted(set(wanted) & set(screens))
-        if both:
-            raise ValueError('detections: Result {!r} is asked for with top_k as well'.format(both[0]))
-        tiled = {name: s for name, s in screens.items() if isinstance(s, tiled_rule.TiledScreen)}
-        tiled_rule.checked_feed(inputs, tiled)
-        self._top_k, self._detections = wanted, screens
-        fed = {name: inputs[s.input] for name, s in tiled.items()}
-        inputs = ex.host_inputs.stage(inputs, ex.stream_base, ex.sharded or self.owner.sharded)
-        self._tiles = {name: (tiled[name].input, int(np.shape(roi.frames)[0])) for name, roi in fed.items()}    # (staged: the frames are m frames)
+        sharded = ex.sharded or self.owner.sharded
+        asks = ex.answers.checked(inputs, top_k, detections, sharded)
+        fed, inputs = inputs, ex.host_inputs.stage(inputs, ex.stream_base, sharded)
+        self._asks = ex.answers.bound(asks, fed)
         ex.wait_result_readers()
         # The same device-resident tensors as the last calls: the pass is replayed from this request's own recording (one call
         # instead of ~100 dispatches; every request records its own pass on its own stream and keeps its own tensors, so the
@@ -355,13 +346,10 @@ class InferRequest:
             ex._bind_inputs(inputs)
             with ex._results_on_device():        # the shards are gathered in wait(): one collective at a time, on stream 0
                 ex.run_tasks(verbose)
-        if self._top_k:                          # behind the pass, replayed or eager, and outside the recording: one recording serves both
-            ex.launch_top_k(self._top_k, self._replayed)
-        plain = {name: s for name, s in screens.items() if name not in tiled}
-        if plain:                                # likewise
-            ex.launch_detections(plain, self._replayed)
-        if tiled:                                # likewise, with the tile table stage() uploaded
-            ex.launch_tiled_detections(tiled, self._tiles, self._replayed)
+        if self._asks:                           # behind the pass, replayed or eager, and outside the recording: one recording serves every kind
+            G = ex.ienet.G
+            ex.answers.launch(self._asks, self._replayed['results'] if self._replayed is not None else
+                              {name: G.nodes[nid]['result'] for nid, name in ex.ienet.find_node_by_type('Result')})
         self._in_flight = True
 
     def wait(self) -> dict:
@@ -371,17 +359,11 @@ class InferRequest:
         self._in_flight = False
         out = {}
         replayed, self._replayed = self._replayed, None
-        top_k, self._top_k = self._top_k, {}
-        screens, self._detections = self._detections, {}
-        tiles, self._tiles = self._tiles, {}
+        asks, self._asks = self._asks, {}
         for nid, name in ex.ienet.find_node_by_type('Result'):
             value = replayed['results'][name] if replayed is not None else G.nodes[nid]['result']
-            if name in top_k:                    # (n, k) pairs come back; the Result itself stays where it is
-                G.nodes[nid]['result'], out[name] = value, ex.read_top_k(name, top_k[name], value)
-            elif name in tiles:                  # the frames' detections come back; the records stay where they are
-                G.nodes[nid]['result'], out[name] = value, ex.read_tiled_detections(name, screens[name], tiles[name], value)
-            elif name in screens:                # the survivors come back; the records stay where they are
-                G.nodes[nid]['result'], out[name] = value, ex.read_detections(name, screens[name], value)
+            if name in asks:                     # the answer comes back; the Result itself stays where it is, on the device
+                G.nodes[nid]['result'], out[name] = value, ex.answers.read(name, asks[name], value)
             else:
                 G.nodes[nid]['result'] = out[name] = ex._read_back(value, self.owner.comm)
         return out
@@ -471,12 +453,10 @@ class Executable_Network:
         # events behind the launches of OTHER requests that read this network's device-resident Result (a DetectedRois fed from this
         # request while in flight): the next pass, eager or replayed, waits for them on the device before it can overwrite that tensor
         self._result_readers = []
-        self._top_k_blocks = {}         # {(Result name, k): top_k.Blocks}: the device block and the page-locked block of a top_k pass
-        self._detection_blocks = {}     # {(Result name, resolved DetectionScreen): detections.Blocks}, likewise for a detections pass
-        self._tile_blocks = {}          # {(Result name, resolved TiledScreen, m): tiled_detections.Blocks}, likewise for a tiled one
         if input_formats is None:
             input_formats = {name: info.frozen() for name, info in ienetwork.input_info.items()}
         self.host_inputs = HostInputs(input_formats)    # host arrays in a declared format or the request's own buffers -> device tensors
+        self.answers = Answers(self)    # Results asked for with top_k= / detections=: their blocks, launches and read-backs
         self._graph = None              # the recorded pass (capture_graph): {'handle', 'inputs', 'keep', 'results', 'by_hand'}
         self._auto_graph = {'key': None, 'seen': 0, 'failed': False, 'captured': False}     # infer()'s own recording (_graph_for)
         self._auto_graph_busy = False   # _graph_for is recording
@@ -526,9 +506,7 @@ class Executable_Network:
         self.release_graph()
         self.host_inputs.release()                  # page-locked buffers go back once the caller holds no view of them
         self._result_readers = []
-        self._top_k_blocks = {}
-        self._detection_blocks = {}
-        self._tile_blocks = {}
+        self.answers.release()
         G = self.ienet.G
         for nid in G.nodes:
             node = G.nodes[nid]
@@ -552,100 +530,6 @@ class Executable_Network:
 
     def start_async(self, request_id: int, inputs: dict, top_k=None, detections=None):
         self.requests[request_id].start_async(inputs, top_k, detections)
-
-    def launch_top_k(self, top_k: dict, replayed):
-        """pvhip_topk_rows_f32 for every Result named in `top_k` = {name: k} that the pass just issued (`replayed`: its recording, or None
-        for an eager pass) leaves on the device, on the base stream behind that pass; wait_done() then waits for an event behind the
-        launches.  The blocks are this request's own, made on first use per (name, k).  A Result that is a host array gets the rule in
-        numpy when it is read (read_top_k)."""
-        G = self.ienet.G
-        values = {name: (replayed['results'][name] if replayed is not None else G.nodes[nid]['result'])
-                  for nid, name in self.ienet.find_node_by_type('Result') if name in top_k}
-        values = {name: value for name, value in values.items() if isinstance(value, device.DeviceTensor)}
-        if not values:
-            return
-        device.select_stream(self.stream_base)
-        for name, value in values.items():
-            key = (name, top_k[name])
-            if key not in self._top_k_blocks:
-                self._top_k_blocks[key] = top_k_rule.Blocks(top_k_rule.rows_of(value.shape)[0], top_k[name])
-            self._top_k_blocks[key].launch(value)
-        self._pending = (self._pending[0] if self._pending is not None else None, self._order_event().record())
-        device.select_stream(0)
-
-    def read_top_k(self, name: str, k: int, value):
-        """The TopK of Result `name` after wait_done(): one copy from the block launch_top_k filled, on this network's drained base
-        stream; the rule in numpy for a Result that is a host array."""
-        if not isinstance(value, device.DeviceTensor):
-            return top_k_rule.top_k_rows(np.asarray(value), k)
-        device.select_stream(self.stream_base)
-        out = self._top_k_blocks[(name, k)].read_back()
-        device.select_stream(0)
-        return out
-
-    def launch_detections(self, screens: dict, replayed):
-        """pvhip_detections_compact for every Result named in `screens` = {name: resolved DetectionScreen}, exactly as launch_top_k does
-        its launch: on the base stream behind the pass that `replayed` (or the eager pass) just issued, outside the recording, with the
-        event wait_done() waits for behind it.  The blocks are this request's own, made on first use per (name, screen).  A Result that
-        is a host array gets the rule in numpy when it is read (read_detections)."""
-        G = self.ienet.G
-        values = {name: (replayed['results'][name] if replayed is not None else G.nodes[nid]['result'])
-                  for nid, name in self.ienet.find_node_by_type('Result') if name in screens}
-        values = {name: value for name, value in values.items() if isinstance(value, device.DeviceTensor)}
-        if not values:
-            return
-        images = int(self.ienet.batch_size)
-        device.select_stream(self.stream_base)
-        for name, value in values.items():
-            key = (name, screens[name])
-            if key not in self._detection_blocks:
-                self._detection_blocks[key] = detections_rule.Blocks(images, value.shape[-2] // images, screens[name])
-            self._detection_blocks[key].launch(value)
-        self._pending = (self._pending[0] if self._pending is not None else None, self._order_event().record())
-        device.select_stream(0)
-
-    def read_detections(self, name: str, screen, value):
-        """The Detections of Result `name` after wait_done(): the header and then the rows it counts, from the blocks launch_detections
-        filled, on this network's drained base stream; the rule in numpy for a Result that is a host array."""
-        if not isinstance(value, device.DeviceTensor):
-            return detections_rule.compact_records(np.asarray(value), int(self.ienet.batch_size), screen)
-        device.select_stream(self.stream_base)
-        out = self._detection_blocks[(name, screen)].read_back()
-        device.select_stream(0)
-        return out
-
-    def launch_tiled_detections(self, screens: dict, tiles: dict, replayed):
-        """pvhip_detections_merge_tiles for every Result named in `screens` = {name: resolved TiledScreen}, as launch_detections does its
-        launch: on the base stream behind the pass -- and behind the upload of the tile table, which that stream waited for in stage() --,
-        outside the recording.  `tiles` = {name: (input name, m)}: the table is that input's slot's, on the device.  The blocks are this
-        request's own, made on first use per (name, screen, m)."""
-        G = self.ienet.G
-        values = {name: (replayed['results'][name] if replayed is not None else G.nodes[nid]['result'])
-                  for nid, name in self.ienet.find_node_by_type('Result') if name in screens}
-        values = {name: value for name, value in values.items() if isinstance(value, device.DeviceTensor)}
-        if not values:
-            return
-        n = int(self.ienet.batch_size)
-        device.select_stream(self.stream_base)
-        for name, value in values.items():
-            source, m = tiles[name]
-            key = (name, screens[name], m)
-            if key not in self._tile_blocks:
-                self._tile_blocks[key] = tiled_rule.Blocks(n, value.shape[-2] // n, m, screens[name])
-            self._tile_blocks[key].launch(value, self.host_inputs.slots[source].rois)
-        self._pending = (self._pending[0] if self._pending is not None else None, self._order_event().record())
-        device.select_stream(0)
-
-    def read_tiled_detections(self, name: str, screen, tiles, value):
-        """The Detections over frames of Result `name` after wait_done(): the header and then the rows it counts, from the blocks
-        launch_tiled_detections filled; the rule in numpy, on the page-locked table, for a Result that is a host array."""
-        source, m = tiles
-        if not isinstance(value, device.DeviceTensor):
-            return tiled_rule.merge_tiles(np.asarray(value), self.host_inputs.slots[source].rois_host, m, screen)
-        device.select_stream(self.stream_base)
-        out = self._tile_blocks[(name, screen, m)].read_back()
-        device.select_stream(0)
-        return out
 
     def wait(self, request_id: int) -> dict:
         return self.requests[request_id].wait()

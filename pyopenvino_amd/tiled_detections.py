@@ -48,6 +48,10 @@ class TiledScreen(_Tiled):
         frozen = [detections._frozen(v) for v in (labels, min_size)]
         return super().__new__(cls, min_confidence, frozen[0], frozen[1], max_per_tile, overlap, threshold, per_label, max_per_frame, input)
 
+    def resolved_in(self, ienet, per_tile: int, what='') -> 'TiledScreen':
+        """What detections.checked() makes of this screen for a Result of `ienet` with P = `per_tile`: resolved, with its `input` named."""
+        return resolved(self, int(ienet.batch_size), per_tile, what)._replace(input=checked_input(ienet, self, what))
+
 
 def resolved(screen: TiledScreen, tiles: int, per_tile: int, what='') -> TiledScreen:
     """`screen` with every value checked and in its one form for n = `tiles` batch rows of P = `per_tile` records -- max_per_tile and
@@ -107,11 +111,6 @@ def checked_feed(inputs: dict, screens: dict):
                 name, screen.input, type(fed).__name__))
 
 
-def _edge(v, extent, rounded):
-    with np.errstate(over='ignore', invalid='ignore'):
-        return rounded(np.minimum(np.maximum(v * extent, np.float32(0)), extent)).astype(np.int64)
-
-
 def _overlap(box, others, kind: str, threshold: float):
     """Step 3's comparison of one int64 (x0, y0, w, h) with the rows of `others`."""
     iw = np.minimum(box[0] + box[2], others[:, 0] + others[:, 2]) - np.maximum(box[0], others[:, 0])
@@ -125,42 +124,27 @@ def _overlap(box, others, kind: str, threshold: float):
 def merge_tiles(records, rois, frames: int, screen) -> Detections:
     """The rule in numpy on a host array of float32 records, (1, 1, R, 7) or (R, 7), of the n tiles `rois` (an integer (n, 5) table, row
     b = (f, x, y, w, h)) of `frames` = m frames: what a Result computed on the host gets.  `screen`: a TiledScreen, or a min_confidence."""
-    rec, t = np.asarray(records), np.asarray(rois)
-    if rec.dtype != np.float32 or rec.ndim not in (2, 4) or rec.shape[-1] != 7 or tuple(rec.shape[:-2]) not in ((), (1, 1)) or rec.shape[-2] < 1:
-        raise ValueError('detections: float32 records of shape (1, 1, R, 7) or (R, 7), got {} {}'.format(rec.dtype, rec.shape))
-    if t.ndim != 2 or t.shape[1] != 5 or t.shape[0] < 1 or t.dtype.kind not in 'iu' or rec.shape[-2] % t.shape[0]:
+    rec, t = detections.records_checked(records), np.asarray(rois)
+    if t.ndim != 2 or t.shape[1] != 5 or t.shape[0] < 1 or t.dtype.kind not in 'iu' or rec.shape[0] % t.shape[0]:
         raise ValueError('detections: an integer (n, 5) table of tiles with n dividing the {} records, got {} {}'.format(
-            rec.shape[-2], t.dtype, t.shape))
+            rec.shape[0], t.dtype, t.shape))
     if not detections._count(frames):
         raise ValueError('detections: {!r} frames'.format(frames))
-    rec, t = rec.reshape(-1, 7), t.astype(np.int64)
+    t = t.astype(np.int64)
     n, m = t.shape[0], int(frames)
     P = rec.shape[0] // n
     if not isinstance(screen, TiledScreen):
         screen = TiledScreen(min_confidence=screen)
-    conf, labels, (min_h, min_w), cap, kind, threshold, per_label, frame_cap, _ = resolved(screen, n, P)
-    # 1. candidates
+    conf, labels, min_size, cap, kind, threshold, per_label, frame_cap, _ = resolved(screen, n, P)
+    # 1. candidates: the plain screen over each tile's own extent
     f, x, y, w, h = t.T
     tile_ok = (f >= 0) & (f < m) & (w >= 1) & (w <= detections.MAX_EXTENT) & (h >= 1) & (h <= detections.MAX_EXTENT)
-    dead = ~(rec[:, 0] >= 0).reshape(n, P)
-    end = np.where(dead.any(axis=1), dead.argmax(axis=1), P)
-    keep = ((np.arange(P)[None, :] < end[:, None]) & tile_ok[:, None]).ravel()
-    keep &= (rec[:, 2] >= np.float32(conf)) & np.isfinite(rec[:, 3:7]).all(axis=1)
-    if labels is not None:
-        keep &= np.isin(rec[:, 1], np.asarray(labels, np.int64).astype(np.float32))
-    corners = np.where(keep[:, None], rec[:, 3:7], np.float32(0))
-    fw, fh = np.repeat(np.where(tile_ok, w, 1), P).astype(np.float32), np.repeat(np.where(tile_ok, h, 1), P).astype(np.float32)
-    x0, y0 = _edge(corners[:, 0], fw, np.floor), _edge(corners[:, 1], fh, np.floor)
-    bw, bh = _edge(corners[:, 2], fw, np.ceil) - x0, _edge(corners[:, 3], fh, np.ceil) - y0
-    keep &= (bw >= min_w) & (bh >= min_h)
-    keep = keep.reshape(n, P)
+    fh, fw = np.repeat(np.where(tile_ok, h, 1), P).astype(np.float32), np.repeat(np.where(tile_ok, w, 1), P).astype(np.float32)
+    keep, x0, y0, bw, bh, label = detections.screened(rec, n, conf, labels, min_size, fh, fw, ~tile_ok)
     cand = np.flatnonzero((keep & (np.cumsum(keep, axis=1) <= cap)).ravel())
     tile = cand // P
     boxes = np.stack([(x[tile] + x0[cand]).astype(np.int32), (y[tile] + y0[cand]).astype(np.int32), bw[cand], bh[cand]], axis=1).astype(np.int64)
-    label = rec[cand, 1]
-    whole = np.isfinite(label) & (label >= np.float32(-2.0 ** 31)) & (label < np.float32(2.0 ** 31))
-    with np.errstate(invalid='ignore'):
-        label = np.where(whole, np.where(whole, label, np.float32(0)).astype(np.int32), np.int32(-1)).astype(np.int32)
+    label = label[cand]
     score = rec[cand, 2]
     counts, selected, rows = np.zeros(m, np.int32), np.zeros(m, np.int32), []
     for frame in range(m):
@@ -188,23 +172,16 @@ def merge_tiles(records, rois, frames: int, screen) -> Detections:
     return Detections(counts, selected, table, label[rows].astype(np.int32), score[rows].copy(), kept.astype(np.int32))
 
 
-class Blocks:
-    """What a request keeps for one (Result name, resolved screen, m): the device header (counts, selected, total), rows and candidate
-    scratch that pvhip_detections_merge_tiles writes, the labels on the device (uploaded once, here), and the page-locked host twins of
-    header and rows that wait() reads back into: 4 (2 m + 1) bytes, then exactly 32 total bytes."""
-    __slots__ = ('tiles', 'per_tile', 'frames', 'screen', 'header', 'rows', 'scratch', 'labels', 'header_host', 'rows_host')
+class Blocks(detections.TableBlocks):
+    """The blocks of one (Result name, resolved screen, m): what pvhip_detections_merge_tiles writes, and its candidate scratch."""
+    __slots__ = ('tiles', 'per_tile', 'frames', 'scratch')
+    ENTRY = 'pvhip_detections_merge_tiles'
 
     def __init__(self, tiles: int, per_tile: int, frames: int, screen: TiledScreen):
-        self.tiles, self.per_tile, self.frames, self.screen = tiles, per_tile, frames, screen
         slots = tiles * screen.max_per_tile
-        capacity = min(slots, frames * screen.max_per_frame)
-        self.header = device.DeviceTensor.empty((2 * frames + 1,), np.int32)
-        self.rows = device.DeviceTensor.empty((capacity, 8), np.int32)
+        super().__init__(frames, min(slots, frames * screen.max_per_frame), screen)
+        self.tiles, self.per_tile, self.frames = tiles, per_tile, frames
         self.scratch = device.DeviceTensor.empty((9 * slots + tiles,), np.int32)
-        self.header_host = device.host_empty((2 * frames + 1,), np.int32)
-        self.rows_host = device.host_empty((capacity, 8), np.int32)
-        # ([]: a device pointer with no label behind it, which selects nothing; None: NULL, any label)
-        self.labels = None if screen.labels is None else device.DeviceTensor.from_numpy(np.asarray(screen.labels + (0,), np.int32))
 
     def launch(self, result, table):
         """The entry's three launches on the current stream, behind whatever wrote `result` and uploaded `table` (the slot's (n, 5)
@@ -212,19 +189,27 @@ class Blocks:
         s = self.screen
         assert result.dtype == np.float32 and int(np.prod(result.shape)) == 7 * self.tiles * self.per_tile
         assert table.dtype == np.int32 and tuple(table.shape) == (self.tiles, 5)
-        device.call('pvhip_detections_merge_tiles', device.ptr(result), device.ptr(table), self.tiles, self.per_tile, self.frames,
+        device.call(self.ENTRY, device.ptr(result), device.ptr(table), self.tiles, self.per_tile, self.frames,
                     s.min_confidence, device.ptr(self.labels), 0 if s.labels is None else len(s.labels), s.min_size[0], s.min_size[1],
                     s.max_per_tile, OVERLAPS[s.overlap], s.threshold, int(s.per_label), s.max_per_frame, ctypes.c_void_p(self.scratch.ptr),
                     ctypes.c_void_p(self.header.ptr), ctypes.c_void_p(self.rows.ptr))
 
-    def read_back(self) -> Detections:
-        """The answer, copied on the current stream, which has drained: the header, then the rows it counts; the arrays are the
-        caller's own."""
-        m = self.frames
-        device.call('pvhip_memcpy_d2h', ctypes.c_void_p(self.header_host.ctypes.data), ctypes.c_void_p(self.header.ptr), self.header_host.nbytes)
-        total = int(self.header_host[2 * m])
-        if not 0 <= total <= self.rows_host.shape[0]:
-            raise device.PvhipError('pvhip_detections_merge_tiles left total = {} of at most {} rows'.format(total, self.rows_host.shape[0]))
-        if total:
-            device.call('pvhip_memcpy_d2h', ctypes.c_void_p(self.rows_host.ctypes.data), ctypes.c_void_p(self.rows.ptr), 32 * total)
-        return Detections(self.header_host[:m].copy(), self.header_host[m:2 * m].copy(), *detections._split(self.rows_host, total))
+
+class Ask(collections.namedtuple('Ask', 'screen tiles frames slot')):
+    """A Result asked for with a resolved TiledScreen over n = `tiles` batch rows, as answers.py drives it (top_k.Ask); `frames` = m
+    and `slot`, the staged input's with the tile table page-locked and on the device, are known once the pass's inputs are staged."""
+    __slots__ = ()
+
+    def bound(self, inputs, slots):
+        return self._replace(frames=int(np.shape(inputs[self.screen.input].frames)[0]), slot=slots[self.screen.input])
+
+    def key(self, name):
+        return (name, self.screen, self.frames)
+
+    def launch(self, blocks, value):
+        blocks = blocks or Blocks(self.tiles, value.shape[-2] // self.tiles, self.frames, self.screen)
+        blocks.launch(value, self.slot.rois)
+        return blocks
+
+    def on_host(self, value):
+        return merge_tiles(value, self.slot.rois_host, self.frames, self.screen)

@@ -98,3 +98,23 @@ class Blocks:
         """The pair, copied on the current stream, which has drained; the arrays are the caller's own."""
         device.call('pvhip_memcpy_d2h', ctypes.c_void_p(self.host.ctypes.data), ctypes.c_void_p(self.dev.ptr), self.host.nbytes)
         return TopK(self.host[0].copy(), self.host[1].view(np.float32).copy())
+
+
+class Ask(collections.namedtuple('Ask', 'k')):
+    """A Result asked for with top_k=k, as answers.py drives it: the key of its blocks, the launch on the value a pass left on the
+    device -- into `blocks`, or into new ones for None: they are returned --, and the rule on a host value."""
+    __slots__ = ()
+
+    def bound(self, inputs, slots):
+        return self
+
+    def key(self, name):
+        return (name, self.k)
+
+    def launch(self, blocks, value):
+        blocks = blocks or Blocks(rows_of(value.shape)[0], self.k)
+        blocks.launch(value)
+        return blocks
+
+    def on_host(self, value):
+        return top_k_rows(value, self.k)

@@ -183,7 +183,7 @@ def test_argument_rules():
                 start(d)
             assert str(e.value).startswith('detections: '), str(e.value)
         for r in network.requests:
-            assert not r._in_flight and not r._detections and not r.runner._detection_blocks and not r.runner._top_k_blocks
+            assert not r._in_flight and not r._asks and not r.runner.answers.blocks
             assert not r.runner.host_inputs.slots and r.runner._pending is None
 
     def each_form(match, **opt):
@@ -427,11 +427,12 @@ def test_public_path_on_ssd_mobilenet(hip):
     _same(results[2], detections_ref.compact(full_x, m, (300, 300), min_confidence=0.3), 'call 2')
     _same(results[3], detections_ref.as_words(results[0]), 'call 3 vs call 0')
     # the request's own blocks, one per (name, screen)
-    keys = sorted(det._detection_blocks, key=repr)
+    keys = sorted(det.answers.blocks, key=repr)
     assert len(keys) == 3 and {k[0] for k in keys} == {out_name}
+    assert all(len(k) == 2 and type(k[1]) is DetectionScreen for k in keys)         # no key of another kind
     assert {(k[1].min_confidence, k[1].max_per_image, k[1].frame_size) for k in keys} == {(conf, 100, (300, 300)), (0.3, 100, (300, 300)), (0.0, 3, hw)}
     det.release_device_state()
-    assert not det._detection_blocks
+    assert not det.answers.blocks
 
 
 @pytest.mark.gpu

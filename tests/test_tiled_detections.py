@@ -244,8 +244,7 @@ def test_argument_rules():
                 start(d)
             assert str(e.value).startswith('detections: '), str(e.value)
         for r in ex.requests:
-            assert not r._in_flight and not r._detections and not r._tiles and not r._top_k
-            assert not r.runner._tile_blocks and not r.runner._detection_blocks and not r.runner._top_k_blocks
+            assert not r._in_flight and not r._asks and not r.runner.answers.blocks
             assert not r.runner.host_inputs.slots and r.runner._pending is None
 
     def each_form(match, **opt):
@@ -554,11 +553,14 @@ def test_public_path_on_ssd_mobilenet(hip):
     checked, largest = det.host_inputs.formats[name].checked_rois(table, hw, m)
     assert np.array_equal(checked, table) and largest[0] <= hw[0] and largest[1] <= hw[1]
     # the request's own blocks, one per (name, screen, m)
-    keys = sorted(det._tile_blocks, key=repr)
+    keys = sorted((k for k in det.answers.blocks if len(k) == 3), key=repr)
     assert len(keys) == 2 and {(k[0], k[2]) for k in keys} == {(out_name, m)}
     assert {(k[1].min_confidence, k[1].max_per_tile, k[1].max_per_frame, k[1].input) for k in keys} == {(conf, 100, 400, name), (0.0, 30, 5, name)}
+    # (no key of another kind but call 2's plain screen)
+    assert [k for k in det.answers.blocks if len(k) != 3] == [(out_name, DetectionScreen(conf, (300, 300), None, (1, 1), 100))]
+    assert all(type(k[1]) is TiledScreen for k in keys)
     det.release_device_state()
-    assert not det._tile_blocks and not det._detection_blocks
+    assert not det.answers.blocks
 
 
 @pytest.mark.gpu

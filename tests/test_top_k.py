@@ -120,7 +120,7 @@ def test_argument_rules():
                 start(k)
             assert str(e.value).startswith('top_k: '), str(e.value)
         for r in network.requests:
-            assert not r._in_flight and not r.runner._top_k_blocks and not r.runner.host_inputs.slots and r.runner._pending is None
+            assert not r._in_flight and not r._asks and not r.runner.answers.blocks and not r.runner.host_inputs.slots and r.runner._pending is None
 
     for bad in (0, -1, 65, 1001, 2 ** 31):
         refused('outside 1', bad)
@@ -350,9 +350,9 @@ def test_public_path_on_googlenet(hip):
         else:
             first[key] = res if kind is not None else np.array(res, copy=True)
     assert ex._auto_graph['captured'] and ex._graph is not None              # one recording served every kind
-    assert sorted(ex._top_k_blocks) == [(out_name, 1), (out_name, 5), (out_name, 64)]      # the request's own blocks, one per (name, k)
+    assert sorted(ex.answers.blocks) == [(out_name, 1), (out_name, 5), (out_name, 64)]     # the request's own blocks, one per (name, k), no other kind's
     ex.release_device_state()
-    assert not ex._top_k_blocks
+    assert not ex.answers.blocks
 
 
 @pytest.mark.gpu
