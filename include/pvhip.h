@@ -528,6 +528,16 @@ int pvhip_detection_output_f32(const float* loc, const float* conf, const float*
  * `labels` NULL (any label; num_labels == 0) or a device pointer; else PVHIP_EINVAL. */
 int pvhip_detections_to_rois(const float* records, int* rois, int* record_of, int* counts, int n, int images, int records_per_image,
                              int frame_h, int frame_w, float min_confidence, const int* labels, int num_labels, int min_h, int min_w);
+/* Addition to ABI v18 (the version number is unchanged: nothing existing changed): the same table for a detector whose input was fitted
+ * (pvhip_input_preprocess_fit_f32 below): the detector saw the frame in the rectangle [dy, dy + ih) x [dx, dx + iw) of its (net_h, net_w)
+ * input.  Each corner is mapped back in fp32, never contracted, three roundings: u = (xmin * (float)net_w - (float)dx) / (float)iw, xmax
+ * alike, ymin / ymax with net_h, dy, ih; then the rule above with u in the place of the corner: floor / ceil of the clamped product
+ * with the frame extent, min_h / min_w.  The finite check is on the record's own corners.  A box in the padding clamps to the frame's
+ * edge; one wholly in the padding has extent 0 and is dropped.  net_h, net_w in [1, 2^24], iw, ih >= 1, dx, dy >= 0, dx + iw <= net_w,
+ * dy + ih <= net_h, and the limits above; else PVHIP_EINVAL.  In numpy: tests/letterbox_ref.py. */
+int pvhip_detections_to_rois_fit(const float* records, int* rois, int* record_of, int* counts, int n, int images, int records_per_image,
+                                 int frame_h, int frame_w, float min_confidence, const int* labels, int num_labels, int min_h, int min_w,
+                                 int net_h, int net_w, int dx, int dy, int iw, int ih);
 
 /* ---------------------------------------------------------------- a classifier's answer ---- */
 /* Addition to ABI v18 (the version number is unchanged: nothing existing changed): the k best entries of every row of a contiguous
@@ -566,6 +576,11 @@ int pvhip_topk_rows_f32(const float* x, int rows, int cols, int k, int* indices,
  * non-NULL `labels` with num_labels == 0 selects nothing), no NULL records / header / rows; else PVHIP_EINVAL and nothing is launched. */
 int pvhip_detections_compact(const float* records, int images, int records_per_image, int frame_h, int frame_w, float min_confidence,
                              const int* labels, int num_labels, int min_h, int min_w, int max_per_image, int* header, int* rows);
+/* Addition to ABI v18 (the version number is unchanged: nothing existing changed): the same answer for a detector whose input was fitted:
+ * the rectangle rule of pvhip_detections_to_rois_fit (one device function serves all four entries), everything else as above. */
+int pvhip_detections_compact_fit(const float* records, int images, int records_per_image, int frame_h, int frame_w, float min_confidence,
+                                 const int* labels, int num_labels, int min_h, int min_w, int max_per_image, int* header, int* rows,
+                                 int net_h, int net_w, int dx, int dy, int iw, int ih);
 /* Addition to ABI v18 (the version number is unchanged: nothing existing changed): a TILED detector's answer.  The n batch rows of the
  * pass are tiles of m frames -- `tiles` is the (n, 5) int32 device table of a RoiInput, row b = (f, x, y, w, h): batch row b saw the
  * rectangle [y, y + h) x [x, x + w) of frame f --, and the records of all tiles become one table of FRAME detections: shifted into frame
@@ -678,6 +693,30 @@ int         pvhip_input_preprocess_packed_f32(const void* src, float* dst, int n
 int         pvhip_input_preprocess_packed_roi_f32(const void* src, float* dst, const int* rois, int n, int m, int src_h, int src_w,
                                                   int dst_h, int dst_w, int max_roi_h, int max_roi_w, int kind, int reverse_channels,
                                                   const float* mean, const float* std_scale);
+/* Addition to ABI v18 (the version number is unchanged: nothing existing changed): the launches above with an aspect-preserving fit
+ * (preprocess_info.resize_fit 'LETTERBOX' / 'TOP_LEFT') in place of the stretch.  Each takes the arguments of the matching _roi_ entry --
+ * rois == NULL: whole images, image b is source image b, and m, max_roi_h, max_roi_w are ignored (taken as n, src_h, src_w) -- plus
+ * `fit` (1 LETTERBOX, 2 TOP_LEFT) and `pad_value`, one finite fp32 number in source units.  The geometry, integers only (int64): a
+ * source (or rectangle) of (hs, ws) onto (hd, wd) = (dst_h, dst_w) is fitted into
+ *   wide, ws hd >= hs wd:  iw = wd, ih = min(max((2 hs wd + ws) / (2 ws), 1), hd)   (the short side rounded half up)
+ *   else:                  ih = hd, iw = min(max((2 ws hd + hs) / (2 hs), 1), wd)
+ *   LETTERBOX: dx = (wd - iw) / 2, dy = (hd - ih) / 2 (floor);  TOP_LEFT: dx = dy = 0.
+ * Output pixel (y, x) inside [dy, dy + ih) x [dx, dx + iw) is exactly what the entry without the fit gives at (y - dy, x - dx) for the
+ * same source onto a destination of (ih, iw): the same taps, the same fp32 expression in the same order, the rule that a source or
+ * rectangle of exactly (ih, iw) is copied included.  Outside, the interpolated value is pad_value, and it goes through the same
+ * (v - mean[k]) / std_scale[k].  A geometry of whole images that fills the destination IS the launch without the fit.  An invalid or
+ * oversized rectangle is written as quiet NaN over the whole image, padding included; a tile that lies wholly in the padding reads
+ * nothing of `src`.  In numpy: tests/letterbox_ref.py, matched bit for bit.  The limits of the _roi_ entries, fit 1 or 2, pad_value
+ * finite; else PVHIP_EINVAL and nothing is launched. */
+int         pvhip_input_preprocess_fit_f32(const void* src, float* dst, const int* rois, int n, int m, int c, int src_h, int src_w,
+                                           int dst_h, int dst_w, int max_roi_h, int max_roi_w, int src_u8, int src_nhwc,
+                                           int reverse_channels, const float* mean, const float* std_scale, int fit, float pad_value);
+int         pvhip_input_preprocess_yuv_fit_f32(const void* src, float* dst, const int* rois, int n, int m, int src_h, int src_w,
+                                               int dst_h, int dst_w, int max_roi_h, int max_roi_w, int planar, int reverse_channels,
+                                               const float* mean, const float* std_scale, int fit, float pad_value);
+int         pvhip_input_preprocess_packed_fit_f32(const void* src, float* dst, const int* rois, int n, int m, int src_h, int src_w,
+                                                  int dst_h, int dst_w, int max_roi_h, int max_roi_w, int kind, int reverse_channels,
+                                                  const float* mean, const float* std_scale, int fit, float pad_value);
 
 #ifdef __cplusplus
 }

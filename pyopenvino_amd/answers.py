@@ -1,12 +1,15 @@
 """Answers behind the pass: the Results a start named with ``top_k=`` or ``detections=`` come back from wait() as a ``TopK`` or a
 ``Detections`` made on the device instead of as the tensor.  One ``Answers`` per Executable_Network (one per request), as ``HostInputs``
 is on the way in: the request checks the arguments, binds the asks to the staged inputs, launches behind the pass and reads after it.
+A plain screen over a detector whose input declares a fit (preprocess_info.resize_fit) learns its geometry in bound(), from the extent
+of the frames the pass was fed.
 
-An ask is one Result's question in its resolved form -- top_k.Ask, detections.Ask or tiled_detections.Ask, each with `bound`, `key`,
+An ask is one Result's question in its resolved form -- top_k.Ask, detections.Ask / FittedAsk or tiled_detections.Ask, each with `bound`, `key`,
 `launch` and `on_host` --; which kind it is matters only where checked() makes it."""
 import numpy as np
 
 from . import detections as detections_rule, device, tiled_detections as tiled_rule, top_k as top_k_rule
+from .input_format import DetectedRois, RoiInput
 
 
 class Answers:
@@ -32,11 +35,33 @@ class Answers:
         if both:
             raise ValueError('detections: Result {!r} is asked for with top_k as well'.format(both[0]))
         tiled = {name: s for name, s in screens.items() if isinstance(s, tiled_rule.TiledScreen)}
+        formats = self.runner.host_inputs.formats
+        for name, s in tiled.items():           # (the geometry would be one per tile)
+            if s.input in formats and formats[s.input].fitted:
+                raise ValueError('detections: Result {!r}: a TiledScreen over input {!r}, which declares resize_fit {}'.format(
+                    name, s.input, formats[s.input].fit))
         tiled_rule.checked_feed(inputs, tiled)
+        fitted = self._fitted_input() if len(screens) > len(tiled) else None
+        if fitted is not None and isinstance(inputs, dict) and isinstance(inputs.get(fitted), (RoiInput, DetectedRois)):
+            raise ValueError('detections: input {!r} declares resize_fit {} and is fed a {}: every row has a geometry of its own'.format(
+                fitted, formats[fitted].fit, type(inputs[fitted]).__name__))
         n = int(ienet.batch_size)
         asks = {name: top_k_rule.Ask(k) for name, k in wanted.items()}
-        asks.update((name, tiled_rule.Ask(s, n, None, None) if name in tiled else detections_rule.Ask(s, n)) for name, s in screens.items())
+        for name, s in screens.items():
+            if name in tiled:
+                asks[name] = tiled_rule.Ask(s, n, None, None)
+            elif fitted is None:
+                asks[name] = detections_rule.Ask(s, n)
+            else:
+                given = detections[name] if isinstance(detections, dict) else detections
+                explicit = isinstance(given, detections_rule.DetectionScreen) and given.frame_size is not None
+                asks[name] = detections_rule.FittedAsk(s, n, fitted, formats[fitted], explicit, None)
         return asks
+
+    def _fitted_input(self):
+        """The name of the network's single 4-D Parameter when its format declares a fit, else None."""
+        names = [name for name, fmt in self.runner.host_inputs.formats.items() if len(fmt.dims) == 4]
+        return names[0] if len(names) == 1 and self.runner.host_inputs.formats[names[0]].fitted else None
 
     def bound(self, asks: dict, inputs: dict) -> dict:
         """`asks` for the pass whose `inputs`, as they were fed, host_inputs.stage() has just staged: a tiled ask learns its frame count

@@ -251,11 +251,13 @@ struct RoiArgs {
     const int*   labels;   // [num_labels], or NULL: any label
     int   n, N, P, H, W, num_labels, min_h, min_w;
     float conf;
+    DetectionFit fit;      // FIT kernel: the geometry of the detector's fitted input
 };
 
 constexpr int kRoiImages = 4096;  // list ends held in LDS at once
 constexpr int kRoiLabels = kScreenLabels;
 
+template <bool FIT>
 __global__ __launch_bounds__(kDetBlock) void detections_to_rois_kernel(RoiArgs a) {
     __shared__ int   ends[kRoiImages];
     __shared__ int   wave_total[2][kDetBlock / 64];
@@ -285,7 +287,8 @@ __global__ __launch_bounds__(kDetBlock) void detections_to_rois_kernel(RoiArgs a
             if (r < r1) {
                 b = r / P;
                 keep = r - b * P < ends[b - b0] &&
-                       detection_screen(a.rec + (size_t)r * 7, a.conf, labels, a.labels != nullptr, a.num_labels, fh, fw, a.min_h, a.min_w, q);
+                       detection_screen<FIT>(a.rec + (size_t)r * 7, a.conf, labels, a.labels != nullptr, a.num_labels, fh, fw, a.min_h, a.min_w, q,
+                                             a.fit);
             }
             const unsigned long long votes = __ballot(keep);
             const int rank = __builtin_amdgcn_mbcnt_hi((unsigned)(votes >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)votes, 0u));
@@ -317,13 +320,12 @@ __global__ __launch_bounds__(kDetBlock) void detections_to_rois_kernel(RoiArgs a
     if (tid == 0) { a.counts[0] = count; a.counts[1] = base; }
 }
 
-}  // namespace
-
-extern "C" {
-
-int pvhip_detections_to_rois(const float* records, int* rois, int* record_of, int* counts, int n, int images, int records_per_image,
-                             int frame_h, int frame_w, float min_confidence, const int* labels, int num_labels, int min_h, int min_w) {
+// The one launcher of detections_to_rois_kernel; fit: NULL, or the geometry of the _fit entry.
+int to_rois_launch(const float* records, int* rois, int* record_of, int* counts, int n, int images, int records_per_image,
+                   int frame_h, int frame_w, float min_confidence, const int* labels, int num_labels, int min_h, int min_w,
+                   const DetectionFit* fit) {
     PVHIP_REQUIRE_INIT();
+    PVHIP_CHECK_ARG(fit == nullptr || detection_fit_ok(*fit));
     PVHIP_CHECK_ARG(records != nullptr && rois != nullptr && record_of != nullptr && counts != nullptr);
     PVHIP_CHECK_ARG(n >= 1 && images >= 1 && records_per_image >= 1 && min_h >= 1 && min_w >= 1);
     PVHIP_CHECK_ARG((long long)images * records_per_image < ((1LL << 31) / 7));
@@ -333,9 +335,29 @@ int pvhip_detections_to_rois(const float* records, int* rois, int* record_of, in
     a.rec = records; a.rois = rois; a.rec_of = record_of; a.counts = counts; a.labels = labels;
     a.n = n; a.N = images; a.P = records_per_image; a.H = frame_h; a.W = frame_w;
     a.num_labels = num_labels; a.min_h = min_h; a.min_w = min_w; a.conf = min_confidence;
-    hipLaunchKernelGGL(detections_to_rois_kernel, dim3(1), dim3(kDetBlock), 0, state().stream, a);
+    a.fit = fit != nullptr ? *fit : DetectionFit{};
+    if (fit != nullptr) hipLaunchKernelGGL(detections_to_rois_kernel<true>, dim3(1), dim3(kDetBlock), 0, state().stream, a);
+    else                hipLaunchKernelGGL(detections_to_rois_kernel<false>, dim3(1), dim3(kDetBlock), 0, state().stream, a);
     PVHIP_LAUNCH_CHECK();
     return PVHIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pvhip_detections_to_rois(const float* records, int* rois, int* record_of, int* counts, int n, int images, int records_per_image,
+                             int frame_h, int frame_w, float min_confidence, const int* labels, int num_labels, int min_h, int min_w) {
+    return to_rois_launch(records, rois, record_of, counts, n, images, records_per_image, frame_h, frame_w, min_confidence, labels,
+                          num_labels, min_h, min_w, nullptr);
+}
+
+int pvhip_detections_to_rois_fit(const float* records, int* rois, int* record_of, int* counts, int n, int images, int records_per_image,
+                                 int frame_h, int frame_w, float min_confidence, const int* labels, int num_labels, int min_h, int min_w,
+                                 int net_h, int net_w, int dx, int dy, int iw, int ih) {
+    const DetectionFit g{net_h, net_w, dx, dy, iw, ih};
+    return to_rois_launch(records, rois, record_of, counts, n, images, records_per_image, frame_h, frame_w, min_confidence, labels,
+                          num_labels, min_h, min_w, &g);
 }
 
 int pvhip_detection_output_f32(const float* loc, const float* conf, const float* priors, float* out, int n,

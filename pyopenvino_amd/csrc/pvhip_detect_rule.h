@@ -15,14 +15,31 @@ struct DetectionRect {
     int x0, y0, w, h;
 };
 
+// The geometry of a fitted detector input (pvhip_input_preprocess_fit_f32): the detector saw the frame in the rectangle
+// [dy, dy + ih) x [dx, dx + iw) of its (Hn, Wn) input, so a normalised corner v of its records is u = (v Wn - dx) / iw of the frame (Hn, dy,
+// ih for a y): three fp32 roundings, never contracted.
+struct DetectionFit {
+    int Hn, Wn, dx, dy, iw, ih;
+};
+
+__device__ __forceinline__ float unfit(float v, int N, int d, int i) { return (v * (float)N - (float)d) / (float)i; }
+
 // True when the live record q = [rank, label, score, xmin, ymin, xmax, ymax] is selected: score >= conf (false for NaN), four finite
 // corners, (when `filtered`) label == (float)labels[j] for some j < num_labels, and a rectangle over (fh, fw) of at least (min_h, min_w),
 // which is left in `r`.  `labels` may hold ints (global memory) or the same values as floats (LDS); fp32 throughout, never contracted.
-template <typename L>
+// FIT: the rectangle is that of the corners mapped back through `g` (the finite check is on the record's own corners); a box in the padding
+// clamps to the frame's edge, one wholly in it has extent 0 and is dropped.
+template <bool FIT = false, typename L>
 __device__ __forceinline__ bool detection_screen(const float* __restrict__ q, float conf, const L* labels, bool filtered, int num_labels,
-                                                 float fh, float fw, int min_h, int min_w, DetectionRect& r) {
-    const float label = q[1], score = q[2], xa = q[3], ya = q[4], xb = q[5], yb = q[6];
+                                                 float fh, float fw, int min_h, int min_w, DetectionRect& r,
+                                                 const DetectionFit& g = DetectionFit{}) {
+    const float label = q[1], score = q[2];
+    float xa = q[3], ya = q[4], xb = q[5], yb = q[6];
     bool keep = score >= conf && isfinite(xa) && isfinite(ya) && isfinite(xb) && isfinite(yb);
+    if (FIT) {
+        xa = unfit(xa, g.Wn, g.dx, g.iw); xb = unfit(xb, g.Wn, g.dx, g.iw);
+        ya = unfit(ya, g.Hn, g.dy, g.ih); yb = unfit(yb, g.Hn, g.dy, g.ih);
+    }
     if (keep && filtered) {
         bool listed = false;
         for (int j = 0; j < num_labels; ++j) listed = listed || label == (float)labels[j];
@@ -46,6 +63,12 @@ struct ScreenWalk {
     float conf;
 };
 
+// A geometry the _fit entries accept: extents exact as fp32, the rectangle inside the input.
+inline bool detection_fit_ok(const DetectionFit& g) {
+    return g.Hn >= 1 && g.Hn <= (1 << 24) && g.Wn >= 1 && g.Wn <= (1 << 24) && g.iw >= 1 && g.ih >= 1 && g.dx >= 0 && g.dy >= 0 &&
+           g.iw <= g.Wn - g.dx && g.ih <= g.Hn - g.dy;
+}
+
 __device__ __forceinline__ int lanes_below(unsigned long long votes) {
     return __builtin_amdgcn_mbcnt_hi((unsigned)(votes >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)votes, 0u));
 }
@@ -53,8 +76,8 @@ __device__ __forceinline__ int lanes_below(unsigned long long votes) {
 // Walks image b over a frame of (H, W), 64 records at a time, and hands every survivor with rank < limit to `emit(rank, record, rectangle,
 // q)`.  Returns the number of survivors seen (all of them when limit >= P).  The whole wave calls it; everything that steers the loop is
 // wave-uniform.
-template <typename Emit>
-__device__ __forceinline__ int walk_image(const ScreenWalk& a, int b, int H, int W, int limit, Emit emit) {
+template <bool FIT = false, typename Emit>
+__device__ __forceinline__ int walk_image(const ScreenWalk& a, int b, int H, int W, int limit, Emit emit, const DetectionFit& g = DetectionFit{}) {
     const int   lane = threadIdx.x & (kWave - 1);
     const float fh = (float)H, fw = (float)W;
     int seen = 0;
@@ -67,7 +90,7 @@ __device__ __forceinline__ int walk_image(const ScreenWalk& a, int b, int H, int
         const int  first = ends ? __builtin_ctzll(ends) : kWave;               // the list ends at this lane's record
         DetectionRect rect{0, 0, 0, 0};
         const bool keep = valid && lane < first &&
-                          detection_screen(q, a.conf, a.labels, a.labels != nullptr, a.num_labels, fh, fw, a.min_h, a.min_w, rect);
+                          detection_screen<FIT>(q, a.conf, a.labels, a.labels != nullptr, a.num_labels, fh, fw, a.min_h, a.min_w, rect, g);
         const unsigned long long votes = __ballot(keep);
         const int rank = seen + lanes_below(votes);
         if (keep && rank < limit) emit(rank, r, rect, q);

@@ -28,6 +28,16 @@
 // reads its image's five ints, takes S = (h, w) for its taps and adds (id, y, x) to the addresses it stages from; a rectangle of exactly
 // the destination's extent is copied (fp32 sources: no 0 * inf; bytes give the same bits either way).  The table is device data, so an image whose rectangle does not lie inside a frame, or
 // exceeds the maxima the launch was sized for, is written as quiet NaN and nothing is read for it.  tests/roi_ref.py is the rule in numpy.
+//
+// An aspect-preserving fit (the _fit_ entries; preprocess_info.resize_fit 'LETTERBOX' / 'TOP_LEFT'): the source -- a whole image, or the
+// rectangle of a table -- is scaled by ONE factor into the rectangle [dy, dy + ih) x [dx, dx + iw) of the destination (fit_rect: integers
+// only, the short side rounded half up) by the rule above onto (ih, iw), and the rest of the destination is the pad value, which goes through
+// the same mean / scale.  No new interpolation: every kernel takes it as one more template parameter beside ROI.  tile_of computes the
+// rectangle per workgroup (a table is device data) and fills a tile that lies wholly in the padding without touching `src`; fill_tables
+// runs the taps over (ih, iw) at d - dx, d - dy, clamped into the rectangle, so a tile stages what its intersection with the rectangle
+// reads; the inner loops replace the value of a pixel outside it by the pad (quads may straddle the edge: dx is any integer; the stores do
+// not change).  The tiles are sized by a bound on the taps' step over every rectangle the launch may meet (Reach), and a workgroup whose
+// tile would still not fit its slots writes NaN instead of staging.  tests/letterbox_ref.py is the rule in numpy.
 #include "pvhip_common.h"
 
 #pragma clang fp contract(off)
@@ -78,36 +88,84 @@ struct TileArgs {
     unsigned stage_bytes;     // LDS bytes of the staging area (the coordinate tables follow it)
     const int* rois;          // ROI kernels: n x (id, x, y, w, h); hs, ws are then the extent of each of the m frames
     int m, mh, mw;            // ... the frame count and the largest h and w the launch was sized for
+    int fit;                  // FIT kernels: 1 LETTERBOX (the fitted rectangle is centred), 2 TOP_LEFT
+    float pad;                // ... the value outside the fitted rectangle, in source units (it goes through mean / scale)
 };
+
+// The fitted rectangle of a source (or ROI rectangle) of (hs, ws) in a destination of (hd, wd): one scale factor for both axes, the short
+// side rounded half up and kept in [1, D]; integers only (include/pvhip.h states the rule, tests/letterbox_ref.py is the same in numpy).
+struct FitRect {
+    int dx, dy, iw, ih;
+};
+
+__host__ __device__ inline FitRect fit_rect(int hs, int ws, int hd, int wd, int fit) {
+    long long iw = wd, ih = hd;
+    if ((long long)ws * hd >= (long long)hs * wd) {
+        ih = (2LL * hs * wd + ws) / (2LL * ws);
+        ih = ih < 1 ? 1 : (ih > hd ? hd : ih);
+    } else {
+        iw = (2LL * ws * hd + hs) / (2LL * hs);
+        iw = iw < 1 ? 1 : (iw > wd ? wd : iw);
+    }
+    FitRect r;
+    r.iw = (int)iw; r.ih = (int)ih;
+    r.dx = fit == 1 ? (wd - r.iw) / 2 : 0;
+    r.dy = fit == 1 ? (hd - r.ih) / 2 : 0;
+    return r;
+}
 
 // The tile of one workgroup: columns tx0.. (twv of them) of rows ty0.. (thv of them) of image n, whose taps see a source of hs x ws
 // pixels: the whole of source image img = n, or (ROI kernels) the rectangle at column ox, row oy of frame img.
+// FIT kernels: the taps run over the fitted rectangle [dy, dy + ih) x [dx, dx + iw) of the destination, everything outside it is `pad`;
+// else that rectangle is the destination.
 struct Tile {
     int n, tx0, ty0, twv, thv;
     int hs, ws, img, ox, oy;
+    int dx, dy, iw, ih;
 };
 
+// Every pixel of the tile, in all c planes, becomes v (FIT: (v - mean) / std_scale, as finish_quad computes it).
+template <bool EPILOGUE>
+__device__ __forceinline__ void fill_tile(const TileArgs& a, int c, const Tile& t, float v) {
+    const size_t plane_out = (size_t)a.hd * a.wd;
+    float* out_n = a.dst + (size_t)t.n * c * plane_out;
+    for (int oc = 0; oc < c; ++oc) {
+        float w = v;
+        if (EPILOGUE && a.mean != nullptr) w = w - a.mean[oc];
+        if (EPILOGUE && a.std_scale != nullptr) w = w / a.std_scale[oc];
+        for (int i = threadIdx.x; i < t.thv * t.twv; i += kBlock) {
+            const int r = i / t.twv;
+            out_n[oc * plane_out + (size_t)(t.ty0 + r) * a.wd + t.tx0 + (i - r * t.twv)] = w;
+        }
+    }
+}
+
 // grid (ceil(wd / tw), ceil(hd / th), n).  ROI: the image's rectangle (id, x, y, w, h) is read once per workgroup; false: it does not lie
-// inside frame id or exceeds the launch's maxima, the tile is filled with quiet NaN in all c planes and the workgroup is done.
-template <bool ROI>
+// inside frame id or exceeds the launch's maxima, the tile is filled with quiet NaN in all c planes -- padding included -- and the
+// workgroup is done.  FIT: the fitted rectangle follows from the extent the taps see (per workgroup: a table is device data); false too
+// when the tile lies wholly in the padding: it is filled with the pad value and nothing of `src` is touched.
+template <bool ROI, bool FIT>
 __device__ __forceinline__ bool tile_of(const TileArgs& a, int c, Tile& t) {
     t.n = blockIdx.z; t.tx0 = blockIdx.x * a.tw; t.ty0 = blockIdx.y * a.th;
     t.twv = min(a.tw, a.wd - t.tx0); t.thv = min(a.th, a.hd - t.ty0);
     t.hs = a.hs; t.ws = a.ws; t.img = t.n; t.ox = 0; t.oy = 0;
+    t.dx = 0; t.dy = 0; t.iw = a.wd; t.ih = a.hd;
     if (ROI) {
         const int* q = a.rois + 5 * (size_t)t.n;
         t.img = q[0]; t.ox = q[1]; t.oy = q[2]; t.ws = q[3]; t.hs = q[4];
-        if (t.img >= 0 && t.img < a.m && t.ox >= 0 && t.oy >= 0 && t.ws >= 1 && t.hs >= 1 && t.ws <= a.mw && t.hs <= a.mh
-            && (long long)t.ox + t.ws <= a.ws && (long long)t.oy + t.hs <= a.hs)
-            return true;
-        const size_t plane_out = (size_t)a.hd * a.wd;
-        float* out_n = a.dst + (size_t)t.n * c * plane_out;
-        for (int oc = 0; oc < c; ++oc)
-            for (int i = threadIdx.x; i < t.thv * t.twv; i += kBlock) {
-                const int r = i / t.twv;
-                out_n[oc * plane_out + (size_t)(t.ty0 + r) * a.wd + t.tx0 + (i - r * t.twv)] = __builtin_nanf("");
-            }
-        return false;
+        if (!(t.img >= 0 && t.img < a.m && t.ox >= 0 && t.oy >= 0 && t.ws >= 1 && t.hs >= 1 && t.ws <= a.mw && t.hs <= a.mh
+              && (long long)t.ox + t.ws <= a.ws && (long long)t.oy + t.hs <= a.hs)) {
+            fill_tile<false>(a, c, t, __builtin_nanf(""));
+            return false;
+        }
+    }
+    if (FIT) {
+        const FitRect f = fit_rect(t.hs, t.ws, a.hd, a.wd, a.fit);
+        t.dx = f.dx; t.dy = f.dy; t.iw = f.iw; t.ih = f.ih;
+        if (t.tx0 >= t.dx + t.iw || t.tx0 + t.twv <= t.dx || t.ty0 >= t.dy + t.ih || t.ty0 + t.thv <= t.dy) {
+            fill_tile<true>(a, c, t, a.pad);
+            return false;
+        }
     }
     return true;
 }
@@ -124,9 +182,14 @@ struct Tables {
     static constexpr size_t bytes(int tw, int th) { return 3 * sizeof(int) * ((size_t)tw + (size_t)th); }
 };
 
-// taps(d, S, D): the Tap of destination index d.  Read the tables after a __syncthreads().
-template <class Taps>
+// taps(d, S, D): the Tap of destination index d.  Read the tables after a __syncthreads().  FIT: index d of the destination is index
+// d - dx (d - dy) of the fitted rectangle, clamped into it -- a pixel of the padding gets the taps of the nearest inner column (row), which
+// the tile stages anyway, and its value is replaced by the pad --, so the source the tile reads is that of its intersection with the
+// fitted rectangle (not empty: tile_of).
+template <bool FIT, class Taps>
 __device__ __forceinline__ Tables fill_tables(unsigned char* lds, const TileArgs& a, const Tile& t, Taps taps) {
+    auto col = [&](int d) { return FIT ? taps(min(max(d - t.dx, 0), t.iw - 1), t.ws, t.iw) : taps(d, t.ws, a.wd); };
+    auto row = [&](int d) { return FIT ? taps(min(max(d - t.dy, 0), t.ih - 1), t.hs, t.ih) : taps(d, t.hs, a.hd); };
     Tables b;
     b.cx0 = reinterpret_cast<int*>(lds + a.stage_bytes);
     b.cx1 = b.cx0 + a.tw;
@@ -135,15 +198,15 @@ __device__ __forceinline__ Tables fill_tables(unsigned char* lds, const TileArgs
     b.ry1 = b.ry0 + a.th;
     b.rfy = reinterpret_cast<float*>(b.ry1 + a.th);
     for (int j = threadIdx.x; j < t.twv; j += kBlock) {
-        const Tap p = taps(t.tx0 + j, t.ws, a.wd);
+        const Tap p = col(t.tx0 + j);
         b.cx0[j] = p.i0; b.cx1[j] = p.i1; b.cfx[j] = p.f;
     }
     for (int j = threadIdx.x; j < t.thv; j += kBlock) {
-        const Tap p = taps(t.ty0 + j, t.hs, a.hd);
+        const Tap p = row(t.ty0 + j);
         b.ry0[j] = p.i0; b.ry1[j] = p.i1; b.rfy[j] = p.f;
     }
-    b.xs0 = taps(t.tx0, t.ws, a.wd).i0; b.xs1 = taps(t.tx0 + t.twv - 1, t.ws, a.wd).i1;
-    b.ys0 = taps(t.ty0, t.hs, a.hd).i0; b.ys1 = taps(t.ty0 + t.thv - 1, t.hs, a.hd).i1;
+    b.xs0 = col(t.tx0).i0; b.xs1 = col(t.tx0 + t.twv - 1).i1;
+    b.ys0 = row(t.ty0).i0; b.ys1 = row(t.ty0 + t.thv - 1).i1;
     return b;
 }
 
@@ -200,6 +263,13 @@ __device__ __forceinline__ void finish_quad(const TileArgs& a, int oc, float (&v
     }
 }
 
+// FIT: row r / column j of the tile lies in the fitted rectangle.
+__device__ __forceinline__ bool row_inside(const Tile& t, int r) { return (unsigned)(t.ty0 + r - t.dy) < (unsigned)t.ih; }
+__device__ __forceinline__ bool col_inside(const Tile& t, int j) { return (unsigned)(t.tx0 + j - t.dx) < (unsigned)t.iw; }
+
+// A span of `span` bytes fits a slot of `slot` bytes as the launchers size them.
+__device__ __forceinline__ bool span_fits(int span, unsigned slot) { return ((unsigned)span + 30) / 16 * 16 <= slot; }
+
 // ------------------------------------------------------------------------------------------------------------ U8 / FP32 images
 struct PrepArgs : TileArgs {
     int c, nhwc;
@@ -207,19 +277,24 @@ struct PrepArgs : TileArgs {
 };
 
 // dynamic LDS stage_bytes + Tables::bytes(tw, th).  ROI (with RESIZE): image n is a rectangle of a frame (see the file comment).
-template <bool U8, bool RESIZE, bool VS, bool ROI>
+// FIT (with RESIZE): the source is fitted into the destination and padded (see the file comment).
+template <bool U8, bool RESIZE, bool VS, bool ROI, bool FIT = false>
 __global__ __launch_bounds__(kBlock) void preprocess_kernel(PrepArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     constexpr int ES = U8 ? 1 : 4;
     Tile t;
-    if (!tile_of<ROI>(a, a.c, t)) return;
-    // (workgroup-uniform) the rectangle has the destination's extent: fp32 sources are copied, identity weights would turn an inf
-    // neighbour into NaN (bytes interpolate to the same bits: weight 0 on a finite value)
-    const bool copy = ROI && !U8 && t.hs == a.hd && t.ws == a.wd;
-    const Tables tb = fill_tables(lds, a, t, [&](int d, int S, int D) { return copy ? tap<false>(d, S, D) : tap<RESIZE>(d, S, D); });
+    if (!tile_of<ROI, FIT>(a, a.c, t)) return;
+    // (workgroup-uniform) the rectangle has the destination's extent (FIT: the source has the fitted rectangle's): fp32 sources are
+    // copied, identity weights would turn an inf neighbour into NaN (bytes interpolate to the same bits: weight 0 on a finite value)
+    const bool copy = (ROI || FIT) && !U8 && t.hs == t.ih && t.ws == t.iw;
+    const Tables tb = fill_tables<FIT>(lds, a, t, [&](int d, int S, int D) { return copy ? tap<false>(d, S, D) : tap<RESIZE>(d, S, D); });
     const int rows = tb.ys1 - tb.ys0 + 1;
     const int cs = a.nhwc ? a.c : 1, planes = a.nhwc ? 1 : a.c;
     const int span = (tb.xs1 - tb.xs0 + 1) * cs * ES;        // bytes of one staged span
+    if (FIT && !(span_fits(span, a.slot) && (size_t)planes * rows * a.slot <= a.stage_bytes)) {   // (never, by fit_steps' bound)
+        fill_tile<false>(a, a.c, t, __builtin_nanf(""));
+        return;
+    }
     // span s = plane * rows + row: its first byte in the source
     auto span_src = [&](int s) -> const unsigned char* {
         const int p = s / rows, r = s - p * rows;
@@ -242,6 +317,7 @@ __global__ __launch_bounds__(kBlock) void preprocess_kernel(PrepArgs a) {
         const int r = i / nq, j0 = 4 * (i - r * nq);
         const int y0 = tb.ry0[r] - tb.ys0, y1 = tb.ry1[r] - tb.ys0;
         const float fy = tb.rfy[r], gy = 1.0f - fy;
+        const bool rin = !FIT || row_inside(t, r);
         int xa[4], xb[4];
         float fx[4], gx[4];
 #pragma unroll
@@ -269,16 +345,17 @@ __global__ __launch_bounds__(kBlock) void preprocess_kernel(PrepArgs a) {
                 } else {
                     v[u] = pixel<U8>(l0, xa[u] + ch);
                 }
+                if (FIT && !(rin && col_inside(t, j0 + u))) v[u] = a.pad;
             }
             finish_quad<VS>(a, oc, v, o, j0, t.twv);
         }
     }
 }
 
-template <bool U8, bool RESIZE, bool ROI>
+template <bool U8, bool RESIZE, bool ROI, bool FIT = false>
 void launch(const PrepArgs& a, dim3 grid, size_t lds, bool vs, hipStream_t st) {
-    if (vs) hipLaunchKernelGGL((preprocess_kernel<U8, RESIZE, true, ROI>), grid, dim3(kBlock), lds, st, a);
-    else    hipLaunchKernelGGL((preprocess_kernel<U8, RESIZE, false, ROI>), grid, dim3(kBlock), lds, st, a);
+    if (vs) hipLaunchKernelGGL((preprocess_kernel<U8, RESIZE, true, ROI, FIT>), grid, dim3(kBlock), lds, st, a);
+    else    hipLaunchKernelGGL((preprocess_kernel<U8, RESIZE, false, ROI, FIT>), grid, dim3(kBlock), lds, st, a);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- YUV 4:2:0 sources
@@ -314,12 +391,12 @@ __device__ __forceinline__ void yuv_to_bgr(int y, int u, int v, float (&o)[3]) {
 // dynamic LDS stage_bytes + Tables::bytes(tw, th).  ROI (with RESIZE): the chroma of a pixel is that of its ABSOLUTE 2 x 2 block of the
 // frame, so a rectangle may start on odd coordinates and have odd sizes.  (A rectangle of the destination's extent needs no copy path
 // here: the converted pixels are bytes, and weight 0 on a finite value interpolates to the same bits.)
-template <bool RESIZE, bool VS, bool ROI>
+template <bool RESIZE, bool VS, bool ROI, bool FIT = false>
 __global__ __launch_bounds__(kBlock) void preprocess_yuv_kernel(YuvArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     Tile t;
-    if (!tile_of<ROI>(a, 3, t)) return;
-    const Tables tb = fill_tables(lds, a, t, [](int d, int S, int D) { return tap<RESIZE>(d, S, D); });
+    if (!tile_of<ROI, FIT>(a, 3, t)) return;
+    const Tables tb = fill_tables<FIT>(lds, a, t, [](int d, int S, int D) { return tap<RESIZE>(d, S, D); });
     const int ox = t.ox, oy = t.oy, xs0 = tb.xs0, ys0 = tb.ys0;
     const int rows = tb.ys1 - ys0 + 1, yspan = tb.xs1 - xs0 + 1;
     const int ps0 = (ox + xs0) >> 1, cr0 = (oy + ys0) >> 1, crows = ((oy + tb.ys1) >> 1) - cr0 + 1;   // first chroma pair and row, chroma rows
@@ -335,6 +412,11 @@ __global__ __launch_bounds__(kBlock) void preprocess_yuv_kernel(YuvArgs a) {
         const int p = s >= crows ? 1 : 0;
         return chroma + ((size_t)p * (a.hs >> 1) + cr0 + s - p * crows) * hw + ps0;
     };
+    if (FIT && !(span_fits(yspan, a.yslot) && span_fits(cspan, a.cslot) &&
+                 (size_t)rows * a.yslot + (size_t)crows * (a.planar ? 2 : 1) * a.cslot <= a.stage_bytes)) {   // (never, by fit_steps' bound)
+        fill_tile<false>(a, 3, t, __builtin_nanf(""));
+        return;
+    }
     unsigned char* lds_c = lds + (unsigned)rows * a.yslot;
     const unsigned ybps = (unsigned)yspan / 16 + 2, cbps = (unsigned)cspan / 16 + 2;
     const unsigned yblk = (unsigned)rows * ybps, cblk = (unsigned)(crows * (a.planar ? 2 : 1)) * cbps;
@@ -355,6 +437,7 @@ __global__ __launch_bounds__(kBlock) void preprocess_yuv_kernel(YuvArgs a) {
     for (int i = threadIdx.x; i < t.thv * nq; i += kBlock) {
         const int r = i / nq, j0 = 4 * (i - r * nq);
         const float fy = tb.rfy[r], gy = 1.0f - fy;
+        const bool rin = !FIT || row_inside(t, r);
         // the two tapped rows: their Y spans, and the U and V of the chroma rows under them
         const unsigned char *ly[2], *lu[2], *lv[2];
 #pragma unroll
@@ -389,6 +472,10 @@ __global__ __launch_bounds__(kBlock) void preprocess_yuv_kernel(YuvArgs a) {
 #pragma unroll
                 for (int c = 0; c < 3; ++c) v[c][u] = p00[c];
             }
+            if (FIT && !(rin && col_inside(t, j0 + u))) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) v[c][u] = a.pad;
+            }
         }
         float* o = out_n + (size_t)(t.ty0 + r) * a.wd + t.tx0 + j0;
 #pragma unroll
@@ -401,10 +488,10 @@ __global__ __launch_bounds__(kBlock) void preprocess_yuv_kernel(YuvArgs a) {
     }
 }
 
-template <bool RESIZE, bool ROI>
+template <bool RESIZE, bool ROI, bool FIT = false>
 void launch_yuv(const YuvArgs& a, dim3 grid, size_t lds, bool vs, hipStream_t st) {
-    if (vs) hipLaunchKernelGGL((preprocess_yuv_kernel<RESIZE, true, ROI>), grid, dim3(kBlock), lds, st, a);
-    else    hipLaunchKernelGGL((preprocess_yuv_kernel<RESIZE, false, ROI>), grid, dim3(kBlock), lds, st, a);
+    if (vs) hipLaunchKernelGGL((preprocess_yuv_kernel<RESIZE, true, ROI, FIT>), grid, dim3(kBlock), lds, st, a);
+    else    hipLaunchKernelGGL((preprocess_yuv_kernel<RESIZE, false, ROI, FIT>), grid, dim3(kBlock), lds, st, a);
 }
 
 // ------------------------------------------------------------------------------------------------------ packed 4-byte-unit sources
@@ -443,18 +530,22 @@ __device__ __forceinline__ void packed_to_bgr(const unsigned char* l, int ox, in
 
 // dynamic LDS stage_bytes + Tables::bytes(tw, th).  ROI (with RESIZE): a 4:2:2 pixel keeps the chroma of its ABSOLUTE column pair, so a
 // rectangle may start on an odd x and have an odd w.  (No copy path for a rectangle of the destination's extent: the pixels are bytes.)
-template <int KIND, bool RESIZE, bool VS, bool ROI>
+template <int KIND, bool RESIZE, bool VS, bool ROI, bool FIT = false>
 __global__ __launch_bounds__(kBlock) void preprocess_packed_kernel(PackedArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     constexpr bool YUV = KIND < 2;
     Tile t;
-    if (!tile_of<ROI>(a, 3, t)) return;
-    const Tables tb = fill_tables(lds, a, t, [](int d, int S, int D) { return tap<RESIZE>(d, S, D); });
+    if (!tile_of<ROI, FIT>(a, 3, t)) return;
+    const Tables tb = fill_tables<FIT>(lds, a, t, [](int d, int S, int D) { return tap<RESIZE>(d, S, D); });
     const int ox = t.ox, oy = t.oy, ys0 = tb.ys0;
     const int rows = tb.ys1 - ys0 + 1;
     const int u0 = YUV ? (ox + tb.xs0) >> 1 : ox + tb.xs0;                         // the first and the last unit of every staged row
     const int u1 = YUV ? (ox + tb.xs1) >> 1 : ox + tb.xs1;
     const int span = (u1 - u0 + 1) * 4;
+    if (FIT && !(span_fits(span, a.slot) && (size_t)rows * a.slot <= a.stage_bytes)) {   // (never, by fit_steps' bound)
+        fill_tile<false>(a, 3, t, __builtin_nanf(""));
+        return;
+    }
     const size_t row_bytes = (size_t)a.ws * (YUV ? 2 : 4);
     const unsigned char* frame = a.src + (size_t)t.img * ((size_t)a.hs * row_bytes);
     auto row_src = [&](int r) -> const unsigned char* { return frame + (size_t)(oy + ys0 + r) * row_bytes + (size_t)u0 * 4; };
@@ -472,6 +563,7 @@ __global__ __launch_bounds__(kBlock) void preprocess_packed_kernel(PackedArgs a)
     for (int i = threadIdx.x; i < t.thv * nq; i += kBlock) {
         const int r = i / nq, j0 = 4 * (i - r * nq);
         const float fy = tb.rfy[r], gy = 1.0f - fy;
+        const bool rin = !FIT || row_inside(t, r);
         const int r0 = tb.ry0[r] - ys0, r1 = tb.ry1[r] - ys0;                      // the two tapped rows
         const unsigned char* l0 = span_base(lds + (unsigned)r0 * a.slot, row_src(r0));
         const unsigned char* l1 = span_base(lds + (unsigned)r1 * a.slot, row_src(r1));
@@ -498,6 +590,10 @@ __global__ __launch_bounds__(kBlock) void preprocess_packed_kernel(PackedArgs a)
 #pragma unroll
                 for (int c = 0; c < 3; ++c) v[c][u] = p00[c];
             }
+            if (FIT && !(rin && col_inside(t, j0 + u))) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) v[c][u] = a.pad;
+            }
         }
         float* o = out_n + (size_t)(t.ty0 + r) * a.wd + t.tx0 + j0;
 #pragma unroll
@@ -512,14 +608,15 @@ __global__ __launch_bounds__(kBlock) void preprocess_packed_kernel(PackedArgs a)
 
 template <int KIND>
 void launch_packed(const PackedArgs& a, dim3 grid, size_t lds, bool vs, bool roi, bool resize, hipStream_t st) {
-#define PVHIP_PACKED(RESIZE, ROI)                                                                                              \
+#define PVHIP_PACKED(RESIZE, ROI, FIT)                                                                                         \
     do {                                                                                                                           \
-        if (vs) hipLaunchKernelGGL((preprocess_packed_kernel<KIND, RESIZE, true, ROI>), grid, dim3(kBlock), lds, st, a);           \
-        else    hipLaunchKernelGGL((preprocess_packed_kernel<KIND, RESIZE, false, ROI>), grid, dim3(kBlock), lds, st, a);          \
+        if (vs) hipLaunchKernelGGL((preprocess_packed_kernel<KIND, RESIZE, true, ROI, FIT>), grid, dim3(kBlock), lds, st, a);      \
+        else    hipLaunchKernelGGL((preprocess_packed_kernel<KIND, RESIZE, false, ROI, FIT>), grid, dim3(kBlock), lds, st, a);     \
     } while (0)
-    if (roi)         PVHIP_PACKED(true, true);
-    else if (resize) PVHIP_PACKED(true, false);
-    else             PVHIP_PACKED(false, false);
+    if (a.fit)       { if (roi) PVHIP_PACKED(true, true, true); else PVHIP_PACKED(true, false, true); }
+    else if (roi)    PVHIP_PACKED(true, true, false);
+    else if (resize) PVHIP_PACKED(true, false, false);
+    else             PVHIP_PACKED(false, false, false);
 #undef PVHIP_PACKED
 }
 
@@ -539,7 +636,7 @@ int common_args(TileArgs& a, const void* src, float* dst, const int* rois, int n
     PVHIP_CHECK_ARG(m >= 1 && roi_h >= 1 && roi_h <= src_h && roi_w >= 1 && roi_w <= src_w);
     a.src = (const unsigned char*)src; a.dst = dst; a.mean = mean; a.std_scale = std_scale;
     a.hs = src_h; a.ws = src_w; a.hd = dst_h; a.wd = dst_w; a.reverse = reverse_channels ? 1 : 0;
-    a.rois = rois; a.m = m; a.mh = roi_h; a.mw = roi_w;
+    a.rois = rois; a.m = m; a.mh = roi_h; a.mw = roi_w; a.fit = 0; a.pad = 0.0f;
     return PVHIP_OK;
 }
 
@@ -549,6 +646,51 @@ size_t extent(bool resize, int t, int S, int D) {
     const size_t e = ((size_t)(t - 1) * (size_t)S + (size_t)D - 1) / (size_t)D + 2;
     return e < (size_t)S ? e : (size_t)S;
 }
+
+// What a tile reads along both axes: rows(t) / cols(t) source rows (columns) at most for t destination rows (columns).  Without a fit
+// that is extent() of the launch's largest source onto the destination.  With one, the taps of an image run over its own fitted
+// rectangle (ih, iw), and a tile of t rows holds t' <= min(t, ih) rows of it, which read at most min(hs, ceil((t' - 1) hs / ih) + 2)
+// source rows (extent()'s argument: i0 advances by at most ceil(k hs / ih) over k steps, i1 <= i0 + 1); so a bound on the step hs / ih
+// of every image of the launch bounds the tile:
+//   whole images  (ih, iw) is known here: the steps are src_h / ih and src_w / iw exactly;
+//   ROI           the rectangle (hs, ws) <= (mh, mw) is device data.  Let r = hs wd / ws.  Wide (ws hd >= hs wd, so r <= hd): iw = wd, the
+//                 column step is ws / wd <= mw / wd; ih = floor(r + 1/2) unclamped from above, and either ih = 1 -- then t' = 1 and the tile
+//                 reads 2 rows at most, below any bound of this form -- or r >= 3/2 and ih >= r - 1/2 >= r / 2, so hs / ih <= 2 hs / r =
+//                 2 ws / wd <= 2 mw / wd.  Tall: the same with the axes swapped: row step hs / hd <= mh / hd, column step <= 2 mh / hd.
+//                 Hence rows step <= max(mh / hd, 2 mw / wd), columns step <= max(mw / wd, 2 mh / hd), each capped by (mh, mw).
+// The kernels check the slots they were given all the same and write NaN rather than stage past them.
+struct Reach {
+    bool fit, resize;
+    int S_h, S_w, D_h, D_w;                // !fit: extent()'s arguments
+    size_t rn, rd, cn, cd;                 // fit: the row and column steps rn / rd, cn / cd
+    static size_t by(int t, size_t num, size_t den, int cap) {
+        const size_t e = ((size_t)(t - 1) * num + den - 1) / den + 2;      // (t < 2^31, num < 2^33)
+        return e < (size_t)cap ? e : (size_t)cap;
+    }
+    size_t rows(int t) const { return fit ? by(t, rn, rd, S_h) : extent(resize, t, S_h, D_h); }
+    size_t cols(int t) const { return fit ? by(t, cn, cd, S_w) : extent(resize, t, S_w, D_w); }
+};
+
+Reach reach_of(const TileArgs& a, bool roi, bool resize) {
+    Reach r{a.fit != 0, resize, a.mh, a.mw, a.hd, a.wd, 0, 1, 0, 1};
+    if (!r.fit) return r;
+    if (!roi) {
+        const FitRect f = fit_rect(a.hs, a.ws, a.hd, a.wd, a.fit);
+        r.rn = (size_t)a.hs; r.rd = (size_t)f.ih; r.cn = (size_t)a.ws; r.cd = (size_t)f.iw;
+        return r;
+    }
+    const size_t mh = (size_t)a.mh, mw = (size_t)a.mw, hd = (size_t)a.hd, wd = (size_t)a.wd;
+    if (mh * wd >= 2 * mw * hd) { r.rn = mh; r.rd = hd; } else { r.rn = 2 * mw; r.rd = wd; }
+    if (mw * hd >= 2 * mh * wd) { r.cn = mw; r.cd = wd; } else { r.cn = 2 * mh; r.cd = hd; }
+    return r;
+}
+
+// What the _fit_ entries add to the launchers' arguments; fit 0: none.  false: not a fit, or no finite pad.
+struct Fit {
+    int fit;
+    float pad;
+    bool ok() const { return (fit == 1 || fit == 2) && pad - pad == 0.0f; }
+};
 
 struct TilePlan {
     dim3 grid;
@@ -577,24 +719,31 @@ int plan_tiles(TileArgs& a, int n, StageOf stage_of, TilePlan& p) {
 
 // The one launcher of preprocess_kernel.
 int preprocess_launch(const void* src, float* dst, const int* rois, int n, int m, int c, int src_h, int src_w, int dst_h, int dst_w,
-                      int roi_h, int roi_w, int src_u8, int src_nhwc, int reverse_channels, const float* mean, const float* std_scale) {
+                      int roi_h, int roi_w, int src_u8, int src_nhwc, int reverse_channels, const float* mean, const float* std_scale,
+                      Fit fit = Fit{0, 0.0f}) {
     PrepArgs a;
     int rc = common_args(a, src, dst, rois, n, m, c, src_h, src_w, dst_h, dst_w, roi_h, roi_w, reverse_channels, mean, std_scale);
     if (rc != PVHIP_OK) return rc;
     PVHIP_CHECK_ARG(c <= kMaxChannels);
     PVHIP_CHECK_ARG(src_u8 || (uintptr_t)src % 4 == 0);                              // fp32 sources are element-aligned
-    const bool roi = rois != nullptr, resize = roi || src_h != dst_h || src_w != dst_w;
+    const bool roi = rois != nullptr, resize = roi || fit.fit || src_h != dst_h || src_w != dst_w;
     if (!resize && !reverse_channels && mean == nullptr && std_scale == nullptr)      // the format alone: the same bits as the
         return pvhip_input_to_nchw_f32(src, dst, n, c, dst_h, dst_w, src_u8, src_nhwc);   // path without preprocessing
+    a.fit = fit.fit; a.pad = fit.pad;
+    const Reach reach = reach_of(a, roi, resize);
     const size_t es = src_u8 ? 1 : 4;
     const size_t cs = src_nhwc ? (size_t)c : 1, planes = src_nhwc ? 1 : (size_t)c;
-    auto slot_of = [&](int tw) { return (extent(resize, tw, roi_w, dst_w) * cs * es + 30) / 16 * 16; };
+    auto slot_of = [&](int tw) { return (reach.cols(tw) * cs * es + 30) / 16 * 16; };
     TilePlan p;
-    rc = plan_tiles(a, n, [&](int tw, int th) { return planes * extent(resize, th, roi_h, dst_h) * slot_of(tw); }, p);
+    rc = plan_tiles(a, n, [&](int tw, int th) { return planes * reach.rows(th) * slot_of(tw); }, p);
     if (rc != PVHIP_OK) return rc;
     a.c = c; a.nhwc = src_nhwc ? 1 : 0; a.slot = (unsigned)slot_of(a.tw);
     hipStream_t st = state().stream;
-    if (roi)         src_u8 ? launch<true, true, true>(a, p.grid, p.lds, p.vs, st) : launch<false, true, true>(a, p.grid, p.lds, p.vs, st);
+    if (fit.fit) {
+        if (roi) src_u8 ? launch<true, true, true, true>(a, p.grid, p.lds, p.vs, st) : launch<false, true, true, true>(a, p.grid, p.lds, p.vs, st);
+        else     src_u8 ? launch<true, true, false, true>(a, p.grid, p.lds, p.vs, st) : launch<false, true, false, true>(a, p.grid, p.lds, p.vs, st);
+    }
+    else if (roi)    src_u8 ? launch<true, true, true>(a, p.grid, p.lds, p.vs, st) : launch<false, true, true>(a, p.grid, p.lds, p.vs, st);
     else if (src_u8) resize ? launch<true, true, false>(a, p.grid, p.lds, p.vs, st) : launch<true, false, false>(a, p.grid, p.lds, p.vs, st);
     else             resize ? launch<false, true, false>(a, p.grid, p.lds, p.vs, st) : launch<false, false, false>(a, p.grid, p.lds, p.vs, st);
     PVHIP_LAUNCH_CHECK();
@@ -603,19 +752,22 @@ int preprocess_launch(const void* src, float* dst, const int* rois, int n, int m
 
 // The one launcher of preprocess_yuv_kernel.
 int preprocess_yuv_launch(const void* src, float* dst, const int* rois, int n, int m, int src_h, int src_w, int dst_h, int dst_w,
-                          int roi_h, int roi_w, int planar, int reverse_channels, const float* mean, const float* std_scale) {
+                          int roi_h, int roi_w, int planar, int reverse_channels, const float* mean, const float* std_scale,
+                          Fit fit = Fit{0, 0.0f}) {
     YuvArgs a;
     int rc = common_args(a, src, dst, rois, n, m, 3, src_h, src_w, dst_h, dst_w, roi_h, roi_w, reverse_channels, mean, std_scale);
     if (rc != PVHIP_OK) return rc;
     PVHIP_CHECK_ARG(src_h % 2 == 0 && src_w % 2 == 0);                               // 4:2:0: one (U, V) per 2 x 2 block
     PVHIP_CHECK_ARG(planar == 0 || planar == 1);
-    const bool roi = rois != nullptr, resize = roi || src_h != dst_h || src_w != dst_w;
+    const bool roi = rois != nullptr, resize = roi || fit.fit || src_h != dst_h || src_w != dst_w;
+    a.fit = fit.fit; a.pad = fit.pad;
+    const Reach reach = reach_of(a, roi, resize);
     // e consecutive rows (columns) lie over at most e / 2 + 1 chroma rows (pairs): the first may be an odd one
     auto halves = [](size_t e, int S) { return e / 2 + 1 < (size_t)S / 2 ? e / 2 + 1 : (size_t)S / 2; };
-    auto yslot_of = [&](int tw) { return (extent(resize, tw, roi_w, dst_w) + 30) / 16 * 16; };
-    auto cslot_of = [&](int tw) { return (halves(extent(resize, tw, roi_w, dst_w), src_w) * (planar ? 1 : 2) + 30) / 16 * 16; };
+    auto yslot_of = [&](int tw) { return (reach.cols(tw) + 30) / 16 * 16; };
+    auto cslot_of = [&](int tw) { return (halves(reach.cols(tw), src_w) * (planar ? 1 : 2) + 30) / 16 * 16; };
     auto stage_of = [&](int tw, int th) {
-        const size_t e = extent(resize, th, roi_h, dst_h);
+        const size_t e = reach.rows(th);
         return e * yslot_of(tw) + halves(e, src_h) * (planar ? 2 : 1) * cslot_of(tw);
     };
     TilePlan p;
@@ -623,7 +775,8 @@ int preprocess_yuv_launch(const void* src, float* dst, const int* rois, int n, i
     if (rc != PVHIP_OK) return rc;
     a.planar = planar; a.yslot = (unsigned)yslot_of(a.tw); a.cslot = (unsigned)cslot_of(a.tw);
     hipStream_t st = state().stream;
-    if (roi) launch_yuv<true, true>(a, p.grid, p.lds, p.vs, st);
+    if (fit.fit) roi ? launch_yuv<true, true, true>(a, p.grid, p.lds, p.vs, st) : launch_yuv<true, false, true>(a, p.grid, p.lds, p.vs, st);
+    else if (roi) launch_yuv<true, true>(a, p.grid, p.lds, p.vs, st);
     else     resize ? launch_yuv<true, false>(a, p.grid, p.lds, p.vs, st) : launch_yuv<false, false>(a, p.grid, p.lds, p.vs, st);
     PVHIP_LAUNCH_CHECK();
     return PVHIP_OK;
@@ -631,19 +784,22 @@ int preprocess_yuv_launch(const void* src, float* dst, const int* rois, int n, i
 
 // The one launcher of preprocess_packed_kernel.  kind: 0 YUY2, 1 UYVY, 2 BGRX, 3 RGBX.
 int preprocess_packed_launch(const void* src, float* dst, const int* rois, int n, int m, int src_h, int src_w, int dst_h, int dst_w,
-                             int roi_h, int roi_w, int kind, int reverse_channels, const float* mean, const float* std_scale) {
+                             int roi_h, int roi_w, int kind, int reverse_channels, const float* mean, const float* std_scale,
+                             Fit fit = Fit{0, 0.0f}) {
     PackedArgs a;
     int rc = common_args(a, src, dst, rois, n, m, 3, src_h, src_w, dst_h, dst_w, roi_h, roi_w, reverse_channels, mean, std_scale);
     if (rc != PVHIP_OK) return rc;
     PVHIP_CHECK_ARG(kind >= 0 && kind <= 3);
     const bool yuv = kind < 2;
     PVHIP_CHECK_ARG(!yuv || src_w % 2 == 0);                                         // 4:2:2: one (U, V) per column pair
-    const bool roi = rois != nullptr, resize = roi || src_h != dst_h || src_w != dst_w;
+    const bool roi = rois != nullptr, resize = roi || fit.fit || src_h != dst_h || src_w != dst_w;
+    a.fit = fit.fit; a.pad = fit.pad;
+    const Reach reach = reach_of(a, roi, resize);
     // e consecutive columns lie in at most e / 2 + 1 groups of 4:2:2 (the first may be an odd one), and in e units of an X kind
     auto units = [&](size_t e) { return !yuv ? e : (e / 2 + 1 < (size_t)src_w / 2 ? e / 2 + 1 : (size_t)src_w / 2); };
-    auto slot_of = [&](int tw) { return (units(extent(resize, tw, roi_w, dst_w)) * 4 + 30) / 16 * 16; };
+    auto slot_of = [&](int tw) { return (units(reach.cols(tw)) * 4 + 30) / 16 * 16; };
     TilePlan p;
-    rc = plan_tiles(a, n, [&](int tw, int th) { return extent(resize, th, roi_h, dst_h) * slot_of(tw); }, p);
+    rc = plan_tiles(a, n, [&](int tw, int th) { return reach.rows(th) * slot_of(tw); }, p);
     if (rc != PVHIP_OK) return rc;
     a.slot = (unsigned)slot_of(a.tw);
     hipStream_t st = state().stream;
@@ -704,5 +860,40 @@ int pvhip_input_preprocess_packed_roi_f32(const void* src, float* dst, const int
     return preprocess_packed_launch(src, dst, rois, n, m, src_h, src_w, dst_h, dst_w, max_roi_h, max_roi_w, kind, reverse_channels, mean,
                                     std_scale);
 }
+
+// The fitted forms: rois == NULL means whole images.  A fit of whole images that fills the destination is the existing launch.
+#define PVHIP_FIT_ARGS()                                                                                                      \
+    PVHIP_REQUIRE_INIT();                                                                                                      \
+    const Fit f{fit, pad_value};                                                                                               \
+    PVHIP_CHECK_ARG(f.ok());                                                                                                   \
+    PVHIP_CHECK_ARG(src_h > 0 && src_w > 0 && dst_h > 0 && dst_w > 0);                                                         \
+    if (rois == nullptr) { m = n; max_roi_h = src_h; max_roi_w = src_w; }                                                      \
+    const FitRect g = fit_rect(src_h, src_w, dst_h, dst_w, fit);                                                               \
+    const Fit used = rois == nullptr && g.iw == dst_w && g.ih == dst_h ? Fit{0, 0.0f} : f
+
+int pvhip_input_preprocess_fit_f32(const void* src, float* dst, const int* rois, int n, int m, int c, int src_h, int src_w, int dst_h,
+                                   int dst_w, int max_roi_h, int max_roi_w, int src_u8, int src_nhwc, int reverse_channels,
+                                   const float* mean, const float* std_scale, int fit, float pad_value) {
+    PVHIP_FIT_ARGS();
+    return preprocess_launch(src, dst, rois, n, m, c, src_h, src_w, dst_h, dst_w, max_roi_h, max_roi_w, src_u8, src_nhwc, reverse_channels,
+                             mean, std_scale, used);
+}
+
+int pvhip_input_preprocess_yuv_fit_f32(const void* src, float* dst, const int* rois, int n, int m, int src_h, int src_w, int dst_h,
+                                       int dst_w, int max_roi_h, int max_roi_w, int planar, int reverse_channels, const float* mean,
+                                       const float* std_scale, int fit, float pad_value) {
+    PVHIP_FIT_ARGS();
+    return preprocess_yuv_launch(src, dst, rois, n, m, src_h, src_w, dst_h, dst_w, max_roi_h, max_roi_w, planar, reverse_channels, mean,
+                                 std_scale, used);
+}
+
+int pvhip_input_preprocess_packed_fit_f32(const void* src, float* dst, const int* rois, int n, int m, int src_h, int src_w, int dst_h,
+                                          int dst_w, int max_roi_h, int max_roi_w, int kind, int reverse_channels, const float* mean,
+                                          const float* std_scale, int fit, float pad_value) {
+    PVHIP_FIT_ARGS();
+    return preprocess_packed_launch(src, dst, rois, n, m, src_h, src_w, dst_h, dst_w, max_roi_h, max_roi_w, kind, reverse_channels, mean,
+                                    std_scale, used);
+}
+#undef PVHIP_FIT_ARGS
 
 }  // extern "C"

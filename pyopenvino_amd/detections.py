@@ -9,6 +9,11 @@ ymin, xmax, ymax] with normalised corners; image b is rows [b P, (b + 1) P) of t
   rectangle over frames of (H, W), in float32, never contracted: x0 = floor(min(max(xmin W, 0), W)), x1 = ceil(min(max(xmax W, 0), W)),
             y0 / y1 alike with H; dropped when x1 - x0 < min_size[1] or y1 - y0 < min_size[0]
 -- so far exactly DetectedRois' rule (pvhip_detections_to_rois, tests/detected_rois_ref.py) --;
+  fitted    a detector whose input declares a fit (preprocess_info.resize_fit) saw the frame in the rectangle [dy, dy + ih) x [dx, dx + iw)
+            of its (Hn, Wn) input: with `fit` = (Hn, Wn, dx, dy, iw, ih) every corner is mapped back first, in float32, three roundings,
+            u = (xmin float32(Wn) - float32(dx)) / float32(iw) (ymin: Hn, dy, ih), and the rectangle is that of u; the finite check is on the
+            record's own corners.  A box in the padding clamps to the frame's edge, one wholly in it has extent 0 and is dropped
+            (pvhip_detections_compact_fit, pvhip_detections_to_rois_fit; tests/letterbox_ref.py);
   cap       image b keeps its first counts[b] = min(selected[b], max_per_image) survivors in position order: its best scores, because
             an image's records stand in descending score order;
   table     the kept survivors of all images in (image, position) order, no gap between images; total = sum(counts);
@@ -110,9 +115,28 @@ def records_checked(records) -> np.ndarray:
     return rec.reshape(-1, 7)
 
 
-def screened(rec, groups: int, conf, labels, min_size, height, width, empty=None) -> tuple:
+def checked_fit(fit, what='fit'):
+    """`fit` as six ints (Hn, Wn, dx, dy, iw, ih) -- a rectangle of at least 1 x 1 inside an input of at most 2^24 x 2^24 --, or None;
+    ValueError."""
+    if fit is None:
+        return None
+    try:
+        g = tuple(fit)
+        ok = len(g) == 6 and all(not isinstance(v, bool) and isinstance(v, (int, np.integer)) for v in g)
+    except TypeError:
+        ok = False
+    if ok:
+        Hn, Wn, dx, dy, iw, ih = g = tuple(int(v) for v in g)
+        ok = 1 <= Hn <= MAX_EXTENT and 1 <= Wn <= MAX_EXTENT and iw >= 1 and ih >= 1 and dx >= 0 and dy >= 0 and dx + iw <= Wn and dy + ih <= Hn
+    if not ok:
+        raise ValueError('detections: {} is (Hn, Wn, dx, dy, iw, ih), a rectangle inside the detector\'s input, got {!r}'.format(what, fit))
+    return g
+
+
+def screened(rec, groups: int, conf, labels, min_size, height, width, empty=None, fit=None) -> tuple:
     """The rule's `live`, `selected` and `rectangle` on (N P, 7) records of N = `groups` lists, over frames of (`height`, `width`) -- two
-    numbers, or float32 arrays with one extent per record --; `empty`: (N,) bool, the lists that take nothing.  (keep, x0, y0, w, h, label):
+    numbers, or float32 arrays with one extent per record --; `empty`: (N,) bool, the lists that take nothing; `fit`: the six ints of a
+    fitted detector input, whose corners are mapped back first.  (keep, x0, y0, w, h, label):
     the (N, P) mask of the survivors before any cap, their rectangles as int64 and the rows' label words, one entry per record."""
     N, P = groups, rec.shape[0] // groups
     dead = ~(rec[:, 0] >= 0).reshape(N, P)
@@ -124,6 +148,11 @@ def screened(rec, groups: int, conf, labels, min_size, height, width, empty=None
     if labels is not None:
         keep &= np.isin(rec[:, 1], np.asarray(labels, np.int64).astype(np.float32))
     corners = np.where(keep[:, None], rec[:, 3:7], np.float32(0))
+    if fit is not None:
+        Hn, Wn, dx, dy, iw, ih = fit
+        with np.errstate(over='ignore'):
+            corners = np.stack([(corners[:, k] * np.float32(N_) - np.float32(d)) / np.float32(i)
+                                for k, (N_, d, i) in enumerate(((Wn, dx, iw), (Hn, dy, ih), (Wn, dx, iw), (Hn, dy, ih)))], axis=1)
 
     def edge(v, extent, rounded):
         e = np.float32(extent)
@@ -140,15 +169,17 @@ def screened(rec, groups: int, conf, labels, min_size, height, width, empty=None
     return keep.reshape(N, P), x0, y0, w, h, label
 
 
-def compact_records(records, images: int, screen) -> Detections:
+def compact_records(records, images: int, screen, fit=None) -> Detections:
     """The rule in numpy on a host array of float32 records, (1, 1, R, 7) or (R, 7), of `images` images: what a Result computed on the
-    host (a foreign plugin set) gets.  `screen`: a DetectionScreen with a frame_size (there is no network here to take it from)."""
+    host (a foreign plugin set) gets.  `screen`: a DetectionScreen with a frame_size (there is no network here to take it from); `fit`:
+    None, or (Hn, Wn, dx, dy, iw, ih) of a fitted detector input."""
     rec = records_checked(records)
+    fit = checked_fit(fit)
     if not _count(images) or rec.shape[0] % images:
         raise ValueError('detections: {} records do not divide into {!r} images'.format(rec.shape[0], images))
     N, P = int(images), rec.shape[0] // int(images)
     conf, (H, W), labels, min_size, cap = resolved(screen, P)
-    keep, x0, y0, w, h, label = screened(rec, N, conf, labels, min_size, H, W)
+    keep, x0, y0, w, h, label = screened(rec, N, conf, labels, min_size, H, W, fit=fit)
     selected = keep.sum(axis=1).astype(np.int32)
     kept = np.flatnonzero((keep & (np.cumsum(keep, axis=1) <= cap)).ravel())
     rois = np.stack([kept // P, x0[kept], y0[kept], w[kept], h[kept]], axis=1).astype(np.int32).reshape(-1, 5)
@@ -252,13 +283,15 @@ class Blocks(TableBlocks):
         super().__init__(images, images * min(per_image, screen.max_per_image), screen)
         self.images, self.per_image = images, per_image
 
-    def launch(self, result):
-        """The entry's two launches on the current stream, behind whatever wrote `result` there."""
+    def launch(self, result, frame_size=None, fit=None):
+        """The entry's two launches on the current stream, behind whatever wrote `result` there; `fit`: the six ints of a fitted
+        detector input (pvhip_detections_compact_fit), over frames of `frame_size` (default: the screen's)."""
         s = self.screen
+        frame = s.frame_size if frame_size is None else frame_size
         assert result.dtype == np.float32 and int(np.prod(result.shape)) == 7 * self.images * self.per_image
-        device.call(self.ENTRY, device.ptr(result), self.images, self.per_image, s.frame_size[0], s.frame_size[1],
+        device.call(self.ENTRY + ('_fit' if fit is not None else ''), device.ptr(result), self.images, self.per_image, frame[0], frame[1],
                     s.min_confidence, device.ptr(self.labels), 0 if s.labels is None else len(s.labels), s.min_size[0], s.min_size[1],
-                    s.max_per_image, ctypes.c_void_p(self.header.ptr), ctypes.c_void_p(self.rows.ptr))
+                    s.max_per_image, ctypes.c_void_p(self.header.ptr), ctypes.c_void_p(self.rows.ptr), *(fit or ()))
 
 
 class Ask(collections.namedtuple('Ask', 'screen images')):
@@ -278,3 +311,32 @@ class Ask(collections.namedtuple('Ask', 'screen images')):
 
     def on_host(self, value):
         return compact_records(value, self.images, self.screen)
+
+
+class FittedAsk(collections.namedtuple('FittedAsk', 'screen images input format explicit fit')):
+    """The Ask of a detector whose 4-D Parameter `input`, of InputFormat `format`, declares a fit: `fit` = (Hn, Wn, dx, dy, iw, ih) is known
+    once the pass's inputs are staged (bound), from the extent of the frames that pass was fed, and frame_size -- unless the caller gave
+    one (`explicit`) -- is that extent."""
+    __slots__ = ()
+
+    def bound(self, inputs, slots):
+        extent = slots[self.input].fed if self.input in slots else None
+        if extent is None:                      # a device tensor at the network's own extent: nothing was fitted
+            return self._replace(fit=None)
+        screen = self.screen if self.explicit else self.screen._replace(frame_size=(int(extent[0]), int(extent[1])))
+        if not _pair(screen.frame_size, MAX_EXTENT):
+            raise ValueError('detections: frames of {} are more than 2^24 wide or high'.format(tuple(extent)))
+        fmt = self.format
+        return self._replace(screen=screen, fit=(int(fmt.dims[2]), int(fmt.dims[3])) + tuple(fmt.fit_geometry(extent)))
+
+    def key(self, name):
+        # (the blocks serve every frame extent: neither their size nor their labels depend on it)
+        return (name, self.screen if self.fit is None else self.screen._replace(frame_size=None))
+
+    def launch(self, blocks, value):
+        blocks = blocks or Blocks(self.images, value.shape[-2] // self.images, self.screen)
+        blocks.launch(value, self.screen.frame_size, self.fit)
+        return blocks
+
+    def on_host(self, value):
+        return compact_records(value, self.images, self.screen, self.fit)

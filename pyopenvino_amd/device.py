@@ -150,6 +150,10 @@ SIGNATURES = {
     'pvhip_detections_to_rois': (_c.c_int, [_c.c_void_p] * 4 + [_c.c_int] * 5 + [_c.c_float, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int]),
     'pvhip_topk_rows_f32': (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p]),
     'pvhip_detections_compact': (_c.c_int, [_c.c_void_p] + [_c.c_int] * 4 + [_c.c_float, _c.c_void_p] + [_c.c_int] * 4 + [_c.c_void_p] * 2),
+    'pvhip_detections_compact_fit': (_c.c_int, [_c.c_void_p] + [_c.c_int] * 4 + [_c.c_float, _c.c_void_p] + [_c.c_int] * 4 + [_c.c_void_p] * 2 +
+                                     [_c.c_int] * 6),
+    'pvhip_detections_to_rois_fit': (_c.c_int, [_c.c_void_p] * 4 + [_c.c_int] * 5 + [_c.c_float, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int] +
+                                     [_c.c_int] * 6),
     'pvhip_detections_merge_tiles': (_c.c_int, [_c.c_void_p] * 2 + [_c.c_int] * 3 + [_c.c_float, _c.c_void_p] + [_c.c_int] * 5 + [_c.c_float] +
                                      [_c.c_int] * 2 + [_c.c_void_p] * 3),
     'pvhip_comm_unique_id': (_c.c_int, [_c.c_void_p]),
@@ -164,6 +168,9 @@ SIGNATURES = {
     'pvhip_input_preprocess_yuv_roi_f32': (_c.c_int, [_c.c_void_p, _fp, _c.c_void_p] + [_c.c_int] * 10 + [_fp, _fp]),
     'pvhip_input_preprocess_packed_f32': (_c.c_int, [_c.c_void_p, _fp] + [_c.c_int] * 7 + [_fp, _fp]),
     'pvhip_input_preprocess_packed_roi_f32': (_c.c_int, [_c.c_void_p, _fp, _c.c_void_p] + [_c.c_int] * 10 + [_fp, _fp]),
+    'pvhip_input_preprocess_fit_f32': (_c.c_int, [_c.c_void_p, _fp, _c.c_void_p] + [_c.c_int] * 12 + [_fp, _fp, _c.c_int, _c.c_float]),
+    'pvhip_input_preprocess_yuv_fit_f32': (_c.c_int, [_c.c_void_p, _fp, _c.c_void_p] + [_c.c_int] * 10 + [_fp, _fp, _c.c_int, _c.c_float]),
+    'pvhip_input_preprocess_packed_fit_f32': (_c.c_int, [_c.c_void_p, _fp, _c.c_void_p] + [_c.c_int] * 10 + [_fp, _fp, _c.c_int, _c.c_float]),
 }
 
 # entry points whose return value is not a status code

@@ -6,7 +6,7 @@ import ctypes
 
 import numpy as np
 
-from . import device
+from . import detections as detections_rule, device
 from .input_format import DetectedRois, DetectedTable, RoiInput
 
 
@@ -36,13 +36,14 @@ class _Slot:
     The device table is the head of one block `table` of 6 n + 2 ints, (n, 5) rois | (n,) record_of | (count, selected): what
     pvhip_detections_to_rois writes for a DetectedRois (`detected`: what that needs besides, once one is fed) and detected_rois() reads
     back in one copy."""
-    __slots__ = ('fixed', 'event', 'mean', 'std', 'extents', 'rois_host', 'rois', 'table', 'detected')
+    __slots__ = ('fixed', 'event', 'mean', 'std', 'extents', 'rois_host', 'rois', 'table', 'detected', 'fed')
 
     def __init__(self, fmt):
         self.fixed, self.event = device.DeviceTensor.empty(fmt.dims), device.Event(timed=False)
         self.mean, self.std = (None, None) if fmt.mean is None else (device.DeviceTensor.from_numpy(fmt.mean), device.DeviceTensor.from_numpy(fmt.std))
         self.extents = collections.OrderedDict()
         self.rois_host = self.rois = self.table = self.detected = None
+        self.fed = None                         # the extent of the whole images the last pass was staged from (what a declared fit fitted)
 
     def roi_table(self):
         if self.rois_host is None:
@@ -142,10 +143,11 @@ class HostInputs:
     @staticmethod
     def _detections_of(name, det):
         """What DetectedRois `det` reads, nothing waited for and nothing copied: (records -- a DeviceTensor or a host array --, the images
-        they belong to by default or None, the runner whose pass produces them and the event behind that pass, or (None, None))."""
+        they belong to by default or None, the runner whose pass produces them and the event behind that pass, or (None, None), the geometry
+        of the detector's fitted input or None)."""
         src = det.detections
         if not (hasattr(src, 'runner') and hasattr(src, 'start_async')):         # (an InferRequest: inference_engine imports this module)
-            return (src if isinstance(src, device.DeviceTensor) else np.asarray(src)), None, None, None
+            return (src if isinstance(src, device.DeviceTensor) else np.asarray(src)), None, None, None, None
         runner = src.runner
         net = runner.ienet
         results = net.find_node_by_type('Result')
@@ -162,9 +164,21 @@ class HostInputs:
         value = replayed['results'][results[0][1]] if replayed is not None else net.G.nodes[nid].get('result')
         if value is None:
             raise RuntimeError('input {}: the detector request never ran: start_async() or infer() it first'.format(name))
+        fit = runner.host_inputs.detector_fit()
         if not isinstance(value, device.DeviceTensor):        # waited for: its host Results, like an array
-            return np.asarray(value), net.batch_size, None, None
-        return value, net.batch_size, runner, (pending[1] if pending is not None else None)
+            return np.asarray(value), net.batch_size, None, None, fit
+        return value, net.batch_size, runner, (pending[1] if pending is not None else None), fit
+
+    def detector_fit(self):
+        """(Hn, Wn, dx, dy, iw, ih) of the pass this network was last fed, when its single 4-D Parameter declares a fit and was staged
+        from whole images; else None: what a DetectedRois over this network's records maps their corners back with."""
+        names = [name for name, fmt in self.formats.items() if len(fmt.dims) == 4]
+        if len(names) != 1 or not self.formats[names[0]].fitted:
+            return None
+        fmt, slot = self.formats[names[0]], self.slots.get(names[0])
+        if slot is None or slot.fed is None:
+            return None
+        return (int(fmt.dims[2]), int(fmt.dims[3])) + tuple(fmt.fit_geometry(slot.fed))
 
     def _stage_detected(self, name, fmt, det, sharded):
         """The frames of DetectedRois `det` in this request's page-locked buffers, its records (a host array: in the slot's page-locked
@@ -175,7 +189,9 @@ class HostInputs:
         frames = det.frames if isinstance(det.frames, np.ndarray) else np.asarray(det.frames)
         extent, m = fmt.frames_extent_of(frames)
         conf, labels, (min_h, min_w) = det.checked_options(name)
-        records, images, runner, done = self._detections_of(name, det)
+        records, images, runner, done, fit = self._detections_of(name, det)
+        if det.detector_fit is not None:
+            fit = detections_rule.checked_fit(det.detector_fit, 'input {}: detector_fit'.format(name))
         images = det.images if det.images is not None else (images if images is not None else m)
         per_image = det.checked_records(name, records.shape, records.dtype, images, m)
         staged = self._staging(name, extent, m)
@@ -202,9 +218,9 @@ class HostInputs:
         def launch():
             if done is not None:
                 done.wait()                                   # the detector's pass, on the device
-            device.call('pvhip_detections_to_rois', device.ptr(d.source), ctypes.c_void_p(slot.table.ptr),
+            device.call('pvhip_detections_to_rois' + ('_fit' if fit is not None else ''), device.ptr(d.source), ctypes.c_void_p(slot.table.ptr),
                         ctypes.c_void_p(slot.table.ptr + 20 * n), ctypes.c_void_p(slot.table.ptr + 24 * n), n, images, per_image, *extent,
-                        conf, listed, 0 if labels is None else len(labels), min_h, min_w)
+                        conf, listed, 0 if labels is None else len(labels), min_h, min_w, *(fit or ()))
             if runner is not None:                            # its next pass may overwrite that Result: not before this launch has read it
                 runner._result_readers.append(d.read.record())
 
@@ -243,13 +259,24 @@ class HostInputs:
         """The one launch that makes `slot.fixed` of what `staged` uploaded (none for FP32 NCHW at the network's extent):
         pvhip_input_preprocess_yuv_f32 for NV12 / I420 frames, pvhip_input_preprocess_packed_f32 for YUY2 / UYVY / BGRX / RGBX frames,
         pvhip_input_preprocess_f32 when a resize, channel reversal or mean / scale is in effect, else pvhip_input_to_nchw_f32;
-        `largest` = (max_h, max_w) of a RoiInput's table: the _roi_f32 forms."""
+        `largest` = (max_h, max_w) of a RoiInput's table: the _roi_f32 forms.  A declared fit: the _fit_f32 forms of the three, with
+        the table or NULL."""
         fixed = slot.fixed
         src, dst = device.ptr(staged.staging), device.ptr(fixed)
         n, c, dst_hw = fixed.shape[0], fixed.shape[1], fixed.shape[2:]
         how = (int(fmt.color == 'I420'),) if fmt.yuv else (fmt.packed_kind,) if fmt.packed else (int(fmt.u8), int(fmt.nhwc))
         pre = (int(fmt.reverse), device.ptr(slot.mean), device.ptr(slot.std))
-        if largest is not None:
+        if fmt.fitted and (largest is not None or fmt.yuv or fmt.packed or staged.preprocess):
+            where = (src, dst, device.ptr(slot.rois if largest is not None else None), n, staged.frames if largest is not None else n)
+            sizes = (*staged.extent, *dst_hw, *(largest if largest is not None else staged.extent))
+            tail = (*how, *pre, fmt.fit_code, fmt.pad)
+            if fmt.yuv:
+                device.call('pvhip_input_preprocess_yuv_fit_f32', *where, *sizes, *tail)
+            elif fmt.packed:
+                device.call('pvhip_input_preprocess_packed_fit_f32', *where, *sizes, *tail)
+            else:
+                device.call('pvhip_input_preprocess_fit_f32', *where, c, *sizes, *tail)
+        elif largest is not None:
             where = (src, dst, device.ptr(slot.rois), n, staged.frames)
             if fmt.yuv:
                 device.call('pvhip_input_preprocess_yuv_roi_f32', *where, *staged.extent, *dst_hw, *largest, *how, *pre)
@@ -286,12 +313,15 @@ class HostInputs:
                 staged, uploads, make_table = self._stage_detected(name, self._format(name), arr, sharded)
                 largest = staged.extent                       # the host does not know the largest rectangle: the frame bounds it
             elif fmt is None or isinstance(arr, (device.DeviceTensor, device.ChannelSlice, device.BlockedHalf)):
+                if name in self.slots:
+                    self.slots[name].fed = None
                 continue
             else:
                 staged = self._find_or_copy(name, fmt, arr)
                 if staged is None:
                     continue
             slot = self.slots[name]
+            slot.fed = staged.extent if largest is None else None
             slot.extents.move_to_end(staged.key)
             while len(slot.extents) > self.MAX_SOURCE_EXTENTS:
                 slot.extents.popitem(last=False)

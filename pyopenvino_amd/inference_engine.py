@@ -312,6 +312,10 @@ class InferRequest:
     and read back in two copies, 4 (2 n + 1) bytes and 32 bytes per row; the full Result stays on the device, where a ``DetectedRois``
     of another request reads it as before.  ValueError ('detections: ...'), before anything is staged or launched: an unknown name, a
     Result of another shape or precision, a value of the screen out of range, a sharded batch, no such Result for an unnamed form.
+    On a network whose 4-D Parameter declares ``preprocess_info.resize_fit`` 'LETTERBOX' / 'TOP_LEFT' the detector saw the frame in a
+    rectangle of its input: every corner is mapped back through the geometry of the frames this pass was fed before the rectangle rule
+    (pvhip_detections_compact_fit), and `frame_size` None means the extent of those frames; ValueError when that input is fed a
+    ``RoiInput`` / ``DetectedRois`` in the same pass (a geometry per row), or for a TiledScreen over it.
     A ``TiledScreen`` in the place of a DetectionScreen, for a pass whose 4-D input is fed a ``RoiInput(frames, tiles)``: the batch rows
     are tiles of the m frames and the Result comes back as a Detections over FRAMES -- shifted into frame pixels, ordered by score and
     suppressed across the tiles of a frame by the rule of tiled_detections.py --, made by pvhip_detections_merge_tiles behind the pass with

@@ -10,6 +10,22 @@ import numpy as np
 # pvhip_input_preprocess_packed_f32: packed YUV 4:2:2 (n, h, w, 2) and four-byte pixels (n, h, w, 4)
 YUV420_FORMATS = ('NV12', 'I420')
 PACKED_KINDS = {'YUY2': 0, 'UYVY': 1, 'BGRX': 2, 'RGBX': 3}
+# how a resized source is placed in the Parameter's extent, with the `fit` of the pvhip_input_preprocess_*_fit_f32 entries
+RESIZE_FITS = {'STRETCH': 0, 'LETTERBOX': 1, 'TOP_LEFT': 2}
+
+
+def fit_geometry(src_hw, dst_hw, fit) -> tuple:
+    """(dx, dy, iw, ih): the rectangle of a destination (hd, wd) that a source (or ROI rectangle) of (hs, ws) is fitted into -- one scale
+    factor for both axes, the short side rounded half up and kept in [1, D]; 'LETTERBOX' centres it (floor), 'TOP_LEFT' does not; 'STRETCH'
+    is the whole destination.  Python ints: the rule of include/pvhip.h (pvhip_input_preprocess_fit_f32) word for word."""
+    (hs, ws), (hd, wd) = (int(v) for v in src_hw), (int(v) for v in dst_hw)
+    if fit == 'STRETCH':
+        return 0, 0, wd, hd
+    if ws * hd >= hs * wd:
+        iw, ih = wd, min(max((2 * hs * wd + ws) // (2 * ws), 1), hd)
+    else:
+        ih, iw = hd, min(max((2 * ws * hd + hs) // (2 * hs), 1), wd)
+    return ((wd - iw) // 2, (hd - ih) // 2, iw, ih) if fit == 'LETTERBOX' else (0, 0, iw, ih)
 
 
 @dataclasses.dataclass(frozen=True, eq=False)
@@ -17,7 +33,8 @@ class InputFormat:
     """One input's format as a fixed value (``InputInfo.frozen()``; load_network makes one per input and every request reads that one):
     ``dims`` the (n, c, h, w) of the fp32 tensor the IR expects, ``supported`` / ``declared`` as InputInfo has them, ``u8`` / ``nhwc`` the
     declared precision and layout, ``resize`` / ``reverse`` / ``mean`` / ``std`` the declared preprocessing (fp32 arrays of c values, or
-    None without MEAN_VALUE), ``color`` the declared colour format: 'RAW', or 'NV12' / 'I420' for YUV 4:2:0 frames, uint8 of shape
+    None without MEAN_VALUE), ``fit`` / ``pad`` the declared placement of a resized source ('STRETCH', or 'LETTERBOX' / 'TOP_LEFT': one
+    scale factor, the rest of the extent filled with ``pad``; ``fit_geometry``), ``color`` the declared colour format: 'RAW', or 'NV12' / 'I420' for YUV 4:2:0 frames, uint8 of shape
     (n, 3 h / 2, w), or 'YUY2' / 'UYVY' for packed YUV 4:2:2 frames, uint8 of shape (n, h, w, 2), or 'BGRX' / 'RGBX' for four-byte
     pixels, uint8 of shape (n, h, w, 4), whatever ``u8`` / ``nhwc`` say.  An extent is the (h, w) of a caller's image.  A RoiInput's frames have the same
     shapes with their own count m in place of n (``host_shape(extent, frames=m)``, ``frames_extent_of``) and a table ``checked_rois``
@@ -33,6 +50,21 @@ class InputFormat:
     mean: np.ndarray
     std: np.ndarray
     color: str = 'RAW'
+    fit: str = 'STRETCH'
+    pad: float = 0.0
+
+    @property
+    def fitted(self) -> bool:
+        """A fit other than the stretch is declared: the pvhip_input_preprocess_*_fit_f32 entries, with ``fit_code`` as their `fit`."""
+        return self.fit != 'STRETCH'
+
+    @property
+    def fit_code(self) -> int:
+        return RESIZE_FITS[self.fit]
+
+    def fit_geometry(self, extent) -> tuple:
+        """(dx, dy, iw, ih) of a source of `extent` = (h, w) in the network's extent under the declared fit."""
+        return fit_geometry(extent, self.dims[2:], self.fit)
 
     @property
     def yuv(self) -> bool:
@@ -184,8 +216,11 @@ class InputFormat:
 
     def needs_preprocess(self, extent) -> bool:
         """Arrays of `extent` go through pvhip_input_preprocess_f32 (YUV 4:2:0 frames: pvhip_input_preprocess_yuv_f32, frames of 4-byte
-        units: pvhip_input_preprocess_packed_f32, always): something besides the format change is in effect."""
-        return tuple(extent) != tuple(self.dims[2:]) or self.reverse or self.mean is not None or self.yuv or self.packed
+        units: pvhip_input_preprocess_packed_f32, always): something besides the format change is in effect -- a declared fit that
+        leaves padding among it."""
+        h, w = self.dims[2:]
+        return (tuple(extent) != (h, w) or self.reverse or self.mean is not None or self.yuv or self.packed
+                or (self.fitted and self.fit_geometry(extent) != (0, 0, w, h)))
 
     def needs_convert(self, extent) -> bool:
         """Arrays of `extent` are not the fp32 NCHW tensor itself: they are uploaded into a staging tensor and converted by one launch."""
@@ -226,14 +261,19 @@ class DetectedRois:
     of them, in the order (image, position), become batch rows 0..count-1; the other rows are quiet NaN.  The table is made on the device
     (pvhip_detections_to_rois; the rule in numpy: tests/detected_rois_ref.py); ``InferRequest.detected_rois(name)`` reads it back.
 
+    A detector whose input declares a fit (``preprocess_info.resize_fit``) saw the frame in a rectangle of its input: its corners are
+    mapped back first (pvhip_detections_to_rois_fit).  For a detector request the geometry is that of the pass it was last fed; for
+    records given as a tensor or an array it is `detector_fit` = (Hn, Wn, dx, dy, iw, ih), the detector's input extent and
+    ``InputFormat.fit_geometry`` of the frames it was fed (None: no fit).
+
     The detector may be started again as soon as ``start_async`` of this input has returned: its next pass waits, on the device, until
     the table has been made.  ``detector.wait()`` may come before or after that ``start_async``."""
-    __slots__ = ('frames', 'detections', 'output', 'images', 'min_confidence', 'labels', 'min_size')
+    __slots__ = ('frames', 'detections', 'output', 'images', 'min_confidence', 'labels', 'min_size', 'detector_fit')
     MAX_LABELS = 64
 
-    def __init__(self, frames, detections, output=None, images=None, min_confidence=0.5, labels=None, min_size=(1, 1)):
+    def __init__(self, frames, detections, output=None, images=None, min_confidence=0.5, labels=None, min_size=(1, 1), detector_fit=None):
         self.frames, self.detections, self.output, self.images = frames, detections, output, images
-        self.min_confidence, self.labels, self.min_size = min_confidence, labels, min_size
+        self.min_confidence, self.labels, self.min_size, self.detector_fit = min_confidence, labels, min_size, detector_fit
 
     def __repr__(self):
         return 'DetectedRois(frames={}, detections={})'.format(getattr(self.frames, 'shape', None), type(self.detections).__name__)
@@ -372,7 +412,7 @@ class InputInfo:
         color = pre.color_format if pre is not None else 'RAW'
         return InputFormat(self.name, self.dims, self.supported(), self.declared, self._precision == 'U8' or color != 'RAW', self._layout == 'NHWC',
                            pre is not None and pre.resize_algorithm == 'RESIZE_BILINEAR', pre is not None and pre.reverse_channels, mean, std,
-                           color)
+                           color, pre.resize_fit if pre is not None else 'STRETCH', pre.pad_value if pre is not None else 0.0)
 
     def preprocessing(self):
         """(resize, reverse_channels, (mean, std_scale) or None) as declared; (False, False, None) when nothing is."""
@@ -384,6 +424,9 @@ class InputInfo:
         if pre is not None and pre.mean_variant == 'MEAN_VALUE' and len(pre._channels) != self.dims[1]:
             raise ValueError('input {}: mean_variant MEAN_VALUE with {} channels (preprocess_info.init), the input has {}'.format(
                 self.name, len(pre._channels), self.dims[1]))
+        if pre is not None and pre.resize_fit != 'STRETCH' and pre.resize_algorithm != 'RESIZE_BILINEAR':
+            raise ValueError('input {}: resize_fit {} places a resized source: it needs preprocess_info.resize_algorithm = '
+                             '\'RESIZE_BILINEAR\''.format(self.name, pre.resize_fit))
         if pre is not None and pre.color_format != 'RAW':
             if self.dims[1] != 3:
                 raise ValueError('input {}: color_format {} converts to 3 channels (B, G, R), the input has {}'.format(
@@ -443,6 +486,12 @@ class PreProcessInfo:
       * ``resize_algorithm``: 'NO_RESIZE' (default) or 'RESIZE_BILINEAR' -- a source of any (h, w) is resized to the Parameter's extent
         (half-pixel centres, clamped at the border, as cv2 INTER_LINEAR; no antialiasing, so large downscales alias); a source at the
         network's own extent is not resized at all;
+      * ``resize_fit``: 'STRETCH' (default: the source is stretched onto the whole extent whatever its shape) or 'LETTERBOX' /
+        'TOP_LEFT' (OpenVINO Model API's ``fit_to_window_letterbox`` / ``fit_to_window``): the source is scaled by ONE factor into the
+        rectangle (dx, dy, iw, ih) of ``InputFormat.fit_geometry`` -- integers only: the long side full, the short side rounded half up,
+        centred (floor) for LETTERBOX, at the origin for TOP_LEFT -- by the same bilinear rule onto (ih, iw), and the rest of the extent
+        is ``pad_value`` (one finite fp32 number in source units, default 0; it goes through mean / scale like a pixel).  Needs
+        RESIZE_BILINEAR.  ``infer(..., detections=)`` and ``DetectedRois`` map a fitted detector's boxes back to the frame;
       * ``reverse_channels``: output channel c takes source channel C-1-c (a BGR frame into an RGB-trained IR);
       * ``mean_variant``: 'NONE' (default) or 'MEAN_VALUE': y = (v - self[c].mean_value) / self[c].std_scale, after ``init(C)``;
       * ``color_format``: 'RAW' (default: the array holds the channels themselves) or 'NV12' / 'I420': the array holds YUV 4:2:0 frames as a
@@ -469,10 +518,12 @@ class PreProcessInfo:
     RESIZE_ALGORITHMS = ('NO_RESIZE', 'RESIZE_BILINEAR')
     MEAN_VARIANTS = ('NONE', 'MEAN_VALUE')
     COLOR_FORMATS = ('RAW', 'NV12', 'I420', 'YUY2', 'UYVY', 'BGRX', 'RGBX')
+    RESIZE_FITS = tuple(RESIZE_FITS)
 
     def __init__(self, info):
         self._info = info
         self._resize, self._mean_variant, self._reverse, self._color = 'NO_RESIZE', 'NONE', False, 'RAW'
+        self._fit, self._pad = 'STRETCH', 0.0
         self._channels = []
 
     @property
@@ -482,6 +533,24 @@ class PreProcessInfo:
     @resize_algorithm.setter
     def resize_algorithm(self, value):
         self._resize = self._info._checked('preprocess_info.resize_algorithm', value, self.RESIZE_ALGORITHMS)
+
+    @property
+    def resize_fit(self):
+        return self._fit
+
+    @resize_fit.setter
+    def resize_fit(self, value):
+        self._fit = self._info._checked('preprocess_info.resize_fit', value, self.RESIZE_FITS)
+
+    @property
+    def pad_value(self):
+        return self._pad
+
+    @pad_value.setter
+    def pad_value(self, value):
+        value = self._number('pad_value', value)
+        self._info._declare('preprocess_info.pad_value')
+        self._pad = value
 
     @property
     def mean_variant(self):
