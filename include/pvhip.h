@@ -616,6 +616,34 @@ int pvhip_detections_compact_fit(const float* records, int images, int records_p
 int pvhip_detections_merge_tiles(const float* records, const int* tiles, int n, int records_per_tile, int frames, float min_confidence,
                                  const int* labels, int num_labels, int min_h, int min_w, int max_per_tile, int overlap, float threshold,
                                  int per_label, int max_per_frame, int* scratch, int* header, int* rows);
+/* Addition to ABI v18 (the version number is unchanged: nothing existing changed): the answer of a detector whose batch rows are REGIONS
+ * of m frames -- of any aspect, placed in its (net_h, net_w) input by the fit the preprocessing launch used (pvhip_input_preprocess_fit_f32
+ * with the same table) --: a second-stage detector behind a first one (person -> face, vehicle -> plate), or tiles that are not the
+ * network's aspect.  `regions` is the (n, 5) int32 device table, row b = (f, x, y, w, h): a RoiInput's table, or the one
+ * pvhip_detections_to_rois wrote, whose rows from `count` on are (-1, 0, 0, 0, 0).  `fit`: 0 STRETCH, 1 LETTERBOX, 2 TOP_LEFT.
+ *   1. candidates  region b contributes nothing if f is outside [0, m), or w or h is outside [1, 2^24].  Otherwise (dx, dy, iw, ih) is the
+ *      fitted rectangle of a source of (hs, ws) = (h, w) in (hd, wd) = (net_h, net_w) by the integer rule stated at
+ *      pvhip_input_preprocess_fit_f32 (one function serves the launch that places the pixels and this one), and the region's candidates are
+ *      exactly the records pvhip_detections_compact_fit selects over (frame_h, frame_w) = (h, w) with (net_h, net_w, dx, dy, iw, ih): a
+ *      record is live in front of the list end; score >= min_confidence; the finite check is on the record's own four corners; the label
+ *      filter; each corner is mapped back in fp32, never contracted, three roundings, u = (xmin * (float)net_w - (float)dx) / (float)iw
+ *      (ymin / ymax with net_h, dy, ih); the rectangle is floor / ceil of the clamped fp32 products of u with the region's extent, subject
+ *      to (min_h, min_w).  A box in the padding therefore clamps to the region's edge and one wholly in the padding is dropped.  With fit 0
+ *      no mapping is applied at all (net_h and net_w are not read): the answer is pvhip_detections_merge_tiles' bit for bit.  The frame
+ *      rectangle is (x + x0, y + y0, w, h) (the sums wrap as int32 do).  A region keeps its first max_per_region candidates in position
+ *      order.  selected[f] = the kept candidates of all regions of frame f.
+ *   2. - 4. order, suppression, cap and table: those of pvhip_detections_merge_tiles unchanged -- descending score, ties to the lower flat
+ *      record; greedy, int64 areas, (double)inter > (double)threshold * (double)den, equality does not suppress; max_per_frame; rows
+ *      (f, x0, y0, w, h, label, score bits, record), the region of a row is record / P.  For a table pvhip_detections_to_rois wrote,
+ *      record_of[record / P] there is the first-stage record the box came from.
+ * header, `rows` and `scratch` (9 * n * max_per_region + n ints) as for pvhip_detections_merge_tiles.  The same rule in numpy:
+ * tests/regions_ref.py, matched word for word.  Three launches on the current stream (the candidates launch computes each region's geometry
+ * once per wave; the frames and write launches are pvhip_detections_merge_tiles' own), no allocation, no atomics, no wait of one workgroup
+ * on another.  The limits of pvhip_detections_merge_tiles, fit in {0, 1, 2}, and net_h, net_w in [1, 2^24] when fit != 0; else PVHIP_EINVAL
+ * and nothing is launched. */
+int pvhip_detections_merge_regions(const float* records, const int* regions, int n, int records_per_region, int frames, float min_confidence,
+                                   const int* labels, int num_labels, int min_h, int min_w, int max_per_region, int overlap, float threshold,
+                                   int per_label, int max_per_frame, int net_h, int net_w, int fit, int* scratch, int* header, int* rows);
 
 /* ---------------------------------------------------------------- multi-GPU gather ---------- */
 /* No reference counterpart (the reference is single-process).  Batch shards are independent; the only

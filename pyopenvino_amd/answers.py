@@ -4,8 +4,8 @@ is on the way in: the request checks the arguments, binds the asks to the staged
 A plain screen over a detector whose input declares a fit (preprocess_info.resize_fit) learns its geometry in bound(), from the extent
 of the frames the pass was fed.
 
-An ask is one Result's question in its resolved form -- top_k.Ask, detections.Ask / FittedAsk or tiled_detections.Ask, each with `bound`, `key`,
-`launch` and `on_host` --; which kind it is matters only where checked() makes it."""
+An ask is one Result's question in its resolved form -- top_k.Ask, detections.Ask / FittedAsk or tiled_detections.Ask / RegionAsk, each with
+`bound`, `key`, `launch` and `on_host` --; which kind it is matters only where checked() makes it."""
 import numpy as np
 
 from . import detections as detections_rule, device, tiled_detections as tiled_rule, top_k as top_k_rule
@@ -14,7 +14,7 @@ from .input_format import DetectedRois, RoiInput
 
 class Answers:
     """`blocks` = {ask.key(Result name): its Blocks}, this request's own device and page-locked blocks, made on first use: (name, k),
-    (name, resolved DetectionScreen) or (name, resolved TiledScreen, m)."""
+    (name, resolved DetectionScreen) or (name, resolved TiledScreen or RegionScreen, m)."""
 
     def __init__(self, runner):
         self.runner, self.blocks = runner, {}       # runner: the Executable_Network whose base stream and Results these are
@@ -40,8 +40,9 @@ class Answers:
             if s.input in formats and formats[s.input].fitted:
                 raise ValueError('detections: Result {!r}: a TiledScreen over input {!r}, which declares resize_fit {}'.format(
                     name, s.input, formats[s.input].fit))
-        tiled_rule.checked_feed(inputs, tiled)
-        fitted = self._fitted_input() if len(screens) > len(tiled) else None
+        regions = {name: s for name, s in screens.items() if isinstance(s, tiled_rule.RegionScreen)}     # (any declared fit: a geometry per row)
+        tiled_rule.checked_feed(inputs, {**tiled, **regions})
+        fitted = self._fitted_input() if len(screens) > len(tiled) + len(regions) else None
         if fitted is not None and isinstance(inputs, dict) and isinstance(inputs.get(fitted), (RoiInput, DetectedRois)):
             raise ValueError('detections: input {!r} declares resize_fit {} and is fed a {}: every row has a geometry of its own'.format(
                 fitted, formats[fitted].fit, type(inputs[fitted]).__name__))
@@ -50,6 +51,8 @@ class Answers:
         for name, s in screens.items():
             if name in tiled:
                 asks[name] = tiled_rule.Ask(s, n, None, None)
+            elif name in regions:
+                asks[name] = self._region_ask(s, n)
             elif fitted is None:
                 asks[name] = detections_rule.Ask(s, n)
             else:
@@ -57,6 +60,12 @@ class Answers:
                 explicit = isinstance(given, detections_rule.DetectionScreen) and given.frame_size is not None
                 asks[name] = detections_rule.FittedAsk(s, n, fitted, formats[fitted], explicit, None)
         return asks
+
+    def _region_ask(self, screen, n):
+        """The ask of a resolved RegionScreen: the extent and the declared fit of its input, and how the table of a DetectedRois is read."""
+        ex, fmt = self.runner, self.runner.host_inputs.formats[screen.input]
+        return tiled_rule.RegionAsk(screen, n, None, None, (int(fmt.dims[2]), int(fmt.dims[3])), fmt.fit,
+                                    lambda: ex.host_inputs.detected_rois(screen.input, ex.stream_base), None)
 
     def _fitted_input(self):
         """The name of the network's single 4-D Parameter when its format declares a fit, else None."""

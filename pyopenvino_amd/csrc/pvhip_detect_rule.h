@@ -1,8 +1,8 @@
 // The screen and the rectangle of one live DetectionOutput record: the one place where pvhip_detections_to_rois and
 // pvhip_detections_compact (include/pvhip.h states the rule of both) decide whether a record survives and what its rectangle is.
 // Whether a record is live -- in front of its image's first row whose column 0 is not >= 0 -- is the caller's business: the
-// kernels find the list end in different ways.  walk_image below is the wave-per-image way of pvhip_detections_compact and
-// pvhip_detections_merge_tiles.
+// kernels find the list end in different ways.  walk_image below is the wave-per-image way of pvhip_detections_compact,
+// pvhip_detections_merge_tiles and pvhip_detections_merge_regions.
 #pragma once
 
 #include "pvhip_common.h"

@@ -39,6 +39,7 @@
 // not change).  The tiles are sized by a bound on the taps' step over every rectangle the launch may meet (Reach), and a workgroup whose
 // tile would still not fit its slots writes NaN instead of staging.  tests/letterbox_ref.py is the rule in numpy.
 #include "pvhip_common.h"
+#include "pvhip_fit_rect.h"
 
 #pragma clang fp contract(off)
 
@@ -91,28 +92,6 @@ struct TileArgs {
     int fit;                  // FIT kernels: 1 LETTERBOX (the fitted rectangle is centred), 2 TOP_LEFT
     float pad;                // ... the value outside the fitted rectangle, in source units (it goes through mean / scale)
 };
-
-// The fitted rectangle of a source (or ROI rectangle) of (hs, ws) in a destination of (hd, wd): one scale factor for both axes, the short
-// side rounded half up and kept in [1, D]; integers only (include/pvhip.h states the rule, tests/letterbox_ref.py is the same in numpy).
-struct FitRect {
-    int dx, dy, iw, ih;
-};
-
-__host__ __device__ inline FitRect fit_rect(int hs, int ws, int hd, int wd, int fit) {
-    long long iw = wd, ih = hd;
-    if ((long long)ws * hd >= (long long)hs * wd) {
-        ih = (2LL * hs * wd + ws) / (2LL * ws);
-        ih = ih < 1 ? 1 : (ih > hd ? hd : ih);
-    } else {
-        iw = (2LL * ws * hd + hs) / (2LL * hs);
-        iw = iw < 1 ? 1 : (iw > wd ? wd : iw);
-    }
-    FitRect r;
-    r.iw = (int)iw; r.ih = (int)ih;
-    r.dx = fit == 1 ? (wd - r.iw) / 2 : 0;
-    r.dy = fit == 1 ? (hd - r.ih) / 2 : 0;
-    return r;
-}
 
 // The tile of one workgroup: columns tx0.. (twv of them) of rows ty0.. (thv of them) of image n, whose taps see a source of hs x ws
 // pixels: the whole of source image img = n, or (ROI kernels) the rectangle at column ox, row oy of frame img.

@@ -4,6 +4,12 @@
 // (pvhip_detections_merge_tiles), tests/tiles_ref.py is the same in numpy; the screen and the rectangle are pvhip_detect_rule.h's, the
 // walk over a tile's records is pvhip_detections_compact's.
 //
+// pvhip_detections_merge_regions is the same answer for batch rows that are REGIONS of any aspect -- a RoiInput's table or the table
+// pvhip_detections_to_rois left on the device -- placed in the detector's input by an aspect-preserving fit: the candidates kernel is a
+// template on FIT, each wave computes its region's fitted rectangle once (fit_rect, pvhip_fit_rect.h: the function the preprocessing launch
+// placed the pixels with) and walks its records with it (walk_image<true>: every corner mapped back before the rectangle rule).  The
+// frames and write kernels do not know the difference.
+//
 // Three launches on one stream, at most kMaxCandidates = 4096 candidates in all:
 //   tiles   one wave per tile (walk_image): candidate `rank` < max_per_tile of tile b becomes row b max_per_tile + rank of the scratch,
 //           already in its final form (f, x + x0, y + y0, w, h, label, score bits, record); taken[b] counts them.  A tile whose frame is
@@ -26,6 +32,7 @@
 // records and the table alone.
 #include "pvhip_common.h"
 #include "pvhip_detect_rule.h"
+#include "pvhip_fit_rect.h"
 
 using namespace pvhip;
 
@@ -51,7 +58,15 @@ struct MergeArgs {
     float threshold;
 };
 
-__global__ __launch_bounds__(kBlock) void tiles_candidates_kernel(MergeArgs a) {
+// The detector's input extent and how a region was placed in it (1 LETTERBOX, 2 TOP_LEFT).
+struct FitNet {
+    int net_h, net_w, fit;
+};
+
+// FIT: launched with one FitNet behind the MergeArgs; without it the kernel's arguments -- and its code -- are what the tiles entry always
+// launched.
+template <bool FIT, typename... Net>
+__global__ __launch_bounds__(kBlock) void tiles_candidates_kernel(MergeArgs a, Net... net) {
     const int b = blockIdx.x * kTilesPerBlock + (threadIdx.x >> 6);
     if (b >= a.n) return;                                                       // (the whole wave: nothing below meets a barrier)
     const int* t = a.tiles + 5 * (size_t)b;
@@ -59,11 +74,17 @@ __global__ __launch_bounds__(kBlock) void tiles_candidates_kernel(MergeArgs a) {
     int taken = 0;
     if (f >= 0 && f < a.m && w >= 1 && w <= kMaxExtent && h >= 1 && h <= kMaxExtent) {
         int4* out = a.cand + 2 * (size_t)b * a.per_tile;
-        const int seen = walk_image(a.walk, b, h, w, a.per_tile, [&](int rank, int r, const DetectionRect& rect, const float* q) {
+        DetectionFit g{};
+        if constexpr (FIT) {                                                    // (wave-uniform: once per region)
+            const FitNet  q = (net, ...);
+            const FitRect p = fit_rect(h, w, q.net_h, q.net_w, q.fit);
+            g = DetectionFit{q.net_h, q.net_w, p.dx, p.dy, p.iw, p.ih};
+        }
+        const int seen = walk_image<FIT>(a.walk, b, h, w, a.per_tile, [&](int rank, int r, const DetectionRect& rect, const float* q) {
             // (a frame rectangle wraps like an int32 sum where the table is no RoiInput's: defined, and the rule's)
             out[2 * rank + 0] = make_int4(f, (int)((unsigned)x + (unsigned)rect.x0), (int)((unsigned)y + (unsigned)rect.y0), rect.w);
             out[2 * rank + 1] = make_int4(rect.h, detection_label(q[1]), (int)__float_as_uint(q[2]), r);
-        });
+        }, g);
         taken = min(seen, a.per_tile);
     }
     if ((threadIdx.x & (kWave - 1)) == 0) a.taken[b] = taken;
@@ -265,11 +286,10 @@ __global__ __launch_bounds__(kBlock) void tiles_write_kernel(MergeArgs a) {
 
 }  // namespace
 
-extern "C" {
-
-int pvhip_detections_merge_tiles(const float* records, const int* tiles, int n, int records_per_tile, int frames, float min_confidence,
-                                 const int* labels, int num_labels, int min_h, int min_w, int max_per_tile, int overlap, float threshold,
-                                 int per_label, int max_per_frame, int* scratch, int* header, int* rows) {
+// The argument checks and the three launches of both entries; fit 0: no mapping at all (net_h, net_w unused).
+static int pvhip_detections_merge(const float* records, const int* tiles, int n, int records_per_tile, int frames, float min_confidence, const int* labels,
+                                 int num_labels, int min_h, int min_w, int max_per_tile, int overlap, float threshold, int per_label,
+                                 int max_per_frame, int net_h, int net_w, int fit, int* scratch, int* header, int* rows) {
     PVHIP_REQUIRE_INIT();
     PVHIP_CHECK_ARG(records != nullptr && tiles != nullptr && scratch != nullptr && header != nullptr && rows != nullptr);
     PVHIP_CHECK_ARG(((uintptr_t)rows & 15u) == 0 && ((uintptr_t)scratch & 15u) == 0);
@@ -282,6 +302,8 @@ int pvhip_detections_merge_tiles(const float* records, const int* tiles, int n, 
     PVHIP_CHECK_ARG(overlap == PVHIP_OVERLAP_IOU || overlap == PVHIP_OVERLAP_IOS);
     PVHIP_CHECK_ARG(threshold >= 0.0f && threshold <= 1.0f);                    // (false for NaN)
     PVHIP_CHECK_ARG(per_label == 0 || per_label == 1);
+    PVHIP_CHECK_ARG(fit >= 0 && fit <= 2);
+    PVHIP_CHECK_ARG(fit == 0 || (net_h >= 1 && net_h <= kMaxExtent && net_w >= 1 && net_w <= kMaxExtent));
     MergeArgs a;
     a.walk  = ScreenWalk{records, labels, records_per_tile, num_labels, min_h, min_w, min_confidence};
     a.tiles = tiles;
@@ -295,11 +317,28 @@ int pvhip_detections_merge_tiles(const float* records, const int* tiles, int n, 
     a.sort_n = 1;
     while (a.sort_n < a.slots) a.sort_n <<= 1;
     const dim3 tile_grid((n + kTilesPerBlock - 1) / kTilesPerBlock);
-    hipLaunchKernelGGL(tiles_candidates_kernel, tile_grid, dim3(kBlock), 0, state().stream, a);
+    if (fit != 0) hipLaunchKernelGGL((tiles_candidates_kernel<true, FitNet>), tile_grid, dim3(kBlock), 0, state().stream, a, FitNet{net_h, net_w, fit});
+    else          hipLaunchKernelGGL(tiles_candidates_kernel<false>, tile_grid, dim3(kBlock), 0, state().stream, a);
     hipLaunchKernelGGL(tiles_frames_kernel, dim3(frames), dim3(kFrameBlock), 0, state().stream, a);
     hipLaunchKernelGGL(tiles_write_kernel, tile_grid, dim3(kBlock), 0, state().stream, a);
     PVHIP_LAUNCH_CHECK();
     return PVHIP_OK;
+}
+
+extern "C" {
+
+int pvhip_detections_merge_tiles(const float* records, const int* tiles, int n, int records_per_tile, int frames, float min_confidence,
+                                 const int* labels, int num_labels, int min_h, int min_w, int max_per_tile, int overlap, float threshold,
+                                 int per_label, int max_per_frame, int* scratch, int* header, int* rows) {
+    return pvhip_detections_merge(records, tiles, n, records_per_tile, frames, min_confidence, labels, num_labels, min_h, min_w, max_per_tile,
+                                  overlap, threshold, per_label, max_per_frame, 0, 0, 0, scratch, header, rows);
+}
+
+int pvhip_detections_merge_regions(const float* records, const int* regions, int n, int records_per_region, int frames, float min_confidence,
+                                   const int* labels, int num_labels, int min_h, int min_w, int max_per_region, int overlap, float threshold,
+                                   int per_label, int max_per_frame, int net_h, int net_w, int fit, int* scratch, int* header, int* rows) {
+    return pvhip_detections_merge(records, regions, n, records_per_region, frames, min_confidence, labels, num_labels, min_h, min_w,
+                                  max_per_region, overlap, threshold, per_label, max_per_frame, net_h, net_w, fit, scratch, header, rows);
 }
 
 }  // extern "C"

@@ -156,6 +156,8 @@ SIGNATURES = {
                                      [_c.c_int] * 6),
     'pvhip_detections_merge_tiles': (_c.c_int, [_c.c_void_p] * 2 + [_c.c_int] * 3 + [_c.c_float, _c.c_void_p] + [_c.c_int] * 5 + [_c.c_float] +
                                      [_c.c_int] * 2 + [_c.c_void_p] * 3),
+    'pvhip_detections_merge_regions': (_c.c_int, [_c.c_void_p] * 2 + [_c.c_int] * 3 + [_c.c_float, _c.c_void_p] + [_c.c_int] * 5 + [_c.c_float] +
+                                       [_c.c_int] * 5 + [_c.c_void_p] * 3),
     'pvhip_comm_unique_id': (_c.c_int, [_c.c_void_p]),
     'pvhip_comm_init': (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int]),
     'pvhip_comm_allgather_f32': (_c.c_int, [_fp, _fp, _c.c_size_t]),

@@ -321,6 +321,11 @@ class InferRequest:
     suppressed across the tiles of a frame by the rule of tiled_detections.py --, made by pvhip_detections_merge_tiles behind the pass with
     the tile table stage() uploaded, and read back in the same two copies, 4 (2 m + 1) bytes and 32 bytes per row.  ValueError before
     anything is staged or launched, besides the above: that input fed anything but a RoiInput, more than 4096 candidates.
+    A ``RegionScreen`` in that place, for batch rows that are regions of any aspect: the input may be fed a RoiInput or a
+    ``DetectedRois`` -- a second-stage detector behind a first one, the table never leaving the device -- and may declare any resize_fit;
+    every region's corners are mapped back through the geometry its own pixels were placed with (pvhip_detections_merge_regions, the
+    rule of tiled_detections.py) and the answer is the same Detections over frames, ``detected_rois(name).records[records // P]`` being the
+    first-stage record of each box.  ValueError as for a TiledScreen: that input fed anything but a RoiInput or a DetectedRois.
     `top_k` and `detections` may be given together, for different Results."""
 
     def __init__(self, owner, runner, index: int):
