@@ -271,11 +271,18 @@ __device__ __forceinline__ void lds_dma_b32(__amdgpu_buffer_rsrc_t r, float* dst
                  :: "s"(lds), "v"(voff), "s"(r), "s"(soff) : "memory");
 #endif
 }
+// NT: nontemporal, for data that is read once (the pooling / depthwise streams: 6.0-6.4 TB/s against 5.1-5.4 plain with 16-byte nt
+// loads and stores, profiles/r03_stream_sweep.md)
+template <bool NT = false>
 __device__ __forceinline__ void lds_dma_b128(__amdgpu_buffer_rsrc_t r, float* dst, unsigned voff, unsigned soff) {
 #if defined(__HIP_DEVICE_COMPILE__)
     const unsigned lds = (unsigned)(unsigned long)(lds_void_p)dst;
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
-                 :: "s"(lds), "v"(voff), "s"(r), "s"(soff) : "memory");
+    if (NT)
+        asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen nt lds"
+                     :: "s"(lds), "v"(voff), "s"(r), "s"(soff) : "memory");
+    else
+        asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
+                     :: "s"(lds), "v"(voff), "s"(r), "s"(soff) : "memory");
 #endif
 }
 __device__ __forceinline__ void lds_dma_wait_all() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }

@@ -21,7 +21,6 @@ using namespace pvhip;
 namespace {
 
 typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
 constexpr int kBK = 16;
 constexpr int kRingDepth1 = 2;          // ... for single pixels (odd rows: the 7x7 modules, only with PVHIP_FUSE_POOLCONV=1: 0.080 ms against 0.067 for the two launches; 0.089 with one stage)
@@ -43,14 +42,6 @@ struct PoolConvArgs {
     int prio;             // producers at wave priority 3 (PVHIP_POOLCONV_PRIO=0: everything at 0)
     int abl;              // diagnostic build (PVHIP_CONV_ABLATE bits, wrong results): 1 no activation loads, 2 no pooling arithmetic, 4 no MFMAs, 8 no weight copies, 16 no stores, 32 no loads of the outer columns, 64 s_memtime stamps (pvhip_diag_poolconv_stamps)
 };
-
-__device__ __forceinline__ void pc_dma_b128(__amdgpu_buffer_rsrc_t r, float* dst, unsigned voff, unsigned soff) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    const unsigned lds = (unsigned)(unsigned long)(lds_ptr_t)dst;
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
-                 :: "s"(lds), "v"(voff), "s"(r), "s"(soff) : "memory");
-#endif
-}
 
 typedef float pc_f4 __attribute__((ext_vector_type(4)));
 typedef float pc_f2 __attribute__((ext_vector_type(2)));
@@ -257,7 +248,7 @@ __global__ __launch_bounds__(NW * 128, (BM <= 64 && VEC == 1) || (BM <= 64 && VE
 #define PVP_LOAD_A(s_, buf_)                                                                                     \
     _Pragma("unroll") for (int q = 0; q < A_PER_WAVE; ++q)                                                       \
         if (A_PIECES % CONSUMERS == 0 || wid + CONSUMERS * q < A_PIECES)                                         \
-            if (!(abl & 8)) pc_dma_b128(wr, &As[buf_][0][0] + (wid + CONSUMERS * q) * 256, avoff[q], (unsigned)(s_) * a_stage_bytes);
+            if (!(abl & 8)) lds_dma_b128(wr, &As[buf_][0][0] + (wid + CONSUMERS * q) * 256, avoff[q], (unsigned)(s_) * a_stage_bytes);
 #pragma unroll
         for (int i = 0; i < TM; ++i)
 #pragma unroll
