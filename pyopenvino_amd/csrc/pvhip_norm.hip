@@ -1,4 +1,10 @@
-// SoftMax (row-wise, wave-shuffle reductions) and cross-channel LRN (register sliding window).
+// SoftMax (row-wise, wave-shuffle reductions), cross-channel LRN (register sliding window), and the launches that fuse LRN with a 3x3
+// MaxPool: LRN -> MaxPool, MaxPool -> LRN and MaxPool -> LRN -> 1x1 convolution.  The fused kernels are assembled from parts that exist
+// once: the band of a workgroup (LrnBand), the pooling geometry of an owned output (PoolTap, pool3x3_from_lds), the LRN arithmetic
+// (lrn_value, ChannelWindow) and the raw-plane walk of the MaxPool-first kernels (pooled_lrn_walk); on the host, one plan
+// (plan_lrn_pool) that says what will be launched.
+#include <type_traits>
+
 #include "pvhip_common.h"
 
 using namespace pvhip;
@@ -63,41 +69,67 @@ __global__ __launch_bounds__(kBlock) void softmax_rows_kernel(const float* __res
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// The LRN arithmetic, ONCE: the squares of window[0 .. SIZE) summed in ascending channel order, the order np.sum(axis=1) uses
+// (LRN.py:19), then centre / (bias + alpha * sum)^beta.  Every kernel below -- the plain one and the three fused ones -- calls this, on
+// one float or on the VEC pixels of a lane: that is what makes every fused form carry the bits of the separate launches.
+template <int VEC>
+using lrn_vec = float __attribute__((ext_vector_type(VEC)));
+constexpr int kLrnT = 8;      // channels per chunk of the channel walks (C must be a multiple)
+
+template <int SIZE, int BETA_MODE, class V>
+__device__ __forceinline__ V lrn_value(const V* window, V centre, float alpha, float beta, float bias) {
+    V s = window[0] * window[0];
+#pragma unroll
+    for (int q = 1; q < SIZE; ++q) s = s + window[q] * window[q];
+    if constexpr (std::is_same<V, float>::value) {
+        return lrn_div(centre, bias + alpha * s, beta, BETA_MODE);
+    } else {
+        V o;
+#pragma unroll
+        for (int v = 0; v < (int)(sizeof(V) / sizeof(float)); ++v) o[v] = lrn_div(centre[v], bias + alpha * s[v], beta, BETA_MODE);
+        return o;
+    }
+}
+
+// The last SIZE values of one pixel along the channel axis (channels outside the tensor are an exact 0): after push(v) of channel ch
+// the window is centred on channel ch - SIZE / 2.
+template <int SIZE>
+struct ChannelWindow {
+    float v[SIZE];
+    __device__ __forceinline__ void clear() {
+#pragma unroll
+        for (int q = 0; q < SIZE; ++q) v[q] = 0.0f;
+    }
+    __device__ __forceinline__ void push(float x) {
+#pragma unroll
+        for (int q = 0; q + 1 < SIZE; ++q) v[q] = v[q + 1];
+        v[SIZE - 1] = x;
+    }
+};
+
 // One lane owns VEC adjacent pixels of one image and walks the channel axis in chunks of T = 8 channels
 // (C must be a multiple of 8; other channel counts take the generic kernel).  The T loads of chunk k+1 are
 // issued before the outputs that chunk k completes are computed, so T independent 16-byte loads per lane are
 // in flight; every element is read once and written once.  After chunk k has landed the computable outputs
 // are channels [T*k - HALF, T*k + T - HALF).  The loop body is branch-free: the first chunk, the last chunk and
 // the trailing HALF outputs are peeled.  Window for channel c is [c - SIZE/2, c + SIZE/2] clipped to [0, C);
-// squares are summed in ascending channel order, the order np.sum(axis=1) uses (LRN.py:19); channels outside
-// the tensor contribute an exact 0.
+// channels outside the tensor contribute an exact 0.
+// (This walk and lrn_maxpool3x3_kernel's are the same skeleton written twice: as ONE inline function with the store as a sink it cost
+// registers in both kernels, profiles/norm_refactor.md.)
 template <int SIZE, int VEC, int BETA_MODE>
 __global__ __launch_bounds__(kBlock) void lrn_window_kernel(const float* __restrict__ x, float* __restrict__ y, int n,
                                                              int c, int hw, float alpha, float beta, float bias) {
-    constexpr int beta_mode = BETA_MODE;   // compile-time: keeps the per-element path branch-free
     constexpr int HALF = SIZE / 2;
-    constexpr int T    = 8;
+    constexpr int T    = kLrnT;
     constexpr int E    = 2 * HALF + T;      // ext[]: channels [T*k - 2*HALF, T*k + T)
     static_assert(2 * HALF <= T, "window halo must fit in one chunk");
-    typedef float vec_t __attribute__((ext_vector_type(VEC)));
+    typedef lrn_vec<VEC> vec_t;
     const int      cols_per_img = hw / VEC;
     const unsigned total        = (unsigned)n * (unsigned)cols_per_img;
     const unsigned stride       = gridDim.x * blockDim.x;
     const int      n_chunks     = c / T;
     const size_t   cstride      = (size_t)hw / VEC;   // channel stride in vec_t units
-
-    // one output: centre ext[j + HALF], window ext[j .. j + SIZE)
-#define PV_LRN_OUT(j_, ch_)                                                                    \
-    {                                                                                          \
-        vec_t s_ = ext[(j_)] * ext[(j_)];                                                      \
-        _Pragma("unroll") for (int q = 1; q < SIZE; ++q) s_ = s_ + ext[(j_) + q] * ext[(j_) + q]; \
-        vec_t o_;                                                                              \
-        _Pragma("unroll") for (int v = 0; v < VEC; ++v) {                                      \
-            const float d_ = bias + alpha * s_[v];                                             \
-            o_[v]          = lrn_div(ext[(j_) + HALF][v], d_, beta, beta_mode);                \
-        }                                                                                      \
-        stnt(yv + (size_t)(ch_) * cstride, o_);                                                      \
-    }
 
     for (unsigned t = blockIdx.x * blockDim.x + threadIdx.x; t < total; t += stride) {
         const unsigned img  = t / (unsigned)cols_per_img;
@@ -106,6 +138,9 @@ __global__ __launch_bounds__(kBlock) void lrn_window_kernel(const float* __restr
         const vec_t* __restrict__ xv = reinterpret_cast<const vec_t*>(x + base);
         vec_t* __restrict__       yv = reinterpret_cast<vec_t*>(y + base);
         vec_t ext[E], nxt[T];
+        // one output: centre ext[j + HALF], window ext[j .. j + SIZE)
+        auto norm = [&](const vec_t* w) { return lrn_value<SIZE, BETA_MODE>(w, w[HALF], alpha, beta, bias); };
+        auto put  = [&](vec_t o, int ch) { stnt(yv + (size_t)ch * cstride, o); };
 #pragma unroll
         for (int j = 0; j < 2 * HALF; ++j) ext[j] = (vec_t)(0.0f);
 #pragma unroll
@@ -117,11 +152,11 @@ __global__ __launch_bounds__(kBlock) void lrn_window_kernel(const float* __restr
             for (int j = 0; j < T; ++j) nxt[j] = ldnt(xn + (size_t)j * cstride);
             if (k == 0) {
 #pragma unroll
-                for (int j = HALF; j < T; ++j) PV_LRN_OUT(j, j - HALF)
+                for (int j = HALF; j < T; ++j) put(norm(ext + j), j - HALF);
             } else {
                 const int ch0 = k * T - HALF;
 #pragma unroll
-                for (int j = 0; j < T; ++j) PV_LRN_OUT(j, ch0 + j)
+                for (int j = 0; j < T; ++j) put(norm(ext + j), ch0 + j);
             }
 #pragma unroll
             for (int j = 0; j < 2 * HALF; ++j) ext[j] = ext[T + j];
@@ -133,34 +168,25 @@ __global__ __launch_bounds__(kBlock) void lrn_window_kernel(const float* __restr
             const int k = n_chunks - 1, ch0 = k * T - HALF;
             if (k == 0) {
 #pragma unroll
-                for (int j = HALF; j < T; ++j) PV_LRN_OUT(j, j - HALF)
+                for (int j = HALF; j < T; ++j) put(norm(ext + j), j - HALF);
             } else {
 #pragma unroll
-                for (int j = 0; j < T; ++j) PV_LRN_OUT(j, ch0 + j)
+                for (int j = 0; j < T; ++j) put(norm(ext + j), ch0 + j);
             }
 #pragma unroll
             for (int j = 0; j < 2 * HALF; ++j) ext[j] = ext[T + j];
 #pragma unroll
             for (int j = 0; j < T; ++j) ext[2 * HALF + j] = (vec_t)(0.0f);
 #pragma unroll
-            for (int j = 0; j < HALF; ++j) PV_LRN_OUT(j, c - HALF + j)
+            for (int j = 0; j < HALF; ++j) put(norm(ext + j), c - HALF + j);
         }
     }
-#undef PV_LRN_OUT
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// LRN followed by a 3x3 MaxPool (GoogLeNet's conv2/norm2 -> pool2/3x3_s2) in ONE pass over the input: the LRN
-// tensor (1.2 GB of traffic at batch 256: written once, read once) never exists.
-//
-// A workgroup owns one image and a band of pooled rows; its input band (the rows those windows touch, full width)
-// is one dense run per channel plane.  It walks the channel axis exactly like lrn_window_kernel -- one lane owns
-// VEC adjacent pixels of the band, chunks of T = 8 channels, the loads of chunk k+1 in flight while chunk k is
-// normalised, squares summed in ascending channel order -- but the normalised values of a chunk go to LDS ([T][band])
-// instead of HBM, and after a barrier the workgroup pools those T planes (9 LDS reads per output; taps outside the
-// tensor clamped onto a tap inside the same window, max(m, 0) where the window touches zero-pad cells, NaN wins: the
-// rules of maxpool3x3_cols_kernel) and stores T x band_rows x ow outputs.  The LRN arithmetic is lrn_window_kernel's,
-// so the result carries the bits of the two separate launches.
+// The fused LRN / 3x3 MaxPool kernels.  A workgroup owns one image and a band of pooled rows; its input band (the rows those windows
+// touch, full width) is one dense run per channel plane, one lane per VEC adjacent pixels of it, and a chunk of T = 8 channel planes
+// of the band lies in LDS ([T][plane_l]) while the workgroup pools out of it.
 struct LrnPoolArgs {
     const float* x;
     float*       y;
@@ -173,84 +199,143 @@ struct LrnPoolArgs {
     int   abl;                   // diagnostic build (PVHIP_CONV_ABLATE bits, wrong results): 1 no LRN arithmetic, 2 no pooling, 4 no stores, 8 loads hit L2
 };
 
+// What a workgroup and a lane own of the input: the band prologue of the three fused kernels.
+struct LrnBand {
+    int    img;                  // the image
+    int    oy0, rows_t;          // first pooled row of the band, pooled rows in it (the last band may be short)
+    int    iy_lo;                // first input row of the band
+    int    hw, ohw;
+    int    out_pp;               // pooled outputs per plane and full band
+    bool   active;               // this lane owns VEC pixels of the input band
+    size_t cstride;              // channel stride of the input in units of VEC floats
+    const float* x0;             // the lane's pixels in channel 0 of the image
+    float* mine;                 // ... and their place in LDS plane 0
+};
+
+template <int ST, int VEC>
+__device__ __forceinline__ LrnBand lrn_band(const LrnPoolArgs& a, const FastDiv& d_bands, float* planes) {
+    LrnBand b;
+    const int tid = threadIdx.x;
+    b.img = (int)fdiv(blockIdx.x, d_bands);
+    const int band = (int)blockIdx.x - b.img * a.n_bands;
+    b.oy0 = band * a.band_rows;
+    const int oy1 = min(a.oh, b.oy0 + a.band_rows);
+    b.rows_t = oy1 - b.oy0;
+    b.iy_lo  = max(0, b.oy0 * ST - a.pt);
+    const int iy_hi   = min(a.h, (oy1 - 1) * ST + 3 - a.pt);
+    const int band_px = (iy_hi - b.iy_lo) * a.w;
+    b.hw = a.h * a.w, b.ohw = a.oh * a.ow;
+    b.active  = tid * VEC < band_px;
+    b.cstride = (size_t)b.hw / VEC;
+    b.x0      = a.x + (size_t)b.img * a.c * b.hw + (size_t)b.iy_lo * a.w + (b.active ? tid * VEC : 0);
+    b.mine    = planes + tid * VEC;
+    b.out_pp  = a.band_rows * a.ow;
+    return b;
+}
+
+// Pooling geometry of ONE owned output, computed ONCE per lane: a lane owns the same output pixels of the band in every plane of every
+// chunk (the first version redid two divisions, six clamps and the pad tests per output, plane and chunk: ~60 vector instructions per
+// output against ~15 of LRN arithmetic per four inputs -- the kernel ran at 3.6 TB/s, VALU-bound).  Nine LDS byte offsets (taps outside
+// the tensor clamped onto a tap inside the same window), the output offset in its plane, and whether the window touches zero-pad cells
+// (then max(m, 0)).  rem: the output's index in the band.
+struct PoolTap {
+    unsigned tap[9];
+    unsigned outo;
+    bool     live, zpad;
+};
+// The NI owned outputs of a lane, field by field, each filled from the PoolTap that pool_tap() returns.  lrn_maxpool3x3_kernel, whose
+// pooling lambdas capture this struct, copies the fields in its own body instead of calling set(): any function that is handed the
+// captured struct to fill took up to twelve registers more there (164 against 155 in <5, 4, 4, 2, 1>; profiles/norm_refactor.md).
+template <int NI>
+struct PoolTaps {
+    unsigned tap[NI][9];
+    unsigned outo[NI];
+    bool     live[NI], zpad[NI];
+    __device__ __forceinline__ void set(int i, const PoolTap& o) {
+#pragma unroll
+        for (int q = 0; q < 9; ++q) tap[i][q] = o.tap[q];
+        outo[i] = o.outo, live[i] = o.live, zpad[i] = o.zpad;
+    }
+};
+
+template <int ST>
+__device__ __forceinline__ PoolTap pool_tap(const LrnPoolArgs& a, const LrnBand& b, unsigned rem, const FastDiv& d_ow) {
+    PoolTap t;
+    const unsigned oyl = fdiv(rem, d_ow), ox = rem - oyl * (unsigned)a.ow;
+    t.live = (int)rem < b.out_pp && (int)oyl < b.rows_t;
+    const int oy = b.oy0 + (int)oyl;
+    const int py0 = oy * ST - a.pt, px0 = (int)ox * ST - a.pl;
+    const int c0 = min(max(px0, 0), a.w - 1), c1 = min(max(px0 + 1, 0), a.w - 1), c2 = min(max(px0 + 2, 0), a.w - 1);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const int r = (min(max(py0 + k, 0), a.h - 1) - b.iy_lo) * a.w;
+        t.tap[3 * k + 0] = t.live ? (unsigned)(r + c0) * 4u : 0u;
+        t.tap[3 * k + 1] = t.live ? (unsigned)(r + c1) * 4u : 0u;
+        t.tap[3 * k + 2] = t.live ? (unsigned)(r + c2) * 4u : 0u;
+    }
+    const bool zc = (px0 < 0) || (min((int)ox * ST + 2, a.wp - 1) - a.pl >= a.w);
+    const bool zr = (py0 < 0) || (min(oy * ST + 2, a.hp - 1) - a.pt >= a.h);
+    t.zpad = zc || zr;
+    t.outo = (unsigned)(oy * a.ow) + ox;
+    return t;
+}
+
+// The 3x3 maximum of one output out of one LDS plane: nine reads, row maxima first; a NaN IS the maximum (max3_nan), as for np.max --
+// the rules of maxpool3x3_cols_kernel.
+template <int NI>
+__device__ __forceinline__ float pool3x3_from_lds(const char* plane, const PoolTaps<NI>& t, int i) {
+    float h[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float v0 = *reinterpret_cast<const float*>(plane + t.tap[i][3 * k + 0]);
+        const float v1 = *reinterpret_cast<const float*>(plane + t.tap[i][3 * k + 1]);
+        const float v2 = *reinterpret_cast<const float*>(plane + t.tap[i][3 * k + 2]);
+        h[k] = max3_nan(v0, v1, v2);
+    }
+    const float m = max3_nan(h[0], h[1], h[2]);
+    return t.zpad[i] ? max3_nan(m, 0.0f, 0.0f) : m;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// LRN followed by a 3x3 MaxPool (GoogLeNet's conv2/norm2 -> pool2/3x3_s2) in ONE pass over the input: the LRN
+// tensor (1.2 GB of traffic at batch 256: written once, read once) never exists.
+//
+// The workgroup walks the channel axis exactly like lrn_window_kernel -- chunks of T = 8 channels, the loads of chunk k+1 in flight while
+// chunk k is normalised -- but the normalised values of a chunk go to LDS plane `slot` instead of HBM, and at the end of a chunk, after a
+// barrier, the workgroup pools those planes (9 LDS reads per output, or pool4) and stores n_pl x band_rows x ow outputs.  The LRN
+// arithmetic is lrn_window_kernel's (lrn_value), so the result carries the bits of the two separate launches.
 template <int SIZE, int VEC, int BETA_MODE, int ST, int NI>     // NI: pooled outputs of a band and plane per lane (ceil(band_rows * ow / 256))
 __global__ __launch_bounds__(kBlock) void lrn_maxpool3x3_kernel(LrnPoolArgs a, FastDiv d_bands, FastDiv d_ow) {
-    constexpr int beta_mode = BETA_MODE;
     constexpr int HALF = SIZE / 2;
-    constexpr int T    = 8;
+    constexpr int T    = kLrnT;
     constexpr int E    = 2 * HALF + T;
     static_assert(2 * HALF <= T, "window halo must fit in one chunk");
-    typedef float vec_t __attribute__((ext_vector_type(VEC)));
+    typedef lrn_vec<VEC> vec_t;
     extern __shared__ __attribute__((aligned(16))) float planes[];   // [T][plane_l]
 #ifdef PVHIP_DIAG
     const int abl = a.abl;          // scripts/time_lrnpool_abl.py: parts switched off
 #else
     constexpr int abl = 0;
 #endif
-
     const int tid = threadIdx.x;
-    const int img = (int)fdiv(blockIdx.x, d_bands), band = (int)blockIdx.x - img * a.n_bands;
-    const int oy0 = band * a.band_rows, oy1 = min(a.oh, oy0 + a.band_rows);
-    const int rows_t = oy1 - oy0;
-    const int iy_lo = max(0, oy0 * ST - a.pt), iy_hi = min(a.h, (oy1 - 1) * ST + 3 - a.pt);
-    const int band_px = (iy_hi - iy_lo) * a.w;
-    const int hw = a.h * a.w, ohw = a.oh * a.ow;
-    const bool   active  = tid * VEC < band_px;
-    const size_t cstride = (size_t)hw / VEC;
-    const vec_t* __restrict__ xv =
-        reinterpret_cast<const vec_t*>(a.x + (size_t)img * a.c * hw + (size_t)iy_lo * a.w + (active ? tid * VEC : 0));
-    float* const mine = planes + tid * VEC;
-    const int    n_chunks = a.c / T;
-    const int    out_pp   = a.band_rows * a.ow;            // pooled outputs per plane and full band
-
-    // normalise ext[j_ + HALF] with the window ext[j_ .. j_ + SIZE) into LDS plane slot_
-#define PV_LRN_TO_LDS(j_, slot_)                                                               \
-    {                                                                                          \
-        vec_t s_ = ext[(j_)] * ext[(j_)];                                                      \
-        _Pragma("unroll") for (int q = 1; q < SIZE; ++q) s_ = s_ + ext[(j_) + q] * ext[(j_) + q]; \
-        vec_t o_;                                                                              \
-        _Pragma("unroll") for (int v = 0; v < VEC; ++v) {                                      \
-            const float d_ = a.bias + a.alpha * s_[v];                                         \
-            o_[v]          = (abl & 1) ? ext[(j_) + HALF][v] : lrn_div(ext[(j_) + HALF][v], d_, a.beta, beta_mode); \
-        }                                                                                      \
-        if (active) *reinterpret_cast<vec_t*>(mine + (slot_) * a.plane_l) = o_;                \
-    }
-
-    // ---- pooling geometry, ONCE per lane: a lane owns the same NI output pixels of the band in every plane of every chunk (the
-    // first version redid two divisions, six clamps and the pad tests per output, plane and chunk: ~60 vector instructions per
-    // output against ~15 of LRN arithmetic per four inputs -- the kernel ran at 3.6 TB/s, VALU-bound).  Nine LDS byte offsets per
-    // owned pixel (taps outside the tensor clamped onto a tap inside the same window), the output offset, and whether the window
-    // touches zero-pad cells (then max(m, 0)).
-    unsigned tap[NI][9];
-    unsigned outo[NI];
-    bool     live[NI], zpad[NI];
+    const LrnBand b = lrn_band<ST, VEC>(a, d_bands, planes);
+    PoolTaps<NI> t;
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
-        const unsigned rem = (unsigned)(tid + i * kBlock);
-        const unsigned oyl = fdiv(rem, d_ow), ox = rem - oyl * (unsigned)a.ow;
-        live[i] = (int)rem < out_pp && (int)oyl < rows_t;
-        const int oy = oy0 + (int)oyl;
-        const int py0 = oy * ST - a.pt, px0 = (int)ox * ST - a.pl;
-        const int c0 = min(max(px0, 0), a.w - 1), c1 = min(max(px0 + 1, 0), a.w - 1), c2 = min(max(px0 + 2, 0), a.w - 1);
+        const PoolTap o = pool_tap<ST>(a, b, (unsigned)(tid + i * kBlock), d_ow);     // copied HERE, not by t.set(): see PoolTaps
 #pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const int r = (min(max(py0 + k, 0), a.h - 1) - iy_lo) * a.w;
-            tap[i][3 * k + 0] = live[i] ? (unsigned)(r + c0) * 4u : 0u;
-            tap[i][3 * k + 1] = live[i] ? (unsigned)(r + c1) * 4u : 0u;
-            tap[i][3 * k + 2] = live[i] ? (unsigned)(r + c2) * 4u : 0u;
-        }
-        const bool zc = (px0 < 0) || (min((int)ox * ST + 2, a.wp - 1) - a.pl >= a.w);
-        const bool zr = (py0 < 0) || (min(oy * ST + 2, a.hp - 1) - a.pt >= a.h);
-        zpad[i] = zc || zr;
-        outo[i] = (unsigned)(oy * a.ow) + ox;
+        for (int q = 0; q < 9; ++q) t.tap[i][q] = o.tap[q];
+        t.outo[i] = o.outo, t.live[i] = o.live, t.zpad[i] = o.zpad;
     }
-    float* const yimg = a.y + (size_t)img * a.c * ohw;
+    float* const yimg = a.y + (size_t)b.img * a.c * b.ohw;
     const char* const planes_b = reinterpret_cast<const char*>(planes);
     const unsigned plane_bytes = (unsigned)a.plane_l * 4u;
+    const int      n_chunks    = a.c / T;
 
     // ---- the same pooling with FOUR adjacent outputs of a row per lane (round 5; a.pool4): their windows are nine columns of three rows -- two 16-byte
     // and one 4-byte LDS read per row instead of 36 4-byte ones, sixteen v_maximum3_f32 as before, ONE 16-byte store instead of four 4-byte ones; the
     // quads of a band fit one wave's lanes (rows_t x ow / 4 <= 64), so the planes of a chunk are dealt over the four waves (plane p: wave p % 4).
+    // A different read pattern from PoolTap's, so a path of its own; the band is the same LrnBand.
     unsigned p4_row[3] = {0u, 0u, 0u}, p4_c8 = 0u, p4_out = 0u, p4_z = 0u;
     bool     p4_live = false;
     const int wv4 = tid >> 6;
@@ -258,11 +343,11 @@ __global__ __launch_bounds__(kBlock) void lrn_maxpool3x3_kernel(LrnPoolArgs a, F
         if (a.pool4 != 0) {
             const int ql = tid & 63, qpr = a.ow >> 2;
             const int oyl = ql / qpr, oxq = ql - oyl * qpr;
-            p4_live = oyl < rows_t;
-            const int oy = oy0 + (p4_live ? oyl : 0);
+            p4_live = oyl < b.rows_t;
+            const int oy = b.oy0 + (p4_live ? oyl : 0);
             const int py0 = oy * ST, c0 = 8 * oxq;                    // (pt = pl = 0)
 #pragma unroll
-            for (int k = 0; k < 3; ++k) p4_row[k] = (unsigned)((min(py0 + k, a.h - 1) - iy_lo) * a.w + c0) * 4u;
+            for (int k = 0; k < 3; ++k) p4_row[k] = (unsigned)((min(py0 + k, a.h - 1) - b.iy_lo) * a.w + c0) * 4u;
             p4_c8 = (unsigned)(min(c0 + 8, a.w - 1) - c0) * 4u;        // the ninth column, clamped into the window (a duplicate does not change a maximum)
             const bool zr = min(oy * ST + 2, a.hp - 1) >= a.h;
 #pragma unroll
@@ -292,7 +377,7 @@ __global__ __launch_bounds__(kBlock) void lrn_maxpool3x3_kernel(LrnPoolArgs a, F
                     const float mj = max3_nan(hm[0][j], hm[1][j], hm[2][j]);
                     m[j] = ((p4_z >> j) & 1u) ? max3_nan(mj, 0.0f, 0.0f) : mj;
                 }
-                if (!(abl & 4)) *reinterpret_cast<f4_t*>(a.y + (size_t)img * a.c * (a.oh * a.ow) + (size_t)(ch0 + p) * (a.oh * a.ow) + p4_out) = m;
+                if (!(abl & 4)) *reinterpret_cast<f4_t*>(a.y + (size_t)b.img * a.c * (a.oh * a.ow) + (size_t)(ch0 + p) * (a.oh * a.ow) + p4_out) = m;
             }
         }
         __syncthreads();
@@ -305,20 +390,11 @@ __global__ __launch_bounds__(kBlock) void lrn_maxpool3x3_kernel(LrnPoolArgs a, F
         __syncthreads();
 #pragma unroll
         for (int i = 0; i < NI; ++i) {
-            if (!live[i] || (abl & 2)) continue;
-            float* yo = yimg + (size_t)ch0 * ohw + outo[i];
+            if (!t.live[i] || (abl & 2)) continue;
+            float* yo = yimg + (size_t)ch0 * b.ohw + t.outo[i];
             unsigned pb = 0u;
-            for (int p = 0; p < n_pl; ++p, pb += plane_bytes, yo += ohw) {
-                float h[3];                      // row maxima: a NaN IS the maximum (max3_nan), as for np.max
-#pragma unroll
-                for (int k = 0; k < 3; ++k) {
-                    const float v0 = *reinterpret_cast<const float*>(planes_b + pb + tap[i][3 * k + 0]);
-                    const float v1 = *reinterpret_cast<const float*>(planes_b + pb + tap[i][3 * k + 1]);
-                    const float v2 = *reinterpret_cast<const float*>(planes_b + pb + tap[i][3 * k + 2]);
-                    h[k] = max3_nan(v0, v1, v2);
-                }
-                float m = max3_nan(h[0], h[1], h[2]);
-                if (zpad[i]) m = max3_nan(m, 0.0f, 0.0f);
+            for (int p = 0; p < n_pl; ++p, pb += plane_bytes, yo += b.ohw) {
+                const float m = pool3x3_from_lds(planes_b + pb, t, i);
                 // PLAIN stores: a lane writes one float per plane, 896-byte runs per plane and band -- nontemporal stores of such pieces
                 // cost 4 % here and 9 % in maxpool3x3_lrn_kernel (the dense 16-byte runs of the MaxPool kernel are the opposite case)
                 if (!(abl & 4)) *yo = m;
@@ -327,22 +403,27 @@ __global__ __launch_bounds__(kBlock) void lrn_maxpool3x3_kernel(LrnPoolArgs a, F
         __syncthreads();
     };
 
+    // ---- the channel walk of lrn_window_kernel, with LDS plane `slot` as the destination and the pooling at the end of each chunk
+    const vec_t* __restrict__ xv = reinterpret_cast<const vec_t*>(b.x0);
     vec_t ext[E], nxt[T];
+    // normalise ext[j + HALF] with the window ext[j .. j + SIZE) into LDS plane slot
+    auto norm   = [&](const vec_t* w) { return (abl & 1) ? w[HALF] : lrn_value<SIZE, BETA_MODE>(w, w[HALF], a.alpha, a.beta, a.bias); };
+    auto to_lds = [&](vec_t o, int slot) { if (b.active) *reinterpret_cast<vec_t*>(b.mine + slot * a.plane_l) = o; };
 #pragma unroll
     for (int j = 0; j < 2 * HALF; ++j) ext[j] = (vec_t)(0.0f);
 #pragma unroll
-    for (int j = 0; j < T; ++j) ext[2 * HALF + j] = ldnt(xv + (size_t)j * cstride);
+    for (int j = 0; j < T; ++j) ext[2 * HALF + j] = ldnt(xv + (size_t)j * b.cstride);
     for (int k = 0; k + 1 < n_chunks; ++k) {
-        const vec_t* __restrict__ xn = xv + (size_t)((abl & 8) ? 0 : (k + 1) * T) * cstride;        // abl 8: the first chunk again (L2 hits)
+        const vec_t* __restrict__ xn = xv + (size_t)((abl & 8) ? 0 : (k + 1) * T) * b.cstride;        // abl 8: the first chunk again (L2 hits)
 #pragma unroll
-        for (int j = 0; j < T; ++j) nxt[j] = ldnt(xn + (size_t)j * cstride);
+        for (int j = 0; j < T; ++j) nxt[j] = ldnt(xn + (size_t)j * b.cstride);
         if (k == 0) {
 #pragma unroll
-            for (int j = HALF; j < T; ++j) PV_LRN_TO_LDS(j, j - HALF)
+            for (int j = HALF; j < T; ++j) to_lds(norm(ext + j), j - HALF);
             pool(T - HALF, 0);
         } else {
 #pragma unroll
-            for (int j = 0; j < T; ++j) PV_LRN_TO_LDS(j, j)
+            for (int j = 0; j < T; ++j) to_lds(norm(ext + j), j);
             pool(T, k * T - HALF);
         }
 #pragma unroll
@@ -354,11 +435,11 @@ __global__ __launch_bounds__(kBlock) void lrn_maxpool3x3_kernel(LrnPoolArgs a, F
         const int k = n_chunks - 1;
         if (k == 0) {
 #pragma unroll
-            for (int j = HALF; j < T; ++j) PV_LRN_TO_LDS(j, j - HALF)
+            for (int j = HALF; j < T; ++j) to_lds(norm(ext + j), j - HALF);
             pool(T - HALF, 0);
         } else {
 #pragma unroll
-            for (int j = 0; j < T; ++j) PV_LRN_TO_LDS(j, j)
+            for (int j = 0; j < T; ++j) to_lds(norm(ext + j), j);
             pool(T, k * T - HALF);
         }
 #pragma unroll
@@ -366,66 +447,91 @@ __global__ __launch_bounds__(kBlock) void lrn_maxpool3x3_kernel(LrnPoolArgs a, F
 #pragma unroll
         for (int j = 0; j < T; ++j) ext[2 * HALF + j] = (vec_t)(0.0f);
 #pragma unroll
-        for (int j = 0; j < HALF; ++j) PV_LRN_TO_LDS(j, j)
+        for (int j = 0; j < HALF; ++j) to_lds(norm(ext + j), j);
         pool(HALF, a.c - HALF);
     }
-#undef PV_LRN_TO_LDS
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// The other order: a 3x3 MaxPool followed by LRN (GoogLeNet's pool1/3x3_s2 -> pool1/norm1) in ONE pass: the pooled
-// tensor (411 MB at batch 256: written once, read once) never exists.  Same bands, same lane <-> input pixels for the
-// loads; the RAW planes of a chunk of 8 channels go to LDS, every lane pools its own NI output pixels out of them (the
-// geometry of lrn_maxpool3x3_kernel, computed once) and the pooled values of consecutive channels ARE the stream the LRN
-// window slides over: five of them in registers per owned pixel, squares summed in ascending channel order, the
-// arithmetic of lrn_window_kernel -- the bits of the two separate launches.
-template <int SIZE, int VEC, int BETA_MODE, int ST, int NI>
-__global__ __launch_bounds__(kBlock) void maxpool3x3_lrn_kernel(LrnPoolArgs a, FastDiv d_bands, FastDiv d_ow) {
-    constexpr int beta_mode = BETA_MODE;
+// A new pooled value v of channel ch enters the window w of the owned output at offset outo of its plane; the window is then centred on
+// channel ch - SIZE / 2, whose normalised value goes to sink(outo, value, channel).  (A free function, not a lambda of the walk below: a
+// closure that captures the windows -- register arrays -- doubled maxpool3x3_lrn_kernel's registers at NI = 2, profiles/norm_refactor.md.)
+template <int SIZE, int BETA_MODE, class Sink>
+__device__ __forceinline__ void push_pooled(ChannelWindow<SIZE>& w, const LrnPoolArgs& a, unsigned outo, float v, int ch, Sink&& sink) {
+    w.push(v);
+    if (ch >= SIZE / 2) sink(outo, lrn_value<SIZE, BETA_MODE>(w.v, w.v[SIZE / 2], a.alpha, a.beta, a.bias), ch - SIZE / 2);
+}
+
+// The other order, MaxPool then LRN: the RAW planes of a chunk of 8 channels go to LDS (the loads of chunk k+1 in flight meanwhile), every
+// lane pools its own NI output pixels out of them, and the pooled values of consecutive channels ARE the stream the LRN window slides
+// over: SIZE of them in registers per owned pixel (ChannelWindow), the arithmetic of lrn_window_kernel.  The normalised value of the
+// output at offset outo of its plane and channel ch goes to sink(outo, value, ch).  ALL_LANES: lanes without an output walk along (their
+// taps read offset 0) instead of skipping the pooling -- for a sink in which every lane of the wave must take part.
+// maxpool3x3_lrn_conv1x1_kernel walks this way (its sink is the MFMA); maxpool3x3_lrn_kernel keeps the loop written out, see there.
+template <int SIZE, int VEC, int BETA_MODE, int NI, bool ALL_LANES, class Sink>
+__device__ __forceinline__ void pooled_lrn_walk(const LrnPoolArgs& a, const LrnBand& b, const float* planes, const PoolTaps<NI>& t, Sink&& sink) {
     constexpr int HALF = SIZE / 2;
-    constexpr int T    = 8;
-    typedef float vec_t __attribute__((ext_vector_type(VEC)));
-    extern __shared__ __attribute__((aligned(16))) float planes[];   // [T][plane_l]
-
-    const int tid = threadIdx.x;
-    const int img = (int)fdiv(blockIdx.x, d_bands), band = (int)blockIdx.x - img * a.n_bands;
-    const int oy0 = band * a.band_rows, oy1 = min(a.oh, oy0 + a.band_rows);
-    const int rows_t = oy1 - oy0;
-    const int iy_lo = max(0, oy0 * ST - a.pt), iy_hi = min(a.h, (oy1 - 1) * ST + 3 - a.pt);
-    const int band_px = (iy_hi - iy_lo) * a.w;
-    const int hw = a.h * a.w, ohw = a.oh * a.ow;
-    const bool   active  = tid * VEC < band_px;
-    const size_t cstride = (size_t)hw / VEC;
-    const vec_t* __restrict__ xv =
-        reinterpret_cast<const vec_t*>(a.x + (size_t)img * a.c * hw + (size_t)iy_lo * a.w + (active ? tid * VEC : 0));
-    float* const mine = planes + tid * VEC;
-    const int    n_chunks = a.c / T;
-    const int    out_pp   = a.band_rows * a.ow;
-
-    unsigned tap[NI][9];
-    unsigned outo[NI];
-    bool     live[NI], zpad[NI];
+    constexpr int T    = kLrnT;
+    typedef lrn_vec<VEC> vec_t;
+    const vec_t* __restrict__ xv = reinterpret_cast<const vec_t*>(b.x0);
+    const char* const planes_b = reinterpret_cast<const char*>(planes);
+    const unsigned plane_bytes = (unsigned)a.plane_l * 4u;
+    const int      n_chunks    = a.c / T;
+    ChannelWindow<SIZE> win[NI];           // pooled values of channels ch - SIZE + 1 .. ch of the owned pixels
+#pragma unroll
+    for (int i = 0; i < NI; ++i) win[i].clear();
+    vec_t cur[T], nxt[T];
+#pragma unroll
+    for (int j = 0; j < T; ++j) cur[j] = ldnt(xv + (size_t)j * b.cstride);
+    for (int k = 0; k < n_chunks; ++k) {
+        if (k + 1 < n_chunks) {
+            const vec_t* __restrict__ xn = xv + (size_t)(k + 1) * T * b.cstride;
+#pragma unroll
+            for (int j = 0; j < T; ++j) nxt[j] = ldnt(xn + (size_t)j * b.cstride);
+        }
+        if (b.active) {
+#pragma unroll
+            for (int j = 0; j < T; ++j) *reinterpret_cast<vec_t*>(b.mine + j * a.plane_l) = cur[j];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < NI; ++i) {
+            if (!ALL_LANES && !t.live[i]) continue;
+            unsigned pb = 0u;
+#pragma unroll
+            for (int p = 0; p < T; ++p, pb += plane_bytes) push_pooled<SIZE, BETA_MODE>(win[i], a, t.outo[i], pool3x3_from_lds(planes_b + pb, t, i), k * T + p, sink);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < T; ++j) cur[j] = nxt[j];
+    }
+    // the trailing HALF channels: their windows run past the tensor (zeros)
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
-        const unsigned rem = (unsigned)(tid + i * kBlock);
-        const unsigned oyl = fdiv(rem, d_ow), ox = rem - oyl * (unsigned)a.ow;
-        live[i] = (int)rem < out_pp && (int)oyl < rows_t;
-        const int oy = oy0 + (int)oyl;
-        const int py0 = oy * ST - a.pt, px0 = (int)ox * ST - a.pl;
-        const int c0 = min(max(px0, 0), a.w - 1), c1 = min(max(px0 + 1, 0), a.w - 1), c2 = min(max(px0 + 2, 0), a.w - 1);
+        if (!ALL_LANES && !t.live[i]) continue;
 #pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const int r = (min(max(py0 + k, 0), a.h - 1) - iy_lo) * a.w;
-            tap[i][3 * k + 0] = live[i] ? (unsigned)(r + c0) * 4u : 0u;
-            tap[i][3 * k + 1] = live[i] ? (unsigned)(r + c1) * 4u : 0u;
-            tap[i][3 * k + 2] = live[i] ? (unsigned)(r + c2) * 4u : 0u;
-        }
-        const bool zc = (px0 < 0) || (min((int)ox * ST + 2, a.wp - 1) - a.pl >= a.w);
-        const bool zr = (py0 < 0) || (min(oy * ST + 2, a.hp - 1) - a.pt >= a.h);
-        zpad[i] = zc || zr;
-        outo[i] = (unsigned)(oy * a.ow) + ox;
+        for (int j = 0; j < HALF; ++j) push_pooled<SIZE, BETA_MODE>(win[i], a, t.outo[i], 0.0f, a.c + j, sink);
     }
-    float* const yimg = a.y + (size_t)img * a.c * ohw;
+}
+
+// 3x3 MaxPool followed by LRN (GoogLeNet's pool1/3x3_s2 -> pool1/norm1) in ONE pass: the pooled tensor (411 MB at batch 256: written
+// once, read once) never exists.  Same bands and same lane <-> input pixels as lrn_maxpool3x3_kernel, the loop of pooled_lrn_walk with
+// "store the normalised value" in the place of the sink -- the bits of the two separate launches.  The loop is WRITTEN OUT here, with the
+// windows as plain arrays and the push as a local macro: as a call of pooled_lrn_walk with a store sink this kernel's GoogLeNet launch
+// took 0.180 - 0.191 ms against 0.175 and its NI = 2 instantiations 16 to 21 registers more (profiles/norm_refactor.md).
+template <int SIZE, int VEC, int BETA_MODE, int ST, int NI>
+__global__ __launch_bounds__(kBlock) void maxpool3x3_lrn_kernel(LrnPoolArgs a, FastDiv d_bands, FastDiv d_ow) {
+    constexpr int HALF = SIZE / 2;
+    constexpr int T    = kLrnT;
+    typedef lrn_vec<VEC> vec_t;
+    extern __shared__ __attribute__((aligned(16))) float planes[];   // [T][plane_l]
+    const LrnBand b = lrn_band<ST, VEC>(a, d_bands, planes);
+    const vec_t* __restrict__ xv = reinterpret_cast<const vec_t*>(b.x0);
+    const int n_chunks = a.c / T;
+    PoolTaps<NI> t;
+#pragma unroll
+    for (int i = 0; i < NI; ++i) t.set(i, pool_tap<ST>(a, b, (unsigned)(threadIdx.x + i * kBlock), d_ow));
+    float* const yimg = a.y + (size_t)b.img * a.c * b.ohw;
     const char* const planes_b = reinterpret_cast<const char*>(planes);
     const unsigned plane_bytes = (unsigned)a.plane_l * 4u;
 
@@ -435,51 +541,37 @@ __global__ __launch_bounds__(kBlock) void maxpool3x3_lrn_kernel(LrnPoolArgs a, F
 #pragma unroll
         for (int q = 0; q < SIZE; ++q) win[i][q] = 0.0f;
 
-    // a new pooled value v_ of channel ch_ enters the window; the window is then centred on channel ch_ - HALF
-#define PV_PUSH_EMIT(i_, v_, ch_)                                                              \
+    // a new pooled value v_ of channel ch_ enters the window; the window is then centred on channel ch_ - HALF (plain store: see lrn_maxpool3x3_kernel)
+#define PV_PUSH_STORE(i_, v_, ch_)                                                             \
     {                                                                                          \
         _Pragma("unroll") for (int q = 0; q + 1 < SIZE; ++q) win[i_][q] = win[i_][q + 1];      \
         win[i_][SIZE - 1] = (v_);                                                              \
-        if ((ch_) >= HALF) {                                                                   \
-            float s_ = win[i_][0] * win[i_][0];                                                \
-            _Pragma("unroll") for (int q = 1; q < SIZE; ++q) s_ = s_ + win[i_][q] * win[i_][q]; \
-            const float d_ = a.bias + a.alpha * s_;                                            \
-            yimg[(size_t)((ch_) - HALF) * ohw + outo[i_]] = lrn_div(win[i_][HALF], d_, a.beta, beta_mode);   /* plain store: see lrn_maxpool3x3_kernel */ \
-        }                                                                                      \
+        if ((ch_) >= HALF)                                                                     \
+            yimg[(size_t)((ch_) - HALF) * b.ohw + t.outo[i_]] = lrn_value<SIZE, BETA_MODE>(win[i_], win[i_][HALF], a.alpha, a.beta, a.bias); \
     }
 
     vec_t cur[T], nxt[T];
 #pragma unroll
-    for (int j = 0; j < T; ++j) cur[j] = ldnt(xv + (size_t)j * cstride);
+    for (int j = 0; j < T; ++j) cur[j] = ldnt(xv + (size_t)j * b.cstride);
     for (int k = 0; k < n_chunks; ++k) {
         if (k + 1 < n_chunks) {
-            const vec_t* __restrict__ xn = xv + (size_t)(k + 1) * T * cstride;
+            const vec_t* __restrict__ xn = xv + (size_t)(k + 1) * T * b.cstride;
 #pragma unroll
-            for (int j = 0; j < T; ++j) nxt[j] = ldnt(xn + (size_t)j * cstride);
+            for (int j = 0; j < T; ++j) nxt[j] = ldnt(xn + (size_t)j * b.cstride);
         }
-        if (active) {
+        if (b.active) {
 #pragma unroll
-            for (int j = 0; j < T; ++j) *reinterpret_cast<vec_t*>(mine + j * a.plane_l) = cur[j];
+            for (int j = 0; j < T; ++j) *reinterpret_cast<vec_t*>(b.mine + j * a.plane_l) = cur[j];
         }
         __syncthreads();
 #pragma unroll
         for (int i = 0; i < NI; ++i) {
-            if (!live[i]) continue;
+            if (!t.live[i]) continue;
             unsigned pb = 0u;
 #pragma unroll
             for (int p = 0; p < T; ++p, pb += plane_bytes) {
-                float h[3];                      // row maxima: a NaN IS the maximum (max3_nan), as for np.max
-#pragma unroll
-                for (int q = 0; q < 3; ++q) {
-                    const float v0 = *reinterpret_cast<const float*>(planes_b + pb + tap[i][3 * q + 0]);
-                    const float v1 = *reinterpret_cast<const float*>(planes_b + pb + tap[i][3 * q + 1]);
-                    const float v2 = *reinterpret_cast<const float*>(planes_b + pb + tap[i][3 * q + 2]);
-                    h[q] = max3_nan(v0, v1, v2);
-                }
-                float m = max3_nan(h[0], h[1], h[2]);
-                if (zpad[i]) m = max3_nan(m, 0.0f, 0.0f);
-                const float pooled = m;
-                PV_PUSH_EMIT(i, pooled, k * T + p)
+                const float pooled = pool3x3_from_lds(planes_b + pb, t, i);
+                PV_PUSH_STORE(i, pooled, k * T + p)
             }
         }
         __syncthreads();
@@ -489,11 +581,11 @@ __global__ __launch_bounds__(kBlock) void maxpool3x3_lrn_kernel(LrnPoolArgs a, F
     // the trailing HALF channels: their windows run past the tensor (zeros)
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
-        if (!live[i]) continue;
+        if (!t.live[i]) continue;
 #pragma unroll
-        for (int j = 0; j < HALF; ++j) PV_PUSH_EMIT(i, 0.0f, a.c + j)
+        for (int j = 0; j < HALF; ++j) PV_PUSH_STORE(i, 0.0f, a.c + j)
     }
-#undef PV_PUSH_EMIT
+#undef PV_PUSH_STORE
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -519,28 +611,14 @@ struct PoolLrnConvArgs {
 
 template <int BETA_MODE, int ST, int KT>        // KT: 32-channel tiles of the convolution's output (k_out <= 32 KT)
 __global__ __launch_bounds__(kBlock) void maxpool3x3_lrn_conv1x1_kernel(PoolLrnConvArgs ca, FastDiv d_bands, FastDiv d_ow) {
-    constexpr int beta_mode = BETA_MODE;
-    constexpr int SIZE = 5, HALF = SIZE / 2, T = 8, VEC = 4;
-    typedef float vec_t __attribute__((ext_vector_type(VEC)));
+    constexpr int SIZE = 5, T = kLrnT, VEC = 4;
     extern __shared__ __attribute__((aligned(16))) float planes[];   // [T][plane_l], then the weights [c][32 KT]
     const LrnPoolArgs& a = ca.p;
     float* const wl = planes + T * a.plane_l;
 
     const int tid = threadIdx.x;
     const int lane = tid & (kWave - 1);
-    const int img = (int)fdiv(blockIdx.x, d_bands), band = (int)blockIdx.x - img * a.n_bands;
-    const int oy0 = band * a.band_rows, oy1 = min(a.oh, oy0 + a.band_rows);
-    const int rows_t = oy1 - oy0;
-    const int iy_lo = max(0, oy0 * ST - a.pt), iy_hi = min(a.h, (oy1 - 1) * ST + 3 - a.pt);
-    const int band_px = (iy_hi - iy_lo) * a.w;
-    const int hw = a.h * a.w, ohw = a.oh * a.ow;
-    const bool   active  = tid * VEC < band_px;
-    const size_t cstride = (size_t)hw / VEC;
-    const vec_t* __restrict__ xv =
-        reinterpret_cast<const vec_t*>(a.x + (size_t)img * a.c * hw + (size_t)iy_lo * a.w + (active ? tid * VEC : 0));
-    float* const mine = planes + tid * VEC;
-    const int    n_chunks = a.c / T;
-    const int    out_pp   = a.band_rows * a.ow;
+    const LrnBand b = lrn_band<ST, VEC>(a, d_bands, planes);
 
     // the transposed weights: wl[c][k] = W[k][c], zeros past k_out
     for (int e = tid; e < a.c * 32 * KT; e += kBlock) {
@@ -548,104 +626,32 @@ __global__ __launch_bounds__(kBlock) void maxpool3x3_lrn_conv1x1_kernel(PoolLrnC
         wl[e] = k < ca.k_out ? ca.cw[(size_t)k * a.c + c] : 0.0f;
     }
 
-    unsigned tap[9];
-    unsigned outo;
-    bool     live, zpad;
-    {
-        const unsigned rem = (unsigned)tid;
-        const unsigned oyl = fdiv(rem, d_ow), ox = rem - oyl * (unsigned)a.ow;
-        live = (int)rem < out_pp && (int)oyl < rows_t;
-        const int oy = oy0 + (int)oyl;
-        const int py0 = oy * ST - a.pt, px0 = (int)ox * ST - a.pl;
-        const int c0 = min(max(px0, 0), a.w - 1), c1 = min(max(px0 + 1, 0), a.w - 1), c2 = min(max(px0 + 2, 0), a.w - 1);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const int r = (min(max(py0 + k, 0), a.h - 1) - iy_lo) * a.w;
-            tap[3 * k + 0] = live ? (unsigned)(r + c0) * 4u : 0u;
-            tap[3 * k + 1] = live ? (unsigned)(r + c1) * 4u : 0u;
-            tap[3 * k + 2] = live ? (unsigned)(r + c2) * 4u : 0u;
-        }
-        const bool zc = (px0 < 0) || (min((int)ox * ST + 2, a.wp - 1) - a.pl >= a.w);
-        const bool zr = (py0 < 0) || (min(oy * ST + 2, a.hp - 1) - a.pt >= a.h);
-        zpad = zc || zr;
-        outo = live ? (unsigned)(oy * a.ow) + ox : 0xffffffffu;
-    }
-    const char* const planes_b = reinterpret_cast<const char*>(planes);
-    const unsigned plane_bytes = (unsigned)a.plane_l * 4u;
+    PoolTaps<1> t;                                             // one output per lane
+    t.set(0, pool_tap<ST>(a, b, (unsigned)tid, d_ow));
+    if (!t.live[0]) t.outo[0] = 0xffffffffu;                         // a dead lane: the epilogue stores nothing for it
     const float* const wl_lane = wl + (lane & 31);
-
-    float win[SIZE];
-#pragma unroll
-    for (int q = 0; q < SIZE; ++q) win[q] = 0.0f;
     floatx32 acc[KT];
 #pragma unroll
     for (int kt = 0; kt < KT; ++kt)
 #pragma unroll
         for (int r = 0; r < 32; ++r) acc[kt][r] = 0.0f;
 
-    // a new pooled value v_ of channel ch_ enters the window; the window is then centred on channel ch_ - HALF, whose normalised value -- what
-    // maxpool3x3_lrn_kernel stores -- is this lane's column of the outer product with that channel's weights (every lane takes part: no branch)
-#define PV_PUSH_MFMA(v_, ch_)                                                                  \
-    {                                                                                          \
-        _Pragma("unroll") for (int q = 0; q + 1 < SIZE; ++q) win[q] = win[q + 1];              \
-        win[SIZE - 1] = (v_);                                                                  \
-        if ((ch_) >= HALF) {                                                                   \
-            float s_ = win[0] * win[0];                                                        \
-            _Pragma("unroll") for (int q = 1; q < SIZE; ++q) s_ = s_ + win[q] * win[q];        \
-            const float d_ = a.bias + a.alpha * s_;                                            \
-            const float o_ = live ? lrn_div(win[HALF], d_, a.beta, beta_mode) : 0.0f;          \
-            const float* const wc_ = wl_lane + ((ch_) - HALF) * (32 * KT);                     \
-            _Pragma("unroll") for (int kt = 0; kt < KT; ++kt)                                  \
-                acc[kt] = __builtin_amdgcn_mfma_f32_32x32x1f32(wc_[32 * kt], o_, acc[kt], 0, 0, 0); \
-        }                                                                                      \
-    }
-
-    vec_t cur[T], nxt[T];
+    // the normalised value of channel ch -- what maxpool3x3_lrn_kernel stores -- is this lane's column of the outer product with that channel's
+    // weights: one k = 1 MFMA per 32 output channels (every lane takes part: no branch; a dead lane contributes a zero column).  The pooled
+    // value reaches the MFMA through max3_nan's builtin and plain C++ only: no inline asm on the way (stale MFMA operands, see max3_nan)
+    pooled_lrn_walk<SIZE, VEC, BETA_MODE, 1, true>(a, b, planes, t, [&](unsigned, float v, int ch) {
+        const float o = t.live[0] ? v : 0.0f;
+        const float* const wc = wl_lane + ch * (32 * KT);
 #pragma unroll
-    for (int j = 0; j < T; ++j) cur[j] = ldnt(xv + (size_t)j * cstride);
-    for (int k = 0; k < n_chunks; ++k) {
-        if (k + 1 < n_chunks) {
-            const vec_t* __restrict__ xn = xv + (size_t)(k + 1) * T * cstride;
-#pragma unroll
-            for (int j = 0; j < T; ++j) nxt[j] = ldnt(xn + (size_t)j * cstride);
-        }
-        if (active) {
-#pragma unroll
-            for (int j = 0; j < T; ++j) *reinterpret_cast<vec_t*>(mine + j * a.plane_l) = cur[j];
-        }
-        __syncthreads();
-        {
-            unsigned pb = 0u;
-#pragma unroll
-            for (int p = 0; p < T; ++p, pb += plane_bytes) {
-                float h[3];                      // row maxima: a NaN IS the maximum (max3_nan), as for np.max
-#pragma unroll
-                for (int q = 0; q < 3; ++q) {
-                    const float v0 = *reinterpret_cast<const float*>(planes_b + pb + tap[3 * q + 0]);
-                    const float v1 = *reinterpret_cast<const float*>(planes_b + pb + tap[3 * q + 1]);
-                    const float v2 = *reinterpret_cast<const float*>(planes_b + pb + tap[3 * q + 2]);
-                    h[q] = max3_nan(v0, v1, v2);
-                }
-                float m = max3_nan(h[0], h[1], h[2]);
-                if (zpad) m = max3_nan(m, 0.0f, 0.0f);
-                PV_PUSH_MFMA(m, k * T + p)
-            }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < T; ++j) cur[j] = nxt[j];
-    }
-    // the trailing HALF channels: their windows run past the tensor (zeros)
-#pragma unroll
-    for (int j = 0; j < HALF; ++j) PV_PUSH_MFMA(0.0f, a.c + j)
-#undef PV_PUSH_MFMA
+        for (int kt = 0; kt < KT; ++kt) acc[kt] = __builtin_amdgcn_mfma_f32_32x32x1f32(wc[32 * kt], o, acc[kt], 0, 0, 0);
+    });
 
     // ---- epilogue: acc[kt][16 b + v] at lane (j = lane & 31, h = lane >> 5) = output channel 32 kt + 8 (v / 4) + 4 h + v % 4 of the pixel of lane 32 b + j
     const int h2 = lane >> 5;
     unsigned outo_b[2];
-    outo_b[0] = (unsigned)__shfl((int)outo, lane & 31, kWave);
-    outo_b[1] = (unsigned)__shfl((int)outo, 32 + (lane & 31), kWave);
-    float* const yimg = ca.y + (size_t)img * ca.k_out * ohw;
+    outo_b[0] = (unsigned)__shfl((int)t.outo[0], lane & 31, kWave);
+    outo_b[1] = (unsigned)__shfl((int)t.outo[0], 32 + (lane & 31), kWave);
+    float* const yimg = ca.y + (size_t)b.img * ca.k_out * b.ohw;
     const ActBounds ab = act_bounds(ca.act, ca.act_lo, ca.act_hi);
 #pragma unroll
     for (int kt = 0; kt < KT; ++kt) {
@@ -656,16 +662,16 @@ __global__ __launch_bounds__(kBlock) void maxpool3x3_lrn_conv1x1_kernel(PoolLrnC
             bv[v] = (ca.cbias != nullptr && kk < ca.k_out) ? ca.cbias[kk] : 0.0f;
         }
 #pragma unroll
-        for (int b = 0; b < 2; ++b) {
+        for (int bl = 0; bl < 2; ++bl) {
             float vv[16];
 #pragma unroll
-            for (int v = 0; v < 16; ++v) vv[v] = acc[kt][16 * b + v];
+            for (int v = 0; v < 16; ++v) vv[v] = acc[kt][16 * bl + v];
             bias_act_n<16>(vv, bv, ca.cbias != nullptr, ca.act, ab);
-            if (outo_b[b] != 0xffffffffu) {
+            if (outo_b[bl] != 0xffffffffu) {
 #pragma unroll
                 for (int v = 0; v < 16; ++v) {
                     const int kk = 32 * kt + 8 * (v >> 2) + 4 * h2 + (v & 3);
-                    if (kk < ca.k_out) yimg[(size_t)kk * ohw + outo_b[b]] = vv[v];
+                    if (kk < ca.k_out) yimg[(size_t)kk * b.ohw + outo_b[bl]] = vv[v];
                 }
             }
         }
@@ -833,36 +839,94 @@ bool plan_lrn_pool_wave(int n, int c, int h, int w, int size, float beta, float 
     return (size_t)4 * 4 * a.rows_in * w * sizeof(float) <= 64 * 1024;
 }
 
-// Geometry of the fused launch, or false when the pair is outside what lrn_maxpool3x3_kernel covers.
-bool plan_lrn_pool(int n, int c, int h, int w, int size, float beta, float bias, int oh, int ow, int kh, int kw, int sh, int sw,
-                   int pt, int pl, int pb, int pr, LrnPoolArgs& a, int& vec, int& bm, size_t& lds) {
-    if (n <= 0 || c < 8 || c % 8 != 0 || h <= 0 || w <= 0 || oh <= 0 || ow <= 0) return false;
-    if (size != 5 || kh != 3 || kw != 3 || sh != sw || (sh != 1 && sh != 2)) return false;
-    if (pt < 0 || pl < 0 || pb < 0 || pr < 0 || pt > 2 || pl > 2) return false;
-    if ((oh - 1) * sh > pt + h - 1 || (ow - 1) * sw > pl + w - 1) return false;       // clamped taps stay inside their window
-    if ((unsigned long long)n * c * h * w >= (1ull << 31)) return false;
-    bm = lrn_beta_mode(beta, bias);
-    if (bm != 4 && bm != 1) return false;
-    vec = (w % 4 == 0) ? 4 : 1;
-    int rows = (kBlock * vec / w - 3) / sh + 1;                 // largest band whose input rows fit the 256 lanes
-    if (kBlock * vec / w < 3 && h >= 3) return false;
-    if (rows < 1) return false;
+// What a fused LRN / MaxPool launch will be, decided HERE and nowhere else: the _supported queries report `ok`, the entries launch
+// what the plan says.  The geometry is the pooling's, whichever node comes first.
+struct LrnPoolPlan {
+    bool        ok = false;      // the pair is inside what the workgroup kernels cover
+    LrnPoolArgs a{};             // geometry (x, y, alpha, beta, bias are the entry's to fill); a.pool4: which body of lrn_maxpool3x3_kernel runs
+    int         vec = 0;         // pixels per lane: 4 where a row is a whole number of 16-byte pieces
+    int         bm  = 0;         // beta mode: 4 or 1
+    int         st  = 0;         // pooling stride: 1 or 2
+    int         ni  = 0;         // pooled outputs of a band and plane per lane: instantiations for 1, 2 and 4
+    size_t      lds = 0;
+};
+
+LrnPoolPlan plan_lrn_pool(int n, int c, int h, int w, int size, float beta, float bias, int oh, int ow, int kh, int kw, int sh, int sw,
+                          int pt, int pl, int pb, int pr) {
+    LrnPoolPlan p;
+    LrnPoolArgs& a = p.a;
+    if (n <= 0 || c < 8 || c % 8 != 0 || h <= 0 || w <= 0 || oh <= 0 || ow <= 0) return p;
+    if (size != 5 || kh != 3 || kw != 3 || sh != sw || (sh != 1 && sh != 2)) return p;
+    if (pt < 0 || pl < 0 || pb < 0 || pr < 0 || pt > 2 || pl > 2) return p;
+    if ((oh - 1) * sh > pt + h - 1 || (ow - 1) * sw > pl + w - 1) return p;       // clamped taps stay inside their window
+    if ((unsigned long long)n * c * h * w >= (1ull << 31)) return p;
+    p.bm = lrn_beta_mode(beta, bias);
+    if (p.bm != 4 && p.bm != 1) return p;
+    p.st  = sh;
+    p.vec = (w % 4 == 0) ? 4 : 1;
+    int rows = (kBlock * p.vec / w - 3) / sh + 1;                 // largest band whose input rows fit the 256 lanes
+    if (kBlock * p.vec / w < 3 && h >= 3) return p;
+    if (rows < 1) return p;
     if (rows > oh) rows = oh;
     int bands = (oh + rows - 1) / rows;
     rows  = (oh + bands - 1) / bands;
     bands = (oh + rows - 1) / rows;
     int in_rows = (rows - 1) * sh + 3;
     if (in_rows > h) in_rows = h;
-    if (in_rows * w > kBlock * vec) return false;
+    if (in_rows * w > kBlock * p.vec) return p;
     a.n = n; a.c = c; a.h = h; a.w = w; a.oh = oh; a.ow = ow; a.pt = pt; a.pl = pl; a.hp = h + pt + pb; a.wp = w + pl + pr;
     a.band_rows = rows; a.n_bands = bands;
-    // the kernels are instantiated for up to four pooled outputs per lane and plane; a pooled row wider than the input row (ow > w) with
-    // a tall band needs more: the QUERY must say no there, so that the caller falls back to two launches instead of failing at run time
-    if ((rows * ow + kBlock - 1) / kBlock > 4) return false;
-    a.plane_l   = (in_rows * w + 3) & ~3;
-    lds         = (size_t)8 * a.plane_l * sizeof(float);
-    return lds <= 64 * 1024 && (long long)n * bands < (1ll << 31);
+    // the kernels are instantiated for up to four pooled outputs per lane and plane (1 at stride 2: a band holds <= 1024 input pixels; up
+    // to 4 at stride 1); a pooled row wider than the input row (ow > w) with a tall band needs more: the QUERY must say no there, so that
+    // the caller falls back to two launches instead of failing at run time
+    p.ni = (rows * ow + kBlock - 1) / kBlock;
+    if (p.ni > 4) return p;
+    // four pooled outputs per lane (pool4 in lrn_maxpool3x3_kernel); 2 ow <= w: the eight columns a quad reads whole lie in the row, only
+    // the ninth is clamped.  PVHIP_TUNE6=1 keeps one per lane (A/B runs)
+    a.pool4 = (p.vec == 4 && sh == 2 && pt == 0 && pl == 0 && ow % 4 == 0 && 2 * ow <= w && (ow / 4) * rows <= kWave && settings().tune[6] != 1) ? 1 : 0;
+    a.plane_l = (in_rows * w + 3) & ~3;
+    p.lds     = (size_t)kLrnT * a.plane_l * sizeof(float);
+    p.ok      = p.lds <= 64 * 1024 && (long long)n * bands < (1ll << 31);
+    return p;
 }
+
+// MaxPool then LRN then a 1x1 / stride 1 / unpadded convolution: the plan above with one pooled output per lane (bands of at most 256
+// outputs), rows of a multiple of four pixels, and at most 64 input and 64 output channels (the transposed weights stay in LDS).
+LrnPoolPlan plan_pool_lrn_conv(int n, int c, int h, int w, int oh, int ow, int kh, int kw, int sh, int sw, int pt, int pl, int pb, int pr, int size,
+                               float beta, float bias, int k_out) {
+    LrnPoolPlan p = plan_lrn_pool(n, c, h, w, size, beta, bias, oh, ow, kh, kw, sh, sw, pt, pl, pb, pr);
+    if (!p.ok) return p;
+    p.ok = false;
+    if (p.vec != 4 || p.a.band_rows * ow > kBlock || k_out <= 0 || k_out > 64 || c > 64) return p;
+    if ((unsigned long long)n * k_out * oh * ow >= (1ull << 31)) return p;
+    p.lds += (size_t)c * 32 * ((k_out + 31) / 32) * sizeof(float);
+    p.ok = p.lds <= 64 * 1024;
+    return p;
+}
+
+// The launch of a two-node kernel K_<5, vec, bm, st, NI> as the plan P_ says; the macro defines one launcher per kernel, right below.
+#define PV_LRN_POOL_NI(K_, P_, VEC_, BM_, ST_, NI_) \
+    hipLaunchKernelGGL((K_<5, VEC_, BM_, ST_, NI_>), dim3((unsigned)(P_.a.n * P_.a.n_bands)), dim3(kBlock), P_.lds, state().stream, P_.a, \
+                       make_fastdiv((unsigned)P_.a.n_bands), make_fastdiv((unsigned)P_.a.ow))
+#define PV_LRN_POOL_ST(K_, P_, VEC_, BM_, ST_)                          \
+    {                                                                   \
+        if (P_.ni <= 1) PV_LRN_POOL_NI(K_, P_, VEC_, BM_, ST_, 1);      \
+        else if (P_.ni <= 2) PV_LRN_POOL_NI(K_, P_, VEC_, BM_, ST_, 2); \
+        else PV_LRN_POOL_NI(K_, P_, VEC_, BM_, ST_, 4);                 \
+    }
+#define PV_LRN_POOL_BM(K_, P_, VEC_, BM_) \
+    { if (P_.st == 1) PV_LRN_POOL_ST(K_, P_, VEC_, BM_, 1) else PV_LRN_POOL_ST(K_, P_, VEC_, BM_, 2) }
+#define PV_LRN_POOL_LAUNCHER(NAME_, K_)                                                                   \
+    void NAME_(const LrnPoolPlan& plan) {                                                                 \
+        if (plan.vec == 4) { if (plan.bm == 4) PV_LRN_POOL_BM(K_, plan, 4, 4) else PV_LRN_POOL_BM(K_, plan, 4, 1) } \
+        else               { if (plan.bm == 4) PV_LRN_POOL_BM(K_, plan, 1, 4) else PV_LRN_POOL_BM(K_, plan, 1, 1) } \
+    }
+PV_LRN_POOL_LAUNCHER(launch_lrn_maxpool, lrn_maxpool3x3_kernel)
+PV_LRN_POOL_LAUNCHER(launch_maxpool_lrn, maxpool3x3_lrn_kernel)
+#undef PV_LRN_POOL_LAUNCHER
+#undef PV_LRN_POOL_BM
+#undef PV_LRN_POOL_ST
+#undef PV_LRN_POOL_NI
 
 // Fallback for window sizes without a register-window instantiation: every lane re-reads its window.
 __global__ __launch_bounds__(kBlock) void lrn_generic_kernel(const float* __restrict__ x, float* __restrict__ y, int n,
@@ -1006,10 +1070,7 @@ int pvhip_lrn_form(int n, int c, int hw, int size, float beta, float bias, int* 
 
 int pvhip_lrn_maxpool_supported(int n, int c, int h, int w, int size, float beta, float bias, int oh, int ow, int kh, int kw,
                                 int sh, int sw, int pad_top, int pad_left, int pad_bottom, int pad_right) {
-    LrnPoolArgs a{};
-    int vec = 0, bm = 0;
-    size_t lds = 0;
-    return plan_lrn_pool(n, c, h, w, size, beta, bias, oh, ow, kh, kw, sh, sw, pad_top, pad_left, pad_bottom, pad_right, a, vec, bm, lds) ? 1 : 0;
+    return plan_lrn_pool(n, c, h, w, size, beta, bias, oh, ow, kh, kw, sh, sw, pad_top, pad_left, pad_bottom, pad_right).ok ? 1 : 0;
 }
 
 int pvhip_lrn_maxpool_f32(const float* x, float* y, int n, int c, int h, int w, int size, float alpha, float beta, float bias,
@@ -1032,40 +1093,15 @@ int pvhip_lrn_maxpool_f32(const float* x, float* y, int n, int c, int h, int w, 
             }
         }
     }
-    LrnPoolArgs a{};
-    int vec = 0, bm = 0;
-    size_t lds = 0;
-    if (!plan_lrn_pool(n, c, h, w, size, beta, bias, oh, ow, kh, kw, sh, sw, pad_top, pad_left, pad_bottom, pad_right, a, vec, bm, lds))
+    LrnPoolPlan p = plan_lrn_pool(n, c, h, w, size, beta, bias, oh, ow, kh, kw, sh, sw, pad_top, pad_left, pad_bottom, pad_right);
+    if (!p.ok)
         return fail(PVHIP_EUNSUPPORTED, "pvhip_lrn_maxpool_f32: shape outside the fused kernel (ask pvhip_lrn_maxpool_supported first)");
     PVHIP_CHECK_ARG(x != nullptr && y != nullptr);
-    a.x = x; a.y = y; a.alpha = alpha; a.beta = beta; a.bias = bias;
-    a.abl = 0;
+    p.a.x = x; p.a.y = y; p.a.alpha = alpha; p.a.beta = beta; p.a.bias = bias;
 #ifdef PVHIP_DIAG
-    a.abl = settings().conv_ablate;
+    p.a.abl = settings().conv_ablate;
 #endif
-    // four pooled outputs per lane (pool4 in the kernel): PVHIP_TUNE6=1 keeps one per lane (A/B runs)
-    a.pool4 = (vec == 4 && sh == 2 && pad_top == 0 && pad_left == 0 && ow % 4 == 0 && 2 * ow <= w && (ow / 4) * a.band_rows <= kWave && settings().tune[6] != 1) ? 1 : 0;      // (2 ow <= w: the eight columns a quad reads whole lie in the row; only the ninth is clamped)
-    const dim3 grid((unsigned)(n * a.n_bands));
-    const FastDiv d_bands = make_fastdiv((unsigned)a.n_bands), d_ow = make_fastdiv((unsigned)ow);
-    const int ni = (a.band_rows * ow + kBlock - 1) / kBlock;          // 1 at stride 2 (a band holds <= 1024 input pixels), up to 4 at stride 1
-#define PV_LP(VEC_, BM_, ST_, NI_) \
-    hipLaunchKernelGGL((lrn_maxpool3x3_kernel<5, VEC_, BM_, ST_, NI_>), grid, dim3(kBlock), lds, state().stream, a, d_bands, d_ow)
-#define PV_LP_NI(VEC_, BM_, ST_)                                  \
-    {                                                             \
-        if (ni <= 1) PV_LP(VEC_, BM_, ST_, 1);                    \
-        else if (ni <= 2) PV_LP(VEC_, BM_, ST_, 2);               \
-        else PV_LP(VEC_, BM_, ST_, 4);                            \
-    }
-    if (ni > 4) return fail(PVHIP_EUNSUPPORTED, "pvhip_lrn_maxpool_f32: more than four pooled outputs per lane and plane");
-    if (vec == 4) {
-        if (bm == 4) { if (sh == 1) PV_LP_NI(4, 4, 1) else PV_LP_NI(4, 4, 2) }
-        else         { if (sh == 1) PV_LP_NI(4, 1, 1) else PV_LP_NI(4, 1, 2) }
-    } else {
-        if (bm == 4) { if (sh == 1) PV_LP_NI(1, 4, 1) else PV_LP_NI(1, 4, 2) }
-        else         { if (sh == 1) PV_LP_NI(1, 1, 1) else PV_LP_NI(1, 1, 2) }
-    }
-#undef PV_LP_NI
-#undef PV_LP
+    launch_lrn_maxpool(p);
     PVHIP_LAUNCH_CHECK();
     return PVHIP_OK;
 }
@@ -1073,95 +1109,55 @@ int pvhip_lrn_maxpool_f32(const float* x, float* y, int n, int c, int h, int w, 
 // MaxPool (3x3) then LRN as one launch: same coverage rules as the other order (the geometry is the pooling's either way).
 int pvhip_maxpool_lrn_supported(int n, int c, int h, int w, int oh, int ow, int kh, int kw, int sh, int sw, int pad_top, int pad_left,
                                 int pad_bottom, int pad_right, int size, float beta, float bias) {
-    LrnPoolArgs a{};
-    int vec = 0, bm = 0;
-    size_t lds = 0;
-    return plan_lrn_pool(n, c, h, w, size, beta, bias, oh, ow, kh, kw, sh, sw, pad_top, pad_left, pad_bottom, pad_right, a, vec, bm, lds) ? 1 : 0;
+    return plan_lrn_pool(n, c, h, w, size, beta, bias, oh, ow, kh, kw, sh, sw, pad_top, pad_left, pad_bottom, pad_right).ok ? 1 : 0;
 }
 
 int pvhip_maxpool_lrn_f32(const float* x, float* y, int n, int c, int h, int w, int oh, int ow, int kh, int kw, int sh, int sw,
                           int pad_top, int pad_left, int pad_bottom, int pad_right, int size, float alpha, float beta, float bias) {
     PVHIP_REQUIRE_INIT();
-    LrnPoolArgs a{};
-    int vec = 0, bm = 0;
-    size_t lds = 0;
-    if (!plan_lrn_pool(n, c, h, w, size, beta, bias, oh, ow, kh, kw, sh, sw, pad_top, pad_left, pad_bottom, pad_right, a, vec, bm, lds))
+    LrnPoolPlan p = plan_lrn_pool(n, c, h, w, size, beta, bias, oh, ow, kh, kw, sh, sw, pad_top, pad_left, pad_bottom, pad_right);
+    if (!p.ok)
         return fail(PVHIP_EUNSUPPORTED, "pvhip_maxpool_lrn_f32: shape outside the fused kernel (ask pvhip_maxpool_lrn_supported first)");
     PVHIP_CHECK_ARG(x != nullptr && y != nullptr);
-    a.x = x; a.y = y; a.alpha = alpha; a.beta = beta; a.bias = bias;
-    const dim3 grid((unsigned)(n * a.n_bands));
-    const FastDiv d_bands = make_fastdiv((unsigned)a.n_bands), d_ow = make_fastdiv((unsigned)ow);
-    const int ni = (a.band_rows * ow + kBlock - 1) / kBlock;
-    if (ni > 4) return fail(PVHIP_EUNSUPPORTED, "pvhip_maxpool_lrn_f32: more than four pooled outputs per lane and plane");
-#define PV_PL(VEC_, BM_, ST_, NI_) \
-    hipLaunchKernelGGL((maxpool3x3_lrn_kernel<5, VEC_, BM_, ST_, NI_>), grid, dim3(kBlock), lds, state().stream, a, d_bands, d_ow)
-#define PV_PL_NI(VEC_, BM_, ST_)                                  \
-    {                                                             \
-        if (ni <= 1) PV_PL(VEC_, BM_, ST_, 1);                    \
-        else if (ni <= 2) PV_PL(VEC_, BM_, ST_, 2);               \
-        else PV_PL(VEC_, BM_, ST_, 4);                            \
-    }
-    if (vec == 4) {
-        if (bm == 4) { if (sh == 1) PV_PL_NI(4, 4, 1) else PV_PL_NI(4, 4, 2) }
-        else         { if (sh == 1) PV_PL_NI(4, 1, 1) else PV_PL_NI(4, 1, 2) }
-    } else {
-        if (bm == 4) { if (sh == 1) PV_PL_NI(1, 4, 1) else PV_PL_NI(1, 4, 2) }
-        else         { if (sh == 1) PV_PL_NI(1, 1, 1) else PV_PL_NI(1, 1, 2) }
-    }
-#undef PV_PL_NI
-#undef PV_PL
+    p.a.x = x; p.a.y = y; p.a.alpha = alpha; p.a.beta = beta; p.a.bias = bias;
+    launch_maxpool_lrn(p);
     PVHIP_LAUNCH_CHECK();
     return PVHIP_OK;
 }
 
-// MaxPool (3x3) then LRN then a 1x1 / stride 1 / unpadded convolution (+ bias, activation) as ONE launch (round 5): the MaxPool + LRN geometry of
-// pvhip_maxpool_lrn_f32 with one pooled output per lane (bands of at most 256 outputs), a window of five channels, rows of a multiple of four
-// pixels; at most 64 input and 64 output channels (the transposed weights stay in LDS).
-static bool plan_pool_lrn_conv(int n, int c, int h, int w, int oh, int ow, int kh, int kw, int sh, int sw, int pt, int pl, int pb, int pr, int size,
-                               float beta, float bias, int k_out, LrnPoolArgs& a, int& bm, size_t& lds) {
-    int vec = 0;
-    if (!plan_lrn_pool(n, c, h, w, size, beta, bias, oh, ow, kh, kw, sh, sw, pt, pl, pb, pr, a, vec, bm, lds)) return false;
-    if (vec != 4 || a.band_rows * ow > kBlock || k_out <= 0 || k_out > 64 || c > 64) return false;
-    if ((unsigned long long)n * k_out * oh * ow >= (1ull << 31)) return false;
-    lds += (size_t)c * 32 * ((k_out + 31) / 32) * sizeof(float);
-    return lds <= 64 * 1024;
-}
-
+// MaxPool (3x3) then LRN then a 1x1 / stride 1 / unpadded convolution (+ bias, activation) as ONE launch (round 5): see plan_pool_lrn_conv.
 int pvhip_maxpool_lrn_conv1x1_supported(int n, int c, int h, int w, int oh, int ow, int kh, int kw, int sh, int sw, int pad_top, int pad_left,
                                         int pad_bottom, int pad_right, int size, float beta, float bias, int k_out) {
-    LrnPoolArgs a{};
-    int bm = 0;
-    size_t lds = 0;
-    return plan_pool_lrn_conv(n, c, h, w, oh, ow, kh, kw, sh, sw, pad_top, pad_left, pad_bottom, pad_right, size, beta, bias, k_out, a, bm, lds) ? 1 : 0;
+    return plan_pool_lrn_conv(n, c, h, w, oh, ow, kh, kw, sh, sw, pad_top, pad_left, pad_bottom, pad_right, size, beta, bias, k_out).ok ? 1 : 0;
 }
 
 int pvhip_maxpool_lrn_conv1x1_f32(const float* x, const float* w_oihw, float* y, int n, int c, int h, int w, int oh, int ow, int kh, int kw, int sh, int sw,
                                   int pad_top, int pad_left, int pad_bottom, int pad_right, int size, float alpha, float beta, float bias,
                                   int k_out, const float* conv_bias, int act, float act_lo, float act_hi) {
     PVHIP_REQUIRE_INIT();
-    PoolLrnConvArgs ca{};
-    int bm = 0;
-    size_t lds = 0;
-    if (!plan_pool_lrn_conv(n, c, h, w, oh, ow, kh, kw, sh, sw, pad_top, pad_left, pad_bottom, pad_right, size, beta, bias, k_out, ca.p, bm, lds))
+    const LrnPoolPlan p = plan_pool_lrn_conv(n, c, h, w, oh, ow, kh, kw, sh, sw, pad_top, pad_left, pad_bottom, pad_right, size, beta, bias, k_out);
+    if (!p.ok)
         return fail(PVHIP_EUNSUPPORTED, "pvhip_maxpool_lrn_conv1x1_f32: shape outside the fused kernel (ask pvhip_maxpool_lrn_conv1x1_supported first)");
     PVHIP_CHECK_ARG(x != nullptr && w_oihw != nullptr && y != nullptr && act >= 0 && act <= 2);
+    PoolLrnConvArgs ca{};
+    ca.p = p.a;
+    ca.p.pool4 = 0;           // (lrn_maxpool3x3_kernel's)
     ca.p.x = x; ca.p.y = nullptr; ca.p.alpha = alpha; ca.p.beta = beta; ca.p.bias = bias;
     ca.cw = w_oihw; ca.cbias = conv_bias; ca.y = y; ca.k_out = k_out; ca.act = act; ca.act_lo = act_lo; ca.act_hi = act_hi;
     const dim3 grid((unsigned)(n * ca.p.n_bands));
     const FastDiv d_bands = make_fastdiv((unsigned)ca.p.n_bands), d_ow = make_fastdiv((unsigned)ow);
     const int kt = (k_out + 31) / 32;
-#define PV_PLC(BM_, ST_, KT_) hipLaunchKernelGGL((maxpool3x3_lrn_conv1x1_kernel<BM_, ST_, KT_>), grid, dim3(kBlock), lds, state().stream, ca, d_bands, d_ow)
-    if (bm == 4) {
-        if (sh == 1) { if (kt == 1) PV_PLC(4, 1, 1); else PV_PLC(4, 1, 2); }
-        else         { if (kt == 1) PV_PLC(4, 2, 1); else PV_PLC(4, 2, 2); }
+#define PV_PLC(BM_, ST_, KT_) hipLaunchKernelGGL((maxpool3x3_lrn_conv1x1_kernel<BM_, ST_, KT_>), grid, dim3(kBlock), p.lds, state().stream, ca, d_bands, d_ow)
+    if (p.bm == 4) {
+        if (p.st == 1) { if (kt == 1) PV_PLC(4, 1, 1); else PV_PLC(4, 1, 2); }
+        else           { if (kt == 1) PV_PLC(4, 2, 1); else PV_PLC(4, 2, 2); }
     } else {
-        if (sh == 1) { if (kt == 1) PV_PLC(1, 1, 1); else PV_PLC(1, 1, 2); }
-        else         { if (kt == 1) PV_PLC(1, 2, 1); else PV_PLC(1, 2, 2); }
+        if (p.st == 1) { if (kt == 1) PV_PLC(1, 1, 1); else PV_PLC(1, 1, 2); }
+        else           { if (kt == 1) PV_PLC(1, 2, 1); else PV_PLC(1, 2, 2); }
     }
 #undef PV_PLC
     PVHIP_LAUNCH_CHECK();
     return PVHIP_OK;
 }
-
 
 }  // extern "C"

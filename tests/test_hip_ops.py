@@ -1091,6 +1091,120 @@ def test_fused_lrn_pool_query_and_launch_agree(hip):
     assert not dev.call('pvhip_lrn_maxpool_supported', 1, 8, 124, 8, 5, 0.75, 1.0, 126, 10, 3, 3, 1, 1, 2, 2, 2, 2)
 
 
+# Rows for the instantiations of lrn_maxpool3x3_kernel / maxpool3x3_lrn_kernel <5, VEC, BETA_MODE, ST, NI> that the cases above do not
+# launch.  Which one a row reaches was derived from the plan rule (plan_lrn_pool: vec = 4 where w % 4 == 0, the largest band of pooled
+# rows whose input rows fit 256 lanes x vec, bands evened out, ni = ceil(band_rows * ow / 256) rounded up to 1 / 2 / 4); there is no form
+# query for the fused entries, so nothing here can ask the library.
+LRN_POOL_FORM_ROWS = [
+    # (x shape, stride, (pt, pl, pb, pr), rounding, NaN in the input)
+    ((1, 8, 41, 4), 1, (2, 2, 2, 2), 'floor', True),        # vec 4, ST 1, NI 2: 43 x 6 outputs in one band
+    ((1, 8, 84, 4), 1, (2, 2, 2, 2), 'floor', False),       # vec 4, ST 1, NI 4 (ni = 3)
+    ((2, 16, 27, 36), 1, (1, 1, 1, 1), 'floor', False),     # vec 4, ST 1, NI 2: two bands of 14 rows, two chunks of channels
+    ((1, 8, 50, 3), 1, (2, 2, 2, 2), 'floor', False),       # vec 1, ST 1, NI 2
+    ((1, 8, 252, 1), 1, (2, 2, 2, 2), 'floor', False),      # vec 1, ST 1, NI 4 (ni = 3)
+    ((1, 8, 169, 4), 2, (2, 2, 2, 2), 'floor', False),      # vec 4, ST 2, NI 2
+    ((1, 16, 9, 8), 2, (0, 0, 0, 0), 'ceil', False),        # vec 4, ST 2, NI 1, four outputs per lane (pool4); PVHIP_TUNE6=1: one per lane
+]
+# beta = 0.75 with bias = 0 is beta mode 1 (two square roots and a division instead of the log2 / exp2 pair of mode 4)
+LRN_POOL_MODE1_ROWS = [
+    ((1, 16, 9, 12), 1, (1, 1, 1, 1), 'ceil', False),
+    ((2, 8, 13, 20), 2, (1, 1, 0, 0), 'floor', False),
+]
+
+
+def _pooled_extent(size, st, p0, p1, rounding):
+    span = size + p0 + p1 - 3
+    return (span // st if rounding == 'floor' else -(-span // st)) + 1
+
+
+def _lrn_pool_launches(x, st, pads, rounding, bias):
+    """(LRN then MaxPool in two launches, the same fused, MaxPool then LRN in two launches, the same fused) through the C entries."""
+    from pyopenvino_amd import device as dev
+    n, c, h, w = x.shape
+    pt, pl, pb, pr = pads
+    oh, ow = _pooled_extent(h, st, pt, pb, rounding), _pooled_extent(w, st, pl, pr, rounding)
+    geo = (oh, ow, 3, 3, st, st, pt, pl, pb, pr)
+    lrn = (5, 1e-4, 0.75, bias)
+    p = lambda t: ctypes.c_void_p(t.ptr)
+    xd, mid_l, mid_p = dev.DeviceTensor.from_numpy(x), dev.DeviceTensor.empty(x.shape), dev.DeviceTensor.empty((n, c, oh, ow))
+    out = [dev.DeviceTensor.empty((n, c, oh, ow)) for _ in range(4)]
+    assert dev.call('pvhip_lrn_maxpool_supported', n, c, h, w, 5, 0.75, bias, *geo)
+    assert dev.call('pvhip_maxpool_lrn_supported', n, c, h, w, *geo, 5, 0.75, bias)
+    dev.call('pvhip_lrn_f32', p(xd), p(mid_l), n, c, h * w, *lrn)
+    dev.call('pvhip_maxpool2d_f32', p(mid_l), p(out[0]), n, c, h, w, *geo)
+    dev.call('pvhip_lrn_maxpool_f32', p(xd), p(out[1]), n, c, h, w, *lrn, *geo)
+    dev.call('pvhip_maxpool2d_f32', p(xd), p(mid_p), n, c, h, w, *geo)
+    dev.call('pvhip_lrn_f32', p(mid_p), p(out[2]), n, c, oh * ow, *lrn)
+    dev.call('pvhip_maxpool_lrn_f32', p(xd), p(out[3]), n, c, h, w, *geo, *lrn)
+    dev.synchronize()
+    return [np.asarray(t) for t in out]
+
+
+@pytest.mark.parametrize('xs,st,pads,rounding,nan,bias', [r + (1.0,) for r in LRN_POOL_FORM_ROWS] + [r + (0.0,) for r in LRN_POOL_MODE1_ROWS],
+                         ids=lambda v: 'x'.join(map(str, v)) if isinstance(v, tuple) else str(v))
+def test_fused_lrn_pool_instantiations_have_the_bits_of_the_two_launches(hip, xs, st, pads, rounding, nan, bias):
+    """Both orders of LRN and 3x3 MaxPool as one launch, on the shapes that reach the kernel instantiations the model-shaped cases do
+    not: bit for bit what the two launches give, and, where the oracle takes the padding, its two nodes within the tolerance."""
+    from pyopenvino_amd import device as dev
+    x = rnd(sum(xs) + st, xs, 40.0)
+    x[x == 0.0] = 1.0
+    if nan:
+        x[0, 1, 2, 3] = np.nan
+    lp_two, lp_one, pl_two, pl_one = _lrn_pool_launches(x, st, pads, rounding, bias)
+    assert_bit_exact(lp_one, lp_two, 'fused LRN+MaxPool vs two launches {} {}'.format(xs, pads))
+    assert_bit_exact(pl_one, pl_two, 'fused MaxPool+LRN vs two launches {} {}'.format(xs, pads))
+    assert np.isnan(lp_one).any() == nan and np.isnan(pl_one).any() == nan
+    if bias == 1.0 and max(pads) <= 1:
+        axes = np.array([1], dtype=np.int64)
+        lrn_data = {'alpha': '9.9999997473787516e-05', 'beta': '0.75', 'bias': '1', 'size': '5'}
+        pool_node = make_node('MaxPool', [x], pool_data((3, 3), (st, st), pads[:2], pads[2:], rounding))
+        o_lrn = first_out(oracle_plugin('LRN').compute(make_node('LRN', [x, axes], lrn_data), {0: x, 1: axes}, kernel_type='special'))
+        assert_close(lp_one, first_out(oracle_plugin('MaxPool').compute(pool_node, {0: o_lrn}, kernel_type='special')), helpers.REL_TOL,
+                     'fused LRN+MaxPool vs oracle {}'.format(xs))
+        o_pool = first_out(oracle_plugin('MaxPool').compute(pool_node, {0: x}, kernel_type='special'))
+        assert_close(pl_one, first_out(oracle_plugin('LRN').compute(make_node('LRN', [o_pool, axes], lrn_data), {0: o_pool, 1: axes},
+                                                                     kernel_type='special')), helpers.REL_TOL, 'fused MaxPool+LRN vs oracle {}'.format(xs))
+    if st == 2 and max(pads) == 0 and xs[3] % 4 == 0:
+        os.environ['PVHIP_TUNE6'] = '1'         # the one-output-per-lane body of lrn_maxpool3x3_kernel on a shape that takes pool4 by default
+        try:
+            dev.reload_settings()
+            assert_bit_exact(_lrn_pool_launches(x, st, pads, rounding, bias)[1], lp_two, 'fused LRN+MaxPool, one output per lane {}'.format(xs))
+        finally:
+            del os.environ['PVHIP_TUNE6']
+            dev.reload_settings()
+
+
+@pytest.mark.parametrize('xs,st,pb,pe,rounding,k_out,act', [
+    ((1, 24, 12, 16), (1, 1), (1, 1), (1, 1), 'floor', 8, ('clamp', -0.25, 0.5)),       # one 32-channel tile of outputs
+    ((3, 16, 24, 20), (2, 2), (0, 0), (0, 0), 'ceil', 40, None),                        # two
+])
+def test_fused_maxpool_lrn_conv1x1_beta_mode_1_has_the_bits_of_the_three_launches(hip, xs, st, pb, pe, rounding, k_out, act):
+    """maxpool3x3_lrn_conv1x1_kernel with bias = 0 (beta mode 1): bit for bit MaxPool, LRN and the pointwise convolution launched one
+    after the other (those are held to float64 in mode 1 by the LRN-*-m1 rows of test_pool_norm_forms.py)."""
+    x = rnd(sum(xs), xs, 40.0)
+    x[x == 0.0] = 1.0
+    axes = np.array([1], dtype=np.int64)
+    pool_plugin = hip_plugin('MaxPool')
+    pool_node = make_node('MaxPool', [x], pool_data((3, 3), st, pb, pe, rounding))
+    pooled = first_out(pool_plugin.compute(dict(pool_node), {0: x}))
+    lrn_node = make_node('LRN', [pooled, axes], {'alpha': '9.9999997473787516e-05', 'beta': '0.75', 'bias': '0', 'size': '5'})
+    lrn_node['output'][2]['dims'] = tuple(pooled.shape)
+    normed = first_out(hip_plugin('LRN').compute(dict(lrn_node), {0: pooled, 1: axes}))
+    w = rnd(7, (k_out, xs[1], 1, 1), (2.0 / xs[1]) ** 0.5)
+    bias = rnd(9, (1, k_out, 1, 1))
+    conv_node = make_node('Convolution', [normed, w], conv_data((1, 1), (0, 0), (0, 0)))
+    assert pool_plugin.lrn_conv_fusable(pool_node, lrn_node, conv_node)
+    cn = dict(conv_node)
+    cn['_fuse_bias'], cn['_fuse_act'] = hip.DeviceTensor.from_numpy(bias), act
+    three = np.asarray(first_out(hip_plugin('Convolution').compute(cn, {0: normed, 1: w})))
+    fused_node = dict(pool_node)
+    fused_node['_fuse_lrn'] = lrn_node
+    fused_node['_fuse_conv'] = {'node': conv_node, 'w': w, 'bias': hip.DeviceTensor.from_numpy(bias), 'act': act}
+    got = np.asarray(first_out(pool_plugin.compute(fused_node, {0: x})))
+    assert np.isfinite(got).all()
+    assert_bit_exact(got, three, 'fused MaxPool+LRN+1x1, beta mode 1, vs three launches {}'.format(xs))
+
+
 def test_concat_inception_shapes_bit_exact(hip):
     parts = [rnd(i, (3, c, 7, 7)) for i, c in enumerate((384, 384, 128, 128))]
     vs_oracle('Concat', parts, {'axis': '1'})
