@@ -745,6 +745,30 @@ int         pvhip_input_preprocess_yuv_fit_f32(const void* src, float* dst, cons
 int         pvhip_input_preprocess_packed_fit_f32(const void* src, float* dst, const int* rois, int n, int m, int src_h, int src_w,
                                                   int dst_h, int dst_w, int max_roi_h, int max_roi_w, int kind, int reverse_channels,
                                                   const float* mean, const float* std_scale, int fit, float pad_value);
+/* Addition to ABI v18 (the version number is unchanged: nothing existing changed): affine warps.  Image b of `dst` (n, c, dst_h, dst_w) is
+ * frame id of the m frames in `src`, sampled through a 2 x 3 matrix: `table` is a device pointer to n x 7 int64
+ * (id, A00, A01, C0, A10, A11, C1), the coefficients in Q16 (the host's rint(v * 65536), ties to even; |A| <= 2^26, |C| <= 2^40, so
+ * nothing below overflows int64).  `format` says what the frames are and `how` is the last format argument of the matching entry
+ * above: format 0 raw, how = src_u8 | src_nhwc << 1; format 1 YUV 4:2:0, how = planar; format 2 frames of 4-byte units, how = kind.
+ * Output pixel (y, x) of image b, integers for coordinates and fp32 in a fixed order for values:
+ *   SX = A00 x + A01 y + C0,  SY = A10 x + A11 y + C1                                  (int64)
+ *   ix = SX >> 16 (arithmetic: floor),  fx = float(SX & 0xFFFF) * 2^-16 (exact);  iy, fy likewise
+ *   P(r, c) = the pixel of frame id at row r, column c when 0 <= r < src_h and 0 <= c < src_w (compared in int64), else pad_value in
+ *             every channel; for formats 1 and 2 the converted uint8 B, G, R of the entries above (a 4:2:0 pixel takes the chroma of
+ *             its 2 x 2 block of the frame, a 4:2:2 pixel that of its absolute column pair: the same functions, the same constants)
+ *   top = fx == 0 ? P(iy, ix) : (1 - fx) P(iy, ix) + fx P(iy, ix + 1);   bot: the same on row iy + 1, used only when fy != 0
+ *   v   = fy == 0 ? top : (1 - fy) top + fy bot                                        (fp32, in that order, never contracted to fma)
+ * and then the reversal (reverse_channels = 1: output channel k reads channel c-1-k) and (v - mean[k]) / std_scale[k] of the entries
+ * above; pad_value is in source units and goes through them like a pixel.  A zero fraction takes no second tap: an integer translation
+ * is a copy bit for bit (fp32 -0.0, infinities and NaN included), A00 = -65536 a reversed copy.  Pixel centres sit at the integers: the
+ * matrix is the one cv2.warpAffine takes with WARP_INVERSE_MAP.  In numpy: tests/warp_ref.py, matched bit for bit.  The table is read
+ * on the device only: an image whose id is outside [0, m) is written as quiet NaN, and nothing of `src` is read for it.  One launch on
+ * the current stream, no allocation.  The limits of the _roi_ entries for the format (format 0: c <= 1024, fp32 sources 4-byte aligned;
+ * format 1: src_h, src_w even, how 0 or 1; format 2: how in 0..3, src_w even for kinds 0 and 1), and table != NULL, m >= 1, format in
+ * 0..2, how in 0..3 for format 0, c == 3 for formats 1 and 2, pad_value finite; else PVHIP_EINVAL and nothing is launched. */
+int         pvhip_input_preprocess_warp_f32(const void* src, float* dst, const long long* table, int n, int m, int c, int src_h,
+                                            int src_w, int dst_h, int dst_w, int format, int how, int reverse_channels,
+                                            const float* mean, const float* std_scale, float pad_value);
 
 #ifdef __cplusplus
 }

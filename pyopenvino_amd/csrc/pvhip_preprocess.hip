@@ -38,6 +38,25 @@
 // reads; the inner loops replace the value of a pixel outside it by the pad (quads may straddle the edge: dx is any integer; the stores do
 // not change).  The tiles are sized by a bound on the taps' step over every rectangle the launch may meet (Reach), and a workgroup whose
 // tile would still not fit its slots writes NaN instead of staging.  tests/letterbox_ref.py is the rule in numpy.
+//
+// Affine warps (the warp entry; preprocess_warp_kernel): image b is frame id of m frames sampled through a 2 x 3 matrix in Q16,
+// table[b] = (id, A00, A01, C0, A10, A11, C1) as int64.  For output pixel (y, x): SX = A00 x + A01 y + C0, SY = A10 x + A11 y + C1 in
+// int64; ix = SX >> 16, fx = float(SX & 0xFFFF) 2^-16 (exact), iy and fy likewise; P(r, c) is the frame's pixel when 0 <= r < H and
+// 0 <= c < W (64-bit compares), else the pad in every channel -- for the colour formats the B, G, R that yuv_to_bgr / packed_to_bgr
+// give, with the chroma of the pixel's block of the FRAME --; top = fx == 0 ? P(iy, ix) : (1-fx) P(iy, ix) + fx P(iy, ix+1), bot the
+// same on row iy + 1, v = fy == 0 ? top : (1-fy) top + fy bot, then the epilogue of the other kernels.  A zero fraction takes the one
+// tap as it is, so an integer translation is a copy bit for bit.  tests/warp_ref.py is the rule in numpy.
+// This kernel stages nothing: the source footprint of an output tile is a parallelogram, and at the rotations and downscales a warp is
+// for, its bounding box is mostly pixels nobody reads (a 16 x 16 tile at scale 8 and 45 degrees spans about 180^2 source pixels, over
+// kStageBudget).  It gathers its taps from global memory through the caches: a lane produces a quad of one row for every channel
+// (finish_quad, as above), SX and SY advancing by A00 and A10 per pixel, and the format is a fetch functor (RawFetch, Yuv420Fetch,
+// PackedFetch) over pixel<U8>, yuv_to_bgr and packed_to_bgr; the channels of a uint8 NHWC tap, a 4-byte unit and NV12's (U, V) pair
+// are one load each.  Tile: 32 x 32 output pixels per workgroup, 8 quads x 32 rows, so a wave owns 32 x 8 pixels: the most compact
+// footprint whose rows are still whole 128-byte lines of float4 stores per plane -- under a rotation a wave's taps then fall into
+// about as few source lines as its pixel count allows, where the 64 x 16 alternative (a wave: 64 x 4) stretches them along one axis
+// -- and 32 divides the 224 of the classifiers here, which 64 does not.  Measured (profiles/warp_input.md; 256 rows of 1080p frames
+// -> 224 x 224, uint8 NHWC / NV12): 30 degrees at scale 3 313 / 156 us against 326 / 198 us for 64 x 16, upright at scale 3 48.6 /
+// 55.5 us against 47.2 / 53.9 us -- and 174 / 141 us for the ROI launch on the same rectangles.
 #include "pvhip_common.h"
 #include "pvhip_fit_rect.h"
 
@@ -599,6 +618,206 @@ void launch_packed(const PackedArgs& a, dim3 grid, size_t lds, bool vs, bool roi
 #undef PVHIP_PACKED
 }
 
+// ------------------------------------------------------------------------------------------------------------------ affine warps
+// Image b is frame id of m frames sampled through the 2 x 3 matrix of row b of `table` = n x (id, A00, A01, C0, A10, A11, C1), int64,
+// the coefficients in Q16 (the warp entry; the rule is in the file comment and, in numpy, in tests/warp_ref.py).
+struct WarpArgs : TileArgs {
+    const long long* table;
+    int c;
+};
+
+// The tile of a workgroup: kWarpTileW x kWarpTileH output pixels of one image, a quad of one row per lane (kBlock quads).  See the
+// file comment for the choice; -DPVHIP_WARP_TILE_W=64 builds the 64 x 16 alternative scripts/bench_warp_input.py compares it with.
+#ifndef PVHIP_WARP_TILE_W
+#define PVHIP_WARP_TILE_W 32
+#endif
+constexpr int kWarpTileW = PVHIP_WARP_TILE_W, kWarpQuads = kWarpTileW / 4, kWarpTileH = kBlock / kWarpQuads;
+static_assert(kWarpTileW % 4 == 0 && kBlock % kWarpQuads == 0, "a tile is whole quads, one per lane");
+
+// The fetch functors: one frame of the launch's format.  f(r, col, s0, step, kn, p): p[k] = source channel s0 + k step of the pixel at
+// row r, column col of the frame, k < kn <= K (K output channels are produced per pass over the taps; colour formats have K = c = 3).
+// (r, col) is inside the frame.
+template <bool U8, bool NHWC>
+struct RawFetch {
+    static constexpr int K = 4;
+    const unsigned char *frame, *end4;                        // end4: where the last 4 bytes of the m frames start (NULL: fewer than 4)
+    int hs, ws, c;
+    __device__ RawFetch(const WarpArgs& a, int id)
+        : frame(a.src + (size_t)id * ((size_t)a.c * a.hs * a.ws) * (U8 ? 1 : 4)),
+          end4((size_t)a.m * a.c * a.hs * a.ws >= 4 ? a.src + (size_t)a.m * a.c * a.hs * a.ws - 4 : nullptr), hs(a.hs), ws(a.ws), c(a.c) {}
+    __device__ __forceinline__ void operator()(int r, int col, int s0, int step, int kn, float (&p)[K]) const {
+        // NHWC: the channels of a tap lie side by side
+        const int e = NHWC ? (r * ws + col) * c + s0 : (s0 * hs + r) * ws + col, ke = NHWC ? step : step * hs * ws;
+        if (U8 && NHWC && end4 != nullptr) {
+            // ... for bytes within 4 consecutive ones: ONE 32-bit load at any alignment, moved back where it would pass the frames' end
+            const unsigned char* lo = frame + e + (step < 0 ? 1 - kn : 0);
+            const unsigned char* at = lo < end4 ? lo : end4;
+            unsigned w;
+            __builtin_memcpy(&w, at, 4);
+            const int first = (int)(lo - at);
+#pragma unroll
+            for (int k = 0; k < K; ++k) p[k] = k < kn ? (float)((w >> (8 * (first + (step < 0 ? kn - 1 - k : k)))) & 255u) : 0.0f;
+            return;
+        }
+#pragma unroll
+        for (int k = 0; k < K; ++k) p[k] = k < kn ? pixel<U8>(frame, e + k * ke) : 0.0f;
+    }
+};
+
+// B, G, R in the order the output channels take them.
+__device__ __forceinline__ void bgr_in_order(const float (&o)[3], int step, float (&p)[3]) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) p[k] = step < 0 ? o[2 - k] : o[k];
+}
+
+template <bool PLANAR>
+struct Yuv420Fetch {
+    static constexpr int K = 3;
+    const unsigned char *frame, *chroma;
+    int ws, hw, vplane;
+    __device__ Yuv420Fetch(const WarpArgs& a, int id)
+        : frame(a.src + (size_t)id * ((size_t)a.hs * a.ws / 2 * 3)), chroma(frame + (size_t)a.hs * a.ws), ws(a.ws), hw(a.ws >> 1),
+          vplane((a.hs >> 1) * (a.ws >> 1)) {}
+    __device__ __forceinline__ void operator()(int r, int col, int, int step, int, float (&p)[K]) const {
+        const unsigned char* cp = PLANAR ? chroma + (r >> 1) * hw + (col >> 1) : chroma + (r >> 1) * ws + 2 * (col >> 1);
+        float o[3];
+        if (PLANAR) {
+            yuv_to_bgr(frame[r * ws + col], cp[0], cp[vplane], o);
+        } else {
+            unsigned short uv;                                // NV12's (U, V) pair: one 16-bit load at any alignment
+            __builtin_memcpy(&uv, cp, 2);
+            yuv_to_bgr(frame[r * ws + col], uv & 255, uv >> 8, o);
+        }
+        bgr_in_order(o, step, p);
+    }
+};
+
+// A4: the frames are 4-byte aligned, so a unit is one 32-bit load (a frame and a row are whole units); else its bytes one by one.
+template <int KIND, bool A4>
+struct PackedFetch {
+    static constexpr int K = 3;
+    const unsigned char* frame;
+    int row_bytes;
+    __device__ PackedFetch(const WarpArgs& a, int id)
+        : frame(a.src + (size_t)id * ((size_t)a.hs * a.ws * (KIND < 2 ? 2 : 4))), row_bytes(a.ws * (KIND < 2 ? 2 : 4)) {}
+    __device__ __forceinline__ void operator()(int r, int col, int, int step, int, float (&p)[K]) const {
+        const int unit = KIND < 2 ? col >> 1 : col;
+        const unsigned char* g = frame + (size_t)r * row_bytes + (size_t)unit * 4;
+        float o[3];
+        if (A4) {
+            const unsigned w = *reinterpret_cast<const unsigned*>(g);
+            const unsigned char b[4] = {(unsigned char)w, (unsigned char)(w >> 8), (unsigned char)(w >> 16), (unsigned char)(w >> 24)};
+            packed_to_bgr<KIND>(b, 0, col, unit, o);
+        } else {
+            packed_to_bgr<KIND>(g, 0, col, unit, o);
+        }
+        bgr_in_order(o, step, p);
+    }
+};
+
+// The taps of one output pixel along one axis: i0 = S >> 16 and i0 + 1 where they lie inside [0, extent) -- compared in 64 bits --,
+// else index 0 (a load that is always legal, its value replaced by the pad) with in = false; f the fraction, f == 0 exactly when q == 0.
+struct WarpTap {
+    int i0, i1, q;
+    bool in0, in1;
+    float f;
+};
+
+__device__ __forceinline__ WarpTap warp_tap(long long s, int extent) {
+    const long long i = s >> 16;
+    WarpTap t;
+    t.in0 = i >= 0 && i < extent;
+    t.in1 = i + 1 >= 0 && i + 1 < extent;
+    t.i0 = t.in0 ? (int)i : 0;
+    t.i1 = t.in1 ? (int)(i + 1) : 0;
+    t.q = (int)(s & 0xFFFF);
+    t.f = (float)t.q * (1.0f / 65536.0f);
+    return t;
+}
+
+// The quad of one lane: output columns x.. of row y of image t.n, for every channel.  WHOLE: every coefficient of the image's matrix is
+// a whole number (workgroup-uniform), so no pixel has a second tap: the one tap is copied.
+template <class Fetch, bool VS, bool WHOLE>
+__device__ __forceinline__ void warp_quad(const WarpArgs& a, const Tile& t, const Fetch& fetch, int r, int j0, long long sx, long long sy,
+                                          long long ax, long long ay) {
+    constexpr int K = Fetch::K;
+    WarpTap tx[4], ty[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {                             // SX, SY advance by A00, A10 per pixel
+        tx[u] = warp_tap(sx + u * ax, a.ws);
+        ty[u] = warp_tap(sy + u * ay, a.hs);
+    }
+    const size_t plane_out = (size_t)a.hd * a.wd;
+    float* o = a.dst + (size_t)t.n * a.c * plane_out + (size_t)(t.ty0 + r) * a.wd + t.tx0 + j0;
+    for (int oc0 = 0; oc0 < a.c; oc0 += K) {
+        const int kn = min(K, a.c - oc0);
+        const int s0 = a.reverse ? a.c - 1 - oc0 : oc0, step = a.reverse ? -1 : 1;
+        float v[K][4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            if (j0 + u >= t.twv) {                            // (a pixel past the tile is neither fetched nor stored)
+#pragma unroll
+                for (int k = 0; k < K; ++k) v[k][u] = 0.0f;
+                continue;
+            }
+            const WarpTap &cx = tx[u], &cy = ty[u];
+            float p00[K], p01[K], p10[K], p11[K];
+            fetch(cy.i0, cx.i0, s0, step, kn, p00);
+            if (!WHOLE) {
+                fetch(cy.i0, cx.i1, s0, step, kn, p01);
+                fetch(cy.i1, cx.i0, s0, step, kn, p10);
+                fetch(cy.i1, cx.i1, s0, step, kn, p11);
+            }
+            const float gx = 1.0f - cx.f, gy = 1.0f - cy.f;
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                const float q00 = cy.in0 && cx.in0 ? p00[k] : a.pad;
+                if (WHOLE) {
+                    v[k][u] = q00;
+                    continue;
+                }
+                const float q01 = cy.in0 && cx.in1 ? p01[k] : a.pad, q10 = cy.in1 && cx.in0 ? p10[k] : a.pad;
+                const float q11 = cy.in1 && cx.in1 ? p11[k] : a.pad;
+                const float top = cx.q == 0 ? q00 : gx * q00 + cx.f * q01;
+                const float bot = cx.q == 0 ? q10 : gx * q10 + cx.f * q11;
+                v[k][u] = cy.q == 0 ? top : gy * top + cy.f * bot;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < K; ++k)
+            if (k < kn) finish_quad<VS>(a, oc0 + k, v[k], o + (size_t)(oc0 + k) * plane_out, j0, t.twv);
+    }
+}
+
+// grid (ceil(wd / kWarpTileW), ceil(hd / kWarpTileH), n); no LDS.  The table row is read once per workgroup (uniform loads); an image
+// whose id is no frame is filled with quiet NaN and nothing of `src` is read for it.
+template <class Fetch, bool VS>
+__global__ __launch_bounds__(kBlock) void preprocess_warp_kernel(WarpArgs a) {
+    Tile t;
+    t.n = blockIdx.z; t.tx0 = blockIdx.x * kWarpTileW; t.ty0 = blockIdx.y * kWarpTileH;
+    t.twv = min(kWarpTileW, a.wd - t.tx0); t.thv = min(kWarpTileH, a.hd - t.ty0);
+    const long long* q = a.table + 7 * (size_t)t.n;
+    const long long id = q[0];
+    if (!(id >= 0 && id < a.m)) {
+        fill_tile<false>(a, a.c, t, __builtin_nanf(""));
+        return;
+    }
+    const long long a00 = q[1], a01 = q[2], c0 = q[3], a10 = q[4], a11 = q[5], c1 = q[6];
+    const int r = threadIdx.x / kWarpQuads, j0 = 4 * (threadIdx.x % kWarpQuads);
+    if (r >= t.thv || j0 >= t.twv) return;
+    const long long x = t.tx0 + j0, y = t.ty0 + r;            // (|A| <= 2^26, |C| <= 2^40, x, y < 2^31: below 2^59)
+    const long long sx = a00 * x + a01 * y + c0, sy = a10 * x + a11 * y + c1;
+    const Fetch fetch(a, (int)id);
+    if (((a00 | a01 | c0 | a10 | a11 | c1) & 0xFFFF) == 0) warp_quad<Fetch, VS, true>(a, t, fetch, r, j0, sx, sy, a00, a10);
+    else                                                   warp_quad<Fetch, VS, false>(a, t, fetch, r, j0, sx, sy, a00, a10);
+}
+
+template <class Fetch>
+void launch_warp(const WarpArgs& a, dim3 grid, bool vs, hipStream_t st) {
+    if (vs) hipLaunchKernelGGL((preprocess_warp_kernel<Fetch, true>), grid, dim3(kBlock), 0, st, a);
+    else    hipLaunchKernelGGL((preprocess_warp_kernel<Fetch, false>), grid, dim3(kBlock), 0, st, a);
+}
+
 // ---------------------------------------------------------------------------------------------------------------------- launchers
 // The launchers take rois == NULL: image b is the whole of source image b, with m = n and (roi_h, roi_w) = (src_h, src_w); else image b
 // is a rectangle of one of m frames, and the tiles and LDS slots are sized for the largest rectangle (roi_h, roi_w): extent() is
@@ -792,6 +1011,52 @@ int preprocess_packed_launch(const void* src, float* dst, const int* rois, int n
     return PVHIP_OK;
 }
 
+// The one launcher of preprocess_warp_kernel.  format 0 raw (how = src_u8 | src_nhwc << 1), 1 YUV 4:2:0 (how = planar), 2 frames of
+// 4-byte units (how = kind): the limits of the launcher of that format above.
+int preprocess_warp_launch(const void* src, float* dst, const long long* table, int n, int m, int c, int src_h, int src_w, int dst_h,
+                           int dst_w, int format, int how, int reverse_channels, const float* mean, const float* std_scale, float pad_value) {
+    WarpArgs a;
+    int rc = common_args(a, src, dst, nullptr, n, m, c, src_h, src_w, dst_h, dst_w, src_h, src_w, reverse_channels, mean, std_scale);
+    if (rc != PVHIP_OK) return rc;
+    PVHIP_CHECK_ARG(table != nullptr);
+    PVHIP_CHECK_ARG(pad_value - pad_value == 0.0f);
+    PVHIP_CHECK_ARG(format >= 0 && format <= 2);
+    PVHIP_CHECK_ARG(format == 0 || c == 3);
+    PVHIP_CHECK_ARG(how >= 0 && how <= (format == 1 ? 1 : 3));
+    if (format == 0) {
+        PVHIP_CHECK_ARG(c <= kMaxChannels);
+        PVHIP_CHECK_ARG((how & 1) || (uintptr_t)src % 4 == 0);                       // fp32 sources are element-aligned
+    } else if (format == 1) {
+        PVHIP_CHECK_ARG(src_h % 2 == 0 && src_w % 2 == 0);                           // 4:2:0: one (U, V) per 2 x 2 block
+    } else {
+        PVHIP_CHECK_ARG(how >= 2 || src_w % 2 == 0);                                 // 4:2:2: one (U, V) per column pair
+    }
+    const dim3 grid((unsigned)((dst_w + kWarpTileW - 1) / kWarpTileW), (unsigned)((dst_h + kWarpTileH - 1) / kWarpTileH), (unsigned)n);
+    PVHIP_CHECK_ARG(grid.y <= 65535);
+    a.table = table; a.c = c; a.pad = pad_value;
+    const bool vs = (uintptr_t)dst % 16 == 0 && dst_w % 4 == 0;
+    const bool a4 = (uintptr_t)src % 4 == 0;
+    hipStream_t st = state().stream;
+    switch (format * 8 + how * 2 + (format == 2 && a4 ? 1 : 0)) {
+        case 0:  launch_warp<RawFetch<false, false>>(a, grid, vs, st); break;
+        case 2:  launch_warp<RawFetch<true, false>>(a, grid, vs, st); break;
+        case 4:  launch_warp<RawFetch<false, true>>(a, grid, vs, st); break;
+        case 6:  launch_warp<RawFetch<true, true>>(a, grid, vs, st); break;
+        case 8:  launch_warp<Yuv420Fetch<false>>(a, grid, vs, st); break;
+        case 10: launch_warp<Yuv420Fetch<true>>(a, grid, vs, st); break;
+        case 16: launch_warp<PackedFetch<0, false>>(a, grid, vs, st); break;
+        case 17: launch_warp<PackedFetch<0, true>>(a, grid, vs, st); break;
+        case 18: launch_warp<PackedFetch<1, false>>(a, grid, vs, st); break;
+        case 19: launch_warp<PackedFetch<1, true>>(a, grid, vs, st); break;
+        case 20: launch_warp<PackedFetch<2, false>>(a, grid, vs, st); break;
+        case 21: launch_warp<PackedFetch<2, true>>(a, grid, vs, st); break;
+        case 22: launch_warp<PackedFetch<3, false>>(a, grid, vs, st); break;
+        default: launch_warp<PackedFetch<3, true>>(a, grid, vs, st); break;
+    }
+    PVHIP_LAUNCH_CHECK();
+    return PVHIP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -874,5 +1139,12 @@ int pvhip_input_preprocess_packed_fit_f32(const void* src, float* dst, const int
                                     std_scale, used);
 }
 #undef PVHIP_FIT_ARGS
+
+int pvhip_input_preprocess_warp_f32(const void* src, float* dst, const long long* table, int n, int m, int c, int src_h, int src_w,
+                                    int dst_h, int dst_w, int format, int how, int reverse_channels, const float* mean,
+                                    const float* std_scale, float pad_value) {
+    return preprocess_warp_launch(src, dst, table, n, m, c, src_h, src_w, dst_h, dst_w, format, how, reverse_channels, mean, std_scale,
+                                  pad_value);
+}
 
 }  // extern "C"

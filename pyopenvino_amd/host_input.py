@@ -7,7 +7,7 @@ import ctypes
 import numpy as np
 
 from . import detections as detections_rule, device
-from .input_format import DetectedRois, DetectedTable, RoiInput
+from .input_format import DetectedRois, DetectedTable, RoiInput, WarpInput
 
 
 class _Staging:
@@ -35,14 +35,14 @@ class _Slot:
     -- a RoiInput's frames under (extent, m) --, and the (n, 5) int32 table of a RoiInput, page-locked and on the device, once one is fed.
     The device table is the head of one block `table` of 6 n + 2 ints, (n, 5) rois | (n,) record_of | (count, selected): what
     pvhip_detections_to_rois writes for a DetectedRois (`detected`: what that needs besides, once one is fed) and detected_rois() reads
-    back in one copy."""
-    __slots__ = ('fixed', 'event', 'mean', 'std', 'extents', 'rois_host', 'rois', 'table', 'detected', 'fed')
+    back in one copy.  `warps_host` / `warps`: the (n, 7) int64 table of a WarpInput, page-locked and on the device, once one is fed."""
+    __slots__ = ('fixed', 'event', 'mean', 'std', 'extents', 'rois_host', 'rois', 'table', 'detected', 'fed', 'warps_host', 'warps')
 
     def __init__(self, fmt):
         self.fixed, self.event = device.DeviceTensor.empty(fmt.dims), device.Event(timed=False)
         self.mean, self.std = (None, None) if fmt.mean is None else (device.DeviceTensor.from_numpy(fmt.mean), device.DeviceTensor.from_numpy(fmt.std))
         self.extents = collections.OrderedDict()
-        self.rois_host = self.rois = self.table = self.detected = None
+        self.rois_host = self.rois = self.table = self.detected = self.warps_host = self.warps = None
         self.fed = None                         # the extent of the whole images the last pass was staged from (what a declared fit fitted)
 
     def roi_table(self):
@@ -52,6 +52,13 @@ class _Slot:
             self.table = device.DeviceTensor.empty((6 * n + 2,), np.int32)
             self.rois = device.DeviceTensor(self.table._block, (n, 5), np.int32)
         return self.rois_host
+
+    def warp_table(self):
+        if self.warps_host is None:
+            n = self.fixed.shape[0]
+            self.warps_host = device.host_empty((n, 7), np.int64)
+            self.warps = device.DeviceTensor.empty((n, 7), np.int64)
+        return self.warps_host
 
 
 class _Detected:
@@ -123,6 +130,34 @@ class HostInputs:
         fmt = self._format(name)
         fmt.checked_frames(1)               # (a resize is declared)
         return self._slot(name).roi_table()
+
+    def warp_buffer(self, name) -> np.ndarray:
+        """The page-locked (n, 7) int64 table a WarpInput of input `name` is uploaded from."""
+        fmt = self._format(name)
+        fmt.warp_declared()
+        return self._slot(name).warp_table()
+
+    def _stage_warps(self, name, fmt, warp):
+        """The frames and the table of WarpInput `warp` in this request's page-locked buffers -- copied, unless they are those buffers
+        --, everything checked before anything is allocated: the staging."""
+        fmt.warp_declared()
+        frames = warp.frames if isinstance(warp.frames, np.ndarray) else np.asarray(warp.frames)
+        extent, m = fmt.frames_extent_of(frames, 'WarpInput')
+        slot, given = self.slots.get(name), warp.matrices
+        own = (slot is not None and slot.warps_host is not None and isinstance(given, np.ndarray) and given.dtype == np.int64
+               and given.shape == slot.warps_host.shape and given.flags.c_contiguous and given.ctypes.data == slot.warps_host.ctypes.data)
+        if own:
+            if warp.ids is not None:
+                raise ValueError('input {}: the warp_buffer holds the frame of each row in its first column: ids is None with it'.format(name))
+            fmt.checked_warp_table(given, m)
+        else:
+            table = fmt.checked_warps(given, warp.ids, m)
+        staged = self._staging(name, extent, m)
+        if not (frames.dtype == staged.host.dtype and frames.flags.c_contiguous and frames.ctypes.data == staged.host.ctypes.data):
+            np.copyto(staged.host, frames, casting='same_kind' if staged.host.dtype == np.float32 else 'safe')
+        if not own:
+            np.copyto(self.slots[name].warp_table(), table)
+        return staged
 
     def _stage_rois(self, name, fmt, roi):
         """The frames and the table of RoiInput `roi` in this request's page-locked buffers -- copied, unless they are those buffers --,
@@ -255,18 +290,23 @@ class HostInputs:
         return staged
 
     @staticmethod
-    def _convert(fmt, slot, staged, largest):
+    def _convert(fmt, slot, staged, largest, warped=False):
         """The one launch that makes `slot.fixed` of what `staged` uploaded (none for FP32 NCHW at the network's extent):
         pvhip_input_preprocess_yuv_f32 for NV12 / I420 frames, pvhip_input_preprocess_packed_f32 for YUY2 / UYVY / BGRX / RGBX frames,
         pvhip_input_preprocess_f32 when a resize, channel reversal or mean / scale is in effect, else pvhip_input_to_nchw_f32;
         `largest` = (max_h, max_w) of a RoiInput's table: the _roi_f32 forms.  A declared fit: the _fit_f32 forms of the three, with
-        the table or NULL."""
+        the table or NULL.  `warped`: the frames of a WarpInput: pvhip_input_preprocess_warp_f32 for every format, whatever fit is
+        declared."""
         fixed = slot.fixed
         src, dst = device.ptr(staged.staging), device.ptr(fixed)
         n, c, dst_hw = fixed.shape[0], fixed.shape[1], fixed.shape[2:]
         how = (int(fmt.color == 'I420'),) if fmt.yuv else (fmt.packed_kind,) if fmt.packed else (int(fmt.u8), int(fmt.nhwc))
         pre = (int(fmt.reverse), device.ptr(slot.mean), device.ptr(slot.std))
-        if fmt.fitted and (largest is not None or fmt.yuv or fmt.packed or staged.preprocess):
+        if warped:
+            form = (1, how[0]) if fmt.yuv else (2, how[0]) if fmt.packed else (0, how[0] | how[1] << 1)
+            device.call('pvhip_input_preprocess_warp_f32', src, dst, device.ptr(slot.warps), n, staged.frames, c, *staged.extent, *dst_hw,
+                        *form, *pre, fmt.pad)
+        elif fmt.fitted and (largest is not None or fmt.yuv or fmt.packed or staged.preprocess):
             where = (src, dst, device.ptr(slot.rois if largest is not None else None), n, staged.frames if largest is not None else n)
             sizes = (*staged.extent, *dst_hw, *(largest if largest is not None else staged.extent))
             tail = (*how, *pre, fmt.fit_code, fmt.pad)
@@ -297,7 +337,7 @@ class HostInputs:
         """`inputs` with every host input of a declared format, or in one of this request's own buffers, replaced by the request's fixed
         tensor: the caller's array is copied into the page-locked buffer of its extent unless it IS that buffer, the buffer is uploaded on
         the copy stream, stream `stream_base` waits for the copy's event and converts (_convert: one launch at the most).  A RoiInput's
-        frames and table go the same way, both uploaded on the copy stream behind the one event.  A DetectedRois' frames too -- with its
+        frames and table go the same way, both uploaded on the copy stream behind the one event, and so do a WarpInput's.  A DetectedRois' frames too -- with its
         labels, and its records when they are a host array --; its table is made by pvhip_detections_to_rois on `stream_base`, behind the
         detector's pass when the records are the Result of a request in flight, and the ROI launch is sized for whole frames: the host
         never sees the table (`sharded`: the batch is sharded over ranks, which a DetectedRois refuses).
@@ -306,7 +346,11 @@ class HostInputs:
         out = dict(inputs)
         for name, arr in inputs.items():
             fmt, largest, uploads, make_table = self.formats.get(name), None, (), None
-            if isinstance(arr, RoiInput):
+            warped = isinstance(arr, WarpInput)
+            if warped:
+                staged = self._stage_warps(name, self._format(name), arr)
+                uploads = ((self.slots[name].warps, self.slots[name].warps_host),)
+            elif isinstance(arr, RoiInput):
                 staged, largest = self._stage_rois(name, self._format(name), arr)
                 uploads = ((self.slots[name].rois, self.slots[name].rois_host),)
             elif isinstance(arr, DetectedRois):
@@ -321,7 +365,7 @@ class HostInputs:
                 if staged is None:
                     continue
             slot = self.slots[name]
-            slot.fed = staged.extent if largest is None else None
+            slot.fed = staged.extent if largest is None and not warped else None
             slot.extents.move_to_end(staged.key)
             while len(slot.extents) > self.MAX_SOURCE_EXTENTS:
                 slot.extents.popitem(last=False)
@@ -338,7 +382,7 @@ class HostInputs:
                     slot.detected.source = None
             if make_table is not None:
                 make_table()
-            self._convert(fmt, slot, staged, largest)
+            self._convert(fmt, slot, staged, largest, warped)
             device.select_stream(0)
             out[name] = slot.fixed
         return out

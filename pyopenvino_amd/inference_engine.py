@@ -401,6 +401,13 @@ class InferRequest:
         ``input_buffer``."""
         return self.runner.host_inputs.roi_buffer(name)
 
+    def warp_buffer(self, name: str) -> np.ndarray:
+        """The page-locked (n, 7) int64 table this request uploads the matrices of a ``WarpInput`` of input `name` from, row b =
+        (id, A00, A01, C0, A10, A11, C1) with the coefficients in Q16 (``WarpInput.fixed``).  ``WarpInput(input_buffer(name, (h, w),
+        frames=m), warp_buffer(name))`` costs no host copy; its values are checked by the limits of ``WarpInput.fixed`` when the pass
+        starts; ownership as for ``input_buffer``."""
+        return self.runner.host_inputs.warp_buffer(name)
+
     def detected_rois(self, name: str):
         """After ``wait()`` of a pass whose input `name` was a ``DetectedRois``: the record (count, selected, rois, records) -- `rois` the
         (n, 5) int32 table that pass used, rows >= count being (-1, 0, 0, 0, 0); `records[k]` the flat row of the detections batch row

@@ -160,10 +160,10 @@ class InputFormat:
                 self.name, declared, self.host_shape(('h', 'w')), self._packed_any_hw(), a.shape))
         return self.checked_extent(a.shape[1:3])
 
-    def _roi_declared(self):
+    def _roi_declared(self, what='RoiInput is cropped and resized'):
         if not self.resize:
-            raise ValueError('input {}: a RoiInput is cropped and resized on the device: it needs a declared resize '
-                             '(preprocess_info.resize_algorithm = \'RESIZE_BILINEAR\')'.format(self.name))
+            raise ValueError('input {}: a {} on the device: it needs a declared resize '
+                             '(preprocess_info.resize_algorithm = \'RESIZE_BILINEAR\')'.format(self.name, what))
 
     def checked_frames(self, frames) -> int:
         """The frame count m of a RoiInput as an int >= 1 (any count: it is independent of the batch)."""
@@ -172,9 +172,12 @@ class InputFormat:
             raise ValueError('input {}: a RoiInput has m >= 1 frames, not {!r}'.format(self.name, frames))
         return int(frames)
 
-    def frames_extent_of(self, a):
-        """((h, w), m) of the frames array `a` of a RoiInput, checked against this format."""
-        self._roi_declared()
+    def frames_extent_of(self, a, what='RoiInput'):
+        """((h, w), m) of the frames array `a` of a RoiInput (`what`: of a WarpInput), checked against this format."""
+        if what == 'RoiInput':
+            self._roi_declared()
+        else:
+            self.warp_declared()
         if self.yuv:
             ok = a.ndim == 3 and a.shape[0] >= 1 and a.shape[1] % 3 == 0
             declared, any_hw = 'declared {}'.format(self.color), 'any even h, w'
@@ -185,8 +188,8 @@ class InputFormat:
             ok = a.ndim == 4 and a.shape[0] >= 1 and a.shape[3 if self.nhwc else 1] == self.dims[1]
             declared, any_hw = 'declared {} / {}'.format('U8' if self.u8 else 'FP32', 'NHWC' if self.nhwc else 'NCHW'), 'any h, w'
         if not ok:
-            raise ValueError('input {}: {} frames of a RoiInput have shape {} for any m >= 1 and {}; got {}'.format(
-                self.name, declared, self.host_shape(('h', 'w'), frames='m'), any_hw, a.shape))
+            raise ValueError('input {}: {} frames of a {} have shape {} for any m >= 1 and {}; got {}'.format(
+                self.name, declared, what, self.host_shape(('h', 'w'), frames='m'), any_hw, a.shape))
         if self.yuv:
             return self.checked_extent((a.shape[1] // 3 * 2, a.shape[2])), a.shape[0]
         return self.checked_extent(a.shape[1:3] if self.nhwc or self.packed else a.shape[2:4]), a.shape[0]
@@ -213,6 +216,58 @@ class InputFormat:
             raise ValueError('input {}: rois[{}] = {} is no rectangle (id, x, y, w, h) with w, h >= 1 inside one of {} frames of {}'.format(
                 self.name, b, tuple(int(v) for v in t[b]), frames, (H, W)))
         return np.ascontiguousarray(t, np.int32), (int(h.max()), int(w.max()))
+
+    def warp_declared(self):
+        self._roi_declared('WarpInput is sampled')
+
+    def _checked_warp_ids(self, ids, frames):
+        """The frame of every row of a WarpInput over `frames` frames as n ints in [0, frames): `ids`, or by default row b's frame b
+        (frames == n) or frame 0 (frames == 1)."""
+        n = self.dims[0]
+        if ids is None:
+            if frames != n and frames != 1:
+                raise ValueError('input {}: a WarpInput without ids reads frame b for row b (m == n) or frame 0 (m == 1); with {} frames '
+                                 'for {} rows, ids names the frame of each row'.format(self.name, frames, n))
+            return np.arange(n, dtype=np.int64) if frames == n else np.zeros(n, np.int64)
+        i = np.asarray(ids)
+        if i.shape != (n,) or i.dtype.kind not in 'iu':
+            raise ValueError('input {}: ids holds {} integers, the frame of each batch row; got {} {}'.format(self.name, n, i.dtype, i.shape))
+        if i.dtype == np.uint64:
+            i = np.minimum(i, np.uint64(np.iinfo(np.int64).max))
+        i = i.astype(np.int64)
+        bad = (i < 0) | (i >= frames)
+        if bad.any():
+            b = int(np.argmax(bad))
+            raise ValueError('input {}: ids[{}] = {} is none of {} frames'.format(self.name, b, int(i[b]), frames))
+        return i
+
+    def checked_warps(self, matrices, ids, frames):
+        """The table of a WarpInput over `frames` frames as a C-contiguous int64 (n, 7) array, row b = (id, A00, A01, C0, A10, A11, C1):
+        ``WarpInput.fixed(matrices)`` behind the frame of each row (`ids`, or its default)."""
+        self.warp_declared()
+        n = self.dims[0]
+        try:
+            q = WarpInput.fixed(matrices)
+        except ValueError as e:
+            raise ValueError('input {}: {}'.format(self.name, e)) from None
+        if q.shape[0] != n:
+            raise ValueError('input {}: matrices has shape {} -- one 2 x 3 matrix per batch row --, got {}'.format(
+                self.name, (n, 2, 3), np.shape(matrices)))
+        table = np.empty((n, 7), np.int64)
+        table[:, 0] = self._checked_warp_ids(ids, frames)
+        table[:, 1:] = q
+        return table
+
+    def checked_warp_table(self, table, frames):
+        """`table`, an int64 (n, 7) array already in the device's form (``InferRequest.warp_buffer``), checked by the limits of
+        ``WarpInput.fixed`` and ``ids``; returned as it is."""
+        self.warp_declared()
+        bad = WarpInput.beyond_limits(table[:, 1:])
+        if bad.any():
+            b = int(np.argmax(bad))
+            raise ValueError('input {}: {}'.format(self.name, WarpInput.limit_text(b, table[b, 1:])))
+        self._checked_warp_ids(table[:, 0], frames)
+        return table
 
     def needs_preprocess(self, extent) -> bool:
         """Arrays of `extent` go through pvhip_input_preprocess_f32 (YUV 4:2:0 frames: pvhip_input_preprocess_yuv_f32, frames of 4-byte
@@ -244,6 +299,68 @@ class RoiInput:
 
     def __repr__(self):
         return 'RoiInput(frames={}, rois={})'.format(getattr(self.frames, 'shape', None), getattr(self.rois, 'shape', None))
+
+
+class WarpInput:
+    """A network input given as affine warps of frames (a face aligned by its eye line, a plate cut along its own axis, a rotated box, a
+    mirrored copy): ``infer({name: WarpInput(frames, matrices, ids)})``, wherever a RoiInput is accepted.  `frames`: m >= 1 source
+    frames in the input's declared host format, exactly as for RoiInput (every format: U8 / FP32, NHWC / NCHW, NV12, I420, YUY2, UYVY,
+    BGRX, RGBX); uploaded once and not modified.  `matrices`: real numbers of shape (n, 2, 3); row b maps an OUTPUT pixel index (x, y)
+    of the network's extent to a SOURCE position in frame pixels, sx = a00 x + a01 y + c0, sy = a10 x + a11 y + c1, pixel centres at
+    the integers: the matrix ``cv2.warpAffine(..., flags=INTER_LINEAR | WARP_INVERSE_MAP)`` takes (pyopenvino_amd.warp has helpers:
+    ``invert`` of a forward matrix, ``from_roi``, ``rotated_rect``, ``apply``).  `ids`: (n,) integers in [0, m), the frame each row
+    reads; None: row b reads frame b when m == n and frame 0 when m == 1.  The device samples every row bilinearly in one launch
+    (pvhip_input_preprocess_warp_f32; the rule in numpy: tests/warp_ref.py): the coefficients are quantised to Q16 on the host
+    (``WarpInput.fixed``), coordinates are 64-bit integers, a tap outside the frame has the value ``preprocess_info.pad_value`` in
+    every channel (in source units: it goes through mean / scale like a pixel), no antialiasing; then reversal and mean / scale as
+    declared.  A zero fraction reads no second tap, so an integer translation is a copy bit for bit and a mirror a reversed copy.  For
+    the colour formats a pixel is the converted B, G, R with the chroma of its block of the frame.  The input needs
+    ``preprocess_info.resize_algorithm = 'RESIZE_BILINEAR'``.  A declared ``resize_fit`` plays no part in a warp: the matrix places
+    the pixels (``infer(..., detections=)`` on such an input refuses a WarpInput as it does a RoiInput).  ``warp.from_roi`` is NOT bit
+    for bit a RoiInput at scales other than 1: a RoiInput's taps clamp at the rectangle's edge and its fractions are exact rationals,
+    a warp's are Q16 and its border is the pad.  With `frames` = ``InferRequest.input_buffer(name, (h, w), frames=m)`` and `matrices`
+    = ``InferRequest.warp_buffer(name)`` -- the (n, 7) int64 table (id, A00, A01, C0, A10, A11, C1) itself, `ids` None -- nothing
+    is copied on the host."""
+    __slots__ = ('frames', 'matrices', 'ids')
+    LINEAR_LIMIT = 1 << 26           # |A| at most: a scale of 1024
+    TRANSLATION_LIMIT = 1 << 40      # |C| at most: 2^24 pixels
+
+    def __init__(self, frames, matrices, ids=None):
+        self.frames, self.matrices, self.ids = frames, matrices, ids
+
+    def __repr__(self):
+        return 'WarpInput(frames={}, matrices={})'.format(getattr(self.frames, 'shape', None), getattr(self.matrices, 'shape', None))
+
+    @classmethod
+    def beyond_limits(cls, q):
+        """Which rows of (n, 6) Q16 coefficients (A00, A01, C0, A10, A11, C1), int64 or float64, break a limit."""
+        a, c = q[:, [0, 1, 3, 4]], q[:, [2, 5]]               # (no np.abs: the smallest int64 has none)
+        return ((a > cls.LINEAR_LIMIT) | (a < -cls.LINEAR_LIMIT)).any(1) | ((c > cls.TRANSLATION_LIMIT) | (c < -cls.TRANSLATION_LIMIT)).any(1)
+
+    @staticmethod
+    def limit_text(b, row):
+        return ('matrices[{}] is beyond the limits of a warp -- finite, |a| <= 1024 for the four linear terms, |c| <= 2^24 for the '
+                'translations --: in Q16 {}'.format(b, [float(v) for v in row]))
+
+    @classmethod
+    def fixed(cls, matrices) -> np.ndarray:
+        """(n, 6) int64: the coefficients (a00, a01, c0, a10, a11, c1) of every row in Q16, ``np.rint(np.float64(v) * 65536)`` (ties to
+        even), as the device takes them.  ValueError, naming the row, for a value that is not finite, |A| > 2^26 for a linear term or
+        |C| > 2^40 for a translation: with these limits A00 x + A01 y + C0 cannot overflow int64 for any extent a launch admits.  Host
+        arithmetic only: no device is needed."""
+        t = np.asarray(matrices)
+        if t.ndim != 3 or t.shape[1:] != (2, 3):
+            raise ValueError('matrices has shape (n, 2, 3) -- one 2 x 3 matrix per batch row --, got {}'.format(t.shape))
+        if t.dtype.kind not in 'fiu':
+            raise ValueError('matrices holds real numbers, got dtype {}'.format(t.dtype))
+        with np.errstate(invalid='ignore', over='ignore'):
+            q = np.rint(t.astype(np.float64).reshape(-1, 6) * 65536.0)
+        bad = ~np.isfinite(q).all(1)
+        bad |= cls.beyond_limits(np.where(np.isfinite(q), q, 0.0))
+        if bad.any():
+            b = int(np.argmax(bad))
+            raise ValueError(cls.limit_text(b, q[b]))
+        return q.astype(np.int64)
 
 
 class DetectedRois:
@@ -544,6 +661,9 @@ class PreProcessInfo:
 
     @property
     def pad_value(self):
+        """One finite fp32 number in source units (default 0) that goes through mean / scale like a pixel: what a declared
+        ``resize_fit`` fills the extent outside the fitted rectangle with, and the value, in every channel, of a tap of a ``WarpInput``
+        outside its frame (there with or without a declared fit)."""
         return self._pad
 
     @pad_value.setter
