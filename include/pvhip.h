@@ -769,6 +769,45 @@ int         pvhip_input_preprocess_packed_fit_f32(const void* src, float* dst, c
 int         pvhip_input_preprocess_warp_f32(const void* src, float* dst, const long long* table, int n, int m, int c, int src_h,
                                             int src_w, int dst_h, int dst_w, int format, int how, int reverse_channels,
                                             const float* mean, const float* std_scale, float pad_value);
+/* Addition to ABI v18 (the version number is unchanged: nothing existing changed): the YUV launches above for frames of another matrix
+ * or range (preprocess_info.color_standard / color_range).  ONE integer rule converts every YUV pixel, in 32-bit ints with arithmetic
+ * shifts, and six ints say which encoding it undoes:
+ *   y = max(Y - yoff, 0),  u = U - 128,  v = V - 128,  t = y CY + 2^19
+ *   B = clamp((t + CBU u) >> 20),  G = clamp((t - CGV v - CGU u) >> 20),  R = clamp((t + CRV v) >> 20)        clamp to [0, 255]
+ *   matrix  full_range                       yoff       CY      CRV      CGV      CGU      CBU
+ *     0         0       BT.601 limited        16   1220542  1673527   852492   409993  2116026    (what every entry above applies)
+ *     0         1       BT.601 full (JFIF)     0   1048576  1470104   748826   360853  1858077
+ *     1         0       BT.709 limited        16   1220945  1879825   558796   223607  2215014
+ *     1         1       BT.709 full            0   1048576  1651297   490864   196424  1945738
+ *     2         0       BT.2020 limited       16   1220945  1760217   682019   196426  2245811
+ *     2         1       BT.2020 full           0   1048576  1546230   599107   172546  1972791
+ * Row (0, 0) is cv2's three-decimal coefficients, kept bit for bit; every other row is rint(x 2^20) of CRV = 2 (1 - Kr), CBU = 2 (1 - Kb),
+ * CGV = 2 Kr (1 - Kr) / Kg, CGU = 2 Kb (1 - Kb) / Kg with Kg = 1 - Kr - Kb and (Kr, Kb) = (0.299, 0.114), (0.2126, 0.0722),
+ * (0.2627, 0.0593), times 255/224 for limited range, where CY = 255/219 too.  Over all 2^24 byte triples every intermediate stays below
+ * 5.8e8 and each channel is within 1 of the rounded, clamped float64 matrix value.  The chroma a pixel takes does not change (4:2:0: its
+ * 2 x 2 block; 4:2:2: its absolute column pair; no interpolation), nor does anything behind the conversion.  In numpy:
+ * tests/colorimetry_ref.py.
+ *   _yuv_color_     the arguments of pvhip_input_preprocess_yuv_fit_f32, then matrix and full_range.  fit may be 0 as well: the stretch,
+ *                   whatever pad_value holds.  fit = 0 and rois == NULL is pvhip_input_preprocess_yuv_f32, fit = 0 with a table
+ *                   pvhip_input_preprocess_yuv_roi_f32; with (matrix, full_range) = (0, 0) each form is its existing entry bit for bit.
+ *   _packed_color_  the same over pvhip_input_preprocess_packed_fit_f32; kinds 2 and 3 hold nothing to convert: PVHIP_EINVAL for them
+ *                   unless matrix and full_range are both 0.
+ *   _warp_color_    the arguments of pvhip_input_preprocess_warp_f32, then matrix and full_range; format 0, and format 2 with how 2 or 3,
+ *                   likewise only with both 0.
+ * One launch on the current stream, no allocation; the kernels of the entries above, reading the six ints from the launch arguments
+ * ((0, 0) takes the very instantiations of those entries, whose constants are literals).  The
+ * limits of the entry each generalises, matrix in 0..2, full_range 0 or 1; else PVHIP_EINVAL and nothing is launched. */
+int         pvhip_input_preprocess_yuv_color_f32(const void* src, float* dst, const int* rois, int n, int m, int src_h, int src_w,
+                                                 int dst_h, int dst_w, int max_roi_h, int max_roi_w, int planar, int reverse_channels,
+                                                 const float* mean, const float* std_scale, int fit, float pad_value, int matrix,
+                                                 int full_range);
+int         pvhip_input_preprocess_packed_color_f32(const void* src, float* dst, const int* rois, int n, int m, int src_h, int src_w,
+                                                    int dst_h, int dst_w, int max_roi_h, int max_roi_w, int kind, int reverse_channels,
+                                                    const float* mean, const float* std_scale, int fit, float pad_value, int matrix,
+                                                    int full_range);
+int         pvhip_input_preprocess_warp_color_f32(const void* src, float* dst, const long long* table, int n, int m, int c, int src_h,
+                                                  int src_w, int dst_h, int dst_w, int format, int how, int reverse_channels,
+                                                  const float* mean, const float* std_scale, float pad_value, int matrix, int full_range);
 
 #ifdef __cplusplus
 }

@@ -358,29 +358,71 @@ void launch(const PrepArgs& a, dim3 grid, size_t lds, bool vs, hipStream_t st) {
 
 // ---------------------------------------------------------------------------------------------------------------- YUV 4:2:0 sources
 // A decoder's frame -- uint8, 3 h / 2 rows of w bytes per image: the Y plane, then NV12's h/2 rows of w/2 (U, V) pairs or I420's U plane
-// and V plane of h/2 x w/2 bytes each -- converted to B, G, R by the BT.601 limited-range rule in 20-bit fixed point
-//   t = max(Y - 16, 0) * 1220542 + 2^19,  R = (t + 1673527 (V - 128)) >> 20,  G = (t - 852492 (V - 128) - 409993 (U - 128)) >> 20,
-//   B = (t + 2116026 (U - 128)) >> 20  (arithmetic shifts), each clamped to [0, 255],
-// with the (U, V) of the pixel's 2 x 2 block (no chroma interpolation); the uint8 image that gives is then resized, reversed and scaled
-// exactly as a U8 NHWC source is above.  tests/yuv_ref.py is the conversion in numpy; every intermediate stays within +-5.7e8.
+// and V plane of h/2 x w/2 bytes each -- converted to B, G, R by ONE rule in 20-bit fixed point, whose six ints (YuvRule) say which
+// matrix and range the frames were encoded with (preprocess_info.color_standard / color_range; kYuvRules):
+//   t = max(Y - yoff, 0) * CY + 2^19,  R = (t + CRV (V - 128)) >> 20,  G = (t - CGV (V - 128) - CGU (U - 128)) >> 20,
+//   B = (t + CBU (U - 128)) >> 20  (arithmetic shifts), each clamped to [0, 255],
+// BT.601 limited range -- yoff 16 and 1220542, 1673527, 852492, 409993, 2116026 -- where nothing is declared, with the (U, V) of the
+// pixel's 2 x 2 block (no chroma interpolation); the uint8 image that gives is then resized, reversed and scaled exactly as a U8 NHWC
+// source is above.  tests/yuv_ref.py is the BT.601 conversion in numpy and tests/colorimetry_ref.py all six; every intermediate stays
+// within +-5.8e8.
 //
 // A tile stages the Y spans it reads and, behind them, the chroma spans under them: rows ys0/2..ys1/2, of each the pairs xs0/2..xs1/2 of
 // the ABSOLUTE columns (a tile may start on an odd column) -- one span per row for NV12, one in each plane for I420.  A pixel is converted
 // where it is tapped, so a downscale converts four pixels per output pixel however many it staged, and the three channels of a quad come
 // from one pass over its taps.
+//
+// The rule of a launch.  It travels in the launch arguments, so the kernels read it from scalar registers: one yuv_to_bgr, and no
+// kernel instantiation per rule -- but one more of each staged kernel, LIT, in which the rule is row [0][0] as literals: what every
+// launch without a declared standard or range takes, instruction for instruction the code it was before rules were arguments.  From
+// scalar registers the same conversion schedules 1.4 to 4 % slower (profiles/colorimetry.md), which a declared rule pays and the
+// default does not.  The warp kernel gathers from global memory and showed no difference: it has the one form.
+struct YuvRule {
+    int yoff, cy, crv, cgv, cgu, cbu;
+};
+
+// kYuvRules[matrix][full_range]: matrix 0 BT.601, 1 BT.709, 2 BT.2020.  Row [0][0] is the three-decimal constants of cv2 (1.164, 1.596,
+// 0.813, 0.391, 2.018); every other row is rint(x 2^20) of 2 (1 - Kr), 2 Kr (1 - Kr) / Kg, 2 Kb (1 - Kb) / Kg, 2 (1 - Kb) with
+// (Kr, Kb) = (0.299, 0.114), (0.2126, 0.0722), (0.2627, 0.0593) and Kg = 1 - Kr - Kb, times 255/224 (and the luma gain 255/219) for
+// limited range.  yoff = 0 makes the luma clamp the identity: full range is no second code path.
+constexpr YuvRule kYuvRules[3][2] = {
+    {{16, 1220542, 1673527, 852492, 409993, 2116026}, {0, 1048576, 1470104, 748826, 360853, 1858077}},
+    {{16, 1220945, 1879825, 558796, 223607, 2215014}, {0, 1048576, 1651297, 490864, 196424, 1945738}},
+    {{16, 1220945, 1760217, 682019, 196426, 2245811}, {0, 1048576, 1546230, 599107, 172546, 1972791}},
+};
+
+// What yuv_to_bgr's masks assume of every row: a byte for yoff, constants below 2^23.
+constexpr bool yuv_rules_fit() {
+    for (const auto& matrix : kYuvRules)
+        for (const YuvRule& r : matrix)
+            for (int c : {r.cy, r.crv, r.cgv, r.cgu, r.cbu})
+                if (r.yoff < 0 || r.yoff > 255 || c < 0 || c >= (1 << 23)) return false;
+    return true;
+}
+static_assert(yuv_rules_fit(), "a rule's constants are 23-bit: the products of yuv_to_bgr are 24-bit multiplies");
+
 struct YuvArgs : TileArgs {
     int planar;
     unsigned yslot, cslot;    // LDS bytes per staged Y span and per staged chroma span (multiples of 16)
+    YuvRule rule;
 };
 
-// B, G, R (in that order) of one pixel, as the floats of the converted bytes.
-__device__ __forceinline__ void yuv_to_bgr(int y, int u, int v, float (&o)[3]) {
-    y = y - 16 < 0 ? 0 : y - 16;
+// B, G, R (in that order) of one pixel, as the floats of the converted bytes.  LIT: the rule is kYuvRules[0][0], whatever `k` holds.
+// Else the constants come from scalar registers, where the compiler knows nothing of their range: the masks (scalar instructions,
+// once per wave, and the identity on every row of the table) tell it they are 23-bit, so each product stays a full-rate 24-bit
+// multiply.
+template <bool LIT = false>
+__device__ __forceinline__ void yuv_to_bgr(const YuvRule& k, int y, int u, int v, float (&o)[3]) {
+    constexpr int kBits = (1 << 23) - 1;
+    constexpr YuvRule d = kYuvRules[0][0];
+    const int yoff = LIT ? d.yoff : k.yoff & 255, cy = LIT ? d.cy : k.cy & kBits, crv = LIT ? d.crv : k.crv & kBits;
+    const int cgv = LIT ? d.cgv : k.cgv & kBits, cgu = LIT ? d.cgu : k.cgu & kBits, cbu = LIT ? d.cbu : k.cbu & kBits;
+    y = max(y, yoff) - yoff;
     u -= 128; v -= 128;
-    const int t = y * 1220542 + (1 << 19);
-    const int b = (t + 2116026 * u) >> 20;
-    const int g = (t - 852492 * v - 409993 * u) >> 20;
-    const int r = (t + 1673527 * v) >> 20;
+    const int t = y * cy + (1 << 19);
+    const int b = (t + cbu * u) >> 20;
+    const int g = (t - cgv * v - cgu * u) >> 20;
+    const int r = (t + crv * v) >> 20;
     o[0] = (float)min(max(b, 0), 255);
     o[1] = (float)min(max(g, 0), 255);
     o[2] = (float)min(max(r, 0), 255);
@@ -389,7 +431,7 @@ __device__ __forceinline__ void yuv_to_bgr(int y, int u, int v, float (&o)[3]) {
 // dynamic LDS stage_bytes + Tables::bytes(tw, th).  ROI (with RESIZE): the chroma of a pixel is that of its ABSOLUTE 2 x 2 block of the
 // frame, so a rectangle may start on odd coordinates and have odd sizes.  (A rectangle of the destination's extent needs no copy path
 // here: the converted pixels are bytes, and weight 0 on a finite value interpolates to the same bits.)
-template <bool RESIZE, bool VS, bool ROI, bool FIT = false>
+template <bool RESIZE, bool VS, bool ROI, bool FIT = false, bool LIT = true>
 __global__ __launch_bounds__(kBlock) void preprocess_yuv_kernel(YuvArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     Tile t;
@@ -453,13 +495,13 @@ __global__ __launch_bounds__(kBlock) void preprocess_yuv_kernel(YuvArgs a) {
             const int xa = tb.cx0[j], xb = tb.cx1[j];
             const int pa = (((ox + xa) >> 1) - ps0) * cstep, pb = (((ox + xb) >> 1) - ps0) * cstep;
             float p00[3];
-            yuv_to_bgr(ly[0][xa - xs0], lu[0][pa], lv[0][pa], p00);
+            yuv_to_bgr<LIT>(a.rule, ly[0][xa - xs0], lu[0][pa], lv[0][pa], p00);
             if (RESIZE) {
                 const float fx = tb.cfx[j], gx = 1.0f - fx;
                 float p01[3], p10[3], p11[3];
-                yuv_to_bgr(ly[0][xb - xs0], lu[0][pb], lv[0][pb], p01);
-                yuv_to_bgr(ly[1][xa - xs0], lu[1][pa], lv[1][pa], p10);
-                yuv_to_bgr(ly[1][xb - xs0], lu[1][pb], lv[1][pb], p11);
+                yuv_to_bgr<LIT>(a.rule, ly[0][xb - xs0], lu[0][pb], lv[0][pb], p01);
+                yuv_to_bgr<LIT>(a.rule, ly[1][xa - xs0], lu[1][pa], lv[1][pa], p10);
+                yuv_to_bgr<LIT>(a.rule, ly[1][xb - xs0], lu[1][pb], lv[1][pb], p11);
 #pragma unroll
                 for (int c = 0; c < 3; ++c) {
                     const float top = gx * p00[c] + fx * p01[c];
@@ -487,9 +529,11 @@ __global__ __launch_bounds__(kBlock) void preprocess_yuv_kernel(YuvArgs a) {
 }
 
 template <bool RESIZE, bool ROI, bool FIT = false>
-void launch_yuv(const YuvArgs& a, dim3 grid, size_t lds, bool vs, hipStream_t st) {
-    if (vs) hipLaunchKernelGGL((preprocess_yuv_kernel<RESIZE, true, ROI, FIT>), grid, dim3(kBlock), lds, st, a);
-    else    hipLaunchKernelGGL((preprocess_yuv_kernel<RESIZE, false, ROI, FIT>), grid, dim3(kBlock), lds, st, a);
+void launch_yuv(const YuvArgs& a, dim3 grid, size_t lds, bool vs, bool lit, hipStream_t st) {
+#define PVHIP_YUV(VS, LIT) hipLaunchKernelGGL((preprocess_yuv_kernel<RESIZE, VS, ROI, FIT, LIT>), grid, dim3(kBlock), lds, st, a)
+    if (lit) { if (vs) PVHIP_YUV(true, true); else PVHIP_YUV(false, true); }
+    else     { if (vs) PVHIP_YUV(true, false); else PVHIP_YUV(false, false); }
+#undef PVHIP_YUV
 }
 
 // ------------------------------------------------------------------------------------------------------ packed 4-byte-unit sources
@@ -508,16 +552,17 @@ void launch_yuv(const YuvArgs& a, dim3 grid, size_t lds, bool vs, hipStream_t st
 // and the byte positions inside a unit are compile-time constants of KIND.
 struct PackedArgs : TileArgs {
     unsigned slot;            // LDS bytes per staged row span (a multiple of 16)
+    YuvRule rule;             // kinds 0 and 1
 };
 
 // B, G, R of the pixel at column x of its rectangle (absolute column ox + x), from the row span `l` whose first unit is unit u0.
-template <int KIND>
-__device__ __forceinline__ void packed_to_bgr(const unsigned char* l, int ox, int x, int u0, float (&o)[3]) {
+template <int KIND, bool LIT = false>
+__device__ __forceinline__ void packed_to_bgr(const YuvRule& k, const unsigned char* l, int ox, int x, int u0, float (&o)[3]) {
     if (KIND < 2) {
         const int ax = ox + x;
         const unsigned char* g = l + 4 * ((ax >> 1) - u0);
         constexpr int Y = KIND == 0 ? 0 : 1, U = KIND == 0 ? 1 : 0, V = KIND == 0 ? 3 : 2;
-        yuv_to_bgr(g[Y + 2 * (ax & 1)], g[U], g[V], o);
+        yuv_to_bgr<LIT>(k, g[Y + 2 * (ax & 1)], g[U], g[V], o);
     } else {
         const unsigned char* g = l + 4 * (ox + x - u0);
         o[0] = (float)g[KIND == 2 ? 0 : 2];
@@ -528,7 +573,7 @@ __device__ __forceinline__ void packed_to_bgr(const unsigned char* l, int ox, in
 
 // dynamic LDS stage_bytes + Tables::bytes(tw, th).  ROI (with RESIZE): a 4:2:2 pixel keeps the chroma of its ABSOLUTE column pair, so a
 // rectangle may start on an odd x and have an odd w.  (No copy path for a rectangle of the destination's extent: the pixels are bytes.)
-template <int KIND, bool RESIZE, bool VS, bool ROI, bool FIT = false>
+template <int KIND, bool RESIZE, bool VS, bool ROI, bool FIT = false, bool LIT = true>
 __global__ __launch_bounds__(kBlock) void preprocess_packed_kernel(PackedArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     constexpr bool YUV = KIND < 2;
@@ -571,13 +616,13 @@ __global__ __launch_bounds__(kBlock) void preprocess_packed_kernel(PackedArgs a)
             const int j = j0 + u < t.twv ? j0 + u : j0;       // (a pixel past the tile computes column j0 again and is not stored)
             const int xa = tb.cx0[j], xb = tb.cx1[j];
             float p00[3];
-            packed_to_bgr<KIND>(l0, ox, xa, u0, p00);
+            packed_to_bgr<KIND, LIT>(a.rule, l0, ox, xa, u0, p00);
             if (RESIZE) {
                 const float fx = tb.cfx[j], gx = 1.0f - fx;
                 float p01[3], p10[3], p11[3];
-                packed_to_bgr<KIND>(l0, ox, xb, u0, p01);
-                packed_to_bgr<KIND>(l1, ox, xa, u0, p10);
-                packed_to_bgr<KIND>(l1, ox, xb, u0, p11);
+                packed_to_bgr<KIND, LIT>(a.rule, l0, ox, xb, u0, p01);
+                packed_to_bgr<KIND, LIT>(a.rule, l1, ox, xa, u0, p10);
+                packed_to_bgr<KIND, LIT>(a.rule, l1, ox, xb, u0, p11);
 #pragma unroll
                 for (int c = 0; c < 3; ++c) {
                     const float top = gx * p00[c] + fx * p01[c];
@@ -604,12 +649,12 @@ __global__ __launch_bounds__(kBlock) void preprocess_packed_kernel(PackedArgs a)
     }
 }
 
-template <int KIND>
+template <int KIND, bool LIT = true>
 void launch_packed(const PackedArgs& a, dim3 grid, size_t lds, bool vs, bool roi, bool resize, hipStream_t st) {
 #define PVHIP_PACKED(RESIZE, ROI, FIT)                                                                                         \
     do {                                                                                                                           \
-        if (vs) hipLaunchKernelGGL((preprocess_packed_kernel<KIND, RESIZE, true, ROI, FIT>), grid, dim3(kBlock), lds, st, a);      \
-        else    hipLaunchKernelGGL((preprocess_packed_kernel<KIND, RESIZE, false, ROI, FIT>), grid, dim3(kBlock), lds, st, a);     \
+        if (vs) hipLaunchKernelGGL((preprocess_packed_kernel<KIND, RESIZE, true, ROI, FIT, LIT>), grid, dim3(kBlock), lds, st, a);      \
+        else    hipLaunchKernelGGL((preprocess_packed_kernel<KIND, RESIZE, false, ROI, FIT, LIT>), grid, dim3(kBlock), lds, st, a);\
     } while (0)
     if (a.fit)       { if (roi) PVHIP_PACKED(true, true, true); else PVHIP_PACKED(true, false, true); }
     else if (roi)    PVHIP_PACKED(true, true, false);
@@ -624,6 +669,7 @@ void launch_packed(const PackedArgs& a, dim3 grid, size_t lds, bool vs, bool roi
 struct WarpArgs : TileArgs {
     const long long* table;
     int c;
+    YuvRule rule;             // the colour formats
 };
 
 // The tile of a workgroup: kWarpTileW x kWarpTileH output pixels of one image, a quad of one row per lane (kBlock quads).  See the
@@ -675,18 +721,19 @@ struct Yuv420Fetch {
     static constexpr int K = 3;
     const unsigned char *frame, *chroma;
     int ws, hw, vplane;
+    const YuvRule& rule;
     __device__ Yuv420Fetch(const WarpArgs& a, int id)
         : frame(a.src + (size_t)id * ((size_t)a.hs * a.ws / 2 * 3)), chroma(frame + (size_t)a.hs * a.ws), ws(a.ws), hw(a.ws >> 1),
-          vplane((a.hs >> 1) * (a.ws >> 1)) {}
+          vplane((a.hs >> 1) * (a.ws >> 1)), rule(a.rule) {}
     __device__ __forceinline__ void operator()(int r, int col, int, int step, int, float (&p)[K]) const {
         const unsigned char* cp = PLANAR ? chroma + (r >> 1) * hw + (col >> 1) : chroma + (r >> 1) * ws + 2 * (col >> 1);
         float o[3];
         if (PLANAR) {
-            yuv_to_bgr(frame[r * ws + col], cp[0], cp[vplane], o);
+            yuv_to_bgr(rule, frame[r * ws + col], cp[0], cp[vplane], o);
         } else {
             unsigned short uv;                                // NV12's (U, V) pair: one 16-bit load at any alignment
             __builtin_memcpy(&uv, cp, 2);
-            yuv_to_bgr(frame[r * ws + col], uv & 255, uv >> 8, o);
+            yuv_to_bgr(rule, frame[r * ws + col], uv & 255, uv >> 8, o);
         }
         bgr_in_order(o, step, p);
     }
@@ -698,8 +745,9 @@ struct PackedFetch {
     static constexpr int K = 3;
     const unsigned char* frame;
     int row_bytes;
+    const YuvRule& rule;
     __device__ PackedFetch(const WarpArgs& a, int id)
-        : frame(a.src + (size_t)id * ((size_t)a.hs * a.ws * (KIND < 2 ? 2 : 4))), row_bytes(a.ws * (KIND < 2 ? 2 : 4)) {}
+        : frame(a.src + (size_t)id * ((size_t)a.hs * a.ws * (KIND < 2 ? 2 : 4))), row_bytes(a.ws * (KIND < 2 ? 2 : 4)), rule(a.rule) {}
     __device__ __forceinline__ void operator()(int r, int col, int, int step, int, float (&p)[K]) const {
         const int unit = KIND < 2 ? col >> 1 : col;
         const unsigned char* g = frame + (size_t)r * row_bytes + (size_t)unit * 4;
@@ -707,9 +755,9 @@ struct PackedFetch {
         if (A4) {
             const unsigned w = *reinterpret_cast<const unsigned*>(g);
             const unsigned char b[4] = {(unsigned char)w, (unsigned char)(w >> 8), (unsigned char)(w >> 16), (unsigned char)(w >> 24)};
-            packed_to_bgr<KIND>(b, 0, col, unit, o);
+            packed_to_bgr<KIND>(rule, b, 0, col, unit, o);
         } else {
-            packed_to_bgr<KIND>(g, 0, col, unit, o);
+            packed_to_bgr<KIND>(rule, g, 0, col, unit, o);
         }
         bgr_in_order(o, step, p);
     }
@@ -948,10 +996,10 @@ int preprocess_launch(const void* src, float* dst, const int* rois, int n, int m
     return PVHIP_OK;
 }
 
-// The one launcher of preprocess_yuv_kernel.
+// The one launcher of preprocess_yuv_kernel.  rule: NULL for BT.601 limited range, the LIT kernels (so too in the launchers below).
 int preprocess_yuv_launch(const void* src, float* dst, const int* rois, int n, int m, int src_h, int src_w, int dst_h, int dst_w,
                           int roi_h, int roi_w, int planar, int reverse_channels, const float* mean, const float* std_scale,
-                          Fit fit = Fit{0, 0.0f}) {
+                          Fit fit = Fit{0, 0.0f}, const YuvRule* rule = nullptr) {
     YuvArgs a;
     int rc = common_args(a, src, dst, rois, n, m, 3, src_h, src_w, dst_h, dst_w, roi_h, roi_w, reverse_channels, mean, std_scale);
     if (rc != PVHIP_OK) return rc;
@@ -971,11 +1019,12 @@ int preprocess_yuv_launch(const void* src, float* dst, const int* rois, int n, i
     TilePlan p;
     rc = plan_tiles(a, n, stage_of, p);
     if (rc != PVHIP_OK) return rc;
-    a.planar = planar; a.yslot = (unsigned)yslot_of(a.tw); a.cslot = (unsigned)cslot_of(a.tw);
+    a.planar = planar; a.yslot = (unsigned)yslot_of(a.tw); a.cslot = (unsigned)cslot_of(a.tw); a.rule = rule ? *rule : kYuvRules[0][0];
     hipStream_t st = state().stream;
-    if (fit.fit) roi ? launch_yuv<true, true, true>(a, p.grid, p.lds, p.vs, st) : launch_yuv<true, false, true>(a, p.grid, p.lds, p.vs, st);
-    else if (roi) launch_yuv<true, true>(a, p.grid, p.lds, p.vs, st);
-    else     resize ? launch_yuv<true, false>(a, p.grid, p.lds, p.vs, st) : launch_yuv<false, false>(a, p.grid, p.lds, p.vs, st);
+    const bool lit = rule == nullptr;
+    if (fit.fit) roi ? launch_yuv<true, true, true>(a, p.grid, p.lds, p.vs, lit, st) : launch_yuv<true, false, true>(a, p.grid, p.lds, p.vs, lit, st);
+    else if (roi) launch_yuv<true, true>(a, p.grid, p.lds, p.vs, lit, st);
+    else     resize ? launch_yuv<true, false>(a, p.grid, p.lds, p.vs, lit, st) : launch_yuv<false, false>(a, p.grid, p.lds, p.vs, lit, st);
     PVHIP_LAUNCH_CHECK();
     return PVHIP_OK;
 }
@@ -983,7 +1032,7 @@ int preprocess_yuv_launch(const void* src, float* dst, const int* rois, int n, i
 // The one launcher of preprocess_packed_kernel.  kind: 0 YUY2, 1 UYVY, 2 BGRX, 3 RGBX.
 int preprocess_packed_launch(const void* src, float* dst, const int* rois, int n, int m, int src_h, int src_w, int dst_h, int dst_w,
                              int roi_h, int roi_w, int kind, int reverse_channels, const float* mean, const float* std_scale,
-                             Fit fit = Fit{0, 0.0f}) {
+                             Fit fit = Fit{0, 0.0f}, const YuvRule* rule = nullptr) {
     PackedArgs a;
     int rc = common_args(a, src, dst, rois, n, m, 3, src_h, src_w, dst_h, dst_w, roi_h, roi_w, reverse_channels, mean, std_scale);
     if (rc != PVHIP_OK) return rc;
@@ -999,11 +1048,11 @@ int preprocess_packed_launch(const void* src, float* dst, const int* rois, int n
     TilePlan p;
     rc = plan_tiles(a, n, [&](int tw, int th) { return reach.rows(th) * slot_of(tw); }, p);
     if (rc != PVHIP_OK) return rc;
-    a.slot = (unsigned)slot_of(a.tw);
+    a.slot = (unsigned)slot_of(a.tw); a.rule = rule ? *rule : kYuvRules[0][0];
     hipStream_t st = state().stream;
     switch (kind) {
-        case 0:  launch_packed<0>(a, p.grid, p.lds, p.vs, roi, resize, st); break;
-        case 1:  launch_packed<1>(a, p.grid, p.lds, p.vs, roi, resize, st); break;
+        case 0:  rule ? launch_packed<0, false>(a, p.grid, p.lds, p.vs, roi, resize, st) : launch_packed<0>(a, p.grid, p.lds, p.vs, roi, resize, st); break;
+        case 1:  rule ? launch_packed<1, false>(a, p.grid, p.lds, p.vs, roi, resize, st) : launch_packed<1>(a, p.grid, p.lds, p.vs, roi, resize, st); break;
         case 2:  launch_packed<2>(a, p.grid, p.lds, p.vs, roi, resize, st); break;
         default: launch_packed<3>(a, p.grid, p.lds, p.vs, roi, resize, st); break;
     }
@@ -1014,7 +1063,8 @@ int preprocess_packed_launch(const void* src, float* dst, const int* rois, int n
 // The one launcher of preprocess_warp_kernel.  format 0 raw (how = src_u8 | src_nhwc << 1), 1 YUV 4:2:0 (how = planar), 2 frames of
 // 4-byte units (how = kind): the limits of the launcher of that format above.
 int preprocess_warp_launch(const void* src, float* dst, const long long* table, int n, int m, int c, int src_h, int src_w, int dst_h,
-                           int dst_w, int format, int how, int reverse_channels, const float* mean, const float* std_scale, float pad_value) {
+                           int dst_w, int format, int how, int reverse_channels, const float* mean, const float* std_scale, float pad_value,
+                           const YuvRule* rule = nullptr) {
     WarpArgs a;
     int rc = common_args(a, src, dst, nullptr, n, m, c, src_h, src_w, dst_h, dst_w, src_h, src_w, reverse_channels, mean, std_scale);
     if (rc != PVHIP_OK) return rc;
@@ -1033,7 +1083,7 @@ int preprocess_warp_launch(const void* src, float* dst, const long long* table, 
     }
     const dim3 grid((unsigned)((dst_w + kWarpTileW - 1) / kWarpTileW), (unsigned)((dst_h + kWarpTileH - 1) / kWarpTileH), (unsigned)n);
     PVHIP_CHECK_ARG(grid.y <= 65535);
-    a.table = table; a.c = c; a.pad = pad_value;
+    a.table = table; a.c = c; a.pad = pad_value; a.rule = rule ? *rule : kYuvRules[0][0];
     const bool vs = (uintptr_t)dst % 16 == 0 && dst_w % 4 == 0;
     const bool a4 = (uintptr_t)src % 4 == 0;
     hipStream_t st = state().stream;
@@ -1106,19 +1156,20 @@ int pvhip_input_preprocess_packed_roi_f32(const void* src, float* dst, const int
 }
 
 // The fitted forms: rois == NULL means whole images.  A fit of whole images that fills the destination is the existing launch.
-#define PVHIP_FIT_ARGS()                                                                                                      \
+// STRETCH (the _color_ entries): fit 0 is taken too, and is the launch without a fit whatever pad_value holds.
+#define PVHIP_FIT_ARGS(STRETCH)                                                                                               \
     PVHIP_REQUIRE_INIT();                                                                                                      \
     const Fit f{fit, pad_value};                                                                                               \
-    PVHIP_CHECK_ARG(f.ok());                                                                                                   \
+    PVHIP_CHECK_ARG(f.ok() || (STRETCH && fit == 0));                                                                          \
     PVHIP_CHECK_ARG(src_h > 0 && src_w > 0 && dst_h > 0 && dst_w > 0);                                                         \
     if (rois == nullptr) { m = n; max_roi_h = src_h; max_roi_w = src_w; }                                                      \
     const FitRect g = fit_rect(src_h, src_w, dst_h, dst_w, fit);                                                               \
-    const Fit used = rois == nullptr && g.iw == dst_w && g.ih == dst_h ? Fit{0, 0.0f} : f
+    const Fit used = fit == 0 || (rois == nullptr && g.iw == dst_w && g.ih == dst_h) ? Fit{0, 0.0f} : f
 
 int pvhip_input_preprocess_fit_f32(const void* src, float* dst, const int* rois, int n, int m, int c, int src_h, int src_w, int dst_h,
                                    int dst_w, int max_roi_h, int max_roi_w, int src_u8, int src_nhwc, int reverse_channels,
                                    const float* mean, const float* std_scale, int fit, float pad_value) {
-    PVHIP_FIT_ARGS();
+    PVHIP_FIT_ARGS(false);
     return preprocess_launch(src, dst, rois, n, m, c, src_h, src_w, dst_h, dst_w, max_roi_h, max_roi_w, src_u8, src_nhwc, reverse_channels,
                              mean, std_scale, used);
 }
@@ -1126,7 +1177,7 @@ int pvhip_input_preprocess_fit_f32(const void* src, float* dst, const int* rois,
 int pvhip_input_preprocess_yuv_fit_f32(const void* src, float* dst, const int* rois, int n, int m, int src_h, int src_w, int dst_h,
                                        int dst_w, int max_roi_h, int max_roi_w, int planar, int reverse_channels, const float* mean,
                                        const float* std_scale, int fit, float pad_value) {
-    PVHIP_FIT_ARGS();
+    PVHIP_FIT_ARGS(false);
     return preprocess_yuv_launch(src, dst, rois, n, m, src_h, src_w, dst_h, dst_w, max_roi_h, max_roi_w, planar, reverse_channels, mean,
                                  std_scale, used);
 }
@@ -1134,9 +1185,34 @@ int pvhip_input_preprocess_yuv_fit_f32(const void* src, float* dst, const int* r
 int pvhip_input_preprocess_packed_fit_f32(const void* src, float* dst, const int* rois, int n, int m, int src_h, int src_w, int dst_h,
                                           int dst_w, int max_roi_h, int max_roi_w, int kind, int reverse_channels, const float* mean,
                                           const float* std_scale, int fit, float pad_value) {
-    PVHIP_FIT_ARGS();
+    PVHIP_FIT_ARGS(false);
     return preprocess_packed_launch(src, dst, rois, n, m, src_h, src_w, dst_h, dst_w, max_roi_h, max_roi_w, kind, reverse_channels, mean,
                                     std_scale, used);
+}
+
+// The _color_ entries: the launches above with the rule kYuvRules[matrix][full_range] in place of BT.601 limited range, which (0, 0) is.
+#define PVHIP_COLOR_RULE()                                                                                                    \
+    PVHIP_REQUIRE_INIT();                                                                                                      \
+    PVHIP_CHECK_ARG(matrix >= 0 && matrix <= 2 && (full_range == 0 || full_range == 1));                                       \
+    const YuvRule* rule = matrix || full_range ? &kYuvRules[matrix][full_range] : nullptr
+
+int pvhip_input_preprocess_yuv_color_f32(const void* src, float* dst, const int* rois, int n, int m, int src_h, int src_w, int dst_h,
+                                         int dst_w, int max_roi_h, int max_roi_w, int planar, int reverse_channels, const float* mean,
+                                         const float* std_scale, int fit, float pad_value, int matrix, int full_range) {
+    PVHIP_COLOR_RULE();
+    PVHIP_FIT_ARGS(true);
+    return preprocess_yuv_launch(src, dst, rois, n, m, src_h, src_w, dst_h, dst_w, max_roi_h, max_roi_w, planar, reverse_channels, mean,
+                                 std_scale, used, rule);
+}
+
+int pvhip_input_preprocess_packed_color_f32(const void* src, float* dst, const int* rois, int n, int m, int src_h, int src_w, int dst_h,
+                                            int dst_w, int max_roi_h, int max_roi_w, int kind, int reverse_channels, const float* mean,
+                                            const float* std_scale, int fit, float pad_value, int matrix, int full_range) {
+    PVHIP_COLOR_RULE();
+    PVHIP_CHECK_ARG(kind < 2 || (matrix == 0 && full_range == 0));                   // four-byte pixels: nothing to convert
+    PVHIP_FIT_ARGS(true);
+    return preprocess_packed_launch(src, dst, rois, n, m, src_h, src_w, dst_h, dst_w, max_roi_h, max_roi_w, kind, reverse_channels, mean,
+                                    std_scale, used, rule);
 }
 #undef PVHIP_FIT_ARGS
 
@@ -1146,5 +1222,15 @@ int pvhip_input_preprocess_warp_f32(const void* src, float* dst, const long long
     return preprocess_warp_launch(src, dst, table, n, m, c, src_h, src_w, dst_h, dst_w, format, how, reverse_channels, mean, std_scale,
                                   pad_value);
 }
+
+int pvhip_input_preprocess_warp_color_f32(const void* src, float* dst, const long long* table, int n, int m, int c, int src_h, int src_w,
+                                          int dst_h, int dst_w, int format, int how, int reverse_channels, const float* mean,
+                                          const float* std_scale, float pad_value, int matrix, int full_range) {
+    PVHIP_COLOR_RULE();
+    PVHIP_CHECK_ARG((format != 0 && !(format == 2 && how >= 2)) || (matrix == 0 && full_range == 0));   // raw frames, four-byte pixels
+    return preprocess_warp_launch(src, dst, table, n, m, c, src_h, src_w, dst_h, dst_w, format, how, reverse_channels, mean, std_scale,
+                                  pad_value, rule);
+}
+#undef PVHIP_COLOR_RULE
 
 }  // extern "C"

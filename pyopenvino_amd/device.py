@@ -174,6 +174,12 @@ SIGNATURES = {
     'pvhip_input_preprocess_yuv_fit_f32': (_c.c_int, [_c.c_void_p, _fp, _c.c_void_p] + [_c.c_int] * 10 + [_fp, _fp, _c.c_int, _c.c_float]),
     'pvhip_input_preprocess_packed_fit_f32': (_c.c_int, [_c.c_void_p, _fp, _c.c_void_p] + [_c.c_int] * 10 + [_fp, _fp, _c.c_int, _c.c_float]),
     'pvhip_input_preprocess_warp_f32': (_c.c_int, [_c.c_void_p, _fp, _c.c_void_p] + [_c.c_int] * 10 + [_fp, _fp, _c.c_float]),
+    'pvhip_input_preprocess_yuv_color_f32': (_c.c_int, [_c.c_void_p, _fp, _c.c_void_p] + [_c.c_int] * 10
+                                             + [_fp, _fp, _c.c_int, _c.c_float, _c.c_int, _c.c_int]),
+    'pvhip_input_preprocess_packed_color_f32': (_c.c_int, [_c.c_void_p, _fp, _c.c_void_p] + [_c.c_int] * 10
+                                                + [_fp, _fp, _c.c_int, _c.c_float, _c.c_int, _c.c_int]),
+    'pvhip_input_preprocess_warp_color_f32': (_c.c_int, [_c.c_void_p, _fp, _c.c_void_p] + [_c.c_int] * 10
+                                              + [_fp, _fp, _c.c_float, _c.c_int, _c.c_int]),
 }
 
 # entry points whose return value is not a status code

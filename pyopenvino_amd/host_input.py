@@ -296,7 +296,8 @@ class HostInputs:
         pvhip_input_preprocess_f32 when a resize, channel reversal or mean / scale is in effect, else pvhip_input_to_nchw_f32;
         `largest` = (max_h, max_w) of a RoiInput's table: the _roi_f32 forms.  A declared fit: the _fit_f32 forms of the three, with
         the table or NULL.  `warped`: the frames of a WarpInput: pvhip_input_preprocess_warp_f32 for every format, whatever fit is
-        declared."""
+        declared.  A format whose colour rule is not BT.601 limited range (``InputFormat.default_rule``) takes the _color_f32 form of
+        its launch, whichever of these it is, with the rule behind the same arguments; every other format exactly the entries above."""
         fixed = slot.fixed
         src, dst = device.ptr(staged.staging), device.ptr(fixed)
         n, c, dst_hw = fixed.shape[0], fixed.shape[1], fixed.shape[2:]
@@ -304,8 +305,14 @@ class HostInputs:
         pre = (int(fmt.reverse), device.ptr(slot.mean), device.ptr(slot.std))
         if warped:
             form = (1, how[0]) if fmt.yuv else (2, how[0]) if fmt.packed else (0, how[0] | how[1] << 1)
-            device.call('pvhip_input_preprocess_warp_f32', src, dst, device.ptr(slot.warps), n, staged.frames, c, *staged.extent, *dst_hw,
-                        *form, *pre, fmt.pad)
+            entry, rule = ('pvhip_input_preprocess_warp_f32', ()) if fmt.default_rule else ('pvhip_input_preprocess_warp_color_f32', fmt.color_rule)
+            device.call(entry, src, dst, device.ptr(slot.warps), n, staged.frames, c, *staged.extent, *dst_hw, *form, *pre, fmt.pad, *rule)
+        elif not fmt.default_rule:
+            # (load_network admits another rule for YUV formats only) one entry per family: the table or NULL, the fit or 0
+            roi = largest is not None
+            device.call('pvhip_input_preprocess_yuv_color_f32' if fmt.yuv else 'pvhip_input_preprocess_packed_color_f32', src, dst,
+                        device.ptr(slot.rois if roi else None), n, staged.frames if roi else n, *staged.extent, *dst_hw,
+                        *(largest if roi else staged.extent), *how, *pre, fmt.fit_code, fmt.pad, *fmt.color_rule)
         elif fmt.fitted and (largest is not None or fmt.yuv or fmt.packed or staged.preprocess):
             where = (src, dst, device.ptr(slot.rois if largest is not None else None), n, staged.frames if largest is not None else n)
             sizes = (*staged.extent, *dst_hw, *(largest if largest is not None else staged.extent))

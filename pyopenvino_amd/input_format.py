@@ -12,6 +12,11 @@ YUV420_FORMATS = ('NV12', 'I420')
 PACKED_KINDS = {'YUY2': 0, 'UYVY': 1, 'BGRX': 2, 'RGBX': 3}
 # how a resized source is placed in the Parameter's extent, with the `fit` of the pvhip_input_preprocess_*_fit_f32 entries
 RESIZE_FITS = {'STRETCH': 0, 'LETTERBOX': 1, 'TOP_LEFT': 2}
+# the matrix a YUV format's frames were encoded with, with the `matrix` of the pvhip_input_preprocess_*_color_f32 entries, and their range
+# (`full_range` 0 / 1); 'BGRX' / 'RGBX' hold nothing to convert
+COLOR_STANDARDS = {'BT601': 0, 'BT709': 1, 'BT2020': 2}
+COLOR_RANGES = {'LIMITED': 0, 'FULL': 1}
+YUV_FORMATS = YUV420_FORMATS + ('YUY2', 'UYVY')
 
 
 def fit_geometry(src_hw, dst_hw, fit) -> tuple:
@@ -36,7 +41,9 @@ class InputFormat:
     None without MEAN_VALUE), ``fit`` / ``pad`` the declared placement of a resized source ('STRETCH', or 'LETTERBOX' / 'TOP_LEFT': one
     scale factor, the rest of the extent filled with ``pad``; ``fit_geometry``), ``color`` the declared colour format: 'RAW', or 'NV12' / 'I420' for YUV 4:2:0 frames, uint8 of shape
     (n, 3 h / 2, w), or 'YUY2' / 'UYVY' for packed YUV 4:2:2 frames, uint8 of shape (n, h, w, 2), or 'BGRX' / 'RGBX' for four-byte
-    pixels, uint8 of shape (n, h, w, 4), whatever ``u8`` / ``nhwc`` say.  An extent is the (h, w) of a caller's image.  A RoiInput's frames have the same
+    pixels, uint8 of shape (n, h, w, 4), whatever ``u8`` / ``nhwc`` say; ``standard`` / ``full_range`` the declared matrix ('BT601', 'BT709',
+    'BT2020') and range of a YUV format's frames, which ``color_rule`` hands every launch that converts them -- a plain pass, a RoiInput, a
+    DetectedRois, a WarpInput and a fitted input alike: the rule belongs to the format, not to the feed.  An extent is the (h, w) of a caller's image.  A RoiInput's frames have the same
     shapes with their own count m in place of n (``host_shape(extent, frames=m)``, ``frames_extent_of``) and a table ``checked_rois``
     accepts."""
     name: str
@@ -52,6 +59,18 @@ class InputFormat:
     color: str = 'RAW'
     fit: str = 'STRETCH'
     pad: float = 0.0
+    standard: str = 'BT601'
+    full_range: bool = False
+
+    @property
+    def color_rule(self) -> tuple:
+        """(matrix, full_range) as the pvhip_input_preprocess_*_color_f32 entries take them; (0, 0), BT.601 limited range, is the rule
+        of the entries without them (``default_rule``)."""
+        return COLOR_STANDARDS[self.standard], int(self.full_range)
+
+    @property
+    def default_rule(self) -> bool:
+        return self.color_rule == (0, 0)
 
     @property
     def fitted(self) -> bool:
@@ -445,7 +464,8 @@ class InputInfo:
     of any extent, channel reversal and mean / scale to that launch (``pvhip_input_preprocess_f32``); its ``color_format`` 'NV12' /
     'I420' makes the array a decoder's YUV 4:2:0 frames, uint8 of shape (n, 3 h / 2, w), converted to B, G, R in that launch
     (``pvhip_input_preprocess_yuv_f32``), 'YUY2' / 'UYVY' a camera's packed YUV 4:2:2 frames, uint8 of shape (n, h, w, 2), and 'BGRX' /
-    'RGBX' a screen capture's four-byte pixels, uint8 of shape (n, h, w, 4) (``pvhip_input_preprocess_packed_f32``)."""
+    'RGBX' a screen capture's four-byte pixels, uint8 of shape (n, h, w, 4) (``pvhip_input_preprocess_packed_f32``); its
+    ``color_standard`` / ``color_range`` say which matrix and range the YUV frames were encoded with (the ``_color_f32`` forms)."""
     PRECISIONS = ('FP32', 'U8')
     LAYOUTS = ('NCHW', 'NHWC')
 
@@ -529,7 +549,8 @@ class InputInfo:
         color = pre.color_format if pre is not None else 'RAW'
         return InputFormat(self.name, self.dims, self.supported(), self.declared, self._precision == 'U8' or color != 'RAW', self._layout == 'NHWC',
                            pre is not None and pre.resize_algorithm == 'RESIZE_BILINEAR', pre is not None and pre.reverse_channels, mean, std,
-                           color, pre.resize_fit if pre is not None else 'STRETCH', pre.pad_value if pre is not None else 0.0)
+                           color, pre.resize_fit if pre is not None else 'STRETCH', pre.pad_value if pre is not None else 0.0,
+                           pre.color_standard if pre is not None else 'BT601', pre is not None and pre.color_range == 'FULL')
 
     def preprocessing(self):
         """(resize, reverse_channels, (mean, std_scale) or None) as declared; (False, False, None) when nothing is."""
@@ -544,6 +565,9 @@ class InputInfo:
         if pre is not None and pre.resize_fit != 'STRETCH' and pre.resize_algorithm != 'RESIZE_BILINEAR':
             raise ValueError('input {}: resize_fit {} places a resized source: it needs preprocess_info.resize_algorithm = '
                              '\'RESIZE_BILINEAR\''.format(self.name, pre.resize_fit))
+        if pre is not None and pre.color_format not in YUV_FORMATS and (pre.color_standard, pre.color_range) != ('BT601', 'LIMITED'):
+            raise ValueError('input {}: color_standard {} / color_range {} say how YUV frames were encoded; color_format {} holds nothing to '
+                             'convert'.format(self.name, pre.color_standard, pre.color_range, pre.color_format))
         if pre is not None and pre.color_format != 'RAW':
             if self.dims[1] != 3:
                 raise ValueError('input {}: color_format {} converts to 3 channels (B, G, R), the input has {}'.format(
@@ -614,8 +638,8 @@ class PreProcessInfo:
       * ``color_format``: 'RAW' (default: the array holds the channels themselves) or 'NV12' / 'I420': the array holds YUV 4:2:0 frames as a
         video decoder writes them and ``cv2.cvtColor(..., COLOR_YUV2BGR_NV12 / _I420)`` takes them -- uint8 of shape (n, 3 h / 2, w), h and
         w even: h rows of Y, then for NV12 h / 2 rows of w / 2 interleaved (U, V) pairs, for I420 the U plane and the V plane of
-        h / 2 x w / 2 bytes each.  The device converts them to B, G, R (BT.601 limited range in 20-bit integers, the chroma of a pixel's
-        2 x 2 block; pvhip_input_preprocess_yuv_f32) and resizes, reverses (R, G, B) and scales that image as it does a U8 B, G, R one.
+        h / 2 x w / 2 bytes each.  The device converts them to B, G, R (BT.601 limited range in 20-bit integers unless ``color_standard`` /
+        ``color_range`` say otherwise, the chroma of a pixel's 2 x 2 block; pvhip_input_preprocess_yuv_f32) and resizes, reverses (R, G, B) and scales that image as it does a U8 B, G, R one.
         Or 'YUY2' / 'UYVY' / 'BGRX' / 'RGBX': the array holds frames of 4-byte units, converted by pvhip_input_preprocess_packed_f32
         (the same rule in numpy: tests/packed_ref.py):
           - YUY2 / UYVY (packed YUV 4:2:2, a camera's or a capture card's frames): uint8 of shape (n, h, w, 2), the (h, w, 2) array
@@ -629,6 +653,15 @@ class PreProcessInfo:
         The resulting uint8 B, G, R image is resized, reversed (R, G, B) and scaled bit for bit as a U8 NHWC source is.  The rectangle
         of a RoiInput is the crop of the converted frame: a 4:2:2 pixel keeps the chroma of its absolute column pair, so rectangles
         may start on odd x and have odd w.
+      * ``color_standard``: 'BT601' (default), 'BT709' or 'BT2020', and ``color_range``: 'LIMITED' (default: Y in [16, 235], chroma in
+        [16, 240]) or 'FULL' (JFIF: all of [0, 255]): the matrix and range the frames of a YUV ``color_format`` were encoded with -- BT.601
+        for SD video, BT.709 for HD (a 1080p decoder's frames), BT.2020 for 8-bit HEVC / AV1 streams that say so; FULL for MJPEG webcams
+        and JPEG decoders.  One integer rule converts all six (include/pvhip.h has its table, tests/colorimetry_ref.py is the rule in
+        numpy): y = max(Y - yoff, 0), t = y CY + 2^19, B = (t + CBU u) >> 20, G = (t - CGV v - CGU u) >> 20, R = (t + CRV v) >> 20, clamped,
+        the constants rint(x 2^20) of the standard's matrix; 'BT601' / 'LIMITED' keeps cv2's three-decimal constants bit for bit.  The
+        chroma a pixel takes and everything behind the conversion stay as they are, for every way of feeding the input (arrays,
+        ``input_buffer``, RoiInput, DetectedRois, WarpInput, a declared fit).  Anything but the defaults beside 'RAW', 'BGRX' or 'RGBX'
+        is refused at load: there is nothing to convert.
         For every format but 'RAW' the Parameter has 3 channels; ``precision`` is U8 by implication ('FP32' declared beside it is
         refused at load), ``layout`` is not consulted; without a declared resize the network's own extent must be legal for the format.
     Set between ``read_network`` and ``load_network``, like ``precision``; setting anything makes the input declared."""
@@ -636,10 +669,13 @@ class PreProcessInfo:
     MEAN_VARIANTS = ('NONE', 'MEAN_VALUE')
     COLOR_FORMATS = ('RAW', 'NV12', 'I420', 'YUY2', 'UYVY', 'BGRX', 'RGBX')
     RESIZE_FITS = tuple(RESIZE_FITS)
+    COLOR_STANDARDS = tuple(COLOR_STANDARDS)
+    COLOR_RANGES = tuple(COLOR_RANGES)
 
     def __init__(self, info):
         self._info = info
         self._resize, self._mean_variant, self._reverse, self._color = 'NO_RESIZE', 'NONE', False, 'RAW'
+        self._standard, self._range = 'BT601', 'LIMITED'
         self._fit, self._pad = 'STRETCH', 0.0
         self._channels = []
 
@@ -687,6 +723,22 @@ class PreProcessInfo:
     @color_format.setter
     def color_format(self, value):
         self._color = self._info._checked('preprocess_info.color_format', value, self.COLOR_FORMATS)
+
+    @property
+    def color_standard(self):
+        return self._standard
+
+    @color_standard.setter
+    def color_standard(self, value):
+        self._standard = self._info._checked('preprocess_info.color_standard', value, self.COLOR_STANDARDS)
+
+    @property
+    def color_range(self):
+        return self._range
+
+    @color_range.setter
+    def color_range(self, value):
+        self._range = self._info._checked('preprocess_info.color_range', value, self.COLOR_RANGES)
 
     @property
     def reverse_channels(self):

@@ -12,6 +12,10 @@ copy stream the same way.  The frames are forward-converted random images (yuv_r
 conversion mostly does not saturate.  Prints one JSON line (median and per-round microseconds per launch and per copy, bytes moved, TB/s
 of the launch, GB/s of the copy, upload + launch per request); --out writes it too.
 
+--standard BT709|BT2020 / --range FULL: the nv12 and i420 launches go through pvhip_input_preprocess_yuv_color_f32 with that rule (the
+frames stay the same bytes: the launch reads and writes as much, only its six constants differ); the defaults, BT601 / LIMITED, time the
+existing entry as every default-format pass calls it.
+
 --kernel nv12|i420|bgr: only that kind's launches of the first case, the run to take under  rocprofv3 --kernel-trace --stats.
 Run each GPU step under its own time limit, e.g.  timeout -k 10 300 python scripts/bench_preprocess_yuv.py --out profiles/preprocess_yuv.json
 """
@@ -32,6 +36,8 @@ from pyopenvino_amd import device  # noqa: E402
 
 CASES = [(256, (480, 640), (224, 224)), (128, (480, 640), (300, 300))]
 KINDS = ('bgr', 'nv12', 'i420')
+STANDARDS = ('BT601', 'BT709', 'BT2020')
+RANGES = ('LIMITED', 'FULL')
 
 
 def frames(rng, n, h, w, kind):
@@ -80,11 +86,14 @@ def main():
     ap.add_argument('--warmup', type=int, default=10)
     ap.add_argument('--rounds', type=int, default=5, help='rounds over the kinds (alternating, one process)')
     ap.add_argument('--kernel', choices=KINDS, default=None, help='only the launches of this kind, first case (see above)')
+    ap.add_argument('--standard', choices=STANDARDS, default='BT601', help='the matrix of the YUV launches (see above)')
+    ap.add_argument('--range', choices=RANGES, default='LIMITED', help='the range of the YUV launches')
     ap.add_argument('--out', default=None, help='also write the JSON line to this file')
     ap.add_argument('--head', default=None, help='git commit to report (default: git rev-parse HEAD, when the tree is a checkout)')
     args = ap.parse_args()
     device.init(0)
     rng = np.random.default_rng(2026)
+    rule = (STANDARDS.index(args.standard), RANGES.index(args.range))
     cases = {}
     for n, (hs, ws), (hd, wd) in CASES[:1] if args.kernel else CASES:
         dst = device.DeviceTensor.empty((n, 3, hd, wd))
@@ -97,9 +106,12 @@ def main():
             s, d = ctypes.c_void_p(src[kind].ptr), ctypes.c_void_p(dst.ptr)
             if kind == 'bgr':
                 launch[kind] = lambda s=s, d=d: device.call('pvhip_input_preprocess_f32', s, d, n, 3, hs, ws, hd, wd, 1, 1, 0, None, None)
-            else:
+            elif rule == (0, 0):
                 launch[kind] = lambda s=s, d=d, p=int(kind == 'i420'): device.call('pvhip_input_preprocess_yuv_f32', s, d, n, hs, ws, hd, wd,
                                                                                      p, 0, None, None)
+            else:
+                launch[kind] = lambda s=s, d=d, p=int(kind == 'i420'): device.call('pvhip_input_preprocess_yuv_color_f32', s, d, None, n, n,
+                                                                                     hs, ws, hd, wd, hs, ws, p, 0, None, None, 0, 0.0, *rule)
             copy[kind] = lambda s=s, h=host[kind]: device.call('pvhip_memcpy_h2d_async', s, ctypes.c_void_p(h.ctypes.data), h.nbytes)
         us = {kind: {'launch': [], 'copy': []} for kind in launch}
         for _ in range(args.rounds):
@@ -125,6 +137,7 @@ def main():
         cases['{}x{}x{}->{}x{}'.format(n, hs, ws, hd, wd)] = rows
         del src, host, dst
     line = {'metric': 'one request\'s input: uint8 frames -> (n, 3, h, w) fp32, launch and page-locked upload, event-timed', 'cases': cases,
+            'standard': args.standard, 'range': args.range, 'library': os.path.basename(device.LIB_PATH),
             'launches_per_round': args.steps, 'rounds': args.rounds, 'git_head': git_head(args.head), 'device': device.device_name(),
             'date': time.strftime('%Y-%m-%d')}
     text = json.dumps(line)
