@@ -9,11 +9,14 @@
 // Then y = (v - mean[c]) / std_scale[c], output channel c reading source channel C-1-c under reversal.  tests/preprocess_ref.py is the
 // same rule in numpy; the kernels match it bit for bit.
 //
-// Three kernels -- preprocess_kernel for U8 / FP32 images, preprocess_yuv_kernel for YUV 4:2:0 frames (NV12, I420), which converts every
-// tapped pixel to B, G, R in front of the interpolation, and preprocess_packed_kernel for frames of 4-byte units (packed YUV 4:2:2: YUY2,
-// UYVY; four-byte pixels: BGRX, RGBX), which decodes every tapped pixel -- differ in what they stage and in their inner loops, and share
-// the rest (TileArgs):
-// a workgroup owns a tile of `th` output rows x `tw` output columns of one image (normally whole rows; plan_tiles).  It
+// ONE tile body (staged_tile) over three sources.  A source is the one place that knows a format -- what a tile stages of it, where a
+// tapped row lies in LDS and how a tapped pixel is decoded, and on the host the checks and the LDS sizes that go with them --:
+// RawSource for U8 / FP32 images, Yuv420Source for YUV 4:2:0 frames (NV12, I420), which converts every tapped pixel to B, G, R in front of
+// the interpolation, and PackedSource for frames of 4-byte units (packed YUV 4:2:2: YUY2, UYVY; four-byte pixels: BGRX, RGBX), which
+// decodes every tapped pixel.  The three kernels -- preprocess_kernel, preprocess_yuv_kernel, preprocess_packed_kernel -- are the body
+// over one source each; one launcher (launch_staged) plans and launches all of them, the form of a launch -- resize, table, fit, store
+// form, literal colour rule -- becoming template arguments in one place (with_form).
+// A workgroup owns a tile of `th` output rows x `tw` output columns of one image (normally whole rows; plan_tiles).  It
 //   1. finds its tile and the source extent its taps see (tile_of);
 //   2. tabulates the tile's column and row coordinates (x0, x1, fx), (y0, y1, fy) in LDS (fill_tables);
 //   3. stages the source it reads -- for every row y0(first)..y1(last) the contiguous span of columns x0(first)..x1(last): per channel
@@ -35,7 +38,7 @@
 // the same mean / scale.  No new interpolation: every kernel takes it as one more template parameter beside ROI.  tile_of computes the
 // rectangle per workgroup (a table is device data) and fills a tile that lies wholly in the padding without touching `src`; fill_tables
 // runs the taps over (ih, iw) at d - dx, d - dy, clamped into the rectangle, so a tile stages what its intersection with the rectangle
-// reads; the inner loops replace the value of a pixel outside it by the pad (quads may straddle the edge: dx is any integer; the stores do
+// reads; the quad loop replaces the value of a pixel outside it by the pad (quads may straddle the edge: dx is any integer; the stores do
 // not change).  The tiles are sized by a bound on the taps' step over every rectangle the launch may meet (Reach), and a workgroup whose
 // tile would still not fit its slots writes NaN instead of staging.  tests/letterbox_ref.py is the rule in numpy.
 //
@@ -59,6 +62,8 @@
 // 55.5 us against 47.2 / 53.9 us -- and 174 / 141 us for the ROI launch on the same rectangles.
 #include "pvhip_common.h"
 #include "pvhip_fit_rect.h"
+
+#include <type_traits>
 
 #pragma clang fp contract(off)
 
@@ -97,7 +102,33 @@ __device__ __forceinline__ Tap tap(int d, int S, int D) {
     return t;
 }
 
-// What a launch of either kernel is given; each kernel's own members follow it (PrepArgs, YuvArgs).
+// What the _fit_ entries add to a launch; fit 0: none.  false: not a fit, or no finite pad.
+struct Fit {
+    int fit;
+    float pad;
+    bool ok() const { return (fit == 1 || fit == 2) && pad - pad == 0.0f; }
+};
+
+struct YuvRule;
+
+// What an entry asks of its launcher (launch_staged, preprocess_warp_launch), as the caller gave it.  rois == NULL: image b is the whole
+// of source image b, with m = n and (roi_h, roi_w) = (src_h, src_w); else image b is a rectangle of one of m frames, and the tiles and
+// LDS slots are sized for the largest rectangle (roi_h, roi_w): extent() is monotone in S, so the budget holds for every image.
+struct Job {
+    const void* src;
+    float* dst;
+    const int* rois;
+    int n, m, c;
+    int src_h, src_w, dst_h, dst_w, roi_h, roi_w;
+    int how;                  // raw: src_u8 | src_nhwc << 1; YUV 4:2:0: planar; 4-byte units: kind
+    int reverse;
+    const float *mean, *std_scale;
+    Fit fit;                  // (the warp entries: fit 0 and their pad)
+    const YuvRule* rule;      // NULL: BT.601 limited range, the LIT kernels
+    const long long* table;   // the warp entries
+};
+
+// What a launch of any kernel is given; each kernel's own members follow it (PrepArgs, YuvArgs, PackedArgs, WarpArgs).
 struct TileArgs {
     const unsigned char* src;
     float* dst;
@@ -267,6 +298,30 @@ __device__ __forceinline__ bool col_inside(const Tile& t, int j) { return (unsig
 
 // A span of `span` bytes fits a slot of `slot` bytes as the launchers size them.
 __device__ __forceinline__ bool span_fits(int span, unsigned slot) { return ((unsigned)span + 30) / 16 * 16 <= slot; }
+// ... and the slot they give a span of at most `span` bytes.
+size_t slot_for(size_t span) { return (span + 30) / 16 * 16; }
+
+// ------------------------------------------------------------------------------------------------------------------- the sources
+// A source is the one place that knows a format: RawSource<U8>, Yuv420Source<LIT>, PackedSource<KIND, LIT>.  staged_tile and
+// launch_staged are written over what each of them declares:
+//   Args                          the kernel's argument struct, TileArgs and the format's own members;
+//   K                             the channels one decode yields; the c channels of the destination are c / K groups of K;
+//   Lit<L>                        the source with the YuvRule as literals (L) or from the arguments; itself where it has no rule;
+// on the host, beside the device code they bound (cols, rows: the source columns and rows a tile reads at most, Reach):
+//   check(job, a)                 the format's argument checks; sets the format's members of a (a holds common_args' already);
+//   stage_bytes(a, rows, cols)    the LDS bytes a tile stages;     set_slots(a, cols): the slot members of a;
+// on the device, constructed for one tile from (a, t, tb, lds) once the coordinate tables are filled -- a source COPIES what it needs of
+// the tile and the tables into members of its own (ox, ys0, ...) and keeps no reference to either: with references in the struct the
+// 4:2:2 kernels came out a register and 0.3 - 1.0 us a launch worse (profiles/preprocess_source_refactor.md) --:
+//   channels(a)                   the destination's channels;
+//   kCopies, copies<CROP>(t)      where kCopies: (workgroup-uniform) the tile takes every pixel's one tap as it is.  A source that
+//                                 never copies declares kCopies false and no copies(): its kernels then carry no trace of the rule;
+//   groups(), kGroups, fits()     c / K (kGroups: 1 where that is known here, else 0); every span fits its slot and the slots fit
+//                                 stage_bytes (FIT kernels check it);
+//   blocks(), stage(i)            the 16-byte blocks the tile stages, and block i of them;
+//   row(r, g)                     the handle (Row) of the r-th staged source row (tap row - ys0) for channel group g;
+//   decode(row, x, o)             o[0..K) = the channels of group g of the pixel at column x of that row.
+// x is a tap coordinate: relative to the image's rectangle, as the tables hold it.
 
 // ------------------------------------------------------------------------------------------------------------ U8 / FP32 images
 struct PrepArgs : TileArgs {
@@ -274,87 +329,65 @@ struct PrepArgs : TileArgs {
     unsigned slot;            // LDS bytes per staged span (a multiple of 16)
 };
 
-// dynamic LDS stage_bytes + Tables::bytes(tw, th).  ROI (with RESIZE): image n is a rectangle of a frame (see the file comment).
-// FIT (with RESIZE): the source is fitted into the destination and padded (see the file comment).
-template <bool U8, bool RESIZE, bool VS, bool ROI, bool FIT = false>
-__global__ __launch_bounds__(kBlock) void preprocess_kernel(PrepArgs a) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-    constexpr int ES = U8 ? 1 : 4;
-    Tile t;
-    if (!tile_of<ROI, FIT>(a, a.c, t)) return;
-    // (workgroup-uniform) the rectangle has the destination's extent (FIT: the source has the fitted rectangle's): fp32 sources are
-    // copied, identity weights would turn an inf neighbour into NaN (bytes interpolate to the same bits: weight 0 on a finite value)
-    const bool copy = (ROI || FIT) && !U8 && t.hs == t.ih && t.ws == t.iw;
-    const Tables tb = fill_tables<FIT>(lds, a, t, [&](int d, int S, int D) { return copy ? tap<false>(d, S, D) : tap<RESIZE>(d, S, D); });
-    const int rows = tb.ys1 - tb.ys0 + 1;
-    const int cs = a.nhwc ? a.c : 1, planes = a.nhwc ? 1 : a.c;
-    const int span = (tb.xs1 - tb.xs0 + 1) * cs * ES;        // bytes of one staged span
-    if (FIT && !(span_fits(span, a.slot) && (size_t)planes * rows * a.slot <= a.stage_bytes)) {   // (never, by fit_steps' bound)
-        fill_tile<false>(a, a.c, t, __builtin_nanf(""));
-        return;
+// One span per source row: of each channel plane (NCHW), or of all channels side by side (NHWC).  A group is one channel, whatever c.
+template <bool U8>
+struct RawSource {
+    using Args = PrepArgs;
+    template <bool>
+    using Lit = RawSource;
+    static constexpr int K = 1, ES = U8 ? 1 : 4;
+
+    static int check(const Job& j, Args& a) {
+        PVHIP_CHECK_ARG(j.c <= kMaxChannels);
+        PVHIP_CHECK_ARG(U8 || (uintptr_t)j.src % 4 == 0);                            // fp32 sources are element-aligned
+        a.c = j.c; a.nhwc = j.how >> 1;
+        return PVHIP_OK;
     }
+    static size_t slot_bytes(const Args& a, size_t cols) { return slot_for(cols * (a.nhwc ? (size_t)a.c : 1) * ES); }
+    static size_t stage_bytes(const Args& a, size_t rows, size_t cols) { return (a.nhwc ? 1 : (size_t)a.c) * rows * slot_bytes(a, cols); }
+    static void set_slots(Args& a, size_t cols) { a.slot = (unsigned)slot_bytes(a, cols); }
+
+    const Args& a;
+    int img, ox, oy, xs0, ys0;    // the frame and the rectangle's corner in it; the first staged column and row
+    unsigned char* lds;
+    int rows, cs, planes, span;   // staged rows; elements per pixel of a span, spans per row; bytes of one staged span
+    unsigned bps;                 // 16-byte blocks a span touches at most
+
+    __device__ __forceinline__ static int channels(const Args& a) { return a.c; }
+    // the rectangle has the destination's extent (FIT: the source has the fitted rectangle's): fp32 sources are copied, identity weights
+    // would turn an inf neighbour into NaN (bytes interpolate to the same bits: weight 0 on a finite value)
+    static constexpr bool kCopies = true;
+    template <bool CROP>
+    __device__ __forceinline__ static bool copies(const Tile& t) { return CROP && !U8 && t.hs == t.ih && t.ws == t.iw; }
+
+    __device__ __forceinline__ RawSource(const Args& a, const Tile& t, const Tables& tb, unsigned char* lds)
+        : a(a), img(t.img), ox(t.ox), oy(t.oy), xs0(tb.xs0), ys0(tb.ys0), lds(lds), rows(tb.ys1 - tb.ys0 + 1), cs(a.nhwc ? a.c : 1), planes(a.nhwc ? 1 : a.c),
+          span((tb.xs1 - tb.xs0 + 1) * cs * ES), bps((unsigned)span / 16 + 2) {}
+    static constexpr int kGroups = 0;         // c of them
+    __device__ __forceinline__ int groups() const { return a.c; }
+    __device__ __forceinline__ bool fits() const { return span_fits(span, a.slot) && (size_t)planes * rows * a.slot <= a.stage_bytes; }
     // span s = plane * rows + row: its first byte in the source
-    auto span_src = [&](int s) -> const unsigned char* {
+    __device__ __forceinline__ const unsigned char* span_src(int s) const {
         const int p = s / rows, r = s - p * rows;
-        const size_t e = a.nhwc ? ((size_t)t.img * a.hs + t.oy + tb.ys0 + r) * a.ws * (size_t)a.c + (size_t)(t.ox + tb.xs0) * a.c
-                                : (((size_t)t.img * a.c + p) * a.hs + t.oy + tb.ys0 + r) * a.ws + t.ox + tb.xs0;
+        const size_t e = a.nhwc ? ((size_t)img * a.hs + oy + ys0 + r) * a.ws * (size_t)a.c + (size_t)(ox + xs0) * a.c
+                                : (((size_t)img * a.c + p) * a.hs + oy + ys0 + r) * a.ws + ox + xs0;
         return a.src + e * ES;
-    };
-    const unsigned bps = (unsigned)span / 16 + 2;             // 16-byte blocks a span touches at most
-    const unsigned nblk = (unsigned)(planes * rows) * bps;
-    for (unsigned i = threadIdx.x; i < nblk; i += kBlock) {
+    }
+    __device__ __forceinline__ unsigned blocks() const { return (unsigned)(planes * rows) * bps; }
+    __device__ __forceinline__ void stage(unsigned i) const {
         const unsigned s = i / bps;
         stage_block(span_src((int)s), span, lds + s * a.slot, i - s * bps);
     }
-    __syncthreads();
-
-    const int nq = (t.twv + 3) >> 2;
-    const size_t plane_out = (size_t)a.hd * a.wd;
-    float* out_n = a.dst + (size_t)t.n * a.c * plane_out;
-    for (int i = threadIdx.x; i < t.thv * nq; i += kBlock) {
-        const int r = i / nq, j0 = 4 * (i - r * nq);
-        const int y0 = tb.ry0[r] - tb.ys0, y1 = tb.ry1[r] - tb.ys0;
-        const float fy = tb.rfy[r], gy = 1.0f - fy;
-        const bool rin = !FIT || row_inside(t, r);
-        int xa[4], xb[4];
-        float fx[4], gx[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int j = j0 + u < t.twv ? j0 + u : j0;       // (a pixel past the tile computes column j0 again and is not stored)
-            xa[u] = (tb.cx0[j] - tb.xs0) * cs;
-            xb[u] = (tb.cx1[j] - tb.xs0) * cs;
-            fx[u] = tb.cfx[j];
-            gx[u] = 1.0f - fx[u];
-        }
-        float* o = out_n + (size_t)(t.ty0 + r) * a.wd + t.tx0 + j0;
-        for (int oc = 0; oc < a.c; ++oc, o += plane_out) {
-            const int sc = a.reverse ? a.c - 1 - oc : oc;
-            const int s0 = (a.nhwc ? 0 : sc) * rows + y0, s1 = (a.nhwc ? 0 : sc) * rows + y1;
-            const unsigned char* l0 = span_base(lds + (unsigned)s0 * a.slot, span_src(s0));
-            const unsigned char* l1 = span_base(lds + (unsigned)s1 * a.slot, span_src(s1));
-            const int ch = a.nhwc ? sc : 0;
-            float v[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                if (RESIZE && !copy) {
-                    const float top = gx[u] * pixel<U8>(l0, xa[u] + ch) + fx[u] * pixel<U8>(l0, xb[u] + ch);
-                    const float bot = gx[u] * pixel<U8>(l1, xa[u] + ch) + fx[u] * pixel<U8>(l1, xb[u] + ch);
-                    v[u] = gy * top + fy * bot;
-                } else {
-                    v[u] = pixel<U8>(l0, xa[u] + ch);
-                }
-                if (FIT && !(rin && col_inside(t, j0 + u))) v[u] = a.pad;
-            }
-            finish_quad<VS>(a, oc, v, o, j0, t.twv);
-        }
+    struct Row {
+        const unsigned char* l;
+        int ch;                   // the channel's element inside a pixel of the span
+    };
+    __device__ __forceinline__ Row row(int r, int g) const {
+        const int s = (a.nhwc ? 0 : g) * rows + r;
+        return Row{span_base(lds + (unsigned)s * a.slot, span_src(s)), a.nhwc ? g : 0};
     }
-}
-
-template <bool U8, bool RESIZE, bool ROI, bool FIT = false>
-void launch(const PrepArgs& a, dim3 grid, size_t lds, bool vs, hipStream_t st) {
-    if (vs) hipLaunchKernelGGL((preprocess_kernel<U8, RESIZE, true, ROI, FIT>), grid, dim3(kBlock), lds, st, a);
-    else    hipLaunchKernelGGL((preprocess_kernel<U8, RESIZE, false, ROI, FIT>), grid, dim3(kBlock), lds, st, a);
-}
+    __device__ __forceinline__ void decode(const Row& w, int x, float (&o)[K]) const { o[0] = pixel<U8>(w.l, (x - xs0) * cs + w.ch); }
+};
 
 // ---------------------------------------------------------------------------------------------------------------- YUV 4:2:0 sources
 // A decoder's frame -- uint8, 3 h / 2 rows of w bytes per image: the Y plane, then NV12's h/2 rows of w/2 (U, V) pairs or I420's U plane
@@ -428,39 +461,65 @@ __device__ __forceinline__ void yuv_to_bgr(const YuvRule& k, int y, int u, int v
     o[2] = (float)min(max(r, 0), 255);
 }
 
-// dynamic LDS stage_bytes + Tables::bytes(tw, th).  ROI (with RESIZE): the chroma of a pixel is that of its ABSOLUTE 2 x 2 block of the
-// frame, so a rectangle may start on odd coordinates and have odd sizes.  (A rectangle of the destination's extent needs no copy path
-// here: the converted pixels are bytes, and weight 0 on a finite value interpolates to the same bits.)
-template <bool RESIZE, bool VS, bool ROI, bool FIT = false, bool LIT = true>
-__global__ __launch_bounds__(kBlock) void preprocess_yuv_kernel(YuvArgs a) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-    Tile t;
-    if (!tile_of<ROI, FIT>(a, 3, t)) return;
-    const Tables tb = fill_tables<FIT>(lds, a, t, [](int d, int S, int D) { return tap<RESIZE>(d, S, D); });
-    const int ox = t.ox, oy = t.oy, xs0 = tb.xs0, ys0 = tb.ys0;
-    const int rows = tb.ys1 - ys0 + 1, yspan = tb.xs1 - xs0 + 1;
-    const int ps0 = (ox + xs0) >> 1, cr0 = (oy + ys0) >> 1, crows = ((oy + tb.ys1) >> 1) - cr0 + 1;   // first chroma pair and row, chroma rows
-    const int cstep = a.planar ? 1 : 2;                                            // bytes from one U (V) to the next
-    const int cspan = (((ox + tb.xs1) >> 1) - ps0 + 1) * cstep;
-    const int hw = a.ws >> 1;
-    const unsigned char* frame = a.src + (size_t)t.img * ((size_t)a.hs * a.ws / 2 * 3);
-    const unsigned char* chroma = frame + (size_t)a.hs * a.ws;
-    auto y_src = [&](int r) -> const unsigned char* { return frame + (size_t)(oy + ys0 + r) * a.ws + ox + xs0; };
+// ROI: the chroma of a pixel is that of its ABSOLUTE 2 x 2 block of the frame, so a rectangle may start on odd coordinates and have odd
+// sizes.  (A rectangle of the destination's extent needs no copy path here: the converted pixels are bytes, and weight 0 on a finite
+// value interpolates to the same bits.)
+template <bool LIT = true>
+struct Yuv420Source {
+    using Args = YuvArgs;
+    template <bool L>
+    using Lit = Yuv420Source<L>;
+    static constexpr int K = 3;
+
+    static int check(const Job& j, Args& a) {
+        PVHIP_CHECK_ARG(j.src_h % 2 == 0 && j.src_w % 2 == 0);                       // 4:2:0: one (U, V) per 2 x 2 block
+        PVHIP_CHECK_ARG(j.how == 0 || j.how == 1);
+        a.planar = j.how; a.rule = j.rule ? *j.rule : kYuvRules[0][0];
+        return PVHIP_OK;
+    }
+    // e consecutive rows (columns) lie over at most e / 2 + 1 chroma rows (pairs): the first may be an odd one
+    static size_t halves(size_t e, int S) { return e / 2 + 1 < (size_t)S / 2 ? e / 2 + 1 : (size_t)S / 2; }
+    static size_t yslot_bytes(const Args&, size_t cols) { return slot_for(cols); }
+    static size_t cslot_bytes(const Args& a, size_t cols) { return slot_for(halves(cols, a.ws) * (a.planar ? 1 : 2)); }
+    static size_t stage_bytes(const Args& a, size_t rows, size_t cols) {
+        return rows * yslot_bytes(a, cols) + halves(rows, a.hs) * (a.planar ? 2 : 1) * cslot_bytes(a, cols);
+    }
+    static void set_slots(Args& a, size_t cols) { a.yslot = (unsigned)yslot_bytes(a, cols); a.cslot = (unsigned)cslot_bytes(a, cols); }
+
+    const Args& a;
+    int ox, oy, xs0, ys0;         // the rectangle's corner in the frame; the first staged column and row
+    unsigned char* lds;
+    int rows, yspan;              // staged Y rows, bytes of one of them
+    int ps0, cr0, crows;          // first chroma pair and row, chroma rows
+    int cstep, cspan, hw;         // bytes from one U (V) to the next; bytes of one chroma span; a chroma plane's row
+    const unsigned char *frame, *chroma;
+    unsigned char* lds_c;         // the chroma slots, behind the Y slots
+    unsigned ybps, cbps, yblk, cblk;
+
+    __device__ __forceinline__ static int channels(const Args&) { return K; }
+    static constexpr bool kCopies = false;
+
+    __device__ __forceinline__ Yuv420Source(const Args& a, const Tile& t, const Tables& tb, unsigned char* lds)
+        : a(a), ox(t.ox), oy(t.oy), xs0(tb.xs0), ys0(tb.ys0), lds(lds), rows(tb.ys1 - tb.ys0 + 1), yspan(tb.xs1 - tb.xs0 + 1), ps0((t.ox + tb.xs0) >> 1),
+          cr0((t.oy + tb.ys0) >> 1), crows(((t.oy + tb.ys1) >> 1) - cr0 + 1), cstep(a.planar ? 1 : 2),
+          cspan((((t.ox + tb.xs1) >> 1) - ps0 + 1) * cstep), hw(a.ws >> 1), frame(a.src + (size_t)t.img * ((size_t)a.hs * a.ws / 2 * 3)),
+          chroma(frame + (size_t)a.hs * a.ws), lds_c(lds + (unsigned)rows * a.yslot), ybps((unsigned)yspan / 16 + 2),
+          cbps((unsigned)cspan / 16 + 2), yblk((unsigned)rows * ybps), cblk((unsigned)(crows * (a.planar ? 2 : 1)) * cbps) {}
+    static constexpr int kGroups = 1;
+    __device__ __forceinline__ int groups() const { return 1; }
+    __device__ __forceinline__ bool fits() const {
+        return span_fits(yspan, a.yslot) && span_fits(cspan, a.cslot) &&
+               (size_t)rows * a.yslot + (size_t)crows * (a.planar ? 2 : 1) * a.cslot <= a.stage_bytes;
+    }
+    __device__ __forceinline__ const unsigned char* y_src(int r) const { return frame + (size_t)(oy + ys0 + r) * a.ws + ox + xs0; }
     // chroma span s: NV12 row s of the pairs; I420 row s of U for s < crows, row s - crows of V after them
-    auto c_src = [&](int s) -> const unsigned char* {
+    __device__ __forceinline__ const unsigned char* c_src(int s) const {
         if (!a.planar) return chroma + (size_t)(cr0 + s) * a.ws + 2 * ps0;
         const int p = s >= crows ? 1 : 0;
         return chroma + ((size_t)p * (a.hs >> 1) + cr0 + s - p * crows) * hw + ps0;
-    };
-    if (FIT && !(span_fits(yspan, a.yslot) && span_fits(cspan, a.cslot) &&
-                 (size_t)rows * a.yslot + (size_t)crows * (a.planar ? 2 : 1) * a.cslot <= a.stage_bytes)) {   // (never, by fit_steps' bound)
-        fill_tile<false>(a, 3, t, __builtin_nanf(""));
-        return;
     }
-    unsigned char* lds_c = lds + (unsigned)rows * a.yslot;
-    const unsigned ybps = (unsigned)yspan / 16 + 2, cbps = (unsigned)cspan / 16 + 2;
-    const unsigned yblk = (unsigned)rows * ybps, cblk = (unsigned)(crows * (a.planar ? 2 : 1)) * cbps;
-    for (unsigned i = threadIdx.x; i < yblk + cblk; i += kBlock) {
+    __device__ __forceinline__ unsigned blocks() const { return yblk + cblk; }
+    __device__ __forceinline__ void stage(unsigned i) const {
         if (i < yblk) {
             const unsigned s = i / ybps;
             stage_block(y_src((int)s), yspan, lds + s * a.yslot, i - s * ybps);
@@ -469,72 +528,23 @@ __global__ __launch_bounds__(kBlock) void preprocess_yuv_kernel(YuvArgs a) {
             stage_block(c_src((int)s), cspan, lds_c + s * a.cslot, i - yblk - s * cbps);
         }
     }
-    __syncthreads();
-
-    const int nq = (t.twv + 3) >> 2;
-    const size_t plane_out = (size_t)a.hd * a.wd;
-    float* out_n = a.dst + (size_t)t.n * 3 * plane_out;
-    for (int i = threadIdx.x; i < t.thv * nq; i += kBlock) {
-        const int r = i / nq, j0 = 4 * (i - r * nq);
-        const float fy = tb.rfy[r], gy = 1.0f - fy;
-        const bool rin = !FIT || row_inside(t, r);
-        // the two tapped rows: their Y spans, and the U and V of the chroma rows under them
-        const unsigned char *ly[2], *lu[2], *lv[2];
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            const int ya = k ? tb.ry1[r] : tb.ry0[r];
-            const int yr = ya - ys0, cr = ((oy + ya) >> 1) - cr0;
-            ly[k] = span_base(lds + (unsigned)yr * a.yslot, y_src(yr));
-            lu[k] = span_base(lds_c + (unsigned)cr * a.cslot, c_src(cr));
-            lv[k] = a.planar ? span_base(lds_c + (unsigned)(crows + cr) * a.cslot, c_src(crows + cr)) : lu[k] + 1;
-        }
-        float v[3][4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int j = j0 + u < t.twv ? j0 + u : j0;       // (a pixel past the tile computes column j0 again and is not stored)
-            const int xa = tb.cx0[j], xb = tb.cx1[j];
-            const int pa = (((ox + xa) >> 1) - ps0) * cstep, pb = (((ox + xb) >> 1) - ps0) * cstep;
-            float p00[3];
-            yuv_to_bgr<LIT>(a.rule, ly[0][xa - xs0], lu[0][pa], lv[0][pa], p00);
-            if (RESIZE) {
-                const float fx = tb.cfx[j], gx = 1.0f - fx;
-                float p01[3], p10[3], p11[3];
-                yuv_to_bgr<LIT>(a.rule, ly[0][xb - xs0], lu[0][pb], lv[0][pb], p01);
-                yuv_to_bgr<LIT>(a.rule, ly[1][xa - xs0], lu[1][pa], lv[1][pa], p10);
-                yuv_to_bgr<LIT>(a.rule, ly[1][xb - xs0], lu[1][pb], lv[1][pb], p11);
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    const float top = gx * p00[c] + fx * p01[c];
-                    const float bot = gx * p10[c] + fx * p11[c];
-                    v[c][u] = gy * top + fy * bot;
-                }
-            } else {
-#pragma unroll
-                for (int c = 0; c < 3; ++c) v[c][u] = p00[c];
-            }
-            if (FIT && !(rin && col_inside(t, j0 + u))) {
-#pragma unroll
-                for (int c = 0; c < 3; ++c) v[c][u] = a.pad;
-            }
-        }
-        float* o = out_n + (size_t)(t.ty0 + r) * a.wd + t.tx0 + j0;
-#pragma unroll
-        for (int oc = 0; oc < 3; ++oc, o += plane_out) {
-            float w[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) w[u] = a.reverse ? v[2 - oc][u] : v[oc][u];
-            finish_quad<VS>(a, oc, w, o, j0, t.twv);
-        }
+    // a tapped row: its Y span, and the U and V of the chroma row under it
+    struct Row {
+        const unsigned char *ly, *lu, *lv;
+    };
+    __device__ __forceinline__ Row row(int yr, int) const {
+        const int cr = ((oy + ys0 + yr) >> 1) - cr0;
+        Row w;
+        w.ly = span_base(lds + (unsigned)yr * a.yslot, y_src(yr));
+        w.lu = span_base(lds_c + (unsigned)cr * a.cslot, c_src(cr));
+        w.lv = a.planar ? span_base(lds_c + (unsigned)(crows + cr) * a.cslot, c_src(crows + cr)) : w.lu + 1;
+        return w;
     }
-}
-
-template <bool RESIZE, bool ROI, bool FIT = false>
-void launch_yuv(const YuvArgs& a, dim3 grid, size_t lds, bool vs, bool lit, hipStream_t st) {
-#define PVHIP_YUV(VS, LIT) hipLaunchKernelGGL((preprocess_yuv_kernel<RESIZE, VS, ROI, FIT, LIT>), grid, dim3(kBlock), lds, st, a)
-    if (lit) { if (vs) PVHIP_YUV(true, true); else PVHIP_YUV(false, true); }
-    else     { if (vs) PVHIP_YUV(true, false); else PVHIP_YUV(false, false); }
-#undef PVHIP_YUV
-}
+    __device__ __forceinline__ void decode(const Row& w, int x, float (&o)[K]) const {
+        const int p = (((ox + x) >> 1) - ps0) * cstep;
+        yuv_to_bgr<LIT>(a.rule, w.ly[x - xs0], w.lu[p], w.lv[p], o);
+    }
+};
 
 // ------------------------------------------------------------------------------------------------------ packed 4-byte-unit sources
 // Frames whose rows are 4-byte units, uint8, any alignment:
@@ -571,97 +581,169 @@ __device__ __forceinline__ void packed_to_bgr(const YuvRule& k, const unsigned c
     }
 }
 
-// dynamic LDS stage_bytes + Tables::bytes(tw, th).  ROI (with RESIZE): a 4:2:2 pixel keeps the chroma of its ABSOLUTE column pair, so a
-// rectangle may start on an odd x and have an odd w.  (No copy path for a rectangle of the destination's extent: the pixels are bytes.)
-template <int KIND, bool RESIZE, bool VS, bool ROI, bool FIT = false, bool LIT = true>
-__global__ __launch_bounds__(kBlock) void preprocess_packed_kernel(PackedArgs a) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-    constexpr bool YUV = KIND < 2;
-    Tile t;
-    if (!tile_of<ROI, FIT>(a, 3, t)) return;
-    const Tables tb = fill_tables<FIT>(lds, a, t, [](int d, int S, int D) { return tap<RESIZE>(d, S, D); });
-    const int ox = t.ox, oy = t.oy, ys0 = tb.ys0;
-    const int rows = tb.ys1 - ys0 + 1;
-    const int u0 = YUV ? (ox + tb.xs0) >> 1 : ox + tb.xs0;                         // the first and the last unit of every staged row
-    const int u1 = YUV ? (ox + tb.xs1) >> 1 : ox + tb.xs1;
-    const int span = (u1 - u0 + 1) * 4;
-    if (FIT && !(span_fits(span, a.slot) && (size_t)rows * a.slot <= a.stage_bytes)) {   // (never, by fit_steps' bound)
-        fill_tile<false>(a, 3, t, __builtin_nanf(""));
-        return;
+// ROI: a 4:2:2 pixel keeps the chroma of its ABSOLUTE column pair, so a rectangle may start on an odd x and have an odd w.  (No copy
+// path for a rectangle of the destination's extent: the pixels are bytes.)  Kinds 2 and 3 convert nothing: they have the LIT form only.
+template <int KIND, bool LIT = true>
+struct PackedSource {
+    using Args = PackedArgs;
+    template <bool L>
+    using Lit = PackedSource<KIND, L || KIND >= 2>;
+    static constexpr int K = 3;
+    static constexpr bool YUV = KIND < 2;
+
+    static int check(const Job& j, Args& a) {
+        PVHIP_CHECK_ARG(!YUV || j.src_w % 2 == 0);                                   // 4:2:2: one (U, V) per column pair
+        a.rule = j.rule ? *j.rule : kYuvRules[0][0];
+        return PVHIP_OK;
     }
-    const size_t row_bytes = (size_t)a.ws * (YUV ? 2 : 4);
-    const unsigned char* frame = a.src + (size_t)t.img * ((size_t)a.hs * row_bytes);
-    auto row_src = [&](int r) -> const unsigned char* { return frame + (size_t)(oy + ys0 + r) * row_bytes + (size_t)u0 * 4; };
-    const unsigned bps = (unsigned)span / 16 + 2;             // 16-byte blocks a span touches at most
-    const unsigned nblk = (unsigned)rows * bps;
-    for (unsigned i = threadIdx.x; i < nblk; i += kBlock) {
+    // e consecutive columns lie in at most e / 2 + 1 groups of 4:2:2 (the first may be an odd one), and in e units of an X kind
+    static size_t units(const Args& a, size_t e) { return !YUV ? e : (e / 2 + 1 < (size_t)a.ws / 2 ? e / 2 + 1 : (size_t)a.ws / 2); }
+    static size_t slot_bytes(const Args& a, size_t cols) { return slot_for(units(a, cols) * 4); }
+    static size_t stage_bytes(const Args& a, size_t rows, size_t cols) { return rows * slot_bytes(a, cols); }
+    static void set_slots(Args& a, size_t cols) { a.slot = (unsigned)slot_bytes(a, cols); }
+
+    const Args& a;
+    int ox, oy, ys0;              // the rectangle's corner in the frame; the first staged row
+    unsigned char* lds;
+    int rows, u0, span;           // staged rows; the first unit of every one of them, and their bytes
+    size_t row_bytes;
+    const unsigned char* frame;
+    unsigned bps;                 // 16-byte blocks a span touches at most
+
+    __device__ __forceinline__ static int channels(const Args&) { return K; }
+    static constexpr bool kCopies = false;
+
+    __device__ __forceinline__ PackedSource(const Args& a, const Tile& t, const Tables& tb, unsigned char* lds)
+        : a(a), ox(t.ox), oy(t.oy), ys0(tb.ys0), lds(lds), rows(tb.ys1 - tb.ys0 + 1), u0(YUV ? (t.ox + tb.xs0) >> 1 : t.ox + tb.xs0),
+          span(((YUV ? (t.ox + tb.xs1) >> 1 : t.ox + tb.xs1) - u0 + 1) * 4), row_bytes((size_t)a.ws * (YUV ? 2 : 4)),
+          frame(a.src + (size_t)t.img * ((size_t)a.hs * row_bytes)), bps((unsigned)span / 16 + 2) {}
+    static constexpr int kGroups = 1;
+    __device__ __forceinline__ int groups() const { return 1; }
+    __device__ __forceinline__ bool fits() const { return span_fits(span, a.slot) && (size_t)rows * a.slot <= a.stage_bytes; }
+    __device__ __forceinline__ const unsigned char* row_src(int r) const { return frame + (size_t)(oy + ys0 + r) * row_bytes + (size_t)u0 * 4; }
+    __device__ __forceinline__ unsigned blocks() const { return (unsigned)rows * bps; }
+    __device__ __forceinline__ void stage(unsigned i) const {
         const unsigned s = i / bps;
         stage_block(row_src((int)s), span, lds + s * a.slot, i - s * bps);
     }
+    struct Row {
+        const unsigned char* l;
+    };
+    __device__ __forceinline__ Row row(int r, int) const {
+        return Row{span_base(lds + (unsigned)r * a.slot, row_src(r))};
+    }
+    __device__ __forceinline__ void decode(const Row& w, int x, float (&o)[K]) const { packed_to_bgr<KIND, LIT>(a.rule, w.l, ox, x, u0, o); }
+};
+
+// ---------------------------------------------------------------------------------------------------- the tile body, the kernels
+// One workgroup's tile, steps 1 to 4 of the file comment, for any source.  dynamic LDS: stage_bytes + Tables::bytes(tw, th).
+// ROI (with RESIZE): image n is a rectangle of a frame; FIT (with RESIZE): the source is fitted into the destination and padded (see
+// the file comment).  VS: finish_quad.  The interpolation is the file comment's, in its order; a tile without resize, and one that
+// copies(), takes the one tap as it is.
+template <class Source, bool CROP>
+__device__ __forceinline__ bool copies_of(const Tile& t) {
+    if constexpr (Source::kCopies) return Source::template copies<CROP>(t);
+    else return false;
+}
+
+template <class Source, bool RESIZE, bool VS, bool ROI, bool FIT>
+__device__ __forceinline__ void staged_tile(const typename Source::Args& a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    constexpr int K = Source::K;
+    const int c = Source::channels(a);
+    Tile t;
+    if (!tile_of<ROI, FIT>(a, c, t)) return;
+    const bool one_tap = !RESIZE || copies_of<Source, ROI || FIT>(t);      // (workgroup-uniform)
+    const Tables tb = fill_tables<FIT>(lds, a, t, [&](int d, int S, int D) {
+        if constexpr (Source::kCopies) return one_tap ? tap<false>(d, S, D) : tap<RESIZE>(d, S, D);
+        else return tap<RESIZE>(d, S, D);
+    });
+    const Source src(a, t, tb, lds);
+    if (FIT && !src.fits()) {                                 // (never, by Reach's bound)
+        fill_tile<false>(a, c, t, __builtin_nanf(""));
+        return;
+    }
+    for (unsigned i = threadIdx.x; i < src.blocks(); i += kBlock) src.stage(i);
     __syncthreads();
 
     const int nq = (t.twv + 3) >> 2;
     const size_t plane_out = (size_t)a.hd * a.wd;
-    float* out_n = a.dst + (size_t)t.n * 3 * plane_out;
+    float* out_n = a.dst + (size_t)t.n * c * plane_out;
     for (int i = threadIdx.x; i < t.thv * nq; i += kBlock) {
         const int r = i / nq, j0 = 4 * (i - r * nq);
         const float fy = tb.rfy[r], gy = 1.0f - fy;
         const bool rin = !FIT || row_inside(t, r);
-        const int r0 = tb.ry0[r] - ys0, r1 = tb.ry1[r] - ys0;                      // the two tapped rows
-        const unsigned char* l0 = span_base(lds + (unsigned)r0 * a.slot, row_src(r0));
-        const unsigned char* l1 = span_base(lds + (unsigned)r1 * a.slot, row_src(r1));
-        float v[3][4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int j = j0 + u < t.twv ? j0 + u : j0;       // (a pixel past the tile computes column j0 again and is not stored)
-            const int xa = tb.cx0[j], xb = tb.cx1[j];
-            float p00[3];
-            packed_to_bgr<KIND, LIT>(a.rule, l0, ox, xa, u0, p00);
-            if (RESIZE) {
-                const float fx = tb.cfx[j], gx = 1.0f - fx;
-                float p01[3], p10[3], p11[3];
-                packed_to_bgr<KIND, LIT>(a.rule, l0, ox, xb, u0, p01);
-                packed_to_bgr<KIND, LIT>(a.rule, l1, ox, xa, u0, p10);
-                packed_to_bgr<KIND, LIT>(a.rule, l1, ox, xb, u0, p11);
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    const float top = gx * p00[c] + fx * p01[c];
-                    const float bot = gx * p10[c] + fx * p11[c];
-                    v[c][u] = gy * top + fy * bot;
-                }
-            } else {
-#pragma unroll
-                for (int c = 0; c < 3; ++c) v[c][u] = p00[c];
-            }
-            if (FIT && !(rin && col_inside(t, j0 + u))) {
-#pragma unroll
-                for (int c = 0; c < 3; ++c) v[c][u] = a.pad;
-            }
-        }
+        const int r0 = tb.ry0[r] - tb.ys0, r1 = tb.ry1[r] - tb.ys0;   // the two tapped rows, among the staged ones
         float* o = out_n + (size_t)(t.ty0 + r) * a.wd + t.tx0 + j0;
+        // output channels g K .. g K + K - 1 read source group g, under reversal the last group first and its channels backwards
+        int g = 0;
+        do {                                                  // (kGroups == 1: no loop is emitted at all, the colour kernels' form)
+            const int sg = a.reverse ? src.groups() - 1 - g : g;
+            const typename Source::Row w0 = src.row(r0, sg), w1 = src.row(r1, sg);
+            float v[K][4];
 #pragma unroll
-        for (int oc = 0; oc < 3; ++oc, o += plane_out) {
-            float w[4];
+            for (int u = 0; u < 4; ++u) {
+                const int j = j0 + u < t.twv ? j0 + u : j0;   // (a pixel past the tile computes column j0 again and is not stored)
+                const int xa = tb.cx0[j], xb = tb.cx1[j];
+                float p00[K];
+                src.decode(w0, xa, p00);
+                if (Source::kCopies ? !one_tap : RESIZE) {
+                    const float fx = tb.cfx[j], gx = 1.0f - fx;
+                    float p01[K], p10[K], p11[K];
+                    src.decode(w0, xb, p01);
+                    src.decode(w1, xa, p10);
+                    src.decode(w1, xb, p11);
 #pragma unroll
-            for (int u = 0; u < 4; ++u) w[u] = a.reverse ? v[2 - oc][u] : v[oc][u];
-            finish_quad<VS>(a, oc, w, o, j0, t.twv);
-        }
+                    for (int k = 0; k < K; ++k) {
+                        const float top = gx * p00[k] + fx * p01[k];
+                        const float bot = gx * p10[k] + fx * p11[k];
+                        v[k][u] = gy * top + fy * bot;
+                    }
+                } else {
+#pragma unroll
+                    for (int k = 0; k < K; ++k) v[k][u] = p00[k];
+                }
+                if (FIT && !(rin && col_inside(t, j0 + u))) {
+#pragma unroll
+                    for (int k = 0; k < K; ++k) v[k][u] = a.pad;
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < K; ++k, o += plane_out) {
+                float w[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) w[u] = a.reverse ? v[K - 1 - k][u] : v[k][u];
+                finish_quad<VS>(a, g * K + k, w, o, j0, t.twv);
+            }
+        } while (Source::kGroups != 1 && ++g < src.groups());
     }
 }
 
-template <int KIND, bool LIT = true>
-void launch_packed(const PackedArgs& a, dim3 grid, size_t lds, bool vs, bool roi, bool resize, hipStream_t st) {
-#define PVHIP_PACKED(RESIZE, ROI, FIT)                                                                                         \
-    do {                                                                                                                           \
-        if (vs) hipLaunchKernelGGL((preprocess_packed_kernel<KIND, RESIZE, true, ROI, FIT, LIT>), grid, dim3(kBlock), lds, st, a);      \
-        else    hipLaunchKernelGGL((preprocess_packed_kernel<KIND, RESIZE, false, ROI, FIT, LIT>), grid, dim3(kBlock), lds, st, a);\
-    } while (0)
-    if (a.fit)       { if (roi) PVHIP_PACKED(true, true, true); else PVHIP_PACKED(true, false, true); }
-    else if (roi)    PVHIP_PACKED(true, true, false);
-    else if (resize) PVHIP_PACKED(true, false, false);
-    else             PVHIP_PACKED(false, false, false);
-#undef PVHIP_PACKED
+// The kernels: the body over each source, and kernel_of: the kernel of a source's form.
+template <class>
+struct Type {};
+
+template <bool U8, bool RESIZE, bool VS, bool ROI, bool FIT = false>
+__global__ __launch_bounds__(kBlock) void preprocess_kernel(PrepArgs a) {
+    staged_tile<RawSource<U8>, RESIZE, VS, ROI, FIT>(a);
 }
+
+template <bool RESIZE, bool VS, bool ROI, bool FIT = false, bool LIT = true>
+__global__ __launch_bounds__(kBlock) void preprocess_yuv_kernel(YuvArgs a) {
+    staged_tile<Yuv420Source<LIT>, RESIZE, VS, ROI, FIT>(a);
+}
+
+template <int KIND, bool RESIZE, bool VS, bool ROI, bool FIT = false, bool LIT = true>
+__global__ __launch_bounds__(kBlock) void preprocess_packed_kernel(PackedArgs a) {
+    staged_tile<PackedSource<KIND, LIT>, RESIZE, VS, ROI, FIT>(a);
+}
+
+template <bool RESIZE, bool VS, bool ROI, bool FIT, bool U8>
+constexpr auto kernel_of(Type<RawSource<U8>>) { return preprocess_kernel<U8, RESIZE, VS, ROI, FIT>; }
+template <bool RESIZE, bool VS, bool ROI, bool FIT, bool LIT>
+constexpr auto kernel_of(Type<Yuv420Source<LIT>>) { return preprocess_yuv_kernel<RESIZE, VS, ROI, FIT, LIT>; }
+template <bool RESIZE, bool VS, bool ROI, bool FIT, int KIND, bool LIT>
+constexpr auto kernel_of(Type<PackedSource<KIND, LIT>>) { return preprocess_packed_kernel<KIND, RESIZE, VS, ROI, FIT, LIT>; }
 
 // ------------------------------------------------------------------------------------------------------------------ affine warps
 // Image b is frame id of m frames sampled through the 2 x 3 matrix of row b of `table` = n x (id, A00, A01, C0, A10, A11, C1), int64,
@@ -867,22 +949,17 @@ void launch_warp(const WarpArgs& a, dim3 grid, bool vs, hipStream_t st) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------- launchers
-// The launchers take rois == NULL: image b is the whole of source image b, with m = n and (roi_h, roi_w) = (src_h, src_w); else image b
-// is a rectangle of one of m frames, and the tiles and LDS slots are sized for the largest rectangle (roi_h, roi_w): extent() is
-// monotone in S, so the budget holds for every image.
-
-// What both launchers check, and the members of `a` that follow from the arguments alone; c: the destination's channels.
-int common_args(TileArgs& a, const void* src, float* dst, const int* rois, int n, int m, int c, int src_h, int src_w, int dst_h, int dst_w,
-                int roi_h, int roi_w, int reverse_channels, const float* mean, const float* std_scale) {
+// What every launcher checks of a Job, and the members of `a` that follow from it alone.
+int common_args(TileArgs& a, const Job& j) {
     PVHIP_REQUIRE_INIT();
-    PVHIP_CHECK_ARG(src != nullptr && dst != nullptr);
-    PVHIP_CHECK_ARG(n > 0 && n <= 65535 && c > 0 && src_h > 0 && src_w > 0 && dst_h > 0 && dst_w > 0);
-    PVHIP_CHECK_ARG((size_t)src_h * (size_t)src_w * (size_t)c < ((size_t)1 << 31));   // one image's elements index in 32 bits
-    PVHIP_CHECK_ARG((size_t)dst_h * (size_t)dst_w * (size_t)c < ((size_t)1 << 31));
-    PVHIP_CHECK_ARG(m >= 1 && roi_h >= 1 && roi_h <= src_h && roi_w >= 1 && roi_w <= src_w);
-    a.src = (const unsigned char*)src; a.dst = dst; a.mean = mean; a.std_scale = std_scale;
-    a.hs = src_h; a.ws = src_w; a.hd = dst_h; a.wd = dst_w; a.reverse = reverse_channels ? 1 : 0;
-    a.rois = rois; a.m = m; a.mh = roi_h; a.mw = roi_w; a.fit = 0; a.pad = 0.0f;
+    PVHIP_CHECK_ARG(j.src != nullptr && j.dst != nullptr);
+    PVHIP_CHECK_ARG(j.n > 0 && j.n <= 65535 && j.c > 0 && j.src_h > 0 && j.src_w > 0 && j.dst_h > 0 && j.dst_w > 0);
+    PVHIP_CHECK_ARG((size_t)j.src_h * (size_t)j.src_w * (size_t)j.c < ((size_t)1 << 31));   // one image's elements index in 32 bits
+    PVHIP_CHECK_ARG((size_t)j.dst_h * (size_t)j.dst_w * (size_t)j.c < ((size_t)1 << 31));
+    PVHIP_CHECK_ARG(j.m >= 1 && j.roi_h >= 1 && j.roi_h <= j.src_h && j.roi_w >= 1 && j.roi_w <= j.src_w);
+    a.src = (const unsigned char*)j.src; a.dst = j.dst; a.mean = j.mean; a.std_scale = j.std_scale;
+    a.hs = j.src_h; a.ws = j.src_w; a.hd = j.dst_h; a.wd = j.dst_w; a.reverse = j.reverse ? 1 : 0;
+    a.rois = j.rois; a.m = j.m; a.mh = j.roi_h; a.mw = j.roi_w; a.fit = j.fit.fit; a.pad = j.fit.pad;
     return PVHIP_OK;
 }
 
@@ -931,13 +1008,6 @@ Reach reach_of(const TileArgs& a, bool roi, bool resize) {
     return r;
 }
 
-// What the _fit_ entries add to the launchers' arguments; fit 0: none.  false: not a fit, or no finite pad.
-struct Fit {
-    int fit;
-    float pad;
-    bool ok() const { return (fit == 1 || fit == 2) && pad - pad == 0.0f; }
-};
-
 struct TilePlan {
     dim3 grid;
     size_t lds;
@@ -963,129 +1033,102 @@ int plan_tiles(TileArgs& a, int n, StageOf stage_of, TilePlan& p) {
     return PVHIP_OK;
 }
 
-// The one launcher of preprocess_kernel.
-int preprocess_launch(const void* src, float* dst, const int* rois, int n, int m, int c, int src_h, int src_w, int dst_h, int dst_w,
-                      int roi_h, int roi_w, int src_u8, int src_nhwc, int reverse_channels, const float* mean, const float* std_scale,
-                      Fit fit = Fit{0, 0.0f}) {
-    PrepArgs a;
-    int rc = common_args(a, src, dst, rois, n, m, c, src_h, src_w, dst_h, dst_w, roi_h, roi_w, reverse_channels, mean, std_scale);
-    if (rc != PVHIP_OK) return rc;
-    PVHIP_CHECK_ARG(c <= kMaxChannels);
-    PVHIP_CHECK_ARG(src_u8 || (uintptr_t)src % 4 == 0);                              // fp32 sources are element-aligned
-    const bool roi = rois != nullptr, resize = roi || fit.fit || src_h != dst_h || src_w != dst_w;
-    if (!resize && !reverse_channels && mean == nullptr && std_scale == nullptr)      // the format alone: the same bits as the
-        return pvhip_input_to_nchw_f32(src, dst, n, c, dst_h, dst_w, src_u8, src_nhwc);   // path without preprocessing
-    a.fit = fit.fit; a.pad = fit.pad;
-    const Reach reach = reach_of(a, roi, resize);
-    const size_t es = src_u8 ? 1 : 4;
-    const size_t cs = src_nhwc ? (size_t)c : 1, planes = src_nhwc ? 1 : (size_t)c;
-    auto slot_of = [&](int tw) { return (reach.cols(tw) * cs * es + 30) / 16 * 16; };
-    TilePlan p;
-    rc = plan_tiles(a, n, [&](int tw, int th) { return planes * reach.rows(th) * slot_of(tw); }, p);
-    if (rc != PVHIP_OK) return rc;
-    a.c = c; a.nhwc = src_nhwc ? 1 : 0; a.slot = (unsigned)slot_of(a.tw);
-    hipStream_t st = state().stream;
-    if (fit.fit) {
-        if (roi) src_u8 ? launch<true, true, true, true>(a, p.grid, p.lds, p.vs, st) : launch<false, true, true, true>(a, p.grid, p.lds, p.vs, st);
-        else     src_u8 ? launch<true, true, false, true>(a, p.grid, p.lds, p.vs, st) : launch<false, true, false, true>(a, p.grid, p.lds, p.vs, st);
-    }
-    else if (roi)    src_u8 ? launch<true, true, true>(a, p.grid, p.lds, p.vs, st) : launch<false, true, true>(a, p.grid, p.lds, p.vs, st);
-    else if (src_u8) resize ? launch<true, true, false>(a, p.grid, p.lds, p.vs, st) : launch<true, false, false>(a, p.grid, p.lds, p.vs, st);
-    else             resize ? launch<false, true, false>(a, p.grid, p.lds, p.vs, st) : launch<false, false, false>(a, p.grid, p.lds, p.vs, st);
-    PVHIP_LAUNCH_CHECK();
-    return PVHIP_OK;
-}
+template <bool B>
+using Flag = std::integral_constant<bool, B>;
 
-// The one launcher of preprocess_yuv_kernel.  rule: NULL for BT.601 limited range, the LIT kernels (so too in the launchers below).
-int preprocess_yuv_launch(const void* src, float* dst, const int* rois, int n, int m, int src_h, int src_w, int dst_h, int dst_w,
-                          int roi_h, int roi_w, int planar, int reverse_channels, const float* mean, const float* std_scale,
-                          Fit fit = Fit{0, 0.0f}, const YuvRule* rule = nullptr) {
-    YuvArgs a;
-    int rc = common_args(a, src, dst, rois, n, m, 3, src_h, src_w, dst_h, dst_w, roi_h, roi_w, reverse_channels, mean, std_scale);
-    if (rc != PVHIP_OK) return rc;
-    PVHIP_CHECK_ARG(src_h % 2 == 0 && src_w % 2 == 0);                               // 4:2:0: one (U, V) per 2 x 2 block
-    PVHIP_CHECK_ARG(planar == 0 || planar == 1);
-    const bool roi = rois != nullptr, resize = roi || fit.fit || src_h != dst_h || src_w != dst_w;
-    a.fit = fit.fit; a.pad = fit.pad;
-    const Reach reach = reach_of(a, roi, resize);
-    // e consecutive rows (columns) lie over at most e / 2 + 1 chroma rows (pairs): the first may be an odd one
-    auto halves = [](size_t e, int S) { return e / 2 + 1 < (size_t)S / 2 ? e / 2 + 1 : (size_t)S / 2; };
-    auto yslot_of = [&](int tw) { return (reach.cols(tw) + 30) / 16 * 16; };
-    auto cslot_of = [&](int tw) { return (halves(reach.cols(tw), src_w) * (planar ? 1 : 2) + 30) / 16 * 16; };
-    auto stage_of = [&](int tw, int th) {
-        const size_t e = reach.rows(th);
-        return e * yslot_of(tw) + halves(e, src_h) * (planar ? 2 : 1) * cslot_of(tw);
+// The form of a staged launch as compile-time flags: f(RESIZE, VS, ROI, FIT, LIT), over the five (RESIZE, ROI, FIT) that exist.
+template <class F>
+void with_form(bool resize, bool roi, bool fit, bool vs, bool lit, F f) {
+    constexpr Flag<true> yes{};
+    constexpr Flag<false> no{};
+    auto rest = [&](auto R, auto O, auto T) {
+        if (lit) { if (vs) f(R, yes, O, T, yes); else f(R, no, O, T, yes); }
+        else     { if (vs) f(R, yes, O, T, no); else f(R, no, O, T, no); }
     };
-    TilePlan p;
-    rc = plan_tiles(a, n, stage_of, p);
-    if (rc != PVHIP_OK) return rc;
-    a.planar = planar; a.yslot = (unsigned)yslot_of(a.tw); a.cslot = (unsigned)cslot_of(a.tw); a.rule = rule ? *rule : kYuvRules[0][0];
-    hipStream_t st = state().stream;
-    const bool lit = rule == nullptr;
-    if (fit.fit) roi ? launch_yuv<true, true, true>(a, p.grid, p.lds, p.vs, lit, st) : launch_yuv<true, false, true>(a, p.grid, p.lds, p.vs, lit, st);
-    else if (roi) launch_yuv<true, true>(a, p.grid, p.lds, p.vs, lit, st);
-    else     resize ? launch_yuv<true, false>(a, p.grid, p.lds, p.vs, lit, st) : launch_yuv<false, false>(a, p.grid, p.lds, p.vs, lit, st);
-    PVHIP_LAUNCH_CHECK();
-    return PVHIP_OK;
+    if (fit)         { if (roi) rest(yes, yes, yes); else rest(yes, no, yes); }
+    else if (roi)    rest(yes, yes, no);
+    else if (resize) rest(yes, no, no);
+    else             rest(no, no, no);
 }
 
-// The one launcher of preprocess_packed_kernel.  kind: 0 YUY2, 1 UYVY, 2 BGRX, 3 RGBX.
-int preprocess_packed_launch(const void* src, float* dst, const int* rois, int n, int m, int src_h, int src_w, int dst_h, int dst_w,
-                             int roi_h, int roi_w, int kind, int reverse_channels, const float* mean, const float* std_scale,
-                             Fit fit = Fit{0, 0.0f}, const YuvRule* rule = nullptr) {
-    PackedArgs a;
-    int rc = common_args(a, src, dst, rois, n, m, 3, src_h, src_w, dst_h, dst_w, roi_h, roi_w, reverse_channels, mean, std_scale);
+bool resizes(const Job& j) { return j.rois != nullptr || j.fit.fit || j.src_h != j.dst_h || j.src_w != j.dst_w; }
+
+// What a launch of `Source` checks of its Job, in this order, and the members of `a` that follow from the Job alone.
+template <class Source>
+int checked_args(typename Source::Args& a, const Job& j) {
+    const int rc = common_args(a, j);
+    return rc != PVHIP_OK ? rc : Source::check(j, a);
+}
+
+// The one launcher of the staged kernels.  No declared rule: the LIT kernels (with_form also hands a source without a rule, and kinds
+// 2 and 3, the flag: their Lit<> is the one form they have).
+template <class Source>
+int launch_staged(const Job& j) {
+    typename Source::Args a;
+    int rc = checked_args<Source>(a, j);
     if (rc != PVHIP_OK) return rc;
-    PVHIP_CHECK_ARG(kind >= 0 && kind <= 3);
-    const bool yuv = kind < 2;
-    PVHIP_CHECK_ARG(!yuv || src_w % 2 == 0);                                         // 4:2:2: one (U, V) per column pair
-    const bool roi = rois != nullptr, resize = roi || fit.fit || src_h != dst_h || src_w != dst_w;
-    a.fit = fit.fit; a.pad = fit.pad;
+    const bool roi = j.rois != nullptr, resize = resizes(j);
     const Reach reach = reach_of(a, roi, resize);
-    // e consecutive columns lie in at most e / 2 + 1 groups of 4:2:2 (the first may be an odd one), and in e units of an X kind
-    auto units = [&](size_t e) { return !yuv ? e : (e / 2 + 1 < (size_t)src_w / 2 ? e / 2 + 1 : (size_t)src_w / 2); };
-    auto slot_of = [&](int tw) { return (units(reach.cols(tw)) * 4 + 30) / 16 * 16; };
     TilePlan p;
-    rc = plan_tiles(a, n, [&](int tw, int th) { return reach.rows(th) * slot_of(tw); }, p);
+    rc = plan_tiles(a, j.n, [&](int tw, int th) { return Source::stage_bytes(a, reach.rows(th), reach.cols(tw)); }, p);
     if (rc != PVHIP_OK) return rc;
-    a.slot = (unsigned)slot_of(a.tw); a.rule = rule ? *rule : kYuvRules[0][0];
+    Source::set_slots(a, reach.cols(a.tw));
     hipStream_t st = state().stream;
-    switch (kind) {
-        case 0:  rule ? launch_packed<0, false>(a, p.grid, p.lds, p.vs, roi, resize, st) : launch_packed<0>(a, p.grid, p.lds, p.vs, roi, resize, st); break;
-        case 1:  rule ? launch_packed<1, false>(a, p.grid, p.lds, p.vs, roi, resize, st) : launch_packed<1>(a, p.grid, p.lds, p.vs, roi, resize, st); break;
-        case 2:  launch_packed<2>(a, p.grid, p.lds, p.vs, roi, resize, st); break;
-        default: launch_packed<3>(a, p.grid, p.lds, p.vs, roi, resize, st); break;
-    }
+    with_form(resize, roi, a.fit != 0, p.vs, j.rule == nullptr, [&](auto R, auto V, auto O, auto T, auto L) {
+        using Form = typename Source::template Lit<decltype(L)::value>;
+        constexpr auto kernel = kernel_of<decltype(R)::value, decltype(V)::value, decltype(O)::value, decltype(T)::value>(Type<Form>{});
+        hipLaunchKernelGGL(kernel, p.grid, dim3(kBlock), p.lds, st, a);
+    });
     PVHIP_LAUNCH_CHECK();
     return PVHIP_OK;
 }
 
-// The one launcher of preprocess_warp_kernel.  format 0 raw (how = src_u8 | src_nhwc << 1), 1 YUV 4:2:0 (how = planar), 2 frames of
-// 4-byte units (how = kind): the limits of the launcher of that format above.
-int preprocess_warp_launch(const void* src, float* dst, const long long* table, int n, int m, int c, int src_h, int src_w, int dst_h,
-                           int dst_w, int format, int how, int reverse_channels, const float* mean, const float* std_scale, float pad_value,
-                           const YuvRule* rule = nullptr) {
+// U8 / FP32 images.  The format alone is no launch of these kernels: the same bits as the path without preprocessing, after the
+// checks of a launch.
+template <bool U8>
+int launch_raw(const Job& j) {
+    if (resizes(j) || j.reverse || j.mean != nullptr || j.std_scale != nullptr) return launch_staged<RawSource<U8>>(j);
+    PrepArgs a;
+    const int rc = checked_args<RawSource<U8>>(a, j);
+    return rc != PVHIP_OK ? rc : pvhip_input_to_nchw_f32(j.src, j.dst, j.n, j.c, j.dst_h, j.dst_w, U8, j.how >> 1);
+}
+
+int launch_packed(const Job& j) {
+    PVHIP_REQUIRE_INIT();
+    PVHIP_CHECK_ARG(j.how >= 0 && j.how <= 3);   // 0 YUY2, 1 UYVY, 2 BGRX, 3 RGBX
+    switch (j.how) {
+        case 0:  return launch_staged<PackedSource<0>>(j);
+        case 1:  return launch_staged<PackedSource<1>>(j);
+        case 2:  return launch_staged<PackedSource<2>>(j);
+        default: return launch_staged<PackedSource<3>>(j);
+    }
+}
+
+// The one launcher of preprocess_warp_kernel.  format 0 raw, 1 YUV 4:2:0, 2 frames of 4-byte units, with the `how` and the limits of
+// that format's source above; the pad is j.fit.pad.
+int preprocess_warp_launch(const Job& j, int format) {
     WarpArgs a;
-    int rc = common_args(a, src, dst, nullptr, n, m, c, src_h, src_w, dst_h, dst_w, src_h, src_w, reverse_channels, mean, std_scale);
+    int rc = common_args(a, j);
     if (rc != PVHIP_OK) return rc;
-    PVHIP_CHECK_ARG(table != nullptr);
-    PVHIP_CHECK_ARG(pad_value - pad_value == 0.0f);
+    const int how = j.how;
+    PVHIP_CHECK_ARG(j.table != nullptr);
+    PVHIP_CHECK_ARG(j.fit.pad - j.fit.pad == 0.0f);
     PVHIP_CHECK_ARG(format >= 0 && format <= 2);
-    PVHIP_CHECK_ARG(format == 0 || c == 3);
+    PVHIP_CHECK_ARG(format == 0 || j.c == 3);
     PVHIP_CHECK_ARG(how >= 0 && how <= (format == 1 ? 1 : 3));
     if (format == 0) {
-        PVHIP_CHECK_ARG(c <= kMaxChannels);
-        PVHIP_CHECK_ARG((how & 1) || (uintptr_t)src % 4 == 0);                       // fp32 sources are element-aligned
+        PVHIP_CHECK_ARG(j.c <= kMaxChannels);
+        PVHIP_CHECK_ARG((how & 1) || (uintptr_t)j.src % 4 == 0);                     // fp32 sources are element-aligned
     } else if (format == 1) {
-        PVHIP_CHECK_ARG(src_h % 2 == 0 && src_w % 2 == 0);                           // 4:2:0: one (U, V) per 2 x 2 block
+        PVHIP_CHECK_ARG(j.src_h % 2 == 0 && j.src_w % 2 == 0);                       // 4:2:0: one (U, V) per 2 x 2 block
     } else {
-        PVHIP_CHECK_ARG(how >= 2 || src_w % 2 == 0);                                 // 4:2:2: one (U, V) per column pair
+        PVHIP_CHECK_ARG(how >= 2 || j.src_w % 2 == 0);                               // 4:2:2: one (U, V) per column pair
     }
-    const dim3 grid((unsigned)((dst_w + kWarpTileW - 1) / kWarpTileW), (unsigned)((dst_h + kWarpTileH - 1) / kWarpTileH), (unsigned)n);
+    const dim3 grid((unsigned)((j.dst_w + kWarpTileW - 1) / kWarpTileW), (unsigned)((j.dst_h + kWarpTileH - 1) / kWarpTileH), (unsigned)j.n);
     PVHIP_CHECK_ARG(grid.y <= 65535);
-    a.table = table; a.c = c; a.pad = pad_value; a.rule = rule ? *rule : kYuvRules[0][0];
-    const bool vs = (uintptr_t)dst % 16 == 0 && dst_w % 4 == 0;
-    const bool a4 = (uintptr_t)src % 4 == 0;
+    a.table = j.table; a.c = j.c; a.rule = j.rule ? *j.rule : kYuvRules[0][0];
+    const bool vs = (uintptr_t)j.dst % 16 == 0 && j.dst_w % 4 == 0;
+    const bool a4 = (uintptr_t)j.src % 4 == 0;
     hipStream_t st = state().stream;
     switch (format * 8 + how * 2 + (format == 2 && a4 ? 1 : 0)) {
         case 0:  launch_warp<RawFetch<false, false>>(a, grid, vs, st); break;
@@ -1107,19 +1150,52 @@ int preprocess_warp_launch(const void* src, float* dst, const long long* table, 
     return PVHIP_OK;
 }
 
+// The entries' Jobs: whole images (rois NULL: m = n and the maxima are the frame's) or a table's rectangles.
+Job job_of(const void* src, float* dst, const int* rois, int n, int m, int c, int src_h, int src_w, int dst_h, int dst_w, int roi_h,
+           int roi_w, int how, int reverse_channels, const float* mean, const float* std_scale) {
+    return Job{src, dst, rois, n, m, c, src_h, src_w, dst_h, dst_w, roi_h, roi_w, how, reverse_channels, mean, std_scale, Fit{0, 0.0f},
+               nullptr, nullptr};
+}
+
+int raw_how(int src_u8, int src_nhwc) { return (src_u8 ? 1 : 0) | (src_nhwc ? 2 : 0); }
+
+int launch_raw(const Job& j) { return j.how & 1 ? launch_raw<true>(j) : launch_raw<false>(j); }
+
+// The fitted forms: rois == NULL means whole images.  A fit of whole images that fills the destination is the launch without a fit.
+// stretch (the _color_ entries): fit 0 is taken too, and is the launch without a fit whatever pad_value holds.
+int set_fit(Job& j, int fit, float pad_value, bool stretch) {
+    PVHIP_REQUIRE_INIT();
+    const Fit f{fit, pad_value};
+    PVHIP_CHECK_ARG(f.ok() || (stretch && fit == 0));
+    PVHIP_CHECK_ARG(j.src_h > 0 && j.src_w > 0 && j.dst_h > 0 && j.dst_w > 0);
+    if (j.rois == nullptr) { j.m = j.n; j.roi_h = j.src_h; j.roi_w = j.src_w; }
+    const FitRect g = fit_rect(j.src_h, j.src_w, j.dst_h, j.dst_w, fit);
+    if (fit != 0 && !(j.rois == nullptr && g.iw == j.dst_w && g.ih == j.dst_h)) j.fit = f;
+    return PVHIP_OK;
+}
+
+// The _color_ entries: the rule kYuvRules[matrix][full_range] in place of BT.601 limited range, which (0, 0) is.
+int set_rule(Job& j, int matrix, int full_range) {
+    PVHIP_REQUIRE_INIT();
+    PVHIP_CHECK_ARG(matrix >= 0 && matrix <= 2 && (full_range == 0 || full_range == 1));
+    j.rule = matrix || full_range ? &kYuvRules[matrix][full_range] : nullptr;
+    return PVHIP_OK;
+}
+
 }  // namespace
 
 extern "C" {
 
 int pvhip_input_preprocess_f32(const void* src, float* dst, int n, int c, int src_h, int src_w, int dst_h, int dst_w,
                                int src_u8, int src_nhwc, int reverse_channels, const float* mean, const float* std_scale) {
-    return preprocess_launch(src, dst, nullptr, n, n, c, src_h, src_w, dst_h, dst_w, src_h, src_w, src_u8, src_nhwc, reverse_channels,
-                             mean, std_scale);
+    return launch_raw(job_of(src, dst, nullptr, n, n, c, src_h, src_w, dst_h, dst_w, src_h, src_w, raw_how(src_u8, src_nhwc),
+                             reverse_channels, mean, std_scale));
 }
 
 int pvhip_input_preprocess_yuv_f32(const void* src, float* dst, int n, int src_h, int src_w, int dst_h, int dst_w, int planar,
                                    int reverse_channels, const float* mean, const float* std_scale) {
-    return preprocess_yuv_launch(src, dst, nullptr, n, n, src_h, src_w, dst_h, dst_w, src_h, src_w, planar, reverse_channels, mean, std_scale);
+    return launch_staged<Yuv420Source<>>(job_of(src, dst, nullptr, n, n, 3, src_h, src_w, dst_h, dst_w, src_h, src_w, planar,
+                                                reverse_channels, mean, std_scale));
 }
 
 int pvhip_input_preprocess_roi_f32(const void* src, float* dst, const int* rois, int n, int m, int c, int src_h, int src_w, int dst_h,
@@ -1127,8 +1203,8 @@ int pvhip_input_preprocess_roi_f32(const void* src, float* dst, const int* rois,
                                    const float* mean, const float* std_scale) {
     PVHIP_REQUIRE_INIT();
     PVHIP_CHECK_ARG(rois != nullptr);
-    return preprocess_launch(src, dst, rois, n, m, c, src_h, src_w, dst_h, dst_w, max_roi_h, max_roi_w, src_u8, src_nhwc, reverse_channels,
-                             mean, std_scale);
+    return launch_raw(job_of(src, dst, rois, n, m, c, src_h, src_w, dst_h, dst_w, max_roi_h, max_roi_w, raw_how(src_u8, src_nhwc),
+                             reverse_channels, mean, std_scale));
 }
 
 int pvhip_input_preprocess_yuv_roi_f32(const void* src, float* dst, const int* rois, int n, int m, int src_h, int src_w, int dst_h,
@@ -1136,14 +1212,14 @@ int pvhip_input_preprocess_yuv_roi_f32(const void* src, float* dst, const int* r
                                        const float* std_scale) {
     PVHIP_REQUIRE_INIT();
     PVHIP_CHECK_ARG(rois != nullptr);
-    return preprocess_yuv_launch(src, dst, rois, n, m, src_h, src_w, dst_h, dst_w, max_roi_h, max_roi_w, planar, reverse_channels, mean,
-                                 std_scale);
+    return launch_staged<Yuv420Source<>>(job_of(src, dst, rois, n, m, 3, src_h, src_w, dst_h, dst_w, max_roi_h, max_roi_w, planar,
+                                                reverse_channels, mean, std_scale));
 }
 
 int pvhip_input_preprocess_packed_f32(const void* src, float* dst, int n, int src_h, int src_w, int dst_h, int dst_w, int kind,
                                       int reverse_channels, const float* mean, const float* std_scale) {
-    return preprocess_packed_launch(src, dst, nullptr, n, n, src_h, src_w, dst_h, dst_w, src_h, src_w, kind, reverse_channels, mean,
-                                    std_scale);
+    return launch_packed(job_of(src, dst, nullptr, n, n, 3, src_h, src_w, dst_h, dst_w, src_h, src_w, kind, reverse_channels, mean,
+                                std_scale));
 }
 
 int pvhip_input_preprocess_packed_roi_f32(const void* src, float* dst, const int* rois, int n, int m, int src_h, int src_w, int dst_h,
@@ -1151,86 +1227,72 @@ int pvhip_input_preprocess_packed_roi_f32(const void* src, float* dst, const int
                                           const float* std_scale) {
     PVHIP_REQUIRE_INIT();
     PVHIP_CHECK_ARG(rois != nullptr);
-    return preprocess_packed_launch(src, dst, rois, n, m, src_h, src_w, dst_h, dst_w, max_roi_h, max_roi_w, kind, reverse_channels, mean,
-                                    std_scale);
+    return launch_packed(job_of(src, dst, rois, n, m, 3, src_h, src_w, dst_h, dst_w, max_roi_h, max_roi_w, kind, reverse_channels, mean,
+                                std_scale));
 }
-
-// The fitted forms: rois == NULL means whole images.  A fit of whole images that fills the destination is the existing launch.
-// STRETCH (the _color_ entries): fit 0 is taken too, and is the launch without a fit whatever pad_value holds.
-#define PVHIP_FIT_ARGS(STRETCH)                                                                                               \
-    PVHIP_REQUIRE_INIT();                                                                                                      \
-    const Fit f{fit, pad_value};                                                                                               \
-    PVHIP_CHECK_ARG(f.ok() || (STRETCH && fit == 0));                                                                          \
-    PVHIP_CHECK_ARG(src_h > 0 && src_w > 0 && dst_h > 0 && dst_w > 0);                                                         \
-    if (rois == nullptr) { m = n; max_roi_h = src_h; max_roi_w = src_w; }                                                      \
-    const FitRect g = fit_rect(src_h, src_w, dst_h, dst_w, fit);                                                               \
-    const Fit used = fit == 0 || (rois == nullptr && g.iw == dst_w && g.ih == dst_h) ? Fit{0, 0.0f} : f
 
 int pvhip_input_preprocess_fit_f32(const void* src, float* dst, const int* rois, int n, int m, int c, int src_h, int src_w, int dst_h,
                                    int dst_w, int max_roi_h, int max_roi_w, int src_u8, int src_nhwc, int reverse_channels,
                                    const float* mean, const float* std_scale, int fit, float pad_value) {
-    PVHIP_FIT_ARGS(false);
-    return preprocess_launch(src, dst, rois, n, m, c, src_h, src_w, dst_h, dst_w, max_roi_h, max_roi_w, src_u8, src_nhwc, reverse_channels,
-                             mean, std_scale, used);
+    Job j = job_of(src, dst, rois, n, m, c, src_h, src_w, dst_h, dst_w, max_roi_h, max_roi_w, raw_how(src_u8, src_nhwc), reverse_channels,
+                   mean, std_scale);
+    const int rc = set_fit(j, fit, pad_value, false);
+    return rc != PVHIP_OK ? rc : launch_raw(j);
 }
 
 int pvhip_input_preprocess_yuv_fit_f32(const void* src, float* dst, const int* rois, int n, int m, int src_h, int src_w, int dst_h,
                                        int dst_w, int max_roi_h, int max_roi_w, int planar, int reverse_channels, const float* mean,
                                        const float* std_scale, int fit, float pad_value) {
-    PVHIP_FIT_ARGS(false);
-    return preprocess_yuv_launch(src, dst, rois, n, m, src_h, src_w, dst_h, dst_w, max_roi_h, max_roi_w, planar, reverse_channels, mean,
-                                 std_scale, used);
+    Job j = job_of(src, dst, rois, n, m, 3, src_h, src_w, dst_h, dst_w, max_roi_h, max_roi_w, planar, reverse_channels, mean, std_scale);
+    const int rc = set_fit(j, fit, pad_value, false);
+    return rc != PVHIP_OK ? rc : launch_staged<Yuv420Source<>>(j);
 }
 
 int pvhip_input_preprocess_packed_fit_f32(const void* src, float* dst, const int* rois, int n, int m, int src_h, int src_w, int dst_h,
                                           int dst_w, int max_roi_h, int max_roi_w, int kind, int reverse_channels, const float* mean,
                                           const float* std_scale, int fit, float pad_value) {
-    PVHIP_FIT_ARGS(false);
-    return preprocess_packed_launch(src, dst, rois, n, m, src_h, src_w, dst_h, dst_w, max_roi_h, max_roi_w, kind, reverse_channels, mean,
-                                    std_scale, used);
+    Job j = job_of(src, dst, rois, n, m, 3, src_h, src_w, dst_h, dst_w, max_roi_h, max_roi_w, kind, reverse_channels, mean, std_scale);
+    const int rc = set_fit(j, fit, pad_value, false);
+    return rc != PVHIP_OK ? rc : launch_packed(j);
 }
-
-// The _color_ entries: the launches above with the rule kYuvRules[matrix][full_range] in place of BT.601 limited range, which (0, 0) is.
-#define PVHIP_COLOR_RULE()                                                                                                    \
-    PVHIP_REQUIRE_INIT();                                                                                                      \
-    PVHIP_CHECK_ARG(matrix >= 0 && matrix <= 2 && (full_range == 0 || full_range == 1));                                       \
-    const YuvRule* rule = matrix || full_range ? &kYuvRules[matrix][full_range] : nullptr
 
 int pvhip_input_preprocess_yuv_color_f32(const void* src, float* dst, const int* rois, int n, int m, int src_h, int src_w, int dst_h,
                                          int dst_w, int max_roi_h, int max_roi_w, int planar, int reverse_channels, const float* mean,
                                          const float* std_scale, int fit, float pad_value, int matrix, int full_range) {
-    PVHIP_COLOR_RULE();
-    PVHIP_FIT_ARGS(true);
-    return preprocess_yuv_launch(src, dst, rois, n, m, src_h, src_w, dst_h, dst_w, max_roi_h, max_roi_w, planar, reverse_channels, mean,
-                                 std_scale, used, rule);
+    Job j = job_of(src, dst, rois, n, m, 3, src_h, src_w, dst_h, dst_w, max_roi_h, max_roi_w, planar, reverse_channels, mean, std_scale);
+    int rc = set_rule(j, matrix, full_range);
+    if (rc == PVHIP_OK) rc = set_fit(j, fit, pad_value, true);
+    return rc != PVHIP_OK ? rc : launch_staged<Yuv420Source<>>(j);
 }
 
 int pvhip_input_preprocess_packed_color_f32(const void* src, float* dst, const int* rois, int n, int m, int src_h, int src_w, int dst_h,
                                             int dst_w, int max_roi_h, int max_roi_w, int kind, int reverse_channels, const float* mean,
                                             const float* std_scale, int fit, float pad_value, int matrix, int full_range) {
-    PVHIP_COLOR_RULE();
+    Job j = job_of(src, dst, rois, n, m, 3, src_h, src_w, dst_h, dst_w, max_roi_h, max_roi_w, kind, reverse_channels, mean, std_scale);
+    int rc = set_rule(j, matrix, full_range);
+    if (rc != PVHIP_OK) return rc;
     PVHIP_CHECK_ARG(kind < 2 || (matrix == 0 && full_range == 0));                   // four-byte pixels: nothing to convert
-    PVHIP_FIT_ARGS(true);
-    return preprocess_packed_launch(src, dst, rois, n, m, src_h, src_w, dst_h, dst_w, max_roi_h, max_roi_w, kind, reverse_channels, mean,
-                                    std_scale, used, rule);
+    rc = set_fit(j, fit, pad_value, true);
+    return rc != PVHIP_OK ? rc : launch_packed(j);
 }
-#undef PVHIP_FIT_ARGS
 
 int pvhip_input_preprocess_warp_f32(const void* src, float* dst, const long long* table, int n, int m, int c, int src_h, int src_w,
                                     int dst_h, int dst_w, int format, int how, int reverse_channels, const float* mean,
                                     const float* std_scale, float pad_value) {
-    return preprocess_warp_launch(src, dst, table, n, m, c, src_h, src_w, dst_h, dst_w, format, how, reverse_channels, mean, std_scale,
-                                  pad_value);
+    Job j = job_of(src, dst, nullptr, n, m, c, src_h, src_w, dst_h, dst_w, src_h, src_w, how, reverse_channels, mean, std_scale);
+    j.table = table; j.fit.pad = pad_value;
+    return preprocess_warp_launch(j, format);
 }
 
 int pvhip_input_preprocess_warp_color_f32(const void* src, float* dst, const long long* table, int n, int m, int c, int src_h, int src_w,
                                           int dst_h, int dst_w, int format, int how, int reverse_channels, const float* mean,
                                           const float* std_scale, float pad_value, int matrix, int full_range) {
-    PVHIP_COLOR_RULE();
+    Job j = job_of(src, dst, nullptr, n, m, c, src_h, src_w, dst_h, dst_w, src_h, src_w, how, reverse_channels, mean, std_scale);
+    j.table = table; j.fit.pad = pad_value;
+    const int rc = set_rule(j, matrix, full_range);
+    if (rc != PVHIP_OK) return rc;
     PVHIP_CHECK_ARG((format != 0 && !(format == 2 && how >= 2)) || (matrix == 0 && full_range == 0));   // raw frames, four-byte pixels
-    return preprocess_warp_launch(src, dst, table, n, m, c, src_h, src_w, dst_h, dst_w, format, how, reverse_channels, mean, std_scale,
-                                  pad_value, rule);
+    return preprocess_warp_launch(j, format);
 }
-#undef PVHIP_COLOR_RULE
 
 }  // extern "C"

@@ -375,6 +375,21 @@ def test_fit_kernel_when_a_row_exceeds_the_lds_budget(hip, c):
         assert_bit_exact(_device_fit(hip, 'FP32-NCHW', frames, dst_hw, fit, pad, **opt), want, '{} {} {}'.format(dst_hw, fit, pad))
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize('fmt, src_hw', [('NV12', (4, 70000)), ('I420', (4, 70000)), ('YUY2', (3, 70000)), ('BGRX', (3, 20000))])
+def test_fit_kernel_of_colour_frames_when_a_row_exceeds_the_lds_budget(hip, fmt, src_hw):
+    """The colour sources on the same path: one source row (70 KB of luma with its chroma, 140 KB of YUY2 groups, 80 KB of four-byte
+    pixels) is over the LDS budget, so the output rows split into column tiles, most of them wholly in the padding; the inner rectangle
+    is one row high."""
+    rng = np.random.default_rng(70000 + FORMATS.index(fmt))
+    frames = _make_frames(rng, fmt, 2, src_hw)
+    options = _options(rng)
+    for dst_hw, fit, pad, opt in (((20, 24), 'LETTERBOX', 114.0, options[1]), ((19, 23), 'TOP_LEFT', 0.0, options[0])):
+        assert letterbox_ref.geometry(src_hw, dst_hw, fit)[2:] == (dst_hw[1], 1)
+        want = letterbox_ref.fit_frames(frames, dst_hw, fit, pad, **_ref_opts(fmt), **opt)
+        assert_bit_exact(_device_fit(hip, fmt, frames, dst_hw, fit, pad, **opt), want, '{} {} {} {}'.format(fmt, dst_hw, fit, pad))
+
+
 def _roi_table(dst_hw):
     """Over frames of (40, 48): wide; tall; exactly its own fitted (ih, iw); 1 x 48; 40 x 1; invalid (a frame that is not there)."""
     hd, wd = dst_hw
