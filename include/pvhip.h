@@ -808,6 +808,38 @@ int         pvhip_input_preprocess_packed_color_f32(const void* src, float* dst,
 int         pvhip_input_preprocess_warp_color_f32(const void* src, float* dst, const long long* table, int n, int m, int c, int src_h,
                                                   int src_w, int dst_h, int dst_w, int format, int how, int reverse_channels,
                                                   const float* mean, const float* std_scale, float pad_value, int matrix, int full_range);
+/* Addition to ABI v18 (the version number is unchanged: nothing existing changed): projective warps.  Image b of `dst` (n, c, dst_h, dst_w)
+ * is frame id of the m frames in `src`, sampled through a 3 x 3 homography: `table` is a device pointer to n x 10 int64
+ * (id, Q00, Q01, Q02, Q10, Q11, Q12, Q20, Q21, Q22).  The matrix maps an output pixel index (x, y) to the source position
+ * sx = (h00 x + h01 y + h02) / (h20 x + h21 y + h22), sy = (h10 x + h11 y + h12) / (the same denominator), pixel centres at the integers:
+ * the one cv2.warpPerspective takes with WARP_INVERSE_MAP.  The host scales each matrix by ONE power of two of its own, which the ratio
+ * does not see and the table therefore does not store: with B_r = |h_r0| (dst_w - 1) + |h_r1| (dst_h - 1) + |h_r2| for its three rows r
+ * and B = max B_r in [2^(e-1), 2^e), Q = rint(double(h) * 2^(51-e)), ties to even (a matrix with a non-finite value or B == 0 is none).
+ * Then |Q_r0| (dst_w - 1) + |Q_r1| (dst_h - 1) + |Q_r2| <= 2^52 for every r -- the limit of a table filled directly as well --, so each
+ * linear form below is exact as int64 and as binary64.  Output pixel (y, x) of image b:
+ *   NX = Q00 x + Q01 y + Q02,  NY = Q10 x + Q11 y + Q12,  D = Q20 x + Q21 y + Q22          (int64)
+ *   TX = floor(double(NX) / double(D) * 65536.0),  TY likewise          (binary64: one correctly rounded division each, no reciprocal
+ *                                                                        shared between the two, nothing contracted)
+ *   the pixel is pad_value in every channel unless D != 0 and |TX| < 2^47 and |TY| < 2^47 (compares that a NaN fails); else
+ *   SX = (int64)TX,  SY = (int64)TY
+ * and from SX, SY on the rule of pvhip_input_preprocess_warp_f32 word for word: ix = SX >> 16, fx = float(SX & 0xFFFF) * 2^-16, a tap
+ * outside the frame is pad_value, a zero fraction reads no second tap, top, bot and v in fp32 in that order without fma, colour frames
+ * converted per tap with the chroma of the pixel's block of the frame, then the reversal and (v - mean[k]) / std_scale[k].  A negative D
+ * is a legal denominator: -H is the same map as H; where D changes sign inside an image (the horizon of the map) the pixels with D == 0
+ * are the pad and those on either side are sampled.  With (Q20, Q21, Q22) = (0, 0, 2^16) and Q16 coefficients in the first two rows it is
+ * the warp entry bit for bit.  In numpy: tests/perspective_ref.py, matched bit for bit.  The table is read on the device only: an image
+ * whose id is outside [0, m) is written as quiet NaN, and nothing of `src` is read for it; the device cannot check the limit, so it
+ * computes the forms in wrapping unsigned arithmetic and a table beyond it gives other pixels, never a load outside the frames.  `format`,
+ * `how`, every other argument and every limit are those of pvhip_input_preprocess_warp_f32 -- table != NULL, m >= 1, format in 0..2,
+ * c == 3 for formats 1 and 2, pad_value finite and the rest --; else PVHIP_EINVAL and nothing is launched.  _color_: then matrix and full_range
+ * as pvhip_input_preprocess_warp_color_f32 takes them, under its limits.  One launch on the current stream, no allocation. */
+int         pvhip_input_preprocess_perspective_f32(const void* src, float* dst, const long long* table, int n, int m, int c, int src_h,
+                                                   int src_w, int dst_h, int dst_w, int format, int how, int reverse_channels,
+                                                   const float* mean, const float* std_scale, float pad_value);
+int         pvhip_input_preprocess_perspective_color_f32(const void* src, float* dst, const long long* table, int n, int m, int c,
+                                                         int src_h, int src_w, int dst_h, int dst_w, int format, int how,
+                                                         int reverse_channels, const float* mean, const float* std_scale,
+                                                         float pad_value, int matrix, int full_range);
 
 #ifdef __cplusplus
 }

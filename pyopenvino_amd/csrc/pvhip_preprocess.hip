@@ -60,6 +60,16 @@
 // -- and 32 divides the 224 of the classifiers here, which 64 does not.  Measured (profiles/warp_input.md; 256 rows of 1080p frames
 // -> 224 x 224, uint8 NHWC / NV12): 30 degrees at scale 3 313 / 156 us against 326 / 198 us for 64 x 16, upright at scale 3 48.6 /
 // 55.5 us against 47.2 / 53.9 us -- and 174 / 141 us for the ROI launch on the same rectangles.
+//
+// Projective warps (the perspective entry; preprocess_perspective_kernel): image b is frame id sampled through a 3 x 3 homography,
+// table[b] = (id, Q00 .. Q22) as int64, the matrix scaled on the host by a power of two of its own so that every linear form stays
+// below 2^52 over the extent (the ratio does not see the scale).  For output pixel (y, x): NX = Q00 x + Q01 y + Q02, NY = Q10 x +
+// Q11 y + Q12, D = Q20 x + Q21 y + Q22 in int64; TX = floor(double(NX) / double(D) * 65536), TY likewise -- binary64, one IEEE division
+// each (the compiler's v_div_scale / v_rcp / v_div_fmas / v_div_fixup sequence: no reciprocal shared, nothing contracted), exact
+// operands, so numpy's float64 gives the same bits --; the pixel is the pad unless D != 0 and |TX|, |TY| < 2^47; else SX = TX, SY = TY
+// and the rule above from there on.  Only where the sample position comes from is new: the kernel has the tile, the fetch functors and
+// the quad body (sample_quad) of the affine kernel, two divisions per pixel in place of two additions, and no whole-number form.
+// tests/perspective_ref.py is the rule in numpy; include/pvhip.h states it in full.
 #include "pvhip_common.h"
 #include "pvhip_fit_rect.h"
 
@@ -865,18 +875,12 @@ __device__ __forceinline__ WarpTap warp_tap(long long s, int extent) {
     return t;
 }
 
-// The quad of one lane: output columns x.. of row y of image t.n, for every channel.  WHOLE: every coefficient of the image's matrix is
-// a whole number (workgroup-uniform), so no pixel has a second tap: the one tap is copied.
+// The quad of one lane behind its taps (both warp kernels): output columns t.tx0 + j0.. of row t.ty0 + r of image t.n, for every
+// channel, pixel u sampled at (ty[u], tx[u]).  WHOLE: no pixel has a second tap (workgroup-uniform): the one tap is copied.
 template <class Fetch, bool VS, bool WHOLE>
-__device__ __forceinline__ void warp_quad(const WarpArgs& a, const Tile& t, const Fetch& fetch, int r, int j0, long long sx, long long sy,
-                                          long long ax, long long ay) {
+__device__ __forceinline__ void sample_quad(const WarpArgs& a, const Tile& t, const Fetch& fetch, int r, int j0, const WarpTap (&tx)[4],
+                                            const WarpTap (&ty)[4]) {
     constexpr int K = Fetch::K;
-    WarpTap tx[4], ty[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {                             // SX, SY advance by A00, A10 per pixel
-        tx[u] = warp_tap(sx + u * ax, a.ws);
-        ty[u] = warp_tap(sy + u * ay, a.hs);
-    }
     const size_t plane_out = (size_t)a.hd * a.wd;
     float* o = a.dst + (size_t)t.n * a.c * plane_out + (size_t)(t.ty0 + r) * a.wd + t.tx0 + j0;
     for (int oc0 = 0; oc0 < a.c; oc0 += K) {
@@ -919,31 +923,96 @@ __device__ __forceinline__ void warp_quad(const WarpArgs& a, const Tile& t, cons
     }
 }
 
-// grid (ceil(wd / kWarpTileW), ceil(hd / kWarpTileH), n); no LDS.  The table row is read once per workgroup (uniform loads); an image
-// whose id is no frame is filled with quiet NaN and nothing of `src` is read for it.
+// The affine front end of a quad: SX, SY of its first pixel, advancing by A00, A10 per pixel.
+template <class Fetch, bool VS, bool WHOLE>
+__device__ __forceinline__ void warp_quad(const WarpArgs& a, const Tile& t, const Fetch& fetch, int r, int j0, long long sx, long long sy,
+                                          long long ax, long long ay) {
+    WarpTap tx[4], ty[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        tx[u] = warp_tap(sx + u * ax, a.ws);
+        ty[u] = warp_tap(sy + u * ay, a.hs);
+    }
+    sample_quad<Fetch, VS, WHOLE>(a, t, fetch, r, j0, tx, ty);
+}
+
+// The tile of this workgroup and the row of its image in a table of `columns` int64 per image (both warp kernels).  The row is read
+// once per workgroup (uniform loads); NULL: the image's id is no frame, the tile is filled with quiet NaN and the workgroup is done.
+__device__ __forceinline__ const long long* warp_tile_of(const WarpArgs& a, int columns, Tile& t) {
+    t.n = blockIdx.z; t.tx0 = blockIdx.x * kWarpTileW; t.ty0 = blockIdx.y * kWarpTileH;
+    t.twv = min(kWarpTileW, a.wd - t.tx0); t.thv = min(kWarpTileH, a.hd - t.ty0);
+    const long long* q = a.table + columns * (size_t)t.n;
+    if (!(q[0] >= 0 && q[0] < a.m)) {
+        fill_tile<false>(a, a.c, t, __builtin_nanf(""));
+        return nullptr;
+    }
+    return q;
+}
+
+// grid (ceil(wd / kWarpTileW), ceil(hd / kWarpTileH), n); no LDS.  An image whose id is no frame is filled with quiet NaN and nothing
+// of `src` is read for it.
 template <class Fetch, bool VS>
 __global__ __launch_bounds__(kBlock) void preprocess_warp_kernel(WarpArgs a) {
     Tile t;
-    t.n = blockIdx.z; t.tx0 = blockIdx.x * kWarpTileW; t.ty0 = blockIdx.y * kWarpTileH;
-    t.twv = min(kWarpTileW, a.wd - t.tx0); t.thv = min(kWarpTileH, a.hd - t.ty0);
-    const long long* q = a.table + 7 * (size_t)t.n;
-    const long long id = q[0];
-    if (!(id >= 0 && id < a.m)) {
-        fill_tile<false>(a, a.c, t, __builtin_nanf(""));
-        return;
-    }
+    const long long* q = warp_tile_of(a, 7, t);
+    if (q == nullptr) return;
     const long long a00 = q[1], a01 = q[2], c0 = q[3], a10 = q[4], a11 = q[5], c1 = q[6];
     const int r = threadIdx.x / kWarpQuads, j0 = 4 * (threadIdx.x % kWarpQuads);
     if (r >= t.thv || j0 >= t.twv) return;
     const long long x = t.tx0 + j0, y = t.ty0 + r;            // (|A| <= 2^26, |C| <= 2^40, x, y < 2^31: below 2^59)
     const long long sx = a00 * x + a01 * y + c0, sy = a10 * x + a11 * y + c1;
-    const Fetch fetch(a, (int)id);
+    const Fetch fetch(a, (int)q[0]);
     if (((a00 | a01 | c0 | a10 | a11 | c1) & 0xFFFF) == 0) warp_quad<Fetch, VS, true>(a, t, fetch, r, j0, sx, sy, a00, a10);
     else                                                   warp_quad<Fetch, VS, false>(a, t, fetch, r, j0, sx, sy, a00, a10);
 }
 
+// ------------------------------------------------------------------------------------------------------------- projective warps
+// Image b is frame id of m frames sampled through the homography of row b of `table` = n x (id, Q00 .. Q22), int64, the matrix scaled
+// by a power of two of its own (the perspective entry; the rule is in the file comment and, in numpy, in tests/perspective_ref.py).
+// The taps of one output pixel whose linear forms are nx, ny and d: SX = floor(nx / d * 65536), SY likewise, in binary64 -- one IEEE
+// division each --; a pixel with d == 0 or a position beyond 2^47 (a NaN fails the compares) has no tap inside the frame and no
+// fraction: it is the pad.  The conversion to int64 stands behind the range test, so it is defined for every table.
+__device__ __forceinline__ void perspective_taps(const WarpArgs& a, long long nx, long long ny, long long d, WarpTap& tx, WarpTap& ty) {
+    constexpr double kLimit = 140737488355328.0;              // 2^47: ix, iy below 2^31
+    const double den = (double)d;
+    const double px = __builtin_floor((double)nx / den * 65536.0), py = __builtin_floor((double)ny / den * 65536.0);
+    const bool ok = d != 0 && __builtin_fabs(px) < kLimit && __builtin_fabs(py) < kLimit;
+    tx = warp_tap((long long)(ok ? px : 0.0), a.ws);
+    ty = warp_tap((long long)(ok ? py : 0.0), a.hs);
+    if (!ok) {                                                // (index 0: the load that is always legal)
+        tx.in0 = tx.in1 = ty.in0 = ty.in1 = false;
+        tx.i1 = ty.i1 = 0;
+    }
+}
+
+// The grid and the tile of preprocess_warp_kernel.  NX, NY and D advance by Q00, Q10 and Q20 per pixel; there is no WHOLE form.  The
+// device cannot check the table's limit: the forms are computed in unsigned arithmetic, which wraps, so a table beyond it gives other
+// pixels and nothing undefined; every index still passes warp_tap's 64-bit range test.
+template <class Fetch, bool VS>
+__global__ __launch_bounds__(kBlock) void preprocess_perspective_kernel(WarpArgs a) {
+    typedef unsigned long long u64;
+    Tile t;
+    const long long* q = warp_tile_of(a, 10, t);
+    if (q == nullptr) return;
+    const u64 q00 = q[1], q01 = q[2], q02 = q[3], q10 = q[4], q11 = q[5], q12 = q[6], q20 = q[7], q21 = q[8], q22 = q[9];
+    const int r = threadIdx.x / kWarpQuads, j0 = 4 * (threadIdx.x % kWarpQuads);
+    if (r >= t.thv || j0 >= t.twv) return;
+    const u64 x = t.tx0 + j0, y = t.ty0 + r;
+    const u64 nx = q00 * x + q01 * y + q02, ny = q10 * x + q11 * y + q12, d = q20 * x + q21 * y + q22;
+    WarpTap tx[4], ty[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) perspective_taps(a, (long long)(nx + u * q00), (long long)(ny + u * q10), (long long)(d + u * q20), tx[u], ty[u]);
+    const Fetch fetch(a, (int)q[0]);
+    sample_quad<Fetch, VS, false>(a, t, fetch, r, j0, tx, ty);
+}
+
 template <class Fetch>
-void launch_warp(const WarpArgs& a, dim3 grid, bool vs, hipStream_t st) {
+void launch_warp(const WarpArgs& a, dim3 grid, bool vs, bool perspective, hipStream_t st) {
+    if (perspective) {
+        if (vs) hipLaunchKernelGGL((preprocess_perspective_kernel<Fetch, true>), grid, dim3(kBlock), 0, st, a);
+        else    hipLaunchKernelGGL((preprocess_perspective_kernel<Fetch, false>), grid, dim3(kBlock), 0, st, a);
+        return;
+    }
     if (vs) hipLaunchKernelGGL((preprocess_warp_kernel<Fetch, true>), grid, dim3(kBlock), 0, st, a);
     else    hipLaunchKernelGGL((preprocess_warp_kernel<Fetch, false>), grid, dim3(kBlock), 0, st, a);
 }
@@ -1104,9 +1173,10 @@ int launch_packed(const Job& j) {
     }
 }
 
-// The one launcher of preprocess_warp_kernel.  format 0 raw, 1 YUV 4:2:0, 2 frames of 4-byte units, with the `how` and the limits of
-// that format's source above; the pad is j.fit.pad.
-int preprocess_warp_launch(const Job& j, int format) {
+// The one launcher of preprocess_warp_kernel and (`perspective`: j.table has ten columns) of preprocess_perspective_kernel: the same
+// checks, grid and fetch forms.  format 0 raw, 1 YUV 4:2:0, 2 frames of 4-byte units, with the `how` and the limits of that format's
+// source above; the pad is j.fit.pad.
+int preprocess_warp_launch(const Job& j, int format, bool perspective) {
     WarpArgs a;
     int rc = common_args(a, j);
     if (rc != PVHIP_OK) return rc;
@@ -1131,20 +1201,20 @@ int preprocess_warp_launch(const Job& j, int format) {
     const bool a4 = (uintptr_t)j.src % 4 == 0;
     hipStream_t st = state().stream;
     switch (format * 8 + how * 2 + (format == 2 && a4 ? 1 : 0)) {
-        case 0:  launch_warp<RawFetch<false, false>>(a, grid, vs, st); break;
-        case 2:  launch_warp<RawFetch<true, false>>(a, grid, vs, st); break;
-        case 4:  launch_warp<RawFetch<false, true>>(a, grid, vs, st); break;
-        case 6:  launch_warp<RawFetch<true, true>>(a, grid, vs, st); break;
-        case 8:  launch_warp<Yuv420Fetch<false>>(a, grid, vs, st); break;
-        case 10: launch_warp<Yuv420Fetch<true>>(a, grid, vs, st); break;
-        case 16: launch_warp<PackedFetch<0, false>>(a, grid, vs, st); break;
-        case 17: launch_warp<PackedFetch<0, true>>(a, grid, vs, st); break;
-        case 18: launch_warp<PackedFetch<1, false>>(a, grid, vs, st); break;
-        case 19: launch_warp<PackedFetch<1, true>>(a, grid, vs, st); break;
-        case 20: launch_warp<PackedFetch<2, false>>(a, grid, vs, st); break;
-        case 21: launch_warp<PackedFetch<2, true>>(a, grid, vs, st); break;
-        case 22: launch_warp<PackedFetch<3, false>>(a, grid, vs, st); break;
-        default: launch_warp<PackedFetch<3, true>>(a, grid, vs, st); break;
+        case 0:  launch_warp<RawFetch<false, false>>(a, grid, vs, perspective, st); break;
+        case 2:  launch_warp<RawFetch<true, false>>(a, grid, vs, perspective, st); break;
+        case 4:  launch_warp<RawFetch<false, true>>(a, grid, vs, perspective, st); break;
+        case 6:  launch_warp<RawFetch<true, true>>(a, grid, vs, perspective, st); break;
+        case 8:  launch_warp<Yuv420Fetch<false>>(a, grid, vs, perspective, st); break;
+        case 10: launch_warp<Yuv420Fetch<true>>(a, grid, vs, perspective, st); break;
+        case 16: launch_warp<PackedFetch<0, false>>(a, grid, vs, perspective, st); break;
+        case 17: launch_warp<PackedFetch<0, true>>(a, grid, vs, perspective, st); break;
+        case 18: launch_warp<PackedFetch<1, false>>(a, grid, vs, perspective, st); break;
+        case 19: launch_warp<PackedFetch<1, true>>(a, grid, vs, perspective, st); break;
+        case 20: launch_warp<PackedFetch<2, false>>(a, grid, vs, perspective, st); break;
+        case 21: launch_warp<PackedFetch<2, true>>(a, grid, vs, perspective, st); break;
+        case 22: launch_warp<PackedFetch<3, false>>(a, grid, vs, perspective, st); break;
+        default: launch_warp<PackedFetch<3, true>>(a, grid, vs, perspective, st); break;
     }
     PVHIP_LAUNCH_CHECK();
     return PVHIP_OK;
@@ -1179,6 +1249,14 @@ int set_rule(Job& j, int matrix, int full_range) {
     PVHIP_REQUIRE_INIT();
     PVHIP_CHECK_ARG(matrix >= 0 && matrix <= 2 && (full_range == 0 || full_range == 1));
     j.rule = matrix || full_range ? &kYuvRules[matrix][full_range] : nullptr;
+    return PVHIP_OK;
+}
+
+// ... of the warp entries: raw frames and four-byte pixels hold nothing to convert.
+int set_warp_rule(Job& j, int format, int matrix, int full_range) {
+    const int rc = set_rule(j, matrix, full_range);
+    if (rc != PVHIP_OK) return rc;
+    PVHIP_CHECK_ARG((format != 0 && !(format == 2 && j.how >= 2)) || (matrix == 0 && full_range == 0));
     return PVHIP_OK;
 }
 
@@ -1281,7 +1359,7 @@ int pvhip_input_preprocess_warp_f32(const void* src, float* dst, const long long
                                     const float* std_scale, float pad_value) {
     Job j = job_of(src, dst, nullptr, n, m, c, src_h, src_w, dst_h, dst_w, src_h, src_w, how, reverse_channels, mean, std_scale);
     j.table = table; j.fit.pad = pad_value;
-    return preprocess_warp_launch(j, format);
+    return preprocess_warp_launch(j, format, false);
 }
 
 int pvhip_input_preprocess_warp_color_f32(const void* src, float* dst, const long long* table, int n, int m, int c, int src_h, int src_w,
@@ -1289,10 +1367,25 @@ int pvhip_input_preprocess_warp_color_f32(const void* src, float* dst, const lon
                                           const float* std_scale, float pad_value, int matrix, int full_range) {
     Job j = job_of(src, dst, nullptr, n, m, c, src_h, src_w, dst_h, dst_w, src_h, src_w, how, reverse_channels, mean, std_scale);
     j.table = table; j.fit.pad = pad_value;
-    const int rc = set_rule(j, matrix, full_range);
-    if (rc != PVHIP_OK) return rc;
-    PVHIP_CHECK_ARG((format != 0 && !(format == 2 && how >= 2)) || (matrix == 0 && full_range == 0));   // raw frames, four-byte pixels
-    return preprocess_warp_launch(j, format);
+    const int rc = set_warp_rule(j, format, matrix, full_range);
+    return rc != PVHIP_OK ? rc : preprocess_warp_launch(j, format, false);
+}
+
+int pvhip_input_preprocess_perspective_f32(const void* src, float* dst, const long long* table, int n, int m, int c, int src_h, int src_w,
+                                           int dst_h, int dst_w, int format, int how, int reverse_channels, const float* mean,
+                                           const float* std_scale, float pad_value) {
+    Job j = job_of(src, dst, nullptr, n, m, c, src_h, src_w, dst_h, dst_w, src_h, src_w, how, reverse_channels, mean, std_scale);
+    j.table = table; j.fit.pad = pad_value;
+    return preprocess_warp_launch(j, format, true);
+}
+
+int pvhip_input_preprocess_perspective_color_f32(const void* src, float* dst, const long long* table, int n, int m, int c, int src_h,
+                                                 int src_w, int dst_h, int dst_w, int format, int how, int reverse_channels,
+                                                 const float* mean, const float* std_scale, float pad_value, int matrix, int full_range) {
+    Job j = job_of(src, dst, nullptr, n, m, c, src_h, src_w, dst_h, dst_w, src_h, src_w, how, reverse_channels, mean, std_scale);
+    j.table = table; j.fit.pad = pad_value;
+    const int rc = set_warp_rule(j, format, matrix, full_range);
+    return rc != PVHIP_OK ? rc : preprocess_warp_launch(j, format, true);
 }
 
 }  // extern "C"

@@ -180,6 +180,9 @@ SIGNATURES = {
                                                 + [_fp, _fp, _c.c_int, _c.c_float, _c.c_int, _c.c_int]),
     'pvhip_input_preprocess_warp_color_f32': (_c.c_int, [_c.c_void_p, _fp, _c.c_void_p] + [_c.c_int] * 10
                                               + [_fp, _fp, _c.c_float, _c.c_int, _c.c_int]),
+    'pvhip_input_preprocess_perspective_f32': (_c.c_int, [_c.c_void_p, _fp, _c.c_void_p] + [_c.c_int] * 10 + [_fp, _fp, _c.c_float]),
+    'pvhip_input_preprocess_perspective_color_f32': (_c.c_int, [_c.c_void_p, _fp, _c.c_void_p] + [_c.c_int] * 10
+                                                     + [_fp, _fp, _c.c_float, _c.c_int, _c.c_int]),
 }
 
 # entry points whose return value is not a status code

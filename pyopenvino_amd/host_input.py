@@ -7,7 +7,7 @@ import ctypes
 import numpy as np
 
 from . import detections as detections_rule, device
-from .input_format import DetectedRois, DetectedTable, RoiInput, WarpInput
+from .input_format import DetectedRois, DetectedTable, PerspectiveInput, RoiInput, WarpInput
 
 
 class _Staging:
@@ -35,14 +35,17 @@ class _Slot:
     -- a RoiInput's frames under (extent, m) --, and the (n, 5) int32 table of a RoiInput, page-locked and on the device, once one is fed.
     The device table is the head of one block `table` of 6 n + 2 ints, (n, 5) rois | (n,) record_of | (count, selected): what
     pvhip_detections_to_rois writes for a DetectedRois (`detected`: what that needs besides, once one is fed) and detected_rois() reads
-    back in one copy.  `warps_host` / `warps`: the (n, 7) int64 table of a WarpInput, page-locked and on the device, once one is fed."""
-    __slots__ = ('fixed', 'event', 'mean', 'std', 'extents', 'rois_host', 'rois', 'table', 'detected', 'fed', 'warps_host', 'warps')
+    back in one copy.  `warps_host` / `warps`: the (n, 7) int64 table of a WarpInput, page-locked and on the device, once one is fed;
+    `perspectives_host` / `perspectives`: the (n, 10) int64 table of a PerspectiveInput likewise."""
+    __slots__ = ('fixed', 'event', 'mean', 'std', 'extents', 'rois_host', 'rois', 'table', 'detected', 'fed', 'warps_host', 'warps',
+                 'perspectives_host', 'perspectives')
 
     def __init__(self, fmt):
         self.fixed, self.event = device.DeviceTensor.empty(fmt.dims), device.Event(timed=False)
         self.mean, self.std = (None, None) if fmt.mean is None else (device.DeviceTensor.from_numpy(fmt.mean), device.DeviceTensor.from_numpy(fmt.std))
         self.extents = collections.OrderedDict()
         self.rois_host = self.rois = self.table = self.detected = self.warps_host = self.warps = None
+        self.perspectives_host = self.perspectives = None
         self.fed = None                         # the extent of the whole images the last pass was staged from (what a declared fit fitted)
 
     def roi_table(self):
@@ -59,6 +62,13 @@ class _Slot:
             self.warps_host = device.host_empty((n, 7), np.int64)
             self.warps = device.DeviceTensor.empty((n, 7), np.int64)
         return self.warps_host
+
+    def perspective_table(self):
+        if self.perspectives_host is None:
+            n = self.fixed.shape[0]
+            self.perspectives_host = device.host_empty((n, 10), np.int64)
+            self.perspectives = device.DeviceTensor.empty((n, 10), np.int64)
+        return self.perspectives_host
 
 
 class _Detected:
@@ -137,26 +147,38 @@ class HostInputs:
         fmt.warp_declared()
         return self._slot(name).warp_table()
 
+    def perspective_buffer(self, name) -> np.ndarray:
+        """The page-locked (n, 10) int64 table a PerspectiveInput of input `name` is uploaded from."""
+        fmt = self._format(name)
+        fmt.perspective_declared()
+        return self._slot(name).perspective_table()
+
     def _stage_warps(self, name, fmt, warp):
-        """The frames and the table of WarpInput `warp` in this request's page-locked buffers -- copied, unless they are those buffers
-        --, everything checked before anything is allocated: the staging."""
-        fmt.warp_declared()
-        frames = warp.frames if isinstance(warp.frames, np.ndarray) else np.asarray(warp.frames)
-        extent, m = fmt.frames_extent_of(frames, 'WarpInput')
+        """The frames and the table of WarpInput or PerspectiveInput `warp` in this request's page-locked buffers -- copied, unless
+        they are those buffers --, everything checked before anything is allocated: the staging."""
         slot, given = self.slots.get(name), warp.matrices
-        own = (slot is not None and slot.warps_host is not None and isinstance(given, np.ndarray) and given.dtype == np.int64
-               and given.shape == slot.warps_host.shape and given.flags.c_contiguous and given.ctypes.data == slot.warps_host.ctypes.data)
+        if isinstance(warp, PerspectiveInput):
+            declared, checked, checked_table = fmt.perspective_declared, fmt.checked_perspectives, fmt.checked_perspective_table
+            buffer, table_of, host = 'perspective', _Slot.perspective_table, slot.perspectives_host if slot is not None else None
+        else:
+            declared, checked, checked_table = fmt.warp_declared, fmt.checked_warps, fmt.checked_warp_table
+            buffer, table_of, host = 'warp', _Slot.warp_table, slot.warps_host if slot is not None else None
+        declared()
+        frames = warp.frames if isinstance(warp.frames, np.ndarray) else np.asarray(warp.frames)
+        extent, m = fmt.frames_extent_of(frames, type(warp).__name__)
+        own = (host is not None and isinstance(given, np.ndarray) and given.dtype == np.int64
+               and given.shape == host.shape and given.flags.c_contiguous and given.ctypes.data == host.ctypes.data)
         if own:
             if warp.ids is not None:
-                raise ValueError('input {}: the warp_buffer holds the frame of each row in its first column: ids is None with it'.format(name))
-            fmt.checked_warp_table(given, m)
+                raise ValueError('input {}: the {}_buffer holds the frame of each row in its first column: ids is None with it'.format(name, buffer))
+            checked_table(given, m)
         else:
-            table = fmt.checked_warps(given, warp.ids, m)
+            table = checked(given, warp.ids, m)
         staged = self._staging(name, extent, m)
         if not (frames.dtype == staged.host.dtype and frames.flags.c_contiguous and frames.ctypes.data == staged.host.ctypes.data):
             np.copyto(staged.host, frames, casting='same_kind' if staged.host.dtype == np.float32 else 'safe')
         if not own:
-            np.copyto(self.slots[name].warp_table(), table)
+            np.copyto(table_of(self.slots[name]), table)
         return staged
 
     def _stage_rois(self, name, fmt, roi):
@@ -296,7 +318,8 @@ class HostInputs:
         pvhip_input_preprocess_f32 when a resize, channel reversal or mean / scale is in effect, else pvhip_input_to_nchw_f32;
         `largest` = (max_h, max_w) of a RoiInput's table: the _roi_f32 forms.  A declared fit: the _fit_f32 forms of the three, with
         the table or NULL.  `warped`: the frames of a WarpInput: pvhip_input_preprocess_warp_f32 for every format, whatever fit is
-        declared.  A format whose colour rule is not BT.601 limited range (``InputFormat.default_rule``) takes the _color_f32 form of
+        declared; `warped` = 'perspective': those of a PerspectiveInput, pvhip_input_preprocess_perspective_f32 with the same arguments
+        and the (n, 10) table.  A format whose colour rule is not BT.601 limited range (``InputFormat.default_rule``) takes the _color_f32 form of
         its launch, whichever of these it is, with the rule behind the same arguments; every other format exactly the entries above."""
         fixed = slot.fixed
         src, dst = device.ptr(staged.staging), device.ptr(fixed)
@@ -305,8 +328,10 @@ class HostInputs:
         pre = (int(fmt.reverse), device.ptr(slot.mean), device.ptr(slot.std))
         if warped:
             form = (1, how[0]) if fmt.yuv else (2, how[0]) if fmt.packed else (0, how[0] | how[1] << 1)
-            entry, rule = ('pvhip_input_preprocess_warp_f32', ()) if fmt.default_rule else ('pvhip_input_preprocess_warp_color_f32', fmt.color_rule)
-            device.call(entry, src, dst, device.ptr(slot.warps), n, staged.frames, c, *staged.extent, *dst_hw, *form, *pre, fmt.pad, *rule)
+            family, table = ('perspective', slot.perspectives) if warped == 'perspective' else ('warp', slot.warps)
+            entry, rule = (family + '_f32', ()) if fmt.default_rule else (family + '_color_f32', fmt.color_rule)
+            device.call('pvhip_input_preprocess_' + entry, src, dst, device.ptr(table), n, staged.frames, c, *staged.extent, *dst_hw, *form,
+                        *pre, fmt.pad, *rule)
         elif not fmt.default_rule:
             # (load_network admits another rule for YUV formats only) one entry per family: the table or NULL, the fit or 0
             roi = largest is not None
@@ -344,7 +369,7 @@ class HostInputs:
         """`inputs` with every host input of a declared format, or in one of this request's own buffers, replaced by the request's fixed
         tensor: the caller's array is copied into the page-locked buffer of its extent unless it IS that buffer, the buffer is uploaded on
         the copy stream, stream `stream_base` waits for the copy's event and converts (_convert: one launch at the most).  A RoiInput's
-        frames and table go the same way, both uploaded on the copy stream behind the one event, and so do a WarpInput's.  A DetectedRois' frames too -- with its
+        frames and table go the same way, both uploaded on the copy stream behind the one event, and so do a WarpInput's and a PerspectiveInput's.  A DetectedRois' frames too -- with its
         labels, and its records when they are a host array --; its table is made by pvhip_detections_to_rois on `stream_base`, behind the
         detector's pass when the records are the Result of a request in flight, and the ROI launch is sized for whole frames: the host
         never sees the table (`sharded`: the batch is sharded over ranks, which a DetectedRois refuses).
@@ -353,10 +378,11 @@ class HostInputs:
         out = dict(inputs)
         for name, arr in inputs.items():
             fmt, largest, uploads, make_table = self.formats.get(name), None, (), None
-            warped = isinstance(arr, WarpInput)
+            warped = 'perspective' if isinstance(arr, PerspectiveInput) else isinstance(arr, WarpInput)
             if warped:
                 staged = self._stage_warps(name, self._format(name), arr)
-                uploads = ((self.slots[name].warps, self.slots[name].warps_host),)
+                slot = self.slots[name]
+                uploads = ((slot.perspectives, slot.perspectives_host) if warped == 'perspective' else (slot.warps, slot.warps_host),)
             elif isinstance(arr, RoiInput):
                 staged, largest = self._stage_rois(name, self._format(name), arr)
                 uploads = ((self.slots[name].rois, self.slots[name].rois_host),)

@@ -408,6 +408,13 @@ class InferRequest:
         starts; ownership as for ``input_buffer``."""
         return self.runner.host_inputs.warp_buffer(name)
 
+    def perspective_buffer(self, name: str) -> np.ndarray:
+        """The page-locked (n, 10) int64 table this request uploads the matrices of a ``PerspectiveInput`` of input `name` from, row b =
+        (id, Q00, Q01, Q02, Q10, Q11, Q12, Q20, Q21, Q22), each matrix scaled by a power of two of its own
+        (``PerspectiveInput.fixed``).  ``PerspectiveInput(input_buffer(name, (h, w), frames=m), perspective_buffer(name))`` costs no host
+        copy; its values are checked by the limit of ``PerspectiveInput.fixed`` when the pass starts; ownership as for ``input_buffer``."""
+        return self.runner.host_inputs.perspective_buffer(name)
+
     def detected_rois(self, name: str):
         """After ``wait()`` of a pass whose input `name` was a ``DetectedRois``: the record (count, selected, rois, records) -- `rois` the
         (n, 5) int32 table that pass used, rows >= count being (-1, 0, 0, 0, 0); `records[k]` the flat row of the detections batch row

@@ -43,7 +43,7 @@ class InputFormat:
     (n, 3 h / 2, w), or 'YUY2' / 'UYVY' for packed YUV 4:2:2 frames, uint8 of shape (n, h, w, 2), or 'BGRX' / 'RGBX' for four-byte
     pixels, uint8 of shape (n, h, w, 4), whatever ``u8`` / ``nhwc`` say; ``standard`` / ``full_range`` the declared matrix ('BT601', 'BT709',
     'BT2020') and range of a YUV format's frames, which ``color_rule`` hands every launch that converts them -- a plain pass, a RoiInput, a
-    DetectedRois, a WarpInput and a fitted input alike: the rule belongs to the format, not to the feed.  An extent is the (h, w) of a caller's image.  A RoiInput's frames have the same
+    DetectedRois, a WarpInput, a PerspectiveInput and a fitted input alike: the rule belongs to the format, not to the feed.  An extent is the (h, w) of a caller's image.  A RoiInput's frames have the same
     shapes with their own count m in place of n (``host_shape(extent, frames=m)``, ``frames_extent_of``) and a table ``checked_rois``
     accepts."""
     name: str
@@ -192,11 +192,11 @@ class InputFormat:
         return int(frames)
 
     def frames_extent_of(self, a, what='RoiInput'):
-        """((h, w), m) of the frames array `a` of a RoiInput (`what`: of a WarpInput), checked against this format."""
+        """((h, w), m) of the frames array `a` of a RoiInput (`what`: of a WarpInput or a PerspectiveInput), checked against this format."""
         if what == 'RoiInput':
             self._roi_declared()
         else:
-            self.warp_declared()
+            self._roi_declared(what + ' is sampled')
         if self.yuv:
             ok = a.ndim == 3 and a.shape[0] >= 1 and a.shape[1] % 3 == 0
             declared, any_hw = 'declared {}'.format(self.color), 'any even h, w'
@@ -285,6 +285,38 @@ class InputFormat:
         if bad.any():
             b = int(np.argmax(bad))
             raise ValueError('input {}: {}'.format(self.name, WarpInput.limit_text(b, table[b, 1:])))
+        self._checked_warp_ids(table[:, 0], frames)
+        return table
+
+    def perspective_declared(self):
+        self._roi_declared('PerspectiveInput is sampled')
+
+    def checked_perspectives(self, matrices, ids, frames):
+        """The table of a PerspectiveInput over `frames` frames as a C-contiguous int64 (n, 10) array, row b = (id, Q00, Q01, Q02, Q10,
+        Q11, Q12, Q20, Q21, Q22): ``PerspectiveInput.fixed(matrices, the network's extent)`` behind the frame of each row (`ids`, or
+        its default)."""
+        self.perspective_declared()
+        n = self.dims[0]
+        try:
+            q = PerspectiveInput.fixed(matrices, self.dims[2:])
+        except ValueError as e:
+            raise ValueError('input {}: {}'.format(self.name, e)) from None
+        if q.shape[0] != n:
+            raise ValueError('input {}: matrices has shape {} -- one 3 x 3 matrix per batch row --, got {}'.format(
+                self.name, (n, 3, 3), np.shape(matrices)))
+        table = np.empty((n, 10), np.int64)
+        table[:, 0] = self._checked_warp_ids(ids, frames)
+        table[:, 1:] = q
+        return table
+
+    def checked_perspective_table(self, table, frames):
+        """`table`, an int64 (n, 10) array already in the device's form (``InferRequest.perspective_buffer``), checked by the limit of
+        ``PerspectiveInput.fixed`` over the network's extent and ``ids``; returned as it is."""
+        self.perspective_declared()
+        bad = PerspectiveInput.beyond_limits(table[:, 1:], self.dims[2:])
+        if bad.any():
+            b = int(np.argmax(bad))
+            raise ValueError('input {}: {}'.format(self.name, PerspectiveInput.limit_text(b, table[b, 1:], self.dims[2:])))
         self._checked_warp_ids(table[:, 0], frames)
         return table
 
@@ -379,6 +411,79 @@ class WarpInput:
         if bad.any():
             b = int(np.argmax(bad))
             raise ValueError(cls.limit_text(b, q[b]))
+        return q.astype(np.int64)
+
+
+class PerspectiveInput:
+    """A network input given as homographies of frames (a plate seen from the kerb, a document on a desk, a sign or a screen seen at an
+    angle, a road or court plane rectified to a bird's-eye view: four corners in the frame, not a rotated rectangle):
+    ``infer({name: PerspectiveInput(frames, matrices, ids)})``, wherever a WarpInput is accepted.  `frames` and `ids`: exactly as for
+    WarpInput.  `matrices`: real numbers of shape (n, 3, 3); row b maps an OUTPUT pixel index (x, y) of the network's extent to a SOURCE
+    position in frame pixels, sx = (h00 x + h01 y + h02) / (h20 x + h21 y + h22), sy = (h10 x + h11 y + h12) / (the same denominator),
+    pixel centres at the integers: the matrix ``cv2.warpPerspective(..., flags=INTER_LINEAR | WARP_INVERSE_MAP)`` takes
+    (pyopenvino_amd.perspective has helpers: ``from_quad`` of four frame points, ``from_affine``, ``invert`` of a forward matrix,
+    ``apply``).  The device samples every row bilinearly in one launch (pvhip_input_preprocess_perspective_f32; the rule in numpy:
+    tests/perspective_ref.py): each matrix is scaled by a power of two of its own and rounded to integers on the host
+    (``PerspectiveInput.fixed``: the ratio does not see the scale), the three linear forms are exact 64-bit integers below 2^52, the
+    position in Q16 is floor(N / D * 65536) with ONE correctly rounded binary64 division per axis, and from there on the rule is
+    WarpInput's word for word: a tap outside the frame has the value ``preprocess_info.pad_value``, a zero fraction reads no second
+    tap, colour frames are converted per tap, then reversal and mean / scale as declared.  A pixel whose denominator is 0 (the
+    horizon of the map) or whose position is beyond 2^31 pixels is the pad; a negative denominator is a legal one: -H is the same map
+    as H.  No antialiasing.  The input needs ``preprocess_info.resize_algorithm = 'RESIZE_BILINEAR'``; a declared ``resize_fit`` plays
+    no part, and ``infer(..., detections=)`` refuses a PerspectiveInput wherever it refuses a WarpInput.  With `frames` =
+    ``InferRequest.input_buffer(name, (h, w), frames=m)`` and `matrices` = ``InferRequest.perspective_buffer(name)`` -- the (n, 10)
+    int64 table (id, Q00, Q01, Q02, Q10, Q11, Q12, Q20, Q21, Q22) itself, `ids` None -- nothing is copied on the host."""
+    __slots__ = ('frames', 'matrices', 'ids')
+    FORM_LIMIT = 1 << 52             # |Q_r0| (wd - 1) + |Q_r1| (hd - 1) + |Q_r2| at most, for each row r of a matrix
+
+    def __init__(self, frames, matrices, ids=None):
+        self.frames, self.matrices, self.ids = frames, matrices, ids
+
+    def __repr__(self):
+        return 'PerspectiveInput(frames={}, matrices={})'.format(getattr(self.frames, 'shape', None), getattr(self.matrices, 'shape', None))
+
+    @classmethod
+    def beyond_limits(cls, q, dst_hw):
+        """Which rows of (n, 9) integer coefficients (Q00 .. Q22) break the limit over an extent `dst_hw` = (hd, wd): a bound on one of
+        the three linear forms above 2^52.  Python ints: no int64 of a table overflows here."""
+        hd, wd = (int(v) for v in dst_hw)
+        bad = np.zeros(len(q), bool)
+        for b, row in enumerate(np.asarray(q).reshape(-1, 9).tolist()):
+            bad[b] = any(abs(row[r]) * (wd - 1) + abs(row[r + 1]) * (hd - 1) + abs(row[r + 2]) > cls.FORM_LIMIT for r in (0, 3, 6))
+        return bad
+
+    @staticmethod
+    def limit_text(b, row, dst_hw):
+        return ('matrices[{}] is beyond the limit of a perspective table -- |Q_r0| (w - 1) + |Q_r1| (h - 1) + |Q_r2| <= 2^52 for each of '
+                'its three rows r over the extent {} --: {}'.format(b, tuple(int(v) for v in dst_hw), [int(v) for v in row]))
+
+    @classmethod
+    def fixed(cls, matrices, dst_hw) -> np.ndarray:
+        """(n, 9) int64: the coefficients (h00 .. h22) of every row as the device takes them over an extent `dst_hw` = (hd, wd), each
+        matrix scaled by one power of two of its own: with B_r = |h_r0| (wd - 1) + |h_r1| (hd - 1) + |h_r2| for its three rows and
+        B = max B_r in [2^(e-1), 2^e), Q = ``np.rint(np.float64(h) * 2^(51 - e))`` (ties to even).  Each of the three linear forms then
+        stays below 2^52 in magnitude over the whole extent -- exact as int64 and as binary64 --, and the scale cancels in the ratio, so
+        it is not stored.  ValueError, naming the row, for a matrix with a value that is not finite or with B == 0.  Host arithmetic
+        only: no device is needed."""
+        t = np.asarray(matrices)
+        if t.ndim != 3 or t.shape[1:] != (3, 3):
+            raise ValueError('matrices has shape (n, 3, 3) -- one 3 x 3 matrix per batch row --, got {}'.format(t.shape))
+        if t.dtype.kind not in 'fiu':
+            raise ValueError('matrices holds real numbers, got dtype {}'.format(t.dtype))
+        hd, wd = (int(v) for v in dst_hw)
+        if hd < 1 or wd < 1:
+            raise ValueError('the extent {} is empty'.format((hd, wd)))
+        h = t.astype(np.float64)
+        with np.errstate(invalid='ignore', over='ignore'):
+            bound = (np.abs(h) * np.array([wd - 1, hd - 1, 1], np.float64)).sum(2).max(1)
+        bad = ~np.isfinite(bound) | (bound == 0) | ~np.isfinite(h).all((1, 2))
+        if bad.any():
+            b = int(np.argmax(bad))
+            raise ValueError('matrices[{}] is no homography over the extent {} -- every value finite, and the largest of its three bounds '
+                             '|h_r0| (w - 1) + |h_r1| (h - 1) + |h_r2| neither zero nor beyond binary64 --: {}'.format(
+                                 b, (hd, wd), h[b].tolist()))
+        e = np.frexp(bound)[1]
+        q = np.rint(np.ldexp(h, (51 - e)[:, None, None])).reshape(-1, 9)
         return q.astype(np.int64)
 
 
@@ -698,8 +803,9 @@ class PreProcessInfo:
     @property
     def pad_value(self):
         """One finite fp32 number in source units (default 0) that goes through mean / scale like a pixel: what a declared
-        ``resize_fit`` fills the extent outside the fitted rectangle with, and the value, in every channel, of a tap of a ``WarpInput``
-        outside its frame (there with or without a declared fit)."""
+        ``resize_fit`` fills the extent outside the fitted rectangle with, and the value, in every channel, of a tap of a ``WarpInput`` or a
+        ``PerspectiveInput`` outside its frame, and of a pixel a ``PerspectiveInput`` has no position for (there with or without a
+        declared fit)."""
         return self._pad
 
     @pad_value.setter
