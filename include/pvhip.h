@@ -840,6 +840,35 @@ int         pvhip_input_preprocess_perspective_color_f32(const void* src, float*
                                                          int src_h, int src_w, int dst_h, int dst_w, int format, int how,
                                                          int reverse_channels, const float* mean, const float* std_scale,
                                                          float pad_value, int matrix, int full_range);
+/* Addition to ABI v18 (the version number is unchanged: nothing existing changed): the table of the warp entry above made on the device
+ * from a landmark network's points, so that a cascade aligns its crops without reading them on the host.  Row b of the n x 7 int64
+ * `table` becomes the least-squares similarity, without reflection, from the K points of a template onto the K landmarks of row b -- which
+ * is directly the inverse map a warp takes: an output pixel at a template point reads the frame at the landmark.
+ * All of it is binary64, every operation rounded once, in the order written, nothing contracted.
+ *   `tmpl`, 2 K + 3 doubles the host makes once of the template's points (t_ix, t_iy), output pixel indices with centres at the integers:
+ *     tbx = (t_0x + t_1x + ...) / K in index order, tby likewise;  cx_i = t_ix - tbx,  cy_i = t_iy - tby;
+ *     S = sum over i of (cx_i cx_i + cy_i cy_i), each term formed first and then added in index order, starting from term 0;
+ *     every value finite, |t| <= 2^24 and S != 0;  laid out as (tbx, tby, S, cx_0, cy_0, cx_1, cy_1, ...).
+ *   `points`, fp32 (rows, 2 K) as x0, y0, x1, y1, ..., normalised to the row's region on pixel-edge coordinates: 0 is the region's left
+ *     or top edge, 1 its right or bottom edge.  `regions`: int32 (rows, 5), row b = (id, x, y, w, h) as the _roi_ entries take it; NULL:
+ *     row b's region is the whole frame, (m == 1 ? 0 : b, 0, 0, src_w, src_h).
+ *   Row b is void when b >= rows, id is outside [0, m), w or h is outside [1, 2^24], or one of its 2 K values is not finite.  Else
+ *     px_i = (double(x) + double(u_i) double(w)) - 0.5,  py_i likewise with y and h          (frame pixels, centres at the integers)
+ *     mx = (px_0 + px_1 + ...) / K,  my likewise;   dx_i = px_i - mx,  dy_i = py_i - my
+ *     A = sum of (cx_i dx_i + cy_i dy_i),  B = sum of (cx_i dy_i - cy_i dx_i), each term formed first and then added, in index order
+ *     a = A / S,  b = B / S;   c0 = mx - (a tbx - b tby),  c1 = my - (b tbx + a tby)
+ *     the matrix is [[a, -b, c0], [b, a, c1]] and its Q16 coefficients rint(v 65536), ties to even, A01 = rint(-b 65536).
+ *   The row is void as well when one of the six is not finite, when one breaks the limits of the warp entry (|A| <= 2^26, |C| <= 2^40), or
+ *   when A00 == 0 and A10 == 0 (every point in one place).  A valid row is (id, A00, A01, C0, A10, A11, C1), a void one
+ *   (-1, 0, 0, 0, 0, 0, 0) -- which the warp entry writes as quiet NaN, reading nothing for it.  valid[b] = 1 or 0 for b < n, and
+ *   valid[n] = the number of valid rows (a second launch of one wave: nothing is added atomically).
+ * The fit minimises sum |M t_i - p_i|^2 over the landmarks' space; cv2.estimateAffinePartial2D of landmarks -> template, inverted,
+ * minimises in the template's space: the two agree where the fit is exact.  In Python floats: pyopenvino_amd/landmarks.py; in numpy:
+ * tests/landmark_warps_ref.py; matched bit for bit.  One thread per row, 64 per workgroup, on the current stream, no allocation.
+ * No NULL pointer but `regions`, n, rows, m >= 1, K in [2, 32], src_h, src_w in [1, 2^24], points / regions / valid 4-byte and tmpl /
+ * table 8-byte aligned; else PVHIP_EINVAL and nothing is launched. */
+int         pvhip_landmarks_to_warps(const float* points, const int* regions, const double* tmpl, long long* table, int* valid, int n,
+                                     int rows, int k, int m, int src_h, int src_w);
 
 #ifdef __cplusplus
 }

@@ -7,7 +7,8 @@ import ctypes
 import numpy as np
 
 from . import detections as detections_rule, device
-from .input_format import DetectedRois, DetectedTable, PerspectiveInput, RoiInput, WarpInput
+from . import landmarks as landmark_rule
+from .input_format import DetectedRois, DetectedTable, LandmarkTable, LandmarkWarps, PerspectiveInput, RoiInput, WarpInput
 
 
 class _Staging:
@@ -36,16 +37,23 @@ class _Slot:
     The device table is the head of one block `table` of 6 n + 2 ints, (n, 5) rois | (n,) record_of | (count, selected): what
     pvhip_detections_to_rois writes for a DetectedRois (`detected`: what that needs besides, once one is fed) and detected_rois() reads
     back in one copy.  `warps_host` / `warps`: the (n, 7) int64 table of a WarpInput, page-locked and on the device, once one is fed;
-    `perspectives_host` / `perspectives`: the (n, 10) int64 table of a PerspectiveInput likewise."""
+    `perspectives_host` / `perspectives`: the (n, 10) int64 table of a PerspectiveInput likewise.  The device warp table is the head of
+    one block `warp_block` of 56 n + 4 (n + 1) bytes, (n, 7) int64 | (n,) valid | count: what pvhip_landmarks_to_warps writes for a
+    LandmarkWarps (`landmarks`: what that needs besides, once one is fed) and landmark_warps() reads back in one copy.  `last`: what the
+    input was last fed -- 'table' (a RoiInput or a DetectedRois: `rois` holds that pass's regions), 'images' (whole images), 'warp' (a
+    WarpInput, a PerspectiveInput or a LandmarkWarps: no rectangle per row) or None (anything else): what a LandmarkWarps over this
+    network's Result normalises its points to.  `table_readers`: events behind the launches of OTHER requests that read `rois` on the
+    device (a LandmarkWarps fed from this request); stage() waits for them before anything overwrites the table."""
     __slots__ = ('fixed', 'event', 'mean', 'std', 'extents', 'rois_host', 'rois', 'table', 'detected', 'fed', 'warps_host', 'warps',
-                 'perspectives_host', 'perspectives')
+                 'perspectives_host', 'perspectives', 'warp_block', 'landmarks', 'last', 'table_readers')
 
     def __init__(self, fmt):
         self.fixed, self.event = device.DeviceTensor.empty(fmt.dims), device.Event(timed=False)
         self.mean, self.std = (None, None) if fmt.mean is None else (device.DeviceTensor.from_numpy(fmt.mean), device.DeviceTensor.from_numpy(fmt.std))
         self.extents = collections.OrderedDict()
         self.rois_host = self.rois = self.table = self.detected = self.warps_host = self.warps = None
-        self.perspectives_host = self.perspectives = None
+        self.perspectives_host = self.perspectives = self.warp_block = self.landmarks = None
+        self.last, self.table_readers = None, []
         self.fed = None                         # the extent of the whole images the last pass was staged from (what a declared fit fitted)
 
     def roi_table(self):
@@ -60,7 +68,8 @@ class _Slot:
         if self.warps_host is None:
             n = self.fixed.shape[0]
             self.warps_host = device.host_empty((n, 7), np.int64)
-            self.warps = device.DeviceTensor.empty((n, 7), np.int64)
+            self.warp_block = device.DeviceTensor.empty((56 * n + 4 * (n + 1),), np.uint8)
+            self.warps = device.DeviceTensor(self.warp_block._block, (n, 7), np.int64)
         return self.warps_host
 
     def perspective_table(self):
@@ -89,6 +98,34 @@ class _Detected:
             self.records_host = device.host_empty((rows, 7), np.float32)
             self.records = device.DeviceTensor.empty((rows, 7), np.float32)
         return self.records_host
+
+
+class _Landmarks:
+    """What a slot keeps for LandmarkWarps inputs: the packed template, page-locked and on the device, and the bytes of the one uploaded
+    last (`packed`: a template is uploaded once); the points and the regions of host arrays, page-locked and on the device, for the row
+    count last fed; the event recorded behind the launch that reads a landmark request's Result and region table (that request's next
+    pass waits for it); `source` / `regions_source`: the device tensors the last launch read, kept alive until the next pass of this
+    input; `live`: the last pass of the input was a LandmarkWarps."""
+    __slots__ = ('template_host', 'template', 'packed', 'points_host', 'points', 'regions_host', 'regions', 'read', 'source',
+                 'regions_source', 'live')
+
+    def __init__(self):
+        self.template_host = device.host_empty((2 * landmark_rule.MAX_POINTS + 3,), np.float64)
+        self.template = device.DeviceTensor.empty(self.template_host.shape, np.float64)
+        self.packed = self.points_host = self.points = self.regions_host = self.regions = self.source = self.regions_source = None
+        self.read, self.live = device.Event(timed=False), False
+
+    def points_for(self, rows, values):
+        if self.points_host is None or self.points_host.shape != (rows, values):
+            self.points_host = device.host_empty((rows, values), np.float32)
+            self.points = device.DeviceTensor.empty((rows, values), np.float32)
+        return self.points_host
+
+    def regions_for(self, rows):
+        if self.regions_host is None or self.regions_host.shape[0] != rows:
+            self.regions_host = device.host_empty((rows, 5), np.int32)
+            self.regions = device.DeviceTensor.empty((rows, 5), np.int32)
+        return self.regions_host
 
 
 class HostInputs:
@@ -295,6 +332,118 @@ class HostInputs:
         device.select_stream(0)
         return DetectedTable(int(t[6 * n]), int(t[6 * n + 1]), t[:5 * n].reshape(n, 5).copy(), t[5 * n:6 * n].copy())
 
+    @staticmethod
+    def _landmarks_of(name, lw):
+        """What LandmarkWarps `lw` reads, nothing waited for and nothing copied: (points -- a DeviceTensor or a host array --, the runner
+        whose pass produces them and the event behind that pass, or (None, None), the _Slot whose `rois` that pass was fed or None: the
+        whole frame)."""
+        src = lw.landmarks
+        if not (hasattr(src, 'runner') and hasattr(src, 'start_async')):         # (an InferRequest: inference_engine imports this module)
+            return (src if isinstance(src, device.DeviceTensor) else np.asarray(src)), None, None, None
+        runner = src.runner
+        net = runner.ienet
+        results = net.find_node_by_type('Result')
+        if lw.output is not None:
+            results = [r for r in results if r[1] == lw.output]
+            if not results:
+                raise ValueError('input {}: the landmark network has no Result named {!r}'.format(name, lw.output))
+        elif len(results) != 1:
+            raise ValueError('input {}: the landmark network has {} Results: output= names the one that holds the points'.format(name, len(results)))
+        nid = results[0][0]
+        fed = runner.host_inputs
+        names = [k for k, f in fed.formats.items() if len(f.dims) == 4]
+        owner = fed.slots.get(names[0]) if len(names) == 1 else None
+        if len(names) == 1 and fed.formats[names[0]].fitted:
+            raise ValueError('input {}: input {!r} of the landmark network declares resize_fit {}: its points are normalised to a fitted '
+                             'rectangle, not to the region'.format(name, names[0], fed.formats[names[0]].fit))
+        if owner is not None and owner.last == 'warp':
+            raise ValueError('input {}: input {!r} of the landmark network was last fed a WarpInput, a PerspectiveInput or a LandmarkWarps: '
+                             'its rows have no rectangle the points are normalised to'.format(name, names[0]))
+        replayed, pending = (src._replayed, runner._pending) if src._in_flight else (None, None)
+        value = replayed['results'][results[0][1]] if replayed is not None else net.G.nodes[nid].get('result')
+        if value is None:
+            raise RuntimeError('input {}: the landmark request never ran: start_async() or infer() it first'.format(name))
+        owner = owner if owner is not None and owner.last == 'table' else None
+        if not isinstance(value, device.DeviceTensor):        # waited for: its host Results, like an array
+            return np.asarray(value), runner, None, owner
+        return value, runner, (pending[1] if pending is not None else None), owner
+
+    def _stage_landmarks(self, name, fmt, lw, sharded):
+        """The frames of LandmarkWarps `lw` in this request's page-locked buffers, its template, and its points and regions when they are
+        host arrays, everything checked before anything is allocated: (staging, [(device tensor, page-locked array)] to upload beside the
+        frames, launch), launch() being what `stage` issues on the base stream in front of the warp launch."""
+        if sharded:
+            raise NotImplementedError('input {}: LandmarkWarps with a batch sharded over ranks'.format(name))
+        fmt.warp_declared()
+        frames = lw.frames if isinstance(lw.frames, np.ndarray) else np.asarray(lw.frames)
+        extent, m = fmt.frames_extent_of(frames, 'LandmarkWarps')
+        packed = lw.checked_template(name)
+        k = (len(packed) - 3) // 2
+        points, runner, done, owner = self._landmarks_of(name, lw)
+        rows = lw.checked_points(name, points.shape, points.dtype, k)
+        regions = lw.checked_regions(name, rows)
+        if regions is not None:
+            owner = None
+        elif owner is not None and owner.rois.shape[0] != rows:
+            raise ValueError('input {}: the landmark pass was fed a table of {} regions, its Result holds {} rows of points: regions names '
+                             'the rectangle of each row'.format(name, owner.rois.shape[0], rows))
+        elif owner is None and m != 1 and m != rows:
+            raise ValueError('input {}: landmarks over whole frames read frame b for row b (m == N) or frame 0 (m == 1); with {} frames for {} '
+                             'rows of points, regions names the frame and the rectangle of each row'.format(name, m, rows))
+        staged = self._staging(name, extent, m)
+        if not (frames.dtype == staged.host.dtype and frames.flags.c_contiguous and frames.ctypes.data == staged.host.ctypes.data):
+            np.copyto(staged.host, frames, casting='same_kind' if staged.host.dtype == np.float32 else 'safe')
+        slot = self.slots[name]
+        slot.warp_table()
+        if slot.landmarks is None:
+            slot.landmarks = _Landmarks()
+        lm = slot.landmarks
+        uploads = []
+        if lm.packed != packed.tobytes():                      # a template is uploaded once
+            lm.template_host[:len(packed)] = packed
+            lm.packed = packed.tobytes()
+            uploads.append((lm.template, lm.template_host))
+        if isinstance(points, device.DeviceTensor):
+            lm.source = points
+        else:
+            np.copyto(lm.points_for(rows, 2 * k), points.reshape(rows, 2 * k))
+            lm.source = lm.points
+            uploads.append((lm.points, lm.points_host))
+        if regions is not None:
+            np.copyto(lm.regions_for(rows), regions)
+            lm.regions_source = lm.regions
+            uploads.append((lm.regions, lm.regions_host))
+        else:
+            lm.regions_source = owner.rois if owner is not None else None       # NULL: the whole frame
+        n = slot.fixed.shape[0]
+
+        def launch():
+            if done is not None:
+                done.wait()                                   # the landmark pass, on the device
+            device.call('pvhip_landmarks_to_warps', device.ptr(lm.source), device.ptr(lm.regions_source), device.ptr(lm.template),
+                        device.ptr(slot.warps), ctypes.c_void_p(slot.warp_block.ptr + 56 * n), n, rows, k, m, *extent)
+            if (runner is not None and isinstance(points, device.DeviceTensor)) or owner is not None:
+                read = lm.read.record()
+                if runner is not None and isinstance(points, device.DeviceTensor):
+                    runner._result_readers.append(read)       # its next pass may overwrite that Result: not before this launch has read it
+                if owner is not None and read not in owner.table_readers:       # (one event per consumer slot, recorded again each pass)
+                    owner.table_readers.append(read)          # nor may its next stage() overwrite that table
+
+        return staged, uploads, launch
+
+    def landmark_warps(self, name, stream_base) -> LandmarkTable:
+        """The table the last pass of input `name` used, read back in one copy on stream `stream_base`, which has drained."""
+        self._format(name)
+        slot = self.slots.get(name)
+        if slot is None or slot.landmarks is None or not slot.landmarks.live:
+            raise RuntimeError('input {}: its last pass was not fed a LandmarkWarps'.format(name))
+        n = slot.fixed.shape[0]
+        device.select_stream(stream_base)
+        raw = np.asarray(slot.warp_block)
+        device.select_stream(0)
+        valid = raw[56 * n:].view(np.int32)
+        return LandmarkTable(int(valid[n]), valid[:n] != 0, raw[:56 * n].view(np.int64).reshape(n, 7).copy())
+
     def _find_or_copy(self, name, fmt, arr):
         """The staging host array `arr` is fed through: the one whose page-locked buffer `arr` is, else -- for a declared format -- the
         one of its extent with `arr` copied into it; None: the input goes the default way."""
@@ -372,12 +521,16 @@ class HostInputs:
         frames and table go the same way, both uploaded on the copy stream behind the one event, and so do a WarpInput's and a PerspectiveInput's.  A DetectedRois' frames too -- with its
         labels, and its records when they are a host array --; its table is made by pvhip_detections_to_rois on `stream_base`, behind the
         detector's pass when the records are the Result of a request in flight, and the ROI launch is sized for whole frames: the host
-        never sees the table (`sharded`: the batch is sharded over ranks, which a DetectedRois refuses).
+        never sees the table (`sharded`: the batch is sharded over ranks, which a DetectedRois refuses).  A LandmarkWarps' frames likewise
+        -- with its template, once, and its points and regions when they are host arrays --; its table is fitted by
+        pvhip_landmarks_to_warps on `stream_base`, behind the landmark pass when the points are the Result of a request in flight, and the
+        warp launch reads it unchanged.  That launch may read ANOTHER request's region table: it leaves an event in that slot's
+        `table_readers`, and the copy stream and `stream_base` wait for those before this call uploads or makes a table for the slot.
         Every other input is returned unchanged (and goes the default way).  All but the MAX_SOURCE_EXTENTS most recently fed extents
         of an input are released here: the request has no pass in flight, so nothing reads those buffers any more."""
         out = dict(inputs)
         for name, arr in inputs.items():
-            fmt, largest, uploads, make_table = self.formats.get(name), None, (), None
+            fmt, largest, uploads, make_table, make_warps = self.formats.get(name), None, (), None, None
             warped = 'perspective' if isinstance(arr, PerspectiveInput) else isinstance(arr, WarpInput)
             if warped:
                 staged = self._stage_warps(name, self._format(name), arr)
@@ -389,16 +542,28 @@ class HostInputs:
             elif isinstance(arr, DetectedRois):
                 staged, uploads, make_table = self._stage_detected(name, self._format(name), arr, sharded)
                 largest = staged.extent                       # the host does not know the largest rectangle: the frame bounds it
+            elif isinstance(arr, LandmarkWarps):
+                staged, uploads, make_warps = self._stage_landmarks(name, self._format(name), arr, sharded)
+                warped = True
             elif fmt is None or isinstance(arr, (device.DeviceTensor, device.ChannelSlice, device.BlockedHalf)):
                 if name in self.slots:
-                    self.slots[name].fed = None
+                    self.slots[name].fed = self.slots[name].last = None
                 continue
             else:
                 staged = self._find_or_copy(name, fmt, arr)
                 if staged is None:
+                    if name in self.slots:
+                        self.slots[name].last = None
                     continue
             slot = self.slots[name]
             slot.fed = staged.extent if largest is None and not warped else None
+            slot.last = 'warp' if warped else 'table' if largest is not None else 'images'
+            if slot.table_readers:                            # launches of other requests still read `rois`: nothing overwrites it before them
+                readers, slot.table_readers = slot.table_readers, []
+                for stream in (device.COPY_STREAM, stream_base):
+                    device.select_stream(stream)
+                    for event in readers:
+                        event.wait()
             slot.extents.move_to_end(staged.key)
             while len(slot.extents) > self.MAX_SOURCE_EXTENTS:
                 slot.extents.popitem(last=False)
@@ -413,8 +578,14 @@ class HostInputs:
                 slot.detected.live = make_table is not None
                 if make_table is None:
                     slot.detected.source = None
+            if slot.landmarks is not None:
+                slot.landmarks.live = make_warps is not None
+                if make_warps is None:
+                    slot.landmarks.source = slot.landmarks.regions_source = None
             if make_table is not None:
                 make_table()
+            if make_warps is not None:
+                make_warps()
             self._convert(fmt, slot, staged, largest, warped)
             device.select_stream(0)
             out[name] = slot.fixed

@@ -425,6 +425,16 @@ class InferRequest:
             raise RuntimeError('request {} is still in flight: wait() first'.format(self.index))
         return self.runner.host_inputs.detected_rois(name, self.runner.stream_base)
 
+    def landmark_warps(self, name: str):
+        """After ``wait()`` of a pass whose input `name` was a ``LandmarkWarps``: the record (count, valid, table) -- `table` the (n, 7)
+        int64 table that pass used, row b = (id, A00, A01, C0, A10, A11, C1) in Q16, void rows being (-1, 0, 0, 0, 0, 0, 0); `valid` which
+        rows are not void, (n,) bool; `count` how many.  ``warp.apply(table[b, 1:].reshape(2, 3) / 65536, xy)`` maps points `xy` of row
+        b's network pixels -- what the consumer found in the aligned crop -- back to positions in frame ``table[b, 0]``.  One small
+        page-locked read-back on this request's drained stream.  RuntimeError when the last pass of that input was fed anything else."""
+        if self._in_flight:
+            raise RuntimeError('request {} is still in flight: wait() first'.format(self.index))
+        return self.runner.host_inputs.landmark_warps(name, self.runner.stream_base)
+
 
 @contextlib.contextmanager
 def _overridden(obj, **values):

@@ -6,6 +6,8 @@ import dataclasses
 
 import numpy as np
 
+from . import landmarks as landmark_rule
+
 # color formats whose frames are YUV 4:2:0 planes, (n, 3 h / 2, w), and those whose frames are rows of 4-byte units with the `kind` of
 # pvhip_input_preprocess_packed_f32: packed YUV 4:2:2 (n, h, w, 2) and four-byte pixels (n, h, w, 4)
 YUV420_FORMATS = ('NV12', 'I420')
@@ -553,6 +555,83 @@ class DetectedRois:
         if shape[-2] * 7 >= 2 ** 31:
             raise ValueError('input {}: {} records are more than one launch indexes'.format(name, shape[-2]))
         return int(shape[-2]) // int(images)
+
+
+class LandmarkWarps:
+    """A network input given as crops aligned by the points another network found (a cascade: detector, crops, a landmark regressor on
+    the crops, then the aligned crop into a recognition or attribute network, all on this GPU):
+    ``start_async({name: LandmarkWarps(frames, landmarks, template)})``, wherever a WarpInput is accepted, for every declared host
+    format.  `frames`: as for WarpInput; this request uploads them, as a DetectedRois uploads its own.  `template`: (K, 2) real numbers,
+    2 <= K <= 32; point i is the place (x, y) landmark i shall land at, in output pixel indices of this input's extent, pixel centres
+    at the integers.  `landmarks`: K points per row, float32 of shape (N, 2 K) or (N, 2 K, 1, 1) as x0, y0, x1, y1, ..., normalised to
+    the region the landmark network saw -- 0 its left or top edge, 1 its right or bottom edge --, as
+      * the ``InferRequest`` of another loaded network whose Result (`output` names it when there are several) has that shape: in flight,
+        its device-resident Result is read with no host wait -- this request's stream waits for the landmark pass on the device --;
+        waited for, its last host Results are taken like an array;
+      * a ``device.DeviceTensor``, or a host array (uploaded behind the same event as the frames).
+    `regions`: the (id, x, y, w, h) each row of points is normalised to.  None: for a request whose single 4-D Parameter was last fed a
+    ``RoiInput`` or a ``DetectedRois``, that pass's (N, 5) table, still on the device; for a request last fed whole images, and for
+    tensors and arrays, the whole frame -- row b reads frame b (m == N) or frame 0 (m == 1).  Or an integer (N, 5) array, uploaded
+    behind the frames' event.
+    The (n, 7) table of a WarpInput is fitted on the device (pvhip_landmarks_to_warps; the rule in Python floats:
+    pyopenvino_amd/landmarks.py, in numpy: tests/landmark_warps_ref.py): row b is the least-squares similarity, without reflection,
+    from the template's points to row b's landmarks in frame pixels, in binary64 with every operation rounded once -- directly the
+    inverse map a warp takes.  It is NOT ``warp.invert(cv2.estimateAffinePartial2D(landmarks -> template))``: that call minimises in the
+    template's space, this fit in the frame's; the two agree where the fit is exact.  A row is void -- quiet NaN in the input tensor --
+    when it lies behind the N rows of points, its region's id is none of the m frames, its region's w or h is outside [1, 2^24] (the
+    rows behind a DetectedRois' count), one of its 2 K values is not finite, the fitted matrix breaks a WarpInput's limits, or all its
+    points coincide.  ``InferRequest.landmark_warps(name)`` reads the table back.  From there on the pass is a WarpInput's word for word.
+
+    The landmark request may be started again as soon as ``start_async`` of this input has returned: its next pass waits, on the device,
+    until the table has been fitted -- of its Result and of its region table alike.  This input keeps that Result tensor alive until its
+    own next pass, so the landmark request's next pass writes another one; a request records its pass for replay only when that
+    allocates nothing new, so let the landmark request run a few passes on its own before the chain starts (as a DetectedRois'
+    detector: scripts/bench_landmark_warps.py does).  ValueError for a landmark request whose 4-D input
+    declares a ``resize_fit`` other than STRETCH (the points would need its geometry) or was last fed a WarpInput, a PerspectiveInput or
+    a LandmarkWarps (no rectangle to be normalised to)."""
+    __slots__ = ('frames', 'landmarks', 'template', 'output', 'regions')
+
+    def __init__(self, frames, landmarks, template, output=None, regions=None):
+        self.frames, self.landmarks, self.template, self.output, self.regions = frames, landmarks, template, output, regions
+
+    def __repr__(self):
+        return 'LandmarkWarps(frames={}, landmarks={})'.format(getattr(self.frames, 'shape', None), type(self.landmarks).__name__)
+
+    def checked_template(self, name) -> np.ndarray:
+        """``landmarks.packed_template(template)`` for input `name`: the 2 K + 3 doubles the device takes; or ValueError."""
+        try:
+            return landmark_rule.packed_template(self.template)
+        except ValueError as e:
+            raise ValueError('input {}: {}'.format(name, e)) from None
+
+    @staticmethod
+    def checked_points(name, shape, dtype, k) -> int:
+        """The row count N of points of `shape` and `dtype` for a template of `k` points; or ValueError."""
+        if np.dtype(dtype) != np.float32 or len(shape) not in (2, 4) or shape[0] < 1 or tuple(shape[2:]) not in ((), (1, 1)):
+            raise ValueError('input {}: landmarks are float32 points of shape (N, 2 K) or (N, 2 K, 1, 1), got {} {}'.format(
+                name, np.dtype(dtype).name, tuple(shape)))
+        if shape[1] != 2 * k:
+            raise ValueError('input {}: landmarks of shape {} hold {} values per row, the template of {} points needs {}'.format(
+                name, tuple(shape), shape[1], k, 2 * k))
+        return int(shape[0])
+
+    def checked_regions(self, name, rows):
+        """`regions` as a C-contiguous int32 (rows, 5) array, or None when none is given; or ValueError."""
+        if self.regions is None:
+            return None
+        t = np.asarray(self.regions)
+        if t.shape != (rows, 5) or t.dtype.kind not in 'iu':
+            raise ValueError('input {}: regions is an integer table of shape {} -- one (id, x, y, w, h) per row of landmarks --, got {} {}'.format(
+                name, (rows, 5), t.dtype, t.shape))
+        lo, hi = np.iinfo(np.int32).min, np.iinfo(np.int32).max
+        if t.size and (int(t.min()) < lo or int(t.max()) > hi):
+            raise ValueError('input {}: regions holds 32-bit integers, got values in [{}, {}]'.format(name, int(t.min()), int(t.max())))
+        return np.ascontiguousarray(t, np.int32)
+
+
+# what InferRequest.landmark_warps returns: how many rows of the pass were valid, which ones ((n,) bool), and the (n, 7) int64 table
+# (id, A00, A01, C0, A10, A11, C1) the pass used, void rows being (-1, 0, 0, 0, 0, 0, 0)
+LandmarkTable = collections.namedtuple('LandmarkTable', 'count valid table')
 
 
 # what InferRequest.detected_rois returns: the (n, 5) int32 table the pass used, the flat row of the detections each batch row came from
