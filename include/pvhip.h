@@ -553,6 +553,46 @@ int pvhip_detections_to_rois_fit(const float* records, int* rois, int* record_of
  * PVHIP_EINVAL and nothing is launched. */
 int pvhip_topk_rows_f32(const float* x, int rows, int cols, int k, int* indices, float* values);
 
+/* ---------------------------------------------------------------- an embedding network's answer ---- */
+/* Addition to ABI v18 (the version number is unchanged: nothing existing changed): the k best rows of a gallery of enrolled embeddings
+ * for every row of a contiguous (n, d) fp32 Result -- what a user of a recognition network makes on the host with `gallery @ x.T` and an
+ * argpartition -- so that only (n, k) triples are read back and no (n, g) score matrix is written anywhere.  The rule
+ * (pyopenvino_amd/gallery.py and tests/gallery_ref.py state the same one, matched bit for bit):
+ *   1. norm    of a row v[0..d) of float32: s = the binary64 sum of (double)v[i] * (double)v[i] for i ascending, started from 0.0, one
+ *      rounding per addition (the squares are exact in binary64); the row is void when an element is not finite or when s == 0;
+ *      r = sqrt(s), correctly rounded binary64.
+ *   2. gallery rows, on the host when the gallery is made: under PVHIP_GALLERY_COSINE u[g][i] = (float)((double)v[i] / r); under
+ *      PVHIP_GALLERY_DOT u = v, and a row is void only for an element that is not finite.  A gallery has no void row.
+ *   3. chain   a[r][g] starts at +0.0f; for i = 0 .. d - 1 in order a = fmaf(x[r][i], u[g][i], a): fp32, one rounding per step,
+ *      subnormals kept.  x is the Result's own bits, not normalised.  A chain may end at -0.0 (a negative underflow); a zero of either sign
+ *      counts as +0.0 from here on, so the zero padding behind d does not change the answer.
+ *   4. order   per row the gallery rows are sorted by a in the total order of pvhip_topk_rows_f32 above: NaN first, then descending,
+ *      +0 equal to -0, ties to the lower gallery index; the first k are the candidates.  A chain of finite factors may overflow to an infinity and then stays there: it never holds NaN.
+ *   5. score   under PVHIP_GALLERY_DOT score = a; under PVHIP_GALLERY_COSINE score = (float)((double)a / r_row), r_row from 1. on the
+ *      query row.  A NaN score is the quiet NaN 0x7FC00000.  Slot j is kept when has_min_score == 0 or score >= min_score (a NaN is not);
+ *      counts[r] is the length of the leading run of kept slots; the slots behind it are void: index -1, score the quiet NaN 0x7FC00000.
+ *   6. a void query row -- an element that is not finite under either metric, or s == 0 under PVHIP_GALLERY_COSINE -- has count 0 and
+ *      every slot void (the quiet-NaN rows behind `count` of a DetectedRois or LandmarkWarps pass are such rows).
+ * `x` may be only 4-byte aligned (a Result that starts inside a tensor).  `packed` is the gallery in the matrix cores' operand order,
+ * 16-byte aligned: g padded to gp, a multiple of 32, and d to dp, a multiple of 8, with zeros; blocks of 32 gallery rows hold groups of 8
+ * consecutive i; in a group lane ((i & 1) << 5) | j holds 4 floats, elements i0 + (i & 1) + 2 t, t = 0..3, of gallery row 32 b + j:
+ *     packed[((b * (dp / 8) + i / 8) * 64 + (((i & 1) << 5) | (g & 31))) * 4 + ((i & 7) >> 1)] = u[g][i],   b = g / 32
+ * -- the lane's B operand of four consecutive 32x32x2 matrix steps in one 16-byte load, 1 KB contiguous per wave.
+ * Two launches on the current stream, no allocation.  Scores: one workgroup per (4 chunks of PVHIP_GALLERY_CHUNK gallery rows, block of 32
+ * query rows), the blocks of one gallery piece side by side on one XCD; the query block is copied once into LDS (32 * dp * 4 bytes: d <= 1024), rows >= n and void rows zero-filled; each wave
+ * walks the 32-row blocks of its chunk with v_mfma_f32_32x32x2_f32, i in order, one accumulator tile per block -- bit for bit the chain
+ * of 3. --, turns the tiles into the 64-bit keys of pvhip_topk_rows_f32 (low word: the gallery row) and writes the best k of every
+ * (query row, chunk) to `scratch` by the same rounds.  Merge: one wave per query row computes 1., merges the chunks' keys by the same
+ * rounds and writes 5. and 6.  `scratch`: 8 * n * ceil(g / PVHIP_GALLERY_CHUNK) * k bytes, 8-byte aligned, the caller's, overwritten.
+ * `counts` (n) int32, `indices` (n, k) int32, `scores` (n, k) fp32; `norms` NULL or (n) binary64, 8-byte aligned: r of every row (of a
+ * row with an element that is not finite: NaN).  1 <= n, n * d < 2^31, ceil(n / 32) * ceil(g / 1024) < 2^30, 1 <= d <= 1024, 1 <= g <= 2^24, 1 <= k <= min(g, 64), metric one
+ * of the two, min_score finite when has_min_score (0 or 1), no NULL or misaligned pointer; else PVHIP_EINVAL and nothing is launched. */
+#define PVHIP_GALLERY_COSINE 0
+#define PVHIP_GALLERY_DOT    1
+#define PVHIP_GALLERY_CHUNK  256
+int pvhip_gallery_match_f32(const float* x, int n, int d, const float* packed, int g, int k, int metric, int has_min_score,
+                            float min_score, void* scratch, int* counts, int* indices, float* scores, double* norms);
+
 /* ---------------------------------------------------------------- a detector's answer ------ */
 /* Addition to ABI v18 (the version number is unchanged: nothing existing changed): the records of pvhip_detection_output_f32 become one
  * flat table of the detections a caller wants -- what the reference's sample makes on the host with `for record in res.reshape(100, 7):

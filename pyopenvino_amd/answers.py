@@ -1,20 +1,20 @@
-"""Answers behind the pass: the Results a start named with ``top_k=`` or ``detections=`` come back from wait() as a ``TopK`` or a
-``Detections`` made on the device instead of as the tensor.  One ``Answers`` per Executable_Network (one per request), as ``HostInputs``
+"""Answers behind the pass: the Results a start named with ``top_k=``, ``detections=`` or ``matches=`` come back from wait() as a ``TopK``, a
+``Detections`` or a ``Matches`` made on the device instead of as the tensor.  One ``Answers`` per Executable_Network (one per request), as ``HostInputs``
 is on the way in: the request checks the arguments, binds the asks to the staged inputs, launches behind the pass and reads after it.
 A plain screen over a detector whose input declares a fit (preprocess_info.resize_fit) learns its geometry in bound(), from the extent
 of the frames the pass was fed.
 
-An ask is one Result's question in its resolved form -- top_k.Ask, detections.Ask / FittedAsk or tiled_detections.Ask / RegionAsk, each with
+An ask is one Result's question in its resolved form -- top_k.Ask, detections.Ask / FittedAsk, tiled_detections.Ask / RegionAsk or gallery.Ask, each with
 `bound`, `key`, `launch` and `on_host` --; which kind it is matters only where checked() makes it."""
 import numpy as np
 
-from . import detections as detections_rule, device, tiled_detections as tiled_rule, top_k as top_k_rule
+from . import detections as detections_rule, device, gallery as gallery_rule, tiled_detections as tiled_rule, top_k as top_k_rule
 from .input_format import DetectedRois, LandmarkWarps, PerspectiveInput, RoiInput, WarpInput
 
 
 class Answers:
     """`blocks` = {ask.key(Result name): its Blocks}, this request's own device and page-locked blocks, made on first use: (name, k),
-    (name, resolved DetectionScreen) or (name, resolved TiledScreen or RegionScreen, m)."""
+    (name, resolved DetectionScreen), (name, resolved TiledScreen or RegionScreen, m) or (name, id of the Gallery, k)."""
 
     def __init__(self, runner):
         self.runner, self.blocks = runner, {}       # runner: the Executable_Network whose base stream and Results these are
@@ -22,18 +22,24 @@ class Answers:
     def release(self):
         self.blocks = {}
 
-    def checked(self, inputs, top_k, detections, sharded: bool) -> dict:
-        """{Result name: ask} of the `top_k` and `detections` arguments of a start with `inputs`, {} when nothing is asked; ValueError.
-        Everything is looked up in the network as it was read: no device is needed, nothing is staged, allocated or launched."""
-        if top_k is None and detections is None:
+    def checked(self, inputs, top_k, detections, sharded: bool, matches=None) -> dict:
+        """{Result name: ask} of the `top_k`, `detections` and `matches` arguments of a start with `inputs`, {} when nothing is asked;
+        ValueError.  Everything is looked up in the network as it was read: no device is needed, nothing is staged, allocated or launched."""
+        if top_k is None and detections is None and matches is None:
             return {}
         ienet = self.runner.ienet
+        matched = gallery_rule.checked(ienet, matches, sharded)
+        if top_k is None and detections is None:
+            return {name: gallery_rule.Ask(match) for name, match in matched.items()}
         tiled_rule.checked_top_k(top_k, detections)
         wanted = top_k_rule.checked(ienet, top_k, sharded)
         screens = detections_rule.checked(ienet, detections, sharded)
         both = sorted(set(wanted) & set(screens))
         if both:
             raise ValueError('detections: Result {!r} is asked for with top_k as well'.format(both[0]))
+        both = sorted(set(matched) & (set(wanted) | set(screens)))
+        if both:
+            raise ValueError('matches: Result {!r} is asked for with {} as well'.format(both[0], 'top_k' if both[0] in wanted else 'detections'))
         tiled = {name: s for name, s in screens.items() if isinstance(s, tiled_rule.TiledScreen)}
         formats = self.runner.host_inputs.formats
         for name, s in tiled.items():           # (the geometry would be one per tile)
@@ -59,6 +65,7 @@ class Answers:
                 given = detections[name] if isinstance(detections, dict) else detections
                 explicit = isinstance(given, detections_rule.DetectionScreen) and given.frame_size is not None
                 asks[name] = detections_rule.FittedAsk(s, n, fitted, formats[fitted], explicit, None)
+        asks.update((name, gallery_rule.Ask(match)) for name, match in matched.items())
         return asks
 
     def _region_ask(self, screen, n):

@@ -3,7 +3,7 @@
 // (pvhip_topk_rows_f32), tests/topk_ref.py is the same in numpy.
 //
 // A latency kernel (the Result of a batch of 256 is 1 MB): one wave per row, four rows per workgroup, no LDS, no sorting network.
-//   key     every element becomes a 64-bit key: high word = its float bits made order-preserving as an unsigned, -0.0 folded onto +0.0
+//   key     (pvhip_topk_keys.h) every element becomes a 64-bit key: high word = its float bits made order-preserving as an unsigned, -0.0 folded onto +0.0
 //           and every NaN mapped to the maximum; low word = 0x7FFFFFFF - index.  All keys of a row are distinct and nonzero, and the
 //           rule's order is the descending order of the keys.
 //   rounds  round j takes the wave-wide maximum of the keys strictly below round j - 1's winner; nothing is mutated.  Lane j keeps
@@ -14,6 +14,7 @@
 //   rows    of up to 1024 columns are turned into keys once and stay in registers (17 keys per lane); longer rows are read again in
 //           every round and hit in L2.
 #include "pvhip_common.h"
+#include "pvhip_topk_keys.h"
 
 using namespace pvhip;
 
@@ -22,30 +23,6 @@ namespace {
 constexpr int      kTopKMax   = 64;            // one winner per lane
 constexpr int      kRegPieces = 4;             // 16-byte pieces per lane of a register-resident row: 64 * 4 * 4 = 1024 columns
 constexpr int      kRegCols   = kWave * kRegPieces * 4;
-constexpr unsigned kIndexTop  = 0x7FFFFFFFu;   // low word of the key of index 0 (rows * cols < 2^31): no key is all ones, the bound of round 0
-
-__device__ __forceinline__ unsigned long long topk_key(unsigned bits, unsigned index) {
-    const unsigned mag = bits & 0x7FFFFFFFu;
-    unsigned ord;
-    if (mag > 0x7F800000u) ord = 0xFFFFFFFFu;                                   // NaN, any sign and payload: before every number
-    else if (mag == 0u) ord = 0x80000000u;                                      // +0.0 and -0.0 are equal
-    else ord = (bits & 0x80000000u) ? ~bits : (bits | 0x80000000u);             // (+inf: 0xFF800000; -inf: 0x007FFFFF)
-    return ((unsigned long long)ord << 32) | (unsigned long long)(kIndexTop - index);
-}
-
-// best = max(best, key) among the keys strictly below `below`
-__device__ __forceinline__ void topk_take(unsigned long long& best, unsigned long long key, unsigned long long below) {
-    best = (key < below && key > best) ? key : best;
-}
-
-__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        const unsigned long long o = __shfl_xor(v, m, kWave);
-        v = o > v ? o : v;
-    }
-    return v;
-}
 
 template <bool kInRegs>
 __global__ __launch_bounds__(kBlock) void topk_rows_kernel(const unsigned* __restrict__ x, int rows, int cols, int k,

@@ -184,6 +184,7 @@ SIGNATURES = {
     'pvhip_input_preprocess_perspective_color_f32': (_c.c_int, [_c.c_void_p, _fp, _c.c_void_p] + [_c.c_int] * 10
                                                      + [_fp, _fp, _c.c_float, _c.c_int, _c.c_int]),
     'pvhip_landmarks_to_warps': (_c.c_int, [_c.c_void_p] * 5 + [_c.c_int] * 6),
+    'pvhip_gallery_match_f32': (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p] + [_c.c_int] * 4 + [_c.c_float] + [_c.c_void_p] * 5),
 }
 
 # entry points whose return value is not a status code

@@ -326,22 +326,29 @@ class InferRequest:
     every region's corners are mapped back through the geometry its own pixels were placed with (pvhip_detections_merge_regions, the
     rule of tiled_detections.py) and the answer is the same Detections over frames, ``detected_rois(name).records[records // P]`` being the
     first-stage record of each box.  ValueError as for a TiledScreen: that input fed anything but a RoiInput or a DetectedRois.
-    `top_k` and `detections` may be given together, for different Results."""
+    `matches` = a ``GalleryMatch``, a ``Gallery`` (k = 1, no threshold) or {Result name: either}: those embedding Results -- every FP32
+    Result declared (n, D) or (n, D, 1, ...) with the gallery's D for the unnamed forms -- come back from wait() as a ``Matches`` (counts,
+    indices, ids, scores): the k best gallery rows of every batch row by the rule of gallery.py, made by pvhip_gallery_match_f32 behind
+    the pass (two launches; the gallery is uploaded once, on the first of them) and read back in one copy of 4 n + 8 n k bytes; the full
+    Result stays on the device.  ValueError ('matches: ...'), before anything is staged or launched: no such Result for an unnamed form,
+    an unknown name, a Result of another shape, precision or D, a value of another type, k or min_score out of range, a sharded batch,
+    a Result that top_k or detections names as well.
+    `top_k`, `detections` and `matches` may be given together, for different Results."""
 
     def __init__(self, owner, runner, index: int):
         self.owner, self.runner, self.index = owner, runner, index      # owner: the network load_network returned
         self._in_flight, self._replayed = False, None
-        self._asks = {}                 # {Result name: ask} of the pass in flight (answers.py): what top_k= and detections= named
+        self._asks = {}                 # {Result name: ask} of the pass in flight (answers.py): what top_k=, detections= and matches= named
 
-    def start_async(self, inputs: dict, top_k=None, detections=None):
-        self._start(inputs, top_k, False, detections)
+    def start_async(self, inputs: dict, top_k=None, detections=None, matches=None):
+        self._start(inputs, top_k, False, detections, matches)
 
-    def _start(self, inputs, top_k, verbose, detections=None):
+    def _start(self, inputs, top_k, verbose, detections=None, matches=None):
         if self._in_flight:
             raise RuntimeError('request {} is still in flight: wait() first'.format(self.index))
         ex = self.runner
         sharded = ex.sharded or self.owner.sharded
-        asks = ex.answers.checked(inputs, top_k, detections, sharded)
+        asks = ex.answers.checked(inputs, top_k, detections, sharded, matches)
         fed, inputs = inputs, ex.host_inputs.stage(inputs, ex.stream_base, sharded)
         self._asks = ex.answers.bound(asks, fed)
         ex.wait_result_readers()
@@ -377,8 +384,8 @@ class InferRequest:
                 G.nodes[nid]['result'] = out[name] = ex._read_back(value, self.owner.comm)
         return out
 
-    def infer(self, inputs: dict, top_k=None, detections=None) -> dict:
-        self.start_async(inputs, top_k, detections)
+    def infer(self, inputs: dict, top_k=None, detections=None, matches=None) -> dict:
+        self.start_async(inputs, top_k, detections, matches)
         return self.wait()
 
     def input_buffer(self, name: str, source_size=None, frames=None) -> np.ndarray:
@@ -561,8 +568,8 @@ class Executable_Network:
                 event.wait()
             device.select_stream(0)
 
-    def start_async(self, request_id: int, inputs: dict, top_k=None, detections=None):
-        self.requests[request_id].start_async(inputs, top_k, detections)
+    def start_async(self, request_id: int, inputs: dict, top_k=None, detections=None, matches=None):
+        self.requests[request_id].start_async(inputs, top_k, detections, matches)
 
     def wait(self, request_id: int) -> dict:
         return self.requests[request_id].wait()
@@ -1064,12 +1071,13 @@ class Executable_Network:
             return None
         return self._graph
 
-    def infer(self, inputs: dict, verbose: bool = False, top_k=None, detections=None) -> dict:
+    def infer(self, inputs: dict, verbose: bool = False, top_k=None, detections=None, matches=None) -> dict:
         """`top_k` = k or {Result name: k}: those Results come back as a ``TopK`` of the k best classes per batch row; `detections` = a
-        ``DetectionScreen``, a min_confidence or {Result name: either}: those come back as a ``Detections`` (InferRequest)."""
-        if top_k is not None or detections is not None:   # the pass of request 0 (this network's own graph and streams), waited for at once
+        ``DetectionScreen``, a min_confidence or {Result name: either}: those come back as a ``Detections``; `matches` = a ``Gallery``, a
+        ``GalleryMatch`` or {Result name: either}: those come back as a ``Matches`` of the k best gallery rows per batch row (InferRequest)."""
+        if top_k is not None or detections is not None or matches is not None:   # the pass of request 0 (this network's own graph and streams), waited for at once
             request = self.requests[0] if self.requests else InferRequest(self, self, 0)
-            request._start(inputs, top_k, verbose, detections)
+            request._start(inputs, top_k, verbose, detections, matches)
             return request.wait()
         inputs = self.host_inputs.stage(inputs, self.stream_base, self.sharded)
         self.wait_result_readers()
