@@ -34,7 +34,7 @@ extern "C" {
 #define PVHIP_ECOMM        -4   /* RCCL failure / library not loadable                        */
 #define PVHIP_EUNSUPPORTED -5   /* configuration outside what the kernels implement           */
 
-#define PVHIP_ABI_VERSION   18
+#define PVHIP_ABI_VERSION   19
 
 /* ---------------------------------------------------------------- runtime plumbing ---------- */
 /* No reference counterpart: the reference computes in host numpy arrays (inference_engine.py:245-256
@@ -118,6 +118,34 @@ int pvhip_add_f32(const float* a, const float* b, float* out, int rank,
                   const int64_t* shape, const int64_t* a_strides, const int64_t* b_strides);
 int pvhip_mul_f32(const float* a, const float* b, float* out, int rank,
                   const int64_t* shape, const int64_t* a_strides, const int64_t* b_strides);
+/* ABI v19.  Which instantiation and grid a launch of the entries above takes: host-only like the pooling queries further down (no
+ * device needed, before pvhip_init too; PVHIP_STREAM_NT / PVHIP_STREAM_WG are honoured), answered by the SAME plan function the launcher
+ * switches on.  form[PVHIP_FORM_INTS]; a slot set of its own per family, unused slots 0; kind PVHIP_FORM_NONE (-1) when nothing is launched.
+ * pvhip_unary_form(n): unary_f4_kernel<Op, NT, U> over n elements (ReLU, Clamp and Sigmoid share the launcher).                          */
+#define PVHIP_UNARY_F4            0   /* unary_f4_kernel                                                                     */
+#define PVHIP_UNARY_FORM_KIND     0
+#define PVHIP_UNARY_FORM_NT       1   /* nontemporal accesses (the <true, 4> instantiation), else <false, 1>                 */
+#define PVHIP_UNARY_FORM_U        2   /* 4 KiB pieces per workgroup and run                                                  */
+#define PVHIP_UNARY_FORM_GRID     3   /* workgroups launched                                                                 */
+#define PVHIP_UNARY_FORM_RUNS     4   /* 1: at least one whole run of U x 256 float4                                         */
+#define PVHIP_UNARY_FORM_REM4     5   /* 1: float4 left behind the last whole run                                            */
+#define PVHIP_UNARY_FORM_TAIL     6   /* 1: n % 4 != 0, the scalar tail stores                                               */
+#define PVHIP_UNARY_FORM_WRAPS    7   /* 1: more whole runs than workgroups, a workgroup's run loop goes round again         */
+int pvhip_unary_form(size_t n, int* form);
+/* pvhip_binary_form: the arguments of pvhip_add_f32 / pvhip_mul_f32 without the pointers; commutative = 1 is what both pass (0: the
+ * operands of a swapped launch are put back in order, the kSwap instantiations -- reached by the diagnostic build's subtract only). */
+#define PVHIP_BINARY_SAME         0   /* binary_same_kernel<Op, NT>: both operands have the output shape                     */
+#define PVHIP_BINARY_CHANNEL      1   /* binary_channel_kernel<Op, kSwap>: out as [outer][C][inner], one operand holds C values */
+#define PVHIP_BINARY_CHANNEL4     2   /* binary_channel4_kernel<Op, kSwap, NT, U>: the same with inner % 4 == 0 and n % 4 == 0 */
+#define PVHIP_BINARY_STRIDED      3   /* binary_strided_kernel: any strides                                                  */
+#define PVHIP_BINARY_FORM_KIND    0
+#define PVHIP_BINARY_FORM_BCAST   1   /* 0: neither operand is broadcast, 1: the second (b), 2: the first (a): b is streamed */
+#define PVHIP_BINARY_FORM_SWAP    2   /* 1: the kSwap instantiation (BCAST == 2 and not commutative)                         */
+#define PVHIP_BINARY_FORM_NT      3   /* nontemporal accesses (SAME, CHANNEL4; CHANNEL4 then takes U = 4)                    */
+#define PVHIP_BINARY_FORM_C       4   /* CHANNEL, CHANNEL4: values of the broadcast operand                                  */
+#define PVHIP_BINARY_FORM_INNER   5   /* CHANNEL, CHANNEL4: elements behind the channel axes                                 */
+#define PVHIP_BINARY_FORM_GRID    6   /* workgroups launched                                                                 */
+int pvhip_binary_form(int rank, const int64_t* shape, const int64_t* a_strides, const int64_t* b_strides, int commutative, int* form);
 
 /* ---------------------------------------------------------------- pooling / normalisation --- */
 /* MaxPool.py:41-72 kernel_MaxPool_numpy: max over the kh x kw window of the ZERO-padded input
@@ -216,6 +244,14 @@ int pvhip_maxpool_lrn_conv1x1_f32(const float* x, const float* w_oihw, float* y,
  * dst[outer][sum(inner)] at its running offset.  srcs / inner are HOST arrays of n_src entries.  */
 #define PVHIP_MAX_CONCAT 16
 int pvhip_concat_f32(int n_src, const float* const* srcs, const int64_t* inner, float* dst, int64_t outer);
+/* ABI v19.  The copy unit and grid of that launch (host-only; PVHIP_FORM_NONE for an empty output; PVHIP_EINVAL / PVHIP_EUNSUPPORTED
+ * as the entry).  Transpose, pad2d and the c8 conversions have one kernel each and no query.                                       */
+#define PVHIP_CONCAT_SCALAR       0   /* concat_kernel<float>: some inner[i] is no multiple of 4                              */
+#define PVHIP_CONCAT_VEC4         1   /* concat_kernel<float4>                                                               */
+#define PVHIP_CONCAT_FORM_KIND    0
+#define PVHIP_CONCAT_FORM_GRID_X  1   /* workgroups per source                                                               */
+#define PVHIP_CONCAT_FORM_GRID_Y  2   /* sources (zero-length ones included)                                                 */
+int pvhip_concat_form(int n_src, const int64_t* inner, int64_t outer, int* form);
 /* The zero-padded image Convolution.py:64-66 builds before it slides its window, as a tensor: y (n, c, h + pad_top + pad_bottom,
  * w + pad_left + pad_right) = x (n, c, h, w) with zeros around; channel_add (c floats, may be NULL) is added to every element of x on
  * the way (Add.py:9-14 of a per-channel constant feeding the convolution: one pass instead of two).  The Convolution plugin pads the
@@ -231,6 +267,23 @@ int pvhip_transpose_f32(const float* x, float* y, int rank, const int64_t* in_sh
  * trans_a), B is stored [K,N] (or [N,K] when trans_b); fp32 MFMA (v_mfma_f32_32x32x2_f32).        */
 int pvhip_matmul_f32(const float* a, const float* b, float* c, int m, int n, int k,
                      int trans_a, int trans_b);
+/* ABI v19.  What pvhip_matmul_f32 (f16 = 0) / pvhip_matmul_f16 (f16 = 1) launch for these extents: host-only, answered by the plan
+ * function the launcher switches on.  Outputs of fewer than 512 tiles of 64 x 64 split the reduction over grid.z into chunks of a
+ * multiple of 16 (at most ceil(k / 64) of them) and sum the partial tiles in split order -- the same bits on every launch.
+ * PVHIP_EUNSUPPORTED for m > 65535 * 64, as the entries.                                                                          */
+#define PVHIP_MATMUL_MEMSET        0   /* k == 0: the output is zeroed                                                        */
+#define PVHIP_MATMUL_SINGLE        1   /* one launch of matmul_kernel                                                         */
+#define PVHIP_MATMUL_SPLIT         2   /* matmul_kernel over grid.z = splits into a workspace + matmul_reduce_kernel          */
+#define PVHIP_MATMUL_FORM_KIND     0
+#define PVHIP_MATMUL_FORM_GRID_X   1   /* tiles along n                                                                       */
+#define PVHIP_MATMUL_FORM_GRID_Y   2   /* tiles along m                                                                       */
+#define PVHIP_MATMUL_FORM_SPLITS   3
+#define PVHIP_MATMUL_FORM_K_CHUNK  4   /* reduction elements per split (a multiple of 16)                                     */
+#define PVHIP_MATMUL_FORM_LAST_K   5   /* ... of the last split: k - (splits - 1) * k_chunk                                   */
+#define PVHIP_MATMUL_FORM_A_K_FAST 6   /* 1: consecutive lanes stage A along k (its contiguous axis), 0: along m              */
+#define PVHIP_MATMUL_FORM_B_N_FAST 7   /* 1: consecutive lanes stage B along n, 0: along k                                    */
+#define PVHIP_MATMUL_FORM_F16      8   /* 1: operands rounded to fp16 while staged (matmul_kernel<true>)                      */
+int pvhip_matmul_form(int m, int n, int k, int trans_a, int trans_b, int f16, int* form);
 
 
 /* Convolution.py:57-87 im2col + kernel_Convolution_im2col ("special"), as an implicit GEMM:
@@ -702,6 +755,19 @@ int pvhip_comm_destroy(void);
  * (n, c, h, w)).  Exact: dst == src.transpose(0, 3, 1, 2).astype(float32) bit for bit.  fp32 NCHW is a device copy.  n <= 65535,
  * c * h * w < 2^31, c <= 4096 for NHWC (pvhip_layout.hip). */
 int         pvhip_input_to_nchw_f32(const void* src, float* dst, int n, int c, int h, int w, int src_u8, int src_nhwc);
+/* ABI v19.  What that entry launches (host-only): src_align / dst_align are the two addresses modulo 16, which decide the 16-byte forms.
+ * PVHIP_EINVAL as the entry (c > 4096 for NHWC).                                                                                   */
+#define PVHIP_INPUT_COPY           0   /* fp32 NCHW: a device copy                                                            */
+#define PVHIP_INPUT_U8_LINEAR      1   /* u8_to_f32_kernel                                                                    */
+#define PVHIP_INPUT_NHWC           2   /* nhwc_to_nchw_kernel<T, VL, VS>                                                      */
+#define PVHIP_INPUT_FORM_KIND      0
+#define PVHIP_INPUT_FORM_VEC       1   /* U8_LINEAR: 1 when the word loop is taken (src 4-byte, dst 16-byte aligned, >= 4 elements) */
+#define PVHIP_INPUT_FORM_TILE      2   /* NHWC: pixels per workgroup (1024 halved until tile * c * sizeof(T) <= 16 KB)        */
+#define PVHIP_INPUT_FORM_VL        3   /* NHWC: 16-byte loads                                                                 */
+#define PVHIP_INPUT_FORM_VS        4   /* NHWC: 16-byte stores                                                                */
+#define PVHIP_INPUT_FORM_GRID_X    5
+#define PVHIP_INPUT_FORM_GRID_Y    6
+int         pvhip_input_to_nchw_form(int n, int c, int h, int w, int src_u8, int src_nhwc, int src_align, int dst_align, int* form);
 /* Addition to ABI v17 (the version number is unchanged: nothing existing changed): an input with declared preprocessing
  * (IENetwork.input_info[name].preprocess_info) -- bilinear resize of a (src_h, src_w) source to the Parameter's (dst_h, dst_w), channel
  * reversal, per-channel mean / scale -- and the format change above, in ONE launch into the fp32 NCHW tensor `dst` (n, c, dst_h, dst_w).

@@ -48,6 +48,11 @@ int pvhip_diag_wino4s_simd(unsigned long long* out);
 int pvhip_diag_wino4s_trace(unsigned* out);                  /* workgroup 3 of the last launch: [wave][stage < 96][saw the image / finished] in cycles since its start */        /* the same workgroups: 16 waves x 4 SIMDs, how often wave w ran on SIMD s */      /* conv_wino4s_kernel (shared-V form): 16 waves x 8 cycle accounts, read and cleared */
 /* the same run's epilogue phases: [wave 0..7][write 0, barrier, read + store 0, barrier, write 1, barrier, read + store 1, barrier]  */
 int pvhip_diag_wino4_epilogue(unsigned long long* out);
+/* out = a - b with the arguments of pvhip_add_f32, launched as a NON-commutative op: when `a` is the broadcast operand the channel kernels
+ * stream b and put the operands back in order (their kSwap instantiations), which Add and Multiply never reach.  A second op functor on
+ * the product's kernels; pvhip_binary_form(..., commutative = 0, ...) names the form (tests/diag_variants.py).                            */
+int pvhip_diag_sub_f32(const float* a, const float* b, float* out, int rank, const int64_t* shape, const int64_t* a_strides,
+                       const int64_t* b_strides);
 
 #ifdef __cplusplus
 }

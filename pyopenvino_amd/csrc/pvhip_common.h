@@ -310,6 +310,14 @@ __device__ __forceinline__ void lds_dma_wait_all() { asm volatile("s_waitcnt vmc
                                __func__, #cond);                                      \
     } while (0)
 
+// The same inside a helper that an entry and its form query share: the message names the entry (`who`), not the helper.
+#define PVHIP_CHECK_ARG_AS(who, cond)                                                 \
+    do {                                                                              \
+        if (!(cond))                                                                  \
+            return pvhip::fail(PVHIP_EINVAL, "%s: argument check failed: %s",         \
+                               who, #cond);                                           \
+    } while (0)
+
 // After a kernel launch: surface launch-configuration errors immediately.
 #define PVHIP_LAUNCH_CHECK()                                                          \
     do {                                                                              \

@@ -84,17 +84,36 @@ __global__ __launch_bounds__(kBlock) void unary_f4_kernel(const float* __restric
     if (t < n) y[t] = op(x[t]);
 }
 
+// The instantiation and grid of a unary launch over n > 0 elements (launch_unary switches on it, pvhip_unary_form reports it).
+struct UnaryPlan {
+    bool     nt;
+    int      u;
+    unsigned grid;
+};
+UnaryPlan plan_unary(size_t n) {
+    const size_t n4 = n / 4;
+    UnaryPlan    p;
+    p.nt = stream_nt(n * 8);
+    if (p.nt) {                      // large: runs of four pieces per workgroup, nontemporal, up to 2 x PVHIP_STREAM_WG workgroups per CU
+        const size_t cap = (size_t)kNumCU * 2 * (size_t)settings().stream_wg, runs = (n4 + 4 * kBlock - 1) / (4 * kBlock);
+        p.u    = 4;
+        p.grid = (unsigned)(runs < cap ? runs : cap);
+        if (p.grid < 1) p.grid = 1;  // n < 4 under PVHIP_STREAM_NT=2: no float4 at all, the scalar tail still needs its workgroup
+    } else {
+        p.u    = 1;
+        p.grid = (unsigned)stream_grid(n4 > 0 ? n4 : 1);
+    }
+    return p;
+}
+
 template <class Op>
 int launch_unary(const float* x, float* y, size_t n, Op op) {
     if (n == 0) return PVHIP_OK;
-    const size_t n4 = n / 4;
-    hipStream_t  st = state().stream;
-    if (stream_nt(n * 8)) {          // large: runs of four pieces per workgroup, nontemporal, up to 2 x PVHIP_STREAM_WG workgroups per CU
-        const size_t cap = (size_t)kNumCU * 2 * (size_t)settings().stream_wg, runs = (n4 + 4 * kBlock - 1) / (4 * kBlock);
-        hipLaunchKernelGGL((unary_f4_kernel<Op, true, 4>), dim3((unsigned)(runs < cap ? runs : cap)), dim3(kBlock), 0, st, x, y, n4, n, op);
-    } else {
-        hipLaunchKernelGGL((unary_f4_kernel<Op, false, 1>), dim3(stream_grid(n4 > 0 ? n4 : 1)), dim3(kBlock), 0, st, x, y, n4, n, op);
-    }
+    const size_t    n4 = n / 4;
+    hipStream_t     st = state().stream;
+    const UnaryPlan p  = plan_unary(n);
+    if (p.nt) hipLaunchKernelGGL((unary_f4_kernel<Op, true, 4>), dim3(p.grid), dim3(kBlock), 0, st, x, y, n4, n, op);
+    else      hipLaunchKernelGGL((unary_f4_kernel<Op, false, 1>), dim3(p.grid), dim3(kBlock), 0, st, x, y, n4, n, op);
     return PVHIP_OK;
 }
 
@@ -260,69 +279,100 @@ bool channel_pattern(int rank, const int64_t* shape, const int64_t* st, int64_t*
     return true;
 }
 
-template <class Op>
-int launch_binary(const char* who, const float* a, const float* b, float* out, int rank, const int64_t* shape,
-                  const int64_t* as, const int64_t* bs, bool commutative) {
+// The element count of a binary launch, or why the arguments are refused.
+int binary_count(const char* who, int rank, const int64_t* shape, size_t* n_out) {
     if (rank < 0 || rank > PVHIP_MAX_RANK) return fail(PVHIP_EINVAL, "%s: rank %d not in [0,%d]", who, rank, PVHIP_MAX_RANK);
     size_t n = 1;
     for (int d = 0; d < rank; ++d) {
         if (shape[d] < 0) return fail(PVHIP_EINVAL, "%s: negative extent", who);
         n *= (size_t)shape[d];
     }
-    if (n == 0) return PVHIP_OK;
+    *n_out = n;
+    return PVHIP_OK;
+}
+
+// Which kernel, instantiation and grid a binary launch over n > 0 elements takes (launch_binary switches on it, pvhip_binary_form
+// reports it).  bcast: 0 neither operand is broadcast, 1 the second (b), 2 the first (a) -- the kernels then stream b, and kSwap puts
+// the operands of a non-commutative op back in order.
+struct BinaryPlan {
+    int     kind  = PVHIP_BINARY_STRIDED;
+    int     bcast = 0;
+    bool    swap = false, nt = false;
+    int     u = 1;
+    int64_t C = 0, inner = 0;
+    int     grid = 1;
+};
+BinaryPlan plan_binary(int rank, const int64_t* shape, const int64_t* as, const int64_t* bs, size_t n, bool commutative) {
+    BinaryPlan   p;
     const size_t n4     = n / 4;
     const bool   a_full = is_contiguous(rank, shape, as);
     const bool   b_full = is_contiguous(rank, shape, bs);
-    Op           op;
     if (a_full && b_full) {
-        const int g = stream_grid(n4 > 0 ? (n4 + 1) / 2 : 1);
-        if (stream_nt(n * 12)) hipLaunchKernelGGL((binary_same_kernel<Op, true>), dim3(g), dim3(kBlock), 0, state().stream, a, b, out, n4, n, op);
-        else                   hipLaunchKernelGGL((binary_same_kernel<Op, false>), dim3(g), dim3(kBlock), 0, state().stream, a, b, out, n4, n, op);
+        p.kind = PVHIP_BINARY_SAME;
+        p.grid = stream_grid(n4 > 0 ? (n4 + 1) / 2 : 1);
+        p.nt   = stream_nt(n * 12);
+        return p;
+    }
+    if (n < (1ull << 32)) {
+        const bool b_bcast = a_full && channel_pattern(rank, shape, bs, &p.C, &p.inner);
+        if (b_bcast || (b_full && channel_pattern(rank, shape, as, &p.C, &p.inner))) {
+            p.bcast = b_bcast ? 1 : 2;
+            p.swap  = !b_bcast && !commutative;
+            if (p.inner % 4 == 0 && n % 4 == 0 && n < (1ull << 31)) {
+                const unsigned runs = (unsigned)((n4 + 4 * kBlock - 1) / (4 * kBlock)), cap = (unsigned)(kNumCU * 2 * settings().stream_wg);
+                p.kind = PVHIP_BINARY_CHANNEL4;
+                p.nt   = stream_nt(n * 8);
+                p.u    = p.nt ? 4 : 1;
+                p.grid = p.nt ? (int)(runs < cap ? runs : cap) : stream_grid(n4);
+            } else {
+                p.kind = PVHIP_BINARY_CHANNEL;
+                p.grid = grid_for(n4 > 0 ? n4 : 1);
+            }
+            return p;
+        }
+    }
+    p.C = p.inner = 0;
+    p.grid        = grid_for(n);
+    return p;
+}
+
+template <class Op>
+int launch_binary(const char* who, const float* a, const float* b, float* out, int rank, const int64_t* shape,
+                  const int64_t* as, const int64_t* bs, bool commutative) {
+    size_t    n  = 0;
+    const int rc = binary_count(who, rank, shape, &n);
+    if (rc) return rc;
+    if (n == 0) return PVHIP_OK;
+    const size_t     n4 = n / 4;
+    const BinaryPlan p  = plan_binary(rank, shape, as, bs, n, commutative);
+    hipStream_t      st = state().stream;
+    Op               op;
+    // the streamed operand and the broadcast one: when `a` is the broadcast operand the kernels stream b, and a non-commutative op
+    // gets its operands back in order through kSwap
+    const float* full = p.bcast == 2 ? b : a;
+    const float* vec  = p.bcast == 2 ? a : b;
+    if (p.kind == PVHIP_BINARY_SAME) {
+        if (p.nt) hipLaunchKernelGGL((binary_same_kernel<Op, true>), dim3(p.grid), dim3(kBlock), 0, st, a, b, out, n4, n, op);
+        else      hipLaunchKernelGGL((binary_same_kernel<Op, false>), dim3(p.grid), dim3(kBlock), 0, st, a, b, out, n4, n, op);
         return PVHIP_OK;
     }
-    int64_t C = 0, inner = 0;
-    if (n < (1ull << 32)) {
-        if (a_full && channel_pattern(rank, shape, bs, &C, &inner)) {
-            const int g = grid_for(n4 > 0 ? n4 : 1);
-            if (inner % 4 == 0 && n % 4 == 0 && n < (1ull << 31)) {
-                const bool     nt   = stream_nt(n * 8);
-                const unsigned runs = (unsigned)((n4 + 4 * kBlock - 1) / (4 * kBlock)), cap = (unsigned)(kNumCU * 2 * settings().stream_wg);
-                const int      gs   = nt ? (int)(runs < cap ? runs : cap) : stream_grid(n4);
-                if (nt)
-                    hipLaunchKernelGGL((binary_channel4_kernel<Op, false, true, 4>), dim3(gs), dim3(kBlock), 0, state().stream, a, b, out, (unsigned)n4,
-                                       (unsigned)C, make_fastdiv((unsigned)(inner / 4)), make_fastdiv((unsigned)C), op);
-                else
-                    hipLaunchKernelGGL((binary_channel4_kernel<Op, false, false, 1>), dim3(gs), dim3(kBlock), 0, state().stream, a, b, out, (unsigned)n4,
-                                       (unsigned)C, make_fastdiv((unsigned)(inner / 4)), make_fastdiv((unsigned)C), op);
-                return PVHIP_OK;
-            }
-            hipLaunchKernelGGL((binary_channel_kernel<Op, false>), dim3(g), dim3(kBlock), 0, state().stream, a, b, out,
-                               (unsigned)n4, (unsigned)n, (unsigned)C, (unsigned)inner, op);
-            return PVHIP_OK;
-        }
-        if (b_full && channel_pattern(rank, shape, as, &C, &inner)) {
-            // the broadcast operand is `a`: stream b, keep operand order for non-commutative ops
-            const int g = grid_for(n4 > 0 ? n4 : 1);
-            if (inner % 4 == 0 && n % 4 == 0 && n < (1ull << 31)) {
-                const bool     nt   = stream_nt(n * 8);
-                const unsigned runs = (unsigned)((n4 + 4 * kBlock - 1) / (4 * kBlock)), cap = (unsigned)(kNumCU * 2 * settings().stream_wg);
-                const int      gs   = nt ? (int)(runs < cap ? runs : cap) : stream_grid(n4);
-#define PV_CH4(SWAP_, NT_, U_)                                                                                                  \
-    hipLaunchKernelGGL((binary_channel4_kernel<Op, SWAP_, NT_, U_>), dim3(gs), dim3(kBlock), 0, state().stream, b, a, out, (unsigned)n4, \
-                       (unsigned)C, make_fastdiv((unsigned)(inner / 4)), make_fastdiv((unsigned)C), op)
-                if (commutative) { if (nt) PV_CH4(false, true, 4); else PV_CH4(false, false, 1); }
-                else             { if (nt) PV_CH4(true, true, 4); else PV_CH4(true, false, 1); }
+    if (p.kind == PVHIP_BINARY_CHANNEL4) {
+#define PV_CH4(SWAP_, NT_, U_)                                                                                                     \
+    hipLaunchKernelGGL((binary_channel4_kernel<Op, SWAP_, NT_, U_>), dim3(p.grid), dim3(kBlock), 0, st, full, vec, out, (unsigned)n4, \
+                       (unsigned)p.C, make_fastdiv((unsigned)(p.inner / 4)), make_fastdiv((unsigned)p.C), op)
+        if (p.swap) { if (p.nt) PV_CH4(true, true, 4); else PV_CH4(true, false, 1); }
+        else        { if (p.nt) PV_CH4(false, true, 4); else PV_CH4(false, false, 1); }
 #undef PV_CH4
-                return PVHIP_OK;
-            }
-            if (commutative)
-                hipLaunchKernelGGL((binary_channel_kernel<Op, false>), dim3(g), dim3(kBlock), 0, state().stream, b, a, out,
-                                   (unsigned)n4, (unsigned)n, (unsigned)C, (unsigned)inner, op);
-            else
-                hipLaunchKernelGGL((binary_channel_kernel<Op, true>), dim3(g), dim3(kBlock), 0, state().stream, b, a, out,
-                                   (unsigned)n4, (unsigned)n, (unsigned)C, (unsigned)inner, op);
-            return PVHIP_OK;
-        }
+        return PVHIP_OK;
+    }
+    if (p.kind == PVHIP_BINARY_CHANNEL) {
+        if (p.swap)
+            hipLaunchKernelGGL((binary_channel_kernel<Op, true>), dim3(p.grid), dim3(kBlock), 0, st, full, vec, out,
+                               (unsigned)n4, (unsigned)n, (unsigned)p.C, (unsigned)p.inner, op);
+        else
+            hipLaunchKernelGGL((binary_channel_kernel<Op, false>), dim3(p.grid), dim3(kBlock), 0, st, full, vec, out,
+                               (unsigned)n4, (unsigned)n, (unsigned)p.C, (unsigned)p.inner, op);
+        return PVHIP_OK;
     }
     StridedArgs s;
     s.rank = rank;
@@ -331,7 +381,7 @@ int launch_binary(const char* who, const float* a, const float* b, float* out, i
         s.as[d]    = d < rank ? as[d] : 0;
         s.bs[d]    = d < rank ? bs[d] : 0;
     }
-    hipLaunchKernelGGL(binary_strided_kernel<Op>, dim3(grid_for(n)), dim3(kBlock), 0, state().stream, a, b, out, n, s, op);
+    hipLaunchKernelGGL(binary_strided_kernel<Op>, dim3(p.grid), dim3(kBlock), 0, st, a, b, out, n, s, op);
     return PVHIP_OK;
 }
 
@@ -385,5 +435,62 @@ int pvhip_mul_f32(const float* a, const float* b, float* out, int rank, const in
     PVHIP_LAUNCH_CHECK();
     return PVHIP_OK;
 }
+
+int pvhip_unary_form(size_t n, int* form) {
+    PVHIP_CHECK_ARG(form != nullptr);
+    for (int i = 0; i < PVHIP_FORM_INTS; ++i) form[i] = 0;
+    form[PVHIP_UNARY_FORM_KIND] = PVHIP_FORM_NONE;
+    if (n == 0) return PVHIP_OK;                                     // nothing is launched
+    const UnaryPlan p     = plan_unary(n);
+    const size_t    n4    = n / 4, run = (size_t)p.u * kBlock, nruns = n4 / run;
+    form[PVHIP_UNARY_FORM_KIND]  = PVHIP_UNARY_F4;
+    form[PVHIP_UNARY_FORM_NT]    = p.nt ? 1 : 0;
+    form[PVHIP_UNARY_FORM_U]     = p.u;
+    form[PVHIP_UNARY_FORM_GRID]  = (int)p.grid;
+    form[PVHIP_UNARY_FORM_RUNS]  = nruns > 0 ? 1 : 0;
+    form[PVHIP_UNARY_FORM_REM4]  = n4 % run != 0 ? 1 : 0;
+    form[PVHIP_UNARY_FORM_TAIL]  = n % 4 != 0 ? 1 : 0;
+    form[PVHIP_UNARY_FORM_WRAPS] = nruns > (size_t)p.grid ? 1 : 0;
+    return PVHIP_OK;
+}
+
+int pvhip_binary_form(int rank, const int64_t* shape, const int64_t* a_strides, const int64_t* b_strides, int commutative, int* form) {
+    PVHIP_CHECK_ARG(form != nullptr);
+    for (int i = 0; i < PVHIP_FORM_INTS; ++i) form[i] = 0;
+    form[PVHIP_BINARY_FORM_KIND] = PVHIP_FORM_NONE;
+    PVHIP_CHECK_ARG(rank == 0 || (shape && a_strides && b_strides));
+    size_t    n  = 0;
+    const int rc = binary_count("pvhip_binary_form", rank, shape, &n);
+    if (rc) return rc;
+    if (n == 0) return PVHIP_OK;                                     // nothing is launched
+    const BinaryPlan p = plan_binary(rank, shape, a_strides, b_strides, n, commutative != 0);
+    form[PVHIP_BINARY_FORM_KIND]  = p.kind;
+    form[PVHIP_BINARY_FORM_BCAST] = p.bcast;
+    form[PVHIP_BINARY_FORM_SWAP]  = p.swap ? 1 : 0;
+    form[PVHIP_BINARY_FORM_NT]    = p.nt ? 1 : 0;
+    form[PVHIP_BINARY_FORM_C]     = (int)p.C;
+    form[PVHIP_BINARY_FORM_INNER] = (int)p.inner;
+    form[PVHIP_BINARY_FORM_GRID]  = p.grid;
+    return PVHIP_OK;
+}
+
+#ifdef PVHIP_DIAG   // diagnostic build only (include/pvhip_diag.h): not in the product library
+// out = a - b through launch_binary with commutative = false: the kSwap instantiations of the channel kernels, which no entry of
+// the product reaches while Add and Multiply are its only binary ops (tests/diag_variants.py).  A second op functor, not a kernel.
+namespace {
+struct SubOp {
+    __device__ __forceinline__ float operator()(float a, float b) const { return a - b; }
+};
+}  // namespace
+int pvhip_diag_sub_f32(const float* a, const float* b, float* out, int rank, const int64_t* shape,
+                       const int64_t* a_strides, const int64_t* b_strides) {
+    PVHIP_REQUIRE_INIT();
+    PVHIP_CHECK_ARG(a && b && out && (rank == 0 || (shape && a_strides && b_strides)));
+    int rc = launch_binary<SubOp>("pvhip_diag_sub_f32", a, b, out, rank, shape, a_strides, b_strides, false);
+    if (rc) return rc;
+    PVHIP_LAUNCH_CHECK();
+    return PVHIP_OK;
+}
+#endif  // PVHIP_DIAG
 
 }  // extern "C"

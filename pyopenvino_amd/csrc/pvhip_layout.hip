@@ -75,19 +75,58 @@ __global__ __launch_bounds__(kBlock) void nhwc_to_nchw_kernel(const T* __restric
 
 constexpr size_t kTileBytes = 16384;     // LDS per workgroup at most (ten workgroups per CU still fit)
 
+// What pvhip_input_to_nchw_f32 launches for a geometry and the two addresses modulo 16 (the entry switches on it, pvhip_input_to_nchw_form
+// reports it).  U8_LINEAR: n4 words through the vector loop; NHWC: the tile, the two 16-byte forms and the grid.
+struct InputPlan {
+    int      kind = PVHIP_FORM_NONE;
+    size_t   n4 = 0;
+    unsigned tile = 0, gx = 0, gy = 0;
+    bool     vl = false, vs = false;
+};
+InputPlan plan_input(int n, int c, size_t p, bool src_u8, bool src_nhwc, unsigned src_align, unsigned dst_align) {
+    InputPlan    q;
+    const size_t total = (size_t)n * (size_t)c * p;
+    if (!src_nhwc && !src_u8) {
+        q.kind = PVHIP_INPUT_COPY;
+        return q;
+    }
+    if (!src_nhwc) {
+        const bool vec = (src_align % 4 == 0) && (dst_align % 16 == 0);
+        q.kind = PVHIP_INPUT_U8_LINEAR;
+        q.n4   = vec ? total / 4 : 0;
+        const size_t work = q.n4 > 0 ? q.n4 : total, blocks = (work + kBlock - 1) / kBlock;
+        q.gx = (unsigned)(blocks < ((size_t)1 << 30) ? blocks : ((size_t)1 << 30));
+        q.gy = 1;
+        return q;
+    }
+    const size_t es = src_u8 ? 1 : sizeof(float);
+    q.kind = PVHIP_INPUT_NHWC;
+    q.tile = 1024;                       // 1024 pixels: one float4 per lane and channel
+    while (q.tile > 1 && q.tile * (size_t)c * es > kTileBytes) q.tile >>= 1;
+    q.vl = (src_align % 16 == 0) && (p * c * es) % 16 == 0 && ((size_t)q.tile * c * es) % 16 == 0;
+    q.vs = (dst_align % 16 == 0) && p % 4 == 0 && q.tile % 4 == 0;
+    q.gx = (unsigned)((p + q.tile - 1) / q.tile);
+    q.gy = (unsigned)n;
+    return q;
+}
+
 template <typename T>
-int launch_nhwc(const T* x, float* y, int n, int c, unsigned p, hipStream_t st) {
-    const size_t es = sizeof(T);
-    unsigned tile = 1024;                // 1024 pixels: one float4 per lane and channel
-    while (tile > 1 && tile * (size_t)c * es > kTileBytes) tile >>= 1;
-    const bool vl = ((uintptr_t)x % 16 == 0) && ((size_t)p * c * es) % 16 == 0 && ((size_t)tile * c * es) % 16 == 0;
-    const bool vs = ((uintptr_t)y % 16 == 0) && p % 4 == 0 && tile % 4 == 0;
-    const dim3 grid((p + tile - 1) / tile, (unsigned)n);
-    const size_t lds = (size_t)tile * c * es;
-    if (vl && vs)  hipLaunchKernelGGL((nhwc_to_nchw_kernel<T, true, true>), grid, dim3(kBlock), lds, st, x, y, c, p, tile);
-    else if (vl)   hipLaunchKernelGGL((nhwc_to_nchw_kernel<T, true, false>), grid, dim3(kBlock), lds, st, x, y, c, p, tile);
-    else if (vs)   hipLaunchKernelGGL((nhwc_to_nchw_kernel<T, false, true>), grid, dim3(kBlock), lds, st, x, y, c, p, tile);
-    else           hipLaunchKernelGGL((nhwc_to_nchw_kernel<T, false, false>), grid, dim3(kBlock), lds, st, x, y, c, p, tile);
+int launch_nhwc(const InputPlan& q, const T* x, float* y, int c, unsigned p, hipStream_t st) {
+    const dim3     grid(q.gx, q.gy);
+    const unsigned tile = q.tile;
+    const size_t   lds  = (size_t)tile * c * sizeof(T);
+    if (q.vl && q.vs) hipLaunchKernelGGL((nhwc_to_nchw_kernel<T, true, true>), grid, dim3(kBlock), lds, st, x, y, c, p, tile);
+    else if (q.vl)    hipLaunchKernelGGL((nhwc_to_nchw_kernel<T, true, false>), grid, dim3(kBlock), lds, st, x, y, c, p, tile);
+    else if (q.vs)    hipLaunchKernelGGL((nhwc_to_nchw_kernel<T, false, true>), grid, dim3(kBlock), lds, st, x, y, c, p, tile);
+    else              hipLaunchKernelGGL((nhwc_to_nchw_kernel<T, false, false>), grid, dim3(kBlock), lds, st, x, y, c, p, tile);
+    return PVHIP_OK;
+}
+
+// The argument checks of the entry that do not look at the pointers.
+int check_input_geometry(const char* who, int n, int c, int h, int w, int src_nhwc) {
+    PVHIP_CHECK_ARG_AS(who, n > 0 && c > 0 && h > 0 && w > 0 && n <= 65535);
+    PVHIP_CHECK_ARG_AS(who, (size_t)h * (size_t)w * (size_t)c < ((size_t)1 << 31));       // one image's elements index in 32 bits
+    if (src_nhwc) PVHIP_CHECK_ARG_AS(who, c <= 4096);          // one pixel's channels fit the LDS tile
     return PVHIP_OK;
 }
 
@@ -98,28 +137,42 @@ extern "C" {
 int pvhip_input_to_nchw_f32(const void* src, float* dst, int n, int c, int h, int w, int src_u8, int src_nhwc) {
     PVHIP_REQUIRE_INIT();
     PVHIP_CHECK_ARG(src != nullptr && dst != nullptr);
-    PVHIP_CHECK_ARG(n > 0 && c > 0 && h > 0 && w > 0 && n <= 65535);
+    const int rc = check_input_geometry("pvhip_input_to_nchw_f32", n, c, h, w, src_nhwc);
+    if (rc) return rc;
     const size_t p = (size_t)h * (size_t)w;
-    PVHIP_CHECK_ARG(p * (size_t)c < ((size_t)1 << 31));       // one image's elements index in 32 bits
     const size_t total = (size_t)n * (size_t)c * p;
     hipStream_t st = state().stream;
-    if (src_nhwc) PVHIP_CHECK_ARG(c <= 4096);                  // one pixel's channels fit the LDS tile
-    if (!src_nhwc && !src_u8) {         // nothing to convert
+    const InputPlan q = plan_input(n, c, p, src_u8 != 0, src_nhwc != 0, (unsigned)((uintptr_t)src % 16), (unsigned)((uintptr_t)dst % 16));
+    if (q.kind == PVHIP_INPUT_COPY) {   // nothing to convert
         PVHIP_HIP(hipMemcpyAsync(dst, src, total * sizeof(float), hipMemcpyDeviceToDevice, st));
         return PVHIP_OK;
     }
-    if (!src_nhwc) {
-        const bool vec = ((uintptr_t)src % 4 == 0) && ((uintptr_t)dst % 16 == 0);
-        const size_t n4 = vec ? total / 4 : 0;
-        const size_t work = n4 > 0 ? n4 : total, blocks = (work + kBlock - 1) / kBlock;
-        hipLaunchKernelGGL(u8_to_f32_kernel, dim3((unsigned)(blocks < ((size_t)1 << 30) ? blocks : ((size_t)1 << 30))), dim3(kBlock), 0, st,
-                           (const unsigned char*)src, dst, n4, total);
+    if (q.kind == PVHIP_INPUT_U8_LINEAR) {
+        hipLaunchKernelGGL(u8_to_f32_kernel, dim3(q.gx), dim3(kBlock), 0, st, (const unsigned char*)src, dst, q.n4, total);
     } else if (src_u8) {
-        launch_nhwc((const unsigned char*)src, dst, n, c, (unsigned)p, st);
+        launch_nhwc(q, (const unsigned char*)src, dst, c, (unsigned)p, st);
     } else {
-        launch_nhwc((const float*)src, dst, n, c, (unsigned)p, st);
+        launch_nhwc(q, (const float*)src, dst, c, (unsigned)p, st);
     }
     PVHIP_LAUNCH_CHECK();
+    return PVHIP_OK;
+}
+
+int pvhip_input_to_nchw_form(int n, int c, int h, int w, int src_u8, int src_nhwc, int src_align, int dst_align, int* form) {
+    PVHIP_CHECK_ARG(form != nullptr);
+    for (int i = 0; i < PVHIP_FORM_INTS; ++i) form[i] = 0;
+    form[PVHIP_INPUT_FORM_KIND] = PVHIP_FORM_NONE;
+    PVHIP_CHECK_ARG(src_align >= 0 && src_align < 16 && dst_align >= 0 && dst_align < 16);
+    const int rc = check_input_geometry("pvhip_input_to_nchw_form", n, c, h, w, src_nhwc);
+    if (rc) return rc;
+    const InputPlan q = plan_input(n, c, (size_t)h * (size_t)w, src_u8 != 0, src_nhwc != 0, (unsigned)src_align, (unsigned)dst_align);
+    form[PVHIP_INPUT_FORM_KIND]   = q.kind;
+    form[PVHIP_INPUT_FORM_VEC]    = q.n4 > 0 ? 1 : 0;
+    form[PVHIP_INPUT_FORM_TILE]   = (int)q.tile;
+    form[PVHIP_INPUT_FORM_VL]     = q.vl ? 1 : 0;
+    form[PVHIP_INPUT_FORM_VS]     = q.vs ? 1 : 0;
+    form[PVHIP_INPUT_FORM_GRID_X] = (int)q.gx;
+    form[PVHIP_INPUT_FORM_GRID_Y] = (int)q.gy;
     return PVHIP_OK;
 }
 

@@ -101,21 +101,25 @@ __global__ __launch_bounds__(kBlock) void matmul_reduce_kernel(const float* __re
 
 namespace pvhip {
 
-int matmul_impl(const float* a, const float* b, float* c, int m, int n, int k, int trans_a, int trans_b, int round_f16) {
-    PVHIP_REQUIRE_INIT();
-    PVHIP_CHECK_ARG(m >= 0 && n >= 0 && k >= 0);
+// What a launch of these extents does: nothing (an empty output), a memset (k == 0), one launch, or split-K plus the reduction.
+// matmul_impl switches on it and pvhip_matmul_form reports it.  PVHIP_EUNSUPPORTED when M has more tiles than grid.y holds.
+struct MatMulPlan {
+    int  kind = PVHIP_FORM_NONE;
+    dim3 grid;
+    int  splits = 0, k_chunk = 0;
+    long sam = 0, sak = 0, sbk = 0, sbn = 0;
+};
+
+int plan_matmul(int m, int n, int k, int trans_a, int trans_b, MatMulPlan& q) {
     if ((size_t)m * n == 0) return PVHIP_OK;
-    PVHIP_CHECK_ARG(c != nullptr && (k == 0 || (a != nullptr && b != nullptr)));
-    if (k == 0) return pvhip_memset(c, 0, (size_t)m * n * sizeof(float));
-    MatMulArgs p;
-    p.a = a; p.b = b; p.c = c; p.M = m; p.N = n; p.K = k;
-    if (trans_a) { p.sam = 1; p.sak = m; } else { p.sam = k; p.sak = 1; }   // stored [K,M] / [M,K]
-    if (trans_b) { p.sbk = 1; p.sbn = k; } else { p.sbk = n; p.sbn = 1; }   // stored [N,K] / [K,N]
-    dim3 grid((n + kTN - 1) / kTN, (m + kTM - 1) / kTM, 1);
-    if (grid.y > 65535) return fail(PVHIP_EUNSUPPORTED, "pvhip_matmul: M=%d too large for the tile grid", m);
+    if (k == 0) { q.kind = PVHIP_MATMUL_MEMSET; return PVHIP_OK; }
+    if (trans_a) { q.sam = 1; q.sak = m; } else { q.sam = k; q.sak = 1; }   // stored [K,M] / [M,K]
+    if (trans_b) { q.sbk = 1; q.sbn = k; } else { q.sbk = n; q.sbn = 1; }   // stored [N,K] / [K,N]
+    q.grid = dim3((n + kTN - 1) / kTN, (m + kTM - 1) / kTM, 1);
+    if (q.grid.y > 65535) return fail(PVHIP_EUNSUPPORTED, "pvhip_matmul: M=%d too large for the tile grid", m);
     // Split the reduction over workgroups when the output has too few tiles to fill the chip (the FC layers
     // of the IRs: 64 tiles at batch 256); partial tiles go to a workspace and are summed in split order.
-    const long tiles  = (long)grid.x * grid.y;
+    const long tiles  = (long)q.grid.x * q.grid.y;
     int        splits = 1;
     if (tiles < 2 * kNumCU) {
         splits = (int)((4 * kNumCU + tiles - 1) / tiles);
@@ -123,24 +127,46 @@ int matmul_impl(const float* a, const float* b, float* c, int m, int n, int k, i
         if (splits > max_splits) splits = max_splits;
         if (splits < 1) splits = 1;
     }
-    p.k_chunk = ((k + splits - 1) / splits + kTK - 1) / kTK * kTK;
-    splits    = (k + p.k_chunk - 1) / p.k_chunk;
-    if (splits <= 1) {
-        p.k_chunk = (k + kTK - 1) / kTK * kTK;
-        if (round_f16) hipLaunchKernelGGL(matmul_kernel<true>, grid, dim3(kBlock), 0, state().stream, p);
-        else           hipLaunchKernelGGL(matmul_kernel<false>, grid, dim3(kBlock), 0, state().stream, p);
+    q.k_chunk = ((k + splits - 1) / splits + kTK - 1) / kTK * kTK;
+    q.splits  = (k + q.k_chunk - 1) / q.k_chunk;
+    if (q.splits <= 1) {
+        q.kind    = PVHIP_MATMUL_SINGLE;
+        q.splits  = 1;
+        q.k_chunk = (k + kTK - 1) / kTK * kTK;
+        return PVHIP_OK;
+    }
+    q.kind   = PVHIP_MATMUL_SPLIT;
+    q.grid.z = q.splits;
+    return PVHIP_OK;
+}
+
+int matmul_impl(const float* a, const float* b, float* c, int m, int n, int k, int trans_a, int trans_b, int round_f16) {
+    PVHIP_REQUIRE_INIT();
+    PVHIP_CHECK_ARG(m >= 0 && n >= 0 && k >= 0);
+    if ((size_t)m * n == 0) return PVHIP_OK;
+    PVHIP_CHECK_ARG(c != nullptr && (k == 0 || (a != nullptr && b != nullptr)));
+    MatMulPlan q;
+    int        rc = plan_matmul(m, n, k, trans_a, trans_b, q);
+    if (rc) return rc;
+    if (q.kind == PVHIP_MATMUL_MEMSET) return pvhip_memset(c, 0, (size_t)m * n * sizeof(float));
+    MatMulArgs p;
+    p.a = a; p.b = b; p.c = c; p.M = m; p.N = n; p.K = k;
+    p.sam = q.sam; p.sak = q.sak; p.sbk = q.sbk; p.sbn = q.sbn;
+    p.k_chunk = q.k_chunk;
+    if (q.kind == PVHIP_MATMUL_SINGLE) {
+        if (round_f16) hipLaunchKernelGGL(matmul_kernel<true>, q.grid, dim3(kBlock), 0, state().stream, p);
+        else           hipLaunchKernelGGL(matmul_kernel<false>, q.grid, dim3(kBlock), 0, state().stream, p);
         PVHIP_LAUNCH_CHECK();
         return PVHIP_OK;
     }
     void* ws = nullptr;
-    int   rc = pvhip_malloc(&ws, (size_t)splits * m * n * sizeof(float));
+    rc = pvhip_malloc(&ws, (size_t)q.splits * m * n * sizeof(float));
     if (rc) return rc;
-    p.c    = static_cast<float*>(ws);
-    grid.z = splits;
-    if (round_f16) hipLaunchKernelGGL(matmul_kernel<true>, grid, dim3(kBlock), 0, state().stream, p);
-    else           hipLaunchKernelGGL(matmul_kernel<false>, grid, dim3(kBlock), 0, state().stream, p);
+    p.c = static_cast<float*>(ws);
+    if (round_f16) hipLaunchKernelGGL(matmul_kernel<true>, q.grid, dim3(kBlock), 0, state().stream, p);
+    else           hipLaunchKernelGGL(matmul_kernel<false>, q.grid, dim3(kBlock), 0, state().stream, p);
     hipLaunchKernelGGL(matmul_reduce_kernel, dim3(grid_for((size_t)m * n)), dim3(kBlock), 0, state().stream,
-                       static_cast<const float*>(ws), c, (size_t)m * n, splits);
+                       static_cast<const float*>(ws), c, (size_t)m * n, q.splits);
     (void)pvhip_free(ws);   // stream-ordered: the pool hands the block out again only to later work on this stream
     PVHIP_LAUNCH_CHECK();
     return PVHIP_OK;
@@ -152,6 +178,27 @@ extern "C" {
 
 int pvhip_matmul_f32(const float* a, const float* b, float* c, int m, int n, int k, int trans_a, int trans_b) {
     return pvhip::matmul_impl(a, b, c, m, n, k, trans_a, trans_b, 0);
+}
+
+int pvhip_matmul_form(int m, int n, int k, int trans_a, int trans_b, int f16, int* form) {
+    PVHIP_CHECK_ARG(form != nullptr);
+    for (int i = 0; i < PVHIP_FORM_INTS; ++i) form[i] = 0;
+    form[PVHIP_MATMUL_FORM_KIND] = PVHIP_FORM_NONE;
+    PVHIP_CHECK_ARG(m >= 0 && n >= 0 && k >= 0);
+    pvhip::MatMulPlan q;
+    const int rc = pvhip::plan_matmul(m, n, k, trans_a, trans_b, q);
+    if (rc) return rc;
+    form[PVHIP_MATMUL_FORM_KIND] = q.kind;
+    if (q.kind == PVHIP_FORM_NONE || q.kind == PVHIP_MATMUL_MEMSET) return PVHIP_OK;
+    form[PVHIP_MATMUL_FORM_GRID_X]   = (int)q.grid.x;
+    form[PVHIP_MATMUL_FORM_GRID_Y]   = (int)q.grid.y;
+    form[PVHIP_MATMUL_FORM_SPLITS]   = q.splits;
+    form[PVHIP_MATMUL_FORM_K_CHUNK]  = q.k_chunk;
+    form[PVHIP_MATMUL_FORM_LAST_K]   = k - (q.splits - 1) * q.k_chunk;
+    form[PVHIP_MATMUL_FORM_A_K_FAST] = q.sak == 1 ? 1 : 0;
+    form[PVHIP_MATMUL_FORM_B_N_FAST] = q.sbn == 1 ? 1 : 0;
+    form[PVHIP_MATMUL_FORM_F16]      = f16 ? 1 : 0;
+    return PVHIP_OK;
 }
 
 }  // extern "C"

@@ -68,26 +68,58 @@ __global__ __launch_bounds__(kBlock) void transpose_kernel(const float* __restri
     }
 }
 
-}  // namespace
-
-extern "C" {
-
-int pvhip_concat_f32(int n_src, const float* const* srcs, const int64_t* inner, float* dst, int64_t outer) {
-    PVHIP_REQUIRE_INIT();
-    PVHIP_CHECK_ARG(n_src >= 1 && n_src <= PVHIP_MAX_CONCAT && srcs != nullptr && inner != nullptr && outer >= 0);
+// The copy unit and grid of a Concat launch (pvhip_concat_f32 switches on it, pvhip_concat_form reports it); kind stays
+// PVHIP_FORM_NONE for an empty output.  Argument errors and the 2^31 refusal are the entry's own.
+struct ConcatPlan {
+    int kind = PVHIP_FORM_NONE, gx = 0, gy = 0;
+};
+int plan_concat(const char* who, int n_src, const int64_t* inner, int64_t outer, ConcatPlan& p) {
+    PVHIP_CHECK_ARG_AS(who, n_src >= 1 && n_src <= PVHIP_MAX_CONCAT && inner != nullptr && outer >= 0);
     int64_t total = 0, max_inner = 0;
     bool    vec4  = true;
     for (int i = 0; i < n_src; ++i) {
-        PVHIP_CHECK_ARG(inner[i] >= 0);
+        PVHIP_CHECK_ARG_AS(who, inner[i] >= 0);
         if (inner[i] % 4 != 0) vec4 = false;
         total += inner[i];
         if (inner[i] > max_inner) max_inner = inner[i];
     }
     if (total == 0 || outer == 0) return PVHIP_OK;
-    PVHIP_CHECK_ARG(dst != nullptr);
     if ((unsigned long long)total * (unsigned long long)outer >= (1ull << 31))
-        return fail(PVHIP_EUNSUPPORTED, "pvhip_concat_f32: tensor exceeds 2^31 elements");
-    const unsigned div = vec4 ? 4u : 1u;
+        return fail(PVHIP_EUNSUPPORTED, "%s: tensor exceeds 2^31 elements", who);
+    p.kind = vec4 ? PVHIP_CONCAT_VEC4 : PVHIP_CONCAT_SCALAR;
+    p.gx   = grid_for((size_t)(max_inner / (vec4 ? 4 : 1)) * (size_t)outer);
+    p.gy   = n_src;
+    return PVHIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pvhip_concat_form(int n_src, const int64_t* inner, int64_t outer, int* form) {
+    PVHIP_CHECK_ARG(form != nullptr);
+    for (int i = 0; i < PVHIP_FORM_INTS; ++i) form[i] = 0;
+    form[PVHIP_CONCAT_FORM_KIND] = PVHIP_FORM_NONE;
+    ConcatPlan p;
+    const int  rc = plan_concat("pvhip_concat_form", n_src, inner, outer, p);
+    if (rc) return rc;
+    form[PVHIP_CONCAT_FORM_KIND] = p.kind;
+    if (p.kind == PVHIP_FORM_NONE) return PVHIP_OK;
+    form[PVHIP_CONCAT_FORM_GRID_X] = p.gx;
+    form[PVHIP_CONCAT_FORM_GRID_Y] = p.gy;
+    return PVHIP_OK;
+}
+
+int pvhip_concat_f32(int n_src, const float* const* srcs, const int64_t* inner, float* dst, int64_t outer) {
+    PVHIP_REQUIRE_INIT();
+    PVHIP_CHECK_ARG(srcs != nullptr);
+    ConcatPlan plan;
+    const int  rc = plan_concat("pvhip_concat_f32", n_src, inner, outer, plan);
+    if (rc) return rc;
+    if (plan.kind == PVHIP_FORM_NONE) return PVHIP_OK;
+    PVHIP_CHECK_ARG(dst != nullptr);
+    const bool     vec4 = plan.kind == PVHIP_CONCAT_VEC4;
+    const unsigned div  = vec4 ? 4u : 1u;
     ConcatArgs     a;
     a.n_src        = n_src;
     unsigned off   = 0;
@@ -104,13 +136,11 @@ int pvhip_concat_f32(int n_src, const float* const* srcs, const int64_t* inner, 
     }
     a.total_inner = off;
     a.outer       = (unsigned)outer;
-    const size_t work = (size_t)(max_inner / div) * (size_t)outer;
-    const int    gx   = grid_for(work);
     if (vec4)
-        hipLaunchKernelGGL(concat_kernel<float4>, dim3(gx, n_src), dim3(kBlock), 0, state().stream, a,
+        hipLaunchKernelGGL(concat_kernel<float4>, dim3(plan.gx, plan.gy), dim3(kBlock), 0, state().stream, a,
                            reinterpret_cast<float4*>(dst));
     else
-        hipLaunchKernelGGL(concat_kernel<float>, dim3(gx, n_src), dim3(kBlock), 0, state().stream, a, dst);
+        hipLaunchKernelGGL(concat_kernel<float>, dim3(plan.gx, plan.gy), dim3(kBlock), 0, state().stream, a, dst);
     PVHIP_LAUNCH_CHECK();
     return PVHIP_OK;
 }

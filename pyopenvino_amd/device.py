@@ -70,6 +70,11 @@ SIGNATURES = {
     'pvhip_sigmoid_f32': (_c.c_int, [_fp, _fp, _c.c_size_t]),
     'pvhip_add_f32': (_c.c_int, [_fp, _fp, _fp, _c.c_int, _i64p, _i64p, _i64p]),
     'pvhip_mul_f32': (_c.c_int, [_fp, _fp, _fp, _c.c_int, _i64p, _i64p, _i64p]),
+    'pvhip_unary_form': (_c.c_int, [_c.c_size_t, _c.POINTER(_c.c_int)]),
+    'pvhip_binary_form': (_c.c_int, [_c.c_int, _i64p, _i64p, _i64p, _c.c_int, _c.POINTER(_c.c_int)]),
+    'pvhip_concat_form': (_c.c_int, [_c.c_int, _i64p, _c.c_int64, _c.POINTER(_c.c_int)]),
+    'pvhip_matmul_form': (_c.c_int, [_c.c_int] * 6 + [_c.POINTER(_c.c_int)]),
+    'pvhip_input_to_nchw_form': (_c.c_int, [_c.c_int] * 8 + [_c.POINTER(_c.c_int)]),
     'pvhip_maxpool2d_f32': (_c.c_int, [_fp, _fp] + [_c.c_int] * 14),
     'pvhip_avgpool2d_f32': (_c.c_int, [_fp, _fp] + [_c.c_int] * 10),
     'pvhip_softmax_rows_f32': (_c.c_int, [_fp, _fp, _c.c_int, _c.c_int]),

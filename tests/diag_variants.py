@@ -1,6 +1,7 @@
 """Tests of what exists in the DIAGNOSTIC build only (libpvhip_diag.so: make -C pyopenvino_amd/csrc diag; include/pvhip_diag.h): the
 predecessor convolution kernels kept for A/B runs (PVHIP_CONV_KERNEL=lds|wave, every PVHIP_CONV_TILE / PVHIP_CONV_WTILE), the opt-in
-16-byte gather (PVHIP_CONV_PW) and the fp32-MFMA ceiling probe.  NOT collected by `pytest tests/` (the file name does not match
+16-byte gather (PVHIP_CONV_PW), the fp32-MFMA ceiling probe, and the subtract that reaches the kSwap instantiations of the binary channel
+kernels (pvhip_diag_sub_f32; the rows are tests/test_light_op_forms.py's SUB_ROWS).  NOT collected by `pytest tests/` (the file name does not match
 test_*.py): tests/test_hip_ops.py::test_diagnostic_build_variants_in_their_own_process runs it in a process of its own with
 PVHIP_LIBRARY=pyopenvino_amd/libpvhip_diag.so, so that the main test process only ever loads the product library.  GPU only.
 
@@ -133,3 +134,29 @@ def test_conv_fused_bias_and_activation_bit_exact(hip, monkeypatch):
             got = first_out(hip_plugin(type_).compute(fused_node, {0: x, 1: w}))
             assert_bit_exact(got, want, '{} fused bias + {}'.format(type_, act[0]))
 
+
+
+def test_subtract_reaches_the_swapped_channel_kernels(hip):
+    """binary_channel_kernel<Op, true> and binary_channel4_kernel<Op, true, ...> put the operands of a non-commutative op back in order when
+    the FIRST operand is the broadcast one.  Add and Multiply never take them (both are commutative), and through either nothing could
+    tell a swapped launch from an unswapped one: pvhip_diag_sub_f32 (a - b as a non-commutative op on the product's kernels) can -- b - a
+    is another tensor.  The rows are tests/test_light_op_forms.py's SUB_ROWS; each is also launched the other way round (the broadcast
+    operand second: the unswapped instantiation with the same functor), against a - b in float64, bit for bit."""
+    import ctypes
+    import test_light_op_forms as forms
+    lib = hip.load_library()
+    lib.pvhip_diag_sub_f32.restype = ctypes.c_int
+    lib.pvhip_diag_sub_f32.argtypes = hip.SIGNATURES['pvhip_add_f32'][1]
+    assert forms.SUB_ROWS
+    for row in forms.SUB_ROWS:
+        assert forms.class_of(row) == row.cls and 'swapped' in row.cls[2], row.id
+        got = forms.launch_binary(hip, row, {'Subtract': 'pvhip_diag_sub_f32'})['Subtract']
+        forms.compare(row, 'Subtract', got, row.id)
+        a, b = forms.inputs(row)
+        wrong = (b.astype(np.float64) - a.astype(np.float64)).astype(np.float32)
+        assert not np.array_equal(got, wrong), row.id + ': the row could not tell the operand order'
+        # the same operands the other way round: b - a with the broadcast operand second
+        other = forms.Row(row.id + '-unswapped', 'binary', None, a=row.kw['b'], b=row.kw['a'], commutative=False)
+        assert 'swapped' not in forms.class_of(other)[2]
+        got = forms.launch_binary(hip, other, {'Subtract': 'pvhip_diag_sub_f32'})['Subtract']
+        forms.compare(other, 'Subtract', got, other.id)

@@ -193,6 +193,54 @@ def matmul(a, b, transpose_a=False, transpose_b=False):
     return (a.T if transpose_a else a) @ (b.T if transpose_b else b)
 
 
+def pad2d(x, pads_begin, pads_end, channel_add=None):
+    """pvhip_pad2d_f32: the zero-padded image Convolution.py:64-66 builds; channel_add (c values) is added to every element of x on the
+    way, never to the padding."""
+    x = _f64(x)
+    if channel_add is not None:
+        x = x + _f64(channel_add).reshape(1, -1, 1, 1)
+    return np.pad(x, [(0, 0), (0, 0), (pads_begin[0], pads_end[0]), (pads_begin[1], pads_end[1])])
+
+
+def u8_to_f32(x):
+    """The widening copy of a U8 input: every uint8 value is an fp32 (and a float64) value."""
+    x = np.asarray(x)
+    assert x.dtype == np.uint8
+    return x.astype(np.float64)
+
+
+def nhwc_to_nchw(x):
+    """(n, h, w, c) uint8 or fp32 -> (n, c, h, w); values are moved, never computed on."""
+    x = np.asarray(x)
+    assert x.ndim == 4 and x.dtype in (np.uint8, np.float32)
+    return np.ascontiguousarray(x.transpose(0, 3, 1, 2)).astype(np.float64)
+
+
+def c8_blocks(c):
+    """Channel blocks of eight of a c8 tensor: whole 16-channel stages (include/pvhip.h pvhip_c8_f16_*)."""
+    return (int(c) + 15) // 16 * 2
+
+
+def c8_pack(x):
+    """pvhip_c8_f16_from_f32 restated: (n, c, h, w) fp32 -> float16 [n][c8_blocks(c)][h * w][8], round to nearest even (numpy's
+    astype(np.float16)), channels c .. 16 * ceil(c / 16) - 1 are +0."""
+    x = np.asarray(x, dtype=np.float32)
+    n, c, h, w = x.shape
+    cb = c8_blocks(c)
+    full = np.zeros((n, cb * 8, h * w), dtype=np.float16)
+    with np.errstate(over='ignore'):
+        full[:, :c] = x.reshape(n, c, h * w).astype(np.float16)
+    return np.ascontiguousarray(full.reshape(n, cb, 8, h * w).transpose(0, 1, 3, 2))
+
+
+def c8_unpack(xb, c):
+    """pvhip_c8_f16_to_f32 restated: the first c channels of a c8 tensor as (n, c, h * w) fp32 (exact: every fp16 value is an fp32 value)."""
+    xb = np.asarray(xb)
+    assert xb.dtype == np.float16 and xb.ndim == 4 and xb.shape[3] == 8
+    n, cb, hw, _ = xb.shape
+    return np.ascontiguousarray(xb.transpose(0, 1, 3, 2).reshape(n, cb * 8, hw)[:, :c]).astype(np.float32)
+
+
 def softmax_rows(x):
     """Per leading-axis row, no max shift."""
     x = _f64(x)

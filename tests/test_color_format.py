@@ -263,9 +263,9 @@ def test_abi_declares_the_yuv_entry():
     header = open(os.path.join(helpers.REPO, 'include', 'pvhip.h')).read()
     assert ENTRY in device.SIGNATURES and ENTRY + '(' in header
     assert len(device.SIGNATURES[ENTRY][1]) == 11
-    assert re.search(r'#define\s+PVHIP_ABI_VERSION\s+18\b', header)
+    assert re.search(r'#define\s+PVHIP_ABI_VERSION\s+19\b', header)
     lib = device.load_library()
-    assert hasattr(lib, ENTRY) and lib.pvhip_abi_version() == 18
+    assert hasattr(lib, ENTRY) and lib.pvhip_abi_version() == 19
 
 
 # ---------------------------------------------------------------------------------------------------------------- GPU

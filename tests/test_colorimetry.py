@@ -257,7 +257,7 @@ def test_abi_declares_and_exports_the_color_entries():
         m = re.search(r'\b' + entry + r'\s*\(([^;]*?)\)\s*;', code, flags=re.S)
         assert m and len(m.group(1).split(',')) == count and ' '.join(m.group(1).split()).endswith('int matrix, int full_range')
         assert hasattr(lib, entry) and re.search(r' T ' + entry + r'\b', nm)
-    assert re.search(r'#define\s+PVHIP_ABI_VERSION\s+18\b', header) and lib.pvhip_abi_version() == 18
+    assert re.search(r'#define\s+PVHIP_ABI_VERSION\s+19\b', header) and lib.pvhip_abi_version() == 19
 
 
 # ---------------------------------------------------------------------------------------------------------------- GPU

@@ -187,9 +187,9 @@ def test_abi_declares_the_entry():
     assert ENTRY in device.SIGNATURES and len(device.SIGNATURES[ENTRY][1]) == 14 and ENTRY not in device._NOT_STATUS
     m = re.search(r'\b' + ENTRY + r'\s*\(([^;]*?)\)\s*;', code, flags=re.S)
     assert m and len(m.group(1).split(',')) == 14
-    assert re.search(r'#define\s+PVHIP_ABI_VERSION\s+18\b', header)
+    assert re.search(r'#define\s+PVHIP_ABI_VERSION\s+19\b', header)
     lib = device.load_library()
-    assert hasattr(lib, ENTRY) and lib.pvhip_abi_version() == 18
+    assert hasattr(lib, ENTRY) and lib.pvhip_abi_version() == 19
     assert pyopenvino_amd.DetectedRois is input_format.DetectedRois and 'DetectedRois' in pyopenvino_amd.__all__
 
 

@@ -268,9 +268,9 @@ def test_abi_declares_the_entry():
     for phrase in ('Addition to ABI v18 (the version number is unchanged', 'min(selected[b], max_per_image)', '(b, x0, y0, w, h, label, score bits, record)',
                    'counts[images], then selected[images], then total', 'tests/detections_ref.py'):
         assert phrase in comment, phrase                       # the rule is stated there
-    assert re.search(r'#define\s+PVHIP_ABI_VERSION\s+18\b', header)
+    assert re.search(r'#define\s+PVHIP_ABI_VERSION\s+19\b', header)
     lib = device.load_library()
-    assert hasattr(lib, ENTRY) and lib.pvhip_abi_version() == 18
+    assert hasattr(lib, ENTRY) and lib.pvhip_abi_version() == 19
     assert pyopenvino_amd.Detections is detections.Detections and pyopenvino_amd.DetectionScreen is detections.DetectionScreen
     assert 'Detections' in pyopenvino_amd.__all__ and 'DetectionScreen' in pyopenvino_amd.__all__
     assert pyopenvino_amd.Detections._fields == ('counts', 'selected', 'rois', 'labels', 'scores', 'records')

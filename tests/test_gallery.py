@@ -339,9 +339,9 @@ def test_abi_declares_the_entry():
     assert re.search(r'#define\s+PVHIP_GALLERY_CHUNK\s+{}\b'.format(C), header) and C % 32 == 0
     assert re.search(r'#define\s+PVHIP_GALLERY_COSINE\s+0\b', header) and re.search(r'#define\s+PVHIP_GALLERY_DOT\s+1\b', header)
     assert gallery_rule.METRICS == {'COSINE': 0, 'DOT': 1}
-    assert re.search(r'#define\s+PVHIP_ABI_VERSION\s+18\b', header)
+    assert re.search(r'#define\s+PVHIP_ABI_VERSION\s+19\b', header)
     lib = device.load_library()
-    assert hasattr(lib, ENTRY) and lib.pvhip_abi_version() == 18
+    assert hasattr(lib, ENTRY) and lib.pvhip_abi_version() == 19
     for name in ('Gallery', 'GalleryMatch', 'Matches'):
         assert name in pyopenvino_amd.__all__ and getattr(pyopenvino_amd, name) is getattr(gallery_rule, name)
     assert Matches._fields == ('counts', 'indices', 'ids', 'scores') and GalleryMatch._fields == ('gallery', 'k', 'min_score')

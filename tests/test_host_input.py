@@ -141,7 +141,7 @@ def test_abi_declares_the_async_upload_and_the_conversion():
     for name in ('pvhip_memcpy_h2d_async', 'pvhip_input_to_nchw_f32', 'pvhip_host_stats'):
         assert name in device.SIGNATURES and name + '(' in header, name
     lib = device.load_library()
-    assert lib.pvhip_abi_version() == 18
+    assert lib.pvhip_abi_version() == 19
     blocks, nbytes = ctypes.c_size_t(7), ctypes.c_size_t(7)
     assert lib.pvhip_host_stats(ctypes.byref(blocks), ctypes.byref(nbytes)) == 0      # no device needed
     assert (blocks.value, nbytes.value) == (0, 0)

@@ -262,9 +262,9 @@ def test_abi_declares_the_fit_entries():
         assert m and len(m.group(1).split(',')) == count, entry
         comment = re.search(r'/\*((?:(?!\*/).)*)\*/\s*(?:int\s+pvhip_\w+\s*\([^;]*;\s*)*int\s+' + entry + r'\b', header, flags=re.S).group(1)
         assert 'Addition to ABI v18 (the version number is unchanged' in comment, entry
-    assert re.search(r'#define\s+PVHIP_ABI_VERSION\s+18\b', header)
+    assert re.search(r'#define\s+PVHIP_ABI_VERSION\s+19\b', header)
     lib = device.load_library()
-    assert all(hasattr(lib, e) for e in ENTRIES + RULE_ENTRIES) and lib.pvhip_abi_version() == 18
+    assert all(hasattr(lib, e) for e in ENTRIES + RULE_ENTRIES) and lib.pvhip_abi_version() == 19
 
 
 # ---------------------------------------------------------------------------------------------------------------- GPU

@@ -362,9 +362,9 @@ def test_abi_declares_the_packed_entries():
         m = re.search(r'\b' + entry + r'\s*\(([^;]*?)\)\s*;', code, flags=re.S)
         assert m and len(m.group(1).split(',')) == count, entry
         assert entry not in device._NOT_STATUS                # a status, like every launch
-    assert re.search(r'#define\s+PVHIP_ABI_VERSION\s+18\b', header)
+    assert re.search(r'#define\s+PVHIP_ABI_VERSION\s+19\b', header)
     lib = device.load_library()
-    assert hasattr(lib, ENTRY) and hasattr(lib, ENTRY_ROI) and lib.pvhip_abi_version() == 18
+    assert hasattr(lib, ENTRY) and hasattr(lib, ENTRY_ROI) and lib.pvhip_abi_version() == 19
 
 
 # ---------------------------------------------------------------------------------------------------------------- GPU

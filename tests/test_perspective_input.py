@@ -340,7 +340,7 @@ def test_abi_declares_the_perspective_entries():
         assert m and len(m.group(1).split(',')) == count and 'const long long* table' in m.group(1) and 'float pad_value' in m.group(1)
         assert hasattr(lib, entry)
     assert 'int matrix' in re.search(ENTRY_COLOR + r'\s*\(([^;]*?)\)\s*;', code, flags=re.S).group(1)
-    assert re.search(r'#define\s+PVHIP_ABI_VERSION\s+18\b', header) and lib.pvhip_abi_version() == 18
+    assert re.search(r'#define\s+PVHIP_ABI_VERSION\s+19\b', header) and lib.pvhip_abi_version() == 19
     import pyopenvino_amd
     from pyopenvino_amd import input_format
     assert pyopenvino_amd.PerspectiveInput is input_format.PerspectiveInput and 'PerspectiveInput' in pyopenvino_amd.__all__

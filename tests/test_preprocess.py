@@ -215,7 +215,7 @@ def test_abi_declares_the_preprocessing_entry():
     name = 'pvhip_input_preprocess_f32'
     assert name in device.SIGNATURES and name + '(' in header
     assert len(device.SIGNATURES[name][1]) == 13
-    assert re.search(r'#define\s+PVHIP_ABI_VERSION\s+18\b', header)
+    assert re.search(r'#define\s+PVHIP_ABI_VERSION\s+19\b', header)
     assert hasattr(device.load_library(), name)
 
 

@@ -393,9 +393,9 @@ def test_abi_declares_the_entry():
                    'never contracted', 'one wholly in the padding is dropped', 'bit for bit', 'tests/regions_ref.py', 'fit in {0, 1, 2}',
                    'net_h, net_w in [1, 2^24] when fit != 0'):
         assert phrase in comment, phrase                       # the rule is stated there
-    assert re.search(r'#define\s+PVHIP_ABI_VERSION\s+18\b', header)
+    assert re.search(r'#define\s+PVHIP_ABI_VERSION\s+19\b', header)
     lib = device.load_library()
-    assert hasattr(lib, ENTRY) and lib.pvhip_abi_version() == 18
+    assert hasattr(lib, ENTRY) and lib.pvhip_abi_version() == 19
     assert pyopenvino_amd.RegionScreen is tiled_detections.RegionScreen and 'RegionScreen' in pyopenvino_amd.__all__
     # the launch that places the pixels and the launch that maps the boxes back share one function
     csrc = os.path.join(helpers.REPO, 'pyopenvino_amd', 'csrc')

@@ -355,9 +355,9 @@ def test_abi_declares_the_entry():
         assert phrase in comment, phrase                       # the rule is stated there
     for kind, value in tiled_detections.OVERLAPS.items():
         assert re.search(r'#define\s+PVHIP_OVERLAP_{}\s+{}\b'.format(kind, value), header)
-    assert re.search(r'#define\s+PVHIP_ABI_VERSION\s+18\b', header)
+    assert re.search(r'#define\s+PVHIP_ABI_VERSION\s+19\b', header)
     lib = device.load_library()
-    assert hasattr(lib, ENTRY) and lib.pvhip_abi_version() == 18
+    assert hasattr(lib, ENTRY) and lib.pvhip_abi_version() == 19
     assert pyopenvino_amd.TiledScreen is tiled_detections.TiledScreen and 'TiledScreen' in pyopenvino_amd.__all__
     makefile = open(os.path.join(helpers.REPO, 'pyopenvino_amd', 'csrc', 'Makefile')).read()
     assert re.search(r'^SRCS\s*:=[^\n]*(\\\n[^\n]*)*pvhip_tiles\.hip', makefile, flags=re.M)

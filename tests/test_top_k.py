@@ -192,9 +192,9 @@ def test_abi_declares_the_entry():
     m = re.search(r'\bint\s+' + ENTRY + r'\s*\(([^;]*?)\)\s*;', code, flags=re.S)
     assert m and len(m.group(1).split(',')) == 6
     assert 'np.lexsort((np.arange(cols), -np.where(isnan, 0, x), ~isnan))[:k]' in header          # the rule is stated there
-    assert re.search(r'#define\s+PVHIP_ABI_VERSION\s+18\b', header)
+    assert re.search(r'#define\s+PVHIP_ABI_VERSION\s+19\b', header)
     lib = device.load_library()
-    assert hasattr(lib, ENTRY) and lib.pvhip_abi_version() == 18
+    assert hasattr(lib, ENTRY) and lib.pvhip_abi_version() == 19
     assert pyopenvino_amd.TopK is top_k.TopK and 'TopK' in pyopenvino_amd.__all__ and pyopenvino_amd.TopK._fields == ('indices', 'values')
 
 

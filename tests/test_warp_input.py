@@ -387,9 +387,9 @@ def test_abi_declares_the_warp_entry():
     assert ENTRY in device.SIGNATURES and len(device.SIGNATURES[ENTRY][1]) == 16 and ENTRY not in device._NOT_STATUS
     m = re.search(r'\b' + ENTRY + r'\s*\(([^;]*?)\)\s*;', code, flags=re.S)
     assert m and len(m.group(1).split(',')) == 16 and 'const long long* table' in m.group(1) and 'float pad_value' in m.group(1)
-    assert re.search(r'#define\s+PVHIP_ABI_VERSION\s+18\b', header)
+    assert re.search(r'#define\s+PVHIP_ABI_VERSION\s+19\b', header)
     lib = device.load_library()
-    assert hasattr(lib, ENTRY) and lib.pvhip_abi_version() == 18
+    assert hasattr(lib, ENTRY) and lib.pvhip_abi_version() == 19
     import pyopenvino_amd
     from pyopenvino_amd import input_format
     assert pyopenvino_amd.WarpInput is input_format.WarpInput and 'WarpInput' in pyopenvino_amd.__all__
