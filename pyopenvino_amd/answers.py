@@ -9,7 +9,7 @@ An ask is one Result's question in its resolved form -- top_k.Ask, detections.As
 import numpy as np
 
 from . import detections as detections_rule, device, gallery as gallery_rule, tiled_detections as tiled_rule, top_k as top_k_rule
-from .input_format import DetectedRois, LandmarkWarps, PerspectiveInput, RoiInput, WarpInput
+from .input_format import FrameFeed
 
 
 class Answers:
@@ -49,7 +49,7 @@ class Answers:
         regions = {name: s for name, s in screens.items() if isinstance(s, tiled_rule.RegionScreen)}     # (any declared fit: a geometry per row)
         tiled_rule.checked_feed(inputs, {**tiled, **regions})
         fitted = self._fitted_input() if len(screens) > len(tiled) + len(regions) else None
-        if fitted is not None and isinstance(inputs, dict) and isinstance(inputs.get(fitted), (RoiInput, DetectedRois, WarpInput, PerspectiveInput, LandmarkWarps)):
+        if fitted is not None and isinstance(inputs, dict) and isinstance(inputs.get(fitted), FrameFeed):
             raise ValueError('detections: input {!r} declares resize_fit {} and is fed a {}: every row has a geometry of its own'.format(
                 fitted, formats[fitted].fit, type(inputs[fitted]).__name__))
         n = int(ienet.batch_size)

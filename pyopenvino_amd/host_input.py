@@ -1,6 +1,7 @@
 """Host inputs of one request: arrays handed in a declared format (input_format.InputFormat) or in the request's own page-locked buffers
-(InferRequest.input_buffer) become the fixed fp32 NCHW device tensor its pass reads -- asynchronous upload on the copy stream, one
-conversion launch on the request's first stream, no host synchronisation."""
+(InferRequest.input_buffer), and the frames of a FrameFeed with its table, become the fixed fp32 NCHW device tensor its pass reads --
+asynchronous upload on the copy stream, one conversion launch on the request's first stream (InputFormat.conversion chooses it), no
+host synchronisation."""
 import collections
 import ctypes
 
@@ -8,130 +9,146 @@ import numpy as np
 
 from . import detections as detections_rule, device
 from . import landmarks as landmark_rule
-from .input_format import DetectedRois, DetectedTable, LandmarkTable, LandmarkWarps, PerspectiveInput, RoiInput, WarpInput
+from .input_format import DetectedRois, DetectedTable, FrameFeed, LandmarkTable, LandmarkWarps, PerspectiveInput, RoiInput, WarpInput
+
+NULL = ctypes.c_void_p(0)
+
+
+def _is_array(a, host) -> bool:
+    """`a` is the page-locked array `host` -- the object itself, or a view of all of it --: nothing has to be copied."""
+    return a is host or (isinstance(a, np.ndarray) and a.dtype == host.dtype and a.shape == host.shape and a.flags.c_contiguous
+                         and a.ctypes.data == host.ctypes.data)
+
+
+class _Pair:
+    """A page-locked array `host` and the device tensor `device` of its shape and dtype it is uploaded into.  `block`: the longer device
+    block that tensor is the head of -- what a table-making launch writes behind the table and a read-back takes in one copy --, given
+    as its (shape, dtype); else the tensor itself."""
+    __slots__ = ('host', 'device', 'block')
+
+    def __init__(self, shape, dtype, block=None):
+        self.host = device.host_empty(shape, dtype)
+        self.block = device.DeviceTensor.empty(*(block or (shape, dtype)))
+        self.device = self.block if block is None else device.DeviceTensor(self.block._block, shape, dtype)
+
+    @classmethod
+    def of_shape(cls, pair, shape, dtype):
+        """`pair` when it has `shape`, else a new one: what is fed with another row count every pass keeps its buffers while it can."""
+        return pair if pair is not None and pair.host.shape == shape else cls(shape, dtype)
+
+    def holds(self, a) -> bool:
+        return _is_array(a, self.host)
+
+    @property
+    def upload(self):
+        return self.device, self.host
+
+
+# the table of a slot by FrameFeed.KIND, (columns, dtype, the block behind it for n rows or None): 'roi' (n, 5) rois | (n,) record_of |
+# (count, selected), what pvhip_detections_to_rois writes for a DetectedRois; 'warp' (n, 7) int64 | (n,) valid | count, what
+# pvhip_landmarks_to_warps writes for a LandmarkWarps
+TABLES = {'roi': (5, np.int32, lambda n: ((6 * n + 2,), np.int32)), 'warp': (7, np.int64, lambda n: ((56 * n + 4 * (n + 1),), np.uint8)),
+          'perspective': (10, np.int64, None)}
 
 
 class _Staging:
     """One source extent of one input: the page-locked host array and the device tensor it is uploaded into (the slot's fixed tensor
-    itself when nothing has to be converted).  `frames` = m: the m frames of a RoiInput instead (always uploaded into a tensor of their
+    itself when nothing has to be converted).  `frames` = m: the m frames of a FrameFeed instead (always uploaded into a tensor of their
     own).  It holds no reference back to its slot, so dropping it frees its memory at once."""
-    __slots__ = ('host', 'staging', 'extent', 'frames', 'preprocess')
+    __slots__ = ('host', 'staging', 'extent', 'frames')
 
     def __init__(self, fmt, extent, fixed, frames=None):
         shape, dtype = fmt.host_shape(extent, frames), fmt.host_dtype
         self.host = device.host_empty(shape, dtype)
         self.staging = device.DeviceTensor.empty(shape, dtype) if frames is not None or fmt.needs_convert(extent) else fixed
-        self.extent, self.frames, self.preprocess = extent, frames, fmt.needs_preprocess(extent)
+        self.extent, self.frames = extent, frames
 
     @property
     def key(self):
-        """What _Slot.extents files it under: the extent, or (extent, m) for the frames of a RoiInput."""
+        """What _Slot.extents files it under: the extent, or (extent, m) for the frames of a FrameFeed."""
         return self.extent if self.frames is None else (self.extent, self.frames)
+
+    def copy_in(self, a):
+        """The caller's images or frames `a`, checked, in the page-locked array -- copied unless they are that array."""
+        if not _is_array(a, self.host):
+            np.copyto(self.host, a, casting='same_kind' if self.host.dtype == np.float32 else 'safe')
+        return self
 
 
 class _Slot:
     """What a request keeps for one input whatever the source extent: the fp32 NCHW tensor the pass reads -- the same address on every
     call, so the pass is recorded and replayed like a device-resident one whatever the source size --, the copy's event, mean / scale on
-    the device (c floats each, uploaded once per request: load_network needs no device) and {extent: _Staging}, least recently fed first
-    -- a RoiInput's frames under (extent, m) --, and the (n, 5) int32 table of a RoiInput, page-locked and on the device, once one is fed.
-    The device table is the head of one block `table` of 6 n + 2 ints, (n, 5) rois | (n,) record_of | (count, selected): what
-    pvhip_detections_to_rois writes for a DetectedRois (`detected`: what that needs besides, once one is fed) and detected_rois() reads
-    back in one copy.  `warps_host` / `warps`: the (n, 7) int64 table of a WarpInput, page-locked and on the device, once one is fed;
-    `perspectives_host` / `perspectives`: the (n, 10) int64 table of a PerspectiveInput likewise.  The device warp table is the head of
-    one block `warp_block` of 56 n + 4 (n + 1) bytes, (n, 7) int64 | (n,) valid | count: what pvhip_landmarks_to_warps writes for a
-    LandmarkWarps (`landmarks`: what that needs besides, once one is fed) and landmark_warps() reads back in one copy.  `last`: what the
-    input was last fed -- 'table' (a RoiInput or a DetectedRois: `rois` holds that pass's regions), 'images' (whole images), 'warp' (a
-    WarpInput, a PerspectiveInput or a LandmarkWarps: no rectangle per row) or None (anything else): what a LandmarkWarps over this
-    network's Result normalises its points to.  `table_readers`: events behind the launches of OTHER requests that read `rois` on the
-    device (a LandmarkWarps fed from this request); stage() waits for them before anything overwrites the table."""
-    __slots__ = ('fixed', 'event', 'mean', 'std', 'extents', 'rois_host', 'rois', 'table', 'detected', 'fed', 'warps_host', 'warps',
-                 'perspectives_host', 'perspectives', 'warp_block', 'landmarks', 'last', 'table_readers')
+    the device (c floats each, uploaded once per request: load_network needs no device), `extents` = {extent: _Staging}, least recently
+    fed first -- a FrameFeed's frames under (extent, m) --, `tables` = {FrameFeed.KIND: _Pair}, the table of each kind once one is fed
+    (TABLES), and `producers` = {DetectedRois: _Detected, LandmarkWarps: _Landmarks}, what a feed whose table a launch makes needs besides.
+    `fed`: the extent of the whole images the last pass was staged from (what a declared fit fitted), else None.  `last`: what the
+    input was last fed -- 'table' (a feed of rectangles: tables['roi'] holds that pass's regions), 'images' (whole images), 'warp' (a
+    sampled feed: no rectangle per row) or None (anything else): what a LandmarkWarps over this network's Result normalises its points
+    to.  `table_readers`: events behind the launches of OTHER requests that read tables['roi'] on the device (a LandmarkWarps fed from
+    this request); stage() waits for them before anything overwrites the table."""
+    __slots__ = ('fixed', 'event', 'mean', 'std', 'extents', 'tables', 'producers', 'fed', 'last', 'table_readers')
 
     def __init__(self, fmt):
         self.fixed, self.event = device.DeviceTensor.empty(fmt.dims), device.Event(timed=False)
         self.mean, self.std = (None, None) if fmt.mean is None else (device.DeviceTensor.from_numpy(fmt.mean), device.DeviceTensor.from_numpy(fmt.std))
-        self.extents = collections.OrderedDict()
-        self.rois_host = self.rois = self.table = self.detected = self.warps_host = self.warps = None
-        self.perspectives_host = self.perspectives = self.warp_block = self.landmarks = None
-        self.last, self.table_readers = None, []
-        self.fed = None                         # the extent of the whole images the last pass was staged from (what a declared fit fitted)
+        self.extents, self.tables, self.producers = collections.OrderedDict(), {}, {}
+        self.fed, self.last, self.table_readers = None, None, []
 
-    def roi_table(self):
-        if self.rois_host is None:
-            n = self.fixed.shape[0]
-            self.rois_host = device.host_empty((n, 5), np.int32)
-            self.table = device.DeviceTensor.empty((6 * n + 2,), np.int32)
-            self.rois = device.DeviceTensor(self.table._block, (n, 5), np.int32)
-        return self.rois_host
+    def table(self, kind) -> _Pair:
+        pair = self.tables.get(kind)
+        if pair is None:
+            n, (columns, dtype, block) = self.fixed.shape[0], TABLES[kind]
+            pair = self.tables[kind] = _Pair((n, columns), dtype, block and block(n))
+        return pair
 
-    def warp_table(self):
-        if self.warps_host is None:
-            n = self.fixed.shape[0]
-            self.warps_host = device.host_empty((n, 7), np.int64)
-            self.warp_block = device.DeviceTensor.empty((56 * n + 4 * (n + 1),), np.uint8)
-            self.warps = device.DeviceTensor(self.warp_block._block, (n, 7), np.int64)
-        return self.warps_host
-
-    def perspective_table(self):
-        if self.perspectives_host is None:
-            n = self.fixed.shape[0]
-            self.perspectives_host = device.host_empty((n, 10), np.int64)
-            self.perspectives = device.DeviceTensor.empty((n, 10), np.int64)
-        return self.perspectives_host
+    def producer(self, made):
+        found = self.producers.get(made.FEED)
+        if found is None:
+            found = self.producers[made.FEED] = made()
+        return found
 
 
-class _Detected:
-    """What a slot keeps for DetectedRois inputs: the labels, page-locked and on the device; the records of a host array, page-locked and
-    on the device, for the record count last fed; the event recorded behind the launch that reads a detector's Result (the detector's
-    next pass waits for it); `source`: the device tensor the last launch read, kept alive until the next pass of this input; `live`: the
-    last pass of the input was a DetectedRois."""
-    __slots__ = ('labels_host', 'labels', 'records_host', 'records', 'read', 'source', 'live')
+class _Producer:
+    """What a slot keeps for a feed whose table is made on the device from another request's Result or from arrays: the event recorded
+    behind the launch that reads that Result (the request's next pass waits for it); `sources`: the device tensors the last launch
+    read, kept alive until the next pass of this input; `live`: the last pass of the input was such a feed."""
+    __slots__ = ('read', 'sources', 'live')
 
     def __init__(self):
-        self.labels_host = device.host_empty((DetectedRois.MAX_LABELS,), np.int32)
-        self.labels = device.DeviceTensor.empty(self.labels_host.shape, np.int32)
-        self.records_host = self.records = self.source = None
-        self.read, self.live = device.Event(timed=False), False
-
-    def records_for(self, rows):
-        if self.records_host is None or self.records_host.shape[0] != rows:
-            self.records_host = device.host_empty((rows, 7), np.float32)
-            self.records = device.DeviceTensor.empty((rows, 7), np.float32)
-        return self.records_host
+        self.read, self.sources, self.live = device.Event(timed=False), (), False
 
 
-class _Landmarks:
-    """What a slot keeps for LandmarkWarps inputs: the packed template, page-locked and on the device, and the bytes of the one uploaded
-    last (`packed`: a template is uploaded once); the points and the regions of host arrays, page-locked and on the device, for the row
-    count last fed; the event recorded behind the launch that reads a landmark request's Result and region table (that request's next
-    pass waits for it); `source` / `regions_source`: the device tensors the last launch read, kept alive until the next pass of this
-    input; `live`: the last pass of the input was a LandmarkWarps."""
-    __slots__ = ('template_host', 'template', 'packed', 'points_host', 'points', 'regions_host', 'regions', 'read', 'source',
-                 'regions_source', 'live')
+class _Detected(_Producer):
+    """DetectedRois: the labels, and the records of a host array for the record count last fed."""
+    __slots__ = ('labels', 'records')
+    FEED = DetectedRois
 
     def __init__(self):
-        self.template_host = device.host_empty((2 * landmark_rule.MAX_POINTS + 3,), np.float64)
-        self.template = device.DeviceTensor.empty(self.template_host.shape, np.float64)
-        self.packed = self.points_host = self.points = self.regions_host = self.regions = self.source = self.regions_source = None
-        self.read, self.live = device.Event(timed=False), False
+        super().__init__()
+        self.labels, self.records = _Pair((DetectedRois.MAX_LABELS,), np.int32), None
 
-    def points_for(self, rows, values):
-        if self.points_host is None or self.points_host.shape != (rows, values):
-            self.points_host = device.host_empty((rows, values), np.float32)
-            self.points = device.DeviceTensor.empty((rows, values), np.float32)
-        return self.points_host
 
-    def regions_for(self, rows):
-        if self.regions_host is None or self.regions_host.shape[0] != rows:
-            self.regions_host = device.host_empty((rows, 5), np.int32)
-            self.regions = device.DeviceTensor.empty((rows, 5), np.int32)
-        return self.regions_host
+class _Landmarks(_Producer):
+    """LandmarkWarps: the packed template and the bytes of the one uploaded last (`packed`: a template is uploaded once), and the points
+    and the regions of host arrays for the row count last fed."""
+    __slots__ = ('template', 'packed', 'points', 'regions')
+    FEED = LandmarkWarps
+
+    def __init__(self):
+        super().__init__()
+        self.template, self.packed = _Pair((2 * landmark_rule.MAX_POINTS + 3,), np.float64), None
+        self.points = self.regions = None
+
+
+# what a stager hands stage(): the _Staging of the frames, the _Pair.upload's beside them, the launch to issue on the base stream in
+# front of the conversion or None, `largest` and `kind` as InputFormat.conversion takes them
+_Staged = collections.namedtuple('_Staged', 'staging uploads launch largest kind')
 
 
 class HostInputs:
     """The host-input state of one Executable_Network (one per request): `formats` = {input name: InputFormat}, fixed at load_network
     and shared by every request; `slots` = {input name: _Slot} of the inputs fed from the host so far."""
-    # source extents (h, w) of a resized input -- and (extent, frame count) pairs of its RoiInputs -- whose buffers a request keeps at once
+    # source extents (h, w) of a resized input -- and (extent, frame count) pairs of its FrameFeeds -- whose buffers a request keeps at once
     MAX_SOURCE_EXTENTS = 4
 
     def __init__(self, formats):
@@ -150,7 +167,7 @@ class HostInputs:
         return slot
 
     def _staging(self, name, extent, frames=None):
-        """The staging of input `name` for sources of `extent` (`frames` = m: for the m frames of a RoiInput), made on first use."""
+        """The staging of input `name` for sources of `extent` (`frames` = m: for the m frames of a FrameFeed), made on first use."""
         slot = self._slot(name)
         key = extent if frames is None else (extent, frames)
         staged = slot.extents.get(key)
@@ -166,102 +183,88 @@ class HostInputs:
 
     def buffer(self, name, source_size=None, frames=None) -> np.ndarray:
         """The page-locked array input `name` is uploaded from for sources of `source_size` (default: the network's extent); `frames`
-        = m: the one the m frames of a RoiInput are uploaded from."""
+        = m: the one the m frames of a FrameFeed are uploaded from."""
         fmt = self._format(name)
         if frames is not None:
             frames = fmt.checked_frames(frames)
         return self._staging(name, fmt.checked_extent(source_size), frames).host
 
+    def _table_buffer(self, name, feed) -> np.ndarray:
+        self._format(name).resize_declared(feed)
+        return self._slot(name).table(feed.KIND).host
+
     def roi_buffer(self, name) -> np.ndarray:
         """The page-locked (n, 5) int32 table a RoiInput of input `name` is uploaded from."""
-        fmt = self._format(name)
-        fmt.checked_frames(1)               # (a resize is declared)
-        return self._slot(name).roi_table()
+        return self._table_buffer(name, RoiInput)
 
     def warp_buffer(self, name) -> np.ndarray:
         """The page-locked (n, 7) int64 table a WarpInput of input `name` is uploaded from."""
-        fmt = self._format(name)
-        fmt.warp_declared()
-        return self._slot(name).warp_table()
+        return self._table_buffer(name, WarpInput)
 
     def perspective_buffer(self, name) -> np.ndarray:
         """The page-locked (n, 10) int64 table a PerspectiveInput of input `name` is uploaded from."""
-        fmt = self._format(name)
-        fmt.perspective_declared()
-        return self._slot(name).perspective_table()
+        return self._table_buffer(name, PerspectiveInput)
 
-    def _stage_warps(self, name, fmt, warp):
+    def _stage_matrices(self, name, fmt, warp, sharded):
         """The frames and the table of WarpInput or PerspectiveInput `warp` in this request's page-locked buffers -- copied, unless
-        they are those buffers --, everything checked before anything is allocated: the staging."""
-        slot, given = self.slots.get(name), warp.matrices
-        if isinstance(warp, PerspectiveInput):
-            declared, checked, checked_table = fmt.perspective_declared, fmt.checked_perspectives, fmt.checked_perspective_table
-            buffer, table_of, host = 'perspective', _Slot.perspective_table, slot.perspectives_host if slot is not None else None
-        else:
-            declared, checked, checked_table = fmt.warp_declared, fmt.checked_warps, fmt.checked_warp_table
-            buffer, table_of, host = 'warp', _Slot.warp_table, slot.warps_host if slot is not None else None
-        declared()
-        frames = warp.frames if isinstance(warp.frames, np.ndarray) else np.asarray(warp.frames)
-        extent, m = fmt.frames_extent_of(frames, type(warp).__name__)
-        own = (host is not None and isinstance(given, np.ndarray) and given.dtype == np.int64
-               and given.shape == host.shape and given.flags.c_contiguous and given.ctypes.data == host.ctypes.data)
+        they are those buffers --, everything checked before anything is allocated."""
+        feed, slot, given = type(warp), self.slots.get(name), warp.matrices
+        fmt.resize_declared(feed)
+        frames = np.asarray(warp.frames)
+        extent, m = fmt.frames_extent_of(frames, feed)
+        pair = slot.tables.get(feed.KIND) if slot is not None else None
+        own = pair is not None and pair.holds(given)
         if own:
             if warp.ids is not None:
-                raise ValueError('input {}: the {}_buffer holds the frame of each row in its first column: ids is None with it'.format(name, buffer))
-            checked_table(given, m)
+                raise ValueError('input {}: the {}_buffer holds the frame of each row in its first column: ids is None with it'.format(name, feed.BUFFER))
+            fmt.checked_matrix_table(feed, given, m)
         else:
-            table = checked(given, warp.ids, m)
-        staged = self._staging(name, extent, m)
-        if not (frames.dtype == staged.host.dtype and frames.flags.c_contiguous and frames.ctypes.data == staged.host.ctypes.data):
-            np.copyto(staged.host, frames, casting='same_kind' if staged.host.dtype == np.float32 else 'safe')
+            table = fmt.checked_matrices(feed, given, warp.ids, m)
+        staged = self._staging(name, extent, m).copy_in(frames)
+        pair = self.slots[name].table(feed.KIND)
         if not own:
-            np.copyto(table_of(self.slots[name]), table)
-        return staged
+            np.copyto(pair.host, table)
+        return _Staged(staged, (pair.upload,), None, None, feed.KIND)
 
-    def _stage_rois(self, name, fmt, roi):
+    def _stage_rois(self, name, fmt, roi, sharded):
         """The frames and the table of RoiInput `roi` in this request's page-locked buffers -- copied, unless they are those buffers --,
-        everything checked before anything is allocated: (staging, (max_h, max_w))."""
-        frames = roi.frames if isinstance(roi.frames, np.ndarray) else np.asarray(roi.frames)
+        everything checked before anything is allocated; `largest` is the (max_h, max_w) of its rectangles."""
+        frames = np.asarray(roi.frames)
         extent, m = fmt.frames_extent_of(frames)
         table, largest = fmt.checked_rois(roi.rois, extent, m)
-        staged = self._staging(name, extent, m)
-        if not (frames.dtype == staged.host.dtype and frames.flags.c_contiguous and frames.ctypes.data == staged.host.ctypes.data):
-            np.copyto(staged.host, frames, casting='same_kind' if staged.host.dtype == np.float32 else 'safe')
-        rois_host = self.slots[name].roi_table()
-        own = (isinstance(roi.rois, np.ndarray) and roi.rois.dtype == np.int32 and roi.rois.flags.c_contiguous
-               and roi.rois.ctypes.data == rois_host.ctypes.data)
-        if not own:
-            np.copyto(rois_host, table)
-        return staged, largest
+        staged = self._staging(name, extent, m).copy_in(frames)
+        pair = self.slots[name].table('roi')
+        if not pair.holds(roi.rois):
+            np.copyto(pair.host, table)
+        return _Staged(staged, (pair.upload,), None, largest, 'roi')
 
     @staticmethod
-    def _detections_of(name, det):
-        """What DetectedRois `det` reads, nothing waited for and nothing copied: (records -- a DeviceTensor or a host array --, the images
-        they belong to by default or None, the runner whose pass produces them and the event behind that pass, or (None, None), the geometry
-        of the detector's fitted input or None)."""
-        src = det.detections
+    def _result_of(name, src, output, words, checks):
+        """What a feed over `src` reads, nothing waited for and nothing copied: (value -- a DeviceTensor or a host array --, the runner
+        whose pass produces it or None, the event behind that pass or None, what `checks` returned or None).  `src`: a DeviceTensor or
+        an array; or the InferRequest of another network, in flight -- its device-resident Result -- or waited for -- its host Results,
+        like an array.  `output` names the Result when there are several; `words` = (the network, its request, the Result `output`
+        names) as the texts say them; `checks(runner, node id, Result name)` runs before the Result is asked for."""
         if not (hasattr(src, 'runner') and hasattr(src, 'start_async')):         # (an InferRequest: inference_engine imports this module)
-            return (src if isinstance(src, device.DeviceTensor) else np.asarray(src)), None, None, None, None
+            return (src if isinstance(src, device.DeviceTensor) else np.asarray(src)), None, None, None
         runner = src.runner
         net = runner.ienet
         results = net.find_node_by_type('Result')
-        if det.output is not None:
-            results = [r for r in results if r[1] == det.output]
+        if output is not None:
+            results = [r for r in results if r[1] == output]
             if not results:
-                raise ValueError('input {}: the detector has no Result named {!r}'.format(name, det.output))
+                raise ValueError('input {}: the {} has no Result named {!r}'.format(name, words[0], output))
         elif len(results) != 1:
-            raise ValueError('input {}: the detector has {} Results: output= names the DetectionOutput one'.format(name, len(results)))
+            raise ValueError('input {}: the {} has {} Results: output= names {}'.format(name, words[0], len(results), words[2]))
         nid = results[0][0]
-        if [net.G.nodes[p]['type'] for p in net.G.pred[nid]] != ['DetectionOutput']:
-            raise ValueError('input {}: Result {!r} of the detector is no DetectionOutput'.format(name, results[0][1]))
+        checked = checks(runner, nid, results[0][1])
         replayed, pending = (src._replayed, runner._pending) if src._in_flight else (None, None)
         value = replayed['results'][results[0][1]] if replayed is not None else net.G.nodes[nid].get('result')
         if value is None:
-            raise RuntimeError('input {}: the detector request never ran: start_async() or infer() it first'.format(name))
-        fit = runner.host_inputs.detector_fit()
+            raise RuntimeError('input {}: the {} never ran: start_async() or infer() it first'.format(name, words[1]))
         if not isinstance(value, device.DeviceTensor):        # waited for: its host Results, like an array
-            return np.asarray(value), net.batch_size, None, None, fit
-        return value, net.batch_size, runner, (pending[1] if pending is not None else None), fit
+            return np.asarray(value), runner, None, checked
+        return value, runner, (pending[1] if pending is not None else None), checked
 
     def detector_fit(self):
         """(Hn, Wn, dx, dy, iw, ih) of the pass this network was last fed, when its single 4-D Parameter declares a fit and was staged
@@ -276,171 +279,148 @@ class HostInputs:
 
     def _stage_detected(self, name, fmt, det, sharded):
         """The frames of DetectedRois `det` in this request's page-locked buffers, its records (a host array: in the slot's page-locked
-        buffer) and its options, everything checked before anything is allocated: (staging, [(device tensor, page-locked array)] to
-        upload beside the frames, launch), launch() being what `stage` issues on the base stream in front of the ROI launch."""
+        buffer) and its options, everything checked before anything is allocated; the launch makes the table of the ROI launch behind
+        it, which is sized for whole frames: the host does not know the largest rectangle, the frame bounds it."""
         if sharded:
             raise NotImplementedError('input {}: DetectedRois with a batch sharded over ranks'.format(name))
-        frames = det.frames if isinstance(det.frames, np.ndarray) else np.asarray(det.frames)
+        frames = np.asarray(det.frames)
         extent, m = fmt.frames_extent_of(frames)
         conf, labels, (min_h, min_w) = det.checked_options(name)
-        records, images, runner, done, fit = self._detections_of(name, det)
+
+        def is_detection_output(runner, nid, result):
+            net = runner.ienet
+            if [net.G.nodes[p]['type'] for p in net.G.pred[nid]] != ['DetectionOutput']:
+                raise ValueError('input {}: Result {!r} of the detector is no DetectionOutput'.format(name, result))
+
+        records, runner, done, _ = self._result_of(name, det.detections, det.output, ('detector', 'detector request', 'the DetectionOutput one'),
+                                                   is_detection_output)
+        images, fit = (runner.ienet.batch_size, runner.host_inputs.detector_fit()) if runner is not None else (None, None)
         if det.detector_fit is not None:
             fit = detections_rule.checked_fit(det.detector_fit, 'input {}: detector_fit'.format(name))
         images = det.images if det.images is not None else (images if images is not None else m)
         per_image = det.checked_records(name, records.shape, records.dtype, images, m)
-        staged = self._staging(name, extent, m)
-        if not (frames.dtype == staged.host.dtype and frames.flags.c_contiguous and frames.ctypes.data == staged.host.ctypes.data):
-            np.copyto(staged.host, frames, casting='same_kind' if staged.host.dtype == np.float32 else 'safe')
+        staged = self._staging(name, extent, m).copy_in(frames)
         slot = self.slots[name]
-        slot.roi_table()
-        if slot.detected is None:
-            slot.detected = _Detected()
-        d = slot.detected
+        table, d = slot.table('roi').block, slot.producer(_Detected)
         uploads = []
         if labels is not None and len(labels):
-            d.labels_host[:len(labels)] = labels
-            uploads.append((d.labels, d.labels_host))
-        listed = device.ptr(d.labels if labels is not None else None)       # NULL: any label
+            d.labels.host[:len(labels)] = labels
+            uploads.append(d.labels.upload)
+        listed = device.ptr(d.labels.device if labels is not None else None)       # NULL: any label
         if isinstance(records, device.DeviceTensor):
-            d.source = records
+            d.sources = (records,)
         else:
-            np.copyto(d.records_for(images * per_image), records.reshape(-1, 7))
-            d.source = d.records
-            uploads.append((d.records, d.records_host))
+            d.records = _Pair.of_shape(d.records, (images * per_image, 7), np.float32)
+            np.copyto(d.records.host, records.reshape(-1, 7))
+            d.sources = (d.records.device,)
+            uploads.append(d.records.upload)
+            runner = None                                     # (waited for: nothing of the detector's is read on the device)
         n = slot.fixed.shape[0]
 
         def launch():
             if done is not None:
                 done.wait()                                   # the detector's pass, on the device
-            device.call('pvhip_detections_to_rois' + ('_fit' if fit is not None else ''), device.ptr(d.source), ctypes.c_void_p(slot.table.ptr),
-                        ctypes.c_void_p(slot.table.ptr + 20 * n), ctypes.c_void_p(slot.table.ptr + 24 * n), n, images, per_image, *extent,
+            device.call('pvhip_detections_to_rois' + ('_fit' if fit is not None else ''), device.ptr(d.sources[0]), ctypes.c_void_p(table.ptr),
+                        ctypes.c_void_p(table.ptr + 20 * n), ctypes.c_void_p(table.ptr + 24 * n), n, images, per_image, *extent,
                         conf, listed, 0 if labels is None else len(labels), min_h, min_w, *(fit or ()))
             if runner is not None:                            # its next pass may overwrite that Result: not before this launch has read it
                 runner._result_readers.append(d.read.record())
 
-        return staged, uploads, launch
+        return _Staged(staged, uploads, launch, extent, 'roi')
 
     def detected_rois(self, name, stream_base) -> DetectedTable:
         """The table the last pass of input `name` used, read back in one copy on stream `stream_base`, which has drained."""
-        self._format(name)
-        slot = self.slots.get(name)
-        if slot is None or slot.detected is None or not slot.detected.live:
-            raise RuntimeError('input {}: its last pass was not fed a DetectedRois'.format(name))
-        n = slot.fixed.shape[0]
-        device.select_stream(stream_base)
-        t = np.asarray(slot.table)
-        device.select_stream(0)
+        t, n = self._made_table(name, DetectedRois, stream_base)
         return DetectedTable(int(t[6 * n]), int(t[6 * n + 1]), t[:5 * n].reshape(n, 5).copy(), t[5 * n:6 * n].copy())
 
-    @staticmethod
-    def _landmarks_of(name, lw):
-        """What LandmarkWarps `lw` reads, nothing waited for and nothing copied: (points -- a DeviceTensor or a host array --, the runner
-        whose pass produces them and the event behind that pass, or (None, None), the _Slot whose `rois` that pass was fed or None: the
-        whole frame)."""
-        src = lw.landmarks
-        if not (hasattr(src, 'runner') and hasattr(src, 'start_async')):         # (an InferRequest: inference_engine imports this module)
-            return (src if isinstance(src, device.DeviceTensor) else np.asarray(src)), None, None, None
-        runner = src.runner
-        net = runner.ienet
-        results = net.find_node_by_type('Result')
-        if lw.output is not None:
-            results = [r for r in results if r[1] == lw.output]
-            if not results:
-                raise ValueError('input {}: the landmark network has no Result named {!r}'.format(name, lw.output))
-        elif len(results) != 1:
-            raise ValueError('input {}: the landmark network has {} Results: output= names the one that holds the points'.format(name, len(results)))
-        nid = results[0][0]
-        fed = runner.host_inputs
-        names = [k for k, f in fed.formats.items() if len(f.dims) == 4]
-        owner = fed.slots.get(names[0]) if len(names) == 1 else None
-        if len(names) == 1 and fed.formats[names[0]].fitted:
-            raise ValueError('input {}: input {!r} of the landmark network declares resize_fit {}: its points are normalised to a fitted '
-                             'rectangle, not to the region'.format(name, names[0], fed.formats[names[0]].fit))
-        if owner is not None and owner.last == 'warp':
-            raise ValueError('input {}: input {!r} of the landmark network was last fed a WarpInput, a PerspectiveInput or a LandmarkWarps: '
-                             'its rows have no rectangle the points are normalised to'.format(name, names[0]))
-        replayed, pending = (src._replayed, runner._pending) if src._in_flight else (None, None)
-        value = replayed['results'][results[0][1]] if replayed is not None else net.G.nodes[nid].get('result')
-        if value is None:
-            raise RuntimeError('input {}: the landmark request never ran: start_async() or infer() it first'.format(name))
-        owner = owner if owner is not None and owner.last == 'table' else None
-        if not isinstance(value, device.DeviceTensor):        # waited for: its host Results, like an array
-            return np.asarray(value), runner, None, owner
-        return value, runner, (pending[1] if pending is not None else None), owner
+    def _made_table(self, name, feed, stream_base):
+        """(the block behind the table a launch made for the last pass of input `name`, read back on stream `stream_base`, n)."""
+        self._format(name)
+        slot = self.slots.get(name)
+        if slot is None or feed not in slot.producers or not slot.producers[feed].live:
+            raise RuntimeError('input {}: its last pass was not fed a {}'.format(name, feed.__name__))
+        device.select_stream(stream_base)
+        raw = np.asarray(slot.tables[feed.KIND].block)
+        device.select_stream(0)
+        return raw, slot.fixed.shape[0]
 
     def _stage_landmarks(self, name, fmt, lw, sharded):
         """The frames of LandmarkWarps `lw` in this request's page-locked buffers, its template, and its points and regions when they are
-        host arrays, everything checked before anything is allocated: (staging, [(device tensor, page-locked array)] to upload beside the
-        frames, launch), launch() being what `stage` issues on the base stream in front of the warp launch."""
+        host arrays, everything checked before anything is allocated; the launch fits the table of the warp launch behind it."""
         if sharded:
             raise NotImplementedError('input {}: LandmarkWarps with a batch sharded over ranks'.format(name))
-        fmt.warp_declared()
-        frames = lw.frames if isinstance(lw.frames, np.ndarray) else np.asarray(lw.frames)
-        extent, m = fmt.frames_extent_of(frames, 'LandmarkWarps')
+        fmt.resize_declared(WarpInput)
+        frames = np.asarray(lw.frames)
+        extent, m = fmt.frames_extent_of(frames, LandmarkWarps)
         packed = lw.checked_template(name)
         k = (len(packed) - 3) // 2
-        points, runner, done, owner = self._landmarks_of(name, lw)
+
+        def region_owner(runner, nid, result):
+            """The _Slot whose region table the landmark pass was fed, or None: the whole frame."""
+            fed = runner.host_inputs
+            names = [key for key, f in fed.formats.items() if len(f.dims) == 4]
+            owner = fed.slots.get(names[0]) if len(names) == 1 else None
+            if len(names) == 1 and fed.formats[names[0]].fitted:
+                raise ValueError('input {}: input {!r} of the landmark network declares resize_fit {}: its points are normalised to a fitted '
+                                 'rectangle, not to the region'.format(name, names[0], fed.formats[names[0]].fit))
+            if owner is not None and owner.last == 'warp':
+                raise ValueError('input {}: input {!r} of the landmark network was last fed a WarpInput, a PerspectiveInput or a LandmarkWarps: '
+                                 'its rows have no rectangle the points are normalised to'.format(name, names[0]))
+            return owner if owner is not None and owner.last == 'table' else None
+
+        points, runner, done, owner = self._result_of(name, lw.landmarks, lw.output,
+                                                      ('landmark network', 'landmark request', 'the one that holds the points'), region_owner)
         rows = lw.checked_points(name, points.shape, points.dtype, k)
         regions = lw.checked_regions(name, rows)
+        given = owner.tables['roi'].device if owner is not None else None
         if regions is not None:
-            owner = None
-        elif owner is not None and owner.rois.shape[0] != rows:
+            owner = given = None
+        elif owner is not None and given.shape[0] != rows:
             raise ValueError('input {}: the landmark pass was fed a table of {} regions, its Result holds {} rows of points: regions names '
-                             'the rectangle of each row'.format(name, owner.rois.shape[0], rows))
+                             'the rectangle of each row'.format(name, given.shape[0], rows))
         elif owner is None and m != 1 and m != rows:
             raise ValueError('input {}: landmarks over whole frames read frame b for row b (m == N) or frame 0 (m == 1); with {} frames for {} '
                              'rows of points, regions names the frame and the rectangle of each row'.format(name, m, rows))
-        staged = self._staging(name, extent, m)
-        if not (frames.dtype == staged.host.dtype and frames.flags.c_contiguous and frames.ctypes.data == staged.host.ctypes.data):
-            np.copyto(staged.host, frames, casting='same_kind' if staged.host.dtype == np.float32 else 'safe')
+        staged = self._staging(name, extent, m).copy_in(frames)
         slot = self.slots[name]
-        slot.warp_table()
-        if slot.landmarks is None:
-            slot.landmarks = _Landmarks()
-        lm = slot.landmarks
+        table, lm = slot.table('warp'), slot.producer(_Landmarks)
         uploads = []
         if lm.packed != packed.tobytes():                      # a template is uploaded once
-            lm.template_host[:len(packed)] = packed
+            lm.template.host[:len(packed)] = packed
             lm.packed = packed.tobytes()
-            uploads.append((lm.template, lm.template_host))
+            uploads.append(lm.template.upload)
         if isinstance(points, device.DeviceTensor):
-            lm.source = points
+            source = points
         else:
-            np.copyto(lm.points_for(rows, 2 * k), points.reshape(rows, 2 * k))
-            lm.source = lm.points
-            uploads.append((lm.points, lm.points_host))
+            lm.points = _Pair.of_shape(lm.points, (rows, 2 * k), np.float32)
+            np.copyto(lm.points.host, points.reshape(rows, 2 * k))
+            source, runner = lm.points.device, None           # (waited for: no Result of the landmark request's is read on the device)
+            uploads.append(lm.points.upload)
         if regions is not None:
-            np.copyto(lm.regions_for(rows), regions)
-            lm.regions_source = lm.regions
-            uploads.append((lm.regions, lm.regions_host))
-        else:
-            lm.regions_source = owner.rois if owner is not None else None       # NULL: the whole frame
+            lm.regions = _Pair.of_shape(lm.regions, (rows, 5), np.int32)
+            np.copyto(lm.regions.host, regions)
+            given = lm.regions.device
+            uploads.append(lm.regions.upload)
+        lm.sources = (source, given)                          # (no regions, NULL: the whole frame)
         n = slot.fixed.shape[0]
 
         def launch():
             if done is not None:
                 done.wait()                                   # the landmark pass, on the device
-            device.call('pvhip_landmarks_to_warps', device.ptr(lm.source), device.ptr(lm.regions_source), device.ptr(lm.template),
-                        device.ptr(slot.warps), ctypes.c_void_p(slot.warp_block.ptr + 56 * n), n, rows, k, m, *extent)
-            if (runner is not None and isinstance(points, device.DeviceTensor)) or owner is not None:
+            device.call('pvhip_landmarks_to_warps', device.ptr(source), device.ptr(given), device.ptr(lm.template.device),
+                        device.ptr(table.device), ctypes.c_void_p(table.block.ptr + 56 * n), n, rows, k, m, *extent)
+            if runner is not None or owner is not None:
                 read = lm.read.record()
-                if runner is not None and isinstance(points, device.DeviceTensor):
+                if runner is not None:
                     runner._result_readers.append(read)       # its next pass may overwrite that Result: not before this launch has read it
                 if owner is not None and read not in owner.table_readers:       # (one event per consumer slot, recorded again each pass)
                     owner.table_readers.append(read)          # nor may its next stage() overwrite that table
 
-        return staged, uploads, launch
+        return _Staged(staged, uploads, launch, None, 'warp')
 
     def landmark_warps(self, name, stream_base) -> LandmarkTable:
         """The table the last pass of input `name` used, read back in one copy on stream `stream_base`, which has drained."""
-        self._format(name)
-        slot = self.slots.get(name)
-        if slot is None or slot.landmarks is None or not slot.landmarks.live:
-            raise RuntimeError('input {}: its last pass was not fed a LandmarkWarps'.format(name))
-        n = slot.fixed.shape[0]
-        device.select_stream(stream_base)
-        raw = np.asarray(slot.warp_block)
-        device.select_stream(0)
+        raw, n = self._made_table(name, LandmarkWarps, stream_base)
         valid = raw[56 * n:].view(np.int32)
         return LandmarkTable(int(valid[n]), valid[:n] != 0, raw[:56 * n].view(np.int64).reshape(n, 7).copy())
 
@@ -448,103 +428,40 @@ class HostInputs:
         """The staging host array `arr` is fed through: the one whose page-locked buffer `arr` is, else -- for a declared format -- the
         one of its extent with `arr` copied into it; None: the input goes the default way."""
         slot = self.slots.get(name)
-        if slot is not None and isinstance(arr, np.ndarray):
-            # (the frames buffer of a RoiInput is none of them: handed in without its table it is an array like any other)
+        if slot is not None:
+            # (the frames buffer of a FrameFeed is none of them: handed in without its table it is an array like any other)
             for s in slot.extents.values():
-                if s.frames is None and arr.shape == s.host.shape and arr.dtype == s.host.dtype and arr.ctypes.data == s.host.ctypes.data:
+                if s.frames is None and _is_array(arr, s.host):
                     return s
         if not fmt.declared:
             return None
         a = np.asarray(arr)
-        staged = self._staging(name, fmt.extent_of(a))
-        np.copyto(staged.host, a, casting='same_kind' if staged.host.dtype == np.float32 else 'safe')
-        return staged
+        return self._staging(name, fmt.extent_of(a)).copy_in(a)
 
-    @staticmethod
-    def _convert(fmt, slot, staged, largest, warped=False):
-        """The one launch that makes `slot.fixed` of what `staged` uploaded (none for FP32 NCHW at the network's extent):
-        pvhip_input_preprocess_yuv_f32 for NV12 / I420 frames, pvhip_input_preprocess_packed_f32 for YUY2 / UYVY / BGRX / RGBX frames,
-        pvhip_input_preprocess_f32 when a resize, channel reversal or mean / scale is in effect, else pvhip_input_to_nchw_f32;
-        `largest` = (max_h, max_w) of a RoiInput's table: the _roi_f32 forms.  A declared fit: the _fit_f32 forms of the three, with
-        the table or NULL.  `warped`: the frames of a WarpInput: pvhip_input_preprocess_warp_f32 for every format, whatever fit is
-        declared; `warped` = 'perspective': those of a PerspectiveInput, pvhip_input_preprocess_perspective_f32 with the same arguments
-        and the (n, 10) table.  A format whose colour rule is not BT.601 limited range (``InputFormat.default_rule``) takes the _color_f32 form of
-        its launch, whichever of these it is, with the rule behind the same arguments; every other format exactly the entries above."""
-        fixed = slot.fixed
-        src, dst = device.ptr(staged.staging), device.ptr(fixed)
-        n, c, dst_hw = fixed.shape[0], fixed.shape[1], fixed.shape[2:]
-        how = (int(fmt.color == 'I420'),) if fmt.yuv else (fmt.packed_kind,) if fmt.packed else (int(fmt.u8), int(fmt.nhwc))
-        pre = (int(fmt.reverse), device.ptr(slot.mean), device.ptr(slot.std))
-        if warped:
-            form = (1, how[0]) if fmt.yuv else (2, how[0]) if fmt.packed else (0, how[0] | how[1] << 1)
-            family, table = ('perspective', slot.perspectives) if warped == 'perspective' else ('warp', slot.warps)
-            entry, rule = (family + '_f32', ()) if fmt.default_rule else (family + '_color_f32', fmt.color_rule)
-            device.call('pvhip_input_preprocess_' + entry, src, dst, device.ptr(table), n, staged.frames, c, *staged.extent, *dst_hw, *form,
-                        *pre, fmt.pad, *rule)
-        elif not fmt.default_rule:
-            # (load_network admits another rule for YUV formats only) one entry per family: the table or NULL, the fit or 0
-            roi = largest is not None
-            device.call('pvhip_input_preprocess_yuv_color_f32' if fmt.yuv else 'pvhip_input_preprocess_packed_color_f32', src, dst,
-                        device.ptr(slot.rois if roi else None), n, staged.frames if roi else n, *staged.extent, *dst_hw,
-                        *(largest if roi else staged.extent), *how, *pre, fmt.fit_code, fmt.pad, *fmt.color_rule)
-        elif fmt.fitted and (largest is not None or fmt.yuv or fmt.packed or staged.preprocess):
-            where = (src, dst, device.ptr(slot.rois if largest is not None else None), n, staged.frames if largest is not None else n)
-            sizes = (*staged.extent, *dst_hw, *(largest if largest is not None else staged.extent))
-            tail = (*how, *pre, fmt.fit_code, fmt.pad)
-            if fmt.yuv:
-                device.call('pvhip_input_preprocess_yuv_fit_f32', *where, *sizes, *tail)
-            elif fmt.packed:
-                device.call('pvhip_input_preprocess_packed_fit_f32', *where, *sizes, *tail)
-            else:
-                device.call('pvhip_input_preprocess_fit_f32', *where, c, *sizes, *tail)
-        elif largest is not None:
-            where = (src, dst, device.ptr(slot.rois), n, staged.frames)
-            if fmt.yuv:
-                device.call('pvhip_input_preprocess_yuv_roi_f32', *where, *staged.extent, *dst_hw, *largest, *how, *pre)
-            elif fmt.packed:
-                device.call('pvhip_input_preprocess_packed_roi_f32', *where, *staged.extent, *dst_hw, *largest, *how, *pre)
-            else:
-                device.call('pvhip_input_preprocess_roi_f32', *where, c, *staged.extent, *dst_hw, *largest, *how, *pre)
-        elif fmt.yuv:
-            device.call('pvhip_input_preprocess_yuv_f32', src, dst, n, *staged.extent, *dst_hw, *how, *pre)
-        elif fmt.packed:
-            device.call('pvhip_input_preprocess_packed_f32', src, dst, n, *staged.extent, *dst_hw, *how, *pre)
-        elif staged.preprocess:
-            device.call('pvhip_input_preprocess_f32', src, dst, n, c, *staged.extent, *dst_hw, *how, *pre)
-        elif staged.staging is not fixed:
-            device.call('pvhip_input_to_nchw_f32', src, dst, *fixed.shape, *how)
+    _STAGERS = {RoiInput: _stage_rois, DetectedRois: _stage_detected, WarpInput: _stage_matrices, PerspectiveInput: _stage_matrices,
+                LandmarkWarps: _stage_landmarks}
 
     def stage(self, inputs: dict, stream_base: int, sharded: bool = False) -> dict:
         """`inputs` with every host input of a declared format, or in one of this request's own buffers, replaced by the request's fixed
         tensor: the caller's array is copied into the page-locked buffer of its extent unless it IS that buffer, the buffer is uploaded on
-        the copy stream, stream `stream_base` waits for the copy's event and converts (_convert: one launch at the most).  A RoiInput's
-        frames and table go the same way, both uploaded on the copy stream behind the one event, and so do a WarpInput's and a PerspectiveInput's.  A DetectedRois' frames too -- with its
-        labels, and its records when they are a host array --; its table is made by pvhip_detections_to_rois on `stream_base`, behind the
-        detector's pass when the records are the Result of a request in flight, and the ROI launch is sized for whole frames: the host
-        never sees the table (`sharded`: the batch is sharded over ranks, which a DetectedRois refuses).  A LandmarkWarps' frames likewise
-        -- with its template, once, and its points and regions when they are host arrays --; its table is fitted by
-        pvhip_landmarks_to_warps on `stream_base`, behind the landmark pass when the points are the Result of a request in flight, and the
-        warp launch reads it unchanged.  That launch may read ANOTHER request's region table: it leaves an event in that slot's
+        the copy stream, stream `stream_base` waits for the copy's event and converts (InputFormat.conversion: one launch at the most).
+        A FrameFeed goes the same way through its stager (_STAGERS): its frames, and what it uploads beside them -- the table of a
+        RoiInput, a WarpInput or a PerspectiveInput; a DetectedRois' labels, and its records when they are a host array; a LandmarkWarps'
+        template, once, and its points and regions when they are host arrays --, all on the copy stream behind the one event.  The
+        table of a DetectedRois or a LandmarkWarps is made by the stager's launch on `stream_base` in front of the conversion, behind
+        the other request's pass when it reads the Result of one in flight: the host never sees it (`sharded`: the batch is sharded over
+        ranks, which both refuse).  A LandmarkWarps' launch may read ANOTHER request's region table: it leaves an event in that slot's
         `table_readers`, and the copy stream and `stream_base` wait for those before this call uploads or makes a table for the slot.
         Every other input is returned unchanged (and goes the default way).  All but the MAX_SOURCE_EXTENTS most recently fed extents
         of an input are released here: the request has no pass in flight, so nothing reads those buffers any more."""
         out = dict(inputs)
         for name, arr in inputs.items():
-            fmt, largest, uploads, make_table, make_warps = self.formats.get(name), None, (), None, None
-            warped = 'perspective' if isinstance(arr, PerspectiveInput) else isinstance(arr, WarpInput)
-            if warped:
-                staged = self._stage_warps(name, self._format(name), arr)
-                slot = self.slots[name]
-                uploads = ((slot.perspectives, slot.perspectives_host) if warped == 'perspective' else (slot.warps, slot.warps_host),)
-            elif isinstance(arr, RoiInput):
-                staged, largest = self._stage_rois(name, self._format(name), arr)
-                uploads = ((self.slots[name].rois, self.slots[name].rois_host),)
-            elif isinstance(arr, DetectedRois):
-                staged, uploads, make_table = self._stage_detected(name, self._format(name), arr, sharded)
-                largest = staged.extent                       # the host does not know the largest rectangle: the frame bounds it
-            elif isinstance(arr, LandmarkWarps):
-                staged, uploads, make_warps = self._stage_landmarks(name, self._format(name), arr, sharded)
-                warped = True
+            fmt = self.formats.get(name)
+            stager = self._STAGERS.get(type(arr))
+            if stager is None and isinstance(arr, FrameFeed):     # (a subclass of one of the five)
+                stager = next(self._STAGERS[cls] for cls in type(arr).__mro__ if cls in self._STAGERS)
+            if stager is not None:
+                staged = stager(self, name, self._format(name), arr, sharded)
             elif fmt is None or isinstance(arr, (device.DeviceTensor, device.ChannelSlice, device.BlockedHalf)):
                 if name in self.slots:
                     self.slots[name].fed = self.slots[name].last = None
@@ -555,38 +472,37 @@ class HostInputs:
                     if name in self.slots:
                         self.slots[name].last = None
                     continue
-            slot = self.slots[name]
-            slot.fed = staged.extent if largest is None and not warped else None
-            slot.last = 'warp' if warped else 'table' if largest is not None else 'images'
-            if slot.table_readers:                            # launches of other requests still read `rois`: nothing overwrites it before them
+                staged = _Staged(staged, (), None, None, None)
+            slot, (staging, uploads, launch, largest, kind) = self.slots[name], staged
+            slot.fed = staging.extent if kind is None else None
+            slot.last = 'images' if kind is None else 'table' if arr.RECTANGLES else 'warp'
+            if slot.table_readers:                            # launches of other requests still read the table: nothing overwrites it before them
                 readers, slot.table_readers = slot.table_readers, []
                 for stream in (device.COPY_STREAM, stream_base):
                     device.select_stream(stream)
                     for event in readers:
                         event.wait()
-            slot.extents.move_to_end(staged.key)
+            slot.extents.move_to_end(staging.key)
             while len(slot.extents) > self.MAX_SOURCE_EXTENTS:
                 slot.extents.popitem(last=False)
             device.select_stream(device.COPY_STREAM)
-            device.call('pvhip_memcpy_h2d_async', device.ptr(staged.staging), ctypes.c_void_p(staged.host.ctypes.data), staged.host.nbytes)
-            for dst, host in uploads:
+            for dst, host in ((staging.staging, staging.host), *uploads):
                 device.call('pvhip_memcpy_h2d_async', device.ptr(dst), ctypes.c_void_p(host.ctypes.data), host.nbytes)
             slot.event.record()
             device.select_stream(stream_base)
             slot.event.wait()
-            if slot.detected is not None:
-                slot.detected.live = make_table is not None
-                if make_table is None:
-                    slot.detected.source = None
-            if slot.landmarks is not None:
-                slot.landmarks.live = make_warps is not None
-                if make_warps is None:
-                    slot.landmarks.source = slot.landmarks.regions_source = None
-            if make_table is not None:
-                make_table()
-            if make_warps is not None:
-                make_warps()
-            self._convert(fmt, slot, staged, largest, warped)
+            for feed, producer in slot.producers.items():
+                producer.live = isinstance(arr, feed)
+                if not producer.live:
+                    producer.sources = ()
+            if launch is not None:
+                launch()
+            entry, args = fmt.conversion(staging.extent, staging.frames, largest, kind)
+            if entry is not None:
+                ptr, table = device.ptr, slot.tables.get(kind)
+                operands = {'src': ptr(staging.staging), 'dst': ptr(slot.fixed), 'table': ptr(table and table.device), 'mean': ptr(slot.mean),
+                            'std': ptr(slot.std), 'NULL': NULL}
+                device.call(entry, *map(operands.get, args, args))      # (every argument that is no operand's name stands for itself)
             device.select_stream(0)
             out[name] = slot.fixed
         return out

@@ -1,8 +1,11 @@
 """The format a caller hands a network input in: what is declared between ``read_network`` and ``load_network`` (InputInfo, PreProcessInfo,
 PreProcessChannel: OpenVINO 2021's ``IENetwork.input_info``) and the fixed value it becomes at load (InputFormat), which owns the shape
-arithmetic of that format.  Host only: nothing here touches the device (host_input.py stages arrays of these formats)."""
+arithmetic of that format and the choice of the launch that converts it (``InputFormat.conversion``); and the inputs given as frames
+and a rule per batch row instead of images (FrameFeed: RoiInput, DetectedRois, WarpInput, PerspectiveInput, LandmarkWarps), each
+stating what the format checks of it.  Host only: nothing here touches the device (host_input.py stages arrays of these formats)."""
 import collections
 import dataclasses
+import functools
 
 import numpy as np
 
@@ -45,9 +48,10 @@ class InputFormat:
     (n, 3 h / 2, w), or 'YUY2' / 'UYVY' for packed YUV 4:2:2 frames, uint8 of shape (n, h, w, 2), or 'BGRX' / 'RGBX' for four-byte
     pixels, uint8 of shape (n, h, w, 4), whatever ``u8`` / ``nhwc`` say; ``standard`` / ``full_range`` the declared matrix ('BT601', 'BT709',
     'BT2020') and range of a YUV format's frames, which ``color_rule`` hands every launch that converts them -- a plain pass, a RoiInput, a
-    DetectedRois, a WarpInput, a PerspectiveInput and a fitted input alike: the rule belongs to the format, not to the feed.  An extent is the (h, w) of a caller's image.  A RoiInput's frames have the same
-    shapes with their own count m in place of n (``host_shape(extent, frames=m)``, ``frames_extent_of``) and a table ``checked_rois``
-    accepts."""
+    DetectedRois, a WarpInput, a PerspectiveInput and a fitted input alike: the rule belongs to the format, not to the feed.  An extent is the (h, w) of a caller's image.  A FrameFeed's frames have the same
+    shapes with their own count m in place of n (``host_shape(extent, frames=m)``, ``frames_extent_of``); a RoiInput's table is what
+    ``checked_rois`` accepts, a WarpInput's or a PerspectiveInput's what ``checked_matrices`` makes (in the request's own buffer:
+    ``checked_matrix_table``).  ``conversion`` names the launch and its arguments for an extent and a feed."""
     name: str
     dims: tuple
     supported: bool
@@ -181,24 +185,25 @@ class InputFormat:
                 self.name, declared, self.host_shape(('h', 'w')), self._packed_any_hw(), a.shape))
         return self.checked_extent(a.shape[1:3])
 
-    def _roi_declared(self, what='RoiInput is cropped and resized'):
+    def resize_declared(self, feed=None):
+        """ValueError unless a resize is declared: every FrameFeed needs one (`feed`: the class the text names; default: RoiInput)."""
+        feed = feed or RoiInput
         if not self.resize:
-            raise ValueError('input {}: a {} on the device: it needs a declared resize '
-                             '(preprocess_info.resize_algorithm = \'RESIZE_BILINEAR\')'.format(self.name, what))
+            raise ValueError('input {}: a {} {} on the device: it needs a declared resize '
+                             '(preprocess_info.resize_algorithm = \'RESIZE_BILINEAR\')'.format(self.name, feed.__name__, feed.HOW))
 
     def checked_frames(self, frames) -> int:
         """The frame count m of a RoiInput as an int >= 1 (any count: it is independent of the batch)."""
-        self._roi_declared()
+        self.resize_declared()
         if isinstance(frames, bool) or not isinstance(frames, (int, np.integer)) or frames < 1:
             raise ValueError('input {}: a RoiInput has m >= 1 frames, not {!r}'.format(self.name, frames))
         return int(frames)
 
-    def frames_extent_of(self, a, what='RoiInput'):
-        """((h, w), m) of the frames array `a` of a RoiInput (`what`: of a WarpInput or a PerspectiveInput), checked against this format."""
-        if what == 'RoiInput':
-            self._roi_declared()
-        else:
-            self._roi_declared(what + ' is sampled')
+    def frames_extent_of(self, a, feed=None):
+        """((h, w), m) of the frames array `a` of a FrameFeed (`feed`: the class the texts name; default: RoiInput), checked against
+        this format."""
+        self.resize_declared(feed)
+        what = (feed or RoiInput).__name__
         if self.yuv:
             ok = a.ndim == 3 and a.shape[0] >= 1 and a.shape[1] % 3 == 0
             declared, any_hw = 'declared {}'.format(self.color), 'any even h, w'
@@ -219,7 +224,7 @@ class InputFormat:
         """The table of a RoiInput over `frames` frames of `extent` as a C-contiguous int32 (n, 5) array, and the (max h, max w) of its
         rectangles: row b = (id, x, y, w, h), the order of OpenVINO's ROI struct, is the rectangle [y, y + h) x [x, x + w) of frame id
         that becomes batch row b.  Integers only, 0 <= id < frames, w, h >= 1 and the rectangle inside the frame."""
-        self._roi_declared()
+        self.resize_declared()
         t = np.asarray(rois)
         n, (H, W) = self.dims[0], extent
         if t.shape != (n, 5):
@@ -238,12 +243,9 @@ class InputFormat:
                 self.name, b, tuple(int(v) for v in t[b]), frames, (H, W)))
         return np.ascontiguousarray(t, np.int32), (int(h.max()), int(w.max()))
 
-    def warp_declared(self):
-        self._roi_declared('WarpInput is sampled')
-
-    def _checked_warp_ids(self, ids, frames):
-        """The frame of every row of a WarpInput over `frames` frames as n ints in [0, frames): `ids`, or by default row b's frame b
-        (frames == n) or frame 0 (frames == 1)."""
+    def _checked_ids(self, ids, frames):
+        """The frame of every row of a WarpInput or a PerspectiveInput over `frames` frames as n ints in [0, frames): `ids`, or by default
+        row b's frame b (frames == n) or frame 0 (frames == 1)."""
         n = self.dims[0]
         if ids is None:
             if frames != n and frames != 1:
@@ -262,65 +264,63 @@ class InputFormat:
             raise ValueError('input {}: ids[{}] = {} is none of {} frames'.format(self.name, b, int(i[b]), frames))
         return i
 
-    def checked_warps(self, matrices, ids, frames):
-        """The table of a WarpInput over `frames` frames as a C-contiguous int64 (n, 7) array, row b = (id, A00, A01, C0, A10, A11, C1):
-        ``WarpInput.fixed(matrices)`` behind the frame of each row (`ids`, or its default)."""
-        self.warp_declared()
+    def checked_matrices(self, feed, matrices, ids, frames):
+        """The table of a `feed` (WarpInput or PerspectiveInput, the class) over `frames` frames as a C-contiguous int64 (n, feed.COLUMNS)
+        array: row b is the frame of the row (`ids`, or its default) in front of ``feed.fixed(matrices, the network's extent)``."""
+        self.resize_declared(feed)
         n = self.dims[0]
         try:
-            q = WarpInput.fixed(matrices)
+            q = feed.fixed(matrices, self.dims[2:])
         except ValueError as e:
             raise ValueError('input {}: {}'.format(self.name, e)) from None
         if q.shape[0] != n:
-            raise ValueError('input {}: matrices has shape {} -- one 2 x 3 matrix per batch row --, got {}'.format(
-                self.name, (n, 2, 3), np.shape(matrices)))
-        table = np.empty((n, 7), np.int64)
-        table[:, 0] = self._checked_warp_ids(ids, frames)
+            raise ValueError('input {}: matrices has shape {} -- one {} x {} matrix per batch row --, got {}'.format(
+                self.name, (n,) + feed.MATRIX, *feed.MATRIX, np.shape(matrices)))
+        table = np.empty((n, feed.COLUMNS), np.int64)
+        table[:, 0] = self._checked_ids(ids, frames)
         table[:, 1:] = q
         return table
 
-    def checked_warp_table(self, table, frames):
-        """`table`, an int64 (n, 7) array already in the device's form (``InferRequest.warp_buffer``), checked by the limits of
-        ``WarpInput.fixed`` and ``ids``; returned as it is."""
-        self.warp_declared()
-        bad = WarpInput.beyond_limits(table[:, 1:])
+    def checked_matrix_table(self, feed, table, frames):
+        """`table`, an int64 (n, feed.COLUMNS) array already in the device's form (``InferRequest.warp_buffer`` / ``perspective_buffer``),
+        checked by the limits of ``feed.fixed`` over the network's extent and by ``ids``; returned as it is."""
+        self.resize_declared(feed)
+        bad = feed.beyond_limits(table[:, 1:], self.dims[2:])
         if bad.any():
             b = int(np.argmax(bad))
-            raise ValueError('input {}: {}'.format(self.name, WarpInput.limit_text(b, table[b, 1:])))
-        self._checked_warp_ids(table[:, 0], frames)
+            raise ValueError('input {}: {}'.format(self.name, feed.limit_text(b, table[b, 1:], self.dims[2:])))
+        self._checked_ids(table[:, 0], frames)
         return table
 
-    def perspective_declared(self):
-        self._roi_declared('PerspectiveInput is sampled')
-
-    def checked_perspectives(self, matrices, ids, frames):
-        """The table of a PerspectiveInput over `frames` frames as a C-contiguous int64 (n, 10) array, row b = (id, Q00, Q01, Q02, Q10,
-        Q11, Q12, Q20, Q21, Q22): ``PerspectiveInput.fixed(matrices, the network's extent)`` behind the frame of each row (`ids`, or
-        its default)."""
-        self.perspective_declared()
-        n = self.dims[0]
-        try:
-            q = PerspectiveInput.fixed(matrices, self.dims[2:])
-        except ValueError as e:
-            raise ValueError('input {}: {}'.format(self.name, e)) from None
-        if q.shape[0] != n:
-            raise ValueError('input {}: matrices has shape {} -- one 3 x 3 matrix per batch row --, got {}'.format(
-                self.name, (n, 3, 3), np.shape(matrices)))
-        table = np.empty((n, 10), np.int64)
-        table[:, 0] = self._checked_warp_ids(ids, frames)
-        table[:, 1:] = q
-        return table
-
-    def checked_perspective_table(self, table, frames):
-        """`table`, an int64 (n, 10) array already in the device's form (``InferRequest.perspective_buffer``), checked by the limit of
-        ``PerspectiveInput.fixed`` over the network's extent and ``ids``; returned as it is."""
-        self.perspective_declared()
-        bad = PerspectiveInput.beyond_limits(table[:, 1:], self.dims[2:])
-        if bad.any():
-            b = int(np.argmax(bad))
-            raise ValueError('input {}: {}'.format(self.name, PerspectiveInput.limit_text(b, table[b, 1:], self.dims[2:])))
-        self._checked_warp_ids(table[:, 0], frames)
-        return table
+    @functools.lru_cache(maxsize=1024)                         # (a pure function of the format and hashable arguments, asked every pass)
+    def conversion(self, extent, frames=None, largest=None, kind=None) -> tuple:
+        """(entry, arguments) of the one launch that makes the fp32 NCHW tensor of arrays of `extent`, the operands as the names 'src',
+        'dst', 'table', 'mean', 'std' and 'NULL' (host_input.py puts the addresses in); (None, ()) for FP32 NCHW at the network's extent
+        with nothing declared besides: the upload is the tensor.  `frames` = m and `kind`: a FrameFeed's frames and FrameFeed.KIND;
+        `largest` = (max_h, max_w) of its rectangles for 'roi' (for a DetectedRois the frame: the host does not know them).  The entry is
+        pvhip_input_preprocess_<family><form>f32: family 'yuv_' for NV12 / I420 frames, 'packed_' for YUY2 / UYVY / BGRX / RGBX ones, ''
+        for the rest; form 'roi_' with a table of rectangles, 'fit_' -- with the table or NULL -- under a declared fit that places
+        anything, 'color_' -- the table or NULL, the fit or 0 -- for a colour rule other than BT.601 limited range, '' for whole
+        images.  A 'warp' or a 'perspective' is pvhip_input_preprocess_<kind>[_color]_f32 for every format, whatever fit is declared.
+        A bare change of precision or layout is pvhip_input_to_nchw_f32."""
+        n, c, hd, wd = self.dims
+        how = (int(self.color == 'I420'),) if self.yuv else (self.packed_kind,) if self.packed else (int(self.u8), int(self.nhwc))
+        pre = (int(self.reverse), 'mean' if self.mean is not None else 'NULL', 'std' if self.std is not None else 'NULL')
+        rule = () if self.default_rule else self.color_rule
+        if kind in ('warp', 'perspective'):
+            form = (1, how[0]) if self.yuv else (2, how[0]) if self.packed else (0, how[0] | how[1] << 1)
+            return ('pvhip_input_preprocess_{}{}_f32'.format(kind, '_color' if rule else ''),
+                    ('src', 'dst', 'table', n, frames, c, *extent, hd, wd, *form, *pre, self.pad, *rule))
+        roi = largest is not None
+        family = 'yuv_' if self.yuv else 'packed_' if self.packed else ''
+        changed = bool(family) or self.needs_preprocess(extent)
+        form = 'color_' if rule else 'fit_' if self.fitted and (roi or changed) else 'roi_' if roi else ''
+        if not form and not changed:
+            return ('pvhip_input_to_nchw_f32', ('src', 'dst', *self.dims, *how)) if frames is not None or self.needs_convert(extent) else (None, ())
+        where = ('src', 'dst', 'table' if roi else 'NULL', n, frames if roi else n) if form else ('src', 'dst', n)
+        sizes = (*extent, hd, wd, *((largest if roi else extent) if form else ()))
+        fit = (self.fit_code, self.pad) if form in ('fit_', 'color_') else ()
+        return 'pvhip_input_preprocess_' + family + form + 'f32', (*where, *(() if family else (c,)), *sizes, *how, *pre, *fit, *rule)
 
     def needs_preprocess(self, extent) -> bool:
         """Arrays of `extent` go through pvhip_input_preprocess_f32 (YUV 4:2:0 frames: pvhip_input_preprocess_yuv_f32, frames of 4-byte
@@ -335,7 +335,18 @@ class InputFormat:
         return self.needs_preprocess(extent) or self.u8 or self.nhwc
 
 
-class RoiInput:
+class FrameFeed:
+    """A network input given as m >= 1 source frames in the input's declared host format -- the leading count is m, whatever the batch n
+    -- and a rule that makes each batch row of them on the device: what RoiInput, DetectedRois, WarpInput, PerspectiveInput and
+    LandmarkWarps share.  ``HOW``: what the device does with the frames, as the "needs a declared resize" error says it; ``RECTANGLES``:
+    every row is a rectangle (id, x, y, w, h) of a frame, so points in the row can be normalised to it -- no row of a sampled feed has
+    one; ``KIND``: the conversion its rows go through and the table of the request they are read from, 'roi', 'warp' or 'perspective'
+    (``InputFormat.conversion``)."""
+    __slots__ = ()             # (every feed names `frames` first among its own)
+    HOW, RECTANGLES, KIND = 'is sampled', False, 'warp'
+
+
+class RoiInput(FrameFeed):
     """A network input given as regions of interest (OpenVINO 2021's ROI blobs, ``make_shared_blob(frame, ROI{id, posX, posY, sizeX,
     sizeY})``): ``infer({name: RoiInput(frames, rois)})``.  `frames`: m >= 1 source frames in the input's declared host format -- the
     leading count is m, whatever the batch n --; `rois`: an integer (n, 5) table, row b = (id, x, y, w, h): batch row b is the rectangle
@@ -346,6 +357,7 @@ class RoiInput:
     origin and odd sizes (only the frame's extent is even), and so may a YUY2 / UYVY one (only the frame's width is even).  With `frames` = ``InferRequest.input_buffer(name, (h, w), frames=m)`` and
     `rois` = ``InferRequest.roi_buffer(name)`` nothing is copied on the host."""
     __slots__ = ('frames', 'rois')
+    HOW, RECTANGLES, KIND = 'is cropped and resized', True, 'roi'
 
     def __init__(self, frames, rois):
         self.frames, self.rois = frames, rois
@@ -354,7 +366,7 @@ class RoiInput:
         return 'RoiInput(frames={}, rois={})'.format(getattr(self.frames, 'shape', None), getattr(self.rois, 'shape', None))
 
 
-class WarpInput:
+class WarpInput(FrameFeed):
     """A network input given as affine warps of frames (a face aligned by its eye line, a plate cut along its own axis, a rotated box, a
     mirrored copy): ``infer({name: WarpInput(frames, matrices, ids)})``, wherever a RoiInput is accepted.  `frames`: m >= 1 source
     frames in the input's declared host format, exactly as for RoiInput (every format: U8 / FP32, NHWC / NCHW, NV12, I420, YUY2, UYVY,
@@ -375,6 +387,7 @@ class WarpInput:
     = ``InferRequest.warp_buffer(name)`` -- the (n, 7) int64 table (id, A00, A01, C0, A10, A11, C1) itself, `ids` None -- nothing
     is copied on the host."""
     __slots__ = ('frames', 'matrices', 'ids')
+    MATRIX, COLUMNS, BUFFER = (2, 3), 7, 'warp'      # a row's matrix, its row of the table (id, A00 .. C1), InferRequest.warp_buffer
     LINEAR_LIMIT = 1 << 26           # |A| at most: a scale of 1024
     TRANSLATION_LIMIT = 1 << 40      # |C| at most: 2^24 pixels
 
@@ -385,18 +398,19 @@ class WarpInput:
         return 'WarpInput(frames={}, matrices={})'.format(getattr(self.frames, 'shape', None), getattr(self.matrices, 'shape', None))
 
     @classmethod
-    def beyond_limits(cls, q):
-        """Which rows of (n, 6) Q16 coefficients (A00, A01, C0, A10, A11, C1), int64 or float64, break a limit."""
+    def beyond_limits(cls, q, dst_hw=None):
+        """Which rows of (n, 6) Q16 coefficients (A00, A01, C0, A10, A11, C1), int64 or float64, break a limit (whatever the extent
+        `dst_hw`: PerspectiveInput's three operations take the same arguments and use it)."""
         a, c = q[:, [0, 1, 3, 4]], q[:, [2, 5]]               # (no np.abs: the smallest int64 has none)
         return ((a > cls.LINEAR_LIMIT) | (a < -cls.LINEAR_LIMIT)).any(1) | ((c > cls.TRANSLATION_LIMIT) | (c < -cls.TRANSLATION_LIMIT)).any(1)
 
     @staticmethod
-    def limit_text(b, row):
+    def limit_text(b, row, dst_hw=None):
         return ('matrices[{}] is beyond the limits of a warp -- finite, |a| <= 1024 for the four linear terms, |c| <= 2^24 for the '
                 'translations --: in Q16 {}'.format(b, [float(v) for v in row]))
 
     @classmethod
-    def fixed(cls, matrices) -> np.ndarray:
+    def fixed(cls, matrices, dst_hw=None) -> np.ndarray:
         """(n, 6) int64: the coefficients (a00, a01, c0, a10, a11, c1) of every row in Q16, ``np.rint(np.float64(v) * 65536)`` (ties to
         even), as the device takes them.  ValueError, naming the row, for a value that is not finite, |A| > 2^26 for a linear term or
         |C| > 2^40 for a translation: with these limits A00 x + A01 y + C0 cannot overflow int64 for any extent a launch admits.  Host
@@ -416,7 +430,7 @@ class WarpInput:
         return q.astype(np.int64)
 
 
-class PerspectiveInput:
+class PerspectiveInput(FrameFeed):
     """A network input given as homographies of frames (a plate seen from the kerb, a document on a desk, a sign or a screen seen at an
     angle, a road or court plane rectified to a bird's-eye view: four corners in the frame, not a rotated rectangle):
     ``infer({name: PerspectiveInput(frames, matrices, ids)})``, wherever a WarpInput is accepted.  `frames` and `ids`: exactly as for
@@ -436,6 +450,7 @@ class PerspectiveInput:
     ``InferRequest.input_buffer(name, (h, w), frames=m)`` and `matrices` = ``InferRequest.perspective_buffer(name)`` -- the (n, 10)
     int64 table (id, Q00, Q01, Q02, Q10, Q11, Q12, Q20, Q21, Q22) itself, `ids` None -- nothing is copied on the host."""
     __slots__ = ('frames', 'matrices', 'ids')
+    MATRIX, COLUMNS, BUFFER, KIND = (3, 3), 10, 'perspective', 'perspective'     # (id, Q00 .. Q22), InferRequest.perspective_buffer
     FORM_LIMIT = 1 << 52             # |Q_r0| (wd - 1) + |Q_r1| (hd - 1) + |Q_r2| at most, for each row r of a matrix
 
     def __init__(self, frames, matrices, ids=None):
@@ -489,7 +504,7 @@ class PerspectiveInput:
         return q.astype(np.int64)
 
 
-class DetectedRois:
+class DetectedRois(FrameFeed):
     """A network input given as the regions another network detected (a cascade: detector, then classifier, both on this GPU):
     ``start_async({name: DetectedRois(frames, detections)})``, wherever a RoiInput is accepted.  `frames`: as for RoiInput.  `detections`:
     DetectionOutput records [rank, label, score, xmin, ymin, xmax, ymax] with normalised corners, as
@@ -512,6 +527,7 @@ class DetectedRois:
     The detector may be started again as soon as ``start_async`` of this input has returned: its next pass waits, on the device, until
     the table has been made.  ``detector.wait()`` may come before or after that ``start_async``."""
     __slots__ = ('frames', 'detections', 'output', 'images', 'min_confidence', 'labels', 'min_size', 'detector_fit')
+    HOW, RECTANGLES, KIND = RoiInput.HOW, True, 'roi'
     MAX_LABELS = 64
 
     def __init__(self, frames, detections, output=None, images=None, min_confidence=0.5, labels=None, min_size=(1, 1), detector_fit=None):
@@ -557,7 +573,7 @@ class DetectedRois:
         return int(shape[-2]) // int(images)
 
 
-class LandmarkWarps:
+class LandmarkWarps(FrameFeed):
     """A network input given as crops aligned by the points another network found (a cascade: detector, crops, a landmark regressor on
     the crops, then the aligned crop into a recognition or attribute network, all on this GPU):
     ``start_async({name: LandmarkWarps(frames, landmarks, template)})``, wherever a WarpInput is accepted, for every declared host

@@ -275,11 +275,11 @@ class Ask(collections.namedtuple('Ask', 'screen tiles frames slot')):
 
     def launch(self, blocks, value):
         blocks = blocks or Blocks(self.tiles, value.shape[-2] // self.tiles, self.frames, self.screen)
-        blocks.launch(value, self.slot.rois)
+        blocks.launch(value, self.slot.tables['roi'].device)
         return blocks
 
     def on_host(self, value):
-        return merge_tiles(value, self.slot.rois_host, self.frames, self.screen)
+        return merge_tiles(value, self.slot.tables['roi'].host, self.frames, self.screen)
 
 
 class RegionAsk(collections.namedtuple('RegionAsk', 'screen tiles frames slot net_hw fit table_of detected')):
@@ -296,9 +296,9 @@ class RegionAsk(collections.namedtuple('RegionAsk', 'screen tiles frames slot ne
 
     def launch(self, blocks, value):
         blocks = blocks or RegionBlocks(self.tiles, value.shape[-2] // self.tiles, self.frames, self.screen)
-        blocks.launch(value, self.slot.rois, self.net_hw[0], self.net_hw[1], RESIZE_FITS[self.fit])
+        blocks.launch(value, self.slot.tables['roi'].device, self.net_hw[0], self.net_hw[1], RESIZE_FITS[self.fit])
         return blocks
 
     def on_host(self, value):
-        table = self.table_of().rois if self.detected else self.slot.rois_host
+        table = self.table_of().rois if self.detected else self.slot.tables['roi'].host
         return merge_regions(value, table, self.frames, self.screen, self.net_hw, self.fit)

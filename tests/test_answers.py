@@ -53,7 +53,7 @@ def test_the_stage_on_host_values():
     opt = dict(opt, threshold=0.1, per_label=False)            # (so that the random boxes suppress each other)
     asks = answers.checked({name: roi}, None, {out_name: TiledScreen(**opt)}, False)
     assert type(asks[out_name]) is tiled_detections.Ask and asks[out_name].frames is None and asks[out_name].tiles == 4
-    ex.host_inputs.slots[name] = types.SimpleNamespace(rois_host=TABLE.copy(), rois=None)
+    ex.host_inputs.slots[name] = types.SimpleNamespace(tables={'roi': types.SimpleNamespace(host=TABLE.copy(), device=None)})
     try:
         asks = answers.bound(asks, {name: roi})
         assert asks[out_name].frames == 2 and asks[out_name].key(out_name) == (out_name, asks[out_name].screen, 2)

@@ -232,17 +232,17 @@ def test_perspective_input_argument_rules(kind):
     ex = ie.load_network(net)
     rng = np.random.default_rng(3)
     M = rng.uniform(-2, 2, (n, 3, 3))
-    t = fmt.checked_perspectives(M, IDS, 3)
+    t = fmt.checked_matrices(PerspectiveInput, M, IDS, 3)
     assert t.dtype == np.int64 and t.shape == (n, 10) and t.flags.c_contiguous
     assert t[:, 0].tolist() == IDS and np.array_equal(t[:, 1:], PerspectiveInput.fixed(M, dst)) and np.array_equal(t, pref.table_of(M, IDS, dst))
-    assert fmt.checked_perspectives(M, None, n)[:, 0].tolist() == [0, 1, 2, 3]
-    assert fmt.checked_perspectives(M.tolist(), None, 1)[:, 0].tolist() == [0, 0, 0, 0]
+    assert fmt.checked_matrices(PerspectiveInput, M, None, n)[:, 0].tolist() == [0, 1, 2, 3]
+    assert fmt.checked_matrices(PerspectiveInput, M.tolist(), None, 1)[:, 0].tolist() == [0, 0, 0, 0]
     dtype = fmt.host_dtype
 
     def refused(match, matrices, ids, m):
         frames = np.zeros(wt._frame_shape(kind, m, hw), dtype)
         with pytest.raises(ValueError, match=match) as by_format:
-            fmt.checked_perspectives(matrices, ids, m)
+            fmt.checked_matrices(PerspectiveInput, matrices, ids, m)
         with pytest.raises(ValueError) as by_infer:
             ex.infer({name: PerspectiveInput(frames, matrices, ids)})
         assert str(by_format.value) == str(by_infer.value) and str(by_infer.value).startswith('input {}: '.format(name))
@@ -261,19 +261,19 @@ def test_perspective_input_argument_rules(kind):
     refused(r'matrices\[2\] is no homography', bad, IDS, 3)
     assert not ex.host_inputs.slots                           # nothing was allocated
     # a table already in the device's form (the perspective_buffer): the limit over the network's extent, and the ids
-    assert fmt.checked_perspective_table(t, 3) is t
+    assert fmt.checked_matrix_table(PerspectiveInput, t, 3) is t
     for column, value, match in ((1, 1 << 52, r'matrices\[2\] is beyond the limit'), (9, -(1 << 52) - 1, r'matrices\[2\]'),
                                  (5, np.iinfo(np.int64).min, r'matrices\[2\]'), (0, 3, r'ids\[2\] = 3'), (0, -1, r'ids\[2\] = -1')):
         over = t.copy()
         over[2, column] = value
         with pytest.raises(ValueError, match='^input {}: {}'.format(name, match)):
-            fmt.checked_perspective_table(over, 3)
+            fmt.checked_matrix_table(PerspectiveInput, over, 3)
     ok = np.zeros(wt._frame_shape(kind, 3, hw), dtype)
     for shape in (ok.shape[1:], (0,) + ok.shape[1:]):
         with pytest.raises(ValueError, match='frames of a PerspectiveInput') as by_infer:
             ex.infer({name: PerspectiveInput(np.zeros(shape, dtype), M, IDS)})
         with pytest.raises(ValueError) as by_format:
-            fmt.frames_extent_of(np.zeros(shape, dtype), 'PerspectiveInput')
+            fmt.frames_extent_of(np.zeros(shape, dtype), PerspectiveInput)
         assert str(by_format.value) == str(by_infer.value)
     with pytest.raises(KeyError):
         ex.infer({'no such input': PerspectiveInput(ok, M, IDS)})
@@ -297,8 +297,8 @@ def test_perspective_input_needs_a_declared_resize(kind):
     M = np.stack([IDENTITY] * n, 0)
     with pytest.raises(ValueError, match='a PerspectiveInput is sampled on the device.*resize_algorithm') as by_infer:
         ex.infer({name: PerspectiveInput(frames, M)})
-    for refused in (lambda: fmt.checked_perspectives(M, None, 1), lambda: fmt.perspective_declared(),
-                    lambda: ex.requests[0].perspective_buffer(name), lambda: fmt.checked_perspective_table(np.zeros((n, 10), np.int64), 1)):
+    for refused in (lambda: fmt.checked_matrices(PerspectiveInput, M, None, 1), lambda: fmt.resize_declared(PerspectiveInput),
+                    lambda: ex.requests[0].perspective_buffer(name), lambda: fmt.checked_matrix_table(PerspectiveInput, np.zeros((n, 10), np.int64), 1)):
         with pytest.raises(ValueError) as by_format:
             refused()
         assert str(by_format.value) == str(by_infer.value)
@@ -594,7 +594,7 @@ def test_perspective_buffer_feeds_without_a_host_copy(hip):
     assert tbuf.shape == (n, 10) and tbuf.dtype == np.int64 and tbuf.flags.c_contiguous and req.perspective_buffer(name) is tbuf
     assert ex.requests[0].perspective_buffer(name) is not tbuf
     slot = req.runner.host_inputs.slots[name]
-    assert tbuf is slot.perspectives_host and buf is slot.extents[(hw, m)].host
+    assert tbuf is slot.tables['perspective'].host and buf is slot.extents[(hw, m)].host
     buf[...] = frames
     tbuf[...] = pref.table_of(M, ids, dst)
     copies, staged = [], []

@@ -362,7 +362,7 @@ def test_the_stage_on_host_values(fit):
         asks = answers.checked({name: feed}, None, {out_name: RegionScreen(**opt)}, False)
         detected = isinstance(feed, DetectedRois)
         # (stage() fills the slot on a device; here by hand: a RoiInput's page-locked table, a DetectedRois' read-back)
-        ex.host_inputs.slots[name] = types.SimpleNamespace(rois_host=None if detected else table.copy(), rois=None)
+        ex.host_inputs.slots[name] = types.SimpleNamespace(tables={'roi': types.SimpleNamespace(host=None if detected else table.copy(), device=None)})
         asks[out_name] = asks[out_name]._replace(table_of=lambda: read.append(1) or input_format.DetectedTable(3, 3, behind.copy(), np.arange(4, dtype=np.int32)))
         try:
             asks = answers.bound(asks, {name: feed})

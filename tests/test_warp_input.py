@@ -234,18 +234,18 @@ def test_warp_input_argument_rules(kind):
     ex = ie.load_network(net)
     rng = np.random.default_rng(3)
     M = rng.uniform(-2, 2, (n, 2, 3))
-    t = fmt.checked_warps(M, IDS, 3)
+    t = fmt.checked_matrices(WarpInput, M, IDS, 3)
     assert t.dtype == np.int64 and t.shape == (n, 7) and t.flags.c_contiguous
     assert t[:, 0].tolist() == IDS and np.array_equal(t[:, 1:], WarpInput.fixed(M)) and np.array_equal(t, warp_ref.table_of(M, IDS))
-    assert fmt.checked_warps(M, None, n)[:, 0].tolist() == [0, 1, 2, 3]            # m == n: row b reads frame b
-    assert fmt.checked_warps(M.tolist(), None, 1)[:, 0].tolist() == [0, 0, 0, 0]   # m == 1: every row reads the frame
-    assert fmt.checked_warps(M, np.array(IDS, np.uint8), 3)[:, 0].tolist() == IDS
+    assert fmt.checked_matrices(WarpInput, M, None, n)[:, 0].tolist() == [0, 1, 2, 3]            # m == n: row b reads frame b
+    assert fmt.checked_matrices(WarpInput, M.tolist(), None, 1)[:, 0].tolist() == [0, 0, 0, 0]   # m == 1: every row reads the frame
+    assert fmt.checked_matrices(WarpInput, M, np.array(IDS, np.uint8), 3)[:, 0].tolist() == IDS
     dtype = fmt.host_dtype
 
     def refused(match, matrices, ids, m):
         frames = np.zeros(_frame_shape(kind, m, hw), dtype)
         with pytest.raises(ValueError, match=match) as by_format:
-            fmt.checked_warps(matrices, ids, m)
+            fmt.checked_matrices(WarpInput, matrices, ids, m)
         with pytest.raises(ValueError) as by_infer:
             ex.infer({name: WarpInput(frames, matrices, ids)})
         assert str(by_format.value) == str(by_infer.value) and str(by_infer.value).startswith('input {}: '.format(name))
@@ -266,25 +266,25 @@ def test_warp_input_argument_rules(kind):
     refused(r'matrices\[2\] is beyond the limits', big, IDS, 3)
     assert not ex.host_inputs.slots                           # nothing was allocated
     # a table already in the device's form (the warp_buffer): the same limits
-    assert fmt.checked_warp_table(t, 3) is t
+    assert fmt.checked_matrix_table(WarpInput, t, 3) is t
     for column, value, match in ((1, (1 << 26) + 1, r'matrices\[2\]'), (2, -(1 << 26) - 1, r'matrices\[2\]'), (3, (1 << 40) + 1, r'matrices\[2\]'),
                                  (6, -(1 << 40) - 1, r'matrices\[2\]'), (5, np.iinfo(np.int64).min, r'matrices\[2\]'),
                                  (4, np.iinfo(np.int64).max, r'matrices\[2\]'), (0, 3, r'ids\[2\] = 3'), (0, -1, r'ids\[2\] = -1')):
         bad = t.copy()
         bad[2, column] = value
         with pytest.raises(ValueError, match='^input {}: {}'.format(name, match)):
-            fmt.checked_warp_table(bad, 3)
+            fmt.checked_matrix_table(WarpInput, bad, 3)
     for column, value in ((1, 1 << 26), (2, -(1 << 26)), (3, 1 << 40), (6, -(1 << 40))):     # the limits themselves are inside
         edge = t.copy()
         edge[2, column] = value
-        fmt.checked_warp_table(edge, 3)
+        fmt.checked_matrix_table(WarpInput, edge, 3)
     # the frames: RoiInput's checks
     ok = np.zeros(_frame_shape(kind, 3, hw), dtype)
     for shape in (ok.shape[1:], (0,) + ok.shape[1:], ok.shape + (1,)):
         with pytest.raises(ValueError, match='frames of a WarpInput') as by_infer:
             ex.infer({name: WarpInput(np.zeros(shape, dtype), M, IDS)})
         with pytest.raises(ValueError) as by_format:
-            fmt.frames_extent_of(np.zeros(shape, dtype), 'WarpInput')
+            fmt.frames_extent_of(np.zeros(shape, dtype), WarpInput)
         assert str(by_format.value) == str(by_infer.value)
     with pytest.raises(KeyError):
         ex.infer({'no such input': WarpInput(ok, M, IDS)})
@@ -306,8 +306,8 @@ def test_warp_input_needs_a_declared_resize(kind):
     M = _translation(0, 0, n)
     with pytest.raises(ValueError, match='a WarpInput is sampled on the device.*resize_algorithm') as by_infer:
         ex.infer({name: WarpInput(frames, M)})
-    for refused in (lambda: fmt.checked_warps(M, None, 1), lambda: fmt.warp_declared(), lambda: ex.requests[0].warp_buffer(name),
-                    lambda: fmt.checked_warp_table(np.zeros((n, 7), np.int64), 1)):
+    for refused in (lambda: fmt.checked_matrices(WarpInput, M, None, 1), lambda: fmt.resize_declared(WarpInput), lambda: ex.requests[0].warp_buffer(name),
+                    lambda: fmt.checked_matrix_table(WarpInput, np.zeros((n, 7), np.int64), 1)):
         with pytest.raises(ValueError) as by_format:
             refused()
         assert str(by_format.value) == str(by_infer.value)
@@ -652,7 +652,7 @@ def test_warp_buffer_feeds_without_a_host_copy(hip):
     assert tbuf.shape == (n, 7) and tbuf.dtype == np.int64 and tbuf.flags.c_contiguous and req.warp_buffer(name) is tbuf
     assert ex.requests[0].warp_buffer(name) is not tbuf
     slot = req.runner.host_inputs.slots[name]
-    assert tbuf is slot.warps_host and buf is slot.extents[(hw, m)].host
+    assert tbuf is slot.tables['warp'].host and buf is slot.extents[(hw, m)].host
     buf[...] = frames
     tbuf[...] = _table(M, ids)
     copies = []
