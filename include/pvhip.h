@@ -646,6 +646,44 @@ int pvhip_topk_rows_f32(const float* x, int rows, int cols, int k, int* indices,
 int pvhip_gallery_match_f32(const float* x, int n, int d, const float* packed, int g, int k, int metric, int has_min_score,
                             float min_score, void* scratch, int* counts, int* indices, float* scores, double* norms);
 
+/* ---------------------------------------------------------------- a heatmap network's answer ---- */
+/* Addition to ABI v19 (the version number is unchanged: nothing existing changed): the peak of every plane of a contiguous (n, k, h, w)
+ * fp32 stack of heatmaps -- what a user of a landmark, pose or corner head makes on the host with an argmax per plane after reading
+ * 4 n k h w bytes back -- so that only 16 bytes per plane are read back.  The rule (pyopenvino_amd/keypoints.py states the same one in
+ * numpy and tests/keypoints_ref.py in plain loops, matched bit for bit), for the plane v[0..h)[0..w) of batch row r and channel c:
+ *   1. peak    p is the first position of the plane's h * w values in the total order of pvhip_topk_rows_f32 above: NaN of any sign or
+ *      payload first, then descending with +0.0 == -0.0, ties to the lower flat index.  py = p / w, px = p % w.  positions[r][c] = p;
+ *      scores[r][c] holds the bits of v[py][px] unchanged.
+ *   2. valid   the keypoint is valid iff its score is not NaN and (has_min == 0 or score >= min_score).  The quiet-NaN rows behind
+ *      `count` of a DetectedRois or LandmarkWarps pass are void all through.
+ *   3. refine  PVHIP_PEAKS_NONE: ox = oy = 0.  PVHIP_PEAKS_QUARTER: if 1 <= px <= w - 2, with l = v[py][px - 1] and r = v[py][px + 1],
+ *      ox = +0.25f if r > l, -0.25f if r < l, else 0 (equal values, zeros of either sign, either neighbour NaN); on the plane's first or
+ *      last column ox = 0.  oy likewise in y with h, from v[py - 1][px] and v[py + 1][px].  h == 1 or w == 1 never refines that axis.
+ *      fx = (float)px + ox, fy = (float)py + oy, fp32 (exact below 2^22).
+ *   4. space   PVHIP_PEAKS_HEATMAP: (fx, fy).  PVHIP_PEAKS_NORMALISED, on the pixel-edge convention pvhip_landmarks_to_warps reads (0 the
+ *      left or top edge, 1 the right or bottom edge): x = (float)((double)(fx + 0.5f) / (double)w), y = (float)((double)(fy + 0.5f) /
+ *      (double)h): one fp32 addition, one correctly rounded binary64 division, one rounding to fp32.  points[r][c] = (x, y); a void
+ *      keypoint's are two quiet NaNs 0x7FC00000.  A valid NORMALISED block read as (n, 2 k) is what pvhip_landmarks_to_warps takes.
+ * `positions` (n, k) int32, `scores` (n, k) fp32, `points` (n, k, 2) fp32; no counts are written (the caller counts the valid points).
+ * `x` may be only 4-byte aligned, and a plane starts on a 16-byte boundary only when h * w % 4 == 0: each plane is split at its own
+ * 16-byte boundaries.  One launch on the current stream, every plane read once (the peak and its neighbours once more), no atomics, no
+ * workspace.  Two forms, by h * w: PVHIP_PEAKS_FORM_WAVE, one wave per plane, four planes per workgroup, up to 1024 elements;
+ * PVHIP_PEAKS_FORM_BLOCK, one 256-thread workgroup per plane, the waves' winners combined through LDS.  pvhip_heatmap_peaks_form
+ * returns the form of (h, w) -- no status, no device needed --, PVHIP_PEAKS_FORM_NONE for a plane the entry refuses.
+ * n, k, h, w >= 1, 2 <= h * w <= PVHIP_PEAKS_MAX_PLANE, n * k < 2^31, refine and space each one of the two, has_min 0 or 1, min_score
+ * finite, no NULL or misaligned pointer; else PVHIP_EINVAL and nothing is launched. */
+#define PVHIP_PEAKS_NONE        0
+#define PVHIP_PEAKS_QUARTER     1
+#define PVHIP_PEAKS_HEATMAP     0
+#define PVHIP_PEAKS_NORMALISED  1
+#define PVHIP_PEAKS_FORM_NONE   0
+#define PVHIP_PEAKS_FORM_WAVE   1
+#define PVHIP_PEAKS_FORM_BLOCK  2
+#define PVHIP_PEAKS_MAX_PLANE   (1 << 24)
+int pvhip_heatmap_peaks_form(int h, int w);
+int pvhip_heatmap_peaks_f32(const float* x, int n, int k, int h, int w, int refine, int space, int has_min, float min_score,
+                            int* positions, float* scores, float* points);
+
 /* ---------------------------------------------------------------- a detector's answer ------ */
 /* Addition to ABI v18 (the version number is unchanged: nothing existing changed): the records of pvhip_detection_output_f32 become one
  * flat table of the detections a caller wants -- what the reference's sample makes on the host with `for record in res.reshape(100, 7):

@@ -1,20 +1,21 @@
-"""Answers behind the pass: the Results a start named with ``top_k=``, ``detections=`` or ``matches=`` come back from wait() as a ``TopK``, a
-``Detections`` or a ``Matches`` made on the device instead of as the tensor.  One ``Answers`` per Executable_Network (one per request), as ``HostInputs``
+"""Answers behind the pass: the Results a start named with ``top_k=``, ``detections=``, ``matches=`` or ``keypoints=`` come back from wait() as a
+``TopK``, a ``Detections``, a ``Matches`` or a ``Keypoints`` made on the device instead of as the tensor.  One ``Answers`` per Executable_Network (one per request), as ``HostInputs``
 is on the way in: the request checks the arguments, binds the asks to the staged inputs, launches behind the pass and reads after it.
 A plain screen over a detector whose input declares a fit (preprocess_info.resize_fit) learns its geometry in bound(), from the extent
 of the frames the pass was fed.
 
-An ask is one Result's question in its resolved form -- top_k.Ask, detections.Ask / FittedAsk, tiled_detections.Ask / RegionAsk or gallery.Ask, each with
+An ask is one Result's question in its resolved form -- top_k.Ask, detections.Ask / FittedAsk, tiled_detections.Ask / RegionAsk, gallery.Ask or keypoints.Ask, each with
 `bound`, `key`, `launch` and `on_host` --; which kind it is matters only where checked() makes it."""
 import numpy as np
 
-from . import detections as detections_rule, device, gallery as gallery_rule, tiled_detections as tiled_rule, top_k as top_k_rule
+from . import detections as detections_rule, device, gallery as gallery_rule, keypoints as keypoints_rule, tiled_detections as tiled_rule, \
+    top_k as top_k_rule
 from .input_format import FrameFeed
 
 
 class Answers:
     """`blocks` = {ask.key(Result name): its Blocks}, this request's own device and page-locked blocks, made on first use: (name, k),
-    (name, resolved DetectionScreen), (name, resolved TiledScreen or RegionScreen, m) or (name, id of the Gallery, k)."""
+    (name, resolved DetectionScreen), (name, resolved TiledScreen or RegionScreen, m), (name, id of the Gallery, k) or (name, refine, space)."""
 
     def __init__(self, runner):
         self.runner, self.blocks = runner, {}       # runner: the Executable_Network whose base stream and Results these are
@@ -22,9 +23,22 @@ class Answers:
     def release(self):
         self.blocks = {}
 
-    def checked(self, inputs, top_k, detections, sharded: bool, matches=None) -> dict:
-        """{Result name: ask} of the `top_k`, `detections` and `matches` arguments of a start with `inputs`, {} when nothing is asked;
-        ValueError.  Everything is looked up in the network as it was read: no device is needed, nothing is staged, allocated or launched."""
+    def checked(self, inputs, top_k, detections, sharded: bool, matches=None, keypoints=None) -> dict:
+        """{Result name: ask} of the `top_k`, `detections`, `matches` and `keypoints` arguments of a start with `inputs`, {} when nothing
+        is asked; ValueError.  Everything is looked up in the network as it was read: no device is needed, nothing is staged, allocated or
+        launched."""
+        asks = self._checked(inputs, top_k, detections, sharded, matches)
+        if keypoints is None:
+            return asks
+        for name, screen in keypoints_rule.checked(self.runner.ienet, keypoints, sharded).items():
+            if name in asks:
+                kind = 'top_k' if isinstance(asks[name], top_k_rule.Ask) else 'matches' if isinstance(asks[name], gallery_rule.Ask) else 'detections'
+                raise ValueError('keypoints: Result {!r} is asked for with {} as well'.format(name, kind))
+            asks[name] = keypoints_rule.Ask(screen)
+        return asks
+
+    def _checked(self, inputs, top_k, detections, sharded, matches) -> dict:
+        """The asks of `top_k`, `detections` and `matches`."""
         if top_k is None and detections is None and matches is None:
             return {}
         ienet = self.runner.ienet

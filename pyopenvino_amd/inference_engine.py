@@ -333,22 +333,31 @@ class InferRequest:
     Result stays on the device.  ValueError ('matches: ...'), before anything is staged or launched: no such Result for an unnamed form,
     an unknown name, a Result of another shape, precision or D, a value of another type, k or min_score out of range, a sharded batch,
     a Result that top_k or detections names as well.
-    `top_k`, `detections` and `matches` may be given together, for different Results."""
+    `keypoints` = a ``PeakScreen``, a real number (its min_score), True (the default screen) or {Result name: any of these}: those heatmap
+    Results -- every FP32 Result declared (n, K, H, W) with n the batch, 2 <= H * W <= 2^24 and not of the detector shape (1, 1, R, 7) for
+    the unnamed forms -- come back from wait() as a ``Keypoints`` (counts, points, scores, positions): the peak of every plane by the rule
+    of keypoints.py -- first in top_k's order, moved a quarter pixel toward its larger neighbour under 'QUARTER', in heatmap pixels or
+    normalised to the plane --, made by pvhip_heatmap_peaks_f32 behind the pass (one launch) and read back in one copy of 16 n K bytes;
+    the full Result stays on the device.  The rows behind `count` of a DetectedRois or LandmarkWarps pass have counts 0 and NaN points.
+    ValueError ('keypoints: ...'), before anything is staged or launched: no such Result for an unnamed form, an unknown name, a Result of
+    another rank, shape or precision, a value of another type, refine or space unknown, min_score not a finite real of float32, a sharded
+    batch, a Result that top_k, detections or matches names as well.
+    `top_k`, `detections`, `matches` and `keypoints` may be given together, for different Results."""
 
     def __init__(self, owner, runner, index: int):
         self.owner, self.runner, self.index = owner, runner, index      # owner: the network load_network returned
         self._in_flight, self._replayed = False, None
-        self._asks = {}                 # {Result name: ask} of the pass in flight (answers.py): what top_k=, detections= and matches= named
+        self._asks = {}                 # {Result name: ask} of the pass in flight (answers.py): what top_k=, detections=, matches= and keypoints= named
 
-    def start_async(self, inputs: dict, top_k=None, detections=None, matches=None):
-        self._start(inputs, top_k, False, detections, matches)
+    def start_async(self, inputs: dict, top_k=None, detections=None, matches=None, keypoints=None):
+        self._start(inputs, top_k, False, detections, matches, keypoints)
 
-    def _start(self, inputs, top_k, verbose, detections=None, matches=None):
+    def _start(self, inputs, top_k, verbose, detections=None, matches=None, keypoints=None):
         if self._in_flight:
             raise RuntimeError('request {} is still in flight: wait() first'.format(self.index))
         ex = self.runner
         sharded = ex.sharded or self.owner.sharded
-        asks = ex.answers.checked(inputs, top_k, detections, sharded, matches)
+        asks = ex.answers.checked(inputs, top_k, detections, sharded, matches, keypoints)
         fed, inputs = inputs, ex.host_inputs.stage(inputs, ex.stream_base, sharded)
         self._asks = ex.answers.bound(asks, fed)
         ex.wait_result_readers()
@@ -384,8 +393,8 @@ class InferRequest:
                 G.nodes[nid]['result'] = out[name] = ex._read_back(value, self.owner.comm)
         return out
 
-    def infer(self, inputs: dict, top_k=None, detections=None, matches=None) -> dict:
-        self.start_async(inputs, top_k, detections, matches)
+    def infer(self, inputs: dict, top_k=None, detections=None, matches=None, keypoints=None) -> dict:
+        self.start_async(inputs, top_k, detections, matches, keypoints)
         return self.wait()
 
     def input_buffer(self, name: str, source_size=None, frames=None) -> np.ndarray:
@@ -568,8 +577,8 @@ class Executable_Network:
                 event.wait()
             device.select_stream(0)
 
-    def start_async(self, request_id: int, inputs: dict, top_k=None, detections=None, matches=None):
-        self.requests[request_id].start_async(inputs, top_k, detections, matches)
+    def start_async(self, request_id: int, inputs: dict, top_k=None, detections=None, matches=None, keypoints=None):
+        self.requests[request_id].start_async(inputs, top_k, detections, matches, keypoints)
 
     def wait(self, request_id: int) -> dict:
         return self.requests[request_id].wait()
@@ -1071,13 +1080,15 @@ class Executable_Network:
             return None
         return self._graph
 
-    def infer(self, inputs: dict, verbose: bool = False, top_k=None, detections=None, matches=None) -> dict:
+    def infer(self, inputs: dict, verbose: bool = False, top_k=None, detections=None, matches=None, keypoints=None) -> dict:
         """`top_k` = k or {Result name: k}: those Results come back as a ``TopK`` of the k best classes per batch row; `detections` = a
         ``DetectionScreen``, a min_confidence or {Result name: either}: those come back as a ``Detections``; `matches` = a ``Gallery``, a
-        ``GalleryMatch`` or {Result name: either}: those come back as a ``Matches`` of the k best gallery rows per batch row (InferRequest)."""
-        if top_k is not None or detections is not None or matches is not None:   # the pass of request 0 (this network's own graph and streams), waited for at once
+        ``GalleryMatch`` or {Result name: either}: those come back as a ``Matches`` of the k best gallery rows per batch row; `keypoints` = a
+        ``PeakScreen``, a min_score, True or {Result name: any of these}: those heatmap Results come back as a ``Keypoints`` of the peak of
+        every plane (InferRequest)."""
+        if top_k is not None or detections is not None or matches is not None or keypoints is not None:   # the pass of request 0 (this network's own graph and streams), waited for at once
             request = self.requests[0] if self.requests else InferRequest(self, self, 0)
-            request._start(inputs, top_k, verbose, detections, matches)
+            request._start(inputs, top_k, verbose, detections, matches, keypoints)
             return request.wait()
         inputs = self.host_inputs.stage(inputs, self.stream_base, self.sharded)
         self.wait_result_readers()
