@@ -1,16 +1,27 @@
-"""Answers behind the pass: the Results a start named with ``top_k=``, ``detections=``, ``matches=`` or ``keypoints=`` come back from wait() as a
-``TopK``, a ``Detections``, a ``Matches`` or a ``Keypoints`` made on the device instead of as the tensor.  One ``Answers`` per Executable_Network (one per request), as ``HostInputs``
-is on the way in: the request checks the arguments, binds the asks to the staged inputs, launches behind the pass and reads after it.
-A plain screen over a detector whose input declares a fit (preprocess_info.resize_fit) learns its geometry in bound(), from the extent
-of the frames the pass was fed.
+"""Answers behind the pass: the Results a start named with ``top_k=``, ``detections=``, ``matches=`` or ``keypoints=`` come back from
+wait() as a ``TopK``, a ``Detections``, a ``Matches`` or a ``Keypoints`` made on the device instead of as the tensor.  One ``Answers`` per
+Executable_Network (one per request), as ``HostInputs`` is on the way in: the request checks the arguments, binds the asks to the staged
+inputs, launches behind the pass and reads after it.
 
-An ask is one Result's question in its resolved form -- top_k.Ask, detections.Ask / FittedAsk, tiled_detections.Ask / RegionAsk, gallery.Ask or keypoints.Ask, each with
-`bound`, `key`, `launch` and `on_host` --; which kind it is matters only where checked() makes it."""
+An ask is one Result's question in its resolved form, an ``ask.Ask`` (ask.py states the protocol: KEYWORD, `bound`, `key`, `launch`,
+`on_host`): top_k.Ask, detections.Ask / FittedAsk, tiled_detections.Ask / RegionAsk, gallery.Ask or keypoints.Ask.  Which kind it is
+matters only where checked() makes it; the rule of each kind, its argument's forms and its refusals are stated in its module.  A plain
+screen over a detector whose input declares a fit (preprocess_info.resize_fit) learns its geometry in bound(), from the extent of the
+frames the pass was fed."""
 import numpy as np
 
 from . import detections as detections_rule, device, gallery as gallery_rule, keypoints as keypoints_rule, tiled_detections as tiled_rule, \
     top_k as top_k_rule
 from .input_format import FrameFeed
+
+
+def _no_clash(keyword: str, names, asks: dict, screens=()):
+    """No Result of `names`, which `keyword` asks for, is among the `asks` or the `screens` of the keywords in front of it; ValueError for
+    the first that is: the later keyword speaks and names the earlier."""
+    for name in names:
+        if name in asks or name in screens:
+            raise ValueError('{}: Result {!r} is asked for with {} as well'.format(
+                keyword, name, asks[name].KEYWORD if name in asks else detections_rule.Ask.KEYWORD))
 
 
 class Answers:
@@ -26,67 +37,57 @@ class Answers:
     def checked(self, inputs, top_k, detections, sharded: bool, matches=None, keypoints=None) -> dict:
         """{Result name: ask} of the `top_k`, `detections`, `matches` and `keypoints` arguments of a start with `inputs`, {} when nothing
         is asked; ValueError.  Everything is looked up in the network as it was read: no device is needed, nothing is staged, allocated or
-        launched."""
-        asks = self._checked(inputs, top_k, detections, sharded, matches)
-        if keypoints is None:
-            return asks
-        for name, screen in keypoints_rule.checked(self.runner.ienet, keypoints, sharded).items():
-            if name in asks:
-                kind = 'top_k' if isinstance(asks[name], top_k_rule.Ask) else 'matches' if isinstance(asks[name], gallery_rule.Ask) else 'detections'
-                raise ValueError('keypoints: Result {!r} is asked for with {} as well'.format(name, kind))
-            asks[name] = keypoints_rule.Ask(screen)
-        return asks
-
-    def _checked(self, inputs, top_k, detections, sharded, matches) -> dict:
-        """The asks of `top_k`, `detections` and `matches`."""
-        if top_k is None and detections is None and matches is None:
+        launched.  The checks run in this order, which is not the keywords': matches' own, a tiled or region screen for a Result `top_k`
+        names, top_k's, detections', a Result under two of the three, what a tiled, region or fitted screen asks of its feed, keypoints',
+        a Result under keypoints and another."""
+        if top_k is detections is matches is keypoints is None:
             return {}
-        ienet = self.runner.ienet
-        matched = gallery_rule.checked(ienet, matches, sharded)
-        if top_k is None and detections is None:
-            return {name: gallery_rule.Ask(match) for name, match in matched.items()}
-        tiled_rule.checked_top_k(top_k, detections)
-        wanted = top_k_rule.checked(ienet, top_k, sharded)
-        screens = detections_rule.checked(ienet, detections, sharded)
-        both = sorted(set(wanted) & set(screens))
-        if both:
-            raise ValueError('detections: Result {!r} is asked for with top_k as well'.format(both[0]))
-        both = sorted(set(matched) & (set(wanted) | set(screens)))
-        if both:
-            raise ValueError('matches: Result {!r} is asked for with {} as well'.format(both[0], 'top_k' if both[0] in wanted else 'detections'))
-        tiled = {name: s for name, s in screens.items() if isinstance(s, tiled_rule.TiledScreen)}
-        formats = self.runner.host_inputs.formats
-        for name, s in tiled.items():           # (the geometry would be one per tile)
-            if s.input in formats and formats[s.input].fitted:
-                raise ValueError('detections: Result {!r}: a TiledScreen over input {!r}, which declares resize_fit {}'.format(
-                    name, s.input, formats[s.input].fit))
-        regions = {name: s for name, s in screens.items() if isinstance(s, tiled_rule.RegionScreen)}     # (any declared fit: a geometry per row)
-        tiled_rule.checked_feed(inputs, {**tiled, **regions})
-        fitted = self._fitted_input() if len(screens) > len(tiled) + len(regions) else None
-        if fitted is not None and isinstance(inputs, dict) and isinstance(inputs.get(fitted), FrameFeed):
-            raise ValueError('detections: input {!r} declares resize_fit {} and is fed a {}: every row has a geometry of its own'.format(
-                fitted, formats[fitted].fit, type(inputs[fitted]).__name__))
-        n = int(ienet.batch_size)
-        asks = {name: top_k_rule.Ask(k) for name, k in wanted.items()}
-        for name, s in screens.items():
-            if name in tiled:
-                asks[name] = tiled_rule.Ask(s, n, None, None)
-            elif name in regions:
-                asks[name] = self._region_ask(s, n)
-            elif fitted is None:
-                asks[name] = detections_rule.Ask(s, n)
-            else:
-                given = detections[name] if isinstance(detections, dict) else detections
-                explicit = isinstance(given, detections_rule.DetectionScreen) and given.frame_size is not None
-                asks[name] = detections_rule.FittedAsk(s, n, fitted, formats[fitted], explicit, None)
-        asks.update((name, gallery_rule.Ask(match)) for name, match in matched.items())
+        ex, ienet, asks = self.runner, self.runner.ienet, {}
+        matched = gallery_rule.checked(ienet, matches, sharded) if matches is not None else {}
+        if detections is not None:              # (a kind's module is asked only when its keyword is given: a pass pays for what it names)
+            tiled_rule.checked_top_k(top_k, detections)
+        if top_k is not None:
+            asks = {name: top_k_rule.Ask(k) for name, k in top_k_rule.checked(ienet, top_k, sharded).items()}
+        screens = detections_rule.checked(ienet, detections, sharded) if detections is not None else {}
+        if screens and asks:
+            _no_clash('detections', sorted(screens), asks)
+        if matched and (asks or screens):
+            _no_clash('matches', sorted(matched), asks, screens)
+        if screens:
+            formats, n = ex.host_inputs.formats, int(ienet.batch_size)
+            tiled = {name: s for name, s in screens.items() if isinstance(s, tiled_rule.TiledScreen)}
+            for name, s in tiled.items():           # (the geometry would be one per tile)
+                if s.input in formats and formats[s.input].fitted:
+                    raise ValueError('detections: Result {!r}: a TiledScreen over input {!r}, which declares resize_fit {}'.format(
+                        name, s.input, formats[s.input].fit))
+            regions = {name: s for name, s in screens.items() if isinstance(s, tiled_rule.RegionScreen)}     # (any declared fit: a geometry per row)
+            tiled_rule.checked_feed(inputs, {**tiled, **regions})
+            fitted = self._fitted_input() if len(screens) > len(tiled) + len(regions) else None
+            if fitted is not None and isinstance(inputs, dict) and isinstance(inputs.get(fitted), FrameFeed):
+                raise ValueError('detections: input {!r} declares resize_fit {} and is fed a {}: every row has a geometry of its own'.format(
+                    fitted, formats[fitted].fit, type(inputs[fitted]).__name__))
+            for name, s in screens.items():
+                if name in tiled:
+                    asks[name] = tiled_rule.Ask(s, n, None, None)
+                elif name in regions:           # the extent and the declared fit of its input, and how the table of a DetectedRois is read
+                    fmt = formats[s.input]
+                    asks[name] = tiled_rule.RegionAsk(s, n, None, None, (int(fmt.dims[2]), int(fmt.dims[3])), fmt.fit,
+                                                      lambda s=s: ex.host_inputs.detected_rois(s.input, ex.stream_base), None)     # (called with no argument: `s` is bound here, not in the loop's last round)
+                elif fitted is None:
+                    asks[name] = detections_rule.Ask(s, n)
+                else:
+                    given = detections[name] if isinstance(detections, dict) else detections
+                    explicit = isinstance(given, detections_rule.DetectionScreen) and given.frame_size is not None
+                    asks[name] = detections_rule.FittedAsk(s, n, fitted, formats[fitted], explicit, None)
+        if matched:
+            asks.update((name, gallery_rule.Ask(match)) for name, match in matched.items())
+        if keypoints is not None:
+            peaks = keypoints_rule.checked(ienet, keypoints, sharded)
+            if asks:                            # (keypoints speaks of the first Result in its own order)
+                _no_clash('keypoints', peaks, asks)
+            for name, screen in peaks.items():
+                asks[name] = keypoints_rule.Ask(screen)
         return asks
-
-    def _region_ask(self, screen, n):
-        """The ask of a resolved RegionScreen: the extent and the declared fit of its input, and how the table of a DetectedRois is read."""
-        ex, fmt = self.runner, self.runner.host_inputs.formats[screen.input]
-        return tiled_rule.RegionAsk(screen, n, None, None, (int(fmt.dims[2]), int(fmt.dims[3])), fmt.fit,
-                                    lambda: ex.host_inputs.detected_rois(screen.input, ex.stream_base), None)
 
     def _fitted_input(self):
         """The name of the network's single 4-D Parameter when its format declares a fit, else None."""
@@ -109,7 +110,8 @@ class Answers:
             return
         device.select_stream(ex.stream_base)
         for name, ask in on_device:
-            self.blocks[ask.key(name)] = ask.launch(self.blocks.get(ask.key(name)), values[name])      # (made on first use)
+            key = ask.key(name)
+            self.blocks[key] = ask.launch(self.blocks.get(key), values[name])      # (made on first use)
         ex._pending = (ex._pending[0] if ex._pending is not None else None, ex._order_event().record())
         device.select_stream(0)
 

@@ -18,13 +18,16 @@ ymin, xmax, ymax] with normalised corners; image b is rows [b P, (b + 1) P) of t
             an image's records stand in descending score order;
   table     the kept survivors of all images in (image, position) order, no gap between images; total = sum(counts);
   row       (b, x0, y0, w, h, label, score bits, record): label = int32 of column 1 (truncated) when that is finite and in
-            [-2^31, 2^31), else -1; the score's bits are the record's own; record = b P + p."""
+            [-2^31, 2^31), else -1; the score's bits are the record's own; record = b P + p.
+The Result itself stays on the device, where a ``DetectedRois`` of another request reads it as before.  Over a fitted input `frame_size`
+None means the extent of the frames the pass was fed; that input fed a ``RoiInput`` / ``DetectedRois`` in the same pass (a geometry per row)
+is a ValueError, as is a TiledScreen over it (answers.py)."""
 import collections
 import ctypes
 
 import numpy as np
 
-from . import device
+from . import ask, device
 
 MAX_LABELS = 64
 MAX_EXTENT = 1 << 24                 # a frame extent is exact as float32
@@ -202,37 +205,29 @@ def _declared_extent(ienet):
     return (shapes[0][2], shapes[0][3]) if len(shapes) == 1 else None
 
 
+def _fits(port, screen, batch):
+    return records_of(port, batch) is not None and port['precision'] == 'FP32'
+
+
+def _none_fits(ports, screen, batch):
+    described = ', '.join('{!r} {} {}'.format(name, port['precision'], tuple(port['dims'])) for name, port in sorted(ports.items()))
+    return 'detections: the network has no FP32 Result of shape (1, 1, R, 7) with R a multiple of the batch {} (it has {})'.format(batch, described)
+
+
 def checked(ienet, detections, sharded: bool) -> dict:
     """{Result name: resolved DetectionScreen} of the `detections` argument of infer() / start_async() -- a DetectionScreen or a
-    min_confidence for every detector Result, or {Result name: either} --, {} for None; a ``TiledScreen`` in the place of a
-    DetectionScreen resolves to a TiledScreen with its `input` named.  Everything is looked up in the network as it was read: no device
-    is needed, nothing is allocated."""
+    min_confidence for every detector Result (FP32, declared (1, 1, R, 7) with R a multiple of the batch), or {Result name: either} --,
+    {} for None; a ``TiledScreen`` or a ``RegionScreen`` in the place of a DetectionScreen resolves to one with its `input` named.
+    Everything is looked up in the network as it was read: no device is needed, nothing is allocated.  ValueError ('detections: ...'): an
+    unknown name, no such Result for an unnamed form, a sharded batch, a Result of another shape or precision, a value of the screen out
+    of range."""
     if detections is None:
         return {}
-    results = {name: next(iter(ienet.G.nodes[nid]['input'].values())) for nid, name in ienet.find_node_by_type('Result')}
     batch = int(ienet.batch_size)
-    if isinstance(detections, dict):
-        unknown = [name for name in detections if name not in results]
-        if unknown:
-            raise ValueError('detections: the network has no Result named {!r} (it has {})'.format(unknown[0], sorted(results)))
-        wanted = dict(detections)
-    else:
-        wanted = {name: detections for name, port in results.items() if records_of(port, batch) is not None and port['precision'] == 'FP32'}
-        if not wanted:
-            described = ', '.join('{!r} {} {}'.format(name, port['precision'], tuple(port['dims'])) for name, port in sorted(results.items()))
-            raise ValueError('detections: the network has no FP32 Result of shape (1, 1, R, 7) with R a multiple of the batch {} (it has {})'.format(
-                batch, described))
-    if wanted and sharded:
-        raise ValueError('detections: not with a batch sharded over ranks')
+    ports, wanted = ask.named(ienet, 'detections', detections, sharded, _fits, _none_fits)
     out = {}
     for name, screen in wanted.items():
-        port = results[name]
-        per_image = records_of(port, batch)
-        if per_image is None:
-            raise ValueError('detections: Result {!r} has shape {}: not (1, 1, R, 7) with R a multiple of the batch {}'.format(
-                name, tuple(port['dims']), batch))
-        if port['precision'] != 'FP32':
-            raise ValueError('detections: Result {!r} is {}: FP32 Results only'.format(name, port['precision']))
+        per_image = ask.declared('detections', name, ports[name], records_of(ports[name], batch), '(1, 1, R, 7) with R a multiple of the batch {}', batch)
         if batch * per_image >= (1 << 31) // 7:
             raise ValueError('detections: Result {!r} has too many records ({} x {})'.format(name, batch, per_image))
         what = 'Result {!r}: '.format(name)
@@ -294,30 +289,28 @@ class Blocks(TableBlocks):
                     s.max_per_image, ctypes.c_void_p(self.header.ptr), ctypes.c_void_p(self.rows.ptr), *(fit or ()))
 
 
-class Ask(collections.namedtuple('Ask', 'screen images')):
-    """A Result of `images` images asked for with a resolved DetectionScreen, as answers.py drives it (top_k.Ask)."""
+class Ask(ask.Ask, collections.namedtuple('Ask', 'screen images')):
+    """A Result of `images` images asked for with a resolved DetectionScreen."""
     __slots__ = ()
-
-    def bound(self, inputs, slots):
-        return self
+    KEYWORD = 'detections'
 
     def key(self, name):
         return (name, self.screen)
 
-    def launch(self, blocks, value):
-        blocks = blocks or Blocks(self.images, value.shape[-2] // self.images, self.screen)
-        blocks.launch(value)
-        return blocks
+    def blocks_for(self, value):
+        return Blocks(self.images, value.shape[-2] // self.images, self.screen)
 
     def on_host(self, value):
         return compact_records(value, self.images, self.screen)
 
 
-class FittedAsk(collections.namedtuple('FittedAsk', 'screen images input format explicit fit')):
+class FittedAsk(ask.Ask, collections.namedtuple('FittedAsk', 'screen images input format explicit fit')):
     """The Ask of a detector whose 4-D Parameter `input`, of InputFormat `format`, declares a fit: `fit` = (Hn, Wn, dx, dy, iw, ih) is known
     once the pass's inputs are staged (bound), from the extent of the frames that pass was fed, and frame_size -- unless the caller gave
     one (`explicit`) -- is that extent."""
     __slots__ = ()
+    KEYWORD = 'detections'
+    blocks_for = Ask.blocks_for
 
     def bound(self, inputs, slots):
         extent = slots[self.input].fed if self.input in slots else None
@@ -333,10 +326,8 @@ class FittedAsk(collections.namedtuple('FittedAsk', 'screen images input format 
         # (the blocks serve every frame extent: neither their size nor their labels depend on it)
         return (name, self.screen if self.fit is None else self.screen._replace(frame_size=None))
 
-    def launch(self, blocks, value):
-        blocks = blocks or Blocks(self.images, value.shape[-2] // self.images, self.screen)
-        blocks.launch(value, self.screen.frame_size, self.fit)
-        return blocks
+    def launch_with(self):
+        return (self.screen.frame_size, self.fit)
 
     def on_host(self, value):
         return compact_records(value, self.images, self.screen, self.fit)

@@ -27,14 +27,14 @@ import ctypes
 
 import numpy as np
 
-from . import device
+from . import ask, device
+from .ask import QUIET_NAN
 from .top_k import MAX_K, rows_of
 
 CHUNK = 256             # PVHIP_GALLERY_CHUNK of include/pvhip.h: gallery rows per list of k keys (tests place G on both sides of it)
 MAX_D = 1024
 MAX_G = 1 << 24
 METRICS = {'COSINE': 0, 'DOT': 1}       # PVHIP_GALLERY_COSINE, PVHIP_GALLERY_DOT
-QUIET_NAN = np.array([0x7FC00000], np.uint32).view(np.float32)[0]
 
 GalleryMatch = collections.namedtuple('GalleryMatch', 'gallery k min_score', defaults=(1, None))
 GalleryMatch.__doc__ = ('How to match a Result against a Gallery: the `k` best gallery rows of every batch row (1 .. min(G, 64)), and of '
@@ -164,12 +164,7 @@ def resolved(value, what='matches') -> GalleryMatch:
     gallery, k, min_score = value
     if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= min(gallery.size, MAX_K):
         raise ValueError('{}: k = {!r} outside 1 .. min(G = {}, {})'.format(what, k, gallery.size, MAX_K))
-    if min_score is not None:
-        if isinstance(min_score, bool) or not isinstance(min_score, (int, float, np.integer, np.floating)) \
-                or not np.isfinite(min_score) or abs(float(min_score)) > float(np.finfo(np.float32).max):
-            raise ValueError('{}: min_score is None or a finite real (of float32), got {!r}'.format(what, min_score))
-        min_score = float(np.float32(min_score))
-    return GalleryMatch(gallery, int(k), min_score)
+    return GalleryMatch(gallery, int(k), None if min_score is None else ask.checked_min_score(min_score, what))
 
 
 def match_rows(x, match) -> Matches:
@@ -210,39 +205,29 @@ def _ids_of(gallery, indices):
     return np.where(indices >= 0, gallery.ids[np.maximum(indices, 0)], np.int32(-1)).astype(np.int32)
 
 
+def _fits(port, match, batch):
+    rows = rows_of(port['dims'])
+    return rows is not None and port['precision'] == 'FP32' and rows[1] == match.gallery.dim
+
+
+def _none_fits(ports, match, batch):
+    return 'matches: no FP32 Result of shape (n, {0}) or (n, {0}, 1, ...) to match against {1!r} (the Results: {2})'.format(
+        match.gallery.dim, match.gallery, {name: tuple(port['dims']) for name, port in ports.items()})
+
+
 def checked(ienet, matches, sharded: bool) -> dict:
-    """{Result name: GalleryMatch} of the `matches` argument of infer() / start_async() -- a Gallery or a GalleryMatch for every FP32
-    Result declared (n, D) or (n, D, 1, ...) with the gallery's D, or {Result name: either} --, {} for None.  Everything is looked up in
-    the network as it was read: no device is needed, nothing is allocated."""
+    """{Result name: GalleryMatch} of the `matches` argument of infer() / start_async() -- a Gallery (k = 1, no threshold) or a
+    GalleryMatch for every FP32 Result declared (n, D) or (n, D, 1, ...) with the gallery's D, or {Result name: either} --, {} for None.
+    Everything is looked up in the network as it was read: no device is needed, nothing is allocated.  ValueError ('matches: ...'): an
+    unknown name, a value of another type, k or min_score out of range, no such Result for an unnamed form, a sharded batch, a Result of
+    another shape, precision or D."""
     if matches is None:
         return {}
-    ports = {name: next(iter(ienet.G.nodes[nid]['input'].values())) for nid, name in ienet.find_node_by_type('Result')}
-
-    def fits(port, gallery):
-        rows = rows_of(port['dims'])
-        return rows is not None and port['precision'] == 'FP32' and rows[1] == gallery.dim
-
-    if isinstance(matches, dict):
-        unknown = [name for name in matches if name not in ports]
-        if unknown:
-            raise ValueError('matches: the network has no Result named {!r} (it has {})'.format(unknown[0], sorted(ports)))
-        wanted = {name: resolved(value, 'matches: Result {!r}'.format(name)) for name, value in matches.items()}
-    else:
-        match = resolved(matches)
-        wanted = {name: match for name, port in ports.items() if fits(port, match.gallery)}
-        if not wanted:
-            raise ValueError('matches: no FP32 Result of shape (n, {0}) or (n, {0}, 1, ...) to match against {1!r} (the Results: {2})'.format(
-                match.gallery.dim, match.gallery, {name: tuple(port['dims']) for name, port in ports.items()}))
-    if wanted and sharded:
-        raise ValueError('matches: not with a batch sharded over ranks')
+    ports, wanted = ask.named(ienet, 'matches', matches, sharded, _fits, _none_fits, resolved)
     for name, match in wanted.items():
-        port = ports[name]
-        if rows_of(port['dims']) is None:
-            raise ValueError('matches: Result {!r} has shape {}: not (n, D) or (n, D, 1, ...)'.format(name, tuple(port['dims'])))
-        if port['precision'] != 'FP32':
-            raise ValueError('matches: Result {!r} is {}: FP32 Results only'.format(name, port['precision']))
-        if not fits(port, match.gallery):
-            raise ValueError('matches: Result {!r} has D = {}, {!r} has {}'.format(name, rows_of(port['dims'])[1], match.gallery, match.gallery.dim))
+        rows = ask.declared('matches', name, ports[name], rows_of(ports[name]['dims']), '(n, D) or (n, D, 1, ...)')
+        if rows[1] != match.gallery.dim:
+            raise ValueError('matches: Result {!r} has D = {}, {!r} has {}'.format(name, rows[1], match.gallery, match.gallery.dim))
     return wanted
 
 
@@ -255,20 +240,19 @@ def scratch_bytes(n: int, G: int, k: int) -> int:
     return 8 * n * chunks_of(G) * k
 
 
-class Blocks:
+class Blocks(ask.FlatBlocks):
     """What a request keeps for one (Result name, gallery, k): the scratch block, the device block pvhip_gallery_match_f32 writes
     -- (n,) int32 counts, (n, k) int32 indices, (n, k) float32 scores -- and the page-locked host block it is read back into in one copy
     of 4 n + 8 n k bytes.  None of them depends on min_score, which is an argument of the launch: a caller that varies the threshold
     from call to call keeps one set of blocks.  The scratch is the large one, scratch_bytes(n, G, k) = 8 n ceil(G / CHUNK) k bytes
     (n = 256, G = 1 M, k = 64: 512 MB; k = 5: 40 MB); the blocks hold their Gallery, and so its copy in HBM, until the request's
     release_device_state()."""
-    __slots__ = ('n', 'gallery', 'k', 'scratch', 'dev', 'host')
+    __slots__ = ('n', 'gallery', 'k', 'scratch')
 
     def __init__(self, n: int, gallery: Gallery, k: int):
+        super().__init__(n + 2 * n * k)
         self.n, self.gallery, self.k = n, gallery, k
         self.scratch = device.DeviceTensor.empty((scratch_bytes(n, gallery.size, k) // 8,), np.int64)
-        self.dev = device.DeviceTensor.empty((n + 2 * n * k,), np.int32)
-        self.host = device.host_empty((n + 2 * n * k,), np.int32)
 
     def launch(self, result, min_score):
         """The launch pair on the current stream, behind whatever wrote `result` there (and behind the gallery's upload, the first time)."""
@@ -283,30 +267,26 @@ class Blocks:
 
     def read_back(self) -> Matches:
         """The answer, copied on the current stream, which has drained; the arrays are the caller's own."""
-        device.call('pvhip_memcpy_d2h', ctypes.c_void_p(self.host.ctypes.data), ctypes.c_void_p(self.dev.ptr), self.host.nbytes)
-        n, k = self.n, self.k
-        indices = self.host[n:n + n * k].reshape(n, k).copy()
-        return Matches(self.host[:n].copy(), indices, _ids_of(self.gallery, indices),
-                       self.host[n + n * k:].view(np.float32).reshape(n, k).copy())
+        host, n, k = self.words(), self.n, self.k
+        indices = host[n:n + n * k].reshape(n, k).copy()
+        return Matches(host[:n].copy(), indices, _ids_of(self.gallery, indices), host[n + n * k:].view(np.float32).reshape(n, k).copy())
 
 
-class Ask(collections.namedtuple('Ask', 'match')):
-    """A Result asked for with matches=, as answers.py drives it: the key of its blocks, the launches on the value a pass left on the
-    device -- into `blocks`, or into new ones for None: they are returned --, and the rule on a host value."""
+class Ask(ask.Ask, collections.namedtuple('Ask', 'match')):
+    """A Result asked for with matches=, in its resolved form."""
     __slots__ = ()
-
-    def bound(self, inputs, slots):
-        return self
+    KEYWORD = 'matches'
 
     def key(self, name):
         """(name, id of the gallery, k): what the blocks' sizes depend on.  min_score is no part of it -- it goes with the launch --, so
         that thresholds that vary from call to call share one scratch block."""
         return (name, id(self.match.gallery), self.match.k)
 
-    def launch(self, blocks, value):
-        blocks = blocks or Blocks(rows_of(value.shape)[0], self.match.gallery, self.match.k)
-        blocks.launch(value, self.match.min_score)
-        return blocks
+    def blocks_for(self, value):
+        return Blocks(rows_of(value.shape)[0], self.match.gallery, self.match.k)
+
+    def launch_with(self):
+        return (self.match.min_score,)
 
     def on_host(self, value):
         return match_rows(value, self.match)

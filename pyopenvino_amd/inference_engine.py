@@ -301,48 +301,16 @@ class InferRequest:
     compute streams, so that the kernels of several requests interleave on the device -- the HBM-bound layers of one
     run beside the matrix-core-bound layers of another, and each fills the other's tails.
 
-    `top_k` = k (every Result) or {Result name: k}: those Results come back from wait() as a ``TopK`` (indices, values) of shape (n, k)
-    -- the k best classes of every batch row by the rule of top_k.py -- made by one launch behind the pass and read back in one copy of
-    8 n k bytes; the full Result stays on the device.  Results not named come back whole.  ValueError, before anything is staged or
-    launched: a Result whose declared shape is not (n, C) or (n, C, 1, ...), k outside 1 .. min(C, 64), an unknown name, a sharded batch.
+    A start may ask for the answer of a Result in the place of the tensor: it is made on the device by launches behind the pass and read
+    back by wait() in one or two small copies, while the full Result stays on the device.  Results not named come back whole; the keywords
+    may be given together, for different Results; every refusal is a ValueError raised before anything is staged or launched (answers.py):
 
-    `detections` = a ``DetectionScreen``, a min_confidence, or {Result name: either}: those detector Results -- every FP32 Result declared
-    (1, 1, R, 7) for the unnamed forms -- come back from wait() as a ``Detections`` (counts, selected, rois, labels, scores, records):
-    the records that pass the screen as one flat table by the rule of detections.py, made by pvhip_detections_compact behind the pass
-    and read back in two copies, 4 (2 n + 1) bytes and 32 bytes per row; the full Result stays on the device, where a ``DetectedRois``
-    of another request reads it as before.  ValueError ('detections: ...'), before anything is staged or launched: an unknown name, a
-    Result of another shape or precision, a value of the screen out of range, a sharded batch, no such Result for an unnamed form.
-    On a network whose 4-D Parameter declares ``preprocess_info.resize_fit`` 'LETTERBOX' / 'TOP_LEFT' the detector saw the frame in a
-    rectangle of its input: every corner is mapped back through the geometry of the frames this pass was fed before the rectangle rule
-    (pvhip_detections_compact_fit), and `frame_size` None means the extent of those frames; ValueError when that input is fed a
-    ``RoiInput`` / ``DetectedRois`` in the same pass (a geometry per row), or for a TiledScreen over it.
-    A ``TiledScreen`` in the place of a DetectionScreen, for a pass whose 4-D input is fed a ``RoiInput(frames, tiles)``: the batch rows
-    are tiles of the m frames and the Result comes back as a Detections over FRAMES -- shifted into frame pixels, ordered by score and
-    suppressed across the tiles of a frame by the rule of tiled_detections.py --, made by pvhip_detections_merge_tiles behind the pass with
-    the tile table stage() uploaded, and read back in the same two copies, 4 (2 m + 1) bytes and 32 bytes per row.  ValueError before
-    anything is staged or launched, besides the above: that input fed anything but a RoiInput, more than 4096 candidates.
-    A ``RegionScreen`` in that place, for batch rows that are regions of any aspect: the input may be fed a RoiInput or a
-    ``DetectedRois`` -- a second-stage detector behind a first one, the table never leaving the device -- and may declare any resize_fit;
-    every region's corners are mapped back through the geometry its own pixels were placed with (pvhip_detections_merge_regions, the
-    rule of tiled_detections.py) and the answer is the same Detections over frames, ``detected_rois(name).records[records // P]`` being the
-    first-stage record of each box.  ValueError as for a TiledScreen: that input fed anything but a RoiInput or a DetectedRois.
-    `matches` = a ``GalleryMatch``, a ``Gallery`` (k = 1, no threshold) or {Result name: either}: those embedding Results -- every FP32
-    Result declared (n, D) or (n, D, 1, ...) with the gallery's D for the unnamed forms -- come back from wait() as a ``Matches`` (counts,
-    indices, ids, scores): the k best gallery rows of every batch row by the rule of gallery.py, made by pvhip_gallery_match_f32 behind
-    the pass (two launches; the gallery is uploaded once, on the first of them) and read back in one copy of 4 n + 8 n k bytes; the full
-    Result stays on the device.  ValueError ('matches: ...'), before anything is staged or launched: no such Result for an unnamed form,
-    an unknown name, a Result of another shape, precision or D, a value of another type, k or min_score out of range, a sharded batch,
-    a Result that top_k or detections names as well.
-    `keypoints` = a ``PeakScreen``, a real number (its min_score), True (the default screen) or {Result name: any of these}: those heatmap
-    Results -- every FP32 Result declared (n, K, H, W) with n the batch, 2 <= H * W <= 2^24 and not of the detector shape (1, 1, R, 7) for
-    the unnamed forms -- come back from wait() as a ``Keypoints`` (counts, points, scores, positions): the peak of every plane by the rule
-    of keypoints.py -- first in top_k's order, moved a quarter pixel toward its larger neighbour under 'QUARTER', in heatmap pixels or
-    normalised to the plane --, made by pvhip_heatmap_peaks_f32 behind the pass (one launch) and read back in one copy of 16 n K bytes;
-    the full Result stays on the device.  The rows behind `count` of a DetectedRois or LandmarkWarps pass have counts 0 and NaN points.
-    ValueError ('keypoints: ...'), before anything is staged or launched: no such Result for an unnamed form, an unknown name, a Result of
-    another rank, shape or precision, a value of another type, refine or space unknown, min_score not a finite real of float32, a sharded
-    batch, a Result that top_k, detections or matches names as well.
-    `top_k`, `detections`, `matches` and `keypoints` may be given together, for different Results."""
+        keyword        value, for every fitting Result, or {Result name: value}               comes back as   module
+        `top_k`        k                                                                       ``TopK``        top_k.py
+        `detections`   a ``DetectionScreen`` or a min_confidence                               ``Detections``  detections.py
+                       a ``TiledScreen`` / ``RegionScreen`` over a RoiInput / DetectedRois      ``Detections``  tiled_detections.py
+        `matches`      a ``Gallery`` or a ``GalleryMatch``                                      ``Matches``     gallery.py
+        `keypoints`    a ``PeakScreen``, a min_score or True                                    ``Keypoints``   keypoints.py"""
 
     def __init__(self, owner, runner, index: int):
         self.owner, self.runner, self.index = owner, runner, index      # owner: the network load_network returned
@@ -350,14 +318,15 @@ class InferRequest:
         self._asks = {}                 # {Result name: ask} of the pass in flight (answers.py): what top_k=, detections=, matches= and keypoints= named
 
     def start_async(self, inputs: dict, top_k=None, detections=None, matches=None, keypoints=None):
-        self._start(inputs, top_k, False, detections, matches, keypoints)
+        self._start(inputs, (top_k, detections, matches, keypoints), False)
 
-    def _start(self, inputs, top_k, verbose, detections=None, matches=None, keypoints=None):
+    def _start(self, inputs, asked, verbose):
+        """`asked`: (top_k, detections, matches, keypoints) as the public signatures took them."""
         if self._in_flight:
             raise RuntimeError('request {} is still in flight: wait() first'.format(self.index))
         ex = self.runner
         sharded = ex.sharded or self.owner.sharded
-        asks = ex.answers.checked(inputs, top_k, detections, sharded, matches, keypoints)
+        asks = ex.answers.checked(inputs, asked[0], asked[1], sharded, asked[2], asked[3])
         fed, inputs = inputs, ex.host_inputs.stage(inputs, ex.stream_base, sharded)
         self._asks = ex.answers.bound(asks, fed)
         ex.wait_result_readers()
@@ -372,21 +341,26 @@ class InferRequest:
             with ex._results_on_device():        # the shards are gathered in wait(): one collective at a time, on stream 0
                 ex.run_tasks(verbose)
         if self._asks:                           # behind the pass, replayed or eager, and outside the recording: one recording serves every kind
-            G = ex.ienet.G
-            ex.answers.launch(self._asks, self._replayed['results'] if self._replayed is not None else
-                              {name: G.nodes[nid]['result'] for nid, name in ex.ienet.find_node_by_type('Result')})
+            ex.answers.launch(self._asks, self._values())
         self._in_flight = True
+
+    def _values(self, results=None) -> dict:
+        """{Result name: what the pass in flight, replayed or eager, leaves there}; `results`: the Result nodes, when the caller has them."""
+        if self._replayed is not None:
+            return self._replayed['results']
+        G = self.runner.ienet.G
+        return {name: G.nodes[nid]['result'] for nid, name in results or self.runner.ienet.find_node_by_type('Result')}
 
     def wait(self) -> dict:
         ex = self.runner
         G = ex.ienet.G
         ex.wait_done()
         self._in_flight = False
-        out = {}
-        replayed, self._replayed = self._replayed, None
+        out, results = {}, ex.ienet.find_node_by_type('Result')
+        values, self._replayed = self._values(results), None
         asks, self._asks = self._asks, {}
-        for nid, name in ex.ienet.find_node_by_type('Result'):
-            value = replayed['results'][name] if replayed is not None else G.nodes[nid]['result']
+        for nid, name in results:
+            value = values[name]
             if name in asks:                     # the answer comes back; the Result itself stays where it is, on the device
                 G.nodes[nid]['result'], out[name] = value, ex.answers.read(name, asks[name], value)
             else:
@@ -1081,14 +1055,10 @@ class Executable_Network:
         return self._graph
 
     def infer(self, inputs: dict, verbose: bool = False, top_k=None, detections=None, matches=None, keypoints=None) -> dict:
-        """`top_k` = k or {Result name: k}: those Results come back as a ``TopK`` of the k best classes per batch row; `detections` = a
-        ``DetectionScreen``, a min_confidence or {Result name: either}: those come back as a ``Detections``; `matches` = a ``Gallery``, a
-        ``GalleryMatch`` or {Result name: either}: those come back as a ``Matches`` of the k best gallery rows per batch row; `keypoints` = a
-        ``PeakScreen``, a min_score, True or {Result name: any of these}: those heatmap Results come back as a ``Keypoints`` of the peak of
-        every plane (InferRequest)."""
-        if top_k is not None or detections is not None or matches is not None or keypoints is not None:   # the pass of request 0 (this network's own graph and streams), waited for at once
+        """`top_k`, `detections`, `matches`, `keypoints`: the Results they name come back as their answers (InferRequest has the table)."""
+        if not (top_k is detections is matches is keypoints is None):     # something is asked: the pass of request 0 (this network's own graph and streams), waited for at once
             request = self.requests[0] if self.requests else InferRequest(self, self, 0)
-            request._start(inputs, top_k, verbose, detections, matches, keypoints)
+            request._start(inputs, (top_k, detections, matches, keypoints), verbose)
             return request.wait()
         inputs = self.host_inputs.stage(inputs, self.stream_base, self.sharded)
         self.wait_result_readers()

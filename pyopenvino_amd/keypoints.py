@@ -22,12 +22,12 @@ import ctypes
 
 import numpy as np
 
-from . import device
+from . import ask, device
+from .ask import QUIET_NAN
 
 REFINES = {'NONE': 0, 'QUARTER': 1}             # PVHIP_PEAKS_NONE, PVHIP_PEAKS_QUARTER
 SPACES = {'HEATMAP': 0, 'NORMALISED': 1}        # PVHIP_PEAKS_HEATMAP, PVHIP_PEAKS_NORMALISED
 MAX_PLANE = 1 << 24                             # PVHIP_PEAKS_MAX_PLANE: H * W at most (a flat index is exact in fp32)
-QUIET_NAN = np.array([0x7FC00000], np.uint32).view(np.float32)[0]
 
 PeakScreen = collections.namedtuple('PeakScreen', 'min_score refine space', defaults=(None, 'QUARTER', 'NORMALISED'))
 PeakScreen.__doc__ = ('How to read a heatmap Result: a keypoint is valid when its peak is at least `min_score` (None: any peak that is not NaN); '
@@ -52,12 +52,7 @@ def resolved(value, what='keypoints') -> PeakScreen:
         raise ValueError('{}: refine {!r} is not one of {}'.format(what, refine, sorted(REFINES)))
     if not isinstance(space, str) or space not in SPACES:
         raise ValueError('{}: space {!r} is not one of {}'.format(what, space, sorted(SPACES)))
-    if min_score is not None:
-        if isinstance(min_score, bool) or not isinstance(min_score, (int, float, np.integer, np.floating)) \
-                or not np.isfinite(min_score) or abs(float(min_score)) > float(np.finfo(np.float32).max):
-            raise ValueError('{}: min_score is None or a finite real (of float32), got {!r}'.format(what, min_score))
-        min_score = float(np.float32(min_score))
-    return PeakScreen(min_score, refine, space)
+    return PeakScreen(None if min_score is None else ask.checked_min_score(min_score, what), refine, space)
 
 
 def planes_of(dims, batch=None):
@@ -121,53 +116,41 @@ def to_frame(points, regions):
     return np.stack([(t[:, None, 1] + u[:, :, 0] * t[:, None, 3]) - 0.5, (t[:, None, 2] + u[:, :, 1] * t[:, None, 4]) - 0.5], axis=2)
 
 
+def _fits(port, screen, batch):
+    dims = planes_of(port['dims'], batch)
+    return dims is not None and port['precision'] == 'FP32' and not (dims[:2] == (1, 1) and dims[3] == 7)
+
+
+def _none_fits(ports, screen, batch):
+    return 'keypoints: no FP32 Result of shape (n = {}, K, H, W) with 2 <= H * W <= 2^24 (the Results: {})'.format(
+        batch, {name: tuple(port['dims']) for name, port in ports.items()})
+
+
 def checked(ienet, keypoints, sharded: bool) -> dict:
     """{Result name: resolved PeakScreen} of the `keypoints` argument of infer() / start_async() -- a PeakScreen, a min_score or True for
     every FP32 Result declared (n, K, H, W) with n the batch, 2 <= H * W <= 2^24 and not of the detector shape (1, 1, R, 7), or {Result
-    name: any of these} --, {} for None.  Everything is looked up in the network as it was read: no device is needed, nothing is allocated."""
+    name: any of these} --, {} for None.  Everything is looked up in the network as it was read: no device is needed, nothing is allocated.
+    ValueError ('keypoints: ...'): an unknown name, a value of another type, refine or space unknown, min_score not a finite real of
+    float32, no such Result for an unnamed form, a sharded batch, a Result of another rank, shape or precision."""
     if keypoints is None:
         return {}
-    ports = {name: next(iter(ienet.G.nodes[nid]['input'].values())) for nid, name in ienet.find_node_by_type('Result')}
     batch = int(ienet.batch_size)
-    if isinstance(keypoints, dict):
-        unknown = [name for name in keypoints if name not in ports]
-        if unknown:
-            raise ValueError('keypoints: the network has no Result named {!r} (it has {})'.format(unknown[0], sorted(ports)))
-        wanted = {name: resolved(value, 'keypoints: Result {!r}'.format(name)) for name, value in keypoints.items()}
-    else:
-        screen = resolved(keypoints)
-
-        def fits(port):
-            dims = planes_of(port['dims'], batch)
-            return dims is not None and port['precision'] == 'FP32' and not (dims[:2] == (1, 1) and dims[3] == 7)
-
-        wanted = {name: screen for name, port in ports.items() if fits(port)}
-        if not wanted:
-            raise ValueError('keypoints: no FP32 Result of shape (n = {}, K, H, W) with 2 <= H * W <= 2^24 (the Results: {})'.format(
-                batch, {name: tuple(port['dims']) for name, port in ports.items()}))
-    if wanted and sharded:
-        raise ValueError('keypoints: not with a batch sharded over ranks')
+    ports, wanted = ask.named(ienet, 'keypoints', keypoints, sharded, _fits, _none_fits, resolved)
     for name in wanted:
-        port = ports[name]
-        if planes_of(port['dims'], batch) is None:
-            raise ValueError('keypoints: Result {!r} has shape {}: not (n = {}, K, H, W) with 2 <= H * W <= 2^24'.format(
-                name, tuple(port['dims']), batch))
-        if port['precision'] != 'FP32':
-            raise ValueError('keypoints: Result {!r} is {}: FP32 Results only'.format(name, port['precision']))
+        ask.declared('keypoints', name, ports[name], planes_of(ports[name]['dims'], batch), '(n = {}, K, H, W) with 2 <= H * W <= 2^24', batch)
     return wanted
 
 
-class Blocks:
+class Blocks(ask.FlatBlocks):
     """What a request keeps for one (Result name, refine, space): the device block pvhip_heatmap_peaks_f32 writes -- (n, K) int32
     positions, (n, K) float32 scores, (n, K, 2) float32 points -- and the page-locked host block it is read back into in one copy of
     16 n K bytes.  Neither depends on min_score, which is an argument of the launch: a caller that varies the threshold from call to call
     keeps one pair of blocks."""
-    __slots__ = ('n', 'K', 'refine', 'space', 'dev', 'host')
+    __slots__ = ('n', 'K', 'refine', 'space')
 
     def __init__(self, n: int, K: int, refine: str, space: str):
+        super().__init__(4 * n * K)
         self.n, self.K, self.refine, self.space = n, K, refine, space
-        self.dev = device.DeviceTensor.empty((4 * n * K,), np.int32)
-        self.host = device.host_empty((4 * n * K,), np.int32)
 
     def launch(self, result, min_score):
         """One launch on the current stream, behind whatever wrote `result` there."""
@@ -181,30 +164,27 @@ class Blocks:
     def read_back(self) -> Keypoints:
         """The answer, copied on the current stream, which has drained; the arrays are the caller's own.  A valid point is finite and a
         void one NaN: the counts are formed here."""
-        device.call('pvhip_memcpy_d2h', ctypes.c_void_p(self.host.ctypes.data), ctypes.c_void_p(self.dev.ptr), self.host.nbytes)
-        n, K = self.n, self.K
-        points = self.host[2 * n * K:].view(np.float32).reshape(n, K, 2).copy()
+        host, n, K = self.words(), self.n, self.K
+        points = host[2 * n * K:].view(np.float32).reshape(n, K, 2).copy()
         return Keypoints((~np.isnan(points[:, :, 0])).sum(axis=1).astype(np.int32), points,
-                         self.host[n * K:2 * n * K].view(np.float32).reshape(n, K).copy(), self.host[:n * K].reshape(n, K).copy())
+                         host[n * K:2 * n * K].view(np.float32).reshape(n, K).copy(), host[:n * K].reshape(n, K).copy())
 
 
-class Ask(collections.namedtuple('Ask', 'screen')):
-    """A Result asked for with keypoints=, as answers.py drives it: the key of its blocks, the launch on the value a pass left on the
-    device -- into `blocks`, or into new ones for None: they are returned --, and the rule on a host value."""
+class Ask(ask.Ask, collections.namedtuple('Ask', 'screen')):
+    """A Result asked for with keypoints=, in its resolved form."""
     __slots__ = ()
-
-    def bound(self, inputs, slots):
-        return self
+    KEYWORD = 'keypoints'
 
     def key(self, name):
         """(name, refine, space).  min_score is no part of it: it goes with the launch."""
         return (name, self.screen.refine, self.screen.space)
 
-    def launch(self, blocks, value):
+    def blocks_for(self, value):
         n, K = planes_of(value.shape)[:2]
-        blocks = blocks or Blocks(n, K, self.screen.refine, self.screen.space)
-        blocks.launch(value, self.screen.min_score)
-        return blocks
+        return Blocks(n, K, self.screen.refine, self.screen.space)
+
+    def launch_with(self):
+        return (self.screen.min_score,)
 
     def on_host(self, value):
         return peaks(value, self.screen)

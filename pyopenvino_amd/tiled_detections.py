@@ -25,13 +25,15 @@ contribute nothing --, placed in the (Hn, Wn) input by the input's declared resi
 input_format.fit_geometry((h, w), (Hn, Wn), fit), the integer rule that placed the region's pixels, region b's candidates are what
 detections.py's `fitted` rule selects over frames of (h, w) with (Hn, Wn, *g): every corner mapped back by (v N - d) / i in float32, three
 roundings, the finite check on the record's own corners; a box in the padding clamps to the region's edge, one wholly in it is dropped.
-'STRETCH' maps nothing: TiledScreen's answer bit for bit.  Steps 2 to 4 are unchanged."""
+'STRETCH' maps nothing: TiledScreen's answer bit for bit.  Steps 2 to 4 are unchanged.
+ValueError before anything is staged or launched, besides detections.py's: the screen's input fed anything but a RoiInput (a RegionScreen's:
+or a DetectedRois), more than 4096 candidates, a Result that `top_k` names as well, a TiledScreen over an input that declares a fit."""
 import collections
 import ctypes
 
 import numpy as np
 
-from . import detections, device
+from . import ask, detections, device
 from .detections import Detections
 from .input_format import RESIZE_FITS, DetectedRois, RoiInput, fit_geometry
 
@@ -262,10 +264,12 @@ class RegionBlocks(Blocks):
     ENTRY = 'pvhip_detections_merge_regions'
 
 
-class Ask(collections.namedtuple('Ask', 'screen tiles frames slot')):
-    """A Result asked for with a resolved TiledScreen over n = `tiles` batch rows, as answers.py drives it (top_k.Ask); `frames` = m
-    and `slot`, the staged input's with the tile table page-locked and on the device, are known once the pass's inputs are staged."""
+class Ask(ask.Ask, collections.namedtuple('Ask', 'screen tiles frames slot')):
+    """A Result asked for with a resolved TiledScreen over n = `tiles` batch rows; `frames` = m and `slot`, the staged input's with the
+    tile table page-locked and on the device, are known once the pass's inputs are staged."""
     __slots__ = ()
+    KEYWORD = 'detections'
+    BLOCKS = Blocks
 
     def bound(self, inputs, slots):
         return self._replace(frames=int(np.shape(inputs[self.screen.input].frames)[0]), slot=slots[self.screen.input])
@@ -273,31 +277,32 @@ class Ask(collections.namedtuple('Ask', 'screen tiles frames slot')):
     def key(self, name):
         return (name, self.screen, self.frames)
 
-    def launch(self, blocks, value):
-        blocks = blocks or Blocks(self.tiles, value.shape[-2] // self.tiles, self.frames, self.screen)
-        blocks.launch(value, self.slot.tables['roi'].device)
-        return blocks
+    def blocks_for(self, value):
+        return self.BLOCKS(self.tiles, value.shape[-2] // self.tiles, self.frames, self.screen)
+
+    def launch_with(self):
+        return (self.slot.tables['roi'].device,)
 
     def on_host(self, value):
         return merge_tiles(value, self.slot.tables['roi'].host, self.frames, self.screen)
 
 
-class RegionAsk(collections.namedtuple('RegionAsk', 'screen tiles frames slot net_hw fit table_of detected')):
+class RegionAsk(ask.Ask, collections.namedtuple('RegionAsk', 'screen tiles frames slot net_hw fit table_of detected')):
     """A Result asked for with a resolved RegionScreen over n = `tiles` batch rows: Ask, with `net_hw` = (Hn, Wn) and `fit`, the declared
     resize_fit, of the screen's input (its InputFormat's) and `table_of`, a function of no arguments that reads the table of a DetectedRois
     back after the pass (host_inputs.detected_rois); `detected`, known once bound: the pass was fed a DetectedRois, whose table only the
     device knows."""
     __slots__ = ()
-    key = Ask.key
+    KEYWORD = 'detections'
+    BLOCKS = RegionBlocks
+    key, blocks_for = Ask.key, Ask.blocks_for
 
     def bound(self, inputs, slots):
         fed = inputs[self.screen.input]
         return self._replace(frames=int(np.shape(fed.frames)[0]), slot=slots[self.screen.input], detected=isinstance(fed, DetectedRois))
 
-    def launch(self, blocks, value):
-        blocks = blocks or RegionBlocks(self.tiles, value.shape[-2] // self.tiles, self.frames, self.screen)
-        blocks.launch(value, self.slot.tables['roi'].device, self.net_hw[0], self.net_hw[1], RESIZE_FITS[self.fit])
-        return blocks
+    def launch_with(self):
+        return (self.slot.tables['roi'].device, self.net_hw[0], self.net_hw[1], RESIZE_FITS[self.fit])
 
     def on_host(self, value):
         table = self.table_of().rois if self.detected else self.slot.tables['roi'].host

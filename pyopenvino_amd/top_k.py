@@ -12,7 +12,7 @@ import ctypes
 
 import numpy as np
 
-from . import device
+from . import ask, device
 
 MAX_K = 64
 
@@ -48,44 +48,31 @@ def rows_of(dims):
 
 def checked(ienet, top_k, sharded: bool) -> dict:
     """{Result name: k} of the `top_k` argument of infer() / start_async() -- an int for every Result, or {Result name: k} --, {} for
-    None.  Everything is looked up in the network as it was read: no device is needed, nothing is allocated."""
+    None.  Everything is looked up in the network as it was read: no device is needed, nothing is allocated.  ValueError ('top_k: ...'):
+    an unknown name, a sharded batch, a k that is no count, a Result whose declared shape is not (n, C) or (n, C, 1, ...) or that is not
+    FP32, k outside 1 .. min(C, 64)."""
     if top_k is None:
         return {}
-    results = {name: ienet.G.nodes[nid] for nid, name in ienet.find_node_by_type('Result')}
-    if isinstance(top_k, dict):
-        unknown = [name for name in top_k if name not in results]
-        if unknown:
-            raise ValueError('top_k: the network has no Result named {!r} (it has {})'.format(unknown[0], sorted(results)))
-        wanted = dict(top_k)
-    else:
-        wanted = {name: top_k for name in results}
-    if wanted and sharded:
-        raise ValueError('top_k: not with a batch sharded over ranks')
+    ports, wanted = ask.named(ienet, 'top_k', top_k, sharded)
     out = {}
     for name, k in wanted.items():
         if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
             raise ValueError('top_k: Result {!r}: k is a count from 1 to {}, got {!r}'.format(name, MAX_K, k))
-        port = next(iter(results[name]['input'].values()))
-        rows = rows_of(port['dims'])
-        if rows is None:
-            raise ValueError('top_k: Result {!r} has shape {}: not (n, C) or (n, C, 1, ...)'.format(name, tuple(port['dims'])))
-        if port['precision'] != 'FP32':
-            raise ValueError('top_k: Result {!r} is {}: FP32 Results only'.format(name, port['precision']))
+        rows = ask.declared('top_k', name, ports[name], rows_of(ports[name]['dims']), '(n, C) or (n, C, 1, ...)')
         if not 1 <= k <= min(rows[1], MAX_K):
             raise ValueError('top_k: Result {!r}: k = {} outside 1 .. min(C = {}, {})'.format(name, int(k), rows[1], MAX_K))
         out[name] = int(k)
     return out
 
 
-class Blocks:
+class Blocks(ask.FlatBlocks):
     """What a request keeps for one (Result name, k): the device block pvhip_topk_rows_f32 writes -- (n, k) int32 indices, then (n, k)
     float32 values -- and the page-locked host block it is read back into in one copy of 8 n k bytes."""
-    __slots__ = ('n', 'k', 'dev', 'host')
+    __slots__ = ('n', 'k')
 
     def __init__(self, n: int, k: int):
+        super().__init__(2 * n * k)
         self.n, self.k = n, k
-        self.dev = device.DeviceTensor.empty((2, n, k), np.int32)
-        self.host = device.host_empty((2, n, k), np.int32)
 
     def launch(self, result):
         """One launch on the current stream, behind whatever wrote `result` there."""
@@ -96,25 +83,20 @@ class Blocks:
 
     def read_back(self) -> TopK:
         """The pair, copied on the current stream, which has drained; the arrays are the caller's own."""
-        device.call('pvhip_memcpy_d2h', ctypes.c_void_p(self.host.ctypes.data), ctypes.c_void_p(self.dev.ptr), self.host.nbytes)
-        return TopK(self.host[0].copy(), self.host[1].view(np.float32).copy())
+        pair = self.words().reshape(2, self.n, self.k)
+        return TopK(pair[0].copy(), pair[1].view(np.float32).copy())
 
 
-class Ask(collections.namedtuple('Ask', 'k')):
-    """A Result asked for with top_k=k, as answers.py drives it: the key of its blocks, the launch on the value a pass left on the
-    device -- into `blocks`, or into new ones for None: they are returned --, and the rule on a host value."""
+class Ask(ask.Ask, collections.namedtuple('Ask', 'k')):
+    """A Result asked for with top_k=k."""
     __slots__ = ()
-
-    def bound(self, inputs, slots):
-        return self
+    KEYWORD = 'top_k'
 
     def key(self, name):
         return (name, self.k)
 
-    def launch(self, blocks, value):
-        blocks = blocks or Blocks(rows_of(value.shape)[0], self.k)
-        blocks.launch(value)
-        return blocks
+    def blocks_for(self, value):
+        return Blocks(rows_of(value.shape)[0], self.k)
 
     def on_host(self, value):
         return top_k_rows(value, self.k)
