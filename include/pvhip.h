@@ -684,6 +684,39 @@ int pvhip_heatmap_peaks_form(int h, int w);
 int pvhip_heatmap_peaks_f32(const float* x, int n, int k, int h, int w, int refine, int space, int has_min, float min_score,
                             int* positions, float* scores, float* points);
 
+/* ---------------------------------------------------------------- a segmentation network's answer ---- */
+/* Addition to ABI v19 (the version number is unchanged: nothing existing changed): the class map of a contiguous (n, c, h, w) fp32 stack
+ * of per-class score planes -- what a user of a semantic segmentation head makes on the host with an argmax across the planes after
+ * reading 4 n c h w bytes back, and the pixel count and bounding rectangle of every class with it -- so that one byte per pixel and 20
+ * bytes per (row, class) are read back.  The rule (pyopenvino_amd/segments.py states the same one in numpy and tests/segments_ref.py in
+ * plain loops, matched exactly), for pixel (y, x) of batch row r, with v[k] = X[r][k][y][x]:
+ *   1. best    k* is the first class of the pixel's c values in the total order of pvhip_topk_rows_f32 above: NaN of any sign or payload
+ *      first, then descending with +0.0 == -0.0, ties to the lower class.
+ *   2. void    the pixel is void iff v[k*] is NaN or (has_min == 1 and v[k*] < min_score).  Any NaN among a pixel's c scores therefore
+ *      voids it: the quiet-NaN rows behind `count` of a DetectedRois or LandmarkWarps pass are void all through.  Equality keeps.
+ *   3. label   labels[r][y][x] = k*, or PVHIP_SEGMENT_VOID (255) when void.  With c == 1 and a min_score: a thresholded mask.
+ *   4. sums    areas[r][k] is the number of pixels of row r labelled k; extents[r][k] = (x0, y0, x1, y1) is min x, min y, max x + 1 and
+ *      max y + 1 over those pixels.  Exact integers: the order in which they are accumulated does not matter.
+ * `labels` (n, h, w) uint8, `areas` (n, c) int32, `extents` (n, c, 4) int32.  A class without pixels in a row reads (w, h, 0, 0) in
+ * `extents` at this level, the state the initialising launch leaves, and not the (0, 0, 0, 0) of the public answer: the caller turns
+ * it (areas[r][k] == 0 says where).  `x` may be only 4-byte aligned and `labels` only byte aligned: the flat run of n h w label bytes
+ * is cut at its own 4-byte boundaries into quads of four pixels, each one aligned 32-bit store (the partial quads at the two ends of
+ * the run are stored by the byte), and the 16-byte loads of a quad stand at whatever 4-byte phase the planes put them.  Two launches on
+ * the current stream: one initialises `areas` and `extents`; one walks the quads with a bounded grid, a lane per quad, the classes four
+ * loads at a time, one 32-bit order word per pixel, areas and extents summed per (wave, row, class), gathered per workgroup in LDS and sent by integer vector atomics.
+ * Every score is read once; no workspace.  One form, PVHIP_SEGMENT_FORM_QUADS; pvhip_segment_labels_form returns the form of
+ * (c, h, w) -- no status, no device needed --, PVHIP_SEGMENT_FORM_NONE for what the entry refuses.
+ * n, c, h, w >= 1, c <= PVHIP_SEGMENT_MAX_CLASSES, 2 <= h * w <= PVHIP_SEGMENT_MAX_PLANE, n * h * w < 2^31, has_min 0 or 1, min_score
+ * finite, no NULL pointer, x / areas / extents 4-byte aligned; else PVHIP_EINVAL and nothing is launched. */
+#define PVHIP_SEGMENT_VOID         255
+#define PVHIP_SEGMENT_MAX_CLASSES  255
+#define PVHIP_SEGMENT_MAX_PLANE    (1 << 24)
+#define PVHIP_SEGMENT_FORM_NONE    0
+#define PVHIP_SEGMENT_FORM_QUADS   1
+int pvhip_segment_labels_form(int c, int h, int w);
+int pvhip_segment_labels_f32(const float* x, int n, int c, int h, int w, int has_min, float min_score,
+                             unsigned char* labels, int* areas, int* extents);
+
 /* ---------------------------------------------------------------- a detector's answer ------ */
 /* Addition to ABI v18 (the version number is unchanged: nothing existing changed): the records of pvhip_detection_output_f32 become one
  * flat table of the detections a caller wants -- what the reference's sample makes on the host with `for record in res.reshape(100, 7):
