@@ -684,6 +684,51 @@ int pvhip_heatmap_peaks_form(int h, int w);
 int pvhip_heatmap_peaks_f32(const float* x, int n, int k, int h, int w, int refine, int space, int has_min, float min_score,
                             int* positions, float* scores, float* points);
 
+/* ---------------------------------------------------------------- the local maxima of heatmaps ---- */
+/* Addition to ABI v19 (the version number is unchanged: nothing existing changed): the local maxima of every plane of a contiguous
+ * (n, k, h, w) fp32 stack of heatmaps with several objects per plane -- what a user of a CenterNet-style detector or of a multi-person
+ * pose head makes on the host with a 3 x 3 maximum filter and a partial sort after reading 4 n k h w bytes back -- so that 4 + 20
+ * max_per_row bytes per batch row are read back.  The rule (pyopenvino_amd/maxima.py states the same one in numpy and
+ * tests/maxima_ref.py in plain loops, matched bit for bit), for the plane v[0..h)[0..w) of batch row r and channel c:
+ *   1. maximum  key(q) is the key of (v[q], flat index q) in the total order of pvhip_topk_rows_f32 above: NaN of any sign or payload
+ *      first, then descending with +0.0 == -0.0, ties to the lower index.  Position p is a maximum iff v[p] is not NaN and key(p) is
+ *      larger than the key of each of its at most eight neighbours that lie inside the plane.  A plateau therefore yields only those
+ *      of its pixels that have no plateau neighbour before them in raster order; a flat plane has one maximum, at index 0.  A NaN is
+ *      never a maximum and suppresses all its neighbours: the quiet-NaN rows behind `count` of a DetectedRois or LandmarkWarps pass
+ *      have count 0.
+ *   2. screen   the maximum passes iff has_min == 0 or v[p] >= min_score.  Equality keeps.
+ *   3. per plane  the first max_per_plane passing maxima are kept, in descending key order.
+ *   4. per row  the kept maxima of the row's k planes are ordered by descending value, ties to the lower channel, then to the lower
+ *      position: the key of (value, c * h * w + p).  The first max_per_row are the answer.
+ *   5. refine / space  rules 3 and 4 of pvhip_heatmap_peaks_f32 above, word for word, applied at each answered position, with the same
+ *      PVHIP_PEAKS_NONE / PVHIP_PEAKS_QUARTER and PVHIP_PEAKS_HEATMAP / PVHIP_PEAKS_NORMALISED.
+ * `counts` (n) int32, `channels` (n, max_per_row) int32, `positions` (n, max_per_row) int32 the flat py * w + px, `scores`
+ * (n, max_per_row) fp32 the plane's own bits, `points` (n, max_per_row, 2) fp32 (x, y).  The first counts[r] slots of row r are its
+ * maxima, best first; the slots behind them are (-1, -1, quiet NaN, quiet NaN, quiet NaN), quiet NaN being 0x7FC00000.  `scratch` is
+ * device memory of n * k * max_per_plane 8-byte words that only the two launches read and write.  `x` may be only 4-byte aligned and a
+ * plane starts at any 4-byte phase.  Two launches on the current stream, no initialising one, no global-memory atomics: (1) every plane
+ * goes through LDS once in tiles of whole rows (column chunks of 1022, in the wave form 510, where w is larger) with a halo of one row above and below each
+ * tile (and one column beside a chunk), its 3 x 3 test runs on 32-bit order words, separably, and the max_per_plane largest passing
+ * keys of the plane, found by a bounded buffer of keys in LDS that is sorted and cut whenever the next tile could overflow it, go to
+ * `scratch`, padded with zeros; (2) one workgroup per batch row keeps the max_per_row largest of its k * max_per_plane keys, re-keyed
+ * with the channel, by the same device function, and one lane per slot writes the answer.  Two forms of launch (1), by h * w:
+ * PVHIP_MAXIMA_FORM_WAVE, one wave per plane, up to 1024 elements; PVHIP_MAXIMA_FORM_BLOCK, one 256-thread workgroup per plane.
+ * pvhip_heatmap_maxima_form returns the form of (h, w) -- no status, no device needed --, PVHIP_MAXIMA_FORM_NONE for a plane the
+ * entry refuses.
+ * n, k, h, w >= 1, 2 <= h * w <= PVHIP_MAXIMA_MAX_PLANE, k * h * w <= 2^31 - 1, 1 <= max_per_plane <= PVHIP_MAXIMA_MAX_PER_PLANE,
+ * 1 <= max_per_row <= PVHIP_MAXIMA_MAX_PER_ROW, n * k * max_per_plane < 2^31, refine and space each one of the two, has_min 0 or 1,
+ * min_score finite, no NULL pointer, `scratch` 8-byte and the others 4-byte aligned; else PVHIP_EINVAL and nothing is launched. */
+#define PVHIP_MAXIMA_MAX_PLANE      (1 << 24)
+#define PVHIP_MAXIMA_MAX_PER_PLANE  256
+#define PVHIP_MAXIMA_MAX_PER_ROW    1024
+#define PVHIP_MAXIMA_FORM_NONE      0
+#define PVHIP_MAXIMA_FORM_WAVE      1
+#define PVHIP_MAXIMA_FORM_BLOCK     2
+int pvhip_heatmap_maxima_form(int h, int w);
+int pvhip_heatmap_maxima_f32(const float* x, int n, int k, int h, int w, int max_per_plane, int max_per_row, int refine, int space,
+                             int has_min, float min_score, unsigned long long* scratch, int* counts, int* channels, int* positions,
+                             float* scores, float* points);
+
 /* ---------------------------------------------------------------- a segmentation network's answer ---- */
 /* Addition to ABI v19 (the version number is unchanged: nothing existing changed): the class map of a contiguous (n, c, h, w) fp32 stack
  * of per-class score planes -- what a user of a semantic segmentation head makes on the host with an argmax across the planes after

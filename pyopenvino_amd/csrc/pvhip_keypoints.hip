@@ -14,6 +14,7 @@
 //           L2: the plane has just gone through it), applies valid / refine / space and writes the answer.
 // Planes are walked by a grid-stride loop, so that n * K up to 2^31 - 1 needs no grid of that size.
 #include "pvhip_common.h"
+#include "pvhip_point_rule.h"
 #include "pvhip_topk_keys.h"
 
 using namespace pvhip;
@@ -22,7 +23,6 @@ namespace {
 
 constexpr int      kWavePlane = 1024;          // H * W at most for the wave form: 4 pieces of 16 bytes per lane
 constexpr int      kWaves     = kBlock / kWave;
-constexpr unsigned kQuietNaN  = 0x7FC00000u;
 
 struct PeakRule {
     int   h, w, refine, space, has_min;
@@ -53,10 +53,6 @@ __device__ __forceinline__ unsigned long long plane_scan(const unsigned* __restr
     return best;
 }
 
-__device__ __forceinline__ float quarter(float before, float after) {
-    return after > before ? 0.25f : (after < before ? -0.25f : 0.0f);           // (equal, zeros of either sign, a NaN: 0)
-}
-
 // Rules 2-4 for the plane whose largest key is `key`; one lane.
 __device__ __forceinline__ void plane_finish(const float* __restrict__ plane, unsigned long long key, const PeakRule& rule, size_t at,
                                              int* __restrict__ positions, unsigned* __restrict__ scores, unsigned* __restrict__ points) {
@@ -66,21 +62,7 @@ __device__ __forceinline__ void plane_finish(const float* __restrict__ plane, un
     const bool     nan  = (bits & 0x7FFFFFFFu) > 0x7F800000u;
     const bool     valid = !nan && (!rule.has_min || v >= rule.min_score);
     unsigned ux = kQuietNaN, uy = kQuietNaN;
-    if (valid) {
-        const int py = p / rule.w, px = p - py * rule.w;
-        float ox = 0.0f, oy = 0.0f;
-        if (rule.refine == PVHIP_PEAKS_QUARTER) {
-            if (px >= 1 && px <= rule.w - 2) ox = quarter(plane[p - 1], plane[p + 1]);
-            if (py >= 1 && py <= rule.h - 2) oy = quarter(plane[p - rule.w], plane[p + rule.w]);
-        }
-        float fx = (float)px + ox, fy = (float)py + oy;
-        if (rule.space == PVHIP_PEAKS_NORMALISED) {
-            fx = (float)((double)(fx + 0.5f) / (double)rule.w);
-            fy = (float)((double)(fy + 0.5f) / (double)rule.h);
-        }
-        ux = __float_as_uint(fx);
-        uy = __float_as_uint(fy);
-    }
+    if (valid) point_of(plane, p, rule.h, rule.w, rule.refine, rule.space, ux, uy);       // rules 3 and 4: pvhip_point_rule.h
     positions[at]      = p;
     scores[at]         = bits;                                                  // the plane's own bits
     points[2 * at]     = ux;

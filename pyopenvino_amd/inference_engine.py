@@ -311,23 +311,24 @@ class InferRequest:
                        a ``TiledScreen`` / ``RegionScreen`` over a RoiInput / DetectedRois      ``Detections``  tiled_detections.py
         `matches`      a ``Gallery`` or a ``GalleryMatch``                                      ``Matches``     gallery.py
         `keypoints`    a ``PeakScreen``, a min_score or True                                    ``Keypoints``   keypoints.py
-        `segments`     a ``SegmentScreen``, a min_score or True                                 ``Segments``    segments.py"""
+        `segments`     a ``SegmentScreen``, a min_score or True                                 ``Segments``    segments.py
+        `maxima`       a ``MaximaScreen``, a min_score or True                                  ``Maxima``      maxima.py"""
 
     def __init__(self, owner, runner, index: int):
         self.owner, self.runner, self.index = owner, runner, index      # owner: the network load_network returned
         self._in_flight, self._replayed = False, None
-        self._asks = {}                 # {Result name: ask} of the pass in flight (answers.py): what top_k=, detections=, matches=, keypoints= and segments= named
+        self._asks = {}                 # {Result name: ask} of the pass in flight (answers.py): what top_k=, detections=, matches=, keypoints=, segments= and maxima= named
 
-    def start_async(self, inputs: dict, top_k=None, detections=None, matches=None, keypoints=None, segments=None):
-        self._start(inputs, (top_k, detections, matches, keypoints, segments), False)
+    def start_async(self, inputs: dict, top_k=None, detections=None, matches=None, keypoints=None, segments=None, maxima=None):
+        self._start(inputs, (top_k, detections, matches, keypoints, segments, maxima), False)
 
     def _start(self, inputs, asked, verbose):
-        """`asked`: (top_k, detections, matches, keypoints, segments) as the public signatures took them."""
+        """`asked`: (top_k, detections, matches, keypoints, segments, maxima) as the public signatures took them."""
         if self._in_flight:
             raise RuntimeError('request {} is still in flight: wait() first'.format(self.index))
         ex = self.runner
         sharded = ex.sharded or self.owner.sharded
-        asks = ex.answers.checked(inputs, asked[0], asked[1], sharded, asked[2], asked[3], asked[4])
+        asks = ex.answers.checked(inputs, asked[0], asked[1], sharded, asked[2], asked[3], asked[4], asked[5])
         fed, inputs = inputs, ex.host_inputs.stage(inputs, ex.stream_base, sharded)
         self._asks = ex.answers.bound(asks, fed)
         ex.wait_result_readers()
@@ -368,8 +369,8 @@ class InferRequest:
                 G.nodes[nid]['result'] = out[name] = ex._read_back(value, self.owner.comm)
         return out
 
-    def infer(self, inputs: dict, top_k=None, detections=None, matches=None, keypoints=None, segments=None) -> dict:
-        self.start_async(inputs, top_k, detections, matches, keypoints, segments)
+    def infer(self, inputs: dict, top_k=None, detections=None, matches=None, keypoints=None, segments=None, maxima=None) -> dict:
+        self.start_async(inputs, top_k, detections, matches, keypoints, segments, maxima)
         return self.wait()
 
     def input_buffer(self, name: str, source_size=None, frames=None) -> np.ndarray:
@@ -552,8 +553,8 @@ class Executable_Network:
                 event.wait()
             device.select_stream(0)
 
-    def start_async(self, request_id: int, inputs: dict, top_k=None, detections=None, matches=None, keypoints=None, segments=None):
-        self.requests[request_id].start_async(inputs, top_k, detections, matches, keypoints, segments)
+    def start_async(self, request_id: int, inputs: dict, top_k=None, detections=None, matches=None, keypoints=None, segments=None, maxima=None):
+        self.requests[request_id].start_async(inputs, top_k, detections, matches, keypoints, segments, maxima)
 
     def wait(self, request_id: int) -> dict:
         return self.requests[request_id].wait()
@@ -1055,11 +1056,11 @@ class Executable_Network:
             return None
         return self._graph
 
-    def infer(self, inputs: dict, verbose: bool = False, top_k=None, detections=None, matches=None, keypoints=None, segments=None) -> dict:
-        """`top_k`, `detections`, `matches`, `keypoints`, `segments`: the Results they name come back as their answers (InferRequest has the table)."""
-        if not (top_k is detections is matches is keypoints is segments is None):     # something is asked: the pass of request 0 (this network's own graph and streams), waited for at once
+    def infer(self, inputs: dict, verbose: bool = False, top_k=None, detections=None, matches=None, keypoints=None, segments=None, maxima=None) -> dict:
+        """`top_k`, `detections`, `matches`, `keypoints`, `segments`, `maxima`: the Results they name come back as their answers (InferRequest has the table)."""
+        if not (top_k is detections is matches is keypoints is segments is maxima is None):     # something is asked: the pass of request 0 (this network's own graph and streams), waited for at once
             request = self.requests[0] if self.requests else InferRequest(self, self, 0)
-            request._start(inputs, (top_k, detections, matches, keypoints, segments), verbose)
+            request._start(inputs, (top_k, detections, matches, keypoints, segments, maxima), verbose)
             return request.wait()
         inputs = self.host_inputs.stage(inputs, self.stream_base, self.sharded)
         self.wait_result_readers()

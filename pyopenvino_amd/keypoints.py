@@ -103,7 +103,8 @@ def peaks(x, screen=True) -> Keypoints:
 def to_frame(points, regions):
     """'NORMALISED' `points` (n, K, 2) float32 through the integer (n, 5) table (id, x, y, w, h) of the regions the rows were cropped
     from: (n, K, 2) float64 in frame pixels, centres at the integers -- (float(x) + float(u) float(w)) - 0.5 in binary64, the position
-    ``landmarks.to_warps`` forms from the same point --; void points stay NaN."""
+    ``landmarks.to_warps`` forms from the same point --; void points stay NaN.  The `points` (n, R, 2) of a ``Maxima`` go through unchanged:
+    K is whatever the second extent is, and the filler slots behind a row's count stay NaN."""
     p = np.asarray(points)
     t = np.asarray(regions)
     if p.dtype != np.float32 or p.ndim != 3 or p.shape[2] != 2:
