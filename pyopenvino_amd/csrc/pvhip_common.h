@@ -101,6 +101,19 @@ inline int grid_for(size_t work_items, int per_block = kBlock) {
     return (int)b;
 }
 
+// The vector offset of a range-checked buffer load (or LDS-DMA copy) that must read zeros: past every buffer's range, whatever the
+// scalar offset adds -- a cell of the zero padding, a row outside the image, a tile past the end cost no test and no arithmetic.
+constexpr unsigned kOob = 0x80000000u;
+
+// XCD-aware tile walk: the tile (the first tile of a persistent walk) of workgroup `bid` in a grid of G.  The hardware deals
+// workgroups out to the eight XCDs round robin (XCD = bid & 7), and each XCD has an L2 of its own.  This gives the workgroups of one
+// XCD a contiguous run of tiles, the first G & 7 XCDs one tile more, so that neighbouring tiles -- the channel groups of one pixel
+// tile, which the tile orders keep back to back -- run on one XCD: the groups after the first find the activation tile in that L2.
+__device__ __forceinline__ int xcd_tile(int bid, int G) {
+    const int xcd = bid & 7, q = G >> 3, r = G & 7;
+    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+}
+
 // Division by a run-time-uniform divisor as multiply-high + shift (exact for n < 2^31).
 struct FastDiv {
     unsigned mul, shift, d;

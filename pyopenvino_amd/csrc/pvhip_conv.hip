@@ -59,19 +59,13 @@ __global__ __launch_bounds__(kBlock, 2) void conv_igemm_dma_kernel(ConvArgs a) {
     constexpr int A_PIECES = kBK * BM * 4 / 1024;          // 1-KiB wave-instructions per weight tile
     constexpr int A_PER_WAVE = (A_PIECES + 3) / 4;
     constexpr int B_LOADS = kBK * BN / kBlock;             // gather instructions per wave per stage
-    constexpr unsigned kOob = 0x80000000u;
     static_assert(BM % 32 == 0 && A_PIECES >= 1, "weight tile is whole 1-KiB pieces");
 
     __shared__ __attribute__((aligned(1024))) float As[2][kBK][BM];
     __shared__ __attribute__((aligned(1024))) float Bs[2][kBK][BN];
 
     const int nwg = gridDim.x;
-    int       lid;
-    {
-        const int bid = blockIdx.x;
-        const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-        lid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    }
+    const int lid = xcd_tile(blockIdx.x, nwg);
     const int mt    = lid % a.n_mtiles;
     const int ptile = lid / a.n_mtiles;
     const int m0    = mt * BM;

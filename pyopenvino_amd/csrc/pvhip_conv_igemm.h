@@ -130,12 +130,7 @@ __global__ __launch_bounds__(kBlock, 2) void conv_igemm_kernel(ConvArgs a) {
     // ---- tile assignment: XCD-aware remap so that workgroups sharing an L2 work on neighbouring
     // pixel tiles and all output-channel tiles of one pixel tile run back to back on one XCD.
     const int nwg = gridDim.x;
-    int       lid;
-    {
-        const int bid = blockIdx.x;
-        const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-        lid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    }
+    const int lid = xcd_tile(blockIdx.x, nwg);
     const int mt    = lid % a.n_mtiles;
     const int ptile = lid / a.n_mtiles;
     const int m0    = mt * BM;

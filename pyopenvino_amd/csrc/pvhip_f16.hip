@@ -18,23 +18,21 @@
 //                     of stage t.
 //   pvhip_matmul_f16  MatMul of an FP16 IR: fp16-rounded operands on the split-K fp32-MFMA kernel of pvhip_matmul.hip (exact products,
 //                     fp32 accumulation: the arithmetic of the f16 instruction; the FC layers are launch-size bound).
+// The vector types and the output placement are the FP16 family's (pvhip_f16_c8.h); the weight panel here is this kernel's own.
 #include <hip/hip_fp16.h>
 
-#include "pvhip_common.h"
+#include "pvhip_f16_c8.h"
 
 using namespace pvhip;
 
 namespace {
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef _Float16 half2v __attribute__((ext_vector_type(2)));
 typedef const __attribute__((address_space(4))) int* const_int_p;
 
 constexpr int kBK = 32;            // reduction rows per stage = two MFMA steps of 16
 constexpr int kLd = kBK + 8;       // LDS row of a pixel / an output channel in halves (80 bytes: b128 reads conflict-free)
 constexpr int kCBM = 64, kCBN = 128;
-constexpr unsigned kOob = 0x80000000u;
 
 struct ConvF16Args {
     const float*    x;
@@ -59,13 +57,7 @@ __global__ __launch_bounds__(kBlock) void conv_f16_kernel(ConvF16Args a) {
     __shared__ __attribute__((aligned(16))) _Float16 As[2][kCBM][kLd];
     __shared__ __attribute__((aligned(16))) _Float16 Bs[2][kCBN][kLd];
 
-    const int nwg = gridDim.x;
-    int       lid;
-    {
-        const int bid = blockIdx.x;
-        const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-        lid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    }
+    const int lid   = xcd_tile(blockIdx.x, gridDim.x);       // the channel tiles of a pixel tile back to back on one XCD
     const int mt    = lid % a.n_mtiles;
     const int ptile = lid / a.n_mtiles;
     const int tid   = threadIdx.x;
@@ -229,11 +221,11 @@ int pvhip_conv2d_f16(const float* x, const float* wpack, float* y, int n, int c,
     PVHIP_CHECK_ARG(n >= 0 && c > 0 && h > 0 && w > 0 && k_out > 0 && kh > 0 && kw > 0 && oh >= 0 && ow >= 0);
     PVHIP_CHECK_ARG(sh > 0 && sw > 0 && pad_top >= 0 && pad_left >= 0);
     PVHIP_CHECK_ARG(out_channels_total == 0 || (out_channel_offset >= 0 && out_channel_offset + k_out <= out_channels_total));
-    const unsigned long long in_e  = (unsigned long long)n * c * h * w,
-                             out_e = (unsigned long long)n * (out_channels_total > 0 ? out_channels_total : k_out) * oh * ow;
-    if (kh * kw >= 63 || in_e >= (1ull << 29) || out_e >= (1ull << 31))
+    const unsigned long long in_e = (unsigned long long)n * c * h * w;
+    const ConvPlace place = conv_place(n, k_out, oh, ow, out_channels_total, out_channel_offset);
+    if (kh * kw >= 63 || in_e >= (1ull << 29) || place.elems >= (1ull << 31))
         return fail(PVHIP_EUNSUPPORTED, "pvhip_conv2d_f16: window of 63+ taps, input of 2^29+ elements or output of 2^31+");
-    if (out_e == 0) return PVHIP_OK;
+    if (place.elems == 0) return PVHIP_OK;
     PVHIP_CHECK_ARG(x != nullptr && wpack != nullptr && y != nullptr);
     ConvF16Args a;
     a.kred_pad = round_up_int(c * kh * kw, kBK);
@@ -246,8 +238,8 @@ int pvhip_conv2d_f16(const float* x, const float* wpack, float* y, int n, int c,
     a.x_bytes = (unsigned)(in_e * 4ull);
     a.P = n * oh * ow;
     a.act = act; a.lo = act_lo; a.hi = act_hi;
-    a.y_ctotal = out_channels_total > 0 ? out_channels_total : k_out;
-    a.y_coff   = out_channels_total > 0 ? out_channel_offset : 0;
+    a.y_ctotal = place.ctotal;
+    a.y_coff   = place.coff;
     const long grid = (long)((a.P + kCBN - 1) / kCBN) * a.n_mtiles;
     hipLaunchKernelGGL(conv_f16_kernel, dim3((unsigned)grid), dim3(kBlock), 0, state().stream, a);
     PVHIP_LAUNCH_CHECK();

@@ -15,24 +15,21 @@
 // (HBM latency) and then its weight loads (L2 latency) -- and the first wait for a weight fragment was a wait for the copy in
 // front of it.  Here the copies are alone in the producer's queue, three stage buffers deep, and the consumers' queues hold
 // nothing but weight fragments; one s_barrier per stage joins them.
-#include "pvhip_common.h"
+// The c8 tensor, the fragment panel, the row-tile plan and the counted wait are those of pvhip_f16_c8.h; the kernel that packs the
+// panel for every reader, and the conversions at the boundary of the blocked layout, are in this file.
+#include "pvhip_f16_c8.h"
 
 using namespace pvhip;
 
 namespace {
 
-typedef float    floatx16 __attribute__((ext_vector_type(16)));
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-
 constexpr int kC8Threads = 320;     // four consumer waves + the producer wave
 constexpr int kC8MaxBuf  = 8;       // stage buffers: as many as fit (C8Args.nbuf)
 constexpr int kC8MaxRows = 10;      // LDS rows per channel block and stage (R + 2 pad): 3 x 2 x 10 KB = 60 KB
-constexpr unsigned kOob  = 0x80000000u;
 
 struct C8Args {
     const _Float16* xb;      // [N][CB][H*W][8]
-    const _Float16* wf;      // [n_mtiles][CB / 2][taps][tm][64 lanes][8 halves]  (the span kernel's fragments)
+    const _Float16* wf;      // [n_mtiles][CB / 2][taps][tm][64 lanes][8 halves]  (the fragment panel of pvhip_f16_c8.h)
     float*          y;
     const float*    bias;
     int N, CB, H, W, K;
@@ -45,45 +42,6 @@ struct C8Args {
     float lo, hi;
     int   y_ctotal, y_coff;
 };
-
-__device__ __forceinline__ void c8_wait_vmcnt(int n) {      // until at most n of this wave's copies are in flight (n: wave-uniform, even)
-#if defined(__HIP_DEVICE_COMPILE__)
-    switch (n < 62 ? n : 62) {
-        case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
-        case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-        case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
-        case 8: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
-        case 10: asm volatile("s_waitcnt vmcnt(10)" ::: "memory"); break;
-        case 12: asm volatile("s_waitcnt vmcnt(12)" ::: "memory"); break;
-        case 14: asm volatile("s_waitcnt vmcnt(14)" ::: "memory"); break;
-        case 16: asm volatile("s_waitcnt vmcnt(16)" ::: "memory"); break;
-        case 18: asm volatile("s_waitcnt vmcnt(18)" ::: "memory"); break;
-        case 20: asm volatile("s_waitcnt vmcnt(20)" ::: "memory"); break;
-        case 22: asm volatile("s_waitcnt vmcnt(22)" ::: "memory"); break;
-        case 24: asm volatile("s_waitcnt vmcnt(24)" ::: "memory"); break;
-        case 26: asm volatile("s_waitcnt vmcnt(26)" ::: "memory"); break;
-        case 28: asm volatile("s_waitcnt vmcnt(28)" ::: "memory"); break;
-        case 30: asm volatile("s_waitcnt vmcnt(30)" ::: "memory"); break;
-        case 32: asm volatile("s_waitcnt vmcnt(32)" ::: "memory"); break;
-        case 34: asm volatile("s_waitcnt vmcnt(34)" ::: "memory"); break;
-        case 36: asm volatile("s_waitcnt vmcnt(36)" ::: "memory"); break;
-        case 38: asm volatile("s_waitcnt vmcnt(38)" ::: "memory"); break;
-        case 40: asm volatile("s_waitcnt vmcnt(40)" ::: "memory"); break;
-        case 42: asm volatile("s_waitcnt vmcnt(42)" ::: "memory"); break;
-        case 44: asm volatile("s_waitcnt vmcnt(44)" ::: "memory"); break;
-        case 46: asm volatile("s_waitcnt vmcnt(46)" ::: "memory"); break;
-        case 48: asm volatile("s_waitcnt vmcnt(48)" ::: "memory"); break;
-        case 50: asm volatile("s_waitcnt vmcnt(50)" ::: "memory"); break;
-        case 52: asm volatile("s_waitcnt vmcnt(52)" ::: "memory"); break;
-        case 54: asm volatile("s_waitcnt vmcnt(54)" ::: "memory"); break;
-        case 56: asm volatile("s_waitcnt vmcnt(56)" ::: "memory"); break;
-        case 58: asm volatile("s_waitcnt vmcnt(58)" ::: "memory"); break;
-        case 60: asm volatile("s_waitcnt vmcnt(60)" ::: "memory"); break;
-        case 62: asm volatile("s_waitcnt vmcnt(62)" ::: "memory"); break;
-        default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;      // fewer in flight than allowed: correct, only slower
-    }
-#endif
-}
 
 #ifdef PVHIP_DIAG
 // diagnostic build: cycle accounts of conv_f16_c8_kernel, summed over every 16th workgroup (scripts/stamps_f16_c8.py).
@@ -118,12 +76,7 @@ __global__ __launch_bounds__(kC8Threads, (KS == 5 && NB == 4) ? 3 : 4) void conv
     // tiles = (channel group, image, row tile), the channel groups of a pixel tile back to back; the workgroups of one XCD
     // (blockIdx & 7) take neighbouring tiles, so that the groups of a pixel tile find it in that XCD's L2
     const int G = gridDim.x;
-    int       L;
-    {
-        const int bid = blockIdx.x;
-        const int xcd = bid & 7, q = G >> 3, r = G & 7;
-        L = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    }
+    const int L = xcd_tile(blockIdx.x, G);
     const int my_tiles = L < a.n_tiles ? (a.n_tiles - L + G - 1) / G : 0;
     const int S = my_tiles * ncs;                                        // stages of this workgroup
 
@@ -163,7 +116,7 @@ __global__ __launch_bounds__(kC8Threads, (KS == 5 && NB == 4) ? 3 : 4) void conv
         PVC8_STAMP(8, p1 - p0);
         for (int s = 0; s < S; ++s) {
             const unsigned long long q0 = PVC8_NOW();
-            c8_wait_vmcnt((s_i - s - 1) * n_ins);                        // stage s has landed (the younger ones may fly)
+            wait_vmcnt((s_i - s - 1) * n_ins);                        // stage s has landed (the younger ones may fly)
             const unsigned long long q1 = PVC8_NOW();
             asm volatile("s_barrier" ::: "memory");                      // B(s): the consumers have also finished stage s - 1 ...
             const unsigned long long q2 = PVC8_NOW();
@@ -310,8 +263,7 @@ __global__ __launch_bounds__(kC8Threads, (KS == 5 && NB == 4) ? 3 : 4) void conv
 #undef PVC8_HAVE
 }
 
-// w (K, C, ks, ks) fp32 -> fp16 fragments [mt][cs][tap][i][lane][q]: channel (mt * TM + i) * 32 + lane % 32, input channel
-// cs * 16 + 8 * (lane / 32) + q; output channels past K and input channels past C (C is padded to whole stages) are zero
+// The fragment panel of pvhip_f16_c8.h, for every kernel that reads it: ncs = the stages of C padded to whole ones
 __global__ __launch_bounds__(kBlock) void conv_f16_c8_pack_kernel(const float* __restrict__ w, _Float16* __restrict__ wf, int K, int C,
                                                                   int ncs, int taps, int tm, size_t total) {
     for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
@@ -353,26 +305,6 @@ __global__ __launch_bounds__(kBlock) void c8_to_f32_kernel(const _Float16* __res
     }
 }
 
-inline int c8_blocks(int c) { return (c + 15) / 16 * 2; }             // channel blocks of a c8 tensor: whole 16-channel stages
-inline int c8_mtiles(int k) { return (k + 127) / 128; }
-inline int c8_tm(int k) { const int t32 = (k + 31) / 32, nm = c8_mtiles(k); return (t32 + nm - 1) / nm; }
-
-struct C8Tile { int R, tiles, rows, nb; };
-inline bool c8_tile(int h, int w, int ks, C8Tile& t) {
-    const int pad = (ks - 1) / 2;
-    if (h <= 0 || w <= 0 || w + 2 * pad > 64) return false;           // lane l fetches column l - pad: the row and its padding in 64 lanes
-    int r = 128 / w;
-    if (r > kC8MaxRows - 2 * pad) r = kC8MaxRows - 2 * pad;
-    if (r > h) r = h;
-    if (r < 1) return false;
-    t.tiles = (h + r - 1) / r;
-    t.R     = (h + t.tiles - 1) / t.tiles;
-    t.tiles = (h + t.R - 1) / t.R;
-    t.rows  = t.R + 2 * pad;
-    t.nb    = t.R * w <= 64 ? 2 : 4;
-    return true;
-}
-
 template <int KS>
 void launch_c8(const C8Args& a, int grid, int nb, size_t lds) {
     if (nb == 2) hipLaunchKernelGGL((conv_f16_c8_kernel<KS, 2>), dim3(grid), dim3(kC8Threads), lds, state().stream, a);
@@ -380,6 +312,12 @@ void launch_c8(const C8Args& a, int grid, int nb, size_t lds) {
 }
 
 }  // namespace
+
+void pvhip::launch_frag_pack(const float* w_oihw, float* wf, int k, int c, int taps) {
+    const size_t total = frag_panel_halves(k, c, taps);
+    hipLaunchKernelGGL(conv_f16_c8_pack_kernel, dim3(grid_for(total)), dim3(kBlock), 0, state().stream, w_oihw, reinterpret_cast<_Float16*>(wf), k, c,
+                       c8_blocks(c) / 2, taps, frag_tm(k), total);
+}
 
 extern "C" {
 
@@ -414,23 +352,19 @@ int pvhip_conv2d_f16_c8_supported(int c, int h, int w, int kh, int kw, int sh, i
     if (c <= 0 || kh != kw || (kh != 1 && kh != 3 && kh != 5) || sh != 1 || sw != 1) return 0;
     const int pad = (kh - 1) / 2;
     if (pad_top != pad || pad_left != pad || oh != h || ow != w) return 0;
-    C8Tile t;
-    return c8_tile(h, w, kh, t) ? 1 : 0;
+    C8RowTiles t;
+    return c8_row_tiles(h, w, pad, kC8MaxRows, t) ? 1 : 0;
 }
 
 size_t pvhip_conv2d_f16_c8_pack_elems(int k_out, int c, int kh, int kw) {          // FLOATS of the fragment panel
     if (k_out <= 0 || c <= 0 || kh <= 0 || kw <= 0) return 0;
-    const size_t halves = (size_t)c8_mtiles(k_out) * (c8_blocks(c) / 2) * kh * kw * c8_tm(k_out) * 512;
-    return (halves + 1) / 2;
+    return frag_panel_halves(k_out, c, kh * kw) / 2;                               // (whole fragments of 512 halves)
 }
 
 int pvhip_conv2d_f16_c8_pack(const float* w_oihw, float* wf, int k_out, int c, int kh, int kw) {
     PVHIP_REQUIRE_INIT();
     PVHIP_CHECK_ARG(w_oihw != nullptr && wf != nullptr && k_out > 0 && c > 0 && kh > 0 && kh == kw && kh <= 5);
-    const int    ncs   = c8_blocks(c) / 2;
-    const size_t total = (size_t)c8_mtiles(k_out) * ncs * kh * kw * c8_tm(k_out) * 512;
-    hipLaunchKernelGGL(conv_f16_c8_pack_kernel, dim3(grid_for(total)), dim3(kBlock), 0, state().stream, w_oihw, reinterpret_cast<_Float16*>(wf), k_out, c,
-                       ncs, kh * kw, c8_tm(k_out), total);
+    launch_frag_pack(w_oihw, wf, k_out, c, kh * kw);
     PVHIP_LAUNCH_CHECK();
     return PVHIP_OK;
 }
@@ -444,25 +378,25 @@ int pvhip_conv2d_f16_c8(const void* xb, const float* wf, float* y, int n, int c,
         return fail(PVHIP_EUNSUPPORTED, "pvhip_conv2d_f16_c8: stride-1 \"same\" 1x1 / 3x3 / 5x5 windows over rows of at most %d pixels", 64 - 2 * pad);
     PVHIP_CHECK_ARG(out_channels_total == 0 || (out_channel_offset >= 0 && out_channel_offset + k_out <= out_channels_total));
     const int cb = c8_blocks(c);
-    const unsigned long long in_b = (unsigned long long)n * cb * h * w * 16ull,
-                             out_e = (unsigned long long)n * (out_channels_total > 0 ? out_channels_total : k_out) * h * w;
-    if (in_b >= (1ull << 31) || out_e >= (1ull << 31)) return fail(PVHIP_EUNSUPPORTED, "pvhip_conv2d_f16_c8: input exceeds 2^31 bytes or output 2^31 elements");
+    const unsigned long long in_b = (unsigned long long)n * cb * h * w * 16ull;
+    const ConvPlace place = conv_place(n, k_out, h, w, out_channels_total, out_channel_offset);
+    if (in_b >= (1ull << 31) || place.elems >= (1ull << 31)) return fail(PVHIP_EUNSUPPORTED, "pvhip_conv2d_f16_c8: input exceeds 2^31 bytes or output 2^31 elements");
     if (n == 0) return PVHIP_OK;
     PVHIP_CHECK_ARG(xb != nullptr && wf != nullptr && y != nullptr);
-    C8Tile t;
-    c8_tile(h, w, kh, t);
+    C8RowTiles t;
+    c8_row_tiles(h, w, pad, kC8MaxRows, t);
     C8Args a;
     a.xb = static_cast<const _Float16*>(xb); a.wf = reinterpret_cast<const _Float16*>(wf); a.y = y; a.bias = bias;
     a.N = n; a.CB = cb; a.H = h; a.W = w; a.K = k_out;
-    a.tm = c8_tm(k_out);
-    a.n_mtiles = c8_mtiles(k_out);
+    a.tm = frag_tm(k_out);
+    a.n_mtiles = frag_mtiles(k_out);
     a.tiles_per_image = t.tiles;
     a.R = t.R; a.rows = t.rows;
     a.x_bytes  = (unsigned)in_b;
-    a.wf_bytes = (unsigned)(pvhip_conv2d_f16_c8_pack_elems(k_out, c, kh, kw) * 4);
+    a.wf_bytes = (unsigned)(frag_panel_halves(k_out, c, kh * kw) * 2);
     a.act = act; a.lo = act_lo; a.hi = act_hi;
-    a.y_ctotal = out_channels_total > 0 ? out_channels_total : k_out;
-    a.y_coff   = out_channels_total > 0 ? out_channel_offset : 0;
+    a.y_ctotal = place.ctotal;
+    a.y_coff   = place.coff;
     const long tiles = (long)n * t.tiles * a.n_mtiles;
     if (tiles > 0x3fffffffL) return fail(PVHIP_EUNSUPPORTED, "pvhip_conv2d_f16_c8: too many tiles");
     a.n_tiles = (int)tiles;

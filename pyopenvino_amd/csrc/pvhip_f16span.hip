@@ -14,17 +14,16 @@
 //      zero padding -- rows of W + 2 * pad pixels, the border never written -- so that a tap is a constant shift and needs no test;
 //   3. every tap is then one ds_read_b128 per 32 pixels (the eight channels of a lane's MFMA operand) and one MFMA per channel tile.
 // The waves split the OUTPUT CHANNELS (wave w: tile w of the group), so no two waves load the same weights; the weights
-// never touch LDS: fp16 MFMA fragments packed once ([channel group][stage][tap][tile][lane][8 halves]: one 16-byte load per lane and
-// MFMA, the next tap's in flight).  The first version split the PIXELS between the waves, read eight floats and converted them per tap,
-// and every wave loaded every weight fragment: 216 KB of weights per workgroup and stage through L1 -- slower than the kernel it replaces.
-#include "pvhip_common.h"
+// never touch LDS: fp16 MFMA fragments packed once (the fragment panel of pvhip_f16_c8.h, [channel group][stage][tap][tile][lane][8
+// halves]: one 16-byte load per lane and MFMA, the next tap's in flight).  The first version split the PIXELS between the waves, read
+// eight floats and converted them per tap, and every wave loaded every weight fragment: 216 KB of weights per workgroup and stage
+// through L1 -- slower than the kernel it replaces.
+#include "pvhip_f16_c8.h"
 
 using namespace pvhip;
 
 namespace {
 
-typedef float    floatx16 __attribute__((ext_vector_type(16)));
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
 constexpr int kSC    = 16;           // input channels per stage = the K of one MFMA
@@ -232,26 +231,6 @@ __global__ __launch_bounds__(kBlock) void conv_f16_span_kernel(SpanArgs a) {
     }
 }
 
-// w (K, C, ks, ks) fp32 -> fp16 fragments [mt][cs][tap][i][lane][q]: channel (mt * TM + i) * 32 + lane % 32, input channel
-// cs * 16 + 8 * (lane / 32) + q; channels past K are zero
-__global__ __launch_bounds__(kBlock) void conv_f16_span_pack_kernel(const float* __restrict__ w, _Float16* __restrict__ wf, int K, int C,
-                                                                    int taps, int tm, size_t total) {
-    const int ncs = C / kSC;
-    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
-        const int q = (int)(e & 7), lane = (int)((e >> 3) & 63);
-        size_t    f = e >> 9;                       // ((mt * ncs + cs) * taps + tap) * tm + i
-        const int i = (int)(f % tm);   f /= tm;
-        const int tap = (int)(f % taps); f /= taps;
-        const int cs = (int)(f % ncs);
-        const int mt = (int)(f / ncs);
-        const int k = (mt * tm + i) * 32 + (lane & 31), c = cs * kSC + 8 * (lane >> 5) + q;
-        wf[e] = k < K ? (_Float16)w[((size_t)k * C + c) * taps + tap] : (_Float16)0.0f;
-    }
-}
-
-inline int span_mtiles(int k) { return (k + 127) / 128; }      // channel groups of up to 128: one tile per wave (two: 300 registers, one wave per SIMD)
-inline int span_tm(int k) { const int t32 = (k + 31) / 32, nm = span_mtiles(k); return (t32 + nm - 1) / nm; }
-
 template <int KS, bool VEC>
 void launch_span(const SpanArgs& a, int grid) {
     hipLaunchKernelGGL((conv_f16_span_kernel<1, KS, VEC>), dim3(grid), dim3(kBlock), 0, state().stream, a);
@@ -272,16 +251,13 @@ int pvhip_conv2d_f16_span_supported(int c, int h, int w, int kh, int kw, int sh,
 
 size_t pvhip_conv2d_f16_span_pack_elems(int k_out, int c, int kh, int kw) {       // FLOATS of the fragment panel
     if (k_out <= 0 || c <= 0 || c % kSC != 0 || kh <= 0 || kw <= 0) return 0;
-    const size_t halves = (size_t)span_mtiles(k_out) * (c / kSC) * kh * kw * span_tm(k_out) * 512;
-    return (halves + 1) / 2;
+    return frag_panel_halves(k_out, c, kh * kw) / 2;                              // (whole fragments of 512 halves)
 }
 
 int pvhip_conv2d_f16_span_pack(const float* w_oihw, float* wf, int k_out, int c, int kh, int kw) {
     PVHIP_REQUIRE_INIT();
     PVHIP_CHECK_ARG(w_oihw != nullptr && wf != nullptr && k_out > 0 && c > 0 && c % kSC == 0 && kh > 0 && kh == kw && kh <= 5);
-    const size_t total = (size_t)span_mtiles(k_out) * (c / kSC) * kh * kw * span_tm(k_out) * 512;
-    hipLaunchKernelGGL(conv_f16_span_pack_kernel, dim3(grid_for(total)), dim3(kBlock), 0, state().stream, w_oihw,
-                       reinterpret_cast<_Float16*>(wf), k_out, c, kh * kw, span_tm(k_out), total);
+    launch_frag_pack(w_oihw, wf, k_out, c, kh * kw);
     PVHIP_LAUNCH_CHECK();
     return PVHIP_OK;
 }
@@ -294,22 +270,22 @@ int pvhip_conv2d_f16_span(const float* x, const float* wf, float* y, int n, int 
     if (!pvhip_conv2d_f16_span_supported(c, h, w, kh, kw, sh, sw, pad_top, pad_left, oh, ow))
         return fail(PVHIP_EUNSUPPORTED, "pvhip_conv2d_f16_span: stride-1 \"same\" 1x1 / 3x3 / 5x5 windows with C %% 16 == 0 and rows of at most %d floats", 61);
     PVHIP_CHECK_ARG(out_channels_total == 0 || (out_channel_offset >= 0 && out_channel_offset + k_out <= out_channels_total));
-    const unsigned long long in_e = (unsigned long long)n * c * h * w,
-                             out_e = (unsigned long long)n * (out_channels_total > 0 ? out_channels_total : k_out) * h * w;
-    if (in_e >= (1ull << 29) || out_e >= (1ull << 31)) return fail(PVHIP_EUNSUPPORTED, "pvhip_conv2d_f16_span: input exceeds 2^29 elements or output 2^31");
+    const unsigned long long in_e = (unsigned long long)n * c * h * w;
+    const ConvPlace place = conv_place(n, k_out, h, w, out_channels_total, out_channel_offset);
+    if (in_e >= (1ull << 29) || place.elems >= (1ull << 31)) return fail(PVHIP_EUNSUPPORTED, "pvhip_conv2d_f16_span: input exceeds 2^29 elements or output 2^31");
     if (n == 0) return PVHIP_OK;
     PVHIP_CHECK_ARG(x != nullptr && wf != nullptr && y != nullptr);
     SpanArgs a;
     a.x = x; a.wf = reinterpret_cast<const _Float16*>(wf); a.y = y; a.bias = bias;
     a.N = n; a.C = c; a.H = h; a.W = w; a.K = k_out;
-    a.tm = span_tm(k_out);
+    a.tm = frag_tm(k_out);
     a.tiles_per_image = (h * w + kTile - 1) / kTile;
-    a.n_mtiles = span_mtiles(k_out);
+    a.n_mtiles = frag_mtiles(k_out);
     a.x_bytes  = (unsigned)(in_e * 4ull);
-    a.wf_bytes = (unsigned)(pvhip_conv2d_f16_span_pack_elems(k_out, c, kh, kw) * 4);
+    a.wf_bytes = (unsigned)(frag_panel_halves(k_out, c, kh * kw) * 2);
     a.act = act; a.lo = act_lo; a.hi = act_hi;
-    a.y_ctotal = out_channels_total > 0 ? out_channels_total : k_out;
-    a.y_coff   = out_channels_total > 0 ? out_channel_offset : 0;
+    a.y_ctotal = place.ctotal;
+    a.y_coff   = place.coff;
     a.abl = 0;
 #ifdef PVHIP_DIAG
     a.abl = settings().conv_ablate;

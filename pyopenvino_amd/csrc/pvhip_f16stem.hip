@@ -8,17 +8,14 @@
 // selects the row -- so the operand of a lane is eight consecutive floats of one LDS row: three ds_read_b64 and one ds_read_b32 (stride 2
 // keeps the first tap 8-byte aligned), rounded to fp16 (nearest even) on the way.  21 filter rows = 11 steps (10.5: the last half step
 // multiplies zeros).  Weights: fp16 fragments in that k order straight from L2, one step ahead; no copy is in flight then.  Output: fp16
-// blocked by eight channels, as the MaxPool + LRN launch behind it reads it.
-#include "pvhip_common.h"
+// blocked by eight channels (the c8 tensor of pvhip_f16_c8.h), as the MaxPool + LRN launch behind it reads it.
+#include "pvhip_f16_c8.h"
 
 using namespace pvhip;
 
 namespace {
 
-typedef float    floatx16 __attribute__((ext_vector_type(16)));
 typedef float    float2v __attribute__((ext_vector_type(2)));
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
 
 constexpr int kC = 3, kKH = 7, kKW = 7, kST = 2;
 constexpr int kR = 2;                               // output rows per workgroup
@@ -26,7 +23,6 @@ constexpr int kRows = kST * (kR - 1) + kKH;         // input rows per channel: 9
 constexpr int kLdsRow = 256;                        // floats per LDS row: one copy instruction (64 lanes x 16 bytes) never reaches into the next row
 constexpr int kFRows = kC * kKH;                    // filter rows: 21
 constexpr int kSteps = (kFRows + 1) / 2;            // MFMA steps: 11
-constexpr unsigned kOob = 0x80000000u;
 
 struct StemArgs {
     const float*    xp;      // zero-padded input [N][3][HP][WP], WP % 4 == 0
@@ -151,7 +147,6 @@ __global__ __launch_bounds__(kBlock, 4) void conv_f16_stem_kernel(StemArgs a) {
     const int P0  = oy0 * a.OW + l31;
     // two register groups at a time, v_permlane32_swap between the lane halves: a lane of the lower half ends up with all eight channels of
     // block 4 ct + 2 gp, its partner in the upper half with those of the next block -- one 16-byte store per lane (see conv_f16_c8m_kernel)
-    typedef unsigned uint4v __attribute__((ext_vector_type(4)));
 #pragma unroll
     for (int gp = 0; gp < 2; ++gp) {
         float bs0[2][4], bs1[2][4];

@@ -78,7 +78,6 @@ __global__ __launch_bounds__(NW * 128, (BM <= 64 && VEC == 1) || (BM <= 64 && VE
     constexpr int GROUPS = BN / VEC;                 // pixel groups per channel row of the tile
     constexpr int CSUB = PRODUCERS * kWave / GROUPS;  // channels the producer lanes cover at once
     constexpr int ITER = kBK / CSUB;                 // producer iterations per stage
-    constexpr unsigned kOob = 0x80000000u;
     constexpr bool kWide = VEC == 2;                 // a group of two pixels is loaded as four (the columns around it ride along)
     typedef float vec_t __attribute__((ext_vector_type(VEC)));
 
@@ -86,12 +85,7 @@ __global__ __launch_bounds__(NW * 128, (BM <= 64 && VEC == 1) || (BM <= 64 && VE
     __shared__ __attribute__((aligned(1024))) float Bs[2][kBK][BN];
 
     const int nwg = gridDim.x;
-    int       lid;
-    {
-        const int bid = blockIdx.x;
-        const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-        lid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    }
+    const int lid = xcd_tile(blockIdx.x, nwg);
     const int mt    = lid % a.n_mtiles;
     const int ptile = lid / a.n_mtiles;
     const int m0    = mt * BM;

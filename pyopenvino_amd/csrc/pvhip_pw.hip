@@ -33,7 +33,6 @@ typedef float float4v __attribute__((ext_vector_type(4)));
 typedef float float2v __attribute__((ext_vector_type(2)));
 
 constexpr int kBK = 16;            // input channels per stage
-constexpr unsigned kOob = 0x80000000u;
 
 struct PwArgs {
     const float* x;
@@ -164,12 +163,7 @@ __global__ __launch_bounds__(kBlock, NB == 3 ? 6 : 4) void conv_pw_kernel(PwArgs
     // XCD-aware tile order: the channel chunks of one pixel tile run back to back on one XCD (the chunks after the first
     // find the activation tile in that L2)
     const int nwg = gridDim.x;
-    int       lid;
-    {
-        const int bid = blockIdx.x;
-        const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-        lid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    }
+    const int lid = xcd_tile(blockIdx.x, nwg);
     const int chunk = lid % a.nchunk;
     const int p0    = (lid / a.nchunk) * BN;
     const int lane  = threadIdx.x & (kWave - 1);

@@ -41,7 +41,6 @@ constexpr int kSteps = (kTaps + 3) / 4;              // 37
 constexpr int kNG    = 7;                            // 16-pixel groups per output row: rows of at most 112 pixels
 constexpr int kWaves = 2 * kTR;                      // 8: two per SIMD
 constexpr int kThreads = kWaves * kWave;             // 512; ONE workgroup per CU
-constexpr unsigned kOob = 0x80000000u;
 constexpr bool kTransposeStores = true;              // the epilogue's stores as whole output rows, through LDS (a.tstores; PVHIP_TUNE4=1 switches it off)
 constexpr int kTsPitch = 116;                        // floats per channel row of a wave's transposition buffer (112 pixels + 4)
 constexpr int kTsWave  = 16 * kTsPitch;              // one accumulator tile: 16 channels

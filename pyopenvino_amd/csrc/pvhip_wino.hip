@@ -134,7 +134,6 @@ __global__ __launch_bounds__(WAVES * kWave, (WAVES == 8 || MT * NTL == 1) ? 4 : 
     static_assert(WAVES == 4 || WAVES == 8, "four or eight waves");
     constexpr int THREADS = WAVES * kWave;
     constexpr int TPW = TILES * 4 / WAVES;    // accumulator tiles per wave and xi
-    constexpr unsigned kOob = 0x80000000u;
     constexpr int KB = 32 * MT, NT = 32 * NTL;
     constexpr int U_PIECES = 16 * kCB * KB * 4 / 1024;      // 1-KiB pieces of one U stage image: 8 * MT
     constexpr int U_PER_WAVE = U_PIECES / WAVES;
@@ -148,12 +147,7 @@ __global__ __launch_bounds__(WAVES * kWave, (WAVES == 8 || MT * NTL == 1) ? 4 : 
     static_assert(sizeof(Stage) == (TILES == 2 ? 48 : 32) * 1024, "48 (32) KB of LDS");
 
     const int nwg = gridDim.x;
-    int       lid;
-    {
-        const int bid = blockIdx.x;
-        const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-        lid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    }
+    const int lid = xcd_tile(blockIdx.x, nwg);
     const int kb = lid % a.n_kb;          // the channel blocks of one patch block run back to back on one XCD
     const int tb = lid / a.n_kb;
 
@@ -618,7 +612,6 @@ __global__ __launch_bounds__(512, 4) void conv_wino4_kernel(WinoArgs a) {
     static_assert(M == 4 || M == 2, "F(4x4,3x3) or F(2x2,5x5)");
     constexpr int PAD = (M == 4) ? 1 : 2;               // 6 = M + kernel - 1 input rows / columns starting at M*t - PAD
     constexpr int KB = 32, NT = 32, WAVES = 8, CONSUMERS = 6;
-    constexpr unsigned kOob = 0x80000000u;
     // V0 first: the epilogue's exchange area is V1 and the space behind it, and V0 holds stage 0 of the NEXT tile by then.  The
     // weight images U do not pass through LDS: every consumer loads its own MFMA A operands straight into registers (three 16-byte
     // loads per lane and stage from a panel packed in that order: wino4_u_offset) -- an LDS-DMA piece costs its wave 60-185 issue
@@ -635,12 +628,7 @@ __global__ __launch_bounds__(512, 4) void conv_wino4_kernel(WinoArgs a) {
     (void)r_entry;
 
     const int G = gridDim.x;
-    int       L;                 // first tile: workgroups of one XCD (blockIdx & 7) take neighbouring tiles (same patches, other channel blocks)
-    {
-        const int bid = blockIdx.x;
-        const int xcd = bid & 7, q = G >> 3, r = G & 7;
-        L = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    }
+    const int L = xcd_tile(blockIdx.x, G);                 // first tile: workgroups of one XCD (blockIdx & 7) take neighbouring tiles (same patches, other channel blocks)
     const int n_tiles = a.n_tiles;
     const int n_eff   = a.n_stages + (a.n_stages & 1);       // an odd stage count runs one more stage on the panel's spare zero image
 
@@ -1207,7 +1195,6 @@ __global__ __launch_bounds__(1024, 4) void conv_wino4s_kernel(WinoArgs a) {
     static_assert(M == 4 || M == 2, "F(4x4,3x3) or F(2x2,5x5)");
     constexpr int PAD = (M == 4) ? 1 : 2;
     constexpr int KB = 32, NT = 32, CONS = 12;
-    constexpr unsigned kOob = 0x80000000u;
     constexpr int kExBuf = 6 * 4 * 32 * M;            // floats of one exchange buffer: [row][slot][patch][M columns], 4 slots = 2 accumulator registers x 2 lane halves
     struct Smem {
         float    V[kSRing][kXi4][kCB][NT];             // 4 x 18 KB
@@ -1218,12 +1205,7 @@ __global__ __launch_bounds__(1024, 4) void conv_wino4s_kernel(WinoArgs a) {
     static_assert(sizeof(Smem) <= 150 * 1024, "one workgroup per CU");
 
     const int G = gridDim.x;
-    int       L;
-    {
-        const int bid = blockIdx.x;
-        const int xcd = bid & 7, q = G >> 3, r = G & 7;
-        L = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    }
+    const int L = xcd_tile(blockIdx.x, G);
     const int n_kp    = (a.n_kb + 1) >> 1;              // pairs of channel blocks (an odd count: the last pair is one block, its second consumer group only keeps the counters going)
     const int n_tb_s  = a.n_tiles / n_kp;               // patch blocks
 #define PVS_PAIR(t_)  (a.s_order ? (t_) / n_tb_s : (t_) % n_kp)

@@ -241,6 +241,26 @@ def c8_unpack(xb, c):
     return np.ascontiguousarray(xb.transpose(0, 1, 3, 2).reshape(n, cb * 8, hw)[:, :c]).astype(np.float32)
 
 
+def f16_fragments(w):
+    """pvhip_conv2d_f16_c8_pack / pvhip_conv2d_f16_span_pack restated: (k, c, ks, ks) fp32 weights -> the float16 MFMA fragment panel
+    [mt][cs][tap][i][lane][q] (csrc/pvhip_f16_c8.h).  Output channels come in groups of up to 128 (mt), a group in tm 32-channel tiles
+    (i), the same tm for every group; the input channels in stages of 16 (cs), c padded to whole stages.  Lane `lane` of fragment
+    (mt, cs, tap, i) holds, as q = 0 .. 7, output channel (mt * tm + i) * 32 + lane % 32 at input channels cs * 16 + 8 * (lane // 32) + q
+    of window tap `tap`; channels past k and past c are +0."""
+    w = np.asarray(w, dtype=np.float32)
+    k, c, kh, kw = w.shape
+    taps = kh * kw
+    nm = (k + 127) // 128
+    tm = -(-(-(-k // 32)) // nm)
+    ncs = (c + 15) // 16
+    full = np.zeros((nm * tm * 32, ncs * 16, taps), dtype=np.float16)
+    with np.errstate(over='ignore'):
+        full[:k, :c] = w.reshape(k, c, taps).astype(np.float16)
+    # [mt][i][lane % 32][cs][lane // 32][q][tap] -> [mt][cs][tap][i][lane // 32][lane % 32][q]
+    panel = full.reshape(nm, tm, 32, ncs, 2, 8, taps).transpose(0, 3, 6, 1, 4, 2, 5)
+    return np.ascontiguousarray(panel).reshape(nm, ncs, taps, tm, 64, 8)
+
+
 def softmax_rows(x):
     """Per leading-axis row, no max shift."""
     x = _f64(x)

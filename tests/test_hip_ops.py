@@ -1687,6 +1687,63 @@ def test_conv_f16_c8_module_form_blocked_in_blocked_out(hip):
         assert_bit_exact(np.asarray(got), want, 'MaxPool on a blocked tensor {} stride {} pads {} {} {}'.format(xs, st, pb, pe, rounding))
 
 
+def test_f16_fragment_panel_bits(hip):
+    """The 16-byte weight-fragment panel the span, c8 and c8-module kernels read (csrc/pvhip_f16_c8.h) is ref64.f16_fragments bit for bit:
+    pvhip_conv2d_f16_c8_pack -- and pvhip_conv2d_f16_span_pack where C is whole 16-channel stages -- into a block of 0xFF bytes, the
+    words behind the panel untouched, *_pack_elems the panel's size.  One group with a ragged second tile; two groups of tm = 3 with
+    panel rows 130 .. 191 empty; C padded to 32; 33 channels in two tiles."""
+    from pyopenvino_amd import device as dev
+    guard = 16
+    for k, c, ks in [(40, 16, 1), (130, 32, 3), (200, 24, 5), (33, 48, 3)]:
+        w = rnd(k + c, (k, c, ks, ks), 0.5)
+        want = ref64.f16_fragments(w)
+        nm, tm = (k + 127) // 128, -(-(-(-k // 32)) // ((k + 127) // 128))
+        assert want.shape == (nm, (c + 15) // 16, ks * ks, tm, 64, 8)
+        wd = dev.DeviceTensor.from_numpy(w)
+        for entry in ('c8', 'span') if c % 16 == 0 else ('c8',):
+            elems = int(dev.call('pvhip_conv2d_f16_{}_pack_elems'.format(entry), k, c, ks, ks))
+            assert elems * 2 == want.size, (entry, k, c, ks)
+            block = dev.DeviceTensor.from_numpy(np.full(elems + guard, 0xFFFFFFFF, dtype=np.uint32))
+            dev.call('pvhip_conv2d_f16_{}_pack'.format(entry), dev.ptr(wd), dev.ptr(block), k, c, ks, ks)
+            got = np.asarray(block)
+            assert np.all(got[elems:] == 0xFFFFFFFF), 'pvhip_conv2d_f16_{}_pack wrote past its panel'.format(entry)
+            assert np.array_equal(got[:elems].view(np.uint16), want.reshape(-1).view(np.uint16)), \
+                'pvhip_conv2d_f16_{}_pack: fragment panel of K {} C {} {}x{}'.format(entry, k, c, ks, ks)
+    assert dev.call('pvhip_conv2d_f16_span_pack_elems', 200, 24, 5, 5) == 0          # (the span entries take whole stages only)
+
+
+def test_f16_c8_row_tile_plan_corners(hip):
+    """pvhip_conv2d_f16_c8 and pvhip_conv2d_f16_c8_multi (one fp32 destination) on the same blocked input, each against the oracle on
+    fp16-rounded operands (1e-5, as test_conv_f16_c8_blocked_fp16_tensors_between_two_convolutions), where their row-tile plans differ or
+    sit on a boundary: tiles that c8's cap of ten LDS rows cuts and the module form's does not; rows of w + 2 pad = 64 pixels, the widest;
+    R * w = 65 and 64, the first plan of four pixel blocks and the last of two.  Rows of 65 stay unsupported."""
+    from pyopenvino_amd import device as dev
+    plugin = hip_plugin('Convolution')
+    k = 40
+    for xs, kk in [((2, 16, 20, 6), 3), ((2, 16, 20, 6), 5), ((1, 16, 9, 60), 5), ((1, 16, 3, 62), 3), ((2, 16, 5, 13), 3), ((2, 16, 4, 16), 3)]:
+        pad = (kk - 1) // 2
+        x, w = rnd(sum(xs), xs), rnd(k + kk, (k, xs[1], kk, kk), (2.0 / (xs[1] * kk * kk)) ** 0.5)
+        assert dev.call('pvhip_conv2d_f16_c8_supported', xs[1], xs[2], xs[3], kk, kk, 1, 1, pad, pad, xs[2], xs[3]), (xs, kk)
+        assert dev.call('pvhip_conv2d_f16_c8_multi_supported', xs[1], xs[2], xs[3], kk, kk, 0, 1), (xs, kk)
+        want = first_out(oracle_plugin('Convolution').compute(make_node('Convolution', [x, w], conv_data((1, 1), (pad, pad), (pad, pad))),
+                                                              {0: f16r(x), 1: f16r(w)}, kernel_type='special'))
+        xb = dev.BlockedHalf.from_dense(dev.DeviceTensor.from_numpy(x))
+        wd = dev.DeviceTensor.from_numpy(w)
+        node = {}
+        got = np.asarray(plugin.launch_c8(node, xb, wd))
+        assert node['_hip_f16'] == 'c8'
+        assert_close(got, want, 1e-5, 'pvhip_conv2d_f16_c8 {} {}x{}'.format(xs, kk, kk))
+        node = {}
+        (o,) = plugin.launch_c8_multi(node, xb, [(wd, None, None, False)])
+        assert 'c8 module' in node['_hip_f16'] and isinstance(o, dev.DeviceTensor)
+        assert_close(np.asarray(o), want, 1e-5, 'pvhip_conv2d_f16_c8_multi {} {}x{}'.format(xs, kk, kk))
+    for h, w_, kk in [(8, 63, 3), (8, 61, 5)]:                                       # w + 2 pad = 65
+        pad = (kk - 1) // 2
+        assert not dev.call('pvhip_conv2d_f16_c8_supported', 16, h, w_, kk, kk, 1, 1, pad, pad, h, w_), (w_, kk)
+        assert not dev.call('pvhip_conv2d_f16_c8_multi_supported', 16, h, w_, kk, kk, 0, 1), (w_, kk)
+    assert not dev.call('pvhip_conv2d_f16_c8_multi_supported', 16, 8, 63, 1, 1, 1, 1)       # (the pooled 1x1 copies a halo of one)
+
+
 def test_fp16_stem_on_blocked_tensors(hip):
     """FP16 IRs: (1) a convolution on the f16 form of the LDS-DMA kernel stores its output as fp16 blocked by eight channels
     (pvhip_conv2d_f16_dma_c8: node['_out_c8'] on a layer the 1x1 launch does not cover -- GoogLeNet's conv1, through the padding pass with
