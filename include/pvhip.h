@@ -238,6 +238,13 @@ int pvhip_maxpool_lrn_conv1x1_supported(int n, int c, int h, int w, int oh, int 
 int pvhip_maxpool_lrn_conv1x1_f32(const float* x, const float* w_oihw, float* y, int n, int c, int h, int w, int oh, int ow, int kh, int kw,
                                   int sh, int sw, int pad_top, int pad_left, int pad_bottom, int pad_right, int size, float alpha,
                                   float beta, float bias, int k_out, const float* conv_bias, int act, float act_lo, float act_hi);
+/* ... and the same without the pooling (an addition to ABI v19), for a tensor x (n, c, hw) that is pooled already -- the second output of
+ * pvhip_conv2d_stem_direct_pool_f32: LRN (LRN.py:10-22: five channels, beta = 0.75) then the 1x1 convolution with its bias / activation
+ * (Convolution.py:57-87).  A lane owns one pixel and walks the channels; no planes in LDS, no barrier in the loop.  c a multiple of eight and
+ * <= 64, k_out <= 64; y: (n, k_out, hw).  The bits of pvhip_lrn_f32 followed by the pointwise convolution.                                       */
+int pvhip_lrn_conv1x1_supported(int n, int c, int hw, int size, float beta, float bias, int k_out);
+int pvhip_lrn_conv1x1_f32(const float* x, const float* w_oihw, float* y, int n, int c, int hw, int size, float alpha, float beta, float bias,
+                          int k_out, const float* conv_bias, int act, float act_lo, float act_hi);
 
 /* ---------------------------------------------------------------- data movement ------------- */
 /* Concat.py:9-13 kernel_Concat_numpy: srcs[i] is viewed as [outer][inner[i]] and copied to
@@ -519,6 +526,15 @@ int    pvhip_conv2d_stem_f32(const float* xp, const float* wf, float* y, int n, 
 int    pvhip_conv2d_stem_direct_supported(int c, int h, int w, int k_out, int kh, int kw, int sh, int sw, int pad_top, int pad_left, int oh, int ow);
 int    pvhip_conv2d_stem_direct_f32(const float* x, const float* wf, float* y, int n, int h, int w, int k_out, int oh, int ow,
                                     const float* pre_add, const float* bias, int act, float act_lo, float act_hi);
+/* ... with a SECOND output (an addition to ABI v19): yp (n, k_out, poh, pow) = the 3x3 / stride 2 / unpadded / ceil-rounded MaxPool of y (MaxPool.py:41-72:
+ * the window clipped at the extent, a NaN is the maximum; GoogLeNet's pool1/3x3_s2), taken where conv1's values already are.  y keeps the bits of
+ * pvhip_conv2d_stem_direct_f32 (Convolution.py:57-87), yp has the bits of pvhip_maxpool2d_f32 on y, whatever the grid.  _supported (1 / 0): the layer
+ * is the direct form's, oh >= 3, poh = (oh - 2) / 2 + 1, pow = ow / 2, and -- the size rule, for n > 0 -- every CU walks at least eight tiles of four
+ * output rows (n = 0 asks for the shape alone; the entry takes every n of a supported shape).                                                     */
+int    pvhip_conv2d_stem_direct_pool_supported(int n, int c, int h, int w, int k_out, int kh, int kw, int sh, int sw, int pad_top, int pad_left,
+                                               int oh, int ow, int poh, int pow);
+int    pvhip_conv2d_stem_direct_pool_f32(const float* x, const float* wf, float* y, float* yp, int n, int h, int w, int k_out, int oh, int ow,
+                                         int poh, int pow, const float* pre_add, const float* bias, int act, float act_lo, float act_hi);
 /* The same first convolution as WINOGRAD F(3x3, 4x4) on the space-to-depth image (ABI v16; Convolution.py:57-87 for a 7x7 / stride 2 / pad 3 layer
  * over three channels): x'(c; py, px; i, j) = xpad(c, 2 i + py, 2 j + px) turns it into a 4x4 / stride 1 convolution over 12 channels, which
  * 6x6-point tiles (the interpolation points of the F(4x4,3x3) / F(2x2,5x5) kernels) compute with 0.34 of the multiplies.  x: the UNPADDED

@@ -679,6 +679,117 @@ __global__ __launch_bounds__(kBlock) void maxpool3x3_lrn_conv1x1_kernel(PoolLrnC
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// LRN -> 1x1 convolution (+ bias, activation) in ONE pass, for a tensor that is pooled already (the stem convolution's second output): the walk of
+// lrn_window_kernel -- a lane owns ONE pixel and walks the channel axis in chunks of kLrnT, the loads of chunk k + 1 in flight while chunk k is
+// used, the five-channel window in registers (ChannelWindow, lrn_value: the bits of pvhip_lrn_f32) -- with the sink of maxpool3x3_lrn_conv1x1_kernel:
+// the normalised value of channel c is the lane's column of the k = 1 outer product with W[.][c], channel after channel in ascending order (the
+// bits of the pointwise convolution).  No planes in LDS and no barrier in the loop; LDS holds the transposed weights only, at a pitch of
+// 32 KT + 1 floats so that the transposing writes of a wave (consecutive c) fall into different banks.
+struct LrnConvArgs {
+    const float* x;           // (n, c, hw)
+    const float* cw;          // (k_out, c, 1, 1)
+    const float* cbias;       // k_out, or null
+    float*       y;           // (n, k_out, hw)
+    int   n, c, hw, k_out, act;
+    float alpha, beta, bias, act_lo, act_hi;
+};
+
+template <int BETA_MODE, int KT>
+__global__ __launch_bounds__(kBlock, 4) void lrn_conv1x1_kernel(LrnConvArgs a, FastDiv d_hw, FastDiv d_c) {
+    constexpr int SIZE = 5, HALF = SIZE / 2, T = kLrnT, WP = 32 * KT + 1;
+    extern __shared__ __attribute__((aligned(16))) float wl[];      // [c][WP]: wl[c][k] = W[k][c], zeros past k_out
+    const int tid = threadIdx.x, lane = tid & (kWave - 1);
+    const unsigned total = (unsigned)a.n * (unsigned)a.hw;
+    const unsigned t = blockIdx.x * kBlock + tid;
+    const bool     live = t < total;
+    const unsigned tc = live ? t : total - 1;                       // a dead lane walks along on the last pixel (every lane of the wave takes part in the MFMAs)
+    const unsigned img = fdiv(tc, d_hw), px = tc - img * (unsigned)a.hw;
+    const float* __restrict__ xv = a.x + (size_t)img * a.c * a.hw + px;
+    const size_t cstride = (size_t)a.hw;
+    const int    n_chunks = a.c / T;
+    float cur[T], nxt[T];
+#pragma unroll
+    for (int j = 0; j < T; ++j) cur[j] = ldnt(xv + (size_t)j * cstride);          // the first chunk is on its way while the weights are staged
+    // the transposed weights (e = k * c + ci: the global reads of a wave are consecutive), all loads of a lane in flight together
+    {
+        constexpr int NW = 64 * 32 * KT / kBlock;
+        float wv[NW];
+        const int we = a.k_out * a.c;
+#pragma unroll
+        for (int j = 0; j < NW; ++j) wv[j] = tid + j * kBlock < we ? a.cw[tid + j * kBlock] : 0.0f;
+#pragma unroll
+        for (int j = 0; j < NW; ++j) {
+            const int e = tid + j * kBlock;
+            const int k = (int)fdiv((unsigned)e, d_c), ci = e - k * a.c;
+            if (e < a.c * 32 * KT) wl[ci * WP + k] = wv[j];
+        }
+    }
+    __syncthreads();
+
+    const float* const wl_lane = wl + (lane & 31);
+    floatx32 acc[KT];
+#pragma unroll
+    for (int kt = 0; kt < KT; ++kt)
+#pragma unroll
+        for (int r = 0; r < 32; ++r) acc[kt][r] = 0.0f;
+    ChannelWindow<SIZE> win;
+    win.clear();
+    // channel ch enters the window, which is then centred on channel ch - HALF: its normalised value meets the weights of that channel
+    auto push = [&](float v, int ch) {
+        win.push(v);
+        if (ch >= HALF) {
+            const float o = live ? lrn_value<SIZE, BETA_MODE>(win.v, win.v[HALF], a.alpha, a.beta, a.bias) : 0.0f;
+            const float* const wc = wl_lane + (ch - HALF) * WP;
+#pragma unroll
+            for (int kt = 0; kt < KT; ++kt) acc[kt] = __builtin_amdgcn_mfma_f32_32x32x1f32(wc[32 * kt], o, acc[kt], 0, 0, 0);
+        }
+    };
+    for (int k = 0; k < n_chunks; ++k) {
+        if (k + 1 < n_chunks) {
+            const float* __restrict__ xn = xv + (size_t)(k + 1) * T * cstride;
+#pragma unroll
+            for (int j = 0; j < T; ++j) nxt[j] = ldnt(xn + (size_t)j * cstride);
+        }
+#pragma unroll
+        for (int j = 0; j < T; ++j) push(cur[j], k * T + j);
+#pragma unroll
+        for (int j = 0; j < T; ++j) cur[j] = nxt[j];
+    }
+#pragma unroll
+    for (int j = 0; j < HALF; ++j) push(0.0f, a.c + j);             // the trailing channels: their windows run past the tensor (zeros)
+
+    // ---- epilogue (maxpool3x3_lrn_conv1x1_kernel's): acc[kt][16 b + v] at lane (j = lane & 31, h = lane >> 5) = output channel 32 kt + 8 (v / 4) + 4 h + v % 4
+    // of the pixel of lane 32 b + j
+    const int h2 = lane >> 5;
+    const ActBounds ab = act_bounds(a.act, a.act_lo, a.act_hi);
+#pragma unroll
+    for (int bl = 0; bl < 2; ++bl) {
+        const unsigned tb = blockIdx.x * kBlock + (tid & ~(kWave - 1)) + 32 * bl + (lane & 31);      // the pixel of lane 32 b + j of this wave
+        const bool     ok = tb < total;
+        const unsigned ib = fdiv(ok ? tb : 0u, d_hw), pb = (ok ? tb : 0u) - ib * (unsigned)a.hw;
+        float* const   yimg = a.y + (size_t)ib * a.k_out * a.hw + pb;
+#pragma unroll
+        for (int kt = 0; kt < KT; ++kt) {
+            float bv[16], vv[16];
+#pragma unroll
+            for (int v = 0; v < 16; ++v) {
+                const int kk = 32 * kt + 8 * (v >> 2) + 4 * h2 + (v & 3);
+                bv[v] = (a.cbias != nullptr && kk < a.k_out) ? a.cbias[kk] : 0.0f;
+                vv[v] = acc[kt][16 * bl + v];
+            }
+            bias_act_n<16>(vv, bv, a.cbias != nullptr, a.act, ab);
+            if (ok) {
+#pragma unroll
+                for (int v = 0; v < 16; ++v) {
+                    const int kk = 32 * kt + 8 * (v >> 2) + 4 * h2 + (v & 3);
+                    if (kk < a.k_out) yimg[(size_t)kk * a.hw] = vv[v];
+                }
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // LRN + MaxPool 3x3 / stride 2 / no padding, WITHOUT A BARRIER (round 4; GoogLeNet's conv2/norm2 -> pool2/3x3_s2).  The workgroup form
 // above spends a third of its time in its pooling phase and 0.076 of its 0.184 ms in the loop and its two barriers per eight channels
 // (scripts/time_lrnpool_abl.py); its loads alone take 0.112 ms.  Here a WAVE is the unit: it owns four pooled rows of one image and a
@@ -1156,6 +1267,39 @@ int pvhip_maxpool_lrn_conv1x1_f32(const float* x, const float* w_oihw, float* y,
         else           { if (kt == 1) PV_PLC(1, 2, 1); else PV_PLC(1, 2, 2); }
     }
 #undef PV_PLC
+    PVHIP_LAUNCH_CHECK();
+    return PVHIP_OK;
+}
+
+// LRN (five channels, beta = 0.75; LRN.py:10-22) then a 1x1 / stride 1 / unpadded convolution (+ bias, activation; Convolution.py:57-87) as ONE launch
+// on a tensor (n, c, hw) that is pooled already: whole chunks of eight and at most 64 channels in, at most 64 out.  The bits of pvhip_lrn_f32 followed
+// by the pointwise convolution -- and so of pvhip_maxpool_lrn_conv1x1_f32 on the unpooled tensor.
+int pvhip_lrn_conv1x1_supported(int n, int c, int hw, int size, float beta, float bias, int k_out) {
+    if (n <= 0 || c < 8 || c % 8 != 0 || c > 64 || hw <= 0 || size != 5 || k_out <= 0 || k_out > 64) return 0;
+    const int bm = lrn_beta_mode(beta, bias);
+    if (bm != 4 && bm != 1) return 0;
+    if ((unsigned long long)n * c * hw >= (1ull << 31) || (unsigned long long)n * k_out * hw >= (1ull << 31)) return 0;
+    return 1;
+}
+
+int pvhip_lrn_conv1x1_f32(const float* x, const float* w_oihw, float* y, int n, int c, int hw, int size, float alpha, float beta, float bias, int k_out,
+                          const float* conv_bias, int act, float act_lo, float act_hi) {
+    PVHIP_REQUIRE_INIT();
+    if (!pvhip_lrn_conv1x1_supported(n, c, hw, size, beta, bias, k_out))
+        return fail(PVHIP_EUNSUPPORTED, "pvhip_lrn_conv1x1_f32: shape outside the fused kernel (ask pvhip_lrn_conv1x1_supported first)");
+    PVHIP_CHECK_ARG(x != nullptr && w_oihw != nullptr && y != nullptr && act >= 0 && act <= 2);
+    LrnConvArgs a{};
+    a.x = x; a.cw = w_oihw; a.cbias = conv_bias; a.y = y;
+    a.n = n; a.c = c; a.hw = hw; a.k_out = k_out; a.act = act;
+    a.alpha = alpha; a.beta = beta; a.bias = bias; a.act_lo = act_lo; a.act_hi = act_hi;
+    const int    kt = (k_out + 31) / 32;
+    const dim3   grid((unsigned)(((unsigned long long)n * hw + kBlock - 1) / kBlock));
+    const size_t lds = (size_t)c * (32 * kt + 1) * sizeof(float);
+    const FastDiv d_hw = make_fastdiv((unsigned)hw), d_c = make_fastdiv((unsigned)c);
+#define PV_LC(BM_, KT_) hipLaunchKernelGGL((lrn_conv1x1_kernel<BM_, KT_>), grid, dim3(kBlock), lds, state().stream, a, d_hw, d_c)
+    if (lrn_beta_mode(beta, bias) == 4) { if (kt == 1) PV_LC(4, 1); else PV_LC(4, 2); }
+    else                                { if (kt == 1) PV_LC(1, 1); else PV_LC(1, 2); }
+#undef PV_LC
     PVHIP_LAUNCH_CHECK();
     return PVHIP_OK;
 }

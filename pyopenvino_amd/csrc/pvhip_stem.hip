@@ -21,6 +21,8 @@
 //   * epilogue: a lane holds four consecutive pixels of one channel per accumulator tile: bias, activation -- and (the form that reads the image itself) the
 //     16 channels x 112 pixels of a tile pass through the wave's own 7 KB of LDS and leave as whole 448-byte rows, two channels per store instruction
 //     (0.584 -> 0.556 ms on one box: 16 x 64-byte pieces per instruction cost the address unit more than the same bytes as two rows).
+#include <type_traits>
+
 #include "pvhip_common.h"
 
 using namespace pvhip;
@@ -29,6 +31,7 @@ namespace {
 
 typedef float    floatx4 __attribute__((ext_vector_type(4)));
 typedef unsigned uintx4 __attribute__((ext_vector_type(4)));
+typedef float    floatx2 __attribute__((ext_vector_type(2)));
 
 constexpr int kC = 3, kKH = 7, kKW = 7, kST = 2, kPad = 3;
 constexpr int kTR    = 4;                            // output rows per tile: one per pair of waves
@@ -46,6 +49,14 @@ constexpr int kTsPitch = 116;                        // floats per channel row o
 constexpr int kTsWave  = 16 * kTsPitch;              // one accumulator tile: 16 channels
 constexpr int kTsBase  = 2 * kCopies * kLdsRow + 16; // floats: behind the two tile buffers, the spilled piece and the Add's constants
 constexpr int kTsBytes = kWaves * kTsWave * 4;       // 59392
+// the form with a pooled second output (MaxPool 3x3 / stride 2 / no padding / ceil of y): a wave also leaves its row pooled along x in LDS -- the second
+// sixteen of its 32 channels over the transposed tile in its region, once that has been read (row cl & 15, floats 0 .. 55), the first sixteen in the
+// tile buffer the reduction has just finished with ([wave][16][56] from float 4 on: the copies of the tile after next rewrite all of it but the first
+// four floats, which stay zero) -- and behind the regions lies the carry of the row pair a tile leaves to the next one: 64 channels x 56 floats
+constexpr int kHpCols   = 8 * kNG;                   // 56: pooled columns of a row of 112 pixels
+constexpr int kCarryBase = kTsBase + kWaves * kTsWave;
+constexpr int kPoolMinTiles = 8;                     // the size rule of the pooled form: tiles per workgroup from which it is the plan's choice (profiles/stem_pool.md)
+constexpr int kPoolLdsBytes = (kCarryBase + 64 * kHpCols) * 4;     // 153664: under the 160 KB of a CU
 
 struct StemArgs {
     const float* xp;       // zero-padded input [N][3][HP][WP], WP % 4 == 0
@@ -59,6 +70,9 @@ struct StemArgs {
     int act;
     float act_lo, act_hi;
     int tstores;           // 1: the epilogue's stores as whole rows through LDS (DIRECT form)
+    float*   yp;           // POOL: [N][K][POH][POW], MaxPool 3x3 / 2 / ceil of y
+    int      POH, POW;
+    unsigned yp_bytes;
 };
 
 __device__ __forceinline__ float lds_read_f32(unsigned addr) {
@@ -72,8 +86,16 @@ __device__ __forceinline__ float lds_read_f32(unsigned addr) {
 // above, whose piece lies past the image: out of range, zeros), lanes past the image write the right padding's zeros, rows above / below
 // the image are out-of-range copies: zeros.  The per-channel constant of an Add in front of the layer (data/mean) is added IN LDS, by the wave
 // that copied the row, to the image's own positions only -- ten packed adds per wave and tile, outside the reduction loop.
-template <int ABL, bool DIRECT>
+// POOL (DIRECT only): the second output yp = MaxPool 3x3 / stride 2 / no padding / ceil rounding of y (MaxPool.py:41-72: the window clipped at
+// the extent, a NaN is the maximum).  The lane that reads pixels 4 q .. 4 q + 3 of a channel for the whole-row store reads pixel 4 q + 4 too and
+// has two pooled columns; the rows pooled along x wait in LDS (where: the constants above; a barrier in front of the epilogue frees the tile
+// buffer.  Held in registers they were spilled, and a reload's vmcnt(0) waits for the y stores in front of it: 0.82 ms against 0.55).  One more
+// barrier, then the workgroup takes the maxima down the rows: pooled row 2 t from rows 4 t .. 4 t + 2; max(row 4 t + 2, row 4 t + 3) is the
+// carry (each cell read and written by the same lane) and becomes pooled row 2 t + 1 one tile later.  A range that ends inside an image walks
+// one tile further for that row alone; one that begins inside an image leaves it to the workgroup in front: yp does not depend on the grid.
+template <int ABL, bool DIRECT, bool POOL = false>
 __global__ __launch_bounds__(kThreads, 1) void conv_stem_f32_kernel(StemArgs a) {
+    static_assert(!POOL || (DIRECT && ABL == 0 && kTransposeStores), "the pooled output rides on the whole-row stores of the DIRECT form");
     extern __shared__ __attribute__((aligned(1024))) float stem_lds[];          // [2][39][256] (+ 4 floats: the last row's lane 63 in the DIRECT form)
     const int tid  = threadIdx.x;
     const int lane = tid & (kWave - 1);
@@ -87,6 +109,9 @@ __global__ __launch_bounds__(kThreads, 1) void conv_stem_f32_kernel(StemArgs a) 
     int       tile = b_ * per + min(b_, extra);
     const int tile_end = tile + per + (b_ < extra ? 1 : 0);
     if (tile >= tile_end) return;
+    // POOL: a range that ends inside an image walks one tile further (for the first row of that tile only), one that begins inside an image has no carry
+    const int  tile_stop = tile_end + ((POOL && tile_end % a.tiles_per_image != 0) ? 1 : 0);
+    bool       have_carry = false;
 
     const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.xp), 0, a.x_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t yr = __builtin_amdgcn_make_buffer_rsrc(a.y, 0, a.y_bytes, 0x00020000);
@@ -182,7 +207,7 @@ __global__ __launch_bounds__(kThreads, 1) void conv_stem_f32_kernel(StemArgs a) 
     __syncthreads();
     int buf = 0;
     for (;;) {
-        if (ABL != 3 && tile + 1 < tile_end) issue(tile + 1, buf ^ 1);
+        if (ABL != 3 && tile + 1 < tile_stop) issue(tile + 1, buf ^ 1);
         floatx4 acc[kNG][2];
 #pragma unroll
         for (int g = 0; g < kNG; ++g) {
@@ -201,7 +226,7 @@ __global__ __launch_bounds__(kThreads, 1) void conv_stem_f32_kernel(StemArgs a) 
                 for (int g = 0; g < kNG; ++g) p[(m + 1) & 1][g] = lds_read_f32(toff[m + 1] + (unsigned)(g * 16 * kST * 4));
             }
             __builtin_amdgcn_sched_barrier(0);
-            if (DIRECT && m == kSteps / 2 && ABL != 3 && tile + 1 < tile_end) {
+            if (DIRECT && m == kSteps / 2 && ABL != 3 && tile + 1 < tile_stop) {
                 // half a tile after they were issued this wave's copies of the NEXT tile have landed: the Add in front of the layer on those rows
                 // here, between two steps -- ten packed adds and an LDS round trip that the other waves' MFMAs cover -- not in the epilogue
                 lds_dma_wait_all();
@@ -221,6 +246,7 @@ __global__ __launch_bounds__(kThreads, 1) void conv_stem_f32_kernel(StemArgs a) 
         }
         // this wave's copies for the NEXT tile were issued a whole tile ago: no wait to speak of, and the barrier below then publishes all of them
         lds_dma_wait_all();
+        if (POOL) __syncthreads();          // every wave has finished with this tile's buffer: the epilogue stages pooled rows in it
         // ---- epilogue: register r of acc[g][t] = pixel 16 g + 4 kq + r of channel 32 hf + 16 t + l15 of output row oy0 + wr
         if (ABL == 1) {
             floatx4 sum = acc[0][0];
@@ -232,7 +258,7 @@ __global__ __launch_bounds__(kThreads, 1) void conv_stem_f32_kernel(StemArgs a) 
             const int oy  = (tile - img * a.tiles_per_image) * kTR + wr;
             const unsigned plane = (unsigned)(a.OH * a.OW * 4);
             const unsigned rowb  = (unsigned)(((img * a.K + ch0) * a.OH + oy) * a.OW * 4 + 16 * kq);
-            const bool rowok = oy < a.OH;
+            const bool rowok = oy < a.OH && !(POOL && tile >= tile_end);         // (POOL: the tile past the range is computed for the pooled row it completes)
             // bias and activation behind THREE wave-uniform branches for all 56 values (launch constants; per value it would be a branch each)
             if (a.bias != nullptr) {
 #pragma unroll
@@ -244,23 +270,39 @@ __global__ __launch_bounds__(kThreads, 1) void conv_stem_f32_kernel(StemArgs a) 
             }
             // (each activation stores by itself: merging three register assignments of the 56 sums behind the branches cost ~200 copies and spills)
             auto store_all = [&]() {
-                if (kTransposeStores && a.tstores != 0) {
+                if (kTransposeStores && (POOL || a.tstores != 0)) {
                     // Whole rows instead of 16 x 64 bytes per instruction (round 5): the 16 channels x 112 pixels of an accumulator tile pass through THIS
                     // wave's 7 KB of LDS (row pitch 116 floats; no barrier: LDS executes a wave's instructions in order) and leave as 448-byte rows,
                     // two channels per store instruction (lanes 0-27 / 28-55).  The address pattern is what the stores cost (LESSONS 55, 59).
                     float* const tl = stem_lds + kTsBase + wid * kTsWave;
                     const int c2 = lane / 28, q = lane - 28 * c2;               // reader: channel c2 of a pair (lanes 56-63: none), pixel quad q
+                    float* const hp0 = stem_lds + buf * (kCopies * kLdsRow) + 4 + wid * (16 * kHpCols);      // POOL: the first sixteen channels' pooled row
+                    int qe = q;                                                 // the fifth pixel of the second window, clipped at the extent (made here, tile by tile:
+                    if (POOL) asm volatile("" : "+v"(qe));                      // hoisted out of the tile loop it would be one more register across the reduction)
+                    qe = 4 * qe + 4 < a.OW ? 4 * qe + 4 : 4 * qe + 3;
 #pragma unroll
                     for (int t = 0; t < 2; ++t) {
 #pragma unroll
                         for (int g = 0; g < kNG; ++g) *reinterpret_cast<floatx4*>(tl + l15 * kTsPitch + 16 * g + 4 * kq) = acc[g][t];
+                        floatx2 hp[8];
 #pragma unroll
                         for (int p = 0; p < 8; ++p) {
                             const int ch = 32 * hf + 16 * t + 2 * p + c2;
                             const floatx4 v = *reinterpret_cast<const floatx4*>(tl + (2 * p + (c2 & 1)) * kTsPitch + 4 * q);
+                            if (POOL) {      // pooled columns 2 q, 2 q + 1 of the channel this lane has just read
+                                const float e = tl[(2 * p + (c2 & 1)) * kTsPitch + qe];
+                                hp[p] = floatx2{max3_nan(v[0], v[1], v[2]), max3_nan(v[2], v[3], e)};
+                            }
                             const bool ok = rowok && c2 < 2 && ch < a.K && 4 * q < a.OW;
                             const unsigned vo = ok ? (unsigned)(((img * a.K + ch) * a.OH + oy) * a.OW * 4 + 16 * q) : kOob;
                             __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(uintx4, v), yr, vo, 0, 0);
+                        }
+                        if (POOL && c2 < 2) {
+                            // the row pooled along x, once every read of the tile is out (all of them in flight together; LDS runs a wave's instructions in
+                            // order): t = 1 over the transposed tile itself
+#pragma unroll
+                            for (int p = 0; p < 8; ++p)
+                                *reinterpret_cast<floatx2*>((t == 0 ? hp0 + (2 * p + c2) * kHpCols : tl + (2 * p + c2) * kTsPitch) + 2 * q) = hp[p];
                         }
                     }
                     return;
@@ -301,7 +343,61 @@ __global__ __launch_bounds__(kThreads, 1) void conv_stem_f32_kernel(StemArgs a) 
                 store_all();
             }
         }
-        if (++tile >= tile_end) break;
+        if constexpr (POOL) {
+            __syncthreads();                  // every wave's pooled row is in LDS
+            const int  img = tile / a.tiles_per_image, tt = tile - img * a.tiles_per_image;
+            const bool past = tile >= tile_end;                                  // the tile past the range: only the row it completes
+            const bool last = tt == a.tiles_per_image - 1;
+            const bool rv1 = 4 * tt + 1 < a.OH, rv2 = 4 * tt + 2 < a.OH, rv3 = 4 * tt + 3 < a.OH;
+            const bool do_a = !past && 2 * tt < a.POH;                           // pooled row 2 tt: rows 4 tt .. 4 tt + 2 (clipped)
+            const bool do_b = have_carry && tt > 0;                              // pooled row 2 tt - 1: the carry and row 4 tt
+            const bool do_c = !past && last && 2 * tt + 1 < a.POH;               // pooled row 2 tt + 1 of the image's last tile: rows 4 tt + 2, 4 tt + 3
+            const bool keep = !past && !last;                                    // ... of any other tile: one tile later
+            const __amdgpu_buffer_rsrc_t ypr = __builtin_amdgcn_make_buffer_rsrc(a.yp, 0, a.yp_bytes, 0x00020000);
+            auto down = [&](auto vtag) {
+                constexpr int V = decltype(vtag)::value;                         // floats per lane: 4 where a pooled row is whole 16-byte pieces, else 2
+                typedef float    fv __attribute__((ext_vector_type(V)));
+                typedef unsigned uv __attribute__((ext_vector_type(V)));
+                constexpr int per_row = kHpCols / V;
+                int tid_ = tid;                                                  // (opaque: what follows from it is made here, not kept across the reduction)
+                asm volatile("" : "+v"(tid_));
+                for (int e = tid_; e < 64 * per_row; e += kThreads) {
+                    const int ch = e / per_row, x0 = (e - ch * per_row) * V;
+                    // row i of the tile is wave 2 i + (ch >> 5)'s: in its region, or in its part of the tile buffer
+                    const float* const r0p = ((ch & 16) ? stem_lds + kTsBase + (ch >> 5) * kTsWave + (ch & 15) * kTsPitch
+                                                        : stem_lds + buf * (kCopies * kLdsRow) + 4 + ((ch >> 5) * 16 + (ch & 15)) * kHpCols) + x0;
+                    const int rstep = (ch & 16) ? 2 * kTsWave : 2 * 16 * kHpCols;
+                    fv* const cp = reinterpret_cast<fv*>(stem_lds + kCarryBase + ch * kHpCols + x0);
+                    const fv r0 = *reinterpret_cast<const fv*>(r0p);
+                    const fv r1 = *reinterpret_cast<const fv*>(r0p + rstep);
+                    const fv r2 = *reinterpret_cast<const fv*>(r0p + 2 * rstep);
+                    const fv r3 = *reinterpret_cast<const fv*>(r0p + 3 * rstep);
+                    const bool ok = ch < a.K && x0 < a.POW;
+                    const unsigned at = ok ? (unsigned)((((img * a.K + ch) * a.POH + 2 * tt) * a.POW + x0) * 4) : kOob;
+                    const unsigned rowb = (unsigned)(a.POW * 4);
+                    if (do_b) {
+                        const fv m = __builtin_elementwise_maximum(*cp, r0);
+                        if constexpr (V == 4) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(uv, m), ypr, ok ? at - rowb : kOob, 0, 0);
+                        else                  __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(uv, m), ypr, ok ? at - rowb : kOob, 0, 0);
+                    }
+                    if (do_a) {
+                        const fv m = __builtin_elementwise_maximum(__builtin_elementwise_maximum(r0, rv1 ? r1 : r0), rv2 ? r2 : r0);
+                        if constexpr (V == 4) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(uv, m), ypr, at, 0, 0);
+                        else                  __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(uv, m), ypr, at, 0, 0);
+                    }
+                    if (do_c || keep) {
+                        const fv m = __builtin_elementwise_maximum(r2, rv3 ? r3 : r2);
+                        if (keep) *cp = m;
+                        else if constexpr (V == 4) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(uv, m), ypr, ok ? at + rowb : kOob, 0, 0);
+                        else                       __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(uv, m), ypr, ok ? at + rowb : kOob, 0, 0);
+                    }
+                }
+            };
+            if (a.POW % 4 == 0) down(std::integral_constant<int, 4>{});
+            else                down(std::integral_constant<int, 2>{});
+            have_carry = keep;
+        }
+        if (++tile >= tile_stop) break;
         // the other buffer: 37 additions per tile (a whole tile of MFMAs between them)
         const unsigned delta = buf ? (unsigned)(-kBufBytes) : (unsigned)kBufBytes;
 #pragma unroll
@@ -389,7 +485,6 @@ struct StemWinoArgs {
     float act_lo, act_hi;
 };
 
-typedef float floatx2 __attribute__((ext_vector_type(2)));
 typedef float floatx3 __attribute__((ext_vector_type(3)));
 typedef unsigned uintx3 __attribute__((ext_vector_type(3)));
 
@@ -756,6 +851,55 @@ int pvhip_conv2d_stem_direct_f32(const float* x, const float* wf, float* y, int 
     a.x_bytes = (unsigned)in_b; a.y_bytes = (unsigned)out_b;
     a.act = act; a.act_lo = act_lo; a.act_hi = act_hi;
     return stem_launch<true>(a, tiles);
+}
+
+/* The same launch with a SECOND output: yp (n, k_out, poh, pow) = MaxPool 3x3 / stride 2 / no padding / ceil rounding of y (MaxPool.py:41-72: the window
+ * clipped at the extent, a NaN is the maximum), after bias and activation -- the bits of pvhip_maxpool2d_f32 on y; y itself has the bits of
+ * pvhip_conv2d_stem_direct_f32 (Convolution.py:57-87).  _supported: the layer is the direct form's, the pooled extents are that pooling's, and -- the size
+ * rule, when n > 0 is given -- every workgroup walks at least kPoolMinTiles tiles, so that the extra tile of a range that ends inside an image is a small
+ * part of its work (n = 0: the shape alone). */
+int pvhip_conv2d_stem_direct_pool_supported(int n, int c, int h, int w, int k_out, int kh, int kw, int sh, int sw, int pad_top, int pad_left, int oh, int ow,
+                                            int poh, int pow) {
+    if (!pvhip_conv2d_stem_direct_supported(c, h, w, k_out, kh, kw, sh, sw, pad_top, pad_left, oh, ow)) return 0;
+    if (oh < 3 || ow < 4 || poh != (oh - 3 + 1) / 2 + 1 || pow != ow / 2) return 0;
+    if (n < 0) return 0;
+    if (n > 0) {
+        const long tiles = (long)n * ((oh + kTR - 1) / kTR);
+        if (tiles < (long)kPoolMinTiles * kNumCU) return 0;
+    }
+    return 1;
+}
+
+int pvhip_conv2d_stem_direct_pool_f32(const float* x, const float* wf, float* y, float* yp, int n, int h, int w, int k_out, int oh, int ow, int poh, int pow,
+                                      const float* pre_add, const float* bias, int act, float act_lo, float act_hi) {
+    PVHIP_REQUIRE_INIT();
+    PVHIP_CHECK_ARG(n >= 0 && k_out > 0 && k_out <= 64 && h > 0 && w > 0 && oh > 0 && ow > 0 && act >= 0 && act <= 2);
+    if (!pvhip_conv2d_stem_direct_pool_supported(0, kC, h, w, k_out, kKH, kKW, kST, kST, kPad, kPad, oh, ow, poh, pow))
+        return fail(PVHIP_EUNSUPPORTED, "pvhip_conv2d_stem_direct_pool_f32: shape outside the kernel (ask pvhip_conv2d_stem_direct_pool_supported first)");
+    const unsigned long long in_b = (unsigned long long)n * kC * h * w * 4ull, out_b = (unsigned long long)n * k_out * oh * ow * 4ull;
+    if (in_b >= (1ull << 31) || out_b >= (1ull << 31)) return fail(PVHIP_EUNSUPPORTED, "pvhip_conv2d_stem_direct_pool_f32: tensor too large");
+    if (n == 0) return PVHIP_OK;
+    PVHIP_CHECK_ARG(x != nullptr && wf != nullptr && y != nullptr && yp != nullptr);
+    StemArgs a;
+    a.xp = x; a.wf = wf; a.y = y; a.bias = bias; a.pre_add = pre_add;
+    a.N = n; a.HP = h; a.WP = w; a.OH = oh; a.OW = ow; a.K = k_out;
+    a.tiles_per_image = (oh + kTR - 1) / kTR;
+    const long tiles = (long)n * a.tiles_per_image;
+    if (tiles > 0x3fffffffL) return fail(PVHIP_EUNSUPPORTED, "pvhip_conv2d_stem_direct_pool_f32: too many tiles");
+    a.tiles = (int)tiles;
+    a.x_bytes = (unsigned)in_b; a.y_bytes = (unsigned)out_b;
+    a.act = act; a.act_lo = act_lo; a.act_hi = act_hi;
+    a.tstores = 1;
+    a.yp = yp; a.POH = poh; a.POW = pow; a.yp_bytes = (unsigned)((unsigned long long)n * k_out * poh * pow * 4ull);
+    const int grid = (int)(tiles < kNumCU ? tiles : kNumCU);
+    static bool attr_set = false;
+    if (!attr_set) {
+        PVHIP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_stem_f32_kernel<0, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kPoolLdsBytes));
+        attr_set = true;
+    }
+    hipLaunchKernelGGL((conv_stem_f32_kernel<0, true, true>), dim3((unsigned)grid), dim3(kThreads), (size_t)kPoolLdsBytes, state().stream, a);
+    PVHIP_LAUNCH_CHECK();
+    return PVHIP_OK;
 }
 
 /* conv1 as Winograd F(3x3, 4x4) on the space-to-depth image (ABI v16; conv_stem_wino_kernel above): 7x7 / stride 2 / pad 3 over 3 channels of an

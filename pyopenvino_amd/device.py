@@ -143,6 +143,10 @@ SIGNATURES = {
     'pvhip_conv2d_stem_wino_pack': (_c.c_int, [_fp, _fp, _c.c_int]),
     'pvhip_conv2d_stem_wino_f32': (_c.c_int, [_fp, _fp, _fp] + [_c.c_int] * 6 + [_fp, _fp, _c.c_int, _c.c_float, _c.c_float]),
     'pvhip_conv2d_stem_direct_f32': (_c.c_int, [_fp, _fp, _fp] + [_c.c_int] * 6 + [_fp, _fp, _c.c_int, _c.c_float, _c.c_float]),
+    'pvhip_conv2d_stem_direct_pool_supported': (_c.c_int, [_c.c_int] * 15),
+    'pvhip_conv2d_stem_direct_pool_f32': (_c.c_int, [_fp, _fp, _fp, _fp] + [_c.c_int] * 8 + [_fp, _fp, _c.c_int, _c.c_float, _c.c_float]),
+    'pvhip_lrn_conv1x1_supported': (_c.c_int, [_c.c_int] * 4 + [_c.c_float] * 2 + [_c.c_int]),
+    'pvhip_lrn_conv1x1_f32': (_c.c_int, [_fp, _fp, _fp] + [_c.c_int] * 4 + [_c.c_float] * 3 + [_c.c_int, _fp, _c.c_int, _c.c_float, _c.c_float]),
     'pvhip_conv2d_pooled_supported': (_c.c_int, [_c.c_int] * 5),
     'pvhip_conv2d_pooled_f32': (_c.c_int, [_fp, _fp, _fp] + [_c.c_int] * 5 + [_fp, _c.c_int, _c.c_int, _c.c_int, _c.c_float, _c.c_float]),
     'pvhip_conv2d_pooled_f16': (_c.c_int, [_fp, _fp, _fp] + [_c.c_int] * 5 + [_fp, _c.c_int, _c.c_int, _c.c_int, _c.c_float, _c.c_float]),
@@ -199,7 +203,7 @@ SIGNATURES = {
 }
 
 # entry points whose return value is not a status code
-_NOT_STATUS = {'pvhip_host_alloc', 'pvhip_conv2d_stem_wino_supported', 'pvhip_conv2d_stem_wino_pack_elems', 'pvhip_maxpool3x3_lrn_conv1x1_c8_supported', 'pvhip_conv2d_f16_stem_direct_supported', 'pvhip_maxpool_lrn_conv1x1_supported', 'pvhip_conv2d_stem_direct_supported', 'pvhip_conv2d_stem_f32_supported', 'pvhip_conv2d_stem_f32_pack_elems', 'pvhip_conv2d_f16_stem_supported', 'pvhip_conv2d_f16_stem_pack_elems', 'pvhip_lrn_maxpool3x3_c8_supported', 'pvhip_conv2d_f16_c8_multi_supported', 'pvhip_c8_f16_elems', 'pvhip_conv2d_f16_c8_supported', 'pvhip_conv2d_f16_c8_pack_elems', 'pvhip_conv2d_f16_pack_elems', 'pvhip_conv2d_f16_dma_supported', 'pvhip_conv2d_f16_span_supported', 'pvhip_conv2d_f16_span_pack_elems', 'pvhip_conv2d_kernel_kind', 'pvhip_abi_version', 'pvhip_last_error', 'pvhip_conv2d_pack_elems', 'pvhip_lrn_maxpool_supported', 'pvhip_maxpool_lrn_supported',
+_NOT_STATUS = {'pvhip_host_alloc', 'pvhip_conv2d_stem_direct_pool_supported', 'pvhip_lrn_conv1x1_supported', 'pvhip_conv2d_stem_wino_supported', 'pvhip_conv2d_stem_wino_pack_elems', 'pvhip_maxpool3x3_lrn_conv1x1_c8_supported', 'pvhip_conv2d_f16_stem_direct_supported', 'pvhip_maxpool_lrn_conv1x1_supported', 'pvhip_conv2d_stem_direct_supported', 'pvhip_conv2d_stem_f32_supported', 'pvhip_conv2d_stem_f32_pack_elems', 'pvhip_conv2d_f16_stem_supported', 'pvhip_conv2d_f16_stem_pack_elems', 'pvhip_lrn_maxpool3x3_c8_supported', 'pvhip_conv2d_f16_c8_multi_supported', 'pvhip_c8_f16_elems', 'pvhip_conv2d_f16_c8_supported', 'pvhip_conv2d_f16_c8_pack_elems', 'pvhip_conv2d_f16_pack_elems', 'pvhip_conv2d_f16_dma_supported', 'pvhip_conv2d_f16_span_supported', 'pvhip_conv2d_f16_span_pack_elems', 'pvhip_conv2d_kernel_kind', 'pvhip_abi_version', 'pvhip_last_error', 'pvhip_conv2d_pack_elems', 'pvhip_lrn_maxpool_supported', 'pvhip_maxpool_lrn_supported',
                'pvhip_conv2d_multi_supported', 'pvhip_conv2d_pooled_supported', 'pvhip_heatmap_peaks_form', 'pvhip_segment_labels_form', 'pvhip_heatmap_maxima_form'}
 
 
@@ -305,6 +309,8 @@ def _plugin_settings():
         'conv_f16_c8': _env_level('PVHIP_CONV_F16_C8', '2'),
         'fuse_poolconv': _env_level('PVHIP_FUSE_POOLCONV', '2'),    # MaxPool + pool_proj as one launch: 0 = never
         'fuse_stem_conv': _env_level('PVHIP_FUSE_STEM_CONV', '1'),  # the 1x1 convolution behind MaxPool + LRN in the same launch (0 = two launches)
+        # the stem convolution in front of that launch also writes the MaxPool's tensor, the launch is LRN + 1x1 only: 0 = never, 1 = by the size rule, 2 = wherever supported
+        'fuse_stem_pool': _env_level('PVHIP_FUSE_STEM_POOL', '1'),
     }
 
 

@@ -9,7 +9,7 @@ from . import device        # settings only (parsed from the environment at impo
 
 # every hint the dispatcher may put on a task's node dict for its plugin (cleared before a task's own are set, and by release_device_state)
 HINT_KEYS = ('_fuse_pool_in', '_pre_add', '_f16_mfma', '_fuse_bias', '_fuse_act', '_out_into', '_out_c8', '_siblings', '_fuse_pool',
-             '_fuse_lrn', '_fuse_conv')
+             '_fuse_lrn', '_fuse_conv', '_fuse_pool_out', '_pooled_out', '_pooled_in')
 
 
 def data_src(G, nid):          # the node that feeds input port 0 of `nid`, or None
@@ -29,6 +29,7 @@ class FusionPlan:
         self.pool_conv = {}         # Convolution node id -> (MaxPool node folded into its input tile, id of the MaxPool's data input)
         self.pre_add = {}           # Convolution node id -> (Add node folded into its padding pass, Const id, id of the Add's data input)
         self.stem_conv = {}         # MaxPool (leading MaxPool + LRN) -> the 1x1 convolution behind the LRN that rides in the same launch
+        self.stem_pool = {}         # Convolution (the stem) -> the MaxPool behind its chain whose tensor the convolution's launch writes too: that MaxPool's launch is LRN + 1x1 only
         self.c8_out = set()         # FP16 IRs: convolutions whose fused chain hands its output over blocked by eight channels
         self.c8_concat = set()      # ... Concats that get a blocked buffer
         self.c8_entry = set()       # ... the tensor the first blocked module reads, converted once
@@ -84,7 +85,7 @@ class FusionPlan:
 
 def build(G, order, plugins, fuse_epilogues=True, fuse_siblings=True, f16=False):
     """The plan of graph `G` in list-schedule `order` for the plugin registry `plugins` ({layer type: module}).  fuse_epilogues=False:
-    nothing is folded.  Reads device.fuse_poolconv, fuse_stem_conv, conv_f16_c8, conv_f16_dma and PVHIP_SCHEDULE_LOCALITY."""
+    nothing is folded.  Reads device.fuse_poolconv, fuse_stem_conv, fuse_stem_pool, conv_f16_c8, conv_f16_dma and PVHIP_SCHEDULE_LOCALITY."""
     p = FusionPlan(G, order, f16)
     if fuse_epilogues:
         _lrn_then_pool(p, plugins)
@@ -97,6 +98,7 @@ def build(G, order, plugins, fuse_epilogues=True, fuse_siblings=True, f16=False)
             _pre_add(p, conv)
             _siblings(p, conv, fuse_siblings)
             _stem_conv(p, plugins)
+            _stem_pool(p, plugins)
             _c8_writers(p, conv)
             _c8_stem(p, plugins)
             _c8_stem_conv(p, plugins)
@@ -273,6 +275,26 @@ def _stem_conv(p, plugins):
         if pool.lrn_conv_fusable(G.nodes[pid], G.nodes[lid], G.nodes[cid]):
             p.stem_conv[pid] = cid
             p.fused_away.update(p.chain(cid))
+
+
+def _stem_pool(p, plugins):
+    """fp32 IRs: a fused chain that stands alone and is read only by a MaxPool that heads a `stem_conv` launch (GoogLeNet: conv1/7x7_s2 ->
+    pool1/3x3_s2): the convolution's launch writes the pooled tensor as a second output and hands it to the MaxPool task, whose launch is
+    then LRN + 1x1 convolution only.  Nothing else of the plan changes: the chain's port still gets the convolution's own output.
+    PVHIP_FUSE_STEM_POOL: 1 = by the size rule of the native query, 2 = wherever supported, 0 = never."""
+    G, conv, pool = p.G, plugins.get('Convolution'), plugins.get('MaxPool')
+    if p.f16 or device.fuse_stem_pool == 0 or not getattr(conv, 'SUPPORTS_POOLED_OUTPUT', False) or not getattr(pool, 'SUPPORTS_POOLED_INPUT', False):
+        return
+    for cid, f in p.fusion.items():
+        if G.nodes[cid]['type'] != 'Convolution' or f['into'] is not None or any(cid in m for m in (p.siblings, p.fused_away, p.pool_conv)):
+            continue
+        readers = list(G.successors(p.tail(cid)))
+        if len(readers) != 1 or readers[0] not in p.stem_conv or G.edges[(p.tail(cid), readers[0])]['connection'][3] != 0:
+            continue
+        pid = readers[0]
+        if conv.pooled_output_fusable(G.nodes[cid], G.nodes[pid], by_size=device.fuse_stem_pool != 2, pre_add=cid in p.pre_add) and \
+                pool.pooled_input_ok(G.nodes[pid], G.nodes[p.lrn_pool[pid]], G.nodes[p.stem_conv[pid]]):
+            p.stem_pool[cid] = pid
 
 
 def _c8(conv, modules=False):

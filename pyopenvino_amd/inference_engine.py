@@ -601,6 +601,7 @@ class Executable_Network:
     _pool_conv = property(lambda self: self.plan.pool_conv)
     _pre_add = property(lambda self: self.plan.pre_add)
     _stem_conv = property(lambda self: self.plan.stem_conv)
+    _stem_pool = property(lambda self: self.plan.stem_pool)
     _c8_out = property(lambda self: self.plan.c8_out)
     _c8_concat = property(lambda self: self.plan.c8_concat)
     _c8_entry = property(lambda self: self.plan.c8_entry)
@@ -842,6 +843,12 @@ class Executable_Network:
             wsrc = next(G.edges[(p_, stem_conv)]['connection'] for p_ in G.pred[stem_conv] if G.edges[(p_, stem_conv)]['connection'][3] == 1)
             node['_fuse_conv'] = {'node': G.nodes[stem_conv], 'w': G.nodes[wsrc[0]]['output'][wsrc[1]]['data'],     # c8: FP16 IRs, blocked
                                   'bias': G.nodes[sf['bias']]['output'][0]['data'], 'act': sf['act'], 'c8': fp.f16}
+        pooled_by = fp.stem_pool.get(task)   # the stem convolution also writes the tensor of the MaxPool behind it ...
+        if pooled_by is not None:
+            node['_fuse_pool_out'] = G.nodes[pooled_by]
+        for cid, pid in fp.stem_pool.items():    # ... and that MaxPool's launch takes it (a recording holds its address: capture_graph keeps it alive)
+            if pid == task:
+                node['_pooled_in'] = G.nodes[cid].pop('_pooled_out', None)
 
     # ---- hipGraph replay of a whole pass (what the reference's run_tasks loop, :259-292, becomes: one launch call)
     def capture_graph(self, inputs: dict, warm: int = 2, streams=1):
@@ -889,6 +896,8 @@ class Executable_Network:
             self._pending = None
         results = {name: G.nodes[nid]['result'] for nid, name in self.ienet.find_node_by_type('Result')}
         keep = [p['data'] for n in G.nodes for p in G.nodes[n].get('output', {}).values() if 'data' in p] + list(results.values())
+        # ... and the pooled tensor the stem convolution handed to the MaxPool behind it: it is on no port, and the next eager pass drops the hint
+        keep += [G.nodes[n]['_pooled_in'] for n in G.nodes if G.nodes[n].get('_pooled_in') is not None]
         self._graph = {'handle': handle.value, 'inputs': dict(inputs), 'keep': keep, 'results': results,
                        'by_hand': not self._auto_graph_busy}       # a recording made by hand is never replaced by infer()
         device.select_stream(0)

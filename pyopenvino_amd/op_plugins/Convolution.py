@@ -323,6 +323,45 @@ def route(x_shape, w_shape, strides, pads_begin, pads_end, auto_pad='explicit', 
     return _dense_route(*dense, False, pre_add, clamp)
 
 
+# A 7x7 / 2 first convolution on the row-span kernel that reads the image itself can write a SECOND output: the 3x3 / stride 2 / unpadded / ceil MaxPool
+# of its own output (after bias and activation), taken where the values already are.  node['_fuse_pool_out'] = the MaxPool's node dict asks for it;
+# the pooled tensor is left in node['_pooled_out'] (None where this launch could not make it) and the engine hands it to the MaxPool task.  The
+# engine asks pooled_output_fusable() first.
+SUPPORTS_POOLED_OUTPUT = True
+
+
+def _pooled_extent(pool_node: dict, oh: int, ow: int):
+    """(poh, pow) when the node is the MaxPool the stem kernel's second output is (3x3 / stride 2 / no padding / ceil), else None."""
+    from . import MaxPool
+    pa = pool_node['data']
+    geo = tuple(tuple(common_def.string_to_tuple(pa[k])) for k in ('kernel', 'strides', 'pads_begin', 'pads_end'))
+    if geo != ((3, 3), (2, 2), (0, 0), (0, 0)) or pa['rounding_type'] != 'ceil' or pa['auto_pad'] not in ('explicit', 'valid'):
+        return None
+    return MaxPool.calc_output_shape((oh, ow), (3, 3), (2, 2), (0, 0), (0, 0), 'ceil', pa['auto_pad'])
+
+
+def pooled_output_fusable(node: dict, pool_node: dict, by_size: bool = True, pre_add: bool = False) -> bool:
+    """True when this fp32 convolution takes pvhip_conv2d_stem_direct_f32 and that kernel's pooled form covers the MaxPool behind it (IR
+    attributes and port dims; no device needed).  by_size: the native size rule decides too (every CU walks enough tiles)."""
+    try:
+        xs, ws = tuple(int(d) for d in node['input'][0]['dims']), tuple(int(d) for d in node['input'][1]['dims'])
+        if node['input'][0]['precision'] != 'FP32' or len(xs) != 4 or len(ws) != 4:
+            return False
+        attrs = node['data']
+        strides, pads_begin, pads_end = (tuple(common_def.string_to_tuple(attrs[k])) for k in ('strides', 'pads_begin', 'pads_end'))
+        r = _dense_route(xs, ws, strides, pads_begin, pads_end, attrs['auto_pad'], pre_add=pre_add)
+        if r.entry != 'pvhip_conv2d_stem_direct_f32':
+            return False
+        g = _geometry(xs, ws, strides, pads_begin, pads_end, attrs['auto_pad'])
+        pooled = _pooled_extent(pool_node, g.oh, g.ow)
+        if pooled is None or tuple(int(d) for d in pool_node['input'][0]['dims']) != (g.n, g.kn, g.oh, g.ow):
+            return False
+        return bool(dev.call('pvhip_conv2d_stem_direct_pool_supported', g.n if by_size else 0, g.c, g.h, g.w, g.kn, g.kh, g.kw, *g.strides, *g.pads_begin,
+                             g.oh, g.ow, *pooled))
+    except (KeyError, ValueError, AssertionError, IndexError, TypeError):
+        return False
+
+
 def _route_of(node: dict, decide, *facts) -> Route:
     """decide(*facts), kept on the node (node['_hip_route'] = (key, route)) per facts and settings: asked once, not on every launch."""
     key = (dev.settings_serial, decide, facts)
@@ -446,6 +485,16 @@ def _launch_dense(node, r, x, w, strides, pads_begin, pads_end, auto_pad, bias, 
     if stem:
         image = (dev.ptr(pre_add),) if r.entry in _IMAGE_READERS else ()
         epilogue = (act_code,) if r.out == 'blocked' else (act_code, act_lo, act_hi)
+        pool_node = node.get('_fuse_pool_out')
+        if pool_node is not None:
+            node['_pooled_out'] = None
+            pooled = _pooled_extent(pool_node, oh, ow) if r.entry == 'pvhip_conv2d_stem_direct_f32' and into is None else None
+            if pooled is not None and dev.call('pvhip_conv2d_stem_direct_pool_supported', 0, c, h, wd, kn, kh, kw, *strides, *pads_begin, oh, ow, *pooled):
+                yp = dev.DeviceTensor.empty((n, kn, pooled[0], pooled[1]))
+                dev.call('pvhip_conv2d_stem_direct_pool_f32', dev.ptr(x), dev.ptr(wpack), dev.ptr(y), dev.ptr(yp), n, h, wd, kn, oh, ow, pooled[0], pooled[1],
+                         dev.ptr(pre_add), dev.ptr(bias), act_code, act_lo, act_hi)
+                node['_pooled_out'] = yp
+                return y
         dev.call(r.entry, dev.ptr(x), dev.ptr(wpack), dev.ptr(y), n, h, wd, kn, oh, ow, *image, dev.ptr(bias), *epilogue)
     elif r.out == 'blocked':
         dev.call(r.entry, dev.ptr(x), dev.ptr(wpack), dev.ptr(y), n, c, h, wd, kn, kh, kw, oh, ow, strides[0], strides[1], pads_begin[0],

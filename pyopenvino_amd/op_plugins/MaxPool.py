@@ -83,6 +83,24 @@ def lrn_conv_fusable(node: dict, lrn_node: dict, conv_node: dict, f16: bool = Fa
         return False
 
 
+# ... and where the convolution in FRONT of this node has written the pooled tensor already (the stem convolution's second output), the launch is
+# LRN + 1x1 convolution only: node['_pooled_in'] = that tensor, beside '_fuse_lrn' and '_fuse_conv'.  The engine asks pooled_input_ok() first.
+SUPPORTS_POOLED_INPUT = True
+
+
+def pooled_input_ok(node: dict, lrn_node: dict, conv_node: dict) -> bool:
+    """True when pvhip_lrn_conv1x1_f32 covers the LRN and the 1x1 convolution of this triple (IR attributes and port dims; no device needed)."""
+    try:
+        if not lrn_conv_fusable(node, lrn_node, conv_node):
+            return False
+        n, c, oh, ow = (int(d) for d in conv_node['input'][0]['dims'])
+        la = lrn_node['data']
+        return bool(dev.call('pvhip_lrn_conv1x1_supported', n, c, oh * ow, int(la['size']), float(la['beta']), float(la['bias']),
+                             int(conv_node['input'][1]['dims'][0])))
+    except (KeyError, ValueError, AssertionError, IndexError, TypeError):
+        return False
+
+
 def blocked_ok(node: dict, lrn_node: dict = None) -> bool:
     """True when compute() pools a dev.BlockedHalf input of this node as it is and returns a dev.BlockedHalf (FP16 IRs; IR attributes
     and port dims, no device needed): a 3x3 window with a non-empty output, and an LRN folded behind it only over five channels.
@@ -171,6 +189,13 @@ def compute(node: dict, inputs: dict = None, kernel_type: str = 'hip', debug: bo
         assert tuple(cw.shape[1:]) == (c, 1, 1) and (cb is None or cb.size == k_out)
         act_code, act_lo, act_hi = dev.act_args(conv.get('act'))
         yc = dev.DeviceTensor.empty((n, k_out, oh, ow))
+        pooled = node.get('_pooled_in')
+        if pooled is not None:
+            # the convolution in front has written the pooled tensor too: LRN + 1x1 convolution only
+            assert tuple(pooled.shape) == (n, c, oh, ow)
+            dev.call('pvhip_lrn_conv1x1_f32', ctypes.c_void_p(pooled.ptr), ctypes.c_void_p(cw.ptr), ctypes.c_void_p(yc.ptr), n, c, oh * ow,
+                     int(la['size']), float(la['alpha']), float(la['beta']), float(la['bias']), k_out, dev.ptr(cb), act_code, act_lo, act_hi)
+            return {common_def.first_output_port(node): yc}
         dev.call('pvhip_maxpool_lrn_conv1x1_f32', ctypes.c_void_p(x.ptr), ctypes.c_void_p(cw.ptr), ctypes.c_void_p(yc.ptr), n, c, h, w, oh, ow,
                  kernel[0], kernel[1], strides[0], strides[1], pads_begin[0], pads_begin[1], pads_end[0], pads_end[1],
                  int(la['size']), float(la['alpha']), float(la['beta']), float(la['bias']), k_out, dev.ptr(cb),
