@@ -778,6 +778,50 @@ int pvhip_segment_labels_form(int c, int h, int w);
 int pvhip_segment_labels_f32(const float* x, int n, int c, int h, int w, int has_min, float min_score,
                              unsigned char* labels, int* areas, int* extents);
 
+/* ---------------------------------------------------------------- a text recogniser's answer ---- */
+/* Addition to ABI v19 (the version number is unchanged: nothing existing changed): the greedy CTC decoding of a contiguous fp32 tensor of
+ * per-timestep class scores -- what a user of a text recogniser makes on the host with argmax(-1) and a collapse after reading
+ * 4 n t c bytes back -- so that 4 + 12 t bytes per batch row are read back.  `layout` says where the axes stand:
+ * PVHIP_TEXT_LAYOUT_TNC reads x as (t, n, c), PVHIP_TEXT_LAYOUT_NTC as (n, t, c), PVHIP_TEXT_LAYOUT_NCT as (n, c, t).  The rule
+ * (pyopenvino_amd/text.py states the same one in numpy and tests/text_ref.py in plain loops, matched bit for bit), for batch row r
+ * with scores v[t][c]:
+ *   1. winner  w(t) is the first class of timestep t in top_k's total order: NaN of any sign or payload first, then descending with
+ *      +0.0 == -0.0, ties to the lower class.
+ *   2. void    row r is void iff the winning score of any of its timesteps is NaN, that is, iff any of its T * C scores is NaN.
+ *      A void row has length -1 and nothing but filler: the quiet-NaN rows behind `count` of a DetectedRois or LandmarkWarps pass
+ *      are void.  An empty string (length 0) is an answer and not a void row.
+ *   3. emit    timestep t emits iff w(t) != blank and (merge_repeated is false, or t == 0, or w(t) != w(t - 1)).  A repeat across
+ *      a blank therefore emits twice: a, blank, a is aa.
+ *   4. order   the emitting timesteps in ascending t fill slots 0, 1, ...: symbols = w(t), scores = the bits of v[t][w(t)],
+ *      steps = t.
+ * `lengths` (n) int32, `symbols` (n, t) int32, `scores` (n, t) fp32, `steps` (n, t) int32.  The first lengths[r] slots of row r are
+ * its string in time order; the slots behind them -- all of them in a void row -- are (-1, quiet NaN, -1), quiet NaN being 0x7FC00000.
+ * `blank` is the resolved class, 0 .. c - 1; `merge` is merge_repeated as 0 or 1.  `scratch` is device memory of n * t 8-byte words
+ * that only the two launches read and write: scratch[r * t + i] is the key of pvhip_topk_rows_f32's order of (winning score's bits,
+ * w(i)).  `x` may be only 4-byte aligned.  Two launches on the current stream, no global-memory atomics, the same bits every call:
+ * (1) the winners, in one of two forms by the layout: PVHIP_TEXT_FORM_ROWS (TNC, NTC: the class axis is contiguous), one wave per
+ * (r, i) row, split at its 16-byte boundaries into head, body of 16-byte pieces and tail, one pass and one wave-wide maximum, on a
+ * grid of at most PVHIP_TEXT_MAX_BLOCKS workgroups of four waves that stride over the rows; PVHIP_TEXT_FORM_PLANES (NCT: the time
+ * axis is contiguous), a lane per four consecutive timesteps that walks the classes in 16-byte loads at whatever 4-byte phase the
+ * planes stand and takes a strictly larger order word only, one workgroup per 1024 timesteps, no cap; (2) the collapse, one
+ * workgroup per batch row: the row's keys in chunks of 256, void by a workgroup-wide reduction, each emitting timestep's slot from a
+ * ballot prefix within its wave plus wave and chunk offsets through LDS, every slot of the row written once, filler included.
+ * pvhip_ctc_greedy_form returns the form of (layout, t, c) -- no status, no device needed --, PVHIP_TEXT_FORM_NONE for what the
+ * entry refuses.
+ * n, t >= 1, t <= PVHIP_TEXT_MAX_STEPS, c >= 2, n * t * c < 2^31, layout one of the three, 0 <= blank < c, merge 0 or 1, no NULL
+ * pointer, `scratch` 8-byte and the others 4-byte aligned; else PVHIP_EINVAL and nothing is launched. */
+#define PVHIP_TEXT_MAX_STEPS    4096
+#define PVHIP_TEXT_MAX_BLOCKS   2048
+#define PVHIP_TEXT_LAYOUT_TNC   0
+#define PVHIP_TEXT_LAYOUT_NTC   1
+#define PVHIP_TEXT_LAYOUT_NCT   2
+#define PVHIP_TEXT_FORM_NONE    0
+#define PVHIP_TEXT_FORM_ROWS    1
+#define PVHIP_TEXT_FORM_PLANES  2
+int pvhip_ctc_greedy_form(int layout, int t, int c);
+int pvhip_ctc_greedy_f32(const float* x, int n, int t, int c, int layout, int blank, int merge, unsigned long long* scratch,
+                         int* lengths, int* symbols, float* scores, int* steps);
+
 /* ---------------------------------------------------------------- a detector's answer ------ */
 /* Addition to ABI v18 (the version number is unchanged: nothing existing changed): the records of pvhip_detection_output_f32 become one
  * flat table of the detections a caller wants -- what the reference's sample makes on the host with `for record in res.reshape(100, 7):

@@ -10,8 +10,10 @@ from .gallery import Gallery, GalleryMatch, Matches  # noqa: F401
 from .keypoints import Keypoints, PeakScreen  # noqa: F401
 from .segments import Segments, SegmentScreen  # noqa: F401
 from .maxima import Maxima, MaximaScreen  # noqa: F401
+from . import text  # noqa: F401
+from .text import Text, TextScreen  # noqa: F401
 from .input_format import DetectedRois, LandmarkWarps, PerspectiveInput, RoiInput, WarpInput  # noqa: F401
 from .tiled_detections import RegionScreen, TiledScreen  # noqa: F401
 from .top_k import TopK  # noqa: F401
 
-__all__ = ['IECore', 'IENetwork', 'Executable_Network', 'RoiInput', 'WarpInput', 'PerspectiveInput', 'DetectedRois', 'LandmarkWarps', 'TopK', 'Detections', 'DetectionScreen', 'TiledScreen', 'RegionScreen', 'Gallery', 'GalleryMatch', 'Matches', 'PeakScreen', 'Keypoints', 'SegmentScreen', 'Segments', 'MaximaScreen', 'Maxima']
+__all__ = ['IECore', 'IENetwork', 'Executable_Network', 'RoiInput', 'WarpInput', 'PerspectiveInput', 'DetectedRois', 'LandmarkWarps', 'TopK', 'Detections', 'DetectionScreen', 'TiledScreen', 'RegionScreen', 'Gallery', 'GalleryMatch', 'Matches', 'PeakScreen', 'Keypoints', 'SegmentScreen', 'Segments', 'MaximaScreen', 'Maxima', 'TextScreen', 'Text', 'text']

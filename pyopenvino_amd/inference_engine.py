@@ -312,23 +312,24 @@ class InferRequest:
         `matches`      a ``Gallery`` or a ``GalleryMatch``                                      ``Matches``     gallery.py
         `keypoints`    a ``PeakScreen``, a min_score or True                                    ``Keypoints``   keypoints.py
         `segments`     a ``SegmentScreen``, a min_score or True                                 ``Segments``    segments.py
-        `maxima`       a ``MaximaScreen``, a min_score or True                                  ``Maxima``      maxima.py"""
+        `maxima`       a ``MaximaScreen``, a min_score or True                                  ``Maxima``      maxima.py
+        `text`         a ``TextScreen`` or True                                                 ``Text``        text.py"""
 
     def __init__(self, owner, runner, index: int):
         self.owner, self.runner, self.index = owner, runner, index      # owner: the network load_network returned
         self._in_flight, self._replayed = False, None
-        self._asks = {}                 # {Result name: ask} of the pass in flight (answers.py): what top_k=, detections=, matches=, keypoints=, segments= and maxima= named
+        self._asks = {}                 # {Result name: ask} of the pass in flight (answers.py): what top_k=, detections=, matches=, keypoints=, segments=, maxima= and text= named
 
-    def start_async(self, inputs: dict, top_k=None, detections=None, matches=None, keypoints=None, segments=None, maxima=None):
-        self._start(inputs, (top_k, detections, matches, keypoints, segments, maxima), False)
+    def start_async(self, inputs: dict, top_k=None, detections=None, matches=None, keypoints=None, segments=None, maxima=None, text=None):
+        self._start(inputs, (top_k, detections, matches, keypoints, segments, maxima, text), False)
 
     def _start(self, inputs, asked, verbose):
-        """`asked`: (top_k, detections, matches, keypoints, segments, maxima) as the public signatures took them."""
+        """`asked`: (top_k, detections, matches, keypoints, segments, maxima, text) as the public signatures took them."""
         if self._in_flight:
             raise RuntimeError('request {} is still in flight: wait() first'.format(self.index))
         ex = self.runner
         sharded = ex.sharded or self.owner.sharded
-        asks = ex.answers.checked(inputs, asked[0], asked[1], sharded, asked[2], asked[3], asked[4], asked[5])
+        asks = ex.answers.checked(inputs, asked[0], asked[1], sharded, asked[2], asked[3], asked[4], asked[5], asked[6])
         fed, inputs = inputs, ex.host_inputs.stage(inputs, ex.stream_base, sharded)
         self._asks = ex.answers.bound(asks, fed)
         ex.wait_result_readers()
@@ -369,8 +370,8 @@ class InferRequest:
                 G.nodes[nid]['result'] = out[name] = ex._read_back(value, self.owner.comm)
         return out
 
-    def infer(self, inputs: dict, top_k=None, detections=None, matches=None, keypoints=None, segments=None, maxima=None) -> dict:
-        self.start_async(inputs, top_k, detections, matches, keypoints, segments, maxima)
+    def infer(self, inputs: dict, top_k=None, detections=None, matches=None, keypoints=None, segments=None, maxima=None, text=None) -> dict:
+        self.start_async(inputs, top_k, detections, matches, keypoints, segments, maxima, text)
         return self.wait()
 
     def input_buffer(self, name: str, source_size=None, frames=None) -> np.ndarray:
@@ -553,8 +554,8 @@ class Executable_Network:
                 event.wait()
             device.select_stream(0)
 
-    def start_async(self, request_id: int, inputs: dict, top_k=None, detections=None, matches=None, keypoints=None, segments=None, maxima=None):
-        self.requests[request_id].start_async(inputs, top_k, detections, matches, keypoints, segments, maxima)
+    def start_async(self, request_id: int, inputs: dict, top_k=None, detections=None, matches=None, keypoints=None, segments=None, maxima=None, text=None):
+        self.requests[request_id].start_async(inputs, top_k, detections, matches, keypoints, segments, maxima, text)
 
     def wait(self, request_id: int) -> dict:
         return self.requests[request_id].wait()
@@ -1065,11 +1066,11 @@ class Executable_Network:
             return None
         return self._graph
 
-    def infer(self, inputs: dict, verbose: bool = False, top_k=None, detections=None, matches=None, keypoints=None, segments=None, maxima=None) -> dict:
-        """`top_k`, `detections`, `matches`, `keypoints`, `segments`, `maxima`: the Results they name come back as their answers (InferRequest has the table)."""
-        if not (top_k is detections is matches is keypoints is segments is maxima is None):     # something is asked: the pass of request 0 (this network's own graph and streams), waited for at once
+    def infer(self, inputs: dict, verbose: bool = False, top_k=None, detections=None, matches=None, keypoints=None, segments=None, maxima=None, text=None) -> dict:
+        """`top_k`, `detections`, `matches`, `keypoints`, `segments`, `maxima`, `text`: the Results they name come back as their answers (InferRequest has the table)."""
+        if not (top_k is detections is matches is keypoints is segments is maxima is text is None):     # something is asked: the pass of request 0 (this network's own graph and streams), waited for at once
             request = self.requests[0] if self.requests else InferRequest(self, self, 0)
-            request._start(inputs, (top_k, detections, matches, keypoints, segments, maxima), verbose)
+            request._start(inputs, (top_k, detections, matches, keypoints, segments, maxima, text), verbose)
             return request.wait()
         inputs = self.host_inputs.stage(inputs, self.stream_base, self.sharded)
         self.wait_result_readers()
