@@ -822,6 +822,71 @@ int pvhip_ctc_greedy_form(int layout, int t, int c);
 int pvhip_ctc_greedy_f32(const float* x, int n, int t, int c, int layout, int blank, int merge, unsigned long long* scratch,
                          int* lengths, int* symbols, float* scores, int* steps);
 
+/* ---------------------------------------------------------------- a dense detector head's answer ---- */
+/* Addition to ABI v19 (the version number is unchanged: nothing existing changed): the table of detections of a contiguous fp32 tensor of
+ * per-anchor boxes and class scores -- what a user of a YOLO-style export makes on the host with a confidence filter, a box decoding and
+ * a greedy suppression after reading 4 n a e bytes back -- so that 32 bytes per surviving box are read back.  e = 4 + objectness + c
+ * channels per anchor, the first four the box; PVHIP_BOXES_LAYOUT_NCA reads x as (n, e, a) (channel planes, anchors contiguous: YOLOv8 /
+ * v11), PVHIP_BOXES_LAYOUT_NAC as (n, a, e) (YOLOv5 / v7, YOLOX).  The rule (pyopenvino_amd/boxes.py states the same one in numpy and
+ * tests/boxes_ref.py in plain loops, matched bit for bit), for image r and anchor i with channel values v[0 .. e - 1], O = objectness:
+ *   1. winner  k* is the first of the c class scores v[4 + O ..] in the total order of pvhip_topk_rows_f32 above: NaN of any sign or
+ *      payload first, then descending with +0.0 == -0.0, ties to the lower class.  score = v[4 + O + k*], or, with objectness,
+ *      v[4] * v[4 + O + k*] as one fp32 product, rounded once, never contracted.  The anchor is out iff !(score >= min_score) -- so for a
+ *      NaN score; equality keeps.  Any NaN among an anchor's class scores therefore drops it: the quiet-NaN rows behind `count` of a
+ *      DetectedRois or LandmarkWarps pass have counts = selected = 0.
+ *   2. box     all four box numbers must be finite, else the anchor is out.  PVHIP_BOXES_CXCYWH corners in fp32, never contracted:
+ *      xa = cx - w * 0.5f, xb = cx + w * 0.5f, ya and yb alike; PVHIP_BOXES_XYXY: the numbers themselves.  They are pixels of the
+ *      network's input, in which the frame stands in the rectangle [dy, dy + ih) x [dx, dx + iw): a corner p maps to the frame in
+ *      binary64 as t = ((double)p - (double)d) * (double)F / (double)i, three operations, each rounded once, none contracted, (d, i, F) =
+ *      (dx, iw, frame_w) for an x corner and (dy, ih, frame_h) for a y corner.  x0 = floor(min(max(t(xa), 0), frame_w)), x1 =
+ *      ceil(min(max(t(xb), 0), frame_w)), w = x1 - x0; y0, y1, h alike.  The anchor is out when w < min_w or h < min_h (an inverted box
+ *      is), and, with labels != NULL, unless k* == labels[j] for some j < num_labels <= 64 (num_labels 0 with a pointer: every anchor is
+ *      out).  With the identity geometry (0, 0, frame_w, frame_h) p * F / F is p itself: a box on integer pixel edges stays on them.
+ *   3. cap     selected[r] counts the anchors still in.  The max_candidates best of them go on, in descending score with +0.0 == -0.0,
+ *      ties to the lower anchor: the descending order of the keys (score bits, i) of pvhip_topk_rows_f32.
+ *   4. suppression  greedy in that order by the rule of pvhip_detections_merge_tiles below, word for word: int64 areas of the frame
+ *      rectangles, den the union (PVHIP_OVERLAP_IOU) or the smaller area (PVHIP_OVERLAP_IOS), a candidate dropped iff an earlier kept
+ *      one -- of the same k* when per_label -- overlaps it with (double)inter > (double)threshold * (double)den; equality keeps.
+ *   5. table   image r keeps its first counts[r] = min(kept, max_per_image) kept candidates; rows are eight 32-bit words (r, x0, y0, w,
+ *      h, k*, score bits, r * a + i), in (image, order of 3.) order without gaps; total = sum(counts).
+ * `header` = counts[n], selected[n], total; `rows`: n * max_per_image rows of 32 bytes at most, 16-byte aligned; rows >= total are not
+ * written.  `x` may be only 4-byte aligned.  `scratch` is device memory, 16-byte aligned, that only the three launches read and write:
+ * the (n, a) 8-byte keys, the (n, a) int32 winners, then -- at the next 16-byte boundary -- the n * max_per_image staging rows:
+ * PVHIP_BOXES_SCRATCH_BYTES(n, a, max_per_image) bytes.
+ * Three launches on the current stream, no global-memory atomics, no workgroup waits for another, the same bits every call.
+ * (1) score: x is read once; every anchor's key -- that of (score bits, i) when it passes 1. and 2. in full, else 0 -- and its k* are
+ * written.  PVHIP_BOXES_FORM_PLANES (NCA): a lane owns four consecutive anchors and walks the class planes in 16-byte loads at whatever
+ * 4-byte phase they stand, one 32-bit order word and class per anchor, a strictly larger word replacing.  NAC: a team of lanes takes an
+ * anchor's e contiguous numbers in 16-byte pieces between the row's own 16-byte boundaries, then one team-wide maximum of keys --
+ * PVHIP_BOXES_FORM_ROWS_TEAM, 16 lanes and four anchors a wave, for e <= PVHIP_BOXES_TEAM_ROW, PVHIP_BOXES_FORM_ROWS_WAVE, a wave per
+ * anchor, above.  pvhip_dense_boxes_form returns the form of (layout, a, e) -- no status, no device needed --, PVHIP_BOXES_FORM_NONE
+ * for what the entry refuses.  (2) images: one workgroup of 1024 lanes per image keeps the max_candidates largest keys by the bounded
+ * buffer of pvhip_heatmap_maxima_f32 (in dynamic LDS, at most 64 KB), counts selected, makes the sorted survivors' rectangles again by
+ * the device function of (1), suppresses greedily in chunks of 64 as pvhip_detections_merge_tiles does and writes the kept rows to the
+ * image's staging rows.  (3) write: one wave per image sums the counts in front of it and copies its rows in 16-byte stores; the
+ * last image's wave writes total.
+ * n, a, c >= 1, n * a * (4 + objectness + c) < 2^31, layout, box and overlap each one of the two, objectness and per_label 0 or 1,
+ * min_score finite, 0 <= num_labels <= 64 (labels not NULL when > 0), frame_h, frame_w, iw, ih in 1 .. 2^24, dx, dy in 0 .. 2^24,
+ * min_h, min_w >= 1, 1 <= max_candidates <= PVHIP_BOXES_MAX_CANDIDATES, 1 <= max_per_image <= max_candidates, 0 <= threshold <= 1, no
+ * NULL or misaligned pointer; else PVHIP_EINVAL and nothing is launched. */
+#define PVHIP_BOXES_LAYOUT_NCA       0
+#define PVHIP_BOXES_LAYOUT_NAC       1
+#define PVHIP_BOXES_CXCYWH           0
+#define PVHIP_BOXES_XYXY             1
+#define PVHIP_BOXES_FORM_NONE        0
+#define PVHIP_BOXES_FORM_PLANES      1
+#define PVHIP_BOXES_FORM_ROWS_TEAM   2
+#define PVHIP_BOXES_FORM_ROWS_WAVE   3
+#define PVHIP_BOXES_TEAM_ROW         128
+#define PVHIP_BOXES_MAX_CANDIDATES   4096
+#define PVHIP_BOXES_SCRATCH_BYTES(n, a, max_per_image) \
+    ((((size_t)12 * (size_t)(n) * (size_t)(a) + 15u) & ~(size_t)15u) + (size_t)32 * (size_t)(n) * (size_t)(max_per_image))
+int pvhip_dense_boxes_form(int layout, int a, int e);
+int pvhip_dense_boxes_f32(const float* x, int n, int a, int c, int layout, int objectness, int box, float min_score,
+                          const int* labels, int num_labels, int frame_h, int frame_w, int dx, int dy, int iw, int ih,
+                          int min_h, int min_w, int max_candidates, int overlap, float threshold, int per_label, int max_per_image,
+                          void* scratch, int* header, int* rows);
+
 /* ---------------------------------------------------------------- a detector's answer ------ */
 /* Addition to ABI v18 (the version number is unchanged: nothing existing changed): the records of pvhip_detection_output_f32 become one
  * flat table of the detections a caller wants -- what the reference's sample makes on the host with `for record in res.reshape(100, 7):

@@ -12,8 +12,10 @@ from .segments import Segments, SegmentScreen  # noqa: F401
 from .maxima import Maxima, MaximaScreen  # noqa: F401
 from . import text  # noqa: F401
 from .text import Text, TextScreen  # noqa: F401
+from . import boxes  # noqa: F401
+from .boxes import BoxScreen  # noqa: F401
 from .input_format import DetectedRois, LandmarkWarps, PerspectiveInput, RoiInput, WarpInput  # noqa: F401
 from .tiled_detections import RegionScreen, TiledScreen  # noqa: F401
 from .top_k import TopK  # noqa: F401
 
-__all__ = ['IECore', 'IENetwork', 'Executable_Network', 'RoiInput', 'WarpInput', 'PerspectiveInput', 'DetectedRois', 'LandmarkWarps', 'TopK', 'Detections', 'DetectionScreen', 'TiledScreen', 'RegionScreen', 'Gallery', 'GalleryMatch', 'Matches', 'PeakScreen', 'Keypoints', 'SegmentScreen', 'Segments', 'MaximaScreen', 'Maxima', 'TextScreen', 'Text', 'text']
+__all__ = ['IECore', 'IENetwork', 'Executable_Network', 'RoiInput', 'WarpInput', 'PerspectiveInput', 'DetectedRois', 'LandmarkWarps', 'TopK', 'Detections', 'DetectionScreen', 'TiledScreen', 'RegionScreen', 'Gallery', 'GalleryMatch', 'Matches', 'PeakScreen', 'Keypoints', 'SegmentScreen', 'Segments', 'MaximaScreen', 'Maxima', 'TextScreen', 'Text', 'text', 'BoxScreen', 'boxes']

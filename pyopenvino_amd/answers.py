@@ -1,16 +1,16 @@
-"""Answers behind the pass: the Results a start named with ``top_k=``, ``detections=``, ``matches=``, ``keypoints=``, ``segments=``, ``maxima=`` or ``text=`` come back from
-wait() as a ``TopK``, a ``Detections``, a ``Matches``, a ``Keypoints``, a ``Segments``, a ``Maxima`` or a ``Text`` made on the device instead of as the tensor.  One ``Answers`` per
+"""Answers behind the pass: the Results a start named with ``top_k=``, ``detections=``, ``matches=``, ``keypoints=``, ``segments=``, ``maxima=``, ``text=`` or ``boxes=`` come back from
+wait() as a ``TopK``, a ``Detections``, a ``Matches``, a ``Keypoints``, a ``Segments``, a ``Maxima``, a ``Text`` or (a dense head's) a ``Detections`` made on the device instead of as the tensor.  One ``Answers`` per
 Executable_Network (one per request), as ``HostInputs`` is on the way in: the request checks the arguments, binds the asks to the staged
 inputs, launches behind the pass and reads after it.
 
 An ask is one Result's question in its resolved form, an ``ask.Ask`` (ask.py states the protocol: KEYWORD, `bound`, `key`, `launch`,
-`on_host`): top_k.Ask, detections.Ask / FittedAsk, tiled_detections.Ask / RegionAsk, gallery.Ask, keypoints.Ask, segments.Ask, maxima.Ask or text.Ask.  Which kind it is
+`on_host`): top_k.Ask, detections.Ask / FittedAsk, tiled_detections.Ask / RegionAsk, gallery.Ask, keypoints.Ask, segments.Ask, maxima.Ask, text.Ask or boxes.Ask.  Which kind it is
 matters only where checked() makes it; the rule of each kind, its argument's forms and its refusals are stated in its module.  A plain
 screen over a detector whose input declares a fit (preprocess_info.resize_fit) learns its geometry in bound(), from the extent of the
-frames the pass was fed."""
+frames the pass was fed, and so does a BoxScreen over such an input."""
 import numpy as np
 
-from . import detections as detections_rule, device, gallery as gallery_rule, keypoints as keypoints_rule, maxima as maxima_rule, segments as segments_rule, \
+from . import boxes as boxes_rule, detections as detections_rule, device, gallery as gallery_rule, keypoints as keypoints_rule, maxima as maxima_rule, segments as segments_rule, \
     text as text_rule, tiled_detections as tiled_rule, top_k as top_k_rule
 from .input_format import FrameFeed
 
@@ -26,7 +26,7 @@ def _no_clash(keyword: str, names, asks: dict, screens=()):
 
 class Answers:
     """`blocks` = {ask.key(Result name): its Blocks}, this request's own device and page-locked blocks, made on first use: (name, k),
-    (name, resolved DetectionScreen), (name, resolved TiledScreen or RegionScreen, m), (name, id of the Gallery, k), (name, refine, space), of a class map (name,), of local maxima (name, max_per_plane, max_per_row, refine, space) or, of a decoded text, (name, layout)."""
+    (name, resolved DetectionScreen), (name, resolved TiledScreen or RegionScreen, m), (name, id of the Gallery, k), (name, refine, space), of a class map (name,), of local maxima (name, max_per_plane, max_per_row, refine, space), of a decoded text (name, layout) or, of a dense head's boxes, (name, the BoxScreen without min_score and frame_size)."""
 
     def __init__(self, runner):
         self.runner, self.blocks = runner, {}       # runner: the Executable_Network whose base stream and Results these are
@@ -34,13 +34,13 @@ class Answers:
     def release(self):
         self.blocks = {}
 
-    def checked(self, inputs, top_k, detections, sharded: bool, matches=None, keypoints=None, segments=None, maxima=None, text=None) -> dict:
-        """{Result name: ask} of the `top_k`, `detections`, `matches`, `keypoints`, `segments`, `maxima` and `text` arguments of a start with `inputs`, {} when nothing
+    def checked(self, inputs, top_k, detections, sharded: bool, matches=None, keypoints=None, segments=None, maxima=None, text=None, boxes=None) -> dict:
+        """{Result name: ask} of the `top_k`, `detections`, `matches`, `keypoints`, `segments`, `maxima`, `text` and `boxes` arguments of a start with `inputs`, {} when nothing
         is asked; ValueError.  Everything is looked up in the network as it was read: no device is needed, nothing is staged, allocated or
         launched.  The checks run in this order, which is not the keywords': matches' own, a tiled or region screen for a Result `top_k`
         names, top_k's, detections', a Result under two of the three, what a tiled, region or fitted screen asks of its feed, keypoints',
-        a Result under keypoints and another, segments', a Result under segments and another, maxima's, a Result under maxima and another, text's, a Result under text and another."""
-        if top_k is detections is matches is keypoints is segments is maxima is text is None:
+        a Result under keypoints and another, segments', a Result under segments and another, maxima's, a Result under maxima and another, text's, a Result under text and another, boxes', a Result under boxes and another, what a fitted input asks of its feed."""
+        if top_k is detections is matches is keypoints is segments is maxima is text is boxes is None:
             return {}
         ex, ienet, asks = self.runner, self.runner.ienet, {}
         matched = gallery_rule.checked(ienet, matches, sharded) if matches is not None else {}
@@ -105,6 +105,18 @@ class Answers:
                 _no_clash('text', read, asks)
             for name, screen in read.items():
                 asks[name] = text_rule.Ask(screen)
+        if boxes is not None:
+            heads = boxes_rule.checked(ienet, boxes, sharded)
+            if asks:
+                _no_clash('boxes', heads, asks)
+            formats = ex.host_inputs.formats
+            for name, screen in heads.items():
+                fmt = formats.get(screen.input)
+                fitted = fmt is not None and fmt.fitted
+                if fitted and isinstance(inputs, dict) and isinstance(inputs.get(screen.input), FrameFeed):     # (detections=' refusal: a geometry per row)
+                    raise ValueError('boxes: input {!r} declares resize_fit {} and is fed a {}: every row has a geometry of its own'.format(
+                        screen.input, fmt.fit, type(inputs[screen.input]).__name__))
+                asks[name] = boxes_rule.Ask(screen, boxes_rule.extent_of(ienet, screen.input), fmt if fitted else None, None, None)
         return asks
 
     def _fitted_input(self):

@@ -1,4 +1,4 @@
-"""What the kinds of answer share (top_k.py, detections.py, tiled_detections.py, gallery.py, keypoints.py, segments.py, maxima.py, text.py; answers.py drives them): the
+"""What the kinds of answer share (top_k.py, detections.py, tiled_detections.py, gallery.py, keypoints.py, segments.py, maxima.py, text.py, boxes.py; answers.py drives them): the
 Ask protocol, the flat block pair an answer of fixed size is read back through, the resolver of the Results an argument names, and
 the min_score check."""
 import ctypes

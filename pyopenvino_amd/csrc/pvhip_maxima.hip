@@ -19,7 +19,7 @@
 //           distinct, so "larger than every neighbour" is: the order word above those of the four neighbours before it in raster order,
 //           not below those of the four behind it.  Outside the plane stands 0, below every order word; a NaN's word is all ones, which
 //           nothing is above and which is never taken.  The 64-bit key is formed for a maximum only.
-//   keep    (keep_add / keep_cut, used by both launches) keys above the floor are appended to a buffer in LDS through an LDS counter.
+//   keep    (keep_add / keep_cut of pvhip_keep.h, used by both launches) keys above the floor are appended to a buffer in LDS through an LDS counter.
 //           No two maxima are neighbours, so a tile adds at most ceil(rows / 2) * ceil(cols / 2) keys; when the next tile could
 //           overflow the buffer it is sorted descending (the bitonic pattern of tiles_frames_kernel, over the next power of two of its
 //           fill) and cut to the M wanted, and the M-th key becomes the floor: later keys that are not above it are skipped.  The keys
@@ -33,6 +33,7 @@
 #include <cstring>
 
 #include "pvhip_common.h"
+#include "pvhip_keep.h"
 #include "pvhip_point_rule.h"
 #include "pvhip_topk_keys.h"
 
@@ -67,43 +68,6 @@ struct RowPlan {
 };
 
 __device__ __forceinline__ unsigned order_word(unsigned bits) { return (unsigned)(topk_key(bits, 0u) >> 32); }
-
-// ---- keep the largest: a buffer `keys` of `cap` keys in LDS, its fill `*count`
-__device__ __forceinline__ void keep_add(unsigned long long* keys, int* count, int cap, unsigned long long key) {
-    const int slot = atomicAdd(count, 1);                       // (LDS)
-    if (slot < cap) keys[slot] = key;                           // (always: the callers cut before a trip could overflow)
-}
-
-// Sorts the buffer descending and cuts it to `keep`: the new floor.  Every thread of the team calls it, behind a barrier that follows the
-// last keep_add; it ends with a barrier.
-template <int TEAM>
-__device__ __forceinline__ unsigned long long keep_cut(unsigned long long* keys, int* count, int cap, int keep, unsigned long long floor) {
-    const int tid = threadIdx.x;
-    const int n = min(*count, cap);                             // (*count itself: see keep_add)
-    if (n > 1) {
-        int sort_n = 2;
-        while (sort_n < n) sort_n <<= 1;
-        for (int i = n + tid; i < sort_n; i += TEAM) keys[i] = 0ull;
-        __syncthreads();
-        for (int k = 2; k <= sort_n; k <<= 1) {
-            for (int j = k >> 1; j > 0; j >>= 1) {
-                for (int i = tid; i < (sort_n >> 1); i += TEAM) {
-                    const int lo = ((i & ~(j - 1)) << 1) | (i & (j - 1)), hi = lo | j;
-                    const unsigned long long u = keys[lo], v = keys[hi];
-                    if (((lo & k) == 0) ? (u < v) : (u > v)) {
-                        keys[lo] = v;
-                        keys[hi] = u;
-                    }
-                }
-                __syncthreads();
-            }
-        }
-    }
-    if (n >= keep) floor = keys[keep - 1];
-    if (tid == 0 && n > keep) *count = keep;
-    __syncthreads();
-    return floor;
-}
 
 // `count` consecutive words of global memory as order words into LDS: 16-byte loads between the run's own 16-byte boundaries.
 template <int TEAM>

@@ -202,11 +202,14 @@ SIGNATURES = {
     'pvhip_heatmap_maxima_f32': (_c.c_int, [_c.c_void_p] + [_c.c_int] * 9 + [_c.c_float] + [_c.c_void_p] * 6),
     'pvhip_ctc_greedy_form': (_c.c_int, [_c.c_int] * 3),
     'pvhip_ctc_greedy_f32': (_c.c_int, [_c.c_void_p] + [_c.c_int] * 6 + [_c.c_void_p] * 5),
+    'pvhip_dense_boxes_form': (_c.c_int, [_c.c_int] * 3),
+    'pvhip_dense_boxes_f32': (_c.c_int, [_c.c_void_p] + [_c.c_int] * 6 + [_c.c_float, _c.c_void_p] + [_c.c_int] * 11 + [_c.c_float] + [_c.c_int] * 2 +
+                              [_c.c_void_p] * 3),
 }
 
 # entry points whose return value is not a status code
 _NOT_STATUS = {'pvhip_host_alloc', 'pvhip_conv2d_stem_direct_pool_supported', 'pvhip_lrn_conv1x1_supported', 'pvhip_conv2d_stem_wino_supported', 'pvhip_conv2d_stem_wino_pack_elems', 'pvhip_maxpool3x3_lrn_conv1x1_c8_supported', 'pvhip_conv2d_f16_stem_direct_supported', 'pvhip_maxpool_lrn_conv1x1_supported', 'pvhip_conv2d_stem_direct_supported', 'pvhip_conv2d_stem_f32_supported', 'pvhip_conv2d_stem_f32_pack_elems', 'pvhip_conv2d_f16_stem_supported', 'pvhip_conv2d_f16_stem_pack_elems', 'pvhip_lrn_maxpool3x3_c8_supported', 'pvhip_conv2d_f16_c8_multi_supported', 'pvhip_c8_f16_elems', 'pvhip_conv2d_f16_c8_supported', 'pvhip_conv2d_f16_c8_pack_elems', 'pvhip_conv2d_f16_pack_elems', 'pvhip_conv2d_f16_dma_supported', 'pvhip_conv2d_f16_span_supported', 'pvhip_conv2d_f16_span_pack_elems', 'pvhip_conv2d_kernel_kind', 'pvhip_abi_version', 'pvhip_last_error', 'pvhip_conv2d_pack_elems', 'pvhip_lrn_maxpool_supported', 'pvhip_maxpool_lrn_supported',
-               'pvhip_conv2d_multi_supported', 'pvhip_conv2d_pooled_supported', 'pvhip_heatmap_peaks_form', 'pvhip_segment_labels_form', 'pvhip_heatmap_maxima_form', 'pvhip_ctc_greedy_form'}
+               'pvhip_conv2d_multi_supported', 'pvhip_conv2d_pooled_supported', 'pvhip_heatmap_peaks_form', 'pvhip_segment_labels_form', 'pvhip_heatmap_maxima_form', 'pvhip_ctc_greedy_form', 'pvhip_dense_boxes_form'}
 
 
 MAX_CONV_DESTS = 6

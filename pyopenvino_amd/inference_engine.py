@@ -313,23 +313,24 @@ class InferRequest:
         `keypoints`    a ``PeakScreen``, a min_score or True                                    ``Keypoints``   keypoints.py
         `segments`     a ``SegmentScreen``, a min_score or True                                 ``Segments``    segments.py
         `maxima`       a ``MaximaScreen``, a min_score or True                                  ``Maxima``      maxima.py
-        `text`         a ``TextScreen`` or True                                                 ``Text``        text.py"""
+        `text`         a ``TextScreen`` or True                                                 ``Text``        text.py
+        `boxes`        a ``BoxScreen``, a min_score or True                                     ``Detections``  boxes.py"""
 
     def __init__(self, owner, runner, index: int):
         self.owner, self.runner, self.index = owner, runner, index      # owner: the network load_network returned
         self._in_flight, self._replayed = False, None
-        self._asks = {}                 # {Result name: ask} of the pass in flight (answers.py): what top_k=, detections=, matches=, keypoints=, segments=, maxima= and text= named
+        self._asks = {}                 # {Result name: ask} of the pass in flight (answers.py): what top_k=, detections=, matches=, keypoints=, segments=, maxima=, text= and boxes= named
 
-    def start_async(self, inputs: dict, top_k=None, detections=None, matches=None, keypoints=None, segments=None, maxima=None, text=None):
-        self._start(inputs, (top_k, detections, matches, keypoints, segments, maxima, text), False)
+    def start_async(self, inputs: dict, top_k=None, detections=None, matches=None, keypoints=None, segments=None, maxima=None, text=None, boxes=None):
+        self._start(inputs, (top_k, detections, matches, keypoints, segments, maxima, text, boxes), False)
 
     def _start(self, inputs, asked, verbose):
-        """`asked`: (top_k, detections, matches, keypoints, segments, maxima, text) as the public signatures took them."""
+        """`asked`: (top_k, detections, matches, keypoints, segments, maxima, text, boxes) as the public signatures took them."""
         if self._in_flight:
             raise RuntimeError('request {} is still in flight: wait() first'.format(self.index))
         ex = self.runner
         sharded = ex.sharded or self.owner.sharded
-        asks = ex.answers.checked(inputs, asked[0], asked[1], sharded, asked[2], asked[3], asked[4], asked[5], asked[6])
+        asks = ex.answers.checked(inputs, asked[0], asked[1], sharded, asked[2], asked[3], asked[4], asked[5], asked[6], asked[7])
         fed, inputs = inputs, ex.host_inputs.stage(inputs, ex.stream_base, sharded)
         self._asks = ex.answers.bound(asks, fed)
         ex.wait_result_readers()
@@ -370,8 +371,8 @@ class InferRequest:
                 G.nodes[nid]['result'] = out[name] = ex._read_back(value, self.owner.comm)
         return out
 
-    def infer(self, inputs: dict, top_k=None, detections=None, matches=None, keypoints=None, segments=None, maxima=None, text=None) -> dict:
-        self.start_async(inputs, top_k, detections, matches, keypoints, segments, maxima, text)
+    def infer(self, inputs: dict, top_k=None, detections=None, matches=None, keypoints=None, segments=None, maxima=None, text=None, boxes=None) -> dict:
+        self.start_async(inputs, top_k, detections, matches, keypoints, segments, maxima, text, boxes)
         return self.wait()
 
     def input_buffer(self, name: str, source_size=None, frames=None) -> np.ndarray:
@@ -554,8 +555,8 @@ class Executable_Network:
                 event.wait()
             device.select_stream(0)
 
-    def start_async(self, request_id: int, inputs: dict, top_k=None, detections=None, matches=None, keypoints=None, segments=None, maxima=None, text=None):
-        self.requests[request_id].start_async(inputs, top_k, detections, matches, keypoints, segments, maxima, text)
+    def start_async(self, request_id: int, inputs: dict, top_k=None, detections=None, matches=None, keypoints=None, segments=None, maxima=None, text=None, boxes=None):
+        self.requests[request_id].start_async(inputs, top_k, detections, matches, keypoints, segments, maxima, text, boxes)
 
     def wait(self, request_id: int) -> dict:
         return self.requests[request_id].wait()
@@ -1066,11 +1067,11 @@ class Executable_Network:
             return None
         return self._graph
 
-    def infer(self, inputs: dict, verbose: bool = False, top_k=None, detections=None, matches=None, keypoints=None, segments=None, maxima=None, text=None) -> dict:
-        """`top_k`, `detections`, `matches`, `keypoints`, `segments`, `maxima`, `text`: the Results they name come back as their answers (InferRequest has the table)."""
-        if not (top_k is detections is matches is keypoints is segments is maxima is text is None):     # something is asked: the pass of request 0 (this network's own graph and streams), waited for at once
+    def infer(self, inputs: dict, verbose: bool = False, top_k=None, detections=None, matches=None, keypoints=None, segments=None, maxima=None, text=None, boxes=None) -> dict:
+        """`top_k`, `detections`, `matches`, `keypoints`, `segments`, `maxima`, `text`, `boxes`: the Results they name come back as their answers (InferRequest has the table)."""
+        if not (top_k is detections is matches is keypoints is segments is maxima is text is boxes is None):     # something is asked: the pass of request 0 (this network's own graph and streams), waited for at once
             request = self.requests[0] if self.requests else InferRequest(self, self, 0)
-            request._start(inputs, (top_k, detections, matches, keypoints, segments, maxima, text), verbose)
+            request._start(inputs, (top_k, detections, matches, keypoints, segments, maxima, text, boxes), verbose)
             return request.wait()
         inputs = self.host_inputs.stage(inputs, self.stream_base, self.sharded)
         self.wait_result_readers()
