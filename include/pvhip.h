@@ -886,6 +886,49 @@ int pvhip_dense_boxes_f32(const float* x, int n, int a, int c, int layout, int o
                           const int* labels, int num_labels, int frame_h, int frame_w, int dx, int dy, int iw, int ih,
                           int min_h, int min_w, int max_candidates, int overlap, float threshold, int per_label, int max_per_image,
                           void* scratch, int* header, int* rows);
+/* Addition to ABI v19 (the version number is unchanged: nothing existing changed): the same call over a head whose anchors carry `tail`
+ * further channels behind the classes (0 <= tail <= 64; mask coefficients, see below): an anchor has 4 + objectness + c + tail numbers
+ * in memory, of which the three launches read the first 4 + objectness + c and step by all of them -- the image stride of
+ * PVHIP_BOXES_LAYOUT_NCA, the row stride of PVHIP_BOXES_LAYOUT_NAC, and again where launch (2) makes the survivors' rectangles.  The rule,
+ * the header, the rows (word 7 stays r * a + i) and the scratch are the entry's above, which is this one with tail = 0;
+ * n * a * (4 + objectness + c + tail) < 2^31; pvhip_dense_boxes_form is asked with the length read, not the stride. */
+int pvhip_dense_boxes_tail_f32(const float* x, int n, int a, int c, int tail, int layout, int objectness, int box, float min_score,
+                               const int* labels, int num_labels, int frame_h, int frame_w, int dx, int dy, int iw, int ih,
+                               int min_h, int min_w, int max_candidates, int overlap, float threshold, int per_label, int max_per_image,
+                               void* scratch, int* header, int* rows);
+
+/* ---------------------------------------------------------------- instance masks ---- */
+/* Addition to ABI v19 (the version number is unchanged: nothing existing changed): the masks of the boxes a pvhip_dense_boxes_tail_f32
+ * call has just kept, from the `tail` = T mask coefficients of their anchors and the T prototype planes of a second tensor `protos`
+ * (n, T, hp, wp) -- what a user of a YOLOv8-seg / v5-seg / YOLACT export makes on the host with sigmoid(coefficients @ prototypes) > 0.5
+ * after reading both tensors back -- so that 4 * ceil(hp * wp / 32) bytes per kept box are read back.  `head` is that call's x with its
+ * n, a, layout and box, e all the numbers of an anchor and tail_at = 4 + objectness + c the first of the tail; `header` and `rows` are
+ * the blocks that call wrote on the same stream.  The rule (pyopenvino_amd/masks.py states the same one in numpy and tests/masks_ref.py
+ * in plain loops, matched bit for bit), for row j of the table, which is image r and anchor i = rows[j][7] - r * a, with m[t] =
+ * v[tail_at + t] the anchor's coefficients and p[t][q] the planes of image r at the flat pixel q = py * wp + px:
+ *   bit     L = fmaf(m[T - 1], p[T - 1][q], ... fmaf(m[0], p[0][q], +0.0f) ...) in fp32, t ascending, one rounding per step, subnormals
+ *           kept.  The bit is L > 0, which is sigmoid(L) > 0.5 without the transcendental.  A detection with a coefficient that is not
+ *           finite has an empty mask; a pixel with any of its T prototype values not finite is 0 in every mask.
+ *   crop    with crop = 1 the bit is also 0 outside the box: xa, xb, ya, yb the fp32 corners of step 2 of the rule above (network
+ *           pixels, before any frame geometry), pixel (px, py) is inside iff xa * wp <= px * wn < xb * wp and ya * hp <= py * hn <
+ *           yb * hp, the four products in binary64, where they are exact (24-bit significands times extents of at most 2^24); no
+ *           comparison with a NaN corner holds.  crop = 0 skips this.
+ *   layout  `words`: row j is W32 = ceil(hp * wp / 32) uint32 words, pixel q bit q & 31 (least significant first) of word q >> 5; bits
+ *           at and beyond hp * wp are 0.  Rows at and beyond total are not written; room for n * max_per_image * W32 words.
+ * One launch on the current stream, no host read in between: a workgroup finds its image's first row by summing counts[0 .. r).  The
+ * prototypes are the B operand of v_mfma_f32_32x32x2_f32 (32 consecutive flat pixels a column block), read from memory once per image
+ * and kept in registers, PVHIP_MASKS_GROUPS groups of 32 pixels per wave; the coefficients, gathered by rows[][7], are staged in LDS
+ * PVHIP_MASKS_STAGE detections at a time with each detection's integer crop window; one accumulator tile per (32 detections, 32 pixels)
+ * is the rule's chain; a wave-wide ballot per tile register gives the finished words of two detections.  No word is written twice, no
+ * atomics, the same bits every call.  `protos` may be only 4-byte aligned.
+ * 1 <= tail <= 64, 4 <= tail_at, tail_at + tail <= e, n * a * e < 2^31, 1 <= n <= 65535, 2 <= hp * wp <= 2^24, hn, wn in 1 .. 2^24,
+ * crop 0 or 1, 1 <= max_per_image <= PVHIP_BOXES_MAX_CANDIDATES, n * max_per_image * W32 <= 2^26, no NULL or misaligned pointer (rows
+ * 16-byte, the others 4-byte); else PVHIP_EINVAL and nothing is launched. */
+#define PVHIP_MASKS_GROUPS           4
+#define PVHIP_MASKS_STAGE            128
+int pvhip_instance_masks_f32(const float* head, int n, int a, int e, int layout, int tail_at, int tail, int box,
+                             const float* protos, int hp, int wp, int hn, int wn, int crop, int max_per_image,
+                             const int* header, const int* rows, unsigned* words);
 
 /* ---------------------------------------------------------------- a detector's answer ------ */
 /* Addition to ABI v18 (the version number is unchanged: nothing existing changed): the records of pvhip_detection_output_f32 become one

@@ -1,16 +1,16 @@
-"""Answers behind the pass: the Results a start named with ``top_k=``, ``detections=``, ``matches=``, ``keypoints=``, ``segments=``, ``maxima=``, ``text=`` or ``boxes=`` come back from
-wait() as a ``TopK``, a ``Detections``, a ``Matches``, a ``Keypoints``, a ``Segments``, a ``Maxima``, a ``Text`` or (a dense head's) a ``Detections`` made on the device instead of as the tensor.  One ``Answers`` per
+"""Answers behind the pass: the Results a start named with ``top_k=``, ``detections=``, ``matches=``, ``keypoints=``, ``segments=``, ``maxima=``, ``text=``, ``boxes=`` or ``masks=`` come back from
+wait() as a ``TopK``, a ``Detections``, a ``Matches``, a ``Keypoints``, a ``Segments``, a ``Maxima``, a ``Text``, (a dense head's) a ``Detections`` or (its prototype Result's) a ``Masks`` made on the device instead of as the tensor.  One ``Answers`` per
 Executable_Network (one per request), as ``HostInputs`` is on the way in: the request checks the arguments, binds the asks to the staged
 inputs, launches behind the pass and reads after it.
 
 An ask is one Result's question in its resolved form, an ``ask.Ask`` (ask.py states the protocol: KEYWORD, `bound`, `key`, `launch`,
-`on_host`): top_k.Ask, detections.Ask / FittedAsk, tiled_detections.Ask / RegionAsk, gallery.Ask, keypoints.Ask, segments.Ask, maxima.Ask, text.Ask or boxes.Ask.  Which kind it is
+`on_host`): top_k.Ask, detections.Ask / FittedAsk, tiled_detections.Ask / RegionAsk, gallery.Ask, keypoints.Ask, segments.Ask, maxima.Ask, text.Ask, boxes.Ask or masks.Ask.  Which kind it is
 matters only where checked() makes it; the rule of each kind, its argument's forms and its refusals are stated in its module.  A plain
 screen over a detector whose input declares a fit (preprocess_info.resize_fit) learns its geometry in bound(), from the extent of the
 frames the pass was fed, and so does a BoxScreen over such an input."""
 import numpy as np
 
-from . import boxes as boxes_rule, detections as detections_rule, device, gallery as gallery_rule, keypoints as keypoints_rule, maxima as maxima_rule, segments as segments_rule, \
+from . import boxes as boxes_rule, detections as detections_rule, device, gallery as gallery_rule, keypoints as keypoints_rule, masks as masks_rule, maxima as maxima_rule, segments as segments_rule, \
     text as text_rule, tiled_detections as tiled_rule, top_k as top_k_rule
 from .input_format import FrameFeed
 
@@ -26,7 +26,7 @@ def _no_clash(keyword: str, names, asks: dict, screens=()):
 
 class Answers:
     """`blocks` = {ask.key(Result name): its Blocks}, this request's own device and page-locked blocks, made on first use: (name, k),
-    (name, resolved DetectionScreen), (name, resolved TiledScreen or RegionScreen, m), (name, id of the Gallery, k), (name, refine, space), of a class map (name,), of local maxima (name, max_per_plane, max_per_row, refine, space), of a decoded text (name, layout) or, of a dense head's boxes, (name, the BoxScreen without min_score and frame_size)."""
+    (name, resolved DetectionScreen), (name, resolved TiledScreen or RegionScreen, m), (name, id of the Gallery, k), (name, refine, space), of a class map (name,), of local maxima (name, max_per_plane, max_per_row, refine, space), of a decoded text (name, layout) or, of a dense head's boxes, (name, the BoxScreen without min_score and frame_size) and, of its masks, (prototype Result, head, that BoxScreen)."""
 
     def __init__(self, runner):
         self.runner, self.blocks = runner, {}       # runner: the Executable_Network whose base stream and Results these are
@@ -34,13 +34,13 @@ class Answers:
     def release(self):
         self.blocks = {}
 
-    def checked(self, inputs, top_k, detections, sharded: bool, matches=None, keypoints=None, segments=None, maxima=None, text=None, boxes=None) -> dict:
-        """{Result name: ask} of the `top_k`, `detections`, `matches`, `keypoints`, `segments`, `maxima`, `text` and `boxes` arguments of a start with `inputs`, {} when nothing
+    def checked(self, inputs, top_k, detections, sharded: bool, matches=None, keypoints=None, segments=None, maxima=None, text=None, boxes=None, masks=None) -> dict:
+        """{Result name: ask} of the `top_k`, `detections`, `matches`, `keypoints`, `segments`, `maxima`, `text`, `boxes` and `masks` arguments of a start with `inputs`, {} when nothing
         is asked; ValueError.  Everything is looked up in the network as it was read: no device is needed, nothing is staged, allocated or
         launched.  The checks run in this order, which is not the keywords': matches' own, a tiled or region screen for a Result `top_k`
         names, top_k's, detections', a Result under two of the three, what a tiled, region or fitted screen asks of its feed, keypoints',
-        a Result under keypoints and another, segments', a Result under segments and another, maxima's, a Result under maxima and another, text's, a Result under text and another, boxes', a Result under boxes and another, what a fitted input asks of its feed."""
-        if top_k is detections is matches is keypoints is segments is maxima is text is boxes is None:
+        a Result under keypoints and another, segments', a Result under segments and another, maxima's, a Result under maxima and another, text's, a Result under text and another, boxes', a Result under boxes and another, what a fitted input asks of its feed, masks', a Result under masks and another."""
+        if top_k is detections is matches is keypoints is segments is maxima is text is boxes is masks is None:
             return {}
         ex, ienet, asks = self.runner, self.runner.ienet, {}
         matched = gallery_rule.checked(ienet, matches, sharded) if matches is not None else {}
@@ -117,6 +117,12 @@ class Answers:
                     raise ValueError('boxes: input {!r} declares resize_fit {} and is fed a {}: every row has a geometry of its own'.format(
                         screen.input, fmt.fit, type(inputs[screen.input]).__name__))
                 asks[name] = boxes_rule.Ask(screen, boxes_rule.extent_of(ienet, screen.input), fmt if fitted else None, None, None)
+        if masks is not None:
+            heads = {name: a.screen for name, a in asks.items() if isinstance(a, boxes_rule.Ask)}
+            planes = masks_rule.checked(ienet, masks, heads, sharded)
+            _no_clash('masks', planes, asks)
+            for name, (screen, head, shape) in planes.items():
+                asks[name] = masks_rule.Ask(screen, head, asks[screen.head].net_hw, shape)
         return asks
 
     def _fitted_input(self):
@@ -135,21 +141,23 @@ class Answers:
         every kind -- that left `values` = {Result name: tensor}, and behind the tile table stage() uploaded on that stream; wait_done()
         then waits for one event behind them all.  A Result that is a host array gets the rule in numpy when it is read."""
         ex = self.runner
-        on_device = [(name, ask) for name, ask in asks.items() if isinstance(values[name], device.DeviceTensor)]
+        on_device = [(name, ask) for name, ask in asks.items() if all(isinstance(values[o], device.DeviceTensor) for o in (name,) + tuple(ask.needs))]
         if not on_device:
             return
         device.select_stream(ex.stream_base)
-        for name, ask in on_device:
+        for name, ask in sorted(on_device, key=lambda item: bool(item[1].needs)):  # (stable: an ask that needs others stands behind them)
             key = ask.key(name)
-            self.blocks[key] = ask.launch(self.blocks.get(key), values[name])      # (made on first use)
+            others = [(asks[o], values[o], self.blocks[asks[o].key(o)]) for o in ask.needs]
+            self.blocks[key] = ask.launch(self.blocks.get(key), values[name], *others)      # (made on first use)
         ex._pending = (ex._pending[0] if ex._pending is not None else None, ex._order_event().record())
         device.select_stream(0)
 
-    def read(self, name: str, ask, value):
+    def read(self, name: str, ask, value, others=()):
         """The answer of Result `name` after wait_done(): read back from the blocks launch() filled, on the drained base stream; the rule
-        in numpy -- a tiled one on the slot's page-locked table -- for a Result that is a host array."""
-        if not isinstance(value, device.DeviceTensor):
-            return ask.on_host(np.asarray(value))
+        in numpy -- a tiled one on the slot's page-locked table -- for a Result that is a host array.  `others`: (ask, value) of every
+        Result in `ask.needs`; when any of them or `value` is a host array the rule runs in numpy on all, those on the device read back first."""
+        if not all(isinstance(v, device.DeviceTensor) for v in (value,) + tuple(v for _, v in others)):
+            return ask.on_host(np.asarray(value), *[(a, np.asarray(v), None) for a, v in others])
         device.select_stream(self.runner.stream_base)
         out = self.blocks[ask.key(name)].read_back()
         device.select_stream(0)

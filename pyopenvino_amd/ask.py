@@ -1,4 +1,4 @@
-"""What the kinds of answer share (top_k.py, detections.py, tiled_detections.py, gallery.py, keypoints.py, segments.py, maxima.py, text.py, boxes.py; answers.py drives them): the
+"""What the kinds of answer share (top_k.py, detections.py, tiled_detections.py, gallery.py, keypoints.py, segments.py, maxima.py, text.py, boxes.py, masks.py; answers.py drives them): the
 Ask protocol, the flat block pair an answer of fixed size is read back through, the resolver of the Results an argument names, and
 the min_score check."""
 import ctypes
@@ -15,9 +15,12 @@ class Ask:
     that an ask equals the plain tuple of its fields.  A kind states KEYWORD, the argument of infer() / start_async() it came from;
     `key(name)`, the key of its blocks among the request's; `blocks_for(value)`, new blocks for the value a pass left on the device;
     `launch_with()`, what its blocks' launch takes besides that value; `on_host(value)`, the rule in numpy on a host value; and
-    `bound`, when it learns something from the inputs a pass was fed."""
+    `bound`, when it learns something from the inputs a pass was fed.  `needs` lists the other Results of the same start that the
+    ask reads besides its own: answers.py launches it behind their asks and hands its `launch` and `on_host` one (ask, value, blocks)
+    per name (masks.py's ask reads the head's tensor and the table its boxes ask has just written)."""
     __slots__ = ()
     KEYWORD = None
+    needs = ()
 
     def bound(self, inputs, slots):         # (the ask for the pass whose `inputs`, as they were fed, are staged in `slots`)
         return self
@@ -25,9 +28,9 @@ class Ask:
     def launch_with(self) -> tuple:
         return ()
 
-    def launch(self, blocks, value):
+    def launch(self, blocks, value, *others):
         """The launches on the current stream, behind whatever wrote `value` there, into `blocks` -- or into new ones for None --: the
-        blocks."""
+        blocks.  `others`: (ask, value, blocks) of every Result in `needs`, already launched on this stream."""
         blocks = blocks or self.blocks_for(value)
         blocks.launch(value, *self.launch_with())
         return blocks

@@ -31,8 +31,8 @@ channel values e[0 .. E - 1]:
 Where this differs from Ultralytics' post-processing: suppression runs on the integer frame rectangles, not on float network boxes; an
 anchor has one class, its best, and never yields several candidates (no multi_label); class-aware suppression is by equality of the labels,
 not by offsetting the coordinates per class.  Out of scope: several Results of one detector merged (v3 / v4 per-scale grids with anchors
-and sigmoid / exp decoding, RegionYolo), multi-label candidates, normalised box units, rotated boxes, mask coefficients and keypoint
-channels, FP16 Results, K above 4096, merging across tiles or regions, a RoiInput feed on a fitted input."""
+and sigmoid / exp decoding, RegionYolo), multi-label candidates, normalised box units, rotated boxes, keypoint channels (mask
+coefficients ride in `tail`, which this rule steps over: masks.py), FP16 Results, K above 4096, merging across tiles or regions, a RoiInput feed on a fitted input."""
 import collections
 import ctypes
 
@@ -43,12 +43,13 @@ from .detections import Detections
 from .tiled_detections import OVERLAPS, _overlap
 
 MAX_CANDIDATES = 4096                           # PVHIP_BOXES_MAX_CANDIDATES
+MAX_TAIL = 64
 LAYOUTS = {'NCA': 0, 'NAC': 1}                  # PVHIP_BOXES_LAYOUT_*
 BOXES = {'CXCYWH': 0, 'XYXY': 1}                # PVHIP_BOXES_*
 FORM_NONE, FORM_PLANES, FORM_ROWS_TEAM, FORM_ROWS_WAVE = 0, 1, 2, 3      # PVHIP_BOXES_FORM_*
 
 _Screen = collections.namedtuple('BoxScreen', 'min_score layout objectness box frame_size labels min_size max_candidates overlap threshold '
-                                              'per_label max_per_image input')
+                                              'per_label max_per_image input tail')
 
 
 class BoxScreen(_Screen):
@@ -58,14 +59,28 @@ class BoxScreen(_Screen):
     = (H, W) (None: the network's extent, or that of the host frames a fitted input was fed); `labels`: None (any) or at most 64 class
     indices; rectangles of at least `min_size` = (h, w); the `max_candidates` = K <= 4096 best per image are suppressed greedily by
     `overlap` 'IOU' or 'IOS' above `threshold`, among equal classes when `per_label`; at most `max_per_image` (None: K) per image;
-    `input` names the 4-D Parameter when the network has several.  Immutable; checked when a pass is started with it (ValueError)."""
+    `input` names the 4-D Parameter when the network has several; `tail` = T in 0 .. 64: an anchor carries T further channels behind its
+    classes, E = 4 + O + C + T, which play no part in the rule (the mask coefficients of a segmentation head: masks.py reads them).
+    Immutable; checked when a pass is started with it (ValueError).  A screen without a tail equals the plain tuple of the fields in
+    front of `tail`, as it did before there was one; its hash stays the 14-tuple's, so towards such a plain 13-tuple the rule that
+    equal objects hash alike is knowingly not kept: do not key a dict by both."""
     __slots__ = ()
 
     def __new__(cls, min_score=0.25, layout=None, objectness=False, box='CXCYWH', frame_size=None, labels=None, min_size=(1, 1),
-                max_candidates=1024, overlap='IOU', threshold=0.45, per_label=True, max_per_image=None, input=None):
+                max_candidates=1024, overlap='IOU', threshold=0.45, per_label=True, max_per_image=None, input=None, tail=0):
         frozen = [detections._frozen(v) for v in (frame_size, labels, min_size)]
         return super().__new__(cls, min_score, layout, objectness, box, frozen[0], frozen[1], frozen[2], max_candidates, overlap, threshold,
-                               per_label, max_per_image, input)
+                               per_label, max_per_image, input, tail)
+
+    def __eq__(self, other):
+        if type(other) is tuple and len(other) == len(self) - 1:
+            return self[-1] == 0 and self[:-1] == other
+        return tuple.__eq__(self, other)
+
+    def __ne__(self, other):
+        return not self == other
+
+    __hash__ = tuple.__hash__
 
 
 class AmbiguousLayout(ValueError):
@@ -82,7 +97,7 @@ def resolved(value, what='boxes') -> BoxScreen:
         value = BoxScreen(value)
     if not isinstance(value, BoxScreen):
         raise ValueError('{}: a BoxScreen, a min_score or True, got {!r}'.format(what, value))
-    min_score, layout, objectness, box, frame, labels, size, cand, overlap, threshold, per_label, cap, name = value
+    min_score, layout, objectness, box, frame, labels, size, cand, overlap, threshold, per_label, cap, name, tail = value
     if min_score is None:
         raise ValueError('{}: min_score is a finite real (of float32), got None'.format(what))
     min_score = ask.checked_min_score(min_score, what)
@@ -113,12 +128,14 @@ def resolved(value, what='boxes') -> BoxScreen:
         cap = cand
     if not detections._count(cap, int(cand)):
         raise ValueError('{}: max_per_image is None or a count in 1 .. max_candidates = {}, got {!r}'.format(what, cand, cap))
+    if isinstance(tail, bool) or not isinstance(tail, (int, np.integer)) or not 0 <= tail <= MAX_TAIL:
+        raise ValueError('{}: tail is an int in 0 .. {}, got {!r}'.format(what, MAX_TAIL, tail))
     return BoxScreen(min_score, layout, bool(objectness), box, None if frame is None else (int(frame[0]), int(frame[1])), labels,
-                     (int(size[0]), int(size[1])), int(cand), overlap, float(np.float32(threshold)), bool(per_label), int(cap), name)
+                     (int(size[0]), int(size[1])), int(cand), overlap, float(np.float32(threshold)), bool(per_label), int(cap), name, int(tail))
 
 
-def shape_of(dims, layout=None, objectness=False, batch=None):
-    """(layout, n, A, C) of a tensor declared as a dense head -- rank 3, E = 4 + O + C channels with C >= 1, A >= 1, n * A * E < 2^31, n
+def shape_of(dims, layout=None, objectness=False, batch=None, tail=0):
+    """(layout, n, A, C) of a tensor declared as a dense head -- rank 3, E = 4 + O + C + `tail` channels with C >= 1, A >= 1, n * A * E < 2^31, n
     the batch (when given) --, else None.  `layout` None infers it: 'NCA' when dims[1] < dims[2], 'NAC' when dims[1] > dims[2];
     AmbiguousLayout, a ValueError, when they are equal."""
     dims = tuple(int(d) for d in dims)
@@ -129,7 +146,7 @@ def shape_of(dims, layout=None, objectness=False, batch=None):
             raise AmbiguousLayout('shape {} reads as \'NCA\' and as \'NAC\': say which with BoxScreen(layout=...)'.format(dims))
         layout = 'NCA' if dims[1] < dims[2] else 'NAC'
     n, A, E = (dims[0], dims[2], dims[1]) if layout == 'NCA' else dims
-    C = E - 4 - int(bool(objectness))
+    C = E - 4 - int(bool(objectness)) - int(tail)
     if n < 1 or A < 1 or C < 1 or n * A * E >= 1 << 31 or (batch is not None and n != int(batch)):
         return None
     return layout, n, A, C
@@ -150,12 +167,12 @@ def decode(x, screen, net_hw, fit=None) -> Detections:
     screen = resolved(screen, 'decode')
     x = np.asarray(x)
     try:
-        shape = shape_of(x.shape, screen.layout, screen.objectness)
+        shape = shape_of(x.shape, screen.layout, screen.objectness, None, screen.tail)
     except AmbiguousLayout as e:
         raise ValueError('decode: {}'.format(e)) from None
     if x.dtype != np.float32 or shape is None:
-        raise ValueError('decode takes float32 numbers of rank 3 with E = 4 + objectness + C channels, C >= 1 and n * A * E < 2^31, got {} {}'.format(
-            x.dtype, x.shape))
+        raise ValueError('decode takes float32 numbers of rank 3 with E = 4 + objectness + C{} channels, C >= 1 and n * A * E < 2^31, got {} {}'.format(
+            _tail_text(screen.tail), x.dtype, x.shape))
     if not detections._pair(tuple(net_hw), detections.MAX_EXTENT):
         raise ValueError('decode: net_hw is (Hn, Wn) with both in 1 .. 2^24, got {!r}'.format(net_hw))
     Hn, Wn = (int(v) for v in net_hw)
@@ -164,7 +181,7 @@ def decode(x, screen, net_hw, fit=None) -> Detections:
     fh, fw = screen.frame_size or (Hn, Wn)
     O = int(screen.objectness)
     v = x.transpose(0, 2, 1) if layout == 'NCA' else x                                   # (n, A, E)
-    w, score = _winners(v[:, :, 4 + O:])
+    w, score = _winners(v[:, :, 4 + O:4 + O + C])                                        # (the tail plays no part)
     with np.errstate(invalid='ignore', over='ignore', under='ignore'):
         if O:
             score = v[:, :, 4] * score                                                       # one float32 product
@@ -232,16 +249,25 @@ def checked_fit(fit, what='decode'):
 SHAPE = 'rank 3 with the batch n = {} first, E = 4 + objectness + C channels, C >= 1 and n * A * E < 2^31'
 
 
+def _tail_text(tail):
+    return ' + tail = {}'.format(tail) if tail else ''
+
+
+def _shape_text(tail):
+    """SHAPE, with the tail named when there is one."""
+    return SHAPE.replace(' + C channels', ' + C' + _tail_text(tail) + ' channels')
+
+
 def _fits(port, screen, batch):
     try:
-        return port['precision'] == 'FP32' and shape_of(port['dims'], screen.layout, screen.objectness, batch) is not None
+        return port['precision'] == 'FP32' and shape_of(port['dims'], screen.layout, screen.objectness, batch, screen.tail) is not None
     except AmbiguousLayout:
         return False
 
 
 def _none_fits(ports, screen, batch):
     return 'boxes: no FP32 Result of {}{} (the Results: {})'.format(
-        SHAPE.format(batch), ' whose layout can be inferred' if screen.layout is None else ' as {!r}'.format(screen.layout),
+        _shape_text(screen.tail).format(batch), ' whose layout can be inferred' if screen.layout is None else ' as {!r}'.format(screen.layout),
         {name: tuple(port['dims']) for name, port in ports.items()})
 
 
@@ -278,10 +304,10 @@ def checked(ienet, boxes, sharded: bool) -> dict:
     for name, screen in wanted.items():
         what = 'boxes: Result {!r}'.format(name)
         try:
-            shape = shape_of(ports[name]['dims'], screen.layout, screen.objectness, batch)
+            shape = shape_of(ports[name]['dims'], screen.layout, screen.objectness, batch, screen.tail)
         except AmbiguousLayout as e:
             raise ValueError('{}: {}'.format(what, e)) from None
-        expected = SHAPE + (' as {!r}'.format(screen.layout) if screen.layout is not None else '')
+        expected = _shape_text(screen.tail) + (' as {!r}'.format(screen.layout) if screen.layout is not None else '')
         layout = ask.declared('boxes', name, ports[name], shape, expected, batch)[0]
         wanted[name] = screen._replace(layout=layout, input=checked_input(ienet, screen, what))
     return wanted
@@ -297,7 +323,7 @@ class Blocks(detections.TableBlocks):
     their page-locked twins, the labels on the device, and `scratch`, the keys, winners and staging rows between the entry's three
     launches, which stay on the device.  read_back is TableBlocks': the header, 4 (2 n + 1) bytes, then exactly 32 total bytes."""
     __slots__ = ('n', 'A', 'scratch')
-    ENTRY = 'pvhip_dense_boxes_f32'
+    ENTRY, TAIL_ENTRY = 'pvhip_dense_boxes_f32', 'pvhip_dense_boxes_tail_f32'
 
     def __init__(self, n: int, A: int, screen: BoxScreen):
         super().__init__(n, n * screen.max_per_image, screen)
@@ -308,12 +334,16 @@ class Blocks(detections.TableBlocks):
         """One call (three launches) on the current stream, behind whatever wrote `result` there, over frames of `frame_size` that stand
         in the rectangle `fit` = (dx, dy, iw, ih) of the network's input."""
         s = self.screen
-        layout, n, A, C = shape_of(result.shape, s.layout, s.objectness)
+        layout, n, A, C = shape_of(result.shape, s.layout, s.objectness, None, s.tail)
         assert (n, A) == (self.n, self.A) and result.dtype == np.float32
-        device.call(self.ENTRY, device.ptr(result), n, A, C, LAYOUTS[layout], int(s.objectness), BOXES[s.box], min_score, device.ptr(self.labels),
-                    0 if s.labels is None else len(s.labels), frame_size[0], frame_size[1], fit[0], fit[1], fit[2], fit[3], s.min_size[0],
-                    s.min_size[1], s.max_candidates, OVERLAPS[s.overlap], s.threshold, int(s.per_label), s.max_per_image,
-                    ctypes.c_void_p(self.scratch.ptr), ctypes.c_void_p(self.header.ptr), ctypes.c_void_p(self.rows.ptr))
+        rest = (LAYOUTS[layout], int(s.objectness), BOXES[s.box], min_score, device.ptr(self.labels),
+                0 if s.labels is None else len(s.labels), frame_size[0], frame_size[1], fit[0], fit[1], fit[2], fit[3], s.min_size[0],
+                s.min_size[1], s.max_candidates, OVERLAPS[s.overlap], s.threshold, int(s.per_label), s.max_per_image,
+                ctypes.c_void_p(self.scratch.ptr), ctypes.c_void_p(self.header.ptr), ctypes.c_void_p(self.rows.ptr))
+        if s.tail:                              # (the channels behind the classes are stepped over)
+            device.call(self.TAIL_ENTRY, device.ptr(result), n, A, C, s.tail, *rest)
+        else:
+            device.call(self.ENTRY, device.ptr(result), n, A, C, *rest)
 
 
 class Ask(ask.Ask, collections.namedtuple('Ask', 'screen net_hw format frame_size fit')):
@@ -341,7 +371,7 @@ class Ask(ask.Ask, collections.namedtuple('Ask', 'screen net_hw format frame_siz
         return (name, self.screen._replace(min_score=None, frame_size=None))
 
     def blocks_for(self, value):
-        _, n, A, _ = shape_of(value.shape, self.screen.layout, self.screen.objectness)
+        _, n, A, _ = shape_of(value.shape, self.screen.layout, self.screen.objectness, None, self.screen.tail)
         return Blocks(n, A, self.screen._replace(min_score=None, frame_size=None))
 
     def launch_with(self):

@@ -28,6 +28,12 @@
 //           staging rows in their final form, the counts to the header.
 //   write   one wave per image, behind the images launch so every count is there: base = counts[0] + .. + counts[r - 1] (lane-strided
 //           loads, a wave reduction); the image's rows are copied to rows base .. in 16-byte pieces.  The last image's wave writes total.
+//
+// A head with a tail (pvhip_dense_boxes_tail_f32): an anchor carries `tail` further numbers behind its classes -- the mask coefficients
+// of a segmentation head, which pvhip_masks.hip reads.  Head.e stays the length that is read, 4 + objectness + c, and decides the form;
+// Head.es = e + tail is the step: the image stride of the planes form, the row stride of the rows forms (the row's 16-byte split is made
+// of the e numbers read, so no load touches the tail), and the stride by which launch 2 finds a survivor's numbers again.  With tail = 0
+// the two are equal and every address is the one it was.
 #include <cstring>
 
 #include "pvhip_common.h"
@@ -42,6 +48,7 @@ namespace {
 constexpr int kQuad        = 4;                                   // anchors per lane of the planes form
 constexpr int kTeam        = 16;                                  // lanes of a team of the short-row form
 constexpr int kMaxLabels   = 64;
+constexpr int kMaxTail     = 64;                                  // channels behind the classes that no launch reads
 constexpr int kMaxExtent   = 1 << 24;
 constexpr int kMaxCand     = PVHIP_BOXES_MAX_CANDIDATES;
 constexpr int kImageBlock  = 1024;                                // lanes of an image's workgroup
@@ -63,7 +70,8 @@ struct BoxRule {
 
 struct Head {
     const unsigned* x;
-    int n, a, c, e, layout;        // e = 4 + objectness + c
+    int n, a, c, e, layout;        // e = 4 + objectness + c, the numbers of an anchor that are read
+    int es;                        // the numbers of an anchor in memory: e and the tail that no launch here reads
 };
 
 struct Rect {
@@ -109,7 +117,7 @@ __device__ __forceinline__ bool anchor_in(const BoxRule& g, float b0, float b1, 
 __device__ __forceinline__ bool anchor_at(const Head& t, const BoxRule& g, int r, int i, int k, unsigned& score_bits, Rect& rect) {
     const bool   planes = t.layout == PVHIP_BOXES_LAYOUT_NCA;
     const size_t step   = planes ? (size_t)t.a : (size_t)1;
-    const unsigned* at  = t.x + (planes ? (size_t)r * t.e * (size_t)t.a + i : ((size_t)r * t.a + i) * (size_t)t.e);
+    const unsigned* at  = t.x + (planes ? (size_t)r * t.es * (size_t)t.a + i : ((size_t)r * t.a + i) * (size_t)t.es);
     const int first = 4 + g.objectness;
     const float obj = g.objectness ? __uint_as_float(at[4 * step]) : 0.0f;
     return anchor_in(g, __uint_as_float(at[0]), __uint_as_float(at[step]), __uint_as_float(at[2 * step]), __uint_as_float(at[3 * step]), obj,
@@ -148,7 +156,7 @@ __global__ __launch_bounds__(kBlock) void boxes_planes_kernel(Head t, BoxRule g,
     const int    r    = (int)(j / quads);
     const int    i0   = kQuad * (int)(j - (long long)r * quads);
     const size_t a    = (size_t)t.a;
-    const unsigned* at = t.x + (size_t)r * t.e * a + i0;
+    const unsigned* at = t.x + (size_t)r * t.es * a + i0;
     const int live = min(kQuad, t.a - i0);
     const F4 b0 = load_quad(at, live), b1 = load_quad(at + a, live), b2 = load_quad(at + 2 * a, live), b3 = load_quad(at + 3 * a, live);
     F4 obj{0u, 0u, 0u, 0u};
@@ -205,7 +213,7 @@ __device__ __forceinline__ unsigned long long team_max_u64(unsigned long long v)
     return v;
 }
 
-// Memory row m of n * a rows of e numbers: anchor m % a of image m / a.
+// Memory row m of n * a rows of es numbers, the first e of them read: anchor m % a of image m / a.
 template <int TEAM>
 __global__ __launch_bounds__(kBlock) void boxes_rows_kernel(Head t, BoxRule g, int rows, unsigned long long* __restrict__ keys,
                                                             int* __restrict__ winners) {
@@ -213,7 +221,7 @@ __global__ __launch_bounds__(kBlock) void boxes_rows_kernel(Head t, BoxRule g, i
     const int lane = threadIdx.x & (TEAM - 1);
     const int e = t.e, first = 4 + g.objectness;
     for (int m = blockIdx.x * kTeams + (int)threadIdx.x / TEAM; m < rows; m += gridDim.x * kTeams) {     // (the whole team: no barrier below)
-        const unsigned* row = t.x + (size_t)m * e;
+        const unsigned* row = t.x + (size_t)m * t.es;
         // head | body of 16-byte pieces | tail
         const int head = min(e, (int)(((16u - (unsigned)((uintptr_t)row & 15u)) & 15u) >> 2));
         const int npiece = (e - head) >> 2, tail = (e - head) & 3;
@@ -430,19 +438,20 @@ extern "C" {
 
 int pvhip_dense_boxes_form(int layout, int a, int e) { return boxes_form(layout, a, e); }
 
-int pvhip_dense_boxes_f32(const float* x, int n, int a, int c, int layout, int objectness, int box, float min_score,
-                          const int* labels, int num_labels, int frame_h, int frame_w, int dx, int dy, int iw, int ih,
-                          int min_h, int min_w, int max_candidates, int overlap, float threshold, int per_label, int max_per_image,
-                          void* scratch, int* header, int* rows) {
+int pvhip_dense_boxes_tail_f32(const float* x, int n, int a, int c, int tail, int layout, int objectness, int box, float min_score,
+                               const int* labels, int num_labels, int frame_h, int frame_w, int dx, int dy, int iw, int ih,
+                               int min_h, int min_w, int max_candidates, int overlap, float threshold, int per_label, int max_per_image,
+                               void* scratch, int* header, int* rows) {
     PVHIP_REQUIRE_INIT();
     PVHIP_CHECK_ARG(x != nullptr && scratch != nullptr && header != nullptr && rows != nullptr);
     PVHIP_CHECK_ARG(((uintptr_t)x & 3u) == 0 && ((uintptr_t)header & 3u) == 0 && ((uintptr_t)labels & 3u) == 0);
     PVHIP_CHECK_ARG(((uintptr_t)rows & 15u) == 0 && ((uintptr_t)scratch & 15u) == 0);
     PVHIP_CHECK_ARG(n >= 1 && a >= 1 && c >= 1);
     PVHIP_CHECK_ARG(objectness == 0 || objectness == 1);
-    PVHIP_CHECK_ARG((long long)n * a * (4LL + objectness + c) < (1LL << 31));
+    PVHIP_CHECK_ARG(tail >= 0 && tail <= kMaxTail);
+    PVHIP_CHECK_ARG((long long)n * a * (4LL + objectness + c + tail) < (1LL << 31));
     const int e = 4 + objectness + c;
-    const int form = boxes_form(layout, a, e);
+    const int form = boxes_form(layout, a, e);                                  // (of the length read, not of the stride)
     PVHIP_CHECK_ARG(form != PVHIP_BOXES_FORM_NONE);                              // layout one of the two
     PVHIP_CHECK_ARG(box == PVHIP_BOXES_CXCYWH || box == PVHIP_BOXES_XYXY);
     PVHIP_CHECK_ARG(min_score - min_score == 0.0f);                              // finite
@@ -456,7 +465,7 @@ int pvhip_dense_boxes_f32(const float* x, int n, int a, int c, int layout, int o
     PVHIP_CHECK_ARG(threshold >= 0.0f && threshold <= 1.0f);                    // (false for NaN)
     PVHIP_CHECK_ARG(per_label == 0 || per_label == 1);
 
-    const Head    t{reinterpret_cast<const unsigned*>(x), n, a, c, e, layout};
+    const Head    t{reinterpret_cast<const unsigned*>(x), n, a, c, e, layout, e + tail};
     const BoxRule g{labels, num_labels, objectness, box, min_score, frame_h, frame_w, dx, dy, iw, ih, min_h, min_w};
     const size_t  anchors = (size_t)n * (size_t)a;
     char* const   base    = static_cast<char*>(scratch);
@@ -492,6 +501,14 @@ int pvhip_dense_boxes_f32(const float* x, int n, int a, int c, int layout, int o
                        staging, n, max_per_image, header, reinterpret_cast<int4*>(rows));
     PVHIP_LAUNCH_CHECK();
     return PVHIP_OK;
+}
+
+int pvhip_dense_boxes_f32(const float* x, int n, int a, int c, int layout, int objectness, int box, float min_score,
+                          const int* labels, int num_labels, int frame_h, int frame_w, int dx, int dy, int iw, int ih,
+                          int min_h, int min_w, int max_candidates, int overlap, float threshold, int per_label, int max_per_image,
+                          void* scratch, int* header, int* rows) {
+    return pvhip_dense_boxes_tail_f32(x, n, a, c, 0, layout, objectness, box, min_score, labels, num_labels, frame_h, frame_w, dx, dy, iw, ih,
+                                      min_h, min_w, max_candidates, overlap, threshold, per_label, max_per_image, scratch, header, rows);
 }
 
 }  // extern "C"

@@ -205,6 +205,9 @@ SIGNATURES = {
     'pvhip_dense_boxes_form': (_c.c_int, [_c.c_int] * 3),
     'pvhip_dense_boxes_f32': (_c.c_int, [_c.c_void_p] + [_c.c_int] * 6 + [_c.c_float, _c.c_void_p] + [_c.c_int] * 11 + [_c.c_float] + [_c.c_int] * 2 +
                               [_c.c_void_p] * 3),
+    'pvhip_dense_boxes_tail_f32': (_c.c_int, [_c.c_void_p] + [_c.c_int] * 7 + [_c.c_float, _c.c_void_p] + [_c.c_int] * 11 + [_c.c_float] + [_c.c_int] * 2 +
+                                   [_c.c_void_p] * 3),
+    'pvhip_instance_masks_f32': (_c.c_int, [_c.c_void_p] + [_c.c_int] * 7 + [_c.c_void_p] + [_c.c_int] * 6 + [_c.c_void_p] * 3),
 }
 
 # entry points whose return value is not a status code
