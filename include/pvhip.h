@@ -930,6 +930,63 @@ int pvhip_instance_masks_f32(const float* head, int n, int a, int e, int layout,
                              const float* protos, int hp, int wp, int hn, int wn, int crop, int max_per_image,
                              const int* header, const int* rows, unsigned* words);
 
+/* Addition to ABI v19 (the version number is unchanged: nothing existing changed): the same boxes' masks in FRAME pixels -- the logits
+ * upsampled bilinearly to the frame the detector was fed, through the letterbox geometry, and thresholded after the upsampling
+ * (Ultralytics' process_mask with upsample, retina_masks) -- as one packed bitmap per box over its own rectangle.  head, n, a, e, layout,
+ * tail_at, tail, protos, header and rows are pvhip_instance_masks_f32's; (frame_h, frame_w, dx, dy, iw, ih) is the geometry the boxes
+ * call was given.  The rule (pyopenvino_amd/masks.py, make_frame, is the same in numpy and tests/frame_masks_ref.py in plain loops,
+ * matched bit for bit), for row j of the table: image r, anchor i, rectangle (x, y, w, h) = rows[j][1 .. 4], m[t] and p[t][q] as above:
+ *   1. logits    L[q] = fmaf(m[T - 1], p[T - 1][q], ... fmaf(m[0], p[0][q], +0.0f) ...), t ascending, fp32.  A prototype pixel with any
+ *      of its T values not finite has L[q] = NaN.  A detection with a coefficient that is not finite has an all-zero mask; its words are
+ *      still written, as zeros.
+ *   2. position  for frame column X in [x, x + w), in exact integers: N = (2 dx F + (2 X + 1) iw) wp - F wn and D = 2 F wn with F =
+ *      frame_w; P = floor(65536 N / D), floor toward minus infinity; x0 = P >> 16 (arithmetic), fx = (float)(P & 65535) / 65536.  Rows
+ *      alike with (dy, ih, frame_h, hp, hn).  This is the pixel centre X + 0.5 taken back through the inverse of the box rule's map
+ *      t = (p - d) F / i and then to prototype coordinates u wp / wn - 0.5: align_corners = false, in one step from prototypes to frame.
+ *      The taps clamp: xa = clamp(x0, 0, wp - 1), xb = clamp(x0 + 1, 0, wp - 1); rows alike.
+ *   3. value     t0 = L[ya][xa] + fx * (L[ya][xb] - L[ya][xa]), t1 likewise on row yb, v = t0 + fy * (t1 - t0): every operation fp32,
+ *      rounded once, no fma; all four taps are always read; no special cases, NaN and inf follow IEEE.  The bit is v > 0.
+ *   4. layout    Wr = ceil(w / 32).  Row j owns h * Wr words from offsets[j], the exclusive prefix sum in int64; pixel (X, Y) is bit
+ *      (X - x) & 31, least significant first, of word offsets[j] + (Y - y) * Wr + ((X - x) >> 5); padding bits are 0.  A row whose
+ *      rectangle is not inside the frame (x < 0, w < 1, x + w > frame_w, y alike) owns no words: the boxes call never writes one, and
+ *      this keeps the device in bounds whatever its rows hold.
+ *   5. capacity  made is the largest m with offsets[m] <= max_words, used = offsets[made].  Rows from made on have no mask and nothing
+ *      is written for them.
+ * Where this differs from Ultralytics: one interpolation, straight through the letterbox geometry; Q16 fractions; the crop is the integer
+ * rectangle of the row.
+ * `made`: two ints, (made, used), 8-byte aligned, which the host reads first; `words`: room for max_words words, 4-byte aligned; the
+ * host makes offsets itself from the rows by 4.  `scratch`: PVHIP_FRAME_MASKS_SCRATCH_BYTES(n, max_per_image) bytes, 16-byte aligned,
+ * that only the two launches read and write.  Header counts are clamped to max_per_image.
+ * Two launches on the current stream, no global-memory atomics, no workgroup waits for another, the same words every call.  (1) plan: one
+ * workgroup scans the rows, writes the offsets, (made, used) and the cumulative count of bands per row.  A band is a run of rectangle
+ * rows of one detection: the most whose window of prototype pixels -- its clamped tap rows times the rectangle's clamped tap columns --
+ * fits PVHIP_FRAME_MASKS_LDS_FLOATS floats, at most PVHIP_FRAME_MASKS_BAND_ROWS.  (2) masks: `workgroups` persistent workgroups (0: the
+ * entry's choice, PVHIP_FRAME_MASKS_GRID_PER_CU per compute unit) walk the bands with a static stride; per band the window's logits are
+ * made once by fmaf chains into LDS (no matrix instruction: one detection is a matrix-vector product), the positions of 2. once per row
+ * and column, and a wave samples 64 consecutive pixels of a rectangle row (PVHIP_FRAME_MASKS_FORM_ROW, w > 32) or 32 of each of two
+ * rows (PVHIP_FRAME_MASKS_FORM_PAIR) and ballots them into two finished words.  pvhip_frame_masks_form returns the form of a width -- no
+ * status, no device needed --, PVHIP_FRAME_MASKS_FORM_NONE for a width outside 1 .. 16384.
+ * 1 <= tail <= 64, 4 <= tail_at, tail_at + tail <= e, n * a * e < 2^31, 1 <= n <= 65535, hp, wp in 1 .. 4096 with hp * wp >= 2, hn, wn,
+ * frame_h, frame_w, iw, ih in 1 .. 16384, dx, dy in 0 .. 16384 (so the integers of 2. stay below 2^59), 1 <= max_per_image <=
+ * PVHIP_BOXES_MAX_CANDIDATES, n * max_per_image <= 2^24, 1 <= max_words <= 2^28, 0 <= workgroups <= 65535, no NULL or misaligned
+ * pointer; else PVHIP_EINVAL and nothing is launched. */
+#ifndef PVHIP_FRAME_MASKS_LDS_FLOATS
+#define PVHIP_FRAME_MASKS_LDS_FLOATS 8192       /* two prototype rows of 4096 floats: one frame row always fits */
+#endif
+#define PVHIP_FRAME_MASKS_BAND_ROWS  1024
+#define PVHIP_FRAME_MASKS_GRID_PER_CU 3
+#define PVHIP_FRAME_MASKS_FORM_NONE  0
+#define PVHIP_FRAME_MASKS_FORM_ROW   1
+#define PVHIP_FRAME_MASKS_FORM_PAIR  2
+#define PVHIP_FRAME_MASKS_SCRATCH_BYTES(n, max_per_image) \
+    (((size_t)16 + (size_t)12 * ((size_t)(n) * (size_t)(max_per_image) + 1u) + 15u) & ~(size_t)15u)
+int pvhip_frame_masks_form(int w);
+int pvhip_frame_masks_f32(const float* head, int n, int a, int e, int layout, int tail_at, int tail,
+                          const float* protos, int hp, int wp, int hn, int wn,
+                          int frame_h, int frame_w, int dx, int dy, int iw, int ih,
+                          int max_per_image, long long max_words, int workgroups,
+                          const int* header, const int* rows, void* scratch, int* made, unsigned* words);
+
 /* ---------------------------------------------------------------- a detector's answer ------ */
 /* Addition to ABI v18 (the version number is unchanged: nothing existing changed): the records of pvhip_detection_output_f32 become one
  * flat table of the detections a caller wants -- what the reference's sample makes on the host with `for record in res.reshape(100, 7):

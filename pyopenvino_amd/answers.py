@@ -1,5 +1,5 @@
 """Answers behind the pass: the Results a start named with ``top_k=``, ``detections=``, ``matches=``, ``keypoints=``, ``segments=``, ``maxima=``, ``text=``, ``boxes=`` or ``masks=`` come back from
-wait() as a ``TopK``, a ``Detections``, a ``Matches``, a ``Keypoints``, a ``Segments``, a ``Maxima``, a ``Text``, (a dense head's) a ``Detections`` or (its prototype Result's) a ``Masks`` made on the device instead of as the tensor.  One ``Answers`` per
+wait() as a ``TopK``, a ``Detections``, a ``Matches``, a ``Keypoints``, a ``Segments``, a ``Maxima``, a ``Text``, (a dense head's) a ``Detections`` or (its prototype Result's) a ``Masks`` or ``FrameMasks`` made on the device instead of as the tensor.  One ``Answers`` per
 Executable_Network (one per request), as ``HostInputs`` is on the way in: the request checks the arguments, binds the asks to the staged
 inputs, launches behind the pass and reads after it.
 
@@ -26,7 +26,7 @@ def _no_clash(keyword: str, names, asks: dict, screens=()):
 
 class Answers:
     """`blocks` = {ask.key(Result name): its Blocks}, this request's own device and page-locked blocks, made on first use: (name, k),
-    (name, resolved DetectionScreen), (name, resolved TiledScreen or RegionScreen, m), (name, id of the Gallery, k), (name, refine, space), of a class map (name,), of local maxima (name, max_per_plane, max_per_row, refine, space), of a decoded text (name, layout) or, of a dense head's boxes, (name, the BoxScreen without min_score and frame_size) and, of its masks, (prototype Result, head, that BoxScreen)."""
+    (name, resolved DetectionScreen), (name, resolved TiledScreen or RegionScreen, m), (name, id of the Gallery, k), (name, refine, space), of a class map (name,), of local maxima (name, max_per_plane, max_per_row, refine, space), of a decoded text (name, layout) or, of a dense head's boxes, (name, the BoxScreen without min_score and frame_size) and, of its masks, (prototype Result, head, that BoxScreen) or, in frame pixels, (prototype Result, head, that BoxScreen, 'FRAME', max_words)."""
 
     def __init__(self, runner):
         self.runner, self.blocks = runner, {}       # runner: the Executable_Network whose base stream and Results these are
@@ -122,7 +122,7 @@ class Answers:
             planes = masks_rule.checked(ienet, masks, heads, sharded)
             _no_clash('masks', planes, asks)
             for name, (screen, head, shape) in planes.items():
-                asks[name] = masks_rule.Ask(screen, head, asks[screen.head].net_hw, shape)
+                asks[name] = masks_rule.Ask(screen, head, asks[screen.head].net_hw, shape, asks[screen.head])
         return asks
 
     def _fitted_input(self):
