@@ -778,6 +778,62 @@ int pvhip_segment_labels_form(int c, int h, int w);
 int pvhip_segment_labels_f32(const float* x, int n, int c, int h, int w, int has_min, float min_score,
                              unsigned char* labels, int* areas, int* extents);
 
+/* Addition to ABI v19 (the version number is unchanged: nothing existing changed): the same class map in FRAME pixels -- the planes
+ * upsampled bilinearly to the frame the network was fed, through the letterbox geometry, and the best class taken after the upsampling:
+ * F.interpolate(logits, size, mode='bilinear', align_corners=False).argmax(1), in one step from the map to the frame.  x, n, c, h, w,
+ * has_min and min_score are pvhip_segment_labels_f32's; (hn, wn) is the extent of the network's input, (fh, fw) that of the frames, which
+ * stand in the rectangle (dx, dy, iw, ih) of that input (the identity: (0, 0, wn, hn)).  The rule (pyopenvino_amd/segments.py,
+ * frame_labels, is the same in numpy and tests/segments_frame_ref.py in plain loops, matched exactly; no tolerance anywhere), for frame
+ * pixel (X, Y) of batch row r, with L[k] = X[r][k]:
+ *   1. position  rule 2 of pvhip_frame_masks_f32 word for word, with (wp, hp) := (w, h): in exact integers N = (2 dx F + (2 X + 1) iw) w
+ *      - F wn and D = 2 F wn with F = fw; P = floor(65536 N / D), floor toward minus infinity; x0 = P >> 16 (arithmetic), fx =
+ *      (float)(P & 65535) / 65536; the taps clamp: xa = clamp(x0, 0, w - 1), xb = clamp(x0 + 1, 0, w - 1).  Rows alike with (dy, ih, fh,
+ *      h, hn).
+ *   2. value     for every class k: t0 = L[k][ya][xa] + fx * (L[k][ya][xb] - L[k][ya][xa]), t1 likewise on row yb, v[k] = t0 + fy *
+ *      (t1 - t0): every operation fp32, rounded once, no fma; all four taps are always read; no special cases, NaN and inf follow IEEE
+ *      (inf - inf next to the pixel voids it).
+ *   3. best, void, label  rules 1 to 3 of pvhip_segment_labels_f32 on v[k]: k* the first class in the total order -- NaN of any sign or
+ *      payload first, then descending with +0.0 == -0.0, ties to the lower class --; void iff v[k*] is NaN or (has_min == 1 and v[k*] <
+ *      min_score), equality keeps; labels[r][Y][X] = k*, or PVHIP_SEGMENT_VOID (255) when void.
+ *   4. sums      rule 4 of pvhip_segment_labels_f32 over frame pixels: areas[r][k], extents[r][k] = (x0, y0, x1, y1).
+ * Consequence: with the identity geometry and frame == network == map extent every fraction is 0 and a + 0 * (b - a) = a: on finite
+ * planes the answer is pvhip_segment_labels_f32's bit for bit.
+ * `labels` (n, fh, fw) uint8, byte aligned; `areas` (n, c) int32, `extents` (n, c, 4) int32, a class without pixels reading (fw, fh, 0, 0)
+ * at this level, as above.  Two launches on the current stream: one initialises `areas` and `extents`; one samples.  A workgroup owns a
+ * tile of one batch row -- a band of at most PVHIP_SEGMENT_FRAME_BAND_ROWS frame rows times a chunk of PVHIP_SEGMENT_FRAME_COL_CHUNK frame
+ * columns --, and a grid of at most PVHIP_SEGMENT_FRAME_GRID_PER_CU persistent workgroups per compute unit (one workgroup for a launch
+ * of at most PVHIP_SEGMENT_FRAME_MIN_TILES tiles) walks the tiles with a static stride.  The 64-bit divisions of 1. run
+ * once per tile for its rows and once for its columns and leave one packed word each in LDS.  A lane owns quads of four consecutive
+ * pixels of a row, cut at the 4-byte boundaries of the flat label run (one aligned 32-bit store each, byte stores at ragged ends), and
+ * keeps their running best -- segments' 32-bit order word and the class -- in registers; taps are read once where neighbouring pixels
+ * share them.  Every label byte is written exactly once.  Areas and extents are summed per (wave, class), gathered per workgroup in LDS
+ * and sent by integer atomics when the workgroup's batch row changes or its walk ends: the same bits every call.
+ *   PVHIP_SEGMENT_FRAME_FORM_STAGED  a frame pixel steps over at most PVHIP_SEGMENT_FRAME_DIRECT_STEP map pixels on both axes (iw w <=
+ *      STEP fw wn, rows alike): the tile's window of map pixels -- its clamped tap rows times its clamped tap columns -- is staged into
+ *      PVHIP_SEGMENT_FRAME_LDS_FLOATS floats of LDS by coalesced loads, as many classes at a time as fit, at most
+ *      PVHIP_SEGMENT_FRAME_CLASS_CHUNK; a tie or a NaN across the seam of two chunks still resolves to the lower class.  The band is
+ *      the most frame rows whose window of one class fits beside the widest chunk's columns (the bound of pvhip_frame_masks_f32's bands).
+ *   PVHIP_SEGMENT_FRAME_FORM_DIRECT  steeper downsampling: a window would hold map pixels no tap reads, so the four taps are read
+ *      straight from global memory; tables, order, stores and sums are the same.
+ * pvhip_segment_frame_labels_form returns the form -- no status, no device needed --, PVHIP_SEGMENT_FRAME_FORM_NONE for what the entry
+ * refuses.  The matrix cores are not used: resampling as two small matrix products would change the order and number of roundings.
+ * n >= 1, 1 <= c <= PVHIP_SEGMENT_MAX_CLASSES, h, w in 1 .. 4096 with h * w >= 2, hn, wn, fh, fw, iw, ih in 1 .. 16384, dx, dy in
+ * 0 .. 16384 (so the integers of 1. stay below 2^59), n * fh * fw < 2^31, has_min 0 or 1, min_score finite, no NULL pointer, x / areas /
+ * extents 4-byte aligned; else PVHIP_EINVAL and nothing is launched. */
+#define PVHIP_SEGMENT_FRAME_LDS_FLOATS  8192    /* 32 KB of window: with the tables and the sums four workgroups fit a compute unit */
+#define PVHIP_SEGMENT_FRAME_BAND_ROWS   16      /* four rows a wave: sixteen pixels' running best a lane, 32 registers of state */
+#define PVHIP_SEGMENT_FRAME_COL_CHUNK   252     /* 4 * 64 - 4: a row of a chunk is at most 64 quads at any 4-byte phase, one a lane */
+#define PVHIP_SEGMENT_FRAME_CLASS_CHUNK 32      /* DeepLab's 21 and Cityscapes' 19 classes are one chunk: no second barrier pair */
+#define PVHIP_SEGMENT_FRAME_GRID_PER_CU 4       /* what the LDS above lets run at once */
+#define PVHIP_SEGMENT_FRAME_MIN_TILES   4       /* a launch of at most as many tiles is latency either way: one workgroup, one table */
+#define PVHIP_SEGMENT_FRAME_DIRECT_STEP 2       /* beyond two map pixels a frame pixel a window stages more than its taps read */
+#define PVHIP_SEGMENT_FRAME_FORM_NONE   0
+#define PVHIP_SEGMENT_FRAME_FORM_STAGED 1
+#define PVHIP_SEGMENT_FRAME_FORM_DIRECT 2
+int pvhip_segment_frame_labels_form(int c, int h, int w, int hn, int wn, int fh, int fw, int dx, int dy, int iw, int ih);
+int pvhip_segment_frame_labels_f32(const float* x, int n, int c, int h, int w, int hn, int wn, int fh, int fw, int dx, int dy, int iw, int ih,
+                                   int has_min, float min_score, unsigned char* labels, int* areas, int* extents);
+
 /* ---------------------------------------------------------------- a text recogniser's answer ---- */
 /* Addition to ABI v19 (the version number is unchanged: nothing existing changed): the greedy CTC decoding of a contiguous fp32 tensor of
  * per-timestep class scores -- what a user of a text recogniser makes on the host with argmax(-1) and a collapse after reading

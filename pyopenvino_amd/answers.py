@@ -4,7 +4,7 @@ Executable_Network (one per request), as ``HostInputs`` is on the way in: the re
 inputs, launches behind the pass and reads after it.
 
 An ask is one Result's question in its resolved form, an ``ask.Ask`` (ask.py states the protocol: KEYWORD, `bound`, `key`, `launch`,
-`on_host`): top_k.Ask, detections.Ask / FittedAsk, tiled_detections.Ask / RegionAsk, gallery.Ask, keypoints.Ask, segments.Ask, maxima.Ask, text.Ask, boxes.Ask or masks.Ask.  Which kind it is
+`on_host`): top_k.Ask, detections.Ask / FittedAsk, tiled_detections.Ask / RegionAsk, gallery.Ask, keypoints.Ask, segments.Ask / FrameAsk, maxima.Ask, text.Ask, boxes.Ask or masks.Ask.  Which kind it is
 matters only where checked() makes it; the rule of each kind, its argument's forms and its refusals are stated in its module.  A plain
 screen over a detector whose input declares a fit (preprocess_info.resize_fit) learns its geometry in bound(), from the extent of the
 frames the pass was fed, and so does a BoxScreen over such an input."""
@@ -26,7 +26,7 @@ def _no_clash(keyword: str, names, asks: dict, screens=()):
 
 class Answers:
     """`blocks` = {ask.key(Result name): its Blocks}, this request's own device and page-locked blocks, made on first use: (name, k),
-    (name, resolved DetectionScreen), (name, resolved TiledScreen or RegionScreen, m), (name, id of the Gallery, k), (name, refine, space), of a class map (name,), of local maxima (name, max_per_plane, max_per_row, refine, space), of a decoded text (name, layout) or, of a dense head's boxes, (name, the BoxScreen without min_score and frame_size) and, of its masks, (prototype Result, head, that BoxScreen) or, in frame pixels, (prototype Result, head, that BoxScreen, 'FRAME', max_words)."""
+    (name, resolved DetectionScreen), (name, resolved TiledScreen or RegionScreen, m), (name, id of the Gallery, k), (name, refine, space), of a class map (name,) or, in frame pixels, (name, 'FRAME', Fh, Fw), of local maxima (name, max_per_plane, max_per_row, refine, space), of a decoded text (name, layout) or, of a dense head's boxes, (name, the BoxScreen without min_score and frame_size) and, of its masks, (prototype Result, head, that BoxScreen) or, in frame pixels, (prototype Result, head, that BoxScreen, 'FRAME', max_words)."""
 
     def __init__(self, runner):
         self.runner, self.blocks = runner, {}       # runner: the Executable_Network whose base stream and Results these are
@@ -91,8 +91,17 @@ class Answers:
             maps = segments_rule.checked(ienet, segments, sharded)
             if asks:
                 _no_clash('segments', maps, asks)
+            formats = ex.host_inputs.formats
             for name, screen in maps.items():
-                asks[name] = segments_rule.Ask(screen)
+                if not isinstance(screen, segments_rule.FrameSegmentScreen):
+                    asks[name] = segments_rule.Ask(screen)
+                    continue
+                fmt = formats.get(screen.input)
+                fitted = fmt is not None and fmt.fitted
+                if fitted and isinstance(inputs, dict) and isinstance(inputs.get(screen.input), FrameFeed):     # (boxes=' refusal: a geometry per row)
+                    raise ValueError('segments: input {!r} declares resize_fit {} and is fed a {}: every row has a geometry of its own'.format(
+                        screen.input, fmt.fit, type(inputs[screen.input]).__name__))
+                asks[name] = segments_rule.FrameAsk(screen, boxes_rule.extent_of(ienet, screen.input), fmt if fitted else None, None, None)
         if maxima is not None:
             found = maxima_rule.checked(ienet, maxima, sharded)
             if asks:

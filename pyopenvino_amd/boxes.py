@@ -346,6 +346,20 @@ class Blocks(detections.TableBlocks):
             device.call(self.ENTRY, device.ptr(result), n, A, C, *rest)
 
 
+def geometry_of(keyword: str, name: str, frame_size, net_hw, format, slots) -> tuple:
+    """(frame_size, fit = (dx, dy, iw, ih)) of the pass whose inputs are staged in `slots`, for an answer in frame pixels over input `name`
+    of extent `net_hw` (boxes=, and segments= with a FrameSegmentScreen): the identity over `frame_size` or the network's extent, or, when
+    `format` -- the input's InputFormat where it declares a fit, else None -- was fed host frames, the rectangle those frames were fitted
+    into, over `frame_size` or theirs; ValueError('{keyword}: ...')."""
+    extent = slots[name].fed if format is not None and name in slots else None
+    if extent is None:                          # nothing was fitted: a device tensor at the network's own extent, or a stretched input
+        return frame_size or net_hw, (0, 0, net_hw[1], net_hw[0])
+    frame = frame_size or (int(extent[0]), int(extent[1]))
+    if not detections._pair(frame, detections.MAX_EXTENT):
+        raise ValueError('{}: frames of {} are more than 2^24 wide or high'.format(keyword, tuple(extent)))
+    return frame, tuple(int(v) for v in format.fit_geometry(extent))
+
+
 class Ask(ask.Ask, collections.namedtuple('Ask', 'screen net_hw format frame_size fit')):
     """A Result asked for with boxes=, its screen resolved: `net_hw` the extent of the screen's input; `format` that input's InputFormat
     when it declares a fit, else None; `frame_size` and `fit` = (dx, dy, iw, ih), the geometry of the pass, known once its inputs are staged
@@ -355,14 +369,8 @@ class Ask(ask.Ask, collections.namedtuple('Ask', 'screen net_hw format frame_siz
     KEYWORD = 'boxes'
 
     def bound(self, inputs, slots):
-        name = self.screen.input
-        extent = slots[name].fed if self.format is not None and name in slots else None
-        if extent is None:                      # nothing was fitted: a device tensor at the network's own extent, or a stretched input
-            return self._replace(frame_size=self.screen.frame_size or self.net_hw, fit=(0, 0, self.net_hw[1], self.net_hw[0]))
-        frame = self.screen.frame_size or (int(extent[0]), int(extent[1]))
-        if not detections._pair(frame, detections.MAX_EXTENT):
-            raise ValueError('boxes: frames of {} are more than 2^24 wide or high'.format(tuple(extent)))
-        return self._replace(frame_size=frame, fit=tuple(int(v) for v in self.format.fit_geometry(extent)))
+        frame, fit = geometry_of('boxes', self.screen.input, self.screen.frame_size, self.net_hw, self.format, slots)
+        return self._replace(frame_size=frame, fit=fit)
 
     def key(self, name):
         """(name, the screen without min_score and frame_size).  min_score, the frame extent and the geometry go with the launch: the blocks

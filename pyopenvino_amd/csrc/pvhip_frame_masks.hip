@@ -29,6 +29,7 @@
 //             with a coefficient that is not finite skips the stage and writes zeros.
 // No global-memory atomics, no workgroup waits for another, the same words every call.
 #include "pvhip_common.h"
+#include "pvhip_frame_taps.h"
 
 #pragma clang fp contract(off)
 
@@ -66,26 +67,7 @@ __device__ __forceinline__ int* prefix_of(int* info, long long room) { return re
 
 __device__ __forceinline__ bool not_finite(float v) { return (__float_as_uint(v) & 0x7F800000u) == 0x7F800000u; }
 
-// One axis of rule 2: N(X) = c0 + X * step over den, all exact integers below 2^43, so that 65536 N stays below 2^59.
-struct Axis {
-    long long c0, step, den;
-    int ext;                                    // the prototype extent the taps clamp to
-};
-__device__ __forceinline__ Axis axis_of(int d, int i, int F, int P, int N) {
-    return Axis{(2LL * d * F + i) * P - (long long)F * N, 2LL * i * P, 2LL * F * N, P};
-}
-struct Tap {
-    int a, b;                                   // the clamped taps
-    unsigned f;                                 // the Q16 fraction
-};
-__device__ __forceinline__ Tap tap_of(const Axis& ax, int X) {
-    const long long num = (ax.c0 + (long long)X * ax.step) * 65536LL;
-    long long p = num / ax.den;
-    if (num % ax.den < 0) --p;                  // floor toward minus infinity
-    const long long x0 = p >> 16, last = ax.ext - 1;
-    return Tap{(int)min(max(x0, 0LL), last), (int)min(max(x0 + 1, 0LL), last), (unsigned)(p & 65535)};
-}
-__device__ __forceinline__ unsigned packed(const Tap& t, int first) { return (unsigned)(t.a - first) | ((unsigned)(t.b - t.a) << 15) | (t.f << 16); }
+// (Axis, Tap, tap_of and packed -- rule 2 -- are pvhip_frame_taps.h's, shared with pvhip_segments_frame.hip.)
 
 // The height of a detection's bands: the most frame rows whose tap rows times `cw` tap columns fit the LDS window.  k frame rows
 // further on the first tap is at most ceil(k * ih * hp / (fh * hn)) rows further on, and a band's taps are the first row's first
