@@ -1373,6 +1373,49 @@ int         pvhip_input_preprocess_perspective_color_f32(const void* src, float*
 int         pvhip_landmarks_to_warps(const float* points, const int* regions, const double* tmpl, long long* table, int* valid, int n,
                                      int rows, int k, int m, int src_h, int src_w);
 
+/* ---------------------------------------------------------------- connected components of a probability map ---- */
+/* Addition to ABI v19 (the version number is unchanged: nothing existing changed): the connected components of plane `channel` of a
+ * contiguous (n, k, h, w) fp32 stack of score planes -- what a user of a DBNet, PixelLink-style or PSENet text detector, of CRAFT's region
+ * map or of a blob head makes on the host with a threshold and a connected-component labelling after reading 4 n k h w bytes back -- so
+ * that 8 + 80 max_per_image bytes per batch row are read back.  The rule (pyopenvino_amd/components.py states the same one in numpy and
+ * tests/components_ref.py in plain loops, matched exactly; every output is an integer or the plane's own bits), for the plane
+ * P = X[r][channel] of batch row r (channel in -k .. k - 1, a negative one counted from the end):
+ *   1. foreground  pixel p is foreground iff P[p] is not NaN and P[p] >= min_score; equality keeps, a NaN is background: the quiet-NaN
+ *      rows behind `count` of a DetectedRois or LandmarkWarps pass have found = counts = 0.
+ *   2. components  two foreground pixels of one plane are joined when they are horizontal or vertical neighbours and, with
+ *      connectivity == 8, when they are diagonal neighbours; neighbours in (y, x), never in the flat index.  A component is a class of
+ *      the transitive closure; its seed is its smallest flat index y * w + x.
+ *   3. statistics  area; the rectangle min x, min y, max x, max y (`rects`, all four inclusive); the peak, the first of its scores in
+ *      the order of pvhip_topk_rows_f32 among numbers (descending, +0.0 == -0.0), as the bits of the first such pixel in raster order;
+ *      sum = the sum of llrint(clamp((double)v, -32768, 32768) * 65536), ties to even; the five moments sum x, sum y, sum x x,
+ *      sum x y, sum y y over the pixel indices, all int64 (modulo 2^64, which only a plane with a side above 2^19 can reach).
+ *   4. selection   found[r] counts all components; those with area >= min_area are ranked by descending area, ties to the lower seed;
+ *      the first max_per_image are answered and counts[r] is their number.
+ * `counts`, `found` (n) int32; `seeds`, `areas`, `zeros` (n, max_per_image) int32, `peaks` (n, max_per_image) fp32, -1 (all ones) in
+ * seeds, areas and peaks behind counts[r]; `rects` (n, max_per_image, 4) int32; `sums` (n, max_per_image) and `moments`
+ * (n, max_per_image, 5) int64; the statistics behind counts[r] are (w, h, -1, -1) and zeros.  A peak that is a zero reads +0.0 in `peaks`
+ * and its sign in `zeros`: (index << 1 | sign) of the component's first zero in raster order, 0x7FFFFFFF for every other component; the
+ * caller puts it on.  `scratch`: pvhip_components_scratch_bytes(n, h, w, max_per_image) bytes, 16-byte aligned -- three int32 per pixel:
+ * parent, area, peak word --; 0 for what the entry refuses.  `x` may be only 4-byte aligned.
+ * Five launches on the current stream: union-find in LDS over tiles of PVHIP_COMPONENTS_TILE_ROWS x PVHIP_COMPONENTS_TILE_COLS pixels,
+ * a workgroup a tile, the rows as 128-bit masks made of wave ballots; lock-free atomicMin unions across the tiles' seams; flatten with
+ * areas and peaks; one workgroup per image selects; the winners' statistics gathered per workgroup in LDS and sent by integer atomics.
+ * The selection is not a streaming pass: its one workgroup of 256 lanes walks the image's h * w parents 1024 at a time with two barriers
+ * a trip, h * w / 1024 trips one after another (16384 at h * w = 2^24), so its time grows with the size of one image whatever n is, and it
+ * is the launch that bounds the call on large planes (profiles/components.md).
+ * n, h, w >= 1, 1 <= k <= PVHIP_COMPONENTS_MAX_PLANES, 2 <= h * w <= PVHIP_COMPONENTS_MAX_PLANE, n * h * w < 2^31, channel in
+ * -k .. k - 1, connectivity 4 or 8, min_score finite, 1 <= min_area <= 2^24, 1 <= max_per_image <= PVHIP_COMPONENTS_MAX_PER_IMAGE, no NULL
+ * pointer, sums / moments 8-byte and the others 4-byte aligned; else PVHIP_EINVAL and nothing is launched or written. */
+#define PVHIP_COMPONENTS_TILE_ROWS      32
+#define PVHIP_COMPONENTS_TILE_COLS      128
+#define PVHIP_COMPONENTS_MAX_PLANES     255
+#define PVHIP_COMPONENTS_MAX_PLANE      (1 << 24)
+#define PVHIP_COMPONENTS_MAX_PER_IMAGE  1024
+unsigned long long pvhip_components_scratch_bytes(int n, int h, int w, int max_per_image);
+int pvhip_components_f32(const float* x, int n, int k, int h, int w, int channel, int connectivity, float min_score, int min_area,
+                         int max_per_image, void* scratch, int* counts, int* found, int* seeds, int* areas, float* peaks, int* zeros,
+                         int* rects, long long* sums, long long* moments);
+
 #ifdef __cplusplus
 }
 #endif
