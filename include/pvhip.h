@@ -1416,6 +1416,52 @@ int pvhip_components_f32(const float* x, int n, int k, int h, int w, int channel
                          int max_per_image, void* scratch, int* counts, int* found, int* seeds, int* areas, float* peaks, int* zeros,
                          int* rects, long long* sums, long long* moments);
 
+/* ---------------------------------------------------------------- multi-person poses from part-affinity fields ---- */
+/* Addition to ABI v19 (the version number is unchanged: nothing existing changed): the persons of every batch row of a multi-person pose
+ * head -- OpenPose / CPM stages, human-pose-estimation-0001-like heads --, from the candidates pvhip_heatmap_maxima_f32 left in its
+ * `scratch` for the contiguous (n, k, h, w) fp32 heatmaps `heat` (the (n, k, max_per_plane) keys `candidates`, descending and padded with
+ * zeros) and the contiguous (n, channels, h, w) fp32 part-affinity fields `pafs`, so that 4 + 20 max_persons k + 4 max_persons bytes per
+ * batch row are read back instead of both tensors.  The rule (pyopenvino_amd/poses.py states the same one in numpy and
+ * tests/poses_ref.py in plain loops, matched exactly; every operation is fp32 rounded once, no product is fused into a sum, division and
+ * square root are the correctly rounded ones), for batch row r and the `limbs` rows (a, b, cx, cy, founds) of the host table `skeleton`:
+ *   1. candidates  the candidates of joint j are the non-zero keys candidates[r][j][..] in their order, candidate index i = 0 ..; the key's
+ *      index is the position py * w + px.  max_per_plane <= PVHIP_POSES_MAX_CANDIDATES: a limb has at most 1024 pairs.
+ *   2. scoring     for candidate i of joint a at (ax, ay) and candidate j of joint b at (bx, by): dx = bx - ax, dy = by - ay;
+ *      dx == dy == 0 is no connection.  len = sqrtf((float)(dx dx + dy dy)) (the sum exact, in 64 bits), ux = (float)dx / len,
+ *      uy = (float)dy / len.  Sample s = 0 .. samples - 1 stands at the pixel x = ax + floor((2 s dx + (S - 1)) / (2 (S - 1))), y alike:
+ *      the nearest pixel, no interpolation.  v_s = pafs[r][cx][y][x] * ux + pafs[r][cy][y][x] * uy.  A sample passes iff v_s > min_field
+ *      (a NaN does not); c counts the passing samples and sum adds them in order of s from +0; the connection is valid iff
+ *      c >= min_samples, and its score is sum / (float)c.
+ *   3. matching    a limb's valid connections are ranked by descending score (positive, since min_field >= 0: the bits order), ties to the
+ *      lower i, then to the lower j; one is taken iff neither its i nor its j was taken before it.
+ *   4. assembling  limbs in the table's order, a limb's taken connections in rank order.  For (i, j, score): the first person whose
+ *      slot a holds i; if there is one and its slot b is empty, slot b becomes j and total = (total + heat_b_j) + score; if its slot b
+ *      is occupied nothing happens; if there is none, `founds` is 1 and fewer than max_persons persons exist, a new person holds i and j
+ *      with total = (heat_a_i + heat_b_j) + score.  A person is kept iff it has at least min_joints joints and
+ *      total / (float)joints >= min_mean; the kept stay in the order they were made.
+ * `counts` (n) int32; `joints` (n, max_persons, k) int32 positions, -1 where a person lacks the joint; `scores` (n, max_persons, k) fp32,
+ * the heatmap's own bits there; `points` (n, max_persons, k, 2) fp32 by rules 3 and 4 of pvhip_heatmap_peaks_f32 under `refine` and
+ * `space`; `totals` (n, max_persons) fp32; quiet NaNs (0x7FC00000) where a joint is absent and in every slot behind counts[r].  A row of
+ * NaN heat has no candidates: counts[r] = 0.  `scratch`: PVHIP_POSES_SCRATCH_BYTES(n, limbs) bytes, 16-byte aligned: a limb's taken
+ * connections, 16 bytes each, and their number.  `heat` and `pafs` may be only 4-byte aligned.
+ * Two launches on the current stream, no global-memory atomics: a workgroup per (row, limb) scores the pairs' samples flattened over its
+ * 256 lanes, sorts the valid pairs in LDS and matches by wave ballots; a wave per row assembles with persons as lanes.
+ * n, h, w >= 1, 2 <= h * w <= PVHIP_MAXIMA_MAX_PLANE, 1 <= k <= PVHIP_POSES_MAX_JOINTS, both tensors below 2^31 elements,
+ * 1 <= limbs <= PVHIP_POSES_MAX_LIMBS, 1 <= channels <= 2 PVHIP_POSES_MAX_LIMBS, every a != b in 0 .. k - 1, cx and cy in
+ * 0 .. channels - 1, founds 0 or 1, 2 <= samples <= PVHIP_POSES_MAX_SAMPLES, 1 <= min_samples <= samples, min_field finite and >= 0,
+ * 1 <= max_persons <= PVHIP_POSES_MAX_PERSONS, 1 <= min_joints <= k, min_mean finite, no NULL pointer; else PVHIP_EINVAL and nothing is
+ * launched or written. */
+#define PVHIP_POSES_MAX_CANDIDATES  32
+#define PVHIP_POSES_MAX_LIMBS       64
+#define PVHIP_POSES_MAX_PERSONS     64
+#define PVHIP_POSES_MAX_JOINTS      256
+#define PVHIP_POSES_MAX_SAMPLES     16
+#define PVHIP_POSES_SCRATCH_BYTES(n, limbs)  ((unsigned long long)(n) * (unsigned long long)(limbs) * (16ull * PVHIP_POSES_MAX_CANDIDATES + 4ull))
+int pvhip_pose_groups_f32(const float* heat, const unsigned long long* candidates, const float* pafs, int n, int k, int h, int w,
+                          int max_per_plane, int channels, const int* skeleton, int limbs, int refine, int space, int samples,
+                          float min_field, int min_samples, int max_persons, int min_joints, float min_mean, void* scratch, int* counts,
+                          int* joints, float* scores, float* points, float* totals);
+
 #ifdef __cplusplus
 }
 #endif

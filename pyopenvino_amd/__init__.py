@@ -13,6 +13,8 @@ from .segments import FrameSegmentScreen, Segments, SegmentScreen  # noqa: F401
 from .maxima import Maxima, MaximaScreen  # noqa: F401
 from . import components  # noqa: F401
 from .components import Components, ComponentScreen  # noqa: F401
+from . import poses  # noqa: F401
+from .poses import Poses, PoseScreen  # noqa: F401
 from . import text  # noqa: F401
 from .text import Text, TextScreen  # noqa: F401
 from . import boxes  # noqa: F401
@@ -23,4 +25,4 @@ from .input_format import DetectedRois, LandmarkWarps, PerspectiveInput, RoiInpu
 from .tiled_detections import RegionScreen, TiledScreen  # noqa: F401
 from .top_k import TopK  # noqa: F401
 
-__all__ = ['IECore', 'IENetwork', 'Executable_Network', 'RoiInput', 'WarpInput', 'PerspectiveInput', 'DetectedRois', 'LandmarkWarps', 'TopK', 'Detections', 'DetectionScreen', 'TiledScreen', 'RegionScreen', 'Gallery', 'GalleryMatch', 'Matches', 'PeakScreen', 'Keypoints', 'SegmentScreen', 'FrameSegmentScreen', 'Segments', 'MaximaScreen', 'Maxima', 'TextScreen', 'Text', 'text', 'BoxScreen', 'boxes', 'MaskScreen', 'Masks', 'FrameMasks', 'masks', 'ComponentScreen', 'Components', 'components']
+__all__ = ['IECore', 'IENetwork', 'Executable_Network', 'RoiInput', 'WarpInput', 'PerspectiveInput', 'DetectedRois', 'LandmarkWarps', 'TopK', 'Detections', 'DetectionScreen', 'TiledScreen', 'RegionScreen', 'Gallery', 'GalleryMatch', 'Matches', 'PeakScreen', 'Keypoints', 'SegmentScreen', 'FrameSegmentScreen', 'Segments', 'MaximaScreen', 'Maxima', 'TextScreen', 'Text', 'text', 'BoxScreen', 'boxes', 'MaskScreen', 'Masks', 'FrameMasks', 'masks', 'ComponentScreen', 'Components', 'components', 'PoseScreen', 'Poses', 'poses']

@@ -1,16 +1,16 @@
-"""Answers behind the pass: the Results a start named with ``top_k=``, ``detections=``, ``matches=``, ``keypoints=``, ``segments=``, ``maxima=``, ``text=``, ``boxes=``, ``masks=`` or ``components=`` come back from
-wait() as a ``TopK``, a ``Detections``, a ``Matches``, a ``Keypoints``, a ``Segments``, a ``Maxima``, a ``Text``, (a dense head's) a ``Detections`` or (its prototype Result's) a ``Masks`` or ``FrameMasks`` or a ``Components`` made on the device instead of as the tensor.  One ``Answers`` per
+"""Answers behind the pass: the Results a start named with ``top_k=``, ``detections=``, ``matches=``, ``keypoints=``, ``segments=``, ``maxima=``, ``text=``, ``boxes=``, ``masks=``, ``components=`` or ``poses=`` come back from
+wait() as a ``TopK``, a ``Detections``, a ``Matches``, a ``Keypoints``, a ``Segments``, a ``Maxima``, a ``Text``, (a dense head's) a ``Detections`` or (its prototype Result's) a ``Masks`` or ``FrameMasks`` a ``Components`` or a ``Poses`` made on the device instead of as the tensor.  One ``Answers`` per
 Executable_Network (one per request), as ``HostInputs`` is on the way in: the request checks the arguments, binds the asks to the staged
 inputs, launches behind the pass and reads after it.
 
 An ask is one Result's question in its resolved form, an ``ask.Ask`` (ask.py states the protocol: KEYWORD, `bound`, `key`, `launch`,
-`on_host`): top_k.Ask, detections.Ask / FittedAsk, tiled_detections.Ask / RegionAsk, gallery.Ask, keypoints.Ask, segments.Ask / FrameAsk, maxima.Ask, text.Ask, boxes.Ask, masks.Ask or components.Ask.  Which kind it is
+`on_host`): top_k.Ask, detections.Ask / FittedAsk, tiled_detections.Ask / RegionAsk, gallery.Ask, keypoints.Ask, segments.Ask / FrameAsk, maxima.Ask, text.Ask, boxes.Ask, masks.Ask, components.Ask or poses.Ask.  Which kind it is
 matters only where checked() makes it; the rule of each kind, its argument's forms and its refusals are stated in its module.  A plain
 screen over a detector whose input declares a fit (preprocess_info.resize_fit) learns its geometry in bound(), from the extent of the
 frames the pass was fed, and so does a BoxScreen over such an input."""
 import numpy as np
 
-from . import boxes as boxes_rule, components as components_rule, detections as detections_rule, device, gallery as gallery_rule, keypoints as keypoints_rule, masks as masks_rule, maxima as maxima_rule, segments as segments_rule, \
+from . import boxes as boxes_rule, components as components_rule, detections as detections_rule, device, gallery as gallery_rule, keypoints as keypoints_rule, masks as masks_rule, maxima as maxima_rule, poses as poses_rule, segments as segments_rule, \
     text as text_rule, tiled_detections as tiled_rule, top_k as top_k_rule
 from .input_format import FrameFeed
 
@@ -26,7 +26,7 @@ def _no_clash(keyword: str, names, asks: dict, screens=()):
 
 class Answers:
     """`blocks` = {ask.key(Result name): its Blocks}, this request's own device and page-locked blocks, made on first use: (name, k),
-    (name, resolved DetectionScreen), (name, resolved TiledScreen or RegionScreen, m), (name, id of the Gallery, k), (name, refine, space), of a class map (name,) or, in frame pixels, (name, 'FRAME', Fh, Fw), of local maxima (name, max_per_plane, max_per_row, refine, space), of a decoded text (name, layout) or, of a dense head's boxes, (name, the BoxScreen without min_score and frame_size) and, of its masks, (prototype Result, head, that BoxScreen) or, in frame pixels, (prototype Result, head, that BoxScreen, 'FRAME', max_words), of connected components (name, channel, connectivity, max_per_image)."""
+    (name, resolved DetectionScreen), (name, resolved TiledScreen or RegionScreen, m), (name, id of the Gallery, k), (name, refine, space), of a class map (name,) or, in frame pixels, (name, 'FRAME', Fh, Fw), of local maxima (name, max_per_plane, max_per_row, refine, space), of a decoded text (name, layout) or, of a dense head's boxes, (name, the BoxScreen without min_score and frame_size) and, of its masks, (prototype Result, head, that BoxScreen) or, in frame pixels, (prototype Result, head, that BoxScreen, 'FRAME', max_words), of connected components (name, channel, connectivity, max_per_image), of poses (field Result, heat Result, max_persons, L)."""
 
     def __init__(self, runner):
         self.runner, self.blocks = runner, {}       # runner: the Executable_Network whose base stream and Results these are
@@ -34,13 +34,13 @@ class Answers:
     def release(self):
         self.blocks = {}
 
-    def checked(self, inputs, top_k, detections, sharded: bool, matches=None, keypoints=None, segments=None, maxima=None, text=None, boxes=None, masks=None, components=None) -> dict:
-        """{Result name: ask} of the `top_k`, `detections`, `matches`, `keypoints`, `segments`, `maxima`, `text`, `boxes`, `masks` and `components` arguments of a start with `inputs`, {} when nothing
+    def checked(self, inputs, top_k, detections, sharded: bool, matches=None, keypoints=None, segments=None, maxima=None, text=None, boxes=None, masks=None, components=None, poses=None) -> dict:
+        """{Result name: ask} of the `top_k`, `detections`, `matches`, `keypoints`, `segments`, `maxima`, `text`, `boxes`, `masks`, `components` and `poses` arguments of a start with `inputs`, {} when nothing
         is asked; ValueError.  Everything is looked up in the network as it was read: no device is needed, nothing is staged, allocated or
         launched.  The checks run in this order, which is not the keywords': matches' own, a tiled or region screen for a Result `top_k`
         names, top_k's, detections', a Result under two of the three, what a tiled, region or fitted screen asks of its feed, keypoints',
-        a Result under keypoints and another, segments', a Result under segments and another, maxima's, a Result under maxima and another, text's, a Result under text and another, boxes', a Result under boxes and another, what a fitted input asks of its feed, masks', a Result under masks and another, components', a Result under components and another."""
-        if top_k is detections is matches is keypoints is segments is maxima is text is boxes is masks is components is None:
+        a Result under keypoints and another, segments', a Result under segments and another, maxima's, a Result under maxima and another, text's, a Result under text and another, boxes', a Result under boxes and another, what a fitted input asks of its feed, masks', a Result under masks and another, components', a Result under components and another, poses', a Result under poses and another."""
+        if top_k is detections is matches is keypoints is segments is maxima is text is boxes is masks is components is poses is None:
             return {}
         ex, ienet, asks = self.runner, self.runner.ienet, {}
         matched = gallery_rule.checked(ienet, matches, sharded) if matches is not None else {}
@@ -138,6 +138,12 @@ class Answers:
                 _no_clash('components', maps, asks)
             for name, screen in maps.items():
                 asks[name] = components_rule.Ask(screen)
+        if poses is not None:
+            heats = {name: a.screen for name, a in asks.items() if isinstance(a, maxima_rule.Ask)}
+            fields = poses_rule.checked(ienet, poses, heats, sharded)
+            _no_clash('poses', fields, asks)
+            for name, (screen, table) in fields.items():
+                asks[name] = poses_rule.Ask(screen, table)
         return asks
 
     def _fitted_input(self):

@@ -1,4 +1,4 @@
-"""What the kinds of answer share (top_k.py, detections.py, tiled_detections.py, gallery.py, keypoints.py, segments.py, maxima.py, text.py, boxes.py, masks.py; answers.py drives them): the
+"""What the kinds of answer share (top_k.py, detections.py, tiled_detections.py, gallery.py, keypoints.py, segments.py, maxima.py, text.py, boxes.py, masks.py, components.py, poses.py; answers.py drives them): the
 Ask protocol, the flat block pair an answer of fixed size is read back through, the resolver of the Results an argument names, and
 the min_score check."""
 import ctypes
@@ -17,7 +17,8 @@ class Ask:
     `launch_with()`, what its blocks' launch takes besides that value; `on_host(value)`, the rule in numpy on a host value; and
     `bound`, when it learns something from the inputs a pass was fed.  `needs` lists the other Results of the same start that the
     ask reads besides its own: answers.py launches it behind their asks and hands its `launch` and `on_host` one (ask, value, blocks)
-    per name (masks.py's ask reads the head's tensor and the table its boxes ask has just written)."""
+    per name (masks.py's ask reads the head's tensor and the table its boxes ask has just written; poses.py's the heatmaps and the
+    candidate keys its maxima ask has left on the device)."""
     __slots__ = ()
     KEYWORD = None
     needs = ()

@@ -202,6 +202,7 @@ SIGNATURES = {
     'pvhip_heatmap_maxima_f32': (_c.c_int, [_c.c_void_p] + [_c.c_int] * 9 + [_c.c_float] + [_c.c_void_p] * 6),
     'pvhip_components_scratch_bytes': (_c.c_ulonglong, [_c.c_int] * 4),
     'pvhip_components_f32': (_c.c_int, [_c.c_void_p] + [_c.c_int] * 6 + [_c.c_float] + [_c.c_int] * 2 + [_c.c_void_p] * 10),
+    'pvhip_pose_groups_f32': (_c.c_int, [_c.c_void_p] * 3 + [_c.c_int] * 6 + [_c.c_void_p] + [_c.c_int] * 4 + [_c.c_float] + [_c.c_int] * 3 + [_c.c_float] + [_c.c_void_p] * 6),
     'pvhip_ctc_greedy_form': (_c.c_int, [_c.c_int] * 3),
     'pvhip_ctc_greedy_f32': (_c.c_int, [_c.c_void_p] + [_c.c_int] * 6 + [_c.c_void_p] * 5),
     'pvhip_dense_boxes_form': (_c.c_int, [_c.c_int] * 3),

@@ -216,3 +216,23 @@ def fp16_ir(xml_path, blob, out_dir):
     path = os.path.join(out_dir, os.path.basename(xml_path)[:-4] + '_fp16.xml')
     tree.write(path)
     return path, bytes(out)
+
+
+def paint_poses(heat, pafs, skeleton, rows, peak=lambda r, q, k: 0.9 - 0.05 * q):
+    """Paints persons onto heatmaps (n, K, H, W) and part-affinity fields (n, 2L, H, W) in place, for scripts/bench_poses.py and the tests of
+    poses=: `rows` = [[{joint: (x, y)} per person] per batch row]; joint k of person q of row r becomes the pixel `peak(r, q, k)`, and every
+    limb (a, b, cx, cy, founds) of `skeleton` whose two joints a person has leaves its unit vector in planes cx and cy, in a band three
+    pixels wide along the segment.  Returns (heat, pafs)."""
+    for r, people in enumerate(rows):
+        for q, person in enumerate(people):
+            for k, (x, y) in person.items():
+                heat[r, k, y, x] = peak(r, q, k)
+            for a, b, cx, cy, _ in skeleton:
+                if a in person and b in person and person[a] != person[b]:
+                    (ax, ay), (bx, by) = person[a], person[b]
+                    u = np.array([bx - ax, by - ay], np.float64) / np.hypot(bx - ax, by - ay)
+                    for t in np.linspace(0, 1, 4 * (abs(bx - ax) + abs(by - ay)) + 1):
+                        x, y = int(round(ax + t * (bx - ax))), int(round(ay + t * (by - ay)))
+                        ys, xs = slice(max(y - 1, 0), y + 2), slice(max(x - 1, 0), x + 2)
+                        pafs[r, cx, ys, xs], pafs[r, cy, ys, xs] = u[0], u[1]
+    return heat, pafs
