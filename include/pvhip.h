@@ -953,6 +953,53 @@ int pvhip_dense_boxes_tail_f32(const float* x, int n, int a, int c, int tail, in
                                int min_h, int min_w, int max_candidates, int overlap, float threshold, int per_label, int max_per_image,
                                void* scratch, int* header, int* rows);
 
+/* ---------------------------------------------------------------- an oriented detector head's answer ---- */
+/* Addition to ABI v19 (the version number is unchanged: nothing existing changed): the table of rotated boxes of a contiguous fp32 tensor
+ * of per-anchor (cx, cy, w, h, [objectness], c class scores, angle) -- YOLOv8 / v11-obb and the rotated anchor-free heads --, e' = 4 +
+ * objectness + c + 1 channels per anchor, the angle in radians about the centre, counter-clockwise in the image's axes (x right, y down:
+ * clockwise to the eye); layouts as pvhip_dense_boxes_f32's.  The rule (pyopenvino_amd/oriented.py states the same one in numpy and
+ * tests/oriented_ref.py in plain loops, matched bit for bit); every operation from 3. on is one binary64 operation, rounded once, never
+ * contracted:
+ *   1. winner and score  pvhip_dense_boxes_f32's 1. word for word.
+ *   2. screen  cx, cy, w, h and the angle finite and |angle| <= 8; w >= (float)min_w and h >= (float)min_h, in fp32, in network pixels;
+ *      with labels != NULL, k* listed.  selected[r] counts the anchors still in.
+ *   3. cosine and sine  a = (double)angle; k = rint(a * 0.6366197723675814); r = (a - k * 1.5707963267948966) - k *
+ *      6.123233995736766e-17; z = r * r; s = r + r * (z * S(z)), S the Horner form in z of -1/3!, +1/5!, .., +1/17!; c = 1 + z * C(z), C
+ *      that of -1/2!, +1/4!, .., +1/16!; each coefficient the correctly rounded double of the rational.  By k & 3 (two's complement):
+ *      (cos, sin) = (c, s), (-s, c), (-c, -s), (s, -c).
+ *   4. corners  u = ((w * 0.5) * cos, (w * 0.5) * sin), v = (-((h * 0.5) * sin), (h * 0.5) * cos); p0 = (ctr - u) - v, p1 = (ctr + u) - v,
+ *      p2 = (ctr + u) + v, p3 = (ctr - u) + v; area = (double)w * (double)h.
+ *   5. overlap of a later candidate i with a kept candidate j: 0 when per_label and the winners differ; 0 when dx * dx + dy * dy > R * R
+ *      for the centres' differences and R = ((wi + hi) + (wj + hj)) * 0.5; else Sutherland-Hodgman, the polygon of i (from p0 .. p3)
+ *      clipped by the edges (q_e, q_e+1) of j in order: side(p) = (bx - ax) * (py - ay) - (by - ay) * (px - ax), p inside iff side(p) >= 0;
+ *      walking the polygon's edges (p, q) in order p is emitted when inside and, when exactly one of p, q is inside, p + t * (q - p) with
+ *      t = sp / (sp - sq) behind it; at most 8 vertices are kept; an empty polygon ends it.  inter = |sum of (px * qy - qx * py)| * 0.5,
+ *      summed in order from +0.
+ *   6. suppression  the max_candidates best by descending score, ties to the lower anchor (the keys of pvhip_topk_rows_f32), greedily: i
+ *      is dropped iff an earlier kept j has inter > (double)threshold * den, den = (ai + aj) - inter (PVHIP_OVERLAP_IOU) or min(ai, aj)
+ *      (PVHIP_OVERLAP_IOS); equality keeps.  Image r keeps its first counts[r] = min(kept, max_per_image).
+ *   7. frame   each corner coordinate p goes to the frame as (float)((p - (double)d) * (double)F / (double)i), (d, i, F) as in
+ *      pvhip_dense_boxes_f32's 2.; the corners are not clamped.
+ * `header` = counts[n], selected[n], total; `rows`: PVHIP_ORIENTED_ROW_BYTES each, 16-byte aligned, twenty 32-bit words (r, k*, score
+ * bits, r * a + i, cx, cy, w, h, angle -- the anchor's own bits --, p0x, p0y, .., p3y as fp32 in frame pixels, three zero words), in
+ * (image, order of 6.) order without gaps; rows >= total are not written.  `scratch`: PVHIP_ORIENTED_SCRATCH_BYTES(n, a, max_per_image)
+ * bytes of device memory, 16-byte aligned.  Three launches on the current stream, no global-memory atomics, no workgroup waits for another,
+ * the same bits every call: (1) the score walk of pvhip_dense_boxes_f32 over this rule's anchor test (the forms are
+ * pvhip_dense_boxes_form(layout, a, 4 + objectness + c)); (2) one workgroup of 1024 lanes per image: the max_candidates largest keys,
+ * a lane per sorted candidate staging corners, area and w + h in LDS as doubles (120 KB at 1024 candidates), then suppression by pull in
+ * chunks of 64 places -- a cheap screen of (chunk) x (kept earlier) pairs, the passing pairs compacted into a worklist, the clip a pair
+ * per lane, the greedy order inside a chunk resolved on 64 bit rows --; (3) the per-image copy behind the counts.
+ * Arguments as pvhip_dense_boxes_f32's, without `box`; n * a * (5 + objectness + c) < 2^31, 1 <= max_candidates <=
+ * PVHIP_ORIENTED_MAX_CANDIDATES; else PVHIP_EINVAL and nothing is launched. */
+#define PVHIP_ORIENTED_MAX_CANDIDATES 1024
+#define PVHIP_ORIENTED_ROW_BYTES      80
+#define PVHIP_ORIENTED_SCRATCH_BYTES(n, a, max_per_image) \
+    ((((size_t)12 * (size_t)(n) * (size_t)(a) + 15u) & ~(size_t)15u) + (size_t)PVHIP_ORIENTED_ROW_BYTES * (size_t)(n) * (size_t)(max_per_image))
+int pvhip_oriented_boxes_f32(const float* x, int n, int a, int c, int layout, int objectness, float min_score, const int* labels,
+                             int num_labels, int frame_h, int frame_w, int dx, int dy, int iw, int ih, int min_h, int min_w,
+                             int max_candidates, int overlap, float threshold, int per_label, int max_per_image, void* scratch, int* header,
+                             int* rows);
+
 /* ---------------------------------------------------------------- instance masks ---- */
 /* Addition to ABI v19 (the version number is unchanged: nothing existing changed): the masks of the boxes a pvhip_dense_boxes_tail_f32
  * call has just kept, from the `tail` = T mask coefficients of their anchors and the T prototype planes of a second tensor `protos`

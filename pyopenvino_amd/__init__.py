@@ -19,10 +19,12 @@ from . import text  # noqa: F401
 from .text import Text, TextScreen  # noqa: F401
 from . import boxes  # noqa: F401
 from .boxes import BoxScreen  # noqa: F401
+from . import oriented  # noqa: F401
+from .oriented import OrientedBoxScreen, OrientedDetections  # noqa: F401
 from . import masks  # noqa: F401
 from .masks import FrameMasks, MaskScreen, Masks  # noqa: F401
 from .input_format import DetectedRois, LandmarkWarps, PerspectiveInput, RoiInput, WarpInput  # noqa: F401
 from .tiled_detections import RegionScreen, TiledScreen  # noqa: F401
 from .top_k import TopK  # noqa: F401
 
-__all__ = ['IECore', 'IENetwork', 'Executable_Network', 'RoiInput', 'WarpInput', 'PerspectiveInput', 'DetectedRois', 'LandmarkWarps', 'TopK', 'Detections', 'DetectionScreen', 'TiledScreen', 'RegionScreen', 'Gallery', 'GalleryMatch', 'Matches', 'PeakScreen', 'Keypoints', 'SegmentScreen', 'FrameSegmentScreen', 'Segments', 'MaximaScreen', 'Maxima', 'TextScreen', 'Text', 'text', 'BoxScreen', 'boxes', 'MaskScreen', 'Masks', 'FrameMasks', 'masks', 'ComponentScreen', 'Components', 'components', 'PoseScreen', 'Poses', 'poses']
+__all__ = ['OrientedBoxScreen', 'OrientedDetections', 'IECore', 'IENetwork', 'Executable_Network', 'RoiInput', 'WarpInput', 'PerspectiveInput', 'DetectedRois', 'LandmarkWarps', 'TopK', 'Detections', 'DetectionScreen', 'TiledScreen', 'RegionScreen', 'Gallery', 'GalleryMatch', 'Matches', 'PeakScreen', 'Keypoints', 'SegmentScreen', 'FrameSegmentScreen', 'Segments', 'MaximaScreen', 'Maxima', 'TextScreen', 'Text', 'text', 'BoxScreen', 'boxes', 'MaskScreen', 'Masks', 'FrameMasks', 'masks', 'ComponentScreen', 'Components', 'components', 'PoseScreen', 'Poses', 'poses']

@@ -1,16 +1,16 @@
 """Answers behind the pass: the Results a start named with ``top_k=``, ``detections=``, ``matches=``, ``keypoints=``, ``segments=``, ``maxima=``, ``text=``, ``boxes=``, ``masks=``, ``components=`` or ``poses=`` come back from
-wait() as a ``TopK``, a ``Detections``, a ``Matches``, a ``Keypoints``, a ``Segments``, a ``Maxima``, a ``Text``, (a dense head's) a ``Detections`` or (its prototype Result's) a ``Masks`` or ``FrameMasks`` a ``Components`` or a ``Poses`` made on the device instead of as the tensor.  One ``Answers`` per
+wait() as a ``TopK``, a ``Detections``, a ``Matches``, a ``Keypoints``, a ``Segments``, a ``Maxima``, a ``Text``, (a dense head's) a ``Detections``, (an oriented head's) an ``OrientedDetections`` or (its prototype Result's) a ``Masks`` or ``FrameMasks`` a ``Components`` or a ``Poses`` made on the device instead of as the tensor.  One ``Answers`` per
 Executable_Network (one per request), as ``HostInputs`` is on the way in: the request checks the arguments, binds the asks to the staged
 inputs, launches behind the pass and reads after it.
 
 An ask is one Result's question in its resolved form, an ``ask.Ask`` (ask.py states the protocol: KEYWORD, `bound`, `key`, `launch`,
-`on_host`): top_k.Ask, detections.Ask / FittedAsk, tiled_detections.Ask / RegionAsk, gallery.Ask, keypoints.Ask, segments.Ask / FrameAsk, maxima.Ask, text.Ask, boxes.Ask, masks.Ask, components.Ask or poses.Ask.  Which kind it is
+`on_host`): top_k.Ask, detections.Ask / FittedAsk, tiled_detections.Ask / RegionAsk, gallery.Ask, keypoints.Ask, segments.Ask / FrameAsk, maxima.Ask, text.Ask, boxes.Ask, oriented.Ask, masks.Ask, components.Ask or poses.Ask.  Which kind it is
 matters only where checked() makes it; the rule of each kind, its argument's forms and its refusals are stated in its module.  A plain
 screen over a detector whose input declares a fit (preprocess_info.resize_fit) learns its geometry in bound(), from the extent of the
 frames the pass was fed, and so does a BoxScreen over such an input."""
 import numpy as np
 
-from . import boxes as boxes_rule, components as components_rule, detections as detections_rule, device, gallery as gallery_rule, keypoints as keypoints_rule, masks as masks_rule, maxima as maxima_rule, poses as poses_rule, segments as segments_rule, \
+from . import boxes as boxes_rule, components as components_rule, detections as detections_rule, device, gallery as gallery_rule, keypoints as keypoints_rule, masks as masks_rule, maxima as maxima_rule, oriented as oriented_rule, poses as poses_rule, segments as segments_rule, \
     text as text_rule, tiled_detections as tiled_rule, top_k as top_k_rule
 from .input_format import FrameFeed
 
@@ -115,7 +115,7 @@ class Answers:
             for name, screen in read.items():
                 asks[name] = text_rule.Ask(screen)
         if boxes is not None:
-            heads = boxes_rule.checked(ienet, boxes, sharded)
+            heads = oriented_rule.checked(ienet, boxes, sharded)     # (the screen's type picks the kind: a BoxScreen or an OrientedBoxScreen)
             if asks:
                 _no_clash('boxes', heads, asks)
             formats = ex.host_inputs.formats
@@ -125,8 +125,12 @@ class Answers:
                 if fitted and isinstance(inputs, dict) and isinstance(inputs.get(screen.input), FrameFeed):     # (detections=' refusal: a geometry per row)
                     raise ValueError('boxes: input {!r} declares resize_fit {} and is fed a {}: every row has a geometry of its own'.format(
                         screen.input, fmt.fit, type(inputs[screen.input]).__name__))
-                asks[name] = boxes_rule.Ask(screen, boxes_rule.extent_of(ienet, screen.input), fmt if fitted else None, None, None)
+                kind = oriented_rule.Ask if isinstance(screen, oriented_rule.OrientedBoxScreen) else boxes_rule.Ask
+                asks[name] = kind(screen, boxes_rule.extent_of(ienet, screen.input), fmt if fitted else None, None, None)
         if masks is not None:
+            for name, a in asks.items():        # (masks= reads the rectangles of a BoxScreen's table)
+                if isinstance(a, oriented_rule.Ask):
+                    raise ValueError('boxes: Result {!r} is asked for with an OrientedBoxScreen: masks= takes the boxes of a BoxScreen'.format(name))
             heads = {name: a.screen for name, a in asks.items() if isinstance(a, boxes_rule.Ask)}
             planes = masks_rule.checked(ienet, masks, heads, sharded)
             _no_clash('masks', planes, asks)

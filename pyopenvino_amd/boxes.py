@@ -31,7 +31,7 @@ channel values e[0 .. E - 1]:
 Where this differs from Ultralytics' post-processing: suppression runs on the integer frame rectangles, not on float network boxes; an
 anchor has one class, its best, and never yields several candidates (no multi_label); class-aware suppression is by equality of the labels,
 not by offsetting the coordinates per class.  Out of scope: several Results of one detector merged (v3 / v4 per-scale grids with anchors
-and sigmoid / exp decoding, RegionYolo), multi-label candidates, normalised box units, rotated boxes, keypoint channels (mask
+and sigmoid / exp decoding, RegionYolo), multi-label candidates, normalised box units, rotated boxes (oriented.py: an OrientedBoxScreen under the same keyword), keypoint channels (mask
 coefficients ride in `tail`, which this rule steps over: masks.py), FP16 Results, K above 4096, merging across tiles or regions, a RoiInput feed on a fitted input."""
 import collections
 import ctypes

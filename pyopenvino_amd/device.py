@@ -210,6 +210,8 @@ SIGNATURES = {
                               [_c.c_void_p] * 3),
     'pvhip_dense_boxes_tail_f32': (_c.c_int, [_c.c_void_p] + [_c.c_int] * 7 + [_c.c_float, _c.c_void_p] + [_c.c_int] * 11 + [_c.c_float] + [_c.c_int] * 2 +
                                    [_c.c_void_p] * 3),
+    'pvhip_oriented_boxes_f32': (_c.c_int, [_c.c_void_p] + [_c.c_int] * 5 + [_c.c_float, _c.c_void_p] + [_c.c_int] * 11 + [_c.c_float] + [_c.c_int] * 2 +
+                                 [_c.c_void_p] * 3),
     'pvhip_instance_masks_f32': (_c.c_int, [_c.c_void_p] + [_c.c_int] * 7 + [_c.c_void_p] + [_c.c_int] * 6 + [_c.c_void_p] * 3),
     'pvhip_segment_frame_labels_form': (_c.c_int, [_c.c_int] * 11),
     'pvhip_segment_frame_labels_f32': (_c.c_int, [_c.c_void_p] + [_c.c_int] * 13 + [_c.c_float] + [_c.c_void_p] * 3),
